@@ -14,7 +14,15 @@ src/renderer/tiled.rs:294 -> 536); the film stays in HBM.  After the last step t
 with one RCCL reduce (disjoint shards, so the sum is a gather) inside the timed region.
 
 Prints ONE JSON line on rank 0 with `roofline` (HIP-event time of the dominant kernel, measured inside the timed
-region by the engine) and `cpu_baseline` (the oracle on the host cores, bounded sample).
+region by the engine).  A plain run sets up, warms up, times the steps and prints that line, nothing more.  `--full` adds what
+takes runs of its own: `cpu_baseline` (the oracle on the host cores, bounded sample), `parity` (a smoke-size render of the
+engine against the oracle) and, with N > 1, the `strong` legs below; without it those fields are null.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step, after the clocks, as float32 / float64 .npy files (rank 0):
+film_last_step.npy (the (H, W, 4) XYZ film of that step's render, this rank's shard), film_total.npy (the film summed over the warm-up
+and timed steps, reduced over the ranks) and counters_last_step.npy (that step's ray and stage counters).  A film larger than 20 MiB is
+written as a fixed sample of its pixels (seed 0) with film_pixel_index.npy beside it.  The seeds are fixed: the same arguments give the
+same inputs, so two builds can be compared output for output.
 
 `--gpus N` is what runs.  Under a launcher (WORLD_SIZE set) it must equal WORLD_SIZE or the run stops with exit code 2.  Without one and
 N > 1, this process — which makes no GPU call and does not import torch — starts the N ranks as fresh child processes
@@ -23,7 +31,7 @@ N > 1, this process — which makes no GPU call and does not import torch — st
 record whose `n_gpus` / `ranks_seen` is not N is an error (exit code 4), as is a rank without a GPU of its own (`--allow-shared-gpus`
 lets ranks share a device: the one-GPU tests).  For N > 1 the record also carries `strong`: the fixed BASELINE frames (C2: Cornell
 1024 x 1024 x 1024 spp; C4: hdri_test 1024 x 1024 x 2048 spp, L = 6) dealt over the N ranks, one RCCL reduce each, with ms per frame,
-Msamples/s, the reduce's share and the set-up time (`--strong-legs` adds them to a one-GPU run too).
+Msamples/s, the reduce's share and the set-up time (with `--full`; `--strong-legs` adds them to any run, one GPU included).
 """
 import argparse
 import importlib
@@ -81,6 +89,27 @@ def algorithmic_bytes(stage, light_samples):
     if stage == "shadow":
         return (3 + 7 * light_samples) * 4 + 8   # read item, read-modify-write the slot energy
     return 16 * 2                                 # accumulate: film pixel read-modify-write (energy reads are per sample, added below)
+
+
+FILM_DUMP_BYTES = 20 << 20   # per film written by --dump-outputs: two films and the pixel index of a sampled one stay under 64 MB
+
+
+def dump_outputs(out_dir, film_step, film_total, prof):
+    """--dump-outputs: the last timed step's film and counters, and the summed film, as .npy.  A film above FILM_DUMP_BYTES is written as
+    the same fixed sample of its pixels (seed 0), (k, 4) rows in pixel order, with their row-major pixel indices in film_pixel_index.npy.
+    counters_last_step.npy: camera, bounce, shadow and light rays, environment hits, then the 8 stage item counts of the engine's profile."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    films = {"film_last_step": film_step.cpu().numpy(), "film_total": film_total.cpu().numpy()}
+    h, w, c = films["film_last_step"].shape
+    if h * w * c * 4 > FILM_DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(h * w, FILM_DUMP_BYTES // (c * 4), replace=False))
+        films = {k: v.reshape(h * w, c)[idx] for k, v in films.items()}
+        np.save(os.path.join(out_dir, "film_pixel_index.npy"), idx.astype(np.float64))
+    for k, v in films.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+    counters = [prof.camera_rays, prof.bounce_rays, prof.shadow_rays, prof.light_rays, prof.env_hits] + list(prof.stage_items)
+    np.save(os.path.join(out_dir, "counters_last_step.npy"), np.array(counters, dtype=np.float64))
 
 
 RECORD_MARK = "PT_BENCH_RECORD "   # in front of rank 0's record when a bench.py parent launched the ranks (PT_BENCH_PARENT): the parent relays exactly that line
@@ -164,7 +193,7 @@ def main():
     ap.add_argument("--hero", type=int, default=1, help="wavelengths per path: 1, or 4 for the hero-wavelength variant (C5)")
     ap.add_argument("--medium-aware", action="store_true", help="the medium-aware walk (RenderSettings of the reference's PT integrator with mediums: src/integrator/utils.rs:708-1103; scene fog_ball)")
     ap.add_argument("--workload", default=None, help="label for config.workload (default: derived from the arguments)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the oracle baseline (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the oracle baseline, with --full (0 = skip it and the parity render)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: every GPU renders 1/N of the pixels at N x --spp-per-step (per-GPU work fixed); strong: the frame is fixed at --spp-per-step, its tiles dealt over the N GPUs")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (nccl = RCCL) even for one process, so that the film reduce runs through RCCL")
@@ -174,12 +203,16 @@ def main():
     ap.add_argument("--no-strong-legs", action="store_true", help="skip them")
     ap.add_argument("--strong-frames", type=int, default=3, help="timed frames per strong-scaling leg (after one warm-up frame)")
     ap.add_argument("--strong-spp-div", type=int, default=1, help="divide the legs' samples per pixel (C2 1024, C4 2048) by this: tests")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the CPU baseline, the parity render against the oracle and, with N > 1, the strong legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     # ---- how many GPUs: --gpus is what runs.  No launcher and N > 1: be the launcher.  A launcher that disagrees: stop.
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args, sys.argv[1:]))
     if env_world is not None and int(env_world) != args.gpus:
@@ -269,6 +302,8 @@ def main():
     sharding.reduce_film(film_total, dst=0)                      # RCCL over xGMI: the only exchange step
     sync()
     elapsed = sharding.max_over_ranks(time.perf_counter() - t0, "cuda")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, film_step, film_total, profs[-1])
 
     # ---- the fixed BASELINE frames dealt over the N ranks (strong scaling): after the timed region of `value`, with their own clocks
     def strong_leg(name, leg_scene, create_ms, spp, max_bounces, min_bounces, light_samples, hero):
@@ -333,7 +368,7 @@ def main():
                 "film_bytes_reduced": W * H * 16, "setup_ms": create_ms + first_ms, "setup": {"scene_create_ms": create_ms, "first_frame_ms": first_ms}}
 
     strong = None
-    if (world > 1 or args.strong_legs) and not args.no_strong_legs:
+    if ((world > 1 and args.full) or args.strong_legs) and not args.no_strong_legs:
         div = max(1, args.strong_spp_div)
         c2_scene, c2_ms = (scene, scene_create_ms)
         if args.scene != "cornell_box":
@@ -463,7 +498,7 @@ def main():
 
         # ---- CPU baseline: the oracle on the host cores, bounded sample of the same workload
         cpu = None
-        if args.cpu_seconds > 0:
+        if args.full and args.cpu_seconds > 0:
             import oracle_loader
             oracle = oracle_loader.load(pkg)
             oscene = oracle.create_scene(builder)
@@ -493,7 +528,7 @@ def main():
         # ---- the checker next to the number: a smoke-size render of this scene, engine against oracle at the same seed, under the bars the
         # parity tests use (tests/parity_suite.py: L-inf < 1e-4 flat; a pixel whose own 8 ulp exceed that — values above ~128 — gets those)
         parity = None
-        if args.cpu_seconds > 0:
+        if args.full and args.cpu_seconds > 0:
             rd = pkg.api.render_desc(64, 64, 4, args.max_bounces, min_bounces=args.min_bounces, light_samples=L, seed=1, hero_wavelengths=args.hero, medium_aware=args.medium_aware)
             gfilm, gprof = scene.render(rd)
             ofilm, oprof = oscene.render(rd)

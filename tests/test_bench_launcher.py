@@ -94,3 +94,33 @@ def test_real_launcher_starts_n_ranks(tmp_path):
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "1", "--warmup", "0", "--cpu-seconds", "0"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode != 0 and r.stdout.strip() == ""
     assert r.stderr.count("bench.py needs a GPU") >= 2, r.stderr[-3000:]
+
+
+def test_dump_outputs_writes_the_films_and_counters(tmp_path, monkeypatch):
+    """--dump-outputs (CPU tier, CPU tensors in place of the device films): float32 films and float64 counters; a film above the size cap is written as
+    the same fixed, seeded sample of pixels for both films, rows in pixel order, with its pixel indices beside it."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Prof:
+        camera_rays, bounce_rays, shadow_rays, light_rays, env_hits = 4096, 9000, 7000, 0, 12
+        stage_items = list(range(1, 9))
+    step = torch.arange(32 * 32 * 4, dtype=torch.float32).reshape(32, 32, 4)
+    total = 2 * step
+    bench.dump_outputs(str(tmp_path / "whole"), step, total, Prof())
+    got = {f[:-4]: np.load(tmp_path / "whole" / f) for f in os.listdir(tmp_path / "whole")}
+    assert sorted(got) == ["counters_last_step", "film_last_step", "film_total"]
+    assert got["film_last_step"].dtype == np.float32 and np.array_equal(got["film_last_step"], step.numpy()) and np.array_equal(got["film_total"], total.numpy())
+    assert got["counters_last_step"].dtype == np.float64 and got["counters_last_step"].tolist() == [4096, 9000, 7000, 0, 12] + list(range(1, 9))
+    monkeypatch.setattr(bench, "FILM_DUMP_BYTES", 100 * 16)   # 100 of the 1024 pixels
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), step, total, Prof())
+    idx = np.load(tmp_path / "a" / "film_pixel_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 100 and (np.diff(idx) > 0).all() and np.array_equal(idx, np.load(tmp_path / "b" / "film_pixel_index.npy"))
+    rows = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "film_last_step.npy"), step.numpy().reshape(-1, 4)[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "film_total.npy"), total.numpy().reshape(-1, 4)[rows])

@@ -645,7 +645,7 @@ def test_bench_line_contract(pkg):
     import sys
     root = pkg.REPO_ROOT
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--width", "128", "--height", "128",
-                        "--spp-per-step", "20", "--cpu-seconds", "0.5"], capture_output=True, text=True, cwd=root, timeout=600)
+                        "--spp-per-step", "20", "--cpu-seconds", "0.5", "--full"], capture_output=True, text=True, cwd=root, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().split("\n") if l.strip()]
     assert len(lines) == 1
@@ -661,6 +661,34 @@ def test_bench_line_contract(pkg):
     assert "traffic" in rf and rf["kernel"].startswith("k_")
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "Msamples/s" and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb
+
+
+def test_bench_plain_run_and_its_outputs(pkg, tmp_path):
+    """A plain run (no --full) times its steps and prints the same headline record without the CPU baseline, the parity render or the strong legs;
+    --dump-outputs writes the last timed step's film and counters and the summed film, and a second run with the same arguments writes the same bits."""
+    import json
+    import subprocess
+    import sys
+    root = pkg.REPO_ROOT
+    recs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "96", "--height", "64",
+                            "--spp-per-step", "8", "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, cwd=root, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.strip().split("\n") if l.strip()]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+    d = recs[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and abs(d["value"] - 96 * 64 * 8 / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 1e-6
+    assert d["cpu_baseline"] is None and d["parity"] is None and d["strong"] is None and d["roofline"]["kernel"].startswith("k_")
+    out = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(out) == ["counters_last_step", "film_last_step", "film_total"]
+    assert out["film_last_step"].shape == (64, 96, 4) and out["film_last_step"].dtype == np.float32 and out["film_total"].dtype == np.float32
+    assert out["counters_last_step"].dtype == np.float64 and out["counters_last_step"][0] == 96 * 64 * 8
+    assert np.isfinite(out["film_total"][..., :3]).all() and out["film_total"][..., :3].max() >= out["film_last_step"][..., :3].max() > 0
+    for name, a in out.items():
+        assert np.array_equal(a.view(np.uint8), np.load(tmp_path / "b" / (name + ".npy")).view(np.uint8)), name
 
 
 @pytest.mark.parametrize("case", ["many_analytic", "many_analytic_no_disk", "many_analytic_300"])

@@ -178,7 +178,7 @@ def test_bench_gpus_n_launches_n_ranks(tmp_path, n):
         env.pop(k, None)
     import time
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--width", "256", "--height", "256", "--spp-per-step", "16",
-           "--cpu-seconds", "0", "--backend", "gloo", "--strong-spp-div", "64", "--strong-frames", "2"]
+           "--cpu-seconds", "0", "--backend", "gloo", "--strong-spp-div", "64", "--strong-frames", "2", "--full"]
     import torch
     if torch.cuda.device_count() < n:
         if n == 2:

@@ -1,5 +1,6 @@
-"""CPU tier, this container only: the data fixtures and the config / scene files the REFERENCE tree itself holds, read in place from
-/root/reference (never copied, never shipped: the whole module is skipped where that tree is absent, i.e. on the GPU box).
+"""CPU tier: the data fixtures and the config / scene files the REFERENCE tree itself holds, read from their byte-for-byte copies under
+tests/golden/reference_tree (data files only, never its sources; tools/make_reference_fixtures.py writes them from a checkout of that tree),
+and the pixels of its two showcase renders that the last two tests read (tests/golden/reference_showcase.npz).
 
 SURVEY 8(c) names data/test/{cornell.csv, gold.csv, xenon_lamp.spectra, test.png, test.bmp} — the inputs of the reference's own parse
 tests (src/parsing/curves.rs:411-477, src/parsing/texture.rs:302-335).  Those tests only print; what can be pinned here is that the C++
@@ -16,9 +17,9 @@ import zlib
 import numpy as np
 import pytest
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "data", "test")), reason="the reference tree is not on this machine")
 HERE = os.path.dirname(os.path.abspath(__file__))
+REF = os.path.join(HERE, "golden", "reference_tree")
+SHOWCASE = os.path.join(HERE, "golden", "reference_showcase.npz")
 PTCLI = os.path.join(HERE, "..", "rust-pathtracer_amd", "csrc", "ptcli")
 
 
@@ -154,7 +155,7 @@ def test_reference_image_fixtures(sfmod):
     assert 0.0 < float(got.mean()) < 1.0 and float(got.max()) <= 1.0
 
 
-# What each of the reference's own config files does when handed to ptcli --dry-run with --root /root/reference, and why that is what
+# What each of the reference's own config files does when handed to ptcli --dry-run with --root at (the copy of) the reference tree, and why that is what
 # the reference would do with its own tree (it ships neither OBJ meshes other than the four gems / monkey / prism, nor any HDRI).
 CONFIGS = {
     "config.toml": "could not find obj file or mtl file data/meshes/cornell_box.obj",                      # parsing/meshes.rs: the OBJ is not in the tree
@@ -229,9 +230,9 @@ def test_reference_scenes_that_load_render_on_the_oracle(sfmod, oracle, pkg, nam
 
 @pytest.mark.parametrize("name", sorted(SCENES_THAT_LOAD))
 def test_reference_scene_builders_are_the_reference_scene_files(sfmod, oracle, pkg, name):
-    """The GPU tier renders the reference tree's self-contained scenes from scene builders (pkg.scene.REFERENCE_TREE_SCENES — /root/reference does not
-    exist on the GPU box).  Here, where it does: the reference's OWN scene file through the C++ front end and the builder give the oracle the same
-    film bit for bit and the same counters — the builders are those scenes, value for value."""
+    """The GPU tier renders the reference tree's self-contained scenes from scene builders (pkg.scene.REFERENCE_TREE_SCENES).  Here: the reference's
+    OWN scene file (its copy under tests/golden) through the C++ front end and the builder give the oracle the same film bit for bit and the same
+    counters — the builders are those scenes, value for value."""
     builders = dict(pkg.scene.REFERENCE_TREE_SCENES, white_furnace=pkg.scene.white_furnace)
     assert sorted(builders) == sorted(SCENES_THAT_LOAD)
     config = sfmod.Config(os.path.join(os.path.dirname(pkg.__file__), "data", "config_cornell_c1.toml"))
@@ -250,6 +251,25 @@ def test_reference_scene_builders_are_the_reference_scene_files(sfmod, oracle, p
     assert (prof_f.camera_rays, prof_f.bounce_rays, prof_f.shadow_rays, prof_f.env_hits) == (prof_b.camera_rays, prof_b.bounce_rays, prof_b.shadow_rays, prof_b.env_hits)
 
 
+# Cornell showcase patches: centres as fractions of the (square) image, tolerance on (r, g) chromaticity; each is the mean of a window of
+# +-0.03 of the image around its centre
+CORNELL_PATCHES = {"back wall": (0.5, 0.35, 0.05), "right wall (red)": (0.93, 0.5, 0.05), "left wall (green)": (0.08, 0.5, 0.10), "floor": (0.75, 0.95, 0.06),
+                   "ceiling": (0.3, 0.04, 0.05), "tall block front": (0.33, 0.62, 0.06), "short block top": (0.62, 0.70, 0.07)}
+
+
+def _patch_window(shape, cx, cy, r=0.03):
+    h, w = shape[:2]
+    return slice(int((cy - r) * h), int((cy + r) * h)), slice(int((cx - r) * w), int((cx + r) * w))
+
+
+def _block_statistics(show, f=5):
+    """The moissanite test's view of an sRGB image in [0, 1]: linearised, per f x f block the mean colour, the mean luminance and its spread."""
+    N = show.shape[0] // f
+    lin = np.where(show <= 0.04045, show / 12.92, ((show + 0.055) / 1.055) ** 2.4)
+    Y = 0.2126 * lin[..., 0] + 0.7152 * lin[..., 1] + 0.0722 * lin[..., 2]
+    return {"rgb": lin.reshape(N, f, N, f, 3).mean(axis=(1, 3)), "Ymean": Y.reshape(N, f, N, f).mean(axis=(1, 3)), "Yspread": Y.reshape(N, f, N, f).std(axis=(1, 3))}
+
+
 def test_showcase_cornell_box_chromaticities(oracle, pkg):
     """A loose STATISTICAL pin of the oracle against the only pixels in the tree that the reference itself produced:
     showcase/cornell_box_1080p.png.  Its render settings are unknown (exposure, tone mapper, sample count, the author's own cornell_box.obj),
@@ -260,8 +280,8 @@ def test_showcase_cornell_box_chromaticities(oracle, pkg):
     unit, matrix, curve table or wall assignment; it does NOT decide between the close alternatives of profiles/r3_oracle_sensitivity.md
     (those move chromaticities by < 0.01).  Parity stays unpinned."""
     import oracle_loader
-    show = _decode_png(os.path.join(REF, "showcase", "cornell_box_1080p.png"))[..., :3].astype(np.float64) / 255.0
-    assert show.shape[:2] == (1080, 1080)
+    stored = np.load(SHOWCASE)                                # the showcase's 8-bit pixels inside each patch window
+    assert tuple(stored["cornell shape"][:2]) == (1080, 1080)
     sc = oracle.create_scene(pkg.scene.cornell_box())
     film, _ = oracle_loader.render_mt(oracle, sc, pkg.api.render_desc(120, 120, 48, 8, seed=3), os.cpu_count() or 4)
     rgba, _ = oracle.output_film(film, tonemap=pkg.api.TONEMAP_CLAMP, exposure=3.0)   # (bright enough for the 8-bit quantisation not to matter)
@@ -270,15 +290,17 @@ def test_showcase_cornell_box_chromaticities(oracle, pkg):
     def lin(c):
         return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4)
 
-    def chroma(img, cx, cy, r=0.03):
-        h, w, _ = img.shape
-        p = lin(img[int((cy - r) * h):int((cy + r) * h), int((cx - r) * w):int((cx + r) * w)].reshape(-1, 3).mean(0))
+    def chroma(img, cx, cy):
+        return chroma_of(img[_patch_window(img.shape, cx, cy)])
+
+    def chroma_of(patch):
+        p = lin(patch.reshape(-1, 3).mean(0))
         return p[0] / p.sum(), p[1] / p.sum()
-    # patch centres as fractions of the (square) image; tolerance on (r, g) chromaticity
-    patches = {"back wall": (0.5, 0.35, 0.05), "right wall (red)": (0.93, 0.5, 0.05), "left wall (green)": (0.08, 0.5, 0.10), "floor": (0.75, 0.95, 0.06),
-               "ceiling": (0.3, 0.04, 0.05), "tall block front": (0.33, 0.62, 0.06), "short block top": (0.62, 0.70, 0.07)}
-    for name, (cx, cy, tol) in patches.items():
-        a, b = chroma(show, cx, cy), chroma(ours, cx, cy)
+    for name, (cx, cy, tol) in CORNELL_PATCHES.items():
+        show = stored["cornell " + name].astype(np.float64) / 255.0
+        wy, wx = _patch_window((1080, 1080), cx, cy)
+        assert show.shape == (wy.stop - wy.start, wx.stop - wx.start, 3), name
+        a, b = chroma_of(show), chroma(ours, cx, cy)
         assert abs(a[0] - b[0]) <= tol and abs(a[1] - b[1]) <= tol, (name, a, b)
     # the layout itself: green on the left, red on the right, a warm white in between (as the showcase has it)
     gl, rr, bw = chroma(ours, 0.08, 0.5), chroma(ours, 0.93, 0.5), chroma(ours, 0.5, 0.35)
@@ -300,13 +322,11 @@ def test_showcase_moissanite_gem_layout(oracle, pkg):
         culet on the image row 0.815 the showcase shows — it does: the image predates that edit of the file.  Mesh scale 0.5, the 302-triangle
         brilliant_diamond.obj, transform order and the thin-lens camera are what fit.
     Loose and geometric; parity stays unpinned."""
-    show = _decode_png(os.path.join(REF, "showcase", "moissanite_gem_1080p.png"))[..., :3].astype(np.float64) / 255.0
-    assert show.shape[:2] == (1080, 1080)
-    lin = np.where(show <= 0.04045, show / 12.92, ((show + 0.055) / 1.055) ** 2.4)
-    N, f = 216, 5
-    rgb = lin.reshape(N, f, N, f, 3).mean(axis=(1, 3))
-    Y = 0.2126 * lin[..., 0] + 0.7152 * lin[..., 1] + 0.0722 * lin[..., 2]
-    Ymean, Yspread = Y.reshape(N, f, N, f).mean(axis=(1, 3)), Y.reshape(N, f, N, f).std(axis=(1, 3))
+    stored = np.load(SHOWCASE)                                # _block_statistics of the showcase image, 5 x 5 blocks
+    assert tuple(stored["moissanite shape"][:2]) == (1080, 1080)
+    N = 216
+    rgb, Ymean, Yspread = (stored["moissanite " + k].astype(np.float64) for k in ("rgb", "Ymean", "Yspread"))
+    assert rgb.shape == (N, N, 3) and Ymean.shape == Yspread.shape == (N, N)
 
     def id_buffer(gem_z):
         sc = oracle.create_scene(pkg.scene.cornell_gem(gem_z=gem_z))

@@ -222,6 +222,8 @@ class Library:
         self._bsdf_eval = bind("bsdf_eval", C.c_int32, [vp, u32, sz, fpp, fpp, fpp, fpp, fpp])
         self._emission = bind("emission", C.c_int32, [vp, u32, sz, fpp, fpp, fpp])
         self._curve_eval = bind("curve_eval", C.c_int32, [vp, u32, sz, fpp, fpp])
+        # include/pt_debug.h (not the oracle's boundary: the reference cannot sample an emissive mesh face)
+        self._light_sample = bind("light_sample", C.c_int32, [vp, u32, sz, fpp, fpp, fpp, fpp], required=False)
         self._device_info = bind("device_info", C.c_char_p, [], required=False)
         self._output_film = bind("output_film", C.c_int32, [C.POINTER(OutputDesc), fpp, C.POINTER(C.c_uint8), fpp], required=False)
         self._write_png = bind("write_png", C.c_int32, [C.c_char_p, u32, u32, C.POINTER(C.c_uint8), C.c_int32], required=False)
@@ -361,6 +363,17 @@ class Scene:
         f = np.zeros(n, np.float32); wo = np.zeros((n, 3), np.float32); pdf = np.zeros(n, np.float32)
         self.library.check(self.library._bsdf_sample(self.handle, material, n, _fp(lam), _fp(wi), _fp(s2), _fp(f), _fp(wo), _fp(pdf)))
         return f, wo, pdf
+
+    def light_sample(self, entry, origins, s2):
+        """Hittable::sample of light-list entry `entry` from the points `origins` (n, 3) with samples `s2` (n, 2): world directions (n, 3) and solid-angle pdfs (n,)."""
+        if self.library._light_sample is None:
+            raise NotImplementedError("%s has no light_sample entry" % self.library.path)
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        s2 = np.ascontiguousarray(s2, dtype=np.float32).reshape(-1, 2)
+        n = o.shape[0]
+        d = np.zeros((n, 3), np.float32); pdf = np.zeros(n, np.float32)
+        self.library.check(self.library._light_sample(self.handle, entry, n, _fp(o), _fp(s2), _fp(d), _fp(pdf)))
+        return d, pdf
 
     def bsdf_eval(self, material, lam, wi, wo):
         lam = np.ascontiguousarray(lam, dtype=np.float32)

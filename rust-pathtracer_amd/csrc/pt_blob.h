@@ -237,6 +237,11 @@
                                           inward-safe face inward) — the parked closest-hit kernel ends that body's sweep at the first triangle accepted well inside itself (mesh_walk) */
 #define PT_HDR_CORE_WORDS 61        /* words of the core section; the mesh-data section follows it */
 #define PT_HDR_SWEEP_MESH_MASK 57  /* 2 words: the bits that stand for mesh instances (no primitive of their own) */
+#define PT_HDR_LIGHT_FACE_OFF 71   /* (emissive mesh faces) per light-list entry one word: the triangle word offset (mesh-data section) of the face the entry
+                                     stands for — the j-th entry of a mesh instance's run is its mesh's j-th emissive face; 0 for an analytic light.  Header word 0:
+                                     no entry is a mesh face, and the list is not there.  A_f, the face's area (Heron, object space, mesh.rs:200-210), rides in the spare
+                                     fourth word of the face's normal record: the face-normal record without vertex normals, the first vertex normal's with them (0 on
+                                     every face that is no light) — hit_record hands it on for a light-tagged hit in Hit::u, which mesh hits leave 0 otherwise. */
 #define PT_HDR_SWEEP_OWNER_MASK 62 /* 2 words: the bits whose primitive test needs the ray itself (analytic shapes, triangles of transformed
                                       instances); the other bits are triangles tested with the world ray's shear constants (pooled phase 3) */
 

@@ -158,6 +158,8 @@ struct SceneView {
 #define PT_SCENE_NO_CERTS 4u  /* no instance carries a convex-body certificate (PT_FLAG_CONVEX clear): the certificate code of hit_record and stage_shade is compiled out.  Every
                                  vertex-kernel form has this bit but the two made for such scenes (k_shade NO_ENV / FULL "with certificates", pt_kern_shade.hip) — measured: with the
                                  code present behind scalar branches the fused and lean forms still lost 2 % (registers, layout: profiles/r6h_ab_r5b.txt) */
+#define PT_SCENE_NO_MESH_LIGHTS 8u /* no light-list entry is an emissive mesh face (PT_HDR_LIGHT_FACE_OFF = 0): the face's sampler, its pdf and its area in the hit record are
+                                      compiled out.  Every kernel form carries this bit but the few the engine gives a scene with emissive faces (pt_kern_*.hip) */
 PT_HD uint32_t bu(const SceneView& s, uint32_t off) { return s.w[off]; }
 #if defined(__HIP_DEVICE_COMPILE__)
 PT_HD bool scene_has_certificates(const SceneView& s) { return !(s.lacks & PT_SCENE_NO_CERTS) && s.certs != 0u; }
@@ -741,6 +743,7 @@ PT_HD void hit_record(const SceneView& s, F3 o, F3 d, uint32_t best_inst, uint32
     instance_local_ray(s, inst, o, d, &lo, &ld);
     Hit h;
     uint32_t in_safe = 0u;   // PT_HIT_IN_SAFE and the outward threshold of the face (pt_blob.h PT_TRI_FLAGS), handed to the vertex code in the instance word
+    float area = 0.0f;       // the face's A_f (the spare word of its normal record, pt_blob.h PT_HDR_LIGHT_FACE_OFF): 0 unless it is an emissive face
     if (triw != 0u) {
         uint32_t mesh = bu(s, inst + PT_INST_MESH);
         uint32_t normal_off = bu(s, mesh + PT_MESH_NORMAL_OFF);
@@ -757,10 +760,12 @@ PT_HD void hit_record(const SceneView& s, F3 o, F3 d, uint32_t best_inst, uint32
             F4 m0 = mf4(s, nn), m1 = mf4(s, nn + 4), m2 = mf4(s, nn + 8);
             F3 n = add(add(mul(f3(m0.x, m0.y, m0.z), bh.b0), mul(f3(m1.x, m1.y, m1.z), bh.b1)), mul(f3(m2.x, m2.y, m2.z), bh.b2));
             h.n = normalize(n);
+            area = m0.w;
         } else {
             // the face normal, normalize(normalize(cross(p0 - p2, p1 - p2))), as the host computed it with these same functions (pt_scene_host.cpp)
             const F4 fn = mf4(s, pt_f2u(q1.w));
             h.n = f3(fn.x, fn.y, fn.z);
+            area = fn.w;
         }
         h.t = bh.t;
         h.p = add(add(mul(p0, bh.b0), mul(p1, bh.b1)), mul(p2, bh.b2));
@@ -776,6 +781,9 @@ PT_HD void hit_record(const SceneView& s, F3 o, F3 d, uint32_t best_inst, uint32
     h.instance = best_inst | in_safe;
     uint32_t m = bu(s, inst + PT_INST_MATERIAL);
     if (m != PT_MATERIAL_NONE) h.material = m;
+    // A light-tagged hit on a mesh face carries the face's area in u (a mesh hit's u is 0, and no light material reads a texture): the BSDF-hit MIS weight at such a
+    // vertex needs 1 / A_f (light_psa_pdf), and the hit queue has no word for the face.  Compiled out of every form of a scene without emissive faces.
+    if (!(s.lacks & PT_SCENE_NO_MESH_LIGHTS) && triw != 0u && PT_MATERIAL_TAG(h.material) == PT_TAG_LIGHT) h.u = area;
     h.valid = true;
     *out = h;
 }
@@ -2131,9 +2139,23 @@ PT_HD bool world_hit(const SceneView& s, F3 o, F3 d, Hit* out, float bound = PT_
 
 // One light's own shape test on a world ray against the unbounded interval: what nearest_light_hit runs per light whose box passes, and what the lean
 // vertex kernel runs on a light-sample ray of a scene with one light (stage_shade) — ONE helper, so the two cannot drift apart (round-4 advisor).
-PT_HD bool light_shape_hit(const SceneView& s, uint32_t inst, F3 o, F3 d, Hit* h) {
+// `entry`: the light-list entry; for a mesh instance it names the ONE emissive face the entry stands for, whose watertight test runs in instance space with
+// the walk's own arithmetic (triangle_test on instance_local_ray's ray, as mesh_walk): the same t, so the search bound is the walk's distance to that face.
+// Every emissive face has an entry of its own — a test over all entries is a test over every emissive surface.  (Only h->t and h->valid are set then:
+// the callers read nothing else.  A mesh instance named as sweep_run's known light changes nothing there: phase 3 takes the known distance for analytic
+// leaves only, and tests a triangle again, with this same arithmetic.)
+PT_HD bool light_shape_hit(const SceneView& s, uint32_t inst, uint32_t entry, F3 o, F3 d, Hit* h) {
     F3 l0, l1;
     instance_local_ray(s, inst, o, d, &l0, &l1);
+    if (!(s.lacks & PT_SCENE_NO_MESH_LIGHTS) && bu(s, inst + PT_INST_KIND) == PT_SHAPE_MESH) {
+        const uint32_t triw = bu(s, bu(s, PT_HDR_LIGHT_FACE_OFF) + entry);
+        const F4 q0 = mf4(s, triw), q1 = mf4(s, triw + 4), q2 = mf4(s, triw + 8);
+        TriHit th;
+        const bool ok = triangle_test(f3(q0.x, q0.y, q0.z), f3(q1.x, q1.y, q1.z), f3(q2.x, q2.y, q2.z), tri_ray_prepare(l0, l1), 0.0f, PT_INF, &th);
+        h->valid = ok;
+        h->t = ok ? th.t : PT_INF;
+        return ok;
+    }
     return analytic_hit(s, inst, bu(s, inst + PT_INST_KIND), l0, l1, PT_INF, h);
 }
 
@@ -2164,7 +2186,7 @@ PT_HD float nearest_light_hit(const SceneView& s, F3 o, F3 d, uint32_t* which = 
         if (ub != 0ull) { PT_KEEP_BRANCH(); if (PT_WAVE_MEMBER(ub)) { PT_STAT(box_exact); inside = aabb_hit_exact(a, b, o, d, &entry); } }
         if (!inside) continue;
         Hit h;
-        if (light_shape_hit(s, inst_off + bu(s, lo_ + k) * PT_INST_WORDS, o, d, &h) && h.t < best) { best = h.t; light = bu(s, lo_ + k); }
+        if (light_shape_hit(s, inst_off + bu(s, lo_ + k) * PT_INST_WORDS, k, o, d, &h) && h.t < best) { best = h.t; light = bu(s, lo_ + k); }
     }
     if (which != nullptr) *which = light;   // (the instance that gave the distance; 0xffffffff: none)
     return best;
@@ -2532,8 +2554,9 @@ PT_HD uint32_t mediums_add(uint32_t list, uint32_t id, uint32_t* dropped = nullp
 }
 
 // ---------------------------------------------------------------- light sampling (Hittable::sample / psa_pdf)
-// rect.rs:113-173, sphere.rs:88-152, disk.rs:63-104, instance.rs:134-170
-PT_HD void light_sample(const SceneView& s, uint32_t inst, float sx, float sy, F3 from, F3* dir, float* pdf) {
+// rect.rs:113-173, sphere.rs:88-152, disk.rs:63-104, instance.rs:134-170; an emissive mesh face (the reference's todo!(), mesh.rs:213-232): DESIGN.md section 10.
+// `entry`: the light-list entry that was picked (a mesh instance's entries name its emissive faces, PT_HDR_LIGHT_FACE_OFF).
+PT_HD void light_sample(const SceneView& s, uint32_t inst, uint32_t entry, float sx, float sy, F3 from, F3* dir, float* pdf) {
     uint32_t kind = bu(s, inst + PT_INST_KIND), flags = bu(s, inst + PT_INST_FLAGS);
     bool xf = instance_is_transformed(s, inst), two_sided = (flags & 2u) != 0;
     if (xf) from = xf_point(s, inst + PT_INST_REVERSE, from);
@@ -2552,6 +2575,26 @@ PT_HD void light_sample(const SceneView& s, uint32_t inst, float sx, float sy, F
         normal = random_on_unit_sphere(sx, sy);
         point = add(origin, mul(normal, radius));
         area_pdf = 1.0f / (radius * radius * 4.0f * PT_PI);
+    } else if (!(s.lacks & PT_SCENE_NO_MESH_LIGHTS) && kind == PT_SHAPE_MESH) {
+        // sample_surface of the face: the square-root mapping to barycentrics, the point and the normal hit_record reports there (the interpolated vertex
+        // normal, or the face normal), no side choice, area pdf 1 / A_f (A_f computed once by the host); sample() on top of it as AARect's, below
+        const uint32_t triw = bu(s, bu(s, PT_HDR_LIGHT_FACE_OFF) + entry);
+        const uint32_t mesh = bu(s, inst + PT_INST_MESH), normal_off = bu(s, mesh + PT_MESH_NORMAL_OFF);
+        const F4 q0 = mf4(s, triw), q1 = mf4(s, triw + 4), q2 = mf4(s, triw + 8);
+        const float su = pt_sqrt(sx), b0 = 1.0f - su, b1 = sy * su, b2 = 1.0f - b0 - b1;
+        point = add(add(mul(f3(q0.x, q0.y, q0.z), b0), mul(f3(q1.x, q1.y, q1.z), b1)), mul(f3(q2.x, q2.y, q2.z), b2));
+        float area;
+        if (normal_off != 0) {
+            const uint32_t nn = normal_off + (triw - bu(s, mesh + PT_MESH_TRI_OFF));
+            const F4 m0 = mf4(s, nn), m1 = mf4(s, nn + 4), m2 = mf4(s, nn + 8);
+            normal = normalize(add(add(mul(f3(m0.x, m0.y, m0.z), b0), mul(f3(m1.x, m1.y, m1.z), b1)), mul(f3(m2.x, m2.y, m2.z), b2)));
+            area = m0.w;
+        } else {
+            const F4 fn = mf4(s, pt_f2u(q1.w));
+            normal = f3(fn.x, fn.y, fn.z);
+            area = fn.w;
+        }
+        area_pdf = 1.0f / area;
     } else {
         float radius = bf(s, inst + PT_INST_RADIUS);
         float x = sx;
@@ -2569,12 +2612,14 @@ PT_HD void light_sample(const SceneView& s, uint32_t inst, float sx, float sy, F
     if (xf) dn = normalize(xf_vec(s, inst + PT_INST_FORWARD, dn));
     *dir = dn; *pdf = p;
 }
-PT_HD float light_psa_pdf(const SceneView& s, uint32_t inst, float cos_o, float cos_i, F3 from, F3 to) {
+// `area`: for a hit on a mesh face, the A_f hit_record handed on in Hit::u (0: the hit is on no emissive face — its instance's own material emits — and the pdf is 0, as before)
+PT_HD float light_psa_pdf(const SceneView& s, uint32_t inst, float cos_o, float cos_i, F3 from, F3 to, float area = 0.0f) {
     uint32_t kind = bu(s, inst + PT_INST_KIND);
     if (instance_is_transformed(s, inst)) { from = xf_point(s, inst + PT_INST_FORWARD, from); to = xf_point(s, inst + PT_INST_FORWARD, to); }
     F3 dd = sub(to, from);
     float d2 = dot(dd, dd);
     if (kind == PT_SHAPE_RECT) { float s0 = bf(s, inst + PT_INST_SIZE), s1 = bf(s, inst + PT_INST_SIZE + 1); return (1.0f / (s0 * s1)) * d2 / pt_abs(cos_i) / pt_abs(cos_o); }
+    if (!(s.lacks & PT_SCENE_NO_MESH_LIGHTS) && kind == PT_SHAPE_MESH) return area > 0.0f ? (1.0f / area) * d2 / pt_abs(cos_i) / pt_abs(cos_o) : 0.0f;   // (the rect's form)
     float radius = bf(s, inst + PT_INST_RADIUS);
     if (kind == PT_SHAPE_SPHERE) return (1.0f / (radius * radius * 4.0f * PT_PI)) * d2 / pt_abs(cos_i * cos_o);
     if (kind == PT_SHAPE_DISK) return d2 / ((pt_abs(cos_o) * pt_abs(cos_i) + 0.00001f) * (PT_PI * radius * radius));

@@ -21,6 +21,7 @@
 
 #include "pt_kernels.h"   /* first: it switches on the wave-level device code of pt_device.h */
 #include "../../include/pt_api.h"
+#include "../../include/pt_debug.h"
 #include "pt_error.h"
 #include "pt_plan.h"
 #include "pt_scene_host.h"
@@ -70,6 +71,17 @@ __global__ void __launch_bounds__(kBlock) k_probe_material(const uint32_t* __res
         } else {
             f[i] = curve_eval(s, record, lambda[i]);
         }
+    }
+}
+// light_sample of one light-list entry from n points (pt_light_sample): the vertex kernels' own call, every shape's code present (lacks = 0)
+__global__ void __launch_bounds__(kBlock) k_probe_light(const uint32_t* __restrict__ blob, const float* __restrict__ tex, uint32_t entry, uint32_t n,
+                                                       const float* __restrict__ from, const float* __restrict__ s2, float* __restrict__ dir, float* __restrict__ pdf) {
+    SceneView s; s.w = blob; s.tex = tex; s.m = blob + blob[PT_HDR_CORE_WORDS];
+    const uint32_t inst = blob[PT_HDR_INSTANCE_OFF] + blob[blob[PT_HDR_LIGHT_OFF] + entry] * PT_INST_WORDS;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        F3 d;
+        light_sample(s, inst, entry, s2[2 * i], s2[2 * i + 1], f3(from[3 * i], from[3 * i + 1], from[3 * i + 2]), &d, &pdf[i]);
+        dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z;
     }
 }
 __global__ void __launch_bounds__(kBlock) k_probe_numerics(int which, uint32_t n, const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ out) {
@@ -281,9 +293,10 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     const bool sweep = sc->host.blob[PT_HDR_SWEEP_OFF] != 0 && !(sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_NO_SWEEP);
     // the sweep table holds walked meshes: rays that reach one are parked and resumed in full waves (PT_AMD_NO_PARK=1: in line)
     const bool walks = (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_SWEEP_WALKS) != 0;
-    const bool parked = sweep && walks && b.park != nullptr && !(tn.flags & PT_TUNE_NO_PARK);
+    const bool mesh_lights = sc->host.blob[PT_HDR_LIGHT_FACE_OFF] != 0u;   // (emissive mesh faces: PT_FORM_ANY, below)
+    const bool parked = sweep && walks && b.park != nullptr && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights;
     // no sweep table (more than 64 instances, PT_AMD_NO_SWEEP): the top-level tree per lane, every mesh parked (top_walk_run, pt_device.h)
-    const bool parked_walk = !sweep && b.park != nullptr && !(tn.flags & PT_TUNE_NO_PARK);
+    const bool parked_walk = !sweep && b.park != nullptr && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights;
     // PT_AMD_POOL=1: phase 3 of a pure sweep scene pooled per wave (sweep_run_pooled).  Bit-identical, but measured slower than the lane
     // loop on MI355X (C2: k_extend 3155 vs 2475 us, k_shadow 5421 vs 4677 us; DESIGN.md section 5 has the breakdown), so it is not the default.
 #ifdef PT_EXPERIMENTS
@@ -292,8 +305,9 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
 #else
     const bool pooled = false;   // (the pooled kernels are not in the product: make EXTRA=-DPT_EXPERIMENTS builds them, PT_AMD_POOL=1 selects them there)
 #endif
-    // (walked meshes in line under PT_AMD_NO_PARK, and every partly staged or unstaged blob: the run-time choice of PT_FORM_ANY)
-    const int trav_form = parked ? PT_FORM_PARKED : parked_walk ? PT_FORM_PARKED_WALK : (mode != PT_LDS_ALL || (sweep && walks)) ? PT_FORM_ANY : pooled ? PT_FORM_POOLED : sweep ? PT_FORM_SWEEP : PT_FORM_WALK;
+    // (walked meshes in line under PT_AMD_NO_PARK, and every partly staged or unstaged blob: the run-time choice of PT_FORM_ANY.  A scene with emissive mesh faces
+    // takes it too: the specialised traversal forms are compiled without the faces' code — PT_SCENE_NO_MESH_LIGHTS, pt_kern_*.hip — and keep their registers)
+    const int trav_form = parked ? PT_FORM_PARKED : parked_walk ? PT_FORM_PARKED_WALK : (mode != PT_LDS_ALL || (sweep && walks) || mesh_lights) ? PT_FORM_ANY : pooled ? PT_FORM_POOLED : sweep ? PT_FORM_SWEEP : PT_FORM_WALK;
     // The parked kernels take units of work from a counter, a few persistent workgroups per CU, when the whole blob is staged in LDS
     // (C3: k_extend 9175 -> 7880 us, k_shadow 8008 -> 7105, 487 -> 543 Msamples/s: park lists that live across units keep the drains
     // full).  With the mesh in HBM/L2 (C4) the static form wins, 1128 vs 1083 Msamples/s: a wave's parked rays then come from one
@@ -304,6 +318,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     LaunchCfg cfg{grid, lds_bytes, stream, mode};
     cfg.dyn_grid = dyn_grid < grid ? dyn_grid : grid;
     cfg.lacks = sc->lacks;
+    cfg.mesh_lights = mesh_lights;
 #ifdef PT_EXPERIMENTS
     cfg.live_lists = env_u32("PT_AMD_LIVE_LISTS", 0) != 0;   // (k_shadow_live: a measurement build's kernel, profiles/r4_experiments.md)
 #endif
@@ -865,6 +880,20 @@ pt_status pt_camera_samples(pt_scene* sc, const pt_render_desc* rdp, size_t n, c
 pt_status pt_bsdf_sample(pt_scene* sc, uint32_t material, size_t n, const float* lambda, const float* wi, const float* s2, float* f, float* wo, float* pdf) {
     if (!sc || material >= sc->host.material_count) return fail(PT_ERR_INVALID_ARGUMENT, "bad material");
     return probe_material(sc, 0, sc->host.blob[PT_HDR_MATERIAL_OFF] + material * PT_MAT_WORDS, n, lambda, wi, 3, s2, 2, f, wo, pdf);
+}
+pt_status pt_light_sample(pt_scene* sc, uint32_t light_entry, size_t n, const float* from, const float* sample2d, float* dir, float* pdf) {
+    if (!sc || light_entry >= sc->host.light_count) return fail(PT_ERR_INVALID_ARGUMENT, "bad light entry");
+    if (n == 0) return PT_OK;
+    DevBuf df, ds, dd, dp;
+    HIP_TRY(df.alloc(12 * n)); HIP_TRY(ds.alloc(8 * n)); HIP_TRY(dd.alloc(12 * n)); HIP_TRY(dp.alloc(4 * n));
+    HIP_TRY(hipMemcpy(df.p, from, 12 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ds.p, sample2d, 8 * n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_probe_light, dim3(256), dim3(kBlock), 0, 0, sc->d_blob, sc->d_tex, light_entry, (uint32_t)n, df.as<float>(), ds.as<float>(), dd.as<float>(), dp.as<float>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(dir, dd.p, 12 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pdf, dp.p, 4 * n, hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 pt_status pt_bsdf_eval(pt_scene* sc, uint32_t material, size_t n, const float* lambda, const float* wi, const float* wo, float* f, float* pdf) {
     if (!sc || material >= sc->host.material_count) return fail(PT_ERR_INVALID_ARGUMENT, "bad material");

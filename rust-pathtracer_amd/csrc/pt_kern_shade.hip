@@ -16,14 +16,20 @@ namespace ptk {
                                 else PT_GO(K(PT_LDS_NONE), __VA_ARGS__); } while (0)
 // (PT_SCENE_NO_CERTS: the certificate code compiled out — every form but the two a scene WITH a convex-body certificate takes, K_SHADE_NC / K_SHADE_FC: the engine gives such a
 // scene at least the NO_ENV form, never the lean, fused or light-free ones)
-#define K_SHADE_L(M) k_shade<M, PT_SHADE_NL, PT_SHADE_LEAN, PT_SCENE_NO_CERTS>
-#define K_SHADE_LX(M) k_shade<M, PT_SHADE_NL, PT_SHADE_LEAN, PT_SCENE_NO_XF | PT_SCENE_NO_CERTS>
-#define K_SHADE_FUSED k_shade<PT_LDS_ALL, PT_SHADE_NL, PT_SHADE_LEAN, PT_SCENE_NO_XF | PT_SCENE_NO_CERTS, PT_TRAV_SWEEP>
-#define K_SHADE_N(M) k_shade<M, PT_SHADE_NL, PT_SHADE_NO_ENV, PT_SCENE_NO_CERTS>
-#define K_SHADE_F(M) k_shade<M, PT_SHADE_NL, PT_SHADE_FULL, PT_SCENE_NO_CERTS>
-#define K_SHADE_FE(M) k_shade<M, PT_SHADE_NL, PT_SHADE_FULL, PT_SCENE_NO_LIGHTS | PT_SCENE_NO_CERTS>
-#define K_SHADE_NC(M) k_shade<M, PT_SHADE_NL, PT_SHADE_NO_ENV>
-#define K_SHADE_FC(M) k_shade<M, PT_SHADE_NL, PT_SHADE_FULL>
+// (PT_SCENE_NO_MESH_LIGHTS: every form but the three of a scene with emissive mesh faces, K_SHADE_LM / NM / FM, and the medium-aware K_SHADE_MM — with the faces'
+// sampler and pdf.  The lean one is compiled without certificates — the engine gives a scene with both at least NO_ENV —, the other two with them.)
+#define PT_NML PT_SCENE_NO_MESH_LIGHTS
+#define K_SHADE_L(M) k_shade<M, PT_SHADE_NL, PT_SHADE_LEAN, PT_SCENE_NO_CERTS | PT_NML>
+#define K_SHADE_LX(M) k_shade<M, PT_SHADE_NL, PT_SHADE_LEAN, PT_SCENE_NO_XF | PT_SCENE_NO_CERTS | PT_NML>
+#define K_SHADE_FUSED k_shade<PT_LDS_ALL, PT_SHADE_NL, PT_SHADE_LEAN, PT_SCENE_NO_XF | PT_SCENE_NO_CERTS | PT_NML, PT_TRAV_SWEEP>
+#define K_SHADE_N(M) k_shade<M, PT_SHADE_NL, PT_SHADE_NO_ENV, PT_SCENE_NO_CERTS | PT_NML>
+#define K_SHADE_F(M) k_shade<M, PT_SHADE_NL, PT_SHADE_FULL, PT_SCENE_NO_CERTS | PT_NML>
+#define K_SHADE_FE(M) k_shade<M, PT_SHADE_NL, PT_SHADE_FULL, PT_SCENE_NO_LIGHTS | PT_SCENE_NO_CERTS | PT_NML>
+#define K_SHADE_NC(M) k_shade<M, PT_SHADE_NL, PT_SHADE_NO_ENV, PT_NML>
+#define K_SHADE_FC(M) k_shade<M, PT_SHADE_NL, PT_SHADE_FULL, PT_NML>
+#define K_SHADE_LM(M) k_shade<M, PT_SHADE_NL, PT_SHADE_LEAN, PT_SCENE_NO_CERTS>
+#define K_SHADE_NM(M) k_shade<M, PT_SHADE_NL, PT_SHADE_NO_ENV, 0u>
+#define K_SHADE_FM(M) k_shade<M, PT_SHADE_NL, PT_SHADE_FULL, 0u>
 #define PT_ARGS sc.blob, sc.blob_words, sc.tex, rp, bounce, pixels, paths_in, hits, paths_out, shadow, energy, seg_cap, count_in, count_out, shadow_count, block_stats
 #define PT_ARGS_FWD sc, rp, bounce, pixels, paths_in, hits, paths_out, shadow, energy, seg_cap, count_in, count_out, shadow_count, block_stats
 #define PT_CAT2(a, b) a##b
@@ -36,22 +42,26 @@ void PT_PARTNAME(launch_shade_nl)(const LaunchCfg& c, int form, const SceneArgs&
 #if PT_SHADE_PART == 1
 #if PT_SHADE_NL == 1
 #define K_SHADE_M(M) k_shade_medium<M>
-    if (form == PT_SHADE_MEDIUM) { PT_BY_MODE(K_SHADE_M, PT_ARGS); return; }
+#define K_SHADE_MM(M) k_shade_medium<M, 0u>
+    if (form == PT_SHADE_MEDIUM) { if (c.mesh_lights) PT_BY_MODE(K_SHADE_MM, PT_ARGS); else PT_BY_MODE(K_SHADE_M, PT_ARGS); return; }
 #endif
     if (form == PT_SHADE_FULL) {   // (the marginal tables of the importance map behind the blob: stage_marginal)
         LaunchCfg d = c; d.lds_bytes = ((c.lds_bytes + 15u) & ~15u) + sc.marg_bytes;
 #define PT_GO_D(K, ...) go(d, K, __VA_ARGS__)
 #define PT_BY_MODE_D(K, ...) do { if (c.lds_mode == PT_LDS_ALL) PT_GO_D(K(PT_LDS_ALL), __VA_ARGS__); else if (c.lds_mode == PT_LDS_CORE) PT_GO_D(K(PT_LDS_CORE), __VA_ARGS__); \
                                   else PT_GO_D(K(PT_LDS_NONE), __VA_ARGS__); } while (0)
-        if (c.certs) PT_BY_MODE_D(K_SHADE_FC, PT_ARGS);
+        if (c.mesh_lights) PT_BY_MODE_D(K_SHADE_FM, PT_ARGS);
+        else if (c.certs) PT_BY_MODE_D(K_SHADE_FC, PT_ARGS);
         else if ((c.lacks & PT_SCENE_NO_LIGHTS) && PT_SHADE_NL == 1) PT_BY_MODE_D(K_SHADE_FE, PT_ARGS);   // (an environment is the scene's only emitter)
         else PT_BY_MODE_D(K_SHADE_F, PT_ARGS);
     }
+    else if (c.mesh_lights) PT_BY_MODE(K_SHADE_NM, PT_ARGS);
     else if (c.certs) PT_BY_MODE(K_SHADE_NC, PT_ARGS);
     else PT_BY_MODE(K_SHADE_N, PT_ARGS);
 #else
     (void)form;
-    if (c.fuse) PT_GO(K_SHADE_FUSED, PT_ARGS);   // (the engine asks for it only where this form exists: PT_LDS_ALL, lean, no transforms, pure sweep)
+    if (c.mesh_lights) PT_BY_MODE(K_SHADE_LM, PT_ARGS);   // (never fused: the engine gives such a scene the general traversal form)
+    else if (c.fuse) PT_GO(K_SHADE_FUSED, PT_ARGS);   // (the engine asks for it only where this form exists: PT_LDS_ALL, lean, no transforms, pure sweep)
     else if (c.lacks & PT_SCENE_NO_XF) PT_BY_MODE(K_SHADE_LX, PT_ARGS);
     else PT_BY_MODE(K_SHADE_L, PT_ARGS);
 #endif
@@ -63,12 +73,12 @@ hipError_t PT_PARTNAME(allow_lds_shade_nl)(uint32_t bytes) {
 #define PT_ALLOW_MODES(K) allow(reinterpret_cast<const void*>(K(PT_LDS_ALL))); allow(reinterpret_cast<const void*>(K(PT_LDS_CORE))); allow(reinterpret_cast<const void*>(K(PT_LDS_NONE)))
 #if PT_SHADE_PART == 0
     allow(reinterpret_cast<const void*>(K_SHADE_FUSED));
-    PT_ALLOW_MODES(K_SHADE_L); PT_ALLOW_MODES(K_SHADE_LX);
+    PT_ALLOW_MODES(K_SHADE_L); PT_ALLOW_MODES(K_SHADE_LX); PT_ALLOW_MODES(K_SHADE_LM);
 #else
-    PT_ALLOW_MODES(K_SHADE_N); PT_ALLOW_MODES(K_SHADE_F); PT_ALLOW_MODES(K_SHADE_NC); PT_ALLOW_MODES(K_SHADE_FC);
+    PT_ALLOW_MODES(K_SHADE_N); PT_ALLOW_MODES(K_SHADE_F); PT_ALLOW_MODES(K_SHADE_NC); PT_ALLOW_MODES(K_SHADE_FC); PT_ALLOW_MODES(K_SHADE_NM); PT_ALLOW_MODES(K_SHADE_FM);
 #if PT_SHADE_NL == 1
     PT_ALLOW_MODES(K_SHADE_FE);
-    PT_ALLOW_MODES(K_SHADE_M);
+    PT_ALLOW_MODES(K_SHADE_M); PT_ALLOW_MODES(K_SHADE_MM);
 #endif
 #endif
     return worst;

@@ -12,12 +12,14 @@ namespace ptk {
 #define PT_BY_MODE(K, ...) do { if (c.lds_mode == PT_LDS_ALL) PT_GO(K(PT_LDS_ALL), __VA_ARGS__); else if (c.lds_mode == PT_LDS_CORE) PT_GO(K(PT_LDS_CORE), __VA_ARGS__); \
                                 else PT_GO(K(PT_LDS_NONE), __VA_ARGS__); } while (0)
 #define K_SH_PARKED1(M) k_shadow_parked<M, 1>
-#define K_SH_PARKED1E(M) k_shadow_parked<M, 1, PT_SCENE_NO_LIGHTS>
+#define K_SH_PARKED1E(M) k_shadow_parked<M, 1, PT_SCENE_NO_LIGHTS | PT_SCENE_NO_MESH_LIGHTS>
 #define K_SH_PARKED4(M) k_shadow_parked<M, 4>
-#define K_SH_PARKED1W(M) k_shadow_parked<M, 1, 0u, 1>
-#define K_SH_PARKED4W(M) k_shadow_parked<M, 4, 0u, 1>
+#define K_SH_PARKED1W(M) k_shadow_parked<M, 1, PT_SCENE_NO_MESH_LIGHTS, 1>
+#define K_SH_PARKED4W(M) k_shadow_parked<M, 4, PT_SCENE_NO_MESH_LIGHTS, 1>
 #define K_SH_ANY1(M) k_shadow<M, 1, PT_TRAV_ANY>
 #define K_SH_ANY4(M) k_shadow<M, 4, PT_TRAV_ANY>
+#define K_SH_ANY1_MESH_LIGHTS(M) k_shadow<M, 1, PT_TRAV_ANY, true, 0u>   /* (the forms of a scene with emissive mesh faces: light_shape_hit tests the entry's face) */
+#define K_SH_ANY4_MESH_LIGHTS(M) k_shadow<M, 4, PT_TRAV_ANY, true, 0u>
 #define PT_ARGS sc.blob, sc.blob_words, sc.tex, light_samples, shadow, energy, energy_stride, seg_cap, count_in
 
 // `env`: the scene can produce environment rays (env_sampling_probability > 0); the sweep forms without them are leaner
@@ -42,6 +44,7 @@ void launch_shadow(const LaunchCfg& c, int form, int nl, bool env, const SceneAr
         PT_EXP_CASE(8) PT_EXP_CASE(2) PT_EXP_CASE(4) PT_EXP_CASE(0)
     }
 #endif
+    if (c.mesh_lights) { if (hero) PT_BY_MODE(K_SH_ANY4_MESH_LIGHTS, PT_ARGS); else PT_BY_MODE(K_SH_ANY1_MESH_LIGHTS, PT_ARGS); return; }   // (the engine asks for PT_FORM_ANY)
     if (form == PT_FORM_PARKED && c.unit_counter) {
         LaunchCfg d = c; d.grid = c.dyn_grid;
 #define PT_DYN_ARGS sc.blob, sc.blob_words, sc.tex, light_samples, shadow, seg_cap, count_in, park, (uint32_t)c.grid, c.unit_counter, c.walk_policy
@@ -56,8 +59,8 @@ void launch_shadow(const LaunchCfg& c, int form, int nl, bool env, const SceneAr
     } else if (form == PT_FORM_PARKED && !hero && (c.park_block == 512 || c.park_block == 1024)) {   // (the whole blob staged by bigger workgroups)
         uint32_t live_off;
         const uint32_t bytes = parked_lds(c.park_block, c.park_blob_bytes, &live_off);
-        if (c.park_block == 512) go_block(c, 512, bytes, k_shadow_parked<PT_LDS_ALL, 1, 0u, 0, 512>, PT_ARGS, park, c.walk_policy, live_off);
-        else go_block(c, 1024, bytes, k_shadow_parked<PT_LDS_ALL, 1, 0u, 0, 1024>, PT_ARGS, park, c.walk_policy, live_off);
+        if (c.park_block == 512) go_block(c, 512, bytes, k_shadow_parked<PT_LDS_ALL, 1, PT_SCENE_NO_MESH_LIGHTS, 0, 512>, PT_ARGS, park, c.walk_policy, live_off);
+        else go_block(c, 1024, bytes, k_shadow_parked<PT_LDS_ALL, 1, PT_SCENE_NO_MESH_LIGHTS, 0, 1024>, PT_ARGS, park, c.walk_policy, live_off);
         PT_TL_BUMP(c.stream);
     } else if (form == PT_FORM_PARKED) {
         if (hero) PT_PARKED_BY_MODE(K_SH_PARKED4);
@@ -76,17 +79,17 @@ void launch_shadow(const LaunchCfg& c, int form, int nl, bool env, const SceneAr
         const uint32_t at = (c.lds_bytes + 15u) & ~15u, live_off = at / 4u, bytes = at + (uint32_t)(kBlock / 64) * live_cap(light_samples) * 12u;
 #define PT_LIVE(NLv, ENVv, LACKSv) go_block(c, kBlock, bytes, k_shadow_live<PT_LDS_ALL, NLv, PT_TRAV_SWEEP, ENVv, LACKSv>, PT_ARGS, live_off)
         if (c.lacks & PT_SCENE_NO_XF) {
-            if (env) { if (hero) PT_LIVE(4, true, PT_SCENE_NO_XF); else PT_LIVE(1, true, PT_SCENE_NO_XF); }
-            else if (hero) PT_LIVE(4, false, PT_SCENE_NO_XF); else PT_LIVE(1, false, PT_SCENE_NO_XF);
+            if (env) { if (hero) PT_LIVE(4, true, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS); else PT_LIVE(1, true, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS); }
+            else if (hero) PT_LIVE(4, false, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS); else PT_LIVE(1, false, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS);
         } else {
-            if (env) { if (hero) PT_LIVE(4, true, 0u); else PT_LIVE(1, true, 0u); }
-            else if (hero) PT_LIVE(4, false, 0u); else PT_LIVE(1, false, 0u);
+            if (env) { if (hero) PT_LIVE(4, true, PT_SCENE_NO_MESH_LIGHTS); else PT_LIVE(1, true, PT_SCENE_NO_MESH_LIGHTS); }
+            else if (hero) PT_LIVE(4, false, PT_SCENE_NO_MESH_LIGHTS); else PT_LIVE(1, false, PT_SCENE_NO_MESH_LIGHTS);
         }
     }
 #endif
     else if (form == PT_FORM_SWEEP && (c.lacks & PT_SCENE_NO_XF)) {
-        if (env) { if (hero) PT_GO((k_shadow<PT_LDS_ALL, 4, PT_TRAV_SWEEP, true, PT_SCENE_NO_XF>), PT_ARGS); else PT_GO((k_shadow<PT_LDS_ALL, 1, PT_TRAV_SWEEP, true, PT_SCENE_NO_XF>), PT_ARGS); }
-        else if (hero) PT_GO((k_shadow<PT_LDS_ALL, 4, PT_TRAV_SWEEP, false, PT_SCENE_NO_XF>), PT_ARGS); else PT_GO((k_shadow<PT_LDS_ALL, 1, PT_TRAV_SWEEP, false, PT_SCENE_NO_XF>), PT_ARGS);
+        if (env) { if (hero) PT_GO((k_shadow<PT_LDS_ALL, 4, PT_TRAV_SWEEP, true, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS>), PT_ARGS); else PT_GO((k_shadow<PT_LDS_ALL, 1, PT_TRAV_SWEEP, true, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS>), PT_ARGS); }
+        else if (hero) PT_GO((k_shadow<PT_LDS_ALL, 4, PT_TRAV_SWEEP, false, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS>), PT_ARGS); else PT_GO((k_shadow<PT_LDS_ALL, 1, PT_TRAV_SWEEP, false, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS>), PT_ARGS);
     } else if (form == PT_FORM_SWEEP) {
         if (env) { if (hero) PT_GO((k_shadow<PT_LDS_ALL, 4, PT_TRAV_SWEEP, true>), PT_ARGS); else PT_GO((k_shadow<PT_LDS_ALL, 1, PT_TRAV_SWEEP, true>), PT_ARGS); }
         else if (hero) PT_GO((k_shadow<PT_LDS_ALL, 4, PT_TRAV_SWEEP, false>), PT_ARGS); else PT_GO((k_shadow<PT_LDS_ALL, 1, PT_TRAV_SWEEP, false>), PT_ARGS);
@@ -98,23 +101,23 @@ hipError_t allow_lds_shadow(uint32_t bytes) {
     hipError_t worst = hipSuccess;
     auto allow = [&](const void* k) { hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); if (e != hipSuccess) worst = e; };
 #define PT_ALLOW_MODES(K) allow(reinterpret_cast<const void*>(K(PT_LDS_ALL))); allow(reinterpret_cast<const void*>(K(PT_LDS_CORE)))
-    PT_ALLOW_MODES(K_SH_ANY1); PT_ALLOW_MODES(K_SH_ANY4); PT_ALLOW_MODES(K_SH_PARKED1); PT_ALLOW_MODES(K_SH_PARKED4); PT_ALLOW_MODES(K_SH_PARKED1E); PT_ALLOW_MODES(K_SH_PARKED1W); PT_ALLOW_MODES(K_SH_PARKED4W);
+    PT_ALLOW_MODES(K_SH_ANY1); PT_ALLOW_MODES(K_SH_ANY4); PT_ALLOW_MODES(K_SH_ANY1_MESH_LIGHTS); PT_ALLOW_MODES(K_SH_ANY4_MESH_LIGHTS); PT_ALLOW_MODES(K_SH_PARKED1); PT_ALLOW_MODES(K_SH_PARKED4); PT_ALLOW_MODES(K_SH_PARKED1E); PT_ALLOW_MODES(K_SH_PARKED1W); PT_ALLOW_MODES(K_SH_PARKED4W);
 #define K_SH_DYN1(M) k_shadow_parked_dyn<M, 1>
 #define K_SH_DYN4(M) k_shadow_parked_dyn<M, 4>
     PT_ALLOW_MODES(K_SH_DYN1); PT_ALLOW_MODES(K_SH_DYN4);
 #ifdef PT_EXPERIMENTS
-#define PT_ALLOW_LIVE(NLv, ENVv) allow(reinterpret_cast<const void*>(k_shadow_live<PT_LDS_ALL, NLv, PT_TRAV_SWEEP, ENVv, 0u>)); allow(reinterpret_cast<const void*>(k_shadow_live<PT_LDS_ALL, NLv, PT_TRAV_SWEEP, ENVv, PT_SCENE_NO_XF>))
+#define PT_ALLOW_LIVE(NLv, ENVv) allow(reinterpret_cast<const void*>(k_shadow_live<PT_LDS_ALL, NLv, PT_TRAV_SWEEP, ENVv, PT_SCENE_NO_MESH_LIGHTS>)); allow(reinterpret_cast<const void*>(k_shadow_live<PT_LDS_ALL, NLv, PT_TRAV_SWEEP, ENVv, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS>))
     PT_ALLOW_LIVE(1, true); PT_ALLOW_LIVE(1, false); PT_ALLOW_LIVE(4, true); PT_ALLOW_LIVE(4, false);
 #endif
-    allow(reinterpret_cast<const void*>(k_shadow_parked<PT_LDS_ALL, 1, 0u, 0, 512>)); allow(reinterpret_cast<const void*>(k_shadow_parked<PT_LDS_ALL, 1, 0u, 0, 1024>));
+    allow(reinterpret_cast<const void*>(k_shadow_parked<PT_LDS_ALL, 1, PT_SCENE_NO_MESH_LIGHTS, 0, 512>)); allow(reinterpret_cast<const void*>(k_shadow_parked<PT_LDS_ALL, 1, PT_SCENE_NO_MESH_LIGHTS, 0, 1024>));
     { // (the parked forms without a staged blob still keep their live lists in dynamic LDS)
         allow(reinterpret_cast<const void*>(K_SH_PARKED1(PT_LDS_NONE))); allow(reinterpret_cast<const void*>(K_SH_PARKED4(PT_LDS_NONE))); allow(reinterpret_cast<const void*>(K_SH_PARKED1E(PT_LDS_NONE)));
         allow(reinterpret_cast<const void*>(K_SH_PARKED1W(PT_LDS_NONE))); allow(reinterpret_cast<const void*>(K_SH_PARKED4W(PT_LDS_NONE))); }
     allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 1, PT_TRAV_WALK>)); allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 4, PT_TRAV_WALK>));
     allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 1, PT_TRAV_SWEEP, true>)); allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 4, PT_TRAV_SWEEP, true>));
     allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 1, PT_TRAV_SWEEP, false>)); allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 4, PT_TRAV_SWEEP, false>));
-    allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 1, PT_TRAV_SWEEP, true, PT_SCENE_NO_XF>)); allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 4, PT_TRAV_SWEEP, true, PT_SCENE_NO_XF>));
-    allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 1, PT_TRAV_SWEEP, false, PT_SCENE_NO_XF>)); allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 4, PT_TRAV_SWEEP, false, PT_SCENE_NO_XF>));
+    allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 1, PT_TRAV_SWEEP, true, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS>)); allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 4, PT_TRAV_SWEEP, true, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS>));
+    allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 1, PT_TRAV_SWEEP, false, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS>)); allow(reinterpret_cast<const void*>(k_shadow<PT_LDS_ALL, 4, PT_TRAV_SWEEP, false, PT_SCENE_NO_XF | PT_SCENE_NO_MESH_LIGHTS>));
 #ifdef PT_EXPERIMENTS
     allow(reinterpret_cast<const void*>(k_shadow_pooled<PT_LDS_ALL, 1, false>)); allow(reinterpret_cast<const void*>(k_shadow_pooled<PT_LDS_ALL, 4, false>));
     allow(reinterpret_cast<const void*>(k_shadow_pooled<PT_LDS_ALL, 1, true>)); allow(reinterpret_cast<const void*>(k_shadow_pooled<PT_LDS_ALL, 4, true>));

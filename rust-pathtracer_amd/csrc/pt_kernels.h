@@ -135,7 +135,7 @@ __host__ __device__ constexpr uint32_t live_cap(uint32_t light_samples) { return
 #ifndef PT_EMPTY_SEGMENT_EXIT
 #define PT_EMPTY_SEGMENT_EXIT 1   /* a workgroup whose segment is empty returns before it stages the scene (round 5); 0 = stages it, then finds nothing to do */
 #endif
-template <int USE_LDS, uint32_t LACKS = 0u>
+template <int USE_LDS, uint32_t LACKS = PT_SCENE_NO_MESH_LIGHTS>
 __device__ __forceinline__ SceneView stage_scene(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* tex, uint32_t* lds) {
     SceneView s;
     s.tex = tex;
@@ -262,8 +262,10 @@ __global__ void __launch_bounds__(kBlock) k_generate(RenderParams rp, const uint
     if (threadIdx.x == 0) count_out[blockIdx.x] = cnt;
 }
 
-// LACKS (here and in k_shade / k_shadow): what the scene is known not to hold (PT_SCENE_*, pt_device.h) — compiled out of the form.
-template <int USE_LDS, int TRAV, uint32_t LACKS = 0u>
+// LACKS (here and in k_shade / k_shadow): what the scene is known not to hold (PT_SCENE_*, pt_device.h) — compiled out of the form.  Every form carries
+// PT_SCENE_NO_MESH_LIGHTS (the default) but those a scene with emissive mesh faces takes (pt_kern_*.hip: LACKS without that bit); the kernels without a LACKS
+// parameter have no such form and stage their scene with the bit.
+template <int USE_LDS, int TRAV, uint32_t LACKS = PT_SCENE_NO_MESH_LIGHTS>
 __global__ void __launch_bounds__(kBlock) PT_TRAV_OCC k_extend(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* __restrict__ tex,
                                                   Queue paths, Queue hits, uint32_t seg_cap, const uint32_t* __restrict__ count_in) {
     extern __shared__ __align__(16) uint32_t lds[];
@@ -286,7 +288,7 @@ __global__ void __launch_bounds__(kBlock) PT_TRAV_OCC k_extend(const uint32_t* _
 // FUSE_TRAV: PT_NO_FUSE = the closest hits come from k_extend through the hit queue; a traversal form (PT_TRAV_*) = this kernel traces its
 // own segments first (World::hit, then the vertex, as random_walk's loop body does: utils.rs:171-221) — the 44-byte hit record never
 // reaches HBM, the ray is read once, and one launch per bounce goes away.  Not for the FULL form (it sorts its items by the hit queue).
-template <int USE_LDS, int NL, int FORM, uint32_t LACKS = 0u, int FUSE_TRAV = PT_NO_FUSE>
+template <int USE_LDS, int NL, int FORM, uint32_t LACKS = PT_SCENE_NO_MESH_LIGHTS, int FUSE_TRAV = PT_NO_FUSE>
 __global__ void __launch_bounds__(kBlock) PT_SHADE_OCC k_shade(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* __restrict__ tex,
                                                  RenderParams rp, uint32_t bounce, const uint32_t* __restrict__ pixels,
                                                  Queue paths_in, Queue hits, Queue paths_out, Queue shadow, float* __restrict__ energy,
@@ -428,8 +430,8 @@ __global__ void __launch_bounds__(kBlock) PT_SHADE_OCC k_shade(const uint32_t* _
 }
 
 // The medium-aware walk's vertex kernel (stage_shade_medium; pt_render_desc::medium_aware): k_shade with the tracked mediums and the
-// "previous vertex was a medium vertex" flag carried in two more fields of the path record.
-template <int USE_LDS>
+// "previous vertex was a medium vertex" flag carried in two more fields of the path record.  (LACKS: PT_SCENE_NO_MESH_LIGHTS or nothing — the form of a scene with emissive faces.)
+template <int USE_LDS, uint32_t LACKS = PT_SCENE_NO_MESH_LIGHTS>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PT_SHADE_MEDIUM_WAVES)))
 k_shade_medium(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* __restrict__ tex, RenderParams rp, uint32_t bounce, const uint32_t* __restrict__ pixels,
                Queue paths_in, Queue hits, Queue paths_out, Queue shadow, float* __restrict__ energy, uint32_t seg_cap, const uint32_t* __restrict__ count_in,
@@ -441,7 +443,7 @@ k_shade_medium(const uint32_t* __restrict__ blob, uint32_t blob_words, const flo
         return;
     }
     if (threadIdx.x < 16) lds_counts[threadIdx.x] = 0;
-    SceneView s = stage_scene<USE_LDS>(blob, blob_words, tex, lds);
+    SceneView s = stage_scene<USE_LDS, LACKS>(blob, blob_words, tex, lds);
     if (USE_LDS == PT_LDS_NONE) __syncthreads();
     const uint32_t base = blockIdx.x * seg_cap, n = count_in[blockIdx.x];
     uint32_t st_vertices = 0, st_shadow = 0, st_env = 0, st_drops = 0;
@@ -557,7 +559,7 @@ k_shade_medium(const uint32_t* __restrict__ blob, uint32_t blob_words, const flo
 }
 
 constexpr uint32_t kShadowListed = 0x80000000u;   // (a flag in k_shadow's seg_cap argument: segments are far smaller)
-template <int USE_LDS, int NL, int TRAV, bool ENV = true, uint32_t LACKS = 0u>
+template <int USE_LDS, int NL, int TRAV, bool ENV = true, uint32_t LACKS = PT_SCENE_NO_MESH_LIGHTS>
 __global__ void __launch_bounds__(kBlock) PT_SHADOW_OCC k_shadow(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* __restrict__ tex,
                                                   uint32_t light_samples, Queue shadow, float* __restrict__ energy, uint32_t energy_stride,
                                                   uint32_t seg_cap, const uint32_t* __restrict__ count_in) {
@@ -585,7 +587,7 @@ __global__ void __launch_bounds__(kBlock) PT_SHADOW_OCC k_shadow(const uint32_t*
 // ballot; whenever the list holds 64 rays — and at the end — the wave traces 64 of them, every lane busy, and leaves each ray's contribution where its factor
 // was; the item's rays are summed in order at the end as before (pt.rs:349-392).  k_shadow_parked's listing, one step further (it lists before the light
 // pre-pass) and without the parking.  A ray's own search is untouched: same bound, same stop rule, same known light.
-template <int USE_LDS, int NL, int TRAV, bool ENV = true, uint32_t LACKS = 0u>
+template <int USE_LDS, int NL, int TRAV, bool ENV = true, uint32_t LACKS = PT_SCENE_NO_MESH_LIGHTS>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PT_SHADOW_LIVE_WAVES))) k_shadow_live(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* __restrict__ tex,
                                                                       uint32_t light_samples, Queue shadow, float* __restrict__ energy, uint32_t energy_stride,
                                                                       uint32_t seg_cap, const uint32_t* __restrict__ count_in, uint32_t live_off) {
@@ -683,7 +685,7 @@ __global__ void __launch_bounds__(kBlock) PT_POOL_OCC k_extend_pooled(const uint
                                                                      Queue paths, Queue hits, uint32_t seg_cap, const uint32_t* __restrict__ count_in) {
     extern __shared__ __align__(16) uint32_t lds[];
     __shared__ __align__(16) uint32_t pool_all[(kBlock / 64) * PT_POOL_WORDS];
-    SceneView s = stage_scene<USE_LDS>(blob, blob_words, tex, lds);
+    SceneView s = stage_scene<USE_LDS, PT_SCENE_NO_MESH_LIGHTS>(blob, blob_words, tex, lds);
     uint32_t* ws = pool_all + (threadIdx.x >> 6) * PT_POOL_WORDS;
     const uint32_t base = blockIdx.x * seg_cap, n = count_in[blockIdx.x];
     const uint32_t rounds = (n + blockDim.x - 1) / blockDim.x;
@@ -710,7 +712,7 @@ __global__ void __launch_bounds__(kBlock) PT_POOL_OCC k_shadow_pooled(const uint
                                                                      uint32_t seg_cap, const uint32_t* __restrict__ count_in) {
     extern __shared__ __align__(16) uint32_t lds[];
     __shared__ __align__(16) uint32_t pool_all[(kBlock / 64) * PT_POOL_WORDS];
-    SceneView s = stage_scene<USE_LDS>(blob, blob_words, tex, lds);
+    SceneView s = stage_scene<USE_LDS, PT_SCENE_NO_MESH_LIGHTS>(blob, blob_words, tex, lds);
     uint32_t* ws = pool_all + (threadIdx.x >> 6) * PT_POOL_WORDS;
     const uint32_t base = blockIdx.x * seg_cap, n = count_in[blockIdx.x];
     const uint32_t rounds = (n + blockDim.x - 1) / blockDim.x;
@@ -761,7 +763,7 @@ __global__ void __launch_bounds__(kBlock) PT_POOL_OCC k_extend_exp(const uint32_
                                                                   Queue paths, Queue hits, uint32_t seg_cap, const uint32_t* __restrict__ count_in) {
     extern __shared__ __align__(16) uint32_t lds[];
     __shared__ __align__(16) uint32_t pool_all[(EXP & 1) ? (kBlock / 64) * PT_POOL_WORDS : 4];
-    SceneView s = stage_scene<PT_LDS_ALL>(blob, blob_words, tex, lds);
+    SceneView s = stage_scene<PT_LDS_ALL, PT_SCENE_NO_MESH_LIGHTS>(blob, blob_words, tex, lds);
     uint32_t* ws = pool_all + ((EXP & 1) ? (threadIdx.x >> 6) * PT_POOL_WORDS : 0);
     const uint32_t base = blockIdx.x * seg_cap, n = count_in[blockIdx.x];
     const uint32_t rounds = (n + blockDim.x - 1) / blockDim.x;
@@ -792,7 +794,7 @@ template <int EXP>
 __global__ void __launch_bounds__(kBlock) PT_POOL_OCC k_shadow_exp(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* __restrict__ tex,
                                                                   uint32_t light_samples, Queue shadow, Queue sink, uint32_t seg_cap, const uint32_t* __restrict__ count_in) {
     extern __shared__ __align__(16) uint32_t lds[];
-    SceneView s = stage_scene<PT_LDS_ALL>(blob, blob_words, tex, lds);
+    SceneView s = stage_scene<PT_LDS_ALL, PT_SCENE_NO_MESH_LIGHTS>(blob, blob_words, tex, lds);
     uint32_t base = blockIdx.x * seg_cap, n = count_in[blockIdx.x];
     for (uint32_t j = threadIdx.x; j < n; j += blockDim.x) {
         const uint32_t item = base + j;
@@ -928,7 +930,7 @@ k_extend_parked(const uint32_t* __restrict__ blob, uint32_t blob_words, const fl
     __shared__ uint32_t park_counts[BLK / 64];
     constexpr uint32_t kParkCap = kWaveParkCap * (BLK / 64);   // (shadows ptk::kParkCap: this workgroup's entries per field)
     if (PT_EMPTY_SEGMENT_EXIT && count_in[blockIdx.x] == 0u) return;
-    SceneView s = stage_scene<USE_LDS>(blob, blob_words, tex, lds);
+    SceneView s = stage_scene<USE_LDS, PT_SCENE_NO_MESH_LIGHTS>(blob, blob_words, tex, lds);
     const uint32_t wave = PT_UNIFORM(threadIdx.x >> 6);   // (a scalar: with fresh_lane_id below, threadIdx.x need not stay in a register across the rounds)
     uint32_t* pk = park_all + (size_t)blockIdx.x * kParkFields * kParkCap + wave * kWaveParkCap;  // field f of entry e at pk[f * kParkCap + e]
     uint32_t* park_count = &park_counts[wave];
@@ -983,7 +985,7 @@ k_extend_parked(const uint32_t* __restrict__ blob, uint32_t blob_words, const fl
 // direction is a coincidence of the scene's set-up, and the scan's registers cost that 96-VGPR kernel 6 spilled.  Here the form with the scan happens to
 // allocate better than the one without: C3's kernel 4755 -> 4658 us, so every form carries it.)
 // `live_off`: where in the dynamic LDS, in words, the waves' lists of live rays begin (behind the staged blob; launch_shadow).  BLK: see k_extend_parked.
-template <int USE_LDS, int NL, uint32_t LACKS = 0u, int TOP = 0, int BLK = kBlock>
+template <int USE_LDS, int NL, uint32_t LACKS = PT_SCENE_NO_MESH_LIGHTS, int TOP = 0, int BLK = kBlock>
 __global__ void __launch_bounds__(BLK) PT_PARK_OCC k_shadow_parked(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* __restrict__ tex,
                                                                      uint32_t light_samples, Queue shadow, float* __restrict__ energy, uint32_t energy_stride,
                                                                      uint32_t seg_cap, const uint32_t* __restrict__ count_in, uint32_t* __restrict__ park_all, uint32_t walk_policy,
@@ -1141,7 +1143,7 @@ __global__ void __launch_bounds__(kBlock) PT_PARK_EXTEND_OCC k_extend_parked_dyn
                                                                          uint32_t* __restrict__ park_all, uint32_t n_segments, uint32_t* __restrict__ unit_counter, uint32_t walk_policy) {
     extern __shared__ __align__(16) uint32_t lds[];
     __shared__ uint32_t park_counts[kBlock / 64];
-    SceneView s = stage_scene<USE_LDS>(blob, blob_words, tex, lds);
+    SceneView s = stage_scene<USE_LDS, PT_SCENE_NO_MESH_LIGHTS>(blob, blob_words, tex, lds);
     const uint32_t wave = threadIdx.x >> 6, lane = lane_id();
     uint32_t* pk = park_all + (size_t)blockIdx.x * kParkFields * kParkCap + wave * kWaveParkCap;
     uint32_t* park_count = &park_counts[wave];
@@ -1191,7 +1193,7 @@ __global__ void __launch_bounds__(kBlock) PT_PARK_OCC k_shadow_parked_dyn(const 
                                                                          uint32_t* __restrict__ park_all, uint32_t n_segments, uint32_t* __restrict__ unit_counter, uint32_t walk_policy) {
     extern __shared__ __align__(16) uint32_t lds[];
     __shared__ uint32_t park_counts[kBlock / 64];
-    SceneView s = stage_scene<USE_LDS>(blob, blob_words, tex, lds);
+    SceneView s = stage_scene<USE_LDS, PT_SCENE_NO_MESH_LIGHTS>(blob, blob_words, tex, lds);
     const uint32_t wave = threadIdx.x >> 6, lane = lane_id();
     uint32_t* pk = park_all + (size_t)blockIdx.x * kParkFields * kParkCap + wave * kWaveParkCap;
     uint32_t* park_count = &park_counts[wave];
@@ -1280,7 +1282,7 @@ template <int USE_LDS>
 __global__ void __launch_bounds__(kBlock) k_probe_intersect(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* __restrict__ tex,
                                                            uint32_t n, const float* __restrict__ o, const float* __restrict__ d, pt_hit* __restrict__ out) {
     extern __shared__ __align__(16) uint32_t lds[];
-    SceneView s = stage_scene<USE_LDS>(blob, blob_words, tex, lds);
+    SceneView s = stage_scene<USE_LDS, PT_SCENE_NO_MESH_LIGHTS>(blob, blob_words, tex, lds);
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         Hit h;
         bool ok = world_hit(s, f3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), f3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), &h);

@@ -391,6 +391,18 @@ void xf_point(const float* m, const float* p, float* o) {
     for (int r = 0; r < 3; ++r) o[r] = m[4 * r] * p[0] + m[4 * r + 1] * p[1] + m[4 * r + 2] * p[2] + m[4 * r + 3];
 }
 
+// MeshTriangleRef::surface_area (mesh.rs:200-210) in object space, f32, in its order: Heron's formula over the edge lengths |p2 - p0|, |p1 - p0|, |p2 - p1|
+// (a length: sqrt(x x + y y + z z), left to right).  A degenerate face can give 0 or NaN: its sample's pdf is then not finite and becomes 0 (light_sample).
+float triangle_area(const float* V, const uint32_t* ix) {
+    auto dist = [&](uint32_t a, uint32_t b) {
+        const float x = V[3 * b] - V[3 * a], y = V[3 * b + 1] - V[3 * a + 1], z = V[3 * b + 2] - V[3 * a + 2];
+        return std::sqrt(x * x + y * y + z * z);
+    };
+    const float d02 = dist(ix[0], ix[2]), d01 = dist(ix[0], ix[1]), d12 = dist(ix[1], ix[2]);
+    const float s = 0.5f * (d02 + d01 + d12);
+    return std::sqrt(s * (s - d01) * (s - d12) * (s - d02));
+}
+
 }  // namespace
 
 static bool build_host_scene_with(const pt_scene_desc& d, HostScene* hs, std::string* err, bool curve_tables, uint32_t* curve_table_words);
@@ -573,6 +585,7 @@ static bool build_host_scene_with(const pt_scene_desc& d, HostScene* hs, std::st
     std::vector<Box> mesh_box(d.mesh_count);
     hs->mesh_has_light.assign(d.mesh_count, 0);
     std::vector<uint32_t> mesh_light_faces(d.mesh_count, 0);
+    std::vector<std::vector<uint32_t>> mesh_light_list(d.mesh_count);   // the emissive faces of each mesh, in face order (one light-list entry each per instance)
     for (uint32_t mi = 0; mi < d.mesh_count; ++mi) {
         const pt_mesh& m = d.meshes[mi];
         if ((size_t)m.vertex_offset + m.vertex_count > d.vertex_count) return fail("mesh vertices out of range");
@@ -603,7 +616,7 @@ static bool build_host_scene_with(const pt_scene_desc& d, HostScene* hs, std::st
             const uint32_t* ix = d.indices + m.index_offset + 3 * (size_t)f;
             uint32_t mat = m.face_material_offset >= 0 ? d.face_materials[m.face_material_offset + f] : PT_MATERIAL_ID(PT_TAG_MATERIAL, 0);
             if (!material_ok(mat) || mat == PT_MATERIAL_NONE) return fail("mesh face material out of range");
-            if (PT_MATERIAL_TAG(mat) == PT_TAG_LIGHT) mesh_light_faces[mi]++;
+            if (PT_MATERIAL_TAG(mat) == PT_TAG_LIGHT) { mesh_light_faces[mi]++; mesh_light_list[mi].push_back(f); }
             for (int k = 0; k < 3; ++k) {
                 const float* p = V + 3 * ix[k];
                 md.push_back(fbits(p[0])); md.push_back(fbits(p[1])); md.push_back(fbits(p[2])); md.push_back(k == 0 ? mat : 0u);
@@ -633,6 +646,12 @@ static bool build_host_scene_with(const pt_scene_desc& d, HostScene* hs, std::st
                 const uint32_t* ix = d.indices + m.index_offset + 3 * (size_t)f;
                 for (int k = 0; k < 3; ++k) { const float* p = N + 3 * ix[k]; md.push_back(fbits(p[0])); md.push_back(fbits(p[1])); md.push_back(fbits(p[2])); md.push_back(0u); }
             }
+        }
+        // A_f of every emissive face into the spare word of its normal record (pt_blob.h PT_HDR_LIGHT_FACE_OFF): the face normal's, or the first vertex normal's
+        for (uint32_t f : mesh_light_list[mi]) {
+            const size_t at = tri_off + (size_t)f * PT_TRI_WORDS;
+            const uint32_t spare = normal_off != 0u ? normal_off + f * PT_TRI_WORDS + 3u : md[at + 7] + 3u;
+            md[spare] = fbits(triangle_area(V, d.indices + m.index_offset + 3 * (size_t)f));
         }
         // permuted copies of the triangles of a mesh small enough to be taken into the sweep table (pt_blob.h)
         if (m.face_count < PT_SWEEP_MAX_BITS) {
@@ -727,7 +746,7 @@ static bool build_host_scene_with(const pt_scene_desc& d, HostScene* hs, std::st
     pad16(w);
     w[PT_HDR_INSTANCE_OFF] = (uint32_t)w.size(); w[PT_HDR_INSTANCE_COUNT] = d.instance_count;
     std::vector<Box> ibox(d.instance_count);
-    std::vector<uint32_t> lights;
+    std::vector<uint32_t> lights, light_faces;   // light_faces: per entry the triangle word offset of the emissive face it stands for, 0 = an analytic light
     for (uint32_t i = 0; i < d.instance_count; ++i) {
         const pt_instance& in = d.instances[i];
         if (!material_ok(in.material)) return fail("instance material out of range");
@@ -777,13 +796,15 @@ static bool build_host_scene_with(const pt_scene_desc& d, HostScene* hs, std::st
         ibox[i] = b;
         w.insert(w.end(), r, r + PT_INST_WORDS);
         // World::new light list (world/mod.rs:42-66)
-        if (in.kind == PT_SHAPE_MESH) { for (uint32_t k = 0; k < mesh_light_faces[in.mesh]; ++k) lights.push_back(i); }
-        else {
+        // (an emissive face is a light of its own: the j-th entry of the instance's run is the mesh's j-th emissive face)
+        if (in.kind == PT_SHAPE_MESH) {
+            const uint32_t tri_off = w[mesh_off[in.mesh] + PT_MESH_TRI_OFF];
+            for (uint32_t f : mesh_light_list[in.mesh]) { lights.push_back(i); light_faces.push_back(tri_off + f * PT_TRI_WORDS); }
+        } else {
             uint32_t mid = in.material == PT_MATERIAL_NONE ? PT_MATERIAL_ID(PT_TAG_MATERIAL, 0) : in.material;
-            if (PT_MATERIAL_TAG(mid) == PT_TAG_LIGHT) lights.push_back(i);
+            if (PT_MATERIAL_TAG(mid) == PT_TAG_LIGHT) { lights.push_back(i); light_faces.push_back(0u); }
         }
     }
-    for (uint32_t l : lights) if (d.instances[l].kind == PT_SHAPE_MESH) return fail("mesh lights cannot be sampled (todo!() in the reference, mesh.rs:213-232)");
     {   // convex closed mesh instances (pt_blob.h PT_INST_CONVEX_*): certified once per instance, in world space
         auto lightish = [&](uint32_t i) {   // can a hit on instance i carry a Light tag
             const pt_instance& in = d.instances[i];
@@ -892,6 +913,13 @@ static bool build_host_scene_with(const pt_scene_desc& d, HostScene* hs, std::st
         pad16(w);
         w[PT_HDR_LIGHT_NODE_OFF] = (uint32_t)w.size();
         for (uint32_t l : lights) w.push_back(top + bb.leaf_of_shape[l] * PT_NODE_WORDS);
+        bool face_lights = false;
+        for (uint32_t t : light_faces) face_lights = face_lights || t != 0u;
+        if (face_lights) {   // (only a scene with emissive mesh faces has the list: every other scene's blob is word for word what it was before them)
+            pad16(w);
+            w[PT_HDR_LIGHT_FACE_OFF] = (uint32_t)w.size();
+            w.insert(w.end(), light_faces.begin(), light_faces.end());
+        }
         // ---- leaf sweep table (world_hit_sweep): the leaf boxes of both levels in traversal pre-order, as far as 64 mask bits
         // go.  Every instance takes a bit; the triangle leaves of mesh instances are taken in ("inlined") smallest mesh first
         // while they fit; the remaining mesh instances keep only their own bit and their BVH is walked when that bit is hit.
@@ -1163,8 +1191,8 @@ static bool build_host_scene_with(const pt_scene_desc& d, HostScene* hs, std::st
         for (uint32_t i = 0; i < d.instance_count; ++i) {
             const pt_instance& in = d.instances[i];
             if (in.kind == PT_SHAPE_DISK) flags |= PT_FLAG_NO_TOP_CULL;
-            // a mesh whose hits can carry a Light tag is not in the light list (world/mod.rs:45-54 only looks at analytic
-            // instances' own ids and mesh face ids, and mesh face lights are rejected above) but would pass pt.rs:178
+            // a mesh whose hits can carry a Light tag through its instance's material is not in the light list (world/mod.rs:45-54 only looks at
+            // analytic instances' own ids and mesh face ids) but would pass pt.rs:178
             if (in.kind == PT_SHAPE_MESH && in.material != PT_MATERIAL_NONE && PT_MATERIAL_TAG(in.material) == PT_TAG_LIGHT) flags |= PT_FLAG_NO_SHADOW_BOUND;
         }
         w[PT_HDR_FLAGS] = flags;

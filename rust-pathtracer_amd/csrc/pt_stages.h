@@ -302,7 +302,7 @@ PT_HD ShadeOutT<NL> stage_shade(const SceneView& s, const RenderParams& rp, uint
             } else if (!rp.only_direct) {
                 F3 nee_dir = normalize(sub(hit.p, pv.prev_p));
                 uint32_t inst = bu(s, PT_HDR_INSTANCE_OFF) + hit_instance_index(s, hit.instance) * PT_INST_WORDS;
-                float pdfh = light_psa_pdf(s, inst, dot(pv.prev_n, nee_dir), dot(hit.n, nee_dir), pv.prev_p, hit.p);
+                float pdfh = light_psa_pdf(s, inst, dot(pv.prev_n, nee_dir), dot(hit.n, nee_dir), pv.prev_p, hit.p, hit.u);   // (hit.u: a mesh face's A_f, hit_record)
                 float a = pv.prev_pdf;
                 float weight = (a * a) / (a * a + pdfh * pdfh);
                 out.energy_add[0] = weight * pv.beta[0] * emission;
@@ -365,7 +365,7 @@ PT_HD ShadeOutT<NL> stage_shade(const SceneView& s, const RenderParams& rp, uint
                     uint32_t light_id = bu(s, bu(s, PT_HDR_LIGHT_OFF) + (uint32_t)fi);
                     float pick_pdf = 1.0f / (float)n_lights;
                     F3 ldir; float light_pdf;
-                    light_sample(s, bu(s, PT_HDR_INSTANCE_OFF) + light_id * PT_INST_WORDS, q.y, q.z, hit.p, &ldir, &light_pdf);
+                    light_sample(s, bu(s, PT_HDR_INSTANCE_OFF) + light_id * PT_INST_WORDS, (uint32_t)fi, q.y, q.z, hit.p, &ldir, &light_pdf);
                     light_pdf = light_pdf * pick_pdf;
                     if (light_pdf != 0.0f) {
                         F3 bsdf_wo = to_local(fr2, ldir);
@@ -398,7 +398,7 @@ PT_HD ShadeOutT<NL> stage_shade(const SceneView& s, const RenderParams& rp, uint
                             // (light_shape_hit: the very call nearest_light_hit makes per light — it kills a SUBSET of what the light-sample kernel
                             // would drop, which runs the light's box test first; PT_AMD_NO_ONE_LIGHT switches this off and the GPU tests compare the two)
                             Hit lh;
-                            if (!light_shape_hit(s, bu(s, PT_HDR_INSTANCE_OFF) + light_id * PT_INST_WORDS, ray.o, ray.d, &lh)) for (int k = 0; k < NL; ++k) ray.factor[k] = 0.0f;
+                            if (!light_shape_hit(s, bu(s, PT_HDR_INSTANCE_OFF) + light_id * PT_INST_WORDS, 0u, ray.o, ray.d, &lh)) for (int k = 0; k < NL; ++k) ray.factor[k] = 0.0f;
                         }
                     }
                 }
@@ -585,7 +585,7 @@ PT_HD ShadeOutT<1> stage_medium_surface(const SceneView& s, const RenderParams& 
                     const float fi = pt_clamp((float)n_lights * x, 0.0f, (float)n_lights - 1.0f);
                     const uint32_t light_id = bu(s, bu(s, PT_HDR_LIGHT_OFF) + (uint32_t)fi);
                     F3 ldir; float light_pdf;
-                    light_sample(s, bu(s, PT_HDR_INSTANCE_OFF) + light_id * PT_INST_WORDS, q.y, q.z, hit.p, &ldir, &light_pdf);
+                    light_sample(s, bu(s, PT_HDR_INSTANCE_OFF) + light_id * PT_INST_WORDS, (uint32_t)fi, q.y, q.z, hit.p, &ldir, &light_pdf);
                     light_pdf = light_pdf * (1.0f / (float)n_lights);
                     if (light_pdf != 0.0f) {
                         const F3 bsdf_wo = to_local(fr2, ldir);

@@ -111,6 +111,11 @@ class RenderDesc(C.Structure):
                 ("medium_aware", C.c_uint32)]
 
 
+class AdaptiveDesc(C.Structure):
+    """pt_adaptive_desc (include/pt_adaptive.h): the ceiling, the samples per round, the target error."""
+    _fields_ = [("max_samples", C.c_uint32), ("step", C.c_uint32), ("rel_error", C.c_float), ("abs_error", C.c_float)]
+
+
 class Profile(C.Structure):
     _fields_ = [("bounce_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("light_rays", C.c_uint64),
                 ("camera_rays", C.c_uint64), ("env_hits", C.c_uint64), ("seconds", C.c_double),
@@ -224,6 +229,9 @@ class Library:
         self._curve_eval = bind("curve_eval", C.c_int32, [vp, u32, sz, fpp, fpp])
         # include/pt_debug.h (not the oracle's boundary: the reference cannot sample an emissive mesh face)
         self._light_sample = bind("light_sample", C.c_int32, [vp, u32, sz, fpp, fpp, fpp, fpp], required=False)
+        # include/pt_adaptive.h (not the oracle's boundary either: the reference's tiled renderer has no adaptive sampling)
+        self._render_adaptive = bind("render_adaptive", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), fpp, C.POINTER(u32),
+                                                                    C.POINTER(C.c_double), C.POINTER(Profile)], required=False)
         self._device_info = bind("device_info", C.c_char_p, [], required=False)
         self._output_film = bind("output_film", C.c_int32, [C.POINTER(OutputDesc), fpp, C.POINTER(C.c_uint8), fpp], required=False)
         self._write_png = bind("write_png", C.c_int32, [C.c_char_p, u32, u32, C.POINTER(C.c_uint8), C.c_int32], required=False)
@@ -323,6 +331,20 @@ class Scene:
         prof = Profile()
         self.library.check(self.library._render(self.handle, C.byref(rd), _fp(film), C.byref(prof)))
         return film, prof
+
+    def render_adaptive(self, rd, max_samples, rel_error, abs_error=0.0, step=0, stats=False):
+        """pt_render_adaptive: rd.spp samples per pixel at least, max_samples at most, `step` more per round (0 = rd.spp) while a pixel or one of its
+        neighbours has not reached the target error.  Returns (film, counts[, stats], profile): counts [H,W] u32, stats [H,W,2] f64 (S1, S2)."""
+        if self.library._render_adaptive is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_adaptive entry" % (self.library.path, self.library.prefix))
+        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        counts = np.zeros((rd.height, rd.width), dtype=np.uint32)
+        st = np.zeros((rd.height, rd.width, 2), dtype=np.float64) if stats else None
+        ad = AdaptiveDesc(max_samples, step, rel_error, abs_error)
+        prof = Profile()
+        self.library.check(self.library._render_adaptive(self.handle, C.byref(rd), C.byref(ad), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                         st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, C.byref(prof)))
+        return (film, counts, st, prof) if stats else (film, counts, prof)
 
     def render_multi(self, rd, device_mask=0):
         """pt_render_multi: every device of the mask (0 = all) from one blocking call."""

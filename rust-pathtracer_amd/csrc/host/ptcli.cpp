@@ -3,12 +3,13 @@
 // output/<filename>.exr and .png through the film output stage (src/renderer/mod.rs:24-80).
 //
 //   ptcli [--config data/config.toml] [--scene FILE] [-n|--dry-run] [--stdout-log-level L] [--write-log-level L]
-//         [--root DIR] [--output-dir DIR] [--seed N] [--write-film]
+//         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
 // are looked up when they are not found from the working directory; --write-film also stores the raw XYZ film as
-// <filename>.npy for tools/compare_films.py.
+// <filename>.npy for tools/compare_films.py.  --adaptive REL renders every setting that has max_samples > min_samples with
+// pt_render_adaptive (include/pt_adaptive.h): min_samples to max_samples per pixel, relative error target REL.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -18,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "../../../include/pt_adaptive.h"
 #include "../../../include/pt_scene_file.h"
 
 namespace {
@@ -27,12 +29,13 @@ struct Options {
     bool has_scene = false, dry_run = false, write_film = false;
     uint32_t hero = 0;   // --hero-wavelengths: 0 = as the render settings say (1)
     uint64_t seed = 1;
+    float adaptive = -1.0f;   // --adaptive REL: the relative error target; < 0 = off
 };
 
 int usage(const char* msg) {
     if (msg) fprintf(stderr, "error: %s\n", msg);
     fprintf(stderr, "usage: ptcli [--config FILE] [--scene FILE] [-n|--dry-run] [--stdout-log-level LEVEL] [--write-log-level LEVEL]\n"
-                    "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4]\n");
+                    "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL]\n");
     return 2;
 }
 
@@ -67,6 +70,12 @@ int main(int argc, char** argv) {
         else if (a == "--seed") { if (!value(&v)) return usage("--seed needs a value"); o.seed = strtoull(v.c_str(), nullptr, 10); }
         else if (a == "--write-film") o.write_film = true;
         else if (a == "--hero-wavelengths") { if (!value(&v)) return usage("--hero-wavelengths needs a value"); o.hero = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
+        else if (a == "--adaptive") {
+            if (!value(&v)) return usage("--adaptive needs a value");
+            char* end = nullptr;
+            o.adaptive = strtof(v.c_str(), &end);
+            if (end == v.c_str() || *end || !(o.adaptive >= 0.0f)) return usage("--adaptive needs a relative error >= 0");
+        }
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
     }
@@ -109,14 +118,45 @@ int main(int argc, char** argv) {
             if (o.hero) rd.hero_wavelengths = o.hero;   // engine extension (not in the reference's files): 4 wavelengths per path
             std::vector<float> film((size_t)rd.width * rd.height * 4);
             pt_profile prof;
-            printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
-            if (pt_render(scene, &rd, film.data(), &prof) != PT_OK) { fprintf(stderr, "pt_render: %s\n", pt_last_error()); rc = 1; break; }
+            // --adaptive: min_samples .. max_samples per pixel (pt_render_adaptive) where the setting gives a range and the renderer sums in phases of 10
+            bool adaptive = o.adaptive >= 0.0f;
+            pt_adaptive_desc ad = {0u, 0u, o.adaptive, 0.0f};
+            if (adaptive) {
+                uint32_t tw = 0, th = 0;
+                if (pt_config_renderer(config, &tw, &th) == PT_RENDERER_NAIVE) {
+                    if (warnings) fprintf(stderr, "warning: --adaptive: render settings %u use the Naive renderer; rendering %u spp everywhere\n", i, rd.spp);
+                    adaptive = false;
+                } else if (rs.max_samples < 0 || (uint32_t)rs.max_samples <= rd.spp) {
+                    if (warnings) fprintf(stderr, "warning: --adaptive: render settings %u have no max_samples > min_samples; rendering %u spp everywhere\n", i, rd.spp);
+                    adaptive = false;
+                } else {
+                    const uint32_t lo = (rd.spp + 9u) / 10u * 10u, hi = ((uint32_t)rs.max_samples + 9u) / 10u * 10u;
+                    if ((lo != rd.spp || hi != (uint32_t)rs.max_samples) && warnings)
+                        fprintf(stderr, "warning: --adaptive: samples %u..%d rounded up to %u..%u (multiples of 10)\n", rd.spp, rs.max_samples, lo, hi);
+                    rd.spp = lo; ad.max_samples = hi;
+                }
+            }
+            std::vector<uint32_t> counts(adaptive ? (size_t)rd.width * rd.height : 0);
+            uint64_t samples = (uint64_t)rd.width * rd.height * rd.spp;
+            if (adaptive) {
+                printf("rendering %ux%u, %u..%u spp (adaptive, relative error %g), max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, ad.max_samples,
+                       (double)ad.rel_error, rd.max_bounces, rd.light_samples);
+                if (pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), nullptr, &prof) != PT_OK) { fprintf(stderr, "pt_render_adaptive: %s\n", pt_last_error()); rc = 1; break; }
+                uint32_t lo = 0xffffffffu, hi = 0;
+                samples = 0;
+                for (uint32_t c : counts) { samples += c; lo = c < lo ? c : lo; hi = c > hi ? c : hi; }
+                printf("adaptive: %.2f samples per pixel on average, min %u, max %u, %llu rounds\n", (double)samples / (double)counts.size(), lo, hi,
+                       (unsigned long long)prof.kernel_launches[5]);
+            } else {
+                printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
+                if (pt_render(scene, &rd, film.data(), &prof) != PT_OK) { fprintf(stderr, "pt_render: %s\n", pt_last_error()); rc = 1; break; }
+            }
             // Profile::pretty_print (src/profile.rs:20-34)
             const double total = (double)(prof.camera_rays + prof.bounce_rays + prof.shadow_rays + prof.light_rays);
             printf("took %.3fs\n", prof.seconds);
             printf("%llu camera rays, %llu bounce rays, %llu shadow rays, %llu light rays, %llu environment hits\n", (unsigned long long)prof.camera_rays,
                    (unsigned long long)prof.bounce_rays, (unsigned long long)prof.shadow_rays, (unsigned long long)prof.light_rays, (unsigned long long)prof.env_hits);
-            printf("%.1f rays per second, %.3f Msamples/s\n", total / prof.seconds, (double)rd.width * rd.height * rd.spp / prof.seconds * 1e-6);
+            printf("%.1f rays per second, %.3f Msamples/s\n", total / prof.seconds, (double)samples / prof.seconds * 1e-6);
             pt_config_output_desc(config, i, 1.0f, &od);
             std::vector<uint8_t> rgba((size_t)rd.width * rd.height * 4);
             std::vector<float> linear((size_t)rd.width * rd.height * 3);

@@ -20,8 +20,10 @@
 #include <vector>
 
 #include "pt_kernels.h"   /* first: it switches on the wave-level device code of pt_device.h */
+#include "../../include/pt_adaptive.h"
 #include "../../include/pt_api.h"
 #include "../../include/pt_debug.h"
+#include "pt_adaptive_select.h"
 #include "pt_error.h"
 #include "pt_plan.h"
 #include "pt_scene_host.h"
@@ -106,6 +108,79 @@ __global__ void __launch_bounds__(kBlock) k_probe_numerics(int which, uint32_t n
     }
 }
 
+// ---- adaptive sampling (include/pt_adaptive.h): one round's decision and the stable compaction of the next pixel list.
+// mark: every pixel of the round's list takes the list's count and its decision (the byte image was cleared before the launch, so it marks exactly
+// the pixels of this list that are not converged)
+__global__ void __launch_bounds__(kBlock) k_adaptive_mark(const uint32_t* __restrict__ list, uint32_t n, uint32_t count, const double* __restrict__ stats,
+                                                         float rel_error, float abs_error, uint32_t* __restrict__ counts, uint8_t* __restrict__ unconverged) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t p = list[i];
+        counts[p] = count;
+        unconverged[p] = adaptive_unconverged(count, stats[2 * (size_t)p], stats[2 * (size_t)p + 1], rel_error, abs_error) ? 1u : 0u;
+    }
+}
+// keep: one list entry per thread; workgroup b writes how many of its kBlock entries stay (wave ballots), block_counts[b]
+__global__ void __launch_bounds__(kBlock) k_adaptive_keep(const uint32_t* __restrict__ list, uint32_t n, uint32_t count, uint32_t max_samples,
+                                                         const uint8_t* __restrict__ unconverged, uint32_t width, uint32_t height, uint32_t* __restrict__ block_counts) {
+    __shared__ uint32_t wave_kept[kBlock / 64];
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const bool keep = i < n && adaptive_keep(unconverged, width, height, list[i], count, max_samples);
+    const unsigned long long m = __ballot(keep);
+    if (lane_id() == 0) wave_kept[threadIdx.x / 64] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t kept = 0;
+        for (int w = 0; w < kBlock / 64; ++w) kept += wave_kept[w];
+        block_counts[blockIdx.x] = kept;
+    }
+}
+// scan: one workgroup turns the nb block counts into exclusive offsets in place and writes the total behind them (block_counts[nb])
+__global__ void __launch_bounds__(kBlock) k_adaptive_scan(uint32_t* __restrict__ block_counts, uint32_t nb) {
+    __shared__ uint32_t sum[kBlock];
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < nb; base += kBlock) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < nb ? block_counts[i] : 0u;
+        sum[threadIdx.x] = v;
+        __syncthreads();
+        for (uint32_t d = 1; d < (uint32_t)kBlock; d <<= 1) {   // (inclusive Hillis-Steele scan of the chunk)
+            const uint32_t t = threadIdx.x >= d ? sum[threadIdx.x - d] : 0u;
+            __syncthreads();
+            sum[threadIdx.x] += t;
+            __syncthreads();
+        }
+        if (i < nb) block_counts[i] = carry + sum[threadIdx.x] - v;
+        carry += sum[kBlock - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) block_counts[nb] = carry;
+}
+// scatter: the kept entries in list order — workgroup offset, then the waves before this one, then the lanes below this one
+__global__ void __launch_bounds__(kBlock) k_adaptive_scatter(const uint32_t* __restrict__ list, uint32_t n, uint32_t count, uint32_t max_samples,
+                                                            const uint8_t* __restrict__ unconverged, uint32_t width, uint32_t height,
+                                                            const uint32_t* __restrict__ offsets, uint32_t* __restrict__ next) {
+    __shared__ uint32_t wave_kept[kBlock / 64];
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const bool keep = i < n && adaptive_keep(unconverged, width, height, list[i], count, max_samples);
+    const unsigned long long m = __ballot(keep);
+    if (lane_id() == 0) wave_kept[threadIdx.x / 64] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (keep) {
+        uint32_t o = offsets[blockIdx.x];
+        for (uint32_t w = 0; w < threadIdx.x / 64; ++w) o += wave_kept[w];
+        next[o + (uint32_t)__popcll(m & ((1ull << lane_id()) - 1ull))] = list[i];
+    }
+}
+// finish: every pixel of the film divided by its own count (pt_render's division by spp, stage_accumulate_pixel), W = 0
+__global__ void __launch_bounds__(kBlock) k_adaptive_finish(uint32_t n_pixels, const uint32_t* __restrict__ counts, float* __restrict__ film) {
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_pixels; p += gridDim.x * blockDim.x) {
+        float4* px = reinterpret_cast<float4*>(film) + p;
+        const float4 v = *px;
+        const float c = (float)counts[p];
+        *px = make_float4(v.x / c, v.y / c, v.z / c, 0.0f);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 // A device allocation that is freed on every way out of its scope (the probes below return early on any HIP error).
 struct DevBuf {
@@ -131,6 +206,18 @@ struct DeviceBuffers {
         hipFree(paths_a); hipFree(paths_b); hipFree(hits); hipFree(shadow); hipFree(pixels); hipFree(counts); hipFree(energy); hipFree(block_stats); hipFree(park);
         hipFree(unit_counters);
         *this = DeviceBuffers();
+    }
+};
+// pt_render_adaptive: per film pixel its count, (S1, S2) and the unconverged byte; the round's pixel list and the next; the keep kernel's per-workgroup
+// counts, scanned in place, with the total behind them
+struct AdaptiveBuffers {
+    size_t pixels = 0;
+    uint32_t *counts = nullptr, *lists[2] = {nullptr, nullptr}, *block_counts = nullptr;
+    double* stats = nullptr;
+    uint8_t* unconverged = nullptr;
+    void release() {
+        hipFree(counts); hipFree(lists[0]); hipFree(lists[1]); hipFree(block_counts); hipFree(stats); hipFree(unconverged);
+        *this = AdaptiveBuffers();
     }
 };
 
@@ -160,6 +247,7 @@ struct pt_scene {
     uint32_t lacks = 0; // PT_SCENE_* bits: what the scene does not hold (kernel forms without it)
     int device = 0, num_cus = 0;
     DeviceBuffers buf;
+    AdaptiveBuffers adaptive;        // pt_render_adaptive's, kept between calls like buf
     std::vector<hipEvent_t> events;  // pairs (start, stop), grown on demand
     float* film_cache = nullptr;     // pt_render's device film, kept between calls
     size_t film_cache_bytes = 0;
@@ -227,6 +315,21 @@ pt_status ensure_buffers(pt_scene* sc, uint32_t capacity, uint32_t light_samples
     return PT_OK;
 }
 
+pt_status ensure_adaptive_buffers(pt_scene* sc, size_t n_pixels) {
+    AdaptiveBuffers& a = sc->adaptive;
+    if (a.pixels >= n_pixels) return PT_OK;
+    a.release();
+    const size_t blocks = (n_pixels + kBlock - 1) / kBlock;
+    HIP_TRY(hipMalloc(&a.counts, sizeof(uint32_t) * n_pixels));
+    HIP_TRY(hipMalloc(&a.lists[0], sizeof(uint32_t) * n_pixels));
+    HIP_TRY(hipMalloc(&a.lists[1], sizeof(uint32_t) * n_pixels));
+    HIP_TRY(hipMalloc(&a.block_counts, sizeof(uint32_t) * (blocks + 1)));
+    HIP_TRY(hipMalloc(&a.stats, sizeof(double) * 2 * n_pixels));
+    HIP_TRY(hipMalloc(&a.unconverged, n_pixels));
+    a.pixels = n_pixels;
+    return PT_OK;
+}
+
 template <typename K, typename... Args>
 void launch(K kernel, uint32_t lds_bytes, int grid, hipStream_t stream, Args... args) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds_bytes, stream, args...);
@@ -240,7 +343,46 @@ uint32_t env_u32(const char* name, uint32_t dflt) {
 // the value a tuning field stands for (0 = "the default" in the struct)
 uint32_t tuned(uint32_t value, uint32_t dflt) { return value ? value : dflt; }
 
-pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hipStream_t stream, pt_profile* profile) {
+// The rounds of pt_render_adaptive (include/pt_adaptive.h) on render_impl's pass loop `run(list, n, first_sample, sample_count, stats)`:
+// round 0 renders samples [0, spp) of the n0 pixels in lists[0], every later round the next `step` samples of the pixels the round before kept.  The one
+// read-back of a round is the length of the next list (4 bytes): it plans that round's passes.
+template <typename RunPasses>
+pt_status adaptive_rounds(pt_scene* sc, const pt_render_desc& rd, const pt_adaptive_desc& ad, hipStream_t stream, float* d_film, uint32_t n0, RunPasses&& run,
+                          uint32_t* rounds) {
+    AdaptiveBuffers& a = sc->adaptive;
+    const uint32_t film_pixels = rd.width * rd.height;
+    const int small_grid = sc->num_cus * 4;
+    uint32_t n = n0, c = 0, len = rd.spp, cur = 0;
+    for (*rounds = 0;;) {
+        pt_status st = run(a.lists[cur], n, c, len, a.stats);
+        if (st != PT_OK) return st;
+        c += len;
+        ++*rounds;
+        HIP_TRY(hipMemsetAsync(a.unconverged, 0, film_pixels, stream));
+        hipLaunchKernelGGL(k_adaptive_mark, dim3(small_grid), dim3(kBlock), 0, stream, a.lists[cur], n, c, a.stats, ad.rel_error, ad.abs_error, a.counts, a.unconverged);
+        if (c >= ad.max_samples) break;
+        const uint32_t nb = (n + kBlock - 1) / kBlock;
+        hipLaunchKernelGGL(k_adaptive_keep, dim3(nb), dim3(kBlock), 0, stream, a.lists[cur], n, c, ad.max_samples, a.unconverged, rd.width, rd.height, a.block_counts);
+        hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(kBlock), 0, stream, a.block_counts, nb);
+        hipLaunchKernelGGL(k_adaptive_scatter, dim3(nb), dim3(kBlock), 0, stream, a.lists[cur], n, c, ad.max_samples, a.unconverged, rd.width, rd.height,
+                           a.block_counts, a.lists[cur ^ 1u]);
+        HIP_TRY(hipGetLastError());
+        uint32_t next = 0;
+        HIP_TRY(hipMemcpyAsync(&next, a.block_counts + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (next == 0) break;
+        n = next;
+        cur ^= 1u;
+        len = ad.step < ad.max_samples - c ? ad.step : ad.max_samples - c;
+    }
+    hipLaunchKernelGGL(k_adaptive_finish, dim3(small_grid), dim3(kBlock), 0, stream, film_pixels, a.counts, d_film);
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+
+// Set-up (kernel forms, queues, launch configuration) and one pass loop over a device pixel list and a sample range: pt_render runs the loop once over its
+// shard's pixels; with `adaptive` (pt_render_adaptive, its arguments checked) adaptive_rounds runs it once per round.
+pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hipStream_t stream, pt_profile* profile, const pt_adaptive_desc* adaptive = nullptr) {
     if (!sc || !rdp || !d_film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     pt_render_desc rd;
     std::string err;
@@ -251,7 +393,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     const pt_tuning& tn = sc->tuning;
     uint32_t capacity = tuned(tn.batch_slots, 1u << 27);  // path slots per pass (128 Mi ~ 32 GB of queues of the 288 GB; tools/sweep.sh)
     if (capacity < 1024) capacity = 1024;
-    uint64_t want = (uint64_t)pixels.size() * rd.sample_count;
+    uint64_t want = (uint64_t)pixels.size() * (adaptive ? (adaptive->step > rd.spp ? adaptive->step : rd.spp) : rd.sample_count);   // (the longest pass of a round)
     if (want < capacity) capacity = (uint32_t)(want ? want : 1);
     const uint32_t blocks_per_cu = tuned(tn.blocks_per_cu, 64);
     if (blocks_per_cu > 1024) return fail(PT_ERR_INVALID_ARGUMENT, "pt_tuning::blocks_per_cu (PT_AMD_BLOCKS_PER_CU) must be in 1..1024");
@@ -273,7 +415,12 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     pt_status st = ensure_buffers(sc, capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, (hero || rd.medium_aware) ? 4u : 1u, park_block);
     if (st != PT_OK) return st;
     DeviceBuffers& b = sc->buf;
-    if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(b.pixels, pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
+    if (adaptive) {   // (round 0's list: every pixel of the film in shard_pixels' order)
+        st = ensure_adaptive_buffers(sc, (size_t)rd.width * rd.height);
+        if (st != PT_OK) return st;
+        HIP_TRY(hipMemcpyAsync(sc->adaptive.lists[0], pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(sc->adaptive.stats, 0, sizeof(double) * 2 * pixels.size(), stream));
+    } else if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(b.pixels, pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(d_film, 0, sizeof(float) * 4 * (size_t)rd.width * rd.height, stream));
     HIP_TRY(hipMemsetAsync(b.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));
 
@@ -282,8 +429,9 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     rp.seed = rd.seed; rp.width = rd.width; rp.height = rd.height;
     rp.min_bounces = rd.min_bounces; rp.max_bounces = rd.max_bounces; rp.light_samples = rd.light_samples; rp.only_direct = rd.only_direct;
     rp.wavelength_lo = rd.wavelength_lo; rp.wavelength_span = rd.wavelength_hi - rd.wavelength_lo;
-    rp.spp = rd.spp; rp.range_end = rd.first_sample + rd.sample_count;
-    rp.normalize = (rd.first_sample == 0 && rd.sample_count == rd.spp) ? 1u : 0u;
+    // (an adaptive render's film holds running sums until k_adaptive_finish divides each pixel by its own count; its rounds end on phase boundaries)
+    rp.spp = adaptive ? adaptive->max_samples : rd.spp; rp.range_end = rd.first_sample + rd.sample_count;
+    rp.normalize = (!adaptive && rd.first_sample == 0 && rd.sample_count == rd.spp) ? 1u : 0u;
     rp.phase = rd.phase_samples;
     rp.camera = pth::camera_params(sc->host.cameras[rd.camera_index], (float)rd.width / (float)rd.height);
     rp.energy_stride = b.capacity;
@@ -401,45 +549,58 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
         stage_launches[stage]++;
     };
 
-    // the planner's capacity is in items; segments round up, so plan with what surely fits
-    std::vector<pth::Pass> passes = pth::plan_passes((uint32_t)pixels.size(), rd.first_sample, rd.sample_count, capacity, rd.phase_samples);
     uint64_t camera_rays = 0, accumulated_pixels = 0;
-    for (const pth::Pass& pass : passes) {
-        accumulated_pixels += pass.pixel_count;
-        rp.chunk_pixels = pass.pixel_count; rp.first_sample = pass.first_sample; rp.pass_samples = pass.sample_count;
-        uint32_t n = pass.pixel_count * pass.sample_count;
-        if (n > b.capacity) return fail(PT_ERR_DEVICE, "internal: a pass of " + std::to_string(n) + " slots exceeds the queue capacity " + std::to_string(b.capacity));
-        uint32_t seg_cap = segment_capacity(n, grid);
-        camera_rays += n;
-        const uint32_t* d_px = b.pixels + pass.pixel_begin;
-        if (park_dynamic) {
-            HIP_TRY(hipMemsetAsync(b.unit_counters, 0, sizeof(uint32_t) * kUnitCounters, stream));
-            // (round-5 advisor) an event of its own behind the stream's non-kernel work, charged to no stage: k_generate's time begins here, not at the end of the previous pass
-            if (events_ok) { events_ok = event_at(event_stage.size() + 1); if (events_ok) event_stage.push_back(-1); }
+    // The pass loop: samples [first_sample, first_sample + sample_count) of the n pixels of the device list d_list; stats (adaptive rounds): S1 / S2 too
+    auto run_passes = [&](const uint32_t* d_list, uint32_t n_list, uint32_t first_sample, uint32_t sample_count, double* d_stats) -> pt_status {
+        // (a later adaptive round: the stream's work since the previous accumulate — the round's decision and compaction — is charged to no stage)
+        if (camera_rays != 0 && events_ok) { events_ok = event_at(event_stage.size() + 1); if (events_ok) event_stage.push_back(-1); }
+        rp.range_end = first_sample + sample_count;
+        // the planner's capacity is in items; segments round up, so plan with what surely fits
+        std::vector<pth::Pass> passes = pth::plan_passes(n_list, first_sample, sample_count, capacity, rd.phase_samples);
+        for (const pth::Pass& pass : passes) {
+            accumulated_pixels += pass.pixel_count;
+            rp.chunk_pixels = pass.pixel_count; rp.first_sample = pass.first_sample; rp.pass_samples = pass.sample_count;
+            uint32_t n = pass.pixel_count * pass.sample_count;
+            if (n > b.capacity) return fail(PT_ERR_DEVICE, "internal: a pass of " + std::to_string(n) + " slots exceeds the queue capacity " + std::to_string(b.capacity));
+            uint32_t seg_cap = segment_capacity(n, grid);
+            camera_rays += n;
+            const uint32_t* d_px = d_list + pass.pixel_begin;
+            if (park_dynamic) {
+                HIP_TRY(hipMemsetAsync(b.unit_counters, 0, sizeof(uint32_t) * kUnitCounters, stream));
+                // (round-5 advisor) an event of its own behind the stream's non-kernel work, charged to no stage: k_generate's time begins here, not at the end of the previous pass
+                if (events_ok) { events_ok = event_at(event_stage.size() + 1); if (events_ok) event_stage.push_back(-1); }
+            }
+            timed(ST_GENERATE, [&] {
+                if (hero) hipLaunchKernelGGL(k_generate<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, qa, b.energy, n, seg_cap, live[0]);
+                else hipLaunchKernelGGL(k_generate<1>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, qa, b.energy, n, seg_cap, live[0]);
+            });
+            for (uint32_t bounce = 0; bounce < bounce_limit; ++bounce) {
+                Queue qin = (bounce & 1) ? qb : qa, qout = (bounce & 1) ? qa : qb;
+                uint32_t *cin = live[bounce & 1], *cout = live[(bounce + 1) & 1];
+                // kernel variant = staging mode (PT_LDS_*) x traversal form x wavelengths per path (pt_launch.h)
+                if (park_dynamic) cfg.unit_counter = b.unit_counters + 2 * bounce;
+                // (a marked path segment — it left the scene's one certified convex body outward — skips that instance: records the vertex kernel wrote, so from bounce 1 on; never
+                // in the medium-aware walk, whose vertex code makes no marks)
+                cfg.path_marks = (bounce > 0 && !rd.medium_aware && (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_CONVEX)) ? sc->host.blob[PT_HDR_CONVEX_INST] : 0u;
+                if (!cfg.fuse) timed(ST_EXTEND, [&] { launch_extend(cfg, trav_form, sargs, qin, qh, seg_cap, cin, b.park); });
+                if (park_dynamic) cfg.unit_counter = b.unit_counters + 2 * bounce + 1;
+                timed(ST_SHADE, [&] { launch_shade(cfg, hero ? 4 : 1, shade_form, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats); });
+                if (rd.light_samples > 0)   // (shade_form FULL = the scene can produce environment rays)
+                    timed(ST_SHADOW, [&] { launch_shadow(cfg, trav_form, hero ? 4 : 1, shade_form == PT_SHADE_FULL || shade_form == PT_SHADE_MEDIUM, sargs, rd.light_samples, qs, b.energy, b.capacity, rp.live_list ? (seg_cap | kShadowListed) : seg_cap, nshadow, b.park, qh); });
+            }
+            timed(ST_ACCUMULATE, [&] {
+                if (d_stats && hero) hipLaunchKernelGGL(k_accumulate_stats<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film, d_stats);
+                else if (d_stats) hipLaunchKernelGGL(k_accumulate_stats<1>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film, d_stats);
+                else if (hero) hipLaunchKernelGGL(k_accumulate<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film);
+                else hipLaunchKernelGGL(k_accumulate<1>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film);
+            });
         }
-        timed(ST_GENERATE, [&] {
-            if (hero) hipLaunchKernelGGL(k_generate<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, qa, b.energy, n, seg_cap, live[0]);
-            else hipLaunchKernelGGL(k_generate<1>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, qa, b.energy, n, seg_cap, live[0]);
-        });
-        for (uint32_t bounce = 0; bounce < bounce_limit; ++bounce) {
-            Queue qin = (bounce & 1) ? qb : qa, qout = (bounce & 1) ? qa : qb;
-            uint32_t *cin = live[bounce & 1], *cout = live[(bounce + 1) & 1];
-            // kernel variant = staging mode (PT_LDS_*) x traversal form x wavelengths per path (pt_launch.h)
-            if (park_dynamic) cfg.unit_counter = b.unit_counters + 2 * bounce;
-            // (a marked path segment — it left the scene's one certified convex body outward — skips that instance: records the vertex kernel wrote, so from bounce 1 on; never
-            // in the medium-aware walk, whose vertex code makes no marks)
-            cfg.path_marks = (bounce > 0 && !rd.medium_aware && (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_CONVEX)) ? sc->host.blob[PT_HDR_CONVEX_INST] : 0u;
-            if (!cfg.fuse) timed(ST_EXTEND, [&] { launch_extend(cfg, trav_form, sargs, qin, qh, seg_cap, cin, b.park); });
-            if (park_dynamic) cfg.unit_counter = b.unit_counters + 2 * bounce + 1;
-            timed(ST_SHADE, [&] { launch_shade(cfg, hero ? 4 : 1, shade_form, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats); });
-            if (rd.light_samples > 0)   // (shade_form FULL = the scene can produce environment rays)
-                timed(ST_SHADOW, [&] { launch_shadow(cfg, trav_form, hero ? 4 : 1, shade_form == PT_SHADE_FULL || shade_form == PT_SHADE_MEDIUM, sargs, rd.light_samples, qs, b.energy, b.capacity, rp.live_list ? (seg_cap | kShadowListed) : seg_cap, nshadow, b.park, qh); });
-        }
-        timed(ST_ACCUMULATE, [&] {
-            if (hero) hipLaunchKernelGGL(k_accumulate<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film);
-            else hipLaunchKernelGGL(k_accumulate<1>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film);
-        });
-    }
+        return PT_OK;
+    };
+    uint32_t rounds = 0;
+    st = adaptive ? adaptive_rounds(sc, rd, *adaptive, stream, d_film, (uint32_t)pixels.size(), run_passes, &rounds)
+                  : run_passes(b.pixels, (uint32_t)pixels.size(), rd.first_sample, rd.sample_count, nullptr);
+    if (st != PT_OK) return st;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     auto t1 = std::chrono::steady_clock::now();
@@ -464,6 +625,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
         profile->stage_items[6] = (uint64_t)cfg.park_block;   // threads per workgroup of the parked kernels when they ran in their big-workgroup form (pt_tuning::park_block), else 0
         profile->stage_items[7] = rp.camera_record;     // 1: k_generate wrote the camera vertex' lean record (7 of 16 words) and the first bounce's vertex kernel rebuilt the rest
         profile->stage_items[5] = c[BS_MEDIUM_DROPS];   // the medium-aware walk tracks four nested mediums: what a fifth level lost (0 = the walk is the reference's)
+        profile->kernel_launches[5] = rounds;           // pt_render_adaptive: its rounds (0 for pt_render)
     }
     return PT_OK;
 }
@@ -625,6 +787,7 @@ void pt_scene_destroy(pt_scene* sc) {
     if (sc->multi.valid) multi_release(sc->multi);
     hipSetDevice(sc->device);
     sc->buf.release();
+    sc->adaptive.release();
     hipFree(sc->d_blob); hipFree(sc->d_tex); hipFree(sc->film_cache);
     for (auto& e : sc->events) hipEventDestroy(e);
     delete sc;
@@ -634,20 +797,48 @@ pt_status pt_render_device(pt_scene* sc, const pt_render_desc* rd, void* film_de
     return render_impl(sc, rd, static_cast<float*>(film_device), static_cast<hipStream_t>(hip_stream), profile);
 }
 
-pt_status pt_render(pt_scene* sc, const pt_render_desc* rd, float* film, pt_profile* profile) {
-    if (!sc || !rd || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    if (rd->width == 0 || rd->height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
-    HIP_TRY(hipSetDevice(sc->device));
-    const size_t bytes = sizeof(float) * 4 * (size_t)rd->width * rd->height;
+static pt_status ensure_film_cache(pt_scene* sc, size_t bytes) {
     if (sc->film_cache_bytes < bytes) {   // the device film lives as long as the scene: a sequence of renders allocates it once
         if (sc->film_cache) hipFree(sc->film_cache);
         sc->film_cache = nullptr; sc->film_cache_bytes = 0;
         HIP_TRY(hipMalloc(&sc->film_cache, bytes));
         sc->film_cache_bytes = bytes;
     }
-    pt_status st = render_impl(sc, rd, sc->film_cache, nullptr, profile);
+    return PT_OK;
+}
+
+pt_status pt_render(pt_scene* sc, const pt_render_desc* rd, float* film, pt_profile* profile) {
+    if (!sc || !rd || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    if (rd->width == 0 || rd->height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t bytes = sizeof(float) * 4 * (size_t)rd->width * rd->height;
+    pt_status st = ensure_film_cache(sc, bytes);
+    if (st != PT_OK) return st;
+    st = render_impl(sc, rd, sc->film_cache, nullptr, profile);
     if (st != PT_OK) return st;
     HIP_TRY(hipMemcpy(film, sc->film_cache, bytes, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+pt_status pt_render_adaptive(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, float* film, uint32_t* sample_counts, double* stats,
+                             pt_profile* profile) {
+    if (!sc || !rdp || !adp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    pt_render_desc rd;
+    pt_adaptive_desc ad;
+    std::string err;
+    pt_status st = pth::normalize_adaptive_desc(*rdp, *adp, sample_counts != nullptr, (uint32_t)sc->host.cameras.size(), &rd, &ad, &err);
+    if (st != PT_OK) return fail(st, err);
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t n_pixels = (size_t)rd.width * rd.height;
+    st = ensure_film_cache(sc, sizeof(float) * 4 * n_pixels);
+    if (st != PT_OK) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    st = render_impl(sc, &rd, sc->film_cache, nullptr, profile, &ad);
+    if (st != PT_OK) return st;
+    HIP_TRY(hipMemcpy(film, sc->film_cache, sizeof(float) * 4 * n_pixels, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sample_counts, sc->adaptive.counts, sizeof(uint32_t) * n_pixels, hipMemcpyDeviceToHost));
+    if (stats) HIP_TRY(hipMemcpy(stats, sc->adaptive.stats, sizeof(double) * 2 * n_pixels, hipMemcpyDeviceToHost));
+    if (profile) profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (the whole call: set-up, rounds, read-backs)
     return PT_OK;
 }
 

@@ -1276,6 +1276,19 @@ __global__ void __launch_bounds__(kBlock) k_accumulate(RenderParams rp, const ui
         *px = make_float4(f[0], f[1], f[2], f[3]);
     }
 }
+// k_accumulate of an adaptive round (include/pt_adaptive.h): the same film sums, and each pixel's S1 / S2 (stats: two f64 per film pixel) in the same pass
+template <int NL>
+__global__ void __launch_bounds__(kBlock) k_accumulate_stats(RenderParams rp, const uint32_t* __restrict__ pixels, const float* __restrict__ energy,
+                                                            float* __restrict__ film, double* __restrict__ stats) {
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < rp.chunk_pixels; p += gridDim.x * blockDim.x) {
+        uint32_t pixel = pixels[p];
+        float4* px = reinterpret_cast<float4*>(film) + pixel;
+        float4 v = *px;
+        float f[4] = {v.x, v.y, v.z, v.w};
+        stage_accumulate_pixel<NL, true>(rp, energy, p, pixel, f, stats + 2 * (size_t)pixel);
+        *px = make_float4(f[0], f[1], f[2], f[3]);
+    }
+}
 
 // ---- probes (parity tests of single stages)
 template <int USE_LDS>

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/pt_adaptive.h"
 #include "../../include/pt_api.h"
 #include "pt_stages.h"
 
@@ -27,6 +28,10 @@ std::vector<Pass> plan_passes(uint32_t n_pixels, uint32_t first_sample, uint32_t
 ptd::CameraParams camera_params(const pt_camera& c, float aspect_ratio);
 
 bool normalize_render_desc(const pt_render_desc& in, uint32_t camera_count, pt_render_desc* out, std::string* error);
+// pt_render_adaptive's arguments (include/pt_adaptive.h), for the engine and the host emulation alike: PT_OK with the normalised render desc and
+// adaptive desc (step 0 -> spp), or PT_ERR_INVALID_ARGUMENT / PT_ERR_UNSUPPORTED with the reason in *error.
+pt_status normalize_adaptive_desc(const pt_render_desc& in, const pt_adaptive_desc& adaptive, bool has_sample_counts, uint32_t camera_count,
+                                  pt_render_desc* out, pt_adaptive_desc* adaptive_out, std::string* error);
 
 }  // namespace pth
 #endif

@@ -741,11 +741,14 @@ PT_HD void stage_shadow_item(const SceneView& s, uint32_t light_samples, const Q
 
 // ------------------------------------------------------------------------------------------------ accumulate
 // XYZColor::from(SingleWavelength) (math crate; pt.rs:614) and the film sums of tiled.rs:366-398.  With hero wavelengths
-// the sample's colour is the mean of the four wavelengths' XYZ.
-template <int NL>
-PT_HD void stage_accumulate_pixel(const RenderParams& rp, const float* energy, uint32_t p, uint32_t pixel, float* film_px) {
+// the sample's colour is the mean of the four wavelengths' XYZ.  STATS (adaptive sampling, include/pt_adaptive.h): the same pass also adds each
+// sample's Y term y — the value the film's Y sum adds — to the pixel's S1 += y and S2 += y * y, in f64 and in sample order (stats_px = S1, S2).
+template <int NL, bool STATS = false>
+PT_HD void stage_accumulate_pixel(const RenderParams& rp, const float* energy, uint32_t p, uint32_t pixel, float* film_px, double* stats_px = nullptr) {
     float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
     float f0 = film_px[0], f1 = film_px[1], f2 = film_px[2];
+    double s1 = 0.0, s2 = 0.0;
+    if (STATS) { s1 = stats_px[0]; s2 = stats_px[1]; }
     for (uint32_t s_local = 0; s_local < rp.pass_samples; ++s_local) {
         uint32_t sample = rp.first_sample + s_local;
         size_t slot = (size_t)s_local * rp.chunk_pixels + p;
@@ -759,6 +762,7 @@ PT_HD void stage_accumulate_pixel(const RenderParams& rp, const float* energy, u
             float xb, yb, zb;
             xyz_bar(lam[0] * 10.0f, &xb, &yb, &zb);
             t0 += e * xb; t1 += e * yb; t2 += e * zb;
+            if (STATS) { const double y = (double)(e * yb); s1 += y; s2 += y * y; }
         } else {
             float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
             for (int k = 0; k < NL; ++k) {
@@ -768,6 +772,7 @@ PT_HD void stage_accumulate_pixel(const RenderParams& rp, const float* energy, u
                 c0 += e * xb; c1 += e * yb; c2 += e * zb;
             }
             t0 += c0 / 4.0f; t1 += c1 / 4.0f; t2 += c2 / 4.0f;
+            if (STATS) { const double y = (double)(c1 / 4.0f); s1 += y; s2 += y * y; }
         }
         if ((sample + 1) % rp.phase == 0 || sample + 1 == rp.spp || sample + 1 == rp.range_end) {  // phases of 10, tiled.rs:347-361 (or of everything, naive.rs:82-103)
             f0 += t0; f1 += t1; f2 += t2;
@@ -779,6 +784,7 @@ PT_HD void stage_accumulate_pixel(const RenderParams& rp, const float* energy, u
         f0 /= n; f1 /= n; f2 /= n;
     }
     film_px[0] = f0; film_px[1] = f1; film_px[2] = f2; film_px[3] = 0.0f;
+    if (STATS) { stats_px[0] = s1; stats_px[1] = s2; }
 }
 
 }  // namespace ptd

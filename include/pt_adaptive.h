@@ -33,6 +33,14 @@ typedef struct pt_adaptive_desc {
 pt_status pt_render_adaptive(pt_scene* scene, const pt_render_desc* desc, const pt_adaptive_desc* adaptive,
                              float* film_xyzw, uint32_t* sample_counts, double* stats, pt_profile* profile);
 
+/* pt_render_adaptive on every device of device_mask, from one blocking call: the mask means what it means for pt_render_multi (0 = every visible
+ * device; a mask that names none is refused), and the call deals the film's tiles to the devices itself (desc->shard_count 0).  The rounds run in
+ * lockstep: after each round the devices' unconverged images are merged into the film-wide one, so film, sample_counts, stats
+ * and the number of rounds equal pt_render_adaptive's bit for bit, and the ray counters sum to its.  profile->kernel_seconds[5] is the set-up,
+ * [6] the rounds' exchanges plus the final gather.  With one device (no pt_tuning::multi_virtual, no PT_TUNE_MULTI_RCCL) it is pt_render_adaptive. */
+pt_status pt_render_adaptive_multi(pt_scene* scene, const pt_render_desc* desc, const pt_adaptive_desc* adaptive, uint64_t device_mask,
+                                   float* film_xyzw, uint32_t* sample_counts, double* stats, pt_profile* profile);
+
 #ifdef __cplusplus
 }
 #endif

@@ -232,6 +232,8 @@ class Library:
         # include/pt_adaptive.h (not the oracle's boundary either: the reference's tiled renderer has no adaptive sampling)
         self._render_adaptive = bind("render_adaptive", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), fpp, C.POINTER(u32),
                                                                     C.POINTER(C.c_double), C.POINTER(Profile)], required=False)
+        self._render_adaptive_multi = bind("render_adaptive_multi", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), C.c_uint64, fpp,
+                                                                                C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(Profile)], required=False)
         self._device_info = bind("device_info", C.c_char_p, [], required=False)
         self._output_film = bind("output_film", C.c_int32, [C.POINTER(OutputDesc), fpp, C.POINTER(C.c_uint8), fpp], required=False)
         self._write_png = bind("write_png", C.c_int32, [C.c_char_p, u32, u32, C.POINTER(C.c_uint8), C.c_int32], required=False)
@@ -344,6 +346,21 @@ class Scene:
         prof = Profile()
         self.library.check(self.library._render_adaptive(self.handle, C.byref(rd), C.byref(ad), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                          st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, C.byref(prof)))
+        return (film, counts, st, prof) if stats else (film, counts, prof)
+
+    def render_adaptive_multi(self, rd, max_samples, rel_error, abs_error=0.0, step=0, stats=False, device_mask=0):
+        """pt_render_adaptive_multi: render_adaptive on every device of the mask (0 = all) from one blocking call, its outputs bit for bit.
+        Returns (film, counts[, stats], profile) as render_adaptive does."""
+        if self.library._render_adaptive_multi is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_adaptive_multi entry" % (self.library.path, self.library.prefix))
+        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        counts = np.zeros((rd.height, rd.width), dtype=np.uint32)
+        st = np.zeros((rd.height, rd.width, 2), dtype=np.float64) if stats else None
+        ad = AdaptiveDesc(max_samples, step, rel_error, abs_error)
+        prof = Profile()
+        self.library.check(self.library._render_adaptive_multi(self.handle, C.byref(rd), C.byref(ad), C.c_uint64(device_mask), _fp(film),
+                                                               counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                               st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, C.byref(prof)))
         return (film, counts, st, prof) if stats else (film, counts, prof)
 
     def render_multi(self, rd, device_mask=0):

@@ -3,13 +3,14 @@
 // output/<filename>.exr and .png through the film output stage (src/renderer/mod.rs:24-80).
 //
 //   ptcli [--config data/config.toml] [--scene FILE] [-n|--dry-run] [--stdout-log-level L] [--write-log-level L]
-//         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL]
+//         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
 // are looked up when they are not found from the working directory; --write-film also stores the raw XYZ film as
 // <filename>.npy for tools/compare_films.py.  --adaptive REL renders every setting that has max_samples > min_samples with
-// pt_render_adaptive (include/pt_adaptive.h): min_samples to max_samples per pixel, relative error target REL.
+// pt_render_adaptive (include/pt_adaptive.h): min_samples to max_samples per pixel, relative error target REL.  --devices MASK renders every setting on
+// the devices of MASK (bit d = HIP device d, 0 = all) from one call: pt_render_multi, or pt_render_adaptive_multi with --adaptive.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -30,12 +31,14 @@ struct Options {
     uint32_t hero = 0;   // --hero-wavelengths: 0 = as the render settings say (1)
     uint64_t seed = 1;
     float adaptive = -1.0f;   // --adaptive REL: the relative error target; < 0 = off
+    bool multi = false;       // --devices MASK: the node calls (pt_render_multi / pt_render_adaptive_multi)
+    uint64_t device_mask = 0;
 };
 
 int usage(const char* msg) {
     if (msg) fprintf(stderr, "error: %s\n", msg);
     fprintf(stderr, "usage: ptcli [--config FILE] [--scene FILE] [-n|--dry-run] [--stdout-log-level LEVEL] [--write-log-level LEVEL]\n"
-                    "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL]\n");
+                    "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n");
     return 2;
 }
 
@@ -75,6 +78,13 @@ int main(int argc, char** argv) {
             char* end = nullptr;
             o.adaptive = strtof(v.c_str(), &end);
             if (end == v.c_str() || *end || !(o.adaptive >= 0.0f)) return usage("--adaptive needs a relative error >= 0");
+        }
+        else if (a == "--devices") {
+            if (!value(&v)) return usage("--devices needs a value");
+            char* end = nullptr;
+            o.device_mask = strtoull(v.c_str(), &end, 0);
+            if (end == v.c_str() || *end) return usage("--devices needs a device mask (bit d = HIP device d, 0 = all)");
+            o.multi = true;
         }
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
@@ -141,7 +151,9 @@ int main(int argc, char** argv) {
             if (adaptive) {
                 printf("rendering %ux%u, %u..%u spp (adaptive, relative error %g), max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, ad.max_samples,
                        (double)ad.rel_error, rd.max_bounces, rd.light_samples);
-                if (pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), nullptr, &prof) != PT_OK) { fprintf(stderr, "pt_render_adaptive: %s\n", pt_last_error()); rc = 1; break; }
+                const pt_status st = o.multi ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), nullptr, &prof)
+                                             : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), nullptr, &prof);
+                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive", pt_last_error()); rc = 1; break; }
                 uint32_t lo = 0xffffffffu, hi = 0;
                 samples = 0;
                 for (uint32_t c : counts) { samples += c; lo = c < lo ? c : lo; hi = c > hi ? c : hi; }
@@ -149,7 +161,8 @@ int main(int argc, char** argv) {
                        (unsigned long long)prof.kernel_launches[5]);
             } else {
                 printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
-                if (pt_render(scene, &rd, film.data(), &prof) != PT_OK) { fprintf(stderr, "pt_render: %s\n", pt_last_error()); rc = 1; break; }
+                const pt_status st = o.multi ? pt_render_multi(scene, &rd, o.device_mask, film.data(), &prof) : pt_render(scene, &rd, film.data(), &prof);
+                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.multi ? "pt_render_multi" : "pt_render", pt_last_error()); rc = 1; break; }
             }
             // Profile::pretty_print (src/profile.rs:20-34)
             const double total = (double)(prof.camera_rays + prof.bounce_rays + prof.shadow_rays + prof.light_rays);

@@ -11,7 +11,10 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <chrono>
+#include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <cstdio>
@@ -171,14 +174,29 @@ __global__ void __launch_bounds__(kBlock) k_adaptive_scatter(const uint32_t* __r
         next[o + (uint32_t)__popcll(m & ((1ull << lane_id()) - 1ull))] = list[i];
     }
 }
-// finish: every pixel of the film divided by its own count (pt_render's division by spp, stage_accumulate_pixel), W = 0
+// finish: every pixel of the film divided by its own count (pt_render's division by spp, stage_accumulate_pixel), W = 0.  A pixel of count 0 is
+// another device's (pt_render_adaptive_multi) and stays 0: the node's gather adds the films.  On one device every count is at least spp.
 __global__ void __launch_bounds__(kBlock) k_adaptive_finish(uint32_t n_pixels, const uint32_t* __restrict__ counts, float* __restrict__ film) {
     for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_pixels; p += gridDim.x * blockDim.x) {
+        const uint32_t n = counts[p];
+        if (n == 0u) continue;
         float4* px = reinterpret_cast<float4*>(film) + p;
         const float4 v = *px;
-        const float c = (float)counts[p];
+        const float c = (float)n;
         *px = make_float4(v.x / c, v.y / c, v.z / c, 0.0f);
     }
+}
+// the exchange of pt_render_adaptive_multi between the virtual devices of one physical device: dst |= src over two unconverged images of n bytes
+// (0 / 1 per pixel; each device marks only its own shard's pixels, so the OR is the film-wide image), 16 bytes per lane and the tail byte by byte
+__global__ void __launch_bounds__(kBlock) k_mask_or(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, size_t n) {
+    const size_t n16 = n / 16, stride = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint4* d = reinterpret_cast<uint4*>(dst);
+    const uint4* s = reinterpret_cast<const uint4*>(src);
+    for (size_t i = first; i < n16; i += stride) {
+        const uint4 a = d[i], b = s[i];
+        d[i] = make_uint4(a.x | b.x, a.y | b.y, a.z | b.z, a.w | b.w);
+    }
+    for (size_t i = n16 * 16 + first; i < n; i += stride) dst[i] = (uint8_t)(dst[i] | src[i]);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -343,16 +361,65 @@ uint32_t env_u32(const char* name, uint32_t dflt) {
 // the value a tuning field stands for (0 = "the default" in the struct)
 uint32_t tuned(uint32_t value, uint32_t dflt) { return value ? value : dflt; }
 
+// The worker threads of a node call (pt_render_adaptive_multi) meet here between the steps of a round.  The last one to arrive runs the step that needs
+// every device (the exchange, the stop decision) while the others wait.  A worker that fails calls stop(): every worker waiting or arriving later is released
+// with false, so that no thread enters a collective after another has failed, and the first error is kept for the caller.  (C++17: no std::barrier.)
+struct Lockstep {
+    std::mutex mu;
+    std::condition_variable cv;
+    int parties = 0, waiting = 0;
+    uint64_t generation = 0;
+    bool failed = false;
+    pt_status status = PT_OK;
+    std::string error;
+    void stop(pt_status st, const std::string& msg) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!failed) { failed = true; status = st; error = msg; }
+        cv.notify_all();
+    }
+    // `last`: run by the last worker to arrive, with every other one waiting (the lock held); its failure stops them all (message in g_error)
+    bool arrive(const std::function<pt_status()>& last) {
+        std::unique_lock<std::mutex> lk(mu);
+        if (failed) return false;
+        const uint64_t gen = generation;
+        if (++waiting == parties) {
+            waiting = 0;
+            const pt_status st = last();
+            if (st != PT_OK && !failed) { failed = true; status = st; error = g_error; }
+            ++generation;
+            cv.notify_all();
+            return !failed;
+        }
+        cv.wait(lk, [&] { return failed || generation != gen; });
+        return !failed;
+    }
+};
+
+// What the workers of pt_render_adaptive_multi share.  images[v]: virtual device v's unconverged image; merged[v]: the film-wide image its keep reads (the
+// image of the first virtual device on its physical device, where `exchange` merges them).  next[v]: the length of v's next list; total: their sum.
+struct NodeRounds {
+    Lockstep lock;
+    std::function<pt_status()> exchange;
+    std::vector<uint8_t*> images;
+    std::vector<const uint8_t*> merged;
+    std::vector<uint32_t> next;
+    uint64_t total = 0;
+    double exchange_seconds = 0.0;
+};
+
 // The rounds of pt_render_adaptive (include/pt_adaptive.h) on render_impl's pass loop `run(list, n, first_sample, sample_count, stats)`:
 // round 0 renders samples [0, spp) of the n0 pixels in lists[0], every later round the next `step` samples of the pixels the round before kept.  The one
-// read-back of a round is the length of the next list (4 bytes): it plans that round's passes.
+// read-back of a round is the length of the next list (4 bytes): it plans that round's passes.  With `node` (pt_render_adaptive_multi, worker v) the
+// rounds run in lockstep with the other devices: after the marks the images are merged into the film-wide one that every device's keep reads, and the
+// rounds end when no device's next list holds a pixel.  A device whose list is empty goes on taking part with an all-zero image.
 template <typename RunPasses>
 pt_status adaptive_rounds(pt_scene* sc, const pt_render_desc& rd, const pt_adaptive_desc& ad, hipStream_t stream, float* d_film, uint32_t n0, RunPasses&& run,
-                          uint32_t* rounds) {
+                          uint32_t* rounds, NodeRounds* node, int v) {
     AdaptiveBuffers& a = sc->adaptive;
     const uint32_t film_pixels = rd.width * rd.height;
     const int small_grid = sc->num_cus * 4;
     uint32_t n = n0, c = 0, len = rd.spp, cur = 0;
+    const auto stopped = [] { return fail(PT_ERR_DEVICE, "stopped: another device of the node failed"); };
     for (*rounds = 0;;) {
         pt_status st = run(a.lists[cur], n, c, len, a.stats);
         if (st != PT_OK) return st;
@@ -361,16 +428,31 @@ pt_status adaptive_rounds(pt_scene* sc, const pt_render_desc& rd, const pt_adapt
         HIP_TRY(hipMemsetAsync(a.unconverged, 0, film_pixels, stream));
         hipLaunchKernelGGL(k_adaptive_mark, dim3(small_grid), dim3(kBlock), 0, stream, a.lists[cur], n, c, a.stats, ad.rel_error, ad.abs_error, a.counts, a.unconverged);
         if (c >= ad.max_samples) break;
-        const uint32_t nb = (n + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(k_adaptive_keep, dim3(nb), dim3(kBlock), 0, stream, a.lists[cur], n, c, ad.max_samples, a.unconverged, rd.width, rd.height, a.block_counts);
-        hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(kBlock), 0, stream, a.block_counts, nb);
-        hipLaunchKernelGGL(k_adaptive_scatter, dim3(nb), dim3(kBlock), 0, stream, a.lists[cur], n, c, ad.max_samples, a.unconverged, rd.width, rd.height,
-                           a.block_counts, a.lists[cur ^ 1u]);
-        HIP_TRY(hipGetLastError());
+        const uint8_t* unconverged = a.unconverged;
+        if (node) {   // the exchange: every device has marked its own pixels
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (!node->lock.arrive(node->exchange)) return stopped();
+            unconverged = node->merged[v];
+        }
         uint32_t next = 0;
-        HIP_TRY(hipMemcpyAsync(&next, a.block_counts + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (next == 0) break;
+        if (n > 0) {
+            const uint32_t nb = (n + kBlock - 1) / kBlock;
+            hipLaunchKernelGGL(k_adaptive_keep, dim3(nb), dim3(kBlock), 0, stream, a.lists[cur], n, c, ad.max_samples, unconverged, rd.width, rd.height, a.block_counts);
+            hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(kBlock), 0, stream, a.block_counts, nb);
+            hipLaunchKernelGGL(k_adaptive_scatter, dim3(nb), dim3(kBlock), 0, stream, a.lists[cur], n, c, ad.max_samples, unconverged, rd.width, rd.height,
+                               a.block_counts, a.lists[cur ^ 1u]);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&next, a.block_counts + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+        }
+        uint64_t total = next;
+        if (node) {   // the decision: the sum of every device's next length
+            node->next[v] = next;
+            if (!node->lock.arrive([node] { node->total = 0; for (uint32_t k : node->next) node->total += k; return PT_OK; })) return stopped();
+            total = node->total;
+        }
+        if (total == 0) break;
         n = next;
         cur ^= 1u;
         len = ad.step < ad.max_samples - c ? ad.step : ad.max_samples - c;
@@ -381,8 +463,10 @@ pt_status adaptive_rounds(pt_scene* sc, const pt_render_desc& rd, const pt_adapt
 }
 
 // Set-up (kernel forms, queues, launch configuration) and one pass loop over a device pixel list and a sample range: pt_render runs the loop once over its
-// shard's pixels; with `adaptive` (pt_render_adaptive, its arguments checked) adaptive_rounds runs it once per round.
-pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hipStream_t stream, pt_profile* profile, const pt_adaptive_desc* adaptive = nullptr) {
+// shard's pixels; with `adaptive` (pt_render_adaptive, its arguments checked) adaptive_rounds runs it once per round, over the film or (with `node`: worker
+// node_index of pt_render_adaptive_multi) over the desc's shard.
+pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hipStream_t stream, pt_profile* profile, const pt_adaptive_desc* adaptive = nullptr,
+                      NodeRounds* node = nullptr, int node_index = 0) {
     if (!sc || !rdp || !d_film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     pt_render_desc rd;
     std::string err;
@@ -415,11 +499,13 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     pt_status st = ensure_buffers(sc, capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, (hero || rd.medium_aware) ? 4u : 1u, park_block);
     if (st != PT_OK) return st;
     DeviceBuffers& b = sc->buf;
-    if (adaptive) {   // (round 0's list: every pixel of the film in shard_pixels' order)
-        st = ensure_adaptive_buffers(sc, (size_t)rd.width * rd.height);
+    if (adaptive) {   // (round 0's list: every pixel of the film — or of the shard — in shard_pixels' order; counts and stats are zero outside it)
+        const size_t film_pixels = (size_t)rd.width * rd.height;
+        st = ensure_adaptive_buffers(sc, film_pixels);
         if (st != PT_OK) return st;
-        HIP_TRY(hipMemcpyAsync(sc->adaptive.lists[0], pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemsetAsync(sc->adaptive.stats, 0, sizeof(double) * 2 * pixels.size(), stream));
+        if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(sc->adaptive.lists[0], pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(sc->adaptive.stats, 0, sizeof(double) * 2 * film_pixels, stream));
+        if (pixels.size() < film_pixels) HIP_TRY(hipMemsetAsync(sc->adaptive.counts, 0, sizeof(uint32_t) * film_pixels, stream));
     } else if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(b.pixels, pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(d_film, 0, sizeof(float) * 4 * (size_t)rd.width * rd.height, stream));
     HIP_TRY(hipMemsetAsync(b.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));
@@ -598,7 +684,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
         return PT_OK;
     };
     uint32_t rounds = 0;
-    st = adaptive ? adaptive_rounds(sc, rd, *adaptive, stream, d_film, (uint32_t)pixels.size(), run_passes, &rounds)
+    st = adaptive ? adaptive_rounds(sc, rd, *adaptive, stream, d_film, (uint32_t)pixels.size(), run_passes, &rounds, node, node_index)
                   : run_passes(b.pixels, (uint32_t)pixels.size(), rd.first_sample, rd.sample_count, nullptr);
     if (st != PT_OK) return st;
     HIP_TRY(hipGetLastError());
@@ -855,10 +941,11 @@ struct Rccl {
     decltype(&ncclCommInitAll) comm_init_all = nullptr;
     decltype(&ncclCommDestroy) comm_destroy = nullptr;
     decltype(&ncclReduce) reduce = nullptr;
+    decltype(&ncclAllReduce) all_reduce = nullptr;
     decltype(&ncclGroupStart) group_start = nullptr;
     decltype(&ncclGroupEnd) group_end = nullptr;
     decltype(&ncclGetErrorString) error_string = nullptr;
-    bool ok() const { return comm_init_all && comm_destroy && reduce && group_start && group_end && error_string; }
+    bool ok() const { return comm_init_all && comm_destroy && reduce && all_reduce && group_start && group_end && error_string; }
 };
 Rccl& rccl() {
     static Rccl r;
@@ -869,6 +956,7 @@ Rccl& rccl() {
         r.comm_init_all = reinterpret_cast<decltype(r.comm_init_all)>(dlsym(r.handle, "ncclCommInitAll"));
         r.comm_destroy = reinterpret_cast<decltype(r.comm_destroy)>(dlsym(r.handle, "ncclCommDestroy"));
         r.reduce = reinterpret_cast<decltype(r.reduce)>(dlsym(r.handle, "ncclReduce"));
+        r.all_reduce = reinterpret_cast<decltype(r.all_reduce)>(dlsym(r.handle, "ncclAllReduce"));
         r.group_start = reinterpret_cast<decltype(r.group_start)>(dlsym(r.handle, "ncclGroupStart"));
         r.group_end = reinterpret_cast<decltype(r.group_end)>(dlsym(r.handle, "ncclGroupEnd"));
         r.error_string = reinterpret_cast<decltype(r.error_string)>(dlsym(r.handle, "ncclGetErrorString"));
@@ -884,6 +972,13 @@ __global__ void __launch_bounds__(kBlock) k_film_add(float4* __restrict__ dst, c
         const float4 a = dst[i], b = src[i];
         dst[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
     }
+}
+// dst += src over n counts / n statistics: pt_render_adaptive_multi's sample counts and (S1, S2) of those virtual devices (0 outside a device's shard)
+__global__ void __launch_bounds__(kBlock) k_u32_add(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = dst[i] + src[i];
+}
+__global__ void __launch_bounds__(kBlock) k_f64_add(double* __restrict__ dst, const double* __restrict__ src, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = dst[i] + src[i];
 }
 
 static void multi_release(MultiSetup& m) {
@@ -921,33 +1016,38 @@ static pt_status multi_setup(pt_scene* sc, const std::vector<int>& devices, uint
     return PT_OK;
 }
 
-pt_status pt_render_multi(pt_scene* sc, const pt_render_desc* rdp, uint64_t device_mask, float* film, pt_profile* profile) {
-    if (!sc || !rdp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    if (rdp->width == 0 || rdp->height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
-    if (rdp->shard_count > 1) return fail(PT_ERR_INVALID_ARGUMENT, "pt_render_multi deals the tiles itself: shard_count must be 0");
+// The devices of a node call (pt_render_multi, pt_render_adaptive_multi): the physical devices of the mask, the virtual devices per physical one
+// (pt_tuning::multi_virtual, a test mode), n = shards = host threads = streams = replicas, and whether the exchange between physical devices takes RCCL
+// (always for more than one; PT_TUNE_MULTI_RCCL takes it even for one: the call path of a node, on a single GPU).
+struct Node {
+    std::vector<int> devices;
+    uint32_t virt = 1;
+    int np = 0, n = 0;
+    bool use_rccl = false;
+    std::vector<pt_scene*> scene_of;   // per virtual device: this scene or its replica
+    bool single(const pt_scene* sc) const { return !use_rccl && n == 1 && devices[0] == sc->device; }   // (the one-device call itself)
+};
+static pt_status node_devices(pt_scene* sc, uint64_t device_mask, Node* node) {
     const uint32_t visible = pt_device_count();
     if (visible == 0) return fail(PT_ERR_NO_DEVICE, "no HIP device available: the product path has no CPU fallback");
-    std::vector<int> devices;
-    for (uint32_t d = 0; d < visible && d < 64; ++d) if (device_mask == 0 || ((device_mask >> d) & 1ull)) devices.push_back((int)d);
-    if (devices.empty()) return fail(PT_ERR_INVALID_ARGUMENT, "device_mask names no visible HIP device");
-    const int np = (int)devices.size();                                         // physical devices
-    const uint32_t virt = sc->tuning.multi_virtual > 1 ? sc->tuning.multi_virtual : 1u;   // virtual devices per physical one (test mode)
-    const int n = np * (int)virt;                                               // shards = host threads = streams = replicas
-    // the RCCL reduce for more than one physical device; PT_TUNE_MULTI_RCCL takes it even for one (the call path of a node, on a single GPU)
-    const bool use_rccl = np > 1 || (sc->tuning.flags & PT_TUNE_MULTI_RCCL) != 0;
-    if (!use_rccl && n == 1 && devices[0] == sc->device) return pt_render(sc, rdp, film, profile);
-
-    // whatever happens below, the caller gets its current device back
-    struct DeviceGuard { int d = 0; bool ok = false; DeviceGuard() { ok = hipGetDevice(&d) == hipSuccess; } ~DeviceGuard() { if (ok) hipSetDevice(d); } } guard;
-    const auto t_entry = std::chrono::steady_clock::now();
-
-    // one replica per (virtual) device — this scene itself for the first one on its own device — made on first use and kept
+    for (uint32_t d = 0; d < visible && d < 64; ++d) if (device_mask == 0 || ((device_mask >> d) & 1ull)) node->devices.push_back((int)d);
+    if (node->devices.empty()) return fail(PT_ERR_INVALID_ARGUMENT, "device_mask names no visible HIP device");
+    node->np = (int)node->devices.size();
+    node->virt = sc->tuning.multi_virtual > 1 ? sc->tuning.multi_virtual : 1u;
+    node->n = node->np * (int)node->virt;
+    node->use_rccl = node->np > 1 || (sc->tuning.flags & PT_TUNE_MULTI_RCCL) != 0;
+    return PT_OK;
+}
+// one replica per (virtual) device — this scene itself for the first one on its own device — made on first use and kept on the scene; then the
+// streams, device films and communicator (multi_setup)
+static pt_status node_prepare(pt_scene* sc, Node& node, size_t film_bytes) {
+    const uint32_t visible = pt_device_count(), virt = node.virt;
     if (sc->replicas.size() < (size_t)visible * virt) sc->replicas.resize((size_t)visible * virt, nullptr);
-    std::vector<pt_scene*> scene_of(n, nullptr);
-    for (int v = 0; v < n; ++v) {
-        const int d = devices[v / virt];
+    node.scene_of.assign(node.n, nullptr);
+    for (int v = 0; v < node.n; ++v) {
+        const int d = node.devices[v / virt];
         const size_t slot = (size_t)d * virt + (size_t)v % virt;
-        if (d == sc->device && v % (int)virt == 0) { scene_of[v] = sc; continue; }
+        if (d == sc->device && v % (int)virt == 0) { node.scene_of[v] = sc; continue; }
         if (!sc->replicas[slot]) {
             HIP_TRY(hipSetDevice(d));
             pt_scene* r = new pt_scene();
@@ -957,67 +1057,211 @@ pt_status pt_render_multi(pt_scene* sc, const pt_render_desc* rdp, uint64_t devi
             if (st != PT_OK) { const std::string msg = g_error; pt_scene_destroy(r); g_error = msg; return st; }
             sc->replicas[slot] = r;
         }
-        scene_of[v] = sc->replicas[slot];
+        node.scene_of[v] = sc->replicas[slot];
     }
-    const size_t bytes = sizeof(float) * 4 * (size_t)rdp->width * rdp->height;
-    pt_status st = multi_setup(sc, devices, virt, use_rccl, bytes);
-    if (st != PT_OK) return st;
-    MultiSetup& m = sc->multi;
-    std::vector<pt_status> status(n, PT_OK);
-    std::vector<std::string> errors(n);
-    std::vector<pt_profile> profiles(n);
-    const auto t0 = std::chrono::steady_clock::now();
-    auto worker = [&](int v) {
-        auto bad = [&](pt_status s2, const std::string& msg) { status[v] = s2; errors[v] = msg; };
-        if (hipSetDevice(devices[v / virt]) != hipSuccess) return bad(PT_ERR_DEVICE, "hipSetDevice failed");
-        pt_render_desc rd = *rdp;
-        if (n > 1) { rd.shard_index = (uint32_t)v; rd.shard_count = (uint32_t)n; }
-        pt_status s2 = render_impl(scene_of[v], &rd, m.films[v], m.streams[v], &profiles[v]);
-        if (s2 != PT_OK) bad(s2, g_error);   // (g_error is thread-local: carried back to the caller below)
-    };
-    {
-        std::vector<std::thread> pool;
-        for (int v = 1; v < n; ++v) pool.emplace_back(worker, v);
-        worker(0);
-        for (auto& t : pool) t.join();
-    }
-    for (int v = 0; v < n; ++v) if (status[v] != PT_OK) return fail(status[v], "device " + std::to_string(devices[v / virt]) + (virt > 1 ? "." + std::to_string(v % virt) : "") + ": " + errors[v]);
-    // the only exchange step of the path.  Every film is zero outside its own tiles, so the sums are gathers and keep every bit.
-    const auto t_reduce = std::chrono::steady_clock::now();
-    const size_t pixels = (size_t)rdp->width * rdp->height;
-    for (int p = 0; p < np && virt > 1; ++p) {   // (1) the virtual devices of one physical device: added on that device (render_impl has synchronised their streams)
-        HIP_TRY(hipSetDevice(devices[p]));
-        for (uint32_t j = 1; j < virt; ++j)
-            hipLaunchKernelGGL(k_film_add, dim3(1024), dim3(kBlock), 0, m.streams[(size_t)p * virt], reinterpret_cast<float4*>(m.films[(size_t)p * virt]), reinterpret_cast<const float4*>(m.films[(size_t)p * virt + j]), pixels);
+    return multi_setup(sc, node.devices, virt, node.use_rccl, film_bytes);
+}
+// worker(v) for every virtual device: one host thread each, v = 0 on the calling thread
+static void node_run(int n, const std::function<void(int)>& worker) {
+    std::vector<std::thread> pool;
+    for (int v = 1; v < n; ++v) pool.emplace_back(worker, v);
+    worker(0);
+    for (auto& t : pool) t.join();
+}
+// The gather of per-device buffers into the first device of the mask: (1) the virtual devices of one physical device added on that device (their
+// streams are synchronised), (2) one grouped ncclReduce(sum) per buffer between the physical devices, over xGMI.  Every device's buffers are zero outside
+// its own tiles, so the sums are gathers and keep every bit.
+struct GatherPart { std::vector<void*> bufs; size_t count; ncclDataType_t type; };   // bufs: per virtual device; count: elements (floats, u32, f64)
+static pt_status node_gather(MultiSetup& m, const Node& node, const std::vector<GatherPart>& parts) {
+    const uint32_t virt = node.virt;
+    for (int p = 0; p < node.np && virt > 1; ++p) {
+        HIP_TRY(hipSetDevice(node.devices[p]));
+        hipStream_t s = m.streams[(size_t)p * virt];
+        for (const GatherPart& g : parts)
+            for (uint32_t j = 1; j < virt; ++j) {
+                void *dst = g.bufs[(size_t)p * virt], *src = g.bufs[(size_t)p * virt + j];
+                if (g.type == ncclFloat) hipLaunchKernelGGL(k_film_add, dim3(1024), dim3(kBlock), 0, s, static_cast<float4*>(dst), static_cast<const float4*>(src), g.count / 4);
+                else if (g.type == ncclUint32) hipLaunchKernelGGL(k_u32_add, dim3(1024), dim3(kBlock), 0, s, static_cast<uint32_t*>(dst), static_cast<const uint32_t*>(src), g.count);
+                else hipLaunchKernelGGL(k_f64_add, dim3(1024), dim3(kBlock), 0, s, static_cast<double*>(dst), static_cast<const double*>(src), g.count);
+            }
         HIP_TRY(hipGetLastError());
-        if (!use_rccl) HIP_TRY(hipStreamSynchronize(m.streams[(size_t)p * virt]));
+        if (!node.use_rccl) HIP_TRY(hipStreamSynchronize(s));
     }
-    if (use_rccl) {   // (2) the physical devices: one ncclReduce(sum) into the first device of the mask, over xGMI
+    if (node.use_rccl) {
         ncclResult_t rc = rccl().group_start();
-        for (int p = 0; p < np && rc == ncclSuccess; ++p) {
-            hipSetDevice(devices[p]);
-            float* f = m.films[(size_t)p * virt];
-            rc = rccl().reduce(f, f, pixels * 4, ncclFloat, ncclSum, 0, m.comms[p], m.streams[(size_t)p * virt]);
+        for (int p = 0; p < node.np && rc == ncclSuccess; ++p) {
+            hipSetDevice(node.devices[p]);
+            for (const GatherPart& g : parts) {
+                void* b = g.bufs[(size_t)p * virt];
+                rc = rccl().reduce(b, b, g.count, g.type, ncclSum, 0, m.comms[p], m.streams[(size_t)p * virt]);
+                if (rc != ncclSuccess) break;
+            }
         }
         ncclResult_t rc2 = rccl().group_end();
         if (rc == ncclSuccess) rc = rc2;
         if (rc != ncclSuccess) { multi_release(m); return fail(PT_ERR_DEVICE, std::string("ncclReduce: ") + rccl().error_string(rc)); }
-        for (int p = 0; p < np; ++p) { hipSetDevice(devices[p]); if (hipStreamSynchronize(m.streams[(size_t)p * virt]) != hipSuccess) { multi_release(m); return fail(PT_ERR_DEVICE, "stream synchronisation after the film reduce failed"); } }
+        for (int p = 0; p < node.np; ++p) { hipSetDevice(node.devices[p]); if (hipStreamSynchronize(m.streams[(size_t)p * virt]) != hipSuccess) { multi_release(m); return fail(PT_ERR_DEVICE, "stream synchronisation after the film reduce failed"); } }
     }
+    return PT_OK;
+}
+// the summed ray counters and stage figures of the workers' profiles
+static void node_profile(const std::vector<pt_profile>& profiles, pt_profile* profile) {
+    memset(profile, 0, sizeof(*profile));
+    for (const pt_profile& p : profiles) {
+        profile->bounce_rays += p.bounce_rays; profile->shadow_rays += p.shadow_rays; profile->light_rays += p.light_rays;
+        profile->camera_rays += p.camera_rays; profile->env_hits += p.env_hits;
+        for (int k = 0; k < 5; ++k) { profile->kernel_seconds[k] += p.kernel_seconds[k]; profile->kernel_launches[k] += p.kernel_launches[k]; profile->stage_items[k] += p.stage_items[k]; }
+        profile->stage_items[5] += p.stage_items[5];
+    }
+}
+// whatever happens in a node call, the caller gets its current device back
+struct DeviceGuard {
+    int d = 0;
+    bool ok = false;
+    DeviceGuard() { ok = hipGetDevice(&d) == hipSuccess; }
+    ~DeviceGuard() { if (ok) hipSetDevice(d); }
+};
+static std::string device_name(const Node& node, int v) {
+    return "device " + std::to_string(node.devices[v / node.virt]) + (node.virt > 1 ? "." + std::to_string(v % node.virt) : "");
+}
+
+pt_status pt_render_multi(pt_scene* sc, const pt_render_desc* rdp, uint64_t device_mask, float* film, pt_profile* profile) {
+    if (!sc || !rdp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    if (rdp->width == 0 || rdp->height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
+    if (rdp->shard_count > 1) return fail(PT_ERR_INVALID_ARGUMENT, "pt_render_multi deals the tiles itself: shard_count must be 0");
+    Node node;
+    pt_status st = node_devices(sc, device_mask, &node);
+    if (st != PT_OK) return st;
+    if (node.single(sc)) return pt_render(sc, rdp, film, profile);
+
+    DeviceGuard guard;
+    const auto t_entry = std::chrono::steady_clock::now();
+    const size_t bytes = sizeof(float) * 4 * (size_t)rdp->width * rdp->height;
+    st = node_prepare(sc, node, bytes);
+    if (st != PT_OK) return st;
+    MultiSetup& m = sc->multi;
+    const int n = node.n;
+    std::vector<pt_status> status(n, PT_OK);
+    std::vector<std::string> errors(n);
+    std::vector<pt_profile> profiles(n);
+    const auto t0 = std::chrono::steady_clock::now();
+    node_run(n, [&](int v) {
+        auto bad = [&](pt_status s2, const std::string& msg) { status[v] = s2; errors[v] = msg; };
+        if (hipSetDevice(node.devices[v / node.virt]) != hipSuccess) return bad(PT_ERR_DEVICE, "hipSetDevice failed");
+        pt_render_desc rd = *rdp;
+        if (n > 1) { rd.shard_index = (uint32_t)v; rd.shard_count = (uint32_t)n; }
+        pt_status s2 = render_impl(node.scene_of[v], &rd, m.films[v], m.streams[v], &profiles[v]);
+        if (s2 != PT_OK) bad(s2, g_error);   // (g_error is thread-local: carried back to the caller below)
+    });
+    for (int v = 0; v < n; ++v) if (status[v] != PT_OK) return fail(status[v], device_name(node, v) + ": " + errors[v]);
+    // the only exchange step of the path
+    const auto t_reduce = std::chrono::steady_clock::now();
+    const size_t pixels = (size_t)rdp->width * rdp->height;
+    st = node_gather(m, node, {GatherPart{std::vector<void*>(m.films.begin(), m.films.begin() + n), pixels * 4, ncclFloat}});
+    if (st != PT_OK) return st;
     const auto t1 = std::chrono::steady_clock::now();
-    HIP_TRY(hipSetDevice(devices[0]));
+    HIP_TRY(hipSetDevice(node.devices[0]));
     HIP_TRY(hipMemcpy(film, m.films[0], bytes, hipMemcpyDeviceToHost));
     if (profile) {
-        memset(profile, 0, sizeof(*profile));
-        for (const pt_profile& p : profiles) {
-            profile->bounce_rays += p.bounce_rays; profile->shadow_rays += p.shadow_rays; profile->light_rays += p.light_rays;
-            profile->camera_rays += p.camera_rays; profile->env_hits += p.env_hits;
-            for (int k = 0; k < 5; ++k) { profile->kernel_seconds[k] += p.kernel_seconds[k]; profile->kernel_launches[k] += p.kernel_launches[k]; profile->stage_items[k] += p.stage_items[k]; }
-            profile->stage_items[5] += p.stage_items[5];
-        }
+        node_profile(profiles, profile);
         profile->seconds = std::chrono::duration<double>(t1 - t0).count();
         profile->kernel_seconds[5] = std::chrono::duration<double>(t0 - t_entry).count();    // set-up (replicas, streams, films, communicator): ~0 on a repeated call
         profile->kernel_seconds[6] = std::chrono::duration<double>(t1 - t_reduce).count();   // the film reduce
+    }
+    return PT_OK;
+}
+
+pt_status pt_render_adaptive_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, uint64_t device_mask, float* film,
+                                   uint32_t* sample_counts, double* stats, pt_profile* profile) {
+    if (!sc || !rdp || !adp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    pt_render_desc rd;
+    pt_adaptive_desc ad;
+    std::string err;
+    pt_status st = pth::normalize_adaptive_desc(*rdp, *adp, sample_counts != nullptr, (uint32_t)sc->host.cameras.size(), &rd, &ad, &err);
+    if (st != PT_OK) return fail(st, err);
+    Node node;
+    st = node_devices(sc, device_mask, &node);
+    if (st != PT_OK) return st;
+    if (node.single(sc)) return pt_render_adaptive(sc, rdp, adp, film, sample_counts, stats, profile);
+
+    DeviceGuard guard;
+    const auto t_entry = std::chrono::steady_clock::now();
+    const size_t pixels = (size_t)rd.width * rd.height, bytes = sizeof(float) * 4 * pixels;
+    st = node_prepare(sc, node, bytes);
+    if (st != PT_OK) return st;
+    MultiSetup& m = sc->multi;
+    const int n = node.n;
+    const uint32_t virt = node.virt;
+    for (int v = 0; v < n; ++v) {   // (the adaptive buffers exist before the workers start: the exchange reads every device's image)
+        HIP_TRY(hipSetDevice(node.devices[v / virt]));
+        st = ensure_adaptive_buffers(node.scene_of[v], pixels);
+        if (st != PT_OK) return st;
+    }
+    NodeRounds nr;
+    nr.lock.parties = n;
+    nr.next.assign(n, 0u);
+    for (int v = 0; v < n; ++v) nr.images.push_back(node.scene_of[v]->adaptive.unconverged);
+    for (int v = 0; v < n; ++v) nr.merged.push_back(nr.images[(size_t)(v / (int)virt) * virt]);
+    // the exchange of a round (run by the last worker to arrive): the images of the virtual devices ORed on their physical device, then one grouped
+    // all-reduce (max = OR: the shards are disjoint) between the physical devices; every first virtual device then holds the film-wide image
+    nr.exchange = [&]() -> pt_status {
+        const auto t = std::chrono::steady_clock::now();
+        int here = 0;
+        HIP_TRY(hipGetDevice(&here));
+        const unsigned blocks = (unsigned)std::min<size_t>(1024, std::max<size_t>(1, (pixels / 16 + kBlock - 1) / kBlock));
+        for (int p = 0; p < node.np && virt > 1; ++p) {
+            HIP_TRY(hipSetDevice(node.devices[p]));
+            for (uint32_t j = 1; j < virt; ++j)
+                hipLaunchKernelGGL(k_mask_or, dim3(blocks), dim3(kBlock), 0, m.streams[(size_t)p * virt], nr.images[(size_t)p * virt], nr.images[(size_t)p * virt + j], pixels);
+            HIP_TRY(hipGetLastError());
+        }
+        if (node.use_rccl) {
+            ncclResult_t rc = rccl().group_start();
+            for (int p = 0; p < node.np && rc == ncclSuccess; ++p) {
+                hipSetDevice(node.devices[p]);
+                uint8_t* img = nr.images[(size_t)p * virt];
+                rc = rccl().all_reduce(img, img, pixels, ncclUint8, ncclMax, m.comms[p], m.streams[(size_t)p * virt]);
+            }
+            ncclResult_t rc2 = rccl().group_end();
+            if (rc == ncclSuccess) rc = rc2;
+            if (rc != ncclSuccess) { hipSetDevice(here); return fail(PT_ERR_DEVICE, std::string("ncclAllReduce: ") + rccl().error_string(rc)); }
+        }
+        for (int p = 0; p < node.np; ++p) {
+            HIP_TRY(hipSetDevice(node.devices[p]));
+            HIP_TRY(hipStreamSynchronize(m.streams[(size_t)p * virt]));
+        }
+        HIP_TRY(hipSetDevice(here));
+        nr.exchange_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+        return PT_OK;
+    };
+    std::vector<pt_profile> profiles(n);
+    const auto t0 = std::chrono::steady_clock::now();
+    node_run(n, [&](int v) {
+        pt_status s2 = hipSetDevice(node.devices[v / virt]) == hipSuccess ? PT_OK : fail(PT_ERR_DEVICE, "hipSetDevice failed");
+        pt_render_desc rv = rd;
+        if (n > 1) { rv.shard_index = (uint32_t)v; rv.shard_count = (uint32_t)n; }
+        if (s2 == PT_OK) s2 = render_impl(node.scene_of[v], &rv, m.films[v], m.streams[v], &profiles[v], &ad, &nr, v);
+        if (s2 != PT_OK) nr.lock.stop(s2, device_name(node, v) + ": " + g_error);   // (a worker stopped by another's failure finds the first error kept)
+    });
+    if (nr.lock.failed) return fail(nr.lock.status, nr.lock.error);
+    const auto t_gather = std::chrono::steady_clock::now();
+    std::vector<GatherPart> parts = {GatherPart{std::vector<void*>(m.films.begin(), m.films.begin() + n), pixels * 4, ncclFloat},
+                                     GatherPart{{}, pixels, ncclUint32}, GatherPart{{}, 2 * pixels, ncclFloat64}};
+    for (int v = 0; v < n; ++v) { parts[1].bufs.push_back(node.scene_of[v]->adaptive.counts); parts[2].bufs.push_back(node.scene_of[v]->adaptive.stats); }
+    if (!stats) parts.pop_back();
+    st = node_gather(m, node, parts);
+    if (st != PT_OK) return st;
+    const auto t_gathered = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(node.devices[0]));
+    HIP_TRY(hipMemcpy(film, m.films[0], bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sample_counts, node.scene_of[0]->adaptive.counts, sizeof(uint32_t) * pixels, hipMemcpyDeviceToHost));
+    if (stats) HIP_TRY(hipMemcpy(stats, node.scene_of[0]->adaptive.stats, sizeof(double) * 2 * pixels, hipMemcpyDeviceToHost));
+    if (profile) {
+        node_profile(profiles, profile);
+        profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count();   // (the whole call: set-up, rounds, gather, read-backs)
+        profile->kernel_launches[5] = profiles[0].kernel_launches[5];                                          // the rounds (every device ran them all)
+        profile->kernel_seconds[5] = std::chrono::duration<double>(t0 - t_entry).count();                    // set-up: ~0 on a repeated call
+        profile->kernel_seconds[6] = nr.exchange_seconds + std::chrono::duration<double>(t_gathered - t_gather).count();   // the rounds' exchanges + the gather
     }
     return PT_OK;
 }

@@ -125,7 +125,7 @@ pt_status normalize_adaptive_desc(const pt_render_desc& in, const pt_adaptive_de
     if (!has_sample_counts) { *error = "sample_counts is required"; return PT_ERR_INVALID_ARGUMENT; }
     // (the NaiveRenderer's one phase of every sample cannot be extended by rounds)
     if (in.phase_samples != 0 && in.phase_samples != 10) { *error = "adaptive sampling needs phases of 10 samples (phase_samples 0 or 10)"; return PT_ERR_UNSUPPORTED; }
-    if (in.shard_count != 0) { *error = "adaptive sampling renders the whole film on one device (shard_count 0)"; return PT_ERR_UNSUPPORTED; }
+    if (in.shard_count != 0) { *error = "adaptive sampling deals the film's tiles itself (shard_count 0; pt_render_adaptive_multi for several devices)"; return PT_ERR_UNSUPPORTED; }
     if (in.first_sample != 0 || in.sample_count != 0) { *error = "adaptive sampling renders the whole sample range (first_sample 0, sample_count 0)"; return PT_ERR_INVALID_ARGUMENT; }
     if (in.spp % 10 != 0 || a.step % 10 != 0 || a.max_samples % 10 != 0) { *error = "spp, step and max_samples must be multiples of 10"; return PT_ERR_INVALID_ARGUMENT; }
     if (a.max_samples < in.spp) { *error = "max_samples < spp"; return PT_ERR_INVALID_ARGUMENT; }

@@ -3,10 +3,12 @@
 // (src/tonemap/clamp.rs:76-102, reinhard0.rs:84-103,179-196, reinhard1.rs:88-110,203-231), XYZ -> linear RGB of the colour
 // space's primaries, OETF, 8-bit quantisation (src/tonemap/mod.rs:19-37,147-205,316-333), and the two file writers.
 //
-// On the GPU the reduction is a two-level f64 tree (one partial per workgroup, summed on the host in workgroup order), the
-// per-pixel map is one lane per pixel.  The reference sums sequentially (f64 for the luminance-only tonemappers, f32 lanes
-// for the x3 variants); the tree sum differs from those by rounding only, which moves l_w by <= 1e-6 relative (f64) or 1e-4
-// (x3) and an 8-bit output by at most one code value — that is the parity bar of tests/test_output.py.
+// On the GPU the per-pixel map is one lane per pixel.  The log-average of the luminance-only tonemappers is a two-level f64
+// tree (one partial per workgroup, summed on the host in workgroup order); the reference sums it sequentially in f64, and
+// the two differ by f64 rounding only.  The x3 variants' log-average is the reference's own f32 left fold in row-major
+// order (reinhard0.rs:138-160, reinhard1.rs:147-168): its rounding error grows with the film (about 2 % of l_w at
+// 1024x1024) and moves 8-bit outputs by many code values, so it is reproduced, not approximated.  The per-pixel f32 terms
+// ln(0.001f + c.k) are computed in parallel, correctly rounded, and folded in pixel order on the host.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -53,23 +55,32 @@ __host__ __device__ inline uint8_t quantize(float v) {  // (v * 255).ceil().clam
     return (uint8_t)c;
 }
 
-// Tonemapper::initialize: sums of ln(delta + value) over pixels whose luminance is not NaN
-__global__ void __launch_bounds__(kBlock) k_log_sums(const float4* __restrict__ film, uint32_t n, int x3, double* __restrict__ partial) {
-    __shared__ double sh[3][kBlock];
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+// Tonemapper::initialize, luminance only: f64 sums of ln(delta + lum) over pixels whose luminance is not NaN
+__global__ void __launch_bounds__(kBlock) k_log_sums(const float4* __restrict__ film, uint32_t n, int reinhard1, double* __restrict__ partial) {
+    __shared__ double sh[kBlock];
+    double s = 0.0;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        float4 c = film[i];
-        if (c.y != c.y) continue;
-        if (x3) { s0 += pt_log64((double)(0.001f + c.x)); s1 += pt_log64((double)(0.001f + c.y)); s2 += pt_log64((double)(0.001f + c.z)); }
-        else s1 += pt_log64(0.001 + (double)c.y);
+        float y = film[i].y;
+        if (y != y) continue;
+        s += reinhard1 ? pt_log64((double)(0.001f + y)) : pt_log64(0.001 + (double)y);
     }
-    sh[0][threadIdx.x] = s0; sh[1][threadIdx.x] = s1; sh[2][threadIdx.x] = s2;
+    sh[threadIdx.x] = s;
     __syncthreads();
     for (int off = kBlock / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) for (int k = 0; k < 3; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + off];
+        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
         __syncthreads();
     }
-    if (threadIdx.x == 0) for (int k = 0; k < 3; ++k) partial[blockIdx.x * 3 + k] = sh[k][0];
+    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+}
+
+// Tonemapper::initialize, x3: the f32 terms ln(0.001f + c.k) of every pixel (+0.0f, which the fold adds exactly, where the
+// luminance is NaN), for the host's fold in pixel order
+__global__ void __launch_bounds__(kBlock) k_log_terms(const float4* __restrict__ film, uint32_t n, float4* __restrict__ terms) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        float4 c = film[i];
+        terms[i] = (c.y != c.y) ? make_float4(0.0f, 0.0f, 0.0f, 0.0f)
+                                : make_float4(pt_ln(0.001f + c.x), pt_ln(0.001f + c.y), pt_ln(0.001f + c.z), 0.0f);
+    }
 }
 
 __host__ __device__ inline void tonemap_pixel(const OutParams& p, float x, float y, float z, float* ox, float* oy, float* oz) {
@@ -158,28 +169,33 @@ pt_status pt_output_film(const pt_output_desc* d, const float* film, uint8_t* rg
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return ofail(PT_ERR_NO_DEVICE, "no HIP device available: the product path has no CPU fallback");
     const uint32_t n = d->width * d->height;
-    float4* d_film = nullptr; uchar4* d_rgba = nullptr; float* d_lin = nullptr; double* d_part = nullptr;
+    const bool x3 = d->tonemap != PT_TONEMAP_CLAMP && !d->luminance_only;
+    float4* d_film = nullptr; uchar4* d_rgba = nullptr; float* d_lin = nullptr; double* d_part = nullptr; float4* d_terms = nullptr;
     const int grid = 1024;
     hipError_t e = hipMalloc(&d_film, sizeof(float4) * n);
     if (e == hipSuccess) e = hipMalloc(&d_rgba, sizeof(uchar4) * n);
     if (e == hipSuccess && linear_rgb) e = hipMalloc(&d_lin, sizeof(float) * 3 * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc(&d_part, sizeof(double) * 3 * grid);
+    if (e == hipSuccess) e = hipMalloc(&d_part, sizeof(double) * grid);
+    if (e == hipSuccess && x3) e = hipMalloc(&d_terms, sizeof(float4) * n);
     if (e == hipSuccess) e = hipMemcpy(d_film, film, sizeof(float4) * n, hipMemcpyHostToDevice);
     OutParams p; memset(&p, 0, sizeof(p));
     p.n = n; p.tonemap = d->tonemap; p.luminance_only = d->luminance_only; p.colorspace = d->colorspace;
     p.exposure_mult = pt_pow(2.0f, d->exposure); p.key_value = d->key_value; p.inv_white2 = 1.0f / (d->white_point * d->white_point); p.factor = d->factor;
-    if (e == hipSuccess && d->tonemap != PT_TONEMAP_CLAMP) {
-        int x3 = d->luminance_only ? (d->tonemap == PT_TONEMAP_REINHARD1 ? 2 : 0) : 1;
-        hipLaunchKernelGGL(k_log_sums, dim3(grid), dim3(kBlock), 0, 0, d_film, n, x3, d_part);
-        std::vector<double> part(3 * grid);
-        e = hipMemcpy(part.data(), d_part, sizeof(double) * 3 * grid, hipMemcpyDeviceToHost);
-        double s[3] = {0, 0, 0};
-        for (int b = 0; b < grid; ++b) for (int k = 0; k < 3; ++k) s[k] += part[3 * b + k];
-        // l_w = exp(sum_of_log / total_pixels) / factor (reinhard0.rs:66, reinhard1.rs:70; x3: per channel in f32)
-        for (int k = 0; k < 3; ++k) {
-            if (x3 == 1) p.lw[k] = pt_exp((float)s[k] / (float)n) / d->factor;
-            else p.lw[k] = (float)pt_exp64(s[1] / (double)n) / d->factor;
-        }
+    // l_w = exp(sum_of_log / total_pixels) / factor (reinhard0.rs:66,173, reinhard1.rs:68,181)
+    if (e == hipSuccess && x3) {
+        hipLaunchKernelGGL(k_log_terms, dim3(grid), dim3(kBlock), 0, 0, d_film, n, d_terms);
+        std::vector<float> t(4 * (size_t)n);
+        e = hipMemcpy(t.data(), d_terms, sizeof(float4) * n, hipMemcpyDeviceToHost);
+        float s[3] = {0.0f, 0.0f, 0.0f};   // f32x4 lanes, one sequential add per pixel
+        for (size_t i = 0; i < n; ++i) for (int k = 0; k < 3; ++k) s[k] += t[4 * i + k];
+        for (int k = 0; k < 3; ++k) p.lw[k] = pt_exp(s[k] / (float)n) / d->factor;
+    } else if (e == hipSuccess && d->tonemap != PT_TONEMAP_CLAMP) {
+        hipLaunchKernelGGL(k_log_sums, dim3(grid), dim3(kBlock), 0, 0, d_film, n, d->tonemap == PT_TONEMAP_REINHARD1 ? 1 : 0, d_part);
+        std::vector<double> part(grid);
+        e = hipMemcpy(part.data(), d_part, sizeof(double) * grid, hipMemcpyDeviceToHost);
+        double s = 0.0;
+        for (int b = 0; b < grid; ++b) s += part[b];
+        p.lw[0] = p.lw[1] = p.lw[2] = (float)pt_exp64(s / (double)n) / d->factor;
     }
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_output, dim3(grid), dim3(kBlock), 0, 0, d_film, p, d_rgba, d_lin);
@@ -187,7 +203,7 @@ pt_status pt_output_film(const pt_output_desc* d, const float* film, uint8_t* rg
     }
     if (e == hipSuccess) e = hipMemcpy(rgba8, d_rgba, sizeof(uchar4) * n, hipMemcpyDeviceToHost);
     if (e == hipSuccess && linear_rgb) e = hipMemcpy(linear_rgb, d_lin, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost);
-    hipFree(d_film); hipFree(d_rgba); hipFree(d_lin); hipFree(d_part);
+    hipFree(d_film); hipFree(d_rgba); hipFree(d_lin); hipFree(d_part); hipFree(d_terms);
     if (e != hipSuccess) return ofail(PT_ERR_DEVICE, hipGetErrorString(e));
     return PT_OK;
 }

@@ -1,0 +1,46 @@
+/* pt_denoise.h — a variance-guided edge-avoiding (a-trous) filter for the film of pt_render_adaptive(_multi).
+ *
+ * Not part of pt_api.h: that header is the boundary the oracle shares, and the reference has no denoiser.  Exported by libptamd.so (pt_) and by
+ * the host emulation of the tests (ptemu_).  The definition is DESIGN.md section 13 and, operation by operation, csrc/pt_denoise_rules.h; in short:
+ *
+ *   guides     per pixel the mean first-hit normal and distance over camera samples 0 .. guide_samples-1 (pt_camera_samples traced as
+ *              pt_intersect traces them); a pixel whose normal sum is 0 is sky
+ *   variance   of the pixel's mean Y, from the sample count and the f64 sums S1, S2 the adaptive render returns
+ *   a pass     i = 0 .. iterations-1, step 2^i: 25 taps of the B3 spline kernel (3/8, 1/4, 1/16), each weighted by the agreement of the normals
+ *              (dot^(2^a)), of the depths (against the depth gradient) and of the Y values (against sigma_luminance x the square root of the
+ *              two pixels' 3x3-filtered variances); colours are averaged with w, variances with w^2
+ *
+ * Pixels with a non-finite film channel or variance are copied through and never read.  The engine, the emulation and a numpy restatement agree
+ * bit for bit.  Albedo is not demodulated: a textured Lambertian surface is protected by the luminance weight alone. */
+#ifndef PT_DENOISE_H
+#define PT_DENOISE_H
+#include "pt_api.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct pt_denoise_desc {
+    uint32_t width, height;
+    uint32_t iterations;         /* a-trous passes, step 1, 2, 4, ...; 0 = 5; at most 10 */
+    float sigma_luminance;       /* 0 = 4 */
+    float sigma_depth;           /* 0 = 1 */
+    uint32_t normal_power_log2;  /* the normal weight is dot^(2^a); 0 = 7 (power 128); at most 10 */
+    uint32_t device;             /* HIP device the filter runs on (after pt_render_adaptive_multi: the first device of its mask) */
+    uint32_t reserved[1];        /* must be 0 */
+} pt_denoise_desc;
+
+/* guides_xyzw: width*height*4 f32 = (mean first-hit normal xyz, mean first-hit distance) over camera samples 0 .. guide_samples-1 of `desc`
+ * (width, height, seed, wavelength bounds, camera_index; jitter, aperture and camera kind as the render's own first stage has them). */
+pt_status pt_render_guides(pt_scene* scene, const pt_render_desc* desc, uint32_t guide_samples, float* guides_xyzw);
+
+/* film_xyzw, sample_counts (every one at least 2), stats: what pt_render_adaptive(_multi) returned for a film of desc->width x desc->height.
+ * guides_xyzw: pt_render_guides' output (finite).  out_film_xyzw: width*height*4 f32 (W = 0).  out_variance: width*height f32, the filtered
+ * film's variance estimate, may be NULL.  Host arrays in, host arrays out; out_film_xyzw may be film_xyzw. */
+pt_status pt_denoise_film(const pt_denoise_desc* desc, const float* film_xyzw, const uint32_t* sample_counts, const double* stats,
+                          const float* guides_xyzw, float* out_film_xyzw, float* out_variance);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* PT_DENOISE_H */

@@ -116,6 +116,12 @@ class AdaptiveDesc(C.Structure):
     _fields_ = [("max_samples", C.c_uint32), ("step", C.c_uint32), ("rel_error", C.c_float), ("abs_error", C.c_float)]
 
 
+class DenoiseDesc(C.Structure):
+    """pt_denoise_desc (include/pt_denoise.h): film size, passes, the three edge-stopping parameters (0 = default), the device."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_depth", C.c_float),
+                ("normal_power_log2", C.c_uint32), ("device", C.c_uint32), ("reserved", C.c_uint32 * 1)]
+
+
 class Profile(C.Structure):
     _fields_ = [("bounce_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("light_rays", C.c_uint64),
                 ("camera_rays", C.c_uint64), ("env_hits", C.c_uint64), ("seconds", C.c_double),
@@ -234,6 +240,10 @@ class Library:
                                                                     C.POINTER(C.c_double), C.POINTER(Profile)], required=False)
         self._render_adaptive_multi = bind("render_adaptive_multi", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), C.c_uint64, fpp,
                                                                                 C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(Profile)], required=False)
+        # include/pt_denoise.h (the reference has no denoiser; the oracle and older emulation libraries do not export these)
+        self._render_guides = bind("render_guides", C.c_int32, [vp, C.POINTER(RenderDesc), u32, fpp], required=False)
+        self._denoise_film = bind("denoise_film", C.c_int32, [C.POINTER(DenoiseDesc), fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp], required=False)
+        self._denoise_last_error = bind("denoise_last_error", C.c_char_p, [], required=False)   # (the emulation's: the engine reports through pt_last_error)
         self._device_info = bind("device_info", C.c_char_p, [], required=False)
         self._output_film = bind("output_film", C.c_int32, [C.POINTER(OutputDesc), fpp, C.POINTER(C.c_uint8), fpp], required=False)
         self._write_png = bind("write_png", C.c_int32, [C.c_char_p, u32, u32, C.POINTER(C.c_uint8), C.c_int32], required=False)
@@ -285,6 +295,27 @@ class Library:
         st = CompareStats()
         self.check(self._compare_films(w, h, _fp(image), _fp(truth), mode, _fp(out) if want_image else None, C.byref(st)))
         return out, st
+
+    def denoise_film(self, film, counts, stats, guides, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, device=0, variance=False):
+        """pt_denoise_film: the edge-avoiding filter over an adaptive render's film [H,W,4], counts [H,W] u32 and stats [H,W,2] f64 with the guides
+        [H,W,4] of Scene.render_guides.  0 selects a parameter's default.  Returns the filtered film [H,W,4], with variance=True (film, variance [H,W])."""
+        if self._denoise_film is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sdenoise_film entry" % (self.path, self.prefix))
+        film = np.ascontiguousarray(film, dtype=np.float32)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        stats = np.ascontiguousarray(stats, dtype=np.float64)
+        guides = np.ascontiguousarray(guides, dtype=np.float32)
+        h, w = film.shape[:2]
+        if film.shape != (h, w, 4) or counts.shape != (h, w) or stats.shape != (h, w, 2) or guides.shape != (h, w, 4):
+            raise ValueError("film [H,W,4], counts [H,W], stats [H,W,2] and guides [H,W,4] of one film size")
+        d = DenoiseDesc(w, h, iterations, sigma_luminance, sigma_depth, normal_power_log2, device)
+        out = np.zeros((h, w, 4), np.float32)
+        var = np.zeros((h, w), np.float32) if variance else None
+        st = self._denoise_film(C.byref(d), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)), stats.ctypes.data_as(C.POINTER(C.c_double)), _fp(guides),
+                                _fp(out), _fp(var) if variance else None)
+        if st != PT_OK:
+            raise PtError(st, self._denoise_last_error().decode() if self._denoise_last_error else self.last_error())
+        return (out, var) if variance else out
 
     def write_png(self, path, rgba8, colorspace=COLORSPACE_SRGB):
         rgba8 = np.ascontiguousarray(rgba8, np.uint8)
@@ -362,6 +393,32 @@ class Scene:
                                                                counts.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                                st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, C.byref(prof)))
         return (film, counts, st, prof) if stats else (film, counts, prof)
+
+    def render_guides(self, rd, samples=4):
+        """pt_render_guides: [H,W,4] f32 = the mean first-hit normal and distance over camera samples 0 .. samples-1 of the render `rd`."""
+        if self.library._render_guides is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_guides entry" % (self.library.path, self.library.prefix))
+        g = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        st = self.library._render_guides(self.handle, C.byref(rd), samples, _fp(g))
+        if st != PT_OK:
+            err = self.library._denoise_last_error
+            raise PtError(st, err().decode() if err else self.library.last_error())
+        return g
+
+    def render_denoised(self, rd, max_samples=None, rel_error=0.0, abs_error=0.0, step=0, guide_samples=4, iterations=0, sigma_luminance=0.0, sigma_depth=0.0,
+                        normal_power_log2=0, device_mask=None):
+        """An adaptive render with statistics (max_samples None = rd.spp: a fixed count), its guides, and the filter: (film, denoised, counts, profile).
+        `device_mask` (not None) routes the render through render_adaptive_multi; the filter then runs on the first device of the mask."""
+        mx = rd.spp if max_samples is None else max_samples
+        if device_mask is None:
+            film, counts, st, prof = self.render_adaptive(rd, mx, rel_error, abs_error, step, stats=True)
+            device = 0
+        else:
+            film, counts, st, prof = self.render_adaptive_multi(rd, mx, rel_error, abs_error, step, stats=True, device_mask=device_mask)
+            device = (device_mask & -device_mask).bit_length() - 1 if device_mask else 0
+        guides = self.render_guides(rd, guide_samples)
+        den = self.library.denoise_film(film, counts, st, guides, iterations, sigma_luminance, sigma_depth, normal_power_log2, device)
+        return film, den, counts, prof
 
     def render_multi(self, rd, device_mask=0):
         """pt_render_multi: every device of the mask (0 = all) from one blocking call."""

@@ -3,7 +3,7 @@
 // output/<filename>.exr and .png through the film output stage (src/renderer/mod.rs:24-80).
 //
 //   ptcli [--config data/config.toml] [--scene FILE] [-n|--dry-run] [--stdout-log-level L] [--write-log-level L]
-//         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK]
+//         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -11,6 +11,10 @@
 // <filename>.npy for tools/compare_films.py.  --adaptive REL renders every setting that has max_samples > min_samples with
 // pt_render_adaptive (include/pt_adaptive.h): min_samples to max_samples per pixel, relative error target REL.  --devices MASK renders every setting on
 // the devices of MASK (bit d = HIP device d, 0 = all) from one call: pt_render_multi, or pt_render_adaptive_multi with --adaptive.
+// --denoise also writes <filename>_denoised.exr / .png (and .npy with --write-film): the film through pt_denoise_film (include/pt_denoise.h) with guides of
+// --guide-samples K camera samples (default 4).  The filter needs the per-pixel statistics, which the adaptive path alone returns: every setting is rendered
+// through pt_render_adaptive (max_samples = min_samples without --adaptive: the same film, bit for bit, as pt_render's), and a setting that path refuses — the
+// Naive renderer, min_samples not a multiple of 10 — ends the program before anything is rendered.  The files written without the flag stay what they are.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -21,6 +25,7 @@
 #include <vector>
 
 #include "../../../include/pt_adaptive.h"
+#include "../../../include/pt_denoise.h"
 #include "../../../include/pt_scene_file.h"
 
 namespace {
@@ -33,12 +38,15 @@ struct Options {
     float adaptive = -1.0f;   // --adaptive REL: the relative error target; < 0 = off
     bool multi = false;       // --devices MASK: the node calls (pt_render_multi / pt_render_adaptive_multi)
     uint64_t device_mask = 0;
+    bool denoise = false;     // --denoise: <filename>_denoised.* next to the outputs
+    uint32_t guide_samples = 4;
 };
 
 int usage(const char* msg) {
     if (msg) fprintf(stderr, "error: %s\n", msg);
     fprintf(stderr, "usage: ptcli [--config FILE] [--scene FILE] [-n|--dry-run] [--stdout-log-level LEVEL] [--write-log-level LEVEL]\n"
-                    "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n");
+                    "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n"
+                    "             [--denoise] [--guide-samples K]\n");
     return 2;
 }
 
@@ -86,6 +94,13 @@ int main(int argc, char** argv) {
             if (end == v.c_str() || *end) return usage("--devices needs a device mask (bit d = HIP device d, 0 = all)");
             o.multi = true;
         }
+        else if (a == "--denoise") o.denoise = true;
+        else if (a == "--guide-samples") {
+            if (!value(&v)) return usage("--guide-samples needs a value");
+            char* end = nullptr;
+            o.guide_samples = (uint32_t)strtoul(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end || o.guide_samples == 0) return usage("--guide-samples needs a positive count");
+        }
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
     }
@@ -109,6 +124,27 @@ int main(int argc, char** argv) {
     const pt_scene_desc* desc = pt_scene_file_desc(scene_file);
     if (verbose) printf("scene %s: %u instances, %u meshes, %zu triangles, %u materials, %u curves\n", scene_path.c_str(), desc->instance_count, desc->mesh_count,
                         desc->index_count / 3, desc->material_count, desc->curve_count);
+
+    // --denoise: what the adaptive path refuses is refused here, with its message, before anything is rendered or written
+    if (o.denoise && !o.dry_run) {
+        uint32_t tw = 0, th = 0;
+        const bool naive = pt_config_renderer(config, &tw, &th) == PT_RENDERER_NAIVE;
+        for (uint32_t i = 0; i < pt_config_render_settings_count(config); ++i) {
+            pt_render_settings rs; pt_render_desc rd;
+            pt_config_render_settings(config, i, &rs);
+            if (pt_config_render_desc(config, i, o.seed, &rd) != PT_OK) continue;   // (skipped below as well)
+            const bool range = o.adaptive >= 0.0f && !naive && rs.max_samples >= 0 && (uint32_t)rs.max_samples > rd.spp;   // (--adaptive rounds a range up itself)
+            const char* why = naive ? "adaptive sampling needs phases of 10 samples (phase_samples 0 or 10)"
+                                    : ((!range && rd.spp % 10u != 0u) ? "spp, step and max_samples must be multiples of 10" : nullptr);
+            if (why) {
+                fprintf(stderr, "error: --denoise: render settings %u (%s, min_samples %u) cannot take the adaptive path the statistics come from: %s\n", i,
+                        naive ? "Naive renderer" : "Tiled renderer", rd.spp, why);
+                pt_scene_file_free(scene_file);
+                pt_config_free(config);
+                return 1;
+            }
+        }
+    }
 
     printf("constructing renderer\n");
     mkdir(o.output_dir.c_str(), 0777);                                                     // main.rs:155-158
@@ -146,13 +182,22 @@ int main(int argc, char** argv) {
                     rd.spp = lo; ad.max_samples = hi;
                 }
             }
-            std::vector<uint32_t> counts(adaptive ? (size_t)rd.width * rd.height : 0);
+            const bool with_counts = adaptive || o.denoise;
+            std::vector<uint32_t> counts(with_counts ? (size_t)rd.width * rd.height : 0);
+            std::vector<double> stats(o.denoise ? (size_t)rd.width * rd.height * 2 : 0);
             uint64_t samples = (uint64_t)rd.width * rd.height * rd.spp;
-            if (adaptive) {
+            if (!adaptive && o.denoise) {
+                // a fixed count through the adaptive path (max_samples = min_samples, one round): pt_render's film bit for bit, and the statistics
+                printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
+                ad.max_samples = rd.spp; ad.rel_error = 0.0f;
+                const pt_status st = o.multi ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), stats.data(), &prof)
+                                             : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), stats.data(), &prof);
+                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive", pt_last_error()); rc = 1; break; }
+            } else if (adaptive) {
                 printf("rendering %ux%u, %u..%u spp (adaptive, relative error %g), max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, ad.max_samples,
                        (double)ad.rel_error, rd.max_bounces, rd.light_samples);
-                const pt_status st = o.multi ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), nullptr, &prof)
-                                             : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), nullptr, &prof);
+                const pt_status st = o.multi ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof)
+                                             : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof);
                 if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive", pt_last_error()); rc = 1; break; }
                 uint32_t lo = 0xffffffffu, hi = 0;
                 samples = 0;
@@ -181,6 +226,25 @@ int main(int argc, char** argv) {
             }
             if (o.write_film && !write_npy(base + ".npy", film.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", base.c_str()); rc = 1; break; }
             printf("wrote %s.exr and %s.png\n", base.c_str(), base.c_str());
+            if (o.denoise) {
+                std::vector<float> guides((size_t)rd.width * rd.height * 4), clean((size_t)rd.width * rd.height * 4);
+                pt_denoise_desc dd;
+                memset(&dd, 0, sizeof(dd));
+                dd.width = rd.width; dd.height = rd.height;
+                if (o.multi && o.device_mask) while (!((o.device_mask >> dd.device) & 1u)) ++dd.device;   // (the first device of the mask: where the gather left the film)
+                if (pt_render_guides(scene, &rd, o.guide_samples, guides.data()) != PT_OK ||
+                    pt_denoise_film(&dd, film.data(), counts.data(), stats.data(), guides.data(), clean.data(), nullptr) != PT_OK) {
+                    fprintf(stderr, "--denoise: %s\n", pt_last_error()); rc = 1; break;
+                }
+                if (pt_output_film(&od, clean.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }
+                const std::string dbase = base + "_denoised";
+                if (pt_write_exr((dbase + ".exr").c_str(), rd.width, rd.height, linear.data(), od.colorspace) != PT_OK ||
+                    pt_write_png((dbase + ".png").c_str(), rd.width, rd.height, rgba.data(), od.colorspace) != PT_OK) {
+                    fprintf(stderr, "failed to write files: %s\n", pt_last_error()); rc = 1; break;
+                }
+                if (o.write_film && !write_npy(dbase + ".npy", clean.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", dbase.c_str()); rc = 1; break; }
+                printf("wrote %s.exr and %s.png\n", dbase.c_str(), dbase.c_str());
+            }
         }
         if (scene) pt_scene_destroy(scene);
         if (rc == 0) printf("render done\n");

@@ -26,7 +26,9 @@
 #include "../../include/pt_adaptive.h"
 #include "../../include/pt_api.h"
 #include "../../include/pt_debug.h"
+#include "../../include/pt_denoise.h"
 #include "pt_adaptive_select.h"
+#include "pt_denoise_launch.h"
 #include "pt_error.h"
 #include "pt_plan.h"
 #include "pt_scene_host.h"
@@ -1309,6 +1311,37 @@ pt_status pt_camera_samples(pt_scene* sc, const pt_render_desc* rdp, size_t n, c
     HIP_TRY(hipMemcpy(origins, dor.p, 12 * n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(directions, dd.p, 12 * n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(lambda, dl.p, 4 * n, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// include/pt_denoise.h: the guides of the film denoiser.  Per sample index k the camera rays of every pixel (stage_generate, as pt_camera_samples runs it), the
+// closest hits as pt_intersect finds them (the probe kernel in the scene's own staging mode), and the fold of the hit records in k order (pt_denoise.hip).
+pt_status pt_render_guides(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, float* guides) {
+    std::string err;
+    pt_status st = pth::check_guides_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, guides, &err);
+    if (st != PT_OK) return fail(st, err);
+    HIP_TRY(hipSetDevice(sc->device));
+    const uint32_t n = rdp->width * rdp->height;
+    RenderParams rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.seed = rdp->seed; rp.width = rdp->width; rp.height = rdp->height;
+    rp.wavelength_lo = rdp->wavelength_lo; rp.wavelength_span = rdp->wavelength_hi - rdp->wavelength_lo;
+    rp.camera = pth::camera_params(sc->host.cameras[rdp->camera_index], (float)rdp->width / (float)rdp->height);
+    rp.chunk_pixels = 1;
+    DevBuf dor, dd, dh, dsum, dg;
+    HIP_TRY(dor.alloc(12 * (size_t)n)); HIP_TRY(dd.alloc(12 * (size_t)n)); HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n));
+    HIP_TRY(dsum.alloc(sizeof(DnGuideSum) * (size_t)n)); HIP_TRY(dg.alloc(16 * (size_t)n));
+    const int grid = sc->num_cus * 4;
+    const uint32_t lds_bytes = sc->lds_mode == PT_LDS_ALL ? sc->blob_words * 4u : (sc->lds_mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
+    for (uint32_t k = 0; k < guide_samples; ++k) {
+        launch_guide_rays(rp, n, k, dor.as<float>(), dd.as<float>());
+        launch_probe_intersect(LaunchCfg{grid, lds_bytes, (hipStream_t)0, sc->lds_mode}, SceneArgs{sc->d_blob, sc->blob_words, sc->d_tex}, n, dor.as<float>(), dd.as<float>(), dh.as<pt_hit>());
+        launch_guide_fold(n, dh.as<pt_hit>(), dsum.as<DnGuideSum>(), k == 0);
+    }
+    launch_guide_finish(n, dsum.as<DnGuideSum>(), guide_samples, dg.as<float>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(guides, dg.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

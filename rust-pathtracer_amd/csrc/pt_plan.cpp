@@ -1,4 +1,5 @@
 #include "pt_plan.h"
+#include "pt_denoise_rules.h"
 
 #include <cmath>
 
@@ -134,6 +135,43 @@ pt_status normalize_adaptive_desc(const pt_render_desc& in, const pt_adaptive_de
     if (!normalize_render_desc(in, camera_count, &rd, error)) return PT_ERR_INVALID_ARGUMENT;
     *out = rd;
     *adaptive_out = a;
+    return PT_OK;
+}
+
+pt_status normalize_denoise_desc(const pt_denoise_desc* in, const void* film, const void* sample_counts, const void* stats, const void* guides, const void* out_film,
+                                 pt_denoise_desc* out, std::string* error) {
+    if (!in || !film || !sample_counts || !stats || !guides || !out_film) { *error = "null argument"; return PT_ERR_INVALID_ARGUMENT; }
+    pt_denoise_desc d = *in;
+    if (d.width == 0 || d.height == 0) { *error = "width and height must be positive"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((uint64_t)d.width * (uint64_t)d.height > 0x7fffffffull) { *error = "width x height must fit 31 bits"; return PT_ERR_INVALID_ARGUMENT; }
+    if (d.reserved[0] != 0) { *error = "reserved must be 0"; return PT_ERR_INVALID_ARGUMENT; }
+    if (d.iterations > (uint32_t)ptd::DN_MAX_ITERATIONS) { *error = "iterations: at most 10"; return PT_ERR_INVALID_ARGUMENT; }
+    if (d.normal_power_log2 > (uint32_t)ptd::DN_MAX_NORMAL_POWER_LOG2) { *error = "normal_power_log2: at most 10"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!(d.sigma_luminance >= 0.0f) || !pt_isfinite(d.sigma_luminance)) { *error = "sigma_luminance must be finite and >= 0"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!(d.sigma_depth >= 0.0f) || !pt_isfinite(d.sigma_depth)) { *error = "sigma_depth must be finite and >= 0"; return PT_ERR_INVALID_ARGUMENT; }
+    if (d.iterations == 0) d.iterations = (uint32_t)ptd::DN_DEFAULT_ITERATIONS;
+    if (d.normal_power_log2 == 0) d.normal_power_log2 = (uint32_t)ptd::DN_DEFAULT_NORMAL_POWER_LOG2;
+    if (d.sigma_luminance == 0.0f) d.sigma_luminance = DN_DEFAULT_SIGMA_LUMINANCE;
+    if (d.sigma_depth == 0.0f) d.sigma_depth = DN_DEFAULT_SIGMA_DEPTH;
+    *out = d;
+    return PT_OK;
+}
+
+pt_status check_denoise_inputs(const pt_denoise_desc& d, const uint32_t* sample_counts, const float* guides, std::string* error) {
+    const size_t np = (size_t)d.width * d.height;
+    for (size_t p = 0; p < np; ++p)
+        if (sample_counts[p] < 2u) { *error = "a sample count below 2: the variance of a mean needs two samples"; return PT_ERR_INVALID_ARGUMENT; }
+    for (size_t i = 0; i < 4 * np; ++i)
+        if (!pt_isfinite(guides[i])) { *error = "a guide value is not finite"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
+pt_status check_guides_args(const void* scene, const pt_render_desc* rd, uint32_t camera_count, uint32_t guide_samples, const void* guides, std::string* error) {
+    if (!scene || !rd || !guides) { *error = "null argument"; return PT_ERR_INVALID_ARGUMENT; }
+    if (guide_samples == 0) { *error = "guide_samples must be positive"; return PT_ERR_INVALID_ARGUMENT; }
+    if (rd->width == 0 || rd->height == 0 || rd->camera_index >= camera_count) { *error = "width, height must be positive, camera_index in range"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!(rd->wavelength_hi >= rd->wavelength_lo)) { *error = "wavelength_hi must not be below wavelength_lo"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((uint64_t)rd->width * (uint64_t)rd->height > 0x7fffffffull) { *error = "width x height must fit 31 bits"; return PT_ERR_INVALID_ARGUMENT; }
     return PT_OK;
 }
 

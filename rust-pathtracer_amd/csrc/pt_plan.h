@@ -9,6 +9,7 @@
 
 #include "../../include/pt_adaptive.h"
 #include "../../include/pt_api.h"
+#include "../../include/pt_denoise.h"
 #include "pt_stages.h"
 
 namespace pth {
@@ -32,6 +33,14 @@ bool normalize_render_desc(const pt_render_desc& in, uint32_t camera_count, pt_r
 // adaptive desc (step 0 -> spp), or PT_ERR_INVALID_ARGUMENT / PT_ERR_UNSUPPORTED with the reason in *error.
 pt_status normalize_adaptive_desc(const pt_render_desc& in, const pt_adaptive_desc& adaptive, bool has_sample_counts, uint32_t camera_count,
                                   pt_render_desc* out, pt_adaptive_desc* adaptive_out, std::string* error);
+
+// pt_denoise_film's and pt_render_guides' arguments (include/pt_denoise.h), for the engine and the host emulation alike.  normalize_denoise_desc: PT_OK
+// with the defaults filled in (iterations 0 -> 5, sigmas 0 -> 4 and 1, normal_power_log2 0 -> 7), or PT_ERR_INVALID_ARGUMENT with the reason in *error.
+// check_denoise_inputs: every sample count at least 2 (the variance of a mean needs two samples), every guide value finite.
+pt_status normalize_denoise_desc(const pt_denoise_desc* in, const void* film, const void* sample_counts, const void* stats, const void* guides, const void* out_film,
+                                 pt_denoise_desc* out, std::string* error);
+pt_status check_denoise_inputs(const pt_denoise_desc& d, const uint32_t* sample_counts, const float* guides, std::string* error);
+pt_status check_guides_args(const void* scene, const pt_render_desc* rd, uint32_t camera_count, uint32_t guide_samples, const void* guides, std::string* error);
 
 }  // namespace pth
 #endif

@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""The film denoiser (include/pt_denoise.h): what it buys and what it costs.
+
+  python3 tools/denoise_quality.py [--size 256] [--spp 20,40,80] [--ref-spp 4096] [--out profiles/denoise_quality.json]
+  python3 tools/denoise_quality.py --emulation [--out ...]     the definition on the CPU (48x48, 20 spp against 1000 spp: the case tests/test_denoise.py asserts)
+  python3 tools/denoise_quality.py --one-pass 1024             one 1024x1024 render, guides and filter call (the program to run under rocprofv3 --kernel-trace --stats)
+
+Quality: Cornell box, the gem scene, mixed_primitives and hdri_small at size x size, max_bounces 6, seed 1, the defaults of pt_denoise_desc, guides of 4
+samples.  Against a reference render of another seed (77), RMSE over XYZ of the noisy and of the denoised film, their ratio, and the shift of the mean Y.
+Cost: median wall seconds of pt_render_guides and pt_denoise_film (host arrays in and out: transfers and allocations included) beside the render's.
+--out merges into an existing file: the GPU run and the emulation run fill their own keys."""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+SCENES = ("cornell_box", "cornell_gem", "mixed_primitives", "hdri_small")
+BOUNCES = 6
+
+
+def rmse(a, b):
+    return float(np.sqrt(np.mean((a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64)) ** 2)))
+
+
+def timed(fn, reps):
+    out, secs = None, []
+    for _ in range(reps):
+        t = time.perf_counter()
+        out = fn()
+        secs.append(time.perf_counter() - t)
+    return out, statistics.median(secs)
+
+
+def emulation_library(pkg):
+    emu_dir, csrc = os.path.join(ROOT, "tests", "host_emulation"), os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
+    lib = os.path.join(emu_dir, "libptemu_denoise.so")
+    srcs = [os.path.join(emu_dir, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_denoise.cpp")] + [os.path.join(csrc, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
+    if not os.path.exists(lib):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-o", lib] + srcs)
+    return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+
+
+def measure(lib, pkg, name, size, spp, ref, reps):
+    sc = lib.create_scene(getattr(pkg.scene, name)())
+    rd = pkg.api.render_desc(size, size, spp, BOUNCES, seed=1)
+    (film, counts, st, _), t_render = timed(lambda: sc.render_adaptive(rd, spp, 0.0, stats=True), reps)
+    guides, t_guides = timed(lambda: sc.render_guides(rd, 4), reps)
+    den, t_filter = timed(lambda: lib.denoise_film(film, counts, st, guides), reps)
+    e0, e1 = rmse(film, ref), rmse(den, ref)
+    return {"spp": spp, "rmse_noisy": e0, "rmse_denoised": e1, "ratio": e1 / e0, "mean_y_noisy": float(film[..., 1].mean()), "mean_y_denoised": float(den[..., 1].mean()),
+            "mean_y_shift": float(den[..., 1].mean() / film[..., 1].mean() - 1.0), "render_seconds": t_render, "guides_seconds": t_guides, "filter_seconds": t_filter}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--spp", default="20,40,80")
+    ap.add_argument("--ref-spp", type=int, default=4096)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--emulation", action="store_true")
+    ap.add_argument("--one-pass", type=int, default=0, metavar="SIZE")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    pkg = importlib.import_module("rust-pathtracer_amd")
+    if args.one_pass:
+        engine = pkg.load()
+        sc = engine.create_scene(pkg.scene.cornell_box())
+        rd = pkg.api.render_desc(args.one_pass, args.one_pass, 20, BOUNCES, seed=1)
+        film, den, counts, _ = sc.render_denoised(rd)
+        print("denoised %dx%d: mean Y %.6g -> %.6g" % (args.one_pass, args.one_pass, film[..., 1].mean(), den[..., 1].mean()))
+        return
+    if args.emulation:
+        lib, key, size, spps, ref_spp, reps = emulation_library(pkg), "emulation_48", 48, [20], 1000, 1
+    else:
+        lib, key, size, spps, ref_spp, reps = pkg.load(), "gpu_%d" % args.size, args.size, [int(s) for s in args.spp.split(",")], args.ref_spp, args.reps
+    record = {"command": "python3 tools/denoise_quality.py " + " ".join(sys.argv[1:]), "device": "host emulation (CPU)" if args.emulation else lib.device_info(), "size": size, "reference_spp": ref_spp,
+              "reference_seed": 77, "max_bounces": BOUNCES, "guide_samples": 4, "scenes": {}}
+    for name in SCENES:
+        ref, _ = lib.create_scene(getattr(pkg.scene, name)()).render(pkg.api.render_desc(size, size, ref_spp, BOUNCES, seed=77))
+        record["scenes"][name] = [measure(lib, pkg, name, size, spp, ref, reps) for spp in spps]
+        print(name, json.dumps(record["scenes"][name], indent=1), flush=True)
+    if args.out:
+        whole = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        whole[key] = record
+        with open(args.out, "w") as f:
+            json.dump(whole, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -10,8 +10,14 @@
  *              (dot^(2^a)), of the depths (against the depth gradient) and of the Y values (against sigma_luminance x the square root of the
  *              two pixels' 3x3-filtered variances); colours are averaged with w, variances with w^2
  *
+ *   albedo     per pixel the mean, over the same camera samples, of the first hit's reflectance as XYZ factors: a Lambertian hit's texture stack at
+ *              PT_ALBEDO_WAVELENGTHS wavelengths (clamped to 1 as the material clamps it) weighted by the colour-matching functions and normalised
+ *              by their sums; every other hit, and a miss, counts as (1, 1, 1)
+ *
  * Pixels with a non-finite film channel or variance are copied through and never read.  The engine, the emulation and a numpy restatement agree
- * bit for bit.  Albedo is not demodulated: a textured Lambertian surface is protected by the luminance weight alone. */
+ * bit for bit.  pt_denoise_film does not demodulate albedo: a textured Lambertian surface is protected by the luminance weight alone.
+ * pt_denoise_film_albedo does: the film is divided by max(albedo, 1e-3) before the passes (the variance by the square of the Y factor) and
+ * multiplied by it afterwards, so that the filter averages irradiance and the texture is put back unfiltered. */
 #ifndef PT_DENOISE_H
 #define PT_DENOISE_H
 #include "pt_api.h"
@@ -39,6 +45,22 @@ pt_status pt_render_guides(pt_scene* scene, const pt_render_desc* desc, uint32_t
  * film's variance estimate, may be NULL.  Host arrays in, host arrays out; out_film_xyzw may be film_xyzw. */
 pt_status pt_denoise_film(const pt_denoise_desc* desc, const float* film_xyzw, const uint32_t* sample_counts, const double* stats,
                           const float* guides_xyzw, float* out_film_xyzw, float* out_variance);
+
+#define PT_ALBEDO_WAVELENGTHS 16
+
+/* The basis of the albedo for `desc`'s wavelength bounds: lambda = 16 f32 (nm), xyz = 48 f32 (the X, Y and Z weights of the 16 wavelengths, in
+ * this order).  Host only: no device is needed. */
+pt_status pt_albedo_basis(const pt_render_desc* desc, float* lambda, float* xyz);
+
+/* pt_render_guides with a second output from the same probes: albedo_xyzw = width*height*4 f32 (W = 0).  guides_xyzw is bit for bit
+ * pt_render_guides' output. */
+pt_status pt_render_guides_albedo(pt_scene* scene, const pt_render_desc* desc, uint32_t guide_samples, float* guides_xyzw, float* albedo_xyzw);
+
+/* pt_denoise_film on the film demodulated by albedo_xyzw (pt_render_guides_albedo's output: every channel finite and >= 0).  A pixel that the
+ * division makes non-finite is copied through like any dead pixel.  albedo_xyzw NULL = pt_denoise_film; an albedo of ones gives its output bit
+ * for bit. */
+pt_status pt_denoise_film_albedo(const pt_denoise_desc* desc, const float* film_xyzw, const uint32_t* sample_counts, const double* stats,
+                                 const float* guides_xyzw, const float* albedo_xyzw, float* out_film_xyzw, float* out_variance);
 
 #ifdef __cplusplus
 }

@@ -244,6 +244,11 @@ class Library:
         self._render_guides = bind("render_guides", C.c_int32, [vp, C.POINTER(RenderDesc), u32, fpp], required=False)
         self._denoise_film = bind("denoise_film", C.c_int32, [C.POINTER(DenoiseDesc), fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp], required=False)
         self._denoise_last_error = bind("denoise_last_error", C.c_char_p, [], required=False)   # (the emulation's: the engine reports through pt_last_error)
+        self._albedo_basis = bind("albedo_basis", C.c_int32, [C.POINTER(RenderDesc), fpp, fpp], required=False)
+        self._render_guides_albedo = bind("render_guides_albedo", C.c_int32, [vp, C.POINTER(RenderDesc), u32, fpp, fpp], required=False)
+        self._denoise_film_albedo = bind("denoise_film_albedo", C.c_int32, [C.POINTER(DenoiseDesc), fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp],
+                                         required=False)
+        self._denoise_albedo_last_error = bind("denoise_albedo_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the three entries above)
         self._device_info = bind("device_info", C.c_char_p, [], required=False)
         self._output_film = bind("output_film", C.c_int32, [C.POINTER(OutputDesc), fpp, C.POINTER(C.c_uint8), fpp], required=False)
         self._write_png = bind("write_png", C.c_int32, [C.c_char_p, u32, u32, C.POINTER(C.c_uint8), C.c_int32], required=False)
@@ -296,11 +301,27 @@ class Library:
         self.check(self._compare_films(w, h, _fp(image), _fp(truth), mode, _fp(out) if want_image else None, C.byref(st)))
         return out, st
 
-    def denoise_film(self, film, counts, stats, guides, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, device=0, variance=False):
+    def albedo_basis(self, rd):
+        """pt_albedo_basis: the wavelengths [16] (nm) and the X, Y, Z weights [3,16] the albedo of a render `rd` is folded over."""
+        if self._albedo_basis is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %salbedo_basis entry" % (self.path, self.prefix))
+        lam, xyz = np.zeros(16, np.float32), np.zeros((3, 16), np.float32)
+        st = self._albedo_basis(C.byref(rd), _fp(lam), _fp(xyz))
+        if st != PT_OK:
+            raise PtError(st, self._albedo_error())
+        return lam, xyz
+
+    def _albedo_error(self):
+        err = self._denoise_albedo_last_error
+        return err().decode() if err else self.last_error()
+
+    def denoise_film(self, film, counts, stats, guides, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, device=0, variance=False, albedo=None):
         """pt_denoise_film: the edge-avoiding filter over an adaptive render's film [H,W,4], counts [H,W] u32 and stats [H,W,2] f64 with the guides
-        [H,W,4] of Scene.render_guides.  0 selects a parameter's default.  Returns the filtered film [H,W,4], with variance=True (film, variance [H,W])."""
-        if self._denoise_film is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sdenoise_film entry" % (self.path, self.prefix))
+        [H,W,4] of Scene.render_guides.  0 selects a parameter's default.  Returns the filtered film [H,W,4], with variance=True (film, variance [H,W]).
+        `albedo` [H,W,4] (Scene.render_guides_albedo's): pt_denoise_film_albedo, the filter over the film demodulated by it."""
+        entry, name = (self._denoise_film, "denoise_film") if albedo is None else (self._denoise_film_albedo, "denoise_film_albedo")
+        if entry is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %s%s entry" % (self.path, self.prefix, name))
         film = np.ascontiguousarray(film, dtype=np.float32)
         counts = np.ascontiguousarray(counts, dtype=np.uint32)
         stats = np.ascontiguousarray(stats, dtype=np.float64)
@@ -311,9 +332,17 @@ class Library:
         d = DenoiseDesc(w, h, iterations, sigma_luminance, sigma_depth, normal_power_log2, device)
         out = np.zeros((h, w, 4), np.float32)
         var = np.zeros((h, w), np.float32) if variance else None
-        st = self._denoise_film(C.byref(d), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)), stats.ctypes.data_as(C.POINTER(C.c_double)), _fp(guides),
-                                _fp(out), _fp(var) if variance else None)
+        planes = [_fp(guides)]
+        if albedo is not None:
+            albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+            if albedo.shape != (h, w, 4):
+                raise ValueError("albedo [H,W,4] of the film's size")
+            planes.append(_fp(albedo))
+        st = entry(C.byref(d), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)), stats.ctypes.data_as(C.POINTER(C.c_double)), *planes,
+                   _fp(out), _fp(var) if variance else None)
         if st != PT_OK:
+            if albedo is not None:
+                raise PtError(st, self._albedo_error())
             raise PtError(st, self._denoise_last_error().decode() if self._denoise_last_error else self.last_error())
         return (out, var) if variance else out
 
@@ -405,10 +434,23 @@ class Scene:
             raise PtError(st, err().decode() if err else self.library.last_error())
         return g
 
+    def render_guides_albedo(self, rd, samples=4):
+        """pt_render_guides_albedo: (guides, albedo), [H,W,4] f32 each — render_guides' output and, from the same probes, the mean first-hit albedo as XYZ
+        factors (W = 0)."""
+        if self.library._render_guides_albedo is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_guides_albedo entry" % (self.library.path, self.library.prefix))
+        g = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        a = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        st = self.library._render_guides_albedo(self.handle, C.byref(rd), samples, _fp(g), _fp(a))
+        if st != PT_OK:
+            raise PtError(st, self.library._albedo_error())
+        return g, a
+
     def render_denoised(self, rd, max_samples=None, rel_error=0.0, abs_error=0.0, step=0, guide_samples=4, iterations=0, sigma_luminance=0.0, sigma_depth=0.0,
-                        normal_power_log2=0, device_mask=None):
+                        normal_power_log2=0, device_mask=None, albedo=False):
         """An adaptive render with statistics (max_samples None = rd.spp: a fixed count), its guides, and the filter: (film, denoised, counts, profile).
-        `device_mask` (not None) routes the render through render_adaptive_multi; the filter then runs on the first device of the mask."""
+        `device_mask` (not None) routes the render through render_adaptive_multi; the filter then runs on the first device of the mask.  `albedo`: the
+        guides come with the albedo (render_guides_albedo) and the filter demodulates the film by it."""
         mx = rd.spp if max_samples is None else max_samples
         if device_mask is None:
             film, counts, st, prof = self.render_adaptive(rd, mx, rel_error, abs_error, step, stats=True)
@@ -416,8 +458,11 @@ class Scene:
         else:
             film, counts, st, prof = self.render_adaptive_multi(rd, mx, rel_error, abs_error, step, stats=True, device_mask=device_mask)
             device = (device_mask & -device_mask).bit_length() - 1 if device_mask else 0
-        guides = self.render_guides(rd, guide_samples)
-        den = self.library.denoise_film(film, counts, st, guides, iterations, sigma_luminance, sigma_depth, normal_power_log2, device)
+        if albedo:
+            guides, alb = self.render_guides_albedo(rd, guide_samples)
+        else:
+            guides, alb = self.render_guides(rd, guide_samples), None
+        den = self.library.denoise_film(film, counts, st, guides, iterations, sigma_luminance, sigma_depth, normal_power_log2, device, albedo=alb)
         return film, den, counts, prof
 
     def render_multi(self, rd, device_mask=0):

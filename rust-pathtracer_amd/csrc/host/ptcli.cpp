@@ -3,7 +3,7 @@
 // output/<filename>.exr and .png through the film output stage (src/renderer/mod.rs:24-80).
 //
 //   ptcli [--config data/config.toml] [--scene FILE] [-n|--dry-run] [--stdout-log-level L] [--write-log-level L]
-//         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K]
+//         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K] [--demodulate-albedo]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -15,6 +15,8 @@
 // --guide-samples K camera samples (default 4).  The filter needs the per-pixel statistics, which the adaptive path alone returns: every setting is rendered
 // through pt_render_adaptive (max_samples = min_samples without --adaptive: the same film, bit for bit, as pt_render's), and a setting that path refuses — the
 // Naive renderer, min_samples not a multiple of 10 — ends the program before anything is rendered.  The files written without the flag stay what they are.
+// --demodulate-albedo (with --denoise only) filters the film divided by the first-hit albedo: pt_render_guides_albedo and pt_denoise_film_albedo write the same
+// <filename>_denoised.* files.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -40,13 +42,14 @@ struct Options {
     uint64_t device_mask = 0;
     bool denoise = false;     // --denoise: <filename>_denoised.* next to the outputs
     uint32_t guide_samples = 4;
+    bool demodulate = false;  // --demodulate-albedo: the denoised files through the albedo entries
 };
 
 int usage(const char* msg) {
     if (msg) fprintf(stderr, "error: %s\n", msg);
     fprintf(stderr, "usage: ptcli [--config FILE] [--scene FILE] [-n|--dry-run] [--stdout-log-level LEVEL] [--write-log-level LEVEL]\n"
                     "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n"
-                    "             [--denoise] [--guide-samples K]\n");
+                    "             [--denoise] [--guide-samples K] [--demodulate-albedo]\n");
     return 2;
 }
 
@@ -95,6 +98,7 @@ int main(int argc, char** argv) {
             o.multi = true;
         }
         else if (a == "--denoise") o.denoise = true;
+        else if (a == "--demodulate-albedo") o.demodulate = true;
         else if (a == "--guide-samples") {
             if (!value(&v)) return usage("--guide-samples needs a value");
             char* end = nullptr;
@@ -104,6 +108,7 @@ int main(int argc, char** argv) {
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
     }
+    if (o.demodulate && !o.denoise) return usage("--demodulate-albedo needs --denoise");
     const bool verbose = o.stdout_log_level == "info" || o.stdout_log_level == "debug" || o.stdout_log_level == "trace";
     const bool warnings = verbose || o.stdout_log_level == "warn";
     if (!o.root.empty()) pt_scene_file_set_root(o.root.c_str());
@@ -232,8 +237,11 @@ int main(int argc, char** argv) {
                 memset(&dd, 0, sizeof(dd));
                 dd.width = rd.width; dd.height = rd.height;
                 if (o.multi && o.device_mask) while (!((o.device_mask >> dd.device) & 1u)) ++dd.device;   // (the first device of the mask: where the gather left the film)
-                if (pt_render_guides(scene, &rd, o.guide_samples, guides.data()) != PT_OK ||
-                    pt_denoise_film(&dd, film.data(), counts.data(), stats.data(), guides.data(), clean.data(), nullptr) != PT_OK) {
+                std::vector<float> albedo(o.demodulate ? (size_t)rd.width * rd.height * 4 : 0);
+                const pt_status gst = o.demodulate ? pt_render_guides_albedo(scene, &rd, o.guide_samples, guides.data(), albedo.data())
+                                                   : pt_render_guides(scene, &rd, o.guide_samples, guides.data());
+                if (gst != PT_OK || pt_denoise_film_albedo(&dd, film.data(), counts.data(), stats.data(), guides.data(), o.demodulate ? albedo.data() : nullptr,
+                                                           clean.data(), nullptr) != PT_OK) {
                     fprintf(stderr, "--denoise: %s\n", pt_last_error()); rc = 1; break;
                 }
                 if (pt_output_film(&od, clean.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }

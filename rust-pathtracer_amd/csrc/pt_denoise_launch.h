@@ -17,5 +17,15 @@ void launch_guide_fold(uint32_t n_pixels, const pt_hit* hits, ptd::DnGuideSum* s
 // guides[p] = (N / samples, hits ? Z / hits : 0)
 void launch_guide_finish(uint32_t n_pixels, const ptd::DnGuideSum* sums, uint32_t samples, float* guides_xyzw);
 
+// The albedo guide.  layer_off: the blob word offsets of the `rows` texture layers of the scene's Lambertian materials; table: rows x 16 float4, the layers'
+// curve values at the basis wavelengths; material_row[m]: the first row of material m's layers.  albedo_sums: n_pixels float4.
+void albedo_basis(float wavelength_lo, float wavelength_hi, ptd::DnAlbedoBasis* basis);   // (host)
+void launch_albedo_tables(const uint32_t* blob, const float* tex, const ptd::DnAlbedoBasis& basis, uint32_t rows, const uint32_t* layer_off, float* table);
+// launch_guide_fold plus albedo_sums[p] += the hit's albedo
+void launch_guide_fold_albedo(uint32_t n_pixels, const pt_hit* hits, ptd::DnGuideSum* sums, float* albedo_sums, bool first, const uint32_t* blob, const float* tex,
+                              uint32_t material_count, const uint32_t* material_row, const float* table, const ptd::DnAlbedoBasis& basis);
+// launch_guide_finish plus albedo[p] = albedo_sums[p] / samples (W = 0)
+void launch_guide_finish_albedo(uint32_t n_pixels, const ptd::DnGuideSum* sums, const float* albedo_sums, uint32_t samples, float* guides_xyzw, float* albedo_xyzw);
+
 }  // namespace ptk
 #endif

@@ -1,8 +1,9 @@
 // pt_denoise_rules.h — the rules of the film denoiser (include/pt_denoise.h) as PT_HD functions that the engine's kernels
-// (pt_denoise.hip) and the host emulation of the tests (tests/host_emulation/ptemu_denoise.cpp) compile from the same text: the guide fold, the
-// prepared inputs (variance of the mean from the f64 statistics, dead mask, unit normals, depth gradient), the 3x3 variance tent and the 25-tap
-// edge-avoiding gather of one a-trous pass.  All arithmetic is f32 unless a double is written, evaluated without contraction and in the order
-// written here; a numpy restatement (tests/test_denoise.py) gets every result bit for bit.
+// (pt_denoise.hip) and the host emulation of the tests (tests/host_emulation/ptemu_denoise.cpp, ptemu_denoise_albedo.cpp) compile from the same
+// text: the guide fold, the prepared inputs (variance of the mean from the f64 statistics, dead mask, unit normals, depth gradient), the 3x3
+// variance tent and the 25-tap edge-avoiding gather of one a-trous pass, and (last in the file) the albedo guide with the film's demodulation by
+// it.  All arithmetic is f32 unless a double is written, evaluated without contraction and in the order written here; a numpy restatement
+// (tests/test_denoise.py, tests/test_denoise_albedo.py) gets every result bit for bit.
 //
 // The pixel functions are templates over a source `S` of the pass's inputs, so that a kernel may hand them global memory or a tile it staged:
 //   uint32_t S::flags(int x, int y)   DN_DEAD | DN_SKY of an in-film pixel
@@ -13,6 +14,7 @@
 #define PT_DENOISE_RULES_H
 #include <stdint.h>
 
+#include "../../include/pt_api.h"
 #include "../../include/pt_numerics.h"
 
 namespace ptd {
@@ -135,6 +137,113 @@ PT_HD DnColor dn_gather_pixel(const S& src, const DnParams& P, int step, int x, 
         }
     DnColor o;
     o.x = sx / sw; o.y = sy / sw; o.z = sz / sw; o.v = sv / (sw * sw);
+    return o;
+}
+
+// ---- albedo: the first-hit reflectance of a Lambertian surface as XYZ factors, and the film divided by it before the passes
+// The basis: DN_ALBEDO_WAVELENGTHS wavelengths at the centres of equal parts of the render's range, each with its colour-matching weights
+// w[c][j] = xyz_bar(lambda_j x 10) (the form k_accumulate uses) and norm[c] = sum_j w[c][j], j ascending.  `X`: void (float angstrom, float*, float*, float*).
+enum { DN_ALBEDO_WAVELENGTHS = 16 };
+#define DN_ALBEDO_FLOOR 1e-3f
+struct DnAlbedoBasis { float lambda[DN_ALBEDO_WAVELENGTHS]; float w[3][DN_ALBEDO_WAVELENGTHS]; float norm[3]; };
+struct DnAlbedo { float x, y, z; };
+struct DnTexel { uint32_t kind; float t0, t1, t2, t3; };   // a layer's texel at one (u, v): PT_TEXTURE1 holds t0 alone
+struct DnLayerCurves { float c0, c1, c2, c3; };            // a layer's curves at one wavelength (layer_curves of pt_device.h)
+
+PT_HD float dn_albedo_lambda(float lo, float hi, int j) { return lo + ((float)j + 0.5f) * ((hi - lo) / 16.0f); }
+template <class X>
+PT_HD void dn_albedo_basis(float lo, float hi, const X& xyz_bar_of, DnAlbedoBasis* B) {
+    for (int j = 0; j < DN_ALBEDO_WAVELENGTHS; ++j) {
+        B->lambda[j] = dn_albedo_lambda(lo, hi, j);
+        xyz_bar_of(B->lambda[j] * 10.0f, &B->w[0][j], &B->w[1][j], &B->w[2][j]);
+    }
+    for (int c = 0; c < 3; ++c) {
+        float s = 0.0f;
+        for (int j = 0; j < DN_ALBEDO_WAVELENGTHS; ++j) s = s + B->w[c][j];
+        B->norm[c] = s;
+    }
+}
+
+// whether a hit has a material record to look at: valid, not the camera's own tag, the index inside the scene's materials
+PT_HD bool dn_albedo_has_record(int valid, uint32_t material_id, uint32_t material_count) {
+    return valid && PT_MATERIAL_TAG(material_id) != (uint32_t)PT_TAG_CAMERA && PT_MATERIAL_INDEX(material_id) < material_count;
+}
+// the texel(s) of the layer record at word `l` of the blob `w` (pt_blob.h: kind, four curves, width, height, texel offset) that layer_eval reads at (u, v)
+PT_HD DnTexel dn_albedo_texel(const uint32_t* w, const float* tex, uint32_t l, float u, float v) {
+    const uint32_t kind = w[l], tw = w[l + 5], th = w[l + 6], toff = w[l + 7];
+    const float cu = pt_clamp(u, 0.0f, 1.0f - PT_F32_EPSILON), cv = pt_clamp(v, 0.0f, 1.0f - PT_F32_EPSILON);
+    uint32_t x = (uint32_t)(cu * (float)tw), y = (uint32_t)(cv * (float)th);
+    x = x < tw ? x : tw - 1u; y = y < th ? y : th - 1u;   // (never taken for a (u, v) in [0, 1]: no read leaves the texture whatever the hit record holds)
+    const uint32_t idx = y * tw + x;
+    DnTexel t;
+    t.kind = kind; t.t1 = t.t2 = t.t3 = 0.0f;
+    if (kind == (uint32_t)PT_TEXTURE1) { t.t0 = tex[toff + idx]; return t; }
+    const float* p = tex + toff + 4u * idx;
+    t.t0 = p[0]; t.t1 = p[1]; t.t2 = p[2]; t.t3 = p[3];
+    return t;
+}
+// layer_eval's value from the texel and the curves
+PT_HD float dn_layer_value(const DnTexel& t, const DnLayerCurves& c) {
+    if (t.kind == (uint32_t)PT_TEXTURE1) return c.c0 * t.t0;
+    const float e0 = c.c0 * t.t0, e1 = c.c1 * t.t1;
+    const float e2 = c.c2 * t.t2, e3 = c.c3 * t.t3;
+    return (e0 + e1) + (e2 + e3);
+}
+// a Lambertian hit's albedo: rho_j = min(texstack_eval(lambda_j, u, v), 1) — the bits material_prepare puts into its reflectance — folded over the basis.
+// The texels depend on (u, v) only: a layer's are fetched once for the 16 wavelengths.  `T`: the hit's texture stack,
+//   uint32_t T::layers()   DnTexel T::texel(uint32_t layer)   DnLayerCurves T::curves(uint32_t layer, int j)
+template <class T>
+PT_HD DnAlbedo dn_albedo_lambertian(const T& stack, const DnAlbedoBasis& B) {
+    float energy[DN_ALBEDO_WAVELENGTHS];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < DN_ALBEDO_WAVELENGTHS; ++j) energy[j] = 0.0f;
+    const uint32_t layers = stack.layers();
+    for (uint32_t i = 0; i < layers; ++i) {
+        const DnTexel t = stack.texel(i);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int j = 0; j < DN_ALBEDO_WAVELENGTHS; ++j) energy[j] = energy[j] + dn_layer_value(t, stack.curves(i, j));
+    }
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < DN_ALBEDO_WAVELENGTHS; ++j) {
+        const float rho = pt_min(energy[j], 1.0f);
+        sx = sx + rho * B.w[0][j]; sy = sy + rho * B.w[1][j]; sz = sz + rho * B.w[2][j];
+    }
+    DnAlbedo a;
+    a.x = B.norm[0] > 0.0f ? sx / B.norm[0] : 1.0f;
+    a.y = B.norm[1] > 0.0f ? sy / B.norm[1] : 1.0f;
+    a.z = B.norm[2] > 0.0f ? sz / B.norm[2] : 1.0f;
+    return a;
+}
+// A(p) = (sum_k a_k) / K, the samples in order; everything but a valid Lambertian hit adds (1, 1, 1)
+PT_HD void dn_albedo_add(DnAlbedo* s, const DnAlbedo& a) { s->x = s->x + a.x; s->y = s->y + a.y; s->z = s->z + a.z; }
+PT_HD DnAlbedo dn_albedo_finish(const DnAlbedo& s, uint32_t samples) {
+    const float k = (float)samples;
+    DnAlbedo o;
+    o.x = s.x / k; o.y = s.y / k; o.z = s.z / k;
+    return o;
+}
+
+// c0' = c0 / d and v0' = v0 / d.Y^2 with d = max(A, DN_ALBEDO_FLOOR) per channel.  A pixel with a non-finite channel before or after the division is
+// dead and keeps its own c0, v0: it is never read, and comes out as it went in.  (x / 1.0f and x * 1.0f are exact: an albedo of ones changes nothing.)
+PT_HD DnColor dn_demodulate(const DnColor& c, const DnAlbedo& a, uint32_t* dead) {
+    const float dx = pt_max(a.x, DN_ALBEDO_FLOOR), dy = pt_max(a.y, DN_ALBEDO_FLOOR), dz = pt_max(a.z, DN_ALBEDO_FLOOR);
+    DnColor o;
+    o.x = c.x / dx; o.y = c.y / dy; o.z = c.z / dz; o.v = c.v / (dy * dy);
+    *dead = dn_dead(c.x, c.y, c.z, c.v) | dn_dead(o.x, o.y, o.z, o.v);
+    return *dead ? c : o;
+}
+PT_HD DnColor dn_remodulate(const DnColor& c, const DnAlbedo& a, uint32_t flags) {
+    if (flags & DN_DEAD) return c;
+    const float dx = pt_max(a.x, DN_ALBEDO_FLOOR), dy = pt_max(a.y, DN_ALBEDO_FLOOR), dz = pt_max(a.z, DN_ALBEDO_FLOOR);
+    DnColor o;
+    o.x = c.x * dx; o.y = c.y * dy; o.z = c.z * dz; o.v = c.v * (dy * dy);
     return o;
 }
 

@@ -1316,10 +1316,9 @@ pt_status pt_camera_samples(pt_scene* sc, const pt_render_desc* rdp, size_t n, c
 
 // include/pt_denoise.h: the guides of the film denoiser.  Per sample index k the camera rays of every pixel (stage_generate, as pt_camera_samples runs it), the
 // closest hits as pt_intersect finds them (the probe kernel in the scene's own staging mode), and the fold of the hit records in k order (pt_denoise.hip).
-pt_status pt_render_guides(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, float* guides) {
-    std::string err;
-    pt_status st = pth::check_guides_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, guides, &err);
-    if (st != PT_OK) return fail(st, err);
+// `albedo` (may be null): include/pt_denoise.h's second guide, from the same hit records — the fold and the division then run in their albedo forms, after one
+// launch that tabulates the curves of the Lambertian materials' texture layers at the basis wavelengths.
+static pt_status render_guides_impl(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, float* guides, float* albedo) {
     HIP_TRY(hipSetDevice(sc->device));
     const uint32_t n = rdp->width * rdp->height;
     RenderParams rp;
@@ -1328,21 +1327,60 @@ pt_status pt_render_guides(pt_scene* sc, const pt_render_desc* rdp, uint32_t gui
     rp.wavelength_lo = rdp->wavelength_lo; rp.wavelength_span = rdp->wavelength_hi - rdp->wavelength_lo;
     rp.camera = pth::camera_params(sc->host.cameras[rdp->camera_index], (float)rdp->width / (float)rdp->height);
     rp.chunk_pixels = 1;
-    DevBuf dor, dd, dh, dsum, dg;
+    DevBuf dor, dd, dh, dsum, dg, dasum, da, drow, dloff, dtable;
     HIP_TRY(dor.alloc(12 * (size_t)n)); HIP_TRY(dd.alloc(12 * (size_t)n)); HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n));
     HIP_TRY(dsum.alloc(sizeof(DnGuideSum) * (size_t)n)); HIP_TRY(dg.alloc(16 * (size_t)n));
+    DnAlbedoBasis basis;
+    const uint32_t materials = sc->host.material_count;
+    if (albedo) {
+        // the table's rows: the layers of every Lambertian material's texture stack, in material order (a stack two materials share gets two sets of rows)
+        const std::vector<uint32_t>& blob = sc->host.blob;
+        std::vector<uint32_t> material_row(materials ? materials : 1u, 0u), layer_off;
+        for (uint32_t m = 0; m < materials; ++m) {
+            const uint32_t rec = blob[PT_HDR_MATERIAL_OFF] + m * PT_MAT_WORDS;
+            if (blob[rec + PT_MAT_KIND] != (uint32_t)PT_MATERIAL_LAMBERTIAN) continue;
+            const uint32_t ts = blob[rec + PT_MAT_TEXSTACK];
+            material_row[m] = (uint32_t)layer_off.size();
+            for (uint32_t i = 0; i < blob[ts]; ++i) layer_off.push_back(ts + 1u + i * PT_LAYER_WORDS);
+        }
+        const uint32_t rows = (uint32_t)layer_off.size();
+        albedo_basis(rdp->wavelength_lo, rdp->wavelength_hi, &basis);
+        HIP_TRY(dasum.alloc(16 * (size_t)n)); HIP_TRY(da.alloc(16 * (size_t)n));
+        HIP_TRY(drow.alloc(4 * material_row.size())); HIP_TRY(dloff.alloc(4 * (size_t)(rows ? rows : 1u))); HIP_TRY(dtable.alloc(16 * (size_t)(rows ? rows : 1u) * DN_ALBEDO_WAVELENGTHS));
+        HIP_TRY(hipMemcpy(drow.p, material_row.data(), 4 * material_row.size(), hipMemcpyHostToDevice));
+        if (rows) HIP_TRY(hipMemcpy(dloff.p, layer_off.data(), 4 * (size_t)rows, hipMemcpyHostToDevice));
+        launch_albedo_tables(sc->d_blob, sc->d_tex, basis, rows, dloff.as<uint32_t>(), dtable.as<float>());
+    }
     const int grid = sc->num_cus * 4;
     const uint32_t lds_bytes = sc->lds_mode == PT_LDS_ALL ? sc->blob_words * 4u : (sc->lds_mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
     for (uint32_t k = 0; k < guide_samples; ++k) {
         launch_guide_rays(rp, n, k, dor.as<float>(), dd.as<float>());
         launch_probe_intersect(LaunchCfg{grid, lds_bytes, (hipStream_t)0, sc->lds_mode}, SceneArgs{sc->d_blob, sc->blob_words, sc->d_tex}, n, dor.as<float>(), dd.as<float>(), dh.as<pt_hit>());
-        launch_guide_fold(n, dh.as<pt_hit>(), dsum.as<DnGuideSum>(), k == 0);
+        if (albedo)
+            launch_guide_fold_albedo(n, dh.as<pt_hit>(), dsum.as<DnGuideSum>(), dasum.as<float>(), k == 0, sc->d_blob, sc->d_tex, materials, drow.as<uint32_t>(), dtable.as<float>(), basis);
+        else
+            launch_guide_fold(n, dh.as<pt_hit>(), dsum.as<DnGuideSum>(), k == 0);
     }
-    launch_guide_finish(n, dsum.as<DnGuideSum>(), guide_samples, dg.as<float>());
+    if (albedo) launch_guide_finish_albedo(n, dsum.as<DnGuideSum>(), dasum.as<float>(), guide_samples, dg.as<float>(), da.as<float>());
+    else launch_guide_finish(n, dsum.as<DnGuideSum>(), guide_samples, dg.as<float>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(guides, dg.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
+    if (albedo) HIP_TRY(hipMemcpy(albedo, da.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
     return PT_OK;
+}
+pt_status pt_render_guides(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, float* guides) {
+    std::string err;
+    const pt_status st = pth::check_guides_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, guides, &err);
+    if (st != PT_OK) return fail(st, err);
+    return render_guides_impl(sc, rdp, guide_samples, guides, nullptr);
+}
+pt_status pt_render_guides_albedo(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, float* guides, float* albedo) {
+    std::string err;
+    const pt_status st = pth::check_guides_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, guides, &err);
+    if (st != PT_OK) return fail(st, err);
+    if (!albedo) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    return render_guides_impl(sc, rdp, guide_samples, guides, albedo);
 }
 
 pt_status pt_bsdf_sample(pt_scene* sc, uint32_t material, size_t n, const float* lambda, const float* wi, const float* s2, float* f, float* wo, float* pdf) {

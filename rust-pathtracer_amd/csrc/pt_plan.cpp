@@ -175,4 +175,17 @@ pt_status check_guides_args(const void* scene, const pt_render_desc* rd, uint32_
     return PT_OK;
 }
 
+pt_status check_denoise_albedo(const pt_denoise_desc& d, const float* albedo, std::string* error) {
+    const size_t np = (size_t)d.width * d.height;
+    for (size_t i = 0; i < 4 * np; ++i)
+        if (!pt_isfinite(albedo[i]) || !(albedo[i] >= 0.0f)) { *error = "an albedo value is not finite or is negative"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
+pt_status check_albedo_basis_args(const pt_render_desc* rd, const void* lambda, const void* xyz, std::string* error) {
+    if (!rd || !lambda || !xyz) { *error = "null argument"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!(rd->wavelength_hi >= rd->wavelength_lo)) { *error = "wavelength_hi must not be below wavelength_lo"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
 }  // namespace pth

@@ -41,6 +41,9 @@ pt_status normalize_denoise_desc(const pt_denoise_desc* in, const void* film, co
                                  pt_denoise_desc* out, std::string* error);
 pt_status check_denoise_inputs(const pt_denoise_desc& d, const uint32_t* sample_counts, const float* guides, std::string* error);
 pt_status check_guides_args(const void* scene, const pt_render_desc* rd, uint32_t camera_count, uint32_t guide_samples, const void* guides, std::string* error);
+// pt_denoise_film_albedo's albedo plane (every channel finite and >= 0) and pt_albedo_basis' arguments
+pt_status check_denoise_albedo(const pt_denoise_desc& d, const float* albedo, std::string* error);
+pt_status check_albedo_basis_args(const pt_render_desc* rd, const void* lambda, const void* xyz, std::string* error);
 
 }  // namespace pth
 #endif

@@ -532,6 +532,22 @@ def cornell_box():
     return b
 
 
+def cornell_checker(n=8, hi=0.95, lo=0.15, rgba=False):
+    """cornell_box() with an n x n checker of reflectance factors `hi` / `lo` on a rectangle 4 mm in front of its back wall: a textured Lambertian
+    surface (the film denoiser's albedo tests).  `rgba`: the same checker as a four-channel texture over srgb_r / srgb_g / srgb_b / flat_zero."""
+    b = cornell_box()
+    yy, xx = np.mgrid[0:n, 0:n]
+    texels = np.where((xx + yy) % 2 == 0, np.float32(hi), np.float32(lo)).astype(np.float32)
+    if rgba:
+        add_library_curves(b, ["srgb_r", "srgb_g", "srgb_b", "flat_zero"])
+        ts = b.texstack_texture4("checker", [b.curve(c) for c in ("srgb_r", "srgb_g", "srgb_b", "flat_zero")], np.repeat(texels[..., None], 4, -1))
+    else:
+        ts = b.texstack_texture1("checker", b.curve("cornell_white"), texels)
+    m = b.material_lambertian("checker", ts)
+    b.add_rect((0.55, 0.55), (0.555, 0.278, 0.274), "X", True, m)
+    return b
+
+
 def _npz_mesh(name):
     z = np.load(os.path.join(_DATA, "meshes", name + ".npz"))
     n = z["normals"]

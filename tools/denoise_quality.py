@@ -4,10 +4,13 @@
   python3 tools/denoise_quality.py [--size 256] [--spp 20,40,80] [--ref-spp 4096] [--out profiles/denoise_quality.json]
   python3 tools/denoise_quality.py --emulation [--out ...]     the definition on the CPU (48x48, 20 spp against 1000 spp: the case tests/test_denoise.py asserts)
   python3 tools/denoise_quality.py --one-pass 1024             one 1024x1024 render, guides and filter call (the program to run under rocprofv3 --kernel-trace --stats)
+  python3 tools/denoise_quality.py --one-pass 1024 --demodulate   the same on cornell_checker, the guides and the filter once without and once with the albedo
+  python3 tools/denoise_quality.py --library PATH --key NAME   another build of the engine (entries it lacks are left out)
 
-Quality: Cornell box, the gem scene, mixed_primitives and hdri_small at size x size, max_bounces 6, seed 1, the defaults of pt_denoise_desc, guides of 4
-samples.  Against a reference render of another seed (77), RMSE over XYZ of the noisy and of the denoised film, their ratio, and the shift of the mean Y.
-Cost: median wall seconds of pt_render_guides and pt_denoise_film (host arrays in and out: transfers and allocations included) beside the render's.
+Quality: Cornell box, the gem scene, mixed_primitives, hdri_small and cornell_checker at size x size, max_bounces 6, seed 1, the defaults of pt_denoise_desc,
+guides of 4 samples.  Against a reference render of another seed (77), RMSE over XYZ of the noisy film, of the denoised film and of the film denoised with
+albedo demodulation, their ratios, and the shift of the mean Y; for cornell_checker also over the pixels whose sample-0 camera ray hits the checker.
+Cost: median wall seconds of pt_render_guides(_albedo) and pt_denoise_film(_albedo) (host arrays in and out: transfers and allocations included) beside the render's.
 --out merges into an existing file: the GPU run and the emulation run fill their own keys."""
 import argparse
 import importlib
@@ -22,7 +25,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-SCENES = ("cornell_box", "cornell_gem", "mixed_primitives", "hdri_small")
+SCENES = ("cornell_box", "cornell_gem", "mixed_primitives", "hdri_small", "cornell_checker")
 BOUNCES = 6
 
 
@@ -41,46 +44,81 @@ def timed(fn, reps):
 
 def emulation_library(pkg):
     emu_dir, csrc = os.path.join(ROOT, "tests", "host_emulation"), os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
-    lib = os.path.join(emu_dir, "libptemu_denoise.so")
-    srcs = [os.path.join(emu_dir, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_denoise.cpp")] + [os.path.join(csrc, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
+    lib = os.path.join(emu_dir, "libptemu_denoise_albedo.so")
+    srcs = [os.path.join(emu_dir, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_denoise.cpp", "ptemu_denoise_albedo.cpp")] + [os.path.join(csrc, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
     if not os.path.exists(lib):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-o", lib] + srcs)
     return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
 
 
+def checker_mask(sc, builder, rd):
+    """The pixels whose sample-0 camera ray hits cornell_checker's checker."""
+    n = rd.width * rd.height
+    o, d, _ = sc.camera_samples(rd, np.arange(n, dtype=np.uint32), np.zeros(n, np.uint32))
+    h = sc.intersect(o, d)
+    return ((h["valid"] != 0) & (h["material"] == builder.material("checker"))).reshape(rd.height, rd.width)
+
+
 def measure(lib, pkg, name, size, spp, ref, reps):
-    sc = lib.create_scene(getattr(pkg.scene, name)())
+    builder = getattr(pkg.scene, name)()
+    sc = lib.create_scene(builder)
     rd = pkg.api.render_desc(size, size, spp, BOUNCES, seed=1)
     (film, counts, st, _), t_render = timed(lambda: sc.render_adaptive(rd, spp, 0.0, stats=True), reps)
     guides, t_guides = timed(lambda: sc.render_guides(rd, 4), reps)
     den, t_filter = timed(lambda: lib.denoise_film(film, counts, st, guides), reps)
     e0, e1 = rmse(film, ref), rmse(den, ref)
-    return {"spp": spp, "rmse_noisy": e0, "rmse_denoised": e1, "ratio": e1 / e0, "mean_y_noisy": float(film[..., 1].mean()), "mean_y_denoised": float(den[..., 1].mean()),
-            "mean_y_shift": float(den[..., 1].mean() / film[..., 1].mean() - 1.0), "render_seconds": t_render, "guides_seconds": t_guides, "filter_seconds": t_filter}
+    out = {"spp": spp, "rmse_noisy": e0, "rmse_denoised": e1, "ratio": e1 / e0, "mean_y_noisy": float(film[..., 1].mean()), "mean_y_denoised": float(den[..., 1].mean()),
+           "mean_y_shift": float(den[..., 1].mean() / film[..., 1].mean() - 1.0), "render_seconds": t_render, "guides_seconds": t_guides, "filter_seconds": t_filter}
+    films = {"noisy": film, "denoised": den}
+    if lib._render_guides_albedo is not None:
+        (_, albedo), out["guides_albedo_seconds"] = timed(lambda: sc.render_guides_albedo(rd, 4), reps)
+        dem, out["filter_albedo_seconds"] = timed(lambda: lib.denoise_film(film, counts, st, guides, albedo=albedo), reps)
+        e2 = rmse(dem, ref)
+        out.update({"rmse_demodulated": e2, "ratio_demodulated": e2 / e0, "mean_y_shift_demodulated": float(dem[..., 1].mean() / film[..., 1].mean() - 1.0)})
+        films["demodulated"] = dem
+    if name == "cornell_checker":
+        mask = checker_mask(sc, builder, rd)
+        out["checker_pixels"] = int(mask.sum())
+        for k, f in films.items():
+            out["checker_rmse_" + k] = rmse(f[mask], ref[mask])
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=256)
-    ap.add_argument("--spp", default="20,40,80")
+    ap.add_argument("--spp", default=None, help="default 20,40,80; with --emulation 20")
     ap.add_argument("--ref-spp", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--emulation", action="store_true")
     ap.add_argument("--one-pass", type=int, default=0, metavar="SIZE")
+    ap.add_argument("--demodulate", action="store_true", help="--one-pass: cornell_checker, without and with the albedo")
+    ap.add_argument("--library", default=None, metavar="PATH", help="another build of libptamd.so")
+    ap.add_argument("--key", default=None, help="the record's key in --out (default gpu_<size> / emulation_48)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     pkg = importlib.import_module("rust-pathtracer_amd")
     if args.one_pass:
         engine = pkg.load()
-        sc = engine.create_scene(pkg.scene.cornell_box())
         rd = pkg.api.render_desc(args.one_pass, args.one_pass, 20, BOUNCES, seed=1)
+        if args.demodulate:
+            sc = engine.create_scene(pkg.scene.cornell_checker())
+            film, counts, st, _ = sc.render_adaptive(rd, 20, 0.0, stats=True)
+            guides = sc.render_guides(rd, 4)
+            _, albedo = sc.render_guides_albedo(rd, 4)
+            den, dem = engine.denoise_film(film, counts, st, guides), engine.denoise_film(film, counts, st, guides, albedo=albedo)
+            print("denoised %dx%d: mean Y %.6g -> %.6g, demodulated %.6g" % (args.one_pass, args.one_pass, film[..., 1].mean(), den[..., 1].mean(), dem[..., 1].mean()))
+            return
+        sc = engine.create_scene(pkg.scene.cornell_box())
         film, den, counts, _ = sc.render_denoised(rd)
         print("denoised %dx%d: mean Y %.6g -> %.6g" % (args.one_pass, args.one_pass, film[..., 1].mean(), den[..., 1].mean()))
         return
     if args.emulation:
-        lib, key, size, spps, ref_spp, reps = emulation_library(pkg), "emulation_48", 48, [20], 1000, 1
+        lib, key, size, spps, ref_spp, reps = emulation_library(pkg), "emulation_48", 48, [int(s) for s in (args.spp or "20").split(",")], 1000, 1
     else:
-        lib, key, size, spps, ref_spp, reps = pkg.load(), "gpu_%d" % args.size, args.size, [int(s) for s in args.spp.split(",")], args.ref_spp, args.reps
+        lib = pkg.api.Library(args.library, "pt_") if args.library else pkg.load()
+        key, size, spps, ref_spp, reps = "gpu_%d" % args.size, args.size, [int(s) for s in (args.spp or "20,40,80").split(",")], args.ref_spp, args.reps
+    key = args.key or key
     record = {"command": "python3 tools/denoise_quality.py " + " ".join(sys.argv[1:]), "device": "host emulation (CPU)" if args.emulation else lib.device_info(), "size": size, "reference_spp": ref_spp,
               "reference_seed": 77, "max_bounces": BOUNCES, "guide_samples": 4, "scenes": {}}
     for name in SCENES:

@@ -17,7 +17,12 @@
  * Pixels with a non-finite film channel or variance are copied through and never read.  The engine, the emulation and a numpy restatement agree
  * bit for bit.  pt_denoise_film does not demodulate albedo: a textured Lambertian surface is protected by the luminance weight alone.
  * pt_denoise_film_albedo does: the film is divided by max(albedo, 1e-3) before the passes (the variance by the square of the Y factor) and
- * multiplied by it afterwards, so that the filter averages irradiance and the texture is put back unfiltered. */
+ * multiplied by it afterwards, so that the filter averages irradiance and the texture is put back unfiltered.
+ *
+ *   chains     pt_render_guides_chain takes the guides and the albedo not at the first hit but at the first vertex that is not mirror-like: a
+ *              sample walks on through passthrough boundaries and GGX materials with alpha <= alpha_max (refracting at a dielectric, reflecting
+ *              at a metal and on total internal reflection, about the geometric normal, no random number drawn) for at most max_chain vertices;
+ *              the distance is the length of the whole path.  csrc/pt_guides_chain_rules.h holds it operation by operation. */
 #ifndef PT_DENOISE_H
 #define PT_DENOISE_H
 #include "pt_api.h"
@@ -61,6 +66,21 @@ pt_status pt_render_guides_albedo(pt_scene* scene, const pt_render_desc* desc, u
  * for bit. */
 pt_status pt_denoise_film_albedo(const pt_denoise_desc* desc, const float* film_xyzw, const uint32_t* sample_counts, const double* stats,
                                  const float* guides_xyzw, const float* albedo_xyzw, float* out_film_xyzw, float* out_variance);
+
+#define PT_GUIDE_CHAIN_MAX 16
+
+typedef struct pt_guide_chain_desc {
+    uint32_t max_chain;    /* specular vertices followed per sample; at most PT_GUIDE_CHAIN_MAX; 0 = pt_render_guides_albedo bit for bit */
+    float alpha_max;       /* a GGX material with alpha <= alpha_max is specular; 0 = 0.01, which separates the material library's smooth GGX
+                              materials (alpha <= 0.004) from its rough ones (>= 0.02) */
+    uint32_t reserved[2];  /* must be 0 */
+} pt_guide_chain_desc;
+
+/* pt_render_guides_albedo with the guides and the albedo of every sample taken at the end of its specular chain (above).  albedo_xyzw may be
+ * NULL: guides_xyzw is the same with and without it.  On a scene without a specular material any max_chain gives pt_render_guides_albedo's
+ * outputs bit for bit. */
+pt_status pt_render_guides_chain(pt_scene* scene, const pt_render_desc* desc, uint32_t guide_samples, const pt_guide_chain_desc* chain,
+                                 float* guides_xyzw, float* albedo_xyzw);
 
 #ifdef __cplusplus
 }

@@ -122,6 +122,11 @@ class DenoiseDesc(C.Structure):
                 ("normal_power_log2", C.c_uint32), ("device", C.c_uint32), ("reserved", C.c_uint32 * 1)]
 
 
+class GuideChainDesc(C.Structure):
+    """pt_guide_chain_desc (include/pt_denoise.h): the specular vertices followed per guide sample, the GGX alpha up to which a material is specular (0 = 0.01)."""
+    _fields_ = [("max_chain", C.c_uint32), ("alpha_max", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 class Profile(C.Structure):
     _fields_ = [("bounce_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("light_rays", C.c_uint64),
                 ("camera_rays", C.c_uint64), ("env_hits", C.c_uint64), ("seconds", C.c_double),
@@ -249,6 +254,8 @@ class Library:
         self._denoise_film_albedo = bind("denoise_film_albedo", C.c_int32, [C.POINTER(DenoiseDesc), fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp],
                                          required=False)
         self._denoise_albedo_last_error = bind("denoise_albedo_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the three entries above)
+        self._render_guides_chain = bind("render_guides_chain", C.c_int32, [vp, C.POINTER(RenderDesc), u32, C.POINTER(GuideChainDesc), fpp, fpp], required=False)
+        self._guides_chain_last_error = bind("guides_chain_last_error", C.c_char_p, [], required=False)   # (the emulation's)
         self._device_info = bind("device_info", C.c_char_p, [], required=False)
         self._output_film = bind("output_film", C.c_int32, [C.POINTER(OutputDesc), fpp, C.POINTER(C.c_uint8), fpp], required=False)
         self._write_png = bind("write_png", C.c_int32, [C.c_char_p, u32, u32, C.POINTER(C.c_uint8), C.c_int32], required=False)
@@ -446,11 +453,26 @@ class Scene:
             raise PtError(st, self.library._albedo_error())
         return g, a
 
+    def render_guides_chain(self, rd, guide_samples=4, max_chain=8, alpha_max=0.0, albedo=True):
+        """pt_render_guides_chain: (guides, albedo), [H,W,4] f32 each, taken at the end of every sample's specular chain — through passthrough boundaries and
+        GGX materials with alpha <= alpha_max (0 = 0.01), at most max_chain vertices (0 = render_guides_albedo).  albedo=False: (guides, None)."""
+        if self.library._render_guides_chain is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_guides_chain entry" % (self.library.path, self.library.prefix))
+        g = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        a = np.zeros((rd.height, rd.width, 4), dtype=np.float32) if albedo else None
+        cd = GuideChainDesc(max_chain, alpha_max)
+        st = self.library._render_guides_chain(self.handle, C.byref(rd), guide_samples, C.byref(cd), _fp(g), _fp(a) if albedo else None)
+        if st != PT_OK:
+            err = self.library._guides_chain_last_error
+            raise PtError(st, err().decode() if err else self.library.last_error())
+        return g, a
+
     def render_denoised(self, rd, max_samples=None, rel_error=0.0, abs_error=0.0, step=0, guide_samples=4, iterations=0, sigma_luminance=0.0, sigma_depth=0.0,
-                        normal_power_log2=0, device_mask=None, albedo=False):
+                        normal_power_log2=0, device_mask=None, albedo=False, specular_chain=None):
         """An adaptive render with statistics (max_samples None = rd.spp: a fixed count), its guides, and the filter: (film, denoised, counts, profile).
         `device_mask` (not None) routes the render through render_adaptive_multi; the filter then runs on the first device of the mask.  `albedo`: the
-        guides come with the albedo (render_guides_albedo) and the filter demodulates the film by it."""
+        guides come with the albedo (render_guides_albedo) and the filter demodulates the film by it.  `specular_chain` (not None): the guides, and the
+        albedo if asked for, come from render_guides_chain with this max_chain."""
         mx = rd.spp if max_samples is None else max_samples
         if device_mask is None:
             film, counts, st, prof = self.render_adaptive(rd, mx, rel_error, abs_error, step, stats=True)
@@ -458,7 +480,9 @@ class Scene:
         else:
             film, counts, st, prof = self.render_adaptive_multi(rd, mx, rel_error, abs_error, step, stats=True, device_mask=device_mask)
             device = (device_mask & -device_mask).bit_length() - 1 if device_mask else 0
-        if albedo:
+        if specular_chain is not None:
+            guides, alb = self.render_guides_chain(rd, guide_samples, specular_chain, albedo=albedo)
+        elif albedo:
             guides, alb = self.render_guides_albedo(rd, guide_samples)
         else:
             guides, alb = self.render_guides(rd, guide_samples), None

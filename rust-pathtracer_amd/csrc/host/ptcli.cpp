@@ -4,6 +4,7 @@
 //
 //   ptcli [--config data/config.toml] [--scene FILE] [-n|--dry-run] [--stdout-log-level L] [--write-log-level L]
 //         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K] [--demodulate-albedo]
+//         [--guide-chain D] [--guide-alpha-max A]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -16,7 +17,8 @@
 // through pt_render_adaptive (max_samples = min_samples without --adaptive: the same film, bit for bit, as pt_render's), and a setting that path refuses — the
 // Naive renderer, min_samples not a multiple of 10 — ends the program before anything is rendered.  The files written without the flag stay what they are.
 // --demodulate-albedo (with --denoise only) filters the film divided by the first-hit albedo: pt_render_guides_albedo and pt_denoise_film_albedo write the same
-// <filename>_denoised.* files.
+// <filename>_denoised.* files.  --guide-chain D (with --denoise only) takes the guides, and the albedo, at the end of every sample's specular chain of at most D
+// vertices (pt_render_guides_chain; --guide-alpha-max A: the GGX alpha up to which a material counts as specular, default 0.01).
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -43,13 +45,17 @@ struct Options {
     bool denoise = false;     // --denoise: <filename>_denoised.* next to the outputs
     uint32_t guide_samples = 4;
     bool demodulate = false;  // --demodulate-albedo: the denoised files through the albedo entries
+    bool chain = false;       // --guide-chain D: the guides through pt_render_guides_chain
+    uint32_t max_chain = 0;
+    float alpha_max = 0.0f;   // --guide-alpha-max A (0 = the default)
+    bool has_alpha_max = false;
 };
 
 int usage(const char* msg) {
     if (msg) fprintf(stderr, "error: %s\n", msg);
     fprintf(stderr, "usage: ptcli [--config FILE] [--scene FILE] [-n|--dry-run] [--stdout-log-level LEVEL] [--write-log-level LEVEL]\n"
                     "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n"
-                    "             [--denoise] [--guide-samples K] [--demodulate-albedo]\n");
+                    "             [--denoise] [--guide-samples K] [--demodulate-albedo] [--guide-chain D] [--guide-alpha-max A]\n");
     return 2;
 }
 
@@ -105,10 +111,26 @@ int main(int argc, char** argv) {
             o.guide_samples = (uint32_t)strtoul(v.c_str(), &end, 10);
             if (end == v.c_str() || *end || o.guide_samples == 0) return usage("--guide-samples needs a positive count");
         }
+        else if (a == "--guide-chain") {
+            if (!value(&v)) return usage("--guide-chain needs a value");
+            char* end = nullptr;
+            o.max_chain = (uint32_t)strtoul(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end || o.max_chain > PT_GUIDE_CHAIN_MAX) return usage("--guide-chain needs a count of at most 16");
+            o.chain = true;
+        }
+        else if (a == "--guide-alpha-max") {
+            if (!value(&v)) return usage("--guide-alpha-max needs a value");
+            char* end = nullptr;
+            o.alpha_max = strtof(v.c_str(), &end);
+            if (end == v.c_str() || *end || !(o.alpha_max >= 0.0f) || !(o.alpha_max < 1e30f)) return usage("--guide-alpha-max needs a finite alpha >= 0");
+            o.has_alpha_max = true;
+        }
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
     }
     if (o.demodulate && !o.denoise) return usage("--demodulate-albedo needs --denoise");
+    if (o.chain && !o.denoise) return usage("--guide-chain needs --denoise");
+    if (o.has_alpha_max && !o.chain) return usage("--guide-alpha-max needs --guide-chain");
     const bool verbose = o.stdout_log_level == "info" || o.stdout_log_level == "debug" || o.stdout_log_level == "trace";
     const bool warnings = verbose || o.stdout_log_level == "warn";
     if (!o.root.empty()) pt_scene_file_set_root(o.root.c_str());
@@ -238,8 +260,12 @@ int main(int argc, char** argv) {
                 dd.width = rd.width; dd.height = rd.height;
                 if (o.multi && o.device_mask) while (!((o.device_mask >> dd.device) & 1u)) ++dd.device;   // (the first device of the mask: where the gather left the film)
                 std::vector<float> albedo(o.demodulate ? (size_t)rd.width * rd.height * 4 : 0);
-                const pt_status gst = o.demodulate ? pt_render_guides_albedo(scene, &rd, o.guide_samples, guides.data(), albedo.data())
-                                                   : pt_render_guides(scene, &rd, o.guide_samples, guides.data());
+                pt_guide_chain_desc cd;
+                memset(&cd, 0, sizeof(cd));
+                cd.max_chain = o.max_chain; cd.alpha_max = o.alpha_max;
+                const pt_status gst = o.chain ? pt_render_guides_chain(scene, &rd, o.guide_samples, &cd, guides.data(), o.demodulate ? albedo.data() : nullptr)
+                                      : o.demodulate ? pt_render_guides_albedo(scene, &rd, o.guide_samples, guides.data(), albedo.data())
+                                                     : pt_render_guides(scene, &rd, o.guide_samples, guides.data());
                 if (gst != PT_OK || pt_denoise_film_albedo(&dd, film.data(), counts.data(), stats.data(), guides.data(), o.demodulate ? albedo.data() : nullptr,
                                                            clean.data(), nullptr) != PT_OK) {
                     fprintf(stderr, "--denoise: %s\n", pt_last_error()); rc = 1; break;

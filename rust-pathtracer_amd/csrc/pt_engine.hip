@@ -30,6 +30,7 @@
 #include "pt_adaptive_select.h"
 #include "pt_denoise_launch.h"
 #include "pt_error.h"
+#include "pt_guides_chain_launch.h"
 #include "pt_plan.h"
 #include "pt_scene_host.h"
 
@@ -1314,6 +1315,28 @@ pt_status pt_camera_samples(pt_scene* sc, const pt_render_desc* rdp, size_t n, c
     return PT_OK;
 }
 
+// The albedo guide's tables for a render `rdp` of `sc`: the basis, material_row[m] (the first table row of material m's layers) and the curve values of every
+// Lambertian material's texture layers at the basis wavelengths (one launch of k_albedo_tables).
+static pt_status make_albedo_tables(pt_scene* sc, const pt_render_desc* rdp, DnAlbedoBasis* basis, DevBuf* drow, DevBuf* dloff, DevBuf* dtable) {
+    const uint32_t materials = sc->host.material_count;
+    // the table's rows: the layers of every Lambertian material's texture stack, in material order (a stack two materials share gets two sets of rows)
+    const std::vector<uint32_t>& blob = sc->host.blob;
+    std::vector<uint32_t> material_row(materials ? materials : 1u, 0u), layer_off;
+    for (uint32_t m = 0; m < materials; ++m) {
+        const uint32_t rec = blob[PT_HDR_MATERIAL_OFF] + m * PT_MAT_WORDS;
+        if (blob[rec + PT_MAT_KIND] != (uint32_t)PT_MATERIAL_LAMBERTIAN) continue;
+        const uint32_t ts = blob[rec + PT_MAT_TEXSTACK];
+        material_row[m] = (uint32_t)layer_off.size();
+        for (uint32_t i = 0; i < blob[ts]; ++i) layer_off.push_back(ts + 1u + i * PT_LAYER_WORDS);
+    }
+    const uint32_t rows = (uint32_t)layer_off.size();
+    albedo_basis(rdp->wavelength_lo, rdp->wavelength_hi, basis);
+    HIP_TRY(drow->alloc(4 * material_row.size())); HIP_TRY(dloff->alloc(4 * (size_t)(rows ? rows : 1u))); HIP_TRY(dtable->alloc(16 * (size_t)(rows ? rows : 1u) * DN_ALBEDO_WAVELENGTHS));
+    HIP_TRY(hipMemcpy(drow->p, material_row.data(), 4 * material_row.size(), hipMemcpyHostToDevice));
+    if (rows) HIP_TRY(hipMemcpy(dloff->p, layer_off.data(), 4 * (size_t)rows, hipMemcpyHostToDevice));
+    launch_albedo_tables(sc->d_blob, sc->d_tex, *basis, rows, dloff->as<uint32_t>(), dtable->as<float>());
+    return PT_OK;
+}
 // include/pt_denoise.h: the guides of the film denoiser.  Per sample index k the camera rays of every pixel (stage_generate, as pt_camera_samples runs it), the
 // closest hits as pt_intersect finds them (the probe kernel in the scene's own staging mode), and the fold of the hit records in k order (pt_denoise.hip).
 // `albedo` (may be null): include/pt_denoise.h's second guide, from the same hit records — the fold and the division then run in their albedo forms, after one
@@ -1333,23 +1356,9 @@ static pt_status render_guides_impl(pt_scene* sc, const pt_render_desc* rdp, uin
     DnAlbedoBasis basis;
     const uint32_t materials = sc->host.material_count;
     if (albedo) {
-        // the table's rows: the layers of every Lambertian material's texture stack, in material order (a stack two materials share gets two sets of rows)
-        const std::vector<uint32_t>& blob = sc->host.blob;
-        std::vector<uint32_t> material_row(materials ? materials : 1u, 0u), layer_off;
-        for (uint32_t m = 0; m < materials; ++m) {
-            const uint32_t rec = blob[PT_HDR_MATERIAL_OFF] + m * PT_MAT_WORDS;
-            if (blob[rec + PT_MAT_KIND] != (uint32_t)PT_MATERIAL_LAMBERTIAN) continue;
-            const uint32_t ts = blob[rec + PT_MAT_TEXSTACK];
-            material_row[m] = (uint32_t)layer_off.size();
-            for (uint32_t i = 0; i < blob[ts]; ++i) layer_off.push_back(ts + 1u + i * PT_LAYER_WORDS);
-        }
-        const uint32_t rows = (uint32_t)layer_off.size();
-        albedo_basis(rdp->wavelength_lo, rdp->wavelength_hi, &basis);
         HIP_TRY(dasum.alloc(16 * (size_t)n)); HIP_TRY(da.alloc(16 * (size_t)n));
-        HIP_TRY(drow.alloc(4 * material_row.size())); HIP_TRY(dloff.alloc(4 * (size_t)(rows ? rows : 1u))); HIP_TRY(dtable.alloc(16 * (size_t)(rows ? rows : 1u) * DN_ALBEDO_WAVELENGTHS));
-        HIP_TRY(hipMemcpy(drow.p, material_row.data(), 4 * material_row.size(), hipMemcpyHostToDevice));
-        if (rows) HIP_TRY(hipMemcpy(dloff.p, layer_off.data(), 4 * (size_t)rows, hipMemcpyHostToDevice));
-        launch_albedo_tables(sc->d_blob, sc->d_tex, basis, rows, dloff.as<uint32_t>(), dtable.as<float>());
+        const pt_status ast = make_albedo_tables(sc, rdp, &basis, &drow, &dloff, &dtable);
+        if (ast != PT_OK) return ast;
     }
     const int grid = sc->num_cus * 4;
     const uint32_t lds_bytes = sc->lds_mode == PT_LDS_ALL ? sc->blob_words * 4u : (sc->lds_mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
@@ -1381,6 +1390,63 @@ pt_status pt_render_guides_albedo(pt_scene* sc, const pt_render_desc* rdp, uint3
     if (st != PT_OK) return fail(st, err);
     if (!albedo) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     return render_guides_impl(sc, rdp, guide_samples, guides, albedo);
+}
+
+// include/pt_denoise.h: the guides at the end of every sample's specular chain.  Per sample index the camera rays go out as a list with the identity pixel
+// order; per chain vertex the probe runs over the rays still on their way and k_chain_step (pt_guides_chain.hip) folds the ones that end into their pixels'
+// sums and compacts the rest into the next list, whose length comes back in one 4-byte read — the probe's launcher takes its ray count by value.  The last
+// possible vertex (v == max_chain) ends every ray, so nothing is read back after it: max_chain 0 runs pt_render_guides_albedo's launches and no read-back.
+pt_status pt_render_guides_chain(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const pt_guide_chain_desc* chain, float* guides, float* albedo) {
+    std::string err;
+    pt_guide_chain_desc cd;
+    const pt_status st = pth::check_guides_chain_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, chain, guides, &cd, &err);
+    if (st != PT_OK) return fail(st, err);
+    HIP_TRY(hipSetDevice(sc->device));
+    const uint32_t n = rdp->width * rdp->height;
+    RenderParams rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.seed = rdp->seed; rp.width = rdp->width; rp.height = rdp->height;
+    rp.wavelength_lo = rdp->wavelength_lo; rp.wavelength_span = rdp->wavelength_hi - rdp->wavelength_lo;
+    rp.camera = pth::camera_params(sc->host.cameras[rdp->camera_index], (float)rdp->width / (float)rdp->height);
+    rp.chunk_pixels = 1;
+    DevBuf dor[2], dd[2], dstate[2], dh, dsum, dg, dasum, da, drow, dloff, dtable, dcount;
+    for (int i = 0; i < 2; ++i) { HIP_TRY(dor[i].alloc(12 * (size_t)n)); HIP_TRY(dd[i].alloc(12 * (size_t)n)); HIP_TRY(dstate[i].alloc(16 * (size_t)n)); }
+    HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n)); HIP_TRY(dsum.alloc(sizeof(DnGuideSum) * (size_t)n)); HIP_TRY(dg.alloc(16 * (size_t)n));
+    HIP_TRY(dcount.alloc(4 * (size_t)(cd.max_chain + 1u)));
+    HIP_TRY(hipMemsetAsync(dsum.p, 0, sizeof(DnGuideSum) * (size_t)n, 0));
+    ChainAlbedo ca;
+    memset(&ca, 0, sizeof(ca));
+    if (albedo) {
+        HIP_TRY(dasum.alloc(16 * (size_t)n)); HIP_TRY(da.alloc(16 * (size_t)n));
+        HIP_TRY(hipMemsetAsync(dasum.p, 0, 16 * (size_t)n, 0));
+        const pt_status ast = make_albedo_tables(sc, rdp, &ca.basis, &drow, &dloff, &dtable);
+        if (ast != PT_OK) return ast;
+        ca.albedo_sums = dasum.as<float>(); ca.material_row = drow.as<uint32_t>(); ca.table = dtable.as<float>();
+    }
+    const int grid = sc->num_cus * 4;
+    const uint32_t lds_bytes = sc->lds_mode == PT_LDS_ALL ? sc->blob_words * 4u : (sc->lds_mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
+    const ChainRays rays[2] = {{dor[0].as<float>(), dd[0].as<float>(), dstate[0].as<uint4>()}, {dor[1].as<float>(), dd[1].as<float>(), dstate[1].as<uint4>()}};
+    for (uint32_t k = 0; k < guide_samples; ++k) {
+        launch_chain_rays(rp, n, k, rays[0]);
+        HIP_TRY(hipMemsetAsync(dcount.p, 0, 4 * (size_t)(cd.max_chain + 1u), 0));
+        uint32_t active = n;
+        for (uint32_t v = 0; v <= cd.max_chain && active != 0u; ++v) {
+            const ChainRays &in = rays[v & 1u], &out = rays[(v & 1u) ^ 1u];
+            launch_probe_intersect(LaunchCfg{grid, lds_bytes, (hipStream_t)0, sc->lds_mode}, SceneArgs{sc->d_blob, sc->blob_words, sc->d_tex}, active, in.o, in.d, dh.as<pt_hit>());
+            launch_chain_step(active, dh.as<pt_hit>(), in, out, dcount.as<uint32_t>() + v, dsum.as<DnGuideSum>(), ca, v, cd.max_chain, cd.alpha_max, sc->d_blob, sc->d_tex,
+                              sc->host.material_count);
+            if (v == cd.max_chain) break;
+            HIP_TRY(hipMemcpy(&active, dcount.as<uint32_t>() + v, 4, hipMemcpyDeviceToHost));
+            if (active > n) return fail(PT_ERR_DEVICE, "the chain's ray list grew");   // (never: a launch appends at most its own rays)
+        }
+    }
+    if (albedo) launch_guide_finish_albedo(n, dsum.as<DnGuideSum>(), dasum.as<float>(), guide_samples, dg.as<float>(), da.as<float>());
+    else launch_guide_finish(n, dsum.as<DnGuideSum>(), guide_samples, dg.as<float>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(guides, dg.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
+    if (albedo) HIP_TRY(hipMemcpy(albedo, da.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 pt_status pt_bsdf_sample(pt_scene* sc, uint32_t material, size_t n, const float* lambda, const float* wi, const float* s2, float* f, float* wo, float* pdf) {

@@ -1,5 +1,6 @@
 #include "pt_plan.h"
 #include "pt_denoise_rules.h"
+#include "pt_guides_chain_rules.h"
 
 #include <cmath>
 
@@ -185,6 +186,20 @@ pt_status check_denoise_albedo(const pt_denoise_desc& d, const float* albedo, st
 pt_status check_albedo_basis_args(const pt_render_desc* rd, const void* lambda, const void* xyz, std::string* error) {
     if (!rd || !lambda || !xyz) { *error = "null argument"; return PT_ERR_INVALID_ARGUMENT; }
     if (!(rd->wavelength_hi >= rd->wavelength_lo)) { *error = "wavelength_hi must not be below wavelength_lo"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
+pt_status check_guides_chain_args(const void* scene, const pt_render_desc* rd, uint32_t camera_count, uint32_t guide_samples, const pt_guide_chain_desc* chain,
+                                  const void* guides, pt_guide_chain_desc* out, std::string* error) {
+    if (!chain) { *error = "null argument"; return PT_ERR_INVALID_ARGUMENT; }
+    static_assert((int)ptd::DN_CHAIN_MAX == PT_GUIDE_CHAIN_MAX, "the rules' cap is the header's");
+    if (chain->max_chain > (uint32_t)PT_GUIDE_CHAIN_MAX) { *error = "max_chain: at most 16"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!(chain->alpha_max >= 0.0f) || !pt_isfinite(chain->alpha_max)) { *error = "alpha_max must be finite and >= 0"; return PT_ERR_INVALID_ARGUMENT; }
+    if (chain->reserved[0] != 0 || chain->reserved[1] != 0) { *error = "reserved must be 0"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = check_guides_args(scene, rd, camera_count, guide_samples, guides, error);
+    if (st != PT_OK) return st;
+    *out = *chain;
+    if (out->alpha_max == 0.0f) out->alpha_max = DN_CHAIN_DEFAULT_ALPHA_MAX;
     return PT_OK;
 }
 

@@ -44,6 +44,9 @@ pt_status check_guides_args(const void* scene, const pt_render_desc* rd, uint32_
 // pt_denoise_film_albedo's albedo plane (every channel finite and >= 0) and pt_albedo_basis' arguments
 pt_status check_denoise_albedo(const pt_denoise_desc& d, const float* albedo, std::string* error);
 pt_status check_albedo_basis_args(const pt_render_desc* rd, const void* lambda, const void* xyz, std::string* error);
+// pt_render_guides_chain's arguments: the chain desc first (its refusals need no scene), then check_guides_args; *out = the desc with its default filled in
+pt_status check_guides_chain_args(const void* scene, const pt_render_desc* rd, uint32_t camera_count, uint32_t guide_samples, const pt_guide_chain_desc* chain,
+                                  const void* guides, pt_guide_chain_desc* out, std::string* error);
 
 }  // namespace pth
 #endif

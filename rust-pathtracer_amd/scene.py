@@ -548,6 +548,18 @@ def cornell_checker(n=8, hi=0.95, lo=0.15, rgba=False):
     return b
 
 
+def cornell_checker_slab(tilt_deg=5.0):
+    """cornell_checker() with a slab of ggx_glass between the camera and the back wall: two parallel rectangles 10 mm apart, normals outward, tilted
+    `tilt_deg` about z, in front of the blocks.  Seen from the camera the slab covers the checker from its lower edge to a little above its middle — the
+    blocks hide much of the lower half, and the film denoiser's specular-chain tests want a tenth of the film to show the checker through the glass."""
+    b = cornell_checker()
+    glass = add_library_material(b, "ggx_glass")
+    for turn in (0.0, 180.0):   # the far face (normal +x before the tilt), then the near one
+        b.add_rect((0.40, 0.24), (0.005, 0.0, 0.0), "X", False, glass,
+                   transform_from_data(rotate=[((0, 0, 1), tilt_deg + turn)], translate=(0.03, 0.278, 0.215)))
+    return b
+
+
 def _npz_mesh(name):
     z = np.load(os.path.join(_DATA, "meshes", name + ".npz"))
     n = z["normals"]

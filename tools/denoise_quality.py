@@ -6,6 +6,9 @@
   python3 tools/denoise_quality.py --one-pass 1024             one 1024x1024 render, guides and filter call (the program to run under rocprofv3 --kernel-trace --stats)
   python3 tools/denoise_quality.py --one-pass 1024 --demodulate   the same on cornell_checker, the guides and the filter once without and once with the albedo
   python3 tools/denoise_quality.py --library PATH --key NAME   another build of the engine (entries it lacks are left out)
+  python3 tools/denoise_quality.py --chain 8 [--emulation]     specular-chain guides against first-hit guides (key gpu_<size>_chain / emulation_48_chain): the demodulated filter
+                                                               on cornell_checker_slab and cornell_gem, and the wall time of the two guide passes there and on cornell_checker
+  python3 tools/denoise_quality.py --one-pass 1024 --demodulate --chain 8 [--scene cornell_checker_slab]   one render, both guide passes, both filter calls
 
 Quality: Cornell box, the gem scene, mixed_primitives, hdri_small and cornell_checker at size x size, max_bounces 6, seed 1, the defaults of pt_denoise_desc,
 guides of 4 samples.  Against a reference render of another seed (77), RMSE over XYZ of the noisy film, of the denoised film and of the film denoised with
@@ -44,8 +47,8 @@ def timed(fn, reps):
 
 def emulation_library(pkg):
     emu_dir, csrc = os.path.join(ROOT, "tests", "host_emulation"), os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
-    lib = os.path.join(emu_dir, "libptemu_denoise_albedo.so")
-    srcs = [os.path.join(emu_dir, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_denoise.cpp", "ptemu_denoise_albedo.cpp")] + [os.path.join(csrc, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
+    lib = os.path.join(emu_dir, "libptemu_guides_chain.so")
+    srcs = [os.path.join(emu_dir, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_denoise.cpp", "ptemu_denoise_albedo.cpp", "ptemu_guides_chain.cpp")] + [os.path.join(csrc, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
     if not os.path.exists(lib):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-o", lib] + srcs)
     return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
@@ -57,6 +60,62 @@ def checker_mask(sc, builder, rd):
     o, d, _ = sc.camera_samples(rd, np.arange(n, dtype=np.uint32), np.zeros(n, np.uint32))
     h = sc.intersect(o, d)
     return ((h["valid"] != 0) & (h["material"] == builder.material("checker"))).reshape(rd.height, rd.width)
+
+
+def chain_walk(pkg, lib, sc, builder, rd, K, D):
+    """The chains of samples 0 .. K-1 walked in numpy from the probes (the restatement tests/test_guides_chain.py checks the emulation against): per sample how
+    it ended, what it passed, and the rays traced per chain vertex."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_guides_chain as tgc
+    return tgc, tgc.np_chain(pkg.api, lib, sc, builder, rd, K, D, want_albedo=False)[2]
+
+
+def measure_chain(lib, pkg, name, size, spps, ref, reps, D):
+    """Chain guides (max_chain D) against first-hit guides, both with their albedo and the demodulated filter, on one noisy film per spp; the wall time of the
+    two guide passes (median, minimum and maximum of `reps` calls).  specular_*: over the pixels whose sample-0 chain follows at least one vertex; on
+    cornell_checker_slab checker_*: over those whose sample-0 chain crosses the slab and ends on the checker."""
+    builder = getattr(pkg.scene, name)()
+    sc = lib.create_scene(builder)
+    rd = pkg.api.render_desc(size, size, spps[0], BOUNCES, seed=1)
+    out = {"max_chain": D, "guide_seconds": {}}
+    passes = {}
+    for tag, fn in (("first_hit", lambda: sc.render_guides_albedo(rd, 4)), ("chain", lambda: sc.render_guides_chain(rd, 4, D))):
+        fn()
+        secs = []
+        for _ in range(reps):
+            t = time.perf_counter()
+            passes[tag] = fn()
+            secs.append(time.perf_counter() - t)
+        out["guide_seconds"][tag] = {"median": statistics.median(secs), "min": min(secs), "max": max(secs), "runs": reps}
+    tgc, diag = chain_walk(pkg, lib, sc, builder, rd, 4, D)
+    out["rays_per_vertex"] = [sum(dg["rounds"][v] for dg in diag if v < len(dg["rounds"])) for v in range(D + 1)]
+    out["loop_rounds_per_sample"] = [len(dg["rounds"]) for dg in diag]
+    masks = {"specular": (diag[0]["vertex"] > 0).reshape(size, size)}
+    if name == "cornell_checker_slab":
+        crossed = np.zeros(size * size, bool)
+        for p in diag[0]["passed"]:
+            crossed |= p == builder.material("ggx_glass")
+        masks["checker"] = (crossed & (diag[0]["end"] == tgc.END_TERMINAL) & (diag[0]["material"] == builder.material("checker"))).reshape(size, size)
+    out["pixels"] = {k: int(m.sum()) for k, m in masks.items()}
+    out["spp"] = []
+    for spp in spps:
+        rds = pkg.api.render_desc(size, size, spp, BOUNCES, seed=1)
+        film, counts, st, _ = sc.render_adaptive(rds, spp, 0.0, stats=True)
+        films = {"noisy": film}
+        for tag, (g, a) in passes.items():
+            films[tag] = lib.denoise_film(film, counts, st, g, albedo=a)
+        rec = {"spp": spp}
+        for tag, f in films.items():
+            rec["rmse_" + tag] = rmse(f, ref)
+            for k, m in masks.items():
+                if m.any():
+                    rec[k + "_rmse_" + tag] = rmse(f[m], ref[m])
+        rec["ratio_chain_to_first_hit"] = rec["rmse_chain"] / rec["rmse_first_hit"]
+        for k, m in masks.items():
+            if m.any():
+                rec[k + "_ratio_chain_to_first_hit"] = rec[k + "_rmse_chain"] / rec[k + "_rmse_first_hit"]
+        out["spp"].append(rec)
+    return out
 
 
 def measure(lib, pkg, name, size, spp, ref, reps):
@@ -93,6 +152,9 @@ def main():
     ap.add_argument("--emulation", action="store_true")
     ap.add_argument("--one-pass", type=int, default=0, metavar="SIZE")
     ap.add_argument("--demodulate", action="store_true", help="--one-pass: cornell_checker, without and with the albedo")
+    ap.add_argument("--chain", type=int, default=None, metavar="D", help="specular-chain guides of max_chain D against first-hit guides")
+    ap.add_argument("--scene", default="cornell_checker_slab", help="--one-pass --chain: the scene")
+    ap.add_argument("--rounds", action="store_true", help="--one-pass --chain: also print the rays traced per chain vertex (a numpy walk over the probes)")
     ap.add_argument("--library", default=None, metavar="PATH", help="another build of libptamd.so")
     ap.add_argument("--key", default=None, help="the record's key in --out (default gpu_<size> / emulation_48)")
     ap.add_argument("--out", default=None)
@@ -101,6 +163,19 @@ def main():
     if args.one_pass:
         engine = pkg.load()
         rd = pkg.api.render_desc(args.one_pass, args.one_pass, 20, BOUNCES, seed=1)
+        if args.chain is not None:
+            builder = getattr(pkg.scene, args.scene)()
+            sc = engine.create_scene(builder)
+            film, counts, st, _ = sc.render_adaptive(rd, 20, 0.0, stats=True)
+            g0, a0 = sc.render_guides_albedo(rd, 4)
+            g1, a1 = sc.render_guides_chain(rd, 4, args.chain)
+            first, chain = engine.denoise_film(film, counts, st, g0, albedo=a0), engine.denoise_film(film, counts, st, g1, albedo=a1)
+            print("%s %dx%d, max_chain %d: mean Y %.6g -> first-hit guides %.6g, chain guides %.6g"
+                  % (args.scene, args.one_pass, args.one_pass, args.chain, film[..., 1].mean(), first[..., 1].mean(), chain[..., 1].mean()))
+            if args.rounds:   # (not under a profiler: the walk traces its rays through the probe too)
+                _, diag = chain_walk(pkg, engine, sc, builder, rd, 4, args.chain)
+                print("rays per chain vertex, samples 0..3: %s" % [dg["rounds"] for dg in diag])
+            return
         if args.demodulate:
             sc = engine.create_scene(pkg.scene.cornell_checker())
             film, counts, st, _ = sc.render_adaptive(rd, 20, 0.0, stats=True)
@@ -118,10 +193,16 @@ def main():
     else:
         lib = pkg.api.Library(args.library, "pt_") if args.library else pkg.load()
         key, size, spps, ref_spp, reps = "gpu_%d" % args.size, args.size, [int(s) for s in (args.spp or "20,40,80").split(",")], args.ref_spp, args.reps
+    if args.chain is not None:
+        key += "_chain"
     key = args.key or key
     record = {"command": "python3 tools/denoise_quality.py " + " ".join(sys.argv[1:]), "device": "host emulation (CPU)" if args.emulation else lib.device_info(), "size": size, "reference_spp": ref_spp,
               "reference_seed": 77, "max_bounces": BOUNCES, "guide_samples": 4, "scenes": {}}
-    for name in SCENES:
+    for name in (("cornell_checker_slab", "cornell_gem", "cornell_checker") if args.chain is not None else ()):
+        ref, _ = lib.create_scene(getattr(pkg.scene, name)()).render(pkg.api.render_desc(size, size, ref_spp, BOUNCES, seed=77))
+        record["scenes"][name] = measure_chain(lib, pkg, name, size, spps, ref, 5 if not args.emulation else 1, args.chain)
+        print(name, json.dumps(record["scenes"][name], indent=1), flush=True)
+    for name in (SCENES if args.chain is None else ()):
         ref, _ = lib.create_scene(getattr(pkg.scene, name)()).render(pkg.api.render_desc(size, size, ref_spp, BOUNCES, seed=77))
         record["scenes"][name] = [measure(lib, pkg, name, size, spp, ref, reps) for spp in spps]
         print(name, json.dumps(record["scenes"][name], indent=1), flush=True)

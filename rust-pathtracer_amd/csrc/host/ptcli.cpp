@@ -4,7 +4,7 @@
 //
 //   ptcli [--config data/config.toml] [--scene FILE] [-n|--dry-run] [--stdout-log-level L] [--write-log-level L]
 //         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K] [--demodulate-albedo]
-//         [--guide-chain D] [--guide-alpha-max A]
+//         [--guide-chain D] [--guide-alpha-max A] [--spectral-bins B]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -19,6 +19,9 @@
 // --demodulate-albedo (with --denoise only) filters the film divided by the first-hit albedo: pt_render_guides_albedo and pt_denoise_film_albedo write the same
 // <filename>_denoised.* files.  --guide-chain D (with --denoise only) takes the guides, and the albedo, at the end of every sample's specular chain of at most D
 // vertices (pt_render_guides_chain; --guide-alpha-max A: the GGX alpha up to which a material counts as specular, default 0.01).
+// --spectral-bins B (1..64) renders every setting through pt_render_spectral (include/pt_spectral.h) and also writes <filename>_spectral.exr: one FLOAT channel
+// per wavelength bin (times the factor of the EXR payload) beside the R, G, B of <filename>.exr.  The usual files stay byte for byte what they are.  It is
+// refused together with --adaptive, --denoise and a --devices mask that names more than one GPU (or one other than device 0, where the call renders).
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -31,6 +34,7 @@
 #include "../../../include/pt_adaptive.h"
 #include "../../../include/pt_denoise.h"
 #include "../../../include/pt_scene_file.h"
+#include "../../../include/pt_spectral.h"
 
 namespace {
 
@@ -49,13 +53,15 @@ struct Options {
     uint32_t max_chain = 0;
     float alpha_max = 0.0f;   // --guide-alpha-max A (0 = the default)
     bool has_alpha_max = false;
+    uint32_t spectral_bins = 0;   // --spectral-bins B: <filename>_spectral.exr through pt_render_spectral; 0 = off
 };
 
 int usage(const char* msg) {
     if (msg) fprintf(stderr, "error: %s\n", msg);
     fprintf(stderr, "usage: ptcli [--config FILE] [--scene FILE] [-n|--dry-run] [--stdout-log-level LEVEL] [--write-log-level LEVEL]\n"
                     "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n"
-                    "             [--denoise] [--guide-samples K] [--demodulate-albedo] [--guide-chain D] [--guide-alpha-max A]\n");
+                    "             [--denoise] [--guide-samples K] [--demodulate-albedo] [--guide-chain D] [--guide-alpha-max A]\n"
+                    "             [--spectral-bins B]\n");
     return 2;
 }
 
@@ -125,12 +131,26 @@ int main(int argc, char** argv) {
             if (end == v.c_str() || *end || !(o.alpha_max >= 0.0f) || !(o.alpha_max < 1e30f)) return usage("--guide-alpha-max needs a finite alpha >= 0");
             o.has_alpha_max = true;
         }
+        else if (a == "--spectral-bins") {
+            if (!value(&v)) return usage("--spectral-bins needs a value");
+            char* end = nullptr;
+            const unsigned long b = strtoul(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end || b == 0 || b > PT_SPECTRAL_MAX_BINS) return usage("--spectral-bins needs a count in 1..64");
+            o.spectral_bins = (uint32_t)b;
+        }
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
     }
     if (o.demodulate && !o.denoise) return usage("--demodulate-albedo needs --denoise");
     if (o.chain && !o.denoise) return usage("--guide-chain needs --denoise");
     if (o.has_alpha_max && !o.chain) return usage("--guide-alpha-max needs --guide-chain");
+    if (o.spectral_bins && o.adaptive >= 0.0f) return usage("--spectral-bins cannot be combined with --adaptive: an adaptive render has no spectral film");
+    if (o.spectral_bins && o.denoise) return usage("--spectral-bins cannot be combined with --denoise: the denoiser takes the adaptive path, which has no spectral film");
+    if (o.spectral_bins && o.multi) {   // (pt_render_spectral renders on the scene's device, device 0: a mask may name that one alone; 0 = every device of the node)
+        if ((o.device_mask & (o.device_mask - 1)) != 0 || (o.device_mask == 0 && pt_device_count() > 1))
+            return usage("--spectral-bins cannot be combined with --devices naming more than one GPU: pt_render_multi has no spectral film");
+        if (o.device_mask > 1) return usage("--spectral-bins renders on device 0: --devices may name that device alone");
+    }
     const bool verbose = o.stdout_log_level == "info" || o.stdout_log_level == "debug" || o.stdout_log_level == "trace";
     const bool warnings = verbose || o.stdout_log_level == "warn";
     if (!o.root.empty()) pt_scene_file_set_root(o.root.c_str());
@@ -212,6 +232,7 @@ int main(int argc, char** argv) {
             const bool with_counts = adaptive || o.denoise;
             std::vector<uint32_t> counts(with_counts ? (size_t)rd.width * rd.height : 0);
             std::vector<double> stats(o.denoise ? (size_t)rd.width * rd.height * 2 : 0);
+            std::vector<float> spectral;
             uint64_t samples = (uint64_t)rd.width * rd.height * rd.spp;
             if (!adaptive && o.denoise) {
                 // a fixed count through the adaptive path (max_samples = min_samples, one round): pt_render's film bit for bit, and the statistics
@@ -231,6 +252,11 @@ int main(int argc, char** argv) {
                 for (uint32_t c : counts) { samples += c; lo = c < lo ? c : lo; hi = c > hi ? c : hi; }
                 printf("adaptive: %.2f samples per pixel on average, min %u, max %u, %llu rounds\n", (double)samples / (double)counts.size(), lo, hi,
                        (unsigned long long)prof.kernel_launches[5]);
+            } else if (o.spectral_bins) {
+                printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
+                spectral.resize((size_t)o.spectral_bins * rd.width * rd.height);
+                const pt_spectral_desc sd = {o.spectral_bins, {0u, 0u, 0u}};
+                if (pt_render_spectral(scene, &rd, &sd, film.data(), spectral.data(), &prof) != PT_OK) { fprintf(stderr, "pt_render_spectral: %s\n", pt_last_error()); rc = 1; break; }
             } else {
                 printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
                 const pt_status st = o.multi ? pt_render_multi(scene, &rd, o.device_mask, film.data(), &prof) : pt_render(scene, &rd, film.data(), &prof);
@@ -253,6 +279,17 @@ int main(int argc, char** argv) {
             }
             if (o.write_film && !write_npy(base + ".npy", film.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", base.c_str()); rc = 1; break; }
             printf("wrote %s.exr and %s.png\n", base.c_str(), base.c_str());
+            if (!spectral.empty()) {
+                // the bins in the units of the EXR payload: the same factor, applied here, one multiply per value
+                const pt_spectral_desc sd = {o.spectral_bins, {0u, 0u, 0u}};
+                std::vector<float> centres(o.spectral_bins);
+                for (float& v : spectral) v *= od.factor;
+                if (pt_spectral_bin_centres(&rd, &sd, centres.data()) != PT_OK ||
+                    pt_write_exr_spectral((base + "_spectral.exr").c_str(), rd.width, rd.height, o.spectral_bins, centres.data(), spectral.data(), linear.data(), od.colorspace) != PT_OK) {
+                    fprintf(stderr, "--spectral-bins: %s\n", pt_last_error()); rc = 1; break;
+                }
+                printf("wrote %s_spectral.exr (%u bins)\n", base.c_str(), o.spectral_bins);
+            }
             if (o.denoise) {
                 std::vector<float> guides((size_t)rd.width * rd.height * 4), clean((size_t)rd.width * rd.height * 4);
                 pt_denoise_desc dd;

@@ -24,10 +24,12 @@
 
 #include "pt_kernels.h"   /* first: it switches on the wave-level device code of pt_device.h */
 #include "../../include/pt_adaptive.h"
+#include "../../include/pt_spectral.h"
 #include "../../include/pt_api.h"
 #include "../../include/pt_debug.h"
 #include "../../include/pt_denoise.h"
 #include "pt_adaptive_select.h"
+#include "pt_spectral_launch.h"
 #include "pt_denoise_launch.h"
 #include "pt_error.h"
 #include "pt_guides_chain_launch.h"
@@ -272,6 +274,8 @@ struct pt_scene {
     std::vector<hipEvent_t> events;  // pairs (start, stop), grown on demand
     float* film_cache = nullptr;     // pt_render's device film, kept between calls
     size_t film_cache_bytes = 0;
+    float* spectral_cache = nullptr; // pt_render_spectral's device planes (bins x width x height), kept between calls
+    size_t spectral_cache_bytes = 0;
     std::vector<pt_scene*> replicas; // pt_render_multi: this scene on the other (virtual) devices, by device index x virtual index (nullptr = not made yet / this one)
 };
 
@@ -467,10 +471,12 @@ pt_status adaptive_rounds(pt_scene* sc, const pt_render_desc& rd, const pt_adapt
 
 // Set-up (kernel forms, queues, launch configuration) and one pass loop over a device pixel list and a sample range: pt_render runs the loop once over its
 // shard's pixels; with `adaptive` (pt_render_adaptive, its arguments checked) adaptive_rounds runs it once per round, over the film or (with `node`: worker
-// node_index of pt_render_adaptive_multi) over the desc's shard.
+// node_index of pt_render_adaptive_multi) over the desc's shard.  With `d_spectral` (pt_render_spectral: spectral_bins planes of width * height floats, its
+// arguments checked) every pass also adds its samples to the wavelength-binned film (include/pt_spectral.h).
 pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hipStream_t stream, pt_profile* profile, const pt_adaptive_desc* adaptive = nullptr,
-                      NodeRounds* node = nullptr, int node_index = 0) {
+                      NodeRounds* node = nullptr, int node_index = 0, float* d_spectral = nullptr, uint32_t spectral_bins = 0) {
     if (!sc || !rdp || !d_film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    if (adaptive && d_spectral) return fail(PT_ERR_UNSUPPORTED, "the spectral film of an adaptive render is not supported");
     pt_render_desc rd;
     std::string err;
     if (!pth::normalize_render_desc(*rdp, (uint32_t)sc->host.cameras.size(), &rd, &err)) return fail(PT_ERR_INVALID_ARGUMENT, err);
@@ -511,6 +517,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
         if (pixels.size() < film_pixels) HIP_TRY(hipMemsetAsync(sc->adaptive.counts, 0, sizeof(uint32_t) * film_pixels, stream));
     } else if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(b.pixels, pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(d_film, 0, sizeof(float) * 4 * (size_t)rd.width * rd.height, stream));
+    if (d_spectral) HIP_TRY(hipMemsetAsync(d_spectral, 0, sizeof(float) * (size_t)spectral_bins * rd.width * rd.height, stream));
     HIP_TRY(hipMemsetAsync(b.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));
 
     RenderParams rp;
@@ -639,6 +646,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     };
 
     uint64_t camera_rays = 0, accumulated_pixels = 0;
+    hipError_t spectral_error = hipSuccess;
     // The pass loop: samples [first_sample, first_sample + sample_count) of the n pixels of the device list d_list; stats (adaptive rounds): S1 / S2 too
     auto run_passes = [&](const uint32_t* d_list, uint32_t n_list, uint32_t first_sample, uint32_t sample_count, double* d_stats) -> pt_status {
         // (a later adaptive round: the stream's work since the previous accumulate — the round's decision and compaction — is charged to no stage)
@@ -682,7 +690,11 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                 else if (d_stats) hipLaunchKernelGGL(k_accumulate_stats<1>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film, d_stats);
                 else if (hero) hipLaunchKernelGGL(k_accumulate<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film);
                 else hipLaunchKernelGGL(k_accumulate<1>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film);
+                // (the energy planes stay valid until the next pass's k_generate overwrites them)
+                if (d_spectral && spectral_error == hipSuccess)
+                    spectral_error = ptk::launch_accumulate_spectral(hero ? 4 : 1, grid, stream, rp, d_px, b.energy, d_spectral, spectral_bins, rd.width * rd.height);
             });
+            if (spectral_error != hipSuccess) return fail(PT_ERR_DEVICE, std::string("k_accumulate_spectral: ") + hipGetErrorString(spectral_error));
         }
         return PT_OK;
     };
@@ -877,7 +889,7 @@ void pt_scene_destroy(pt_scene* sc) {
     hipSetDevice(sc->device);
     sc->buf.release();
     sc->adaptive.release();
-    hipFree(sc->d_blob); hipFree(sc->d_tex); hipFree(sc->film_cache);
+    hipFree(sc->d_blob); hipFree(sc->d_tex); hipFree(sc->film_cache); hipFree(sc->spectral_cache);
     for (auto& e : sc->events) hipEventDestroy(e);
     delete sc;
 }
@@ -928,6 +940,28 @@ pt_status pt_render_adaptive(pt_scene* sc, const pt_render_desc* rdp, const pt_a
     HIP_TRY(hipMemcpy(sample_counts, sc->adaptive.counts, sizeof(uint32_t) * n_pixels, hipMemcpyDeviceToHost));
     if (stats) HIP_TRY(hipMemcpy(stats, sc->adaptive.stats, sizeof(double) * 2 * n_pixels, hipMemcpyDeviceToHost));
     if (profile) profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (the whole call: set-up, rounds, read-backs)
+    return PT_OK;
+}
+
+pt_status pt_render_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_spectral_desc* sdp, float* film, float* spectral, pt_profile* profile) {
+    std::string err;
+    pt_status st = pth::check_spectral_args(sc, rdp, sdp, film, spectral, &err);
+    if (st != PT_OK) return fail(st, err);
+    if (rdp->width == 0 || rdp->height == 0 || (uint64_t)rdp->width * rdp->height > 0xffffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and the film at most 2^32 - 1 pixels");
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t n_pixels = (size_t)rdp->width * rdp->height, film_bytes = sizeof(float) * 4 * n_pixels, spectral_bytes = sizeof(float) * sdp->bins * n_pixels;
+    st = ensure_film_cache(sc, film_bytes);
+    if (st != PT_OK) return st;
+    if (sc->spectral_cache_bytes < spectral_bytes) {   // (kept with the scene, like the film)
+        if (sc->spectral_cache) hipFree(sc->spectral_cache);
+        sc->spectral_cache = nullptr; sc->spectral_cache_bytes = 0;
+        HIP_TRY(hipMalloc(&sc->spectral_cache, spectral_bytes));
+        sc->spectral_cache_bytes = spectral_bytes;
+    }
+    st = render_impl(sc, rdp, sc->film_cache, nullptr, profile, nullptr, nullptr, 0, sc->spectral_cache, sdp->bins);
+    if (st != PT_OK) return st;
+    HIP_TRY(hipMemcpy(film, sc->film_cache, film_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(spectral, sc->spectral_cache, spectral_bytes, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -12,12 +12,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/pt_api.h"
 #include "../../include/pt_numerics.h"
+#include "../../include/pt_spectral.h"
 #include "pt_error.h"
 
 namespace {
@@ -160,6 +162,58 @@ Chroma chroma_of(int cs) {  // REC709 / REC2020 primaries and effective_gamma, s
 
 }  // namespace
 
+namespace {
+// The uncompressed scanline OpenEXR writer behind pt_write_exr and pt_write_exr_spectral: FLOAT channels in the order given (the caller's: byte-wise name
+// order), channel k's value of pixel i at data[i * stride].  `spectral`: the two string attributes of a spectral file.
+struct ExrChannel { std::string name; const float* data; size_t stride; };
+pt_status write_exr_channels(const char* path, uint32_t w, uint32_t h, const std::vector<ExrChannel>& channels, int32_t colorspace, bool spectral) {
+    FILE* f = fopen(path, "wb");
+    if (!f) return ofail(PT_ERR_INVALID_ARGUMENT, std::string("cannot open ") + path);
+    std::vector<uint8_t> hd;
+    auto put32 = [&](std::vector<uint8_t>& v, uint32_t x) { for (int k = 0; k < 4; ++k) v.push_back((x >> (8 * k)) & 0xff); };
+    auto putf = [&](std::vector<uint8_t>& v, float x) { uint32_t u; memcpy(&u, &x, 4); put32(v, u); };
+    auto puts0 = [&](std::vector<uint8_t>& v, const char* s) { v.insert(v.end(), s, s + strlen(s) + 1); };
+    auto attr = [&](const char* name, const char* type, const std::vector<uint8_t>& val) { puts0(hd, name); puts0(hd, type); put32(hd, (uint32_t)val.size()); hd.insert(hd.end(), val.begin(), val.end()); };
+    auto string_attr = [&](const char* name, const char* text) { attr(name, "string", std::vector<uint8_t>(text, text + strlen(text))); };
+    put32(hd, 20000630u); put32(hd, 2u);
+    std::vector<uint8_t> ch;
+    bool long_names = false;
+    for (const ExrChannel& c : channels) { puts0(ch, c.name.c_str()); put32(ch, 2u /* FLOAT */); ch.push_back(0); ch.push_back(0); ch.push_back(0); ch.push_back(0); put32(ch, 1); put32(ch, 1); long_names = long_names || c.name.size() > 31; }
+    ch.push_back(0);
+    if (long_names) hd[5] |= 0x04;   // (version field bit 10: names longer than 31 bytes)
+    attr("channels", "chlist", ch);
+    Chroma c = chroma_of(colorspace);
+    std::vector<uint8_t> cv; for (float v : {c.rx, c.ry, c.gx, c.gy, c.bx, c.by, c.wx, c.wy}) putf(cv, v);
+    attr("chromaticities", "chromaticities", cv);
+    attr("compression", "compression", {0});
+    std::vector<uint8_t> box; put32(box, 0); put32(box, 0); put32(box, w - 1); put32(box, h - 1);
+    attr("dataWindow", "box2i", box); attr("displayWindow", "box2i", box);
+    if (spectral) string_attr("emissiveUnits", "W.m^-2.sr^-1");
+    attr("lineOrder", "lineOrder", {0});
+    std::vector<uint8_t> one; putf(one, 1.0f); attr("pixelAspectRatio", "float", one);
+    std::vector<uint8_t> v2; putf(v2, 0.0f); putf(v2, 0.0f); attr("screenWindowCenter", "v2f", v2);
+    attr("screenWindowWidth", "float", one);
+    if (spectral) string_attr("spectralLayoutVersion", "1.0");
+    hd.push_back(0);
+    fwrite(hd.data(), 1, hd.size(), f);
+    const size_t nc = channels.size();
+    uint64_t line_bytes = 8 + 4ull * nc * w, table0 = hd.size() + 8ull * h;
+    for (uint32_t y = 0; y < h; ++y) { uint64_t off = table0 + line_bytes * y; fwrite(&off, 8, 1, f); }
+    std::vector<float> row(nc * (size_t)w);
+    for (uint32_t y = 0; y < h; ++y) {
+        int32_t yy = (int32_t)y, sz = (int32_t)(4 * nc * w);
+        fwrite(&yy, 4, 1, f); fwrite(&sz, 4, 1, f);
+        for (size_t k = 0; k < nc; ++k) {
+            const float* src = channels[k].data + ((size_t)y * w) * channels[k].stride;
+            for (uint32_t x = 0; x < w; ++x) row[k * (size_t)w + x] = src[x * channels[k].stride];
+        }
+        fwrite(row.data(), 4, row.size(), f);
+    }
+    const bool ok = fclose(f) == 0;
+    return ok ? PT_OK : ofail(PT_ERR_INVALID_ARGUMENT, std::string("cannot write ") + path);
+}
+}  // namespace
+
 extern "C" {
 
 pt_status pt_output_film(const pt_output_desc* d, const float* film, uint8_t* rgba8, float* linear_rgb) {
@@ -242,41 +296,28 @@ pt_status pt_write_png(const char* path, uint32_t w, uint32_t h, const uint8_t* 
 
 pt_status pt_write_exr(const char* path, uint32_t w, uint32_t h, const float* rgb, int32_t colorspace) {
     if (!path || !rgb || w == 0 || h == 0) return ofail(PT_ERR_INVALID_ARGUMENT, "bad argument");
-    FILE* f = fopen(path, "wb");
-    if (!f) return ofail(PT_ERR_INVALID_ARGUMENT, std::string("cannot open ") + path);
-    std::vector<uint8_t> hd;
-    auto put32 = [&](std::vector<uint8_t>& v, uint32_t x) { for (int k = 0; k < 4; ++k) v.push_back((x >> (8 * k)) & 0xff); };
-    auto putf = [&](std::vector<uint8_t>& v, float x) { uint32_t u; memcpy(&u, &x, 4); put32(v, u); };
-    auto puts0 = [&](std::vector<uint8_t>& v, const char* s) { v.insert(v.end(), s, s + strlen(s) + 1); };
-    auto attr = [&](const char* name, const char* type, const std::vector<uint8_t>& val) { puts0(hd, name); puts0(hd, type); put32(hd, (uint32_t)val.size()); hd.insert(hd.end(), val.begin(), val.end()); };
-    put32(hd, 20000630u); put32(hd, 2u);
-    std::vector<uint8_t> ch;
-    for (const char* n : {"B", "G", "R"}) { puts0(ch, n); put32(ch, 2u /* FLOAT */); ch.push_back(0); ch.push_back(0); ch.push_back(0); ch.push_back(0); put32(ch, 1); put32(ch, 1); }
-    ch.push_back(0);
-    attr("channels", "chlist", ch);
-    Chroma c = chroma_of(colorspace);
-    std::vector<uint8_t> cv; for (float v : {c.rx, c.ry, c.gx, c.gy, c.bx, c.by, c.wx, c.wy}) putf(cv, v);
-    attr("chromaticities", "chromaticities", cv);
-    attr("compression", "compression", {0});
-    std::vector<uint8_t> box; put32(box, 0); put32(box, 0); put32(box, w - 1); put32(box, h - 1);
-    attr("dataWindow", "box2i", box); attr("displayWindow", "box2i", box);
-    attr("lineOrder", "lineOrder", {0});
-    std::vector<uint8_t> one; putf(one, 1.0f); attr("pixelAspectRatio", "float", one);
-    std::vector<uint8_t> v2; putf(v2, 0.0f); putf(v2, 0.0f); attr("screenWindowCenter", "v2f", v2);
-    attr("screenWindowWidth", "float", one);
-    hd.push_back(0);
-    fwrite(hd.data(), 1, hd.size(), f);
-    uint64_t line_bytes = 8 + 12ull * w, table0 = hd.size() + 8ull * h;
-    for (uint32_t y = 0; y < h; ++y) { uint64_t off = table0 + line_bytes * y; fwrite(&off, 8, 1, f); }
-    std::vector<float> row(3 * (size_t)w);
-    for (uint32_t y = 0; y < h; ++y) {
-        int32_t yy = (int32_t)y, sz = (int32_t)(12 * w);
-        fwrite(&yy, 4, 1, f); fwrite(&sz, 4, 1, f);
-        for (uint32_t x = 0; x < w; ++x) { const float* p = rgb + 3 * ((size_t)y * w + x); row[x] = p[2]; row[w + x] = p[1]; row[2 * (size_t)w + x] = p[0]; }
-        fwrite(row.data(), 4, row.size(), f);
+    return write_exr_channels(path, w, h, {{"B", rgb + 2, 3}, {"G", rgb + 1, 3}, {"R", rgb, 3}}, colorspace, false);
+}
+
+pt_status pt_write_exr_spectral(const char* path, uint32_t w, uint32_t h, uint32_t bins, const float* centres_nm, const float* spectral, const float* linear_rgb,
+                                int32_t colorspace) {
+    if (!path) return ofail(PT_ERR_INVALID_ARGUMENT, "path is null");
+    if (w == 0 || h == 0) return ofail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
+    if (bins == 0 || bins > PT_SPECTRAL_MAX_BINS) return ofail(PT_ERR_INVALID_ARGUMENT, "bins must be in 1..64");
+    if (!centres_nm || !spectral) return ofail(PT_ERR_INVALID_ARGUMENT, "centres_nm and spectral are required");
+    std::vector<ExrChannel> channels;
+    if (linear_rgb) channels = {{"B", linear_rgb + 2, 3}, {"G", linear_rgb + 1, 3}, {"R", linear_rgb, 3}};
+    for (uint32_t b = 0; b < bins; ++b) {
+        if (!pt_isfinite(centres_nm[b])) return ofail(PT_ERR_INVALID_ARGUMENT, "a bin centre is not finite");
+        char name[96];
+        snprintf(name, sizeof(name), "S0.%.6fnm", (double)centres_nm[b]);   // (the spectral-EXR convention: a ',' for the decimal point — a '.' separates layers)
+        for (char* c = name + 3; *c; ++c) if (*c == '.') *c = ',';
+        channels.push_back({name, spectral + (size_t)b * w * h, 1});
     }
-    fclose(f);
-    return PT_OK;
+    std::sort(channels.begin(), channels.end(), [](const ExrChannel& a, const ExrChannel& b) { return a.name < b.name; });   // (byte-wise, as the format requires)
+    for (size_t k = 1; k < channels.size(); ++k)
+        if (channels[k].name == channels[k - 1].name) return ofail(PT_ERR_INVALID_ARGUMENT, "two bins share the channel name " + channels[k].name);
+    return write_exr_channels(path, w, h, channels, colorspace, true);
 }
 
 }  // extern "C"

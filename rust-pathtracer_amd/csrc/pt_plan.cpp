@@ -203,4 +203,33 @@ pt_status check_guides_chain_args(const void* scene, const pt_render_desc* rd, u
     return PT_OK;
 }
 
+pt_status check_spectral_desc(const pt_spectral_desc* sd, std::string* error) {
+    if (!sd) { *error = "the spectral desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (sd->bins == 0) { *error = "bins must be positive"; return PT_ERR_INVALID_ARGUMENT; }
+    if (sd->bins > PT_SPECTRAL_MAX_BINS) { *error = "bins: at most 64"; return PT_ERR_INVALID_ARGUMENT; }
+    for (uint32_t r : sd->reserved) if (r != 0) { *error = "pt_spectral_desc::reserved must be 0"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
+pt_status check_spectral_args(const void* scene, const pt_render_desc* rd, const pt_spectral_desc* sd, const void* film, const void* spectral, std::string* error) {
+    if (!scene) { *error = "the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!rd) { *error = "the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = check_spectral_desc(sd, error);
+    if (st != PT_OK) return st;
+    if (!film) { *error = "film_xyzw is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!spectral) { *error = "the spectral film is null"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
+pt_status spectral_bin_centres(const pt_render_desc* rd, const pt_spectral_desc* sd, float* centres_nm, std::string* error) {
+    if (!rd) { *error = "the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = check_spectral_desc(sd, error);
+    if (st != PT_OK) return st;
+    if (!centres_nm) { *error = "centres_nm is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!(rd->wavelength_hi >= rd->wavelength_lo)) { *error = "bad wavelength bounds"; return PT_ERR_INVALID_ARGUMENT; }
+    const float w = (rd->wavelength_hi - rd->wavelength_lo) / (float)sd->bins;
+    for (uint32_t b = 0; b < sd->bins; ++b) centres_nm[b] = rd->wavelength_lo + ((float)b + 0.5f) * w;
+    return PT_OK;
+}
+
 }  // namespace pth

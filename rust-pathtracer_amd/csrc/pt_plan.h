@@ -10,6 +10,7 @@
 #include "../../include/pt_adaptive.h"
 #include "../../include/pt_api.h"
 #include "../../include/pt_denoise.h"
+#include "../../include/pt_spectral.h"
 #include "pt_stages.h"
 
 namespace pth {
@@ -47,6 +48,14 @@ pt_status check_albedo_basis_args(const pt_render_desc* rd, const void* lambda, 
 // pt_render_guides_chain's arguments: the chain desc first (its refusals need no scene), then check_guides_args; *out = the desc with its default filled in
 pt_status check_guides_chain_args(const void* scene, const pt_render_desc* rd, uint32_t camera_count, uint32_t guide_samples, const pt_guide_chain_desc* chain,
                                   const void* guides, pt_guide_chain_desc* out, std::string* error);
+
+// pt_render_spectral's arguments (include/pt_spectral.h), for the engine and the host emulation alike, checked before the engine looks for a device:
+// bins in 1..PT_SPECTRAL_MAX_BINS, reserved words 0, no null pointer; each refusal is PT_ERR_INVALID_ARGUMENT with its own message.  medium_aware
+// is allowed (one wavelength per path, nothing about it differs), and everything else about the render desc is normalize_render_desc's to judge.
+pt_status check_spectral_desc(const pt_spectral_desc* sd, std::string* error);
+pt_status check_spectral_args(const void* scene, const pt_render_desc* rd, const pt_spectral_desc* sd, const void* film, const void* spectral, std::string* error);
+// pt_spectral_bin_centres: centres_nm[b] = lo + ((float)b + 0.5f) * ((hi - lo) / (float)bins)
+pt_status spectral_bin_centres(const pt_render_desc* rd, const pt_spectral_desc* sd, float* centres_nm, std::string* error);
 
 }  // namespace pth
 #endif

@@ -13,10 +13,17 @@
  *
  * Units: the mean per-sample energy that fell into the bin.  NOTHING is divided by the bin width: a spectral density is S[b] / w.
  * Layout: bin-major planes, row-major with y = 0 the top row like the film: spectral[b * width * height + y * width + x], f32.  Pixels outside
- * the call's shard stay 0. */
+ * the call's shard stay 0.
+ *
+ * pt_render_adaptive_spectral is pt_render_adaptive with the same bins: a pixel that took n samples holds the fold of those n samples divided by (float)n,
+ * so its bins are pixel p of pt_render_spectral at spp = n, bit for bit.  pt_denoise_spectral filters that film and its bins together: the taps and the
+ * edge-stopping weights of every a-trous pass are pt_denoise_film's — they come from the XYZ film, its variance and the guides alone — and each bin plane is
+ * averaged with them (csrc/pt_denoise_spectral_rules.h, operation by operation).  The bins have no variance of their own and are not demodulated. */
 #ifndef PT_SPECTRAL_H
 #define PT_SPECTRAL_H
+#include "pt_adaptive.h"
 #include "pt_api.h"
+#include "pt_denoise.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -34,6 +41,23 @@ typedef struct pt_spectral_desc {
  * kernel_seconds[4] (accumulate) includes the spectral kernel. */
 pt_status pt_render_spectral(pt_scene* scene, const pt_render_desc* desc, const pt_spectral_desc* spectral_desc,
                              float* film_xyzw, float* spectral, pt_profile* profile);
+
+/* pt_render_adaptive with a spectral film.  desc, adaptive, film_xyzw, sample_counts (required), stats (may be NULL) and profile: pt_render_adaptive's, with
+ * the same conditions; film, counts, stats, the number of rounds and the ray counters are pt_render_adaptive's bit for bit.  spectral: bins*width*height f32,
+ * required; pixel p's bins are the plain f32 running sums over its n_p samples in sample order, divided once by (float)n_p when the render finishes.
+ * One device only: pt_render_adaptive_multi has no spectral film. */
+pt_status pt_render_adaptive_spectral(pt_scene* scene, const pt_render_desc* desc, const pt_adaptive_desc* adaptive, const pt_spectral_desc* spectral_desc,
+                                      float* film_xyzw, uint32_t* sample_counts, double* stats, float* spectral, pt_profile* profile);
+
+/* pt_denoise_film on film_xyzw (desc, sample_counts, stats, guides_xyzw, out_film_xyzw, out_variance: as pt_denoise_film takes them) and, with the same taps
+ * and weights, on the `bins` (1 .. PT_SPECTRAL_MAX_BINS) planes of `spectral` (bins*width*height f32, the layout above).  Pass i, live pixel p, bin b:
+ *     sb = 0.0f;  sb = sb + w_q * s_b,i(q) over the taps q that pt_denoise_film's pass takes, in its order;  s_b,i+1(p) = sb / sw
+ * with w_q and sw the weights and their sum that the colour of p is averaged with.  A tap that is skipped adds nothing.  A pixel is dead — copied through,
+ * film and bins, and never read — when pt_denoise_film calls it dead or when one of its bins is not finite.  Where no pixel is dead through its bins alone,
+ * out_film_xyzw and out_variance are pt_denoise_film's bit for bit.  There is no albedo form: demodulating the bins needs a per-bin albedo.
+ * Host arrays in, host arrays out; out_film_xyzw may be film_xyzw and out_spectral may be spectral.  out_variance may be NULL. */
+pt_status pt_denoise_spectral(const pt_denoise_desc* desc, uint32_t bins, const float* film_xyzw, const uint32_t* sample_counts, const double* stats,
+                              const float* guides_xyzw, const float* spectral, float* out_film_xyzw, float* out_spectral, float* out_variance);
 
 /* bin b covers [lo + b*w, lo + (b+1)*w), w = (hi-lo)/bins;
  * centres_nm[b] = lo + ((float)b + 0.5f) * w, from the desc's wavelength bounds (f32).  Host only. */

@@ -265,6 +265,11 @@ class Library:
         self._render_spectral = bind("render_spectral", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(SpectralDesc), fpp, fpp, C.POINTER(Profile)], required=False)
         self._spectral_bin_centres = bind("spectral_bin_centres", C.c_int32, [C.POINTER(RenderDesc), C.POINTER(SpectralDesc), fpp], required=False)
         self._write_exr_spectral = bind("write_exr_spectral", C.c_int32, [C.c_char_p, u32, u32, u32, fpp, fpp, fpp, C.c_int32], required=False)
+        self._render_adaptive_spectral = bind("render_adaptive_spectral", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), C.POINTER(SpectralDesc), fpp,
+                                                                                      C.POINTER(u32), C.POINTER(C.c_double), fpp, C.POINTER(Profile)], required=False)
+        self._denoise_spectral = bind("denoise_spectral", C.c_int32, [C.POINTER(DenoiseDesc), u32, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp, fpp],
+                                      required=False)
+        self._denoise_spectral_last_error = bind("denoise_spectral_last_error", C.c_char_p, [], required=False)   # (the emulation's)
         self._device_info = bind("device_info", C.c_char_p, [], required=False)
         self._output_film = bind("output_film", C.c_int32, [C.POINTER(OutputDesc), fpp, C.POINTER(C.c_uint8), fpp], required=False)
         self._write_png = bind("write_png", C.c_int32, [C.c_char_p, u32, u32, C.POINTER(C.c_uint8), C.c_int32], required=False)
@@ -361,6 +366,34 @@ class Library:
                 raise PtError(st, self._albedo_error())
             raise PtError(st, self._denoise_last_error().decode() if self._denoise_last_error else self.last_error())
         return (out, var) if variance else out
+
+    def denoise_spectral(self, film, counts, stats, guides, spectral, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, device=0, variance=False,
+                         albedo=None):
+        """pt_denoise_spectral: denoise_film's filter over the film and, with the same taps and weights, over the bins spectral [B,H,W] of
+        Scene.render_adaptive_spectral.  Returns (denoised [H,W,4], denoised_spectral [B,H,W]), with variance=True (denoised, denoised_spectral, variance [H,W]).
+        There is no albedo form: an `albedo` is refused (demodulating the bins needs a per-bin albedo)."""
+        if albedo is not None:
+            raise PtError(PT_ERR_UNSUPPORTED, "denoise_spectral takes no albedo: demodulating the bins needs a per-bin albedo")
+        if self._denoise_spectral is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sdenoise_spectral entry" % (self.path, self.prefix))
+        film = np.ascontiguousarray(film, dtype=np.float32)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        stats = np.ascontiguousarray(stats, dtype=np.float64)
+        guides = np.ascontiguousarray(guides, dtype=np.float32)
+        spectral = np.ascontiguousarray(spectral, dtype=np.float32)
+        h, w = film.shape[:2]
+        if film.shape != (h, w, 4) or counts.shape != (h, w) or stats.shape != (h, w, 2) or guides.shape != (h, w, 4) or spectral.ndim != 3 or spectral.shape[1:] != (h, w):
+            raise ValueError("film [H,W,4], counts [H,W], stats [H,W,2], guides [H,W,4] and spectral [B,H,W] of one film size")
+        bins = spectral.shape[0]
+        d = DenoiseDesc(w, h, iterations, sigma_luminance, sigma_depth, normal_power_log2, device)
+        out = np.zeros((h, w, 4), np.float32)
+        out_spectral = np.zeros((bins, h, w), np.float32)
+        var = np.zeros((h, w), np.float32) if variance else None
+        st = self._denoise_spectral(C.byref(d), bins, _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)), stats.ctypes.data_as(C.POINTER(C.c_double)), _fp(guides),
+                                    _fp(spectral), _fp(out), _fp(out_spectral), _fp(var) if variance else None)
+        if st != PT_OK:
+            raise PtError(st, self._denoise_spectral_last_error().decode() if self._denoise_spectral_last_error else self.last_error())
+        return (out, out_spectral, var) if variance else (out, out_spectral)
 
     def write_png(self, path, rgba8, colorspace=COLORSPACE_SRGB):
         rgba8 = np.ascontiguousarray(rgba8, np.uint8)
@@ -461,6 +494,22 @@ class Scene:
                                                          st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, C.byref(prof)))
         return (film, counts, st, prof) if stats else (film, counts, prof)
 
+    def render_adaptive_spectral(self, rd, bins, max_samples, rel_error, abs_error=0.0, step=0, stats=False):
+        """pt_render_adaptive_spectral: render_adaptive with a spectral film.  Returns (film, counts[, stats], spectral, profile): film, counts and stats are
+        render_adaptive's bit for bit; spectral [bins,H,W] holds per pixel the bins of render_spectral at that pixel's own sample count."""
+        if self.library._render_adaptive_spectral is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_adaptive_spectral entry" % (self.library.path, self.library.prefix))
+        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        counts = np.zeros((rd.height, rd.width), dtype=np.uint32)
+        st = np.zeros((rd.height, rd.width, 2), dtype=np.float64) if stats else None
+        spectral = np.zeros((max(int(bins), 0), rd.height, rd.width), dtype=np.float32)
+        ad = AdaptiveDesc(max_samples, step, rel_error, abs_error)
+        sd = SpectralDesc(bins)
+        prof = Profile()
+        self.library.check(self.library._render_adaptive_spectral(self.handle, C.byref(rd), C.byref(ad), C.byref(sd), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                                  st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, _fp(spectral), C.byref(prof)))
+        return (film, counts, st, spectral, prof) if stats else (film, counts, spectral, prof)
+
     def render_adaptive_multi(self, rd, max_samples, rel_error, abs_error=0.0, step=0, stats=False, device_mask=0):
         """pt_render_adaptive_multi: render_adaptive on every device of the mask (0 = all) from one blocking call, its outputs bit for bit.
         Returns (film, counts[, stats], profile) as render_adaptive does."""
@@ -534,6 +583,22 @@ class Scene:
             guides, alb = self.render_guides(rd, guide_samples), None
         den = self.library.denoise_film(film, counts, st, guides, iterations, sigma_luminance, sigma_depth, normal_power_log2, device, albedo=alb)
         return film, den, counts, prof
+
+    def render_denoised_spectral(self, rd, bins, max_samples=None, rel_error=0.0, guide_samples=4, specular_chain=0, abs_error=0.0, step=0, iterations=0,
+                                 sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, albedo=False):
+        """render_adaptive_spectral with statistics (max_samples None = rd.spp: a fixed count), its guides — render_guides, or render_guides_chain with max_chain
+        `specular_chain` when that is positive — and denoise_spectral: (film, denoised, spectral, denoised_spectral, counts, profile).  `albedo` is refused, as
+        denoise_spectral refuses it."""
+        if albedo:
+            raise PtError(PT_ERR_UNSUPPORTED, "render_denoised_spectral takes no albedo: demodulating the bins needs a per-bin albedo")
+        mx = rd.spp if max_samples is None else max_samples
+        film, counts, st, spectral, prof = self.render_adaptive_spectral(rd, bins, mx, rel_error, abs_error, step, stats=True)
+        if specular_chain > 0:
+            guides, _ = self.render_guides_chain(rd, guide_samples, specular_chain, albedo=False)
+        else:
+            guides = self.render_guides(rd, guide_samples)
+        den, den_spectral = self.library.denoise_spectral(film, counts, st, guides, spectral, iterations, sigma_luminance, sigma_depth, normal_power_log2)
+        return film, den, spectral, den_spectral, counts, prof
 
     def render_multi(self, rd, device_mask=0):
         """pt_render_multi: every device of the mask (0 = all) from one blocking call."""

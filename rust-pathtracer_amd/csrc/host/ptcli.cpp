@@ -4,7 +4,7 @@
 //
 //   ptcli [--config data/config.toml] [--scene FILE] [-n|--dry-run] [--stdout-log-level L] [--write-log-level L]
 //         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K] [--demodulate-albedo]
-//         [--guide-chain D] [--guide-alpha-max A] [--spectral-bins B]
+//         [--guide-chain D] [--guide-alpha-max A] [--spectral-bins B] [--denoise-spectral-bins B]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -22,6 +22,10 @@
 // --spectral-bins B (1..64) renders every setting through pt_render_spectral (include/pt_spectral.h) and also writes <filename>_spectral.exr: one FLOAT channel
 // per wavelength bin (times the factor of the EXR payload) beside the R, G, B of <filename>.exr.  The usual files stay byte for byte what they are.  It is
 // refused together with --adaptive, --denoise and a --devices mask that names more than one GPU (or one other than device 0, where the call renders).
+// --denoise-spectral-bins B (1..64, with --denoise only) renders every setting through pt_render_adaptive_spectral and filters the film and its bins together
+// (pt_denoise_spectral): next to the usual and the _denoised files, which stay byte for byte what --denoise alone writes, it writes <filename>_spectral.exr and
+// <filename>_denoised_spectral.exr, the bins times the factor of the EXR payload beside the R, G, B of the film and of the denoised film.  It is refused with
+// --spectral-bins, with --demodulate-albedo (the bins have no albedo) and with a --devices mask other than device 0 (the node calls have no spectral film).
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -54,6 +58,7 @@ struct Options {
     float alpha_max = 0.0f;   // --guide-alpha-max A (0 = the default)
     bool has_alpha_max = false;
     uint32_t spectral_bins = 0;   // --spectral-bins B: <filename>_spectral.exr through pt_render_spectral; 0 = off
+    uint32_t denoise_bins = 0;    // --denoise-spectral-bins B: the adaptive spectral render and the joint filter; 0 = off
 };
 
 int usage(const char* msg) {
@@ -61,7 +66,7 @@ int usage(const char* msg) {
     fprintf(stderr, "usage: ptcli [--config FILE] [--scene FILE] [-n|--dry-run] [--stdout-log-level LEVEL] [--write-log-level LEVEL]\n"
                     "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n"
                     "             [--denoise] [--guide-samples K] [--demodulate-albedo] [--guide-chain D] [--guide-alpha-max A]\n"
-                    "             [--spectral-bins B]\n");
+                    "             [--spectral-bins B] [--denoise-spectral-bins B]\n");
     return 2;
 }
 
@@ -138,12 +143,20 @@ int main(int argc, char** argv) {
             if (end == v.c_str() || *end || b == 0 || b > PT_SPECTRAL_MAX_BINS) return usage("--spectral-bins needs a count in 1..64");
             o.spectral_bins = (uint32_t)b;
         }
+        else if (a == "--denoise-spectral-bins") {
+            if (!value(&v)) return usage("--denoise-spectral-bins needs a value");
+            char* end = nullptr;
+            const unsigned long b = strtoul(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end || b == 0 || b > PT_SPECTRAL_MAX_BINS) return usage("--denoise-spectral-bins needs a count in 1..64");
+            o.denoise_bins = (uint32_t)b;
+        }
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
     }
     if (o.demodulate && !o.denoise) return usage("--demodulate-albedo needs --denoise");
     if (o.chain && !o.denoise) return usage("--guide-chain needs --denoise");
     if (o.has_alpha_max && !o.chain) return usage("--guide-alpha-max needs --guide-chain");
+    if (o.denoise_bins && o.spectral_bins) return usage("--denoise-spectral-bins cannot be combined with --spectral-bins: it writes the spectral files itself");
     if (o.spectral_bins && o.adaptive >= 0.0f) return usage("--spectral-bins cannot be combined with --adaptive: an adaptive render has no spectral film");
     if (o.spectral_bins && o.denoise) return usage("--spectral-bins cannot be combined with --denoise: the denoiser takes the adaptive path, which has no spectral film");
     if (o.spectral_bins && o.multi) {   // (pt_render_spectral renders on the scene's device, device 0: a mask may name that one alone; 0 = every device of the node)
@@ -151,6 +164,9 @@ int main(int argc, char** argv) {
             return usage("--spectral-bins cannot be combined with --devices naming more than one GPU: pt_render_multi has no spectral film");
         if (o.device_mask > 1) return usage("--spectral-bins renders on device 0: --devices may name that device alone");
     }
+    if (o.denoise_bins && !o.denoise) return usage("--denoise-spectral-bins needs --denoise");
+    if (o.denoise_bins && o.demodulate) return usage("--denoise-spectral-bins cannot be combined with --demodulate-albedo: demodulating the bins needs a per-bin albedo");
+    if (o.denoise_bins && o.multi && o.device_mask != 1) return usage("--denoise-spectral-bins renders on device 0: --devices may name that device alone");
     const bool verbose = o.stdout_log_level == "info" || o.stdout_log_level == "debug" || o.stdout_log_level == "trace";
     const bool warnings = verbose || o.stdout_log_level == "warn";
     if (!o.root.empty()) pt_scene_file_set_root(o.root.c_str());
@@ -232,21 +248,25 @@ int main(int argc, char** argv) {
             const bool with_counts = adaptive || o.denoise;
             std::vector<uint32_t> counts(with_counts ? (size_t)rd.width * rd.height : 0);
             std::vector<double> stats(o.denoise ? (size_t)rd.width * rd.height * 2 : 0);
-            std::vector<float> spectral;
+            std::vector<float> spectral((size_t)o.denoise_bins * rd.width * rd.height);   // (--spectral-bins sizes it below)
+            const pt_spectral_desc dsd = {o.denoise_bins, {0u, 0u, 0u}};
+            const char* adaptive_entry = o.denoise_bins ? "pt_render_adaptive_spectral" : o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive";
             uint64_t samples = (uint64_t)rd.width * rd.height * rd.spp;
             if (!adaptive && o.denoise) {
                 // a fixed count through the adaptive path (max_samples = min_samples, one round): pt_render's film bit for bit, and the statistics
                 printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
                 ad.max_samples = rd.spp; ad.rel_error = 0.0f;
-                const pt_status st = o.multi ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), stats.data(), &prof)
-                                             : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), stats.data(), &prof);
-                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive", pt_last_error()); rc = 1; break; }
+                const pt_status st = o.denoise_bins ? pt_render_adaptive_spectral(scene, &rd, &ad, &dsd, film.data(), counts.data(), stats.data(), spectral.data(), &prof)
+                                     : o.multi      ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), stats.data(), &prof)
+                                                    : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), stats.data(), &prof);
+                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", adaptive_entry, pt_last_error()); rc = 1; break; }
             } else if (adaptive) {
                 printf("rendering %ux%u, %u..%u spp (adaptive, relative error %g), max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, ad.max_samples,
                        (double)ad.rel_error, rd.max_bounces, rd.light_samples);
-                const pt_status st = o.multi ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof)
-                                             : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof);
-                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive", pt_last_error()); rc = 1; break; }
+                const pt_status st = o.denoise_bins ? pt_render_adaptive_spectral(scene, &rd, &ad, &dsd, film.data(), counts.data(), stats.data(), spectral.data(), &prof)
+                                     : o.multi      ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof)
+                                                    : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof);
+                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", adaptive_entry, pt_last_error()); rc = 1; break; }
                 uint32_t lo = 0xffffffffu, hi = 0;
                 samples = 0;
                 for (uint32_t c : counts) { samples += c; lo = c < lo ? c : lo; hi = c > hi ? c : hi; }
@@ -279,17 +299,24 @@ int main(int argc, char** argv) {
             }
             if (o.write_film && !write_npy(base + ".npy", film.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", base.c_str()); rc = 1; break; }
             printf("wrote %s.exr and %s.png\n", base.c_str(), base.c_str());
-            if (!spectral.empty()) {
-                // the bins in the units of the EXR payload: the same factor, applied here, one multiply per value
-                const pt_spectral_desc sd = {o.spectral_bins, {0u, 0u, 0u}};
-                std::vector<float> centres(o.spectral_bins);
-                for (float& v : spectral) v *= od.factor;
+            // the bins in the units of the EXR payload: the same factor, applied here in place, one multiply per value
+            const uint32_t file_bins = o.spectral_bins ? o.spectral_bins : o.denoise_bins;
+            const auto write_spectral = [&](const std::string& name, std::vector<float>& scaled) {
+                const pt_spectral_desc sd = {file_bins, {0u, 0u, 0u}};
+                std::vector<float> centres(file_bins);
+                for (float& v : scaled) v *= od.factor;
                 if (pt_spectral_bin_centres(&rd, &sd, centres.data()) != PT_OK ||
-                    pt_write_exr_spectral((base + "_spectral.exr").c_str(), rd.width, rd.height, o.spectral_bins, centres.data(), spectral.data(), linear.data(), od.colorspace) != PT_OK) {
-                    fprintf(stderr, "--spectral-bins: %s\n", pt_last_error()); rc = 1; break;
+                    pt_write_exr_spectral((name + ".exr").c_str(), rd.width, rd.height, file_bins, centres.data(), scaled.data(), linear.data(), od.colorspace) != PT_OK) {
+                    fprintf(stderr, "%s: %s\n", o.spectral_bins ? "--spectral-bins" : "--denoise-spectral-bins", pt_last_error());
+                    return false;
                 }
-                printf("wrote %s_spectral.exr (%u bins)\n", base.c_str(), o.spectral_bins);
-            }
+                printf("wrote %s.exr (%u bins)\n", name.c_str(), file_bins);
+                return true;
+            };
+            if (o.denoise_bins) {   // (a copy: the filter below takes the bins as rendered)
+                std::vector<float> noisy(spectral);
+                if (!write_spectral(base + "_spectral", noisy)) { rc = 1; break; }
+            } else if (!spectral.empty() && !write_spectral(base + "_spectral", spectral)) { rc = 1; break; }
             if (o.denoise) {
                 std::vector<float> guides((size_t)rd.width * rd.height * 4), clean((size_t)rd.width * rd.height * 4);
                 pt_denoise_desc dd;
@@ -303,10 +330,13 @@ int main(int argc, char** argv) {
                 const pt_status gst = o.chain ? pt_render_guides_chain(scene, &rd, o.guide_samples, &cd, guides.data(), o.demodulate ? albedo.data() : nullptr)
                                       : o.demodulate ? pt_render_guides_albedo(scene, &rd, o.guide_samples, guides.data(), albedo.data())
                                                      : pt_render_guides(scene, &rd, o.guide_samples, guides.data());
-                if (gst != PT_OK || pt_denoise_film_albedo(&dd, film.data(), counts.data(), stats.data(), guides.data(), o.demodulate ? albedo.data() : nullptr,
-                                                           clean.data(), nullptr) != PT_OK) {
-                    fprintf(stderr, "--denoise: %s\n", pt_last_error()); rc = 1; break;
-                }
+                std::vector<float> clean_spectral(spectral.size());
+                const pt_status dst = gst != PT_OK ? gst
+                                      : o.denoise_bins ? pt_denoise_spectral(&dd, o.denoise_bins, film.data(), counts.data(), stats.data(), guides.data(), spectral.data(), clean.data(),
+                                                                             clean_spectral.data(), nullptr)
+                                                       : pt_denoise_film_albedo(&dd, film.data(), counts.data(), stats.data(), guides.data(), o.demodulate ? albedo.data() : nullptr,
+                                                                                clean.data(), nullptr);
+                if (dst != PT_OK) { fprintf(stderr, "--denoise: %s\n", pt_last_error()); rc = 1; break; }
                 if (pt_output_film(&od, clean.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }
                 const std::string dbase = base + "_denoised";
                 if (pt_write_exr((dbase + ".exr").c_str(), rd.width, rd.height, linear.data(), od.colorspace) != PT_OK ||
@@ -315,6 +345,7 @@ int main(int argc, char** argv) {
                 }
                 if (o.write_film && !write_npy(dbase + ".npy", clean.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", dbase.c_str()); rc = 1; break; }
                 printf("wrote %s.exr and %s.png\n", dbase.c_str(), dbase.c_str());
+                if (o.denoise_bins && !write_spectral(dbase + "_spectral", clean_spectral)) { rc = 1; break; }   // (`linear` now holds the denoised film's R, G, B)
             }
         }
         if (scene) pt_scene_destroy(scene);

@@ -244,6 +244,22 @@ void albedo_basis(float wavelength_lo, float wavelength_hi, DnAlbedoBasis* basis
     dn_albedo_basis(wavelength_lo, wavelength_hi, [](float angstrom, float* x, float* y, float* z) { xyz_bar(angstrom, x, y, z); }, basis);
 }
 
+
+// the filter's kernels for pt_denoise_spectral (pt_denoise_spectral.hip), unchanged
+void launch_dn_prepare(const DnParams& P, const float* film, const uint32_t* counts, const double* stats, const float* guides, float* color, float* geo, uint8_t* flags,
+                       float* grad) {
+    hipLaunchKernelGGL(k_dn_prepare, dim3(line_grid((size_t)P.width * P.height)), dim3(kLine), 0, 0, P, reinterpret_cast<const float4*>(film), counts,
+                       reinterpret_cast<const double2*>(stats), reinterpret_cast<const float4*>(guides), reinterpret_cast<float4*>(color), reinterpret_cast<float4*>(geo), flags,
+                       reinterpret_cast<float2*>(grad));
+}
+void launch_dn_tent(const DnParams& P, const float* color, const float* geo, const uint8_t* flags, float* tent) {
+    const DnBuffers b{reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(geo), tent, flags, nullptr};
+    hipLaunchKernelGGL(k_dn_tent, dim3((P.width + kTileW - 1) / kTileW, (P.height + kTileH - 1) / kTileH), dim3(kTileW, kTileH), 0, 0, P, b, tent);
+}
+void launch_dn_finish(uint32_t n_pixels, const float* color, float* film, float* variance) {
+    hipLaunchKernelGGL(k_dn_finish, dim3(line_grid(n_pixels)), dim3(kLine), 0, 0, n_pixels, reinterpret_cast<const float4*>(color), reinterpret_cast<float4*>(film), variance);
+}
+
 }  // namespace ptk
 
 extern "C" pt_status pt_albedo_basis(const pt_render_desc* desc, float* lambda, float* xyz) {

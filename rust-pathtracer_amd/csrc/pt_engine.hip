@@ -30,6 +30,7 @@
 #include "../../include/pt_denoise.h"
 #include "pt_adaptive_select.h"
 #include "pt_spectral_launch.h"
+#include "pt_spectral_rules.h"
 #include "pt_denoise_launch.h"
 #include "pt_error.h"
 #include "pt_guides_chain_launch.h"
@@ -189,6 +190,15 @@ __global__ void __launch_bounds__(kBlock) k_adaptive_finish(uint32_t n_pixels, c
         const float4 v = *px;
         const float c = (float)n;
         *px = make_float4(v.x / c, v.y / c, v.z / c, 0.0f);
+    }
+}
+// finish of pt_render_adaptive_spectral: every bin of a pixel divided by the pixel's own count (spectral_finish_value); plane by plane, so that neighbouring
+// lanes touch neighbouring floats
+__global__ void __launch_bounds__(kBlock) k_adaptive_finish_spectral(uint32_t n_pixels, uint32_t bins, const uint32_t* __restrict__ counts, float* __restrict__ spectral) {
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_pixels; p += gridDim.x * blockDim.x) {
+        const uint32_t n = counts[p];
+        float* px = spectral + p;
+        for (uint32_t b = 0; b < bins; ++b) px[(size_t)b * n_pixels] = spectral_finish_value(px[(size_t)b * n_pixels], n);
     }
 }
 // the exchange of pt_render_adaptive_multi between the virtual devices of one physical device: dst |= src over two unconverged images of n bytes
@@ -472,11 +482,12 @@ pt_status adaptive_rounds(pt_scene* sc, const pt_render_desc& rd, const pt_adapt
 // Set-up (kernel forms, queues, launch configuration) and one pass loop over a device pixel list and a sample range: pt_render runs the loop once over its
 // shard's pixels; with `adaptive` (pt_render_adaptive, its arguments checked) adaptive_rounds runs it once per round, over the film or (with `node`: worker
 // node_index of pt_render_adaptive_multi) over the desc's shard.  With `d_spectral` (pt_render_spectral: spectral_bins planes of width * height floats, its
-// arguments checked) every pass also adds its samples to the wavelength-binned film (include/pt_spectral.h).
+// arguments checked) every pass also adds its samples to the wavelength-binned film (include/pt_spectral.h); with both (pt_render_adaptive_spectral, one device) the
+// bins hold running sums, a continued pixel starting from its stored value, until k_adaptive_finish_spectral divides each pixel's by its own count.
 pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hipStream_t stream, pt_profile* profile, const pt_adaptive_desc* adaptive = nullptr,
                       NodeRounds* node = nullptr, int node_index = 0, float* d_spectral = nullptr, uint32_t spectral_bins = 0) {
     if (!sc || !rdp || !d_film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    if (adaptive && d_spectral) return fail(PT_ERR_UNSUPPORTED, "the spectral film of an adaptive render is not supported");
+    if (node && d_spectral) return fail(PT_ERR_UNSUPPORTED, "the spectral film of an adaptive render on several devices is not supported");
     pt_render_desc rd;
     std::string err;
     if (!pth::normalize_render_desc(*rdp, (uint32_t)sc->host.cameras.size(), &rd, &err)) return fail(PT_ERR_INVALID_ARGUMENT, err);
@@ -702,6 +713,8 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     st = adaptive ? adaptive_rounds(sc, rd, *adaptive, stream, d_film, (uint32_t)pixels.size(), run_passes, &rounds, node, node_index)
                   : run_passes(b.pixels, (uint32_t)pixels.size(), rd.first_sample, rd.sample_count, nullptr);
     if (st != PT_OK) return st;
+    if (adaptive && d_spectral)
+        hipLaunchKernelGGL(k_adaptive_finish_spectral, dim3(sc->num_cus * 4), dim3(kBlock), 0, stream, rd.width * rd.height, spectral_bins, sc->adaptive.counts, d_spectral);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     auto t1 = std::chrono::steady_clock::now();
@@ -943,6 +956,16 @@ pt_status pt_render_adaptive(pt_scene* sc, const pt_render_desc* rdp, const pt_a
     return PT_OK;
 }
 
+static pt_status ensure_spectral_cache(pt_scene* sc, size_t bytes) {   // (kept with the scene, like the film)
+    if (sc->spectral_cache_bytes < bytes) {
+        if (sc->spectral_cache) hipFree(sc->spectral_cache);
+        sc->spectral_cache = nullptr; sc->spectral_cache_bytes = 0;
+        HIP_TRY(hipMalloc(&sc->spectral_cache, bytes));
+        sc->spectral_cache_bytes = bytes;
+    }
+    return PT_OK;
+}
+
 pt_status pt_render_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_spectral_desc* sdp, float* film, float* spectral, pt_profile* profile) {
     std::string err;
     pt_status st = pth::check_spectral_args(sc, rdp, sdp, film, spectral, &err);
@@ -952,16 +975,36 @@ pt_status pt_render_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_s
     const size_t n_pixels = (size_t)rdp->width * rdp->height, film_bytes = sizeof(float) * 4 * n_pixels, spectral_bytes = sizeof(float) * sdp->bins * n_pixels;
     st = ensure_film_cache(sc, film_bytes);
     if (st != PT_OK) return st;
-    if (sc->spectral_cache_bytes < spectral_bytes) {   // (kept with the scene, like the film)
-        if (sc->spectral_cache) hipFree(sc->spectral_cache);
-        sc->spectral_cache = nullptr; sc->spectral_cache_bytes = 0;
-        HIP_TRY(hipMalloc(&sc->spectral_cache, spectral_bytes));
-        sc->spectral_cache_bytes = spectral_bytes;
-    }
+    st = ensure_spectral_cache(sc, spectral_bytes);
+    if (st != PT_OK) return st;
     st = render_impl(sc, rdp, sc->film_cache, nullptr, profile, nullptr, nullptr, 0, sc->spectral_cache, sdp->bins);
     if (st != PT_OK) return st;
     HIP_TRY(hipMemcpy(film, sc->film_cache, film_bytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(spectral, sc->spectral_cache, spectral_bytes, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+pt_status pt_render_adaptive_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, const pt_spectral_desc* sdp, float* film,
+                                      uint32_t* sample_counts, double* stats, float* spectral, pt_profile* profile) {
+    pt_render_desc rd;
+    pt_adaptive_desc ad;
+    std::string err;
+    pt_status st = pth::check_adaptive_spectral_args(sc, rdp, adp, sdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, film, sample_counts, spectral, &rd, &ad, &err);
+    if (st != PT_OK) return fail(st, err);
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t n_pixels = (size_t)rd.width * rd.height, spectral_bytes = sizeof(float) * sdp->bins * n_pixels;
+    st = ensure_film_cache(sc, sizeof(float) * 4 * n_pixels);
+    if (st != PT_OK) return st;
+    st = ensure_spectral_cache(sc, spectral_bytes);
+    if (st != PT_OK) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    st = render_impl(sc, &rd, sc->film_cache, nullptr, profile, &ad, nullptr, 0, sc->spectral_cache, sdp->bins);
+    if (st != PT_OK) return st;
+    HIP_TRY(hipMemcpy(film, sc->film_cache, sizeof(float) * 4 * n_pixels, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sample_counts, sc->adaptive.counts, sizeof(uint32_t) * n_pixels, hipMemcpyDeviceToHost));
+    if (stats) HIP_TRY(hipMemcpy(stats, sc->adaptive.stats, sizeof(double) * 2 * n_pixels, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(spectral, sc->spectral_cache, spectral_bytes, hipMemcpyDeviceToHost));
+    if (profile) profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (the whole call: set-up, rounds, read-backs)
     return PT_OK;
 }
 

@@ -232,4 +232,28 @@ pt_status spectral_bin_centres(const pt_render_desc* rd, const pt_spectral_desc*
     return PT_OK;
 }
 
+pt_status check_adaptive_spectral_args(const void* scene, const pt_render_desc* rd, const pt_adaptive_desc* ad, const pt_spectral_desc* sd, uint32_t camera_count,
+                                       const void* film, const void* sample_counts, const void* spectral, pt_render_desc* rd_out, pt_adaptive_desc* ad_out,
+                                       std::string* error) {
+    if (!scene) { *error = "the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!rd) { *error = "the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!ad) { *error = "the adaptive desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = check_spectral_desc(sd, error);
+    if (st != PT_OK) return st;
+    if (!film) { *error = "film_xyzw is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!spectral) { *error = "the spectral film is null"; return PT_ERR_INVALID_ARGUMENT; }
+    return normalize_adaptive_desc(*rd, *ad, sample_counts != nullptr, camera_count, rd_out, ad_out, error);
+}
+
+pt_status check_denoise_spectral_args(const pt_denoise_desc* in, uint32_t bins, const void* film, const uint32_t* sample_counts, const void* stats, const float* guides,
+                                      const void* spectral, const void* out_film, const void* out_spectral, pt_denoise_desc* out, std::string* error) {
+    if (bins == 0) { *error = "bins must be positive"; return PT_ERR_INVALID_ARGUMENT; }
+    if (bins > PT_SPECTRAL_MAX_BINS) { *error = "bins: at most 64"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!spectral) { *error = "the spectral film is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!out_spectral) { *error = "out_spectral is null"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = normalize_denoise_desc(in, film, sample_counts, stats, guides, out_film, out, error);
+    if (st != PT_OK) return st;
+    return check_denoise_inputs(*out, sample_counts, guides, error);
+}
+
 }  // namespace pth

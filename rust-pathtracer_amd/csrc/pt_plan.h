@@ -56,6 +56,15 @@ pt_status check_spectral_desc(const pt_spectral_desc* sd, std::string* error);
 pt_status check_spectral_args(const void* scene, const pt_render_desc* rd, const pt_spectral_desc* sd, const void* film, const void* spectral, std::string* error);
 // pt_spectral_bin_centres: centres_nm[b] = lo + ((float)b + 0.5f) * ((hi - lo) / (float)bins)
 pt_status spectral_bin_centres(const pt_render_desc* rd, const pt_spectral_desc* sd, float* centres_nm, std::string* error);
+// pt_render_adaptive_spectral's arguments: no null pointer (sample_counts included; stats may be null), check_spectral_desc's conditions, then
+// normalize_adaptive_desc's, each with its own message; *rd_out and *ad_out as normalize_adaptive_desc leaves them.  The scene is only compared with null:
+// camera_count is what the caller read from it.
+pt_status check_adaptive_spectral_args(const void* scene, const pt_render_desc* rd, const pt_adaptive_desc* ad, const pt_spectral_desc* sd, uint32_t camera_count,
+                                       const void* film, const void* sample_counts, const void* spectral, pt_render_desc* rd_out, pt_adaptive_desc* ad_out,
+                                       std::string* error);
+// pt_denoise_spectral's arguments: bins in 1..PT_SPECTRAL_MAX_BINS and the two spectral pointers, then normalize_denoise_desc and check_denoise_inputs
+pt_status check_denoise_spectral_args(const pt_denoise_desc* in, uint32_t bins, const void* film, const uint32_t* sample_counts, const void* stats, const float* guides,
+                                      const void* spectral, const void* out_film, const void* out_spectral, pt_denoise_desc* out, std::string* error);
 
 }  // namespace pth
 #endif

@@ -45,5 +45,9 @@ PT_HD void spectral_fold_pixel(const RenderParams& rp, uint32_t bins, const floa
     }
 }
 
+// The end of an adaptive render (pt_render_adaptive_spectral): a bin's running sum S of a pixel that took n samples becomes S / (float)n — the division
+// spectral_fold_pixel makes at the end of a whole range of n samples.  n = 0 (a pixel no pass touched) leaves the 0 it holds.
+PT_HD float spectral_finish_value(float S, uint32_t n) { return n == 0u ? S : S / (float)n; }
+
 }  // namespace ptd
 #endif

@@ -9,6 +9,8 @@
   python3 tools/denoise_quality.py --chain 8 [--emulation]     specular-chain guides against first-hit guides (key gpu_<size>_chain / emulation_48_chain): the demodulated filter
                                                                on cornell_checker_slab and cornell_gem, and the wall time of the two guide passes there and on cornell_checker
   python3 tools/denoise_quality.py --one-pass 1024 --demodulate --chain 8 [--scene cornell_checker_slab]   one render, both guide passes, both filter calls
+  python3 tools/denoise_quality.py --spectral-bins 8 [--size 32 --spp 20 --ref-spp 4000]   the joint filter of the film and its bins (pt_denoise_spectral, key gpu_<size>_spectral<B>):
+                                                               per scene and spp also the summed squared error of the noisy and of the denoised bins against a converged pt_render_spectral
 
 Quality: Cornell box, the gem scene, mixed_primitives, hdri_small and cornell_checker at size x size, max_bounces 6, seed 1, the defaults of pt_denoise_desc,
 guides of 4 samples.  Against a reference render of another seed (77), RMSE over XYZ of the noisy film, of the denoised film and of the film denoised with
@@ -118,17 +120,31 @@ def measure_chain(lib, pkg, name, size, spps, ref, reps, D):
     return out
 
 
-def measure(lib, pkg, name, size, spp, ref, reps):
+def sse(a, b):
+    return float(np.sum((a.astype(np.float64) - b.astype(np.float64)) ** 2))
+
+
+def measure(lib, pkg, name, size, spp, ref, reps, bins=0, ref_spectral=None):
+    """`bins` > 0: the render is render_adaptive_spectral (the same film, counts and statistics) and the record gains the summed squared error, over every bin
+    and pixel, of its bins and of denoise_spectral's against ref_spectral."""
     builder = getattr(pkg.scene, name)()
     sc = lib.create_scene(builder)
     rd = pkg.api.render_desc(size, size, spp, BOUNCES, seed=1)
-    (film, counts, st, _), t_render = timed(lambda: sc.render_adaptive(rd, spp, 0.0, stats=True), reps)
+    spectral = None
+    if bins:
+        (film, counts, st, spectral, _), t_render = timed(lambda: sc.render_adaptive_spectral(rd, bins, spp, 0.0, stats=True), reps)
+    else:
+        (film, counts, st, _), t_render = timed(lambda: sc.render_adaptive(rd, spp, 0.0, stats=True), reps)
     guides, t_guides = timed(lambda: sc.render_guides(rd, 4), reps)
     den, t_filter = timed(lambda: lib.denoise_film(film, counts, st, guides), reps)
     e0, e1 = rmse(film, ref), rmse(den, ref)
     out = {"spp": spp, "rmse_noisy": e0, "rmse_denoised": e1, "ratio": e1 / e0, "mean_y_noisy": float(film[..., 1].mean()), "mean_y_denoised": float(den[..., 1].mean()),
            "mean_y_shift": float(den[..., 1].mean() / film[..., 1].mean() - 1.0), "render_seconds": t_render, "guides_seconds": t_guides, "filter_seconds": t_filter}
     films = {"noisy": film, "denoised": den}
+    if bins:
+        (_, den_spectral), out["filter_spectral_seconds"] = timed(lambda: lib.denoise_spectral(film, counts, st, guides, spectral), reps)
+        e0, e1 = sse(spectral, ref_spectral), sse(den_spectral, ref_spectral)
+        out.update({"bins": bins, "sse_bins_noisy": e0, "sse_bins_denoised": e1, "sse_bins_ratio": e1 / e0})
     if lib._render_guides_albedo is not None:
         (_, albedo), out["guides_albedo_seconds"] = timed(lambda: sc.render_guides_albedo(rd, 4), reps)
         dem, out["filter_albedo_seconds"] = timed(lambda: lib.denoise_film(film, counts, st, guides, albedo=albedo), reps)
@@ -155,11 +171,14 @@ def main():
     ap.add_argument("--chain", type=int, default=None, metavar="D", help="specular-chain guides of max_chain D against first-hit guides")
     ap.add_argument("--scene", default="cornell_checker_slab", help="--one-pass --chain: the scene")
     ap.add_argument("--rounds", action="store_true", help="--one-pass --chain: also print the rays traced per chain vertex (a numpy walk over the probes)")
+    ap.add_argument("--spectral-bins", type=int, default=0, metavar="B", help="also the bins' summed squared errors through the joint filter (not with --emulation: it renders no spectral film)")
     ap.add_argument("--library", default=None, metavar="PATH", help="another build of libptamd.so")
     ap.add_argument("--key", default=None, help="the record's key in --out (default gpu_<size> / emulation_48)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     pkg = importlib.import_module("rust-pathtracer_amd")
+    if args.spectral_bins and (args.one_pass or args.emulation or args.chain is not None):
+        ap.error("--spectral-bins measures the engine's joint filter in the quality record: not with --one-pass, --emulation or --chain")
     if args.one_pass:
         engine = pkg.load()
         rd = pkg.api.render_desc(args.one_pass, args.one_pass, 20, BOUNCES, seed=1)
@@ -195,6 +214,8 @@ def main():
         key, size, spps, ref_spp, reps = "gpu_%d" % args.size, args.size, [int(s) for s in (args.spp or "20,40,80").split(",")], args.ref_spp, args.reps
     if args.chain is not None:
         key += "_chain"
+    if args.spectral_bins:
+        key += "_spectral%d" % args.spectral_bins
     key = args.key or key
     record = {"command": "python3 tools/denoise_quality.py " + " ".join(sys.argv[1:]), "device": "host emulation (CPU)" if args.emulation else lib.device_info(), "size": size, "reference_spp": ref_spp,
               "reference_seed": 77, "max_bounces": BOUNCES, "guide_samples": 4, "scenes": {}}
@@ -203,8 +224,12 @@ def main():
         record["scenes"][name] = measure_chain(lib, pkg, name, size, spps, ref, 5 if not args.emulation else 1, args.chain)
         print(name, json.dumps(record["scenes"][name], indent=1), flush=True)
     for name in (SCENES if args.chain is None else ()):
-        ref, _ = lib.create_scene(getattr(pkg.scene, name)()).render(pkg.api.render_desc(size, size, ref_spp, BOUNCES, seed=77))
-        record["scenes"][name] = [measure(lib, pkg, name, size, spp, ref, reps) for spp in spps]
+        ref_rd, ref_spectral = pkg.api.render_desc(size, size, ref_spp, BOUNCES, seed=77), None
+        if args.spectral_bins:   # (render_spectral's film is render's)
+            ref, ref_spectral, _ = lib.create_scene(getattr(pkg.scene, name)()).render_spectral(ref_rd, args.spectral_bins)
+        else:
+            ref, _ = lib.create_scene(getattr(pkg.scene, name)()).render(ref_rd)
+        record["scenes"][name] = [measure(lib, pkg, name, size, spp, ref, reps, args.spectral_bins, ref_spectral) for spp in spps]
         print(name, json.dumps(record["scenes"][name], indent=1), flush=True)
     if args.out:
         whole = json.load(open(args.out)) if os.path.exists(args.out) else {}

@@ -18,7 +18,8 @@
  * pt_render_adaptive_spectral is pt_render_adaptive with the same bins: a pixel that took n samples holds the fold of those n samples divided by (float)n,
  * so its bins are pixel p of pt_render_spectral at spp = n, bit for bit.  pt_denoise_spectral filters that film and its bins together: the taps and the
  * edge-stopping weights of every a-trous pass are pt_denoise_film's — they come from the XYZ film, its variance and the guides alone — and each bin plane is
- * averaged with them (csrc/pt_denoise_spectral_rules.h, operation by operation).  The bins have no variance of their own and are not demodulated. */
+ * averaged with them (csrc/pt_denoise_spectral_rules.h, operation by operation).  The bins have no variance of their own.  pt_denoise_spectral does not
+ * demodulate them; pt_denoise_spectral_albedo does, by the per-bin albedo that pt_render_guides_bin_albedo renders (csrc/pt_denoise_spectral_albedo_rules.h). */
 #ifndef PT_SPECTRAL_H
 #define PT_SPECTRAL_H
 #include "pt_adaptive.h"
@@ -54,10 +55,35 @@ pt_status pt_render_adaptive_spectral(pt_scene* scene, const pt_render_desc* des
  *     sb = 0.0f;  sb = sb + w_q * s_b,i(q) over the taps q that pt_denoise_film's pass takes, in its order;  s_b,i+1(p) = sb / sw
  * with w_q and sw the weights and their sum that the colour of p is averaged with.  A tap that is skipped adds nothing.  A pixel is dead — copied through,
  * film and bins, and never read — when pt_denoise_film calls it dead or when one of its bins is not finite.  Where no pixel is dead through its bins alone,
- * out_film_xyzw and out_variance are pt_denoise_film's bit for bit.  There is no albedo form: demodulating the bins needs a per-bin albedo.
+ * out_film_xyzw and out_variance are pt_denoise_film's bit for bit.  This entry has no albedo form: pt_denoise_spectral_albedo, below, is the one that demodulates.
  * Host arrays in, host arrays out; out_film_xyzw may be film_xyzw and out_spectral may be spectral.  out_variance may be NULL. */
 pt_status pt_denoise_spectral(const pt_denoise_desc* desc, uint32_t bins, const float* film_xyzw, const uint32_t* sample_counts, const double* stats,
                               const float* guides_xyzw, const float* spectral, float* out_film_xyzw, float* out_spectral, float* out_variance);
+
+/* The guides of pt_render_guides_albedo — or, with a chain of max_chain > 0, of pt_render_guides_chain — and from the same probes a per-bin albedo: the mean
+ * reflectance of the guide samples' surfaces at the centre wavelength of each of the render's `bins` (1 .. PT_SPECTRAL_MAX_BINS) wavelength bins.  With
+ * lambda_b = pt_spectral_bin_centres' value for bin b, guide sample k of pixel p gives
+ *     rho_b,k = min(texstack_eval(lambda_b, u, v), 1)    at a valid hit of a Lambertian material (the hit pt_render_guides_albedo evaluates its albedo at;
+ *                                                        with a chain, the end of the sample's specular chain, where pt_render_guides_chain takes its albedo)
+ *     rho_b,k = 1                                        at every other hit, and at a miss
+ *     A_b(p)  = (rho_b,0 + ... + rho_b,K-1) / (float)K   the f32 sum in sample order from 0.0f
+ * chain: NULL (or max_chain 0) = the first hit.  guides_xyzw (required) and albedo_xyzw (may be NULL): width*height*4 f32, those entries' outputs bit for bit.
+ * bin_albedo (required): bins*width*height f32 in the spectral film's layout, bin_albedo[b * width * height + y * width + x]. */
+pt_status pt_render_guides_bin_albedo(pt_scene* scene, const pt_render_desc* desc, uint32_t guide_samples, const pt_guide_chain_desc* chain, uint32_t bins,
+                                      float* guides_xyzw, float* albedo_xyzw, float* bin_albedo);
+
+/* pt_denoise_spectral with the film demodulated by albedo_xyzw as pt_denoise_film_albedo does it, and the bins by bin_albedo:
+ *     before the passes   s_b'(p) = s_b(p) / max(A_b(p), 1e-3f)
+ *     the passes          pt_denoise_spectral's, over the demodulated film (its taps and weights are pt_denoise_film_albedo's) and the s_b'
+ *     after the last      a live pixel's bins are multiplied by the same max(A_b(p), 1e-3f)
+ * A pixel is dead — copied through with its input bits, film and bins, and never read — when pt_denoise_film_albedo calls it dead (pt_denoise_film, with
+ * albedo_xyzw NULL), when one of its bins is not finite, or when one is not finite after the division.  albedo_xyzw (may be NULL): width*height*4 f32, every
+ * channel finite and >= 0.  bin_albedo (may be NULL): bins*width*height f32, every value finite and >= 0.  Both NULL, or both all ones: pt_denoise_spectral's
+ * outputs bit for bit.  bin_albedo NULL alone: the bins are filtered as they are, with the demodulated film's weights.  Where no pixel is dead through its bins
+ * alone, out_film_xyzw and out_variance are pt_denoise_film_albedo's bit for bit.  Everything else is as pt_denoise_spectral takes it. */
+pt_status pt_denoise_spectral_albedo(const pt_denoise_desc* desc, uint32_t bins, const float* film_xyzw, const uint32_t* sample_counts, const double* stats,
+                                     const float* guides_xyzw, const float* albedo_xyzw, const float* spectral, const float* bin_albedo, float* out_film_xyzw,
+                                     float* out_spectral, float* out_variance);
 
 /* bin b covers [lo + b*w, lo + (b+1)*w), w = (hi-lo)/bins;
  * centres_nm[b] = lo + ((float)b + 0.5f) * w, from the desc's wavelength bounds (f32).  Host only. */

@@ -270,6 +270,11 @@ class Library:
         self._denoise_spectral = bind("denoise_spectral", C.c_int32, [C.POINTER(DenoiseDesc), u32, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp, fpp],
                                       required=False)
         self._denoise_spectral_last_error = bind("denoise_spectral_last_error", C.c_char_p, [], required=False)   # (the emulation's)
+        self._render_guides_bin_albedo = bind("render_guides_bin_albedo", C.c_int32, [vp, C.POINTER(RenderDesc), u32, C.POINTER(GuideChainDesc), u32, fpp, fpp, fpp],
+                                              required=False)
+        self._denoise_spectral_albedo = bind("denoise_spectral_albedo", C.c_int32, [C.POINTER(DenoiseDesc), u32, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp,
+                                                                                    fpp, fpp, fpp], required=False)
+        self._denoise_spectral_albedo_last_error = bind("denoise_spectral_albedo_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the two entries above)
         self._device_info = bind("device_info", C.c_char_p, [], required=False)
         self._output_film = bind("output_film", C.c_int32, [C.POINTER(OutputDesc), fpp, C.POINTER(C.c_uint8), fpp], required=False)
         self._write_png = bind("write_png", C.c_int32, [C.c_char_p, u32, u32, C.POINTER(C.c_uint8), C.c_int32], required=False)
@@ -371,9 +376,9 @@ class Library:
                          albedo=None):
         """pt_denoise_spectral: denoise_film's filter over the film and, with the same taps and weights, over the bins spectral [B,H,W] of
         Scene.render_adaptive_spectral.  Returns (denoised [H,W,4], denoised_spectral [B,H,W]), with variance=True (denoised, denoised_spectral, variance [H,W]).
-        There is no albedo form: an `albedo` is refused (demodulating the bins needs a per-bin albedo)."""
+        This entry has no albedo form: an `albedo` is refused (demodulating the bins needs a per-bin albedo: denoise_spectral_albedo takes both)."""
         if albedo is not None:
-            raise PtError(PT_ERR_UNSUPPORTED, "denoise_spectral takes no albedo: demodulating the bins needs a per-bin albedo")
+            raise PtError(PT_ERR_UNSUPPORTED, "denoise_spectral takes no albedo: demodulating the bins needs a per-bin albedo (denoise_spectral_albedo takes one)")
         if self._denoise_spectral is None:
             raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sdenoise_spectral entry" % (self.path, self.prefix))
         film = np.ascontiguousarray(film, dtype=np.float32)
@@ -393,6 +398,41 @@ class Library:
                                     _fp(spectral), _fp(out), _fp(out_spectral), _fp(var) if variance else None)
         if st != PT_OK:
             raise PtError(st, self._denoise_spectral_last_error().decode() if self._denoise_spectral_last_error else self.last_error())
+        return (out, out_spectral, var) if variance else (out, out_spectral)
+
+    def denoise_spectral_albedo(self, film, counts, stats, guides, spectral, albedo=None, bin_albedo=None, iterations=0, sigma_luminance=0.0, sigma_depth=0.0,
+                                normal_power_log2=0, device=0, variance=False):
+        """pt_denoise_spectral_albedo: denoise_spectral over the film demodulated by `albedo` [H,W,4] (as denoise_film(albedo=...) does it) and the bins
+        demodulated by `bin_albedo` [B,H,W] (Scene.render_guides_bin_albedo's); either may be None.  Returns what denoise_spectral returns."""
+        if self._denoise_spectral_albedo is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sdenoise_spectral_albedo entry" % (self.path, self.prefix))
+        film = np.ascontiguousarray(film, dtype=np.float32)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        stats = np.ascontiguousarray(stats, dtype=np.float64)
+        guides = np.ascontiguousarray(guides, dtype=np.float32)
+        spectral = np.ascontiguousarray(spectral, dtype=np.float32)
+        h, w = film.shape[:2]
+        if film.shape != (h, w, 4) or counts.shape != (h, w) or stats.shape != (h, w, 2) or guides.shape != (h, w, 4) or spectral.ndim != 3 or spectral.shape[1:] != (h, w):
+            raise ValueError("film [H,W,4], counts [H,W], stats [H,W,2], guides [H,W,4] and spectral [B,H,W] of one film size")
+        bins = spectral.shape[0]
+        if albedo is not None:
+            albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+            if albedo.shape != (h, w, 4):
+                raise ValueError("albedo [H,W,4] of the film's size")
+        if bin_albedo is not None:
+            bin_albedo = np.ascontiguousarray(bin_albedo, dtype=np.float32)
+            if bin_albedo.shape != (bins, h, w):
+                raise ValueError("bin_albedo [B,H,W] of the spectral film's size")
+        d = DenoiseDesc(w, h, iterations, sigma_luminance, sigma_depth, normal_power_log2, device)
+        out = np.zeros((h, w, 4), np.float32)
+        out_spectral = np.zeros((bins, h, w), np.float32)
+        var = np.zeros((h, w), np.float32) if variance else None
+        st = self._denoise_spectral_albedo(C.byref(d), bins, _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)), stats.ctypes.data_as(C.POINTER(C.c_double)), _fp(guides),
+                                           _fp(albedo) if albedo is not None else None, _fp(spectral), _fp(bin_albedo) if bin_albedo is not None else None,
+                                           _fp(out), _fp(out_spectral), _fp(var) if variance else None)
+        if st != PT_OK:
+            err = self._denoise_spectral_albedo_last_error
+            raise PtError(st, err().decode() if err else self.last_error())
         return (out, out_spectral, var) if variance else (out, out_spectral)
 
     def write_png(self, path, rgba8, colorspace=COLORSPACE_SRGB):
@@ -562,6 +602,21 @@ class Scene:
             raise PtError(st, err().decode() if err else self.library.last_error())
         return g, a
 
+    def render_guides_bin_albedo(self, rd, bins, guide_samples=4, max_chain=0, alpha_max=0.0):
+        """pt_render_guides_bin_albedo: (guides [H,W,4], albedo [H,W,4], bin_albedo [bins,H,W]) from one set of probes — render_guides_albedo's outputs, or with
+        max_chain > 0 render_guides_chain's, and the mean reflectance of the same guide samples at the centre wavelength of each of the render's `bins` bins."""
+        if self.library._render_guides_bin_albedo is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_guides_bin_albedo entry" % (self.library.path, self.library.prefix))
+        g = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        a = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        ba = np.zeros((max(int(bins), 0), rd.height, rd.width), dtype=np.float32)
+        cd = GuideChainDesc(max_chain, alpha_max)
+        st = self.library._render_guides_bin_albedo(self.handle, C.byref(rd), guide_samples, C.byref(cd) if max_chain > 0 else None, bins, _fp(g), _fp(a), _fp(ba))
+        if st != PT_OK:
+            err = self.library._denoise_spectral_albedo_last_error
+            raise PtError(st, err().decode() if err else self.library.last_error())
+        return g, a, ba
+
     def render_denoised(self, rd, max_samples=None, rel_error=0.0, abs_error=0.0, step=0, guide_samples=4, iterations=0, sigma_luminance=0.0, sigma_depth=0.0,
                         normal_power_log2=0, device_mask=None, albedo=False, specular_chain=None):
         """An adaptive render with statistics (max_samples None = rd.spp: a fixed count), its guides, and the filter: (film, denoised, counts, profile).
@@ -585,14 +640,19 @@ class Scene:
         return film, den, counts, prof
 
     def render_denoised_spectral(self, rd, bins, max_samples=None, rel_error=0.0, guide_samples=4, specular_chain=0, abs_error=0.0, step=0, iterations=0,
-                                 sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, albedo=False):
+                                 sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, albedo=False, bin_albedo=False):
         """render_adaptive_spectral with statistics (max_samples None = rd.spp: a fixed count), its guides — render_guides, or render_guides_chain with max_chain
         `specular_chain` when that is positive — and denoise_spectral: (film, denoised, spectral, denoised_spectral, counts, profile).  `albedo` is refused, as
-        denoise_spectral refuses it."""
+        denoise_spectral refuses it.  `bin_albedo`: guides, XYZ albedo and per-bin albedo come from one render_guides_bin_albedo call (with `specular_chain` as its
+        max_chain) and the filter is denoise_spectral_albedo: the film demodulated by the XYZ albedo, the bins by the per-bin albedo."""
         if albedo:
-            raise PtError(PT_ERR_UNSUPPORTED, "render_denoised_spectral takes no albedo: demodulating the bins needs a per-bin albedo")
+            raise PtError(PT_ERR_UNSUPPORTED, "render_denoised_spectral takes no albedo: demodulating the bins needs a per-bin albedo (bin_albedo=True renders one)")
         mx = rd.spp if max_samples is None else max_samples
         film, counts, st, spectral, prof = self.render_adaptive_spectral(rd, bins, mx, rel_error, abs_error, step, stats=True)
+        if bin_albedo:
+            guides, alb, balb = self.render_guides_bin_albedo(rd, bins, guide_samples, specular_chain)
+            den, den_spectral = self.library.denoise_spectral_albedo(film, counts, st, guides, spectral, alb, balb, iterations, sigma_luminance, sigma_depth, normal_power_log2)
+            return film, den, spectral, den_spectral, counts, prof
         if specular_chain > 0:
             guides, _ = self.render_guides_chain(rd, guide_samples, specular_chain, albedo=False)
         else:

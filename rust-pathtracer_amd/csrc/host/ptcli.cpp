@@ -4,7 +4,7 @@
 //
 //   ptcli [--config data/config.toml] [--scene FILE] [-n|--dry-run] [--stdout-log-level L] [--write-log-level L]
 //         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K] [--demodulate-albedo]
-//         [--guide-chain D] [--guide-alpha-max A] [--spectral-bins B] [--denoise-spectral-bins B]
+//         [--guide-chain D] [--guide-alpha-max A] [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -26,6 +26,9 @@
 // (pt_denoise_spectral): next to the usual and the _denoised files, which stay byte for byte what --denoise alone writes, it writes <filename>_spectral.exr and
 // <filename>_denoised_spectral.exr, the bins times the factor of the EXR payload beside the R, G, B of the film and of the denoised film.  It is refused with
 // --spectral-bins, with --demodulate-albedo (the bins have no albedo) and with a --devices mask other than device 0 (the node calls have no spectral film).
+// --demodulate-bins (with --denoise-spectral-bins only) takes the guides, the albedo and a per-bin albedo from pt_render_guides_bin_albedo (honouring --guide-chain)
+// and filters through pt_denoise_spectral_albedo: the same file names; <filename>_denoised.* become what --denoise --demodulate-albedo writes, byte for byte,
+// <filename>_spectral.exr is unchanged and <filename>_denoised_spectral.exr holds the bins of the demodulated filter.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -59,6 +62,7 @@ struct Options {
     bool has_alpha_max = false;
     uint32_t spectral_bins = 0;   // --spectral-bins B: <filename>_spectral.exr through pt_render_spectral; 0 = off
     uint32_t denoise_bins = 0;    // --denoise-spectral-bins B: the adaptive spectral render and the joint filter; 0 = off
+    bool demodulate_bins = false; // --demodulate-bins: the joint filter through the per-bin albedo entries
 };
 
 int usage(const char* msg) {
@@ -66,7 +70,7 @@ int usage(const char* msg) {
     fprintf(stderr, "usage: ptcli [--config FILE] [--scene FILE] [-n|--dry-run] [--stdout-log-level LEVEL] [--write-log-level LEVEL]\n"
                     "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n"
                     "             [--denoise] [--guide-samples K] [--demodulate-albedo] [--guide-chain D] [--guide-alpha-max A]\n"
-                    "             [--spectral-bins B] [--denoise-spectral-bins B]\n");
+                    "             [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]\n");
     return 2;
 }
 
@@ -116,6 +120,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--denoise") o.denoise = true;
         else if (a == "--demodulate-albedo") o.demodulate = true;
+        else if (a == "--demodulate-bins") o.demodulate_bins = true;
         else if (a == "--guide-samples") {
             if (!value(&v)) return usage("--guide-samples needs a value");
             char* end = nullptr;
@@ -164,6 +169,7 @@ int main(int argc, char** argv) {
             return usage("--spectral-bins cannot be combined with --devices naming more than one GPU: pt_render_multi has no spectral film");
         if (o.device_mask > 1) return usage("--spectral-bins renders on device 0: --devices may name that device alone");
     }
+    if (o.demodulate_bins && !o.denoise_bins) return usage("--demodulate-bins needs --denoise-spectral-bins");
     if (o.denoise_bins && !o.denoise) return usage("--denoise-spectral-bins needs --denoise");
     if (o.denoise_bins && o.demodulate) return usage("--denoise-spectral-bins cannot be combined with --demodulate-albedo: demodulating the bins needs a per-bin albedo");
     if (o.denoise_bins && o.multi && o.device_mask != 1) return usage("--denoise-spectral-bins renders on device 0: --devices may name that device alone");
@@ -323,15 +329,20 @@ int main(int argc, char** argv) {
                 memset(&dd, 0, sizeof(dd));
                 dd.width = rd.width; dd.height = rd.height;
                 if (o.multi && o.device_mask) while (!((o.device_mask >> dd.device) & 1u)) ++dd.device;   // (the first device of the mask: where the gather left the film)
-                std::vector<float> albedo(o.demodulate ? (size_t)rd.width * rd.height * 4 : 0);
+                std::vector<float> albedo(o.demodulate || o.demodulate_bins ? (size_t)rd.width * rd.height * 4 : 0);
+                std::vector<float> bin_albedo(o.demodulate_bins ? spectral.size() : 0);
                 pt_guide_chain_desc cd;
                 memset(&cd, 0, sizeof(cd));
                 cd.max_chain = o.max_chain; cd.alpha_max = o.alpha_max;
-                const pt_status gst = o.chain ? pt_render_guides_chain(scene, &rd, o.guide_samples, &cd, guides.data(), o.demodulate ? albedo.data() : nullptr)
+                const pt_status gst = o.demodulate_bins ? pt_render_guides_bin_albedo(scene, &rd, o.guide_samples, o.chain ? &cd : nullptr, o.denoise_bins, guides.data(),
+                                                                                      albedo.data(), bin_albedo.data())
+                                      : o.chain ? pt_render_guides_chain(scene, &rd, o.guide_samples, &cd, guides.data(), o.demodulate ? albedo.data() : nullptr)
                                       : o.demodulate ? pt_render_guides_albedo(scene, &rd, o.guide_samples, guides.data(), albedo.data())
                                                      : pt_render_guides(scene, &rd, o.guide_samples, guides.data());
                 std::vector<float> clean_spectral(spectral.size());
                 const pt_status dst = gst != PT_OK ? gst
+                                      : o.demodulate_bins ? pt_denoise_spectral_albedo(&dd, o.denoise_bins, film.data(), counts.data(), stats.data(), guides.data(), albedo.data(),
+                                                                                       spectral.data(), bin_albedo.data(), clean.data(), clean_spectral.data(), nullptr)
                                       : o.denoise_bins ? pt_denoise_spectral(&dd, o.denoise_bins, film.data(), counts.data(), stats.data(), guides.data(), spectral.data(), clean.data(),
                                                                              clean_spectral.data(), nullptr)
                                                        : pt_denoise_film_albedo(&dd, film.data(), counts.data(), stats.data(), guides.data(), o.demodulate ? albedo.data() : nullptr,

@@ -245,12 +245,18 @@ void albedo_basis(float wavelength_lo, float wavelength_hi, DnAlbedoBasis* basis
 }
 
 
-// the filter's kernels for pt_denoise_spectral (pt_denoise_spectral.hip), unchanged
+// the filter's kernels for pt_denoise_spectral and pt_denoise_spectral_albedo (pt_denoise_spectral.hip, pt_denoise_spectral_albedo.hip), unchanged
 void launch_dn_prepare(const DnParams& P, const float* film, const uint32_t* counts, const double* stats, const float* guides, float* color, float* geo, uint8_t* flags,
                        float* grad) {
     hipLaunchKernelGGL(k_dn_prepare, dim3(line_grid((size_t)P.width * P.height)), dim3(kLine), 0, 0, P, reinterpret_cast<const float4*>(film), counts,
                        reinterpret_cast<const double2*>(stats), reinterpret_cast<const float4*>(guides), reinterpret_cast<float4*>(color), reinterpret_cast<float4*>(geo), flags,
                        reinterpret_cast<float2*>(grad));
+}
+void launch_dn_prepare_albedo(const DnParams& P, const float* film, const uint32_t* counts, const double* stats, const float* guides, const float* albedo, float* color,
+                              float* geo, uint8_t* flags, float* grad) {
+    hipLaunchKernelGGL(k_dn_prepare_albedo, dim3(line_grid((size_t)P.width * P.height)), dim3(kLine), 0, 0, P, reinterpret_cast<const float4*>(film), counts,
+                       reinterpret_cast<const double2*>(stats), reinterpret_cast<const float4*>(guides), reinterpret_cast<const float4*>(albedo),
+                       reinterpret_cast<float4*>(color), reinterpret_cast<float4*>(geo), flags, reinterpret_cast<float2*>(grad));
 }
 void launch_dn_tent(const DnParams& P, const float* color, const float* geo, const uint8_t* flags, float* tent) {
     const DnBuffers b{reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(geo), tent, flags, nullptr};
@@ -258,6 +264,10 @@ void launch_dn_tent(const DnParams& P, const float* color, const float* geo, con
 }
 void launch_dn_finish(uint32_t n_pixels, const float* color, float* film, float* variance) {
     hipLaunchKernelGGL(k_dn_finish, dim3(line_grid(n_pixels)), dim3(kLine), 0, 0, n_pixels, reinterpret_cast<const float4*>(color), reinterpret_cast<float4*>(film), variance);
+}
+void launch_dn_finish_albedo(uint32_t n_pixels, const float* color, const float* albedo, const uint8_t* flags, float* film, float* variance) {
+    hipLaunchKernelGGL(k_dn_finish_albedo, dim3(line_grid(n_pixels)), dim3(kLine), 0, 0, n_pixels, reinterpret_cast<const float4*>(color),
+                       reinterpret_cast<const float4*>(albedo), flags, reinterpret_cast<float4*>(film), variance);
 }
 
 }  // namespace ptk

@@ -32,6 +32,10 @@ void launch_guide_finish_albedo(uint32_t n_pixels, const ptd::DnGuideSum* sums, 
 // live pixels) and k_dn_finish (film = color xyz, W = 0; variance = color w).
 void launch_dn_prepare(const ptd::DnParams& P, const float* film, const uint32_t* counts, const double* stats, const float* guides, float* color, float* geo,
                        uint8_t* flags, float* grad);
+// k_dn_prepare_albedo and k_dn_finish_albedo, for pt_denoise_spectral_albedo: the film demodulated by `albedo` (float4 per pixel) and multiplied back
+void launch_dn_prepare_albedo(const ptd::DnParams& P, const float* film, const uint32_t* counts, const double* stats, const float* guides, const float* albedo, float* color,
+                              float* geo, uint8_t* flags, float* grad);
+void launch_dn_finish_albedo(uint32_t n_pixels, const float* color, const float* albedo, const uint8_t* flags, float* film, float* variance);
 void launch_dn_tent(const ptd::DnParams& P, const float* color, const float* geo, const uint8_t* flags, float* tent);
 void launch_dn_finish(uint32_t n_pixels, const float* color, float* film, float* variance);
 

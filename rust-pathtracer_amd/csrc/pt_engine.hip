@@ -34,6 +34,7 @@
 #include "pt_denoise_launch.h"
 #include "pt_error.h"
 #include "pt_guides_chain_launch.h"
+#include "pt_denoise_spectral_albedo_launch.h"
 #include "pt_plan.h"
 #include "pt_scene_host.h"
 
@@ -1394,7 +1395,8 @@ pt_status pt_camera_samples(pt_scene* sc, const pt_render_desc* rdp, size_t n, c
 
 // The albedo guide's tables for a render `rdp` of `sc`: the basis, material_row[m] (the first table row of material m's layers) and the curve values of every
 // Lambertian material's texture layers at the basis wavelengths (one launch of k_albedo_tables).
-static pt_status make_albedo_tables(pt_scene* sc, const pt_render_desc* rdp, DnAlbedoBasis* basis, DevBuf* drow, DevBuf* dloff, DevBuf* dtable) {
+// (rows_out, may be null: the number of table rows, for make_bin_albedo_table)
+static pt_status make_albedo_tables(pt_scene* sc, const pt_render_desc* rdp, DnAlbedoBasis* basis, DevBuf* drow, DevBuf* dloff, DevBuf* dtable, uint32_t* rows_out = nullptr) {
     const uint32_t materials = sc->host.material_count;
     // the table's rows: the layers of every Lambertian material's texture stack, in material order (a stack two materials share gets two sets of rows)
     const std::vector<uint32_t>& blob = sc->host.blob;
@@ -1412,13 +1414,26 @@ static pt_status make_albedo_tables(pt_scene* sc, const pt_render_desc* rdp, DnA
     HIP_TRY(hipMemcpy(drow->p, material_row.data(), 4 * material_row.size(), hipMemcpyHostToDevice));
     if (rows) HIP_TRY(hipMemcpy(dloff->p, layer_off.data(), 4 * (size_t)rows, hipMemcpyHostToDevice));
     launch_albedo_tables(sc->d_blob, sc->d_tex, *basis, rows, dloff->as<uint32_t>(), dtable->as<float>());
+    if (rows_out) *rows_out = rows;
+    return PT_OK;
+}
+// The per-bin albedo guide's table and sums (include/pt_spectral.h pt_render_guides_bin_albedo): the curve values of make_albedo_tables' rows at the centres of
+// the render's `bins` wavelength bins (one launch of k_bin_albedo_tables), and bins x n zeroed running sums.  *fold: what the fold kernels take.
+static pt_status make_bin_albedo_fold(pt_scene* sc, const pt_render_desc* rdp, uint32_t bins, uint32_t n, uint32_t rows, const DevBuf& drow, const DevBuf& dloff, DevBuf* dbtable,
+                                      DevBuf* dbsum, BinAlbedoFold* fold) {
+    HIP_TRY(dbtable->alloc(16 * (size_t)(rows ? rows : 1u) * bins)); HIP_TRY(dbsum->alloc(4 * (size_t)bins * n));
+    HIP_TRY(hipMemsetAsync(dbsum->p, 0, 4 * (size_t)bins * n, 0));
+    launch_bin_albedo_tables(sc->d_blob, sc->d_tex, rdp->wavelength_lo, dn_bin_width(rdp->wavelength_lo, rdp->wavelength_hi, bins), bins, rows, dloff.as<uint32_t>(),
+                             dbtable->as<float>());
+    *fold = BinAlbedoFold{dbsum->as<float>(), reinterpret_cast<const float4*>(dbtable->p), drow.as<uint32_t>(), bins, n};
     return PT_OK;
 }
 // include/pt_denoise.h: the guides of the film denoiser.  Per sample index k the camera rays of every pixel (stage_generate, as pt_camera_samples runs it), the
 // closest hits as pt_intersect finds them (the probe kernel in the scene's own staging mode), and the fold of the hit records in k order (pt_denoise.hip).
 // `albedo` (may be null): include/pt_denoise.h's second guide, from the same hit records — the fold and the division then run in their albedo forms, after one
-// launch that tabulates the curves of the Lambertian materials' texture layers at the basis wavelengths.
-static pt_status render_guides_impl(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, float* guides, float* albedo) {
+// launch that tabulates the curves of the Lambertian materials' texture layers at the basis wavelengths.  `bin_albedo` (may be null; needs albedo): the per-bin
+// albedo over `bins` bins from the same hit records, folded by a second kernel behind the fold.
+static pt_status render_guides_impl(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, float* guides, float* albedo, uint32_t bins = 0, float* bin_albedo = nullptr) {
     HIP_TRY(hipSetDevice(sc->device));
     const uint32_t n = rdp->width * rdp->height;
     RenderParams rp;
@@ -1427,15 +1442,21 @@ static pt_status render_guides_impl(pt_scene* sc, const pt_render_desc* rdp, uin
     rp.wavelength_lo = rdp->wavelength_lo; rp.wavelength_span = rdp->wavelength_hi - rdp->wavelength_lo;
     rp.camera = pth::camera_params(sc->host.cameras[rdp->camera_index], (float)rdp->width / (float)rdp->height);
     rp.chunk_pixels = 1;
-    DevBuf dor, dd, dh, dsum, dg, dasum, da, drow, dloff, dtable;
+    DevBuf dor, dd, dh, dsum, dg, dasum, da, drow, dloff, dtable, dbtable, dbsum;
+    BinAlbedoFold fold{};
     HIP_TRY(dor.alloc(12 * (size_t)n)); HIP_TRY(dd.alloc(12 * (size_t)n)); HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n));
     HIP_TRY(dsum.alloc(sizeof(DnGuideSum) * (size_t)n)); HIP_TRY(dg.alloc(16 * (size_t)n));
     DnAlbedoBasis basis;
     const uint32_t materials = sc->host.material_count;
     if (albedo) {
         HIP_TRY(dasum.alloc(16 * (size_t)n)); HIP_TRY(da.alloc(16 * (size_t)n));
-        const pt_status ast = make_albedo_tables(sc, rdp, &basis, &drow, &dloff, &dtable);
+        uint32_t rows = 0;
+        const pt_status ast = make_albedo_tables(sc, rdp, &basis, &drow, &dloff, &dtable, &rows);
         if (ast != PT_OK) return ast;
+        if (bin_albedo) {
+            const pt_status bst = make_bin_albedo_fold(sc, rdp, bins, n, rows, drow, dloff, &dbtable, &dbsum, &fold);
+            if (bst != PT_OK) return bst;
+        }
     }
     const int grid = sc->num_cus * 4;
     const uint32_t lds_bytes = sc->lds_mode == PT_LDS_ALL ? sc->blob_words * 4u : (sc->lds_mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
@@ -1446,13 +1467,16 @@ static pt_status render_guides_impl(pt_scene* sc, const pt_render_desc* rdp, uin
             launch_guide_fold_albedo(n, dh.as<pt_hit>(), dsum.as<DnGuideSum>(), dasum.as<float>(), k == 0, sc->d_blob, sc->d_tex, materials, drow.as<uint32_t>(), dtable.as<float>(), basis);
         else
             launch_guide_fold(n, dh.as<pt_hit>(), dsum.as<DnGuideSum>(), k == 0);
+        if (fold.sums) launch_guide_fold_bins(n, dh.as<pt_hit>(), fold, sc->d_blob, sc->d_tex, materials);
     }
     if (albedo) launch_guide_finish_albedo(n, dsum.as<DnGuideSum>(), dasum.as<float>(), guide_samples, dg.as<float>(), da.as<float>());
     else launch_guide_finish(n, dsum.as<DnGuideSum>(), guide_samples, dg.as<float>());
+    if (fold.sums) launch_bin_albedo_finish(n, bins, fold.sums, guide_samples, fold.sums);   // (in place: one value per lane)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(guides, dg.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
     if (albedo) HIP_TRY(hipMemcpy(albedo, da.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
+    if (fold.sums) HIP_TRY(hipMemcpy(bin_albedo, fold.sums, 4 * (size_t)bins * n, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 pt_status pt_render_guides(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, float* guides) {
@@ -1473,11 +1497,9 @@ pt_status pt_render_guides_albedo(pt_scene* sc, const pt_render_desc* rdp, uint3
 // order; per chain vertex the probe runs over the rays still on their way and k_chain_step (pt_guides_chain.hip) folds the ones that end into their pixels'
 // sums and compacts the rest into the next list, whose length comes back in one 4-byte read — the probe's launcher takes its ray count by value.  The last
 // possible vertex (v == max_chain) ends every ray, so nothing is read back after it: max_chain 0 runs pt_render_guides_albedo's launches and no read-back.
-pt_status pt_render_guides_chain(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const pt_guide_chain_desc* chain, float* guides, float* albedo) {
-    std::string err;
-    pt_guide_chain_desc cd;
-    const pt_status st = pth::check_guides_chain_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, chain, guides, &cd, &err);
-    if (st != PT_OK) return fail(st, err);
+// `bin_albedo` (may be null; needs albedo): the per-bin albedo over `bins` bins, folded by k_chain_step at the same terminal vertex.
+static pt_status render_guides_chain_impl(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const pt_guide_chain_desc& cd, float* guides, float* albedo,
+                                          uint32_t bins = 0, float* bin_albedo = nullptr) {
     HIP_TRY(hipSetDevice(sc->device));
     const uint32_t n = rdp->width * rdp->height;
     RenderParams rp;
@@ -1486,7 +1508,7 @@ pt_status pt_render_guides_chain(pt_scene* sc, const pt_render_desc* rdp, uint32
     rp.wavelength_lo = rdp->wavelength_lo; rp.wavelength_span = rdp->wavelength_hi - rdp->wavelength_lo;
     rp.camera = pth::camera_params(sc->host.cameras[rdp->camera_index], (float)rdp->width / (float)rdp->height);
     rp.chunk_pixels = 1;
-    DevBuf dor[2], dd[2], dstate[2], dh, dsum, dg, dasum, da, drow, dloff, dtable, dcount;
+    DevBuf dor[2], dd[2], dstate[2], dh, dsum, dg, dasum, da, drow, dloff, dtable, dcount, dbtable, dbsum;
     for (int i = 0; i < 2; ++i) { HIP_TRY(dor[i].alloc(12 * (size_t)n)); HIP_TRY(dd[i].alloc(12 * (size_t)n)); HIP_TRY(dstate[i].alloc(16 * (size_t)n)); }
     HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n)); HIP_TRY(dsum.alloc(sizeof(DnGuideSum) * (size_t)n)); HIP_TRY(dg.alloc(16 * (size_t)n));
     HIP_TRY(dcount.alloc(4 * (size_t)(cd.max_chain + 1u)));
@@ -1496,9 +1518,14 @@ pt_status pt_render_guides_chain(pt_scene* sc, const pt_render_desc* rdp, uint32
     if (albedo) {
         HIP_TRY(dasum.alloc(16 * (size_t)n)); HIP_TRY(da.alloc(16 * (size_t)n));
         HIP_TRY(hipMemsetAsync(dasum.p, 0, 16 * (size_t)n, 0));
-        const pt_status ast = make_albedo_tables(sc, rdp, &ca.basis, &drow, &dloff, &dtable);
+        uint32_t rows = 0;
+        const pt_status ast = make_albedo_tables(sc, rdp, &ca.basis, &drow, &dloff, &dtable, &rows);
         if (ast != PT_OK) return ast;
         ca.albedo_sums = dasum.as<float>(); ca.material_row = drow.as<uint32_t>(); ca.table = dtable.as<float>();
+        if (bin_albedo) {
+            const pt_status bst = make_bin_albedo_fold(sc, rdp, bins, n, rows, drow, dloff, &dbtable, &dbsum, &ca.bin_fold);
+            if (bst != PT_OK) return bst;
+        }
     }
     const int grid = sc->num_cus * 4;
     const uint32_t lds_bytes = sc->lds_mode == PT_LDS_ALL ? sc->blob_words * 4u : (sc->lds_mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
@@ -1519,11 +1546,34 @@ pt_status pt_render_guides_chain(pt_scene* sc, const pt_render_desc* rdp, uint32
     }
     if (albedo) launch_guide_finish_albedo(n, dsum.as<DnGuideSum>(), dasum.as<float>(), guide_samples, dg.as<float>(), da.as<float>());
     else launch_guide_finish(n, dsum.as<DnGuideSum>(), guide_samples, dg.as<float>());
+    if (ca.bin_fold.sums) launch_bin_albedo_finish(n, bins, ca.bin_fold.sums, guide_samples, ca.bin_fold.sums);   // (in place: one value per lane)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(guides, dg.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
     if (albedo) HIP_TRY(hipMemcpy(albedo, da.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
+    if (ca.bin_fold.sums) HIP_TRY(hipMemcpy(bin_albedo, ca.bin_fold.sums, 4 * (size_t)bins * n, hipMemcpyDeviceToHost));
     return PT_OK;
+}
+pt_status pt_render_guides_chain(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const pt_guide_chain_desc* chain, float* guides, float* albedo) {
+    std::string err;
+    pt_guide_chain_desc cd;
+    const pt_status st = pth::check_guides_chain_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, chain, guides, &cd, &err);
+    if (st != PT_OK) return fail(st, err);
+    return render_guides_chain_impl(sc, rdp, guide_samples, cd, guides, albedo);
+}
+// include/pt_spectral.h: the guides, the XYZ albedo and the per-bin albedo from one set of probes — at the first hit (render_guides_impl), or with a chain of
+// max_chain > 0 at the end of every sample's specular chain (render_guides_chain_impl).  The XYZ albedo is always computed (its tables' rows are the per-bin
+// table's); a caller that passes none gets none.
+pt_status pt_render_guides_bin_albedo(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const pt_guide_chain_desc* chain, uint32_t bins, float* guides,
+                                      float* albedo, float* bin_albedo) {
+    std::string err;
+    pt_guide_chain_desc cd;
+    const pt_status st = pth::check_guides_bin_albedo_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, chain, bins, guides, bin_albedo, &cd, &err);
+    if (st != PT_OK) return fail(st, err);
+    std::vector<float> own_albedo;
+    if (!albedo) { own_albedo.resize(4 * (size_t)rdp->width * rdp->height); albedo = own_albedo.data(); }
+    if (cd.max_chain == 0) return render_guides_impl(sc, rdp, guide_samples, guides, albedo, bins, bin_albedo);
+    return render_guides_chain_impl(sc, rdp, guide_samples, cd, guides, albedo, bins, bin_albedo);
 }
 
 pt_status pt_bsdf_sample(pt_scene* sc, uint32_t material, size_t n, const float* lambda, const float* wi, const float* s2, float* f, float* wo, float* pdf) {

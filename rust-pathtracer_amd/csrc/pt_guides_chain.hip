@@ -34,13 +34,13 @@ struct TableStack {
     __device__ DnLayerCurves curves(uint32_t i, int j) const { const float4 c = table[(row + i) * DN_ALBEDO_WAVELENGTHS + (uint32_t)j]; return DnLayerCurves{c.x, c.y, c.z, c.w}; }
 };
 
-// (ALBEDO false: no albedo sum is kept and the table is never read)
-template <bool ALBEDO>
+// (ALBEDO false: no albedo sum is kept and the table is never read; BINS: the per-bin albedo's sums are folded too, pt_bin_albedo_device.h)
+template <bool ALBEDO, bool BINS>
 __global__ void __launch_bounds__(kLine) k_chain_step(uint32_t n, const pt_hit* __restrict__ hits, const float* __restrict__ d_in, const uint4* __restrict__ state_in,
                                                      float* __restrict__ o_out, float* __restrict__ d_out, uint4* __restrict__ state_out, uint32_t* __restrict__ count_out,
                                                      DnGuideSum* __restrict__ sums, float4* __restrict__ asums, uint32_t vertex, uint32_t max_chain, float alpha_max,
                                                      const uint32_t* __restrict__ blob, const float* __restrict__ tex, uint32_t material_count,
-                                                     const uint32_t* __restrict__ material_row, const float4* __restrict__ table, DnAlbedoBasis B) {
+                                                     const uint32_t* __restrict__ material_row, const float4* __restrict__ table, DnAlbedoBasis B, ptk::BinAlbedoFold bin_fold) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool follows = false;
     DnChainNext next;
@@ -73,6 +73,7 @@ __global__ void __launch_bounds__(kLine) k_chain_step(uint32_t n, const pt_hit* 
                 dn_albedo_add(&as, a);
                 asums[p] = make_float4(as.x, as.y, as.z, 0.0f);
             }
+            if (BINS) ptk::bin_albedo_fold_hit(bin_fold, p, h, blob, tex, material_count);   // (p < bin_fold.plane: a ray's pixel is one of the film's)
         }
     }
     // the next vertex' list: the wave's rays that go on take consecutive places from the one its first lane reserves
@@ -100,13 +101,17 @@ void launch_chain_rays(const RenderParams& rp, uint32_t n_pixels, uint32_t sampl
 void launch_chain_step(uint32_t n, const pt_hit* hits, const ChainRays& in, const ChainRays& out, uint32_t* count_out, DnGuideSum* sums, const ChainAlbedo& albedo,
                        uint32_t vertex, uint32_t max_chain, float alpha_max, const uint32_t* blob, const float* tex, uint32_t material_count) {
     if (n == 0) return;
-    if (albedo.albedo_sums)
-        hipLaunchKernelGGL(k_chain_step<true>, dim3(line_grid(n)), dim3(kLine), 0, 0, n, hits, in.d, in.state, out.o, out.d, out.state, count_out, sums,
+    if (albedo.albedo_sums && albedo.bin_fold.sums)
+        hipLaunchKernelGGL((k_chain_step<true, true>), dim3(line_grid(n)), dim3(kLine), 0, 0, n, hits, in.d, in.state, out.o, out.d, out.state, count_out, sums,
                            reinterpret_cast<float4*>(albedo.albedo_sums), vertex, max_chain, alpha_max, blob, tex, material_count, albedo.material_row,
-                           reinterpret_cast<const float4*>(albedo.table), albedo.basis);
+                           reinterpret_cast<const float4*>(albedo.table), albedo.basis, albedo.bin_fold);
+    else if (albedo.albedo_sums)
+        hipLaunchKernelGGL((k_chain_step<true, false>), dim3(line_grid(n)), dim3(kLine), 0, 0, n, hits, in.d, in.state, out.o, out.d, out.state, count_out, sums,
+                           reinterpret_cast<float4*>(albedo.albedo_sums), vertex, max_chain, alpha_max, blob, tex, material_count, albedo.material_row,
+                           reinterpret_cast<const float4*>(albedo.table), albedo.basis, albedo.bin_fold);
     else
-        hipLaunchKernelGGL(k_chain_step<false>, dim3(line_grid(n)), dim3(kLine), 0, 0, n, hits, in.d, in.state, out.o, out.d, out.state, count_out, sums,
-                           (float4*)nullptr, vertex, max_chain, alpha_max, blob, tex, material_count, (const uint32_t*)nullptr, (const float4*)nullptr, albedo.basis);
+        hipLaunchKernelGGL((k_chain_step<false, false>), dim3(line_grid(n)), dim3(kLine), 0, 0, n, hits, in.d, in.state, out.o, out.d, out.state, count_out, sums,
+                           (float4*)nullptr, vertex, max_chain, alpha_max, blob, tex, material_count, (const uint32_t*)nullptr, (const float4*)nullptr, albedo.basis, albedo.bin_fold);
 }
 
 }  // namespace ptk

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pt_api.h"
+#include "pt_bin_albedo_device.h"
 #include "pt_denoise_rules.h"
 #include "pt_stages.h"
 
@@ -14,7 +15,8 @@ namespace ptk {
 // length so far (one uint4 per ray: pixel, wavelength bits, length bits, 0).
 struct ChainRays { float* o; float* d; uint4* state; };
 // the albedo inputs of launch_guide_fold_albedo (pt_denoise_launch.h); albedo_sums null: the guides alone
-struct ChainAlbedo { float* albedo_sums; const uint32_t* material_row; const float* table; ptd::DnAlbedoBasis basis; };
+// bin_fold (sums null: none; needs albedo_sums): the per-bin albedo's sums, folded at the same terminal vertex (pt_render_guides_bin_albedo)
+struct ChainAlbedo { float* albedo_sums; const uint32_t* material_row; const float* table; ptd::DnAlbedoBasis basis; BinAlbedoFold bin_fold; };
 
 // camera sample `sample` of every pixel 0 .. n_pixels-1 (launch_guide_rays' rays) as the chain's vertex-0 list: ray i is pixel i's, length 0
 void launch_chain_rays(const ptd::RenderParams& rp, uint32_t n_pixels, uint32_t sample, const ChainRays& out);

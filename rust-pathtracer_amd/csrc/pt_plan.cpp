@@ -256,4 +256,28 @@ pt_status check_denoise_spectral_args(const pt_denoise_desc* in, uint32_t bins, 
     return check_denoise_inputs(*out, sample_counts, guides, error);
 }
 
+pt_status check_guides_bin_albedo_args(const void* scene, const pt_render_desc* rd, uint32_t camera_count, uint32_t guide_samples, const pt_guide_chain_desc* chain,
+                                       uint32_t bins, const void* guides, const void* bin_albedo, pt_guide_chain_desc* chain_out, std::string* error) {
+    if (bins == 0) { *error = "bins must be positive"; return PT_ERR_INVALID_ARGUMENT; }
+    if (bins > PT_SPECTRAL_MAX_BINS) { *error = "bins: at most 64"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!bin_albedo) { *error = "bin_albedo is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (chain) return check_guides_chain_args(scene, rd, camera_count, guide_samples, chain, guides, chain_out, error);
+    chain_out->max_chain = 0; chain_out->alpha_max = DN_CHAIN_DEFAULT_ALPHA_MAX; chain_out->reserved[0] = 0; chain_out->reserved[1] = 0;
+    return check_guides_args(scene, rd, camera_count, guide_samples, guides, error);
+}
+
+pt_status check_denoise_spectral_albedo_args(const pt_denoise_desc* in, uint32_t bins, const void* film, const uint32_t* sample_counts, const void* stats,
+                                             const float* guides, const float* albedo, const void* spectral, const float* bin_albedo, const void* out_film,
+                                             const void* out_spectral, pt_denoise_desc* out, std::string* error) {
+    pt_status st = check_denoise_spectral_args(in, bins, film, sample_counts, stats, guides, spectral, out_film, out_spectral, out, error);
+    if (st == PT_OK && albedo) st = check_denoise_albedo(*out, albedo, error);
+    if (st != PT_OK) return st;
+    if (bin_albedo) {
+        const size_t n = (size_t)bins * out->width * out->height;
+        for (size_t i = 0; i < n; ++i)
+            if (!pt_isfinite(bin_albedo[i]) || !(bin_albedo[i] >= 0.0f)) { *error = "a bin_albedo value is not finite or is negative"; return PT_ERR_INVALID_ARGUMENT; }
+    }
+    return PT_OK;
+}
+
 }  // namespace pth

@@ -65,6 +65,15 @@ pt_status check_adaptive_spectral_args(const void* scene, const pt_render_desc* 
 // pt_denoise_spectral's arguments: bins in 1..PT_SPECTRAL_MAX_BINS and the two spectral pointers, then normalize_denoise_desc and check_denoise_inputs
 pt_status check_denoise_spectral_args(const pt_denoise_desc* in, uint32_t bins, const void* film, const uint32_t* sample_counts, const void* stats, const float* guides,
                                       const void* spectral, const void* out_film, const void* out_spectral, pt_denoise_desc* out, std::string* error);
+// pt_render_guides_bin_albedo's arguments: bins in 1..PT_SPECTRAL_MAX_BINS and the bin_albedo pointer, then check_guides_chain_args (chain null: the first
+// hit, check_guides_args alone; *chain_out then has max_chain 0)
+pt_status check_guides_bin_albedo_args(const void* scene, const pt_render_desc* rd, uint32_t camera_count, uint32_t guide_samples, const pt_guide_chain_desc* chain,
+                                       uint32_t bins, const void* guides, const void* bin_albedo, pt_guide_chain_desc* chain_out, std::string* error);
+// pt_denoise_spectral_albedo's arguments: check_denoise_spectral_args, then check_denoise_albedo on albedo (if given) and every bin_albedo value (if given)
+// finite and >= 0
+pt_status check_denoise_spectral_albedo_args(const pt_denoise_desc* in, uint32_t bins, const void* film, const uint32_t* sample_counts, const void* stats,
+                                             const float* guides, const float* albedo, const void* spectral, const float* bin_albedo, const void* out_film,
+                                             const void* out_spectral, pt_denoise_desc* out, std::string* error);
 
 }  // namespace pth
 #endif

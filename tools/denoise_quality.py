@@ -11,6 +11,10 @@
   python3 tools/denoise_quality.py --one-pass 1024 --demodulate --chain 8 [--scene cornell_checker_slab]   one render, both guide passes, both filter calls
   python3 tools/denoise_quality.py --spectral-bins 8 [--size 32 --spp 20 --ref-spp 4000]   the joint filter of the film and its bins (pt_denoise_spectral, key gpu_<size>_spectral<B>):
                                                                per scene and spp also the summed squared error of the noisy and of the denoised bins against a converged pt_render_spectral
+  python3 tools/denoise_quality.py --spectral-bins 8 --bin-albedo [--size 32 --spp 20 --ref-spp 4000]   the bins through pt_denoise_spectral and through
+                                                               pt_denoise_spectral_albedo with pt_render_guides_bin_albedo's per-bin albedo (key gpu_<size>_spectral<B>_bin_albedo):
+                                                               on cornell_checker(rgba=True), cornell_checker and cornell_box the summed squared error of the noisy, the filtered and
+                                                               the demodulated-filter bins, over the whole film and over the pixels whose sample-0 ray hits the checker
 
 Quality: Cornell box, the gem scene, mixed_primitives, hdri_small and cornell_checker at size x size, max_bounces 6, seed 1, the defaults of pt_denoise_desc,
 guides of 4 samples.  Against a reference render of another seed (77), RMSE over XYZ of the noisy film, of the denoised film and of the film denoised with
@@ -159,6 +163,30 @@ def measure(lib, pkg, name, size, spp, ref, reps, bins=0, ref_spectral=None):
     return out
 
 
+def measure_bin_albedo(lib, pkg, name, size, spp, ref_spp, reps, bins):
+    """The bins of one noisy render_adaptive_spectral through denoise_spectral and through denoise_spectral_albedo (guides, XYZ albedo and per-bin albedo of 4
+    samples from one render_guides_bin_albedo call), against render_spectral at ref_spp of seed 77."""
+    builder = pkg.scene.cornell_checker(rgba=True) if name == "cornell_checker_rgba" else getattr(pkg.scene, name)()
+    sc = lib.create_scene(builder)
+    rd = pkg.api.render_desc(size, size, spp, BOUNCES, seed=1)
+    _, ref, _ = sc.render_spectral(pkg.api.render_desc(size, size, ref_spp, BOUNCES, seed=77), bins)
+    film, counts, st, spectral, _ = sc.render_adaptive_spectral(rd, bins, spp, 0.0, stats=True)
+    (guides, albedo, bin_albedo), t_guides = timed(lambda: sc.render_guides_bin_albedo(rd, bins, 4), reps)
+    _, t_guides_albedo = timed(lambda: sc.render_guides_albedo(rd, 4), reps)
+    (_, plain), t_plain = timed(lambda: lib.denoise_spectral(film, counts, st, guides, spectral), reps)
+    (_, demod), t_demod = timed(lambda: lib.denoise_spectral_albedo(film, counts, st, guides, spectral, albedo, bin_albedo), reps)
+    out = {"spp": spp, "bins": bins, "sse_bins_noisy": sse(spectral, ref), "sse_bins_denoised": sse(plain, ref), "sse_bins_demodulated": sse(demod, ref),
+           "guides_bin_albedo_seconds": t_guides, "guides_albedo_seconds": t_guides_albedo, "filter_spectral_seconds": t_plain, "filter_spectral_albedo_seconds": t_demod}
+    out["sse_bins_demodulated_to_denoised"] = out["sse_bins_demodulated"] / out["sse_bins_denoised"]
+    if name.startswith("cornell_checker"):
+        mask = checker_mask(sc, builder, rd)
+        out["checker_pixels"] = int(mask.sum())
+        for k, f in (("noisy", spectral), ("denoised", plain), ("demodulated", demod)):
+            out["checker_sse_bins_" + k] = sse(f[:, mask], ref[:, mask])
+        out["checker_sse_bins_demodulated_to_denoised"] = out["checker_sse_bins_demodulated"] / out["checker_sse_bins_denoised"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=256)
@@ -172,6 +200,7 @@ def main():
     ap.add_argument("--scene", default="cornell_checker_slab", help="--one-pass --chain: the scene")
     ap.add_argument("--rounds", action="store_true", help="--one-pass --chain: also print the rays traced per chain vertex (a numpy walk over the probes)")
     ap.add_argument("--spectral-bins", type=int, default=0, metavar="B", help="also the bins' summed squared errors through the joint filter (not with --emulation: it renders no spectral film)")
+    ap.add_argument("--bin-albedo", action="store_true", help="--spectral-bins: the bins with and without demodulation by the per-bin albedo (its own key and scenes)")
     ap.add_argument("--library", default=None, metavar="PATH", help="another build of libptamd.so")
     ap.add_argument("--key", default=None, help="the record's key in --out (default gpu_<size> / emulation_48)")
     ap.add_argument("--out", default=None)
@@ -179,6 +208,8 @@ def main():
     pkg = importlib.import_module("rust-pathtracer_amd")
     if args.spectral_bins and (args.one_pass or args.emulation or args.chain is not None):
         ap.error("--spectral-bins measures the engine's joint filter in the quality record: not with --one-pass, --emulation or --chain")
+    if args.bin_albedo and not args.spectral_bins:
+        ap.error("--bin-albedo needs --spectral-bins")
     if args.one_pass:
         engine = pkg.load()
         rd = pkg.api.render_desc(args.one_pass, args.one_pass, 20, BOUNCES, seed=1)
@@ -216,6 +247,8 @@ def main():
         key += "_chain"
     if args.spectral_bins:
         key += "_spectral%d" % args.spectral_bins
+    if args.bin_albedo:
+        key += "_bin_albedo"
     key = args.key or key
     record = {"command": "python3 tools/denoise_quality.py " + " ".join(sys.argv[1:]), "device": "host emulation (CPU)" if args.emulation else lib.device_info(), "size": size, "reference_spp": ref_spp,
               "reference_seed": 77, "max_bounces": BOUNCES, "guide_samples": 4, "scenes": {}}
@@ -223,7 +256,10 @@ def main():
         ref, _ = lib.create_scene(getattr(pkg.scene, name)()).render(pkg.api.render_desc(size, size, ref_spp, BOUNCES, seed=77))
         record["scenes"][name] = measure_chain(lib, pkg, name, size, spps, ref, 5 if not args.emulation else 1, args.chain)
         print(name, json.dumps(record["scenes"][name], indent=1), flush=True)
-    for name in (SCENES if args.chain is None else ()):
+    for name in (("cornell_checker_rgba", "cornell_checker", "cornell_box") if args.bin_albedo else ()):
+        record["scenes"][name] = [measure_bin_albedo(lib, pkg, name, size, spp, ref_spp, reps, args.spectral_bins) for spp in spps]
+        print(name, json.dumps(record["scenes"][name], indent=1), flush=True)
+    for name in (SCENES if args.chain is None and not args.bin_albedo else ()):
         ref_rd, ref_spectral = pkg.api.render_desc(size, size, ref_spp, BOUNCES, seed=77), None
         if args.spectral_bins:   # (render_spectral's film is render's)
             ref, ref_spectral, _ = lib.create_scene(getattr(pkg.scene, name)()).render_spectral(ref_rd, args.spectral_bins)

@@ -5,6 +5,8 @@ pt_denoise_spectral, and — for the yardstick, from the same film — pt_denois
 seconds of the calls (host arrays in and out: transfers and allocations included) and the bytes a pass of the gather moves.  Run it under
 `rocprofv3 --kernel-trace --stats -- python3 tools/denoise_spectral_frames.py` for the per-kernel times of profiles/denoise_spectral_kernel_stats.csv:
 k_dn_gather_spectral next to k_dn_gather, k_adaptive_finish_spectral, and k_accumulate_spectral under adaptive rounds, all of one build.
+With `--bin-albedo` the frame also goes through pt_render_guides_bin_albedo (next to pt_render_guides_albedo, the yardstick of its fold) and
+pt_denoise_spectral_albedo: the run behind profiles/denoise_spectral_albedo_kernel_stats.csv (k_guide_fold_bins, k_dn_demodulate_bins, k_dn_remodulate_bins).
 """
 import argparse
 import importlib
@@ -26,6 +28,7 @@ def main():
     ap.add_argument("--step", type=int, default=40)
     ap.add_argument("--rel-error", type=float, default=0.05)
     ap.add_argument("--steps", type=int, default=3, help="timed repetitions of the two filter calls")
+    ap.add_argument("--bin-albedo", action="store_true", help="also the per-bin albedo guide and the filter that demodulates the bins by it")
     args = ap.parse_args()
     pkg = importlib.import_module("rust-pathtracer_amd")
     lib = pkg.load()
@@ -47,11 +50,19 @@ def main():
         return sorted(secs)[len(secs) // 2]
     t_joint = timed(lambda: lib.denoise_spectral(film, counts, st, guides, spectral))
     t_film = timed(lambda: lib.denoise_film(film, counts, st, guides))
+    extra = {}
+    if args.bin_albedo:
+        t_guides_albedo = timed(lambda: sc.render_guides_albedo(rd, 4))
+        t_guides_bins = timed(lambda: sc.render_guides_bin_albedo(rd, args.bins, 4))
+        _, albedo, bin_albedo = sc.render_guides_bin_albedo(rd, args.bins, 4)
+        t_demod = timed(lambda: lib.denoise_spectral_albedo(film, counts, st, guides, spectral, albedo, bin_albedo))
+        extra = {"guides_albedo_seconds": t_guides_albedo, "guides_bin_albedo_seconds": t_guides_bins, "denoise_spectral_albedo_seconds": t_demod,
+                 "demodulate_bytes": 3 * args.bins * 4 * args.size * args.size}
     n = args.size * args.size
     print(json.dumps({"bins": args.bins, "size": args.size, "spp": args.spp, "max_samples": args.max_samples, "step": args.step, "rel_error": args.rel_error,
                       "rounds": int(prof.kernel_launches[5]), "mean_samples": float(counts.mean()), "render_seconds": t_render,
                       "denoise_spectral_seconds": t_joint, "denoise_film_seconds": t_film,
-                      "plane_bytes_per_pass": 2 * args.bins * 4 * n, "device": lib.device_info()}))
+                      "plane_bytes_per_pass": 2 * args.bins * 4 * n, "device": lib.device_info(), **extra}))
 
 
 if __name__ == "__main__":

@@ -85,6 +85,11 @@ int64_t pt_scene_file_material(const pt_scene_file* scene, const char* name);
 int32_t pt_scene_file_curve(const pt_scene_file* scene, const char* name);
 int32_t pt_scene_file_texture(const pt_scene_file* scene, const char* name);
 int32_t pt_scene_file_camera(const pt_scene_file* scene, const char* camera_id);
+/* Any curve of the curves library the scene was loaded with, by name.  The loader resolves curves lazily, so a curve that no material, medium or environment
+ * names — a camera's sensitivity, a colour filter — is not in the scene; this entry resolves it from the library, which the scene file keeps alive.  *curve is
+ * the pt_curve with data_offset 0 into *data (*data_floats floats, owned by the scene file and valid until pt_scene_file_free).  The pt_scene_desc does not
+ * change: the resolved curves live beside the scene's.  An unknown name is PT_ERR_INVALID_ARGUMENT, and the message names the curve. */
+pt_status pt_scene_file_library_curve(pt_scene_file* scene, const char* name, pt_curve* curve, const float** data, uint32_t* data_floats);
 uint32_t pt_scene_file_warning_count(const pt_scene_file* scene);
 const char* pt_scene_file_warning(const pt_scene_file* scene, uint32_t index);
 

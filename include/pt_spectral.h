@@ -19,7 +19,10 @@
  * so its bins are pixel p of pt_render_spectral at spp = n, bit for bit.  pt_denoise_spectral filters that film and its bins together: the taps and the
  * edge-stopping weights of every a-trous pass are pt_denoise_film's — they come from the XYZ film, its variance and the guides alone — and each bin plane is
  * averaged with them (csrc/pt_denoise_spectral_rules.h, operation by operation).  The bins have no variance of their own.  pt_denoise_spectral does not
- * demodulate them; pt_denoise_spectral_albedo does, by the per-bin albedo that pt_render_guides_bin_albedo renders (csrc/pt_denoise_spectral_albedo_rules.h). */
+ * demodulate them; pt_denoise_spectral_albedo does, by the per-bin albedo that pt_render_guides_bin_albedo renders (csrc/pt_denoise_spectral_albedo_rules.h).
+ *
+ * pt_spectral_project develops a spectral film: K weighted sums over the bins of every pixel, the weights a matrix that pt_spectral_response_matrix integrates
+ * from response curves (csrc/pt_spectral_project_rules.h); pt_spectral_project_resident develops the bins a scene's last spectral render left on the device. */
 #ifndef PT_SPECTRAL_H
 #define PT_SPECTRAL_H
 #include "pt_adaptive.h"
@@ -97,6 +100,44 @@ pt_status pt_spectral_bin_centres(const pt_render_desc* desc, const pt_spectral_
 pt_status pt_write_exr_spectral(const char* path, uint32_t width, uint32_t height, uint32_t bins,
                                 const float* centres_nm, const float* spectral,
                                 const float* linear_rgb, int32_t colorspace);
+
+/* ---- developing a spectral film: K weighted sums over the bins (csrc/pt_spectral_project_rules.h) ---------------------------------
+ *
+ * A development projects the bins of every pixel onto K response curves — an observer, a camera's sensitivities, a narrow band, each optionally behind a
+ * colour filter.  With M a row-major matrix [K][bins]:
+ *     out[k * width * height + p] = fold over b = 0 .. bins-1 ascending of acc = acc + M[k][b] * S_b(p), from acc = 0.0f   (f32, multiply and add separate)
+ * Nothing is special-cased: a non-finite bin makes that pixel's outputs non-finite, and a zero weight does not protect against a NaN bin. */
+#define PT_SPECTRAL_MAX_RESPONSES 16
+#define PT_SPECTRAL_MAX_SUBSAMPLES 16
+#define PT_RESPONSE_CIE_X (-1)   /* a response that is no curve: the x, y, z component of the engine's colour-matching fit, xyz_bar(lambda * 10.0f) */
+#define PT_RESPONSE_CIE_Y (-2)
+#define PT_RESPONSE_CIE_Z (-3)
+#define PT_SPECTRAL_NO_FILTER (-1)
+
+/* The matrix of K responses over the `spectral_desc->bins` bins of a render `desc` (its wavelength bounds lo, hi; w = (hi - lo) / (float)bins).  Bin b is sampled
+ * at lambda_{b,j} = lo + ((float)b + ((float)j + 0.5f) / (float)subsamples) * w, j = 0 .. subsamples-1 (1 .. PT_SPECTRAL_MAX_SUBSAMPLES; with 1 the bin centre of
+ * pt_spectral_bin_centres bit for bit), and
+ *     matrix[k * bins + b] = (m = 0.0f;  m = m + r_k(lambda_{b,j}) * f(lambda_{b,j}) for j ascending) / (float)subsamples
+ * responses[k] (K of them, 1 .. PT_SPECTRAL_MAX_RESPONSES) is an index into `curves` or one of PT_RESPONSE_CIE_X / _Y / _Z; `filter` is an index into `curves` or
+ * PT_SPECTRAL_NO_FILTER, and then the term is r_k alone.  curves / curve_data are in pt_scene_desc's representation (curve_data_floats floats; both may be NULL
+ * with curve_count 0); a curve's value has the bits of pt_curve_eval for a scene that holds it.  Nothing is divided by the bin width: S_b is the energy that fell
+ * into the bin, so the Y row times the bins estimates what the film's Y sums.  Host only: no scene, no device. */
+pt_status pt_spectral_response_matrix(const pt_render_desc* desc, const pt_spectral_desc* spectral_desc, const pt_curve* curves, uint32_t curve_count,
+                                      const float* curve_data, uint32_t curve_data_floats, uint32_t K, const int32_t* responses, int32_t filter,
+                                      uint32_t subsamples, float* matrix);
+
+/* The projection above of host planes.  spectral: bins * width * height f32 in pt_render_spectral's layout; matrix: K * bins f32, every entry finite;
+ * out: K * width * height f32, plane-major like the bins.  Runs on device 0. */
+pt_status pt_spectral_project(uint32_t width, uint32_t height, uint32_t bins, uint32_t K, const float* matrix, const float* spectral, float* out);
+
+/* The same projection of the bins that the scene's last successful pt_render_spectral / pt_render_adaptive_spectral left in its device buffer: bit for bit
+ * pt_spectral_project of the array that render returned, without the bins crossing the bus — the matrix goes up and K planes come back.  matrix: K * bins f32
+ * for that render's bins; out: K * width * height f32 for its size (pt_spectral_resident tells all three).  A scene that has not rendered a spectral film, or
+ * whose last spectral render failed, has no resident film and the call fails. */
+pt_status pt_spectral_project_resident(pt_scene* scene, uint32_t K, const float* matrix, float* out);
+
+/* Width, height and bins of the scene's resident spectral film; zeros when it has none. */
+pt_status pt_spectral_resident(pt_scene* scene, uint32_t* width, uint32_t* height, uint32_t* bins);
 
 #ifdef __cplusplus
 }

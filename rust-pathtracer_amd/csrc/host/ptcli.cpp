@@ -5,6 +5,7 @@
 //   ptcli [--config data/config.toml] [--scene FILE] [-n|--dry-run] [--stdout-log-level L] [--write-log-level L]
 //         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K] [--demodulate-albedo]
 //         [--guide-chain D] [--guide-alpha-max A] [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]
+//         [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -29,6 +30,13 @@
 // --demodulate-bins (with --denoise-spectral-bins only) takes the guides, the albedo and a per-bin albedo from pt_render_guides_bin_albedo (honouring --guide-chain)
 // and filters through pt_denoise_spectral_albedo: the same file names; <filename>_denoised.* become what --denoise --demodulate-albedo writes, byte for byte,
 // <filename>_spectral.exr is unchanged and <filename>_denoised_spectral.exr holds the bins of the demodulated filter.
+// --develop cie | CX,CY,CZ (with --spectral-bins or --denoise-spectral-bins only) develops the spectral film into a picture: the bins projected onto three response
+// curves (pt_spectral_response_matrix, pt_spectral_project*), packed as an XYZW film with W = 0 and sent through the setting's own film output to
+// <filename>_developed.exr / .png.  `cie` is the engine's colour-matching fit; CX,CY,CZ are three names of the scene file's curves library (a camera's sensitivities,
+// say: they need not be used by the scene).  --develop-filter CURVE multiplies every response by a curve of that library, --develop-subsamples N (1..16, default 1)
+// integrates the responses over each bin with N samples.  With --spectral-bins the bins are developed where the render left them on the device
+// (pt_spectral_project_resident); with --denoise-spectral-bins the undenoised bins go through pt_spectral_project, and the denoised ones too, to
+// <filename>_denoised_developed.*.  Every other file stays byte for byte what it is.  An unknown curve name ends the program once the scene file is loaded.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -63,6 +71,11 @@ struct Options {
     uint32_t spectral_bins = 0;   // --spectral-bins B: <filename>_spectral.exr through pt_render_spectral; 0 = off
     uint32_t denoise_bins = 0;    // --denoise-spectral-bins B: the adaptive spectral render and the joint filter; 0 = off
     bool demodulate_bins = false; // --demodulate-bins: the joint filter through the per-bin albedo entries
+    bool develop = false;         // --develop: <filename>_developed.* from the bins
+    std::vector<std::string> develop_curves;   // three names of the curves library; empty = the colour-matching fit
+    bool has_develop_filter = false, has_develop_subsamples = false;
+    std::string develop_filter;
+    uint32_t develop_subsamples = 1;
 };
 
 int usage(const char* msg) {
@@ -70,7 +83,8 @@ int usage(const char* msg) {
     fprintf(stderr, "usage: ptcli [--config FILE] [--scene FILE] [-n|--dry-run] [--stdout-log-level LEVEL] [--write-log-level LEVEL]\n"
                     "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n"
                     "             [--denoise] [--guide-samples K] [--demodulate-albedo] [--guide-chain D] [--guide-alpha-max A]\n"
-                    "             [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]\n");
+                    "             [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]\n"
+                    "             [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N]\n");
     return 2;
 }
 
@@ -155,6 +169,34 @@ int main(int argc, char** argv) {
             if (end == v.c_str() || *end || b == 0 || b > PT_SPECTRAL_MAX_BINS) return usage("--denoise-spectral-bins needs a count in 1..64");
             o.denoise_bins = (uint32_t)b;
         }
+        else if (a == "--develop") {
+            if (!value(&v)) return usage("--develop needs a value");
+            o.develop_curves.clear();
+            if (v != "cie") {
+                size_t p = 0;
+                while (true) {
+                    const size_t c = v.find(',', p);
+                    o.develop_curves.push_back(v.substr(p, c == std::string::npos ? std::string::npos : c - p));
+                    if (c == std::string::npos) break;
+                    p = c + 1;
+                }
+                bool ok = o.develop_curves.size() == 3;
+                for (const std::string& n : o.develop_curves) ok = ok && !n.empty();
+                if (!ok) return usage("--develop needs `cie` or three curve names CX,CY,CZ");
+            }
+            o.develop = true;
+        }
+        else if (a == "--develop-filter") {
+            if (!value(&o.develop_filter) || o.develop_filter.empty()) return usage("--develop-filter needs a curve name");
+            o.has_develop_filter = true;
+        }
+        else if (a == "--develop-subsamples") {
+            if (!value(&v)) return usage("--develop-subsamples needs a value");
+            char* end = nullptr;
+            const unsigned long n = strtoul(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end || n == 0 || n > PT_SPECTRAL_MAX_SUBSAMPLES) return usage("--develop-subsamples needs a count in 1..16");
+            o.develop_subsamples = (uint32_t)n; o.has_develop_subsamples = true;
+        }
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
     }
@@ -173,6 +215,9 @@ int main(int argc, char** argv) {
     if (o.denoise_bins && !o.denoise) return usage("--denoise-spectral-bins needs --denoise");
     if (o.denoise_bins && o.demodulate) return usage("--denoise-spectral-bins cannot be combined with --demodulate-albedo: demodulating the bins needs a per-bin albedo");
     if (o.denoise_bins && o.multi && o.device_mask != 1) return usage("--denoise-spectral-bins renders on device 0: --devices may name that device alone");
+    if (o.develop && !o.spectral_bins && !o.denoise_bins) return usage("--develop needs --spectral-bins or --denoise-spectral-bins: it develops their bins");
+    if (o.has_develop_filter && !o.develop) return usage("--develop-filter needs --develop");
+    if (o.has_develop_subsamples && !o.develop) return usage("--develop-subsamples needs --develop");
     const bool verbose = o.stdout_log_level == "info" || o.stdout_log_level == "debug" || o.stdout_log_level == "trace";
     const bool warnings = verbose || o.stdout_log_level == "warn";
     if (!o.root.empty()) pt_scene_file_set_root(o.root.c_str());
@@ -193,6 +238,28 @@ int main(int argc, char** argv) {
     const pt_scene_desc* desc = pt_scene_file_desc(scene_file);
     if (verbose) printf("scene %s: %u instances, %u meshes, %zu triangles, %u materials, %u curves\n", scene_path.c_str(), desc->instance_count, desc->mesh_count,
                         desc->index_count / 3, desc->material_count, desc->curve_count);
+
+    // --develop: the response curves and the filter, from the curves library of the scene file (in pt_scene_desc's representation, for pt_spectral_response_matrix)
+    std::vector<pt_curve> develop_curves;
+    std::vector<float> develop_data;
+    int32_t develop_responses[3] = {PT_RESPONSE_CIE_X, PT_RESPONSE_CIE_Y, PT_RESPONSE_CIE_Z}, develop_filter = PT_SPECTRAL_NO_FILTER;
+    if (o.develop) {
+        std::vector<std::string> names = o.develop_curves;
+        if (o.has_develop_filter) names.push_back(o.develop_filter);
+        for (size_t k = 0; k < names.size(); ++k) {
+            pt_curve c; const float* data = nullptr; uint32_t floats = 0;
+            if (pt_scene_file_library_curve(scene_file, names[k].c_str(), &c, &data, &floats) != PT_OK) {
+                fprintf(stderr, "error: --develop: %s\n", pt_scene_file_last_error());
+                pt_scene_file_free(scene_file);
+                pt_config_free(config);
+                return 1;
+            }
+            c.data_offset = (uint32_t)develop_data.size();
+            develop_data.insert(develop_data.end(), data, data + floats);
+            develop_curves.push_back(c);
+            if (k < o.develop_curves.size()) develop_responses[k] = (int32_t)k; else develop_filter = (int32_t)k;
+        }
+    }
 
     // --denoise: what the adaptive path refuses is refused here, with its message, before anything is rendered or written
     if (o.denoise && !o.dry_run) {
@@ -323,6 +390,29 @@ int main(int argc, char** argv) {
                 std::vector<float> noisy(spectral);
                 if (!write_spectral(base + "_spectral", noisy)) { rc = 1; break; }
             } else if (!spectral.empty() && !write_spectral(base + "_spectral", spectral)) { rc = 1; break; }
+            // --develop: three planes from the bins — the scene's resident ones (bins == nullptr) or a host array as rendered or filtered, before the factor —,
+            // packed as an XYZW film with W = 0, through this setting's film output (buffers of its own: `linear` still serves the spectral files)
+            const auto develop = [&](const std::string& name, const float* bins) {
+                const pt_spectral_desc sd = {file_bins, {0u, 0u, 0u}};
+                const size_t np = (size_t)rd.width * rd.height;
+                std::vector<float> matrix((size_t)3 * file_bins), planes(3 * np), packed(4 * np), dev_linear(3 * np);
+                std::vector<uint8_t> dev_rgba(4 * np);
+                pt_status st = pt_spectral_response_matrix(&rd, &sd, develop_curves.data(), (uint32_t)develop_curves.size(), develop_data.data(), (uint32_t)develop_data.size(),
+                                                           3, develop_responses, develop_filter, o.develop_subsamples, matrix.data());
+                if (st == PT_OK) st = bins ? pt_spectral_project(rd.width, rd.height, file_bins, 3, matrix.data(), bins, planes.data())
+                                           : pt_spectral_project_resident(scene, 3, matrix.data(), planes.data());
+                if (st != PT_OK) { fprintf(stderr, "--develop: %s\n", pt_last_error()); return false; }
+                for (size_t p = 0; p < np; ++p) { packed[4 * p] = planes[p]; packed[4 * p + 1] = planes[np + p]; packed[4 * p + 2] = planes[2 * np + p]; packed[4 * p + 3] = 0.0f; }
+                if (pt_output_film(&od, packed.data(), dev_rgba.data(), dev_linear.data()) != PT_OK ||
+                    pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, dev_linear.data(), od.colorspace) != PT_OK ||
+                    pt_write_png((name + ".png").c_str(), rd.width, rd.height, dev_rgba.data(), od.colorspace) != PT_OK) {
+                    fprintf(stderr, "--develop: %s\n", pt_last_error());
+                    return false;
+                }
+                printf("wrote %s.exr and %s.png (developed from %u bins)\n", name.c_str(), name.c_str(), file_bins);
+                return true;
+            };
+            if (o.develop && !develop(base + "_developed", o.denoise_bins ? spectral.data() : nullptr)) { rc = 1; break; }
             if (o.denoise) {
                 std::vector<float> guides((size_t)rd.width * rd.height * 4), clean((size_t)rd.width * rd.height * 4);
                 pt_denoise_desc dd;
@@ -356,6 +446,7 @@ int main(int argc, char** argv) {
                 }
                 if (o.write_film && !write_npy(dbase + ".npy", clean.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", dbase.c_str()); rc = 1; break; }
                 printf("wrote %s.exr and %s.png\n", dbase.c_str(), dbase.c_str());
+                if (o.develop && o.denoise_bins && !develop(dbase + "_developed", clean_spectral.data())) { rc = 1; break; }   // (before the factor goes into the bins)
                 if (o.denoise_bins && !write_spectral(dbase + "_spectral", clean_spectral)) { rc = 1; break; }   // (`linear` now holds the denoised film's R, G, B)
             }
         }

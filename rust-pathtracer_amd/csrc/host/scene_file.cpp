@@ -285,6 +285,10 @@ struct pt_scene_file {
     std::map<std::string, int> curve_names, texture_names, camera_names;
     std::map<std::string, uint32_t> material_ids;
     std::vector<std::string> warnings;
+    // pt_scene_file_library_curve: the curves library the scene was loaded with, kept alive, and the curves resolved from it on request.  They live beside the
+    // scene's own (curves, curve_data above are untouched: the pt_scene_desc is what it is without them).
+    Lib curves_library;
+    std::map<std::string, CurveM> library_curves;
 
     int add_curve(const CurveM& c) {
         pt_curve r; r.kind = c.kind; r.mode = c.mode; r.p0 = c.p0; r.p1 = c.p1; r.data_offset = (uint32_t)curve_data.size(); r.data_count = c.count;
@@ -429,6 +433,7 @@ void load_scene(const std::string& path, const pt_config* config, pt_scene_file&
     memset(&sf.desc, 0, sizeof(sf.desc));
     Loader L{sf, config, resolve_lib(top.req("curves"), "curves"), resolve_lib(top.req("textures"), "textures"),
              resolve_lib(top.req("materials"), "materials"), resolve_lib(top.req("meshes"), "meshes")};
+    sf.curves_library = L.curves_lib;
     // mediums (mod.rs:389-419, medium.rs): every entry of the library, in file order.  The reference numbers them from 0 in HashMap order while
     // its walk reads id 0 as the vacuum and id k as mediums[k - 1] (utils.rs:768-770), so a material there tracks the medium BEFORE the one
     // it names; here a name means its own medium: id = position + 1.
@@ -876,6 +881,20 @@ int64_t pt_scene_file_material(const pt_scene_file* s, const char* name) { auto 
 int32_t pt_scene_file_curve(const pt_scene_file* s, const char* name) { auto it = s->curve_names.find(name); return it == s->curve_names.end() ? -1 : it->second; }
 int32_t pt_scene_file_texture(const pt_scene_file* s, const char* name) { auto it = s->texture_names.find(name); return it == s->texture_names.end() ? -1 : it->second; }
 int32_t pt_scene_file_camera(const pt_scene_file* s, const char* name) { auto it = s->camera_names.find(name); return it == s->camera_names.end() ? -1 : it->second; }
+pt_status pt_scene_file_library_curve(pt_scene_file* s, const char* name, pt_curve* curve, const float** data, uint32_t* data_floats) {
+    if (!s || !name || !curve || !data || !data_floats) { g_error = "null argument"; return PT_ERR_INVALID_ARGUMENT; }
+    return guarded([&] {
+        auto it = s->library_curves.find(name);
+        if (it == s->library_curves.end()) {
+            const toml::Value* v = s->curves_library.table() ? s->curves_library.table()->find(name) : nullptr;
+            if (!v) fail(std::string("curve `") + name + "` not found in the curves library");
+            it = s->library_curves.emplace(name, curve_from_data(*v, std::string("curves.") + name)).first;
+        }
+        const CurveM& c = it->second;
+        curve->kind = c.kind; curve->mode = c.mode; curve->p0 = c.p0; curve->p1 = c.p1; curve->data_offset = 0; curve->data_count = c.count;
+        *data = c.data.data(); *data_floats = (uint32_t)c.data.size();
+    });
+}
 uint32_t pt_scene_file_warning_count(const pt_scene_file* s) { return s ? (uint32_t)s->warnings.size() : 0; }
 const char* pt_scene_file_warning(const pt_scene_file* s, uint32_t i) { return (s && i < s->warnings.size()) ? s->warnings[i].c_str() : nullptr; }
 

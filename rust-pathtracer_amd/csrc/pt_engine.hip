@@ -31,6 +31,7 @@
 #include "pt_adaptive_select.h"
 #include "pt_spectral_launch.h"
 #include "pt_spectral_rules.h"
+#include "pt_spectral_project_launch.h"
 #include "pt_denoise_launch.h"
 #include "pt_error.h"
 #include "pt_guides_chain_launch.h"
@@ -287,6 +288,13 @@ struct pt_scene {
     size_t film_cache_bytes = 0;
     float* spectral_cache = nullptr; // pt_render_spectral's device planes (bins x width x height), kept between calls
     size_t spectral_cache_bytes = 0;
+    // The resident spectral film (pt_spectral_project_resident): what the last successful spectral render left in spectral_cache.  Cleared when a spectral render
+    // starts and set when it has succeeded; pt_render_spectral and pt_render_adaptive_spectral are the only writers of spectral_cache (ensure_spectral_cache, which
+    // may replace it, runs inside them behind the clearing).
+    bool spectral_valid = false;
+    uint32_t spectral_width = 0, spectral_height = 0, spectral_bins = 0;
+    float* project_cache = nullptr;  // pt_spectral_project_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x PT_SPECTRAL_MAX_BINS floats) and, behind it, its output planes
+    size_t project_cache_bytes = 0;
     std::vector<pt_scene*> replicas; // pt_render_multi: this scene on the other (virtual) devices, by device index x virtual index (nullptr = not made yet / this one)
 };
 
@@ -903,7 +911,7 @@ void pt_scene_destroy(pt_scene* sc) {
     hipSetDevice(sc->device);
     sc->buf.release();
     sc->adaptive.release();
-    hipFree(sc->d_blob); hipFree(sc->d_tex); hipFree(sc->film_cache); hipFree(sc->spectral_cache);
+    hipFree(sc->d_blob); hipFree(sc->d_tex); hipFree(sc->film_cache); hipFree(sc->spectral_cache); hipFree(sc->project_cache);
     for (auto& e : sc->events) hipEventDestroy(e);
     delete sc;
 }
@@ -972,6 +980,7 @@ pt_status pt_render_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_s
     pt_status st = pth::check_spectral_args(sc, rdp, sdp, film, spectral, &err);
     if (st != PT_OK) return fail(st, err);
     if (rdp->width == 0 || rdp->height == 0 || (uint64_t)rdp->width * rdp->height > 0xffffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and the film at most 2^32 - 1 pixels");
+    sc->spectral_valid = false;   // (a spectral render starts: whatever the buffer held is no film from here on)
     HIP_TRY(hipSetDevice(sc->device));
     const size_t n_pixels = (size_t)rdp->width * rdp->height, film_bytes = sizeof(float) * 4 * n_pixels, spectral_bytes = sizeof(float) * sdp->bins * n_pixels;
     st = ensure_film_cache(sc, film_bytes);
@@ -982,6 +991,7 @@ pt_status pt_render_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_s
     if (st != PT_OK) return st;
     HIP_TRY(hipMemcpy(film, sc->film_cache, film_bytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(spectral, sc->spectral_cache, spectral_bytes, hipMemcpyDeviceToHost));
+    sc->spectral_width = rdp->width; sc->spectral_height = rdp->height; sc->spectral_bins = sdp->bins; sc->spectral_valid = true;
     return PT_OK;
 }
 
@@ -992,6 +1002,7 @@ pt_status pt_render_adaptive_spectral(pt_scene* sc, const pt_render_desc* rdp, c
     std::string err;
     pt_status st = pth::check_adaptive_spectral_args(sc, rdp, adp, sdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, film, sample_counts, spectral, &rd, &ad, &err);
     if (st != PT_OK) return fail(st, err);
+    sc->spectral_valid = false;   // (as in pt_render_spectral)
     HIP_TRY(hipSetDevice(sc->device));
     const size_t n_pixels = (size_t)rd.width * rd.height, spectral_bytes = sizeof(float) * sdp->bins * n_pixels;
     st = ensure_film_cache(sc, sizeof(float) * 4 * n_pixels);
@@ -1006,6 +1017,41 @@ pt_status pt_render_adaptive_spectral(pt_scene* sc, const pt_render_desc* rdp, c
     if (stats) HIP_TRY(hipMemcpy(stats, sc->adaptive.stats, sizeof(double) * 2 * n_pixels, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(spectral, sc->spectral_cache, spectral_bytes, hipMemcpyDeviceToHost));
     if (profile) profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (the whole call: set-up, rounds, read-backs)
+    sc->spectral_width = rd.width; sc->spectral_height = rd.height; sc->spectral_bins = sdp->bins; sc->spectral_valid = true;
+    return PT_OK;
+}
+
+pt_status pt_spectral_resident(pt_scene* sc, uint32_t* width, uint32_t* height, uint32_t* bins) {
+    if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
+    if (!width || !height || !bins) return fail(PT_ERR_INVALID_ARGUMENT, "width, height or bins is null");
+    *width = sc->spectral_valid ? sc->spectral_width : 0u; *height = sc->spectral_valid ? sc->spectral_height : 0u; *bins = sc->spectral_valid ? sc->spectral_bins : 0u;
+    return PT_OK;
+}
+
+// include/pt_spectral.h: pt_spectral_project's kernel over spectral_cache, on the stream the render ran on (the null stream), so the bins never cross the bus.
+pt_status pt_spectral_project_resident(pt_scene* sc, uint32_t K, const float* matrix, float* out) {
+    if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
+    if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "the developed planes (out) are null");
+    if (!sc->spectral_valid) return fail(PT_ERR_INVALID_ARGUMENT, "the scene has no resident spectral film: pt_render_spectral or pt_render_adaptive_spectral must have succeeded on it");
+    std::string err;
+    const pt_status st = pth::check_spectral_matrix(K, sc->spectral_bins, matrix, &err);
+    if (st != PT_OK) return fail(st, err);
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t n_pixels = (size_t)sc->spectral_width * sc->spectral_height;
+    const size_t matrix_floats = (size_t)PT_SPECTRAL_MAX_RESPONSES * PT_SPECTRAL_MAX_BINS, bytes = sizeof(float) * (matrix_floats + (size_t)K * n_pixels);
+    if (sc->project_cache_bytes < bytes) {
+        if (sc->project_cache) hipFree(sc->project_cache);
+        sc->project_cache = nullptr; sc->project_cache_bytes = 0;
+        HIP_TRY(hipMalloc(&sc->project_cache, bytes));
+        sc->project_cache_bytes = bytes;
+    }
+    float* d_out = sc->project_cache + matrix_floats;
+    hipStream_t stream = nullptr;
+    HIP_TRY(hipMemcpyAsync(sc->project_cache, matrix, sizeof(float) * K * sc->spectral_bins, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ptk::launch_spectral_project(ptk::spectral_project_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, sc->spectral_bins, K, sc->project_cache,
+                                         sc->spectral_cache, d_out));
+    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(float) * K * n_pixels, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     return PT_OK;
 }
 

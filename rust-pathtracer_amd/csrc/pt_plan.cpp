@@ -280,4 +280,50 @@ pt_status check_denoise_spectral_albedo_args(const pt_denoise_desc* in, uint32_t
     return PT_OK;
 }
 
+pt_status check_spectral_matrix(uint32_t K, uint32_t bins, const float* matrix, std::string* error) {
+    if (!matrix) { *error = "the response matrix is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (K == 0) { *error = "K must be positive: a development needs a response"; return PT_ERR_INVALID_ARGUMENT; }
+    if (K > PT_SPECTRAL_MAX_RESPONSES) { *error = "K: at most 16 responses"; return PT_ERR_INVALID_ARGUMENT; }
+    if (bins == 0) { *error = "bins must be positive"; return PT_ERR_INVALID_ARGUMENT; }
+    if (bins > PT_SPECTRAL_MAX_BINS) { *error = "bins: at most 64"; return PT_ERR_INVALID_ARGUMENT; }
+    for (uint32_t i = 0; i < K * bins; ++i)
+        if (!pt_isfinite(matrix[i])) { *error = "a response matrix entry is not finite"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
+pt_status check_spectral_project_args(uint32_t width, uint32_t height, uint32_t bins, uint32_t K, const float* matrix, const void* spectral, const void* out,
+                                      std::string* error) {
+    if (!spectral) { *error = "the spectral film is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!out) { *error = "the developed planes (out) are null"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = check_spectral_matrix(K, bins, matrix, error);
+    if (st != PT_OK) return st;
+    if (width == 0 || height == 0) { *error = "width and height must be positive"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((uint64_t)width * (uint64_t)height > 0x7fffffffull) { *error = "width x height must fit 31 bits"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
+pt_status check_response_matrix_args(const pt_render_desc* rd, const pt_spectral_desc* sd, const void* curves, uint32_t curve_count, const void* curve_data,
+                                     uint32_t curve_data_floats, uint32_t K, const int32_t* responses, int32_t filter, uint32_t subsamples, const void* matrix,
+                                     std::string* error) {
+    if (!rd) { *error = "the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = check_spectral_desc(sd, error);
+    if (st != PT_OK) return st;
+    if (!responses) { *error = "the responses are null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!matrix) { *error = "the response matrix is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (curve_count != 0 && !curves) { *error = "curves is null with a positive curve_count"; return PT_ERR_INVALID_ARGUMENT; }
+    if (curve_data_floats != 0 && !curve_data) { *error = "curve_data is null with a positive curve_data_floats"; return PT_ERR_INVALID_ARGUMENT; }
+    if (K == 0) { *error = "K must be positive: a development needs a response"; return PT_ERR_INVALID_ARGUMENT; }
+    if (K > PT_SPECTRAL_MAX_RESPONSES) { *error = "K: at most 16 responses"; return PT_ERR_INVALID_ARGUMENT; }
+    if (subsamples == 0) { *error = "subsamples must be positive"; return PT_ERR_INVALID_ARGUMENT; }
+    if (subsamples > PT_SPECTRAL_MAX_SUBSAMPLES) { *error = "subsamples: at most 16"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!(rd->wavelength_hi >= rd->wavelength_lo)) { *error = "bad wavelength bounds"; return PT_ERR_INVALID_ARGUMENT; }
+    for (uint32_t k = 0; k < K; ++k) {
+        const int32_t r = responses[k];
+        const bool cie = r == PT_RESPONSE_CIE_X || r == PT_RESPONSE_CIE_Y || r == PT_RESPONSE_CIE_Z;
+        if (!cie && (r < 0 || (uint32_t)r >= curve_count)) { *error = "response " + std::to_string(k) + " is neither a curve index nor a PT_RESPONSE_CIE constant"; return PT_ERR_INVALID_ARGUMENT; }
+    }
+    if (filter != PT_SPECTRAL_NO_FILTER && (filter < 0 || (uint32_t)filter >= curve_count)) { *error = "the filter is neither a curve index nor PT_SPECTRAL_NO_FILTER"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
 }  // namespace pth

@@ -74,6 +74,17 @@ pt_status check_guides_bin_albedo_args(const void* scene, const pt_render_desc* 
 pt_status check_denoise_spectral_albedo_args(const pt_denoise_desc* in, uint32_t bins, const void* film, const uint32_t* sample_counts, const void* stats,
                                              const float* guides, const float* albedo, const void* spectral, const float* bin_albedo, const void* out_film,
                                              const void* out_spectral, pt_denoise_desc* out, std::string* error);
+// A response matrix as pt_spectral_project and pt_spectral_project_resident take it: the matrix pointer, K in 1..PT_SPECTRAL_MAX_RESPONSES, bins in
+// 1..PT_SPECTRAL_MAX_BINS, every entry finite; each refusal with its own message
+pt_status check_spectral_matrix(uint32_t K, uint32_t bins, const float* matrix, std::string* error);
+// pt_spectral_project's arguments: no null pointer, check_spectral_matrix, width and height positive and width x height within 31 bits
+pt_status check_spectral_project_args(uint32_t width, uint32_t height, uint32_t bins, uint32_t K, const float* matrix, const void* spectral, const void* out,
+                                      std::string* error);
+// pt_spectral_response_matrix's arguments: no null pointer (curves / curve_data may be null when their counts are 0), check_spectral_desc, K and subsamples in
+// range, the bounds in order, every response a curve index or a PT_RESPONSE_CIE_* constant, the filter a curve index or PT_SPECTRAL_NO_FILTER
+pt_status check_response_matrix_args(const pt_render_desc* rd, const pt_spectral_desc* sd, const void* curves, uint32_t curve_count, const void* curve_data,
+                                     uint32_t curve_data_floats, uint32_t K, const int32_t* responses, int32_t filter, uint32_t subsamples, const void* matrix,
+                                     std::string* error);
 
 }  // namespace pth
 #endif

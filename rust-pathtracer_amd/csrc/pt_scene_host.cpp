@@ -4,6 +4,7 @@
 // src/parsing/mod.rs:145-563, src/geometry/mesh.rs:283-305, src/accelerator/mod.rs:31-43).
 #include "pt_scene_host.h"
 #include "pt_device.h"
+#include "pt_spectral_project_rules.h"
 
 #include <algorithm>
 #include <array>
@@ -405,6 +406,82 @@ float triangle_area(const float* V, const uint32_t* ix) {
 
 }  // namespace
 
+// The curves' validation and their records in the blob, for build_host_scene and for build_curve_view alike (one text: a curve's value is the same in both).
+static const char* check_curves(const pt_curve* curves, uint32_t curve_count, size_t curve_data_count) {
+    for (uint32_t i = 0; i < curve_count; ++i) {
+        const pt_curve& c = curves[i];
+        uint32_t per = c.kind == PT_CURVE_TABULATED ? 2 : ((c.kind == PT_CURVE_EXPONENTIAL || c.kind == PT_CURVE_INV_EXPONENTIAL) ? 4 : 1);
+        bool needs_data = c.kind == PT_CURVE_LINEAR || c.kind == PT_CURVE_TABULATED || c.kind == PT_CURVE_EXPONENTIAL || c.kind == PT_CURVE_INV_EXPONENTIAL;
+        if (c.kind < 0 || c.kind > PT_CURVE_CONST) return "unknown curve kind";
+        if (needs_data && ((size_t)c.data_offset + (size_t)c.data_count * per > curve_data_count)) return "curve data out of range";
+        if ((c.kind == PT_CURVE_LINEAR || c.kind == PT_CURVE_TABULATED) && c.data_count == 0) return "empty curve table";
+    }
+    return nullptr;
+}
+static void flatten_curves(const pt_curve* curves, uint32_t curve_count, const float* curve_data, bool curve_tables, std::vector<uint32_t>& w,
+                           std::vector<uint32_t>* curve_off_out, uint32_t* curve_table_words) {
+    pad16(w);
+    std::vector<uint32_t>& curve_off = *curve_off_out;
+    curve_off.assign(curve_count, 0);
+    for (uint32_t i = 0; i < curve_count; ++i) { curve_off[i] = (uint32_t)w.size(); w.resize(w.size() + PT_CURVE_WORDS, 0); }
+    for (uint32_t i = 0; i < curve_count; ++i) {
+        const pt_curve& c = curves[i];
+        uint32_t per = c.kind == PT_CURVE_TABULATED ? 2 : ((c.kind == PT_CURVE_EXPONENTIAL || c.kind == PT_CURVE_INV_EXPONENTIAL) ? 4 : 1);
+        uint32_t off = (uint32_t)w.size();
+        bool has = c.kind == PT_CURVE_LINEAR || c.kind == PT_CURVE_TABULATED || c.kind == PT_CURVE_EXPONENTIAL || c.kind == PT_CURVE_INV_EXPONENTIAL;
+        if (has) for (uint32_t k = 0; k < c.data_count * per; ++k) w.push_back(fbits(curve_data[c.data_offset + k]));
+        // A tabulated curve's cell table (round 5; pt_blob.h PT_CURVE_GRID): the knot range in G equal cells, per cell the number of knots in lower cells — a lower
+        // bound of the binary search's answer for every wavelength of the cell (cell() is monotone), from which curve_eval walks up: the same index, one or two knot
+        // reads instead of log2 n.  cell() here is curve_grid_cell's arithmetic (pt_device.h), operation for operation.
+        uint32_t grid_word = 0, inv_bits = 0;
+        if (curve_tables && c.kind == PT_CURVE_TABULATED && c.data_count >= PT_CURVE_GRID_MIN_KNOTS && c.data_count <= 255u) {
+            const float* kd = curve_data + c.data_offset;
+            const uint32_t n = c.data_count;
+            bool sorted = true;
+            for (uint32_t k = 0; k < n; ++k) sorted = sorted && std::isfinite(kd[2 * k]) && (k == 0 || kd[2 * k] >= kd[2 * (k - 1)]);
+            uint32_t cells = 16; while (cells < n) cells *= 2;
+            const float x0 = kd[0], width = kd[2 * (n - 1)] - x0;
+            const float inv = (float)cells / width;
+            if (sorted && width > 0.0f && std::isfinite(inv) && inv > 0.0f && w.size() < (1u << 24)) {   // (the table's word offset rides in 24 bits of the record's grid word: a core section beyond 64 MB keeps the binary search)
+                const float top = (float)(cells - 1);
+                std::vector<uint32_t> below(cells + 1, 0);   // below[g] = knots in cells < g
+                for (uint32_t k = 0; k < n; ++k) {
+                    const float fi = (kd[2 * k] - x0) * inv;
+                    const uint32_t g = fi >= 0.0f ? (uint32_t)(fi < top ? fi : top) : 0u;
+                    below[g + 1] += 1;
+                }
+                for (uint32_t g = 0; g < cells; ++g) below[g + 1] += below[g];
+                const uint32_t toff = (uint32_t)w.size();
+                for (uint32_t g = 0; g < cells; g += 4) w.push_back(below[g] | below[g + 1] << 8 | below[g + 2] << 16 | below[g + 3] << 24);
+                grid_word = toff | (cells - 1) << 24; inv_bits = fbits(inv); *curve_table_words += cells / 4;
+            }
+        }
+        uint32_t* r = &w[curve_off[i]];
+        r[0] = (uint32_t)c.kind; r[1] = (uint32_t)c.mode; r[2] = fbits(c.p0); r[3] = fbits(c.p1); r[4] = off; r[5] = has ? c.data_count : 0;
+        r[PT_CURVE_GRID] = grid_word; r[PT_CURVE_GRID_INV] = inv_bits;
+    }
+}
+bool build_curve_view(const pt_curve* curves, uint32_t curve_count, const float* curve_data, size_t curve_data_count, std::vector<uint32_t>* blob,
+                      std::vector<uint32_t>* curve_offsets, std::string* err) {
+    if (const char* bad = check_curves(curves, curve_count, curve_data_count)) { *err = bad; return false; }
+    blob->assign(PT_HDR_WORDS, 0);
+    uint32_t table_words = 0;
+    flatten_curves(curves, curve_count, curve_data, true, *blob, curve_offsets, &table_words);
+    return true;
+}
+
+bool spectral_response_matrix(float lo, float hi, uint32_t bins, const pt_curve* curves, uint32_t curve_count, const float* curve_data, size_t curve_data_count,
+                              uint32_t K, const int32_t* responses, int32_t filter, uint32_t subsamples, float* matrix, std::string* err) {
+    std::vector<uint32_t> blob, off;
+    if (!build_curve_view(curves, curve_count, curve_data, curve_data_count, &blob, &off, err)) return false;
+    const float tex = 0.0f;
+    ptd::SceneView view{blob.data(), &tex};
+    const float w = (hi - lo) / (float)bins;
+    for (uint32_t k = 0; k < K; ++k)
+        for (uint32_t b = 0; b < bins; ++b) matrix[(size_t)k * bins + b] = ptd::spectral_matrix_entry(view, off.data(), responses[k], filter, lo, w, b, subsamples);
+    return true;
+}
+
 static bool build_host_scene_with(const pt_scene_desc& d, HostScene* hs, std::string* err, bool curve_tables, uint32_t* curve_table_words);
 // The curves' cell tables are an accelerator, and a scene that fits the LDS whole without them and not with them is better off without (the kernels of a scene staged
 // whole never touch global memory for scene data: G2F at 24.3 KB): built again without the tables then.
@@ -430,14 +507,7 @@ static bool build_host_scene_with(const pt_scene_desc& d, HostScene* hs, std::st
         if (d.environment.importance_luminance_curve >= (int32_t)d.curve_count) return fail("importance luminance curve out of range");
     } else if (d.environment.curve < 0 || (uint32_t)d.environment.curve >= d.curve_count) return fail("environment curve index out of range");
     auto curve_ok = [&](int32_t c) { return c >= 0 && (uint32_t)c < d.curve_count; };
-    for (uint32_t i = 0; i < d.curve_count; ++i) {
-        const pt_curve& c = d.curves[i];
-        uint32_t per = c.kind == PT_CURVE_TABULATED ? 2 : ((c.kind == PT_CURVE_EXPONENTIAL || c.kind == PT_CURVE_INV_EXPONENTIAL) ? 4 : 1);
-        bool needs_data = c.kind == PT_CURVE_LINEAR || c.kind == PT_CURVE_TABULATED || c.kind == PT_CURVE_EXPONENTIAL || c.kind == PT_CURVE_INV_EXPONENTIAL;
-        if (c.kind < 0 || c.kind > PT_CURVE_CONST) return fail("unknown curve kind");
-        if (needs_data && ((size_t)c.data_offset + (size_t)c.data_count * per > d.curve_data_count)) return fail("curve data out of range");
-        if ((c.kind == PT_CURVE_LINEAR || c.kind == PT_CURVE_TABULATED) && c.data_count == 0) return fail("empty curve table");
-    }
+    if (const char* bad = check_curves(d.curves, d.curve_count, d.curve_data_count)) return fail(bad);
     for (uint32_t i = 0; i < d.material_count; ++i) {
         const pt_material& m = d.materials[i];
         switch (m.kind) {
@@ -480,45 +550,8 @@ static bool build_host_scene_with(const pt_scene_desc& d, HostScene* hs, std::st
     hs->cameras.assign(d.cameras, d.cameras + d.camera_count);
 
     // curves
-    pad16(w);
-    std::vector<uint32_t> curve_off(d.curve_count);
-    for (uint32_t i = 0; i < d.curve_count; ++i) { curve_off[i] = (uint32_t)w.size(); w.resize(w.size() + PT_CURVE_WORDS, 0); }
-    for (uint32_t i = 0; i < d.curve_count; ++i) {
-        const pt_curve& c = d.curves[i];
-        uint32_t per = c.kind == PT_CURVE_TABULATED ? 2 : ((c.kind == PT_CURVE_EXPONENTIAL || c.kind == PT_CURVE_INV_EXPONENTIAL) ? 4 : 1);
-        uint32_t off = (uint32_t)w.size();
-        bool has = c.kind == PT_CURVE_LINEAR || c.kind == PT_CURVE_TABULATED || c.kind == PT_CURVE_EXPONENTIAL || c.kind == PT_CURVE_INV_EXPONENTIAL;
-        if (has) for (uint32_t k = 0; k < c.data_count * per; ++k) w.push_back(fbits(d.curve_data[c.data_offset + k]));
-        // A tabulated curve's cell table (round 5; pt_blob.h PT_CURVE_GRID): the knot range in G equal cells, per cell the number of knots in lower cells — a lower
-        // bound of the binary search's answer for every wavelength of the cell (cell() is monotone), from which curve_eval walks up: the same index, one or two knot
-        // reads instead of log2 n.  cell() here is curve_grid_cell's arithmetic (pt_device.h), operation for operation.
-        uint32_t grid_word = 0, inv_bits = 0;
-        if (curve_tables && c.kind == PT_CURVE_TABULATED && c.data_count >= PT_CURVE_GRID_MIN_KNOTS && c.data_count <= 255u) {
-            const float* kd = d.curve_data + c.data_offset;
-            const uint32_t n = c.data_count;
-            bool sorted = true;
-            for (uint32_t k = 0; k < n; ++k) sorted = sorted && std::isfinite(kd[2 * k]) && (k == 0 || kd[2 * k] >= kd[2 * (k - 1)]);
-            uint32_t cells = 16; while (cells < n) cells *= 2;
-            const float x0 = kd[0], width = kd[2 * (n - 1)] - x0;
-            const float inv = (float)cells / width;
-            if (sorted && width > 0.0f && std::isfinite(inv) && inv > 0.0f && w.size() < (1u << 24)) {   // (the table's word offset rides in 24 bits of the record's grid word: a core section beyond 64 MB keeps the binary search)
-                const float top = (float)(cells - 1);
-                std::vector<uint32_t> below(cells + 1, 0);   // below[g] = knots in cells < g
-                for (uint32_t k = 0; k < n; ++k) {
-                    const float fi = (kd[2 * k] - x0) * inv;
-                    const uint32_t g = fi >= 0.0f ? (uint32_t)(fi < top ? fi : top) : 0u;
-                    below[g + 1] += 1;
-                }
-                for (uint32_t g = 0; g < cells; ++g) below[g + 1] += below[g];
-                const uint32_t toff = (uint32_t)w.size();
-                for (uint32_t g = 0; g < cells; g += 4) w.push_back(below[g] | below[g + 1] << 8 | below[g + 2] << 16 | below[g + 3] << 24);
-                grid_word = toff | (cells - 1) << 24; inv_bits = fbits(inv); *curve_table_words += cells / 4;
-            }
-        }
-        uint32_t* r = &w[curve_off[i]];
-        r[0] = (uint32_t)c.kind; r[1] = (uint32_t)c.mode; r[2] = fbits(c.p0); r[3] = fbits(c.p1); r[4] = off; r[5] = has ? c.data_count : 0;
-        r[PT_CURVE_GRID] = grid_word; r[PT_CURVE_GRID_INV] = inv_bits;
-    }
+    std::vector<uint32_t> curve_off;
+    flatten_curves(d.curves, d.curve_count, d.curve_data, curve_tables, w, &curve_off, curve_table_words);
     w[PT_HDR_CURVE_OFF] = d.curve_count ? curve_off[0] : 0; w[PT_HDR_CURVE_COUNT] = d.curve_count;
     hs->curve_offsets = curve_off;
 

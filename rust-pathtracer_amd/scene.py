@@ -190,6 +190,16 @@ class SceneBuilder:
     def curve(self, name):
         return self.curve_names[name]
 
+    def spectral_response_matrix(self, library, rd, bins, responses, filter=None, subsamples=1):
+        """Library.spectral_response_matrix over this description's curves, by name: `responses` is "cie" (the three colour-matching rows) or a sequence whose
+        entries are curve names or api.RESPONSE_CIE_* constants; `filter` is a curve name or None.  float32 [K, bins]."""
+        if isinstance(responses, str):
+            if responses != "cie":
+                raise ValueError("responses: \"cie\" or a sequence of curve names / RESPONSE_CIE_* constants")
+            responses = (api.RESPONSE_CIE_X, api.RESPONSE_CIE_Y, api.RESPONSE_CIE_Z)
+        idx = [self.curve_names[r] if isinstance(r, str) else int(r) for r in responses]
+        return library.spectral_response_matrix(rd, bins, idx, self.curves, self.curve_data, None if filter is None else self.curve_names[filter], subsamples)
+
     # ---- textures (src/parsing/texture.rs)
     def texstack_texture1(self, name, curve, texels=None):
         t = np.ones((1, 1), np.float32) if texels is None else np.asarray(texels, np.float32)

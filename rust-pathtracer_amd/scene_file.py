@@ -55,6 +55,7 @@ def library():
             getattr(L, "pt_scene_file_" + n).restype = C.c_int64; getattr(L, "pt_scene_file_" + n).argtypes = [vp, C.c_char_p]
         for n in ("curve", "texture", "camera"):
             getattr(L, "pt_scene_file_" + n).restype = C.c_int32; getattr(L, "pt_scene_file_" + n).argtypes = [vp, C.c_char_p]
+        L.pt_scene_file_library_curve.argtypes = [vp, C.c_char_p, C.POINTER(api.Curve), C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32)]
         L.pt_scene_file_warning_count.restype = C.c_uint32; L.pt_scene_file_warning_count.argtypes = [vp]
         L.pt_scene_file_warning.restype = C.c_char_p; L.pt_scene_file_warning.argtypes = [vp, C.c_uint32]
         L.pt_image_read.argtypes = [C.c_char_p, C.c_int32, C.c_float, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_float))]
@@ -153,6 +154,28 @@ class SceneFile:
 
     def curve(self, name):
         return library().pt_scene_file_curve(self.handle, name.encode())
+
+    def library_curve(self, name):
+        """pt_scene_file_library_curve: (api.Curve with data_offset 0, float32 data) of any curve of the curves library the scene was loaded with, also one the
+        scene does not use; an unknown name raises SceneFileError naming it.  The scene description is not changed."""
+        import numpy as np
+        c, data, n = api.Curve(), C.POINTER(C.c_float)(), C.c_uint32()
+        _check(library().pt_scene_file_library_curve(self.handle, name.encode(), C.byref(c), C.byref(data), C.byref(n)))
+        return c, (np.ctypeslib.as_array(data, shape=(n.value,)).copy() if n.value else np.zeros(0, np.float32))
+
+    def spectral_response_matrix(self, lib, rd, bins, responses, filter=None, subsamples=1):
+        """Library.spectral_response_matrix with curves of the scene file's curves library, by name: `responses` is "cie" or a sequence of names;
+        `filter` a name or None.  float32 [K, bins]."""
+        names = [] if responses == "cie" else list(responses)
+        idx = [api.RESPONSE_CIE_X, api.RESPONSE_CIE_Y, api.RESPONSE_CIE_Z] if responses == "cie" else list(range(len(names)))
+        curves, chunks, floats = [], [], 0
+        for name in names + ([filter] if filter is not None else []):
+            c, data = self.library_curve(name)
+            c.data_offset = floats
+            floats += data.size
+            curves.append(c); chunks.append(data)
+        import numpy as np
+        return lib.spectral_response_matrix(rd, bins, idx, curves, np.concatenate(chunks) if chunks else None, len(names) if filter is not None else None, subsamples)
 
     def texture(self, name):
         return library().pt_scene_file_texture(self.handle, name.encode())

@@ -22,7 +22,11 @@
  * demodulate them; pt_denoise_spectral_albedo does, by the per-bin albedo that pt_render_guides_bin_albedo renders (csrc/pt_denoise_spectral_albedo_rules.h).
  *
  * pt_spectral_project develops a spectral film: K weighted sums over the bins of every pixel, the weights a matrix that pt_spectral_response_matrix integrates
- * from response curves (csrc/pt_spectral_project_rules.h); pt_spectral_project_resident develops the bins a scene's last spectral render left on the device. */
+ * from response curves (csrc/pt_spectral_project_rules.h); pt_spectral_project_resident develops the bins a scene's last spectral render left on the device.
+ *
+ * pt_render_spectral_multi and pt_render_adaptive_spectral_multi are the two renders on every device of a node, bit for bit.  The bins are not reduced between
+ * the devices: each one packs the planes of its own tiles (csrc/pt_spectral_shard_rules.h) and hands them to the host over its own link, and they stay on it as
+ * its part of the scene's resident film, which pt_spectral_project_resident develops shard by shard. */
 #ifndef PT_SPECTRAL_H
 #define PT_SPECTRAL_H
 #include "pt_adaptive.h"
@@ -49,9 +53,26 @@ pt_status pt_render_spectral(pt_scene* scene, const pt_render_desc* desc, const 
 /* pt_render_adaptive with a spectral film.  desc, adaptive, film_xyzw, sample_counts (required), stats (may be NULL) and profile: pt_render_adaptive's, with
  * the same conditions; film, counts, stats, the number of rounds and the ray counters are pt_render_adaptive's bit for bit.  spectral: bins*width*height f32,
  * required; pixel p's bins are the plain f32 running sums over its n_p samples in sample order, divided once by (float)n_p when the render finishes.
- * One device only: pt_render_adaptive_multi has no spectral film. */
+ * One device: pt_render_adaptive_spectral_multi, below, is the call for several. */
 pt_status pt_render_adaptive_spectral(pt_scene* scene, const pt_render_desc* desc, const pt_adaptive_desc* adaptive, const pt_spectral_desc* spectral_desc,
                                       float* film_xyzw, uint32_t* sample_counts, double* stats, float* spectral, pt_profile* profile);
+
+/* pt_render_spectral on every device of device_mask from one blocking call: film_xyzw, spectral and the ray counters of the profile are pt_render_spectral's bit
+ * for bit, a partial sample range (first_sample / sample_count) included.  device_mask, pt_tuning::multi_virtual and PT_TUNE_MULTI_RCCL mean what they mean for
+ * pt_render_multi (bit d = HIP device d, 0 = all); desc->shard_count must be 0, the call deals the tiles itself.  With one device, no virtual devices and no forced
+ * RCCL the call is pt_render_spectral itself; PT_TUNE_MULTI_RCCL alone takes the node path with one shard that is the whole film.  The film travels as
+ * pt_render_multi's does.  The bins do not: every device packs the planes of its own tiles, copies them to the host and scatters them into `spectral` from its own
+ * host thread; the shards are disjoint and cover the film.  profile (may be NULL): pt_render_multi's; kernel_seconds[5] is the set-up (about 0 on a repeated
+ * call), kernel_seconds[6] the film reduce plus the longest device's pack, copy and scatter. */
+pt_status pt_render_spectral_multi(pt_scene* scene, const pt_render_desc* desc, const pt_spectral_desc* spectral_desc, uint64_t device_mask,
+                                   float* film_xyzw, float* spectral, pt_profile* profile);
+
+/* pt_render_adaptive_spectral on every device of device_mask: film, counts, stats, the number of rounds, the ray counters and the bins are
+ * pt_render_adaptive_spectral's bit for bit.  The devices, the mask and the one-device case are pt_render_spectral_multi's; film, counts and statistics travel as
+ * pt_render_adaptive_multi's do, the bins as pt_render_spectral_multi's.  kernel_seconds[6]: the rounds' exchanges, the gather and the longest device's pack, copy
+ * and scatter. */
+pt_status pt_render_adaptive_spectral_multi(pt_scene* scene, const pt_render_desc* desc, const pt_adaptive_desc* adaptive, const pt_spectral_desc* spectral_desc,
+                                            uint64_t device_mask, float* film_xyzw, uint32_t* sample_counts, double* stats, float* spectral, pt_profile* profile);
 
 /* pt_denoise_film on film_xyzw (desc, sample_counts, stats, guides_xyzw, out_film_xyzw, out_variance: as pt_denoise_film takes them) and, with the same taps
  * and weights, on the `bins` (1 .. PT_SPECTRAL_MAX_BINS) planes of `spectral` (bins*width*height f32, the layout above).  Pass i, live pixel p, bin b:
@@ -130,10 +151,12 @@ pt_status pt_spectral_response_matrix(const pt_render_desc* desc, const pt_spect
  * out: K * width * height f32, plane-major like the bins.  Runs on device 0. */
 pt_status pt_spectral_project(uint32_t width, uint32_t height, uint32_t bins, uint32_t K, const float* matrix, const float* spectral, float* out);
 
-/* The same projection of the bins that the scene's last successful pt_render_spectral / pt_render_adaptive_spectral left in its device buffer: bit for bit
- * pt_spectral_project of the array that render returned, without the bins crossing the bus — the matrix goes up and K planes come back.  matrix: K * bins f32
- * for that render's bins; out: K * width * height f32 for its size (pt_spectral_resident tells all three).  A scene that has not rendered a spectral film, or
- * whose last spectral render failed, has no resident film and the call fails. */
+/* The same projection of the bins that the scene's last successful spectral render — pt_render_spectral, pt_render_adaptive_spectral or one of their node forms —
+ * left on the device: bit for bit pt_spectral_project of the array that render returned, without the bins crossing the bus — the matrix goes up and K planes come
+ * back.  After a node render the resident film is the devices' packed shards: the matrix goes to each of them, each develops its own pixels and K planes' worth of
+ * them come back over its own link.  matrix: K * bins f32 for that render's bins; out: K * width * height f32 for its size (pt_spectral_resident tells all three).
+ * Every spectral render, of either kind, ends the residency of the film before it when it starts.  A scene that has not rendered a spectral film, or whose last
+ * spectral render failed, has no resident film and the call fails. */
 pt_status pt_spectral_project_resident(pt_scene* scene, uint32_t K, const float* matrix, float* out);
 
 /* Width, height and bins of the scene's resident spectral film; zeros when it has none. */

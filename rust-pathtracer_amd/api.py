@@ -273,6 +273,11 @@ class Library:
         self._write_exr_spectral = bind("write_exr_spectral", C.c_int32, [C.c_char_p, u32, u32, u32, fpp, fpp, fpp, C.c_int32], required=False)
         self._render_adaptive_spectral = bind("render_adaptive_spectral", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), C.POINTER(SpectralDesc), fpp,
                                                                                       C.POINTER(u32), C.POINTER(C.c_double), fpp, C.POINTER(Profile)], required=False)
+        self._render_spectral_multi = bind("render_spectral_multi", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(SpectralDesc), C.c_uint64, fpp, fpp, C.POINTER(Profile)],
+                                           required=False)
+        self._render_adaptive_spectral_multi = bind("render_adaptive_spectral_multi", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), C.POINTER(SpectralDesc),
+                                                                                                  C.c_uint64, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, C.POINTER(Profile)],
+                                                    required=False)
         self._denoise_spectral = bind("denoise_spectral", C.c_int32, [C.POINTER(DenoiseDesc), u32, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp, fpp],
                                       required=False)
         self._denoise_spectral_last_error = bind("denoise_spectral_last_error", C.c_char_p, [], required=False)   # (the emulation's)
@@ -577,8 +582,20 @@ class Scene:
         self.library.check(self.library._render_spectral(self.handle, C.byref(rd), C.byref(sd), _fp(film), _fp(spectral), C.byref(prof)))
         return film, spectral, prof
 
+    def render_spectral_multi(self, rd, bins, device_mask=0):
+        """pt_render_spectral_multi: render_spectral on every device of the mask (0 = all) from one blocking call, its outputs bit for bit.  Every device hands
+        over the bins of its own tiles; they stay on it as its part of the scene's resident film."""
+        if self.library._render_spectral_multi is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_spectral_multi entry" % (self.library.path, self.library.prefix))
+        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        spectral = np.zeros((max(int(bins), 0), rd.height, rd.width), dtype=np.float32)
+        sd = SpectralDesc(bins)
+        prof = Profile()
+        self.library.check(self.library._render_spectral_multi(self.handle, C.byref(rd), C.byref(sd), C.c_uint64(device_mask), _fp(film), _fp(spectral), C.byref(prof)))
+        return film, spectral, prof
+
     def spectral_resident(self):
-        """pt_spectral_resident: (width, height, bins) of the spectral film the last successful render_spectral / render_adaptive_spectral left on the device, or
+        """pt_spectral_resident: (width, height, bins) of the spectral film the last successful spectral render (one device or a node) left on the device(s), or
         None when the scene holds none."""
         if self.library._spectral_resident is None:
             raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sspectral_resident entry" % (self.library.path, self.library.prefix))
@@ -630,6 +647,23 @@ class Scene:
         prof = Profile()
         self.library.check(self.library._render_adaptive_spectral(self.handle, C.byref(rd), C.byref(ad), C.byref(sd), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                                   st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, _fp(spectral), C.byref(prof)))
+        return (film, counts, st, spectral, prof) if stats else (film, counts, spectral, prof)
+
+    def render_adaptive_spectral_multi(self, rd, bins, max_samples, rel_error, abs_error=0.0, step=0, stats=False, device_mask=0):
+        """pt_render_adaptive_spectral_multi: render_adaptive_spectral on every device of the mask (0 = all) from one blocking call, its outputs bit for bit.
+        Returns (film, counts[, stats], spectral, profile) as render_adaptive_spectral does."""
+        if self.library._render_adaptive_spectral_multi is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_adaptive_spectral_multi entry" % (self.library.path, self.library.prefix))
+        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        counts = np.zeros((rd.height, rd.width), dtype=np.uint32)
+        st = np.zeros((rd.height, rd.width, 2), dtype=np.float64) if stats else None
+        spectral = np.zeros((max(int(bins), 0), rd.height, rd.width), dtype=np.float32)
+        ad = AdaptiveDesc(max_samples, step, rel_error, abs_error)
+        sd = SpectralDesc(bins)
+        prof = Profile()
+        self.library.check(self.library._render_adaptive_spectral_multi(self.handle, C.byref(rd), C.byref(ad), C.byref(sd), C.c_uint64(device_mask), _fp(film),
+                                                                        counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                                        st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, _fp(spectral), C.byref(prof)))
         return (film, counts, st, spectral, prof) if stats else (film, counts, spectral, prof)
 
     def render_adaptive_multi(self, rd, max_samples, rel_error, abs_error=0.0, step=0, stats=False, device_mask=0):
@@ -722,24 +756,31 @@ class Scene:
         return film, den, counts, prof
 
     def render_denoised_spectral(self, rd, bins, max_samples=None, rel_error=0.0, guide_samples=4, specular_chain=0, abs_error=0.0, step=0, iterations=0,
-                                 sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, albedo=False, bin_albedo=False):
+                                 sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, albedo=False, bin_albedo=False, device_mask=None):
         """render_adaptive_spectral with statistics (max_samples None = rd.spp: a fixed count), its guides — render_guides, or render_guides_chain with max_chain
         `specular_chain` when that is positive — and denoise_spectral: (film, denoised, spectral, denoised_spectral, counts, profile).  `albedo` is refused, as
         denoise_spectral refuses it.  `bin_albedo`: guides, XYZ albedo and per-bin albedo come from one render_guides_bin_albedo call (with `specular_chain` as its
-        max_chain) and the filter is denoise_spectral_albedo: the film demodulated by the XYZ albedo, the bins by the per-bin albedo."""
+        max_chain) and the filter is denoise_spectral_albedo: the film demodulated by the XYZ albedo, the bins by the per-bin albedo.  `device_mask` (not None)
+        routes the render through render_adaptive_spectral_multi; the filter then runs on the first device of the mask."""
         if albedo:
             raise PtError(PT_ERR_UNSUPPORTED, "render_denoised_spectral takes no albedo: demodulating the bins needs a per-bin albedo (bin_albedo=True renders one)")
         mx = rd.spp if max_samples is None else max_samples
-        film, counts, st, spectral, prof = self.render_adaptive_spectral(rd, bins, mx, rel_error, abs_error, step, stats=True)
+        if device_mask is None:
+            film, counts, st, spectral, prof = self.render_adaptive_spectral(rd, bins, mx, rel_error, abs_error, step, stats=True)
+            device = 0
+        else:
+            film, counts, st, spectral, prof = self.render_adaptive_spectral_multi(rd, bins, mx, rel_error, abs_error, step, stats=True, device_mask=device_mask)
+            device = (device_mask & -device_mask).bit_length() - 1 if device_mask else 0
         if bin_albedo:
             guides, alb, balb = self.render_guides_bin_albedo(rd, bins, guide_samples, specular_chain)
-            den, den_spectral = self.library.denoise_spectral_albedo(film, counts, st, guides, spectral, alb, balb, iterations, sigma_luminance, sigma_depth, normal_power_log2)
+            den, den_spectral = self.library.denoise_spectral_albedo(film, counts, st, guides, spectral, alb, balb, iterations, sigma_luminance, sigma_depth, normal_power_log2,
+                                                                     device)
             return film, den, spectral, den_spectral, counts, prof
         if specular_chain > 0:
             guides, _ = self.render_guides_chain(rd, guide_samples, specular_chain, albedo=False)
         else:
             guides = self.render_guides(rd, guide_samples)
-        den, den_spectral = self.library.denoise_spectral(film, counts, st, guides, spectral, iterations, sigma_luminance, sigma_depth, normal_power_log2)
+        den, den_spectral = self.library.denoise_spectral(film, counts, st, guides, spectral, iterations, sigma_luminance, sigma_depth, normal_power_log2, device)
         return film, den, spectral, den_spectral, counts, prof
 
     def render_multi(self, rd, device_mask=0):

@@ -5,7 +5,7 @@
 //   ptcli [--config data/config.toml] [--scene FILE] [-n|--dry-run] [--stdout-log-level L] [--write-log-level L]
 //         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K] [--demodulate-albedo]
 //         [--guide-chain D] [--guide-alpha-max A] [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]
-//         [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N]
+//         [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -37,6 +37,10 @@
 // integrates the responses over each bin with N samples.  With --spectral-bins the bins are developed where the render left them on the device
 // (pt_spectral_project_resident); with --denoise-spectral-bins the undenoised bins go through pt_spectral_project, and the denoised ones too, to
 // <filename>_denoised_developed.*.  Every other file stays byte for byte what it is.  An unknown curve name ends the program once the scene file is loaded.
+// --spectral-devices MASK (with --spectral-bins or --denoise-spectral-bins only; bit d = HIP device d, 0 = all) renders the spectral film on the devices of MASK from
+// one call: pt_render_spectral_multi, or pt_render_adaptive_spectral_multi with --denoise-spectral-bins.  Every file stays byte for byte what the run without it writes.
+// --develop then develops the undenoised bins where the node render left them, shard by shard on the devices (pt_spectral_project_resident), and the filter of
+// --denoise runs on the first device of MASK.  It is refused together with --devices, whose refusals of the spectral flags stay what they are.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -76,6 +80,8 @@ struct Options {
     bool has_develop_filter = false, has_develop_subsamples = false;
     std::string develop_filter;
     uint32_t develop_subsamples = 1;
+    bool spectral_multi = false;  // --spectral-devices MASK: the spectral node calls (pt_render_spectral_multi / pt_render_adaptive_spectral_multi)
+    uint64_t spectral_device_mask = 0;
 };
 
 int usage(const char* msg) {
@@ -84,7 +90,7 @@ int usage(const char* msg) {
                     "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n"
                     "             [--denoise] [--guide-samples K] [--demodulate-albedo] [--guide-chain D] [--guide-alpha-max A]\n"
                     "             [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]\n"
-                    "             [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N]\n");
+                    "             [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK]\n");
     return 2;
 }
 
@@ -197,6 +203,13 @@ int main(int argc, char** argv) {
             if (end == v.c_str() || *end || n == 0 || n > PT_SPECTRAL_MAX_SUBSAMPLES) return usage("--develop-subsamples needs a count in 1..16");
             o.develop_subsamples = (uint32_t)n; o.has_develop_subsamples = true;
         }
+        else if (a == "--spectral-devices") {
+            if (!value(&v)) return usage("--spectral-devices needs a value");
+            char* end = nullptr;
+            o.spectral_device_mask = strtoull(v.c_str(), &end, 0);
+            if (end == v.c_str() || *end) return usage("--spectral-devices needs a device mask (bit d = HIP device d, 0 = all)");
+            o.spectral_multi = true;
+        }
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
     }
@@ -218,6 +231,8 @@ int main(int argc, char** argv) {
     if (o.develop && !o.spectral_bins && !o.denoise_bins) return usage("--develop needs --spectral-bins or --denoise-spectral-bins: it develops their bins");
     if (o.has_develop_filter && !o.develop) return usage("--develop-filter needs --develop");
     if (o.has_develop_subsamples && !o.develop) return usage("--develop-subsamples needs --develop");
+    if (o.spectral_multi && !o.spectral_bins && !o.denoise_bins) return usage("--spectral-devices needs --spectral-bins or --denoise-spectral-bins: it names the devices their spectral film is rendered on");
+    if (o.spectral_multi && o.multi) return usage("--spectral-devices cannot be combined with --devices: a spectral render takes its devices from --spectral-devices alone");
     const bool verbose = o.stdout_log_level == "info" || o.stdout_log_level == "debug" || o.stdout_log_level == "trace";
     const bool warnings = verbose || o.stdout_log_level == "warn";
     if (!o.root.empty()) pt_scene_file_set_root(o.root.c_str());
@@ -323,20 +338,26 @@ int main(int argc, char** argv) {
             std::vector<double> stats(o.denoise ? (size_t)rd.width * rd.height * 2 : 0);
             std::vector<float> spectral((size_t)o.denoise_bins * rd.width * rd.height);   // (--spectral-bins sizes it below)
             const pt_spectral_desc dsd = {o.denoise_bins, {0u, 0u, 0u}};
-            const char* adaptive_entry = o.denoise_bins ? "pt_render_adaptive_spectral" : o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive";
+            const char* adaptive_entry = o.denoise_bins ? (o.spectral_multi ? "pt_render_adaptive_spectral_multi" : "pt_render_adaptive_spectral")
+                                         : o.multi      ? "pt_render_adaptive_multi" : "pt_render_adaptive";
+            // --denoise-spectral-bins: the adaptive spectral render, on one device or (--spectral-devices) on the devices of the mask
+            const auto adaptive_spectral = [&](double* st_out) {
+                return o.spectral_multi ? pt_render_adaptive_spectral_multi(scene, &rd, &ad, &dsd, o.spectral_device_mask, film.data(), counts.data(), st_out, spectral.data(), &prof)
+                                        : pt_render_adaptive_spectral(scene, &rd, &ad, &dsd, film.data(), counts.data(), st_out, spectral.data(), &prof);
+            };
             uint64_t samples = (uint64_t)rd.width * rd.height * rd.spp;
             if (!adaptive && o.denoise) {
                 // a fixed count through the adaptive path (max_samples = min_samples, one round): pt_render's film bit for bit, and the statistics
                 printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
                 ad.max_samples = rd.spp; ad.rel_error = 0.0f;
-                const pt_status st = o.denoise_bins ? pt_render_adaptive_spectral(scene, &rd, &ad, &dsd, film.data(), counts.data(), stats.data(), spectral.data(), &prof)
+                const pt_status st = o.denoise_bins ? adaptive_spectral(stats.data())
                                      : o.multi      ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), stats.data(), &prof)
                                                     : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), stats.data(), &prof);
                 if (st != PT_OK) { fprintf(stderr, "%s: %s\n", adaptive_entry, pt_last_error()); rc = 1; break; }
             } else if (adaptive) {
                 printf("rendering %ux%u, %u..%u spp (adaptive, relative error %g), max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, ad.max_samples,
                        (double)ad.rel_error, rd.max_bounces, rd.light_samples);
-                const pt_status st = o.denoise_bins ? pt_render_adaptive_spectral(scene, &rd, &ad, &dsd, film.data(), counts.data(), stats.data(), spectral.data(), &prof)
+                const pt_status st = o.denoise_bins ? adaptive_spectral(stats.data())
                                      : o.multi      ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof)
                                                     : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof);
                 if (st != PT_OK) { fprintf(stderr, "%s: %s\n", adaptive_entry, pt_last_error()); rc = 1; break; }
@@ -349,7 +370,9 @@ int main(int argc, char** argv) {
                 printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
                 spectral.resize((size_t)o.spectral_bins * rd.width * rd.height);
                 const pt_spectral_desc sd = {o.spectral_bins, {0u, 0u, 0u}};
-                if (pt_render_spectral(scene, &rd, &sd, film.data(), spectral.data(), &prof) != PT_OK) { fprintf(stderr, "pt_render_spectral: %s\n", pt_last_error()); rc = 1; break; }
+                const pt_status st = o.spectral_multi ? pt_render_spectral_multi(scene, &rd, &sd, o.spectral_device_mask, film.data(), spectral.data(), &prof)
+                                                      : pt_render_spectral(scene, &rd, &sd, film.data(), spectral.data(), &prof);
+                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.spectral_multi ? "pt_render_spectral_multi" : "pt_render_spectral", pt_last_error()); rc = 1; break; }
             } else {
                 printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
                 const pt_status st = o.multi ? pt_render_multi(scene, &rd, o.device_mask, film.data(), &prof) : pt_render(scene, &rd, film.data(), &prof);
@@ -412,13 +435,15 @@ int main(int argc, char** argv) {
                 printf("wrote %s.exr and %s.png (developed from %u bins)\n", name.c_str(), name.c_str(), file_bins);
                 return true;
             };
-            if (o.develop && !develop(base + "_developed", o.denoise_bins ? spectral.data() : nullptr)) { rc = 1; break; }
+            // (a node render leaves its bins resident too, with either flag: they are developed on the devices)
+            if (o.develop && !develop(base + "_developed", o.denoise_bins && !o.spectral_multi ? spectral.data() : nullptr)) { rc = 1; break; }
             if (o.denoise) {
                 std::vector<float> guides((size_t)rd.width * rd.height * 4), clean((size_t)rd.width * rd.height * 4);
                 pt_denoise_desc dd;
                 memset(&dd, 0, sizeof(dd));
                 dd.width = rd.width; dd.height = rd.height;
                 if (o.multi && o.device_mask) while (!((o.device_mask >> dd.device) & 1u)) ++dd.device;   // (the first device of the mask: where the gather left the film)
+                if (o.spectral_multi && o.spectral_device_mask) while (!((o.spectral_device_mask >> dd.device) & 1u)) ++dd.device;
                 std::vector<float> albedo(o.demodulate || o.demodulate_bins ? (size_t)rd.width * rd.height * 4 : 0);
                 std::vector<float> bin_albedo(o.demodulate_bins ? spectral.size() : 0);
                 pt_guide_chain_desc cd;

@@ -32,6 +32,8 @@
 #include "pt_spectral_launch.h"
 #include "pt_spectral_rules.h"
 #include "pt_spectral_project_launch.h"
+#include "pt_spectral_shard_launch.h"
+#include "pt_spectral_shard_rules.h"
 #include "pt_denoise_launch.h"
 #include "pt_error.h"
 #include "pt_guides_chain_launch.h"
@@ -268,6 +270,8 @@ struct MultiSetup {
     std::vector<float*> films;        // per virtual device, on its physical device
     std::vector<hipStream_t> streams; // per virtual device
     std::vector<ncclComm_t> comms;    // per physical device (rccl only)
+    std::vector<float*> staging;      // per virtual device: the pinned host buffer its packed spectral planes land in (the spectral node entries; grown on demand)
+    std::vector<size_t> staging_bytes;
     bool valid = false;
 };
 
@@ -293,6 +297,14 @@ struct pt_scene {
     // may replace it, runs inside them behind the clearing).
     bool spectral_valid = false;
     uint32_t spectral_width = 0, spectral_height = 0, spectral_bins = 0;
+    // After a node render (pt_render_spectral_multi / pt_render_adaptive_spectral_multi) the resident film is the set of packed shards instead: spectral_shards
+    // (on the scene the call was made on) names the scenes that hold them — this one and its replicas, which live as long as it does; empty = spectral_cache.
+    // Each of those scenes keeps its own shard: shard_px, the pixel list in pth::shard_pixels' order, and shard_packed, spectral_bins planes of shard_px.size()
+    // floats on its device (k_spectral_pack's output).
+    std::vector<pt_scene*> spectral_shards;
+    std::vector<uint32_t> shard_px;
+    float* shard_packed = nullptr;
+    size_t shard_packed_bytes = 0;
     float* project_cache = nullptr;  // pt_spectral_project_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x PT_SPECTRAL_MAX_BINS floats) and, behind it, its output planes
     size_t project_cache_bytes = 0;
     std::vector<pt_scene*> replicas; // pt_render_multi: this scene on the other (virtual) devices, by device index x virtual index (nullptr = not made yet / this one)
@@ -491,18 +503,22 @@ pt_status adaptive_rounds(pt_scene* sc, const pt_render_desc& rd, const pt_adapt
 // Set-up (kernel forms, queues, launch configuration) and one pass loop over a device pixel list and a sample range: pt_render runs the loop once over its
 // shard's pixels; with `adaptive` (pt_render_adaptive, its arguments checked) adaptive_rounds runs it once per round, over the film or (with `node`: worker
 // node_index of pt_render_adaptive_multi) over the desc's shard.  With `d_spectral` (pt_render_spectral: spectral_bins planes of width * height floats, its
-// arguments checked) every pass also adds its samples to the wavelength-binned film (include/pt_spectral.h); with both (pt_render_adaptive_spectral, one device) the
-// bins hold running sums, a continued pixel starting from its stored value, until k_adaptive_finish_spectral divides each pixel's by its own count.
+// arguments checked) every pass also adds its samples to the wavelength-binned film (include/pt_spectral.h); with both (pt_render_adaptive_spectral and its node
+// form) the bins hold running sums, a continued pixel starting from its stored value, until k_adaptive_finish_spectral divides each pixel's by its own count.
+// `shard_list` (the spectral node entries): the desc's shard as pth::shard_pixels lists it, computed by the caller, who packs the bins by it afterwards — the
+// device copy of it is then left in the scene's buf.pixels whichever kind of render this is.
 pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hipStream_t stream, pt_profile* profile, const pt_adaptive_desc* adaptive = nullptr,
-                      NodeRounds* node = nullptr, int node_index = 0, float* d_spectral = nullptr, uint32_t spectral_bins = 0) {
+                      NodeRounds* node = nullptr, int node_index = 0, float* d_spectral = nullptr, uint32_t spectral_bins = 0,
+                      const std::vector<uint32_t>* shard_list = nullptr) {
     if (!sc || !rdp || !d_film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    if (node && d_spectral) return fail(PT_ERR_UNSUPPORTED, "the spectral film of an adaptive render on several devices is not supported");
     pt_render_desc rd;
     std::string err;
     if (!pth::normalize_render_desc(*rdp, (uint32_t)sc->host.cameras.size(), &rd, &err)) return fail(PT_ERR_INVALID_ARGUMENT, err);
     HIP_TRY(hipSetDevice(sc->device));
 
-    std::vector<uint32_t> pixels = pth::shard_pixels(rd.width, rd.height, rd.tile_width, rd.tile_height, rd.shard_index, rd.shard_count);
+    std::vector<uint32_t> own_list;
+    if (!shard_list) own_list = pth::shard_pixels(rd.width, rd.height, rd.tile_width, rd.tile_height, rd.shard_index, rd.shard_count);
+    const std::vector<uint32_t>& pixels = shard_list ? *shard_list : own_list;
     const pt_tuning& tn = sc->tuning;
     uint32_t capacity = tuned(tn.batch_slots, 1u << 27);  // path slots per pass (128 Mi ~ 32 GB of queues of the 288 GB; tools/sweep.sh)
     if (capacity < 1024) capacity = 1024;
@@ -533,6 +549,8 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
         st = ensure_adaptive_buffers(sc, film_pixels);
         if (st != PT_OK) return st;
         if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(sc->adaptive.lists[0], pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
+        // (the rounds compact into lists[0] again: the list the caller packs by is kept where pt_render keeps its own)
+        if (shard_list && !pixels.empty()) HIP_TRY(hipMemcpyAsync(b.pixels, pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipMemsetAsync(sc->adaptive.stats, 0, sizeof(double) * 2 * film_pixels, stream));
         if (pixels.size() < film_pixels) HIP_TRY(hipMemsetAsync(sc->adaptive.counts, 0, sizeof(uint32_t) * film_pixels, stream));
     } else if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(b.pixels, pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
@@ -911,7 +929,7 @@ void pt_scene_destroy(pt_scene* sc) {
     hipSetDevice(sc->device);
     sc->buf.release();
     sc->adaptive.release();
-    hipFree(sc->d_blob); hipFree(sc->d_tex); hipFree(sc->film_cache); hipFree(sc->spectral_cache); hipFree(sc->project_cache);
+    hipFree(sc->d_blob); hipFree(sc->d_tex); hipFree(sc->film_cache); hipFree(sc->spectral_cache); hipFree(sc->project_cache); hipFree(sc->shard_packed);
     for (auto& e : sc->events) hipEventDestroy(e);
     delete sc;
 }
@@ -981,6 +999,7 @@ pt_status pt_render_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_s
     if (st != PT_OK) return fail(st, err);
     if (rdp->width == 0 || rdp->height == 0 || (uint64_t)rdp->width * rdp->height > 0xffffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and the film at most 2^32 - 1 pixels");
     sc->spectral_valid = false;   // (a spectral render starts: whatever the buffer held is no film from here on)
+    sc->spectral_shards.clear();
     HIP_TRY(hipSetDevice(sc->device));
     const size_t n_pixels = (size_t)rdp->width * rdp->height, film_bytes = sizeof(float) * 4 * n_pixels, spectral_bytes = sizeof(float) * sdp->bins * n_pixels;
     st = ensure_film_cache(sc, film_bytes);
@@ -1003,6 +1022,7 @@ pt_status pt_render_adaptive_spectral(pt_scene* sc, const pt_render_desc* rdp, c
     pt_status st = pth::check_adaptive_spectral_args(sc, rdp, adp, sdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, film, sample_counts, spectral, &rd, &ad, &err);
     if (st != PT_OK) return fail(st, err);
     sc->spectral_valid = false;   // (as in pt_render_spectral)
+    sc->spectral_shards.clear();
     HIP_TRY(hipSetDevice(sc->device));
     const size_t n_pixels = (size_t)rd.width * rd.height, spectral_bytes = sizeof(float) * sdp->bins * n_pixels;
     st = ensure_film_cache(sc, sizeof(float) * 4 * n_pixels);
@@ -1028,6 +1048,17 @@ pt_status pt_spectral_resident(pt_scene* sc, uint32_t* width, uint32_t* height, 
     return PT_OK;
 }
 
+static pt_status ensure_project_cache(pt_scene* sc, size_t bytes) {
+    if (sc->project_cache_bytes < bytes) {
+        if (sc->project_cache) hipFree(sc->project_cache);
+        sc->project_cache = nullptr; sc->project_cache_bytes = 0;
+        HIP_TRY(hipMalloc(&sc->project_cache, bytes));
+        sc->project_cache_bytes = bytes;
+    }
+    return PT_OK;
+}
+static pt_status project_resident_node(pt_scene* sc, uint32_t K, const float* matrix, float* out);
+
 // include/pt_spectral.h: pt_spectral_project's kernel over spectral_cache, on the stream the render ran on (the null stream), so the bins never cross the bus.
 pt_status pt_spectral_project_resident(pt_scene* sc, uint32_t K, const float* matrix, float* out) {
     if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
@@ -1036,15 +1067,12 @@ pt_status pt_spectral_project_resident(pt_scene* sc, uint32_t K, const float* ma
     std::string err;
     const pt_status st = pth::check_spectral_matrix(K, sc->spectral_bins, matrix, &err);
     if (st != PT_OK) return fail(st, err);
+    if (!sc->spectral_shards.empty()) return project_resident_node(sc, K, matrix, out);
     HIP_TRY(hipSetDevice(sc->device));
     const size_t n_pixels = (size_t)sc->spectral_width * sc->spectral_height;
     const size_t matrix_floats = (size_t)PT_SPECTRAL_MAX_RESPONSES * PT_SPECTRAL_MAX_BINS, bytes = sizeof(float) * (matrix_floats + (size_t)K * n_pixels);
-    if (sc->project_cache_bytes < bytes) {
-        if (sc->project_cache) hipFree(sc->project_cache);
-        sc->project_cache = nullptr; sc->project_cache_bytes = 0;
-        HIP_TRY(hipMalloc(&sc->project_cache, bytes));
-        sc->project_cache_bytes = bytes;
-    }
+    const pt_status cached = ensure_project_cache(sc, bytes);
+    if (cached != PT_OK) return cached;
     float* d_out = sc->project_cache + matrix_floats;
     hipStream_t stream = nullptr;
     HIP_TRY(hipMemcpyAsync(sc->project_cache, matrix, sizeof(float) * K * sc->spectral_bins, hipMemcpyHostToDevice, stream));
@@ -1116,6 +1144,7 @@ static void multi_release(MultiSetup& m) {
         if (m.films[v]) hipFree(m.films[v]);
     }
     for (size_t p = 0; p < m.comms.size(); ++p) if (m.comms[p]) { hipSetDevice(m.devices[p]); rccl().comm_destroy(m.comms[p]); }
+    for (float* h : m.staging) if (h) hipHostFree(h);
     m = MultiSetup();
 }
 
@@ -1127,6 +1156,7 @@ static pt_status multi_setup(pt_scene* sc, const std::vector<int>& devices, uint
     m.devices = devices; m.virt = virt; m.rccl = use_rccl; m.film_bytes = film_bytes;
     const size_t nv = devices.size() * virt;
     m.films.assign(nv, nullptr); m.streams.assign(nv, nullptr);
+    m.staging.assign(nv, nullptr); m.staging_bytes.assign(nv, 0);
     for (size_t v = 0; v < nv; ++v) {
         hipError_t e = hipSetDevice(devices[v / virt]);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&m.streams[v], hipStreamNonBlocking);
@@ -1252,14 +1282,100 @@ static std::string device_name(const Node& node, int v) {
     return "device " + std::to_string(node.devices[v / node.virt]) + (node.virt > 1 ? "." + std::to_string(v % node.virt) : "");
 }
 
-pt_status pt_render_multi(pt_scene* sc, const pt_render_desc* rdp, uint64_t device_mask, float* film, pt_profile* profile) {
-    if (!sc || !rdp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    if (rdp->width == 0 || rdp->height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
-    if (rdp->shard_count > 1) return fail(PT_ERR_INVALID_ARGUMENT, "pt_render_multi deals the tiles itself: shard_count must be 0");
+// The spectral film of a node call (pt_render_spectral_multi, pt_render_adaptive_spectral_multi).  The bins are never reduced: every
+// device packs the planes of its own tiles (k_spectral_pack), copies them to its pinned staging buffer and its host thread scatters them into the caller's
+// array; the packed planes stay on the device as its part of the scene's resident film.
+struct NodeSpectral {
+    uint32_t bins = 0;
+    size_t plane_pixels = 0;
+    float* host = nullptr;         // the caller's planes
+    std::vector<double> seconds;   // per worker: its pack, copy and scatter
+};
+// Part of the set-up: every device's pixel list (kept on its scene), full-size planes, packed planes and staging buffer, made once per size and kept.  A
+// shard without a pixel gets no buffer.  rd: normalised.
+static pt_status node_prepare_spectral(MultiSetup& m, const Node& node, const pt_render_desc& rd, uint32_t bins, float* spectral, NodeSpectral* ns) {
+    ns->bins = bins; ns->plane_pixels = (size_t)rd.width * rd.height; ns->host = spectral; ns->seconds.assign(node.n, 0.0);
+    for (int v = 0; v < node.n; ++v) {
+        pt_scene* s = node.scene_of[v];
+        s->shard_px = pth::shard_pixels(rd.width, rd.height, rd.tile_width, rd.tile_height, node.n > 1 ? (uint32_t)v : 0u, node.n > 1 ? (uint32_t)node.n : 0u);
+        HIP_TRY(hipSetDevice(node.devices[v / node.virt]));
+        const pt_status st = ensure_spectral_cache(s, sizeof(float) * bins * ns->plane_pixels);
+        if (st != PT_OK) return st;
+        const size_t packed_bytes = sizeof(float) * bins * s->shard_px.size();
+        if (s->shard_packed_bytes < packed_bytes) {
+            if (s->shard_packed) hipFree(s->shard_packed);
+            s->shard_packed = nullptr; s->shard_packed_bytes = 0;
+            HIP_TRY(hipMalloc(&s->shard_packed, packed_bytes));
+            s->shard_packed_bytes = packed_bytes;
+        }
+        if (m.staging_bytes[v] < packed_bytes) {
+            if (m.staging[v]) hipHostFree(m.staging[v]);
+            m.staging[v] = nullptr; m.staging_bytes[v] = 0;
+            HIP_TRY(hipHostMalloc(&m.staging[v], packed_bytes, hipHostMallocPortable));
+            m.staging_bytes[v] = packed_bytes;
+        }
+    }
+    return PT_OK;
+}
+// Worker v behind its render (the stream is idle: render_impl synchronised it): pack by the list render_impl left in buf.pixels, copy, scatter.  The shards
+// are disjoint and cover the film (every pixel is in exactly one list: tests/test_spectral_multi.py), so the threads never write the same float and the
+// caller's array needs no zeroing.
+static pt_status node_spectral_exchange(MultiSetup& m, const Node& node, NodeSpectral& ns, int v) {
+    pt_scene* s = node.scene_of[v];
+    const uint32_t n_own = (uint32_t)s->shard_px.size();
+    if (n_own == 0) return PT_OK;
+    const auto t = std::chrono::steady_clock::now();
+    HIP_TRY(ptk::launch_spectral_pack(ptk::spectral_pack_grid(s->num_cus, n_own), m.streams[v], s->spectral_cache, (uint32_t)ns.plane_pixels, s->buf.pixels, n_own, ns.bins,
+                                      s->shard_packed));
+    HIP_TRY(hipMemcpyAsync(m.staging[v], s->shard_packed, sizeof(float) * ns.bins * n_own, hipMemcpyDeviceToHost, m.streams[v]));
+    HIP_TRY(hipStreamSynchronize(m.streams[v]));
+    spectral_shard_scatter(m.staging[v], s->shard_px.data(), n_own, ns.bins, ns.host, ns.plane_pixels);
+    ns.seconds[v] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+    return PT_OK;
+}
+static double node_spectral_seconds(const NodeSpectral& ns) { return ns.seconds.empty() ? 0.0 : *std::max_element(ns.seconds.begin(), ns.seconds.end()); }
+// the node render has succeeded: the scene's resident film is the packed shards
+static void node_spectral_resident(pt_scene* sc, const Node& node, const pt_render_desc& rd, uint32_t bins) {
+    sc->spectral_shards = node.scene_of;
+    sc->spectral_width = rd.width; sc->spectral_height = rd.height; sc->spectral_bins = bins; sc->spectral_valid = true;
+}
+
+// pt_spectral_project_resident of a node-resident film: the matrix to every device that holds a shard, pt_spectral_project's kernel over the shard's packed
+// planes (plane stride n_own), K * n_own floats back per device, scattered by the rule the bins were scattered by.
+static pt_status project_resident_node(pt_scene* sc, uint32_t K, const float* matrix, float* out) {
+    DeviceGuard guard;
+    const size_t plane_pixels = (size_t)sc->spectral_width * sc->spectral_height, matrix_floats = (size_t)PT_SPECTRAL_MAX_RESPONSES * PT_SPECTRAL_MAX_BINS;
+    std::vector<std::vector<float>> planes(sc->spectral_shards.size());
+    for (size_t v = 0; v < sc->spectral_shards.size(); ++v) {
+        pt_scene* s = sc->spectral_shards[v];
+        const uint32_t n_own = (uint32_t)s->shard_px.size();
+        if (n_own == 0) continue;
+        HIP_TRY(hipSetDevice(s->device));
+        const pt_status st = ensure_project_cache(s, sizeof(float) * (matrix_floats + (size_t)K * n_own));
+        if (st != PT_OK) return st;
+        planes[v].resize((size_t)K * n_own);
+        float* d_out = s->project_cache + matrix_floats;
+        HIP_TRY(hipMemcpyAsync(s->project_cache, matrix, sizeof(float) * K * sc->spectral_bins, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(ptk::launch_spectral_project(ptk::spectral_project_grid(s->num_cus, n_own), nullptr, n_own, sc->spectral_bins, K, s->project_cache, s->shard_packed, d_out));
+        HIP_TRY(hipMemcpyAsync(planes[v].data(), d_out, sizeof(float) * K * n_own, hipMemcpyDeviceToHost, nullptr));
+    }
+    for (size_t v = 0; v < sc->spectral_shards.size(); ++v) {
+        pt_scene* s = sc->spectral_shards[v];
+        if (s->shard_px.empty()) continue;
+        HIP_TRY(hipSetDevice(s->device));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        spectral_shard_scatter(planes[v].data(), s->shard_px.data(), (uint32_t)s->shard_px.size(), K, out, plane_pixels);
+    }
+    return PT_OK;
+}
+
+// pt_render_multi and, with `sdp` (pt_render_spectral_multi; its arguments checked, rdp normalised), its spectral form
+static pt_status render_multi_impl(pt_scene* sc, const pt_render_desc* rdp, uint64_t device_mask, float* film, pt_profile* profile, const pt_spectral_desc* sdp,
+                                   float* spectral) {
     Node node;
     pt_status st = node_devices(sc, device_mask, &node);
     if (st != PT_OK) return st;
-    if (node.single(sc)) return pt_render(sc, rdp, film, profile);
+    if (node.single(sc)) return sdp ? pt_render_spectral(sc, rdp, sdp, film, spectral, profile) : pt_render(sc, rdp, film, profile);
 
     DeviceGuard guard;
     const auto t_entry = std::chrono::steady_clock::now();
@@ -1268,6 +1384,11 @@ pt_status pt_render_multi(pt_scene* sc, const pt_render_desc* rdp, uint64_t devi
     if (st != PT_OK) return st;
     MultiSetup& m = sc->multi;
     const int n = node.n;
+    NodeSpectral ns;
+    if (sdp) {
+        st = node_prepare_spectral(m, node, *rdp, sdp->bins, spectral, &ns);
+        if (st != PT_OK) return st;
+    }
     std::vector<pt_status> status(n, PT_OK);
     std::vector<std::string> errors(n);
     std::vector<pt_profile> profiles(n);
@@ -1277,7 +1398,10 @@ pt_status pt_render_multi(pt_scene* sc, const pt_render_desc* rdp, uint64_t devi
         if (hipSetDevice(node.devices[v / node.virt]) != hipSuccess) return bad(PT_ERR_DEVICE, "hipSetDevice failed");
         pt_render_desc rd = *rdp;
         if (n > 1) { rd.shard_index = (uint32_t)v; rd.shard_count = (uint32_t)n; }
-        pt_status s2 = render_impl(node.scene_of[v], &rd, m.films[v], m.streams[v], &profiles[v]);
+        pt_scene* s = node.scene_of[v];
+        pt_status s2 = sdp ? render_impl(s, &rd, m.films[v], m.streams[v], &profiles[v], nullptr, nullptr, 0, s->spectral_cache, sdp->bins, &s->shard_px)
+                           : render_impl(s, &rd, m.films[v], m.streams[v], &profiles[v]);
+        if (s2 == PT_OK && sdp) s2 = node_spectral_exchange(m, node, ns, v);
         if (s2 != PT_OK) bad(s2, g_error);   // (g_error is thread-local: carried back to the caller below)
     });
     for (int v = 0; v < n; ++v) if (status[v] != PT_OK) return fail(status[v], device_name(node, v) + ": " + errors[v]);
@@ -1293,23 +1417,39 @@ pt_status pt_render_multi(pt_scene* sc, const pt_render_desc* rdp, uint64_t devi
         node_profile(profiles, profile);
         profile->seconds = std::chrono::duration<double>(t1 - t0).count();
         profile->kernel_seconds[5] = std::chrono::duration<double>(t0 - t_entry).count();    // set-up (replicas, streams, films, communicator): ~0 on a repeated call
-        profile->kernel_seconds[6] = std::chrono::duration<double>(t1 - t_reduce).count();   // the film reduce
+        profile->kernel_seconds[6] = std::chrono::duration<double>(t1 - t_reduce).count() + node_spectral_seconds(ns);   // the film reduce (+ the longest pack, copy and scatter)
     }
+    if (sdp) node_spectral_resident(sc, node, *rdp, sdp->bins);
     return PT_OK;
 }
 
-pt_status pt_render_adaptive_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, uint64_t device_mask, float* film,
-                                   uint32_t* sample_counts, double* stats, pt_profile* profile) {
-    if (!sc || !rdp || !adp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+pt_status pt_render_multi(pt_scene* sc, const pt_render_desc* rdp, uint64_t device_mask, float* film, pt_profile* profile) {
+    if (!sc || !rdp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    if (rdp->width == 0 || rdp->height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
+    if (rdp->shard_count > 1) return fail(PT_ERR_INVALID_ARGUMENT, "pt_render_multi deals the tiles itself: shard_count must be 0");
+    return render_multi_impl(sc, rdp, device_mask, film, profile, nullptr, nullptr);
+}
+
+pt_status pt_render_spectral_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_spectral_desc* sdp, uint64_t device_mask, float* film, float* spectral,
+                                   pt_profile* profile) {
+    if (sc) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts; whatever it is refused for, no film is resident after it)
     pt_render_desc rd;
-    pt_adaptive_desc ad;
     std::string err;
-    pt_status st = pth::normalize_adaptive_desc(*rdp, *adp, sample_counts != nullptr, (uint32_t)sc->host.cameras.size(), &rd, &ad, &err);
+    const pt_status st = pth::check_spectral_multi_args(sc, rdp, sdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, film, spectral, &rd, &err);
     if (st != PT_OK) return fail(st, err);
+    return render_multi_impl(sc, &rd, device_mask, film, profile, sdp, spectral);
+}
+
+// pt_render_adaptive_multi (rdp, adp: the caller's; rd, ad: normalised from them) and, with `sdp` (pt_render_adaptive_spectral_multi; its arguments checked), its
+// spectral form
+static pt_status render_adaptive_multi_impl(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, const pt_render_desc& rd, const pt_adaptive_desc& ad,
+                                            uint64_t device_mask, float* film, uint32_t* sample_counts, double* stats, pt_profile* profile, const pt_spectral_desc* sdp,
+                                            float* spectral) {
     Node node;
-    st = node_devices(sc, device_mask, &node);
+    pt_status st = node_devices(sc, device_mask, &node);
     if (st != PT_OK) return st;
-    if (node.single(sc)) return pt_render_adaptive(sc, rdp, adp, film, sample_counts, stats, profile);
+    if (node.single(sc)) return sdp ? pt_render_adaptive_spectral(sc, rdp, adp, sdp, film, sample_counts, stats, spectral, profile)
+                                    : pt_render_adaptive(sc, rdp, adp, film, sample_counts, stats, profile);
 
     DeviceGuard guard;
     const auto t_entry = std::chrono::steady_clock::now();
@@ -1322,6 +1462,11 @@ pt_status pt_render_adaptive_multi(pt_scene* sc, const pt_render_desc* rdp, cons
     for (int v = 0; v < n; ++v) {   // (the adaptive buffers exist before the workers start: the exchange reads every device's image)
         HIP_TRY(hipSetDevice(node.devices[v / virt]));
         st = ensure_adaptive_buffers(node.scene_of[v], pixels);
+        if (st != PT_OK) return st;
+    }
+    NodeSpectral ns;
+    if (sdp) {
+        st = node_prepare_spectral(m, node, rd, sdp->bins, spectral, &ns);
         if (st != PT_OK) return st;
     }
     NodeRounds nr;
@@ -1367,7 +1512,10 @@ pt_status pt_render_adaptive_multi(pt_scene* sc, const pt_render_desc* rdp, cons
         pt_status s2 = hipSetDevice(node.devices[v / virt]) == hipSuccess ? PT_OK : fail(PT_ERR_DEVICE, "hipSetDevice failed");
         pt_render_desc rv = rd;
         if (n > 1) { rv.shard_index = (uint32_t)v; rv.shard_count = (uint32_t)n; }
-        if (s2 == PT_OK) s2 = render_impl(node.scene_of[v], &rv, m.films[v], m.streams[v], &profiles[v], &ad, &nr, v);
+        pt_scene* s = node.scene_of[v];
+        if (s2 == PT_OK) s2 = sdp ? render_impl(s, &rv, m.films[v], m.streams[v], &profiles[v], &ad, &nr, v, s->spectral_cache, sdp->bins, &s->shard_px)
+                                  : render_impl(s, &rv, m.films[v], m.streams[v], &profiles[v], &ad, &nr, v);
+        if (s2 == PT_OK && sdp) s2 = node_spectral_exchange(m, node, ns, v);
         if (s2 != PT_OK) nr.lock.stop(s2, device_name(node, v) + ": " + g_error);   // (a worker stopped by another's failure finds the first error kept)
     });
     if (nr.lock.failed) return fail(nr.lock.status, nr.lock.error);
@@ -1388,9 +1536,32 @@ pt_status pt_render_adaptive_multi(pt_scene* sc, const pt_render_desc* rdp, cons
         profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count();   // (the whole call: set-up, rounds, gather, read-backs)
         profile->kernel_launches[5] = profiles[0].kernel_launches[5];                                          // the rounds (every device ran them all)
         profile->kernel_seconds[5] = std::chrono::duration<double>(t0 - t_entry).count();                    // set-up: ~0 on a repeated call
-        profile->kernel_seconds[6] = nr.exchange_seconds + std::chrono::duration<double>(t_gathered - t_gather).count();   // the rounds' exchanges + the gather
+        profile->kernel_seconds[6] = nr.exchange_seconds + std::chrono::duration<double>(t_gathered - t_gather).count() + node_spectral_seconds(ns);   // the rounds' exchanges + the gather (+ the longest pack, copy and scatter)
     }
+    if (sdp) node_spectral_resident(sc, node, rd, sdp->bins);
     return PT_OK;
+}
+
+pt_status pt_render_adaptive_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, uint64_t device_mask, float* film,
+                                   uint32_t* sample_counts, double* stats, pt_profile* profile) {
+    if (!sc || !rdp || !adp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    pt_render_desc rd;
+    pt_adaptive_desc ad;
+    std::string err;
+    const pt_status st = pth::normalize_adaptive_desc(*rdp, *adp, sample_counts != nullptr, (uint32_t)sc->host.cameras.size(), &rd, &ad, &err);
+    if (st != PT_OK) return fail(st, err);
+    return render_adaptive_multi_impl(sc, rdp, adp, rd, ad, device_mask, film, sample_counts, stats, profile, nullptr, nullptr);
+}
+
+pt_status pt_render_adaptive_spectral_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, const pt_spectral_desc* sdp, uint64_t device_mask,
+                                            float* film, uint32_t* sample_counts, double* stats, float* spectral, pt_profile* profile) {
+    if (sc) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (as in pt_render_spectral_multi)
+    pt_render_desc rd;
+    pt_adaptive_desc ad;
+    std::string err;
+    const pt_status st = pth::check_adaptive_spectral_args(sc, rdp, adp, sdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, film, sample_counts, spectral, &rd, &ad, &err);
+    if (st != PT_OK) return fail(st, err);
+    return render_adaptive_multi_impl(sc, rdp, adp, rd, ad, device_mask, film, sample_counts, stats, profile, sdp, spectral);
 }
 
 pt_status pt_intersect(pt_scene* sc, size_t n, const float* origins, const float* directions, pt_hit* hits) {

@@ -245,6 +245,15 @@ pt_status check_adaptive_spectral_args(const void* scene, const pt_render_desc* 
     return normalize_adaptive_desc(*rd, *ad, sample_counts != nullptr, camera_count, rd_out, ad_out, error);
 }
 
+pt_status check_spectral_multi_args(const void* scene, const pt_render_desc* rd, const pt_spectral_desc* sd, uint32_t camera_count, const void* film, const void* spectral,
+                                    pt_render_desc* rd_out, std::string* error) {
+    const pt_status st = check_spectral_args(scene, rd, sd, film, spectral, error);
+    if (st != PT_OK) return st;
+    if (rd->shard_count != 0) { *error = "pt_render_spectral_multi deals the film's tiles itself: shard_count must be 0"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!normalize_render_desc(*rd, camera_count, rd_out, error)) return PT_ERR_INVALID_ARGUMENT;
+    return PT_OK;
+}
+
 pt_status check_denoise_spectral_args(const pt_denoise_desc* in, uint32_t bins, const void* film, const uint32_t* sample_counts, const void* stats, const float* guides,
                                       const void* spectral, const void* out_film, const void* out_spectral, pt_denoise_desc* out, std::string* error) {
     if (bins == 0) { *error = "bins must be positive"; return PT_ERR_INVALID_ARGUMENT; }

@@ -62,6 +62,11 @@ pt_status spectral_bin_centres(const pt_render_desc* rd, const pt_spectral_desc*
 pt_status check_adaptive_spectral_args(const void* scene, const pt_render_desc* rd, const pt_adaptive_desc* ad, const pt_spectral_desc* sd, uint32_t camera_count,
                                        const void* film, const void* sample_counts, const void* spectral, pt_render_desc* rd_out, pt_adaptive_desc* ad_out,
                                        std::string* error);
+// pt_render_spectral_multi's arguments: check_spectral_args' conditions, then no shard in the desc (the call deals the tiles itself) and
+// normalize_render_desc's conditions, each with its own message; *rd_out as normalize_render_desc leaves it.  camera_count is what the caller read from the
+// scene.  pt_render_adaptive_spectral_multi takes check_adaptive_spectral_args as it is: that refuses a shard too (normalize_adaptive_desc).
+pt_status check_spectral_multi_args(const void* scene, const pt_render_desc* rd, const pt_spectral_desc* sd, uint32_t camera_count, const void* film, const void* spectral,
+                                    pt_render_desc* rd_out, std::string* error);
 // pt_denoise_spectral's arguments: bins in 1..PT_SPECTRAL_MAX_BINS and the two spectral pointers, then normalize_denoise_desc and check_denoise_inputs
 pt_status check_denoise_spectral_args(const pt_denoise_desc* in, uint32_t bins, const void* film, const uint32_t* sample_counts, const void* stats, const float* guides,
                                       const void* spectral, const void* out_film, const void* out_spectral, pt_denoise_desc* out, std::string* error);

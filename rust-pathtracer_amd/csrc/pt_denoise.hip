@@ -15,8 +15,10 @@
 
 #include "pt_kernels.h"   /* first, as in pt_engine.hip: stage_generate is compiled as the render's own first stage is */
 #include "../../include/pt_denoise.h"
+#include "../../include/pt_spectral.h"
 #include "pt_denoise_launch.h"
 #include "pt_denoise_rules.h"
+#include "pt_denoise_spectral_albedo_rules.h"
 #include "pt_error.h"
 #include "pt_plan.h"
 
@@ -201,6 +203,83 @@ __global__ void __launch_bounds__(kLine) k_dn_finish_albedo(uint32_t n, const fl
     variance[i] = o.v;
 }
 
+// ---------------------------------------------------------------------------------------------- filter, with the bins
+// The gather is k_dn_gather's tile (32x8 pixels, one pixel per lane) with the taps kept: the edge-stopping weight of a tap costs about 200 vector instructions
+// and depends on the colour and the guides alone, so a lane computes its 25 weights once — the 5x5 loops are fully unrolled, every index is static, and the
+// weights and the 25-bit mask of the taps taken stay in registers — writes the colour, and then runs the 25 taps again per chunk of 8 bins: one load, one
+// multiply and one add per tap and bin.  Neighbouring lanes read neighbouring pixels of one plane, so every load is a coalesced row segment.  A tap that is
+// not taken reads the lane's own pixel and its sum is selected away: no branch in the bin loop, and the loads of a chunk are independent of each other.
+// The colour and the bins share one kernel; the alternative — the 25 weights through a 100-byte-per-pixel buffer to a second kernel — was not built: it adds
+// 200 bytes of traffic per pixel and pass to save registers this kernel has to spare (DESIGN.md section 14 has the counts).
+//
+// the pass's inputs in global memory: the film filter's planes and the bins.  A pixel index is a uint32_t as above: normalize_denoise_desc (through
+// check_denoise_spectral_args) refuses width x height above 2^31 - 1 before anything is launched; the plane offset b * plane is formed in size_t.
+struct SpectralSource {
+    const float4* color_; const float4* geo_; const float* tent_; const uint8_t* flags_; const float* bins_; uint32_t width, plane;
+    __device__ uint32_t at(int x, int y) const { return (uint32_t)y * width + (uint32_t)x; }
+    __device__ uint32_t flags(int x, int y) const { return flags_[at(x, y)]; }
+    __device__ DnColor color(int x, int y) const { const float4 c = color_[at(x, y)]; return DnColor{c.x, c.y, c.z, c.w}; }
+    __device__ DnGeo geo(int x, int y) const { const float4 g = geo_[at(x, y)]; return DnGeo{g.x, g.y, g.z, g.w}; }
+    __device__ float tent(int x, int y) const { return tent_[at(x, y)]; }
+    __device__ float bin(uint32_t b, int x, int y) const { return bins_[(size_t)b * plane + at(x, y)]; }
+};
+
+// behind k_dn_prepare: flags |= DN_DEAD where a bin of the pixel is not finite
+__global__ void __launch_bounds__(kLine) k_dn_spectral_dead(uint32_t n, uint32_t bins, const float* __restrict__ spectral, uint8_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t dead = dn_spectral_dead(bins, [&](uint32_t b) { return spectral[(size_t)b * n + i]; });
+    if (dead) flags[i] = (uint8_t)(flags[i] | dead);
+}
+
+// one a-trous pass: out = c_{i+1}, v_{i+1} (k_dn_gather's, bit for bit) and spectral_out = s_{b,i+1} for every bin.  The outputs must not alias the inputs.
+__global__ void __launch_bounds__(kTileW * kTileH, 4) k_dn_gather_spectral(DnParams P, int step, SpectralSource src, const float2* __restrict__ grad, uint32_t bins,
+                                                                        float4* __restrict__ out, float* __restrict__ spectral_out) {
+    const int x = blockIdx.x * kTileW + threadIdx.x, y = blockIdx.y * kTileH + threadIdx.y;
+    if (x >= (int)P.width || y >= (int)P.height) return;
+    const uint32_t i = (uint32_t)y * P.width + (uint32_t)x;
+    const float2 g = grad[i];
+    DnTaps taps;
+    const DnColor o = dn_gather_pixel_taps(src, P, step, x, y, g.x, g.y, &taps);
+    out[i] = make_float4(o.x, o.y, o.z, o.v);
+    float* px = spectral_out + i;
+    const uint32_t plane = src.plane;
+    dn_gather_pixel_bins(src, step, x, y, taps, bins, [&](uint32_t b, float v) { px[(size_t)b * plane] = v; });
+}
+
+// The bins' demodulation, behind k_dn_prepare(_albedo).  One lane per pixel, looping over the planes (neighbouring lanes are neighbouring pixels of one
+// plane): raw -> out (which must not be raw), the dead bit into flags, and a pixel that is dead through its bins alone gets k_dn_prepare's colour of a dead
+// pixel back (k_dn_prepare_albedo had divided it).  HAS_A false: no per-bin albedo, the bins are copied and tested.
+template <bool HAS_A>
+__global__ void __launch_bounds__(kLine) k_dn_demodulate_bins(uint32_t n, uint32_t bins, const float* __restrict__ raw, const float* __restrict__ bin_albedo,
+                                                             const float4* __restrict__ film, const uint32_t* __restrict__ counts, const double2* __restrict__ stats,
+                                                             float* __restrict__ out, float4* __restrict__ color, uint8_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t f = flags[i];
+    const uint32_t dead = dn_bins_demodulate_pixel(bins, f, [&](uint32_t b) { return raw[(size_t)b * n + i]; },
+                                                   [&](uint32_t b) { return HAS_A ? bin_albedo[(size_t)b * n + i] : 1.0f; },
+                                                   [&](uint32_t b, float v) { out[(size_t)b * n + i] = v; });
+    if (dead && !(f & DN_DEAD)) {
+        const float4 c = film[i];
+        const double2 s = stats[i];
+        const DnColor o = dn_bins_dead_color(c.x, c.y, c.z, counts[i], s.x, s.y);
+        color[i] = make_float4(o.x, o.y, o.z, o.v);
+        flags[i] = (uint8_t)(f | dead);
+    }
+}
+// after the last pass, over bins x n_pixels values, in place; a dead pixel keeps what the passes copied through: its input bits
+__global__ void __launch_bounds__(kLine) k_dn_remodulate_bins(size_t total, uint32_t n, const float* __restrict__ bin_albedo, const uint8_t* __restrict__ flags,
+                                                             float* __restrict__ bins) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    if (flags[i % n] & DN_DEAD) return;
+    bins[i] = dn_bin_remodulate(bins[i], bin_albedo[i]);
+}
+
+int line_grid(size_t n) { return (int)((n + kLine - 1) / kLine); }
+
+// ---------------------------------------------------------------------------------------------- the filter's driver
 struct Dev {
     void* p = nullptr;
     Dev() = default;
@@ -211,7 +290,86 @@ struct Dev {
     template <typename T> T* as() const { return static_cast<T*>(p); }
 };
 
-int line_grid(size_t n) { return (int)((n + kLine - 1) / kLine); }
+// host arrays of one call: width x height pixels, the bins and bin_albedo `bins` planes of them
+struct DnHost {
+    const float* film; const uint32_t* counts; const double* stats; const float* guides;   // required
+    const float* albedo; uint32_t bins; const float* spectral; const float* bin_albedo;    // optional: null (bins 0) when absent; bin_albedo only with spectral
+    float* out_film; float* out_spectral; float* out_variance;                             // out_spectral with spectral; out_variance may be null
+};
+
+// The filter behind the four entries, which have checked their arguments: `d` is the normalised descriptor.  What runs depends on which inputs are present
+// alone.  The launches go to the null stream, with one synchronise before the read-backs.
+pt_status dn_filter(const pt_denoise_desc& d, const DnHost& h) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return dfail(PT_ERR_NO_DEVICE, "no HIP device available: the product path has no CPU fallback");
+    if (d.device >= (uint32_t)ndev) return dfail(PT_ERR_INVALID_ARGUMENT, "device out of range");
+#define DN_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return dfail(e_ == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+    DN_TRY(hipSetDevice((int)d.device));
+    const size_t np = (size_t)d.width * d.height, bin_bytes = sizeof(float) * h.bins * np;
+    const uint32_t n = (uint32_t)np;
+    Dev d_film, d_counts, d_stats, d_guides, d_color[2], d_geo, d_tent, d_flags, d_grad, d_var, d_bins[2], d_albedo, d_bin_albedo;
+    DN_TRY(d_film.alloc(16 * np)); DN_TRY(d_counts.alloc(4 * np)); DN_TRY(d_stats.alloc(16 * np)); DN_TRY(d_guides.alloc(16 * np));
+    DN_TRY(d_color[0].alloc(16 * np)); DN_TRY(d_color[1].alloc(16 * np)); DN_TRY(d_geo.alloc(16 * np)); DN_TRY(d_tent.alloc(4 * np));
+    DN_TRY(d_flags.alloc(np)); DN_TRY(d_grad.alloc(8 * np)); DN_TRY(d_var.alloc(4 * np));
+    if (h.spectral) { DN_TRY(d_bins[0].alloc(bin_bytes)); DN_TRY(d_bins[1].alloc(bin_bytes)); }
+    DN_TRY(hipMemcpy(d_film.p, h.film, 16 * np, hipMemcpyHostToDevice));
+    DN_TRY(hipMemcpy(d_counts.p, h.counts, 4 * np, hipMemcpyHostToDevice));
+    DN_TRY(hipMemcpy(d_stats.p, h.stats, 16 * np, hipMemcpyHostToDevice));
+    DN_TRY(hipMemcpy(d_guides.p, h.guides, 16 * np, hipMemcpyHostToDevice));
+    // the bins are divided, or copied through the dead test of the division, where an albedo is given: from the second ping-pong buffer, which is free until
+    // the first pass writes it, into the first.  With no albedo they are tested where they lie.
+    const bool demodulate = h.spectral && (h.albedo || h.bin_albedo);
+    if (h.spectral) DN_TRY(hipMemcpy(d_bins[demodulate ? 1 : 0].p, h.spectral, bin_bytes, hipMemcpyHostToDevice));
+    if (h.albedo) { DN_TRY(d_albedo.alloc(16 * np)); DN_TRY(hipMemcpy(d_albedo.p, h.albedo, 16 * np, hipMemcpyHostToDevice)); }
+    if (h.bin_albedo) { DN_TRY(d_bin_albedo.alloc(bin_bytes)); DN_TRY(hipMemcpy(d_bin_albedo.p, h.bin_albedo, bin_bytes, hipMemcpyHostToDevice)); }
+    DnParams P;
+    P.width = d.width; P.height = d.height; P.sigma_l = d.sigma_luminance; P.sigma_z = d.sigma_depth; P.normal_squarings = d.normal_power_log2;
+    const dim3 line(line_grid(np)), line_block(kLine);
+    if (h.albedo)
+        hipLaunchKernelGGL(k_dn_prepare_albedo, line, line_block, 0, 0, P, d_film.as<float4>(), d_counts.as<uint32_t>(), d_stats.as<double2>(), d_guides.as<float4>(),
+                           d_albedo.as<float4>(), d_color[0].as<float4>(), d_geo.as<float4>(), d_flags.as<uint8_t>(), d_grad.as<float2>());
+    else
+        hipLaunchKernelGGL(k_dn_prepare, line, line_block, 0, 0, P, d_film.as<float4>(), d_counts.as<uint32_t>(), d_stats.as<double2>(), d_guides.as<float4>(),
+                           d_color[0].as<float4>(), d_geo.as<float4>(), d_flags.as<uint8_t>(), d_grad.as<float2>());
+    if (demodulate) {
+        const auto k = h.bin_albedo ? k_dn_demodulate_bins<true> : k_dn_demodulate_bins<false>;
+        hipLaunchKernelGGL(k, line, line_block, 0, 0, n, h.bins, d_bins[1].as<float>(), d_bin_albedo.as<float>(), d_film.as<float4>(), d_counts.as<uint32_t>(),
+                           d_stats.as<double2>(), d_bins[0].as<float>(), d_color[0].as<float4>(), d_flags.as<uint8_t>());
+    } else if (h.spectral) {
+        hipLaunchKernelGGL(k_dn_spectral_dead, line, line_block, 0, 0, n, h.bins, d_bins[0].as<float>(), d_flags.as<uint8_t>());
+    }
+    const dim3 grid((d.width + kTileW - 1) / kTileW, (d.height + kTileH - 1) / kTileH), block(kTileW, kTileH);
+    int cur = 0;
+    for (uint32_t i = 0; i < d.iterations; ++i) {
+        const int step = 1 << i;
+        const DnBuffers b{d_color[cur].as<float4>(), d_geo.as<float4>(), d_tent.as<float>(), d_flags.as<uint8_t>(), d_grad.as<float2>()};
+        float4* out = d_color[cur ^ 1].as<float4>();
+        hipLaunchKernelGGL(k_dn_tent, grid, block, 0, 0, P, b, d_tent.as<float>());
+        if (h.spectral) {
+            const SpectralSource src{b.color, b.geo, b.tent, b.flags, d_bins[cur].as<float>(), d.width, n};
+            hipLaunchKernelGGL(k_dn_gather_spectral, grid, block, 0, 0, P, step, src, b.grad, h.bins, out, d_bins[cur ^ 1].as<float>());
+        } else {
+            hipLaunchKernelGGL(k_dn_gather, grid, block, 0, 0, P, step, b, out);
+        }
+        cur ^= 1;
+    }
+    if (h.albedo)
+        hipLaunchKernelGGL(k_dn_finish_albedo, line, line_block, 0, 0, n, d_color[cur].as<float4>(), d_albedo.as<float4>(), d_flags.as<uint8_t>(), d_film.as<float4>(),
+                           d_var.as<float>());
+    else
+        hipLaunchKernelGGL(k_dn_finish, line, line_block, 0, 0, n, d_color[cur].as<float4>(), d_film.as<float4>(), d_var.as<float>());
+    if (h.bin_albedo) {
+        const size_t total = (size_t)h.bins * np;
+        hipLaunchKernelGGL(k_dn_remodulate_bins, dim3(line_grid(total)), line_block, 0, 0, total, n, d_bin_albedo.as<float>(), d_flags.as<uint8_t>(), d_bins[cur].as<float>());
+    }
+    DN_TRY(hipGetLastError());
+    DN_TRY(hipDeviceSynchronize());
+    DN_TRY(hipMemcpy(h.out_film, d_film.p, 16 * np, hipMemcpyDeviceToHost));
+    if (h.spectral) DN_TRY(hipMemcpy(h.out_spectral, d_bins[cur].p, bin_bytes, hipMemcpyDeviceToHost));
+    if (h.out_variance) DN_TRY(hipMemcpy(h.out_variance, d_var.p, 4 * np, hipMemcpyDeviceToHost));
+#undef DN_TRY
+    return PT_OK;
+}
 
 }  // namespace
 
@@ -245,31 +403,6 @@ void albedo_basis(float wavelength_lo, float wavelength_hi, DnAlbedoBasis* basis
 }
 
 
-// the filter's kernels for pt_denoise_spectral and pt_denoise_spectral_albedo (pt_denoise_spectral.hip, pt_denoise_spectral_albedo.hip), unchanged
-void launch_dn_prepare(const DnParams& P, const float* film, const uint32_t* counts, const double* stats, const float* guides, float* color, float* geo, uint8_t* flags,
-                       float* grad) {
-    hipLaunchKernelGGL(k_dn_prepare, dim3(line_grid((size_t)P.width * P.height)), dim3(kLine), 0, 0, P, reinterpret_cast<const float4*>(film), counts,
-                       reinterpret_cast<const double2*>(stats), reinterpret_cast<const float4*>(guides), reinterpret_cast<float4*>(color), reinterpret_cast<float4*>(geo), flags,
-                       reinterpret_cast<float2*>(grad));
-}
-void launch_dn_prepare_albedo(const DnParams& P, const float* film, const uint32_t* counts, const double* stats, const float* guides, const float* albedo, float* color,
-                              float* geo, uint8_t* flags, float* grad) {
-    hipLaunchKernelGGL(k_dn_prepare_albedo, dim3(line_grid((size_t)P.width * P.height)), dim3(kLine), 0, 0, P, reinterpret_cast<const float4*>(film), counts,
-                       reinterpret_cast<const double2*>(stats), reinterpret_cast<const float4*>(guides), reinterpret_cast<const float4*>(albedo),
-                       reinterpret_cast<float4*>(color), reinterpret_cast<float4*>(geo), flags, reinterpret_cast<float2*>(grad));
-}
-void launch_dn_tent(const DnParams& P, const float* color, const float* geo, const uint8_t* flags, float* tent) {
-    const DnBuffers b{reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(geo), tent, flags, nullptr};
-    hipLaunchKernelGGL(k_dn_tent, dim3((P.width + kTileW - 1) / kTileW, (P.height + kTileH - 1) / kTileH), dim3(kTileW, kTileH), 0, 0, P, b, tent);
-}
-void launch_dn_finish(uint32_t n_pixels, const float* color, float* film, float* variance) {
-    hipLaunchKernelGGL(k_dn_finish, dim3(line_grid(n_pixels)), dim3(kLine), 0, 0, n_pixels, reinterpret_cast<const float4*>(color), reinterpret_cast<float4*>(film), variance);
-}
-void launch_dn_finish_albedo(uint32_t n_pixels, const float* color, const float* albedo, const uint8_t* flags, float* film, float* variance) {
-    hipLaunchKernelGGL(k_dn_finish_albedo, dim3(line_grid(n_pixels)), dim3(kLine), 0, 0, n_pixels, reinterpret_cast<const float4*>(color),
-                       reinterpret_cast<const float4*>(albedo), flags, reinterpret_cast<float4*>(film), variance);
-}
-
 }  // namespace ptk
 
 extern "C" pt_status pt_albedo_basis(const pt_render_desc* desc, float* lambda, float* xyz) {
@@ -296,48 +429,24 @@ extern "C" pt_status pt_denoise_film_albedo(const pt_denoise_desc* desc, const f
     if (st == PT_OK) st = pth::check_denoise_inputs(d, sample_counts, guides, &err);
     if (st == PT_OK && albedo) st = pth::check_denoise_albedo(d, albedo, &err);
     if (st != PT_OK) return dfail(st, err);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return dfail(PT_ERR_NO_DEVICE, "no HIP device available: the product path has no CPU fallback");
-    if (d.device >= (uint32_t)ndev) return dfail(PT_ERR_INVALID_ARGUMENT, "device out of range");
-#define DN_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return dfail(e_ == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
-    DN_TRY(hipSetDevice((int)d.device));
-    const size_t np = (size_t)d.width * d.height;
-    Dev d_film, d_counts, d_stats, d_guides, d_color[2], d_geo, d_tent, d_flags, d_grad, d_var, d_albedo;
-    DN_TRY(d_film.alloc(16 * np)); DN_TRY(d_counts.alloc(4 * np)); DN_TRY(d_stats.alloc(16 * np)); DN_TRY(d_guides.alloc(16 * np));
-    DN_TRY(d_color[0].alloc(16 * np)); DN_TRY(d_color[1].alloc(16 * np)); DN_TRY(d_geo.alloc(16 * np)); DN_TRY(d_tent.alloc(4 * np));
-    DN_TRY(d_flags.alloc(np)); DN_TRY(d_grad.alloc(8 * np)); DN_TRY(d_var.alloc(4 * np));
-    DN_TRY(hipMemcpy(d_film.p, film, 16 * np, hipMemcpyHostToDevice));
-    DN_TRY(hipMemcpy(d_counts.p, sample_counts, 4 * np, hipMemcpyHostToDevice));
-    DN_TRY(hipMemcpy(d_stats.p, stats, 16 * np, hipMemcpyHostToDevice));
-    DN_TRY(hipMemcpy(d_guides.p, guides, 16 * np, hipMemcpyHostToDevice));
-    if (albedo) { DN_TRY(d_albedo.alloc(16 * np)); DN_TRY(hipMemcpy(d_albedo.p, albedo, 16 * np, hipMemcpyHostToDevice)); }
-    DnParams P;
-    P.width = d.width; P.height = d.height; P.sigma_l = d.sigma_luminance; P.sigma_z = d.sigma_depth; P.normal_squarings = d.normal_power_log2;
-    if (albedo)
-        hipLaunchKernelGGL(k_dn_prepare_albedo, dim3(line_grid(np)), dim3(kLine), 0, 0, P, d_film.as<float4>(), d_counts.as<uint32_t>(), d_stats.as<double2>(), d_guides.as<float4>(),
-                           d_albedo.as<float4>(), d_color[0].as<float4>(), d_geo.as<float4>(), d_flags.as<uint8_t>(), d_grad.as<float2>());
-    else
-        hipLaunchKernelGGL(k_dn_prepare, dim3(line_grid(np)), dim3(kLine), 0, 0, P, d_film.as<float4>(), d_counts.as<uint32_t>(), d_stats.as<double2>(), d_guides.as<float4>(),
-                           d_color[0].as<float4>(), d_geo.as<float4>(), d_flags.as<uint8_t>(), d_grad.as<float2>());
-    const dim3 grid((d.width + kTileW - 1) / kTileW, (d.height + kTileH - 1) / kTileH), block(kTileW, kTileH);
-    int cur = 0;
-    for (uint32_t i = 0; i < d.iterations; ++i) {
-        const int step = 1 << i;
-        const DnBuffers b{d_color[cur].as<float4>(), d_geo.as<float4>(), d_tent.as<float>(), d_flags.as<uint8_t>(), d_grad.as<float2>()};
-        float4* out = d_color[cur ^ 1].as<float4>();
-        hipLaunchKernelGGL(k_dn_tent, grid, block, 0, 0, P, b, d_tent.as<float>());
-        hipLaunchKernelGGL(k_dn_gather, grid, block, 0, 0, P, step, b, out);
-        cur ^= 1;
-    }
-    if (albedo)
-        hipLaunchKernelGGL(k_dn_finish_albedo, dim3(line_grid(np)), dim3(kLine), 0, 0, (uint32_t)np, d_color[cur].as<float4>(), d_albedo.as<float4>(), d_flags.as<uint8_t>(),
-                           d_film.as<float4>(), d_var.as<float>());
-    else
-        hipLaunchKernelGGL(k_dn_finish, dim3(line_grid(np)), dim3(kLine), 0, 0, (uint32_t)np, d_color[cur].as<float4>(), d_film.as<float4>(), d_var.as<float>());
-    DN_TRY(hipGetLastError());
-    DN_TRY(hipDeviceSynchronize());
-    DN_TRY(hipMemcpy(out_film, d_film.p, 16 * np, hipMemcpyDeviceToHost));
-    if (out_variance) DN_TRY(hipMemcpy(out_variance, d_var.p, 4 * np, hipMemcpyDeviceToHost));
-#undef DN_TRY
-    return PT_OK;
+    return dn_filter(d, DnHost{film, sample_counts, stats, guides, albedo, 0u, nullptr, nullptr, out_film, nullptr, out_variance});
+}
+
+extern "C" pt_status pt_denoise_spectral(const pt_denoise_desc* desc, uint32_t bins, const float* film, const uint32_t* sample_counts, const double* stats, const float* guides,
+                                         const float* spectral, float* out_film, float* out_spectral, float* out_variance) {
+    pt_denoise_desc d;
+    std::string err;
+    const pt_status st = pth::check_denoise_spectral_args(desc, bins, film, sample_counts, stats, guides, spectral, out_film, out_spectral, &d, &err);
+    if (st != PT_OK) return dfail(st, err);
+    return dn_filter(d, DnHost{film, sample_counts, stats, guides, nullptr, bins, spectral, nullptr, out_film, out_spectral, out_variance});
+}
+
+extern "C" pt_status pt_denoise_spectral_albedo(const pt_denoise_desc* desc, uint32_t bins, const float* film, const uint32_t* sample_counts, const double* stats,
+                                                const float* guides, const float* albedo, const float* spectral, const float* bin_albedo, float* out_film,
+                                                float* out_spectral, float* out_variance) {
+    pt_denoise_desc d;
+    std::string err;
+    const pt_status st = pth::check_denoise_spectral_albedo_args(desc, bins, film, sample_counts, stats, guides, albedo, spectral, bin_albedo, out_film, out_spectral, &d, &err);
+    if (st != PT_OK) return dfail(st, err);
+    return dn_filter(d, DnHost{film, sample_counts, stats, guides, albedo, bins, spectral, bin_albedo, out_film, out_spectral, out_variance});
 }

@@ -27,17 +27,5 @@ void launch_guide_fold_albedo(uint32_t n_pixels, const pt_hit* hits, ptd::DnGuid
 // launch_guide_finish plus albedo[p] = albedo_sums[p] / samples (W = 0)
 void launch_guide_finish_albedo(uint32_t n_pixels, const ptd::DnGuideSum* sums, const float* albedo_sums, uint32_t samples, float* guides_xyzw, float* albedo_xyzw);
 
-// The filter's own kernels, for pt_denoise_spectral (pt_denoise_spectral.hip): k_dn_prepare (color = film xyz + the variance of the mean, geo = unit normal +
-// depth, flags = DN_DEAD | DN_SKY, grad = the depth gradient; float4, float4, byte and float2 per pixel), k_dn_tent (the pass's 3x3-filtered variance of the
-// live pixels) and k_dn_finish (film = color xyz, W = 0; variance = color w).
-void launch_dn_prepare(const ptd::DnParams& P, const float* film, const uint32_t* counts, const double* stats, const float* guides, float* color, float* geo,
-                       uint8_t* flags, float* grad);
-// k_dn_prepare_albedo and k_dn_finish_albedo, for pt_denoise_spectral_albedo: the film demodulated by `albedo` (float4 per pixel) and multiplied back
-void launch_dn_prepare_albedo(const ptd::DnParams& P, const float* film, const uint32_t* counts, const double* stats, const float* guides, const float* albedo, float* color,
-                              float* geo, uint8_t* flags, float* grad);
-void launch_dn_finish_albedo(uint32_t n_pixels, const float* color, const float* albedo, const uint8_t* flags, float* film, float* variance);
-void launch_dn_tent(const ptd::DnParams& P, const float* color, const float* geo, const uint8_t* flags, float* tent);
-void launch_dn_finish(uint32_t n_pixels, const float* color, float* film, float* variance);
-
 }  // namespace ptk
 #endif

@@ -106,17 +106,43 @@ PT_HD float dn_tap_weight(const DnParams& P, int dx, int dy, int step, uint32_t 
     return ((dn_kernel(dx) * dn_kernel(dy)) * e) * l;
 }
 
+enum { DN_TAPS = 25, DN_CENTRE_TAP = 12 };
+
+// the taps of one pixel in one pass, for the filters that average more planes with them (pt_denoise_spectral_rules.h): tap t = (dy + 2) * 5 + (dx + 2) is
+// taken when bit t of `mask` is set, with the weight w[t] (0.0f for a tap not taken: never used); sw = the sum of the taken weights in tap order.  A dead
+// pixel takes no tap (mask 0); a live one always takes its centre.
+struct DnTaps { float w[DN_TAPS]; float sw; uint32_t mask; };
+
 // c_{i+1}(p), v_{i+1}(p): the 25 taps in dy-outer, dx-inner order; a tap outside the film, dead, or sky against surface is skipped; a dead p is
-// copied through
-template <class S>
-PT_HD DnColor dn_gather_pixel(const S& src, const DnParams& P, int step, int x, int y, float grad_x, float grad_y) {
+// copied through.  This is the one text of the gather: dn_gather_pixel, below, is it with KEEP false (T is not looked at); with KEEP, the default, the
+// taps are also recorded in *T, and the colour is the same bit for bit.  With KEEP both loops are unrolled on the device, so that every index into T->w
+// is static and the weights stay in registers (a loop left rolled sends them to scratch); without it the loops stay rolled, as the compiler leaves them:
+// a tap is some 200 instructions.  The pragma is a request, so after any edit of this function re-run tools/resource_usage.py pt_denoise.hip: scratch 0
+// and no spills in k_dn_gather_spectral is the check.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DN_UNROLL_TAPS _Pragma("clang loop unroll_count(KEEP ? 5 : 1)")   /* (KEEP: the template argument below) */
+#else
+#define DN_UNROLL_TAPS
+#endif
+template <bool KEEP = true, class S>
+PT_HD DnColor dn_gather_pixel_taps(const S& src, const DnParams& P, int step, int x, int y, float grad_x, float grad_y, DnTaps* T) {
     const uint32_t fp = src.flags(x, y);
     const DnColor cp = src.color(x, y);
+    if constexpr (KEEP) {
+        T->mask = 0u; T->sw = 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int t = 0; t < DN_TAPS; ++t) T->w[t] = 0.0f;
+    }
     if (fp & DN_DEAD) return cp;
     const DnGeo gp = src.geo(x, y);
     const float tp = src.tent(x, y);
     float sw = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f, sv = 0.0f;
-    for (int dy = -2; dy <= 2; ++dy)
+    [[maybe_unused]] uint32_t mask = 0u;
+    DN_UNROLL_TAPS
+    for (int dy = -2; dy <= 2; ++dy) {
+        DN_UNROLL_TAPS
         for (int dx = -2; dx <= 2; ++dx) {
             const int qx = x + dx * step, qy = y + dy * step;
             if (qx < 0 || qy < 0 || qx >= (int)P.width || qy >= (int)P.height) continue;
@@ -131,13 +157,25 @@ PT_HD DnColor dn_gather_pixel(const S& src, const DnParams& P, int step, int x, 
                 cq = src.color(qx, qy);
                 w = dn_tap_weight(P, dx, dy, step, fp & DN_SKY, gp, grad_x, grad_y, cp.y, tp, src.geo(qx, qy), cq.y, src.tent(qx, qy));
             }
+            if constexpr (KEEP) {
+                const int t = (dy + 2) * 5 + (dx + 2);
+                T->w[t] = w;
+                mask |= 1u << t;
+            }
             sw = sw + w;
             sx = sx + w * cq.x; sy = sy + w * cq.y; sz = sz + w * cq.z;
             sv = sv + (w * w) * cq.v;
         }
+    }
+    if constexpr (KEEP) { T->mask = mask; T->sw = sw; }
     DnColor o;
     o.x = sx / sw; o.y = sy / sw; o.z = sz / sw; o.v = sv / (sw * sw);
     return o;
+}
+#undef DN_UNROLL_TAPS
+template <class S>
+PT_HD DnColor dn_gather_pixel(const S& src, const DnParams& P, int step, int x, int y, float grad_x, float grad_y) {
+    return dn_gather_pixel_taps<false>(src, P, step, x, y, grad_x, grad_y, nullptr);
 }
 
 // ---- albedo: the first-hit reflectance of a Lambertian surface as XYZ factors, and the film divided by it before the passes

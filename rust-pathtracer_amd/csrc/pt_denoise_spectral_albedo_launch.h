@@ -1,4 +1,4 @@
-// pt_denoise_spectral_albedo_launch.h — launchers of the per-bin albedo guide's kernels and of the bins' demodulation (pt_denoise_spectral_albedo.hip).
+// pt_denoise_spectral_albedo_launch.h — launchers of the per-bin albedo guide's kernels (pt_denoise_spectral_albedo.hip).
 // Every pointer is device memory of the current device; the launches go to the null stream.  Planes are bin-major: `bins` planes of n_pixels floats.
 #ifndef PT_DENOISE_SPECTRAL_ALBEDO_LAUNCH_H
 #define PT_DENOISE_SPECTRAL_ALBEDO_LAUNCH_H
@@ -15,13 +15,6 @@ void launch_bin_albedo_tables(const uint32_t* blob, const float* tex, float wave
 void launch_guide_fold_bins(uint32_t n_pixels, const pt_hit* hits, const BinAlbedoFold& fold, const uint32_t* blob, const float* tex, uint32_t material_count);
 // bin_albedo = sums / samples, over bins x n_pixels values
 void launch_bin_albedo_finish(uint32_t n_pixels, uint32_t bins, const float* sums, uint32_t samples, float* bin_albedo);
-
-// behind launch_dn_prepare(_albedo): out = raw / max(bin_albedo, floor) per live pixel (bin_albedo null: out = raw), raw copied for a dead one; flags |= DN_DEAD
-// where a bin is not finite before or after the division, and such a pixel's colour is set back to its film values and variance.  out must not be raw.
-void launch_dn_demodulate_bins(uint32_t n_pixels, uint32_t bins, const float* raw, const float* bin_albedo, const float* film, const uint32_t* counts, const double* stats,
-                               float* out, float* color, uint8_t* flags);
-// after the last pass: spectral *= max(bin_albedo, floor) at the live pixels, in place
-void launch_dn_remodulate_bins(uint32_t n_pixels, uint32_t bins, const float* bin_albedo, const uint8_t* flags, float* spectral);
 
 }  // namespace ptk
 #endif

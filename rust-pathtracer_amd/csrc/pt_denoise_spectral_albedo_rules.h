@@ -1,15 +1,16 @@
 // pt_denoise_spectral_albedo_rules.h — the rules of the per-bin albedo guide and of the joint filter that demodulates the bins by it
 // (pt_render_guides_bin_albedo and pt_denoise_spectral_albedo of include/pt_spectral.h, DESIGN.md section 14, "Demodulating the bins") as PT_HD functions
-// that the engine's kernels (pt_denoise_spectral_albedo.hip, pt_guides_chain.hip) and the host emulation of the tests
-// (tests/host_emulation/ptemu_denoise_spectral_albedo.cpp) compile from the same text.  It rests on pt_denoise_rules.h (the albedo rule of one layer, the
-// floor) and pt_denoise_spectral_rules.h (the passes, which are unchanged).  All arithmetic is f32, without contraction, in the order written.
+// that the engine's kernels (pt_denoise_spectral_albedo.hip and pt_guides_chain.hip for the guide, pt_denoise.hip for the filter) and the host emulation
+// of the tests (tests/host_emulation/ptemu_denoise_spectral_albedo.cpp) compile from the same text.  It rests on pt_denoise_rules.h (the albedo rule of
+// one layer, the floor) and pt_denoise_spectral_rules.h (the passes, which are unchanged).  All arithmetic is f32, without contraction, in the order written.
 #ifndef PT_DENOISE_SPECTRAL_ALBEDO_RULES_H
 #define PT_DENOISE_SPECTRAL_ALBEDO_RULES_H
 #include "pt_blob.h"
 #include "pt_denoise_spectral_rules.h"
 
 // (as in pt_denoise_spectral_rules.h: the chunk loops are unrolled on the device so that every index into a chunk's registers is static — after an edit
-// re-run tools/resource_usage.py on the two .hip files: scratch 0 is the check.  Undefined at the end of the header.)
+// re-run tools/resource_usage.py on pt_denoise_spectral_albedo.hip, pt_guides_chain.hip and pt_denoise.hip: scratch 0 is the check.  Undefined at the end of
+// the header.)
 #if defined(__HIP_DEVICE_COMPILE__)
 #define DN_UNROLL _Pragma("unroll")
 #else

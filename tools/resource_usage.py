@@ -16,7 +16,8 @@ FLAGS = "-std=c++17 -O2 -fPIC -ffp-contract=off -fno-fast-math -fhip-fp32-correc
 
 def demangle(names):
     out = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.split("\n")
-    return [re.sub(r"^void ptk::", "", re.sub(r"\(.*$", "", o)) for o in out]
+    # (a file-local kernel demangles as "(anonymous namespace)::k_name(...)": that prefix goes before the argument list is cut at its "(")
+    return [re.sub(r"^(void )?(ptk::)?", "", re.sub(r"\(.*$", "", o.replace("(anonymous namespace)::", ""))) for o in out]
 
 
 def usage(source, extra):

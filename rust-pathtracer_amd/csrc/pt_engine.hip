@@ -219,18 +219,40 @@ __global__ void __launch_bounds__(kBlock) k_mask_or(uint8_t* __restrict__ dst, c
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// A device allocation that is freed on every way out of its scope (the probes below return early on any HIP error).
+// A device allocation (pinned: a page-locked host one) that is freed on every way out of its scope (the probes below return early on any HIP error).
 struct DevBuf {
     void* p = nullptr;
+    bool pinned = false;
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) hipFree(p); }
+    ~DevBuf() { release(); }
+    void release() { if (p && pinned) hipHostFree(p); else if (p) hipFree(p); p = nullptr; }
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 4); }
     template <typename T> T* as() const { return static_cast<T*>(p); }
 };
+// One that only grows: its owner keeps it between calls, so that a sequence of renders allocates it once; a call that needs more replaces it, and it is freed
+// with its owner.
+struct GrowBuf : DevBuf {
+    size_t bytes = 0;
+    pt_status reserve(size_t want) {
+        if (bytes >= want) return PT_OK;
+        release();
+        bytes = 0;
+        if (pinned) HIP_TRY(hipHostMalloc(&p, want, hipHostMallocPortable));
+        else HIP_TRY(hipMalloc(&p, want));
+        bytes = want;
+        return PT_OK;
+    }
+};
 
 constexpr uint32_t kUnitCounters = 2 * 64 + 2;   // two parked launches per bounce, max_bounces <= 64
+#ifdef PT_EXPERIMENTS
+#define PT_TUNE_EXPERIMENT_POOL (1u << 31)   /* a pt_tuning::flags bit of its own, unnamed in the public header (round-4 advisor: bit 3 means PT_TUNE_NO_LIVE_LIST in every build) */
+#endif
+#ifndef PT_FUSE_HERO
+#define PT_FUSE_HERO 1   /* round 4: built without machine LICM the hero fused form needs 111 VGPRs — four waves per SIMD, not three — and wins: C5 1153 -> 1179 (3625 us against 1160 + 2578) */
+#endif
 struct DeviceBuffers {
     uint32_t capacity = 0, light_samples = 0, nl = 0, park_block = 0;
     uint32_t *paths_a = nullptr, *paths_b = nullptr, *hits = nullptr, *shadow = nullptr, *pixels = nullptr, *counts = nullptr, *park = nullptr;
@@ -270,8 +292,7 @@ struct MultiSetup {
     std::vector<float*> films;        // per virtual device, on its physical device
     std::vector<hipStream_t> streams; // per virtual device
     std::vector<ncclComm_t> comms;    // per physical device (rccl only)
-    std::vector<float*> staging;      // per virtual device: the pinned host buffer its packed spectral planes land in (the spectral node entries; grown on demand)
-    std::vector<size_t> staging_bytes;
+    std::vector<GrowBuf> staging;   // per virtual device: the pinned host buffer its packed spectral planes land in (the spectral node entries; grown on demand)
     bool valid = false;
 };
 
@@ -288,12 +309,10 @@ struct pt_scene {
     DeviceBuffers buf;
     AdaptiveBuffers adaptive;        // pt_render_adaptive's, kept between calls like buf
     std::vector<hipEvent_t> events;  // pairs (start, stop), grown on demand
-    float* film_cache = nullptr;     // pt_render's device film, kept between calls
-    size_t film_cache_bytes = 0;
-    float* spectral_cache = nullptr; // pt_render_spectral's device planes (bins x width x height), kept between calls
-    size_t spectral_cache_bytes = 0;
+    GrowBuf film_cache;            // pt_render's device film, kept between calls
+    GrowBuf spectral_cache;        // pt_render_spectral's device planes (bins x width x height), kept between calls
     // The resident spectral film (pt_spectral_project_resident): what the last successful spectral render left in spectral_cache.  Cleared when a spectral render
-    // starts and set when it has succeeded; pt_render_spectral and pt_render_adaptive_spectral are the only writers of spectral_cache (ensure_spectral_cache, which
+    // starts and set when it has succeeded; pt_render_spectral and pt_render_adaptive_spectral are the only writers of spectral_cache (its reserve, which
     // may replace it, runs inside them behind the clearing).
     bool spectral_valid = false;
     uint32_t spectral_width = 0, spectral_height = 0, spectral_bins = 0;
@@ -303,10 +322,8 @@ struct pt_scene {
     // floats on its device (k_spectral_pack's output).
     std::vector<pt_scene*> spectral_shards;
     std::vector<uint32_t> shard_px;
-    float* shard_packed = nullptr;
-    size_t shard_packed_bytes = 0;
-    float* project_cache = nullptr;  // pt_spectral_project_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x PT_SPECTRAL_MAX_BINS floats) and, behind it, its output planes
-    size_t project_cache_bytes = 0;
+    GrowBuf shard_packed;
+    GrowBuf project_cache;         // pt_spectral_project_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x PT_SPECTRAL_MAX_BINS floats) and, behind it, its output planes
     std::vector<pt_scene*> replicas; // pt_render_multi: this scene on the other (virtual) devices, by device index x virtual index (nullptr = not made yet / this one)
 };
 
@@ -320,13 +337,13 @@ bool scene_has_mesh(const std::vector<uint32_t>& blob) {
 
 std::string g_device_info;
 
+pt_status no_device() { return fail(PT_ERR_NO_DEVICE, "no HIP device available: the product path has no CPU fallback"); }
 pt_status ensure_device() {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n == 0) return fail(PT_ERR_NO_DEVICE, "no HIP device available: the product path has no CPU fallback");
+    if (e != hipSuccess || n == 0) return no_device();
     return PT_OK;
 }
-
 
 // Segment capacity for n items over `grid` segments, rounded up to 64 items so that every segment starts on a
 // 256-byte boundary in every field.
@@ -500,25 +517,38 @@ pt_status adaptive_rounds(pt_scene* sc, const pt_render_desc& rd, const pt_adapt
     return PT_OK;
 }
 
-// Set-up (kernel forms, queues, launch configuration) and one pass loop over a device pixel list and a sample range: pt_render runs the loop once over its
-// shard's pixels; with `adaptive` (pt_render_adaptive, its arguments checked) adaptive_rounds runs it once per round, over the film or (with `node`: worker
-// node_index of pt_render_adaptive_multi) over the desc's shard.  With `d_spectral` (pt_render_spectral: spectral_bins planes of width * height floats, its
-// arguments checked) every pass also adds its samples to the wavelength-binned film (include/pt_spectral.h); with both (pt_render_adaptive_spectral and its node
-// form) the bins hold running sums, a continued pixel starting from its stored value, until k_adaptive_finish_spectral divides each pixel's by its own count.
-// `shard_list` (the spectral node entries): the desc's shard as pth::shard_pixels lists it, computed by the caller, who packs the bins by it afterwards — the
-// device copy of it is then left in the scene's buf.pixels whichever kind of render this is.
-pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hipStream_t stream, pt_profile* profile, const pt_adaptive_desc* adaptive = nullptr,
-                      NodeRounds* node = nullptr, int node_index = 0, float* d_spectral = nullptr, uint32_t spectral_bins = 0,
-                      const std::vector<uint32_t>* shard_list = nullptr) {
-    if (!sc || !rdp || !d_film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    pt_render_desc rd;
-    std::string err;
-    if (!pth::normalize_render_desc(*rdp, (uint32_t)sc->host.cameras.size(), &rd, &err)) return fail(PT_ERR_INVALID_ARGUMENT, err);
-    HIP_TRY(hipSetDevice(sc->device));
+// What is optional about a render (render_impl): a default-constructed job is pt_render's.
+struct RenderJob {
+    // pt_render_adaptive (its arguments checked): adaptive_rounds runs the pass loop once per round, over the film or (with `node`: worker node_index of
+    // pt_render_adaptive_multi) over the desc's shard
+    const pt_adaptive_desc* adaptive = nullptr;
+    NodeRounds* node = nullptr;
+    int node_index = 0;
+    // pt_render_spectral (its arguments checked): spectral_bins planes of width * height floats; every pass also adds its samples to the wavelength-binned film
+    // (include/pt_spectral.h).  With `adaptive` too (pt_render_adaptive_spectral and its node form) the bins hold running sums, a continued pixel starting from its
+    // stored value, until k_adaptive_finish_spectral divides each pixel's by its own count.
+    float* d_spectral = nullptr;
+    uint32_t spectral_bins = 0;
+    // the spectral node entries: the desc's shard as pth::shard_pixels lists it, computed by the caller, who packs the bins by it afterwards — the device copy of it
+    // is then left in the scene's buf.pixels whichever kind of render this is
+    const std::vector<uint32_t>* shard_list = nullptr;
+};
 
-    std::vector<uint32_t> own_list;
-    if (!shard_list) own_list = pth::shard_pixels(rd.width, rd.height, rd.tile_width, rd.tile_height, rd.shard_index, rd.shard_count);
-    const std::vector<uint32_t>& pixels = shard_list ? *shard_list : own_list;
+// What plan_render chooses for a render: the queues' size, the kernel forms and their launch configuration.
+struct RenderPlan {
+    uint32_t capacity = 0;   // path slots per pass
+    int grid = 0;            // queue segments = workgroups per launch
+    bool hero = false;       // four wavelengths per path
+    uint32_t park_block = 0, park_block_extend = 0;
+    int trav_form = 0, shade_form = 0;
+    bool park_dynamic = false, park_big = false;
+    LaunchCfg cfg{};         // (with walk_policy and fuse; unit_counter and path_marks are the pass loop's)
+    uint32_t live_list = 0, camera_record = 0;   // RenderParams' fields of these names
+    uint32_t path_fields = 0, item_fields = 0;
+};
+// The choices of a render, from the scene's blob header, its tuning and the normalised desc `rd` over the pixel list `pixels`: host logic alone, no HIP call.
+pt_status plan_render(const pt_scene* sc, const pt_render_desc& rd, const RenderJob& job, const std::vector<uint32_t>& pixels, hipStream_t stream, RenderPlan* plan) {
+    const pt_adaptive_desc* adaptive = job.adaptive;
     const pt_tuning& tn = sc->tuning;
     uint32_t capacity = tuned(tn.batch_slots, 1u << 27);  // path slots per pass (128 Mi ~ 32 GB of queues of the 288 GB; tools/sweep.sh)
     if (capacity < 1024) capacity = 1024;
@@ -541,48 +571,21 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     const bool few_walks = (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_CONVEX) != 0u;
     const uint32_t park_block = !park_big_ok ? (uint32_t)kBlock : tn.park_block == 0u ? (few_walks ? (uint32_t)kBlock : 512u) : tn.park_block;
     const uint32_t park_block_extend = !park_big_ok || tn.park_block == 0u ? (uint32_t)kBlock : tn.park_block;
-    pt_status st = ensure_buffers(sc, capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, (hero || rd.medium_aware) ? 4u : 1u, park_block);
-    if (st != PT_OK) return st;
-    DeviceBuffers& b = sc->buf;
-    if (adaptive) {   // (round 0's list: every pixel of the film — or of the shard — in shard_pixels' order; counts and stats are zero outside it)
-        const size_t film_pixels = (size_t)rd.width * rd.height;
-        st = ensure_adaptive_buffers(sc, film_pixels);
-        if (st != PT_OK) return st;
-        if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(sc->adaptive.lists[0], pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
-        // (the rounds compact into lists[0] again: the list the caller packs by is kept where pt_render keeps its own)
-        if (shard_list && !pixels.empty()) HIP_TRY(hipMemcpyAsync(b.pixels, pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemsetAsync(sc->adaptive.stats, 0, sizeof(double) * 2 * film_pixels, stream));
-        if (pixels.size() < film_pixels) HIP_TRY(hipMemsetAsync(sc->adaptive.counts, 0, sizeof(uint32_t) * film_pixels, stream));
-    } else if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(b.pixels, pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(d_film, 0, sizeof(float) * 4 * (size_t)rd.width * rd.height, stream));
-    if (d_spectral) HIP_TRY(hipMemsetAsync(d_spectral, 0, sizeof(float) * (size_t)spectral_bins * rd.width * rd.height, stream));
-    HIP_TRY(hipMemsetAsync(b.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));
-
-    RenderParams rp;
-    memset(&rp, 0, sizeof(rp));
-    rp.seed = rd.seed; rp.width = rd.width; rp.height = rd.height;
-    rp.min_bounces = rd.min_bounces; rp.max_bounces = rd.max_bounces; rp.light_samples = rd.light_samples; rp.only_direct = rd.only_direct;
-    rp.wavelength_lo = rd.wavelength_lo; rp.wavelength_span = rd.wavelength_hi - rd.wavelength_lo;
-    // (an adaptive render's film holds running sums until k_adaptive_finish divides each pixel by its own count; its rounds end on phase boundaries)
-    rp.spp = adaptive ? adaptive->max_samples : rd.spp; rp.range_end = rd.first_sample + rd.sample_count;
-    rp.normalize = (!adaptive && rd.first_sample == 0 && rd.sample_count == rd.spp) ? 1u : 0u;
-    rp.phase = rd.phase_samples;
-    rp.camera = pth::camera_params(sc->host.cameras[rd.camera_index], (float)rd.width / (float)rd.height);
-    rp.energy_stride = b.capacity;
-
+    // (the parked kernels' scratch, b.park, by ensure_buffers' rule: the plan is made before the buffers are)
+    const bool no_table = sc->host.blob[PT_HDR_SWEEP_OFF] == 0 || (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_NO_SWEEP);
+    const bool park_scratch = (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_SWEEP_WALKS) || no_table;
     const int mode = sc->lds_mode;
     const uint32_t lds_bytes = mode == PT_LDS_ALL ? sc->blob_words * 4u : (mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
     const bool sweep = sc->host.blob[PT_HDR_SWEEP_OFF] != 0 && !(sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_NO_SWEEP);
     // the sweep table holds walked meshes: rays that reach one are parked and resumed in full waves (PT_AMD_NO_PARK=1: in line)
     const bool walks = (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_SWEEP_WALKS) != 0;
     const bool mesh_lights = sc->host.blob[PT_HDR_LIGHT_FACE_OFF] != 0u;   // (emissive mesh faces: PT_FORM_ANY, below)
-    const bool parked = sweep && walks && b.park != nullptr && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights;
+    const bool parked = sweep && walks && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights;
     // no sweep table (more than 64 instances, PT_AMD_NO_SWEEP): the top-level tree per lane, every mesh parked (top_walk_run, pt_device.h)
-    const bool parked_walk = !sweep && b.park != nullptr && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights;
+    const bool parked_walk = !sweep && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights;
     // PT_AMD_POOL=1: phase 3 of a pure sweep scene pooled per wave (sweep_run_pooled).  Bit-identical, but measured slower than the lane
     // loop on MI355X (C2: k_extend 3155 vs 2475 us, k_shadow 5421 vs 4677 us; DESIGN.md section 5 has the breakdown), so it is not the default.
 #ifdef PT_EXPERIMENTS
-#define PT_TUNE_EXPERIMENT_POOL (1u << 31)   /* a pt_tuning::flags bit of its own, unnamed in the public header (round-4 advisor: bit 3 means PT_TUNE_NO_LIVE_LIST in every build) */
     const bool pooled = sweep && !walks && mode == PT_LDS_ALL && lds_bytes + pool_lds_bytes() <= kLdsBlobLimitBytes && (tn.flags & PT_TUNE_EXPERIMENT_POOL) != 0;
 #else
     const bool pooled = false;   // (the pooled kernels are not in the product: make EXTRA=-DPT_EXPERIMENTS builds them, PT_AMD_POOL=1 selects them there)
@@ -625,7 +628,6 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                     | ((tn.flags & PT_TUNE_NO_AXIS_SCAN) ? 0u : PT_WALK_SCAN_AXIS)
                     | (top_evict <= 1u ? 0u : top_evict << 24)   // (1 = never: 0 in the policy word)
                     | (group_evict <= 1u ? 0u : group_evict << 17);
-    const SceneArgs sargs{sc->d_blob, sc->blob_words, sc->d_tex, marginal_lds_bytes(sc->host.blob.data(), lds_bytes)};
     // light samples can pick the environment only if env_sampling_probability > 0: otherwise k_shade is the form without that branch
     float env_prob; std::memcpy(&env_prob, &sc->host.blob[PT_HDR_ENV_PROB], sizeof env_prob);
     bool has_ggx = false;
@@ -639,34 +641,112 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     const int shade_form = rd.medium_aware ? PT_SHADE_MEDIUM
                          : (env_prob != 0.0f || tn.shade_form == 2) ? PT_SHADE_FULL : (has_ggx || certs || tn.shade_form == 1) ? PT_SHADE_NO_ENV : PT_SHADE_LEAN;
     cfg.certs = certs;
-    // k_shade that traces its own segments: exists for the pure sweep form of a fully staged, transform-free scene shaded by the lean form.
-    // Measured (profiles/r3_experiments.md): C2 +4..5 % (4370 us against 2095 + 2490..2640 per bounce); with four wavelengths per path it
-    // lost in round 3 (C5 996 against 1093 Msamples/s: the traversal then ran at the three waves per SIMD the wide vertex code left) and wins since round 4 (below).
-#ifndef PT_FUSE_HERO
-#define PT_FUSE_HERO 1   /* round 4: built without machine LICM the hero fused form needs 111 VGPRs — four waves per SIMD, not three — and wins: C5 1153 -> 1179 (3625 us against 1160 + 2578) */
-#endif
     // (the plain light-sample kernel walks the list of live items; the parked forms list their live RAYS themselves, the measurement forms read every item)
-    rp.live_list = ((trav_form == PT_FORM_SWEEP || trav_form == PT_FORM_WALK || trav_form == PT_FORM_ANY) && shade_form == PT_SHADE_LEAN && !(tn.flags & PT_TUNE_NO_LIVE_LIST)) ? 1u : 0u;
+    uint32_t live_list = ((trav_form == PT_FORM_SWEEP || trav_form == PT_FORM_WALK || trav_form == PT_FORM_ANY) && shade_form == PT_SHADE_LEAN && !(tn.flags & PT_TUNE_NO_LIVE_LIST)) ? 1u : 0u;
 #ifdef PT_EXPERIMENTS
     // a measurement build runs the shipped kernel pair unless one of its own forms is asked for: those read every item of a segment
-    if (cfg.live_lists || getenv("PT_AMD_EXP_SHADOW")) rp.live_list = 0u;
+    if (cfg.live_lists || getenv("PT_AMD_EXP_SHADOW")) live_list = 0u;
 #endif
-    rp.camera_record = (shade_form == PT_SHADE_LEAN || shade_form == PT_SHADE_FULL || shade_form == PT_SHADE_MEDIUM) ? 1u : 0u;   // (the forms whose bounce-0 launch rebuilds the camera vertex: k_shade, pt_kernels.h)
+    const uint32_t camera_record = (shade_form == PT_SHADE_LEAN || shade_form == PT_SHADE_FULL || shade_form == PT_SHADE_MEDIUM) ? 1u : 0u;   // (the forms whose bounce-0 launch rebuilds the camera vertex: k_shade, pt_kernels.h)
+    // k_shade that traces its own segments: exists for the pure sweep form of a fully staged, transform-free scene shaded by the lean form.
+    // Measured (profiles/r3_experiments.md): C2 +4..5 % (4370 us against 2095 + 2490..2640 per bounce); with four wavelengths per path it
+    // lost in round 3 (C5 996 against 1093 Msamples/s: the traversal then ran at the three waves per SIMD the wide vertex code left) and wins since round 4 (PT_FUSE_HERO).
     cfg.fuse = !(tn.flags & PT_TUNE_NO_FUSE) && (!hero || PT_FUSE_HERO) && trav_form == PT_FORM_SWEEP && shade_form == PT_SHADE_LEAN && (cfg.lacks & PT_SCENE_NO_XF) != 0;
+    // (a queue's tiles are laid out by the number of fields this render uses, pt_stages.h: the buffers are sized for the widest layout seen)
+    const uint32_t path_fields = hero ? Layout<4>::path_fields : (rd.medium_aware ? (uint32_t)PS_FIELDS + 2u : Layout<1>::path_fields);
+    const uint32_t item_fields = hero ? Layout<4>::shadow_queue_fields(rd.light_samples ? rd.light_samples : 1) : Layout<1>::shadow_queue_fields(rd.light_samples ? rd.light_samples : 1);
+    *plan = RenderPlan{capacity, grid, hero, park_block, park_block_extend, trav_form, shade_form, park_dynamic, park_big, cfg, live_list, camera_record,
+                       path_fields, item_fields};
+    return PT_OK;
+}
+
+// A render's profile: the workgroups' counters read back and summed, beside what the pass loop counted and timed on the host.
+pt_status read_profile(pt_scene* sc, const RenderPlan& plan, uint64_t camera_rays, uint64_t accumulated_pixels, const double* stage_ms, const uint64_t* stage_launches,
+                       uint32_t rounds, double seconds, pt_profile* profile) {
+    memset(profile, 0, sizeof(*profile));
+    std::vector<unsigned long long> bs((size_t)plan.grid * BS_FIELDS);
+    HIP_TRY(hipMemcpy(bs.data(), sc->buf.block_stats, sizeof(unsigned long long) * bs.size(), hipMemcpyDeviceToHost));
+    unsigned long long c[BS_FIELDS] = {0, 0, 0, 0, 0, 0};
+    for (int g = 0; g < plan.grid; ++g) for (int k = 0; k < BS_FIELDS; ++k) c[k] += bs[(size_t)g * BS_FIELDS + k];
+    profile->camera_rays = camera_rays;
+    profile->bounce_rays = c[BS_VERTICES] + camera_rays;  // vertices.len() counts the camera vertex (utils.rs:375)
+    profile->shadow_rays = c[BS_SHADOW_RAYS];
+    profile->env_hits = c[BS_ENV_HITS];
+    profile->seconds = seconds;
+    for (int i = 0; i < ST_COUNT; ++i) { profile->kernel_seconds[i] = stage_ms[i] * 1e-3; profile->kernel_launches[i] = stage_launches[i]; }
+    profile->stage_items[ST_GENERATE] = camera_rays; profile->stage_items[ST_EXTEND] = c[BS_SEGMENTS]; profile->stage_items[ST_SHADE] = c[BS_SEGMENTS];
+    profile->stage_items[ST_SHADOW] = c[BS_ITEMS]; profile->stage_items[ST_ACCUMULATE] = accumulated_pixels;
+    profile->stage_items[6] = (uint64_t)plan.cfg.park_block;   // threads per workgroup of the parked kernels when they ran in their big-workgroup form (pt_tuning::park_block), else 0
+    profile->stage_items[7] = plan.camera_record;   // 1: k_generate wrote the camera vertex' lean record (7 of 16 words) and the first bounce's vertex kernel rebuilt the rest
+    profile->stage_items[5] = c[BS_MEDIUM_DROPS];   // the medium-aware walk tracks four nested mediums: what a fifth level lost (0 = the walk is the reference's)
+    profile->kernel_launches[5] = rounds;           // pt_render_adaptive: its rounds (0 for pt_render)
+    return PT_OK;
+}
+
+// A render in four steps: the plan (plan_render), the buffers and the upload of the pixel list, the pass loop — pt_render runs it once over its shard's pixels,
+// an adaptive job once per round (adaptive_rounds) — and the profile (read_profile).  `job`: what is optional about the render.
+pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hipStream_t stream, pt_profile* profile, const RenderJob& job) {
+    if (!sc || !rdp || !d_film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    pt_render_desc rd;
+    std::string err;
+    if (!pth::normalize_render_desc(*rdp, (uint32_t)sc->host.cameras.size(), &rd, &err)) return fail(PT_ERR_INVALID_ARGUMENT, err);
+    HIP_TRY(hipSetDevice(sc->device));
+
+    const pt_adaptive_desc* adaptive = job.adaptive;
+    std::vector<uint32_t> own_list;
+    if (!job.shard_list) own_list = pth::shard_pixels(rd.width, rd.height, rd.tile_width, rd.tile_height, rd.shard_index, rd.shard_count);
+    const std::vector<uint32_t>& pixels = job.shard_list ? *job.shard_list : own_list;
+    RenderPlan plan;
+    pt_status st = plan_render(sc, rd, job, pixels, stream, &plan);
+    if (st != PT_OK) return st;
+    const uint32_t capacity = plan.capacity;
+    const int grid = plan.grid, trav_form = plan.trav_form, shade_form = plan.shade_form;
+    const bool hero = plan.hero, park_dynamic = plan.park_dynamic;
+    LaunchCfg cfg = plan.cfg;
+
+    st = ensure_buffers(sc, capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block);
+    if (st != PT_OK) return st;
+    DeviceBuffers& b = sc->buf;
+    if ((trav_form == PT_FORM_PARKED || trav_form == PT_FORM_PARKED_WALK) && !b.park) return fail(PT_ERR_DEVICE, "internal: a parked traversal form without the parked kernels' scratch");
+    if (adaptive) {   // (round 0's list: every pixel of the film — or of the shard — in shard_pixels' order; counts and stats are zero outside it)
+        const size_t film_pixels = (size_t)rd.width * rd.height;
+        st = ensure_adaptive_buffers(sc, film_pixels);
+        if (st != PT_OK) return st;
+        if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(sc->adaptive.lists[0], pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
+        // (the rounds compact into lists[0] again: the list the caller packs by is kept where pt_render keeps its own)
+        if (job.shard_list && !pixels.empty()) HIP_TRY(hipMemcpyAsync(b.pixels, pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(sc->adaptive.stats, 0, sizeof(double) * 2 * film_pixels, stream));
+        if (pixels.size() < film_pixels) HIP_TRY(hipMemsetAsync(sc->adaptive.counts, 0, sizeof(uint32_t) * film_pixels, stream));
+    } else if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(b.pixels, pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(d_film, 0, sizeof(float) * 4 * (size_t)rd.width * rd.height, stream));
+    if (job.d_spectral) HIP_TRY(hipMemsetAsync(job.d_spectral, 0, sizeof(float) * (size_t)job.spectral_bins * rd.width * rd.height, stream));
+    HIP_TRY(hipMemsetAsync(b.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));
+
+    RenderParams rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.seed = rd.seed; rp.width = rd.width; rp.height = rd.height;
+    rp.min_bounces = rd.min_bounces; rp.max_bounces = rd.max_bounces; rp.light_samples = rd.light_samples; rp.only_direct = rd.only_direct;
+    rp.wavelength_lo = rd.wavelength_lo; rp.wavelength_span = rd.wavelength_hi - rd.wavelength_lo;
+    // (an adaptive render's film holds running sums until k_adaptive_finish divides each pixel by its own count; its rounds end on phase boundaries)
+    rp.spp = adaptive ? adaptive->max_samples : rd.spp; rp.range_end = rd.first_sample + rd.sample_count;
+    rp.normalize = (!adaptive && rd.first_sample == 0 && rd.sample_count == rd.spp) ? 1u : 0u;
+    rp.phase = rd.phase_samples;
+    rp.camera = pth::camera_params(sc->host.cameras[rd.camera_index], (float)rd.width / (float)rd.height);
+    rp.energy_stride = b.capacity;
+    rp.live_list = plan.live_list; rp.camera_record = plan.camera_record;
+
+    const pt_tuning& tn = sc->tuning;
+    const SceneArgs sargs{sc->d_blob, sc->blob_words, sc->d_tex, marginal_lds_bytes(sc->host.blob.data(), cfg.lds_bytes)};
     const uint32_t bounce_limit = rd.only_direct ? 1u : rd.max_bounces;
     const bool timing = !(tn.flags & PT_TUNE_NO_STAGE_TIMING);
     double stage_ms[ST_COUNT] = {0, 0, 0, 0, 0};
     uint64_t stage_launches[ST_COUNT] = {0, 0, 0, 0, 0};
-    // (a queue's tiles are laid out by the number of fields this render uses, pt_stages.h: the buffers are sized for the widest layout seen)
-    const uint32_t path_fields = hero ? Layout<4>::path_fields : (rd.medium_aware ? (uint32_t)PS_FIELDS + 2u : Layout<1>::path_fields);
-    const uint32_t item_fields = hero ? Layout<4>::shadow_queue_fields(rd.light_samples ? rd.light_samples : 1) : Layout<1>::shadow_queue_fields(rd.light_samples ? rd.light_samples : 1);
-    Queue qa{b.paths_a, b.capacity, path_fields}, qb{b.paths_b, b.capacity, path_fields}, qh{b.hits, b.capacity, HS_FIELDS}, qs{b.shadow, b.capacity, item_fields};
+    Queue qa{b.paths_a, b.capacity, plan.path_fields}, qb{b.paths_b, b.capacity, plan.path_fields}, qh{b.hits, b.capacity, HS_FIELDS}, qs{b.shadow, b.capacity, plan.item_fields};
     uint32_t* live[2] = {b.counts, b.counts + grid};  // per-segment live-path counts, ping-pong with the path queues
     uint32_t* nshadow = b.counts + 2 * grid;          // per-segment light-sample item counts; behind them (nshadow + grid) the counts of the live ones (Layout::shadow_live_field)
 
-    auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipStreamSynchronize(stream));
-    t0 = std::chrono::steady_clock::now();
+    const auto t0 = std::chrono::steady_clock::now();
     // HIP events around every launch, recorded on the launch stream and read back after the final sync, so the
     // per-stage device time is measured inside the timed region without stalling it.
     // (round 5: ONE event between two launches — the end of one is the start of the next on the stream — not two: the markers cost a short frame 5 % of its time,
@@ -729,19 +809,19 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                 else if (hero) hipLaunchKernelGGL(k_accumulate<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film);
                 else hipLaunchKernelGGL(k_accumulate<1>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film);
                 // (the energy planes stay valid until the next pass's k_generate overwrites them)
-                if (d_spectral && spectral_error == hipSuccess)
-                    spectral_error = ptk::launch_accumulate_spectral(hero ? 4 : 1, grid, stream, rp, d_px, b.energy, d_spectral, spectral_bins, rd.width * rd.height);
+                if (job.d_spectral && spectral_error == hipSuccess)
+                    spectral_error = ptk::launch_accumulate_spectral(hero ? 4 : 1, grid, stream, rp, d_px, b.energy, job.d_spectral, job.spectral_bins, rd.width * rd.height);
             });
             if (spectral_error != hipSuccess) return fail(PT_ERR_DEVICE, std::string("k_accumulate_spectral: ") + hipGetErrorString(spectral_error));
         }
         return PT_OK;
     };
     uint32_t rounds = 0;
-    st = adaptive ? adaptive_rounds(sc, rd, *adaptive, stream, d_film, (uint32_t)pixels.size(), run_passes, &rounds, node, node_index)
+    st = adaptive ? adaptive_rounds(sc, rd, *adaptive, stream, d_film, (uint32_t)pixels.size(), run_passes, &rounds, job.node, job.node_index)
                   : run_passes(b.pixels, (uint32_t)pixels.size(), rd.first_sample, rd.sample_count, nullptr);
     if (st != PT_OK) return st;
-    if (adaptive && d_spectral)
-        hipLaunchKernelGGL(k_adaptive_finish_spectral, dim3(sc->num_cus * 4), dim3(kBlock), 0, stream, rd.width * rd.height, spectral_bins, sc->adaptive.counts, d_spectral);
+    if (adaptive && job.d_spectral)
+        hipLaunchKernelGGL(k_adaptive_finish_spectral, dim3(sc->num_cus * 4), dim3(kBlock), 0, stream, rd.width * rd.height, job.spectral_bins, sc->adaptive.counts, job.d_spectral);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     auto t1 = std::chrono::steady_clock::now();
@@ -749,25 +829,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
         float ms = 0.0f;
         if (event_stage[k] >= 0 && hipEventElapsedTime(&ms, sc->events[k], sc->events[k + 1]) == hipSuccess) stage_ms[event_stage[k]] += ms;
     }
-    if (profile) {
-        memset(profile, 0, sizeof(*profile));
-        std::vector<unsigned long long> bs((size_t)grid * BS_FIELDS);
-        HIP_TRY(hipMemcpy(bs.data(), b.block_stats, sizeof(unsigned long long) * bs.size(), hipMemcpyDeviceToHost));
-        unsigned long long c[BS_FIELDS] = {0, 0, 0, 0, 0, 0};
-        for (int g = 0; g < grid; ++g) for (int k = 0; k < BS_FIELDS; ++k) c[k] += bs[(size_t)g * BS_FIELDS + k];
-        profile->camera_rays = camera_rays;
-        profile->bounce_rays = c[BS_VERTICES] + camera_rays;  // vertices.len() counts the camera vertex (utils.rs:375)
-        profile->shadow_rays = c[BS_SHADOW_RAYS];
-        profile->env_hits = c[BS_ENV_HITS];
-        profile->seconds = std::chrono::duration<double>(t1 - t0).count();
-        for (int i = 0; i < ST_COUNT; ++i) { profile->kernel_seconds[i] = stage_ms[i] * 1e-3; profile->kernel_launches[i] = stage_launches[i]; }
-        profile->stage_items[ST_GENERATE] = camera_rays; profile->stage_items[ST_EXTEND] = c[BS_SEGMENTS]; profile->stage_items[ST_SHADE] = c[BS_SEGMENTS];
-        profile->stage_items[ST_SHADOW] = c[BS_ITEMS]; profile->stage_items[ST_ACCUMULATE] = accumulated_pixels;
-        profile->stage_items[6] = (uint64_t)cfg.park_block;   // threads per workgroup of the parked kernels when they ran in their big-workgroup form (pt_tuning::park_block), else 0
-        profile->stage_items[7] = rp.camera_record;     // 1: k_generate wrote the camera vertex' lean record (7 of 16 words) and the first bounce's vertex kernel rebuilt the rest
-        profile->stage_items[5] = c[BS_MEDIUM_DROPS];   // the medium-aware walk tracks four nested mediums: what a fifth level lost (0 = the walk is the reference's)
-        profile->kernel_launches[5] = rounds;           // pt_render_adaptive: its rounds (0 for pt_render)
-    }
+    if (profile) return read_profile(sc, plan, camera_rays, accumulated_pixels, stage_ms, stage_launches, rounds, std::chrono::duration<double>(t1 - t0).count(), profile);
     return PT_OK;
 }
 
@@ -929,36 +991,60 @@ void pt_scene_destroy(pt_scene* sc) {
     hipSetDevice(sc->device);
     sc->buf.release();
     sc->adaptive.release();
-    hipFree(sc->d_blob); hipFree(sc->d_tex); hipFree(sc->film_cache); hipFree(sc->spectral_cache); hipFree(sc->project_cache); hipFree(sc->shard_packed);
+    hipFree(sc->d_blob); hipFree(sc->d_tex);
     for (auto& e : sc->events) hipEventDestroy(e);
-    delete sc;
+    delete sc;   // (the grow-only buffers go with it: the replicas are gone and the device is this scene's)
 }
 
 pt_status pt_render_device(pt_scene* sc, const pt_render_desc* rd, void* film_device, void* hip_stream, pt_profile* profile) {
-    return render_impl(sc, rd, static_cast<float*>(film_device), static_cast<hipStream_t>(hip_stream), profile);
+    return render_impl(sc, rd, static_cast<float*>(film_device), static_cast<hipStream_t>(hip_stream), profile, RenderJob());
 }
 
-static pt_status ensure_film_cache(pt_scene* sc, size_t bytes) {
-    if (sc->film_cache_bytes < bytes) {   // the device film lives as long as the scene: a sequence of renders allocates it once
-        if (sc->film_cache) hipFree(sc->film_cache);
-        sc->film_cache = nullptr; sc->film_cache_bytes = 0;
-        HIP_TRY(hipMalloc(&sc->film_cache, bytes));
-        sc->film_cache_bytes = bytes;
+// What a render entry was called with, its arguments checked (rd, ad: normalised where the entry normalises them): the descs of the render and where its results go.
+struct RenderCall {
+    const pt_render_desc* rd = nullptr;
+    const pt_adaptive_desc* ad = nullptr;   // the adaptive entries
+    const pt_spectral_desc* sd = nullptr;   // the spectral entries
+    float* film = nullptr;
+    uint32_t* sample_counts = nullptr;      // the adaptive entries; stats: where the caller wants them
+    double* stats = nullptr;
+    float* spectral = nullptr;              // the spectral entries
+};
+
+// The body of the four one-device entries: the device, the film and the planes kept with the scene, render_impl on the null stream, the read-backs and the resident
+// spectral film.  profile->seconds: render_impl's window for the fixed entries; for the adaptive ones the whole call.
+static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* profile) {
+    const pt_render_desc& rd = *call.rd;
+    if (call.sd) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts: whatever the buffer held is no film from here on)
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t n_pixels = (size_t)rd.width * rd.height, film_bytes = sizeof(float) * 4 * n_pixels, spectral_bytes = call.sd ? sizeof(float) * call.sd->bins * n_pixels : 0;
+    pt_status st = sc->film_cache.reserve(film_bytes);
+    if (st == PT_OK && call.sd) st = sc->spectral_cache.reserve(spectral_bytes);
+    if (st != PT_OK) return st;
+    RenderJob job;
+    job.adaptive = call.ad;
+    if (call.sd) { job.d_spectral = sc->spectral_cache.as<float>(); job.spectral_bins = call.sd->bins; }
+    const hipStream_t stream = nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    st = render_impl(sc, &rd, sc->film_cache.as<float>(), stream, profile, job);
+    if (st != PT_OK) return st;
+    HIP_TRY(hipMemcpy(call.film, sc->film_cache.p, film_bytes, hipMemcpyDeviceToHost));
+    if (call.ad) {
+        HIP_TRY(hipMemcpy(call.sample_counts, sc->adaptive.counts, sizeof(uint32_t) * n_pixels, hipMemcpyDeviceToHost));
+        if (call.stats) HIP_TRY(hipMemcpy(call.stats, sc->adaptive.stats, sizeof(double) * 2 * n_pixels, hipMemcpyDeviceToHost));
     }
+    if (call.sd) HIP_TRY(hipMemcpy(call.spectral, sc->spectral_cache.p, spectral_bytes, hipMemcpyDeviceToHost));
+    if (call.ad && profile) profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (the whole call: set-up, rounds, read-backs)
+    if (call.sd) { sc->spectral_width = rd.width; sc->spectral_height = rd.height; sc->spectral_bins = call.sd->bins; sc->spectral_valid = true; }
     return PT_OK;
 }
 
 pt_status pt_render(pt_scene* sc, const pt_render_desc* rd, float* film, pt_profile* profile) {
     if (!sc || !rd || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     if (rd->width == 0 || rd->height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
-    HIP_TRY(hipSetDevice(sc->device));
-    const size_t bytes = sizeof(float) * 4 * (size_t)rd->width * rd->height;
-    pt_status st = ensure_film_cache(sc, bytes);
-    if (st != PT_OK) return st;
-    st = render_impl(sc, rd, sc->film_cache, nullptr, profile);
-    if (st != PT_OK) return st;
-    HIP_TRY(hipMemcpy(film, sc->film_cache, bytes, hipMemcpyDeviceToHost));
-    return PT_OK;
+    RenderCall call;
+    call.rd = rd; call.film = film;
+    return render_one(sc, call, profile);
 }
 
 pt_status pt_render_adaptive(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, float* film, uint32_t* sample_counts, double* stats,
@@ -969,28 +1055,9 @@ pt_status pt_render_adaptive(pt_scene* sc, const pt_render_desc* rdp, const pt_a
     std::string err;
     pt_status st = pth::normalize_adaptive_desc(*rdp, *adp, sample_counts != nullptr, (uint32_t)sc->host.cameras.size(), &rd, &ad, &err);
     if (st != PT_OK) return fail(st, err);
-    HIP_TRY(hipSetDevice(sc->device));
-    const size_t n_pixels = (size_t)rd.width * rd.height;
-    st = ensure_film_cache(sc, sizeof(float) * 4 * n_pixels);
-    if (st != PT_OK) return st;
-    const auto t0 = std::chrono::steady_clock::now();
-    st = render_impl(sc, &rd, sc->film_cache, nullptr, profile, &ad);
-    if (st != PT_OK) return st;
-    HIP_TRY(hipMemcpy(film, sc->film_cache, sizeof(float) * 4 * n_pixels, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(sample_counts, sc->adaptive.counts, sizeof(uint32_t) * n_pixels, hipMemcpyDeviceToHost));
-    if (stats) HIP_TRY(hipMemcpy(stats, sc->adaptive.stats, sizeof(double) * 2 * n_pixels, hipMemcpyDeviceToHost));
-    if (profile) profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (the whole call: set-up, rounds, read-backs)
-    return PT_OK;
-}
-
-static pt_status ensure_spectral_cache(pt_scene* sc, size_t bytes) {   // (kept with the scene, like the film)
-    if (sc->spectral_cache_bytes < bytes) {
-        if (sc->spectral_cache) hipFree(sc->spectral_cache);
-        sc->spectral_cache = nullptr; sc->spectral_cache_bytes = 0;
-        HIP_TRY(hipMalloc(&sc->spectral_cache, bytes));
-        sc->spectral_cache_bytes = bytes;
-    }
-    return PT_OK;
+    RenderCall call;
+    call.rd = &rd; call.ad = &ad; call.film = film; call.sample_counts = sample_counts; call.stats = stats;
+    return render_one(sc, call, profile);
 }
 
 pt_status pt_render_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_spectral_desc* sdp, float* film, float* spectral, pt_profile* profile) {
@@ -998,20 +1065,9 @@ pt_status pt_render_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_s
     pt_status st = pth::check_spectral_args(sc, rdp, sdp, film, spectral, &err);
     if (st != PT_OK) return fail(st, err);
     if (rdp->width == 0 || rdp->height == 0 || (uint64_t)rdp->width * rdp->height > 0xffffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and the film at most 2^32 - 1 pixels");
-    sc->spectral_valid = false;   // (a spectral render starts: whatever the buffer held is no film from here on)
-    sc->spectral_shards.clear();
-    HIP_TRY(hipSetDevice(sc->device));
-    const size_t n_pixels = (size_t)rdp->width * rdp->height, film_bytes = sizeof(float) * 4 * n_pixels, spectral_bytes = sizeof(float) * sdp->bins * n_pixels;
-    st = ensure_film_cache(sc, film_bytes);
-    if (st != PT_OK) return st;
-    st = ensure_spectral_cache(sc, spectral_bytes);
-    if (st != PT_OK) return st;
-    st = render_impl(sc, rdp, sc->film_cache, nullptr, profile, nullptr, nullptr, 0, sc->spectral_cache, sdp->bins);
-    if (st != PT_OK) return st;
-    HIP_TRY(hipMemcpy(film, sc->film_cache, film_bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(spectral, sc->spectral_cache, spectral_bytes, hipMemcpyDeviceToHost));
-    sc->spectral_width = rdp->width; sc->spectral_height = rdp->height; sc->spectral_bins = sdp->bins; sc->spectral_valid = true;
-    return PT_OK;
+    RenderCall call;
+    call.rd = rdp; call.sd = sdp; call.film = film; call.spectral = spectral;
+    return render_one(sc, call, profile);
 }
 
 pt_status pt_render_adaptive_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, const pt_spectral_desc* sdp, float* film,
@@ -1021,24 +1077,9 @@ pt_status pt_render_adaptive_spectral(pt_scene* sc, const pt_render_desc* rdp, c
     std::string err;
     pt_status st = pth::check_adaptive_spectral_args(sc, rdp, adp, sdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, film, sample_counts, spectral, &rd, &ad, &err);
     if (st != PT_OK) return fail(st, err);
-    sc->spectral_valid = false;   // (as in pt_render_spectral)
-    sc->spectral_shards.clear();
-    HIP_TRY(hipSetDevice(sc->device));
-    const size_t n_pixels = (size_t)rd.width * rd.height, spectral_bytes = sizeof(float) * sdp->bins * n_pixels;
-    st = ensure_film_cache(sc, sizeof(float) * 4 * n_pixels);
-    if (st != PT_OK) return st;
-    st = ensure_spectral_cache(sc, spectral_bytes);
-    if (st != PT_OK) return st;
-    const auto t0 = std::chrono::steady_clock::now();
-    st = render_impl(sc, &rd, sc->film_cache, nullptr, profile, &ad, nullptr, 0, sc->spectral_cache, sdp->bins);
-    if (st != PT_OK) return st;
-    HIP_TRY(hipMemcpy(film, sc->film_cache, sizeof(float) * 4 * n_pixels, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(sample_counts, sc->adaptive.counts, sizeof(uint32_t) * n_pixels, hipMemcpyDeviceToHost));
-    if (stats) HIP_TRY(hipMemcpy(stats, sc->adaptive.stats, sizeof(double) * 2 * n_pixels, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(spectral, sc->spectral_cache, spectral_bytes, hipMemcpyDeviceToHost));
-    if (profile) profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (the whole call: set-up, rounds, read-backs)
-    sc->spectral_width = rd.width; sc->spectral_height = rd.height; sc->spectral_bins = sdp->bins; sc->spectral_valid = true;
-    return PT_OK;
+    RenderCall call;
+    call.rd = &rd; call.ad = &ad; call.sd = sdp; call.film = film; call.sample_counts = sample_counts; call.stats = stats; call.spectral = spectral;
+    return render_one(sc, call, profile);
 }
 
 pt_status pt_spectral_resident(pt_scene* sc, uint32_t* width, uint32_t* height, uint32_t* bins) {
@@ -1048,15 +1089,6 @@ pt_status pt_spectral_resident(pt_scene* sc, uint32_t* width, uint32_t* height, 
     return PT_OK;
 }
 
-static pt_status ensure_project_cache(pt_scene* sc, size_t bytes) {
-    if (sc->project_cache_bytes < bytes) {
-        if (sc->project_cache) hipFree(sc->project_cache);
-        sc->project_cache = nullptr; sc->project_cache_bytes = 0;
-        HIP_TRY(hipMalloc(&sc->project_cache, bytes));
-        sc->project_cache_bytes = bytes;
-    }
-    return PT_OK;
-}
 static pt_status project_resident_node(pt_scene* sc, uint32_t K, const float* matrix, float* out);
 
 // include/pt_spectral.h: pt_spectral_project's kernel over spectral_cache, on the stream the render ran on (the null stream), so the bins never cross the bus.
@@ -1071,13 +1103,14 @@ pt_status pt_spectral_project_resident(pt_scene* sc, uint32_t K, const float* ma
     HIP_TRY(hipSetDevice(sc->device));
     const size_t n_pixels = (size_t)sc->spectral_width * sc->spectral_height;
     const size_t matrix_floats = (size_t)PT_SPECTRAL_MAX_RESPONSES * PT_SPECTRAL_MAX_BINS, bytes = sizeof(float) * (matrix_floats + (size_t)K * n_pixels);
-    const pt_status cached = ensure_project_cache(sc, bytes);
+    const pt_status cached = sc->project_cache.reserve(bytes);
     if (cached != PT_OK) return cached;
-    float* d_out = sc->project_cache + matrix_floats;
+    float* d_matrix = sc->project_cache.as<float>();
+    float* d_out = d_matrix + matrix_floats;
     hipStream_t stream = nullptr;
-    HIP_TRY(hipMemcpyAsync(sc->project_cache, matrix, sizeof(float) * K * sc->spectral_bins, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ptk::launch_spectral_project(ptk::spectral_project_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, sc->spectral_bins, K, sc->project_cache,
-                                         sc->spectral_cache, d_out));
+    HIP_TRY(hipMemcpyAsync(d_matrix, matrix, sizeof(float) * K * sc->spectral_bins, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ptk::launch_spectral_project(ptk::spectral_project_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, sc->spectral_bins, K, d_matrix,
+                                         sc->spectral_cache.as<float>(), d_out));
     HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(float) * K * n_pixels, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return PT_OK;
@@ -1144,8 +1177,7 @@ static void multi_release(MultiSetup& m) {
         if (m.films[v]) hipFree(m.films[v]);
     }
     for (size_t p = 0; p < m.comms.size(); ++p) if (m.comms[p]) { hipSetDevice(m.devices[p]); rccl().comm_destroy(m.comms[p]); }
-    for (float* h : m.staging) if (h) hipHostFree(h);
-    m = MultiSetup();
+    m = MultiSetup();   // (the staging buffers go with it)
 }
 
 // Streams, device films and (for more than one physical device) the RCCL communicator of a device set, made once per scene and film size.
@@ -1156,7 +1188,8 @@ static pt_status multi_setup(pt_scene* sc, const std::vector<int>& devices, uint
     m.devices = devices; m.virt = virt; m.rccl = use_rccl; m.film_bytes = film_bytes;
     const size_t nv = devices.size() * virt;
     m.films.assign(nv, nullptr); m.streams.assign(nv, nullptr);
-    m.staging.assign(nv, nullptr); m.staging_bytes.assign(nv, 0);
+    m.staging = std::vector<GrowBuf>(nv);
+    for (GrowBuf& h : m.staging) h.pinned = true;
     for (size_t v = 0; v < nv; ++v) {
         hipError_t e = hipSetDevice(devices[v / virt]);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&m.streams[v], hipStreamNonBlocking);
@@ -1186,7 +1219,7 @@ struct Node {
 };
 static pt_status node_devices(pt_scene* sc, uint64_t device_mask, Node* node) {
     const uint32_t visible = pt_device_count();
-    if (visible == 0) return fail(PT_ERR_NO_DEVICE, "no HIP device available: the product path has no CPU fallback");
+    if (visible == 0) return no_device();
     for (uint32_t d = 0; d < visible && d < 64; ++d) if (device_mask == 0 || ((device_mask >> d) & 1ull)) node->devices.push_back((int)d);
     if (node->devices.empty()) return fail(PT_ERR_INVALID_ARGUMENT, "device_mask names no visible HIP device");
     node->np = (int)node->devices.size();
@@ -1299,21 +1332,11 @@ static pt_status node_prepare_spectral(MultiSetup& m, const Node& node, const pt
         pt_scene* s = node.scene_of[v];
         s->shard_px = pth::shard_pixels(rd.width, rd.height, rd.tile_width, rd.tile_height, node.n > 1 ? (uint32_t)v : 0u, node.n > 1 ? (uint32_t)node.n : 0u);
         HIP_TRY(hipSetDevice(node.devices[v / node.virt]));
-        const pt_status st = ensure_spectral_cache(s, sizeof(float) * bins * ns->plane_pixels);
-        if (st != PT_OK) return st;
         const size_t packed_bytes = sizeof(float) * bins * s->shard_px.size();
-        if (s->shard_packed_bytes < packed_bytes) {
-            if (s->shard_packed) hipFree(s->shard_packed);
-            s->shard_packed = nullptr; s->shard_packed_bytes = 0;
-            HIP_TRY(hipMalloc(&s->shard_packed, packed_bytes));
-            s->shard_packed_bytes = packed_bytes;
-        }
-        if (m.staging_bytes[v] < packed_bytes) {
-            if (m.staging[v]) hipHostFree(m.staging[v]);
-            m.staging[v] = nullptr; m.staging_bytes[v] = 0;
-            HIP_TRY(hipHostMalloc(&m.staging[v], packed_bytes, hipHostMallocPortable));
-            m.staging_bytes[v] = packed_bytes;
-        }
+        pt_status st = s->spectral_cache.reserve(sizeof(float) * bins * ns->plane_pixels);
+        if (st == PT_OK) st = s->shard_packed.reserve(packed_bytes);
+        if (st == PT_OK) st = m.staging[v].reserve(packed_bytes);
+        if (st != PT_OK) return st;
     }
     return PT_OK;
 }
@@ -1325,11 +1348,11 @@ static pt_status node_spectral_exchange(MultiSetup& m, const Node& node, NodeSpe
     const uint32_t n_own = (uint32_t)s->shard_px.size();
     if (n_own == 0) return PT_OK;
     const auto t = std::chrono::steady_clock::now();
-    HIP_TRY(ptk::launch_spectral_pack(ptk::spectral_pack_grid(s->num_cus, n_own), m.streams[v], s->spectral_cache, (uint32_t)ns.plane_pixels, s->buf.pixels, n_own, ns.bins,
-                                      s->shard_packed));
-    HIP_TRY(hipMemcpyAsync(m.staging[v], s->shard_packed, sizeof(float) * ns.bins * n_own, hipMemcpyDeviceToHost, m.streams[v]));
+    HIP_TRY(ptk::launch_spectral_pack(ptk::spectral_pack_grid(s->num_cus, n_own), m.streams[v], s->spectral_cache.as<float>(), (uint32_t)ns.plane_pixels, s->buf.pixels, n_own, ns.bins,
+                                      s->shard_packed.as<float>()));
+    HIP_TRY(hipMemcpyAsync(m.staging[v].p, s->shard_packed.p, sizeof(float) * ns.bins * n_own, hipMemcpyDeviceToHost, m.streams[v]));
     HIP_TRY(hipStreamSynchronize(m.streams[v]));
-    spectral_shard_scatter(m.staging[v], s->shard_px.data(), n_own, ns.bins, ns.host, ns.plane_pixels);
+    spectral_shard_scatter(m.staging[v].as<float>(), s->shard_px.data(), n_own, ns.bins, ns.host, ns.plane_pixels);
     ns.seconds[v] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
     return PT_OK;
 }
@@ -1351,12 +1374,13 @@ static pt_status project_resident_node(pt_scene* sc, uint32_t K, const float* ma
         const uint32_t n_own = (uint32_t)s->shard_px.size();
         if (n_own == 0) continue;
         HIP_TRY(hipSetDevice(s->device));
-        const pt_status st = ensure_project_cache(s, sizeof(float) * (matrix_floats + (size_t)K * n_own));
+        const pt_status st = s->project_cache.reserve(sizeof(float) * (matrix_floats + (size_t)K * n_own));
         if (st != PT_OK) return st;
         planes[v].resize((size_t)K * n_own);
-        float* d_out = s->project_cache + matrix_floats;
-        HIP_TRY(hipMemcpyAsync(s->project_cache, matrix, sizeof(float) * K * sc->spectral_bins, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(ptk::launch_spectral_project(ptk::spectral_project_grid(s->num_cus, n_own), nullptr, n_own, sc->spectral_bins, K, s->project_cache, s->shard_packed, d_out));
+        float* d_matrix = s->project_cache.as<float>();
+        float* d_out = d_matrix + matrix_floats;
+        HIP_TRY(hipMemcpyAsync(d_matrix, matrix, sizeof(float) * K * sc->spectral_bins, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(ptk::launch_spectral_project(ptk::spectral_project_grid(s->num_cus, n_own), nullptr, n_own, sc->spectral_bins, K, d_matrix, s->shard_packed.as<float>(), d_out));
         HIP_TRY(hipMemcpyAsync(planes[v].data(), d_out, sizeof(float) * K * n_own, hipMemcpyDeviceToHost, nullptr));
     }
     for (size_t v = 0; v < sc->spectral_shards.size(); ++v) {
@@ -1369,87 +1393,16 @@ static pt_status project_resident_node(pt_scene* sc, uint32_t K, const float* ma
     return PT_OK;
 }
 
-// pt_render_multi and, with `sdp` (pt_render_spectral_multi; its arguments checked, rdp normalised), its spectral form
-static pt_status render_multi_impl(pt_scene* sc, const pt_render_desc* rdp, uint64_t device_mask, float* film, pt_profile* profile, const pt_spectral_desc* sdp,
-                                   float* spectral) {
+// The node driver behind the four node entries (call: as for render_one): one worker per (virtual) device renders its shard of the film, the films are gathered
+// on the first device of the mask and read back from there.  An adaptive call (pt_render_adaptive_multi) runs its rounds in lockstep over the NodeRounds and
+// gathers counts and statistics too; a spectral call hands every worker's bins over by node_spectral_exchange and leaves the packed shards resident.
+static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t device_mask, pt_profile* profile) {
+    const pt_render_desc& rd = *call.rd;
+    const bool adaptive = call.ad != nullptr;
     Node node;
     pt_status st = node_devices(sc, device_mask, &node);
     if (st != PT_OK) return st;
-    if (node.single(sc)) return sdp ? pt_render_spectral(sc, rdp, sdp, film, spectral, profile) : pt_render(sc, rdp, film, profile);
-
-    DeviceGuard guard;
-    const auto t_entry = std::chrono::steady_clock::now();
-    const size_t bytes = sizeof(float) * 4 * (size_t)rdp->width * rdp->height;
-    st = node_prepare(sc, node, bytes);
-    if (st != PT_OK) return st;
-    MultiSetup& m = sc->multi;
-    const int n = node.n;
-    NodeSpectral ns;
-    if (sdp) {
-        st = node_prepare_spectral(m, node, *rdp, sdp->bins, spectral, &ns);
-        if (st != PT_OK) return st;
-    }
-    std::vector<pt_status> status(n, PT_OK);
-    std::vector<std::string> errors(n);
-    std::vector<pt_profile> profiles(n);
-    const auto t0 = std::chrono::steady_clock::now();
-    node_run(n, [&](int v) {
-        auto bad = [&](pt_status s2, const std::string& msg) { status[v] = s2; errors[v] = msg; };
-        if (hipSetDevice(node.devices[v / node.virt]) != hipSuccess) return bad(PT_ERR_DEVICE, "hipSetDevice failed");
-        pt_render_desc rd = *rdp;
-        if (n > 1) { rd.shard_index = (uint32_t)v; rd.shard_count = (uint32_t)n; }
-        pt_scene* s = node.scene_of[v];
-        pt_status s2 = sdp ? render_impl(s, &rd, m.films[v], m.streams[v], &profiles[v], nullptr, nullptr, 0, s->spectral_cache, sdp->bins, &s->shard_px)
-                           : render_impl(s, &rd, m.films[v], m.streams[v], &profiles[v]);
-        if (s2 == PT_OK && sdp) s2 = node_spectral_exchange(m, node, ns, v);
-        if (s2 != PT_OK) bad(s2, g_error);   // (g_error is thread-local: carried back to the caller below)
-    });
-    for (int v = 0; v < n; ++v) if (status[v] != PT_OK) return fail(status[v], device_name(node, v) + ": " + errors[v]);
-    // the only exchange step of the path
-    const auto t_reduce = std::chrono::steady_clock::now();
-    const size_t pixels = (size_t)rdp->width * rdp->height;
-    st = node_gather(m, node, {GatherPart{std::vector<void*>(m.films.begin(), m.films.begin() + n), pixels * 4, ncclFloat}});
-    if (st != PT_OK) return st;
-    const auto t1 = std::chrono::steady_clock::now();
-    HIP_TRY(hipSetDevice(node.devices[0]));
-    HIP_TRY(hipMemcpy(film, m.films[0], bytes, hipMemcpyDeviceToHost));
-    if (profile) {
-        node_profile(profiles, profile);
-        profile->seconds = std::chrono::duration<double>(t1 - t0).count();
-        profile->kernel_seconds[5] = std::chrono::duration<double>(t0 - t_entry).count();    // set-up (replicas, streams, films, communicator): ~0 on a repeated call
-        profile->kernel_seconds[6] = std::chrono::duration<double>(t1 - t_reduce).count() + node_spectral_seconds(ns);   // the film reduce (+ the longest pack, copy and scatter)
-    }
-    if (sdp) node_spectral_resident(sc, node, *rdp, sdp->bins);
-    return PT_OK;
-}
-
-pt_status pt_render_multi(pt_scene* sc, const pt_render_desc* rdp, uint64_t device_mask, float* film, pt_profile* profile) {
-    if (!sc || !rdp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    if (rdp->width == 0 || rdp->height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
-    if (rdp->shard_count > 1) return fail(PT_ERR_INVALID_ARGUMENT, "pt_render_multi deals the tiles itself: shard_count must be 0");
-    return render_multi_impl(sc, rdp, device_mask, film, profile, nullptr, nullptr);
-}
-
-pt_status pt_render_spectral_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_spectral_desc* sdp, uint64_t device_mask, float* film, float* spectral,
-                                   pt_profile* profile) {
-    if (sc) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts; whatever it is refused for, no film is resident after it)
-    pt_render_desc rd;
-    std::string err;
-    const pt_status st = pth::check_spectral_multi_args(sc, rdp, sdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, film, spectral, &rd, &err);
-    if (st != PT_OK) return fail(st, err);
-    return render_multi_impl(sc, &rd, device_mask, film, profile, sdp, spectral);
-}
-
-// pt_render_adaptive_multi (rdp, adp: the caller's; rd, ad: normalised from them) and, with `sdp` (pt_render_adaptive_spectral_multi; its arguments checked), its
-// spectral form
-static pt_status render_adaptive_multi_impl(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, const pt_render_desc& rd, const pt_adaptive_desc& ad,
-                                            uint64_t device_mask, float* film, uint32_t* sample_counts, double* stats, pt_profile* profile, const pt_spectral_desc* sdp,
-                                            float* spectral) {
-    Node node;
-    pt_status st = node_devices(sc, device_mask, &node);
-    if (st != PT_OK) return st;
-    if (node.single(sc)) return sdp ? pt_render_adaptive_spectral(sc, rdp, adp, sdp, film, sample_counts, stats, spectral, profile)
-                                    : pt_render_adaptive(sc, rdp, adp, film, sample_counts, stats, profile);
+    if (node.single(sc)) return render_one(sc, call, profile);   // (the one-device entry's body: its checks are among this call's, and have passed)
 
     DeviceGuard guard;
     const auto t_entry = std::chrono::steady_clock::now();
@@ -1459,53 +1412,59 @@ static pt_status render_adaptive_multi_impl(pt_scene* sc, const pt_render_desc* 
     MultiSetup& m = sc->multi;
     const int n = node.n;
     const uint32_t virt = node.virt;
-    for (int v = 0; v < n; ++v) {   // (the adaptive buffers exist before the workers start: the exchange reads every device's image)
+    for (int v = 0; v < n && adaptive; ++v) {   // (the adaptive buffers exist before the workers start: the exchange reads every device's image)
         HIP_TRY(hipSetDevice(node.devices[v / virt]));
         st = ensure_adaptive_buffers(node.scene_of[v], pixels);
         if (st != PT_OK) return st;
     }
     NodeSpectral ns;
-    if (sdp) {
-        st = node_prepare_spectral(m, node, rd, sdp->bins, spectral, &ns);
+    if (call.sd) {
+        st = node_prepare_spectral(m, node, rd, call.sd->bins, call.spectral, &ns);
         if (st != PT_OK) return st;
     }
     NodeRounds nr;
-    nr.lock.parties = n;
-    nr.next.assign(n, 0u);
-    for (int v = 0; v < n; ++v) nr.images.push_back(node.scene_of[v]->adaptive.unconverged);
-    for (int v = 0; v < n; ++v) nr.merged.push_back(nr.images[(size_t)(v / (int)virt) * virt]);
-    // the exchange of a round (run by the last worker to arrive): the images of the virtual devices ORed on their physical device, then one grouped
-    // all-reduce (max = OR: the shards are disjoint) between the physical devices; every first virtual device then holds the film-wide image
-    nr.exchange = [&]() -> pt_status {
-        const auto t = std::chrono::steady_clock::now();
-        int here = 0;
-        HIP_TRY(hipGetDevice(&here));
-        const unsigned blocks = (unsigned)std::min<size_t>(1024, std::max<size_t>(1, (pixels / 16 + kBlock - 1) / kBlock));
-        for (int p = 0; p < node.np && virt > 1; ++p) {
-            HIP_TRY(hipSetDevice(node.devices[p]));
-            for (uint32_t j = 1; j < virt; ++j)
-                hipLaunchKernelGGL(k_mask_or, dim3(blocks), dim3(kBlock), 0, m.streams[(size_t)p * virt], nr.images[(size_t)p * virt], nr.images[(size_t)p * virt + j], pixels);
-            HIP_TRY(hipGetLastError());
-        }
-        if (node.use_rccl) {
-            ncclResult_t rc = rccl().group_start();
-            for (int p = 0; p < node.np && rc == ncclSuccess; ++p) {
-                hipSetDevice(node.devices[p]);
-                uint8_t* img = nr.images[(size_t)p * virt];
-                rc = rccl().all_reduce(img, img, pixels, ncclUint8, ncclMax, m.comms[p], m.streams[(size_t)p * virt]);
+    if (adaptive) {
+        nr.lock.parties = n;
+        nr.next.assign(n, 0u);
+        for (int v = 0; v < n; ++v) nr.images.push_back(node.scene_of[v]->adaptive.unconverged);
+        for (int v = 0; v < n; ++v) nr.merged.push_back(nr.images[(size_t)(v / (int)virt) * virt]);
+        // the exchange of a round (run by the last worker to arrive): the images of the virtual devices ORed on their physical device, then one grouped
+        // all-reduce (max = OR: the shards are disjoint) between the physical devices; every first virtual device then holds the film-wide image
+        nr.exchange = [&]() -> pt_status {
+            const auto t = std::chrono::steady_clock::now();
+            int here = 0;
+            HIP_TRY(hipGetDevice(&here));
+            const unsigned blocks = (unsigned)std::min<size_t>(1024, std::max<size_t>(1, (pixels / 16 + kBlock - 1) / kBlock));
+            for (int p = 0; p < node.np && virt > 1; ++p) {
+                HIP_TRY(hipSetDevice(node.devices[p]));
+                for (uint32_t j = 1; j < virt; ++j)
+                    hipLaunchKernelGGL(k_mask_or, dim3(blocks), dim3(kBlock), 0, m.streams[(size_t)p * virt], nr.images[(size_t)p * virt], nr.images[(size_t)p * virt + j], pixels);
+                HIP_TRY(hipGetLastError());
             }
-            ncclResult_t rc2 = rccl().group_end();
-            if (rc == ncclSuccess) rc = rc2;
-            if (rc != ncclSuccess) { hipSetDevice(here); return fail(PT_ERR_DEVICE, std::string("ncclAllReduce: ") + rccl().error_string(rc)); }
-        }
-        for (int p = 0; p < node.np; ++p) {
-            HIP_TRY(hipSetDevice(node.devices[p]));
-            HIP_TRY(hipStreamSynchronize(m.streams[(size_t)p * virt]));
-        }
-        HIP_TRY(hipSetDevice(here));
-        nr.exchange_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-        return PT_OK;
-    };
+            if (node.use_rccl) {
+                ncclResult_t rc = rccl().group_start();
+                for (int p = 0; p < node.np && rc == ncclSuccess; ++p) {
+                    hipSetDevice(node.devices[p]);
+                    uint8_t* img = nr.images[(size_t)p * virt];
+                    rc = rccl().all_reduce(img, img, pixels, ncclUint8, ncclMax, m.comms[p], m.streams[(size_t)p * virt]);
+                }
+                ncclResult_t rc2 = rccl().group_end();
+                if (rc == ncclSuccess) rc = rc2;
+                if (rc != ncclSuccess) { hipSetDevice(here); return fail(PT_ERR_DEVICE, std::string("ncclAllReduce: ") + rccl().error_string(rc)); }
+            }
+            for (int p = 0; p < node.np; ++p) {
+                HIP_TRY(hipSetDevice(node.devices[p]));
+                HIP_TRY(hipStreamSynchronize(m.streams[(size_t)p * virt]));
+            }
+            HIP_TRY(hipSetDevice(here));
+            nr.exchange_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+            return PT_OK;
+        };
+    }
+    // a worker's failure: `device N[.j]: <message>`.  The fixed form reports the failure of the lowest device; in the adaptive form the first failure stops the
+    // others (Lockstep) and is the one reported.
+    std::vector<pt_status> status(n, PT_OK);
+    std::vector<std::string> errors(n);
     std::vector<pt_profile> profiles(n);
     const auto t0 = std::chrono::steady_clock::now();
     node_run(n, [&](int v) {
@@ -1513,33 +1472,66 @@ static pt_status render_adaptive_multi_impl(pt_scene* sc, const pt_render_desc* 
         pt_render_desc rv = rd;
         if (n > 1) { rv.shard_index = (uint32_t)v; rv.shard_count = (uint32_t)n; }
         pt_scene* s = node.scene_of[v];
-        if (s2 == PT_OK) s2 = sdp ? render_impl(s, &rv, m.films[v], m.streams[v], &profiles[v], &ad, &nr, v, s->spectral_cache, sdp->bins, &s->shard_px)
-                                  : render_impl(s, &rv, m.films[v], m.streams[v], &profiles[v], &ad, &nr, v);
-        if (s2 == PT_OK && sdp) s2 = node_spectral_exchange(m, node, ns, v);
-        if (s2 != PT_OK) nr.lock.stop(s2, device_name(node, v) + ": " + g_error);   // (a worker stopped by another's failure finds the first error kept)
+        RenderJob job;
+        if (adaptive) { job.adaptive = call.ad; job.node = &nr; job.node_index = v; }
+        if (call.sd) { job.d_spectral = s->spectral_cache.as<float>(); job.spectral_bins = call.sd->bins; job.shard_list = &s->shard_px; }
+        if (s2 == PT_OK) s2 = render_impl(s, &rv, m.films[v], m.streams[v], &profiles[v], job);
+        if (s2 == PT_OK && call.sd) s2 = node_spectral_exchange(m, node, ns, v);
+        if (s2 == PT_OK) return;
+        status[v] = s2; errors[v] = device_name(node, v) + ": " + g_error;   // (g_error is thread-local: carried back to the caller below)
+        if (adaptive) nr.lock.stop(s2, errors[v]);   // (a worker stopped by another's failure finds the first error kept)
     });
     if (nr.lock.failed) return fail(nr.lock.status, nr.lock.error);
+    for (int v = 0; v < n; ++v) if (status[v] != PT_OK) return fail(status[v], errors[v]);
+    // the only exchange step of the fixed path
     const auto t_gather = std::chrono::steady_clock::now();
-    std::vector<GatherPart> parts = {GatherPart{std::vector<void*>(m.films.begin(), m.films.begin() + n), pixels * 4, ncclFloat},
-                                     GatherPart{{}, pixels, ncclUint32}, GatherPart{{}, 2 * pixels, ncclFloat64}};
-    for (int v = 0; v < n; ++v) { parts[1].bufs.push_back(node.scene_of[v]->adaptive.counts); parts[2].bufs.push_back(node.scene_of[v]->adaptive.stats); }
-    if (!stats) parts.pop_back();
+    std::vector<GatherPart> parts = {GatherPart{std::vector<void*>(m.films.begin(), m.films.begin() + n), pixels * 4, ncclFloat}};
+    if (adaptive) {
+        parts.insert(parts.end(), {GatherPart{{}, pixels, ncclUint32}, GatherPart{{}, 2 * pixels, ncclFloat64}});
+        for (int v = 0; v < n; ++v) { parts[1].bufs.push_back(node.scene_of[v]->adaptive.counts); parts[2].bufs.push_back(node.scene_of[v]->adaptive.stats); }
+        if (!call.stats) parts.pop_back();
+    }
     st = node_gather(m, node, parts);
     if (st != PT_OK) return st;
     const auto t_gathered = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(node.devices[0]));
-    HIP_TRY(hipMemcpy(film, m.films[0], bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(sample_counts, node.scene_of[0]->adaptive.counts, sizeof(uint32_t) * pixels, hipMemcpyDeviceToHost));
-    if (stats) HIP_TRY(hipMemcpy(stats, node.scene_of[0]->adaptive.stats, sizeof(double) * 2 * pixels, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(call.film, m.films[0], bytes, hipMemcpyDeviceToHost));
+    if (adaptive) {
+        HIP_TRY(hipMemcpy(call.sample_counts, node.scene_of[0]->adaptive.counts, sizeof(uint32_t) * pixels, hipMemcpyDeviceToHost));
+        if (call.stats) HIP_TRY(hipMemcpy(call.stats, node.scene_of[0]->adaptive.stats, sizeof(double) * 2 * pixels, hipMemcpyDeviceToHost));
+    }
     if (profile) {
         node_profile(profiles, profile);
-        profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count();   // (the whole call: set-up, rounds, gather, read-backs)
-        profile->kernel_launches[5] = profiles[0].kernel_launches[5];                                          // the rounds (every device ran them all)
-        profile->kernel_seconds[5] = std::chrono::duration<double>(t0 - t_entry).count();                    // set-up: ~0 on a repeated call
-        profile->kernel_seconds[6] = nr.exchange_seconds + std::chrono::duration<double>(t_gathered - t_gather).count() + node_spectral_seconds(ns);   // the rounds' exchanges + the gather (+ the longest pack, copy and scatter)
+        // seconds: the workers and the gather for the fixed form; for the adaptive form the whole call (set-up, rounds, gather, read-backs)
+        profile->seconds = std::chrono::duration<double>(adaptive ? std::chrono::steady_clock::now() - t_entry : t_gathered - t0).count();
+        if (adaptive) profile->kernel_launches[5] = profiles[0].kernel_launches[5];                        // the rounds (every device ran them all)
+        profile->kernel_seconds[5] = std::chrono::duration<double>(t0 - t_entry).count();    // set-up (replicas, streams, films, communicator): ~0 on a repeated call
+        // the rounds' exchanges (adaptive) + the film reduce or gather (+ the longest pack, copy and scatter)
+        profile->kernel_seconds[6] = nr.exchange_seconds + std::chrono::duration<double>(t_gathered - t_gather).count() + node_spectral_seconds(ns);
     }
-    if (sdp) node_spectral_resident(sc, node, rd, sdp->bins);
+    if (call.sd) node_spectral_resident(sc, node, rd, call.sd->bins);
     return PT_OK;
+}
+
+pt_status pt_render_multi(pt_scene* sc, const pt_render_desc* rdp, uint64_t device_mask, float* film, pt_profile* profile) {
+    if (!sc || !rdp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    if (rdp->width == 0 || rdp->height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
+    if (rdp->shard_count > 1) return fail(PT_ERR_INVALID_ARGUMENT, "pt_render_multi deals the tiles itself: shard_count must be 0");
+    RenderCall call;
+    call.rd = rdp; call.film = film;
+    return render_node(sc, call, device_mask, profile);
+}
+
+pt_status pt_render_spectral_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_spectral_desc* sdp, uint64_t device_mask, float* film, float* spectral,
+                                   pt_profile* profile) {
+    if (sc) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts; whatever it is refused for, no film is resident after it)
+    pt_render_desc rd;
+    std::string err;
+    const pt_status st = pth::check_spectral_multi_args(sc, rdp, sdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, film, spectral, &rd, &err);
+    if (st != PT_OK) return fail(st, err);
+    RenderCall call;
+    call.rd = &rd; call.sd = sdp; call.film = film; call.spectral = spectral;
+    return render_node(sc, call, device_mask, profile);
 }
 
 pt_status pt_render_adaptive_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, uint64_t device_mask, float* film,
@@ -1550,7 +1542,9 @@ pt_status pt_render_adaptive_multi(pt_scene* sc, const pt_render_desc* rdp, cons
     std::string err;
     const pt_status st = pth::normalize_adaptive_desc(*rdp, *adp, sample_counts != nullptr, (uint32_t)sc->host.cameras.size(), &rd, &ad, &err);
     if (st != PT_OK) return fail(st, err);
-    return render_adaptive_multi_impl(sc, rdp, adp, rd, ad, device_mask, film, sample_counts, stats, profile, nullptr, nullptr);
+    RenderCall call;
+    call.rd = &rd; call.ad = &ad; call.film = film; call.sample_counts = sample_counts; call.stats = stats;
+    return render_node(sc, call, device_mask, profile);
 }
 
 pt_status pt_render_adaptive_spectral_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, const pt_spectral_desc* sdp, uint64_t device_mask,
@@ -1561,7 +1555,9 @@ pt_status pt_render_adaptive_spectral_multi(pt_scene* sc, const pt_render_desc* 
     std::string err;
     const pt_status st = pth::check_adaptive_spectral_args(sc, rdp, adp, sdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, film, sample_counts, spectral, &rd, &ad, &err);
     if (st != PT_OK) return fail(st, err);
-    return render_adaptive_multi_impl(sc, rdp, adp, rd, ad, device_mask, film, sample_counts, stats, profile, sdp, spectral);
+    RenderCall call;
+    call.rd = &rd; call.ad = &ad; call.sd = sdp; call.film = film; call.sample_counts = sample_counts; call.stats = stats; call.spectral = spectral;
+    return render_node(sc, call, device_mask, profile);
 }
 
 pt_status pt_intersect(pt_scene* sc, size_t n, const float* origins, const float* directions, pt_hit* hits) {

@@ -133,6 +133,21 @@ class DenoiseDesc(C.Structure):
                 ("normal_power_log2", C.c_uint32), ("device", C.c_uint32), ("reserved", C.c_uint32 * 1)]
 
 
+# include/pt_resident.h: the parts of a scene's resident set, and pt_resident_denoise_desc's flag
+RESIDENT_FILM, RESIDENT_BINS, RESIDENT_GUIDES, RESIDENT_ALBEDO, RESIDENT_BIN_ALBEDO, RESIDENT_DENOISED, RESIDENT_DENOISED_BINS = (1 << i for i in range(7))
+RESIDENT_PLANAR_GATHER = 1
+
+
+class ResidentInfo(C.Structure):
+    """struct pt_resident_info (include/pt_resident.h): the resident set's size, bins and RESIDENT_* bits."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("bins", C.c_uint32), ("parts", C.c_uint32)]
+
+
+class ResidentDenoiseDesc(C.Structure):
+    """pt_resident_denoise_desc (include/pt_resident.h): the filter's parameters (size 0 = the resident one; the device is ignored) and the gather's form."""
+    _fields_ = [("filter", DenoiseDesc), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 class GuideChainDesc(C.Structure):
     """pt_guide_chain_desc (include/pt_denoise.h): the specular vertices followed per guide sample, the GGX alpha up to which a material is specular (0 = 0.01)."""
     _fields_ = [("max_chain", C.c_uint32), ("alpha_max", C.c_float), ("reserved", C.c_uint32 * 2)]
@@ -291,6 +306,13 @@ class Library:
         self._spectral_project = bind("spectral_project", C.c_int32, [u32, u32, u32, u32, fpp, fpp, fpp], required=False)
         self._spectral_project_resident = bind("spectral_project_resident", C.c_int32, [vp, u32, fpp, fpp], required=False)
         self._spectral_resident = bind("spectral_resident", C.c_int32, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)], required=False)
+        # include/pt_resident.h (an emulation library may lack these)
+        self._resident_info = bind("resident_info", C.c_int32, [vp, C.POINTER(ResidentInfo)], required=False)
+        self._resident_guides = bind("resident_guides", C.c_int32, [vp, C.POINTER(RenderDesc), u32, C.POINTER(GuideChainDesc), u32], required=False)
+        self._resident_load = bind("resident_load", C.c_int32, [vp, u32, u32, u32, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp], required=False)
+        self._denoise_resident = bind("denoise_resident", C.c_int32, [vp, C.POINTER(ResidentDenoiseDesc), fpp, fpp, fpp], required=False)
+        self._spectral_project_resident_denoised = bind("spectral_project_resident_denoised", C.c_int32, [vp, u32, fpp, fpp], required=False)
+        self._resident_last_error = bind("resident_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the five entries above)
         self._spectral_project_last_error = bind("spectral_project_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the entries above)
         self._device_info = bind("device_info", C.c_char_p, [], required=False)
         self._output_film = bind("output_film", C.c_int32, [C.POINTER(OutputDesc), fpp, C.POINTER(C.c_uint8), fpp], required=False)
@@ -603,9 +625,79 @@ class Scene:
         self.library.check(self.library._spectral_resident(self.handle, C.byref(w), C.byref(h), C.byref(b)))
         return (w.value, h.value, b.value) if b.value else None
 
-    def spectral_project_resident(self, matrix):
+    def _resident_entry(self, name):
+        entry = getattr(self.library, "_" + name)
+        if entry is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %s%s entry" % (self.library.path, self.library.prefix, name))
+        return entry
+
+    def _resident_check(self, status):
+        if status != PT_OK:
+            err = self.library._resident_last_error
+            raise PtError(status, err().decode() if err else self.library.last_error())
+
+    def resident_info(self):
+        """pt_resident_info: (width, height, bins, parts) of the scene's resident set — parts a set of RESIDENT_* bits, all zeros when nothing is resident."""
+        info = ResidentInfo()
+        self._resident_check(self._resident_entry("resident_info")(self.handle, C.byref(info)))
+        return info.width, info.height, info.bins, info.parts
+
+    def resident_guides(self, rd, guide_samples=4, specular_chain=0, alpha_max=0.0, albedo=False, bin_albedo=False):
+        """pt_resident_guides: render_guides (render_guides_albedo with albedo, render_guides_bin_albedo over the resident bins with bin_albedo too; with
+        specular_chain > 0 at the end of every sample's specular chain) for the resident film, the outputs kept on the device as resident parts."""
+        cd = GuideChainDesc(specular_chain, alpha_max)
+        flags = (RESIDENT_ALBEDO if albedo else 0) | (RESIDENT_BIN_ALBEDO if bin_albedo else 0)
+        self._resident_check(self._resident_entry("resident_guides")(self.handle, C.byref(rd), guide_samples, C.byref(cd) if specular_chain > 0 else None, flags))
+
+    def resident_load(self, film=None, counts=None, stats=None, guides=None, spectral=None, albedo=None, bin_albedo=None):
+        """pt_resident_load: host arrays adopted as resident parts — film [H,W,4], counts [H,W] u32 and stats [H,W,2] f64 together, guides [H,W,4],
+        spectral [B,H,W], albedo [H,W,4], bin_albedo [B,H,W]; what is None stays as it is.  The size is taken from the arrays given."""
+        def arr(a, dtype):
+            return None if a is None else np.ascontiguousarray(a, dtype=dtype)
+        film, counts, stats = arr(film, np.float32), arr(counts, np.uint32), arr(stats, np.float64)
+        spectral, guides, albedo, bin_albedo = (arr(a, np.float32) for a in (spectral, guides, albedo, bin_albedo))
+        sizes = {a.shape[:2] for a in (film, counts, stats, guides, albedo) if a is not None} | {a.shape[1:] for a in (spectral, bin_albedo) if a is not None}
+        nbins = {a.shape[0] for a in (spectral, bin_albedo) if a is not None}
+        if len(sizes) > 1 or len(nbins) > 1 or any(a is not None and a.ndim != 3 for a in (film, stats, spectral, guides, albedo, bin_albedo)):
+            raise ValueError("film [H,W,4], counts [H,W], stats [H,W,2], spectral [B,H,W], guides [H,W,4], albedo [H,W,4] and bin_albedo [B,H,W] of one size")
+        h, w = sizes.pop() if sizes else (0, 0)
+        for a, last in ((film, 4), (stats, 2), (guides, 4), (albedo, 4)):
+            if a is not None and a.shape[2] != last:
+                raise ValueError("film, guides and albedo [H,W,4], stats [H,W,2]")
+        p = lambda a: _fp(a) if a is not None else None
+        self._resident_check(self._resident_entry("resident_load")(
+            self.handle, w, h, nbins.pop() if nbins else 0, p(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)) if counts is not None else None,
+            stats.ctypes.data_as(C.POINTER(C.c_double)) if stats is not None else None, p(spectral), p(guides), p(albedo), p(bin_albedo)))
+
+    def denoise_resident(self, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, film=True, variance=False, spectral=False, planar=False):
+        """pt_denoise_resident: the filter over the resident set, where it lies.  Returns the tuple of what was asked for, in this order: the denoised film
+        [H,W,4] (film), its variance [H,W] (variance), the denoised bins [B,H,W] (spectral) — one array when one is asked for, None when none is.  What is
+        not asked for does not cross the bus; all of it stays resident.  `planar`: the passes over plane-major bins; the bits are the same."""
+        w, h, bins, _ = self.resident_info()
+        d = ResidentDenoiseDesc(DenoiseDesc(0, 0, iterations, sigma_luminance, sigma_depth, normal_power_log2, 0), RESIDENT_PLANAR_GATHER if planar else 0)
+        out = np.zeros((h, w, 4), np.float32) if film else None
+        var = np.zeros((h, w), np.float32) if variance else None
+        sp = np.zeros((bins, h, w), np.float32) if spectral else None
+        self._resident_check(self._resident_entry("denoise_resident")(self.handle, C.byref(d), _fp(out) if film else None, _fp(var) if variance else None,
+                                                                      _fp(sp) if spectral else None))
+        res = tuple(a for a in (out, var, sp) if a is not None)
+        return res[0] if len(res) == 1 else (res if res else None)
+
+    def spectral_project_resident(self, matrix, denoised=False):
         """pt_spectral_project_resident: Library.spectral_project of the resident spectral film with matrix [K,B] — float32 [K,H,W], bit for bit what
-        spectral_project gives for the array that render returned — without the bins crossing the bus."""
+        spectral_project gives for the array that render returned — without the bins crossing the bus.  `denoised`:
+        pt_spectral_project_resident_denoised, the same of the bins that denoise_resident left on the device."""
+        if denoised:
+            entry = self._resident_entry("spectral_project_resident_denoised")
+            matrix = np.ascontiguousarray(matrix, dtype=np.float32)
+            if matrix.ndim != 2:
+                raise ValueError("matrix [K,B]")
+            w, h, bins, parts = self.resident_info()
+            if (parts & RESIDENT_DENOISED_BINS) and matrix.shape[1] != bins:
+                raise ValueError("matrix [K,B] with B = %d, the resident film's bins" % bins)
+            out = np.zeros((matrix.shape[0], h, w), np.float32)
+            self._resident_check(entry(self.handle, matrix.shape[0], _fp(matrix), _fp(out)))
+            return out
         if self.library._spectral_project_resident is None:
             raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sspectral_project_resident entry" % (self.library.path, self.library.prefix))
         matrix = np.ascontiguousarray(matrix, dtype=np.float32)
@@ -734,12 +826,19 @@ class Scene:
         return g, a, ba
 
     def render_denoised(self, rd, max_samples=None, rel_error=0.0, abs_error=0.0, step=0, guide_samples=4, iterations=0, sigma_luminance=0.0, sigma_depth=0.0,
-                        normal_power_log2=0, device_mask=None, albedo=False, specular_chain=None):
+                        normal_power_log2=0, device_mask=None, albedo=False, specular_chain=None, resident=False):
         """An adaptive render with statistics (max_samples None = rd.spp: a fixed count), its guides, and the filter: (film, denoised, counts, profile).
         `device_mask` (not None) routes the render through render_adaptive_multi; the filter then runs on the first device of the mask.  `albedo`: the
         guides come with the albedo (render_guides_albedo) and the filter demodulates the film by it.  `specular_chain` (not None): the guides, and the
-        albedo if asked for, come from render_guides_chain with this max_chain."""
+        albedo if asked for, come from render_guides_chain with this max_chain.  `resident`: guides and filter run on what the render left on the device
+        (resident_guides, denoise_resident); the tuple is the same, bit for bit.  A node render leaves no such film: refused with a device_mask."""
         mx = rd.spp if max_samples is None else max_samples
+        if resident:
+            if device_mask is not None:
+                raise PtError(PT_ERR_UNSUPPORTED, "render_denoised: resident=True takes no device_mask (a node render leaves no film one device can filter)")
+            film, counts, st, prof = self.render_adaptive(rd, mx, rel_error, abs_error, step, stats=True)
+            self.resident_guides(rd, guide_samples, specular_chain or 0, albedo=albedo)
+            return film, self.denoise_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2), counts, prof
         if device_mask is None:
             film, counts, st, prof = self.render_adaptive(rd, mx, rel_error, abs_error, step, stats=True)
             device = 0
@@ -756,15 +855,23 @@ class Scene:
         return film, den, counts, prof
 
     def render_denoised_spectral(self, rd, bins, max_samples=None, rel_error=0.0, guide_samples=4, specular_chain=0, abs_error=0.0, step=0, iterations=0,
-                                 sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, albedo=False, bin_albedo=False, device_mask=None):
+                                 sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, albedo=False, bin_albedo=False, resident=False, device_mask=None):
         """render_adaptive_spectral with statistics (max_samples None = rd.spp: a fixed count), its guides — render_guides, or render_guides_chain with max_chain
         `specular_chain` when that is positive — and denoise_spectral: (film, denoised, spectral, denoised_spectral, counts, profile).  `albedo` is refused, as
         denoise_spectral refuses it.  `bin_albedo`: guides, XYZ albedo and per-bin albedo come from one render_guides_bin_albedo call (with `specular_chain` as its
         max_chain) and the filter is denoise_spectral_albedo: the film demodulated by the XYZ albedo, the bins by the per-bin albedo.  `device_mask` (not None)
-        routes the render through render_adaptive_spectral_multi; the filter then runs on the first device of the mask."""
+        routes the render through render_adaptive_spectral_multi; the filter then runs on the first device of the mask.  `resident`: guides and filter run on
+        what the render left on the device (resident_guides, denoise_resident); the tuple is the same, bit for bit; refused with a device_mask."""
         if albedo:
             raise PtError(PT_ERR_UNSUPPORTED, "render_denoised_spectral takes no albedo: demodulating the bins needs a per-bin albedo (bin_albedo=True renders one)")
         mx = rd.spp if max_samples is None else max_samples
+        if resident:
+            if device_mask is not None:
+                raise PtError(PT_ERR_UNSUPPORTED, "render_denoised_spectral: resident=True takes no device_mask (a node render leaves no film one device can filter)")
+            film, counts, st, spectral, prof = self.render_adaptive_spectral(rd, bins, mx, rel_error, abs_error, step, stats=True)
+            self.resident_guides(rd, guide_samples, specular_chain, albedo=bin_albedo, bin_albedo=bin_albedo)
+            den, den_spectral = self.denoise_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2, spectral=True)
+            return film, den, spectral, den_spectral, counts, prof
         if device_mask is None:
             film, counts, st, spectral, prof = self.render_adaptive_spectral(rd, bins, mx, rel_error, abs_error, step, stats=True)
             device = 0

@@ -5,7 +5,7 @@
 //   ptcli [--config data/config.toml] [--scene FILE] [-n|--dry-run] [--stdout-log-level L] [--write-log-level L]
 //         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K] [--demodulate-albedo]
 //         [--guide-chain D] [--guide-alpha-max A] [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]
-//         [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK]
+//         [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK] [--denoise-resident]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -37,6 +37,10 @@
 // integrates the responses over each bin with N samples.  With --spectral-bins the bins are developed where the render left them on the device
 // (pt_spectral_project_resident); with --denoise-spectral-bins the undenoised bins go through pt_spectral_project, and the denoised ones too, to
 // <filename>_denoised_developed.*.  Every other file stays byte for byte what it is.  An unknown curve name ends the program once the scene file is loaded.
+// --denoise-resident (with --denoise only) runs the guides, the filter and, with --develop, both developments on what the render left on the device
+// (include/pt_resident.h: pt_resident_guides, pt_denoise_resident, pt_spectral_project_resident and pt_spectral_project_resident_denoised): the film and the
+// bins are not uploaded again.  Every file stays byte for byte what the run without it writes.  It is refused together with --devices and --spectral-devices:
+// a node render leaves no film one device can filter.
 // --spectral-devices MASK (with --spectral-bins or --denoise-spectral-bins only; bit d = HIP device d, 0 = all) renders the spectral film on the devices of MASK from
 // one call: pt_render_spectral_multi, or pt_render_adaptive_spectral_multi with --denoise-spectral-bins.  Every file stays byte for byte what the run without it writes.
 // --develop then develops the undenoised bins where the node render left them, shard by shard on the devices (pt_spectral_project_resident), and the filter of
@@ -53,6 +57,7 @@
 #include "../../../include/pt_adaptive.h"
 #include "../../../include/pt_denoise.h"
 #include "../../../include/pt_scene_file.h"
+#include "../../../include/pt_resident.h"
 #include "../../../include/pt_spectral.h"
 
 namespace {
@@ -80,6 +85,7 @@ struct Options {
     bool has_develop_filter = false, has_develop_subsamples = false;
     std::string develop_filter;
     uint32_t develop_subsamples = 1;
+    bool resident = false;        // --denoise-resident: guides, filter and developments on the scene's resident set (include/pt_resident.h)
     bool spectral_multi = false;  // --spectral-devices MASK: the spectral node calls (pt_render_spectral_multi / pt_render_adaptive_spectral_multi)
     uint64_t spectral_device_mask = 0;
 };
@@ -90,7 +96,8 @@ int usage(const char* msg) {
                     "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n"
                     "             [--denoise] [--guide-samples K] [--demodulate-albedo] [--guide-chain D] [--guide-alpha-max A]\n"
                     "             [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]\n"
-                    "             [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK]\n");
+                    "             [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK]\n"
+                    "             [--denoise-resident]\n");
     return 2;
 }
 
@@ -141,6 +148,7 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") o.denoise = true;
         else if (a == "--demodulate-albedo") o.demodulate = true;
         else if (a == "--demodulate-bins") o.demodulate_bins = true;
+        else if (a == "--denoise-resident") o.resident = true;
         else if (a == "--guide-samples") {
             if (!value(&v)) return usage("--guide-samples needs a value");
             char* end = nullptr;
@@ -224,6 +232,9 @@ int main(int argc, char** argv) {
             return usage("--spectral-bins cannot be combined with --devices naming more than one GPU: pt_render_multi has no spectral film");
         if (o.device_mask > 1) return usage("--spectral-bins renders on device 0: --devices may name that device alone");
     }
+    if (o.resident && !o.denoise) return usage("--denoise-resident needs --denoise");
+    if (o.resident && o.multi) return usage("--denoise-resident cannot be combined with --devices: a node render leaves no film one device can filter");
+    if (o.resident && o.spectral_multi) return usage("--denoise-resident cannot be combined with --spectral-devices: a node render leaves no film one device can filter");
     if (o.demodulate_bins && !o.denoise_bins) return usage("--demodulate-bins needs --denoise-spectral-bins");
     if (o.denoise_bins && !o.denoise) return usage("--denoise-spectral-bins needs --denoise");
     if (o.denoise_bins && o.demodulate) return usage("--denoise-spectral-bins cannot be combined with --demodulate-albedo: demodulating the bins needs a per-bin albedo");
@@ -413,17 +424,19 @@ int main(int argc, char** argv) {
                 std::vector<float> noisy(spectral);
                 if (!write_spectral(base + "_spectral", noisy)) { rc = 1; break; }
             } else if (!spectral.empty() && !write_spectral(base + "_spectral", spectral)) { rc = 1; break; }
-            // --develop: three planes from the bins — the scene's resident ones (bins == nullptr) or a host array as rendered or filtered, before the factor —,
-            // packed as an XYZW film with W = 0, through this setting's film output (buffers of its own: `linear` still serves the spectral files)
-            const auto develop = [&](const std::string& name, const float* bins) {
+            // --develop: three planes from the bins — the scene's resident ones (bins == nullptr; `denoised`: the resident denoised ones) or a host array as rendered
+            // or filtered, before the factor —, packed as an XYZW film with W = 0, through this setting's film output (buffers of its own: `linear` still serves
+            // the spectral files)
+            const auto develop = [&](const std::string& name, const float* bins, bool denoised = false) {
                 const pt_spectral_desc sd = {file_bins, {0u, 0u, 0u}};
                 const size_t np = (size_t)rd.width * rd.height;
                 std::vector<float> matrix((size_t)3 * file_bins), planes(3 * np), packed(4 * np), dev_linear(3 * np);
                 std::vector<uint8_t> dev_rgba(4 * np);
                 pt_status st = pt_spectral_response_matrix(&rd, &sd, develop_curves.data(), (uint32_t)develop_curves.size(), develop_data.data(), (uint32_t)develop_data.size(),
                                                            3, develop_responses, develop_filter, o.develop_subsamples, matrix.data());
-                if (st == PT_OK) st = bins ? pt_spectral_project(rd.width, rd.height, file_bins, 3, matrix.data(), bins, planes.data())
-                                           : pt_spectral_project_resident(scene, 3, matrix.data(), planes.data());
+                if (st == PT_OK) st = bins       ? pt_spectral_project(rd.width, rd.height, file_bins, 3, matrix.data(), bins, planes.data())
+                                      : denoised ? pt_spectral_project_resident_denoised(scene, 3, matrix.data(), planes.data())
+                                                 : pt_spectral_project_resident(scene, 3, matrix.data(), planes.data());
                 if (st != PT_OK) { fprintf(stderr, "--develop: %s\n", pt_last_error()); return false; }
                 for (size_t p = 0; p < np; ++p) { packed[4 * p] = planes[p]; packed[4 * p + 1] = planes[np + p]; packed[4 * p + 2] = planes[2 * np + p]; packed[4 * p + 3] = 0.0f; }
                 if (pt_output_film(&od, packed.data(), dev_rgba.data(), dev_linear.data()) != PT_OK ||
@@ -436,8 +449,30 @@ int main(int argc, char** argv) {
                 return true;
             };
             // (a node render leaves its bins resident too, with either flag: they are developed on the devices)
-            if (o.develop && !develop(base + "_developed", o.denoise_bins && !o.spectral_multi ? spectral.data() : nullptr)) { rc = 1; break; }
-            if (o.denoise) {
+            if (o.develop && !develop(base + "_developed", o.denoise_bins && !o.spectral_multi && !o.resident ? spectral.data() : nullptr)) { rc = 1; break; }
+            if (o.denoise && o.resident) {
+                // the render left film, counts, statistics and bins on the device: the guides stay there too, and the filter runs on all of it
+                std::vector<float> clean((size_t)rd.width * rd.height * 4), clean_spectral(spectral.size());
+                pt_guide_chain_desc cd;
+                memset(&cd, 0, sizeof(cd));
+                cd.max_chain = o.max_chain; cd.alpha_max = o.alpha_max;
+                pt_resident_denoise_desc dd;
+                memset(&dd, 0, sizeof(dd));
+                const uint32_t parts = o.demodulate_bins ? (PT_RESIDENT_ALBEDO | PT_RESIDENT_BIN_ALBEDO) : o.demodulate ? PT_RESIDENT_ALBEDO : 0u;
+                pt_status dst = pt_resident_guides(scene, &rd, o.guide_samples, o.chain ? &cd : nullptr, parts);
+                if (dst == PT_OK) dst = pt_denoise_resident(scene, &dd, clean.data(), nullptr, o.denoise_bins ? clean_spectral.data() : nullptr);
+                if (dst != PT_OK) { fprintf(stderr, "--denoise-resident: %s\n", pt_last_error()); rc = 1; break; }
+                if (pt_output_film(&od, clean.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }
+                const std::string dbase = base + "_denoised";
+                if (pt_write_exr((dbase + ".exr").c_str(), rd.width, rd.height, linear.data(), od.colorspace) != PT_OK ||
+                    pt_write_png((dbase + ".png").c_str(), rd.width, rd.height, rgba.data(), od.colorspace) != PT_OK) {
+                    fprintf(stderr, "failed to write files: %s\n", pt_last_error()); rc = 1; break;
+                }
+                if (o.write_film && !write_npy(dbase + ".npy", clean.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", dbase.c_str()); rc = 1; break; }
+                printf("wrote %s.exr and %s.png\n", dbase.c_str(), dbase.c_str());
+                if (o.develop && o.denoise_bins && !develop(dbase + "_developed", nullptr, true)) { rc = 1; break; }
+                if (o.denoise_bins && !write_spectral(dbase + "_spectral", clean_spectral)) { rc = 1; break; }
+            } else if (o.denoise) {
                 std::vector<float> guides((size_t)rd.width * rd.height * 4), clean((size_t)rd.width * rd.height * 4);
                 pt_denoise_desc dd;
                 memset(&dd, 0, sizeof(dd));

@@ -3,6 +3,8 @@
 // the 3x3 variance tent and the 25-tap gather over ping-pong buffers), of the albedo guide (curve tables, the fold and the division with a second
 // sum), and pt_denoise_film(_albedo) itself.  Every per-pixel rule is pt_denoise_rules.h's, the text the host emulation compiles, so the outputs
 // agree with it bit for bit.
+// The filter's launches are ptk::dn_run, on device pointers: the host-array entries run it between an upload and a read-back, pt_denoise_resident
+// (pt_engine.hip) on the buffers the scene keeps, where the bins may lie in quads of four between the passes (pt_denoise_resident_rules.h).
 //
 // One workgroup = one film tile of 32x8 pixels, one pixel per lane (a wave = two rows of 32 pixels: 512 contiguous bytes per float4 plane and row).  The
 // gather reads each input 25 times, from L1 / L2 / the Infinity Cache: it is bound by its arithmetic (about 200 vector instructions per tap: two correctly
@@ -17,6 +19,8 @@
 #include "../../include/pt_denoise.h"
 #include "../../include/pt_spectral.h"
 #include "pt_denoise_launch.h"
+#include "pt_denoise_resident_launch.h"
+#include "pt_denoise_resident_rules.h"
 #include "pt_denoise_rules.h"
 #include "pt_denoise_spectral_albedo_rules.h"
 #include "pt_error.h"
@@ -277,6 +281,67 @@ __global__ void __launch_bounds__(kLine) k_dn_remodulate_bins(size_t total, uint
     bins[i] = dn_bin_remodulate(bins[i], bin_albedo[i]);
 }
 
+// ---------------------------------------------------------------------------------------------- filter, with the bins as quads
+// The resident form's passes (pt_denoise_resident_rules.h): the ping-pong buffers hold quads of four bins per pixel, so the bin loop of a pass issues one
+// 16-byte load per tap and quad where k_dn_gather_spectral issues four 4-byte loads.  Neighbouring lanes read neighbouring quads: a wave's load is two rows
+// of 512 contiguous bytes.  The pixel index is a uint32_t as above; the quad index q * plane + pixel is formed in size_t.
+struct QuadSource {
+    const float4* color_; const float4* geo_; const float* tent_; const uint8_t* flags_; const DnQuad* quads_; uint32_t width, plane;
+    __device__ uint32_t at(int x, int y) const { return (uint32_t)y * width + (uint32_t)x; }
+    __device__ uint32_t flags(int x, int y) const { return flags_[at(x, y)]; }
+    __device__ DnColor color(int x, int y) const { const float4 c = color_[at(x, y)]; return DnColor{c.x, c.y, c.z, c.w}; }
+    __device__ DnGeo geo(int x, int y) const { const float4 g = geo_[at(x, y)]; return DnGeo{g.x, g.y, g.z, g.w}; }
+    __device__ float tent(int x, int y) const { return tent_[at(x, y)]; }
+    __device__ DnQuad bin4(uint32_t q, int x, int y) const { return quads_[dn_quad_index(q, plane, at(x, y))]; }
+};
+
+// Behind k_dn_prepare(_albedo), in the place of k_dn_demodulate_bins and k_dn_spectral_dead: plane-major raw -> quads (which raw does not alias), divided where
+// HAS_A, the dead bit into flags, and a pixel that is dead through its bins alone gets k_dn_prepare's colour of a dead pixel.  One lane per pixel: the reads
+// of a plane and the 16-byte stores of a quad plane are both contiguous over a wave.
+template <bool HAS_A>
+__global__ void __launch_bounds__(kLine) k_dn_bins_to_quads(uint32_t n, uint32_t bins, const float* __restrict__ raw, const float* __restrict__ bin_albedo,
+                                                           const float4* __restrict__ film, const uint32_t* __restrict__ counts, const double2* __restrict__ stats,
+                                                           DnQuad* __restrict__ quads, float4* __restrict__ color, uint8_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t f = flags[i];
+    const uint32_t dead = dn_bins_to_quads_pixel(bins, f, [&](uint32_t b) { return raw[(size_t)b * n + i]; },
+                                                 [&](uint32_t b) { return HAS_A ? bin_albedo[(size_t)b * n + i] : 1.0f; },
+                                                 [&](uint32_t q, DnQuad v) { quads[dn_quad_index(q, n, i)] = v; });
+    if (dead && !(f & DN_DEAD)) {
+        const float4 c = film[i];
+        const double2 s = stats[i];
+        const DnColor o = dn_bins_dead_color(c.x, c.y, c.z, counts[i], s.x, s.y);
+        color[i] = make_float4(o.x, o.y, o.z, o.v);
+        flags[i] = (uint8_t)(f | dead);
+    }
+}
+
+// one a-trous pass: k_dn_gather_spectral's tile and weight phase, the bins as quads.  The outputs must not alias the inputs.
+__global__ void __launch_bounds__(kTileW * kTileH, 4) k_dn_gather_spectral_quad(DnParams P, int step, QuadSource src, const float2* __restrict__ grad, uint32_t quads,
+                                                                             float4* __restrict__ out, DnQuad* __restrict__ quads_out) {
+    const int x = blockIdx.x * kTileW + threadIdx.x, y = blockIdx.y * kTileH + threadIdx.y;
+    if (x >= (int)P.width || y >= (int)P.height) return;
+    const uint32_t i = (uint32_t)y * P.width + (uint32_t)x;
+    const float2 g = grad[i];
+    DnTaps taps;
+    const DnColor o = dn_gather_pixel_taps(src, P, step, x, y, g.x, g.y, &taps);
+    out[i] = make_float4(o.x, o.y, o.z, o.v);
+    DnQuad* px = quads_out + i;
+    const uint32_t plane = src.plane;
+    dn_gather_pixel_bins4(src, step, x, y, taps, quads, [&](uint32_t q, DnQuad v) { px[(size_t)q * plane] = v; });
+}
+
+// after the last pass, in the place of k_dn_remodulate_bins: quads -> plane-major bins, a live pixel's multiplied back where HAS_A
+template <bool HAS_A>
+__global__ void __launch_bounds__(kLine) k_dn_quads_to_bins(uint32_t n, uint32_t bins, const DnQuad* __restrict__ quads, const float* __restrict__ bin_albedo,
+                                                           const uint8_t* __restrict__ flags, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    dn_quads_to_bins_pixel<HAS_A>(bins, flags[i], [&](uint32_t q) { return quads[dn_quad_index(q, n, i)]; },
+                                  [&](uint32_t b) { return bin_albedo[(size_t)b * n + i]; }, [&](uint32_t b, float v) { out[(size_t)b * n + i] = v; });
+}
+
 int line_grid(size_t n) { return (int)((n + kLine - 1) / kLine); }
 
 // ---------------------------------------------------------------------------------------------- the filter's driver
@@ -297,8 +362,8 @@ struct DnHost {
     float* out_film; float* out_spectral; float* out_variance;                             // out_spectral with spectral; out_variance may be null
 };
 
-// The filter behind the four entries, which have checked their arguments: `d` is the normalised descriptor.  What runs depends on which inputs are present
-// alone.  The launches go to the null stream, with one synchronise before the read-backs.
+// The filter behind the four host-array entries, which have checked their arguments: `d` is the normalised descriptor.  Three parts: the upload into device
+// buffers of this call's own, ptk::dn_run on them (the null stream), and one synchronise before the read-backs.
 pt_status dn_filter(const pt_denoise_desc& d, const DnHost& h) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return dfail(PT_ERR_NO_DEVICE, "no HIP device available: the product path has no CPU fallback");
@@ -306,7 +371,6 @@ pt_status dn_filter(const pt_denoise_desc& d, const DnHost& h) {
 #define DN_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return dfail(e_ == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
     DN_TRY(hipSetDevice((int)d.device));
     const size_t np = (size_t)d.width * d.height, bin_bytes = sizeof(float) * h.bins * np;
-    const uint32_t n = (uint32_t)np;
     Dev d_film, d_counts, d_stats, d_guides, d_color[2], d_geo, d_tent, d_flags, d_grad, d_var, d_bins[2], d_albedo, d_bin_albedo;
     DN_TRY(d_film.alloc(16 * np)); DN_TRY(d_counts.alloc(4 * np)); DN_TRY(d_stats.alloc(16 * np)); DN_TRY(d_guides.alloc(16 * np));
     DN_TRY(d_color[0].alloc(16 * np)); DN_TRY(d_color[1].alloc(16 * np)); DN_TRY(d_geo.alloc(16 * np)); DN_TRY(d_tent.alloc(4 * np));
@@ -322,51 +386,18 @@ pt_status dn_filter(const pt_denoise_desc& d, const DnHost& h) {
     if (h.spectral) DN_TRY(hipMemcpy(d_bins[demodulate ? 1 : 0].p, h.spectral, bin_bytes, hipMemcpyHostToDevice));
     if (h.albedo) { DN_TRY(d_albedo.alloc(16 * np)); DN_TRY(hipMemcpy(d_albedo.p, h.albedo, 16 * np, hipMemcpyHostToDevice)); }
     if (h.bin_albedo) { DN_TRY(d_bin_albedo.alloc(bin_bytes)); DN_TRY(hipMemcpy(d_bin_albedo.p, h.bin_albedo, bin_bytes, hipMemcpyHostToDevice)); }
-    DnParams P;
-    P.width = d.width; P.height = d.height; P.sigma_l = d.sigma_luminance; P.sigma_z = d.sigma_depth; P.normal_squarings = d.normal_power_log2;
-    const dim3 line(line_grid(np)), line_block(kLine);
-    if (h.albedo)
-        hipLaunchKernelGGL(k_dn_prepare_albedo, line, line_block, 0, 0, P, d_film.as<float4>(), d_counts.as<uint32_t>(), d_stats.as<double2>(), d_guides.as<float4>(),
-                           d_albedo.as<float4>(), d_color[0].as<float4>(), d_geo.as<float4>(), d_flags.as<uint8_t>(), d_grad.as<float2>());
-    else
-        hipLaunchKernelGGL(k_dn_prepare, line, line_block, 0, 0, P, d_film.as<float4>(), d_counts.as<uint32_t>(), d_stats.as<double2>(), d_guides.as<float4>(),
-                           d_color[0].as<float4>(), d_geo.as<float4>(), d_flags.as<uint8_t>(), d_grad.as<float2>());
-    if (demodulate) {
-        const auto k = h.bin_albedo ? k_dn_demodulate_bins<true> : k_dn_demodulate_bins<false>;
-        hipLaunchKernelGGL(k, line, line_block, 0, 0, n, h.bins, d_bins[1].as<float>(), d_bin_albedo.as<float>(), d_film.as<float4>(), d_counts.as<uint32_t>(),
-                           d_stats.as<double2>(), d_bins[0].as<float>(), d_color[0].as<float4>(), d_flags.as<uint8_t>());
-    } else if (h.spectral) {
-        hipLaunchKernelGGL(k_dn_spectral_dead, line, line_block, 0, 0, n, h.bins, d_bins[0].as<float>(), d_flags.as<uint8_t>());
-    }
-    const dim3 grid((d.width + kTileW - 1) / kTileW, (d.height + kTileH - 1) / kTileH), block(kTileW, kTileH);
-    int cur = 0;
-    for (uint32_t i = 0; i < d.iterations; ++i) {
-        const int step = 1 << i;
-        const DnBuffers b{d_color[cur].as<float4>(), d_geo.as<float4>(), d_tent.as<float>(), d_flags.as<uint8_t>(), d_grad.as<float2>()};
-        float4* out = d_color[cur ^ 1].as<float4>();
-        hipLaunchKernelGGL(k_dn_tent, grid, block, 0, 0, P, b, d_tent.as<float>());
-        if (h.spectral) {
-            const SpectralSource src{b.color, b.geo, b.tent, b.flags, d_bins[cur].as<float>(), d.width, n};
-            hipLaunchKernelGGL(k_dn_gather_spectral, grid, block, 0, 0, P, step, src, b.grad, h.bins, out, d_bins[cur ^ 1].as<float>());
-        } else {
-            hipLaunchKernelGGL(k_dn_gather, grid, block, 0, 0, P, step, b, out);
-        }
-        cur ^= 1;
-    }
-    if (h.albedo)
-        hipLaunchKernelGGL(k_dn_finish_albedo, line, line_block, 0, 0, n, d_color[cur].as<float4>(), d_albedo.as<float4>(), d_flags.as<uint8_t>(), d_film.as<float4>(),
-                           d_var.as<float>());
-    else
-        hipLaunchKernelGGL(k_dn_finish, line, line_block, 0, 0, n, d_color[cur].as<float4>(), d_film.as<float4>(), d_var.as<float>());
-    if (h.bin_albedo) {
-        const size_t total = (size_t)h.bins * np;
-        hipLaunchKernelGGL(k_dn_remodulate_bins, dim3(line_grid(total)), line_block, 0, 0, total, n, d_bin_albedo.as<float>(), d_flags.as<uint8_t>(), d_bins[cur].as<float>());
-    }
+    ptk::DnRun r{};
+    r.film = d_film.as<float>(); r.counts = d_counts.as<uint32_t>(); r.stats = d_stats.as<double>(); r.guides = d_guides.as<float>();
+    r.albedo = d_albedo.as<float>(); r.bins = h.bins; r.spectral = h.spectral ? d_bins[demodulate ? 1 : 0].as<float>() : nullptr; r.bin_albedo = d_bin_albedo.as<float>();
+    r.color[0] = d_color[0].as<float>(); r.color[1] = d_color[1].as<float>(); r.geo = d_geo.as<float>(); r.tent = d_tent.as<float>(); r.flags = d_flags.as<uint8_t>();
+    r.grad = d_grad.as<float>(); r.bin_buf[0] = d_bins[0].as<float>(); r.bin_buf[1] = d_bins[1].as<float>();
+    r.out_film = d_film.as<float>(); r.out_variance = d_var.as<float>();
+    ptk::dn_run(d, &r, nullptr);
     DN_TRY(hipGetLastError());
     DN_TRY(hipDeviceSynchronize());
-    DN_TRY(hipMemcpy(h.out_film, d_film.p, 16 * np, hipMemcpyDeviceToHost));
-    if (h.spectral) DN_TRY(hipMemcpy(h.out_spectral, d_bins[cur].p, bin_bytes, hipMemcpyDeviceToHost));
-    if (h.out_variance) DN_TRY(hipMemcpy(h.out_variance, d_var.p, 4 * np, hipMemcpyDeviceToHost));
+    DN_TRY(hipMemcpy(h.out_film, r.out_film, 16 * np, hipMemcpyDeviceToHost));
+    if (h.spectral) DN_TRY(hipMemcpy(h.out_spectral, r.denoised_bins, bin_bytes, hipMemcpyDeviceToHost));
+    if (h.out_variance) DN_TRY(hipMemcpy(h.out_variance, r.out_variance, 4 * np, hipMemcpyDeviceToHost));
 #undef DN_TRY
     return PT_OK;
 }
@@ -402,6 +433,65 @@ void albedo_basis(float wavelength_lo, float wavelength_hi, DnAlbedoBasis* basis
     dn_albedo_basis(wavelength_lo, wavelength_hi, [](float angstrom, float* x, float* y, float* z) { xyz_bar(angstrom, x, y, z); }, basis);
 }
 
+
+// The run of the filter on device pointers (pt_denoise_resident_launch.h).  The launches are, kernel for kernel and in order, what the host-array entries have
+// always launched; `quads` swaps the three kernels that touch the bins for their quad forms.
+void dn_run(const pt_denoise_desc& d, DnRun* run, hipStream_t stream) {
+    const DnRun& r = *run;
+    const size_t np = (size_t)d.width * d.height;
+    const uint32_t n = (uint32_t)np;
+    DnParams P;
+    P.width = d.width; P.height = d.height; P.sigma_l = d.sigma_luminance; P.sigma_z = d.sigma_depth; P.normal_squarings = d.normal_power_log2;
+    const float4 *film = reinterpret_cast<const float4*>(r.film), *guides = reinterpret_cast<const float4*>(r.guides), *albedo = reinterpret_cast<const float4*>(r.albedo);
+    const double2* stats = reinterpret_cast<const double2*>(r.stats);
+    float4* color[2] = {reinterpret_cast<float4*>(r.color[0]), reinterpret_cast<float4*>(r.color[1])};
+    float4* geo = reinterpret_cast<float4*>(r.geo);
+    float2* grad = reinterpret_cast<float2*>(r.grad);
+    const dim3 line(line_grid(np)), line_block(kLine);
+    if (r.albedo) hipLaunchKernelGGL(k_dn_prepare_albedo, line, line_block, 0, stream, P, film, r.counts, stats, guides, albedo, color[0], geo, r.flags, grad);
+    else hipLaunchKernelGGL(k_dn_prepare, line, line_block, 0, stream, P, film, r.counts, stats, guides, color[0], geo, r.flags, grad);
+    if (r.spectral && r.quads) {
+        const auto k = r.bin_albedo ? k_dn_bins_to_quads<true> : k_dn_bins_to_quads<false>;
+        hipLaunchKernelGGL(k, line, line_block, 0, stream, n, r.bins, r.spectral, r.bin_albedo, film, r.counts, stats, reinterpret_cast<DnQuad*>(r.bin_buf[0]), color[0], r.flags);
+    } else if (r.spectral && r.spectral != r.bin_buf[0]) {
+        const auto k = r.bin_albedo ? k_dn_demodulate_bins<true> : k_dn_demodulate_bins<false>;
+        hipLaunchKernelGGL(k, line, line_block, 0, stream, n, r.bins, r.spectral, r.bin_albedo, film, r.counts, stats, r.bin_buf[0], color[0], r.flags);
+    } else if (r.spectral) {
+        hipLaunchKernelGGL(k_dn_spectral_dead, line, line_block, 0, stream, n, r.bins, r.bin_buf[0], r.flags);
+    }
+    const dim3 grid((d.width + kTileW - 1) / kTileW, (d.height + kTileH - 1) / kTileH), block(kTileW, kTileH);
+    int cur = 0;
+    for (uint32_t i = 0; i < d.iterations; ++i) {
+        const int step = 1 << i;
+        const DnBuffers b{color[cur], geo, r.tent, r.flags, grad};
+        float4* out = color[cur ^ 1];
+        hipLaunchKernelGGL(k_dn_tent, grid, block, 0, stream, P, b, r.tent);
+        if (r.spectral && r.quads) {
+            const QuadSource src{b.color, b.geo, b.tent, b.flags, reinterpret_cast<const DnQuad*>(r.bin_buf[cur]), d.width, n};
+            hipLaunchKernelGGL(k_dn_gather_spectral_quad, grid, block, 0, stream, P, step, src, b.grad, dn_quad_count(r.bins), out, reinterpret_cast<DnQuad*>(r.bin_buf[cur ^ 1]));
+        } else if (r.spectral) {
+            const SpectralSource src{b.color, b.geo, b.tent, b.flags, r.bin_buf[cur], d.width, n};
+            hipLaunchKernelGGL(k_dn_gather_spectral, grid, block, 0, stream, P, step, src, b.grad, r.bins, out, r.bin_buf[cur ^ 1]);
+        } else {
+            hipLaunchKernelGGL(k_dn_gather, grid, block, 0, stream, P, step, b, out);
+        }
+        cur ^= 1;
+    }
+    if (r.albedo) hipLaunchKernelGGL(k_dn_finish_albedo, line, line_block, 0, stream, n, color[cur], albedo, r.flags, reinterpret_cast<float4*>(r.out_film), r.out_variance);
+    else hipLaunchKernelGGL(k_dn_finish, line, line_block, 0, stream, n, color[cur], reinterpret_cast<float4*>(r.out_film), r.out_variance);
+    run->denoised_bins = nullptr;
+    if (r.spectral && r.quads) {
+        const auto k = r.bin_albedo ? k_dn_quads_to_bins<true> : k_dn_quads_to_bins<false>;
+        hipLaunchKernelGGL(k, line, line_block, 0, stream, n, r.bins, reinterpret_cast<const DnQuad*>(r.bin_buf[cur]), r.bin_albedo, r.flags, r.out_bins);
+        run->denoised_bins = r.out_bins;
+    } else if (r.spectral) {
+        if (r.bin_albedo) {
+            const size_t total = (size_t)r.bins * np;
+            hipLaunchKernelGGL(k_dn_remodulate_bins, dim3(line_grid(total)), line_block, 0, stream, total, n, r.bin_albedo, r.flags, r.bin_buf[cur]);
+        }
+        run->denoised_bins = r.bin_buf[cur];
+    }
+}
 
 }  // namespace ptk
 

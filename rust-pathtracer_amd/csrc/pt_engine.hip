@@ -35,6 +35,7 @@
 #include "pt_spectral_shard_launch.h"
 #include "pt_spectral_shard_rules.h"
 #include "pt_denoise_launch.h"
+#include "pt_denoise_resident_launch.h"
 #include "pt_error.h"
 #include "pt_guides_chain_launch.h"
 #include "pt_denoise_spectral_albedo_launch.h"
@@ -296,6 +297,25 @@ struct MultiSetup {
     bool valid = false;
 };
 
+// include/pt_resident.h: what the scene holds on its device for pt_denoise_resident.  film, counts, stats and spectral point into the buffers of the render that
+// made them resident (film_cache, the adaptive buffers, spectral_cache) or into load_*, pt_resident_load's own: that entry never writes a render's buffer, so
+// spectral_valid keeps its meaning.  Everything else lies in buffers that only grow, so a repeated call allocates nothing.
+struct ResidentSet {
+    uint32_t parts = 0, width = 0, height = 0, bins = 0;   // PT_RESIDENT_* bits; bins: of the bins, the per-bin albedo and the denoised bins
+    const float* film = nullptr; const uint32_t* counts = nullptr; const double* stats = nullptr; const float* spectral = nullptr;
+    const float* denoised_bins = nullptr;   // in den_bins (the quad form) or in a bin_buf (the planar form)
+    GrowBuf load_film, load_counts, load_stats, load_spectral;
+    GrowBuf guides, albedo, bin_albedo;
+    GrowBuf color[2], geo, tent, flags, grad, bin_buf[2];   // the filter's scratch (ptk::DnRun)
+    GrowBuf den_film, den_var, den_bins;
+    void end() { parts = 0; width = height = bins = 0; }
+    void tidy() {
+        if (!(parts & (PT_RESIDENT_BINS | PT_RESIDENT_BIN_ALBEDO | PT_RESIDENT_DENOISED_BINS))) bins = 0;
+        if (!parts) width = height = 0;
+    }
+    struct pt_resident_info info() const { struct pt_resident_info i; i.width = width; i.height = height; i.bins = bins; i.parts = parts; return i; }
+};
+
 struct pt_scene {
     pth::HostScene host;
     pt_tuning tuning;
@@ -323,6 +343,7 @@ struct pt_scene {
     std::vector<pt_scene*> spectral_shards;
     std::vector<uint32_t> shard_px;
     GrowBuf shard_packed;
+    ResidentSet resident;          // include/pt_resident.h
     GrowBuf project_cache;         // pt_spectral_project_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x PT_SPECTRAL_MAX_BINS floats) and, behind it, its output planes
     std::vector<pt_scene*> replicas; // pt_render_multi: this scene on the other (virtual) devices, by device index x virtual index (nullptr = not made yet / this one)
 };
@@ -1016,6 +1037,7 @@ struct RenderCall {
 static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* profile) {
     const pt_render_desc& rd = *call.rd;
     if (call.sd) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts: whatever the buffer held is no film from here on)
+    sc->resident.end();   // (film_cache and the adaptive buffers are written from here on; guides and denoised outputs belonged to the film before)
     HIP_TRY(hipSetDevice(sc->device));
     const size_t n_pixels = (size_t)rd.width * rd.height, film_bytes = sizeof(float) * 4 * n_pixels, spectral_bytes = call.sd ? sizeof(float) * call.sd->bins * n_pixels : 0;
     pt_status st = sc->film_cache.reserve(film_bytes);
@@ -1036,6 +1058,12 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
     if (call.sd) HIP_TRY(hipMemcpy(call.spectral, sc->spectral_cache.p, spectral_bytes, hipMemcpyDeviceToHost));
     if (call.ad && profile) profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (the whole call: set-up, rounds, read-backs)
     if (call.sd) { sc->spectral_width = rd.width; sc->spectral_height = rd.height; sc->spectral_bins = call.sd->bins; sc->spectral_valid = true; }
+    if (call.ad) {   // the resident set of include/pt_resident.h: film, counts and statistics, and the bins of a spectral render
+        ResidentSet& r = sc->resident;
+        r.parts = PT_RESIDENT_FILM | (call.sd ? PT_RESIDENT_BINS : 0u);
+        r.width = rd.width; r.height = rd.height; r.bins = call.sd ? call.sd->bins : 0u;
+        r.film = sc->film_cache.as<float>(); r.counts = sc->adaptive.counts; r.stats = sc->adaptive.stats; r.spectral = call.sd ? sc->spectral_cache.as<float>() : nullptr;
+    }
     return PT_OK;
 }
 
@@ -1090,6 +1118,7 @@ pt_status pt_spectral_resident(pt_scene* sc, uint32_t* width, uint32_t* height, 
 }
 
 static pt_status project_resident_node(pt_scene* sc, uint32_t K, const float* matrix, float* out);
+static pt_status project_device_bins(pt_scene* sc, uint32_t K, const float* matrix, uint32_t bins, size_t n_pixels, const float* d_bins, float* out);
 
 // include/pt_spectral.h: pt_spectral_project's kernel over spectral_cache, on the stream the render ran on (the null stream), so the bins never cross the bus.
 pt_status pt_spectral_project_resident(pt_scene* sc, uint32_t K, const float* matrix, float* out) {
@@ -1100,17 +1129,19 @@ pt_status pt_spectral_project_resident(pt_scene* sc, uint32_t K, const float* ma
     const pt_status st = pth::check_spectral_matrix(K, sc->spectral_bins, matrix, &err);
     if (st != PT_OK) return fail(st, err);
     if (!sc->spectral_shards.empty()) return project_resident_node(sc, K, matrix, out);
+    return project_device_bins(sc, K, matrix, sc->spectral_bins, (size_t)sc->spectral_width * sc->spectral_height, sc->spectral_cache.as<float>(), out);
+}
+// pt_spectral_project's kernel over `bins` planes of n_pixels on the scene's device: the matrix goes up, K planes come back
+static pt_status project_device_bins(pt_scene* sc, uint32_t K, const float* matrix, uint32_t bins, size_t n_pixels, const float* d_bins, float* out) {
     HIP_TRY(hipSetDevice(sc->device));
-    const size_t n_pixels = (size_t)sc->spectral_width * sc->spectral_height;
     const size_t matrix_floats = (size_t)PT_SPECTRAL_MAX_RESPONSES * PT_SPECTRAL_MAX_BINS, bytes = sizeof(float) * (matrix_floats + (size_t)K * n_pixels);
     const pt_status cached = sc->project_cache.reserve(bytes);
     if (cached != PT_OK) return cached;
     float* d_matrix = sc->project_cache.as<float>();
     float* d_out = d_matrix + matrix_floats;
     hipStream_t stream = nullptr;
-    HIP_TRY(hipMemcpyAsync(d_matrix, matrix, sizeof(float) * K * sc->spectral_bins, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ptk::launch_spectral_project(ptk::spectral_project_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, sc->spectral_bins, K, d_matrix,
-                                         sc->spectral_cache.as<float>(), d_out));
+    HIP_TRY(hipMemcpyAsync(d_matrix, matrix, sizeof(float) * K * bins, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ptk::launch_spectral_project(ptk::spectral_project_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, bins, K, d_matrix, d_bins, d_out));
     HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(float) * K * n_pixels, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return PT_OK;
@@ -1403,6 +1434,7 @@ static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t devi
     pt_status st = node_devices(sc, device_mask, &node);
     if (st != PT_OK) return st;
     if (node.single(sc)) return render_one(sc, call, profile);   // (the one-device entry's body: its checks are among this call's, and have passed)
+    sc->resident.end();   // (the shards of a node render are no film one device can filter: include/pt_resident.h)
 
     DeviceGuard guard;
     const auto t_entry = std::chrono::steady_clock::now();
@@ -1632,13 +1664,15 @@ static pt_status make_albedo_tables(pt_scene* sc, const pt_render_desc* rdp, DnA
 }
 // The per-bin albedo guide's table and sums (include/pt_spectral.h pt_render_guides_bin_albedo): the curve values of make_albedo_tables' rows at the centres of
 // the render's `bins` wavelength bins (one launch of k_bin_albedo_tables), and bins x n zeroed running sums.  *fold: what the fold kernels take.
+// (sums: device planes of the caller's that the sums, and at the end the per-bin albedo, are to lie in; null = dbsum, allocated here)
 static pt_status make_bin_albedo_fold(pt_scene* sc, const pt_render_desc* rdp, uint32_t bins, uint32_t n, uint32_t rows, const DevBuf& drow, const DevBuf& dloff, DevBuf* dbtable,
-                                      DevBuf* dbsum, BinAlbedoFold* fold) {
-    HIP_TRY(dbtable->alloc(16 * (size_t)(rows ? rows : 1u) * bins)); HIP_TRY(dbsum->alloc(4 * (size_t)bins * n));
-    HIP_TRY(hipMemsetAsync(dbsum->p, 0, 4 * (size_t)bins * n, 0));
+                                      DevBuf* dbsum, float* sums, BinAlbedoFold* fold) {
+    HIP_TRY(dbtable->alloc(16 * (size_t)(rows ? rows : 1u) * bins));
+    if (!sums) { HIP_TRY(dbsum->alloc(4 * (size_t)bins * n)); sums = dbsum->as<float>(); }
+    HIP_TRY(hipMemsetAsync(sums, 0, 4 * (size_t)bins * n, 0));
     launch_bin_albedo_tables(sc->d_blob, sc->d_tex, rdp->wavelength_lo, dn_bin_width(rdp->wavelength_lo, rdp->wavelength_hi, bins), bins, rows, dloff.as<uint32_t>(),
                              dbtable->as<float>());
-    *fold = BinAlbedoFold{dbsum->as<float>(), reinterpret_cast<const float4*>(dbtable->p), drow.as<uint32_t>(), bins, n};
+    *fold = BinAlbedoFold{sums, reinterpret_cast<const float4*>(dbtable->p), drow.as<uint32_t>(), bins, n};
     return PT_OK;
 }
 // include/pt_denoise.h: the guides of the film denoiser.  Per sample index k the camera rays of every pixel (stage_generate, as pt_camera_samples runs it), the
@@ -1646,7 +1680,13 @@ static pt_status make_bin_albedo_fold(pt_scene* sc, const pt_render_desc* rdp, u
 // `albedo` (may be null): include/pt_denoise.h's second guide, from the same hit records — the fold and the division then run in their albedo forms, after one
 // launch that tabulates the curves of the Lambertian materials' texture layers at the basis wavelengths.  `bin_albedo` (may be null; needs albedo): the per-bin
 // albedo over `bins` bins from the same hit records, folded by a second kernel behind the fold.
-static pt_status render_guides_impl(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, float* guides, float* albedo, uint32_t bins = 0, float* bin_albedo = nullptr) {
+// Where the outputs of a guide pass go: host arrays, copied out of device buffers of the call's own — or (device) buffers on the scene's device that the
+// last kernels write where they lie (pt_resident_guides).  That is the only difference between the two.
+struct GuideOut {
+    float* guides; float* albedo; float* bin_albedo; bool device;
+};
+static pt_status render_guides_impl(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const GuideOut& out, uint32_t bins = 0) {
+    float *const guides = out.guides, *const albedo = out.albedo, *const bin_albedo = out.bin_albedo;
     HIP_TRY(hipSetDevice(sc->device));
     const uint32_t n = rdp->width * rdp->height;
     RenderParams rp;
@@ -1658,16 +1698,19 @@ static pt_status render_guides_impl(pt_scene* sc, const pt_render_desc* rdp, uin
     DevBuf dor, dd, dh, dsum, dg, dasum, da, drow, dloff, dtable, dbtable, dbsum;
     BinAlbedoFold fold{};
     HIP_TRY(dor.alloc(12 * (size_t)n)); HIP_TRY(dd.alloc(12 * (size_t)n)); HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n));
-    HIP_TRY(dsum.alloc(sizeof(DnGuideSum) * (size_t)n)); HIP_TRY(dg.alloc(16 * (size_t)n));
+    HIP_TRY(dsum.alloc(sizeof(DnGuideSum) * (size_t)n));
+    float *d_guides = guides, *d_albedo = albedo;
+    if (!out.device) { HIP_TRY(dg.alloc(16 * (size_t)n)); d_guides = dg.as<float>(); }
     DnAlbedoBasis basis;
     const uint32_t materials = sc->host.material_count;
     if (albedo) {
-        HIP_TRY(dasum.alloc(16 * (size_t)n)); HIP_TRY(da.alloc(16 * (size_t)n));
+        HIP_TRY(dasum.alloc(16 * (size_t)n));
+        if (!out.device) { HIP_TRY(da.alloc(16 * (size_t)n)); d_albedo = da.as<float>(); }
         uint32_t rows = 0;
         const pt_status ast = make_albedo_tables(sc, rdp, &basis, &drow, &dloff, &dtable, &rows);
         if (ast != PT_OK) return ast;
         if (bin_albedo) {
-            const pt_status bst = make_bin_albedo_fold(sc, rdp, bins, n, rows, drow, dloff, &dbtable, &dbsum, &fold);
+            const pt_status bst = make_bin_albedo_fold(sc, rdp, bins, n, rows, drow, dloff, &dbtable, &dbsum, out.device ? bin_albedo : nullptr, &fold);
             if (bst != PT_OK) return bst;
         }
     }
@@ -1682,13 +1725,14 @@ static pt_status render_guides_impl(pt_scene* sc, const pt_render_desc* rdp, uin
             launch_guide_fold(n, dh.as<pt_hit>(), dsum.as<DnGuideSum>(), k == 0);
         if (fold.sums) launch_guide_fold_bins(n, dh.as<pt_hit>(), fold, sc->d_blob, sc->d_tex, materials);
     }
-    if (albedo) launch_guide_finish_albedo(n, dsum.as<DnGuideSum>(), dasum.as<float>(), guide_samples, dg.as<float>(), da.as<float>());
-    else launch_guide_finish(n, dsum.as<DnGuideSum>(), guide_samples, dg.as<float>());
+    if (albedo) launch_guide_finish_albedo(n, dsum.as<DnGuideSum>(), dasum.as<float>(), guide_samples, d_guides, d_albedo);
+    else launch_guide_finish(n, dsum.as<DnGuideSum>(), guide_samples, d_guides);
     if (fold.sums) launch_bin_albedo_finish(n, bins, fold.sums, guide_samples, fold.sums);   // (in place: one value per lane)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(guides, dg.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
-    if (albedo) HIP_TRY(hipMemcpy(albedo, da.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
+    if (out.device) return PT_OK;
+    HIP_TRY(hipMemcpy(guides, d_guides, 16 * (size_t)n, hipMemcpyDeviceToHost));
+    if (albedo) HIP_TRY(hipMemcpy(albedo, d_albedo, 16 * (size_t)n, hipMemcpyDeviceToHost));
     if (fold.sums) HIP_TRY(hipMemcpy(bin_albedo, fold.sums, 4 * (size_t)bins * n, hipMemcpyDeviceToHost));
     return PT_OK;
 }
@@ -1696,14 +1740,14 @@ pt_status pt_render_guides(pt_scene* sc, const pt_render_desc* rdp, uint32_t gui
     std::string err;
     const pt_status st = pth::check_guides_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, guides, &err);
     if (st != PT_OK) return fail(st, err);
-    return render_guides_impl(sc, rdp, guide_samples, guides, nullptr);
+    return render_guides_impl(sc, rdp, guide_samples, GuideOut{guides, nullptr, nullptr, false});
 }
 pt_status pt_render_guides_albedo(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, float* guides, float* albedo) {
     std::string err;
     const pt_status st = pth::check_guides_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, guides, &err);
     if (st != PT_OK) return fail(st, err);
     if (!albedo) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    return render_guides_impl(sc, rdp, guide_samples, guides, albedo);
+    return render_guides_impl(sc, rdp, guide_samples, GuideOut{guides, albedo, nullptr, false});
 }
 
 // include/pt_denoise.h: the guides at the end of every sample's specular chain.  Per sample index the camera rays go out as a list with the identity pixel
@@ -1711,8 +1755,8 @@ pt_status pt_render_guides_albedo(pt_scene* sc, const pt_render_desc* rdp, uint3
 // sums and compacts the rest into the next list, whose length comes back in one 4-byte read — the probe's launcher takes its ray count by value.  The last
 // possible vertex (v == max_chain) ends every ray, so nothing is read back after it: max_chain 0 runs pt_render_guides_albedo's launches and no read-back.
 // `bin_albedo` (may be null; needs albedo): the per-bin albedo over `bins` bins, folded by k_chain_step at the same terminal vertex.
-static pt_status render_guides_chain_impl(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const pt_guide_chain_desc& cd, float* guides, float* albedo,
-                                          uint32_t bins = 0, float* bin_albedo = nullptr) {
+static pt_status render_guides_chain_impl(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const pt_guide_chain_desc& cd, const GuideOut& out, uint32_t bins = 0) {
+    float *const guides = out.guides, *const albedo = out.albedo, *const bin_albedo = out.bin_albedo;
     HIP_TRY(hipSetDevice(sc->device));
     const uint32_t n = rdp->width * rdp->height;
     RenderParams rp;
@@ -1723,20 +1767,23 @@ static pt_status render_guides_chain_impl(pt_scene* sc, const pt_render_desc* rd
     rp.chunk_pixels = 1;
     DevBuf dor[2], dd[2], dstate[2], dh, dsum, dg, dasum, da, drow, dloff, dtable, dcount, dbtable, dbsum;
     for (int i = 0; i < 2; ++i) { HIP_TRY(dor[i].alloc(12 * (size_t)n)); HIP_TRY(dd[i].alloc(12 * (size_t)n)); HIP_TRY(dstate[i].alloc(16 * (size_t)n)); }
-    HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n)); HIP_TRY(dsum.alloc(sizeof(DnGuideSum) * (size_t)n)); HIP_TRY(dg.alloc(16 * (size_t)n));
+    HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n)); HIP_TRY(dsum.alloc(sizeof(DnGuideSum) * (size_t)n));
+    float *d_guides = guides, *d_albedo = albedo;
+    if (!out.device) { HIP_TRY(dg.alloc(16 * (size_t)n)); d_guides = dg.as<float>(); }
     HIP_TRY(dcount.alloc(4 * (size_t)(cd.max_chain + 1u)));
     HIP_TRY(hipMemsetAsync(dsum.p, 0, sizeof(DnGuideSum) * (size_t)n, 0));
     ChainAlbedo ca;
     memset(&ca, 0, sizeof(ca));
     if (albedo) {
-        HIP_TRY(dasum.alloc(16 * (size_t)n)); HIP_TRY(da.alloc(16 * (size_t)n));
+        HIP_TRY(dasum.alloc(16 * (size_t)n));
+        if (!out.device) { HIP_TRY(da.alloc(16 * (size_t)n)); d_albedo = da.as<float>(); }
         HIP_TRY(hipMemsetAsync(dasum.p, 0, 16 * (size_t)n, 0));
         uint32_t rows = 0;
         const pt_status ast = make_albedo_tables(sc, rdp, &ca.basis, &drow, &dloff, &dtable, &rows);
         if (ast != PT_OK) return ast;
         ca.albedo_sums = dasum.as<float>(); ca.material_row = drow.as<uint32_t>(); ca.table = dtable.as<float>();
         if (bin_albedo) {
-            const pt_status bst = make_bin_albedo_fold(sc, rdp, bins, n, rows, drow, dloff, &dbtable, &dbsum, &ca.bin_fold);
+            const pt_status bst = make_bin_albedo_fold(sc, rdp, bins, n, rows, drow, dloff, &dbtable, &dbsum, out.device ? bin_albedo : nullptr, &ca.bin_fold);
             if (bst != PT_OK) return bst;
         }
     }
@@ -1757,13 +1804,14 @@ static pt_status render_guides_chain_impl(pt_scene* sc, const pt_render_desc* rd
             if (active > n) return fail(PT_ERR_DEVICE, "the chain's ray list grew");   // (never: a launch appends at most its own rays)
         }
     }
-    if (albedo) launch_guide_finish_albedo(n, dsum.as<DnGuideSum>(), dasum.as<float>(), guide_samples, dg.as<float>(), da.as<float>());
-    else launch_guide_finish(n, dsum.as<DnGuideSum>(), guide_samples, dg.as<float>());
+    if (albedo) launch_guide_finish_albedo(n, dsum.as<DnGuideSum>(), dasum.as<float>(), guide_samples, d_guides, d_albedo);
+    else launch_guide_finish(n, dsum.as<DnGuideSum>(), guide_samples, d_guides);
     if (ca.bin_fold.sums) launch_bin_albedo_finish(n, bins, ca.bin_fold.sums, guide_samples, ca.bin_fold.sums);   // (in place: one value per lane)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(guides, dg.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
-    if (albedo) HIP_TRY(hipMemcpy(albedo, da.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
+    if (out.device) return PT_OK;
+    HIP_TRY(hipMemcpy(guides, d_guides, 16 * (size_t)n, hipMemcpyDeviceToHost));
+    if (albedo) HIP_TRY(hipMemcpy(albedo, d_albedo, 16 * (size_t)n, hipMemcpyDeviceToHost));
     if (ca.bin_fold.sums) HIP_TRY(hipMemcpy(bin_albedo, ca.bin_fold.sums, 4 * (size_t)bins * n, hipMemcpyDeviceToHost));
     return PT_OK;
 }
@@ -1772,7 +1820,7 @@ pt_status pt_render_guides_chain(pt_scene* sc, const pt_render_desc* rdp, uint32
     pt_guide_chain_desc cd;
     const pt_status st = pth::check_guides_chain_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, chain, guides, &cd, &err);
     if (st != PT_OK) return fail(st, err);
-    return render_guides_chain_impl(sc, rdp, guide_samples, cd, guides, albedo);
+    return render_guides_chain_impl(sc, rdp, guide_samples, cd, GuideOut{guides, albedo, nullptr, false});
 }
 // include/pt_spectral.h: the guides, the XYZ albedo and the per-bin albedo from one set of probes — at the first hit (render_guides_impl), or with a chain of
 // max_chain > 0 at the end of every sample's specular chain (render_guides_chain_impl).  The XYZ albedo is always computed (its tables' rows are the per-bin
@@ -1785,8 +1833,127 @@ pt_status pt_render_guides_bin_albedo(pt_scene* sc, const pt_render_desc* rdp, u
     if (st != PT_OK) return fail(st, err);
     std::vector<float> own_albedo;
     if (!albedo) { own_albedo.resize(4 * (size_t)rdp->width * rdp->height); albedo = own_albedo.data(); }
-    if (cd.max_chain == 0) return render_guides_impl(sc, rdp, guide_samples, guides, albedo, bins, bin_albedo);
-    return render_guides_chain_impl(sc, rdp, guide_samples, cd, guides, albedo, bins, bin_albedo);
+    const GuideOut out{guides, albedo, bin_albedo, false};
+    if (cd.max_chain == 0) return render_guides_impl(sc, rdp, guide_samples, out, bins);
+    return render_guides_chain_impl(sc, rdp, guide_samples, cd, out, bins);
+}
+
+// ---- include/pt_resident.h.  Every argument, and what the call needs resident, is checked by pth::check_resident_* before a device is looked for.
+static struct pt_resident_info resident_now(const pt_scene* sc) {
+    if (sc) return sc->resident.info();
+    struct pt_resident_info none;
+    memset(&none, 0, sizeof(none));
+    return none;
+}
+pt_status pt_resident_info(pt_scene* sc, struct pt_resident_info* info) {
+    std::string err;
+    const pt_status st = pth::check_resident_info_args(sc, info, &err);
+    if (st != PT_OK) return fail(st, err);
+    *info = sc->resident.info();
+    return PT_OK;
+}
+// the guide pass of the host-array entries with its outputs kept: the same launches on the same stream, the last of them writing the scene's buffers
+pt_status pt_resident_guides(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const pt_guide_chain_desc* chain, uint32_t flags) {
+    std::string err;
+    pt_guide_chain_desc cd;
+    pt_status st = pth::check_resident_guides_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, chain, flags, resident_now(sc), &cd, &err);
+    if (st != PT_OK) return fail(st, err);
+    ResidentSet& r = sc->resident;
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t np = (size_t)r.width * r.height;
+    r.parts &= ~(PT_RESIDENT_GUIDES | PT_RESIDENT_ALBEDO | PT_RESIDENT_BIN_ALBEDO | PT_RESIDENT_DENOISED | PT_RESIDENT_DENOISED_BINS);
+    r.tidy();
+    const bool albedo = (flags & PT_RESIDENT_ALBEDO) != 0u, bin_albedo = (flags & PT_RESIDENT_BIN_ALBEDO) != 0u;
+    st = r.guides.reserve(16 * np);
+    if (st == PT_OK && albedo) st = r.albedo.reserve(16 * np);
+    if (st == PT_OK && bin_albedo) st = r.bin_albedo.reserve(4 * np * r.bins);
+    if (st != PT_OK) return st;
+    const GuideOut out{r.guides.as<float>(), albedo ? r.albedo.as<float>() : nullptr, bin_albedo ? r.bin_albedo.as<float>() : nullptr, true};
+    st = cd.max_chain == 0 ? render_guides_impl(sc, rdp, guide_samples, out, bin_albedo ? r.bins : 0u) : render_guides_chain_impl(sc, rdp, guide_samples, cd, out, bin_albedo ? r.bins : 0u);
+    if (st != PT_OK) return st;
+    r.parts |= PT_RESIDENT_GUIDES | (albedo ? PT_RESIDENT_ALBEDO : 0u) | (bin_albedo ? PT_RESIDENT_BIN_ALBEDO : 0u);
+    return PT_OK;
+}
+pt_status pt_resident_load(pt_scene* sc, uint32_t width, uint32_t height, uint32_t bins, const float* film, const uint32_t* sample_counts, const double* stats,
+                           const float* spectral, const float* guides, const float* albedo, const float* bin_albedo) {
+    std::string err;
+    pt_status st = pth::check_resident_load_args(sc, width, height, bins, film, sample_counts, stats, spectral, guides, albedo, bin_albedo, resident_now(sc), &err);
+    if (st != PT_OK) return fail(st, err);
+    ResidentSet& r = sc->resident;
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t np = (size_t)width * height;
+    // a part that is given is resident no longer until its upload has succeeded; the denoised parts go with the inputs they came from
+    r.parts &= ~((film ? PT_RESIDENT_FILM : 0u) | (spectral ? PT_RESIDENT_BINS : 0u) | (guides ? PT_RESIDENT_GUIDES : 0u) | (albedo ? PT_RESIDENT_ALBEDO : 0u) |
+                 (bin_albedo ? PT_RESIDENT_BIN_ALBEDO : 0u) | PT_RESIDENT_DENOISED | PT_RESIDENT_DENOISED_BINS);
+    r.tidy();
+    struct Part { GrowBuf* buf; const void* host; size_t bytes; };
+    const Part parts[] = {{&r.load_film, film, 16 * np}, {&r.load_counts, sample_counts, 4 * np}, {&r.load_stats, stats, 16 * np}, {&r.load_spectral, spectral, 4 * np * bins},
+                          {&r.guides, guides, 16 * np}, {&r.albedo, albedo, 16 * np}, {&r.bin_albedo, bin_albedo, 4 * np * bins}};
+    for (const Part& p : parts) {
+        if (!p.host) continue;
+        st = p.buf->reserve(p.bytes);
+        if (st != PT_OK) return st;
+        HIP_TRY(hipMemcpy(p.buf->p, p.host, p.bytes, hipMemcpyHostToDevice));
+    }
+    if (film) { r.film = r.load_film.as<float>(); r.counts = r.load_counts.as<uint32_t>(); r.stats = r.load_stats.as<double>(); r.parts |= PT_RESIDENT_FILM; }
+    if (spectral) { r.spectral = r.load_spectral.as<float>(); r.parts |= PT_RESIDENT_BINS; }
+    if (guides) r.parts |= PT_RESIDENT_GUIDES;
+    if (albedo) r.parts |= PT_RESIDENT_ALBEDO;
+    if (bin_albedo) r.parts |= PT_RESIDENT_BIN_ALBEDO;
+    r.width = width; r.height = height;
+    if (spectral || bin_albedo) r.bins = bins;
+    return PT_OK;
+}
+// The filter where the film is: ptk::dn_run (pt_denoise.hip), the run the host-array entries make between their upload and their read-back, on the resident
+// buffers and the null stream — the stream of the render and the guide pass.  The sources are read only; the scratch and the outputs are the scene's.
+pt_status pt_denoise_resident(pt_scene* sc, const pt_resident_denoise_desc* desc, float* out_film, float* out_variance, float* out_spectral) {
+    std::string err;
+    pt_denoise_desc d;
+    pt_status st = pth::check_resident_denoise_args(sc, desc, out_spectral, resident_now(sc), &d, &err);
+    if (st != PT_OK) return fail(st, err);
+    ResidentSet& r = sc->resident;
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t np = (size_t)r.width * r.height;
+    const bool has_bins = (r.parts & PT_RESIDENT_BINS) != 0u, quads = has_bins && !(desc->flags & PT_RESIDENT_PLANAR_GATHER);
+    r.parts &= ~(PT_RESIDENT_DENOISED | PT_RESIDENT_DENOISED_BINS);
+    struct Want { GrowBuf* buf; size_t bytes; };
+    const size_t bin_buf_bytes = has_bins ? ptk::dn_bin_buf_bytes(np, r.bins, quads) : 0;
+    const Want wants[] = {{&r.color[0], 16 * np}, {&r.color[1], 16 * np}, {&r.geo, 16 * np}, {&r.tent, 4 * np}, {&r.flags, np}, {&r.grad, 8 * np}, {&r.den_film, 16 * np},
+                          {&r.den_var, 4 * np}, {&r.bin_buf[0], bin_buf_bytes}, {&r.bin_buf[1], bin_buf_bytes}, {&r.den_bins, quads ? 4 * np * r.bins : 0}};
+    for (const Want& w : wants) {
+        st = w.bytes ? w.buf->reserve(w.bytes) : PT_OK;
+        if (st != PT_OK) return st;
+    }
+    ptk::DnRun run;
+    memset(&run, 0, sizeof(run));
+    run.film = r.film; run.counts = r.counts; run.stats = r.stats; run.guides = r.guides.as<float>();
+    run.albedo = (r.parts & PT_RESIDENT_ALBEDO) ? r.albedo.as<float>() : nullptr;
+    if (has_bins) {
+        run.bins = r.bins; run.spectral = r.spectral;
+        run.bin_albedo = (r.parts & PT_RESIDENT_BIN_ALBEDO) ? r.bin_albedo.as<float>() : nullptr;
+        run.bin_buf[0] = r.bin_buf[0].as<float>(); run.bin_buf[1] = r.bin_buf[1].as<float>();
+        run.quads = quads; run.out_bins = quads ? r.den_bins.as<float>() : nullptr;
+    }
+    run.color[0] = r.color[0].as<float>(); run.color[1] = r.color[1].as<float>(); run.geo = r.geo.as<float>(); run.tent = r.tent.as<float>();
+    run.flags = r.flags.as<uint8_t>(); run.grad = r.grad.as<float>();
+    run.out_film = r.den_film.as<float>(); run.out_variance = r.den_var.as<float>();
+    const hipStream_t stream = nullptr;
+    ptk::dn_run(d, &run, stream);
+    HIP_TRY(hipGetLastError());
+    if (out_film) HIP_TRY(hipMemcpyAsync(out_film, run.out_film, 16 * np, hipMemcpyDeviceToHost, stream));
+    if (out_variance) HIP_TRY(hipMemcpyAsync(out_variance, run.out_variance, 4 * np, hipMemcpyDeviceToHost, stream));
+    if (out_spectral) HIP_TRY(hipMemcpyAsync(out_spectral, run.denoised_bins, 4 * np * r.bins, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    r.denoised_bins = run.denoised_bins;
+    r.parts |= PT_RESIDENT_DENOISED | (has_bins ? PT_RESIDENT_DENOISED_BINS : 0u);
+    return PT_OK;
+}
+pt_status pt_spectral_project_resident_denoised(pt_scene* sc, uint32_t K, const float* matrix, float* out) {
+    std::string err;
+    const pt_status st = pth::check_resident_project_args(sc, K, matrix, out, resident_now(sc), &err);
+    if (st != PT_OK) return fail(st, err);
+    const ResidentSet& r = sc->resident;
+    return project_device_bins(sc, K, matrix, r.bins, (size_t)r.width * r.height, r.denoised_bins, out);
 }
 
 pt_status pt_bsdf_sample(pt_scene* sc, uint32_t material, size_t n, const float* lambda, const float* wi, const float* s2, float* f, float* wo, float* pdf) {

@@ -3,6 +3,7 @@
 #include "pt_guides_chain_rules.h"
 
 #include <cmath>
+#include <cstring>
 
 namespace pth {
 
@@ -158,13 +159,20 @@ pt_status normalize_denoise_desc(const pt_denoise_desc* in, const void* film, co
     return PT_OK;
 }
 
-pt_status check_denoise_inputs(const pt_denoise_desc& d, const uint32_t* sample_counts, const float* guides, std::string* error) {
-    const size_t np = (size_t)d.width * d.height;
+pt_status check_denoise_counts(size_t np, const uint32_t* sample_counts, std::string* error) {
     for (size_t p = 0; p < np; ++p)
         if (sample_counts[p] < 2u) { *error = "a sample count below 2: the variance of a mean needs two samples"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+pt_status check_denoise_guides(size_t np, const float* guides, std::string* error) {
     for (size_t i = 0; i < 4 * np; ++i)
         if (!pt_isfinite(guides[i])) { *error = "a guide value is not finite"; return PT_ERR_INVALID_ARGUMENT; }
     return PT_OK;
+}
+pt_status check_denoise_inputs(const pt_denoise_desc& d, const uint32_t* sample_counts, const float* guides, std::string* error) {
+    const size_t np = (size_t)d.width * d.height;
+    const pt_status st = check_denoise_counts(np, sample_counts, error);
+    return st != PT_OK ? st : check_denoise_guides(np, guides, error);
 }
 
 pt_status check_guides_args(const void* scene, const pt_render_desc* rd, uint32_t camera_count, uint32_t guide_samples, const void* guides, std::string* error) {
@@ -281,11 +289,12 @@ pt_status check_denoise_spectral_albedo_args(const pt_denoise_desc* in, uint32_t
     pt_status st = check_denoise_spectral_args(in, bins, film, sample_counts, stats, guides, spectral, out_film, out_spectral, out, error);
     if (st == PT_OK && albedo) st = check_denoise_albedo(*out, albedo, error);
     if (st != PT_OK) return st;
-    if (bin_albedo) {
-        const size_t n = (size_t)bins * out->width * out->height;
-        for (size_t i = 0; i < n; ++i)
-            if (!pt_isfinite(bin_albedo[i]) || !(bin_albedo[i] >= 0.0f)) { *error = "a bin_albedo value is not finite or is negative"; return PT_ERR_INVALID_ARGUMENT; }
-    }
+    if (bin_albedo) return check_denoise_bin_albedo((size_t)bins * out->width * out->height, bin_albedo, error);
+    return PT_OK;
+}
+pt_status check_denoise_bin_albedo(size_t n, const float* bin_albedo, std::string* error) {
+    for (size_t i = 0; i < n; ++i)
+        if (!pt_isfinite(bin_albedo[i]) || !(bin_albedo[i] >= 0.0f)) { *error = "a bin_albedo value is not finite or is negative"; return PT_ERR_INVALID_ARGUMENT; }
     return PT_OK;
 }
 
@@ -298,6 +307,85 @@ pt_status check_spectral_matrix(uint32_t K, uint32_t bins, const float* matrix, 
     for (uint32_t i = 0; i < K * bins; ++i)
         if (!pt_isfinite(matrix[i])) { *error = "a response matrix entry is not finite"; return PT_ERR_INVALID_ARGUMENT; }
     return PT_OK;
+}
+
+// ---- include/pt_resident.h
+pt_status check_resident_info_args(const void* scene, const void* info, std::string* error) {
+    if (!scene) { *error = "pt_resident_info: the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!info) { *error = "pt_resident_info: info is null"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
+pt_status check_resident_guides_args(const void* scene, const pt_render_desc* rd, uint32_t camera_count, uint32_t guide_samples, const pt_guide_chain_desc* chain,
+                                     uint32_t flags, const struct pt_resident_info& now, pt_guide_chain_desc* chain_out, std::string* error) {
+    if (!scene) { *error = "pt_resident_guides: the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!rd) { *error = "pt_resident_guides: the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (flags & ~(PT_RESIDENT_ALBEDO | PT_RESIDENT_BIN_ALBEDO)) { *error = "pt_resident_guides: flags holds a bit that is neither PT_RESIDENT_ALBEDO nor PT_RESIDENT_BIN_ALBEDO"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((flags & PT_RESIDENT_BIN_ALBEDO) && !(flags & PT_RESIDENT_ALBEDO)) { *error = "pt_resident_guides: PT_RESIDENT_BIN_ALBEDO needs PT_RESIDENT_ALBEDO"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!(now.parts & PT_RESIDENT_FILM)) { *error = "pt_resident_guides: the scene has no resident film: pt_render_adaptive, pt_render_adaptive_spectral or pt_resident_load must have succeeded on it"; return PT_ERR_INVALID_ARGUMENT; }
+    if (rd->width != now.width || rd->height != now.height) { *error = "pt_resident_guides: the desc's width and height are not the resident film's"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((flags & PT_RESIDENT_BIN_ALBEDO) && !(now.parts & PT_RESIDENT_BINS)) { *error = "pt_resident_guides: PT_RESIDENT_BIN_ALBEDO needs resident bins"; return PT_ERR_INVALID_ARGUMENT; }
+    if (chain) return check_guides_chain_args(scene, rd, camera_count, guide_samples, chain, scene, chain_out, error);
+    chain_out->max_chain = 0; chain_out->alpha_max = DN_CHAIN_DEFAULT_ALPHA_MAX; chain_out->reserved[0] = 0; chain_out->reserved[1] = 0;
+    return check_guides_args(scene, rd, camera_count, guide_samples, scene, error);   // (the guides' destination is the scene's own: never null)
+}
+
+pt_status check_resident_load_args(const void* scene, uint32_t width, uint32_t height, uint32_t bins, const float* film, const uint32_t* sample_counts, const double* stats,
+                                   const float* spectral, const float* guides, const float* albedo, const float* bin_albedo, const struct pt_resident_info& now,
+                                   std::string* error) {
+    if (!scene) { *error = "pt_resident_load: the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!film && !sample_counts && !stats && !spectral && !guides && !albedo && !bin_albedo) { *error = "pt_resident_load: every array is null: nothing to load"; return PT_ERR_INVALID_ARGUMENT; }
+    if (width == 0 || height == 0) { *error = "pt_resident_load: width and height must be positive"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((uint64_t)width * (uint64_t)height > 0x7fffffffull) { *error = "pt_resident_load: width x height must fit 31 bits"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((film || sample_counts || stats) && !(film && sample_counts && stats)) { *error = "pt_resident_load: film_xyzw, sample_counts and stats come together"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((spectral || bin_albedo) && bins == 0) { *error = "pt_resident_load: spectral and bin_albedo need a positive bins"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((spectral || bin_albedo) && bins > PT_SPECTRAL_MAX_BINS) { *error = "pt_resident_load: bins: at most 64"; return PT_ERR_INVALID_ARGUMENT; }
+    // what stays resident: every part that is not replaced; the denoised parts go
+    uint32_t stays = now.parts & ~(PT_RESIDENT_DENOISED | PT_RESIDENT_DENOISED_BINS);
+    if (film) stays &= ~PT_RESIDENT_FILM;
+    if (spectral) stays &= ~PT_RESIDENT_BINS;
+    if (guides) stays &= ~PT_RESIDENT_GUIDES;
+    if (albedo) stays &= ~PT_RESIDENT_ALBEDO;
+    if (bin_albedo) stays &= ~PT_RESIDENT_BIN_ALBEDO;
+    if (stays && (width != now.width || height != now.height)) { *error = "pt_resident_load: width and height are not those of the parts that stay resident"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((spectral || bin_albedo) && (stays & (PT_RESIDENT_BINS | PT_RESIDENT_BIN_ALBEDO)) && bins != now.bins) { *error = "pt_resident_load: bins is not that of the planes that stay resident"; return PT_ERR_INVALID_ARGUMENT; }
+    const size_t np = (size_t)width * height;
+    pt_denoise_desc d;
+    memset(&d, 0, sizeof(d));
+    d.width = width; d.height = height;
+    pt_status st = PT_OK;
+    if (sample_counts) st = check_denoise_counts(np, sample_counts, error);
+    if (st == PT_OK && guides) st = check_denoise_guides(np, guides, error);
+    if (st == PT_OK && albedo) st = check_denoise_albedo(d, albedo, error);
+    if (st == PT_OK && bin_albedo) st = check_denoise_bin_albedo((size_t)bins * np, bin_albedo, error);
+    return st;
+}
+
+pt_status check_resident_denoise_args(const void* scene, const pt_resident_denoise_desc* desc, const void* out_spectral, const struct pt_resident_info& now,
+                                      pt_denoise_desc* out, std::string* error) {
+    if (!scene) { *error = "pt_denoise_resident: the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!desc) { *error = "pt_denoise_resident: the desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (desc->flags & ~PT_RESIDENT_PLANAR_GATHER) { *error = "pt_denoise_resident: flags holds a bit that is not PT_RESIDENT_PLANAR_GATHER"; return PT_ERR_INVALID_ARGUMENT; }
+    for (uint32_t r : desc->reserved) if (r != 0) { *error = "pt_resident_denoise_desc::reserved must be 0"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((desc->filter.width == 0) != (desc->filter.height == 0)) { *error = "pt_denoise_resident: width and height are both 0 or both the resident size"; return PT_ERR_INVALID_ARGUMENT; }
+    pt_denoise_desc f = desc->filter;
+    const bool sized = f.width != 0;
+    if (!sized) { f.width = 1; f.height = 1; }
+    const pt_status st = normalize_denoise_desc(&f, scene, scene, scene, scene, scene, out, error);   // (its arrays are the scene's own: never null)
+    if (st != PT_OK) return st;
+    if (!(now.parts & PT_RESIDENT_FILM)) { *error = "pt_denoise_resident: the scene has no resident film: pt_render_adaptive, pt_render_adaptive_spectral or pt_resident_load must have succeeded on it"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!(now.parts & PT_RESIDENT_GUIDES)) { *error = "pt_denoise_resident: the scene has no resident guides: pt_resident_guides or pt_resident_load must have succeeded on it"; return PT_ERR_INVALID_ARGUMENT; }
+    if (sized && (f.width != now.width || f.height != now.height)) { *error = "pt_denoise_resident: width and height are neither 0 nor the resident size"; return PT_ERR_INVALID_ARGUMENT; }
+    if (out_spectral && !(now.parts & PT_RESIDENT_BINS)) { *error = "pt_denoise_resident: out_spectral without resident bins"; return PT_ERR_INVALID_ARGUMENT; }
+    out->width = now.width; out->height = now.height;
+    return PT_OK;
+}
+
+pt_status check_resident_project_args(const void* scene, uint32_t K, const float* matrix, const void* out, const struct pt_resident_info& now, std::string* error) {
+    if (!scene) { *error = "pt_spectral_project_resident_denoised: the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!out) { *error = "pt_spectral_project_resident_denoised: the developed planes (out) are null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!(now.parts & PT_RESIDENT_DENOISED_BINS)) { *error = "the scene has no resident denoised bins: pt_denoise_resident must have succeeded on it with resident bins"; return PT_ERR_INVALID_ARGUMENT; }
+    return check_spectral_matrix(K, now.bins, matrix, error);
 }
 
 pt_status check_spectral_project_args(uint32_t width, uint32_t height, uint32_t bins, uint32_t K, const float* matrix, const void* spectral, const void* out,

@@ -10,6 +10,7 @@
 #include "../../include/pt_adaptive.h"
 #include "../../include/pt_api.h"
 #include "../../include/pt_denoise.h"
+#include "../../include/pt_resident.h"
 #include "../../include/pt_spectral.h"
 #include "pt_stages.h"
 
@@ -90,6 +91,29 @@ pt_status check_spectral_project_args(uint32_t width, uint32_t height, uint32_t 
 pt_status check_response_matrix_args(const pt_render_desc* rd, const pt_spectral_desc* sd, const void* curves, uint32_t curve_count, const void* curve_data,
                                      uint32_t curve_data_floats, uint32_t K, const int32_t* responses, int32_t filter, uint32_t subsamples, const void* matrix,
                                      std::string* error);
+
+// ---- include/pt_resident.h.  `now`: what the scene holds resident (pt_resident_info's answer), so that the engine and the emulation refuse the same calls
+// with the same words; every check runs before a device is looked for.
+// the two halves of check_denoise_inputs, and the per-bin albedo's value check of check_denoise_spectral_albedo_args
+pt_status check_denoise_counts(size_t n_pixels, const uint32_t* sample_counts, std::string* error);
+pt_status check_denoise_guides(size_t n_pixels, const float* guides, std::string* error);
+pt_status check_denoise_bin_albedo(size_t n_values, const float* bin_albedo, std::string* error);
+pt_status check_resident_info_args(const void* scene, const void* info, std::string* error);
+// pt_resident_guides: the flags known and BIN_ALBEDO only with ALBEDO; a resident film, of desc's size; BIN_ALBEDO only with resident bins; then
+// check_guides_args, or check_guides_chain_args where a chain is given (*chain_out: normalised, max_chain 0 without one)
+pt_status check_resident_guides_args(const void* scene, const pt_render_desc* rd, uint32_t camera_count, uint32_t guide_samples, const pt_guide_chain_desc* chain,
+                                     uint32_t flags, const struct pt_resident_info& now, pt_guide_chain_desc* chain_out, std::string* error);
+// pt_resident_load: something given; the size positive and within 31 bits; film, counts and stats together; bins in 1..64 with spectral or bin_albedo; the
+// size (and bins) those of the parts that stay resident; the values as the host-array denoise entries want them
+pt_status check_resident_load_args(const void* scene, uint32_t width, uint32_t height, uint32_t bins, const float* film, const uint32_t* sample_counts, const double* stats,
+                                   const float* spectral, const float* guides, const float* albedo, const float* bin_albedo, const struct pt_resident_info& now,
+                                   std::string* error);
+// pt_denoise_resident: the desc's flags and reserved words, its filter as normalize_denoise_desc wants it (*out: normalised, with the resident size), a
+// resident film and resident guides, the size 0 or the resident one, out_spectral only with resident bins
+pt_status check_resident_denoise_args(const void* scene, const pt_resident_denoise_desc* desc, const void* out_spectral, const struct pt_resident_info& now,
+                                      pt_denoise_desc* out, std::string* error);
+// pt_spectral_project_resident_denoised: pt_spectral_project_resident's checks, over the resident denoised bins
+pt_status check_resident_project_args(const void* scene, uint32_t K, const float* matrix, const void* out, const struct pt_resident_info& now, std::string* error);
 
 }  // namespace pth
 #endif

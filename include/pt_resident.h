@@ -12,6 +12,9 @@
  *   spectral entries and their node forms ends the residency of every part when it starts; a node render on more than one device, a plain pt_render and a
  *   failed render leave nothing resident.  pt_resident_guides renders GUIDES (ALBEDO, BIN_ALBEDO) for the resident film, pt_resident_load adopts host arrays
  *   as parts, pt_denoise_resident filters what is resident and leaves DENOISED (DENOISED_BINS), pt_spectral_project_resident_denoised develops those.
+ *   An adaptive node render leaves its pieces on the devices — film, counts and statistics on the first device of the mask, the bins as one packed shard per
+ *   device — and the scene remembers where: pt_resident_assemble gathers them on the scene's own device, device to device, as FILM (and BINS), so that the
+ *   guides and the filter follow a node render as they follow a one-device one.  pt_resident_read copies resident FILM and BINS to host arrays.
  *
  * The contract.  Every output of pt_denoise_resident is bit for bit what the host-array entry — pt_denoise_film, pt_denoise_film_albedo, pt_denoise_spectral
  * or pt_denoise_spectral_albedo, whichever the resident set selects — returns for the arrays the render and guide entries returned; the developed planes are
@@ -57,6 +60,23 @@ pt_status pt_resident_guides(pt_scene* scene, const pt_render_desc* desc, uint32
  * every albedo finite and not negative.  It does not make a spectral film resident in pt_spectral_project_resident's sense: that entry is about renders. */
 pt_status pt_resident_load(pt_scene* scene, uint32_t width, uint32_t height, uint32_t bins, const float* film_xyzw, const uint32_t* sample_counts, const double* stats,
                            const float* spectral, const float* guides_xyzw, const float* albedo_xyzw, const float* bin_albedo);
+
+#define PT_RESIDENT_ASSEMBLE_STAGED 1u   /* copy every shard into staging on the scene's device first, also one that already lies there */
+
+/* Makes FILM, and BINS if the render had bins, resident on the scene's own device from the pieces the last adaptive node render (pt_render_adaptive_multi or
+ * pt_render_adaptive_spectral_multi over more than one device, made with stats) left on the devices: bit for bit the arrays that render returned.  Film,
+ * counts and statistics are copied from the first device of the mask; every device's packed shard of the bins is unpacked into full planes, in place when it
+ * lies on the scene's physical device and through a staging buffer the scene keeps (a peer copy) when it does not.  PT_RESIDENT_ASSEMBLE_STAGED takes the
+ * staged route for every shard; both give the same bits.  Nothing but the shards' pixel lists crosses a host link, no peer-access setting is changed, the
+ * caller's current device is kept and the call has synchronised when it returns.  The parts lie in pt_resident_load's buffers, never in a render's: the
+ * undenoised shards still develop where they are (pt_spectral_project_resident).  GUIDES, ALBEDO, BIN_ALBEDO and the denoised parts are resident no longer.
+ * A repeated call allocates nothing.  Every render entry forgets the node render when it starts: refused after a later render, after a fixed-count node
+ * render, after a node render that came down to one device (it left FILM resident itself) and after a failed one. */
+pt_status pt_resident_assemble(pt_scene* scene, uint32_t flags);
+
+/* Copies resident FILM (film_xyzw 4 f32 per pixel, sample_counts u32, stats 2 f64) and BINS (spectral: the resident bins' planes) to host arrays, however they
+ * became resident.  Every pointer may be NULL; one that is given for a part that is not resident is refused. */
+pt_status pt_resident_read(pt_scene* scene, float* film_xyzw, uint32_t* sample_counts, double* stats, float* spectral);
 
 #define PT_RESIDENT_PLANAR_GATHER 1u   /* pt_resident_denoise_desc::flags: the passes over plane-major bins (pt_denoise_spectral's kernels), not over quads of four bins */
 

@@ -136,6 +136,7 @@ class DenoiseDesc(C.Structure):
 # include/pt_resident.h: the parts of a scene's resident set, and pt_resident_denoise_desc's flag
 RESIDENT_FILM, RESIDENT_BINS, RESIDENT_GUIDES, RESIDENT_ALBEDO, RESIDENT_BIN_ALBEDO, RESIDENT_DENOISED, RESIDENT_DENOISED_BINS = (1 << i for i in range(7))
 RESIDENT_PLANAR_GATHER = 1
+RESIDENT_ASSEMBLE_STAGED = 1
 
 
 class ResidentInfo(C.Structure):
@@ -312,7 +313,9 @@ class Library:
         self._resident_load = bind("resident_load", C.c_int32, [vp, u32, u32, u32, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp], required=False)
         self._denoise_resident = bind("denoise_resident", C.c_int32, [vp, C.POINTER(ResidentDenoiseDesc), fpp, fpp, fpp], required=False)
         self._spectral_project_resident_denoised = bind("spectral_project_resident_denoised", C.c_int32, [vp, u32, fpp, fpp], required=False)
-        self._resident_last_error = bind("resident_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the five entries above)
+        self._resident_assemble = bind("resident_assemble", C.c_int32, [vp, u32], required=False)
+        self._resident_read = bind("resident_read", C.c_int32, [vp, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp], required=False)
+        self._resident_last_error = bind("resident_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the seven entries above)
         self._spectral_project_last_error = bind("spectral_project_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the entries above)
         self._device_info = bind("device_info", C.c_char_p, [], required=False)
         self._output_film = bind("output_film", C.c_int32, [C.POINTER(OutputDesc), fpp, C.POINTER(C.c_uint8), fpp], required=False)
@@ -669,6 +672,30 @@ class Scene:
             self.handle, w, h, nbins.pop() if nbins else 0, p(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)) if counts is not None else None,
             stats.ctypes.data_as(C.POINTER(C.c_double)) if stats is not None else None, p(spectral), p(guides), p(albedo), p(bin_albedo)))
 
+    def resident_assemble(self, staged=False):
+        """pt_resident_assemble: the pieces the last adaptive node render (render_adaptive_multi, render_adaptive_spectral_multi with stats=True) left on the
+        devices gathered on the scene's own device as the resident film (and bins), device to device: resident_guides and denoise_resident then follow as after
+        a one-device render.  `staged`: every shard of the bins goes through the staging copy, also one that lies on the scene's device; the bits are the same."""
+        self._resident_check(self._resident_entry("resident_assemble")(self.handle, RESIDENT_ASSEMBLE_STAGED if staged else 0))
+
+    def resident_read(self, film=True, counts=True, stats=True, spectral=False):
+        """pt_resident_read: the resident film [H,W,4] (film), counts [H,W] u32 (counts), stats [H,W,2] f64 (stats) and bins [B,H,W] (spectral) copied to the
+        host, however they became resident.  Returns the tuple of what was asked for, in this order — one array when one is asked for, None when none is."""
+        w, h, bins, _ = self.resident_info()
+        f = np.zeros((h, w, 4), np.float32) if film else None
+        c = np.zeros((h, w), np.uint32) if counts else None
+        st = np.zeros((h, w, 2), np.float64) if stats else None
+        sp = np.zeros((bins, h, w), np.float32) if spectral else None
+        self._resident_check(self._resident_entry("resident_read")(self.handle, _fp(f) if film else None, c.ctypes.data_as(C.POINTER(C.c_uint32)) if counts else None,
+                                                                   st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, _fp(sp) if spectral else None))
+        res = tuple(a for a in (f, c, st, sp) if a is not None)
+        return res[0] if len(res) == 1 else (res if res else None)
+
+    def _assemble_node_render(self):
+        """Behind a node render: the film resident on the scene's device — it already is when the mask came down to this one device."""
+        if not (self.resident_info()[3] & RESIDENT_FILM):
+            self.resident_assemble()
+
     def denoise_resident(self, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, film=True, variance=False, spectral=False, planar=False):
         """pt_denoise_resident: the filter over the resident set, where it lies.  Returns the tuple of what was asked for, in this order: the denoised film
         [H,W,4] (film), its variance [H,W] (variance), the denoised bins [B,H,W] (spectral) — one array when one is asked for, None when none is.  What is
@@ -826,17 +853,26 @@ class Scene:
         return g, a, ba
 
     def render_denoised(self, rd, max_samples=None, rel_error=0.0, abs_error=0.0, step=0, guide_samples=4, iterations=0, sigma_luminance=0.0, sigma_depth=0.0,
-                        normal_power_log2=0, device_mask=None, albedo=False, specular_chain=None, resident=False):
+                        normal_power_log2=0, device_mask=None, albedo=False, specular_chain=None, resident=False, assemble=False):
         """An adaptive render with statistics (max_samples None = rd.spp: a fixed count), its guides, and the filter: (film, denoised, counts, profile).
         `device_mask` (not None) routes the render through render_adaptive_multi; the filter then runs on the first device of the mask.  `albedo`: the
         guides come with the albedo (render_guides_albedo) and the filter demodulates the film by it.  `specular_chain` (not None): the guides, and the
         albedo if asked for, come from render_guides_chain with this max_chain.  `resident`: guides and filter run on what the render left on the device
-        (resident_guides, denoise_resident); the tuple is the same, bit for bit.  A node render leaves no such film: refused with a device_mask."""
+        (resident_guides, denoise_resident); the tuple is the same, bit for bit.  A node render leaves no such film: refused with a device_mask.
+        `assemble` (with a device_mask only): the node render's pieces are assembled on the scene's device (resident_assemble) and guides and filter run
+        there, resident; the tuple is the same, bit for bit."""
         mx = rd.spp if max_samples is None else max_samples
+        if assemble and device_mask is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "render_denoised: assemble=True needs a device_mask (it assembles a node render; resident=True is the one-device form)")
         if resident:
             if device_mask is not None:
                 raise PtError(PT_ERR_UNSUPPORTED, "render_denoised: resident=True takes no device_mask (a node render leaves no film one device can filter)")
             film, counts, st, prof = self.render_adaptive(rd, mx, rel_error, abs_error, step, stats=True)
+            self.resident_guides(rd, guide_samples, specular_chain or 0, albedo=albedo)
+            return film, self.denoise_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2), counts, prof
+        if assemble:
+            film, counts, st, prof = self.render_adaptive_multi(rd, mx, rel_error, abs_error, step, stats=True, device_mask=device_mask)
+            self._assemble_node_render()
             self.resident_guides(rd, guide_samples, specular_chain or 0, albedo=albedo)
             return film, self.denoise_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2), counts, prof
         if device_mask is None:
@@ -855,13 +891,17 @@ class Scene:
         return film, den, counts, prof
 
     def render_denoised_spectral(self, rd, bins, max_samples=None, rel_error=0.0, guide_samples=4, specular_chain=0, abs_error=0.0, step=0, iterations=0,
-                                 sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, albedo=False, bin_albedo=False, resident=False, device_mask=None):
+                                 sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, albedo=False, bin_albedo=False, resident=False, assemble=False, device_mask=None):
         """render_adaptive_spectral with statistics (max_samples None = rd.spp: a fixed count), its guides — render_guides, or render_guides_chain with max_chain
         `specular_chain` when that is positive — and denoise_spectral: (film, denoised, spectral, denoised_spectral, counts, profile).  `albedo` is refused, as
         denoise_spectral refuses it.  `bin_albedo`: guides, XYZ albedo and per-bin albedo come from one render_guides_bin_albedo call (with `specular_chain` as its
         max_chain) and the filter is denoise_spectral_albedo: the film demodulated by the XYZ albedo, the bins by the per-bin albedo.  `device_mask` (not None)
         routes the render through render_adaptive_spectral_multi; the filter then runs on the first device of the mask.  `resident`: guides and filter run on
-        what the render left on the device (resident_guides, denoise_resident); the tuple is the same, bit for bit; refused with a device_mask."""
+        what the render left on the device (resident_guides, denoise_resident); the tuple is the same, bit for bit; refused with a device_mask.  `assemble`
+        (with a device_mask only): the node render's film and packed shards are assembled on the scene's device (resident_assemble) and guides and filter run
+        there, resident: the bins do not go up again; the tuple is the same, bit for bit."""
+        if assemble and device_mask is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "render_denoised_spectral: assemble=True needs a device_mask (it assembles a node render; resident=True is the one-device form)")
         if albedo:
             raise PtError(PT_ERR_UNSUPPORTED, "render_denoised_spectral takes no albedo: demodulating the bins needs a per-bin albedo (bin_albedo=True renders one)")
         mx = rd.spp if max_samples is None else max_samples
@@ -869,6 +909,12 @@ class Scene:
             if device_mask is not None:
                 raise PtError(PT_ERR_UNSUPPORTED, "render_denoised_spectral: resident=True takes no device_mask (a node render leaves no film one device can filter)")
             film, counts, st, spectral, prof = self.render_adaptive_spectral(rd, bins, mx, rel_error, abs_error, step, stats=True)
+            self.resident_guides(rd, guide_samples, specular_chain, albedo=bin_albedo, bin_albedo=bin_albedo)
+            den, den_spectral = self.denoise_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2, spectral=True)
+            return film, den, spectral, den_spectral, counts, prof
+        if assemble:
+            film, counts, st, spectral, prof = self.render_adaptive_spectral_multi(rd, bins, mx, rel_error, abs_error, step, stats=True, device_mask=device_mask)
+            self._assemble_node_render()
             self.resident_guides(rd, guide_samples, specular_chain, albedo=bin_albedo, bin_albedo=bin_albedo)
             den, den_spectral = self.denoise_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2, spectral=True)
             return film, den, spectral, den_spectral, counts, prof

@@ -6,6 +6,7 @@
 //         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K] [--demodulate-albedo]
 //         [--guide-chain D] [--guide-alpha-max A] [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]
 //         [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK] [--denoise-resident]
+//         [--denoise-assemble]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -45,6 +46,11 @@
 // one call: pt_render_spectral_multi, or pt_render_adaptive_spectral_multi with --denoise-spectral-bins.  Every file stays byte for byte what the run without it writes.
 // --develop then develops the undenoised bins where the node render left them, shard by shard on the devices (pt_spectral_project_resident), and the filter of
 // --denoise runs on the first device of MASK.  It is refused together with --devices, whose refusals of the spectral flags stay what they are.
+// --denoise-assemble (with --denoise --denoise-spectral-bins B --spectral-devices MASK only) assembles the node render on the scene's device, device to device
+// (pt_resident_assemble: the film from the first device of MASK, every device's packed shard of the bins unpacked into full planes), and runs the guides, the
+// filter and, with --develop, the denoised development on the assembled set, as --denoise-resident does after a one-device render: the bins are not uploaded
+// again.  The undenoised bins are developed shard by shard where the node render left them, as without the flag.  Every file stays byte for byte what the run
+// without it writes.  It is refused together with --denoise-resident, which is the one-device form.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -88,6 +94,7 @@ struct Options {
     bool resident = false;        // --denoise-resident: guides, filter and developments on the scene's resident set (include/pt_resident.h)
     bool spectral_multi = false;  // --spectral-devices MASK: the spectral node calls (pt_render_spectral_multi / pt_render_adaptive_spectral_multi)
     uint64_t spectral_device_mask = 0;
+    bool assemble = false;        // --denoise-assemble: the node render assembled on the scene's device, then as `resident` (pt_resident_assemble)
 };
 
 int usage(const char* msg) {
@@ -97,7 +104,7 @@ int usage(const char* msg) {
                     "             [--denoise] [--guide-samples K] [--demodulate-albedo] [--guide-chain D] [--guide-alpha-max A]\n"
                     "             [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]\n"
                     "             [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK]\n"
-                    "             [--denoise-resident]\n");
+                    "             [--denoise-resident] [--denoise-assemble]\n");
     return 2;
 }
 
@@ -149,6 +156,7 @@ int main(int argc, char** argv) {
         else if (a == "--demodulate-albedo") o.demodulate = true;
         else if (a == "--demodulate-bins") o.demodulate_bins = true;
         else if (a == "--denoise-resident") o.resident = true;
+        else if (a == "--denoise-assemble") o.assemble = true;
         else if (a == "--guide-samples") {
             if (!value(&v)) return usage("--guide-samples needs a value");
             char* end = nullptr;
@@ -244,6 +252,10 @@ int main(int argc, char** argv) {
     if (o.has_develop_subsamples && !o.develop) return usage("--develop-subsamples needs --develop");
     if (o.spectral_multi && !o.spectral_bins && !o.denoise_bins) return usage("--spectral-devices needs --spectral-bins or --denoise-spectral-bins: it names the devices their spectral film is rendered on");
     if (o.spectral_multi && o.multi) return usage("--spectral-devices cannot be combined with --devices: a spectral render takes its devices from --spectral-devices alone");
+    if (o.assemble && o.resident) return usage("--denoise-assemble cannot be combined with --denoise-resident: that flag is the one-device form, this one assembles a node render");
+    if (o.assemble && !o.denoise) return usage("--denoise-assemble needs --denoise");
+    if (o.assemble && !o.denoise_bins) return usage("--denoise-assemble needs --denoise-spectral-bins: it assembles the node render of the spectral film");
+    if (o.assemble && !o.spectral_multi) return usage("--denoise-assemble needs --spectral-devices: it assembles the node render on those devices");
     const bool verbose = o.stdout_log_level == "info" || o.stdout_log_level == "debug" || o.stdout_log_level == "trace";
     const bool warnings = verbose || o.stdout_log_level == "warn";
     if (!o.root.empty()) pt_scene_file_set_root(o.root.c_str());
@@ -450,7 +462,15 @@ int main(int argc, char** argv) {
             };
             // (a node render leaves its bins resident too, with either flag: they are developed on the devices)
             if (o.develop && !develop(base + "_developed", o.denoise_bins && !o.spectral_multi && !o.resident ? spectral.data() : nullptr)) { rc = 1; break; }
-            if (o.denoise && o.resident) {
+            if (o.denoise && o.assemble) {
+                // the node render left its pieces on the devices: one film on the scene's device from them, unless the mask came down to that device alone and
+                // the render left the film resident itself
+                struct pt_resident_info now;
+                pt_status ast = pt_resident_info(scene, &now);
+                if (ast == PT_OK && !(now.parts & PT_RESIDENT_FILM)) ast = pt_resident_assemble(scene, 0u);
+                if (ast != PT_OK) { fprintf(stderr, "--denoise-assemble: %s\n", pt_last_error()); rc = 1; break; }
+            }
+            if (o.denoise && (o.resident || o.assemble)) {
                 // the render left film, counts, statistics and bins on the device: the guides stay there too, and the filter runs on all of it
                 std::vector<float> clean((size_t)rd.width * rd.height * 4), clean_spectral(spectral.size());
                 pt_guide_chain_desc cd;
@@ -461,7 +481,7 @@ int main(int argc, char** argv) {
                 const uint32_t parts = o.demodulate_bins ? (PT_RESIDENT_ALBEDO | PT_RESIDENT_BIN_ALBEDO) : o.demodulate ? PT_RESIDENT_ALBEDO : 0u;
                 pt_status dst = pt_resident_guides(scene, &rd, o.guide_samples, o.chain ? &cd : nullptr, parts);
                 if (dst == PT_OK) dst = pt_denoise_resident(scene, &dd, clean.data(), nullptr, o.denoise_bins ? clean_spectral.data() : nullptr);
-                if (dst != PT_OK) { fprintf(stderr, "--denoise-resident: %s\n", pt_last_error()); rc = 1; break; }
+                if (dst != PT_OK) { fprintf(stderr, "%s: %s\n", o.assemble ? "--denoise-assemble" : "--denoise-resident", pt_last_error()); rc = 1; break; }
                 if (pt_output_film(&od, clean.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }
                 const std::string dbase = base + "_denoised";
                 if (pt_write_exr((dbase + ".exr").c_str(), rd.width, rd.height, linear.data(), od.colorspace) != PT_OK ||

@@ -283,6 +283,16 @@ struct AdaptiveBuffers {
 
 }  // namespace
 
+// What the last adaptive node render (render_node) left where, for pt_resident_assemble (include/pt_resident.h): film, counts and statistics on `device`, the
+// first device of the mask, and for a spectral render the scenes that hold the packed shards (shard_px, shard_packed).  Kept with the MultiSetup whose films it
+// points into: released with it.  Every render entry forgets it when it starts.
+struct NodeRemembered {
+    pth::NodeRender info;
+    int device = 0;
+    const float* film = nullptr; const uint32_t* counts = nullptr; const double* stats = nullptr;
+    std::vector<pt_scene*> shards;
+};
+
 // What pt_render_multi sets up for a set of devices and a film size, kept on the scene: a frame-by-frame caller pays for streams, device
 // films and the RCCL communicator once (round-2 advice: they were made and destroyed on every call, outside the timed window).
 struct MultiSetup {
@@ -294,6 +304,7 @@ struct MultiSetup {
     std::vector<hipStream_t> streams; // per virtual device
     std::vector<ncclComm_t> comms;    // per physical device (rccl only)
     std::vector<GrowBuf> staging;   // per virtual device: the pinned host buffer its packed spectral planes land in (the spectral node entries; grown on demand)
+    NodeRemembered node_render;
     bool valid = false;
 };
 
@@ -344,6 +355,7 @@ struct pt_scene {
     std::vector<uint32_t> shard_px;
     GrowBuf shard_packed;
     ResidentSet resident;          // include/pt_resident.h
+    GrowBuf assemble_staging, assemble_px;   // pt_resident_assemble's: the packed shards copied from other devices, and the pixel lists uploaded for the unpack
     GrowBuf project_cache;         // pt_spectral_project_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x PT_SPECTRAL_MAX_BINS floats) and, behind it, its output planes
     std::vector<pt_scene*> replicas; // pt_render_multi: this scene on the other (virtual) devices, by device index x virtual index (nullptr = not made yet / this one)
 };
@@ -1004,6 +1016,8 @@ pt_status pt_scene_create_tuned(const pt_scene_desc* desc, const pt_tuning* tuni
 }
 
 static void multi_release(MultiSetup& m);
+// a render entry starts (or is refused): whatever an earlier node render left is no longer described (pt_resident_assemble)
+static void forget_node_render(pt_scene* sc) { if (sc) sc->multi.node_render = NodeRemembered(); }
 void pt_scene_destroy(pt_scene* sc) {
     if (!sc) return;
     for (pt_scene* r : sc->replicas) if (r) pt_scene_destroy(r);
@@ -1036,6 +1050,7 @@ struct RenderCall {
 // spectral film.  profile->seconds: render_impl's window for the fixed entries; for the adaptive ones the whole call.
 static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* profile) {
     const pt_render_desc& rd = *call.rd;
+    forget_node_render(sc);
     if (call.sd) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts: whatever the buffer held is no film from here on)
     sc->resident.end();   // (film_cache and the adaptive buffers are written from here on; guides and denoised outputs belonged to the film before)
     HIP_TRY(hipSetDevice(sc->device));
@@ -1068,6 +1083,7 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
 }
 
 pt_status pt_render(pt_scene* sc, const pt_render_desc* rd, float* film, pt_profile* profile) {
+    forget_node_render(sc);
     if (!sc || !rd || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     if (rd->width == 0 || rd->height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
     RenderCall call;
@@ -1077,6 +1093,7 @@ pt_status pt_render(pt_scene* sc, const pt_render_desc* rd, float* film, pt_prof
 
 pt_status pt_render_adaptive(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, float* film, uint32_t* sample_counts, double* stats,
                              pt_profile* profile) {
+    forget_node_render(sc);
     if (!sc || !rdp || !adp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     pt_render_desc rd;
     pt_adaptive_desc ad;
@@ -1089,6 +1106,7 @@ pt_status pt_render_adaptive(pt_scene* sc, const pt_render_desc* rdp, const pt_a
 }
 
 pt_status pt_render_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_spectral_desc* sdp, float* film, float* spectral, pt_profile* profile) {
+    forget_node_render(sc);
     std::string err;
     pt_status st = pth::check_spectral_args(sc, rdp, sdp, film, spectral, &err);
     if (st != PT_OK) return fail(st, err);
@@ -1100,6 +1118,7 @@ pt_status pt_render_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_s
 
 pt_status pt_render_adaptive_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, const pt_spectral_desc* sdp, float* film,
                                       uint32_t* sample_counts, double* stats, float* spectral, pt_profile* profile) {
+    forget_node_render(sc);
     pt_render_desc rd;
     pt_adaptive_desc ad;
     std::string err;
@@ -1430,11 +1449,12 @@ static pt_status project_resident_node(pt_scene* sc, uint32_t K, const float* ma
 static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t device_mask, pt_profile* profile) {
     const pt_render_desc& rd = *call.rd;
     const bool adaptive = call.ad != nullptr;
+    forget_node_render(sc);
     Node node;
     pt_status st = node_devices(sc, device_mask, &node);
     if (st != PT_OK) return st;
     if (node.single(sc)) return render_one(sc, call, profile);   // (the one-device entry's body: its checks are among this call's, and have passed)
-    sc->resident.end();   // (the shards of a node render are no film one device can filter: include/pt_resident.h)
+    sc->resident.end();   // (the shards of a node render are no film one device can filter until pt_resident_assemble is asked: include/pt_resident.h)
 
     DeviceGuard guard;
     const auto t_entry = std::chrono::steady_clock::now();
@@ -1542,10 +1562,19 @@ static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t devi
         profile->kernel_seconds[6] = nr.exchange_seconds + std::chrono::duration<double>(t_gathered - t_gather).count() + node_spectral_seconds(ns);
     }
     if (call.sd) node_spectral_resident(sc, node, rd, call.sd->bins);
+    if (adaptive) {   // where the pieces lie, for pt_resident_assemble: no device work, and nothing is resident (include/pt_resident.h)
+        NodeRemembered& k = m.node_render;
+        k.info.valid = true; k.info.stats = call.stats != nullptr;
+        k.info.width = rd.width; k.info.height = rd.height; k.info.bins = call.sd ? call.sd->bins : 0u;
+        k.device = node.devices[0];
+        k.film = m.films[0]; k.counts = node.scene_of[0]->adaptive.counts; k.stats = node.scene_of[0]->adaptive.stats;
+        if (call.sd) k.shards = node.scene_of;
+    }
     return PT_OK;
 }
 
 pt_status pt_render_multi(pt_scene* sc, const pt_render_desc* rdp, uint64_t device_mask, float* film, pt_profile* profile) {
+    forget_node_render(sc);
     if (!sc || !rdp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     if (rdp->width == 0 || rdp->height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
     if (rdp->shard_count > 1) return fail(PT_ERR_INVALID_ARGUMENT, "pt_render_multi deals the tiles itself: shard_count must be 0");
@@ -1557,6 +1586,7 @@ pt_status pt_render_multi(pt_scene* sc, const pt_render_desc* rdp, uint64_t devi
 pt_status pt_render_spectral_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_spectral_desc* sdp, uint64_t device_mask, float* film, float* spectral,
                                    pt_profile* profile) {
     if (sc) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts; whatever it is refused for, no film is resident after it)
+    forget_node_render(sc);
     pt_render_desc rd;
     std::string err;
     const pt_status st = pth::check_spectral_multi_args(sc, rdp, sdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, film, spectral, &rd, &err);
@@ -1568,6 +1598,7 @@ pt_status pt_render_spectral_multi(pt_scene* sc, const pt_render_desc* rdp, cons
 
 pt_status pt_render_adaptive_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, uint64_t device_mask, float* film,
                                    uint32_t* sample_counts, double* stats, pt_profile* profile) {
+    forget_node_render(sc);
     if (!sc || !rdp || !adp || !film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     pt_render_desc rd;
     pt_adaptive_desc ad;
@@ -1582,6 +1613,7 @@ pt_status pt_render_adaptive_multi(pt_scene* sc, const pt_render_desc* rdp, cons
 pt_status pt_render_adaptive_spectral_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, const pt_spectral_desc* sdp, uint64_t device_mask,
                                             float* film, uint32_t* sample_counts, double* stats, float* spectral, pt_profile* profile) {
     if (sc) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (as in pt_render_spectral_multi)
+    forget_node_render(sc);
     pt_render_desc rd;
     pt_adaptive_desc ad;
     std::string err;
@@ -1902,6 +1934,85 @@ pt_status pt_resident_load(pt_scene* sc, uint32_t width, uint32_t height, uint32
     if (bin_albedo) r.parts |= PT_RESIDENT_BIN_ALBEDO;
     r.width = width; r.height = height;
     if (spectral || bin_albedo) r.bins = bins;
+    return PT_OK;
+}
+// The pieces of the last adaptive node render gathered on the scene's device, device to device, on the null stream (the stream of the guide pass and the filter).
+// The shards are disjoint and cover the film, so the planes are not zeroed and every float of them is written exactly once.
+pt_status pt_resident_assemble(pt_scene* sc, uint32_t flags) {
+    std::string err;
+    pt_status st = pth::check_resident_assemble(sc, flags, sc ? sc->multi.node_render.info : pth::NodeRender(), &err);
+    if (st != PT_OK) return fail(st, err);
+    const NodeRemembered& k = sc->multi.node_render;
+    ResidentSet& r = sc->resident;
+    DeviceGuard guard;
+    HIP_TRY(hipSetDevice(sc->device));
+    r.end();   // (every part is replaced or belonged to another film; on any failure below nothing is resident)
+    const size_t np = (size_t)k.info.width * k.info.height;
+    const uint32_t bins = k.info.bins;
+    const bool staged_all = (flags & PT_RESIDENT_ASSEMBLE_STAGED) != 0u;
+    // a shard is staged when it lies on another device (or every one, on request); its pixel list is uploaded unless a replica on this device still holds it
+    const auto staged = [&](const pt_scene* s) { return staged_all || s->device != sc->device; };
+    const auto listed = [&](const pt_scene* s) { return s != sc && s->device == sc->device; };
+    size_t staging_floats = 0, px_words = 0;
+    for (const pt_scene* s : k.shards) {
+        if (staged(s)) staging_floats += (size_t)bins * s->shard_px.size();
+        if (!listed(s)) px_words += s->shard_px.size();
+    }
+    st = r.load_film.reserve(16 * np);
+    if (st == PT_OK) st = r.load_counts.reserve(4 * np);
+    if (st == PT_OK) st = r.load_stats.reserve(16 * np);
+    if (st == PT_OK && bins) st = r.load_spectral.reserve(4 * np * bins);
+    if (st == PT_OK && staging_floats) st = sc->assemble_staging.reserve(sizeof(float) * staging_floats);
+    if (st == PT_OK && px_words) st = sc->assemble_px.reserve(sizeof(uint32_t) * px_words);
+    if (st != PT_OK) return st;
+    const hipStream_t stream = nullptr;
+    const bool film_peer = k.device != sc->device;
+    const auto film_copy = [&](void* dst, const void* src, size_t bytes) {
+        return film_peer ? hipMemcpyPeerAsync(dst, sc->device, src, k.device, bytes, stream) : hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream);
+    };
+    HIP_TRY(film_copy(r.load_film.p, k.film, 16 * np));
+    HIP_TRY(film_copy(r.load_counts.p, k.counts, 4 * np));
+    HIP_TRY(film_copy(r.load_stats.p, k.stats, 16 * np));
+    float* stage = sc->assemble_staging.as<float>();
+    uint32_t* lists = sc->assemble_px.as<uint32_t>();
+    for (const pt_scene* s : k.shards) {
+        const uint32_t n_own = (uint32_t)s->shard_px.size();
+        if (n_own == 0) continue;   // (a shard without a pixel moves nothing and launches nothing)
+        const float* packed = s->shard_packed.as<float>();
+        if (staged(s)) {
+            HIP_TRY(hipMemcpyPeerAsync(stage, sc->device, packed, s->device, sizeof(float) * bins * n_own, stream));   // (legal within one device too)
+            packed = stage;
+            stage += (size_t)bins * n_own;
+        }
+        const uint32_t* px = s->buf.pixels;   // (the list its render left there)
+        if (!listed(s)) {
+            HIP_TRY(hipMemcpyAsync(lists, s->shard_px.data(), sizeof(uint32_t) * n_own, hipMemcpyHostToDevice, stream));
+            px = lists;
+            lists += n_own;
+        }
+        HIP_TRY(ptk::launch_spectral_unpack(ptk::spectral_pack_grid(sc->num_cus, n_own), stream, packed, px, n_own, bins, r.load_spectral.as<float>(), (uint32_t)np));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    r.parts = PT_RESIDENT_FILM | (bins ? PT_RESIDENT_BINS : 0u);
+    r.width = k.info.width; r.height = k.info.height; r.bins = bins;
+    r.film = r.load_film.as<float>(); r.counts = r.load_counts.as<uint32_t>(); r.stats = r.load_stats.as<double>();
+    r.spectral = bins ? r.load_spectral.as<float>() : nullptr;
+    return PT_OK;
+}
+pt_status pt_resident_read(pt_scene* sc, float* film, uint32_t* sample_counts, double* stats, float* spectral) {
+    std::string err;
+    const pt_status st = pth::check_resident_read_args(sc, film, sample_counts, stats, spectral, resident_now(sc), &err);
+    if (st != PT_OK) return fail(st, err);
+    const ResidentSet& r = sc->resident;
+    DeviceGuard guard;
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t np = (size_t)r.width * r.height;
+    const hipStream_t stream = nullptr;
+    if (film) HIP_TRY(hipMemcpyAsync(film, r.film, 16 * np, hipMemcpyDeviceToHost, stream));
+    if (sample_counts) HIP_TRY(hipMemcpyAsync(sample_counts, r.counts, 4 * np, hipMemcpyDeviceToHost, stream));
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, r.stats, 16 * np, hipMemcpyDeviceToHost, stream));
+    if (spectral) HIP_TRY(hipMemcpyAsync(spectral, r.spectral, 4 * np * r.bins, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     return PT_OK;
 }
 // The filter where the film is: ptk::dn_run (pt_denoise.hip), the run the host-array entries make between their upload and their read-back, on the resident

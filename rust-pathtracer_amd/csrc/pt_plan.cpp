@@ -388,6 +388,24 @@ pt_status check_resident_project_args(const void* scene, uint32_t K, const float
     return check_spectral_matrix(K, now.bins, matrix, error);
 }
 
+pt_status check_resident_assemble(const void* scene, uint32_t flags, const NodeRender& node, std::string* error) {
+    if (!scene) { *error = "pt_resident_assemble: the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (flags & ~PT_RESIDENT_ASSEMBLE_STAGED) { *error = "pt_resident_assemble: flags holds a bit that is not PT_RESIDENT_ASSEMBLE_STAGED"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!node.valid) { *error = "pt_resident_assemble: the scene has no node render to assemble: pt_render_adaptive_multi or pt_render_adaptive_spectral_multi must have succeeded on it over more than one device, with no render since"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!node.stats) { *error = "pt_resident_assemble: the node render was made without stats: the filter needs the statistics"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
+pt_status check_resident_read_args(const void* scene, const void* film, const void* sample_counts, const void* stats, const void* spectral, const struct pt_resident_info& now,
+                                   std::string* error) {
+    if (!scene) { *error = "pt_resident_read: the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (film && !(now.parts & PT_RESIDENT_FILM)) { *error = "pt_resident_read: film_xyzw without a resident film"; return PT_ERR_INVALID_ARGUMENT; }
+    if (sample_counts && !(now.parts & PT_RESIDENT_FILM)) { *error = "pt_resident_read: sample_counts without a resident film"; return PT_ERR_INVALID_ARGUMENT; }
+    if (stats && !(now.parts & PT_RESIDENT_FILM)) { *error = "pt_resident_read: stats without a resident film"; return PT_ERR_INVALID_ARGUMENT; }
+    if (spectral && !(now.parts & PT_RESIDENT_BINS)) { *error = "pt_resident_read: spectral without resident bins"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
 pt_status check_spectral_project_args(uint32_t width, uint32_t height, uint32_t bins, uint32_t K, const float* matrix, const void* spectral, const void* out,
                                       std::string* error) {
     if (!spectral) { *error = "the spectral film is null"; return PT_ERR_INVALID_ARGUMENT; }

@@ -114,6 +114,18 @@ pt_status check_resident_denoise_args(const void* scene, const pt_resident_denoi
                                       pt_denoise_desc* out, std::string* error);
 // pt_spectral_project_resident_denoised: pt_spectral_project_resident's checks, over the resident denoised bins
 pt_status check_resident_project_args(const void* scene, uint32_t K, const float* matrix, const void* out, const struct pt_resident_info& now, std::string* error);
+// What a scene remembers of its last adaptive node render (pt_render_adaptive_multi, pt_render_adaptive_spectral_multi over more than one device) while the
+// pieces lie where that render left them: the size, the bins (0 without a spectral film) and whether the statistics were gathered.  Every render entry
+// forgets it when it starts.
+struct NodeRender {
+    bool valid = false, stats = false;
+    uint32_t width = 0, height = 0, bins = 0;
+};
+// pt_resident_assemble: the scene; the flags known; a node render to assemble; one made with stats — each refusal with its own message
+pt_status check_resident_assemble(const void* scene, uint32_t flags, const NodeRender& node, std::string* error);
+// pt_resident_read: a pointer that is given names a part that is resident (film_xyzw, sample_counts and stats: FILM; spectral: BINS)
+pt_status check_resident_read_args(const void* scene, const void* film, const void* sample_counts, const void* stats, const void* spectral, const struct pt_resident_info& now,
+                                   std::string* error);
 
 }  // namespace pth
 #endif

@@ -8,6 +8,8 @@
 // and the scatter is the same assignment read from right to left.  Values are moved, never computed with: every bit pattern survives, NaN payloads and
 // -0.0 included.  Every pixel of a film is in exactly one shard's list (tests/test_spectral_multi.py), so scattering every shard writes every float of
 // the planes exactly once.  The planes of a development (K of them, pt_spectral_project_resident) are scattered by the same rule with bins = K.
+// spectral_shard_unpack_item is the scatter as the device runs it (k_spectral_unpack, pt_resident_assemble of include/pt_resident.h): item by item, so the
+// destination planes need no zeroing and the shards may be unpacked in any order or side by side.
 #ifndef PT_SPECTRAL_SHARD_RULES_H
 #define PT_SPECTRAL_SHARD_RULES_H
 #include <stddef.h>
@@ -24,6 +26,12 @@ PT_HD void spectral_shard_pack_item(const float* planes, size_t plane_pixels, co
     const uint32_t pixel = px[i];
 #pragma unroll 4   // (four plane loads in flight per lane)
     for (uint32_t b = 0; b < bins; ++b) packed[spectral_shard_packed_index(b, n_own, i)] = planes[spectral_shard_plane_index(b, plane_pixels, pixel)];
+}
+// The inverse, item i of a shard, every bin: px[i] is read once
+PT_HD void spectral_shard_unpack_item(const float* packed, const uint32_t* px, uint32_t n_own, uint32_t bins, uint32_t i, float* planes, size_t plane_pixels) {
+    const uint32_t pixel = px[i];
+#pragma unroll 4   // (four packed loads in flight per lane)
+    for (uint32_t b = 0; b < bins; ++b) planes[spectral_shard_plane_index(b, plane_pixels, pixel)] = packed[spectral_shard_packed_index(b, n_own, i)];
 }
 // A whole shard back into full-size planes, plane by plane: a host thread reads its packed planes in order and writes runs of a tile row
 PT_HD void spectral_shard_scatter(const float* packed, const uint32_t* px, uint32_t n_own, uint32_t bins, float* planes, size_t plane_pixels) {

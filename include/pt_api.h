@@ -255,8 +255,14 @@ enum {
                                           interior acceptance: pt_blob.h PT_INST_CONVEX_*, PT_PATH_INSIDE_MARK, round 6) */
     PT_TUNE_NO_MESH_SHORTCUTS = 1u << 16, /* PT_AMD_NO_MESH_SHORTCUTS: no mesh is decided without its triangle tests — a closed mesh's inner balls (a bounded light ray through one is blocked)
                                           and its 18-DOP slabs (a ray outside one misses) are not used; the searches they cut short run in full.  A diagnostic: the films are the same bit for bit */
-    PT_TUNE_NO_AXIS_SCAN = 1u << 13    /* PT_AMD_NO_AXIS_SCAN: the parked kernels walk a ray that is parallel to an axis of its mesh like any other (by default the
+    PT_TUNE_NO_AXIS_SCAN = 1u << 13,   /* PT_AMD_NO_AXIS_SCAN: the parked kernels walk a ray that is parallel to an axis of its mesh like any other (by default the
                                           whole wave scans the mesh's leaves for it: such a ray passes most boxes, AABB::hit ignoring the axes its direction is zero along) */
+    PT_TUNE_NO_PASS_OVERLAP = 1u << 17, /* PT_AMD_NO_PASS_OVERLAP: the passes of a render run one after the other on the caller's stream with one set of pass buffers (by default
+                                          consecutive passes overlap on two streams with two sets).  Also what per-kernel profiling wants: a kernel trace's
+                                          durations are per-kernel times only without overlap */
+    PT_TUNE_PASS_SKEW_SHIFT = 18,      /* PT_AMD_PASS_SKEW: three bits of flags from this one up.  With overlap, pass p + 1 starts behind pass p's launches of bounce g:
+                                          0 = the default (g = 0, the best of the four settings measured on C2: profiles/pass_overlap.md), 1 = no skew (the two passes start together), 2 + g = that g (0..5); g is clamped to the last bounce */
+    PT_TUNE_PASS_SKEW_MASK = 7
 };
 typedef struct pt_tuning {
     uint32_t flags;               /* PT_TUNE_* */
@@ -295,7 +301,12 @@ typedef struct pt_profile {      /* Profile (src/profile.rs:2-8) + timing */
     uint64_t bounce_rays, shadow_rays, light_rays, camera_rays, env_hits;
     double seconds;              /* render loop only: the window of src/renderer/tiled.rs:294 -> :536 */
     double kernel_seconds[8];    /* HIP-event time per stage: generate, extend, shade, shadow, accumulate (one event per launch boundary: a launch's time includes
-                                    the few microseconds of gap in front of it; the stream's non-kernel work — memsets — is charged to no stage); pt_render_multi adds
+                                    the few microseconds of gap in front of it; the stream's non-kernel work — memsets — is charged to no stage).  Where passes
+                                    overlapped (two streams, each with its own chain of events) a launch's interval includes time it shared the device with the
+                                    other stream's, so the intervals add up to more than the device was busy: a stage's value is then its intervals summed over both
+                                    streams, times W / (the sum of all stages' intervals), W = the render's device-busy window, first timing event to last over both
+                                    streams (the factor is never taken above 1).  The stages add up to at most W <= seconds; without overlap nothing is scaled.
+                                    pt_render_multi adds
                                     [5] = host seconds spent on set-up before the render window (replicas, streams, device films,
                                     communicator: paid by the first call with a device set and film size, cached on the scene after),
                                     [6] = host seconds of the film reduce; [7] spare */

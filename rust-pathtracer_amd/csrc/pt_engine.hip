@@ -338,8 +338,13 @@ struct pt_scene {
     uint32_t lacks = 0; // PT_SCENE_* bits: what the scene does not hold (kernel forms without it)
     int device = 0, num_cus = 0;
     DeviceBuffers buf;
+    // Pass overlap: a second set of everything a pass writes (its `pixels` stays null: the list is read-only and shared), made by the first
+    // render whose plan has two passes; the stream the odd passes run on; the events that order the two streams (DEP_*), made once and recorded again and again
+    DeviceBuffers buf2;
+    hipStream_t pass_stream = nullptr;
+    std::vector<hipEvent_t> pass_deps;
     AdaptiveBuffers adaptive;        // pt_render_adaptive's, kept between calls like buf
-    std::vector<hipEvent_t> events;  // pairs (start, stop), grown on demand
+    std::vector<hipEvent_t> events, events2;  // the timing events of the caller's stream and of pass_stream: one per launch boundary, grown on demand
     GrowBuf film_cache;            // pt_render's device film, kept between calls
     GrowBuf spectral_cache;        // pt_render_spectral's device planes (bins x width x height), kept between calls
     // The resident spectral film (pt_spectral_project_resident): what the last successful spectral render left in spectral_cache.  Cleared when a spectral render
@@ -385,8 +390,9 @@ uint32_t segment_capacity(uint32_t n, int grid) {
     return (c + 63u) & ~63u;
 }
 
-pt_status ensure_buffers(pt_scene* sc, uint32_t capacity, uint32_t light_samples, size_t n_pixels, int grid, uint32_t nl, uint32_t park_block) {
-    DeviceBuffers& b = sc->buf;
+// `b`: the scene's first set or its second (n_pixels 0: no pixel list of its own).  need_hits: the plan is not fused (a fused plan never touches the hit queue,
+// 5.9 GB at 128 Mi slots: it is made by the first render that needs it).
+pt_status ensure_buffers(pt_scene* sc, DeviceBuffers& b, uint32_t capacity, uint32_t light_samples, size_t n_pixels, int grid, uint32_t nl, uint32_t park_block, bool need_hits) {
     uint32_t total = segment_capacity(capacity, grid) * (uint32_t)grid;
     if (b.capacity < total || b.light_samples < light_samples || b.grid != grid || b.nl < nl || b.park_block < park_block) {
         hipFree(b.paths_a); hipFree(b.paths_b); hipFree(b.hits); hipFree(b.shadow); hipFree(b.energy); hipFree(b.counts); hipFree(b.block_stats); hipFree(b.park);
@@ -397,7 +403,6 @@ pt_status ensure_buffers(pt_scene* sc, uint32_t capacity, uint32_t light_samples
         size_t sh_fields = nlmax == 4 ? Layout<4>::shadow_queue_fields(ls ? ls : 1) : Layout<1>::shadow_queue_fields(ls ? ls : 1);
         HIP_TRY(hipMalloc(&b.paths_a, sizeof(uint32_t) * path_fields * total));
         HIP_TRY(hipMalloc(&b.paths_b, sizeof(uint32_t) * path_fields * total));
-        HIP_TRY(hipMalloc(&b.hits, sizeof(uint32_t) * (size_t)HS_FIELDS * total));
         HIP_TRY(hipMalloc(&b.shadow, sizeof(uint32_t) * sh_fields * total));
         HIP_TRY(hipMalloc(&b.energy, sizeof(float) * (size_t)(nlmax + 1u) * total));   // (+ the plane of wavelength samples, PT_STORED_WAVELENGTH)
         b.nl = nlmax;
@@ -413,6 +418,7 @@ pt_status ensure_buffers(pt_scene* sc, uint32_t capacity, uint32_t light_samples
         if (!b.unit_counters) HIP_TRY(hipMalloc(&b.unit_counters, sizeof(uint32_t) * kUnitCounters));
         b.capacity = total; b.light_samples = ls; b.grid = grid;
     }
+    if (need_hits && !b.hits) HIP_TRY(hipMalloc(&b.hits, sizeof(uint32_t) * (size_t)HS_FIELDS * b.capacity));
     if (b.pixel_capacity < n_pixels) {
         hipFree(b.pixels); b.pixels = nullptr;
         HIP_TRY(hipMalloc(&b.pixels, sizeof(uint32_t) * n_pixels));
@@ -694,13 +700,16 @@ pt_status plan_render(const pt_scene* sc, const pt_render_desc& rd, const Render
 }
 
 // A render's profile: the workgroups' counters read back and summed, beside what the pass loop counted and timed on the host.
-pt_status read_profile(pt_scene* sc, const RenderPlan& plan, uint64_t camera_rays, uint64_t accumulated_pixels, const double* stage_ms, const uint64_t* stage_launches,
+pt_status read_profile(pt_scene* sc, const RenderPlan& plan, bool second_set, uint64_t camera_rays, uint64_t accumulated_pixels, const double* stage_ms, const uint64_t* stage_launches,
                        uint32_t rounds, double seconds, pt_profile* profile) {
     memset(profile, 0, sizeof(*profile));
     std::vector<unsigned long long> bs((size_t)plan.grid * BS_FIELDS);
-    HIP_TRY(hipMemcpy(bs.data(), sc->buf.block_stats, sizeof(unsigned long long) * bs.size(), hipMemcpyDeviceToHost));
     unsigned long long c[BS_FIELDS] = {0, 0, 0, 0, 0, 0};
-    for (int g = 0; g < plan.grid; ++g) for (int k = 0; k < BS_FIELDS; ++k) c[k] += bs[(size_t)g * BS_FIELDS + k];
+    for (const unsigned long long* d_bs : {(const unsigned long long*)sc->buf.block_stats, (const unsigned long long*)(second_set ? sc->buf2.block_stats : nullptr)}) {   // (each set's workgroups count into their own)
+        if (!d_bs) continue;
+        HIP_TRY(hipMemcpy(bs.data(), d_bs, sizeof(unsigned long long) * bs.size(), hipMemcpyDeviceToHost));
+        for (int g = 0; g < plan.grid; ++g) for (int k = 0; k < BS_FIELDS; ++k) c[k] += bs[(size_t)g * BS_FIELDS + k];
+    }
     profile->camera_rays = camera_rays;
     profile->bounce_rays = c[BS_VERTICES] + camera_rays;  // vertices.len() counts the camera vertex (utils.rs:375)
     profile->shadow_rays = c[BS_SHADOW_RAYS];
@@ -715,6 +724,9 @@ pt_status read_profile(pt_scene* sc, const RenderPlan& plan, uint64_t camera_ray
     profile->kernel_launches[5] = rounds;           // pt_render_adaptive: its rounds (0 for pt_render)
     return PT_OK;
 }
+
+// The events that order the two streams of overlapped passes (pt_scene::pass_deps): the fork, and per pass parity the accumulate stage done and the skew bounce done
+enum { DEP_FORK = 0, DEP_ACCUMULATED = 1, DEP_SKEW = 3, DEP_COUNT = 5 };
 
 // A render in four steps: the plan (plan_render), the buffers and the upload of the pixel list, the pass loop — pt_render runs it once over its shard's pixels,
 // an adaptive job once per round (adaptive_rounds) — and the profile (read_profile).  `job`: what is optional about the render.
@@ -737,9 +749,34 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     const bool hero = plan.hero, park_dynamic = plan.park_dynamic;
     LaunchCfg cfg = plan.cfg;
 
-    st = ensure_buffers(sc, capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block);
+#ifdef PT_EXPERIMENTS
+    const bool need_hits = true;   // (the measurement forms of k_shadow keep scratch in the idle hit queue, fused plan or not)
+#else
+    const bool need_hits = !cfg.fuse;
+#endif
+    st = ensure_buffers(sc, sc->buf, capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits);
     if (st != PT_OK) return st;
     DeviceBuffers& b = sc->buf;
+    // Pass overlap: a render whose pass loop plans two passes or more (an adaptive one: in its first round or in a later round over every pixel) gets the second
+    // set of pass buffers, the second stream and the events between the two.  Where the device cannot give them the passes run one after the other as
+    // before: that is no error of the call.
+    bool overlap = !(sc->tuning.flags & PT_TUNE_NO_PASS_OVERLAP);
+    if (overlap) {
+        const uint32_t n_px = (uint32_t)pixels.size();
+        overlap = pth::plan_passes(n_px, rd.first_sample, adaptive ? rd.spp : rd.sample_count, capacity, rd.phase_samples).size() >= 2
+               || (adaptive && adaptive->max_samples > rd.spp && pth::plan_passes(n_px, rd.spp, adaptive->step < adaptive->max_samples - rd.spp ? adaptive->step : adaptive->max_samples - rd.spp, capacity, rd.phase_samples).size() >= 2);
+    }
+    if (overlap) {
+        bool ok = ensure_buffers(sc, sc->buf2, capacity, rd.light_samples, 0, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits) == PT_OK;
+        if (ok && !sc->pass_stream) ok = hipStreamCreateWithFlags(&sc->pass_stream, hipStreamNonBlocking) == hipSuccess;
+        while (ok && sc->pass_deps.size() < DEP_COUNT) {
+            hipEvent_t e;
+            ok = hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+            if (ok) sc->pass_deps.push_back(e);
+        }
+        if (!ok) { sc->buf2.release(); (void)hipGetLastError(); overlap = false; }   // (what was taken is given back, the sticky error cleared)
+    }
+    if (overlap && (trav_form == PT_FORM_PARKED || trav_form == PT_FORM_PARKED_WALK) && !sc->buf2.park) return fail(PT_ERR_DEVICE, "internal: a parked traversal form without the second set's scratch");
     if ((trav_form == PT_FORM_PARKED || trav_form == PT_FORM_PARKED_WALK) && !b.park) return fail(PT_ERR_DEVICE, "internal: a parked traversal form without the parked kernels' scratch");
     if (adaptive) {   // (round 0's list: every pixel of the film — or of the shard — in shard_pixels' order; counts and stats are zero outside it)
         const size_t film_pixels = (size_t)rd.width * rd.height;
@@ -754,6 +791,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     HIP_TRY(hipMemsetAsync(d_film, 0, sizeof(float) * 4 * (size_t)rd.width * rd.height, stream));
     if (job.d_spectral) HIP_TRY(hipMemsetAsync(job.d_spectral, 0, sizeof(float) * (size_t)job.spectral_bins * rd.width * rd.height, stream));
     HIP_TRY(hipMemsetAsync(b.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));
+    if (overlap) HIP_TRY(hipMemsetAsync(sc->buf2.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));   // (in front of the fork event)
 
     RenderParams rp;
     memset(&rp, 0, sizeof(rp));
@@ -765,8 +803,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     rp.normalize = (!adaptive && rd.first_sample == 0 && rd.sample_count == rd.spp) ? 1u : 0u;
     rp.phase = rd.phase_samples;
     rp.camera = pth::camera_params(sc->host.cameras[rd.camera_index], (float)rd.width / (float)rd.height);
-    rp.energy_stride = b.capacity;
-    rp.live_list = plan.live_list; rp.camera_record = plan.camera_record;
+    rp.live_list = plan.live_list; rp.camera_record = plan.camera_record;   // (energy_stride: the set's, per pass)
 
     const pt_tuning& tn = sc->tuning;
     const SceneArgs sargs{sc->d_blob, sc->blob_words, sc->d_tex, marginal_lds_bytes(sc->host.blob.data(), cfg.lds_bytes)};
@@ -774,9 +811,21 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     const bool timing = !(tn.flags & PT_TUNE_NO_STAGE_TIMING);
     double stage_ms[ST_COUNT] = {0, 0, 0, 0, 0};
     uint64_t stage_launches[ST_COUNT] = {0, 0, 0, 0, 0};
-    Queue qa{b.paths_a, b.capacity, plan.path_fields}, qb{b.paths_b, b.capacity, plan.path_fields}, qh{b.hits, b.capacity, HS_FIELDS}, qs{b.shadow, b.capacity, plan.item_fields};
-    uint32_t* live[2] = {b.counts, b.counts + grid};  // per-segment live-path counts, ping-pong with the path queues
-    uint32_t* nshadow = b.counts + 2 * grid;          // per-segment light-sample item counts; behind them (nshadow + grid) the counts of the live ones (Layout::shadow_live_field)
+    // A lane of the pass loop: a set of pass buffers, the stream its passes run on and that stream's chain of timing events.  Lane 0 is the first set on the caller's
+    // stream; lane 1 (overlap only) the second set on the scene's own stream.
+    struct Lane {
+        DeviceBuffers* set; hipStream_t stream; std::vector<hipEvent_t>* events;
+        Queue qa, qb, qh, qs;
+        uint32_t* live[2];         // per-segment live-path counts, ping-pong with the path queues
+        uint32_t* nshadow;         // per-segment light-sample item counts; behind them (nshadow + grid) the counts of the live ones (Layout::shadow_live_field)
+        size_t marks;              // timing events recorded
+        std::vector<int> stage;    // stage[k]: what the interval from event k to event k + 1 is charged to (-1: no stage)
+    };
+    auto make_lane = [&](DeviceBuffers& s, hipStream_t on, std::vector<hipEvent_t>* ev) {
+        return Lane{&s, on, ev, Queue{s.paths_a, s.capacity, plan.path_fields}, Queue{s.paths_b, s.capacity, plan.path_fields}, Queue{s.hits, s.capacity, HS_FIELDS},
+                    Queue{s.shadow, s.capacity, plan.item_fields}, {s.counts, s.counts + grid}, s.counts + 2 * grid, 0, {}};
+    };
+    Lane lanes[2] = {make_lane(b, stream, &sc->events), make_lane(overlap ? sc->buf2 : b, overlap ? sc->pass_stream : stream, &sc->events2)};
 
     HIP_TRY(hipStreamSynchronize(stream));
     const auto t0 = std::chrono::steady_clock::now();
@@ -784,28 +833,50 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     // per-stage device time is measured inside the timed region without stalling it.
     // (round 5: ONE event between two launches — the end of one is the start of the next on the stream — not two: the markers cost a short frame 5 % of its time,
     // G2 9.7 -> 9.2 ms per step without any; a launch's time now includes the gap in front of it, a few microseconds)
-    std::vector<int> event_stage;
-    auto event_at = [&](size_t k) -> bool {
-        while (sc->events.size() <= k) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return false; sc->events.push_back(e); }
-        return hipEventRecord(sc->events[k], stream) == hipSuccess;
+    // (pass overlap: each lane keeps its own chain; a wait for the other stream gets an event of its own behind it, so that the idle time is charged to no stage)
+    bool events_ok = timing;
+    auto mark = [&](Lane& l, int stage) {   // an event behind what the lane's stream holds so far: the interval since the lane's previous one is charged to `stage`
+        if (!events_ok) return;
+        while (l.events->size() <= l.marks) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { events_ok = false; return; } l.events->push_back(e); }
+        if (hipEventRecord((*l.events)[l.marks], l.stream) != hipSuccess) { events_ok = false; return; }
+        if (l.marks > 0) l.stage.push_back(stage);
+        ++l.marks;
     };
-    bool events_ok = timing && event_at(0);
-    auto timed = [&](int stage, auto&& fn) {
+    mark(lanes[0], -1);
+    auto timed = [&](Lane& l, int stage, auto&& fn) {
         fn();
-        if (events_ok) { events_ok = event_at(event_stage.size() + 1); if (events_ok) event_stage.push_back(stage); }
+        mark(l, stage);
         stage_launches[stage]++;
     };
 
     uint64_t camera_rays = 0, accumulated_pixels = 0;
     hipError_t spectral_error = hipSuccess;
+    bool overlapped = false;   // some pass loop of this render ran passes on both lanes
+    const std::vector<hipEvent_t>& dep = sc->pass_deps;
+    const uint32_t skew_code = (tn.flags >> PT_TUNE_PASS_SKEW_SHIFT) & PT_TUNE_PASS_SKEW_MASK;
+    const int32_t skew_bounce = skew_code == 0u ? pth::kPassSkewBounce : (int32_t)skew_code - 2;   // (1: -1, the passes start together)
     // The pass loop: samples [first_sample, first_sample + sample_count) of the n pixels of the device list d_list; stats (adaptive rounds): S1 / S2 too
     auto run_passes = [&](const uint32_t* d_list, uint32_t n_list, uint32_t first_sample, uint32_t sample_count, double* d_stats) -> pt_status {
         // (a later adaptive round: the stream's work since the previous accumulate — the round's decision and compaction — is charged to no stage)
-        if (camera_rays != 0 && events_ok) { events_ok = event_at(event_stage.size() + 1); if (events_ok) event_stage.push_back(-1); }
+        if (camera_rays != 0) mark(lanes[0], -1);
         rp.range_end = first_sample + sample_count;
         // the planner's capacity is in items; segments round up, so plan with what surely fits
         std::vector<pth::Pass> passes = pth::plan_passes(n_list, first_sample, sample_count, capacity, rd.phase_samples);
-        for (const pth::Pass& pass : passes) {
+        // which pass runs on which lane, behind which events (pt_plan.h): without overlap, or with one pass, everything on lane 0 and no event
+        const pth::PassSchedule sch = pth::schedule_passes((uint32_t)passes.size(), bounce_limit, skew_bounce, overlap);
+        const bool two_lanes = sch.steps.size() >= 2 && sch.steps[1].lane == 1u;
+        if (two_lanes) { HIP_TRY(hipEventRecord(dep[DEP_FORK], stream)); overlapped = true; }   // (behind whatever the caller's stream holds: an adaptive round's compaction)
+        for (size_t p = 0; p < passes.size(); ++p) {
+            const pth::Pass& pass = passes[p];
+            const pth::PassStep& step = sch.steps[p];
+            Lane& l = lanes[step.lane];
+            DeviceBuffers& b = *l.set;
+            const hipStream_t stream = l.stream;
+            const Queue &qa = l.qa, &qb = l.qb, &qh = l.qh, &qs = l.qs;
+            uint32_t* const* live = l.live;
+            uint32_t* const nshadow = l.nshadow;
+            cfg.stream = stream;
+            rp.energy_stride = b.capacity;
             accumulated_pixels += pass.pixel_count;
             rp.chunk_pixels = pass.pixel_count; rp.first_sample = pass.first_sample; rp.pass_samples = pass.sample_count;
             uint32_t n = pass.pixel_count * pass.sample_count;
@@ -813,12 +884,15 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
             uint32_t seg_cap = segment_capacity(n, grid);
             camera_rays += n;
             const uint32_t* d_px = d_list + pass.pixel_begin;
+            if (step.wait_fork) HIP_TRY(hipStreamWaitEvent(stream, dep[DEP_FORK], 0));
+            if (step.start_after >= 0) HIP_TRY(hipStreamWaitEvent(stream, dep[DEP_SKEW + (step.start_after & 1)], 0));
+            if (step.wait_fork || step.start_after >= 0) mark(l, -1);
             if (park_dynamic) {
                 HIP_TRY(hipMemsetAsync(b.unit_counters, 0, sizeof(uint32_t) * kUnitCounters, stream));
                 // (round-5 advisor) an event of its own behind the stream's non-kernel work, charged to no stage: k_generate's time begins here, not at the end of the previous pass
-                if (events_ok) { events_ok = event_at(event_stage.size() + 1); if (events_ok) event_stage.push_back(-1); }
+                mark(l, -1);
             }
-            timed(ST_GENERATE, [&] {
+            timed(l, ST_GENERATE, [&] {
                 if (hero) hipLaunchKernelGGL(k_generate<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, qa, b.energy, n, seg_cap, live[0]);
                 else hipLaunchKernelGGL(k_generate<1>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, qa, b.energy, n, seg_cap, live[0]);
             });
@@ -830,13 +904,17 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                 // (a marked path segment — it left the scene's one certified convex body outward — skips that instance: records the vertex kernel wrote, so from bounce 1 on; never
                 // in the medium-aware walk, whose vertex code makes no marks)
                 cfg.path_marks = (bounce > 0 && !rd.medium_aware && (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_CONVEX)) ? sc->host.blob[PT_HDR_CONVEX_INST] : 0u;
-                if (!cfg.fuse) timed(ST_EXTEND, [&] { launch_extend(cfg, trav_form, sargs, qin, qh, seg_cap, cin, b.park); });
+                if (!cfg.fuse) timed(l, ST_EXTEND, [&] { launch_extend(cfg, trav_form, sargs, qin, qh, seg_cap, cin, b.park); });
                 if (park_dynamic) cfg.unit_counter = b.unit_counters + 2 * bounce + 1;
-                timed(ST_SHADE, [&] { launch_shade(cfg, hero ? 4 : 1, shade_form, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats); });
+                timed(l, ST_SHADE, [&] { launch_shade(cfg, hero ? 4 : 1, shade_form, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats); });
                 if (rd.light_samples > 0)   // (shade_form FULL = the scene can produce environment rays)
-                    timed(ST_SHADOW, [&] { launch_shadow(cfg, trav_form, hero ? 4 : 1, shade_form == PT_SHADE_FULL || shade_form == PT_SHADE_MEDIUM, sargs, rd.light_samples, qs, b.energy, b.capacity, rp.live_list ? (seg_cap | kShadowListed) : seg_cap, nshadow, b.park, qh); });
+                    timed(l, ST_SHADOW, [&] { launch_shadow(cfg, trav_form, hero ? 4 : 1, shade_form == PT_SHADE_FULL || shade_form == PT_SHADE_MEDIUM, sargs, rd.light_samples, qs, b.energy, b.capacity, rp.live_list ? (seg_cap | kShadowListed) : seg_cap, nshadow, b.park, qh); });
+                // (the next pass starts behind this bounce: started together the two would run in lock step, tail on tail)
+                if ((int32_t)bounce == step.signal_bounce) HIP_TRY(hipEventRecord(dep[DEP_SKEW + (p & 1)], stream));
             }
-            timed(ST_ACCUMULATE, [&] {
+            // (the film sums keep the pass order: phases of 10, pixels continued across passes)
+            if (step.accumulate_after >= 0) { HIP_TRY(hipStreamWaitEvent(stream, dep[DEP_ACCUMULATED + (step.accumulate_after & 1)], 0)); mark(l, -1); }
+            timed(l, ST_ACCUMULATE, [&] {
                 if (d_stats && hero) hipLaunchKernelGGL(k_accumulate_stats<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film, d_stats);
                 else if (d_stats) hipLaunchKernelGGL(k_accumulate_stats<1>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film, d_stats);
                 else if (hero) hipLaunchKernelGGL(k_accumulate<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film);
@@ -846,7 +924,10 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                     spectral_error = ptk::launch_accumulate_spectral(hero ? 4 : 1, grid, stream, rp, d_px, b.energy, job.d_spectral, job.spectral_bins, rd.width * rd.height);
             });
             if (spectral_error != hipSuccess) return fail(PT_ERR_DEVICE, std::string("k_accumulate_spectral: ") + hipGetErrorString(spectral_error));
+            if (two_lanes) HIP_TRY(hipEventRecord(dep[DEP_ACCUMULATED + (p & 1)], stream));
         }
+        // the join: what the caller's stream holds next — an adaptive round's decision, the final synchronise, the caller's own kernels — sees every pass
+        if (sch.join_pass >= 0) HIP_TRY(hipStreamWaitEvent(stream, dep[DEP_ACCUMULATED + (sch.join_pass & 1)], 0));
         return PT_OK;
     };
     uint32_t rounds = 0;
@@ -858,11 +939,22 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     auto t1 = std::chrono::steady_clock::now();
-    for (size_t k = 0; k < event_stage.size(); ++k) {
+    for (const Lane& l : lanes) for (size_t k = 0; k < l.stage.size(); ++k) {
         float ms = 0.0f;
-        if (event_stage[k] >= 0 && hipEventElapsedTime(&ms, sc->events[k], sc->events[k + 1]) == hipSuccess) stage_ms[event_stage[k]] += ms;
+        if (l.stage[k] >= 0 && hipEventElapsedTime(&ms, (*l.events)[k], (*l.events)[k + 1]) == hipSuccess) stage_ms[l.stage[k]] += ms;
     }
-    if (profile) return read_profile(sc, plan, camera_rays, accumulated_pixels, stage_ms, stage_launches, rounds, std::chrono::duration<double>(t1 - t0).count(), profile);
+    if (overlapped && lanes[0].marks > 0) {
+        // (pt_profile::kernel_seconds: overlapped intervals add up to more than the device was busy, so each stage gets its share of the busy window, the first
+        // timing event to the last over both streams)
+        double window = 0.0, total = 0.0;
+        for (const Lane& l : lanes) {
+            float ms = 0.0f;
+            if (l.marks > 0 && hipEventElapsedTime(&ms, (*lanes[0].events)[0], (*l.events)[l.marks - 1]) == hipSuccess && ms > window) window = ms;
+        }
+        for (double ms : stage_ms) total += ms;
+        if (window > 0.0 && total > window) for (double& ms : stage_ms) ms *= window / total;
+    }
+    if (profile) return read_profile(sc, plan, overlap, camera_rays, accumulated_pixels, stage_ms, stage_launches, rounds, std::chrono::duration<double>(t1 - t0).count(), profile);
     return PT_OK;
 }
 
@@ -968,7 +1060,7 @@ void pt_tuning_default(pt_tuning* t) {
 
         {"PT_AMD_EXACT_SLAB", PT_TUNE_EXACT_SLAB}, {"PT_AMD_NO_CULL", PT_TUNE_NO_CULL}, {"PT_AMD_NO_SWEEP", PT_TUNE_NO_SWEEP}, {"PT_AMD_NO_MESH_SWEEP", PT_TUNE_NO_MESH_SWEEP},
         {"PT_AMD_NO_KNOWN_LIGHT", PT_TUNE_NO_KNOWN_LIGHT}, {"PT_AMD_GENERAL_FORMS", PT_TUNE_GENERAL_FORMS}, {"PT_AMD_NO_FUSE", PT_TUNE_NO_FUSE}, {"PT_AMD_MULTI_RCCL", PT_TUNE_MULTI_RCCL}, {"PT_AMD_NO_AXIS_SCAN", PT_TUNE_NO_AXIS_SCAN}, {"PT_AMD_NO_ONE_LIGHT", PT_TUNE_NO_ONE_LIGHT}, {"PT_AMD_NO_CONVEX", PT_TUNE_NO_CONVEX}, {"PT_AMD_NO_MESH_SHORTCUTS", PT_TUNE_NO_MESH_SHORTCUTS},
-        {"PT_AMD_NO_LIVE_LIST", PT_TUNE_NO_LIVE_LIST},
+        {"PT_AMD_NO_LIVE_LIST", PT_TUNE_NO_LIVE_LIST}, {"PT_AMD_NO_PASS_OVERLAP", PT_TUNE_NO_PASS_OVERLAP},
     };
     for (const auto& f : flags) if (env_u32(f.name, 0)) t->flags |= f.bit;
     if (env_u32("PT_AMD_STAGE_TIMING", 1) == 0) t->flags |= PT_TUNE_NO_STAGE_TIMING;
@@ -985,6 +1077,7 @@ void pt_tuning_default(pt_tuning* t) {
     t->light_prepass_max = env_u32("PT_AMD_LIGHT_PREPASS_MAX", 0);
     t->top_evict_below = env_u32("PT_AMD_TOP_EVICT_BELOW", 0);
     t->group_evict_below = env_u32("PT_AMD_GROUP_EVICT_BELOW", 0);
+    t->flags |= (env_u32("PT_AMD_PASS_SKEW", 0) & PT_TUNE_PASS_SKEW_MASK) << PT_TUNE_PASS_SKEW_SHIFT;
 }
 
 pt_status pt_scene_create(const pt_scene_desc* desc, pt_scene** out) {
@@ -1025,9 +1118,11 @@ void pt_scene_destroy(pt_scene* sc) {
     if (sc->multi.valid) multi_release(sc->multi);
     hipSetDevice(sc->device);
     sc->buf.release();
+    sc->buf2.release();
     sc->adaptive.release();
     hipFree(sc->d_blob); hipFree(sc->d_tex);
-    for (auto& e : sc->events) hipEventDestroy(e);
+    for (auto* list : {&sc->events, &sc->events2, &sc->pass_deps}) for (auto& e : *list) hipEventDestroy(e);
+    if (sc->pass_stream) hipStreamDestroy(sc->pass_stream);
     delete sc;   // (the grow-only buffers go with it: the replicas are gone and the device is this scene's)
 }
 

@@ -38,6 +38,24 @@ std::vector<uint32_t> shard_pixels(uint32_t width, uint32_t height, uint32_t tw,
     return px;
 }
 
+PassSchedule schedule_passes(uint32_t n_passes, uint32_t bounces, int32_t skew_bounce, bool overlap) {
+    PassSchedule sch;
+    sch.steps.assign(n_passes, PassStep{0u, false, -1, -1, -1});
+    if (!overlap || n_passes < 2) return sch;
+    const int32_t g = (skew_bounce < 0 || bounces == 0) ? -1 : (skew_bounce < (int32_t)bounces ? skew_bounce : (int32_t)bounces - 1);
+    for (uint32_t p = 0; p < n_passes; ++p) {
+        PassStep& s = sch.steps[p];
+        s.lane = p & 1u;
+        s.wait_fork = p == 1;
+        s.start_after = (p > 0 && g >= 0) ? (int32_t)p - 1 : -1;
+        s.accumulate_after = p > 0 ? (int32_t)p - 1 : -1;
+        s.signal_bounce = p + 1 < n_passes ? g : -1;
+    }
+    // (an even last pass has waited for the odd one before it in its accumulate stage: the caller's stream is already behind everything)
+    sch.join_pass = ((n_passes - 1) & 1u) ? (int32_t)n_passes - 1 : -1;
+    return sch;
+}
+
 std::vector<Pass> plan_passes(uint32_t n_pixels, uint32_t first_sample, uint32_t sample_count, uint32_t capacity, uint32_t phase_samples) {
     std::vector<Pass> passes;
     if (n_pixels == 0 || sample_count == 0) return passes;

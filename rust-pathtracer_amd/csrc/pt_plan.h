@@ -27,6 +27,22 @@ struct Pass { uint32_t pixel_begin, pixel_count, first_sample, sample_count; };
 // (tiled.rs:347-361) unless the requested range itself does, so the film sums keep the reference's order.
 std::vector<Pass> plan_passes(uint32_t n_pixels, uint32_t first_sample, uint32_t sample_count, uint32_t capacity, uint32_t phase_samples = 10);
 
+// Pass overlap: which of the pass loop's passes runs where, and behind what.  Consecutive passes run on two streams with two sets of pass buffers, so that one
+// pass's launch tails and thin late bounces are filled with the next pass's early launches.  Pass p takes set and stream p % 2 (`lane`; 0 = the caller's
+// stream), so pass p + 2 follows pass p in stream order and at most two passes are in flight.  Everything else is an event:
+//   wait_fork         its first launch waits for the event recorded on the caller's stream when the pass loop began (the first pass of the second stream)
+//   start_after       the pass behind whose bounce `signal_bounce` its first launch waits (-1 = none): two passes started together would run in lock step,
+//                     their tails on top of each other
+//   accumulate_after  the pass behind whose accumulate stage its own waits (-1 = none): the film sums keep the pass order
+//   signal_bounce     the bounce behind whose launches it records the event the next pass starts after (-1 = none)
+// join_pass: the pass behind whose accumulate stage the caller's stream waits before the loop returns (-1 = none: the last pass ran on it, behind every other).
+struct PassStep { uint32_t lane; bool wait_fork; int32_t start_after, accumulate_after, signal_bounce; };
+struct PassSchedule { std::vector<PassStep> steps; int32_t join_pass = -1; };
+// bounces: the vertex launches of a pass; skew_bounce: the bounce g a pass signals behind (clamped to the last one), < 0 = the passes start together;
+// overlap false, or fewer than two passes: every pass on lane 0, no event at all.
+PassSchedule schedule_passes(uint32_t n_passes, uint32_t bounces, int32_t skew_bounce, bool overlap);
+constexpr int32_t kPassSkewBounce = 0;   // the default g: measured best on C2 (profiles/pass_overlap.md)
+
 // ProjectiveCamera::new + with_aspect_ratio (src/camera/projective_camera.rs:27-95, 121-133)
 ptd::CameraParams camera_params(const pt_camera& c, float aspect_ratio);
 

@@ -8,6 +8,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
+# (per-kernel durations and counters: the serial pass loop — with pass overlap two kernels share the device; PT_AMD_NO_PASS_OVERLAP=0 keeps the overlap)
+export PT_AMD_NO_PASS_OVERLAP=${PT_AMD_NO_PASS_OVERLAP:-1}
 ARGS="--steps 2 --warmup 1 --cpu-seconds 0 $*"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/bench_trace.log" 2>&1
 echo "trace rc=$?" >> "$OUT/bench_trace.log"

@@ -6,7 +6,7 @@
 //         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K] [--demodulate-albedo]
 //         [--guide-chain D] [--guide-alpha-max A] [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]
 //         [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK] [--denoise-resident]
-//         [--denoise-assemble]
+//         [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -51,6 +51,13 @@
 // filter and, with --develop, the denoised development on the assembled set, as --denoise-resident does after a one-device render: the bins are not uploaded
 // again.  The undenoised bins are developed shard by shard where the node render left them, as without the flag.  Every file stays byte for byte what the run
 // without it writes.  It is refused together with --denoise-resident, which is the one-device form.
+// --light-groups instance|material renders every setting through pt_render_light_groups (include/pt_light_groups.h) and also writes <filename>_light<g>.exr, group g's
+// film through the setting's own film output.  `instance`: every emitting instance (a light material as its override, or on a face of its mesh) is a group of its
+// own, in scene order; `material`: every light material is, in the order the instances first use them; the environment is the last group when it emits (strength
+// other than 0).  What does not emit is in group 0.  More than 8 groups end the program once the scene file is loaded.  The usual files stay byte for byte what they
+// are: the film is the total.  --light-gains G0,G1,... (with --light-groups only, one gain per group) also writes <filename>_relit.exr / .png: the group films
+// times their gains, mixed where the render left them on the device (pt_light_groups_mix_resident).  Refused together with --adaptive, --denoise, --spectral-bins,
+// --denoise-spectral-bins, --devices, --spectral-devices and --hero-wavelengths.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -62,6 +69,7 @@
 
 #include "../../../include/pt_adaptive.h"
 #include "../../../include/pt_denoise.h"
+#include "../../../include/pt_light_groups.h"
 #include "../../../include/pt_scene_file.h"
 #include "../../../include/pt_resident.h"
 #include "../../../include/pt_spectral.h"
@@ -94,6 +102,9 @@ struct Options {
     bool resident = false;        // --denoise-resident: guides, filter and developments on the scene's resident set (include/pt_resident.h)
     bool spectral_multi = false;  // --spectral-devices MASK: the spectral node calls (pt_render_spectral_multi / pt_render_adaptive_spectral_multi)
     uint64_t spectral_device_mask = 0;
+    int light_groups = 0;         // --light-groups: 1 = a group per emitting instance, 2 = per light material; 0 = off
+    bool has_light_gains = false; // --light-gains: <filename>_relit.* from the resident mix
+    std::vector<float> light_gains;
     bool assemble = false;        // --denoise-assemble: the node render assembled on the scene's device, then as `resident` (pt_resident_assemble)
 };
 
@@ -104,7 +115,7 @@ int usage(const char* msg) {
                     "             [--denoise] [--guide-samples K] [--demodulate-albedo] [--guide-chain D] [--guide-alpha-max A]\n"
                     "             [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]\n"
                     "             [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK]\n"
-                    "             [--denoise-resident] [--denoise-assemble]\n");
+                    "             [--denoise-resident] [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]\n");
     return 2;
 }
 
@@ -226,8 +237,36 @@ int main(int argc, char** argv) {
             if (end == v.c_str() || *end) return usage("--spectral-devices needs a device mask (bit d = HIP device d, 0 = all)");
             o.spectral_multi = true;
         }
+        else if (a == "--light-groups") {
+            if (!value(&v)) return usage("--light-groups needs a value");
+            o.light_groups = v == "instance" ? 1 : v == "material" ? 2 : 0;
+            if (!o.light_groups) return usage("--light-groups needs `instance` or `material`");
+        }
+        else if (a == "--light-gains") {
+            if (!value(&v)) return usage("--light-gains needs a value");
+            o.has_light_gains = true;
+            o.light_gains.clear();
+            for (size_t at = 0; at <= v.size();) {
+                const size_t comma = v.find(',', at);
+                const std::string item = v.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+                char* end = nullptr;
+                const float g = strtof(item.c_str(), &end);
+                if (item.empty() || end == item.c_str() || *end || !(g > -1e30f && g < 1e30f)) return usage("--light-gains needs finite gains G0,G1,...");
+                o.light_gains.push_back(g);
+                if (comma == std::string::npos) break;
+                at = comma + 1;
+            }
+            if (o.light_gains.size() > PT_LIGHT_GROUPS_MAX) return usage("--light-gains takes at most 8 gains");
+        }
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
+    }
+    if (o.has_light_gains && !o.light_groups) return usage("--light-gains needs --light-groups");
+    if (o.light_groups) {
+        const char* with = o.adaptive >= 0.0f ? "--adaptive" : o.denoise ? "--denoise" : o.spectral_bins ? "--spectral-bins" : o.denoise_bins ? "--denoise-spectral-bins"
+                         : o.multi ? "--devices" : o.spectral_multi ? "--spectral-devices" : o.hero ? "--hero-wavelengths" : nullptr;
+        static std::string refusal;
+        if (with) { refusal = std::string("--light-groups cannot be combined with ") + with + ": a group render is one plain render of one wavelength per path on one device"; return usage(refusal.c_str()); }
     }
     if (o.demodulate && !o.denoise) return usage("--demodulate-albedo needs --denoise");
     if (o.chain && !o.denoise) return usage("--guide-chain needs --denoise");
@@ -299,6 +338,48 @@ int main(int argc, char** argv) {
         }
     }
 
+    // --light-groups: a group per emitting instance or per light material in scene order, the environment last when it emits
+    std::vector<uint8_t> instance_group(desc->instance_count, 0);
+    pt_light_groups_desc gd;
+    memset(&gd, 0, sizeof(gd));
+    if (o.light_groups) {
+        std::vector<uint32_t> keys;   // a group's key: the instance (mode 1) or the packed light material (mode 2)
+        uint32_t groups = 0;
+        for (uint32_t i = 0; i < desc->instance_count; ++i) {
+            const pt_instance& in = desc->instances[i];
+            uint32_t light = PT_MATERIAL_NONE;   // the instance's first light material
+            if (in.material != PT_MATERIAL_NONE) { if (PT_MATERIAL_TAG(in.material) == PT_TAG_LIGHT) light = in.material; }
+            else if (in.kind == PT_SHAPE_MESH && in.mesh >= 0 && (uint32_t)in.mesh < desc->mesh_count && desc->meshes[in.mesh].face_material_offset >= 0) {
+                const pt_mesh& m = desc->meshes[in.mesh];
+                for (uint32_t f = 0; f < m.face_count && light == PT_MATERIAL_NONE; ++f) {
+                    const uint32_t id = desc->face_materials[(size_t)m.face_material_offset + f];
+                    if (PT_MATERIAL_TAG(id) == PT_TAG_LIGHT) light = id;
+                }
+            }
+            if (light == PT_MATERIAL_NONE) continue;
+            const uint32_t key = o.light_groups == 1 ? i : light;
+            uint32_t g = 0;
+            while (g < keys.size() && keys[g] != key) ++g;
+            if (g == keys.size()) keys.push_back(key);
+            if (g < PT_LIGHT_GROUPS_MAX) instance_group[i] = (uint8_t)g;
+        }
+        groups = (uint32_t)keys.size();
+        const bool env_emits = desc->environment.strength != 0.0f;
+        gd.environment_group = env_emits ? groups : 0u;
+        if (env_emits) ++groups;
+        if (groups == 0) groups = 1;
+        const char* why = groups > PT_LIGHT_GROUPS_MAX ? "the scene has more than 8 light groups"
+                          : (o.has_light_gains && o.light_gains.size() != groups) ? "--light-gains needs one gain per group" : nullptr;
+        if (why) {
+            fprintf(stderr, "error: --light-groups: %s (%u groups)\n", why, groups);
+            pt_scene_file_free(scene_file);
+            pt_config_free(config);
+            return 1;
+        }
+        gd.group_count = groups; gd.instance_count = desc->instance_count; gd.instance_group = instance_group.data();
+        printf("light groups: %u (%s%s)\n", groups, o.light_groups == 1 ? "one per emitting instance" : "one per light material", env_emits ? ", the environment last" : "");
+    }
+
     // --denoise: what the adaptive path refuses is refused here, with its message, before anything is rendered or written
     if (o.denoise && !o.dry_run) {
         uint32_t tw = 0, th = 0;
@@ -360,6 +441,7 @@ int main(int argc, char** argv) {
             std::vector<uint32_t> counts(with_counts ? (size_t)rd.width * rd.height : 0);
             std::vector<double> stats(o.denoise ? (size_t)rd.width * rd.height * 2 : 0);
             std::vector<float> spectral((size_t)o.denoise_bins * rd.width * rd.height);   // (--spectral-bins sizes it below)
+            std::vector<float> group_films;   // (--light-groups sizes it below)
             const pt_spectral_desc dsd = {o.denoise_bins, {0u, 0u, 0u}};
             const char* adaptive_entry = o.denoise_bins ? (o.spectral_multi ? "pt_render_adaptive_spectral_multi" : "pt_render_adaptive_spectral")
                                          : o.multi      ? "pt_render_adaptive_multi" : "pt_render_adaptive";
@@ -396,6 +478,10 @@ int main(int argc, char** argv) {
                 const pt_status st = o.spectral_multi ? pt_render_spectral_multi(scene, &rd, &sd, o.spectral_device_mask, film.data(), spectral.data(), &prof)
                                                       : pt_render_spectral(scene, &rd, &sd, film.data(), spectral.data(), &prof);
                 if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.spectral_multi ? "pt_render_spectral_multi" : "pt_render_spectral", pt_last_error()); rc = 1; break; }
+            } else if (o.light_groups) {
+                printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u, %u light groups\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples, gd.group_count);
+                group_films.resize((size_t)gd.group_count * rd.width * rd.height * 4);
+                if (pt_render_light_groups(scene, &rd, &gd, film.data(), group_films.data(), &prof) != PT_OK) { fprintf(stderr, "pt_render_light_groups: %s\n", pt_last_error()); rc = 1; break; }
             } else {
                 printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
                 const pt_status st = o.multi ? pt_render_multi(scene, &rd, o.device_mask, film.data(), &prof) : pt_render(scene, &rd, film.data(), &prof);
@@ -418,6 +504,28 @@ int main(int argc, char** argv) {
             }
             if (o.write_film && !write_npy(base + ".npy", film.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", base.c_str()); rc = 1; break; }
             printf("wrote %s.exr and %s.png\n", base.c_str(), base.c_str());
+            // --light-groups: every group's film, and with --light-gains the resident mix, through this setting's film output (buffers of their own)
+            if (o.light_groups) {
+                const size_t np = (size_t)rd.width * rd.height;
+                std::vector<float> g_linear(3 * np), relit(4 * np), matrices;
+                std::vector<uint8_t> g_rgba(4 * np);
+                bool ok = true;
+                for (uint32_t g = 0; ok && g < gd.group_count; ++g) {
+                    const std::string name = base + "_light" + std::to_string(g);
+                    ok = pt_output_film(&od, group_films.data() + 4 * np * g, g_rgba.data(), g_linear.data()) == PT_OK &&
+                         pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, g_linear.data(), od.colorspace) == PT_OK;
+                    if (ok) printf("wrote %s.exr\n", name.c_str());
+                }
+                if (ok && o.has_light_gains) {
+                    for (float gain : o.light_gains) for (int k = 0; k < 9; ++k) matrices.push_back(k % 4 == 0 ? gain : 0.0f);
+                    const std::string name = base + "_relit";
+                    ok = pt_light_groups_mix_resident(scene, matrices.data(), relit.data()) == PT_OK && pt_output_film(&od, relit.data(), g_rgba.data(), g_linear.data()) == PT_OK &&
+                         pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, g_linear.data(), od.colorspace) == PT_OK &&
+                         pt_write_png((name + ".png").c_str(), rd.width, rd.height, g_rgba.data(), od.colorspace) == PT_OK;
+                    if (ok) printf("wrote %s.exr and %s.png (relit from %u light groups)\n", name.c_str(), name.c_str(), gd.group_count);
+                }
+                if (!ok) { fprintf(stderr, "--light-groups: %s\n", pt_last_error()); rc = 1; break; }
+            }
             // the bins in the units of the EXR payload: the same factor, applied here in place, one multiply per value
             const uint32_t file_bins = o.spectral_bins ? o.spectral_bins : o.denoise_bins;
             const auto write_spectral = [&](const std::string& name, std::vector<float>& scaled) {

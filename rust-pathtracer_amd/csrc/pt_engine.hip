@@ -28,7 +28,9 @@
 #include "../../include/pt_api.h"
 #include "../../include/pt_debug.h"
 #include "../../include/pt_denoise.h"
+#include "../../include/pt_light_groups.h"
 #include "pt_adaptive_select.h"
+#include "pt_light_groups_launch.h"
 #include "pt_spectral_launch.h"
 #include "pt_spectral_rules.h"
 #include "pt_spectral_project_launch.h"
@@ -256,6 +258,7 @@ constexpr uint32_t kUnitCounters = 2 * 64 + 2;   // two parked launches per boun
 #endif
 struct DeviceBuffers {
     uint32_t capacity = 0, light_samples = 0, nl = 0, park_block = 0;
+    uint32_t energy_planes = 0;   // planes of `energy`: nl + 1, or a light-group render's 2 + G (pt_light_group_rules.h)
     uint32_t *paths_a = nullptr, *paths_b = nullptr, *hits = nullptr, *shadow = nullptr, *pixels = nullptr, *counts = nullptr, *park = nullptr;
     uint32_t* unit_counters = nullptr;   // parked kernels with dynamic units: one counter per launch of a pass (kUnitCounters), zeroed per pass
     float* energy = nullptr;
@@ -359,6 +362,12 @@ struct pt_scene {
     std::vector<pt_scene*> spectral_shards;
     std::vector<uint32_t> shard_px;
     GrowBuf shard_packed;
+    // The resident group films (include/pt_light_groups.h): what the last successful light-group render left in group_films_cache, group-major float4 films.  Cleared
+    // when a group render starts and set when it has succeeded; pt_render_light_groups is the only writer of the buffer.  group_table: that render's one byte per
+    // instance; group_mix_cache: pt_light_groups_mix_resident's device matrices (PT_LIGHT_GROUPS_MAX x 9 floats) and, behind them, its output film.
+    bool groups_valid = false;
+    uint32_t groups_width = 0, groups_height = 0, groups_count = 0;
+    GrowBuf group_films_cache, group_table, group_mix_cache;
     ResidentSet resident;          // include/pt_resident.h
     GrowBuf assemble_staging, assemble_px;   // pt_resident_assemble's: the packed shards copied from other devices, and the pixel lists uploaded for the unpack
     GrowBuf project_cache;         // pt_spectral_project_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x PT_SPECTRAL_MAX_BINS floats) and, behind it, its output planes
@@ -392,9 +401,12 @@ uint32_t segment_capacity(uint32_t n, int grid) {
 
 // `b`: the scene's first set or its second (n_pixels 0: no pixel list of its own).  need_hits: the plan is not fused (a fused plan never touches the hit queue,
 // 5.9 GB at 128 Mi slots: it is made by the first render that needs it).
-pt_status ensure_buffers(pt_scene* sc, DeviceBuffers& b, uint32_t capacity, uint32_t light_samples, size_t n_pixels, int grid, uint32_t nl, uint32_t park_block, bool need_hits) {
+// group_count: the light groups of the render (0: none) — their energy planes lie behind the total and the wavelength samples.
+pt_status ensure_buffers(pt_scene* sc, DeviceBuffers& b, uint32_t capacity, uint32_t light_samples, size_t n_pixels, int grid, uint32_t nl, uint32_t park_block, bool need_hits,
+                         uint32_t group_count) {
     uint32_t total = segment_capacity(capacity, grid) * (uint32_t)grid;
-    if (b.capacity < total || b.light_samples < light_samples || b.grid != grid || b.nl < nl || b.park_block < park_block) {
+    const uint32_t planes_wanted = group_count ? lg_planes(group_count) : nl + 1u;
+    if (b.capacity < total || b.light_samples < light_samples || b.grid != grid || b.nl < nl || b.park_block < park_block || b.energy_planes < planes_wanted) {
         hipFree(b.paths_a); hipFree(b.paths_b); hipFree(b.hits); hipFree(b.shadow); hipFree(b.energy); hipFree(b.counts); hipFree(b.block_stats); hipFree(b.park);
         b.paths_a = b.paths_b = b.hits = b.shadow = b.counts = b.park = nullptr; b.energy = nullptr; b.block_stats = nullptr; b.capacity = 0;
         uint32_t ls = light_samples > b.light_samples ? light_samples : b.light_samples;
@@ -404,8 +416,10 @@ pt_status ensure_buffers(pt_scene* sc, DeviceBuffers& b, uint32_t capacity, uint
         HIP_TRY(hipMalloc(&b.paths_a, sizeof(uint32_t) * path_fields * total));
         HIP_TRY(hipMalloc(&b.paths_b, sizeof(uint32_t) * path_fields * total));
         HIP_TRY(hipMalloc(&b.shadow, sizeof(uint32_t) * sh_fields * total));
-        HIP_TRY(hipMalloc(&b.energy, sizeof(float) * (size_t)(nlmax + 1u) * total));   // (+ the plane of wavelength samples, PT_STORED_WAVELENGTH)
-        b.nl = nlmax;
+        uint32_t planes = nlmax + 1u;   // (+ the plane of wavelength samples, PT_STORED_WAVELENGTH)
+        for (uint32_t want : {b.energy_planes, planes_wanted}) if (want > planes) planes = want;
+        HIP_TRY(hipMalloc(&b.energy, sizeof(float) * (size_t)planes * total));
+        b.nl = nlmax; b.energy_planes = planes;
         HIP_TRY(hipMalloc(&b.counts, sizeof(uint32_t) * 4 * (size_t)grid));   // (live paths x 2, light-sample items, live light-sample items)
         HIP_TRY(hipMalloc(&b.block_stats, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid));
         // (the parked kernels' scratch: scenes whose sweep table holds walked meshes, and every scene without a sweep table — with or without a mesh: the parked
@@ -571,6 +585,10 @@ struct RenderJob {
     // the spectral node entries: the desc's shard as pth::shard_pixels lists it, computed by the caller, who packs the bins by it afterwards — the device copy of it
     // is then left in the scene's buf.pixels whichever kind of render this is
     const std::vector<uint32_t>* shard_list = nullptr;
+    // pt_render_light_groups (its arguments checked; include/pt_light_groups.h): the group table, its bytes in device memory, and group_count films of width * height
+    // float4 — the render takes the general vertex and light-sample forms that route energy to the groups' planes, and every pass adds each plane to its film
+    const LightGroupTable* groups = nullptr;
+    float* d_group_films = nullptr;
 };
 
 // What plan_render chooses for a render: the queues' size, the kernel forms and their launch configuration.
@@ -619,9 +637,10 @@ pt_status plan_render(const pt_scene* sc, const pt_render_desc& rd, const Render
     // the sweep table holds walked meshes: rays that reach one are parked and resumed in full waves (PT_AMD_NO_PARK=1: in line)
     const bool walks = (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_SWEEP_WALKS) != 0;
     const bool mesh_lights = sc->host.blob[PT_HDR_LIGHT_FACE_OFF] != 0u;   // (emissive mesh faces: PT_FORM_ANY, below)
-    const bool parked = sweep && walks && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights;
+    const bool grouped = job.groups != nullptr;   // (a light-group render: PT_FORM_ANY and the FULL vertex form, whose siblings route the energy: pt_kern_groups.hip)
+    const bool parked = sweep && walks && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights && !grouped;
     // no sweep table (more than 64 instances, PT_AMD_NO_SWEEP): the top-level tree per lane, every mesh parked (top_walk_run, pt_device.h)
-    const bool parked_walk = !sweep && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights;
+    const bool parked_walk = !sweep && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights && !grouped;
     // PT_AMD_POOL=1: phase 3 of a pure sweep scene pooled per wave (sweep_run_pooled).  Bit-identical, but measured slower than the lane
     // loop on MI355X (C2: k_extend 3155 vs 2475 us, k_shadow 5421 vs 4677 us; DESIGN.md section 5 has the breakdown), so it is not the default.
 #ifdef PT_EXPERIMENTS
@@ -631,7 +650,7 @@ pt_status plan_render(const pt_scene* sc, const pt_render_desc& rd, const Render
 #endif
     // (walked meshes in line under PT_AMD_NO_PARK, and every partly staged or unstaged blob: the run-time choice of PT_FORM_ANY.  A scene with emissive mesh faces
     // takes it too: the specialised traversal forms are compiled without the faces' code — PT_SCENE_NO_MESH_LIGHTS, pt_kern_*.hip — and keep their registers)
-    const int trav_form = parked ? PT_FORM_PARKED : parked_walk ? PT_FORM_PARKED_WALK : (mode != PT_LDS_ALL || (sweep && walks) || mesh_lights) ? PT_FORM_ANY : pooled ? PT_FORM_POOLED : sweep ? PT_FORM_SWEEP : PT_FORM_WALK;
+    const int trav_form = parked ? PT_FORM_PARKED : parked_walk ? PT_FORM_PARKED_WALK : (mode != PT_LDS_ALL || (sweep && walks) || mesh_lights || grouped) ? PT_FORM_ANY : pooled ? PT_FORM_POOLED : sweep ? PT_FORM_SWEEP : PT_FORM_WALK;
     // The parked kernels take units of work from a counter, a few persistent workgroups per CU, when the whole blob is staged in LDS
     // (C3: k_extend 9175 -> 7880 us, k_shadow 8008 -> 7105, 487 -> 543 Msamples/s: park lists that live across units keep the drains
     // full).  With the mesh in HBM/L2 (C4) the static form wins, 1128 vs 1083 Msamples/s: a wave's parked rays then come from one
@@ -678,7 +697,7 @@ pt_status plan_render(const pt_scene* sc, const pt_render_desc& rd, const Render
     // (a scene with a convex-body certificate takes at least the NO_ENV form: the lean and fused forms are compiled without the certificate code, pt_kern_shade.hip)
     const bool certs = !rd.medium_aware && (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_CONVEX) != 0u;
     const int shade_form = rd.medium_aware ? PT_SHADE_MEDIUM
-                         : (env_prob != 0.0f || tn.shade_form == 2) ? PT_SHADE_FULL : (has_ggx || certs || tn.shade_form == 1) ? PT_SHADE_NO_ENV : PT_SHADE_LEAN;
+                         : (env_prob != 0.0f || tn.shade_form == 2 || grouped) ? PT_SHADE_FULL : (has_ggx || certs || tn.shade_form == 1) ? PT_SHADE_NO_ENV : PT_SHADE_LEAN;
     cfg.certs = certs;
     // (the plain light-sample kernel walks the list of live items; the parked forms list their live RAYS themselves, the measurement forms read every item)
     uint32_t live_list = ((trav_form == PT_FORM_SWEEP || trav_form == PT_FORM_WALK || trav_form == PT_FORM_ANY) && shade_form == PT_SHADE_LEAN && !(tn.flags & PT_TUNE_NO_LIVE_LIST)) ? 1u : 0u;
@@ -754,7 +773,8 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
 #else
     const bool need_hits = !cfg.fuse;
 #endif
-    st = ensure_buffers(sc, sc->buf, capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits);
+    const uint32_t group_count = job.groups ? job.groups->group_count : 0u;
+    st = ensure_buffers(sc, sc->buf, capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits, group_count);
     if (st != PT_OK) return st;
     DeviceBuffers& b = sc->buf;
     // Pass overlap: a render whose pass loop plans two passes or more (an adaptive one: in its first round or in a later round over every pixel) gets the second
@@ -767,7 +787,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                || (adaptive && adaptive->max_samples > rd.spp && pth::plan_passes(n_px, rd.spp, adaptive->step < adaptive->max_samples - rd.spp ? adaptive->step : adaptive->max_samples - rd.spp, capacity, rd.phase_samples).size() >= 2);
     }
     if (overlap) {
-        bool ok = ensure_buffers(sc, sc->buf2, capacity, rd.light_samples, 0, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits) == PT_OK;
+        bool ok = ensure_buffers(sc, sc->buf2, capacity, rd.light_samples, 0, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits, group_count) == PT_OK;
         if (ok && !sc->pass_stream) ok = hipStreamCreateWithFlags(&sc->pass_stream, hipStreamNonBlocking) == hipSuccess;
         while (ok && sc->pass_deps.size() < DEP_COUNT) {
             hipEvent_t e;
@@ -790,6 +810,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     } else if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(b.pixels, pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(d_film, 0, sizeof(float) * 4 * (size_t)rd.width * rd.height, stream));
     if (job.d_spectral) HIP_TRY(hipMemsetAsync(job.d_spectral, 0, sizeof(float) * (size_t)job.spectral_bins * rd.width * rd.height, stream));
+    if (job.groups) HIP_TRY(hipMemsetAsync(job.d_group_films, 0, sizeof(float) * 4 * (size_t)group_count * rd.width * rd.height, stream));
     HIP_TRY(hipMemsetAsync(b.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));
     if (overlap) HIP_TRY(hipMemsetAsync(sc->buf2.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));   // (in front of the fork event)
 
@@ -850,7 +871,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     };
 
     uint64_t camera_rays = 0, accumulated_pixels = 0;
-    hipError_t spectral_error = hipSuccess;
+    hipError_t spectral_error = hipSuccess, groups_error = hipSuccess;
     bool overlapped = false;   // some pass loop of this render ran passes on both lanes
     const std::vector<hipEvent_t>& dep = sc->pass_deps;
     const uint32_t skew_code = (tn.flags >> PT_TUNE_PASS_SKEW_SHIFT) & PT_TUNE_PASS_SKEW_MASK;
@@ -887,6 +908,10 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
             if (step.wait_fork) HIP_TRY(hipStreamWaitEvent(stream, dep[DEP_FORK], 0));
             if (step.start_after >= 0) HIP_TRY(hipStreamWaitEvent(stream, dep[DEP_SKEW + (step.start_after & 1)], 0));
             if (step.wait_fork || step.start_after >= 0) mark(l, -1);
+            if (job.groups) {   // (the groups' planes, on the pass's own stream: behind the accumulate stage of the pass that used this set before, in front of this pass's vertices)
+                HIP_TRY(hipMemsetAsync(b.energy + (size_t)lg_plane(0) * b.capacity, 0, sizeof(float) * (size_t)group_count * b.capacity, stream));
+                mark(l, -1);
+            }
             if (park_dynamic) {
                 HIP_TRY(hipMemsetAsync(b.unit_counters, 0, sizeof(uint32_t) * kUnitCounters, stream));
                 // (round-5 advisor) an event of its own behind the stream's non-kernel work, charged to no stage: k_generate's time begins here, not at the end of the previous pass
@@ -906,9 +931,14 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                 cfg.path_marks = (bounce > 0 && !rd.medium_aware && (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_CONVEX)) ? sc->host.blob[PT_HDR_CONVEX_INST] : 0u;
                 if (!cfg.fuse) timed(l, ST_EXTEND, [&] { launch_extend(cfg, trav_form, sargs, qin, qh, seg_cap, cin, b.park); });
                 if (park_dynamic) cfg.unit_counter = b.unit_counters + 2 * bounce + 1;
-                timed(l, ST_SHADE, [&] { launch_shade(cfg, hero ? 4 : 1, shade_form, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats); });
-                if (rd.light_samples > 0)   // (shade_form FULL = the scene can produce environment rays)
-                    timed(l, ST_SHADOW, [&] { launch_shadow(cfg, trav_form, hero ? 4 : 1, shade_form == PT_SHADE_FULL || shade_form == PT_SHADE_MEDIUM, sargs, rd.light_samples, qs, b.energy, b.capacity, rp.live_list ? (seg_cap | kShadowListed) : seg_cap, nshadow, b.park, qh); });
+                if (job.groups) {
+                    timed(l, ST_SHADE, [&] { launch_shade_groups(cfg, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats, *job.groups); });
+                    if (rd.light_samples > 0) timed(l, ST_SHADOW, [&] { launch_shadow_groups(cfg, sargs, rd.light_samples, qs, b.energy, b.capacity, seg_cap, nshadow, *job.groups); });
+                } else {
+                    timed(l, ST_SHADE, [&] { launch_shade(cfg, hero ? 4 : 1, shade_form, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats); });
+                    if (rd.light_samples > 0)   // (shade_form FULL = the scene can produce environment rays)
+                        timed(l, ST_SHADOW, [&] { launch_shadow(cfg, trav_form, hero ? 4 : 1, shade_form == PT_SHADE_FULL || shade_form == PT_SHADE_MEDIUM, sargs, rd.light_samples, qs, b.energy, b.capacity, rp.live_list ? (seg_cap | kShadowListed) : seg_cap, nshadow, b.park, qh); });
+                }
                 // (the next pass starts behind this bounce: started together the two would run in lock step, tail on tail)
                 if ((int32_t)bounce == step.signal_bounce) HIP_TRY(hipEventRecord(dep[DEP_SKEW + (p & 1)], stream));
             }
@@ -922,7 +952,10 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                 // (the energy planes stay valid until the next pass's k_generate overwrites them)
                 if (job.d_spectral && spectral_error == hipSuccess)
                     spectral_error = ptk::launch_accumulate_spectral(hero ? 4 : 1, grid, stream, rp, d_px, b.energy, job.d_spectral, job.spectral_bins, rd.width * rd.height);
+                if (job.groups && groups_error == hipSuccess)
+                    groups_error = ptk::launch_accumulate_groups(stream, rp, d_px, b.energy, job.d_group_films, group_count, (size_t)rd.width * rd.height);
             });
+            if (groups_error != hipSuccess) return fail(PT_ERR_DEVICE, std::string("k_accumulate_groups: ") + hipGetErrorString(groups_error));
             if (spectral_error != hipSuccess) return fail(PT_ERR_DEVICE, std::string("k_accumulate_spectral: ") + hipGetErrorString(spectral_error));
             if (two_lanes) HIP_TRY(hipEventRecord(dep[DEP_ACCUMULATED + (p & 1)], stream));
         }
@@ -1044,6 +1077,7 @@ static pt_status scene_to_device(pt_scene* sc) {
         if (e == hipSuccess) e = allow_lds_shade(kLdsBlobLimitBytes > PT_SHADE_LDS_BUDGET ? kLdsBlobLimitBytes : PT_SHADE_LDS_BUDGET);   // (the FULL form's marginal tables ride behind the blob only within PT_SHADE_LDS_BUDGET)
         // (the parked light-sample kernels keep their waves' lists of live rays behind the blob: up to 16 waves x (64 L + 64) words)
         if (e == hipSuccess) e = allow_lds_shadow(kParkBlobLimitBytes + 16u * (64u * PT_MAX_LIGHT_SAMPLES + 64u) * 4u);
+        if (e == hipSuccess) e = allow_lds_groups(kLdsBlobLimitBytes > PT_SHADE_LDS_BUDGET ? kLdsBlobLimitBytes : PT_SHADE_LDS_BUDGET, kLdsBlobLimitBytes);
         if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(e));
     }
     return PT_OK;
@@ -1139,22 +1173,33 @@ struct RenderCall {
     uint32_t* sample_counts = nullptr;      // the adaptive entries; stats: where the caller wants them
     double* stats = nullptr;
     float* spectral = nullptr;              // the spectral entries
+    const pt_light_groups_desc* gd = nullptr;   // pt_render_light_groups; group_films: where the caller wants them (may be null)
+    float* group_films = nullptr;
 };
 
-// The body of the four one-device entries: the device, the film and the planes kept with the scene, render_impl on the null stream, the read-backs and the resident
-// spectral film.  profile->seconds: render_impl's window for the fixed entries; for the adaptive ones the whole call.
+// The body of the five one-device entries: the device, the film and the planes kept with the scene, render_impl on the null stream, the read-backs and the resident
+// spectral film and group films.  profile->seconds: render_impl's window for the fixed entries; for the adaptive ones the whole call.
 static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* profile) {
     const pt_render_desc& rd = *call.rd;
     forget_node_render(sc);
     if (call.sd) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts: whatever the buffer held is no film from here on)
+    if (call.gd) sc->groups_valid = false;   // (likewise the group films)
     sc->resident.end();   // (film_cache and the adaptive buffers are written from here on; guides and denoised outputs belonged to the film before)
     HIP_TRY(hipSetDevice(sc->device));
     const size_t n_pixels = (size_t)rd.width * rd.height, film_bytes = sizeof(float) * 4 * n_pixels, spectral_bytes = call.sd ? sizeof(float) * call.sd->bins * n_pixels : 0;
     pt_status st = sc->film_cache.reserve(film_bytes);
     if (st == PT_OK && call.sd) st = sc->spectral_cache.reserve(spectral_bytes);
+    const size_t group_bytes = call.gd ? film_bytes * call.gd->group_count : 0;
+    if (st == PT_OK && call.gd) st = sc->group_films_cache.reserve(group_bytes);
+    if (st == PT_OK && call.gd) st = sc->group_table.reserve(call.gd->instance_count ? call.gd->instance_count : 1u);
     if (st != PT_OK) return st;
     RenderJob job;
     job.adaptive = call.ad;
+    LightGroupTable table{sc->group_table.as<uint8_t>(), call.gd ? call.gd->environment_group : 0u, call.gd ? call.gd->group_count : 0u};
+    if (call.gd) {
+        if (call.gd->instance_count) HIP_TRY(hipMemcpy(sc->group_table.p, call.gd->instance_group, call.gd->instance_count, hipMemcpyHostToDevice));
+        job.groups = &table; job.d_group_films = sc->group_films_cache.as<float>();
+    }
     if (call.sd) { job.d_spectral = sc->spectral_cache.as<float>(); job.spectral_bins = call.sd->bins; }
     const hipStream_t stream = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1166,6 +1211,8 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
         if (call.stats) HIP_TRY(hipMemcpy(call.stats, sc->adaptive.stats, sizeof(double) * 2 * n_pixels, hipMemcpyDeviceToHost));
     }
     if (call.sd) HIP_TRY(hipMemcpy(call.spectral, sc->spectral_cache.p, spectral_bytes, hipMemcpyDeviceToHost));
+    if (call.gd && call.group_films) HIP_TRY(hipMemcpy(call.group_films, sc->group_films_cache.p, group_bytes, hipMemcpyDeviceToHost));
+    if (call.gd) { sc->groups_width = rd.width; sc->groups_height = rd.height; sc->groups_count = call.gd->group_count; sc->groups_valid = true; }
     if (call.ad && profile) profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (the whole call: set-up, rounds, read-backs)
     if (call.sd) { sc->spectral_width = rd.width; sc->spectral_height = rd.height; sc->spectral_bins = call.sd->bins; sc->spectral_valid = true; }
     if (call.ad) {   // the resident set of include/pt_resident.h: film, counts and statistics, and the bins of a spectral render
@@ -1222,6 +1269,46 @@ pt_status pt_render_adaptive_spectral(pt_scene* sc, const pt_render_desc* rdp, c
     RenderCall call;
     call.rd = &rd; call.ad = &ad; call.sd = sdp; call.film = film; call.sample_counts = sample_counts; call.stats = stats; call.spectral = spectral;
     return render_one(sc, call, profile);
+}
+
+pt_status pt_render_light_groups(pt_scene* sc, const pt_render_desc* rdp, const pt_light_groups_desc* gdp, float* film, float* group_films, pt_profile* profile) {
+    forget_node_render(sc);
+    std::string err;
+    const pt_status st = pth::check_light_groups_args(sc, rdp, gdp, sc ? sc->host.blob[PT_HDR_INSTANCE_COUNT] : 0u, film, &err);
+    if (st != PT_OK) return fail(st, err);
+    if (rdp->width == 0 || rdp->height == 0 || (uint64_t)rdp->width * rdp->height > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and width x height must fit 31 bits");
+    RenderCall call;
+    call.rd = rdp; call.gd = gdp; call.film = film; call.group_films = group_films;
+    return render_one(sc, call, profile);
+}
+
+pt_status pt_light_groups_resident(pt_scene* sc, uint32_t* width, uint32_t* height, uint32_t* group_count) {
+    if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
+    if (!width || !height || !group_count) return fail(PT_ERR_INVALID_ARGUMENT, "width, height or group_count is null");
+    *width = sc->groups_valid ? sc->groups_width : 0u; *height = sc->groups_valid ? sc->groups_height : 0u; *group_count = sc->groups_valid ? sc->groups_count : 0u;
+    return PT_OK;
+}
+
+// include/pt_light_groups.h: pt_light_groups_mix's kernel over group_films_cache, on the stream the render ran on (the null stream), so the group films never cross the bus.
+pt_status pt_light_groups_mix_resident(pt_scene* sc, const float* matrices, float* out) {
+    if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
+    if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "out_xyzw is null");
+    if (!sc->groups_valid) return fail(PT_ERR_INVALID_ARGUMENT, "the scene has no resident group films: pt_render_light_groups must have succeeded on it");
+    std::string err;
+    const pt_status st = pth::check_light_groups_matrices(sc->groups_count, matrices, &err);
+    if (st != PT_OK) return fail(st, err);
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t n_pixels = (size_t)sc->groups_width * sc->groups_height, matrix_floats = (size_t)PT_LIGHT_GROUPS_MAX * 12;   // (the film behind them stays 16-byte aligned)
+    const pt_status cached = sc->group_mix_cache.reserve(sizeof(float) * (matrix_floats + 4 * n_pixels));
+    if (cached != PT_OK) return cached;
+    float* d_matrices = sc->group_mix_cache.as<float>();
+    float* d_out = d_matrices + matrix_floats;
+    hipStream_t stream = nullptr;
+    HIP_TRY(hipMemcpyAsync(d_matrices, matrices, sizeof(float) * 9 * sc->groups_count, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ptk::launch_light_groups_mix(stream, (uint32_t)n_pixels, sc->groups_count, sc->group_films_cache.as<float>(), d_matrices, d_out));
+    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(float) * 4 * n_pixels, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PT_OK;
 }
 
 pt_status pt_spectral_resident(pt_scene* sc, uint32_t* width, uint32_t* height, uint32_t* bins) {

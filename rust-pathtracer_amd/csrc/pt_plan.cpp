@@ -459,4 +459,52 @@ pt_status check_response_matrix_args(const pt_render_desc* rd, const pt_spectral
     return PT_OK;
 }
 
+pt_status check_light_groups_args(const void* scene, const pt_render_desc* rd, const pt_light_groups_desc* gd, uint32_t scene_instances, const void* film,
+                                  std::string* error) {
+    if (!scene) { *error = "the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!rd) { *error = "the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!gd) { *error = "the light groups desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!film) { *error = "film_xyzw is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (gd->group_count == 0 || gd->group_count > PT_LIGHT_GROUPS_MAX) { *error = "group_count must be in 1..8"; return PT_ERR_INVALID_ARGUMENT; }
+    if (gd->reserved[0] != 0 || gd->reserved[1] != 0) { *error = "pt_light_groups_desc::reserved must be 0"; return PT_ERR_INVALID_ARGUMENT; }
+    if (gd->instance_count != scene_instances) {
+        *error = "instance_count is " + std::to_string(gd->instance_count) + ", the scene has " + std::to_string(scene_instances) + " instances";
+        return PT_ERR_INVALID_ARGUMENT;
+    }
+    if (gd->instance_count != 0 && !gd->instance_group) { *error = "instance_group is null"; return PT_ERR_INVALID_ARGUMENT; }
+    for (uint32_t i = 0; i < gd->instance_count; ++i)
+        if (gd->instance_group[i] >= gd->group_count) {
+            *error = "instance " + std::to_string(i) + " is in group " + std::to_string(gd->instance_group[i]) + ": group ids must be below group_count";
+            return PT_ERR_INVALID_ARGUMENT;
+        }
+    if (gd->environment_group >= gd->group_count) { *error = "environment_group must be below group_count"; return PT_ERR_INVALID_ARGUMENT; }
+    if (rd->hero_wavelengths == 4) { *error = "light groups carry one wavelength per path (hero_wavelengths 0 or 1)"; return PT_ERR_UNSUPPORTED; }
+    if (rd->medium_aware) { *error = "light groups are not rendered by the medium-aware walk"; return PT_ERR_UNSUPPORTED; }
+    if (rd->shard_count > 1) { *error = "light groups render the whole film (shard_count 0 or 1)"; return PT_ERR_UNSUPPORTED; }
+    if (rd->first_sample != 0 || (rd->sample_count != 0 && rd->sample_count != rd->spp)) {
+        *error = "light groups render the whole sample range (first_sample 0, sample_count 0 or spp)";
+        return PT_ERR_UNSUPPORTED;
+    }
+    return PT_OK;
+}
+
+pt_status check_light_groups_matrices(uint32_t group_count, const float* matrices, std::string* error) {
+    if (group_count == 0 || group_count > PT_LIGHT_GROUPS_MAX) { *error = "group_count must be in 1..8"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!matrices) { *error = "the matrices are null"; return PT_ERR_INVALID_ARGUMENT; }
+    for (uint32_t i = 0; i < 9u * group_count; ++i)
+        if (!std::isfinite(matrices[i])) { *error = "matrix entry " + std::to_string(i) + " is not finite"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
+pt_status check_light_groups_mix_args(uint32_t width, uint32_t height, uint32_t group_count, const void* group_films, const float* matrices, const void* out,
+                                      std::string* error) {
+    if (!group_films) { *error = "the group films are null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!out) { *error = "out_xyzw is null"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = check_light_groups_matrices(group_count, matrices, error);
+    if (st != PT_OK) return st;
+    if (width == 0 || height == 0) { *error = "width and height must be positive"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((uint64_t)width * (uint64_t)height > 0x7fffffffull) { *error = "width x height must fit 31 bits"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
 }  // namespace pth

@@ -10,6 +10,7 @@
 #include "../../include/pt_adaptive.h"
 #include "../../include/pt_api.h"
 #include "../../include/pt_denoise.h"
+#include "../../include/pt_light_groups.h"
 #include "../../include/pt_resident.h"
 #include "../../include/pt_spectral.h"
 #include "pt_stages.h"
@@ -142,6 +143,18 @@ pt_status check_resident_assemble(const void* scene, uint32_t flags, const NodeR
 // pt_resident_read: a pointer that is given names a part that is resident (film_xyzw, sample_counts and stats: FILM; spectral: BINS)
 pt_status check_resident_read_args(const void* scene, const void* film, const void* sample_counts, const void* stats, const void* spectral, const struct pt_resident_info& now,
                                    std::string* error);
+
+// ---- include/pt_light_groups.h, for the engine and the host emulation alike; every check runs before a device is looked for.
+// pt_render_light_groups: no null pointer (group_films may be null); group_count in 1..PT_LIGHT_GROUPS_MAX, reserved words 0, instance_count the scene's
+// (`scene_instances`), every group id and the environment's below group_count: PT_ERR_INVALID_ARGUMENT.  hero_wavelengths 4, medium_aware, a shard
+// (shard_count > 1) and a partial sample range: PT_ERR_UNSUPPORTED.  Everything else about the render desc is normalize_render_desc's to judge.
+pt_status check_light_groups_args(const void* scene, const pt_render_desc* rd, const pt_light_groups_desc* gd, uint32_t scene_instances, const void* film,
+                                  std::string* error);
+// the matrices of a mix: the pointer, group_count in 1..PT_LIGHT_GROUPS_MAX, every entry finite
+pt_status check_light_groups_matrices(uint32_t group_count, const float* matrices, std::string* error);
+// pt_light_groups_mix: no null pointer, check_light_groups_matrices, width and height positive and width x height within 31 bits
+pt_status check_light_groups_mix_args(uint32_t width, uint32_t height, uint32_t group_count, const void* group_films, const float* matrices, const void* out,
+                                      std::string* error);
 
 }  // namespace pth
 #endif

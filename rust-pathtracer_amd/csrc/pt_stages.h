@@ -743,8 +743,10 @@ PT_HD void stage_shadow_item(const SceneView& s, uint32_t light_samples, const Q
 // XYZColor::from(SingleWavelength) (math crate; pt.rs:614) and the film sums of tiled.rs:366-398.  With hero wavelengths
 // the sample's colour is the mean of the four wavelengths' XYZ.  STATS (adaptive sampling, include/pt_adaptive.h): the same pass also adds each
 // sample's Y term y — the value the film's Y sum adds — to the pixel's S1 += y and S2 += y * y, in f64 and in sample order (stats_px = S1, S2).
+// `wavelengths`: the plane of stored wavelength samples where it does not lie behind `energy`'s NL planes (a light group's plane, pt_light_group_rules.h).
 template <int NL, bool STATS = false>
-PT_HD void stage_accumulate_pixel(const RenderParams& rp, const float* energy, uint32_t p, uint32_t pixel, float* film_px, double* stats_px = nullptr) {
+PT_HD void stage_accumulate_pixel(const RenderParams& rp, const float* energy, uint32_t p, uint32_t pixel, float* film_px, double* stats_px = nullptr,
+                                  const float* wavelengths = nullptr) {
     float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
     float f0 = film_px[0], f1 = film_px[1], f2 = film_px[2];
     double s1 = 0.0, s2 = 0.0;
@@ -755,7 +757,7 @@ PT_HD void stage_accumulate_pixel(const RenderParams& rp, const float* energy, u
         // (round 5) the sample's wavelength sample u as k_generate left it in the plane behind the energies (PT_STORED_WAVELENGTH) — not the film block's Philox draw again,
         // which was 40 % of this loop; hero_lambdas(u)[0] is stage_generate's own expression for the wavelength
         float lam[NL];
-        if (PT_STORED_WAVELENGTH) hero_lambdas<NL>(rp, energy[(size_t)NL * rp.energy_stride + slot], lam);
+        if (PT_STORED_WAVELENGTH) hero_lambdas<NL>(rp, wavelengths ? wavelengths[slot] : energy[(size_t)NL * rp.energy_stride + slot], lam);
         else hero_lambdas<NL>(rp, pt_draw4(rp.seed, pixel, sample, PT_DIM_FILM).z, lam);
         if (NL == 1) {
             float e = energy[slot];

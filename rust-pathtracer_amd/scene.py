@@ -682,6 +682,33 @@ def mixed_small():
     return b
 
 
+def light_groups_room(emit=(True, True, True)):
+    """The scene of the light-group tests (not a reference scene): mixed_small's floor, wall and two spheres with three emitters of three
+    kinds, each with a material of its own — instance 1 a DiffuseLight rect (E5), instance 2 a SharpLight disk (xenon_x5, sharpness 100) — and a constant
+    sky that light samples pick with probability 0.25.  emit[k] False replaces emitter k's emission CURVE (rect, disk, sky) by flat_zero: nothing leaves the
+    scene, no strength changes, and the walk — which never looks at an emission value — is the same."""
+    b = SceneBuilder()
+    add_library_curves(b, ["simple_sky_blue", "flat_zero", "E5", "xenon_x5", "flat_78"])
+    zero = b.curve("flat_zero")
+    b.set_environment_constant(b.curve("simple_sky_blue") if emit[2] else zero, 0.3)
+    b.env_sampling_probability = 0.25
+    l0 = b.material_diffuse_light("light_groups_l0", b.curve("E5") if emit[0] else zero, b.curve("flat_78"), api.SIDED_DUAL)
+    l1 = b.material_sharp_light("light_groups_l1", b.curve("xenon_x5") if emit[1] else zero, b.curve("flat_78"), 100.0, api.SIDED_DUAL)
+    white = add_library_material(b, "lambertian_white")
+    red = add_library_material(b, "lambertian_red")
+    gold = add_library_material(b, "ggx_gold")
+    glass = add_library_material(b, "ggx_glass_rough")
+    b.add_rect((6, 6), (0.0, 0.0, -1.0), "Z", True, white)
+    b.add_rect((1.0, 1.0), (0.0, 0.0, 2.5), "Z", True, l0)
+    b.add_disk(0.7, (0.0, 0.0, 0.0), True, l1,
+               transform_from_data(rotate=[((0, 1, 0), 70.0)], translate=(2.0, 1.5, 1.0)))
+    b.add_sphere(0.6, (0.0, -1.2, -0.4), gold)
+    b.add_sphere(0.5, (0.0, 0.0, 0.0), glass, transform_from_data(scale=(1.0, 1.4, 0.8), translate=(0.3, 1.1, -0.3)))
+    b.add_rect((2.0, 3.0), (0.0, 2.5, 0.5), "Y", True, red)
+    b.add_camera((-5.0, 0.3, 0.8), (0.0, 0.0, 0.0), 35.0, focal_distance=5.0, aperture_diameter=0.05)
+    return b
+
+
 def big_sphere_light():
     """A sphere light of radius 20 000 hanging 0.02 above a floor (not a reference scene): from the floor under it a light sample's hit
     distance is 0.02 .. 1 while the terms of the sphere's quadratic are ~4e8 (|oc|^2 - r^2) and ~2e4 (-b, the root), so the computed

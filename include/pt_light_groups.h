@@ -17,7 +17,9 @@
  *
  * The mix (the relight): with M[g] a row-major 3 x 3 per group, all f32, no contraction,
  *   out_c(p) = fold over g ascending of acc = acc + ((M[g][c][0] * X_g(p) + M[g][c][1] * Y_g(p)) + M[g][c][2] * Z_g(p)), from acc = 0.0f;   out_w = 0.
- * A scaled identity is a group's intensity, a diagonal its tint, a full matrix a white balance of its own, zero switches it off. */
+ * A scaled identity is a group's intensity, a diagonal its tint, a full matrix a white balance of its own, zero switches it off.
+ *
+ * The adaptive group render and the joint filter over group films are pt_light_groups_denoise.h's. */
 #ifndef PT_LIGHT_GROUPS_H
 #define PT_LIGHT_GROUPS_H
 #include "pt_api.h"

@@ -5,6 +5,7 @@
 //   ptcli [--config data/config.toml] [--scene FILE] [-n|--dry-run] [--stdout-log-level L] [--write-log-level L]
 //         [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--adaptive REL] [--devices MASK] [--denoise] [--guide-samples K] [--demodulate-albedo]
 //         [--guide-chain D] [--guide-alpha-max A] [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]
+//         [--denoise-light-groups instance|material]
 //         [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK] [--denoise-resident]
 //         [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]
 //
@@ -58,6 +59,13 @@
 // are: the film is the total.  --light-gains G0,G1,... (with --light-groups only, one gain per group) also writes <filename>_relit.exr / .png: the group films
 // times their gains, mixed where the render left them on the device (pt_light_groups_mix_resident).  Refused together with --adaptive, --denoise, --spectral-bins,
 // --denoise-spectral-bins, --devices, --spectral-devices and --hero-wavelengths.
+// --denoise-light-groups instance|material (with --denoise only; groups formed as --light-groups forms them) renders every setting through
+// pt_render_adaptive_light_groups (include/pt_light_groups_denoise.h) and filters the film and its group films together where the render left them
+// (pt_resident_guides, pt_denoise_light_groups_resident), honouring --demodulate-albedo, --guide-chain and --guide-samples; --denoise-resident is accepted and
+// changes no file.  The usual files and <filename>_denoised.* are byte for byte those of --denoise with the same other flags; it also writes
+// <filename>_light<g>.exr and <filename>_denoised_light<g>.exr and, with --light-gains, <filename>_relit.* and <filename>_denoised_relit.*, the relights of the
+// noisy and of the denoised group films (pt_light_groups_mix_resident, pt_light_groups_mix_resident_denoised).  Refused together with --light-groups,
+// --spectral-bins, --denoise-spectral-bins, --devices, --spectral-devices, --denoise-assemble and --hero-wavelengths.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -70,6 +78,7 @@
 #include "../../../include/pt_adaptive.h"
 #include "../../../include/pt_denoise.h"
 #include "../../../include/pt_light_groups.h"
+#include "../../../include/pt_light_groups_denoise.h"
 #include "../../../include/pt_scene_file.h"
 #include "../../../include/pt_resident.h"
 #include "../../../include/pt_spectral.h"
@@ -104,6 +113,7 @@ struct Options {
     uint64_t spectral_device_mask = 0;
     int light_groups = 0;         // --light-groups: 1 = a group per emitting instance, 2 = per light material; 0 = off
     bool has_light_gains = false; // --light-gains: <filename>_relit.* from the resident mix
+    int denoise_groups = 0;       // --denoise-light-groups: the adaptive group render and the joint filter over the group films; 1 | 2 as light_groups, 0 = off
     std::vector<float> light_gains;
     bool assemble = false;        // --denoise-assemble: the node render assembled on the scene's device, then as `resident` (pt_resident_assemble)
 };
@@ -114,6 +124,7 @@ int usage(const char* msg) {
                     "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n"
                     "             [--denoise] [--guide-samples K] [--demodulate-albedo] [--guide-chain D] [--guide-alpha-max A]\n"
                     "             [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]\n"
+                    "             [--denoise-light-groups instance|material]\n"
                     "             [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK]\n"
                     "             [--denoise-resident] [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]\n");
     return 2;
@@ -242,6 +253,11 @@ int main(int argc, char** argv) {
             o.light_groups = v == "instance" ? 1 : v == "material" ? 2 : 0;
             if (!o.light_groups) return usage("--light-groups needs `instance` or `material`");
         }
+        else if (a == "--denoise-light-groups") {
+            if (!value(&v)) return usage("--denoise-light-groups needs a value");
+            o.denoise_groups = v == "instance" ? 1 : v == "material" ? 2 : 0;
+            if (!o.denoise_groups) return usage("--denoise-light-groups needs `instance` or `material`");
+        }
         else if (a == "--light-gains") {
             if (!value(&v)) return usage("--light-gains needs a value");
             o.has_light_gains = true;
@@ -261,7 +277,14 @@ int main(int argc, char** argv) {
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
     }
-    if (o.has_light_gains && !o.light_groups) return usage("--light-gains needs --light-groups");
+    if (o.denoise_groups) {
+        const char* with = o.light_groups ? "--light-groups" : o.spectral_bins ? "--spectral-bins" : o.denoise_bins ? "--denoise-spectral-bins" : o.multi ? "--devices"
+                         : o.spectral_multi ? "--spectral-devices" : o.assemble ? "--denoise-assemble" : o.hero ? "--hero-wavelengths" : nullptr;
+        static std::string refusal;
+        if (with) { refusal = std::string("--denoise-light-groups cannot be combined with ") + with + ": it is one adaptive group render of one wavelength per path on one device, and its filter"; return usage(refusal.c_str()); }
+        if (!o.denoise) return usage("--denoise-light-groups needs --denoise");
+    }
+    if (o.has_light_gains && !o.light_groups && !o.denoise_groups) return usage("--light-gains needs --light-groups");
     if (o.light_groups) {
         const char* with = o.adaptive >= 0.0f ? "--adaptive" : o.denoise ? "--denoise" : o.spectral_bins ? "--spectral-bins" : o.denoise_bins ? "--denoise-spectral-bins"
                          : o.multi ? "--devices" : o.spectral_multi ? "--spectral-devices" : o.hero ? "--hero-wavelengths" : nullptr;
@@ -342,7 +365,9 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> instance_group(desc->instance_count, 0);
     pt_light_groups_desc gd;
     memset(&gd, 0, sizeof(gd));
-    if (o.light_groups) {
+    const int group_mode = o.light_groups ? o.light_groups : o.denoise_groups;
+    const char* group_flag = o.light_groups ? "--light-groups" : "--denoise-light-groups";
+    if (group_mode) {
         std::vector<uint32_t> keys;   // a group's key: the instance (mode 1) or the packed light material (mode 2)
         uint32_t groups = 0;
         for (uint32_t i = 0; i < desc->instance_count; ++i) {
@@ -357,7 +382,7 @@ int main(int argc, char** argv) {
                 }
             }
             if (light == PT_MATERIAL_NONE) continue;
-            const uint32_t key = o.light_groups == 1 ? i : light;
+            const uint32_t key = group_mode == 1 ? i : light;
             uint32_t g = 0;
             while (g < keys.size() && keys[g] != key) ++g;
             if (g == keys.size()) keys.push_back(key);
@@ -371,13 +396,13 @@ int main(int argc, char** argv) {
         const char* why = groups > PT_LIGHT_GROUPS_MAX ? "the scene has more than 8 light groups"
                           : (o.has_light_gains && o.light_gains.size() != groups) ? "--light-gains needs one gain per group" : nullptr;
         if (why) {
-            fprintf(stderr, "error: --light-groups: %s (%u groups)\n", why, groups);
+            fprintf(stderr, "error: %s: %s (%u groups)\n", group_flag, why, groups);
             pt_scene_file_free(scene_file);
             pt_config_free(config);
             return 1;
         }
         gd.group_count = groups; gd.instance_count = desc->instance_count; gd.instance_group = instance_group.data();
-        printf("light groups: %u (%s%s)\n", groups, o.light_groups == 1 ? "one per emitting instance" : "one per light material", env_emits ? ", the environment last" : "");
+        printf("light groups: %u (%s%s)\n", groups, group_mode == 1 ? "one per emitting instance" : "one per light material", env_emits ? ", the environment last" : "");
     }
 
     // --denoise: what the adaptive path refuses is refused here, with its message, before anything is rendered or written
@@ -444,7 +469,10 @@ int main(int argc, char** argv) {
             std::vector<float> group_films;   // (--light-groups sizes it below)
             const pt_spectral_desc dsd = {o.denoise_bins, {0u, 0u, 0u}};
             const char* adaptive_entry = o.denoise_bins ? (o.spectral_multi ? "pt_render_adaptive_spectral_multi" : "pt_render_adaptive_spectral")
-                                         : o.multi      ? "pt_render_adaptive_multi" : "pt_render_adaptive";
+                                         : o.denoise_groups ? "pt_render_adaptive_light_groups" : o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive";
+            if (o.denoise_groups) group_films.resize((size_t)gd.group_count * rd.width * rd.height * 4);
+            // --denoise-light-groups: the adaptive group render — film, counts and statistics are pt_render_adaptive's bit for bit
+            const auto adaptive_groups = [&] { return pt_render_adaptive_light_groups(scene, &rd, &ad, &gd, film.data(), counts.data(), stats.data(), group_films.data(), &prof); };
             // --denoise-spectral-bins: the adaptive spectral render, on one device or (--spectral-devices) on the devices of the mask
             const auto adaptive_spectral = [&](double* st_out) {
                 return o.spectral_multi ? pt_render_adaptive_spectral_multi(scene, &rd, &ad, &dsd, o.spectral_device_mask, film.data(), counts.data(), st_out, spectral.data(), &prof)
@@ -456,6 +484,7 @@ int main(int argc, char** argv) {
                 printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
                 ad.max_samples = rd.spp; ad.rel_error = 0.0f;
                 const pt_status st = o.denoise_bins ? adaptive_spectral(stats.data())
+                                     : o.denoise_groups ? adaptive_groups()
                                      : o.multi      ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), stats.data(), &prof)
                                                     : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), stats.data(), &prof);
                 if (st != PT_OK) { fprintf(stderr, "%s: %s\n", adaptive_entry, pt_last_error()); rc = 1; break; }
@@ -463,6 +492,7 @@ int main(int argc, char** argv) {
                 printf("rendering %ux%u, %u..%u spp (adaptive, relative error %g), max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, ad.max_samples,
                        (double)ad.rel_error, rd.max_bounces, rd.light_samples);
                 const pt_status st = o.denoise_bins ? adaptive_spectral(stats.data())
+                                     : o.denoise_groups ? adaptive_groups()
                                      : o.multi      ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof)
                                                     : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof);
                 if (st != PT_OK) { fprintf(stderr, "%s: %s\n", adaptive_entry, pt_last_error()); rc = 1; break; }
@@ -504,28 +534,32 @@ int main(int argc, char** argv) {
             }
             if (o.write_film && !write_npy(base + ".npy", film.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", base.c_str()); rc = 1; break; }
             printf("wrote %s.exr and %s.png\n", base.c_str(), base.c_str());
-            // --light-groups: every group's film, and with --light-gains the resident mix, through this setting's film output (buffers of their own)
-            if (o.light_groups) {
+            // --light-groups, --denoise-light-groups: every group's film, and with --light-gains the resident mix, through this setting's film output (buffers of
+            // their own).  `stem`: base, or base + "_denoised" for the films of the joint filter, which are then mixed where that left them.
+            const auto write_groups = [&](const std::string& stem, const std::vector<float>& films, bool denoised) {
                 const size_t np = (size_t)rd.width * rd.height;
                 std::vector<float> g_linear(3 * np), relit(4 * np), matrices;
                 std::vector<uint8_t> g_rgba(4 * np);
                 bool ok = true;
                 for (uint32_t g = 0; ok && g < gd.group_count; ++g) {
-                    const std::string name = base + "_light" + std::to_string(g);
-                    ok = pt_output_film(&od, group_films.data() + 4 * np * g, g_rgba.data(), g_linear.data()) == PT_OK &&
+                    const std::string name = stem + "_light" + std::to_string(g);
+                    ok = pt_output_film(&od, films.data() + 4 * np * g, g_rgba.data(), g_linear.data()) == PT_OK &&
                          pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, g_linear.data(), od.colorspace) == PT_OK;
                     if (ok) printf("wrote %s.exr\n", name.c_str());
                 }
                 if (ok && o.has_light_gains) {
                     for (float gain : o.light_gains) for (int k = 0; k < 9; ++k) matrices.push_back(k % 4 == 0 ? gain : 0.0f);
-                    const std::string name = base + "_relit";
-                    ok = pt_light_groups_mix_resident(scene, matrices.data(), relit.data()) == PT_OK && pt_output_film(&od, relit.data(), g_rgba.data(), g_linear.data()) == PT_OK &&
+                    const std::string name = stem + "_relit";
+                    ok = (denoised ? pt_light_groups_mix_resident_denoised(scene, matrices.data(), relit.data()) : pt_light_groups_mix_resident(scene, matrices.data(), relit.data())) == PT_OK &&
+                         pt_output_film(&od, relit.data(), g_rgba.data(), g_linear.data()) == PT_OK &&
                          pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, g_linear.data(), od.colorspace) == PT_OK &&
                          pt_write_png((name + ".png").c_str(), rd.width, rd.height, g_rgba.data(), od.colorspace) == PT_OK;
                     if (ok) printf("wrote %s.exr and %s.png (relit from %u light groups)\n", name.c_str(), name.c_str(), gd.group_count);
                 }
-                if (!ok) { fprintf(stderr, "--light-groups: %s\n", pt_last_error()); rc = 1; break; }
-            }
+                if (!ok) fprintf(stderr, "%s: %s\n", group_flag, pt_last_error());
+                return ok;
+            };
+            if (group_mode && !write_groups(base, group_films, false)) { rc = 1; break; }
             // the bins in the units of the EXR payload: the same factor, applied here in place, one multiply per value
             const uint32_t file_bins = o.spectral_bins ? o.spectral_bins : o.denoise_bins;
             const auto write_spectral = [&](const std::string& name, std::vector<float>& scaled) {
@@ -578,7 +612,29 @@ int main(int argc, char** argv) {
                 if (ast == PT_OK && !(now.parts & PT_RESIDENT_FILM)) ast = pt_resident_assemble(scene, 0u);
                 if (ast != PT_OK) { fprintf(stderr, "--denoise-assemble: %s\n", pt_last_error()); rc = 1; break; }
             }
-            if (o.denoise && (o.resident || o.assemble)) {
+            if (o.denoise && o.denoise_groups) {
+                // the render left the film, its statistics and the group films on the device, paired: the guides stay there too, and the joint filter runs on all of
+                // it (with or without --denoise-resident: this is the only route, and its files are those of either)
+                const size_t np = (size_t)rd.width * rd.height;
+                std::vector<float> clean(4 * np), clean_groups(4 * np * gd.group_count);
+                pt_guide_chain_desc cd;
+                memset(&cd, 0, sizeof(cd));
+                cd.max_chain = o.max_chain; cd.alpha_max = o.alpha_max;
+                pt_resident_denoise_desc dd;
+                memset(&dd, 0, sizeof(dd));
+                pt_status dst = pt_resident_guides(scene, &rd, o.guide_samples, o.chain ? &cd : nullptr, o.demodulate ? PT_RESIDENT_ALBEDO : 0u);
+                if (dst == PT_OK) dst = pt_denoise_light_groups_resident(scene, &dd, clean.data(), nullptr, clean_groups.data());
+                if (dst != PT_OK) { fprintf(stderr, "--denoise-light-groups: %s\n", pt_last_error()); rc = 1; break; }
+                if (pt_output_film(&od, clean.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }
+                const std::string dbase = base + "_denoised";
+                if (pt_write_exr((dbase + ".exr").c_str(), rd.width, rd.height, linear.data(), od.colorspace) != PT_OK ||
+                    pt_write_png((dbase + ".png").c_str(), rd.width, rd.height, rgba.data(), od.colorspace) != PT_OK) {
+                    fprintf(stderr, "failed to write files: %s\n", pt_last_error()); rc = 1; break;
+                }
+                if (o.write_film && !write_npy(dbase + ".npy", clean.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", dbase.c_str()); rc = 1; break; }
+                printf("wrote %s.exr and %s.png\n", dbase.c_str(), dbase.c_str());
+                if (!write_groups(dbase, clean_groups, true)) { rc = 1; break; }
+            } else if (o.denoise && (o.resident || o.assemble)) {
                 // the render left film, counts, statistics and bins on the device: the guides stay there too, and the filter runs on all of it
                 std::vector<float> clean((size_t)rd.width * rd.height * 4), clean_spectral(spectral.size());
                 pt_guide_chain_desc cd;

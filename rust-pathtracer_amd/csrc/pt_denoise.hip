@@ -20,6 +20,8 @@
 #include "../../include/pt_spectral.h"
 #include "pt_denoise_launch.h"
 #include "pt_denoise_resident_launch.h"
+#include "../../include/pt_light_groups_denoise.h"
+#include "pt_denoise_light_groups_rules.h"
 #include "pt_denoise_resident_rules.h"
 #include "pt_denoise_rules.h"
 #include "pt_denoise_spectral_albedo_rules.h"
@@ -342,6 +344,72 @@ __global__ void __launch_bounds__(kLine) k_dn_quads_to_bins(uint32_t n, uint32_t
                                   [&](uint32_t b) { return bin_albedo[(size_t)b * n + i]; }, [&](uint32_t b, float v) { out[(size_t)b * n + i] = v; });
 }
 
+// ---------------------------------------------------------------------------------------------- filter, with light-group films
+// The joint filter over group films (pt_denoise_light_groups_rules.h) in the films' own layout: group-major float4 films, which is the layout dn_quad_index gives
+// a quad plane, so nothing is transposed into planes or quads and back.  The gather is k_dn_gather_spectral_quad's text over a GroupSource: its tile and
+// weight phase, then one 16-byte load per tap and group in chunks of two groups (dn_gather_pixel_bins4; w rides along as a fourth bin that stays 0).  A text
+// of its own that summed three channels, in chunks of four or of two groups, was measured against it and is not kept: no faster at G = 1 and 3 on the whole and
+// 4 to 9 % slower at G = 8: the weight phase is most of the kernel, and the fourth channel does not show in its time.
+// Neighbouring lanes read neighbouring float4s of one group's film: a wave's load is two rows of 512 contiguous bytes.
+struct GroupSource {
+    const float4* color_; const float4* geo_; const float* tent_; const uint8_t* flags_; const DnQuad* groups_; uint32_t width, plane;
+    __device__ uint32_t at(int x, int y) const { return (uint32_t)y * width + (uint32_t)x; }
+    __device__ uint32_t flags(int x, int y) const { return flags_[at(x, y)]; }
+    __device__ DnColor color(int x, int y) const { const float4 c = color_[at(x, y)]; return DnColor{c.x, c.y, c.z, c.w}; }
+    __device__ DnGeo geo(int x, int y) const { const float4 g = geo_[at(x, y)]; return DnGeo{g.x, g.y, g.z, g.w}; }
+    __device__ float tent(int x, int y) const { return tent_[at(x, y)]; }
+    __device__ DnQuad bin4(uint32_t g, int x, int y) const { return groups_[dn_quad_index(g, plane, at(x, y))]; }
+};
+
+// Behind k_dn_prepare(_albedo): the group films (never written) -> the first ping-pong buffer, divided by the XYZ albedo where HAS_A, the dead bit into flags,
+// and a pixel that is dead through its groups alone gets k_dn_prepare's colour of a dead pixel.  One lane per pixel, one 16-byte load and store per group.
+template <bool HAS_A>
+__global__ void __launch_bounds__(kLine) k_dn_groups_prepare(uint32_t n, uint32_t groups, const DnQuad* __restrict__ raw, const float4* __restrict__ albedo,
+                                                            const float4* __restrict__ film, const uint32_t* __restrict__ counts, const double2* __restrict__ stats,
+                                                            DnQuad* __restrict__ out, float4* __restrict__ color, uint8_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t f = flags[i];
+    DnAlbedo a{1.0f, 1.0f, 1.0f};
+    if (HAS_A) { const float4 a4 = albedo[i]; a = DnAlbedo{a4.x, a4.y, a4.z}; }
+    const uint32_t dead = dn_groups_prepare_pixel<HAS_A>(groups, f, a, [&](uint32_t g) { return raw[dn_quad_index(g, n, i)]; },
+                                                         [&](uint32_t g, DnQuad v) { out[dn_quad_index(g, n, i)] = v; });
+    if (dead && !(f & DN_DEAD)) {
+        const float4 c = film[i];
+        const double2 s = stats[i];
+        const DnColor o = dn_bins_dead_color(c.x, c.y, c.z, counts[i], s.x, s.y);
+        color[i] = make_float4(o.x, o.y, o.z, o.v);
+        flags[i] = (uint8_t)(f | dead);
+    }
+}
+
+// one a-trous pass: k_dn_gather_spectral's tile and weight phase, then the groups.  The outputs must not alias the inputs.
+__global__ void __launch_bounds__(kTileW * kTileH, 4) k_dn_gather_groups(DnParams P, int step, GroupSource src, const float2* __restrict__ grad, uint32_t groups,
+                                                                      float4* __restrict__ out, DnQuad* __restrict__ groups_out) {
+    const int x = blockIdx.x * kTileW + threadIdx.x, y = blockIdx.y * kTileH + threadIdx.y;
+    if (x >= (int)P.width || y >= (int)P.height) return;
+    const uint32_t i = (uint32_t)y * P.width + (uint32_t)x;
+    const float2 g = grad[i];
+    DnTaps taps;
+    const DnColor o = dn_gather_pixel_taps(src, P, step, x, y, g.x, g.y, &taps);
+    out[i] = make_float4(o.x, o.y, o.z, o.v);
+    DnQuad* px = groups_out + i;
+    const uint32_t plane = src.plane;
+    dn_gather_pixel_bins4(src, step, x, y, taps, groups, [&](uint32_t k, DnQuad v) { px[(size_t)k * plane] = v; });
+}
+
+// after the last pass: the ping-pong buffer -> the denoised group films, a live pixel multiplied back where HAS_A, its w 0; a dead one copied through
+template <bool HAS_A>
+__global__ void __launch_bounds__(kLine) k_dn_groups_finish(uint32_t n, uint32_t groups, const DnQuad* __restrict__ in, const float4* __restrict__ albedo,
+                                                           const uint8_t* __restrict__ flags, DnQuad* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t f = flags[i];
+    DnAlbedo a{1.0f, 1.0f, 1.0f};
+    if (HAS_A) { const float4 a4 = albedo[i]; a = DnAlbedo{a4.x, a4.y, a4.z}; }
+    for (uint32_t g = 0; g < groups; ++g) out[dn_quad_index(g, n, i)] = dn_groups_finish_pixel<HAS_A>(f, a, in[dn_quad_index(g, n, i)]);
+}
+
 int line_grid(size_t n) { return (int)((n + kLine - 1) / kLine); }
 
 // ---------------------------------------------------------------------------------------------- the filter's driver
@@ -360,6 +428,7 @@ struct DnHost {
     const float* film; const uint32_t* counts; const double* stats; const float* guides;   // required
     const float* albedo; uint32_t bins; const float* spectral; const float* bin_albedo;    // optional: null (bins 0) when absent; bin_albedo only with spectral
     float* out_film; float* out_spectral; float* out_variance;                             // out_spectral with spectral; out_variance may be null
+    uint32_t groups; const float* group_films; float* out_group_films;                     // pt_denoise_light_groups: group-major float4 films (groups 0: none)
 };
 
 // The filter behind the four host-array entries, which have checked their arguments: `d` is the normalised descriptor.  Three parts: the upload into device
@@ -371,7 +440,8 @@ pt_status dn_filter(const pt_denoise_desc& d, const DnHost& h) {
 #define DN_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return dfail(e_ == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
     DN_TRY(hipSetDevice((int)d.device));
     const size_t np = (size_t)d.width * d.height, bin_bytes = sizeof(float) * h.bins * np;
-    Dev d_film, d_counts, d_stats, d_guides, d_color[2], d_geo, d_tent, d_flags, d_grad, d_var, d_bins[2], d_albedo, d_bin_albedo;
+    Dev d_film, d_counts, d_stats, d_guides, d_color[2], d_geo, d_tent, d_flags, d_grad, d_var, d_bins[2], d_albedo, d_bin_albedo, d_groups, d_group_buf[2];
+    const size_t group_bytes = 16 * np * h.groups;
     DN_TRY(d_film.alloc(16 * np)); DN_TRY(d_counts.alloc(4 * np)); DN_TRY(d_stats.alloc(16 * np)); DN_TRY(d_guides.alloc(16 * np));
     DN_TRY(d_color[0].alloc(16 * np)); DN_TRY(d_color[1].alloc(16 * np)); DN_TRY(d_geo.alloc(16 * np)); DN_TRY(d_tent.alloc(4 * np));
     DN_TRY(d_flags.alloc(np)); DN_TRY(d_grad.alloc(8 * np)); DN_TRY(d_var.alloc(4 * np));
@@ -386,18 +456,25 @@ pt_status dn_filter(const pt_denoise_desc& d, const DnHost& h) {
     if (h.spectral) DN_TRY(hipMemcpy(d_bins[demodulate ? 1 : 0].p, h.spectral, bin_bytes, hipMemcpyHostToDevice));
     if (h.albedo) { DN_TRY(d_albedo.alloc(16 * np)); DN_TRY(hipMemcpy(d_albedo.p, h.albedo, 16 * np, hipMemcpyHostToDevice)); }
     if (h.bin_albedo) { DN_TRY(d_bin_albedo.alloc(bin_bytes)); DN_TRY(hipMemcpy(d_bin_albedo.p, h.bin_albedo, bin_bytes, hipMemcpyHostToDevice)); }
+    if (h.groups) {   // (the finish writes the denoised films over the uploaded ones: the passes have left them behind by then)
+        DN_TRY(d_groups.alloc(group_bytes)); DN_TRY(d_group_buf[0].alloc(group_bytes)); DN_TRY(d_group_buf[1].alloc(group_bytes));
+        DN_TRY(hipMemcpy(d_groups.p, h.group_films, group_bytes, hipMemcpyHostToDevice));
+    }
     ptk::DnRun r{};
     r.film = d_film.as<float>(); r.counts = d_counts.as<uint32_t>(); r.stats = d_stats.as<double>(); r.guides = d_guides.as<float>();
     r.albedo = d_albedo.as<float>(); r.bins = h.bins; r.spectral = h.spectral ? d_bins[demodulate ? 1 : 0].as<float>() : nullptr; r.bin_albedo = d_bin_albedo.as<float>();
     r.color[0] = d_color[0].as<float>(); r.color[1] = d_color[1].as<float>(); r.geo = d_geo.as<float>(); r.tent = d_tent.as<float>(); r.flags = d_flags.as<uint8_t>();
     r.grad = d_grad.as<float>(); r.bin_buf[0] = d_bins[0].as<float>(); r.bin_buf[1] = d_bins[1].as<float>();
     r.out_film = d_film.as<float>(); r.out_variance = d_var.as<float>();
+    r.groups = h.groups; r.group_films = d_groups.as<float>(); r.group_buf[0] = d_group_buf[0].as<float>(); r.group_buf[1] = d_group_buf[1].as<float>();
+    r.out_groups = d_groups.as<float>();
     ptk::dn_run(d, &r, nullptr);
     DN_TRY(hipGetLastError());
     DN_TRY(hipDeviceSynchronize());
     DN_TRY(hipMemcpy(h.out_film, r.out_film, 16 * np, hipMemcpyDeviceToHost));
     if (h.spectral) DN_TRY(hipMemcpy(h.out_spectral, r.denoised_bins, bin_bytes, hipMemcpyDeviceToHost));
     if (h.out_variance) DN_TRY(hipMemcpy(h.out_variance, r.out_variance, 4 * np, hipMemcpyDeviceToHost));
+    if (h.groups) DN_TRY(hipMemcpy(h.out_group_films, r.out_groups, group_bytes, hipMemcpyDeviceToHost));
 #undef DN_TRY
     return PT_OK;
 }
@@ -435,7 +512,8 @@ void albedo_basis(float wavelength_lo, float wavelength_hi, DnAlbedoBasis* basis
 
 
 // The run of the filter on device pointers (pt_denoise_resident_launch.h).  The launches are, kernel for kernel and in order, what the host-array entries have
-// always launched; `quads` swaps the three kernels that touch the bins for their quad forms.
+// always launched; `quads` swaps the three kernels that touch the bins for their quad forms.  `groups` (light-group films, never beside bins) adds the group
+// prepare behind the film's, takes the group gather in every pass and adds the group finish behind the film's; with no groups nothing of that is launched.
 void dn_run(const pt_denoise_desc& d, DnRun* run, hipStream_t stream) {
     const DnRun& r = *run;
     const size_t np = (size_t)d.width * d.height;
@@ -459,6 +537,11 @@ void dn_run(const pt_denoise_desc& d, DnRun* run, hipStream_t stream) {
     } else if (r.spectral) {
         hipLaunchKernelGGL(k_dn_spectral_dead, line, line_block, 0, stream, n, r.bins, r.bin_buf[0], r.flags);
     }
+    DnQuad* group_buf[2] = {reinterpret_cast<DnQuad*>(r.group_buf[0]), reinterpret_cast<DnQuad*>(r.group_buf[1])};
+    if (r.groups) {
+        const auto k = r.albedo ? k_dn_groups_prepare<true> : k_dn_groups_prepare<false>;
+        hipLaunchKernelGGL(k, line, line_block, 0, stream, n, r.groups, reinterpret_cast<const DnQuad*>(r.group_films), albedo, film, r.counts, stats, group_buf[0], color[0], r.flags);
+    }
     const dim3 grid((d.width + kTileW - 1) / kTileW, (d.height + kTileH - 1) / kTileH), block(kTileW, kTileH);
     int cur = 0;
     for (uint32_t i = 0; i < d.iterations; ++i) {
@@ -466,7 +549,10 @@ void dn_run(const pt_denoise_desc& d, DnRun* run, hipStream_t stream) {
         const DnBuffers b{color[cur], geo, r.tent, r.flags, grad};
         float4* out = color[cur ^ 1];
         hipLaunchKernelGGL(k_dn_tent, grid, block, 0, stream, P, b, r.tent);
-        if (r.spectral && r.quads) {
+        if (r.groups) {
+            const GroupSource src{b.color, b.geo, b.tent, b.flags, group_buf[cur], d.width, n};
+            hipLaunchKernelGGL(k_dn_gather_groups, grid, block, 0, stream, P, step, src, b.grad, r.groups, out, group_buf[cur ^ 1]);
+        } else if (r.spectral && r.quads) {
             const QuadSource src{b.color, b.geo, b.tent, b.flags, reinterpret_cast<const DnQuad*>(r.bin_buf[cur]), d.width, n};
             hipLaunchKernelGGL(k_dn_gather_spectral_quad, grid, block, 0, stream, P, step, src, b.grad, dn_quad_count(r.bins), out, reinterpret_cast<DnQuad*>(r.bin_buf[cur ^ 1]));
         } else if (r.spectral) {
@@ -479,6 +565,10 @@ void dn_run(const pt_denoise_desc& d, DnRun* run, hipStream_t stream) {
     }
     if (r.albedo) hipLaunchKernelGGL(k_dn_finish_albedo, line, line_block, 0, stream, n, color[cur], albedo, r.flags, reinterpret_cast<float4*>(r.out_film), r.out_variance);
     else hipLaunchKernelGGL(k_dn_finish, line, line_block, 0, stream, n, color[cur], reinterpret_cast<float4*>(r.out_film), r.out_variance);
+    if (r.groups) {
+        const auto k = r.albedo ? k_dn_groups_finish<true> : k_dn_groups_finish<false>;
+        hipLaunchKernelGGL(k, line, line_block, 0, stream, n, r.groups, group_buf[cur], albedo, r.flags, reinterpret_cast<DnQuad*>(r.out_groups));
+    }
     run->denoised_bins = nullptr;
     if (r.spectral && r.quads) {
         const auto k = r.bin_albedo ? k_dn_quads_to_bins<true> : k_dn_quads_to_bins<false>;
@@ -539,4 +629,14 @@ extern "C" pt_status pt_denoise_spectral_albedo(const pt_denoise_desc* desc, uin
     const pt_status st = pth::check_denoise_spectral_albedo_args(desc, bins, film, sample_counts, stats, guides, albedo, spectral, bin_albedo, out_film, out_spectral, &d, &err);
     if (st != PT_OK) return dfail(st, err);
     return dn_filter(d, DnHost{film, sample_counts, stats, guides, albedo, bins, spectral, bin_albedo, out_film, out_spectral, out_variance});
+}
+
+extern "C" pt_status pt_denoise_light_groups(const pt_denoise_desc* desc, uint32_t group_count, const float* film, const uint32_t* sample_counts, const double* stats,
+                                             const float* guides, const float* albedo, const float* group_films, float* out_film, float* out_variance,
+                                             float* out_group_films) {
+    pt_denoise_desc d;
+    std::string err;
+    const pt_status st = pth::check_denoise_light_groups_args(desc, group_count, film, sample_counts, stats, guides, albedo, group_films, out_film, out_group_films, &d, &err);
+    if (st != PT_OK) return dfail(st, err);
+    return dn_filter(d, DnHost{film, sample_counts, stats, guides, albedo, 0u, nullptr, nullptr, out_film, nullptr, out_variance, group_count, group_films, out_group_films});
 }

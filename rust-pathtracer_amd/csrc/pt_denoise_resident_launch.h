@@ -27,6 +27,10 @@ struct DnRun {
     // outputs
     float* out_film; float* out_variance;   // np float4, np
     const float* denoised_bins;             // set by dn_run: where the denoised bins lie, plane-major (out_bins, or a bin_buf)
+    // Light-group films beside the film (pt_denoise_light_groups_rules.h; never together with bins): `groups` group-major float4 films of np pixels.  group_films
+    // is read only; group_buf are the passes' ping-pong buffers, groups * np float4 each; out_groups takes the denoised films (it may be group_films: the finish
+    // runs after the last read of them, one lane per pixel).  groups 0: none of this is looked at.
+    uint32_t groups; const float* group_films; float* group_buf[2]; float* out_groups;
 };
 // the launches of one run of the normalised descriptor `d` on `stream`; nothing is synchronised
 void dn_run(const pt_denoise_desc& d, DnRun* run, hipStream_t stream);

@@ -29,6 +29,7 @@
 #include "../../include/pt_debug.h"
 #include "../../include/pt_denoise.h"
 #include "../../include/pt_light_groups.h"
+#include "../../include/pt_light_groups_denoise.h"
 #include "pt_adaptive_select.h"
 #include "pt_light_groups_launch.h"
 #include "pt_spectral_launch.h"
@@ -363,11 +364,17 @@ struct pt_scene {
     std::vector<uint32_t> shard_px;
     GrowBuf shard_packed;
     // The resident group films (include/pt_light_groups.h): what the last successful light-group render left in group_films_cache, group-major float4 films.  Cleared
-    // when a group render starts and set when it has succeeded; pt_render_light_groups is the only writer of the buffer.  group_table: that render's one byte per
+    // when a group render starts and set when it has succeeded; pt_render_light_groups and pt_render_adaptive_light_groups are the only writers of the buffer.  group_table: that render's one byte per
     // instance; group_mix_cache: pt_light_groups_mix_resident's device matrices (PT_LIGHT_GROUPS_MAX x 9 floats) and, behind them, its output film.
     bool groups_valid = false;
     uint32_t groups_width = 0, groups_height = 0, groups_count = 0;
     GrowBuf group_films_cache, group_table, group_mix_cache;
+    // include/pt_light_groups_denoise.h.  groups_paired: the group films and the resident FILM came from one render (pt_render_adaptive_light_groups); ended where the
+    // resident film is ended or replaced and where another group render starts.  groups_denoised: pt_denoise_light_groups_resident has left denoised group films in
+    // group_den_films (of groups_width x groups_height x groups_count, beside its film and variance in group_den_film / group_den_var: pt_denoise_resident's
+    // outputs are not touched); cleared when a group render of either kind or that entry starts.  group_dn_buf: the passes' two ping-pong group buffers.
+    bool groups_paired = false, groups_denoised = false;
+    GrowBuf group_dn_buf[2], group_den_films, group_den_film, group_den_var;
     ResidentSet resident;          // include/pt_resident.h
     GrowBuf assemble_staging, assemble_px;   // pt_resident_assemble's: the packed shards copied from other devices, and the pixel lists uploaded for the unpack
     GrowBuf project_cache;         // pt_spectral_project_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x PT_SPECTRAL_MAX_BINS floats) and, behind it, its output planes
@@ -967,6 +974,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     st = adaptive ? adaptive_rounds(sc, rd, *adaptive, stream, d_film, (uint32_t)pixels.size(), run_passes, &rounds, job.node, job.node_index)
                   : run_passes(b.pixels, (uint32_t)pixels.size(), rd.first_sample, rd.sample_count, nullptr);
     if (st != PT_OK) return st;
+    if (adaptive && job.groups) HIP_TRY(ptk::launch_adaptive_finish_groups(stream, rd.width * rd.height, sc->adaptive.counts, job.d_group_films, group_count));
     if (adaptive && job.d_spectral)
         hipLaunchKernelGGL(k_adaptive_finish_spectral, dim3(sc->num_cus * 4), dim3(kBlock), 0, stream, rd.width * rd.height, job.spectral_bins, sc->adaptive.counts, job.d_spectral);
     HIP_TRY(hipGetLastError());
@@ -1183,7 +1191,8 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
     const pt_render_desc& rd = *call.rd;
     forget_node_render(sc);
     if (call.sd) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts: whatever the buffer held is no film from here on)
-    if (call.gd) sc->groups_valid = false;   // (likewise the group films)
+    if (call.gd) { sc->groups_valid = false; sc->groups_denoised = false; }   // (likewise the group films, and the denoised ones that came from them)
+    sc->groups_paired = false;   // (the resident film ends below)
     sc->resident.end();   // (film_cache and the adaptive buffers are written from here on; guides and denoised outputs belonged to the film before)
     HIP_TRY(hipSetDevice(sc->device));
     const size_t n_pixels = (size_t)rd.width * rd.height, film_bytes = sizeof(float) * 4 * n_pixels, spectral_bytes = call.sd ? sizeof(float) * call.sd->bins * n_pixels : 0;
@@ -1213,6 +1222,7 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
     if (call.sd) HIP_TRY(hipMemcpy(call.spectral, sc->spectral_cache.p, spectral_bytes, hipMemcpyDeviceToHost));
     if (call.gd && call.group_films) HIP_TRY(hipMemcpy(call.group_films, sc->group_films_cache.p, group_bytes, hipMemcpyDeviceToHost));
     if (call.gd) { sc->groups_width = rd.width; sc->groups_height = rd.height; sc->groups_count = call.gd->group_count; sc->groups_valid = true; }
+    if (call.gd && call.ad) sc->groups_paired = true;   // (the resident film set below and the group films came from this one render)
     if (call.ad && profile) profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (the whole call: set-up, rounds, read-backs)
     if (call.sd) { sc->spectral_width = rd.width; sc->spectral_height = rd.height; sc->spectral_bins = call.sd->bins; sc->spectral_valid = true; }
     if (call.ad) {   // the resident set of include/pt_resident.h: film, counts and statistics, and the bins of a spectral render
@@ -1282,6 +1292,21 @@ pt_status pt_render_light_groups(pt_scene* sc, const pt_render_desc* rdp, const 
     return render_one(sc, call, profile);
 }
 
+pt_status pt_render_adaptive_light_groups(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, const pt_light_groups_desc* gdp, float* film,
+                                          uint32_t* sample_counts, double* stats, float* group_films, pt_profile* profile) {
+    forget_node_render(sc);
+    pt_render_desc rd;
+    pt_adaptive_desc ad;
+    std::string err;
+    const pt_status st = pth::check_adaptive_light_groups_args(sc, rdp, adp, gdp, sc ? sc->host.blob[PT_HDR_INSTANCE_COUNT] : 0u, sc ? (uint32_t)sc->host.cameras.size() : 0u,
+                                                               film, sample_counts, &rd, &ad, &err);
+    if (st != PT_OK) return fail(st, err);
+    if ((uint64_t)rd.width * rd.height > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and width x height must fit 31 bits");
+    RenderCall call;
+    call.rd = &rd; call.ad = &ad; call.gd = gdp; call.film = film; call.sample_counts = sample_counts; call.stats = stats; call.group_films = group_films;
+    return render_one(sc, call, profile);
+}
+
 pt_status pt_light_groups_resident(pt_scene* sc, uint32_t* width, uint32_t* height, uint32_t* group_count) {
     if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
     if (!width || !height || !group_count) return fail(PT_ERR_INVALID_ARGUMENT, "width, height or group_count is null");
@@ -1290,10 +1315,27 @@ pt_status pt_light_groups_resident(pt_scene* sc, uint32_t* width, uint32_t* heig
 }
 
 // include/pt_light_groups.h: pt_light_groups_mix's kernel over group_films_cache, on the stream the render ran on (the null stream), so the group films never cross the bus.
+// (`films`: group_films_cache, or the denoised group films of include/pt_light_groups_denoise.h — the same size and count)
+static pt_status mix_resident_films(pt_scene* sc, const float* films, const float* matrices, float* out);
 pt_status pt_light_groups_mix_resident(pt_scene* sc, const float* matrices, float* out) {
     if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
     if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "out_xyzw is null");
     if (!sc->groups_valid) return fail(PT_ERR_INVALID_ARGUMENT, "the scene has no resident group films: pt_render_light_groups must have succeeded on it");
+    return mix_resident_films(sc, sc->group_films_cache.as<float>(), matrices, out);
+}
+pt_status pt_light_groups_mix_resident_denoised(pt_scene* sc, const float* matrices, float* out) {
+    if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
+    if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "out_xyzw is null");
+    if (!sc->groups_denoised) return fail(PT_ERR_INVALID_ARGUMENT, "the scene has no resident denoised group films: pt_denoise_light_groups_resident must have succeeded on it");
+    return mix_resident_films(sc, sc->group_den_films.as<float>(), matrices, out);
+}
+pt_status pt_light_groups_denoised_resident(pt_scene* sc, uint32_t* width, uint32_t* height, uint32_t* group_count) {
+    if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
+    if (!width || !height || !group_count) return fail(PT_ERR_INVALID_ARGUMENT, "width, height or group_count is null");
+    *width = sc->groups_denoised ? sc->groups_width : 0u; *height = sc->groups_denoised ? sc->groups_height : 0u; *group_count = sc->groups_denoised ? sc->groups_count : 0u;
+    return PT_OK;
+}
+static pt_status mix_resident_films(pt_scene* sc, const float* films, const float* matrices, float* out) {
     std::string err;
     const pt_status st = pth::check_light_groups_matrices(sc->groups_count, matrices, &err);
     if (st != PT_OK) return fail(st, err);
@@ -1305,7 +1347,7 @@ pt_status pt_light_groups_mix_resident(pt_scene* sc, const float* matrices, floa
     float* d_out = d_matrices + matrix_floats;
     hipStream_t stream = nullptr;
     HIP_TRY(hipMemcpyAsync(d_matrices, matrices, sizeof(float) * 9 * sc->groups_count, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ptk::launch_light_groups_mix(stream, (uint32_t)n_pixels, sc->groups_count, sc->group_films_cache.as<float>(), d_matrices, d_out));
+    HIP_TRY(ptk::launch_light_groups_mix(stream, (uint32_t)n_pixels, sc->groups_count, films, d_matrices, d_out));
     HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(float) * 4 * n_pixels, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return PT_OK;
@@ -1636,6 +1678,7 @@ static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t devi
     pt_status st = node_devices(sc, device_mask, &node);
     if (st != PT_OK) return st;
     if (node.single(sc)) return render_one(sc, call, profile);   // (the one-device entry's body: its checks are among this call's, and have passed)
+    sc->groups_paired = false;
     sc->resident.end();   // (the shards of a node render are no film one device can filter until pt_resident_assemble is asked: include/pt_resident.h)
 
     DeviceGuard guard;
@@ -2097,6 +2140,7 @@ pt_status pt_resident_load(pt_scene* sc, uint32_t width, uint32_t height, uint32
     HIP_TRY(hipSetDevice(sc->device));
     const size_t np = (size_t)width * height;
     // a part that is given is resident no longer until its upload has succeeded; the denoised parts go with the inputs they came from
+    if (film) sc->groups_paired = false;   // (the film the group films came with is replaced)
     r.parts &= ~((film ? PT_RESIDENT_FILM : 0u) | (spectral ? PT_RESIDENT_BINS : 0u) | (guides ? PT_RESIDENT_GUIDES : 0u) | (albedo ? PT_RESIDENT_ALBEDO : 0u) |
                  (bin_albedo ? PT_RESIDENT_BIN_ALBEDO : 0u) | PT_RESIDENT_DENOISED | PT_RESIDENT_DENOISED_BINS);
     r.tidy();
@@ -2129,6 +2173,7 @@ pt_status pt_resident_assemble(pt_scene* sc, uint32_t flags) {
     DeviceGuard guard;
     HIP_TRY(hipSetDevice(sc->device));
     r.end();   // (every part is replaced or belonged to another film; on any failure below nothing is resident)
+    sc->groups_paired = false;
     const size_t np = (size_t)k.info.width * k.info.height;
     const uint32_t bins = k.info.bins;
     const bool staged_all = (flags & PT_RESIDENT_ASSEMBLE_STAGED) != 0u;
@@ -2239,6 +2284,45 @@ pt_status pt_denoise_resident(pt_scene* sc, const pt_resident_denoise_desc* desc
     HIP_TRY(hipStreamSynchronize(stream));
     r.denoised_bins = run.denoised_bins;
     r.parts |= PT_RESIDENT_DENOISED | (has_bins ? PT_RESIDENT_DENOISED_BINS : 0u);
+    return PT_OK;
+}
+// include/pt_light_groups_denoise.h: ptk::dn_run's group form on the resident film, guides and albedo and the group films paired with that film.  The scratch of the
+// film's passes is pt_denoise_resident's (it holds nothing between calls); the outputs are this entry's own, so DENOISED and the buffers behind it stay as they are.
+pt_status pt_denoise_light_groups_resident(pt_scene* sc, const pt_resident_denoise_desc* desc, float* out_film, float* out_variance, float* out_group_films) {
+    std::string err;
+    pt_denoise_desc d;
+    pth::GroupsResident gr;
+    if (sc) { gr.valid = sc->groups_valid; gr.paired = sc->groups_paired; gr.width = sc->groups_width; gr.height = sc->groups_height; gr.group_count = sc->groups_count; }
+    pt_status st = pth::check_resident_denoise_light_groups_args(sc, desc, resident_now(sc), gr, &d, &err);
+    if (st != PT_OK) return fail(st, err);
+    ResidentSet& r = sc->resident;
+    HIP_TRY(hipSetDevice(sc->device));
+    sc->groups_denoised = false;
+    const size_t np = (size_t)r.width * r.height, group_bytes = 16 * np * sc->groups_count;
+    struct Want { GrowBuf* buf; size_t bytes; };
+    const Want wants[] = {{&r.color[0], 16 * np}, {&r.color[1], 16 * np}, {&r.geo, 16 * np}, {&r.tent, 4 * np}, {&r.flags, np}, {&r.grad, 8 * np}, {&sc->group_den_film, 16 * np},
+                          {&sc->group_den_var, 4 * np}, {&sc->group_dn_buf[0], group_bytes}, {&sc->group_dn_buf[1], group_bytes}, {&sc->group_den_films, group_bytes}};
+    for (const Want& w : wants) {
+        st = w.buf->reserve(w.bytes);
+        if (st != PT_OK) return st;
+    }
+    ptk::DnRun run;
+    memset(&run, 0, sizeof(run));
+    run.film = r.film; run.counts = r.counts; run.stats = r.stats; run.guides = r.guides.as<float>();
+    run.albedo = (r.parts & PT_RESIDENT_ALBEDO) ? r.albedo.as<float>() : nullptr;
+    run.color[0] = r.color[0].as<float>(); run.color[1] = r.color[1].as<float>(); run.geo = r.geo.as<float>(); run.tent = r.tent.as<float>();
+    run.flags = r.flags.as<uint8_t>(); run.grad = r.grad.as<float>();
+    run.out_film = sc->group_den_film.as<float>(); run.out_variance = sc->group_den_var.as<float>();
+    run.groups = sc->groups_count; run.group_films = sc->group_films_cache.as<float>();
+    run.group_buf[0] = sc->group_dn_buf[0].as<float>(); run.group_buf[1] = sc->group_dn_buf[1].as<float>(); run.out_groups = sc->group_den_films.as<float>();
+    const hipStream_t stream = nullptr;
+    ptk::dn_run(d, &run, stream);
+    HIP_TRY(hipGetLastError());
+    if (out_film) HIP_TRY(hipMemcpyAsync(out_film, run.out_film, 16 * np, hipMemcpyDeviceToHost, stream));
+    if (out_variance) HIP_TRY(hipMemcpyAsync(out_variance, run.out_variance, 4 * np, hipMemcpyDeviceToHost, stream));
+    if (out_group_films) HIP_TRY(hipMemcpyAsync(out_group_films, run.out_groups, group_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    sc->groups_denoised = true;
     return PT_OK;
 }
 pt_status pt_spectral_project_resident_denoised(pt_scene* sc, uint32_t K, const float* matrix, float* out) {

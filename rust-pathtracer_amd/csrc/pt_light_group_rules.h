@@ -89,6 +89,14 @@ PT_HD void lg_accumulate_pixel(const RenderParams& rp, const float* energy, uint
     stage_accumulate_pixel<1>(rp, energy + (size_t)lg_plane(group) * rp.energy_stride, p, pixel, film_px, nullptr, energy + rp.energy_stride);
 }
 
+// The finish of an adaptive group render (pt_render_adaptive_light_groups): a group film pixel holds running sums, as the film does, until each pixel is divided
+// by its own count — k_adaptive_finish's rule: x / (float)n per channel, w = 0, and a pixel of count 0 is left alone.
+PT_HD void lg_adaptive_finish_pixel(uint32_t count, float* film_px) {
+    if (count == 0u) return;
+    const float c = (float)count;
+    film_px[0] = film_px[0] / c; film_px[1] = film_px[1] / c; film_px[2] = film_px[2] / c; film_px[3] = 0.0f;
+}
+
 // The mix of one pixel.  load(g, &x, &y, &z): group g's film pixel; m: G x 9 floats, row-major 3 x 3 per group.
 template <typename Load>
 PT_HD void lg_mix_pixel(uint32_t group_count, const float* m, Load&& load, float* out_xyzw) {

@@ -1,5 +1,5 @@
 // pt_light_groups.hip — the films of a light-group render (include/pt_light_groups.h) on gfx950: k_accumulate_groups, k_accumulate over
-// the group planes of a pass's energy buffer, k_light_groups_mix, the relight, and the host-array entry pt_light_groups_mix.  The render and the resident
+// the group planes of a pass's energy buffer, k_adaptive_finish_groups, the division of an adaptive group render's running sums, k_light_groups_mix, the relight, and the host-array entry pt_light_groups_mix.  The render and the resident
 // entries are pt_engine.hip's (the films are the scene's); they launch the same kernels.  The per-pixel rules are pt_light_group_rules.h's, the text the host
 // emulation compiles.
 //
@@ -50,6 +50,20 @@ __global__ void __launch_bounds__(kBlock) k_light_groups_mix(uint32_t n_pixels, 
     }
 }
 
+// the finish of an adaptive group render: one lane per pixel and group, the group in blockIdx.y as in k_accumulate_groups; a lane reads its pixel's count and
+// makes one 16-byte load and store (lg_adaptive_finish_pixel)
+__global__ void __launch_bounds__(kBlock) k_adaptive_finish_groups(uint32_t n_pixels, const uint32_t* __restrict__ counts, float* __restrict__ group_films) {
+    float4* film = reinterpret_cast<float4*>(group_films) + (size_t)blockIdx.y * n_pixels;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_pixels; p += gridDim.x * blockDim.x) {
+        const uint32_t n = counts[p];
+        if (n == 0u) continue;
+        const float4 v = film[p];
+        float f[4] = {v.x, v.y, v.z, v.w};
+        lg_adaptive_finish_pixel(n, f);
+        film[p] = make_float4(f[0], f[1], f[2], f[3]);
+    }
+}
+
 // one workgroup per 256 items, at most 16384 (the grid-stride loops take the rest)
 int lanes_grid(uint32_t items) {
     const uint32_t need = (items + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
@@ -74,6 +88,12 @@ hipError_t launch_accumulate_groups(hipStream_t stream, const RenderParams& rp, 
                                     size_t film_pixels) {
     if (group_count == 0 || group_count > LG_MAX_GROUPS || !group_films) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_accumulate_groups, dim3(lanes_grid(rp.chunk_pixels), group_count), dim3(kBlock), 0, stream, rp, pixels, energy, group_films, film_pixels);
+    return hipGetLastError();
+}
+
+hipError_t launch_adaptive_finish_groups(hipStream_t stream, uint32_t n_pixels, const uint32_t* counts, float* group_films, uint32_t group_count) {
+    if (group_count == 0 || group_count > LG_MAX_GROUPS || !group_films || !counts || n_pixels == 0 || n_pixels > 0x7fffffffu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_adaptive_finish_groups, dim3(lanes_grid(n_pixels), group_count), dim3(kBlock), 0, stream, n_pixels, counts, group_films);
     return hipGetLastError();
 }
 

@@ -507,4 +507,51 @@ pt_status check_light_groups_mix_args(uint32_t width, uint32_t height, uint32_t 
     return PT_OK;
 }
 
+// ---- include/pt_light_groups_denoise.h
+pt_status check_adaptive_light_groups_args(const void* scene, const pt_render_desc* rd, const pt_adaptive_desc* ad, const pt_light_groups_desc* gd, uint32_t scene_instances,
+                                           uint32_t camera_count, const void* film, const void* sample_counts, pt_render_desc* rd_out, pt_adaptive_desc* ad_out,
+                                           std::string* error) {
+    if (!scene) { *error = "the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!rd) { *error = "the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!ad) { *error = "the adaptive desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = check_light_groups_args(scene, rd, gd, scene_instances, film, error);
+    if (st != PT_OK) return st;
+    return normalize_adaptive_desc(*rd, *ad, sample_counts != nullptr, camera_count, rd_out, ad_out, error);
+}
+
+pt_status check_denoise_light_groups_args(const pt_denoise_desc* in, uint32_t group_count, const void* film, const uint32_t* sample_counts, const void* stats,
+                                          const float* guides, const float* albedo, const void* group_films, const void* out_film, const void* out_group_films,
+                                          pt_denoise_desc* out, std::string* error) {
+    if (group_count == 0 || group_count > PT_LIGHT_GROUPS_MAX) { *error = "group_count must be in 1..8"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!group_films) { *error = "the group films are null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!out_group_films) { *error = "out_group_films is null"; return PT_ERR_INVALID_ARGUMENT; }
+    pt_status st = normalize_denoise_desc(in, film, sample_counts, stats, guides, out_film, out, error);
+    if (st == PT_OK) st = check_denoise_inputs(*out, sample_counts, guides, error);
+    if (st == PT_OK && albedo) st = check_denoise_albedo(*out, albedo, error);
+    return st;
+}
+
+pt_status check_resident_denoise_light_groups_args(const void* scene, const pt_resident_denoise_desc* desc, const struct pt_resident_info& now, const GroupsResident& groups,
+                                                   pt_denoise_desc* out, std::string* error) {
+    if (!scene) { *error = "pt_denoise_light_groups_resident: the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!desc) { *error = "pt_denoise_light_groups_resident: the desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (desc->flags != 0) { *error = "pt_denoise_light_groups_resident: flags must be 0"; return PT_ERR_INVALID_ARGUMENT; }
+    for (uint32_t r : desc->reserved) if (r != 0) { *error = "pt_resident_denoise_desc::reserved must be 0"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((desc->filter.width == 0) != (desc->filter.height == 0)) { *error = "pt_denoise_light_groups_resident: width and height are both 0 or both the resident size"; return PT_ERR_INVALID_ARGUMENT; }
+    pt_denoise_desc f = desc->filter;
+    const bool sized = f.width != 0;
+    if (!sized) { f.width = 1; f.height = 1; }
+    const pt_status st = normalize_denoise_desc(&f, scene, scene, scene, scene, scene, out, error);   // (its arrays are the scene's own: never null)
+    if (st != PT_OK) return st;
+    if (!(now.parts & PT_RESIDENT_FILM)) { *error = "pt_denoise_light_groups_resident: the scene has no resident film: pt_render_adaptive_light_groups must have succeeded on it"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!groups.valid || !groups.paired || groups.width != now.width || groups.height != now.height) {
+        *error = "pt_denoise_light_groups_resident: the scene has no group films of the resident film's render: pt_render_adaptive_light_groups must have succeeded on it, with no render since";
+        return PT_ERR_INVALID_ARGUMENT;
+    }
+    if (!(now.parts & PT_RESIDENT_GUIDES)) { *error = "pt_denoise_light_groups_resident: the scene has no resident guides: pt_resident_guides or pt_resident_load must have succeeded on it"; return PT_ERR_INVALID_ARGUMENT; }
+    if (sized && (f.width != now.width || f.height != now.height)) { *error = "pt_denoise_light_groups_resident: width and height are neither 0 nor the resident size"; return PT_ERR_INVALID_ARGUMENT; }
+    out->width = now.width; out->height = now.height;
+    return PT_OK;
+}
+
 }  // namespace pth

@@ -11,6 +11,7 @@
 #include "../../include/pt_api.h"
 #include "../../include/pt_denoise.h"
 #include "../../include/pt_light_groups.h"
+#include "../../include/pt_light_groups_denoise.h"
 #include "../../include/pt_resident.h"
 #include "../../include/pt_spectral.h"
 #include "pt_stages.h"
@@ -155,6 +156,26 @@ pt_status check_light_groups_matrices(uint32_t group_count, const float* matrice
 // pt_light_groups_mix: no null pointer, check_light_groups_matrices, width and height positive and width x height within 31 bits
 pt_status check_light_groups_mix_args(uint32_t width, uint32_t height, uint32_t group_count, const void* group_films, const float* matrices, const void* out,
                                       std::string* error);
+
+
+// ---- include/pt_light_groups_denoise.h, for the engine and the host emulation alike; every check runs before a device is looked for.
+// pt_render_adaptive_light_groups: no null pointer (stats and group_films may be null), then everything check_light_groups_args refuses and everything
+// normalize_adaptive_desc refuses, each with its own message; *rd_out and *ad_out as normalize_adaptive_desc leaves them.
+pt_status check_adaptive_light_groups_args(const void* scene, const pt_render_desc* rd, const pt_adaptive_desc* ad, const pt_light_groups_desc* gd, uint32_t scene_instances,
+                                           uint32_t camera_count, const void* film, const void* sample_counts, pt_render_desc* rd_out, pt_adaptive_desc* ad_out,
+                                           std::string* error);
+// pt_denoise_light_groups: group_count in 1..PT_LIGHT_GROUPS_MAX and the two group-film pointers, then pt_denoise_spectral_albedo's rules (normalize_denoise_desc,
+// check_denoise_inputs, check_denoise_albedo where an albedo is given)
+pt_status check_denoise_light_groups_args(const pt_denoise_desc* in, uint32_t group_count, const void* film, const uint32_t* sample_counts, const void* stats,
+                                          const float* guides, const float* albedo, const void* group_films, const void* out_film, const void* out_group_films,
+                                          pt_denoise_desc* out, std::string* error);
+// What a scene remembers of its group films for the resident entries: the last group render's size and count, whether that render was the adaptive one whose
+// film is still the resident one (`paired`), and what pt_denoise_light_groups_resident left (`denoised`)
+struct GroupsResident { bool valid = false, paired = false, denoised = false; uint32_t width = 0, height = 0, group_count = 0; };
+// pt_denoise_light_groups_resident: the scene and the desc, flags 0, reserved words 0, the filter as normalize_denoise_desc wants it (*out: normalised, with the
+// resident size), a resident film and guides, group films paired with that film, the size 0 or the resident one
+pt_status check_resident_denoise_light_groups_args(const void* scene, const pt_resident_denoise_desc* desc, const struct pt_resident_info& now, const GroupsResident& groups,
+                                                   pt_denoise_desc* out, std::string* error);
 
 }  // namespace pth
 #endif

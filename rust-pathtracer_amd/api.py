@@ -140,6 +140,7 @@ def light_group_gains(gains):
 # include/pt_spectral.h: a response that is no curve (a component of the engine's colour-matching fit), the absent filter, the caps of a development
 RESPONSE_CIE_X, RESPONSE_CIE_Y, RESPONSE_CIE_Z = -1, -2, -3
 SPECTRAL_NO_FILTER = -1
+RELAMP_KEEP = -1   # PT_RELAMP_KEEP (include/pt_light_groups_spectral.h): a group keeps its lamp
 SPECTRAL_MAX_RESPONSES, SPECTRAL_MAX_SUBSAMPLES = 16, 16
 
 
@@ -331,6 +332,17 @@ class Library:
         self._light_groups_resident = bind("light_groups_resident", C.c_int32, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)], required=False)
         self._light_groups_mix_resident = bind("light_groups_mix_resident", C.c_int32, [vp, fpp, fpp], required=False)
         self._light_groups_last_error = bind("light_groups_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the entries above)
+        # include/pt_light_groups_spectral.h
+        self._render_light_groups_spectral = bind("render_light_groups_spectral", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(LightGroupsDesc), C.POINTER(SpectralDesc),
+                                                                                              fpp, fpp, fpp, fpp, C.POINTER(Profile)], required=False)
+        self._light_groups_spectral_resident = bind("light_groups_spectral_resident", C.c_int32, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)],
+                                                    required=False)
+        self._light_groups_relamp_matrix = bind("light_groups_relamp_matrix", C.c_int32, [C.POINTER(RenderDesc), C.POINTER(SpectralDesc), C.POINTER(Curve), u32, fpp, u32, u32,
+                                                                                          C.POINTER(C.c_int32), C.c_int32, u32, u32, C.POINTER(C.c_int32),
+                                                                                          C.POINTER(C.c_int32), fpp, fpp], required=False)
+        self._light_groups_relamp = bind("light_groups_relamp", C.c_int32, [u32, u32, u32, u32, u32, fpp, fpp, fpp], required=False)
+        self._light_groups_relamp_resident = bind("light_groups_relamp_resident", C.c_int32, [vp, u32, fpp, fpp], required=False)
+        self._light_groups_spectral_last_error = bind("light_groups_spectral_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the entries above)
         # include/pt_light_groups_denoise.h
         self._render_adaptive_light_groups = bind("render_adaptive_light_groups", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), C.POINTER(LightGroupsDesc), fpp,
                                                                                               C.POINTER(u32), C.POINTER(C.c_double), fpp, C.POINTER(Profile)], required=False)
@@ -608,6 +620,56 @@ class Library:
         self._light_groups_check(self._light_groups_mix(w, h, G, _fp(group_films), _fp(matrices), _fp(out)))
         return out
 
+    def _light_groups_spectral_check(self, status):
+        if status != PT_OK:
+            err = self._light_groups_spectral_last_error
+            raise PtError(status, err().decode() if err else self.last_error())
+
+    def light_groups_relamp_matrix(self, rd, bins, responses, groups, old_curve, new_curve, gain=None, curves=None, curve_data=None, filter=None, subsamples=1):
+        """pt_light_groups_relamp_matrix: float32 [K, G, bins], the matrix of a re-lamp of `groups` = G groups rendered with `bins` bins.  responses, curves,
+        curve_data, filter and subsamples are spectral_response_matrix's.  old_curve[g] / new_curve[g]: indices into `curves` — group g's emission curve as it
+        was rendered and the one to see it under — or RELAMP_KEEP (None); gain [G] (None = all 1).  Entry [k, g, b] integrates response k times
+        new / old over bin b.  With KEEP and gain 1 a group's rows are spectral_response_matrix's bit for bit.  Host only."""
+        if self._light_groups_relamp_matrix is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %slight_groups_relamp_matrix entry" % (self.path, self.prefix))
+        responses = [int(r) for r in responses]
+        K, G = len(responses), int(groups)
+        keep = lambda seq: [RELAMP_KEEP if c is None else int(c) for c in seq]
+        old_curve, new_curve = keep(old_curve), keep(new_curve)
+        if len(old_curve) != G or len(new_curve) != G:
+            raise ValueError("old_curve and new_curve: one entry per group")
+        curves = list(curves) if curves is not None else []
+        carr = (Curve * max(len(curves), 1))(*curves)
+        cd = np.ascontiguousarray(curve_data if curve_data is not None else [], dtype=np.float32).ravel()
+        rarr = (C.c_int32 * max(K, 1))(*responses)
+        oarr, narr = (C.c_int32 * max(G, 1))(*old_curve), (C.c_int32 * max(G, 1))(*new_curve)
+        garr = None
+        if gain is not None:
+            garr = np.ascontiguousarray(gain, dtype=np.float32).ravel()
+            if garr.size != G:
+                raise ValueError("gain: one factor per group")
+        matrix = np.zeros((K, max(G, 0), max(int(bins), 0)), np.float32)
+        sd = SpectralDesc(bins)
+        self._light_groups_spectral_check(self._light_groups_relamp_matrix(
+            C.byref(rd), C.byref(sd), carr if curves else None, len(curves), _fp(cd) if cd.size else None, cd.size, K, rarr,
+            SPECTRAL_NO_FILTER if filter is None else int(filter), subsamples, G, oarr, narr, _fp(garr) if garr is not None else None, _fp(matrix)))
+        return matrix
+
+    def light_groups_relamp(self, group_spectral, matrix):
+        """pt_light_groups_relamp: group_spectral [G,B,H,W] developed by matrix [K,G,B] (light_groups_relamp_matrix makes one): float32 [K,H,W], out[k] = the f32
+        fold of matrix[k,g,b] * group_spectral[g,b] over the planes g * B + b ascending."""
+        if self._light_groups_relamp is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %slight_groups_relamp entry" % (self.path, self.prefix))
+        group_spectral = np.ascontiguousarray(group_spectral, dtype=np.float32)
+        matrix = np.ascontiguousarray(matrix, dtype=np.float32)
+        if group_spectral.ndim != 4 or matrix.ndim != 3 or matrix.shape[1:] != group_spectral.shape[:2]:
+            raise ValueError("group_spectral [G,B,H,W] and matrix [K,G,B]")
+        G, bins, h, w = group_spectral.shape
+        K = matrix.shape[0]
+        out = np.zeros((K, h, w), np.float32)
+        self._light_groups_spectral_check(self._light_groups_relamp(w, h, G, bins, K, _fp(matrix), _fp(group_spectral), _fp(out)))
+        return out
+
     def denoise_light_groups(self, film, counts, stats, guides, group_films, albedo=None, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0,
                              device=0, variance=False):
         """pt_denoise_light_groups: the joint filter over the film and its group films [G,H,W,4] — the taps and weights of denoise_film (with `albedo` [H,W,4]:
@@ -732,6 +794,51 @@ class Scene:
         w, h, g = C.c_uint32(), C.c_uint32(), C.c_uint32()
         self.library._light_groups_check(entry(self.handle, C.byref(w), C.byref(h), C.byref(g)))
         return (w.value, h.value, g.value) if g.value else None
+
+    def render_light_groups_spectral(self, rd, bins, instance_group, environment_group=0, groups=None, read_groups=True, read_bins=True):
+        """pt_render_light_groups_spectral: (film, group_films, spectral, group_spectral, profile) — film [H,W,4] and group_films [G,H,W,4] are
+        render_light_groups' bit for bit, spectral [bins,H,W] is render_spectral's bit for bit, and group_spectral [G,bins,H,W] holds per group the bins of the
+        energy its emitters contributed.  read_groups False leaves the group films on the device alone (None), read_bins False the total and the group bins (both
+        None), for light_groups_relamp_resident and spectral_project_resident."""
+        entry = self._resident_entry("render_light_groups_spectral")
+        ids = np.ascontiguousarray(instance_group, dtype=np.uint8).reshape(-1)
+        G = int(groups) if groups is not None else int(max([int(environment_group)] + [int(i) for i in ids])) + 1
+        gd = LightGroupsDesc(G, ids.size, ids.ctypes.data_as(C.POINTER(C.c_uint8)), int(environment_group))
+        sd = SpectralDesc(bins)
+        B = max(int(bins), 0)
+        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        group_films = np.zeros((max(G, 0), rd.height, rd.width, 4), dtype=np.float32) if read_groups else None
+        spectral = np.zeros((B, rd.height, rd.width), dtype=np.float32) if read_bins else None
+        group_spectral = np.zeros((max(G, 0), B, rd.height, rd.width), dtype=np.float32) if read_bins else None
+        prof = Profile()
+        self.library._light_groups_spectral_check(entry(self.handle, C.byref(rd), C.byref(gd), C.byref(sd), _fp(film), _fp(group_films) if read_groups else None,
+                                                        _fp(spectral) if read_bins else None, _fp(group_spectral) if read_bins else None, C.byref(prof)))
+        return film, group_films, spectral, group_spectral, prof
+
+    def light_groups_spectral_resident(self):
+        """pt_light_groups_spectral_resident: (width, height, groups, bins) of the group bins the last successful render_light_groups_spectral left on the device, or
+        None (any other group render ends them)."""
+        entry = self._resident_entry("light_groups_spectral_resident")
+        w, h, g, b = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self.library._light_groups_spectral_check(entry(self.handle, C.byref(w), C.byref(h), C.byref(g), C.byref(b)))
+        return (w.value, h.value, g.value, b.value) if g.value else None
+
+    def light_groups_relamp_resident(self, matrix):
+        """pt_light_groups_relamp_resident: Library.light_groups_relamp of the resident group bins with matrix [K,G,B] — float32 [K,H,W], bit for bit what the
+        host-array entry gives for the bins render_light_groups_spectral returned; only the matrix goes up and K planes come back."""
+        entry = self._resident_entry("light_groups_relamp_resident")
+        res = self.light_groups_spectral_resident()
+        if res is None:
+            w = h = G = B = 0
+        else:
+            w, h, G, B = res
+        matrix = np.ascontiguousarray(matrix, dtype=np.float32)
+        if res is not None and (matrix.ndim != 3 or matrix.shape[1:] != (G, B)):
+            raise ValueError("matrix [K,%d,%d] for the resident group bins" % (G, B))
+        K = matrix.shape[0] if matrix.ndim else 0
+        out = np.zeros((K, h, w), np.float32)
+        self.library._light_groups_spectral_check(entry(self.handle, K, _fp(matrix), _fp(out) if out.size else _fp(np.zeros(1, np.float32))))
+        return out
 
     def render_adaptive_light_groups(self, rd, max_samples, rel_error, instance_group, environment_group=0, groups=None, abs_error=0.0, step=0, stats=False, read_groups=True):
         """pt_render_adaptive_light_groups: (film, counts[, stats], group_films, profile) — film, counts and stats are render_adaptive's bit for bit; group_films

@@ -8,6 +8,7 @@
 //         [--denoise-light-groups instance|material]
 //         [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK] [--denoise-resident]
 //         [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]
+//         [--relamp-groups instance|material --relamp-bins B [--relamp G:CURVE[,G:CURVE...]] [--relamp-gains g0,g1,...] [--develop-subsamples N]]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -59,6 +60,15 @@
 // are: the film is the total.  --light-gains G0,G1,... (with --light-groups only, one gain per group) also writes <filename>_relit.exr / .png: the group films
 // times their gains, mixed where the render left them on the device (pt_light_groups_mix_resident).  Refused together with --adaptive, --denoise, --spectral-bins,
 // --denoise-spectral-bins, --devices, --spectral-devices and --hero-wavelengths.
+// --relamp-groups instance|material --relamp-bins B renders every setting through pt_render_light_groups_spectral (include/pt_light_groups_spectral.h; groups formed as
+// --light-groups forms them) and also writes <filename>_light<g>_spectral.exr, group g's B wavelength bins (pt_write_exr_spectral, in the units of the EXR payload), and
+// <filename>_relamped.exr / .png: the colour-matching development of the re-lamped group bins, made where the render left them on the device
+// (pt_light_groups_relamp_matrix, pt_light_groups_relamp_resident) and sent through the setting's own film output.  --relamp G:CURVE[,G:CURVE...] shows group G under
+// CURVE, a name of the scene file's curves library, in the place of the emission curve its emitters share; --relamp-gains g0,g1,... scales the groups (one gain per
+// group); --develop-subsamples N integrates over each bin with N samples.  Without --relamp and --relamp-gains the re-lamped picture is the development of the render
+// as it is.  A re-lamped group whose emitters do not share one emission curve, and a re-lamped environment lit by an HDR texture, end the program before anything is
+// rendered.  Every usual file stays byte for byte what it is.  Refused together with --adaptive, --denoise, --light-groups, --spectral-bins, --denoise-spectral-bins,
+// --devices, --spectral-devices and --hero-wavelengths.
 // --denoise-light-groups instance|material (with --denoise only; groups formed as --light-groups forms them) renders every setting through
 // pt_render_adaptive_light_groups (include/pt_light_groups_denoise.h) and filters the film and its group films together where the render left them
 // (pt_resident_guides, pt_denoise_light_groups_resident), honouring --demodulate-albedo, --guide-chain and --guide-samples; --denoise-resident is accepted and
@@ -79,6 +89,7 @@
 #include "../../../include/pt_denoise.h"
 #include "../../../include/pt_light_groups.h"
 #include "../../../include/pt_light_groups_denoise.h"
+#include "../../../include/pt_light_groups_spectral.h"
 #include "../../../include/pt_scene_file.h"
 #include "../../../include/pt_resident.h"
 #include "../../../include/pt_spectral.h"
@@ -115,6 +126,11 @@ struct Options {
     bool has_light_gains = false; // --light-gains: <filename>_relit.* from the resident mix
     int denoise_groups = 0;       // --denoise-light-groups: the adaptive group render and the joint filter over the group films; 1 | 2 as light_groups, 0 = off
     std::vector<float> light_gains;
+    int relamp_groups = 0;        // --relamp-groups: the spectral group render and the re-lamped picture; 1 | 2 as light_groups, 0 = off
+    uint32_t relamp_bins = 0;     // --relamp-bins B
+    bool has_relamp = false, has_relamp_gains = false;
+    std::vector<std::pair<uint32_t, std::string>> relamp;   // --relamp G:CURVE,...
+    std::vector<float> relamp_gains;                        // --relamp-gains
     bool assemble = false;        // --denoise-assemble: the node render assembled on the scene's device, then as `resident` (pt_resident_assemble)
 };
 
@@ -126,7 +142,9 @@ int usage(const char* msg) {
                     "             [--spectral-bins B] [--denoise-spectral-bins B] [--demodulate-bins]\n"
                     "             [--denoise-light-groups instance|material]\n"
                     "             [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK]\n"
-                    "             [--denoise-resident] [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]\n");
+                    "             [--denoise-resident] [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]\n"
+                    "             [--relamp-groups instance|material --relamp-bins B [--relamp G:CURVE[,G:CURVE...]] [--relamp-gains g0,g1,...]\n"
+                    "              [--develop-subsamples N]]\n");
     return 2;
 }
 
@@ -253,6 +271,54 @@ int main(int argc, char** argv) {
             o.light_groups = v == "instance" ? 1 : v == "material" ? 2 : 0;
             if (!o.light_groups) return usage("--light-groups needs `instance` or `material`");
         }
+        else if (a == "--relamp-groups") {
+            if (!value(&v)) return usage("--relamp-groups needs a value");
+            o.relamp_groups = v == "instance" ? 1 : v == "material" ? 2 : 0;
+            if (!o.relamp_groups) return usage("--relamp-groups needs `instance` or `material`");
+        }
+        else if (a == "--relamp-bins") {
+            if (!value(&v)) return usage("--relamp-bins needs a value");
+            char* end = nullptr;
+            const unsigned long b = strtoul(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end || b == 0 || b > PT_SPECTRAL_MAX_BINS) return usage("--relamp-bins needs a count in 1..64");
+            o.relamp_bins = (uint32_t)b;
+        }
+        else if (a == "--relamp") {
+            if (!value(&v)) return usage("--relamp needs a value");
+            o.has_relamp = true;
+            o.relamp.clear();
+            size_t p = 0;
+            while (true) {
+                const size_t c = v.find(',', p);
+                const std::string item = v.substr(p, c == std::string::npos ? std::string::npos : c - p);
+                const size_t colon = item.find(':');
+                char* end = nullptr;
+                const unsigned long g = strtoul(item.c_str(), &end, 10);
+                if (colon == std::string::npos || colon == 0 || end != item.c_str() + colon || colon + 1 >= item.size() || g >= PT_LIGHT_GROUPS_MAX)
+                    return usage("--relamp needs G:CURVE[,G:CURVE...] with G a group in 0..7");
+                for (const auto& have : o.relamp) if (have.first == (uint32_t)g) return usage("--relamp names a group twice");
+                o.relamp.push_back({(uint32_t)g, item.substr(colon + 1)});
+                if (c == std::string::npos) break;
+                p = c + 1;
+            }
+        }
+        else if (a == "--relamp-gains") {
+            if (!value(&v)) return usage("--relamp-gains needs a value");
+            o.has_relamp_gains = true;
+            o.relamp_gains.clear();
+            size_t p = 0;
+            while (true) {
+                const size_t c = v.find(',', p);
+                const std::string item = v.substr(p, c == std::string::npos ? std::string::npos : c - p);
+                char* end = nullptr;
+                const float g = strtof(item.c_str(), &end);
+                if (item.empty() || end == item.c_str() || *end || !(g > -1e30f && g < 1e30f)) return usage("--relamp-gains needs finite gains g0,g1,...");
+                o.relamp_gains.push_back(g);
+                if (c == std::string::npos) break;
+                p = c + 1;
+            }
+            if (o.relamp_gains.size() > PT_LIGHT_GROUPS_MAX) return usage("--relamp-gains takes at most 8 gains");
+        }
         else if (a == "--denoise-light-groups") {
             if (!value(&v)) return usage("--denoise-light-groups needs a value");
             o.denoise_groups = v == "instance" ? 1 : v == "material" ? 2 : 0;
@@ -276,6 +342,17 @@ int main(int argc, char** argv) {
         }
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
+    }
+    if (o.relamp_groups) {
+        const char* with = o.adaptive >= 0.0f ? "--adaptive" : o.denoise ? "--denoise" : o.light_groups ? "--light-groups" : o.spectral_bins ? "--spectral-bins"
+                         : o.denoise_bins ? "--denoise-spectral-bins" : o.multi ? "--devices" : o.spectral_multi ? "--spectral-devices" : o.hero ? "--hero-wavelengths" : nullptr;
+        static std::string refusal;
+        if (with) { refusal = std::string("--relamp-groups cannot be combined with ") + with + ": a spectral group render is one plain render of one wavelength per path on one device"; return usage(refusal.c_str()); }
+        if (!o.relamp_bins) return usage("--relamp-groups needs --relamp-bins");
+    } else {
+        if (o.relamp_bins) return usage("--relamp-bins needs --relamp-groups");
+        if (o.has_relamp) return usage("--relamp needs --relamp-groups");
+        if (o.has_relamp_gains) return usage("--relamp-gains needs --relamp-groups");
     }
     if (o.denoise_groups) {
         const char* with = o.light_groups ? "--light-groups" : o.spectral_bins ? "--spectral-bins" : o.denoise_bins ? "--denoise-spectral-bins" : o.multi ? "--devices"
@@ -311,7 +388,7 @@ int main(int argc, char** argv) {
     if (o.denoise_bins && o.multi && o.device_mask != 1) return usage("--denoise-spectral-bins renders on device 0: --devices may name that device alone");
     if (o.develop && !o.spectral_bins && !o.denoise_bins) return usage("--develop needs --spectral-bins or --denoise-spectral-bins: it develops their bins");
     if (o.has_develop_filter && !o.develop) return usage("--develop-filter needs --develop");
-    if (o.has_develop_subsamples && !o.develop) return usage("--develop-subsamples needs --develop");
+    if (o.has_develop_subsamples && !o.develop && !o.relamp_groups) return usage("--develop-subsamples needs --develop");
     if (o.spectral_multi && !o.spectral_bins && !o.denoise_bins) return usage("--spectral-devices needs --spectral-bins or --denoise-spectral-bins: it names the devices their spectral film is rendered on");
     if (o.spectral_multi && o.multi) return usage("--spectral-devices cannot be combined with --devices: a spectral render takes its devices from --spectral-devices alone");
     if (o.assemble && o.resident) return usage("--denoise-assemble cannot be combined with --denoise-resident: that flag is the one-device form, this one assembles a node render");
@@ -365,8 +442,8 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> instance_group(desc->instance_count, 0);
     pt_light_groups_desc gd;
     memset(&gd, 0, sizeof(gd));
-    const int group_mode = o.light_groups ? o.light_groups : o.denoise_groups;
-    const char* group_flag = o.light_groups ? "--light-groups" : "--denoise-light-groups";
+    const int group_mode = o.light_groups ? o.light_groups : o.denoise_groups ? o.denoise_groups : o.relamp_groups;
+    const char* group_flag = o.light_groups ? "--light-groups" : o.denoise_groups ? "--denoise-light-groups" : "--relamp-groups";
     if (group_mode) {
         std::vector<uint32_t> keys;   // a group's key: the instance (mode 1) or the packed light material (mode 2)
         uint32_t groups = 0;
@@ -403,6 +480,55 @@ int main(int argc, char** argv) {
         }
         gd.group_count = groups; gd.instance_count = desc->instance_count; gd.instance_group = instance_group.data();
         printf("light groups: %u (%s%s)\n", groups, group_mode == 1 ? "one per emitting instance" : "one per light material", env_emits ? ", the environment last" : "");
+    }
+
+    // --relamp-groups: the curves of pt_light_groups_relamp_matrix — the scene's own, where a group's old curve is, and behind them the new ones from the curves
+    // library of the scene file — and per group the old and the new curve
+    std::vector<pt_curve> relamp_curves;
+    std::vector<float> relamp_data;
+    std::vector<int32_t> relamp_old(PT_LIGHT_GROUPS_MAX, PT_RELAMP_KEEP), relamp_new(PT_LIGHT_GROUPS_MAX, PT_RELAMP_KEEP);
+    if (o.relamp_groups) {
+        const auto refuse = [&](const std::string& why) {
+            fprintf(stderr, "error: --relamp-groups: %s\n", why.c_str());
+            pt_scene_file_free(scene_file);
+            pt_config_free(config);
+            return 1;
+        };
+        if (o.has_relamp_gains && o.relamp_gains.size() != gd.group_count) return refuse("--relamp-gains needs one gain per group (" + std::to_string(gd.group_count) + " groups)");
+        relamp_curves.assign(desc->curves, desc->curves + desc->curve_count);
+        relamp_data.assign(desc->curve_data, desc->curve_data + desc->curve_data_count);
+        const bool env_emits = desc->environment.strength != 0.0f;
+        for (const auto& item : o.relamp) {
+            const uint32_t g = item.first;
+            if (g >= gd.group_count) return refuse("--relamp names group " + std::to_string(g) + ", the scene has " + std::to_string(gd.group_count) + " groups");
+            // the emission curve the group's emitters share: every light material of its instances, and the environment's curve when it is the environment's group
+            int32_t old = -1;
+            bool mixed = false, any = false;
+            const auto emitter = [&](int32_t curve) { mixed = mixed || (any && curve != old); old = curve; any = true; };
+            if (env_emits && gd.environment_group == g) {
+                if (desc->environment.kind == PT_ENV_HDR)
+                    return refuse("--relamp names group " + std::to_string(g) + ", the environment, which an HDR texture lights: it has no single emission curve to replace");
+                emitter(desc->environment.curve);
+            }
+            for (uint32_t i = 0; i < desc->instance_count; ++i) {
+                if (instance_group[i] != g) continue;
+                const pt_instance& in = desc->instances[i];
+                const auto light = [&](uint32_t id) { if (PT_MATERIAL_TAG(id) == PT_TAG_LIGHT && PT_MATERIAL_INDEX(id) < desc->material_count) emitter(desc->materials[PT_MATERIAL_INDEX(id)].curve_emit); };
+                if (in.material != PT_MATERIAL_NONE) light(in.material);
+                else if (in.kind == PT_SHAPE_MESH && in.mesh >= 0 && (uint32_t)in.mesh < desc->mesh_count && desc->meshes[in.mesh].face_material_offset >= 0) {
+                    const pt_mesh& m = desc->meshes[in.mesh];
+                    for (uint32_t f = 0; f < m.face_count; ++f) light(desc->face_materials[(size_t)m.face_material_offset + f]);
+                }
+            }
+            if (!any) return refuse("--relamp names group " + std::to_string(g) + ", which holds no emitter");
+            if (mixed) return refuse("--relamp names group " + std::to_string(g) + ", whose emitters have different emission curves: it has no single curve to replace");
+            pt_curve c; const float* data = nullptr; uint32_t floats = 0;
+            if (pt_scene_file_library_curve(scene_file, item.second.c_str(), &c, &data, &floats) != PT_OK) return refuse(std::string("--relamp: ") + pt_scene_file_last_error());
+            c.data_offset = (uint32_t)relamp_data.size();
+            relamp_data.insert(relamp_data.end(), data, data + floats);
+            relamp_old[g] = old; relamp_new[g] = (int32_t)relamp_curves.size();
+            relamp_curves.push_back(c);
+        }
     }
 
     // --denoise: what the adaptive path refuses is refused here, with its message, before anything is rendered or written
@@ -467,6 +593,7 @@ int main(int argc, char** argv) {
             std::vector<double> stats(o.denoise ? (size_t)rd.width * rd.height * 2 : 0);
             std::vector<float> spectral((size_t)o.denoise_bins * rd.width * rd.height);   // (--spectral-bins sizes it below)
             std::vector<float> group_films;   // (--light-groups sizes it below)
+            std::vector<float> group_bins;    // (--relamp-groups sizes it below)
             const pt_spectral_desc dsd = {o.denoise_bins, {0u, 0u, 0u}};
             const char* adaptive_entry = o.denoise_bins ? (o.spectral_multi ? "pt_render_adaptive_spectral_multi" : "pt_render_adaptive_spectral")
                                          : o.denoise_groups ? "pt_render_adaptive_light_groups" : o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive";
@@ -508,6 +635,14 @@ int main(int argc, char** argv) {
                 const pt_status st = o.spectral_multi ? pt_render_spectral_multi(scene, &rd, &sd, o.spectral_device_mask, film.data(), spectral.data(), &prof)
                                                       : pt_render_spectral(scene, &rd, &sd, film.data(), spectral.data(), &prof);
                 if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.spectral_multi ? "pt_render_spectral_multi" : "pt_render_spectral", pt_last_error()); rc = 1; break; }
+            } else if (o.relamp_groups) {
+                printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u, %u light groups of %u bins\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples,
+                       gd.group_count, o.relamp_bins);
+                group_bins.resize((size_t)gd.group_count * o.relamp_bins * rd.width * rd.height);
+                const pt_spectral_desc sd = {o.relamp_bins, {0u, 0u, 0u}};
+                if (pt_render_light_groups_spectral(scene, &rd, &gd, &sd, film.data(), nullptr, nullptr, group_bins.data(), &prof) != PT_OK) {
+                    fprintf(stderr, "pt_render_light_groups_spectral: %s\n", pt_last_error()); rc = 1; break;
+                }
             } else if (o.light_groups) {
                 printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u, %u light groups\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples, gd.group_count);
                 group_films.resize((size_t)gd.group_count * rd.width * rd.height * 4);
@@ -559,7 +694,36 @@ int main(int argc, char** argv) {
                 if (!ok) fprintf(stderr, "%s: %s\n", group_flag, pt_last_error());
                 return ok;
             };
-            if (group_mode && !write_groups(base, group_films, false)) { rc = 1; break; }
+            if (group_mode && !o.relamp_groups && !write_groups(base, group_films, false)) { rc = 1; break; }
+            // --relamp-groups: every group's bins in the units of the EXR payload, and the re-lamped picture — the colour-matching development of the group bins by
+            // the re-lamp matrix, where the render left them on the device — through this setting's film output (buffers of its own)
+            if (o.relamp_groups) {
+                const size_t np = (size_t)rd.width * rd.height, plane = (size_t)o.relamp_bins * np;
+                const pt_spectral_desc sd = {o.relamp_bins, {0u, 0u, 0u}};
+                std::vector<float> centres(o.relamp_bins), scaled(plane), matrix((size_t)3 * gd.group_count * o.relamp_bins), planes(3 * np), packed(4 * np), r_linear(3 * np);
+                std::vector<uint8_t> r_rgba(4 * np);
+                bool ok = pt_spectral_bin_centres(&rd, &sd, centres.data()) == PT_OK;
+                for (uint32_t g = 0; ok && g < gd.group_count; ++g) {
+                    const std::string name = base + "_light" + std::to_string(g) + "_spectral";
+                    for (size_t k = 0; k < plane; ++k) scaled[k] = group_bins[plane * g + k] * od.factor;
+                    ok = pt_write_exr_spectral((name + ".exr").c_str(), rd.width, rd.height, o.relamp_bins, centres.data(), scaled.data(), nullptr, od.colorspace) == PT_OK;
+                    if (ok) printf("wrote %s.exr (%u bins)\n", name.c_str(), o.relamp_bins);
+                }
+                const int32_t cie[3] = {PT_RESPONSE_CIE_X, PT_RESPONSE_CIE_Y, PT_RESPONSE_CIE_Z};
+                ok = ok && pt_light_groups_relamp_matrix(&rd, &sd, relamp_curves.data(), (uint32_t)relamp_curves.size(), relamp_data.data(), (uint32_t)relamp_data.size(), 3, cie,
+                                                         PT_SPECTRAL_NO_FILTER, o.develop_subsamples, gd.group_count, relamp_old.data(), relamp_new.data(),
+                                                         o.has_relamp_gains ? o.relamp_gains.data() : nullptr, matrix.data()) == PT_OK &&
+                     pt_light_groups_relamp_resident(scene, 3, matrix.data(), planes.data()) == PT_OK;
+                if (ok) {
+                    for (size_t p = 0; p < np; ++p) { packed[4 * p] = planes[p]; packed[4 * p + 1] = planes[np + p]; packed[4 * p + 2] = planes[2 * np + p]; packed[4 * p + 3] = 0.0f; }
+                    const std::string name = base + "_relamped";
+                    ok = pt_output_film(&od, packed.data(), r_rgba.data(), r_linear.data()) == PT_OK &&
+                         pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, r_linear.data(), od.colorspace) == PT_OK &&
+                         pt_write_png((name + ".png").c_str(), rd.width, rd.height, r_rgba.data(), od.colorspace) == PT_OK;
+                    if (ok) printf("wrote %s.exr and %s.png (re-lamped from %u light groups of %u bins)\n", name.c_str(), name.c_str(), gd.group_count, o.relamp_bins);
+                }
+                if (!ok) { fprintf(stderr, "--relamp-groups: %s\n", pt_last_error()); rc = 1; break; }
+            }
             // the bins in the units of the EXR payload: the same factor, applied here in place, one multiply per value
             const uint32_t file_bins = o.spectral_bins ? o.spectral_bins : o.denoise_bins;
             const auto write_spectral = [&](const std::string& name, std::vector<float>& scaled) {

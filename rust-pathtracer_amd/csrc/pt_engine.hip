@@ -30,8 +30,10 @@
 #include "../../include/pt_denoise.h"
 #include "../../include/pt_light_groups.h"
 #include "../../include/pt_light_groups_denoise.h"
+#include "../../include/pt_light_groups_spectral.h"
 #include "pt_adaptive_select.h"
 #include "pt_light_groups_launch.h"
+#include "pt_light_groups_spectral_launch.h"
 #include "pt_spectral_launch.h"
 #include "pt_spectral_rules.h"
 #include "pt_spectral_project_launch.h"
@@ -369,6 +371,13 @@ struct pt_scene {
     bool groups_valid = false;
     uint32_t groups_width = 0, groups_height = 0, groups_count = 0;
     GrowBuf group_films_cache, group_table, group_mix_cache;
+    // The resident group bins (include/pt_light_groups_spectral.h): what the last successful pt_render_light_groups_spectral left in group_bins_cache, group-major, then
+    // bin-major planes of width * height floats.  Cleared when a group render of any kind starts (the other two leave none) and set when that render has succeeded;
+    // it is the only writer of the buffer.  relamp_cache: pt_light_groups_relamp_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x 512 floats) and, behind it,
+    // its output planes.
+    bool group_bins_valid = false;
+    uint32_t group_bins_width = 0, group_bins_height = 0, group_bins_groups = 0, group_bins_bins = 0;
+    GrowBuf group_bins_cache, relamp_cache;
     // include/pt_light_groups_denoise.h.  groups_paired: the group films and the resident FILM came from one render (pt_render_adaptive_light_groups); ended where the
     // resident film is ended or replaced and where another group render starts.  groups_denoised: pt_denoise_light_groups_resident has left denoised group films in
     // group_den_films (of groups_width x groups_height x groups_count, beside its film and variance in group_den_film / group_den_var: pt_denoise_resident's
@@ -596,6 +605,9 @@ struct RenderJob {
     // float4 — the render takes the general vertex and light-sample forms that route energy to the groups' planes, and every pass adds each plane to its film
     const LightGroupTable* groups = nullptr;
     float* d_group_films = nullptr;
+    // pt_render_light_groups_spectral (include/pt_light_groups_spectral.h): with groups and d_spectral, group_count * spectral_bins planes of width * height floats —
+    // every pass also adds each group's plane to that group's bins
+    float* d_group_bins = nullptr;
 };
 
 // What plan_render chooses for a render: the queues' size, the kernel forms and their launch configuration.
@@ -818,6 +830,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     HIP_TRY(hipMemsetAsync(d_film, 0, sizeof(float) * 4 * (size_t)rd.width * rd.height, stream));
     if (job.d_spectral) HIP_TRY(hipMemsetAsync(job.d_spectral, 0, sizeof(float) * (size_t)job.spectral_bins * rd.width * rd.height, stream));
     if (job.groups) HIP_TRY(hipMemsetAsync(job.d_group_films, 0, sizeof(float) * 4 * (size_t)group_count * rd.width * rd.height, stream));
+    if (job.d_group_bins) HIP_TRY(hipMemsetAsync(job.d_group_bins, 0, sizeof(float) * (size_t)group_count * job.spectral_bins * rd.width * rd.height, stream));
     HIP_TRY(hipMemsetAsync(b.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));
     if (overlap) HIP_TRY(hipMemsetAsync(sc->buf2.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));   // (in front of the fork event)
 
@@ -878,7 +891,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     };
 
     uint64_t camera_rays = 0, accumulated_pixels = 0;
-    hipError_t spectral_error = hipSuccess, groups_error = hipSuccess;
+    hipError_t spectral_error = hipSuccess, groups_error = hipSuccess, group_bins_error = hipSuccess;
     bool overlapped = false;   // some pass loop of this render ran passes on both lanes
     const std::vector<hipEvent_t>& dep = sc->pass_deps;
     const uint32_t skew_code = (tn.flags >> PT_TUNE_PASS_SKEW_SHIFT) & PT_TUNE_PASS_SKEW_MASK;
@@ -961,7 +974,10 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                     spectral_error = ptk::launch_accumulate_spectral(hero ? 4 : 1, grid, stream, rp, d_px, b.energy, job.d_spectral, job.spectral_bins, rd.width * rd.height);
                 if (job.groups && groups_error == hipSuccess)
                     groups_error = ptk::launch_accumulate_groups(stream, rp, d_px, b.energy, job.d_group_films, group_count, (size_t)rd.width * rd.height);
+                if (job.d_group_bins && group_bins_error == hipSuccess)
+                    group_bins_error = ptk::launch_accumulate_group_bins(stream, rp, d_px, b.energy, job.d_group_bins, group_count, job.spectral_bins, rd.width * rd.height);
             });
+            if (group_bins_error != hipSuccess) return fail(PT_ERR_DEVICE, std::string("k_accumulate_group_bins: ") + hipGetErrorString(group_bins_error));
             if (groups_error != hipSuccess) return fail(PT_ERR_DEVICE, std::string("k_accumulate_groups: ") + hipGetErrorString(groups_error));
             if (spectral_error != hipSuccess) return fail(PT_ERR_DEVICE, std::string("k_accumulate_spectral: ") + hipGetErrorString(spectral_error));
             if (two_lanes) HIP_TRY(hipEventRecord(dep[DEP_ACCUMULATED + (p & 1)], stream));
@@ -1183,6 +1199,8 @@ struct RenderCall {
     float* spectral = nullptr;              // the spectral entries
     const pt_light_groups_desc* gd = nullptr;   // pt_render_light_groups; group_films: where the caller wants them (may be null)
     float* group_films = nullptr;
+    bool group_bins = false;                // pt_render_light_groups_spectral (gd and sd): the group bins too; group_spectral: where the caller wants them (may be null)
+    float* group_spectral = nullptr;
 };
 
 // The body of the five one-device entries: the device, the film and the planes kept with the scene, render_impl on the null stream, the read-backs and the resident
@@ -1191,7 +1209,7 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
     const pt_render_desc& rd = *call.rd;
     forget_node_render(sc);
     if (call.sd) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts: whatever the buffer held is no film from here on)
-    if (call.gd) { sc->groups_valid = false; sc->groups_denoised = false; }   // (likewise the group films, and the denoised ones that came from them)
+    if (call.gd) { sc->groups_valid = false; sc->groups_denoised = false; sc->group_bins_valid = false; }   // (likewise the group films, the denoised ones that came from them, and the group bins)
     sc->groups_paired = false;   // (the resident film ends below)
     sc->resident.end();   // (film_cache and the adaptive buffers are written from here on; guides and denoised outputs belonged to the film before)
     HIP_TRY(hipSetDevice(sc->device));
@@ -1202,6 +1220,15 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
     if (st == PT_OK && call.gd) st = sc->group_films_cache.reserve(group_bytes);
     if (st == PT_OK && call.gd) st = sc->group_table.reserve(call.gd->instance_count ? call.gd->instance_count : 1u);
     if (st != PT_OK) return st;
+    const size_t group_bins_bytes = call.group_bins ? spectral_bytes * call.gd->group_count : 0;
+    const pt_status bins_reserved = call.group_bins ? sc->group_bins_cache.reserve(group_bins_bytes) : PT_OK;
+    if (bins_reserved != PT_OK) (void)hipGetLastError();   // (the refused reservation is no error of a later launch: the scene stays usable)
+    if (bins_reserved != PT_OK && bins_reserved != PT_ERR_OUT_OF_MEMORY) return bins_reserved;
+    if (bins_reserved == PT_ERR_OUT_OF_MEMORY) {
+        return fail(PT_ERR_OUT_OF_MEMORY, "the group bins need group_count x bins x width x height x 4 = " + std::to_string(call.gd->group_count) + " x " + std::to_string(call.sd->bins) +
+                                              " x " + std::to_string(rd.width) + " x " + std::to_string(rd.height) + " x 4 = " + std::to_string(group_bins_bytes) +
+                                              " bytes of device memory, which could not be reserved");
+    }
     RenderJob job;
     job.adaptive = call.ad;
     LightGroupTable table{sc->group_table.as<uint8_t>(), call.gd ? call.gd->environment_group : 0u, call.gd ? call.gd->group_count : 0u};
@@ -1210,6 +1237,7 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
         job.groups = &table; job.d_group_films = sc->group_films_cache.as<float>();
     }
     if (call.sd) { job.d_spectral = sc->spectral_cache.as<float>(); job.spectral_bins = call.sd->bins; }
+    if (call.group_bins) job.d_group_bins = sc->group_bins_cache.as<float>();
     const hipStream_t stream = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     st = render_impl(sc, &rd, sc->film_cache.as<float>(), stream, profile, job);
@@ -1219,7 +1247,12 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
         HIP_TRY(hipMemcpy(call.sample_counts, sc->adaptive.counts, sizeof(uint32_t) * n_pixels, hipMemcpyDeviceToHost));
         if (call.stats) HIP_TRY(hipMemcpy(call.stats, sc->adaptive.stats, sizeof(double) * 2 * n_pixels, hipMemcpyDeviceToHost));
     }
-    if (call.sd) HIP_TRY(hipMemcpy(call.spectral, sc->spectral_cache.p, spectral_bytes, hipMemcpyDeviceToHost));
+    if (call.sd && call.spectral) HIP_TRY(hipMemcpy(call.spectral, sc->spectral_cache.p, spectral_bytes, hipMemcpyDeviceToHost));
+    if (call.group_bins && call.group_spectral) HIP_TRY(hipMemcpy(call.group_spectral, sc->group_bins_cache.p, group_bins_bytes, hipMemcpyDeviceToHost));
+    if (call.group_bins) {
+        sc->group_bins_width = rd.width; sc->group_bins_height = rd.height; sc->group_bins_groups = call.gd->group_count; sc->group_bins_bins = call.sd->bins;
+        sc->group_bins_valid = true;
+    }
     if (call.gd && call.group_films) HIP_TRY(hipMemcpy(call.group_films, sc->group_films_cache.p, group_bytes, hipMemcpyDeviceToHost));
     if (call.gd) { sc->groups_width = rd.width; sc->groups_height = rd.height; sc->groups_count = call.gd->group_count; sc->groups_valid = true; }
     if (call.gd && call.ad) sc->groups_paired = true;   // (the resident film set below and the group films came from this one render)
@@ -1305,6 +1338,53 @@ pt_status pt_render_adaptive_light_groups(pt_scene* sc, const pt_render_desc* rd
     RenderCall call;
     call.rd = &rd; call.ad = &ad; call.gd = gdp; call.film = film; call.sample_counts = sample_counts; call.stats = stats; call.group_films = group_films;
     return render_one(sc, call, profile);
+}
+
+// include/pt_light_groups_spectral.h: a group render with a spectral desc beside its groups desc — the total bins as pt_render_spectral makes them, and every
+// group's own (k_accumulate_group_bins)
+pt_status pt_render_light_groups_spectral(pt_scene* sc, const pt_render_desc* rdp, const pt_light_groups_desc* gdp, const pt_spectral_desc* sdp, float* film,
+                                          float* group_films, float* spectral, float* group_spectral, pt_profile* profile) {
+    forget_node_render(sc);
+    std::string err;
+    const pt_status st = pth::check_light_groups_spectral_args(sc, rdp, gdp, sdp, sc ? sc->host.blob[PT_HDR_INSTANCE_COUNT] : 0u, film, &err);
+    if (st != PT_OK) return fail(st, err);
+    RenderCall call;
+    call.rd = rdp; call.gd = gdp; call.sd = sdp; call.film = film; call.group_films = group_films; call.spectral = spectral;
+    call.group_bins = true; call.group_spectral = group_spectral;
+    return render_one(sc, call, profile);
+}
+
+pt_status pt_light_groups_spectral_resident(pt_scene* sc, uint32_t* width, uint32_t* height, uint32_t* group_count, uint32_t* bins) {
+    if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
+    if (!width || !height || !group_count || !bins) return fail(PT_ERR_INVALID_ARGUMENT, "width, height, group_count or bins is null");
+    const bool v = sc->group_bins_valid;
+    *width = v ? sc->group_bins_width : 0u; *height = v ? sc->group_bins_height : 0u; *group_count = v ? sc->group_bins_groups : 0u; *bins = v ? sc->group_bins_bins : 0u;
+    return PT_OK;
+}
+
+// pt_light_groups_relamp's kernel over group_bins_cache, on the stream the render ran on (the null stream): the matrix goes up, K planes come back
+pt_status pt_light_groups_relamp_resident(pt_scene* sc, uint32_t K, const float* matrix, float* out) {
+    if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
+    if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "the re-lamped planes (out) are null");
+    if (!sc->group_bins_valid) return fail(PT_ERR_INVALID_ARGUMENT, "the scene has no resident group bins: pt_render_light_groups_spectral must have succeeded on it");
+    std::string err;
+    const pt_status st = pth::check_relamp_matrix(K, sc->group_bins_groups, sc->group_bins_bins, matrix, &err);
+    if (st != PT_OK) return fail(st, err);
+    HIP_TRY(hipSetDevice(sc->device));
+    const uint32_t planes = sc->group_bins_groups * sc->group_bins_bins;
+    const size_t n_pixels = (size_t)sc->group_bins_width * sc->group_bins_height;
+    const size_t matrix_floats = (size_t)PT_SPECTRAL_MAX_RESPONSES * PT_LIGHT_GROUPS_MAX * PT_SPECTRAL_MAX_BINS;
+    const pt_status cached = sc->relamp_cache.reserve(sizeof(float) * (matrix_floats + (size_t)K * n_pixels));
+    if (cached != PT_OK) return cached;
+    float* d_matrix = sc->relamp_cache.as<float>();
+    float* d_out = d_matrix + matrix_floats;
+    hipStream_t stream = nullptr;
+    HIP_TRY(hipMemcpyAsync(d_matrix, matrix, sizeof(float) * K * planes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ptk::launch_light_groups_relamp(ptk::spectral_project_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, planes, K, d_matrix,
+                                            sc->group_bins_cache.as<float>(), d_out));
+    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(float) * K * n_pixels, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PT_OK;
 }
 
 pt_status pt_light_groups_resident(pt_scene* sc, uint32_t* width, uint32_t* height, uint32_t* group_count) {

@@ -5,6 +5,8 @@
 #include "pt_scene_host.h"
 #include "pt_device.h"
 #include "pt_spectral_project_rules.h"
+#include "pt_light_groups_spectral_rules.h"
+#include "pt_plan.h"
 
 #include <algorithm>
 #include <array>
@@ -480,6 +482,89 @@ bool spectral_response_matrix(float lo, float hi, uint32_t bins, const pt_curve*
     for (uint32_t k = 0; k < K; ++k)
         for (uint32_t b = 0; b < bins; ++b) matrix[(size_t)k * bins + b] = ptd::spectral_matrix_entry(view, off.data(), responses[k], filter, lo, w, b, subsamples);
     return true;
+}
+
+// ---- include/pt_light_groups_spectral.h: the argument checks of its entries, for the engine and the host emulation alike
+pt_status check_light_groups_spectral_args(const void* scene, const pt_render_desc* rd, const pt_light_groups_desc* gd, const pt_spectral_desc* sd, uint32_t scene_instances,
+                                           const void* film, std::string* error) {
+    pt_status st = check_light_groups_args(scene, rd, gd, scene_instances, film, error);
+    if (st != PT_OK) return st;
+    st = check_spectral_desc(sd, error);
+    if (st != PT_OK) return st;
+    if (rd->width == 0 || rd->height == 0 || (uint64_t)rd->width * rd->height > 0x7fffffffull) {
+        *error = "width and height must be positive and width x height must fit 31 bits";
+        return PT_ERR_INVALID_ARGUMENT;
+    }
+    return PT_OK;
+}
+
+pt_status check_relamp_matrix(uint32_t K, uint32_t group_count, uint32_t bins, const float* matrix, std::string* error) {
+    if (!matrix) { *error = "the re-lamp matrix is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (K == 0) { *error = "K must be positive: a re-lamp needs a response"; return PT_ERR_INVALID_ARGUMENT; }
+    if (K > PT_SPECTRAL_MAX_RESPONSES) { *error = "K: at most 16 responses"; return PT_ERR_INVALID_ARGUMENT; }
+    if (group_count == 0 || group_count > PT_LIGHT_GROUPS_MAX) { *error = "group_count must be in 1..8"; return PT_ERR_INVALID_ARGUMENT; }
+    if (bins == 0) { *error = "bins must be positive"; return PT_ERR_INVALID_ARGUMENT; }
+    if (bins > PT_SPECTRAL_MAX_BINS) { *error = "bins: at most 64"; return PT_ERR_INVALID_ARGUMENT; }
+    for (uint32_t i = 0; i < K * group_count * bins; ++i)
+        if (!std::isfinite(matrix[i])) { *error = "re-lamp matrix entry " + std::to_string(i) + " is not finite"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
+pt_status check_relamp_args(uint32_t width, uint32_t height, uint32_t group_count, uint32_t bins, uint32_t K, const float* matrix, const void* group_spectral,
+                            const void* out, std::string* error) {
+    if (!group_spectral) { *error = "the group bins are null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!out) { *error = "the re-lamped planes (out) are null"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = check_relamp_matrix(K, group_count, bins, matrix, error);
+    if (st != PT_OK) return st;
+    if (width == 0 || height == 0) { *error = "width and height must be positive"; return PT_ERR_INVALID_ARGUMENT; }
+    if ((uint64_t)width * (uint64_t)height > 0x7fffffffull) { *error = "width x height must fit 31 bits"; return PT_ERR_INVALID_ARGUMENT; }
+    return PT_OK;
+}
+
+// pt_light_groups_relamp_matrix: pt_spectral_response_matrix's checks, then the groups' own, then the lane code of pt_light_groups_spectral_rules.h on the host
+pt_status light_groups_relamp_matrix(const pt_render_desc* rd, const pt_spectral_desc* sd, const pt_curve* curves, uint32_t curve_count, const float* curve_data,
+                                     uint32_t curve_data_floats, uint32_t K, const int32_t* responses, int32_t filter, uint32_t subsamples, uint32_t group_count,
+                                     const int32_t* old_curve, const int32_t* new_curve, const float* gain, float* matrix, std::string* error) {
+    const pt_status st = check_response_matrix_args(rd, sd, curves, curve_count, curve_data, curve_data_floats, K, responses, filter, subsamples, matrix, error);
+    if (st != PT_OK) return st;
+    if (group_count == 0 || group_count > PT_LIGHT_GROUPS_MAX) { *error = "group_count must be in 1..8"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!old_curve || !new_curve) { *error = "old_curve or new_curve is null"; return PT_ERR_INVALID_ARGUMENT; }
+    for (uint32_t g = 0; g < group_count; ++g) {
+        const int32_t o = old_curve[g], n = new_curve[g];
+        if (o != PT_RELAMP_KEEP && (o < 0 || (uint32_t)o >= curve_count)) {
+            *error = "old_curve of group " + std::to_string(g) + " is neither a curve index nor PT_RELAMP_KEEP";
+            return PT_ERR_INVALID_ARGUMENT;
+        }
+        if (n != PT_RELAMP_KEEP && (n < 0 || (uint32_t)n >= curve_count)) {
+            *error = "new_curve of group " + std::to_string(g) + " is neither a curve index nor PT_RELAMP_KEEP";
+            return PT_ERR_INVALID_ARGUMENT;
+        }
+        if (n == PT_RELAMP_KEEP && o != PT_RELAMP_KEEP) {
+            *error = "group " + std::to_string(g) + " names an old curve and keeps its lamp: new_curve is PT_RELAMP_KEEP where old_curve is not";
+            return PT_ERR_INVALID_ARGUMENT;
+        }
+        if (gain && !std::isfinite(gain[g])) { *error = "the gain of group " + std::to_string(g) + " is not finite"; return PT_ERR_INVALID_ARGUMENT; }
+    }
+    std::vector<uint32_t> blob, off;
+    if (!build_curve_view(curves, curve_count, curve_data, curve_data_floats, &blob, &off, error)) return PT_ERR_INVALID_ARGUMENT;
+    const float tex = 0.0f;
+    ptd::SceneView view{blob.data(), &tex};
+    const uint32_t bins = sd->bins;
+    const float w = (rd->wavelength_hi - rd->wavelength_lo) / (float)bins;
+    for (uint32_t k = 0; k < K; ++k)
+        for (uint32_t g = 0; g < group_count; ++g) {
+            const int32_t o = old_curve[g], n = o == PT_RELAMP_KEEP ? PT_RELAMP_KEEP : new_curve[g];   // (a kept group's new_curve is not looked at)
+            for (uint32_t b = 0; b < bins; ++b) {
+                const float m = ptd::lg_relamp_matrix_entry(view, off.data(), responses[k], filter, o, n, rd->wavelength_lo, w, b, subsamples);
+                const float v = gain ? gain[g] * m : m;
+                if (!std::isfinite(v)) {
+                    *error = "the re-lamp matrix is not finite at response " + std::to_string(k) + ", group " + std::to_string(g) + ", bin " + std::to_string(b);
+                    return PT_ERR_INVALID_ARGUMENT;
+                }
+                matrix[((size_t)k * group_count + g) * bins + b] = v;
+            }
+        }
+    return PT_OK;
 }
 
 static bool build_host_scene_with(const pt_scene_desc& d, HostScene* hs, std::string* err, bool curve_tables, uint32_t* curve_table_words);

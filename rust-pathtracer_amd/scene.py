@@ -200,6 +200,21 @@ class SceneBuilder:
         idx = [self.curve_names[r] if isinstance(r, str) else int(r) for r in responses]
         return library.spectral_response_matrix(rd, bins, idx, self.curves, self.curve_data, None if filter is None else self.curve_names[filter], subsamples)
 
+    def light_groups_relamp_matrix(self, library, rd, bins, responses, groups, relamp, gain=None, filter=None, subsamples=1):
+        """Library.light_groups_relamp_matrix over this description's curves, by name: `responses` and `filter` as in spectral_response_matrix; `relamp` maps a
+        group to (old curve name, new curve name) — the emission curve its emitters were rendered with and the one to see them under; every other group keeps
+        its lamp.  float32 [K, groups, bins]."""
+        if isinstance(responses, str):
+            if responses != "cie":
+                raise ValueError("responses: \"cie\" or a sequence of curve names / RESPONSE_CIE_* constants")
+            responses = (api.RESPONSE_CIE_X, api.RESPONSE_CIE_Y, api.RESPONSE_CIE_Z)
+        idx = [self.curve_names[r] if isinstance(r, str) else int(r) for r in responses]
+        old, new = [None] * int(groups), [None] * int(groups)
+        for g, (o, n) in dict(relamp).items():
+            old[int(g)], new[int(g)] = self.curve_names[o], self.curve_names[n]
+        return library.light_groups_relamp_matrix(rd, bins, idx, groups, old, new, gain, self.curves, self.curve_data,
+                                                  None if filter is None else self.curve_names[filter], subsamples)
+
     # ---- textures (src/parsing/texture.rs)
     def texstack_texture1(self, name, curve, texels=None):
         t = np.ones((1, 1), np.float32) if texels is None else np.asarray(texels, np.float32)
@@ -682,17 +697,19 @@ def mixed_small():
     return b
 
 
-def light_groups_room(emit=(True, True, True)):
+def light_groups_room(emit=(True, True, True), rect_curve="E5", extra_curves=()):
     """The scene of the light-group tests (not a reference scene): mixed_small's floor, wall and two spheres with three emitters of three
     kinds, each with a material of its own — instance 1 a DiffuseLight rect (E5), instance 2 a SharpLight disk (xenon_x5, sharpness 100) — and a constant
     sky that light samples pick with probability 0.25.  emit[k] False replaces emitter k's emission CURVE (rect, disk, sky) by flat_zero: nothing leaves the
-    scene, no strength changes, and the walk — which never looks at an emission value — is the same."""
+    scene, no strength changes, and the walk — which never looks at an emission value — is the same.  rect_curve: the rect lamp's emission curve by its library
+    name (a re-lamped room, for the same reason the same walk); extra_curves: library curves added behind the scene's own, for a re-lamp matrix to name."""
     b = SceneBuilder()
     add_library_curves(b, ["simple_sky_blue", "flat_zero", "E5", "xenon_x5", "flat_78"])
+    add_library_curves(b, [rect_curve] + list(extra_curves))
     zero = b.curve("flat_zero")
     b.set_environment_constant(b.curve("simple_sky_blue") if emit[2] else zero, 0.3)
     b.env_sampling_probability = 0.25
-    l0 = b.material_diffuse_light("light_groups_l0", b.curve("E5") if emit[0] else zero, b.curve("flat_78"), api.SIDED_DUAL)
+    l0 = b.material_diffuse_light("light_groups_l0", b.curve(rect_curve) if emit[0] else zero, b.curve("flat_78"), api.SIDED_DUAL)
     l1 = b.material_sharp_light("light_groups_l1", b.curve("xenon_x5") if emit[1] else zero, b.curve("flat_78"), 100.0, api.SIDED_DUAL)
     white = add_library_material(b, "lambertian_white")
     red = add_library_material(b, "lambertian_red")

@@ -70,6 +70,9 @@ pt_status pt_resident_load(pt_scene* scene, uint32_t width, uint32_t height, uin
  * staged route for every shard; both give the same bits.  Nothing but the shards' pixel lists crosses a host link, no peer-access setting is changed, the
  * caller's current device is kept and the call has synchronised when it returns.  The parts lie in pt_resident_load's buffers, never in a render's: the
  * undenoised shards still develop where they are (pt_spectral_project_resident).  GUIDES, ALBEDO, BIN_ALBEDO and the denoised parts are resident no longer.
+ * After pt_render_adaptive_light_groups_multi (include/pt_light_groups_multi.h) every device's packed shard of the group films is unpacked the same way, into
+ * the buffer a one-device group render leaves them in, and the group films are resident there and paired with the assembled film, as after
+ * pt_render_adaptive_light_groups: pt_resident_guides, pt_denoise_light_groups_resident and pt_light_groups_mix_resident(_denoised) follow.
  * A repeated call allocates nothing.  Every render entry forgets the node render when it starts: refused after a later render, after a fixed-count node
  * render, after a node render that came down to one device (it left FILM resident itself) and after a failed one. */
 pt_status pt_resident_assemble(pt_scene* scene, uint32_t flags);

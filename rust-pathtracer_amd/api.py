@@ -353,6 +353,12 @@ class Library:
         self._light_groups_mix_resident_denoised = bind("light_groups_mix_resident_denoised", C.c_int32, [vp, fpp, fpp], required=False)
         self._adaptive_light_groups_last_error = bind("adaptive_light_groups_last_error", C.c_char_p, [], required=False)   # (the emulation's)
         self._denoise_light_groups_last_error = bind("denoise_light_groups_last_error", C.c_char_p, [], required=False)   # (the emulation's)
+        # include/pt_light_groups_multi.h
+        self._render_light_groups_multi = bind("render_light_groups_multi", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(LightGroupsDesc), C.c_uint64, fpp, fpp,
+                                                                                        C.POINTER(Profile)], required=False)
+        self._render_adaptive_light_groups_multi = bind("render_adaptive_light_groups_multi", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc),
+                                                                                                          C.POINTER(LightGroupsDesc), C.c_uint64, fpp, C.POINTER(u32),
+                                                                                                          C.POINTER(C.c_double), fpp, C.POINTER(Profile)], required=False)
         # include/pt_resident.h (an emulation library may lack these)
         self._resident_info = bind("resident_info", C.c_int32, [vp, C.POINTER(ResidentInfo)], required=False)
         self._resident_guides = bind("resident_guides", C.c_int32, [vp, C.POINTER(RenderDesc), u32, C.POINTER(GuideChainDesc), u32], required=False)
@@ -788,8 +794,22 @@ class Scene:
         self.library._light_groups_check(entry(self.handle, C.byref(rd), C.byref(gd), _fp(film), _fp(group_films) if read_groups else None, C.byref(prof)))
         return film, group_films, prof
 
+    def render_light_groups_multi(self, rd, instance_group, environment_group=0, groups=None, read_groups=True, device_mask=0):
+        """pt_render_light_groups_multi: render_light_groups on every device of the mask (0 = all) from one blocking call, its outputs bit for bit.  Every device
+        hands over the group films of its own tiles (read_groups False: none of them) and keeps them, packed, as its part of the scene's resident group films."""
+        entry = self._resident_entry("render_light_groups_multi")
+        ids = np.ascontiguousarray(instance_group, dtype=np.uint8).reshape(-1)
+        G = int(groups) if groups is not None else int(max([int(environment_group)] + [int(i) for i in ids])) + 1
+        gd = LightGroupsDesc(G, ids.size, ids.ctypes.data_as(C.POINTER(C.c_uint8)), int(environment_group))
+        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        group_films = np.zeros((max(G, 0), rd.height, rd.width, 4), dtype=np.float32) if read_groups else None
+        prof = Profile()
+        self.library._light_groups_check(entry(self.handle, C.byref(rd), C.byref(gd), C.c_uint64(device_mask), _fp(film), _fp(group_films) if read_groups else None,
+                                               C.byref(prof)))
+        return film, group_films, prof
+
     def light_groups_resident(self):
-        """pt_light_groups_resident: (width, height, groups) of the group films the last successful light-group render left on the device, or None."""
+        """pt_light_groups_resident: (width, height, groups) of the group films the last successful light-group render left on the device(s), or None."""
         entry = self._resident_entry("light_groups_resident")
         w, h, g = C.c_uint32(), C.c_uint32(), C.c_uint32()
         self.library._light_groups_check(entry(self.handle, C.byref(w), C.byref(h), C.byref(g)))
@@ -861,6 +881,26 @@ class Scene:
             raise PtError(status, err().decode() if err else self.library.last_error())
         return (film, counts, st, group_films, prof) if stats else (film, counts, group_films, prof)
 
+    def render_adaptive_light_groups_multi(self, rd, max_samples, rel_error, instance_group, environment_group=0, groups=None, abs_error=0.0, step=0, stats=False,
+                                           read_groups=True, device_mask=0):
+        """pt_render_adaptive_light_groups_multi: render_adaptive_light_groups on every device of the mask (0 = all) from one blocking call, its outputs bit for
+        bit.  Over more than one (virtual) device the group films stay resident as packed shards, paired with no film, until resident_assemble (after a call
+        with stats=True) gathers film and group films on the scene's device."""
+        entry = self._resident_entry("render_adaptive_light_groups_multi")
+        ids = np.ascontiguousarray(instance_group, dtype=np.uint8).reshape(-1)
+        G = int(groups) if groups is not None else int(max([int(environment_group)] + [int(i) for i in ids])) + 1
+        gd = LightGroupsDesc(G, ids.size, ids.ctypes.data_as(C.POINTER(C.c_uint8)), int(environment_group))
+        ad = AdaptiveDesc(max_samples, step, rel_error, abs_error)
+        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
+        counts = np.zeros((rd.height, rd.width), dtype=np.uint32)
+        st = np.zeros((rd.height, rd.width, 2), dtype=np.float64) if stats else None
+        group_films = np.zeros((max(G, 0), rd.height, rd.width, 4), dtype=np.float32) if read_groups else None
+        prof = Profile()
+        status = entry(self.handle, C.byref(rd), C.byref(ad), C.byref(gd), C.c_uint64(device_mask), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                       st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, _fp(group_films) if read_groups else None, C.byref(prof))
+        self.library.check(status)
+        return (film, counts, st, group_films, prof) if stats else (film, counts, group_films, prof)
+
     def light_groups_denoised_resident(self):
         """pt_light_groups_denoised_resident: (width, height, groups) of the denoised group films denoise_light_groups_resident left on the device, or None."""
         entry = self._resident_entry("light_groups_denoised_resident")
@@ -886,12 +926,38 @@ class Scene:
         return got[0] if len(got) == 1 else (got if got else None)
 
     def render_denoised_light_groups(self, rd, instance_group, environment_group=0, groups=None, max_samples=None, rel_error=0.0, abs_error=0.0, step=0, guide_samples=4,
-                                     specular_chain=0, albedo=False, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0):
+                                     specular_chain=0, albedo=False, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, device_mask=None,
+                                     assemble=False):
         """render_adaptive_light_groups with statistics (max_samples None = rd.spp: a fixed count), resident_guides (with `albedo`: the albedo too, and the filter
         demodulates by it; `specular_chain` > 0: guides at the end of every sample's specular chain) and denoise_light_groups_resident, in one call:
-        (film, denoised, group_films, denoised_group_films, counts, profile).  The denoised group films stay on the device for the relight."""
+        (film, denoised, group_films, denoised_group_films, counts, profile).  The denoised group films stay on the device for the relight.  A device_mask
+        routes the render through render_adaptive_light_groups_multi; guides and the joint filter then run over host arrays on the first device of the mask
+        (render_guides*, Library.denoise_light_groups), and the denoised group films are on the host alone.  `assemble` (with a device_mask only): the node
+        render's film and packed group films are assembled on the scene's device (resident_assemble) and guides and filter run resident, as without a mask."""
         mx = rd.spp if max_samples is None else max_samples
-        film, counts, st, group_films, prof = self.render_adaptive_light_groups(rd, mx, rel_error, instance_group, environment_group, groups, abs_error, step, stats=True)
+        if assemble and device_mask is None:
+            raise ValueError("assemble gathers a node render: it needs a device_mask")
+        if device_mask is not None:
+            film, counts, st, group_films, prof = self.render_adaptive_light_groups_multi(rd, mx, rel_error, instance_group, environment_group, groups, abs_error, step,
+                                                                                          stats=True, device_mask=device_mask)
+            if assemble:
+                self._assemble_node_render()
+            elif not (self.resident_info()[3] & RESIDENT_FILM):   # (a mask that came down to the scene's device left the film resident itself)
+                first = 0
+                while device_mask and not (device_mask >> first) & 1:
+                    first += 1
+                if specular_chain > 0:
+                    guides, alb = self.render_guides_chain(rd, guide_samples, specular_chain, albedo=albedo)
+                elif albedo:
+                    guides, alb = self.render_guides_albedo(rd, guide_samples)
+                else:
+                    guides, alb = self.render_guides(rd, guide_samples), None
+                den, den_groups = self.library.denoise_light_groups(film, counts, st, guides, group_films, albedo=alb, iterations=iterations,
+                                                                    sigma_luminance=sigma_luminance, sigma_depth=sigma_depth, normal_power_log2=normal_power_log2,
+                                                                    device=first)[:2]
+                return film, den, group_films, den_groups, counts, prof
+        else:
+            film, counts, st, group_films, prof = self.render_adaptive_light_groups(rd, mx, rel_error, instance_group, environment_group, groups, abs_error, step, stats=True)
         self.resident_guides(rd, guide_samples, specular_chain, albedo=albedo)
         den, den_groups = self.denoise_light_groups_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2)
         return film, den, group_films, den_groups, counts, prof

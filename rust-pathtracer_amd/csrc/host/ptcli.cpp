@@ -8,6 +8,7 @@
 //         [--denoise-light-groups instance|material]
 //         [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK] [--denoise-resident]
 //         [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]
+//         [--light-group-devices MASK]
 //         [--relamp-groups instance|material --relamp-bins B [--relamp G:CURVE[,G:CURVE...]] [--relamp-gains g0,g1,...] [--develop-subsamples N]]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
@@ -76,6 +77,13 @@
 // <filename>_light<g>.exr and <filename>_denoised_light<g>.exr and, with --light-gains, <filename>_relit.* and <filename>_denoised_relit.*, the relights of the
 // noisy and of the denoised group films (pt_light_groups_mix_resident, pt_light_groups_mix_resident_denoised).  Refused together with --light-groups,
 // --spectral-bins, --denoise-spectral-bins, --devices, --spectral-devices, --denoise-assemble and --hero-wavelengths.
+// --light-group-devices MASK (with --light-groups or --denoise-light-groups only; bit d = HIP device d, 0 = all) renders the group render on the devices of MASK from
+// one call (include/pt_light_groups_multi.h): pt_render_light_groups_multi, or pt_render_adaptive_light_groups_multi with --denoise-light-groups.  Every file stays byte
+// for byte what the run without it writes.  The group films are relit where the node render left them, shard by shard on the devices (pt_light_groups_mix_resident).
+// With --denoise-light-groups the guides and the joint filter run over host arrays on the first device of MASK (pt_render_guides*, pt_denoise_light_groups) and the
+// denoised relight is pt_light_groups_mix of the filtered films; with --denoise-assemble, which this flag allows beside --denoise-light-groups, the node render is
+// assembled on the scene's device (pt_resident_assemble: the film, and every device's packed group films unpacked beside it) and guides, filter and denoised relight
+// take the resident route of the one-device run.  It is refused together with --devices, whose refusals of the two group flags stay what they are.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -89,6 +97,7 @@
 #include "../../../include/pt_denoise.h"
 #include "../../../include/pt_light_groups.h"
 #include "../../../include/pt_light_groups_denoise.h"
+#include "../../../include/pt_light_groups_multi.h"
 #include "../../../include/pt_light_groups_spectral.h"
 #include "../../../include/pt_scene_file.h"
 #include "../../../include/pt_resident.h"
@@ -131,6 +140,8 @@ struct Options {
     bool has_relamp = false, has_relamp_gains = false;
     std::vector<std::pair<uint32_t, std::string>> relamp;   // --relamp G:CURVE,...
     std::vector<float> relamp_gains;                        // --relamp-gains
+    bool group_multi = false;     // --light-group-devices MASK: the group node calls (pt_render_light_groups_multi / pt_render_adaptive_light_groups_multi)
+    uint64_t group_device_mask = 0;
     bool assemble = false;        // --denoise-assemble: the node render assembled on the scene's device, then as `resident` (pt_resident_assemble)
 };
 
@@ -143,6 +154,7 @@ int usage(const char* msg) {
                     "             [--denoise-light-groups instance|material]\n"
                     "             [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK]\n"
                     "             [--denoise-resident] [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]\n"
+                    "             [--light-group-devices MASK]\n"
                     "             [--relamp-groups instance|material --relamp-bins B [--relamp G:CURVE[,G:CURVE...]] [--relamp-gains g0,g1,...]\n"
                     "              [--develop-subsamples N]]\n");
     return 2;
@@ -266,6 +278,13 @@ int main(int argc, char** argv) {
             if (end == v.c_str() || *end) return usage("--spectral-devices needs a device mask (bit d = HIP device d, 0 = all)");
             o.spectral_multi = true;
         }
+        else if (a == "--light-group-devices") {
+            if (!value(&v)) return usage("--light-group-devices needs a value");
+            char* end = nullptr;
+            o.group_device_mask = strtoull(v.c_str(), &end, 0);
+            if (end == v.c_str() || *end) return usage("--light-group-devices needs a device mask (bit d = HIP device d, 0 = all)");
+            o.group_multi = true;
+        }
         else if (a == "--light-groups") {
             if (!value(&v)) return usage("--light-groups needs a value");
             o.light_groups = v == "instance" ? 1 : v == "material" ? 2 : 0;
@@ -343,6 +362,8 @@ int main(int argc, char** argv) {
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
     }
+    if (o.group_multi && !o.light_groups && !o.denoise_groups) return usage("--light-group-devices needs --light-groups or --denoise-light-groups: it names the devices their group render runs on");
+    if (o.group_multi && o.multi) return usage("--light-group-devices cannot be combined with --devices: a group render takes its devices from --light-group-devices alone");
     if (o.relamp_groups) {
         const char* with = o.adaptive >= 0.0f ? "--adaptive" : o.denoise ? "--denoise" : o.light_groups ? "--light-groups" : o.spectral_bins ? "--spectral-bins"
                          : o.denoise_bins ? "--denoise-spectral-bins" : o.multi ? "--devices" : o.spectral_multi ? "--spectral-devices" : o.hero ? "--hero-wavelengths" : nullptr;
@@ -356,7 +377,7 @@ int main(int argc, char** argv) {
     }
     if (o.denoise_groups) {
         const char* with = o.light_groups ? "--light-groups" : o.spectral_bins ? "--spectral-bins" : o.denoise_bins ? "--denoise-spectral-bins" : o.multi ? "--devices"
-                         : o.spectral_multi ? "--spectral-devices" : o.assemble ? "--denoise-assemble" : o.hero ? "--hero-wavelengths" : nullptr;
+                         : o.spectral_multi ? "--spectral-devices" : (o.assemble && !o.group_multi) ? "--denoise-assemble" : o.hero ? "--hero-wavelengths" : nullptr;
         static std::string refusal;
         if (with) { refusal = std::string("--denoise-light-groups cannot be combined with ") + with + ": it is one adaptive group render of one wavelength per path on one device, and its filter"; return usage(refusal.c_str()); }
         if (!o.denoise) return usage("--denoise-light-groups needs --denoise");
@@ -381,6 +402,7 @@ int main(int argc, char** argv) {
     }
     if (o.resident && !o.denoise) return usage("--denoise-resident needs --denoise");
     if (o.resident && o.multi) return usage("--denoise-resident cannot be combined with --devices: a node render leaves no film one device can filter");
+    if (o.resident && o.group_multi) return usage("--denoise-resident cannot be combined with --light-group-devices: a node render leaves no film one device can filter (--denoise-assemble gathers one)");
     if (o.resident && o.spectral_multi) return usage("--denoise-resident cannot be combined with --spectral-devices: a node render leaves no film one device can filter");
     if (o.demodulate_bins && !o.denoise_bins) return usage("--demodulate-bins needs --denoise-spectral-bins");
     if (o.denoise_bins && !o.denoise) return usage("--denoise-spectral-bins needs --denoise");
@@ -393,8 +415,9 @@ int main(int argc, char** argv) {
     if (o.spectral_multi && o.multi) return usage("--spectral-devices cannot be combined with --devices: a spectral render takes its devices from --spectral-devices alone");
     if (o.assemble && o.resident) return usage("--denoise-assemble cannot be combined with --denoise-resident: that flag is the one-device form, this one assembles a node render");
     if (o.assemble && !o.denoise) return usage("--denoise-assemble needs --denoise");
-    if (o.assemble && !o.denoise_bins) return usage("--denoise-assemble needs --denoise-spectral-bins: it assembles the node render of the spectral film");
-    if (o.assemble && !o.spectral_multi) return usage("--denoise-assemble needs --spectral-devices: it assembles the node render on those devices");
+    const bool assemble_groups = o.assemble && o.denoise_groups && o.group_multi;   // (the node group render assembled: the other form of the flag)
+    if (o.assemble && !assemble_groups && !o.denoise_bins) return usage("--denoise-assemble needs --denoise-spectral-bins: it assembles the node render of the spectral film");
+    if (o.assemble && !assemble_groups && !o.spectral_multi) return usage("--denoise-assemble needs --spectral-devices: it assembles the node render on those devices");
     const bool verbose = o.stdout_log_level == "info" || o.stdout_log_level == "debug" || o.stdout_log_level == "trace";
     const bool warnings = verbose || o.stdout_log_level == "warn";
     if (!o.root.empty()) pt_scene_file_set_root(o.root.c_str());
@@ -596,10 +619,14 @@ int main(int argc, char** argv) {
             std::vector<float> group_bins;    // (--relamp-groups sizes it below)
             const pt_spectral_desc dsd = {o.denoise_bins, {0u, 0u, 0u}};
             const char* adaptive_entry = o.denoise_bins ? (o.spectral_multi ? "pt_render_adaptive_spectral_multi" : "pt_render_adaptive_spectral")
-                                         : o.denoise_groups ? "pt_render_adaptive_light_groups" : o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive";
+                                         : o.denoise_groups ? (o.group_multi ? "pt_render_adaptive_light_groups_multi" : "pt_render_adaptive_light_groups") : o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive";
             if (o.denoise_groups) group_films.resize((size_t)gd.group_count * rd.width * rd.height * 4);
             // --denoise-light-groups: the adaptive group render — film, counts and statistics are pt_render_adaptive's bit for bit
-            const auto adaptive_groups = [&] { return pt_render_adaptive_light_groups(scene, &rd, &ad, &gd, film.data(), counts.data(), stats.data(), group_films.data(), &prof); };
+            // (--light-group-devices: on the devices of the mask)
+            const auto adaptive_groups = [&] {
+                return o.group_multi ? pt_render_adaptive_light_groups_multi(scene, &rd, &ad, &gd, o.group_device_mask, film.data(), counts.data(), stats.data(), group_films.data(), &prof)
+                                     : pt_render_adaptive_light_groups(scene, &rd, &ad, &gd, film.data(), counts.data(), stats.data(), group_films.data(), &prof);
+            };
             // --denoise-spectral-bins: the adaptive spectral render, on one device or (--spectral-devices) on the devices of the mask
             const auto adaptive_spectral = [&](double* st_out) {
                 return o.spectral_multi ? pt_render_adaptive_spectral_multi(scene, &rd, &ad, &dsd, o.spectral_device_mask, film.data(), counts.data(), st_out, spectral.data(), &prof)
@@ -646,7 +673,9 @@ int main(int argc, char** argv) {
             } else if (o.light_groups) {
                 printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u, %u light groups\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples, gd.group_count);
                 group_films.resize((size_t)gd.group_count * rd.width * rd.height * 4);
-                if (pt_render_light_groups(scene, &rd, &gd, film.data(), group_films.data(), &prof) != PT_OK) { fprintf(stderr, "pt_render_light_groups: %s\n", pt_last_error()); rc = 1; break; }
+                const pt_status st = o.group_multi ? pt_render_light_groups_multi(scene, &rd, &gd, o.group_device_mask, film.data(), group_films.data(), &prof)
+                                                   : pt_render_light_groups(scene, &rd, &gd, film.data(), group_films.data(), &prof);
+                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.group_multi ? "pt_render_light_groups_multi" : "pt_render_light_groups", pt_last_error()); rc = 1; break; }
             } else {
                 printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
                 const pt_status st = o.multi ? pt_render_multi(scene, &rd, o.device_mask, film.data(), &prof) : pt_render(scene, &rd, film.data(), &prof);
@@ -671,7 +700,8 @@ int main(int argc, char** argv) {
             printf("wrote %s.exr and %s.png\n", base.c_str(), base.c_str());
             // --light-groups, --denoise-light-groups: every group's film, and with --light-gains the resident mix, through this setting's film output (buffers of
             // their own).  `stem`: base, or base + "_denoised" for the films of the joint filter, which are then mixed where that left them.
-            const auto write_groups = [&](const std::string& stem, const std::vector<float>& films, bool denoised) {
+            // (host_mix: the films were filtered over host arrays and are mixed from there, pt_light_groups_mix)
+            const auto write_groups = [&](const std::string& stem, const std::vector<float>& films, bool denoised, bool host_mix = false) {
                 const size_t np = (size_t)rd.width * rd.height;
                 std::vector<float> g_linear(3 * np), relit(4 * np), matrices;
                 std::vector<uint8_t> g_rgba(4 * np);
@@ -685,7 +715,8 @@ int main(int argc, char** argv) {
                 if (ok && o.has_light_gains) {
                     for (float gain : o.light_gains) for (int k = 0; k < 9; ++k) matrices.push_back(k % 4 == 0 ? gain : 0.0f);
                     const std::string name = stem + "_relit";
-                    ok = (denoised ? pt_light_groups_mix_resident_denoised(scene, matrices.data(), relit.data()) : pt_light_groups_mix_resident(scene, matrices.data(), relit.data())) == PT_OK &&
+                    ok = (host_mix ? pt_light_groups_mix(rd.width, rd.height, gd.group_count, films.data(), matrices.data(), relit.data())
+                          : denoised ? pt_light_groups_mix_resident_denoised(scene, matrices.data(), relit.data()) : pt_light_groups_mix_resident(scene, matrices.data(), relit.data())) == PT_OK &&
                          pt_output_film(&od, relit.data(), g_rgba.data(), g_linear.data()) == PT_OK &&
                          pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, g_linear.data(), od.colorspace) == PT_OK &&
                          pt_write_png((name + ".png").c_str(), rd.width, rd.height, g_rgba.data(), od.colorspace) == PT_OK;
@@ -776,7 +807,40 @@ int main(int argc, char** argv) {
                 if (ast == PT_OK && !(now.parts & PT_RESIDENT_FILM)) ast = pt_resident_assemble(scene, 0u);
                 if (ast != PT_OK) { fprintf(stderr, "--denoise-assemble: %s\n", pt_last_error()); rc = 1; break; }
             }
-            if (o.denoise && o.denoise_groups) {
+            // (a node group render without --denoise-assemble left no film one device can filter, unless the mask came down to the scene's device alone)
+            bool groups_on_host = false;
+            if (o.denoise && o.denoise_groups && o.group_multi && !o.assemble) {
+                struct pt_resident_info now;
+                if (pt_resident_info(scene, &now) != PT_OK) { fprintf(stderr, "--light-group-devices: %s\n", pt_last_error()); rc = 1; break; }
+                groups_on_host = !(now.parts & PT_RESIDENT_FILM);
+            }
+            if (o.denoise && o.denoise_groups && groups_on_host) {
+                // guides and the joint filter over host arrays, on the first device of the mask: the files of the resident route, byte for byte
+                const size_t np = (size_t)rd.width * rd.height;
+                std::vector<float> guides(4 * np), albedo(o.demodulate ? 4 * np : 0), clean(4 * np), clean_groups(4 * np * gd.group_count);
+                pt_denoise_desc dd;
+                memset(&dd, 0, sizeof(dd));
+                dd.width = rd.width; dd.height = rd.height;
+                if (o.group_device_mask) while (!((o.group_device_mask >> dd.device) & 1u)) ++dd.device;
+                pt_guide_chain_desc cd;
+                memset(&cd, 0, sizeof(cd));
+                cd.max_chain = o.max_chain; cd.alpha_max = o.alpha_max;
+                pt_status dst = o.chain ? pt_render_guides_chain(scene, &rd, o.guide_samples, &cd, guides.data(), o.demodulate ? albedo.data() : nullptr)
+                                : o.demodulate ? pt_render_guides_albedo(scene, &rd, o.guide_samples, guides.data(), albedo.data())
+                                               : pt_render_guides(scene, &rd, o.guide_samples, guides.data());
+                if (dst == PT_OK) dst = pt_denoise_light_groups(&dd, gd.group_count, film.data(), counts.data(), stats.data(), guides.data(), o.demodulate ? albedo.data() : nullptr,
+                                                                group_films.data(), clean.data(), nullptr, clean_groups.data());
+                if (dst != PT_OK) { fprintf(stderr, "--denoise-light-groups: %s\n", pt_last_error()); rc = 1; break; }
+                if (pt_output_film(&od, clean.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }
+                const std::string dbase = base + "_denoised";
+                if (pt_write_exr((dbase + ".exr").c_str(), rd.width, rd.height, linear.data(), od.colorspace) != PT_OK ||
+                    pt_write_png((dbase + ".png").c_str(), rd.width, rd.height, rgba.data(), od.colorspace) != PT_OK) {
+                    fprintf(stderr, "failed to write files: %s\n", pt_last_error()); rc = 1; break;
+                }
+                if (o.write_film && !write_npy(dbase + ".npy", clean.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", dbase.c_str()); rc = 1; break; }
+                printf("wrote %s.exr and %s.png\n", dbase.c_str(), dbase.c_str());
+                if (!write_groups(dbase, clean_groups, true, true)) { rc = 1; break; }
+            } else if (o.denoise && o.denoise_groups) {
                 // the render left the film, its statistics and the group films on the device, paired: the guides stay there too, and the joint filter runs on all of
                 // it (with or without --denoise-resident: this is the only route, and its files are those of either)
                 const size_t np = (size_t)rd.width * rd.height;

@@ -30,9 +30,12 @@
 #include "../../include/pt_denoise.h"
 #include "../../include/pt_light_groups.h"
 #include "../../include/pt_light_groups_denoise.h"
+#include "../../include/pt_light_groups_multi.h"
 #include "../../include/pt_light_groups_spectral.h"
 #include "pt_adaptive_select.h"
 #include "pt_light_groups_launch.h"
+#include "pt_light_groups_shard_launch.h"
+#include "pt_light_groups_shard_rules.h"
 #include "pt_light_groups_spectral_launch.h"
 #include "pt_spectral_launch.h"
 #include "pt_spectral_rules.h"
@@ -290,13 +293,16 @@ struct AdaptiveBuffers {
 }  // namespace
 
 // What the last adaptive node render (render_node) left where, for pt_resident_assemble (include/pt_resident.h): film, counts and statistics on `device`, the
-// first device of the mask, and for a spectral render the scenes that hold the packed shards (shard_px, shard_packed).  Kept with the MultiSetup whose films it
-// points into: released with it.  Every render entry forgets it when it starts.
+// first device of the mask, for a spectral render the scenes that hold the packed shards (shard_px, shard_packed), and for a group render the scenes that hold the
+// packed group films (group_shard_px, group_shard_packed) and their number of groups.  Kept with the MultiSetup whose films it points into: released with it.
+// Every render entry forgets it when it starts.
 struct NodeRemembered {
     pth::NodeRender info;
     int device = 0;
     const float* film = nullptr; const uint32_t* counts = nullptr; const double* stats = nullptr;
     std::vector<pt_scene*> shards;
+    std::vector<pt_scene*> group_shards;
+    uint32_t groups = 0;
 };
 
 // What pt_render_multi sets up for a set of devices and a film size, kept on the scene: a frame-by-frame caller pays for streams, device
@@ -309,7 +315,7 @@ struct MultiSetup {
     std::vector<float*> films;        // per virtual device, on its physical device
     std::vector<hipStream_t> streams; // per virtual device
     std::vector<ncclComm_t> comms;    // per physical device (rccl only)
-    std::vector<GrowBuf> staging;   // per virtual device: the pinned host buffer its packed spectral planes land in (the spectral node entries; grown on demand)
+    std::vector<GrowBuf> staging;   // per virtual device: the pinned host buffer its packed spectral planes or packed group films land in (the spectral and the group node entries; grown on demand)
     NodeRemembered node_render;
     bool valid = false;
 };
@@ -366,11 +372,19 @@ struct pt_scene {
     std::vector<uint32_t> shard_px;
     GrowBuf shard_packed;
     // The resident group films (include/pt_light_groups.h): what the last successful light-group render left in group_films_cache, group-major float4 films.  Cleared
-    // when a group render starts and set when it has succeeded; pt_render_light_groups and pt_render_adaptive_light_groups are the only writers of the buffer.  group_table: that render's one byte per
+    // when a group render starts and set when it has succeeded; the group renders (a node render's worker on its own scene or replica among them) and the group part of
+    // pt_resident_assemble are the only writers of the buffer.  group_table: that render's one byte per
     // instance; group_mix_cache: pt_light_groups_mix_resident's device matrices (PT_LIGHT_GROUPS_MAX x 9 floats) and, behind them, its output film.
     bool groups_valid = false;
     uint32_t groups_width = 0, groups_height = 0, groups_count = 0;
     GrowBuf group_films_cache, group_table, group_mix_cache;
+    // After a node group render (include/pt_light_groups_multi.h) the resident group films are the set of packed shards instead: group_shards (on the scene the call
+    // was made on) names the scenes that hold them — this one and its replicas; empty = group_films_cache.  Each of those scenes keeps its own shard:
+    // group_shard_px, the pixel list in pth::shard_pixels' order (a list of its own: a spectral node render's shard_px may be of another film), and
+    // group_shard_packed, groups_count films of group_shard_px.size() float4 on its device (k_light_groups_pack's output).
+    std::vector<pt_scene*> group_shards;
+    std::vector<uint32_t> group_shard_px;
+    GrowBuf group_shard_packed;
     // The resident group bins (include/pt_light_groups_spectral.h): what the last successful pt_render_light_groups_spectral left in group_bins_cache, group-major, then
     // bin-major planes of width * height floats.  Cleared when a group render of any kind starts (the other two leave none) and set when that render has succeeded;
     // it is the only writer of the buffer.  relamp_cache: pt_light_groups_relamp_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x 512 floats) and, behind it,
@@ -1169,6 +1183,12 @@ pt_status pt_scene_create_tuned(const pt_scene_desc* desc, const pt_tuning* tuni
 static void multi_release(MultiSetup& m);
 // a render entry starts (or is refused): whatever an earlier node render left is no longer described (pt_resident_assemble)
 static void forget_node_render(pt_scene* sc) { if (sc) sc->multi.node_render = NodeRemembered(); }
+// a group render of any kind starts (or a node one is refused): no group films, on one device or in shards, no denoised ones that came from them, no group bins
+static void end_group_films(pt_scene* sc) {
+    if (!sc) return;
+    sc->groups_valid = false; sc->groups_denoised = false; sc->group_bins_valid = false;
+    sc->group_shards.clear();
+}
 void pt_scene_destroy(pt_scene* sc) {
     if (!sc) return;
     for (pt_scene* r : sc->replicas) if (r) pt_scene_destroy(r);
@@ -1209,7 +1229,7 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
     const pt_render_desc& rd = *call.rd;
     forget_node_render(sc);
     if (call.sd) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts: whatever the buffer held is no film from here on)
-    if (call.gd) { sc->groups_valid = false; sc->groups_denoised = false; sc->group_bins_valid = false; }   // (likewise the group films, the denoised ones that came from them, and the group bins)
+    if (call.gd) end_group_films(sc);   // (likewise the group films, the denoised ones that came from them, and the group bins)
     sc->groups_paired = false;   // (the resident film ends below)
     sc->resident.end();   // (film_cache and the adaptive buffers are written from here on; guides and denoised outputs belonged to the film before)
     HIP_TRY(hipSetDevice(sc->device));
@@ -1397,10 +1417,12 @@ pt_status pt_light_groups_resident(pt_scene* sc, uint32_t* width, uint32_t* heig
 // include/pt_light_groups.h: pt_light_groups_mix's kernel over group_films_cache, on the stream the render ran on (the null stream), so the group films never cross the bus.
 // (`films`: group_films_cache, or the denoised group films of include/pt_light_groups_denoise.h — the same size and count)
 static pt_status mix_resident_films(pt_scene* sc, const float* films, const float* matrices, float* out);
+static pt_status mix_resident_node(pt_scene* sc, const float* matrices, float* out);
 pt_status pt_light_groups_mix_resident(pt_scene* sc, const float* matrices, float* out) {
     if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
     if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "out_xyzw is null");
     if (!sc->groups_valid) return fail(PT_ERR_INVALID_ARGUMENT, "the scene has no resident group films: pt_render_light_groups must have succeeded on it");
+    if (!sc->group_shards.empty()) return mix_resident_node(sc, matrices, out);
     return mix_resident_films(sc, sc->group_films_cache.as<float>(), matrices, out);
 }
 pt_status pt_light_groups_mix_resident_denoised(pt_scene* sc, const float* matrices, float* out) {
@@ -1747,9 +1769,93 @@ static pt_status project_resident_node(pt_scene* sc, uint32_t K, const float* ma
     return PT_OK;
 }
 
-// The node driver behind the four node entries (call: as for render_one): one worker per (virtual) device renders its shard of the film, the films are gathered
+// The group films of a node call (pt_render_light_groups_multi, pt_render_adaptive_light_groups_multi; DESIGN.md section 15 "On every device of a node").  Like the
+// bins they are never reduced: every device packs the pixels of its own tiles (k_light_groups_pack), copies them to its pinned staging buffer and its host thread
+// scatters them into the caller's array; the packed films stay on the device as its part of the scene's resident group films.
+struct NodeGroups {
+    const pt_light_groups_desc* gd = nullptr;
+    size_t film_pixels = 0;
+    float* host = nullptr;         // the caller's group films (null: nothing is copied to the host)
+    std::vector<double> seconds;   // per worker: its pack, copy and scatter
+};
+// Part of the set-up: every device's pixel list (kept on its scene), the group table's bytes, full-size group films, packed films and staging buffer, made once
+// per size and kept.  A shard without a pixel gets no packed buffer.  rd: normalised.
+static pt_status node_prepare_groups(MultiSetup& m, const Node& node, const pt_render_desc& rd, const pt_light_groups_desc* gd, float* group_films, NodeGroups* ng) {
+    ng->gd = gd; ng->film_pixels = (size_t)rd.width * rd.height; ng->host = group_films; ng->seconds.assign(node.n, 0.0);
+    for (int v = 0; v < node.n; ++v) {
+        pt_scene* s = node.scene_of[v];
+        s->group_shard_px = pth::shard_pixels(rd.width, rd.height, rd.tile_width, rd.tile_height, node.n > 1 ? (uint32_t)v : 0u, node.n > 1 ? (uint32_t)node.n : 0u);
+        HIP_TRY(hipSetDevice(node.devices[v / node.virt]));
+        const size_t packed_bytes = sizeof(float) * 4 * gd->group_count * s->group_shard_px.size();
+        pt_status st = s->group_films_cache.reserve(sizeof(float) * 4 * gd->group_count * ng->film_pixels);
+        if (st == PT_OK) st = s->group_table.reserve(gd->instance_count ? gd->instance_count : 1u);
+        if (st == PT_OK && packed_bytes) st = s->group_shard_packed.reserve(packed_bytes);
+        if (st == PT_OK && packed_bytes && group_films) st = m.staging[v].reserve(packed_bytes);
+        if (st != PT_OK) return st;
+        if (gd->instance_count) HIP_TRY(hipMemcpy(s->group_table.p, gd->instance_group, gd->instance_count, hipMemcpyHostToDevice));
+    }
+    return PT_OK;
+}
+// Worker v behind its render (the stream is idle: render_impl synchronised it): pack by the list render_impl left in buf.pixels, copy, scatter.  The shards are
+// disjoint and cover the film (every pixel is in exactly one list: tests/test_light_groups_multi.py), so the threads never write the same pixel and the caller's
+// array needs no zeroing.  Without a host array the pack still runs: the packed shard is what stays resident.
+static pt_status node_groups_exchange(MultiSetup& m, const Node& node, NodeGroups& ng, int v) {
+    pt_scene* s = node.scene_of[v];
+    const uint32_t n_own = (uint32_t)s->group_shard_px.size(), G = ng.gd->group_count;
+    if (n_own == 0) return PT_OK;
+    const auto t = std::chrono::steady_clock::now();
+    HIP_TRY(ptk::launch_light_groups_pack(ptk::light_groups_pack_grid(s->num_cus, n_own), m.streams[v], s->group_films_cache.as<float>(), (uint32_t)ng.film_pixels, s->buf.pixels, n_own, G,
+                                          s->group_shard_packed.as<float>()));
+    if (ng.host) HIP_TRY(hipMemcpyAsync(m.staging[v].p, s->group_shard_packed.p, sizeof(float) * 4 * G * n_own, hipMemcpyDeviceToHost, m.streams[v]));
+    HIP_TRY(hipStreamSynchronize(m.streams[v]));
+    if (ng.host) lg_shard_scatter(m.staging[v].as<LgPixel>(), s->group_shard_px.data(), n_own, G, reinterpret_cast<LgPixel*>(ng.host), ng.film_pixels);
+    ng.seconds[v] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+    return PT_OK;
+}
+static double node_groups_seconds(const NodeGroups& ng) { return ng.seconds.empty() ? 0.0 : *std::max_element(ng.seconds.begin(), ng.seconds.end()); }
+// the node render has succeeded: the scene's resident group films are the packed shards, paired with no resident film
+static void node_groups_resident(pt_scene* sc, const Node& node, const pt_render_desc& rd, uint32_t groups) {
+    sc->group_shards = node.scene_of;
+    sc->groups_width = rd.width; sc->groups_height = rd.height; sc->groups_count = groups; sc->groups_valid = true;
+}
+
+// pt_light_groups_mix_resident of node-resident group films: the matrices to every device that holds a shard, pt_light_groups_mix's kernel over the shard's packed
+// films (group stride n_own), n_own pixels back per device, scattered by the rule the group films were scattered by (one film: G = 1).
+static pt_status mix_resident_node(pt_scene* sc, const float* matrices, float* out) {
+    std::string err;
+    const pt_status checked = pth::check_light_groups_matrices(sc->groups_count, matrices, &err);
+    if (checked != PT_OK) return fail(checked, err);
+    DeviceGuard guard;
+    const size_t film_pixels = (size_t)sc->groups_width * sc->groups_height, matrix_floats = (size_t)PT_LIGHT_GROUPS_MAX * 12;   // (the film behind them stays 16-byte aligned)
+    std::vector<std::vector<LgPixel>> mixed(sc->group_shards.size());
+    for (size_t v = 0; v < sc->group_shards.size(); ++v) {
+        pt_scene* s = sc->group_shards[v];
+        const uint32_t n_own = (uint32_t)s->group_shard_px.size();
+        if (n_own == 0) continue;
+        HIP_TRY(hipSetDevice(s->device));
+        const pt_status st = s->group_mix_cache.reserve(sizeof(float) * (matrix_floats + 4 * (size_t)n_own));
+        if (st != PT_OK) return st;
+        mixed[v].resize(n_own);
+        float* d_matrices = s->group_mix_cache.as<float>();
+        float* d_out = d_matrices + matrix_floats;
+        HIP_TRY(hipMemcpyAsync(d_matrices, matrices, sizeof(float) * 9 * sc->groups_count, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(ptk::launch_light_groups_mix(nullptr, n_own, sc->groups_count, s->group_shard_packed.as<float>(), d_matrices, d_out));
+        HIP_TRY(hipMemcpyAsync(mixed[v].data(), d_out, sizeof(float) * 4 * n_own, hipMemcpyDeviceToHost, nullptr));
+    }
+    for (size_t v = 0; v < sc->group_shards.size(); ++v) {
+        pt_scene* s = sc->group_shards[v];
+        if (s->group_shard_px.empty()) continue;
+        HIP_TRY(hipSetDevice(s->device));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        lg_shard_scatter(mixed[v].data(), s->group_shard_px.data(), (uint32_t)s->group_shard_px.size(), 1u, reinterpret_cast<LgPixel*>(out), film_pixels);
+    }
+    return PT_OK;
+}
+
+// The node driver behind the six node entries (call: as for render_one): one worker per (virtual) device renders its shard of the film, the films are gathered
 // on the first device of the mask and read back from there.  An adaptive call (pt_render_adaptive_multi) runs its rounds in lockstep over the NodeRounds and
-// gathers counts and statistics too; a spectral call hands every worker's bins over by node_spectral_exchange and leaves the packed shards resident.
+// gathers counts and statistics too; a spectral call hands every worker's bins over by node_spectral_exchange and leaves the packed shards resident; a group
+// call does the same with every worker's group films (node_groups_exchange).
 static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t device_mask, pt_profile* profile) {
     const pt_render_desc& rd = *call.rd;
     const bool adaptive = call.ad != nullptr;
@@ -1777,6 +1883,11 @@ static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t devi
     NodeSpectral ns;
     if (call.sd) {
         st = node_prepare_spectral(m, node, rd, call.sd->bins, call.spectral, &ns);
+        if (st != PT_OK) return st;
+    }
+    NodeGroups ng;
+    if (call.gd) {
+        st = node_prepare_groups(m, node, rd, call.gd, call.group_films, &ng);
         if (st != PT_OK) return st;
     }
     NodeRounds nr;
@@ -1832,8 +1943,12 @@ static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t devi
         RenderJob job;
         if (adaptive) { job.adaptive = call.ad; job.node = &nr; job.node_index = v; }
         if (call.sd) { job.d_spectral = s->spectral_cache.as<float>(); job.spectral_bins = call.sd->bins; job.shard_list = &s->shard_px; }
+        // (a shard together with groups: the one-device entries refuse it in check_light_groups_args, which this driver's callers do not run on a worker's desc)
+        const LightGroupTable table{s->group_table.as<uint8_t>(), call.gd ? call.gd->environment_group : 0u, call.gd ? call.gd->group_count : 0u};
+        if (call.gd) { job.groups = &table; job.d_group_films = s->group_films_cache.as<float>(); job.shard_list = &s->group_shard_px; }
         if (s2 == PT_OK) s2 = render_impl(s, &rv, m.films[v], m.streams[v], &profiles[v], job);
         if (s2 == PT_OK && call.sd) s2 = node_spectral_exchange(m, node, ns, v);
+        if (s2 == PT_OK && call.gd) s2 = node_groups_exchange(m, node, ng, v);
         if (s2 == PT_OK) return;
         status[v] = s2; errors[v] = device_name(node, v) + ": " + g_error;   // (g_error is thread-local: carried back to the caller below)
         if (adaptive) nr.lock.stop(s2, errors[v]);   // (a worker stopped by another's failure finds the first error kept)
@@ -1864,9 +1979,10 @@ static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t devi
         if (adaptive) profile->kernel_launches[5] = profiles[0].kernel_launches[5];                        // the rounds (every device ran them all)
         profile->kernel_seconds[5] = std::chrono::duration<double>(t0 - t_entry).count();    // set-up (replicas, streams, films, communicator): ~0 on a repeated call
         // the rounds' exchanges (adaptive) + the film reduce or gather (+ the longest pack, copy and scatter)
-        profile->kernel_seconds[6] = nr.exchange_seconds + std::chrono::duration<double>(t_gathered - t_gather).count() + node_spectral_seconds(ns);
+        profile->kernel_seconds[6] = nr.exchange_seconds + std::chrono::duration<double>(t_gathered - t_gather).count() + node_spectral_seconds(ns) + node_groups_seconds(ng);
     }
     if (call.sd) node_spectral_resident(sc, node, rd, call.sd->bins);
+    if (call.gd) node_groups_resident(sc, node, rd, call.gd->group_count);
     if (adaptive) {   // where the pieces lie, for pt_resident_assemble: no device work, and nothing is resident (include/pt_resident.h)
         NodeRemembered& k = m.node_render;
         k.info.valid = true; k.info.stats = call.stats != nullptr;
@@ -1874,6 +1990,7 @@ static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t devi
         k.device = node.devices[0];
         k.film = m.films[0]; k.counts = node.scene_of[0]->adaptive.counts; k.stats = node.scene_of[0]->adaptive.stats;
         if (call.sd) k.shards = node.scene_of;
+        if (call.gd) { k.group_shards = node.scene_of; k.groups = call.gd->group_count; }
     }
     return PT_OK;
 }
@@ -1926,6 +2043,37 @@ pt_status pt_render_adaptive_spectral_multi(pt_scene* sc, const pt_render_desc* 
     if (st != PT_OK) return fail(st, err);
     RenderCall call;
     call.rd = &rd; call.ad = &ad; call.sd = sdp; call.film = film; call.sample_counts = sample_counts; call.stats = stats; call.spectral = spectral;
+    return render_node(sc, call, device_mask, profile);
+}
+
+// include/pt_light_groups_multi.h.  A group call ends the residency of the group films before it, whatever it is refused for.
+pt_status pt_render_light_groups_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_light_groups_desc* gdp, uint64_t device_mask, float* film, float* group_films,
+                                       pt_profile* profile) {
+    end_group_films(sc);
+    forget_node_render(sc);
+    pt_render_desc rd;
+    std::string err;
+    const pt_status st = pth::check_light_groups_multi_args(sc, rdp, gdp, sc ? sc->host.blob[PT_HDR_INSTANCE_COUNT] : 0u, sc ? (uint32_t)sc->host.cameras.size() : 0u, film, &rd, &err);
+    if (st != PT_OK) return fail(st, err);
+    if ((uint64_t)rd.width * rd.height > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and width x height must fit 31 bits");
+    RenderCall call;
+    call.rd = &rd; call.gd = gdp; call.film = film; call.group_films = group_films;
+    return render_node(sc, call, device_mask, profile);
+}
+
+pt_status pt_render_adaptive_light_groups_multi(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, const pt_light_groups_desc* gdp, uint64_t device_mask,
+                                                float* film, uint32_t* sample_counts, double* stats, float* group_films, pt_profile* profile) {
+    end_group_films(sc);
+    forget_node_render(sc);
+    pt_render_desc rd;
+    pt_adaptive_desc ad;
+    std::string err;
+    const pt_status st = pth::check_adaptive_light_groups_multi_args(sc, rdp, adp, gdp, sc ? sc->host.blob[PT_HDR_INSTANCE_COUNT] : 0u, sc ? (uint32_t)sc->host.cameras.size() : 0u,
+                                                                     film, sample_counts, &rd, &ad, &err);
+    if (st != PT_OK) return fail(st, err);
+    if ((uint64_t)rd.width * rd.height > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and width x height must fit 31 bits");
+    RenderCall call;
+    call.rd = &rd; call.ad = &ad; call.gd = gdp; call.film = film; call.sample_counts = sample_counts; call.stats = stats; call.group_films = group_films;
     return render_node(sc, call, device_mask, profile);
 }
 
@@ -2265,10 +2413,19 @@ pt_status pt_resident_assemble(pt_scene* sc, uint32_t flags) {
         if (staged(s)) staging_floats += (size_t)bins * s->shard_px.size();
         if (!listed(s)) px_words += s->shard_px.size();
     }
+    // (a group render's shards, behind the bins' on a 16-byte boundary: pixels of four floats)
+    const uint32_t groups = k.groups;
+    const size_t group_stage_first = (staging_floats + 3) & ~(size_t)3;
+    for (const pt_scene* s : k.group_shards) {
+        if (staged(s)) staging_floats = (staging_floats > group_stage_first ? staging_floats : group_stage_first) + 4 * (size_t)groups * s->group_shard_px.size();
+        if (!listed(s)) px_words += s->group_shard_px.size();
+    }
+    if (!k.group_shards.empty()) end_group_films(sc);   // (the shards are unpacked below: on any failure no group films are resident)
     st = r.load_film.reserve(16 * np);
     if (st == PT_OK) st = r.load_counts.reserve(4 * np);
     if (st == PT_OK) st = r.load_stats.reserve(16 * np);
     if (st == PT_OK && bins) st = r.load_spectral.reserve(4 * np * bins);
+    if (st == PT_OK && !k.group_shards.empty()) st = sc->group_films_cache.reserve(16 * np * groups);
     if (st == PT_OK && staging_floats) st = sc->assemble_staging.reserve(sizeof(float) * staging_floats);
     if (st == PT_OK && px_words) st = sc->assemble_px.reserve(sizeof(uint32_t) * px_words);
     if (st != PT_OK) return st;
@@ -2299,11 +2456,34 @@ pt_status pt_resident_assemble(pt_scene* sc, uint32_t flags) {
         }
         HIP_TRY(ptk::launch_spectral_unpack(ptk::spectral_pack_grid(sc->num_cus, n_own), stream, packed, px, n_own, bins, r.load_spectral.as<float>(), (uint32_t)np));
     }
+    // the group films of an adaptive node group render, into the buffer a one-device group render leaves them in: the same walk over the group shards
+    stage = sc->assemble_staging.as<float>() + group_stage_first;
+    for (const pt_scene* s : k.group_shards) {
+        const uint32_t n_own = (uint32_t)s->group_shard_px.size();
+        if (n_own == 0) continue;
+        const float* packed = s->group_shard_packed.as<float>();
+        if (staged(s)) {
+            HIP_TRY(hipMemcpyPeerAsync(stage, sc->device, packed, s->device, sizeof(float) * 4 * groups * n_own, stream));
+            packed = stage;
+            stage += 4 * (size_t)groups * n_own;
+        }
+        const uint32_t* px = s->buf.pixels;
+        if (!listed(s)) {
+            HIP_TRY(hipMemcpyAsync(lists, s->group_shard_px.data(), sizeof(uint32_t) * n_own, hipMemcpyHostToDevice, stream));
+            px = lists;
+            lists += n_own;
+        }
+        HIP_TRY(ptk::launch_light_groups_unpack(ptk::light_groups_pack_grid(sc->num_cus, n_own), stream, packed, px, n_own, groups, sc->group_films_cache.as<float>(), (uint32_t)np));
+    }
     HIP_TRY(hipStreamSynchronize(stream));
     r.parts = PT_RESIDENT_FILM | (bins ? PT_RESIDENT_BINS : 0u);
     r.width = k.info.width; r.height = k.info.height; r.bins = bins;
     r.film = r.load_film.as<float>(); r.counts = r.load_counts.as<uint32_t>(); r.stats = r.load_stats.as<double>();
     r.spectral = bins ? r.load_spectral.as<float>() : nullptr;
+    if (!k.group_shards.empty()) {   // (the group films lie beside the film they were rendered with, as after pt_render_adaptive_light_groups)
+        sc->groups_width = k.info.width; sc->groups_height = k.info.height; sc->groups_count = groups;
+        sc->groups_valid = true; sc->groups_paired = true;
+    }
     return PT_OK;
 }
 pt_status pt_resident_read(pt_scene* sc, float* film, uint32_t* sample_counts, double* stats, float* spectral) {

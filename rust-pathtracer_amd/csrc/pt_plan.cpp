@@ -459,8 +459,9 @@ pt_status check_response_matrix_args(const pt_render_desc* rd, const pt_spectral
     return PT_OK;
 }
 
-pt_status check_light_groups_args(const void* scene, const pt_render_desc* rd, const pt_light_groups_desc* gd, uint32_t scene_instances, const void* film,
-                                  std::string* error) {
+// node_entry: null for the one-device entries; a node entry's name, whose refusal of a shard is its own
+static pt_status light_groups_args(const void* scene, const pt_render_desc* rd, const pt_light_groups_desc* gd, uint32_t scene_instances, const void* film,
+                                   const char* node_entry, std::string* error) {
     if (!scene) { *error = "the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
     if (!rd) { *error = "the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
     if (!gd) { *error = "the light groups desc is null"; return PT_ERR_INVALID_ARGUMENT; }
@@ -480,12 +481,37 @@ pt_status check_light_groups_args(const void* scene, const pt_render_desc* rd, c
     if (gd->environment_group >= gd->group_count) { *error = "environment_group must be below group_count"; return PT_ERR_INVALID_ARGUMENT; }
     if (rd->hero_wavelengths == 4) { *error = "light groups carry one wavelength per path (hero_wavelengths 0 or 1)"; return PT_ERR_UNSUPPORTED; }
     if (rd->medium_aware) { *error = "light groups are not rendered by the medium-aware walk"; return PT_ERR_UNSUPPORTED; }
+    if (node_entry && rd->shard_count != 0) { *error = std::string(node_entry) + " deals the tiles itself: shard_count must be 0"; return PT_ERR_INVALID_ARGUMENT; }
     if (rd->shard_count > 1) { *error = "light groups render the whole film (shard_count 0 or 1)"; return PT_ERR_UNSUPPORTED; }
     if (rd->first_sample != 0 || (rd->sample_count != 0 && rd->sample_count != rd->spp)) {
         *error = "light groups render the whole sample range (first_sample 0, sample_count 0 or spp)";
         return PT_ERR_UNSUPPORTED;
     }
     return PT_OK;
+}
+
+pt_status check_light_groups_args(const void* scene, const pt_render_desc* rd, const pt_light_groups_desc* gd, uint32_t scene_instances, const void* film,
+                                  std::string* error) {
+    return light_groups_args(scene, rd, gd, scene_instances, film, nullptr, error);
+}
+
+// ---- include/pt_light_groups_multi.h
+pt_status check_light_groups_multi_args(const void* scene, const pt_render_desc* rd, const pt_light_groups_desc* gd, uint32_t scene_instances, uint32_t camera_count,
+                                        const void* film, pt_render_desc* rd_out, std::string* error) {
+    const pt_status st = light_groups_args(scene, rd, gd, scene_instances, film, "pt_render_light_groups_multi", error);
+    if (st != PT_OK) return st;
+    if (!normalize_render_desc(*rd, camera_count, rd_out, error)) return PT_ERR_INVALID_ARGUMENT;
+    return PT_OK;
+}
+pt_status check_adaptive_light_groups_multi_args(const void* scene, const pt_render_desc* rd, const pt_adaptive_desc* ad, const pt_light_groups_desc* gd,
+                                                 uint32_t scene_instances, uint32_t camera_count, const void* film, const void* sample_counts, pt_render_desc* rd_out,
+                                                 pt_adaptive_desc* ad_out, std::string* error) {
+    if (!scene) { *error = "the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!rd) { *error = "the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!ad) { *error = "the adaptive desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = light_groups_args(scene, rd, gd, scene_instances, film, "pt_render_adaptive_light_groups_multi", error);
+    if (st != PT_OK) return st;
+    return normalize_adaptive_desc(*rd, *ad, sample_counts != nullptr, camera_count, rd_out, ad_out, error);
 }
 
 pt_status check_light_groups_matrices(uint32_t group_count, const float* matrices, std::string* error) {

@@ -157,6 +157,15 @@ pt_status check_light_groups_matrices(uint32_t group_count, const float* matrice
 pt_status check_light_groups_mix_args(uint32_t width, uint32_t height, uint32_t group_count, const void* group_films, const float* matrices, const void* out,
                                       std::string* error);
 
+// ---- include/pt_light_groups_multi.h, for the engine and the host emulation alike; every check runs before a device is looked for.
+// pt_render_light_groups_multi: everything check_light_groups_args refuses, with its words, except that a shard in the desc (shard_count != 0) is the node
+// entry's own PT_ERR_INVALID_ARGUMENT ("... deals the tiles itself: shard_count must be 0"); then normalize_render_desc's conditions; *rd_out as that leaves it.
+pt_status check_light_groups_multi_args(const void* scene, const pt_render_desc* rd, const pt_light_groups_desc* gd, uint32_t scene_instances, uint32_t camera_count,
+                                        const void* film, pt_render_desc* rd_out, std::string* error);
+// pt_render_adaptive_light_groups_multi: check_adaptive_light_groups_args with the same exchange of the shard refusal
+pt_status check_adaptive_light_groups_multi_args(const void* scene, const pt_render_desc* rd, const pt_adaptive_desc* ad, const pt_light_groups_desc* gd,
+                                                 uint32_t scene_instances, uint32_t camera_count, const void* film, const void* sample_counts, pt_render_desc* rd_out,
+                                                 pt_adaptive_desc* ad_out, std::string* error);
 
 // ---- include/pt_light_groups_denoise.h, for the engine and the host emulation alike; every check runs before a device is looked for.
 // pt_render_adaptive_light_groups: no null pointer (stats and group_films may be null), then everything check_light_groups_args refuses and everything

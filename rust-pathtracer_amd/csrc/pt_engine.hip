@@ -34,14 +34,12 @@
 #include "../../include/pt_light_groups_spectral.h"
 #include "pt_adaptive_select.h"
 #include "pt_light_groups_launch.h"
-#include "pt_light_groups_shard_launch.h"
-#include "pt_light_groups_shard_rules.h"
 #include "pt_light_groups_spectral_launch.h"
 #include "pt_spectral_launch.h"
 #include "pt_spectral_rules.h"
 #include "pt_spectral_project_launch.h"
-#include "pt_spectral_shard_launch.h"
-#include "pt_spectral_shard_rules.h"
+#include "pt_shard_launch.h"
+#include "pt_shard_rules.h"
 #include "pt_denoise_launch.h"
 #include "pt_denoise_resident_launch.h"
 #include "pt_error.h"
@@ -293,16 +291,14 @@ struct AdaptiveBuffers {
 }  // namespace
 
 // What the last adaptive node render (render_node) left where, for pt_resident_assemble (include/pt_resident.h): film, counts and statistics on `device`, the
-// first device of the mask, for a spectral render the scenes that hold the packed shards (shard_px, shard_packed), and for a group render the scenes that hold the
-// packed group films (group_shard_px, group_shard_packed) and their number of groups.  Kept with the MultiSetup whose films it points into: released with it.
-// Every render entry forgets it when it starts.
+// first device of the mask and, per kind of packed shard (a spectral render's bins in spectral_shard, a group render's films in group_shard), the scenes that hold
+// the shards and their number of planes.  Kept with the MultiSetup whose films it points into: released with it.  Every render entry forgets it when it starts.
 struct NodeRemembered {
     pth::NodeRender info;
     int device = 0;
     const float* film = nullptr; const uint32_t* counts = nullptr; const double* stats = nullptr;
-    std::vector<pt_scene*> shards;
-    std::vector<pt_scene*> group_shards;
-    uint32_t groups = 0;
+    struct Shards { std::vector<pt_scene*> scenes; uint32_t planes = 0; };
+    Shards spectral, groups;
 };
 
 // What pt_render_multi sets up for a set of devices and a film size, kept on the scene: a frame-by-frame caller pays for streams, device
@@ -315,7 +311,7 @@ struct MultiSetup {
     std::vector<float*> films;        // per virtual device, on its physical device
     std::vector<hipStream_t> streams; // per virtual device
     std::vector<ncclComm_t> comms;    // per physical device (rccl only)
-    std::vector<GrowBuf> staging;   // per virtual device: the pinned host buffer its packed spectral planes or packed group films land in (the spectral and the group node entries; grown on demand)
+    std::vector<GrowBuf> staging;   // per virtual device: the pinned host buffer its packed shard lands in (NodePayload: the spectral and the group node entries; grown on demand)
     NodeRemembered node_render;
     bool valid = false;
 };
@@ -337,6 +333,13 @@ struct ResidentSet {
         if (!parts) width = height = 0;
     }
     struct pt_resident_info info() const { struct pt_resident_info i; i.width = width; i.height = height; i.bins = bins; i.parts = parts; return i; }
+};
+
+// A scene's shard of a node render, kept on it (pt_shard_rules.h): px, the pixel list in pth::shard_pixels' order, and packed, the planes of px.size() elements
+// on its device that the pack kernel left (k_spectral_pack: floats; k_light_groups_pack: float4).
+struct Shard {
+    std::vector<uint32_t> px;
+    GrowBuf packed;
 };
 
 struct pt_scene {
@@ -366,11 +369,9 @@ struct pt_scene {
     uint32_t spectral_width = 0, spectral_height = 0, spectral_bins = 0;
     // After a node render (pt_render_spectral_multi / pt_render_adaptive_spectral_multi) the resident film is the set of packed shards instead: spectral_shards
     // (on the scene the call was made on) names the scenes that hold them — this one and its replicas, which live as long as it does; empty = spectral_cache.
-    // Each of those scenes keeps its own shard: shard_px, the pixel list in pth::shard_pixels' order, and shard_packed, spectral_bins planes of shard_px.size()
-    // floats on its device (k_spectral_pack's output).
+    // Each of those scenes keeps its own shard, spectral_shard: spectral_bins planes of floats.
     std::vector<pt_scene*> spectral_shards;
-    std::vector<uint32_t> shard_px;
-    GrowBuf shard_packed;
+    Shard spectral_shard;
     // The resident group films (include/pt_light_groups.h): what the last successful light-group render left in group_films_cache, group-major float4 films.  Cleared
     // when a group render starts and set when it has succeeded; the group renders (a node render's worker on its own scene or replica among them) and the group part of
     // pt_resident_assemble are the only writers of the buffer.  group_table: that render's one byte per
@@ -379,12 +380,11 @@ struct pt_scene {
     uint32_t groups_width = 0, groups_height = 0, groups_count = 0;
     GrowBuf group_films_cache, group_table, group_mix_cache;
     // After a node group render (include/pt_light_groups_multi.h) the resident group films are the set of packed shards instead: group_shards (on the scene the call
-    // was made on) names the scenes that hold them — this one and its replicas; empty = group_films_cache.  Each of those scenes keeps its own shard:
-    // group_shard_px, the pixel list in pth::shard_pixels' order (a list of its own: a spectral node render's shard_px may be of another film), and
-    // group_shard_packed, groups_count films of group_shard_px.size() float4 on its device (k_light_groups_pack's output).
+    // was made on) names the scenes that hold them — this one and its replicas; empty = group_films_cache.  Each of those scenes keeps its own shard,
+    // group_shard: groups_count films of float4.  A shard of its own, list included: a spectral node render's shard, resident at the same time, may be of
+    // another film size.
     std::vector<pt_scene*> group_shards;
-    std::vector<uint32_t> group_shard_px;
-    GrowBuf group_shard_packed;
+    Shard group_shard;
     // The resident group bins (include/pt_light_groups_spectral.h): what the last successful pt_render_light_groups_spectral left in group_bins_cache, group-major, then
     // bin-major planes of width * height floats.  Cleared when a group render of any kind starts (the other two leave none) and set when that render has succeeded;
     // it is the only writer of the buffer.  relamp_cache: pt_light_groups_relamp_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x 512 floats) and, behind it,
@@ -403,6 +403,21 @@ struct pt_scene {
     GrowBuf project_cache;         // pt_spectral_project_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x PT_SPECTRAL_MAX_BINS floats) and, behind it, its output planes
     std::vector<pt_scene*> replicas; // pt_render_multi: this scene on the other (virtual) devices, by device index x virtual index (nullptr = not made yet / this one)
 };
+
+// The two kinds of packed shard (pt_shard_rules.h): the element in floats, which of a scene's shards holds it, and which full-size buffer a render writes
+// and the pack kernel reads.
+struct ShardKind {
+    uint32_t floats;
+    Shard pt_scene::*shard;
+    GrowBuf pt_scene::*full;
+};
+static const ShardKind kSpectralShard = {1u, &pt_scene::spectral_shard, &pt_scene::spectral_cache};
+static const ShardKind kGroupShard = {4u, &pt_scene::group_shard, &pt_scene::group_films_cache};
+// a shard's packed planes back into full-size planes on the host, by the element of the kind
+static void shard_scatter_host(const ShardKind& kind, const void* packed, const std::vector<uint32_t>& px, uint32_t planes, float* full, size_t full_pixels) {
+    if (kind.floats == 1) ptd::shard_scatter(static_cast<const float*>(packed), px.data(), (uint32_t)px.size(), planes, full, full_pixels);
+    else ptd::shard_scatter(static_cast<const ptd::ShardPixel*>(packed), px.data(), (uint32_t)px.size(), planes, reinterpret_cast<ptd::ShardPixel*>(full), full_pixels);
+}
 
 namespace {
 // whether any instance of the flattened scene is a mesh (a scene without one never parks at a mesh: its top-level walks are the ones worth leaving early)
@@ -1691,171 +1706,115 @@ static std::string device_name(const Node& node, int v) {
     return "device " + std::to_string(node.devices[v / node.virt]) + (node.virt > 1 ? "." + std::to_string(v % node.virt) : "");
 }
 
-// The spectral film of a node call (pt_render_spectral_multi, pt_render_adaptive_spectral_multi).  The bins are never reduced: every
-// device packs the planes of its own tiles (k_spectral_pack), copies them to its pinned staging buffer and its host thread scatters them into the caller's
-// array; the packed planes stay on the device as its part of the scene's resident film.
-struct NodeSpectral {
-    uint32_t bins = 0;
-    size_t plane_pixels = 0;
-    float* host = nullptr;         // the caller's planes
+// The per-pixel payload of a node call beside its film: the bins of a spectral call (pt_render_spectral_multi, pt_render_adaptive_spectral_multi; DESIGN.md
+// section 14) or the group films of a group call (pt_render_light_groups_multi, pt_render_adaptive_light_groups_multi; DESIGN.md section 15 "On every device
+// of a node").  It is never reduced: every device packs the planes of its own tiles (k_spectral_pack, k_light_groups_pack), copies them to its pinned
+// staging buffer and its host thread scatters them into the caller's array; the packed planes stay on the device as its part of the scene's resident film
+// or group films.
+struct NodePayload {
+    const ShardKind* kind = nullptr;
+    uint32_t planes = 0;           // bins, or groups
+    size_t film_pixels = 0;
+    float* host = nullptr;         // the caller's planes (null, a group call's choice: nothing is copied to the host)
     std::vector<double> seconds;   // per worker: its pack, copy and scatter
 };
-// Part of the set-up: every device's pixel list (kept on its scene), full-size planes, packed planes and staging buffer, made once per size and kept.  A
-// shard without a pixel gets no buffer.  rd: normalised.
-static pt_status node_prepare_spectral(MultiSetup& m, const Node& node, const pt_render_desc& rd, uint32_t bins, float* spectral, NodeSpectral* ns) {
-    ns->bins = bins; ns->plane_pixels = (size_t)rd.width * rd.height; ns->host = spectral; ns->seconds.assign(node.n, 0.0);
+// Part of the set-up: every device's pixel list (kept on its scene), full-size planes, packed planes and — with a host array — staging buffer, made once per
+// size and kept.  A shard without a pixel gets no packed buffer.  rd: normalised.
+static pt_status node_prepare_payload(MultiSetup& m, const Node& node, const pt_render_desc& rd, const ShardKind& kind, uint32_t planes, float* host, NodePayload* np) {
+    np->kind = &kind; np->planes = planes; np->film_pixels = (size_t)rd.width * rd.height; np->host = host; np->seconds.assign(node.n, 0.0);
     for (int v = 0; v < node.n; ++v) {
         pt_scene* s = node.scene_of[v];
-        s->shard_px = pth::shard_pixels(rd.width, rd.height, rd.tile_width, rd.tile_height, node.n > 1 ? (uint32_t)v : 0u, node.n > 1 ? (uint32_t)node.n : 0u);
+        Shard& shard = s->*kind.shard;
+        shard.px = pth::shard_pixels(rd.width, rd.height, rd.tile_width, rd.tile_height, node.n > 1 ? (uint32_t)v : 0u, node.n > 1 ? (uint32_t)node.n : 0u);
         HIP_TRY(hipSetDevice(node.devices[v / node.virt]));
-        const size_t packed_bytes = sizeof(float) * bins * s->shard_px.size();
-        pt_status st = s->spectral_cache.reserve(sizeof(float) * bins * ns->plane_pixels);
-        if (st == PT_OK) st = s->shard_packed.reserve(packed_bytes);
-        if (st == PT_OK) st = m.staging[v].reserve(packed_bytes);
+        const size_t elem_bytes = sizeof(float) * kind.floats, packed_bytes = elem_bytes * planes * shard.px.size();
+        pt_status st = (s->*kind.full).reserve(elem_bytes * planes * np->film_pixels);
+        if (st == PT_OK) st = shard.packed.reserve(packed_bytes);
+        if (st == PT_OK && host) st = m.staging[v].reserve(packed_bytes);
         if (st != PT_OK) return st;
     }
     return PT_OK;
 }
 // Worker v behind its render (the stream is idle: render_impl synchronised it): pack by the list render_impl left in buf.pixels, copy, scatter.  The shards
-// are disjoint and cover the film (every pixel is in exactly one list: tests/test_spectral_multi.py), so the threads never write the same float and the
-// caller's array needs no zeroing.
-static pt_status node_spectral_exchange(MultiSetup& m, const Node& node, NodeSpectral& ns, int v) {
+// are disjoint and cover the film (every pixel is in exactly one list: tests/test_spectral_multi.py, tests/test_light_groups_multi.py), so the threads never
+// write the same element and the caller's array needs no zeroing.  Without a host array the pack still runs: the packed shard is what stays resident.
+static pt_status node_payload_exchange(MultiSetup& m, const Node& node, NodePayload& np, int v) {
     pt_scene* s = node.scene_of[v];
-    const uint32_t n_own = (uint32_t)s->shard_px.size();
+    const ShardKind& kind = *np.kind;
+    const Shard& shard = s->*kind.shard;
+    const uint32_t n_own = (uint32_t)shard.px.size();
     if (n_own == 0) return PT_OK;
     const auto t = std::chrono::steady_clock::now();
-    HIP_TRY(ptk::launch_spectral_pack(ptk::spectral_pack_grid(s->num_cus, n_own), m.streams[v], s->spectral_cache.as<float>(), (uint32_t)ns.plane_pixels, s->buf.pixels, n_own, ns.bins,
-                                      s->shard_packed.as<float>()));
-    HIP_TRY(hipMemcpyAsync(m.staging[v].p, s->shard_packed.p, sizeof(float) * ns.bins * n_own, hipMemcpyDeviceToHost, m.streams[v]));
+    HIP_TRY(ptk::launch_shard_pack(kind.floats, ptk::shard_pack_grid(s->num_cus, n_own), m.streams[v], (s->*kind.full).as<float>(), (uint32_t)np.film_pixels, s->buf.pixels, n_own,
+                                   np.planes, shard.packed.as<float>()));
+    if (np.host) HIP_TRY(hipMemcpyAsync(m.staging[v].p, shard.packed.p, sizeof(float) * kind.floats * np.planes * n_own, hipMemcpyDeviceToHost, m.streams[v]));
     HIP_TRY(hipStreamSynchronize(m.streams[v]));
-    spectral_shard_scatter(m.staging[v].as<float>(), s->shard_px.data(), n_own, ns.bins, ns.host, ns.plane_pixels);
-    ns.seconds[v] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+    if (np.host) shard_scatter_host(kind, m.staging[v].p, shard.px, np.planes, np.host, np.film_pixels);
+    np.seconds[v] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
     return PT_OK;
 }
-static double node_spectral_seconds(const NodeSpectral& ns) { return ns.seconds.empty() ? 0.0 : *std::max_element(ns.seconds.begin(), ns.seconds.end()); }
-// the node render has succeeded: the scene's resident film is the packed shards
-static void node_spectral_resident(pt_scene* sc, const Node& node, const pt_render_desc& rd, uint32_t bins) {
-    sc->spectral_shards = node.scene_of;
-    sc->spectral_width = rd.width; sc->spectral_height = rd.height; sc->spectral_bins = bins; sc->spectral_valid = true;
-}
+static double node_payload_seconds(const NodePayload& np) { return np.seconds.empty() ? 0.0 : *std::max_element(np.seconds.begin(), np.seconds.end()); }
 
-// pt_spectral_project_resident of a node-resident film: the matrix to every device that holds a shard, pt_spectral_project's kernel over the shard's packed
-// planes (plane stride n_own), K * n_own floats back per device, scattered by the rule the bins were scattered by.
-static pt_status project_resident_node(pt_scene* sc, uint32_t K, const float* matrix, float* out) {
+// A kernel over node-resident shards where they lie: `matrix_bytes` of `matrix` to every device that holds a shard of `shards`, into the scene's `cache` (the
+// matrix at its cap size, matrix_floats, then the output); `launch(s, n_own, d_matrix, packed, d_out)` over the shard's packed planes (plane stride n_own);
+// out_planes * n_own elements of `kind` back per device, scattered into `out` by the rule the shards were scattered by.
+using ShardLaunch = std::function<hipError_t(pt_scene* s, uint32_t n_own, const float* d_matrix, const float* packed, float* d_out)>;
+static pt_status run_resident_shards(const std::vector<pt_scene*>& shards, const ShardKind& kind, uint32_t out_planes, size_t film_pixels, const float* matrix,
+                                     size_t matrix_bytes, size_t matrix_floats, GrowBuf pt_scene::*cache, float* out, const ShardLaunch& launch) {
     DeviceGuard guard;
-    const size_t plane_pixels = (size_t)sc->spectral_width * sc->spectral_height, matrix_floats = (size_t)PT_SPECTRAL_MAX_RESPONSES * PT_SPECTRAL_MAX_BINS;
-    std::vector<std::vector<float>> planes(sc->spectral_shards.size());
-    for (size_t v = 0; v < sc->spectral_shards.size(); ++v) {
-        pt_scene* s = sc->spectral_shards[v];
-        const uint32_t n_own = (uint32_t)s->shard_px.size();
+    std::vector<std::vector<float>> back(shards.size());
+    for (size_t v = 0; v < shards.size(); ++v) {
+        pt_scene* s = shards[v];
+        const Shard& shard = s->*kind.shard;
+        const uint32_t n_own = (uint32_t)shard.px.size();
         if (n_own == 0) continue;
         HIP_TRY(hipSetDevice(s->device));
-        const pt_status st = s->project_cache.reserve(sizeof(float) * (matrix_floats + (size_t)K * n_own));
+        const size_t out_floats = (size_t)kind.floats * out_planes * n_own;
+        const pt_status st = (s->*cache).reserve(sizeof(float) * (matrix_floats + out_floats));
         if (st != PT_OK) return st;
-        planes[v].resize((size_t)K * n_own);
-        float* d_matrix = s->project_cache.as<float>();
+        back[v].resize(out_floats);
+        float* d_matrix = (s->*cache).as<float>();
         float* d_out = d_matrix + matrix_floats;
-        HIP_TRY(hipMemcpyAsync(d_matrix, matrix, sizeof(float) * K * sc->spectral_bins, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(ptk::launch_spectral_project(ptk::spectral_project_grid(s->num_cus, n_own), nullptr, n_own, sc->spectral_bins, K, d_matrix, s->shard_packed.as<float>(), d_out));
-        HIP_TRY(hipMemcpyAsync(planes[v].data(), d_out, sizeof(float) * K * n_own, hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipMemcpyAsync(d_matrix, matrix, matrix_bytes, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(launch(s, n_own, d_matrix, shard.packed.as<float>(), d_out));
+        HIP_TRY(hipMemcpyAsync(back[v].data(), d_out, sizeof(float) * out_floats, hipMemcpyDeviceToHost, nullptr));
     }
-    for (size_t v = 0; v < sc->spectral_shards.size(); ++v) {
-        pt_scene* s = sc->spectral_shards[v];
-        if (s->shard_px.empty()) continue;
+    for (size_t v = 0; v < shards.size(); ++v) {
+        pt_scene* s = shards[v];
+        const Shard& shard = s->*kind.shard;
+        if (shard.px.empty()) continue;
         HIP_TRY(hipSetDevice(s->device));
         HIP_TRY(hipStreamSynchronize(nullptr));
-        spectral_shard_scatter(planes[v].data(), s->shard_px.data(), (uint32_t)s->shard_px.size(), K, out, plane_pixels);
+        shard_scatter_host(kind, back[v].data(), shard.px, out_planes, out, film_pixels);
     }
     return PT_OK;
 }
-
-// The group films of a node call (pt_render_light_groups_multi, pt_render_adaptive_light_groups_multi; DESIGN.md section 15 "On every device of a node").  Like the
-// bins they are never reduced: every device packs the pixels of its own tiles (k_light_groups_pack), copies them to its pinned staging buffer and its host thread
-// scatters them into the caller's array; the packed films stay on the device as its part of the scene's resident group films.
-struct NodeGroups {
-    const pt_light_groups_desc* gd = nullptr;
-    size_t film_pixels = 0;
-    float* host = nullptr;         // the caller's group films (null: nothing is copied to the host)
-    std::vector<double> seconds;   // per worker: its pack, copy and scatter
-};
-// Part of the set-up: every device's pixel list (kept on its scene), the group table's bytes, full-size group films, packed films and staging buffer, made once
-// per size and kept.  A shard without a pixel gets no packed buffer.  rd: normalised.
-static pt_status node_prepare_groups(MultiSetup& m, const Node& node, const pt_render_desc& rd, const pt_light_groups_desc* gd, float* group_films, NodeGroups* ng) {
-    ng->gd = gd; ng->film_pixels = (size_t)rd.width * rd.height; ng->host = group_films; ng->seconds.assign(node.n, 0.0);
-    for (int v = 0; v < node.n; ++v) {
-        pt_scene* s = node.scene_of[v];
-        s->group_shard_px = pth::shard_pixels(rd.width, rd.height, rd.tile_width, rd.tile_height, node.n > 1 ? (uint32_t)v : 0u, node.n > 1 ? (uint32_t)node.n : 0u);
-        HIP_TRY(hipSetDevice(node.devices[v / node.virt]));
-        const size_t packed_bytes = sizeof(float) * 4 * gd->group_count * s->group_shard_px.size();
-        pt_status st = s->group_films_cache.reserve(sizeof(float) * 4 * gd->group_count * ng->film_pixels);
-        if (st == PT_OK) st = s->group_table.reserve(gd->instance_count ? gd->instance_count : 1u);
-        if (st == PT_OK && packed_bytes) st = s->group_shard_packed.reserve(packed_bytes);
-        if (st == PT_OK && packed_bytes && group_films) st = m.staging[v].reserve(packed_bytes);
-        if (st != PT_OK) return st;
-        if (gd->instance_count) HIP_TRY(hipMemcpy(s->group_table.p, gd->instance_group, gd->instance_count, hipMemcpyHostToDevice));
-    }
-    return PT_OK;
+// pt_spectral_project_resident of a node-resident film: pt_spectral_project's kernel over every shard's packed bins, K planes of floats back.
+static pt_status project_resident_node(pt_scene* sc, uint32_t K, const float* matrix, float* out) {
+    const uint32_t bins = sc->spectral_bins;
+    return run_resident_shards(sc->spectral_shards, kSpectralShard, K, (size_t)sc->spectral_width * sc->spectral_height, matrix, sizeof(float) * K * bins,
+                               (size_t)PT_SPECTRAL_MAX_RESPONSES * PT_SPECTRAL_MAX_BINS, &pt_scene::project_cache, out,
+                               [&](pt_scene* s, uint32_t n_own, const float* d_matrix, const float* packed, float* d_out) {
+                                   return ptk::launch_spectral_project(ptk::spectral_project_grid(s->num_cus, n_own), nullptr, n_own, bins, K, d_matrix, packed, d_out);
+                               });
 }
-// Worker v behind its render (the stream is idle: render_impl synchronised it): pack by the list render_impl left in buf.pixels, copy, scatter.  The shards are
-// disjoint and cover the film (every pixel is in exactly one list: tests/test_light_groups_multi.py), so the threads never write the same pixel and the caller's
-// array needs no zeroing.  Without a host array the pack still runs: the packed shard is what stays resident.
-static pt_status node_groups_exchange(MultiSetup& m, const Node& node, NodeGroups& ng, int v) {
-    pt_scene* s = node.scene_of[v];
-    const uint32_t n_own = (uint32_t)s->group_shard_px.size(), G = ng.gd->group_count;
-    if (n_own == 0) return PT_OK;
-    const auto t = std::chrono::steady_clock::now();
-    HIP_TRY(ptk::launch_light_groups_pack(ptk::light_groups_pack_grid(s->num_cus, n_own), m.streams[v], s->group_films_cache.as<float>(), (uint32_t)ng.film_pixels, s->buf.pixels, n_own, G,
-                                          s->group_shard_packed.as<float>()));
-    if (ng.host) HIP_TRY(hipMemcpyAsync(m.staging[v].p, s->group_shard_packed.p, sizeof(float) * 4 * G * n_own, hipMemcpyDeviceToHost, m.streams[v]));
-    HIP_TRY(hipStreamSynchronize(m.streams[v]));
-    if (ng.host) lg_shard_scatter(m.staging[v].as<LgPixel>(), s->group_shard_px.data(), n_own, G, reinterpret_cast<LgPixel*>(ng.host), ng.film_pixels);
-    ng.seconds[v] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-    return PT_OK;
-}
-static double node_groups_seconds(const NodeGroups& ng) { return ng.seconds.empty() ? 0.0 : *std::max_element(ng.seconds.begin(), ng.seconds.end()); }
-// the node render has succeeded: the scene's resident group films are the packed shards, paired with no resident film
-static void node_groups_resident(pt_scene* sc, const Node& node, const pt_render_desc& rd, uint32_t groups) {
-    sc->group_shards = node.scene_of;
-    sc->groups_width = rd.width; sc->groups_height = rd.height; sc->groups_count = groups; sc->groups_valid = true;
-}
-
-// pt_light_groups_mix_resident of node-resident group films: the matrices to every device that holds a shard, pt_light_groups_mix's kernel over the shard's packed
-// films (group stride n_own), n_own pixels back per device, scattered by the rule the group films were scattered by (one film: G = 1).
+// pt_light_groups_mix_resident of node-resident group films: pt_light_groups_mix's kernel over every shard's packed films, one film of pixels back.
 static pt_status mix_resident_node(pt_scene* sc, const float* matrices, float* out) {
     std::string err;
     const pt_status checked = pth::check_light_groups_matrices(sc->groups_count, matrices, &err);
     if (checked != PT_OK) return fail(checked, err);
-    DeviceGuard guard;
-    const size_t film_pixels = (size_t)sc->groups_width * sc->groups_height, matrix_floats = (size_t)PT_LIGHT_GROUPS_MAX * 12;   // (the film behind them stays 16-byte aligned)
-    std::vector<std::vector<LgPixel>> mixed(sc->group_shards.size());
-    for (size_t v = 0; v < sc->group_shards.size(); ++v) {
-        pt_scene* s = sc->group_shards[v];
-        const uint32_t n_own = (uint32_t)s->group_shard_px.size();
-        if (n_own == 0) continue;
-        HIP_TRY(hipSetDevice(s->device));
-        const pt_status st = s->group_mix_cache.reserve(sizeof(float) * (matrix_floats + 4 * (size_t)n_own));
-        if (st != PT_OK) return st;
-        mixed[v].resize(n_own);
-        float* d_matrices = s->group_mix_cache.as<float>();
-        float* d_out = d_matrices + matrix_floats;
-        HIP_TRY(hipMemcpyAsync(d_matrices, matrices, sizeof(float) * 9 * sc->groups_count, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(ptk::launch_light_groups_mix(nullptr, n_own, sc->groups_count, s->group_shard_packed.as<float>(), d_matrices, d_out));
-        HIP_TRY(hipMemcpyAsync(mixed[v].data(), d_out, sizeof(float) * 4 * n_own, hipMemcpyDeviceToHost, nullptr));
-    }
-    for (size_t v = 0; v < sc->group_shards.size(); ++v) {
-        pt_scene* s = sc->group_shards[v];
-        if (s->group_shard_px.empty()) continue;
-        HIP_TRY(hipSetDevice(s->device));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        lg_shard_scatter(mixed[v].data(), s->group_shard_px.data(), (uint32_t)s->group_shard_px.size(), 1u, reinterpret_cast<LgPixel*>(out), film_pixels);
-    }
-    return PT_OK;
+    const uint32_t groups = sc->groups_count;
+    return run_resident_shards(sc->group_shards, kGroupShard, 1u, (size_t)sc->groups_width * sc->groups_height, matrices, sizeof(float) * 9 * groups,
+                               (size_t)PT_LIGHT_GROUPS_MAX * 12 /* (the film behind them stays 16-byte aligned) */, &pt_scene::group_mix_cache, out,
+                               [&](pt_scene*, uint32_t n_own, const float* d_matrices, const float* packed, float* d_out) {
+                                   return ptk::launch_light_groups_mix(nullptr, n_own, groups, packed, d_matrices, d_out);
+                               });
 }
 
 // The node driver behind the six node entries (call: as for render_one): one worker per (virtual) device renders its shard of the film, the films are gathered
 // on the first device of the mask and read back from there.  An adaptive call (pt_render_adaptive_multi) runs its rounds in lockstep over the NodeRounds and
-// gathers counts and statistics too; a spectral call hands every worker's bins over by node_spectral_exchange and leaves the packed shards resident; a group
-// call does the same with every worker's group films (node_groups_exchange).
+// gathers counts and statistics too; a spectral call hands every worker's bins over by node_payload_exchange and leaves the packed shards resident; a group
+// call does the same with every worker's group films.
 static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t device_mask, pt_profile* profile) {
     const pt_render_desc& rd = *call.rd;
     const bool adaptive = call.ad != nullptr;
@@ -1880,14 +1839,19 @@ static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t devi
         st = ensure_adaptive_buffers(node.scene_of[v], pixels);
         if (st != PT_OK) return st;
     }
-    NodeSpectral ns;
+    NodePayload ns, ng;   // (no node entry has both today)
     if (call.sd) {
-        st = node_prepare_spectral(m, node, rd, call.sd->bins, call.spectral, &ns);
+        st = node_prepare_payload(m, node, rd, kSpectralShard, call.sd->bins, call.spectral, &ns);
         if (st != PT_OK) return st;
     }
-    NodeGroups ng;
     if (call.gd) {
-        st = node_prepare_groups(m, node, rd, call.gd, call.group_films, &ng);
+        st = node_prepare_payload(m, node, rd, kGroupShard, call.gd->group_count, call.group_films, &ng);
+        for (int v = 0; v < n && st == PT_OK; ++v) {   // (the group table's bytes on every device)
+            pt_scene* s = node.scene_of[v];
+            HIP_TRY(hipSetDevice(node.devices[v / virt]));
+            st = s->group_table.reserve(call.gd->instance_count ? call.gd->instance_count : 1u);
+            if (st == PT_OK && call.gd->instance_count) HIP_TRY(hipMemcpy(s->group_table.p, call.gd->instance_group, call.gd->instance_count, hipMemcpyHostToDevice));
+        }
         if (st != PT_OK) return st;
     }
     NodeRounds nr;
@@ -1942,13 +1906,13 @@ static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t devi
         pt_scene* s = node.scene_of[v];
         RenderJob job;
         if (adaptive) { job.adaptive = call.ad; job.node = &nr; job.node_index = v; }
-        if (call.sd) { job.d_spectral = s->spectral_cache.as<float>(); job.spectral_bins = call.sd->bins; job.shard_list = &s->shard_px; }
+        if (call.sd) { job.d_spectral = s->spectral_cache.as<float>(); job.spectral_bins = call.sd->bins; job.shard_list = &s->spectral_shard.px; }
         // (a shard together with groups: the one-device entries refuse it in check_light_groups_args, which this driver's callers do not run on a worker's desc)
         const LightGroupTable table{s->group_table.as<uint8_t>(), call.gd ? call.gd->environment_group : 0u, call.gd ? call.gd->group_count : 0u};
-        if (call.gd) { job.groups = &table; job.d_group_films = s->group_films_cache.as<float>(); job.shard_list = &s->group_shard_px; }
+        if (call.gd) { job.groups = &table; job.d_group_films = s->group_films_cache.as<float>(); job.shard_list = &s->group_shard.px; }
         if (s2 == PT_OK) s2 = render_impl(s, &rv, m.films[v], m.streams[v], &profiles[v], job);
-        if (s2 == PT_OK && call.sd) s2 = node_spectral_exchange(m, node, ns, v);
-        if (s2 == PT_OK && call.gd) s2 = node_groups_exchange(m, node, ng, v);
+        if (s2 == PT_OK && call.sd) s2 = node_payload_exchange(m, node, ns, v);
+        if (s2 == PT_OK && call.gd) s2 = node_payload_exchange(m, node, ng, v);
         if (s2 == PT_OK) return;
         status[v] = s2; errors[v] = device_name(node, v) + ": " + g_error;   // (g_error is thread-local: carried back to the caller below)
         if (adaptive) nr.lock.stop(s2, errors[v]);   // (a worker stopped by another's failure finds the first error kept)
@@ -1979,18 +1943,25 @@ static pt_status render_node(pt_scene* sc, const RenderCall& call, uint64_t devi
         if (adaptive) profile->kernel_launches[5] = profiles[0].kernel_launches[5];                        // the rounds (every device ran them all)
         profile->kernel_seconds[5] = std::chrono::duration<double>(t0 - t_entry).count();    // set-up (replicas, streams, films, communicator): ~0 on a repeated call
         // the rounds' exchanges (adaptive) + the film reduce or gather (+ the longest pack, copy and scatter)
-        profile->kernel_seconds[6] = nr.exchange_seconds + std::chrono::duration<double>(t_gathered - t_gather).count() + node_spectral_seconds(ns) + node_groups_seconds(ng);
+        profile->kernel_seconds[6] = nr.exchange_seconds + std::chrono::duration<double>(t_gathered - t_gather).count() + node_payload_seconds(ns) + node_payload_seconds(ng);
     }
-    if (call.sd) node_spectral_resident(sc, node, rd, call.sd->bins);
-    if (call.gd) node_groups_resident(sc, node, rd, call.gd->group_count);
+    // the node render has succeeded: the scene's resident film, or its resident group films (paired with no resident film), are the packed shards
+    if (call.sd) {
+        sc->spectral_shards = node.scene_of;
+        sc->spectral_width = rd.width; sc->spectral_height = rd.height; sc->spectral_bins = call.sd->bins; sc->spectral_valid = true;
+    }
+    if (call.gd) {
+        sc->group_shards = node.scene_of;
+        sc->groups_width = rd.width; sc->groups_height = rd.height; sc->groups_count = call.gd->group_count; sc->groups_valid = true;
+    }
     if (adaptive) {   // where the pieces lie, for pt_resident_assemble: no device work, and nothing is resident (include/pt_resident.h)
         NodeRemembered& k = m.node_render;
         k.info.valid = true; k.info.stats = call.stats != nullptr;
         k.info.width = rd.width; k.info.height = rd.height; k.info.bins = call.sd ? call.sd->bins : 0u;
         k.device = node.devices[0];
         k.film = m.films[0]; k.counts = node.scene_of[0]->adaptive.counts; k.stats = node.scene_of[0]->adaptive.stats;
-        if (call.sd) k.shards = node.scene_of;
-        if (call.gd) { k.group_shards = node.scene_of; k.groups = call.gd->group_count; }
+        if (call.sd) k.spectral = {node.scene_of, call.sd->bins};
+        if (call.gd) k.groups = {node.scene_of, call.gd->group_count};
     }
     return PT_OK;
 }
@@ -2408,24 +2379,26 @@ pt_status pt_resident_assemble(pt_scene* sc, uint32_t flags) {
     // a shard is staged when it lies on another device (or every one, on request); its pixel list is uploaded unless a replica on this device still holds it
     const auto staged = [&](const pt_scene* s) { return staged_all || s->device != sc->device; };
     const auto listed = [&](const pt_scene* s) { return s != sc && s->device == sc->device; };
-    size_t staging_floats = 0, px_words = 0;
-    for (const pt_scene* s : k.shards) {
-        if (staged(s)) staging_floats += (size_t)bins * s->shard_px.size();
-        if (!listed(s)) px_words += s->shard_px.size();
-    }
-    // (a group render's shards, behind the bins' on a 16-byte boundary: pixels of four floats)
-    const uint32_t groups = k.groups;
-    const size_t group_stage_first = (staging_floats + 3) & ~(size_t)3;
-    for (const pt_scene* s : k.group_shards) {
-        if (staged(s)) staging_floats = (staging_floats > group_stage_first ? staging_floats : group_stage_first) + 4 * (size_t)groups * s->group_shard_px.size();
-        if (!listed(s)) px_words += s->group_shard_px.size();
-    }
-    if (!k.group_shards.empty()) end_group_films(sc);   // (the shards are unpacked below: on any failure no group films are resident)
+    // what the shards of a kind need: floats of staging and words of uploaded lists
+    const auto need = [&](const NodeRemembered::Shards& set, const ShardKind& kind, size_t* staging_floats, size_t* px_words) {
+        for (const pt_scene* s : set.scenes) {
+            const size_t n_own = (s->*kind.shard).px.size();
+            if (staged(s)) *staging_floats += (size_t)kind.floats * set.planes * n_own;
+            if (!listed(s)) *px_words += n_own;
+        }
+    };
+    // (a group render's shards are staged behind the bins' on a 16-byte boundary: pixels of four floats)
+    size_t bin_floats = 0, group_floats = 0, px_words = 0;
+    need(k.spectral, kSpectralShard, &bin_floats, &px_words);
+    need(k.groups, kGroupShard, &group_floats, &px_words);
+    const uint32_t groups = k.groups.planes;
+    const size_t group_stage_first = (bin_floats + 3) & ~(size_t)3, staging_floats = group_floats ? group_stage_first + group_floats : bin_floats;
+    if (!k.groups.scenes.empty()) end_group_films(sc);   // (the shards are unpacked below: on any failure no group films are resident)
     st = r.load_film.reserve(16 * np);
     if (st == PT_OK) st = r.load_counts.reserve(4 * np);
     if (st == PT_OK) st = r.load_stats.reserve(16 * np);
     if (st == PT_OK && bins) st = r.load_spectral.reserve(4 * np * bins);
-    if (st == PT_OK && !k.group_shards.empty()) st = sc->group_films_cache.reserve(16 * np * groups);
+    if (st == PT_OK && !k.groups.scenes.empty()) st = sc->group_films_cache.reserve(16 * np * groups);
     if (st == PT_OK && staging_floats) st = sc->assemble_staging.reserve(sizeof(float) * staging_floats);
     if (st == PT_OK && px_words) st = sc->assemble_px.reserve(sizeof(uint32_t) * px_words);
     if (st != PT_OK) return st;
@@ -2437,50 +2410,40 @@ pt_status pt_resident_assemble(pt_scene* sc, uint32_t flags) {
     HIP_TRY(film_copy(r.load_film.p, k.film, 16 * np));
     HIP_TRY(film_copy(r.load_counts.p, k.counts, 4 * np));
     HIP_TRY(film_copy(r.load_stats.p, k.stats, 16 * np));
-    float* stage = sc->assemble_staging.as<float>();
     uint32_t* lists = sc->assemble_px.as<uint32_t>();
-    for (const pt_scene* s : k.shards) {
-        const uint32_t n_own = (uint32_t)s->shard_px.size();
-        if (n_own == 0) continue;   // (a shard without a pixel moves nothing and launches nothing)
-        const float* packed = s->shard_packed.as<float>();
-        if (staged(s)) {
-            HIP_TRY(hipMemcpyPeerAsync(stage, sc->device, packed, s->device, sizeof(float) * bins * n_own, stream));   // (legal within one device too)
-            packed = stage;
-            stage += (size_t)bins * n_own;
+    // the shards of a kind unpacked into `full`, staged from `stage` on
+    const auto unpack = [&](const NodeRemembered::Shards& set, const ShardKind& kind, float* stage, float* full) -> pt_status {
+        for (const pt_scene* s : set.scenes) {
+            const Shard& shard = s->*kind.shard;
+            const uint32_t n_own = (uint32_t)shard.px.size();
+            if (n_own == 0) continue;   // (a shard without a pixel moves nothing and launches nothing)
+            const size_t floats = (size_t)kind.floats * set.planes * n_own;
+            const float* packed = shard.packed.as<float>();
+            if (staged(s)) {
+                HIP_TRY(hipMemcpyPeerAsync(stage, sc->device, packed, s->device, sizeof(float) * floats, stream));   // (legal within one device too)
+                packed = stage;
+                stage += floats;
+            }
+            const uint32_t* px = s->buf.pixels;   // (the list its render left there)
+            if (!listed(s)) {
+                HIP_TRY(hipMemcpyAsync(lists, shard.px.data(), sizeof(uint32_t) * n_own, hipMemcpyHostToDevice, stream));
+                px = lists;
+                lists += n_own;
+            }
+            HIP_TRY(ptk::launch_shard_unpack(kind.floats, ptk::shard_pack_grid(sc->num_cus, n_own), stream, packed, px, n_own, set.planes, full, (uint32_t)np));
         }
-        const uint32_t* px = s->buf.pixels;   // (the list its render left there)
-        if (!listed(s)) {
-            HIP_TRY(hipMemcpyAsync(lists, s->shard_px.data(), sizeof(uint32_t) * n_own, hipMemcpyHostToDevice, stream));
-            px = lists;
-            lists += n_own;
-        }
-        HIP_TRY(ptk::launch_spectral_unpack(ptk::spectral_pack_grid(sc->num_cus, n_own), stream, packed, px, n_own, bins, r.load_spectral.as<float>(), (uint32_t)np));
-    }
-    // the group films of an adaptive node group render, into the buffer a one-device group render leaves them in: the same walk over the group shards
-    stage = sc->assemble_staging.as<float>() + group_stage_first;
-    for (const pt_scene* s : k.group_shards) {
-        const uint32_t n_own = (uint32_t)s->group_shard_px.size();
-        if (n_own == 0) continue;
-        const float* packed = s->group_shard_packed.as<float>();
-        if (staged(s)) {
-            HIP_TRY(hipMemcpyPeerAsync(stage, sc->device, packed, s->device, sizeof(float) * 4 * groups * n_own, stream));
-            packed = stage;
-            stage += 4 * (size_t)groups * n_own;
-        }
-        const uint32_t* px = s->buf.pixels;
-        if (!listed(s)) {
-            HIP_TRY(hipMemcpyAsync(lists, s->group_shard_px.data(), sizeof(uint32_t) * n_own, hipMemcpyHostToDevice, stream));
-            px = lists;
-            lists += n_own;
-        }
-        HIP_TRY(ptk::launch_light_groups_unpack(ptk::light_groups_pack_grid(sc->num_cus, n_own), stream, packed, px, n_own, groups, sc->group_films_cache.as<float>(), (uint32_t)np));
-    }
+        return PT_OK;
+    };
+    st = unpack(k.spectral, kSpectralShard, sc->assemble_staging.as<float>(), r.load_spectral.as<float>());
+    // the group films of an adaptive node group render, into the buffer a one-device group render leaves them in
+    if (st == PT_OK) st = unpack(k.groups, kGroupShard, sc->assemble_staging.as<float>() + group_stage_first, sc->group_films_cache.as<float>());
+    if (st != PT_OK) return st;
     HIP_TRY(hipStreamSynchronize(stream));
     r.parts = PT_RESIDENT_FILM | (bins ? PT_RESIDENT_BINS : 0u);
     r.width = k.info.width; r.height = k.info.height; r.bins = bins;
     r.film = r.load_film.as<float>(); r.counts = r.load_counts.as<uint32_t>(); r.stats = r.load_stats.as<double>();
     r.spectral = bins ? r.load_spectral.as<float>() : nullptr;
-    if (!k.group_shards.empty()) {   // (the group films lie beside the film they were rendered with, as after pt_render_adaptive_light_groups)
+    if (!k.groups.scenes.empty()) {   // (the group films lie beside the film they were rendered with, as after pt_render_adaptive_light_groups)
         sc->groups_width = k.info.width; sc->groups_height = k.info.height; sc->groups_count = groups;
         sc->groups_valid = true; sc->groups_paired = true;
     }

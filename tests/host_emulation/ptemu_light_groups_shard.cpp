@@ -1,14 +1,14 @@
 // ptemu_light_groups_shard.cpp — TEST HARNESS: the packed shard of the group node entries (include/pt_light_groups_multi.h, DESIGN.md section 15 "On every
 // device of a node") on the CPU.  A library of its own beside pt_plan.cpp (tests/test_light_groups_multi.py builds it); not part of the product.
 //
-// Its entry points run the engine's own text over arrays the caller gives: pt_light_groups_shard_rules.h (what k_light_groups_pack and k_light_groups_unpack do
+// Its entry points run the engine's own text over arrays the caller gives: pt_shard_rules.h (what k_light_groups_pack and k_light_groups_unpack do
 // lane after lane, and the host scatter of the node entries), pth::shard_pixels, and the pth::check_* functions the node entries call before they look for a
-// device.  The pixels are moved as LgPixel, four floats at a float's alignment: what the engine's host threads move.
+// device.  The pixels are moved as ShardPixel, four floats at a float's alignment: what the engine's host threads move.
 #include <string>
 #include <vector>
 
 #include "../../rust-pathtracer_amd/csrc/pt_plan.h"
-#include "../../rust-pathtracer_amd/csrc/pt_light_groups_shard_rules.h"
+#include "../../rust-pathtracer_amd/csrc/pt_shard_rules.h"
 #include "../../include/pt_light_groups_multi.h"
 
 using namespace ptd;
@@ -29,18 +29,18 @@ uint32_t ptemu_lg_shard_pixels(uint32_t width, uint32_t height, uint32_t tile_w,
 // one launch of k_light_groups_pack: every item of the list, in lane order
 void ptemu_light_groups_shard_pack(const float* group_films, uint32_t film_pixels, const uint32_t* px, uint32_t n_own, uint32_t groups, float* packed) {
     for (uint32_t i = 0; i < n_own; ++i)
-        lg_shard_pack_item(reinterpret_cast<const LgPixel*>(group_films), film_pixels, px, n_own, groups, i, reinterpret_cast<LgPixel*>(packed));
+        shard_pack_item(reinterpret_cast<const ShardPixel*>(group_films), film_pixels, px, n_own, groups, i, reinterpret_cast<ShardPixel*>(packed));
 }
 
 // what a worker of the node entries does with its staging buffer (and, with groups = 1, what the node-resident mix does with a shard's mixed pixels)
 void ptemu_light_groups_shard_scatter(const float* packed, const uint32_t* px, uint32_t n_own, uint32_t groups, float* group_films, uint32_t film_pixels) {
-    lg_shard_scatter(reinterpret_cast<const LgPixel*>(packed), px, n_own, groups, reinterpret_cast<LgPixel*>(group_films), film_pixels);
+    shard_scatter(reinterpret_cast<const ShardPixel*>(packed), px, n_own, groups, reinterpret_cast<ShardPixel*>(group_films), film_pixels);
 }
 
 // one launch of k_light_groups_unpack (pt_resident_assemble): every item of the list, in lane order
 void ptemu_light_groups_shard_unpack(const float* packed, const uint32_t* px, uint32_t n_own, uint32_t groups, float* group_films, uint32_t film_pixels) {
     for (uint32_t i = 0; i < n_own; ++i)
-        lg_shard_unpack_item(reinterpret_cast<const LgPixel*>(packed), px, n_own, groups, i, reinterpret_cast<LgPixel*>(group_films), film_pixels);
+        shard_unpack_item(reinterpret_cast<const ShardPixel*>(packed), px, n_own, groups, i, reinterpret_cast<ShardPixel*>(group_films), film_pixels);
 }
 
 // the argument checks of pt_render_light_groups_multi and pt_render_adaptive_light_groups_multi (the scene is only compared with null)

@@ -1,13 +1,13 @@
 // ptemu_spectral_shard.cpp — TEST HARNESS: the packed shard of the spectral node entries (include/pt_spectral.h) on the CPU.  A library
 // of its own beside pt_plan.cpp (tests/test_spectral_multi.py builds it); not part of the product.
 //
-// Its entry points run the engine's own text over arrays the caller gives: pt_spectral_shard_rules.h (what k_spectral_pack does lane after lane, and the host
+// Its entry points run the engine's own text over arrays the caller gives: pt_shard_rules.h (what k_spectral_pack does lane after lane, and the host
 // scatter of the node entries), pth::shard_pixels, and the pth::check_* functions the node entries call before they look for a device.
 #include <string>
 #include <vector>
 
 #include "../../rust-pathtracer_amd/csrc/pt_plan.h"
-#include "../../rust-pathtracer_amd/csrc/pt_spectral_shard_rules.h"
+#include "../../rust-pathtracer_amd/csrc/pt_shard_rules.h"
 #include "../../include/pt_spectral.h"
 
 using namespace ptd;
@@ -27,12 +27,12 @@ uint32_t ptemu_shard_pixels(uint32_t width, uint32_t height, uint32_t tile_w, ui
 
 // one launch of k_spectral_pack: every item of the list, in lane order
 void ptemu_spectral_shard_pack(const float* planes, uint32_t plane_pixels, const uint32_t* px, uint32_t n_own, uint32_t bins, float* packed) {
-    for (uint32_t i = 0; i < n_own; ++i) spectral_shard_pack_item(planes, plane_pixels, px, n_own, bins, i, packed);
+    for (uint32_t i = 0; i < n_own; ++i) shard_pack_item(planes, plane_pixels, px, n_own, bins, i, packed);
 }
 
 // what a worker of the node entries does with its staging buffer
 void ptemu_spectral_shard_scatter(const float* packed, const uint32_t* px, uint32_t n_own, uint32_t bins, float* planes, uint32_t plane_pixels) {
-    spectral_shard_scatter(packed, px, n_own, bins, planes, plane_pixels);
+    shard_scatter(packed, px, n_own, bins, planes, plane_pixels);
 }
 
 // the argument checks of pt_render_spectral_multi and pt_render_adaptive_spectral_multi (the scene is only compared with null)

@@ -1,7 +1,7 @@
 """Light groups on every device of a node (pt_render_light_groups_multi, pt_render_adaptive_light_groups_multi, include/pt_light_groups_multi.h, DESIGN.md section
 15 "On every device of a node").  Every device packs the group films of its own tiles (k_light_groups_pack), hands them to the host itself and keeps them as its
 part of the scene's resident group films; nothing is reduced.  The CPU tier checks the pack, scatter and unpack rule the kernels compile
-(csrc/pt_light_groups_shard_rules.h, through tests/host_emulation/ptemu_light_groups_shard.cpp) — every pixel in exactly one shard, every bit kept —, the argument
+(csrc/pt_shard_rules.h, through tests/host_emulation/ptemu_light_groups_shard.cpp) — every pixel in exactly one shard, every bit kept —, the argument
 checks, the command line's refusals and the sanitizer program; the GPU tier checks the entries with virtual devices against the one-device renders bit for bit, the
 node-resident mix, the assemble for the filter, repeated calls, masks and ptcli."""
 import ctypes as C
@@ -39,7 +39,7 @@ def emu_gs(pkg):
     """The packed group shard's rule and the node entries' argument checks on the host (ptemu_light_groups_shard.cpp beside the engine's pt_plan.cpp)."""
     lib = os.path.join(EMU_DIR, "libptemu_light_groups_shard.so")
     srcs = [os.path.join(EMU_DIR, "ptemu_light_groups_shard.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_plan.h", "pt_light_groups_shard_rules.h")] + \
+    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_plan.h", "pt_shard_rules.h")] + \
         [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_light_groups.h", "pt_light_groups_denoise.h", "pt_light_groups_multi.h", "pt_numerics.h")]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
@@ -295,11 +295,11 @@ def test_ptcli_refuses_bad_light_group_devices_while_parsing(pkg, tmp_path):
 
 
 def test_sanitize_program_packs_scatters_and_unpacks_in_exact_buffers(tmp_path):
-    """tools/light_groups_shard_sanitize.cpp, a stand-alone host binary built with the address and undefined-behaviour sanitizers: the tests' films, shard counts
+    """tools/shard_sanitize.cpp, a stand-alone host binary built with the address and undefined-behaviour sanitizers: the tests' films, shard counts
     and group counts in heap buffers of exactly the engine's sizes."""
     exe = str(tmp_path / "light_groups_shard_sanitize")
     subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-Wno-unused-function", "-o", exe, os.path.join(ROOT, "tools", "light_groups_shard_sanitize.cpp"), os.path.join(CSRC, "pt_plan.cpp")])
+                           "-Wno-unused-function", "-o", exe, os.path.join(ROOT, "tools", "shard_sanitize.cpp"), os.path.join(CSRC, "pt_plan.cpp")])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok") and r.stdout.count("every bit back") == 4 and not r.stderr, (r.stdout, r.stderr)
 
@@ -469,6 +469,27 @@ def test_gpu_node_resident_mix(engine, pkg, room_ref):
         assert sc.light_groups_resident() is None
         with pytest.raises(a.PtError, match="no resident group films"):
             sc.light_groups_mix_resident(M)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("groups_first", [False, True], ids=["spectral_then_groups", "groups_then_spectral"])
+def test_gpu_spectral_and_group_shards_of_two_film_sizes_stay_resident_together(engine, pkg, room_ref, groups_first):
+    """One scene, four virtual devices: pt_render_spectral_multi at 40 x 20 with 5 bins and pt_render_light_groups_multi at 77 x 45 with G = 3, in either order.
+    Both stay resident, each in shards with pixel lists of its own film: pt_spectral_project_resident with a 2 x 5 matrix is pt_spectral_project of the bins the
+    spectral call returned, and pt_light_groups_mix_resident is pt_light_groups_mix of the group films the group call returned, both bit for bit."""
+    sc = tuned_scene(engine, pkg, room_ref["builder"], 4)
+    out = {}
+    for groups in (groups_first, not groups_first):
+        if groups:
+            out["groups"] = sc.render_light_groups_multi(room_rd(pkg, spp=4), ROOM_GROUPS, ROOM_ENV_GROUP, device_mask=1)[1]
+        else:
+            out["bins"] = sc.render_spectral_multi(room_rd(pkg, 40, 20, spp=4), 5, device_mask=1)[1]
+    assert sc.spectral_resident() == (40, 20, 5) and sc.light_groups_resident() == (W, H, 3)
+    assert np.any(out["bins"] != 0) and np.any(out["groups"] != 0)
+    K = np.random.default_rng(21).uniform(-1.0, 1.0, (2, 5)).astype(F)
+    M = random_matrices(22, 3)
+    assert np.array_equal(bits(sc.spectral_project_resident(K)), bits(engine.spectral_project(out["bins"], K)))
+    assert np.array_equal(bits(sc.light_groups_mix_resident(M)), bits(engine.light_groups_mix(out["groups"], M)))
 
 
 @pytest.fixture(scope="module")

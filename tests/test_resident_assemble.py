@@ -1,6 +1,6 @@
 """A node render assembled on one device for the resident filter (pt_resident_assemble and pt_resident_read, include/pt_resident.h, DESIGN.md section 14,
 "Assembling a node render").  Everything is moved and nothing computed, so every comparison is bit for bit.  The CPU tier checks the unpack rule the kernel
-compiles (csrc/pt_spectral_shard_rules.h, through tests/host_emulation/ptemu_resident_assemble.cpp) against a numpy restatement, the refusals of
+compiles (csrc/pt_shard_rules.h, through tests/host_emulation/ptemu_resident_assemble.cpp) against a numpy restatement, the refusals of
 pth::check_resident_assemble, the library's exports and bindings, and the refusals of the Python layer and of the command line.  The GPU tier renders on
 virtual devices, assembles, and compares what pt_resident_read returns with the arrays the render returned, the filter on the assembled set with the filter
 after pt_resident_load and with the host-array entry, walks the life of the remembered node render, and compares the Python routes and ptcli's files."""
@@ -36,7 +36,7 @@ def emu_as(pkg):
     """The unpack rule and pt_resident_assemble's checks on the host, beside the pack rule and the shard lists (ptemu_spectral_shard.cpp): a library of its own."""
     lib = os.path.join(EMU_DIR, "libptemu_resident_assemble.so")
     srcs = [os.path.join(EMU_DIR, "ptemu_resident_assemble.cpp"), os.path.join(EMU_DIR, "ptemu_spectral_shard.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_plan.h", "pt_spectral_shard_rules.h")] + \
+    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_plan.h", "pt_shard_rules.h")] + \
         [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_spectral.h", "pt_resident.h", "pt_numerics.h")]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
@@ -56,7 +56,7 @@ def emu_as(pkg):
 
 # ------------------------------------------------------------------------------------------------ CPU tier
 def np_unpack(packed, px, planes):
-    """spectral_shard_unpack_item for every item: planes[b, px[i]] = packed[b, i]"""
+    """shard_unpack_item for every item: planes[b, px[i]] = packed[b, i]"""
     planes[:, px] = packed
 
 

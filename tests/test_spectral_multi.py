@@ -1,6 +1,6 @@
 """The spectral film on every device of a node (pt_render_spectral_multi, pt_render_adaptive_spectral_multi, include/pt_spectral.h).
 Every device packs the bins of its own tiles (k_spectral_pack), hands them to the host itself and keeps them as its part of the scene's resident film; nothing is
-reduced.  The CPU tier checks the pack and scatter rule the kernel compiles (csrc/pt_spectral_shard_rules.h, through tests/host_emulation/ptemu_spectral_shard.cpp)
+reduced.  The CPU tier checks the pack and scatter rule the kernel compiles (csrc/pt_shard_rules.h, through tests/host_emulation/ptemu_spectral_shard.cpp)
 against a numpy restatement — every pixel in exactly one shard, every bit kept —, the argument checks and the command line's refusals; the GPU tier checks the
 entries with virtual devices against the one-device renders bit for bit, the node-resident film's development, repeated calls, masks and ptcli."""
 import ctypes as C
@@ -37,7 +37,7 @@ def emu_sh(pkg):
     """The packed shard's rule and the node entries' argument checks on the host (ptemu_spectral_shard.cpp beside the engine's pt_plan.cpp): a library of its own."""
     lib = os.path.join(EMU_DIR, "libptemu_spectral_shard.so")
     srcs = [os.path.join(EMU_DIR, "ptemu_spectral_shard.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_plan.h", "pt_spectral_shard_rules.h")] + \
+    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_plan.h", "pt_shard_rules.h")] + \
         [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_spectral.h", "pt_numerics.h")]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",

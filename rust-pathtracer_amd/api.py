@@ -4,6 +4,7 @@ Plumbing only: struct layouts, function prototypes and a thin `Library` wrapper 
 binds either the product library (prefix ``pt_``, the HIP engine) or — from tests —
 the CPU oracle (prefix ``ptref_``).  No computation happens here.
 """
+import collections
 import ctypes as C
 import numpy as np
 
@@ -236,8 +237,13 @@ class PtError(RuntimeError):
         self.status = status
 
 
-def _fp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
+def _pointer_to(ctype):
+    """array -> its data as a pointer to `ctype`; None (an output not asked for, an input not given) stays None."""
+    pointer = C.POINTER(ctype)
+    return lambda a: None if a is None else a.ctypes.data_as(pointer)
+
+
+_fp, _u32p, _u8p, _f64p = (_pointer_to(t) for t in (C.c_float, C.c_uint32, C.c_uint8, C.c_double))
 
 
 def render_desc(width, height, spp, max_bounces, min_bounces=1, light_samples=2, only_direct=False,
@@ -248,6 +254,160 @@ def render_desc(width, height, spp, max_bounces, min_bounces=1, light_samples=2,
                       hero_wavelengths, first_sample, sample_count, phase_samples, int(bool(medium_aware)))
 
 
+# One row per entry of the boundary (without prefix).  `required`: a library without the entry does not load (unless Library's `optional` names it); any
+# other missing entry binds as None.  `channel`: the *_last_error entry an emulation library reports this entry's refusals through — the engine, and a
+# library without that channel, report through last_error.  The channels are rows like any other.
+Entry = collections.namedtuple("Entry", "name argtypes restype required channel", defaults=(C.c_int32, False, None))
+
+_P = C.POINTER
+_vp, _str, _sz, _u32, _i32, _u64 = C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_int32, C.c_uint64
+_f32s, _u32s, _f64s, _u8s, _i32s = _P(C.c_float), _P(C.c_uint32), _P(C.c_double), _P(C.c_uint8), _P(C.c_int32)
+_RD, _AD, _SD, _GD, _DD, _RDD, _CHAIN, _PROF = (_P(t) for t in (RenderDesc, AdaptiveDesc, SpectralDesc, LightGroupsDesc, DenoiseDesc, ResidentDenoiseDesc,
+                                                                GuideChainDesc, Profile))
+_DENOISE, _ALBEDO, _BIN_ALBEDO, _PROJECT = "denoise_last_error", "denoise_albedo_last_error", "denoise_spectral_albedo_last_error", "spectral_project_last_error"
+_GROUPS, _GROUP_BINS, _RESIDENT = "light_groups_last_error", "light_groups_spectral_last_error", "resident_last_error"
+
+BINDINGS = (
+    ("pt_api.h", (
+        Entry("scene_create", [_P(SceneDesc), _P(_vp)], required=True),
+        Entry("scene_create_tuned", [_P(SceneDesc), _P(Tuning), _P(_vp)]),
+        Entry("tuning_default", [_P(Tuning)], None),
+        Entry("scene_destroy", [_vp], None, required=True),
+        Entry("last_error", [], _str, required=True),
+        Entry("render", [_vp, _RD, _f32s, _PROF], required=True),
+        Entry("render_device", [_vp, _RD, _vp, _vp, _PROF]),
+        Entry("render_multi", [_vp, _RD, _u64, _f32s, _PROF]),
+        Entry("device_count", [], _u32),
+        Entry("intersect", [_vp, _sz, _f32s, _f32s, _P(Hit)], required=True),
+        Entry("camera_samples", [_vp, _RD, _sz, _u32s, _u32s, _f32s, _f32s, _f32s], required=True),
+        Entry("bsdf_sample", [_vp, _u32, _sz, _f32s, _f32s, _f32s, _f32s, _f32s, _f32s], required=True),
+        Entry("bsdf_eval", [_vp, _u32, _sz, _f32s, _f32s, _f32s, _f32s, _f32s], required=True),
+        Entry("emission", [_vp, _u32, _sz, _f32s, _f32s, _f32s], required=True),
+        Entry("curve_eval", [_vp, _u32, _sz, _f32s, _f32s], required=True),
+        Entry("device_info", [], _str),
+        Entry("output_film", [_P(OutputDesc), _f32s, _u8s, _f32s]),
+        Entry("write_png", [_str, _u32, _u32, _u8s, _i32]),
+        Entry("compare_films", [_u32, _u32, _f32s, _f32s, _i32, _f32s, _P(CompareStats)]),
+        Entry("write_exr", [_str, _u32, _u32, _f32s, _i32]))),
+    # not the oracle's boundary: the reference cannot sample an emissive mesh face (debug_scene_info is the engine's, declared in no public header)
+    ("pt_debug.h", (
+        Entry("light_sample", [_vp, _u32, _sz, _f32s, _f32s, _f32s, _f32s]),
+        Entry("debug_scene_info", [_vp, _i32], _u32))),
+    # not the oracle's boundary either: the reference's tiled renderer has no adaptive sampling
+    ("pt_adaptive.h", (
+        Entry("render_adaptive", [_vp, _RD, _AD, _f32s, _u32s, _f64s, _PROF]),
+        Entry("render_adaptive_multi", [_vp, _RD, _AD, _u64, _f32s, _u32s, _f64s, _PROF]))),
+    # the reference has no denoiser; the oracle and older emulation libraries do not export these
+    ("pt_denoise.h", (
+        Entry("render_guides", [_vp, _RD, _u32, _f32s], channel=_DENOISE),
+        Entry("denoise_film", [_DD, _f32s, _u32s, _f64s, _f32s, _f32s, _f32s], channel=_DENOISE),
+        Entry(_DENOISE, [], _str),
+        Entry("albedo_basis", [_RD, _f32s, _f32s], channel=_ALBEDO),
+        Entry("render_guides_albedo", [_vp, _RD, _u32, _f32s, _f32s], channel=_ALBEDO),
+        Entry("denoise_film_albedo", [_DD, _f32s, _u32s, _f64s, _f32s, _f32s, _f32s, _f32s], channel=_ALBEDO),
+        Entry(_ALBEDO, [], _str),
+        Entry("render_guides_chain", [_vp, _RD, _u32, _CHAIN, _f32s, _f32s], channel="guides_chain_last_error"),
+        Entry("guides_chain_last_error", [], _str))),
+    # the reference keeps no spectrum; an older library without these entries still loads
+    ("pt_spectral.h", (
+        Entry("render_spectral", [_vp, _RD, _SD, _f32s, _f32s, _PROF]),
+        Entry("spectral_bin_centres", [_RD, _SD, _f32s]),
+        Entry("write_exr_spectral", [_str, _u32, _u32, _u32, _f32s, _f32s, _f32s, _i32]),
+        Entry("render_adaptive_spectral", [_vp, _RD, _AD, _SD, _f32s, _u32s, _f64s, _f32s, _PROF]),
+        Entry("render_spectral_multi", [_vp, _RD, _SD, _u64, _f32s, _f32s, _PROF]),
+        Entry("render_adaptive_spectral_multi", [_vp, _RD, _AD, _SD, _u64, _f32s, _u32s, _f64s, _f32s, _PROF]),
+        Entry("denoise_spectral", [_DD, _u32, _f32s, _u32s, _f64s, _f32s, _f32s, _f32s, _f32s, _f32s], channel="denoise_spectral_last_error"),
+        Entry("denoise_spectral_last_error", [], _str),
+        Entry("render_guides_bin_albedo", [_vp, _RD, _u32, _CHAIN, _u32, _f32s, _f32s, _f32s], channel=_BIN_ALBEDO),
+        Entry("denoise_spectral_albedo", [_DD, _u32, _f32s, _u32s, _f64s, _f32s, _f32s, _f32s, _f32s, _f32s, _f32s, _f32s], channel=_BIN_ALBEDO),
+        Entry(_BIN_ALBEDO, [], _str),
+        Entry("spectral_response_matrix", [_RD, _SD, _P(Curve), _u32, _f32s, _u32, _u32, _i32s, _i32, _u32, _f32s], channel=_PROJECT),
+        Entry("spectral_project", [_u32, _u32, _u32, _u32, _f32s, _f32s, _f32s], channel=_PROJECT),
+        Entry("spectral_project_resident", [_vp, _u32, _f32s, _f32s]),
+        Entry("spectral_resident", [_vp, _u32s, _u32s, _u32s]),
+        Entry(_PROJECT, [], _str))),
+    # the reference keeps one film
+    ("pt_light_groups.h", (
+        Entry("render_light_groups", [_vp, _RD, _GD, _f32s, _f32s, _PROF], channel=_GROUPS),
+        Entry("light_groups_mix", [_u32, _u32, _u32, _f32s, _f32s, _f32s], channel=_GROUPS),
+        Entry("light_groups_resident", [_vp, _u32s, _u32s, _u32s], channel=_GROUPS),
+        Entry("light_groups_mix_resident", [_vp, _f32s, _f32s], channel=_GROUPS),
+        Entry(_GROUPS, [], _str))),
+    ("pt_light_groups_spectral.h", (
+        Entry("render_light_groups_spectral", [_vp, _RD, _GD, _SD, _f32s, _f32s, _f32s, _f32s, _PROF], channel=_GROUP_BINS),
+        Entry("light_groups_spectral_resident", [_vp, _u32s, _u32s, _u32s, _u32s], channel=_GROUP_BINS),
+        Entry("light_groups_relamp_matrix", [_RD, _SD, _P(Curve), _u32, _f32s, _u32, _u32, _i32s, _i32, _u32, _u32, _i32s, _i32s, _f32s, _f32s], channel=_GROUP_BINS),
+        Entry("light_groups_relamp", [_u32, _u32, _u32, _u32, _u32, _f32s, _f32s, _f32s], channel=_GROUP_BINS),
+        Entry("light_groups_relamp_resident", [_vp, _u32, _f32s, _f32s], channel=_GROUP_BINS),
+        Entry(_GROUP_BINS, [], _str))),
+    ("pt_light_groups_denoise.h", (
+        Entry("render_adaptive_light_groups", [_vp, _RD, _AD, _GD, _f32s, _u32s, _f64s, _f32s, _PROF], channel="adaptive_light_groups_last_error"),
+        Entry("denoise_light_groups", [_DD, _u32, _f32s, _u32s, _f64s, _f32s, _f32s, _f32s, _f32s, _f32s, _f32s], channel="denoise_light_groups_last_error"),
+        Entry("denoise_light_groups_resident", [_vp, _RDD, _f32s, _f32s, _f32s]),
+        Entry("light_groups_denoised_resident", [_vp, _u32s, _u32s, _u32s]),
+        Entry("light_groups_mix_resident_denoised", [_vp, _f32s, _f32s], channel=_GROUPS),
+        Entry("adaptive_light_groups_last_error", [], _str),
+        Entry("denoise_light_groups_last_error", [], _str))),
+    ("pt_light_groups_multi.h", (
+        Entry("render_light_groups_multi", [_vp, _RD, _GD, _u64, _f32s, _f32s, _PROF], channel=_GROUPS),
+        Entry("render_adaptive_light_groups_multi", [_vp, _RD, _AD, _GD, _u64, _f32s, _u32s, _f64s, _f32s, _PROF]))),
+    # an emulation library may lack these
+    ("pt_resident.h", (
+        Entry("resident_info", [_vp, _P(ResidentInfo)], channel=_RESIDENT),
+        Entry("resident_guides", [_vp, _RD, _u32, _CHAIN, _u32], channel=_RESIDENT),
+        Entry("resident_load", [_vp, _u32, _u32, _u32, _f32s, _u32s, _f64s, _f32s, _f32s, _f32s, _f32s], channel=_RESIDENT),
+        Entry("denoise_resident", [_vp, _RDD, _f32s, _f32s, _f32s], channel=_RESIDENT),
+        Entry("spectral_project_resident_denoised", [_vp, _u32, _f32s, _f32s], channel=_RESIDENT),
+        Entry("resident_assemble", [_vp, _u32], channel=_RESIDENT),
+        Entry("resident_read", [_vp, _f32s, _u32s, _f64s, _f32s], channel=_RESIDENT),
+        Entry(_RESIDENT, [], _str))),
+)
+ENTRIES = {e.name: e for _, rows in BINDINGS for e in rows}
+
+_BINS_LAYOUT, _GROUPS_LAYOUT = ("spectral [B,H,W]", ()), ("group_films [G,H,W,4]", (4,))   # a host-array filter's planes: their name in a refusal, a plane's trailing shape
+
+
+def _filter_inputs(film, counts, stats, guides, planes=None, layout=None, albedo=None, bin_albedo=None):
+    """The inputs of a host-array filter as contiguous arrays of the entry's types, refused unless all are of the film's size:
+    (h, w, film, counts, stats, guides, planes, albedo, bin_albedo).  `planes` with `layout`: the spectral film or the group films."""
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    stats = np.ascontiguousarray(stats, dtype=np.float64)
+    guides = np.ascontiguousarray(guides, dtype=np.float32)
+    h, w = film.shape[:2]
+    ok = film.shape == (h, w, 4) and counts.shape == (h, w) and stats.shape == (h, w, 2) and guides.shape == (h, w, 4)
+    if layout is not None:
+        planes = np.ascontiguousarray(planes, dtype=np.float32)
+        ok = ok and planes.ndim == 3 + len(layout[1]) and planes.shape[1:] == (h, w) + layout[1]
+    if not ok:
+        raise ValueError("film [H,W,4], counts [H,W], stats [H,W,2]%s guides [H,W,4]%s of one film size" % ((",", " and " + layout[0]) if layout else (" and", "")))
+    if albedo is not None:
+        albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+        if albedo.shape != (h, w, 4):
+            raise ValueError("albedo [H,W,4] of the film's size")
+    if bin_albedo is not None:
+        bin_albedo = np.ascontiguousarray(bin_albedo, dtype=np.float32)
+        if bin_albedo.shape != (planes.shape[0], h, w):
+            raise ValueError("bin_albedo [B,H,W] of the spectral film's size")
+    return h, w, film, counts, stats, guides, planes, albedo, bin_albedo
+
+
+def _filter_outputs(h, w, variance, planes=None):
+    """(denoised film, variance or None, denoised planes or None) for a host-array filter over a film of h x w."""
+    return np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.float32) if variance else None, None if planes is None else np.zeros(planes.shape, np.float32)
+
+
+def _asked(*arrays):
+    """The tuple of what was asked for: one array when one is asked for, None when none is."""
+    got = tuple(a for a in arrays if a is not None)
+    return got[0] if len(got) == 1 else (got or None)
+
+
+def _first_device(mask):
+    """The lowest device of a mask; 0 for the mask 0 (= all devices)."""
+    return (mask & -mask).bit_length() - 1 if mask else 0
+
+
 class Library:
     """Binds one implementation of the boundary.  `prefix` is ``pt_`` (product) or ``ptref_`` (oracle)."""
 
@@ -255,126 +415,16 @@ class Library:
         self.path = path
         self.prefix = prefix
         self.lib = C.CDLL(path)
-        L, p = self.lib, prefix
-
-        def bind(name, restype, argtypes, required=True):
+        for e in ENTRIES.values():
             try:
-                fn = getattr(L, p + name)
+                fn = getattr(self.lib, prefix + e.name)
             except AttributeError:
-                if required and name not in optional:
+                if e.required and e.name not in optional:
                     raise
-                return None
-            fn.restype = restype
-            fn.argtypes = argtypes
-            return fn
-
-        vp, fpp, sz, u32 = C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_uint32
-        self._scene_create = bind("scene_create", C.c_int32, [C.POINTER(SceneDesc), C.POINTER(vp)])
-        self._scene_create_tuned = bind("scene_create_tuned", C.c_int32, [C.POINTER(SceneDesc), C.POINTER(Tuning), C.POINTER(vp)], required=False)
-        self._tuning_default = bind("tuning_default", None, [C.POINTER(Tuning)], required=False)
-        self._scene_destroy = bind("scene_destroy", None, [vp])
-        self._last_error = bind("last_error", C.c_char_p, [])
-        self._render = bind("render", C.c_int32, [vp, C.POINTER(RenderDesc), fpp, C.POINTER(Profile)])
-        self._render_device = bind("render_device", C.c_int32, [vp, C.POINTER(RenderDesc), vp, vp, C.POINTER(Profile)], required=False)
-        self._render_multi = bind("render_multi", C.c_int32, [vp, C.POINTER(RenderDesc), C.c_uint64, fpp, C.POINTER(Profile)], required=False)
-        self._device_count = bind("device_count", u32, [], required=False)
-        self._intersect = bind("intersect", C.c_int32, [vp, sz, fpp, fpp, C.POINTER(Hit)])
-        self._camera_samples = bind("camera_samples", C.c_int32, [vp, C.POINTER(RenderDesc), sz, C.POINTER(u32), C.POINTER(u32), fpp, fpp, fpp])
-        self._bsdf_sample = bind("bsdf_sample", C.c_int32, [vp, u32, sz, fpp, fpp, fpp, fpp, fpp, fpp])
-        self._bsdf_eval = bind("bsdf_eval", C.c_int32, [vp, u32, sz, fpp, fpp, fpp, fpp, fpp])
-        self._emission = bind("emission", C.c_int32, [vp, u32, sz, fpp, fpp, fpp])
-        self._curve_eval = bind("curve_eval", C.c_int32, [vp, u32, sz, fpp, fpp])
-        # include/pt_debug.h (not the oracle's boundary: the reference cannot sample an emissive mesh face)
-        self._light_sample = bind("light_sample", C.c_int32, [vp, u32, sz, fpp, fpp, fpp, fpp], required=False)
-        # include/pt_adaptive.h (not the oracle's boundary either: the reference's tiled renderer has no adaptive sampling)
-        self._render_adaptive = bind("render_adaptive", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), fpp, C.POINTER(u32),
-                                                                    C.POINTER(C.c_double), C.POINTER(Profile)], required=False)
-        self._render_adaptive_multi = bind("render_adaptive_multi", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), C.c_uint64, fpp,
-                                                                                C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(Profile)], required=False)
-        # include/pt_denoise.h (the reference has no denoiser; the oracle and older emulation libraries do not export these)
-        self._render_guides = bind("render_guides", C.c_int32, [vp, C.POINTER(RenderDesc), u32, fpp], required=False)
-        self._denoise_film = bind("denoise_film", C.c_int32, [C.POINTER(DenoiseDesc), fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp], required=False)
-        self._denoise_last_error = bind("denoise_last_error", C.c_char_p, [], required=False)   # (the emulation's: the engine reports through pt_last_error)
-        self._albedo_basis = bind("albedo_basis", C.c_int32, [C.POINTER(RenderDesc), fpp, fpp], required=False)
-        self._render_guides_albedo = bind("render_guides_albedo", C.c_int32, [vp, C.POINTER(RenderDesc), u32, fpp, fpp], required=False)
-        self._denoise_film_albedo = bind("denoise_film_albedo", C.c_int32, [C.POINTER(DenoiseDesc), fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp],
-                                         required=False)
-        self._denoise_albedo_last_error = bind("denoise_albedo_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the three entries above)
-        self._render_guides_chain = bind("render_guides_chain", C.c_int32, [vp, C.POINTER(RenderDesc), u32, C.POINTER(GuideChainDesc), fpp, fpp], required=False)
-        self._guides_chain_last_error = bind("guides_chain_last_error", C.c_char_p, [], required=False)   # (the emulation's)
-        # include/pt_spectral.h (the reference keeps no spectrum; an older library without these entries still loads)
-        self._render_spectral = bind("render_spectral", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(SpectralDesc), fpp, fpp, C.POINTER(Profile)], required=False)
-        self._spectral_bin_centres = bind("spectral_bin_centres", C.c_int32, [C.POINTER(RenderDesc), C.POINTER(SpectralDesc), fpp], required=False)
-        self._write_exr_spectral = bind("write_exr_spectral", C.c_int32, [C.c_char_p, u32, u32, u32, fpp, fpp, fpp, C.c_int32], required=False)
-        self._render_adaptive_spectral = bind("render_adaptive_spectral", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), C.POINTER(SpectralDesc), fpp,
-                                                                                      C.POINTER(u32), C.POINTER(C.c_double), fpp, C.POINTER(Profile)], required=False)
-        self._render_spectral_multi = bind("render_spectral_multi", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(SpectralDesc), C.c_uint64, fpp, fpp, C.POINTER(Profile)],
-                                           required=False)
-        self._render_adaptive_spectral_multi = bind("render_adaptive_spectral_multi", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), C.POINTER(SpectralDesc),
-                                                                                                  C.c_uint64, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, C.POINTER(Profile)],
-                                                    required=False)
-        self._denoise_spectral = bind("denoise_spectral", C.c_int32, [C.POINTER(DenoiseDesc), u32, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp, fpp],
-                                      required=False)
-        self._denoise_spectral_last_error = bind("denoise_spectral_last_error", C.c_char_p, [], required=False)   # (the emulation's)
-        self._render_guides_bin_albedo = bind("render_guides_bin_albedo", C.c_int32, [vp, C.POINTER(RenderDesc), u32, C.POINTER(GuideChainDesc), u32, fpp, fpp, fpp],
-                                              required=False)
-        self._denoise_spectral_albedo = bind("denoise_spectral_albedo", C.c_int32, [C.POINTER(DenoiseDesc), u32, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp,
-                                                                                    fpp, fpp, fpp], required=False)
-        self._denoise_spectral_albedo_last_error = bind("denoise_spectral_albedo_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the two entries above)
-        self._spectral_response_matrix = bind("spectral_response_matrix", C.c_int32, [C.POINTER(RenderDesc), C.POINTER(SpectralDesc), C.POINTER(Curve), u32, fpp, u32, u32,
-                                                                                      C.POINTER(C.c_int32), C.c_int32, u32, fpp], required=False)
-        self._spectral_project = bind("spectral_project", C.c_int32, [u32, u32, u32, u32, fpp, fpp, fpp], required=False)
-        self._spectral_project_resident = bind("spectral_project_resident", C.c_int32, [vp, u32, fpp, fpp], required=False)
-        self._spectral_resident = bind("spectral_resident", C.c_int32, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)], required=False)
-        # include/pt_light_groups.h (the reference keeps one film)
-        self._render_light_groups = bind("render_light_groups", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(LightGroupsDesc), fpp, fpp, C.POINTER(Profile)], required=False)
-        self._light_groups_mix = bind("light_groups_mix", C.c_int32, [u32, u32, u32, fpp, fpp, fpp], required=False)
-        self._light_groups_resident = bind("light_groups_resident", C.c_int32, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)], required=False)
-        self._light_groups_mix_resident = bind("light_groups_mix_resident", C.c_int32, [vp, fpp, fpp], required=False)
-        self._light_groups_last_error = bind("light_groups_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the entries above)
-        # include/pt_light_groups_spectral.h
-        self._render_light_groups_spectral = bind("render_light_groups_spectral", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(LightGroupsDesc), C.POINTER(SpectralDesc),
-                                                                                              fpp, fpp, fpp, fpp, C.POINTER(Profile)], required=False)
-        self._light_groups_spectral_resident = bind("light_groups_spectral_resident", C.c_int32, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)],
-                                                    required=False)
-        self._light_groups_relamp_matrix = bind("light_groups_relamp_matrix", C.c_int32, [C.POINTER(RenderDesc), C.POINTER(SpectralDesc), C.POINTER(Curve), u32, fpp, u32, u32,
-                                                                                          C.POINTER(C.c_int32), C.c_int32, u32, u32, C.POINTER(C.c_int32),
-                                                                                          C.POINTER(C.c_int32), fpp, fpp], required=False)
-        self._light_groups_relamp = bind("light_groups_relamp", C.c_int32, [u32, u32, u32, u32, u32, fpp, fpp, fpp], required=False)
-        self._light_groups_relamp_resident = bind("light_groups_relamp_resident", C.c_int32, [vp, u32, fpp, fpp], required=False)
-        self._light_groups_spectral_last_error = bind("light_groups_spectral_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the entries above)
-        # include/pt_light_groups_denoise.h
-        self._render_adaptive_light_groups = bind("render_adaptive_light_groups", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), C.POINTER(LightGroupsDesc), fpp,
-                                                                                              C.POINTER(u32), C.POINTER(C.c_double), fpp, C.POINTER(Profile)], required=False)
-        self._denoise_light_groups = bind("denoise_light_groups", C.c_int32, [C.POINTER(DenoiseDesc), u32, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp, fpp, fpp],
-                                          required=False)
-        self._denoise_light_groups_resident = bind("denoise_light_groups_resident", C.c_int32, [vp, C.POINTER(ResidentDenoiseDesc), fpp, fpp, fpp], required=False)
-        self._light_groups_denoised_resident = bind("light_groups_denoised_resident", C.c_int32, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)], required=False)
-        self._light_groups_mix_resident_denoised = bind("light_groups_mix_resident_denoised", C.c_int32, [vp, fpp, fpp], required=False)
-        self._adaptive_light_groups_last_error = bind("adaptive_light_groups_last_error", C.c_char_p, [], required=False)   # (the emulation's)
-        self._denoise_light_groups_last_error = bind("denoise_light_groups_last_error", C.c_char_p, [], required=False)   # (the emulation's)
-        # include/pt_light_groups_multi.h
-        self._render_light_groups_multi = bind("render_light_groups_multi", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(LightGroupsDesc), C.c_uint64, fpp, fpp,
-                                                                                        C.POINTER(Profile)], required=False)
-        self._render_adaptive_light_groups_multi = bind("render_adaptive_light_groups_multi", C.c_int32, [vp, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc),
-                                                                                                          C.POINTER(LightGroupsDesc), C.c_uint64, fpp, C.POINTER(u32),
-                                                                                                          C.POINTER(C.c_double), fpp, C.POINTER(Profile)], required=False)
-        # include/pt_resident.h (an emulation library may lack these)
-        self._resident_info = bind("resident_info", C.c_int32, [vp, C.POINTER(ResidentInfo)], required=False)
-        self._resident_guides = bind("resident_guides", C.c_int32, [vp, C.POINTER(RenderDesc), u32, C.POINTER(GuideChainDesc), u32], required=False)
-        self._resident_load = bind("resident_load", C.c_int32, [vp, u32, u32, u32, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp, fpp, fpp, fpp], required=False)
-        self._denoise_resident = bind("denoise_resident", C.c_int32, [vp, C.POINTER(ResidentDenoiseDesc), fpp, fpp, fpp], required=False)
-        self._spectral_project_resident_denoised = bind("spectral_project_resident_denoised", C.c_int32, [vp, u32, fpp, fpp], required=False)
-        self._resident_assemble = bind("resident_assemble", C.c_int32, [vp, u32], required=False)
-        self._resident_read = bind("resident_read", C.c_int32, [vp, fpp, C.POINTER(u32), C.POINTER(C.c_double), fpp], required=False)
-        self._resident_last_error = bind("resident_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the seven entries above)
-        self._spectral_project_last_error = bind("spectral_project_last_error", C.c_char_p, [], required=False)   # (the emulation's, for the entries above)
-        self._device_info = bind("device_info", C.c_char_p, [], required=False)
-        self._output_film = bind("output_film", C.c_int32, [C.POINTER(OutputDesc), fpp, C.POINTER(C.c_uint8), fpp], required=False)
-        self._write_png = bind("write_png", C.c_int32, [C.c_char_p, u32, u32, C.POINTER(C.c_uint8), C.c_int32], required=False)
-        self._compare_films = bind("compare_films", C.c_int32, [u32, u32, fpp, fpp, C.c_int32, fpp, C.POINTER(CompareStats)], required=False)
-        self._debug_scene_info = bind("debug_scene_info", u32, [vp, C.c_int32], required=False)
-        self._write_exr = bind("write_exr", C.c_int32, [C.c_char_p, u32, u32, fpp, C.c_int32], required=False)
+                fn = None
+            else:
+                fn.restype, fn.argtypes = e.restype, e.argtypes
+            setattr(self, "_" + e.name, fn)
 
     def last_error(self):
         m = self._last_error()
@@ -383,6 +433,22 @@ class Library:
     def check(self, status):
         if status != PT_OK:
             raise PtError(status, self.last_error())
+
+    def entry(self, name):
+        """The bound entry `name`; a library that lacks it is refused here."""
+        fn = getattr(self, "_" + name)
+        if fn is None:
+            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %s%s entry" % (self.path, self.prefix, name))
+        return fn
+
+    def call(self, name, *args):
+        """The one way into a status-returning entry: refused if the library lacks it; a status other than PT_OK raises PtError with the message of the
+        entry's own channel (ENTRIES) if the library exports that, else last_error's."""
+        status = self.entry(name)(*args)
+        if status != PT_OK:
+            channel = ENTRIES[name].channel
+            err = getattr(self, "_" + channel) if channel else None
+            raise PtError(status, err().decode() if err else self.last_error())
 
     def device_info(self):
         return self._device_info().decode() if self._device_info else "cpu oracle"
@@ -406,7 +472,7 @@ class Library:
         d = OutputDesc(w, h, tonemap, int(bool(luminance_only)), exposure, key_value, white_point, colorspace, factor)
         rgba = np.zeros((h, w, 4), np.uint8)
         lin = np.zeros((h, w, 3), np.float32) if want_linear else None
-        self.check(self._output_film(C.byref(d), _fp(film), rgba.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(lin) if want_linear else None))
+        self.call("output_film", C.byref(d), _fp(film), _u8p(rgba), _fp(lin))
         return rgba, lin
 
     def compare_films(self, image, truth, mode=COMPARE_ABSOLUTE, want_image=True):
@@ -418,52 +484,26 @@ class Library:
         h, w = image.shape[:2]
         out = np.zeros((h, w, 4), np.float32) if want_image else None
         st = CompareStats()
-        self.check(self._compare_films(w, h, _fp(image), _fp(truth), mode, _fp(out) if want_image else None, C.byref(st)))
+        self.call("compare_films", w, h, _fp(image), _fp(truth), mode, _fp(out), C.byref(st))
         return out, st
 
     def albedo_basis(self, rd):
         """pt_albedo_basis: the wavelengths [16] (nm) and the X, Y, Z weights [3,16] the albedo of a render `rd` is folded over."""
-        if self._albedo_basis is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %salbedo_basis entry" % (self.path, self.prefix))
         lam, xyz = np.zeros(16, np.float32), np.zeros((3, 16), np.float32)
-        st = self._albedo_basis(C.byref(rd), _fp(lam), _fp(xyz))
-        if st != PT_OK:
-            raise PtError(st, self._albedo_error())
+        self.call("albedo_basis", C.byref(rd), _fp(lam), _fp(xyz))
         return lam, xyz
-
-    def _albedo_error(self):
-        err = self._denoise_albedo_last_error
-        return err().decode() if err else self.last_error()
 
     def denoise_film(self, film, counts, stats, guides, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, device=0, variance=False, albedo=None):
         """pt_denoise_film: the edge-avoiding filter over an adaptive render's film [H,W,4], counts [H,W] u32 and stats [H,W,2] f64 with the guides
         [H,W,4] of Scene.render_guides.  0 selects a parameter's default.  Returns the filtered film [H,W,4], with variance=True (film, variance [H,W]).
         `albedo` [H,W,4] (Scene.render_guides_albedo's): pt_denoise_film_albedo, the filter over the film demodulated by it."""
-        entry, name = (self._denoise_film, "denoise_film") if albedo is None else (self._denoise_film_albedo, "denoise_film_albedo")
-        if entry is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %s%s entry" % (self.path, self.prefix, name))
-        film = np.ascontiguousarray(film, dtype=np.float32)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        stats = np.ascontiguousarray(stats, dtype=np.float64)
-        guides = np.ascontiguousarray(guides, dtype=np.float32)
-        h, w = film.shape[:2]
-        if film.shape != (h, w, 4) or counts.shape != (h, w) or stats.shape != (h, w, 2) or guides.shape != (h, w, 4):
-            raise ValueError("film [H,W,4], counts [H,W], stats [H,W,2] and guides [H,W,4] of one film size")
+        name = "denoise_film" if albedo is None else "denoise_film_albedo"
+        self.entry(name)
+        h, w, film, counts, stats, guides, _, albedo, _ = _filter_inputs(film, counts, stats, guides, albedo=albedo)
         d = DenoiseDesc(w, h, iterations, sigma_luminance, sigma_depth, normal_power_log2, device)
-        out = np.zeros((h, w, 4), np.float32)
-        var = np.zeros((h, w), np.float32) if variance else None
-        planes = [_fp(guides)]
-        if albedo is not None:
-            albedo = np.ascontiguousarray(albedo, dtype=np.float32)
-            if albedo.shape != (h, w, 4):
-                raise ValueError("albedo [H,W,4] of the film's size")
-            planes.append(_fp(albedo))
-        st = entry(C.byref(d), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)), stats.ctypes.data_as(C.POINTER(C.c_double)), *planes,
-                   _fp(out), _fp(var) if variance else None)
-        if st != PT_OK:
-            if albedo is not None:
-                raise PtError(st, self._albedo_error())
-            raise PtError(st, self._denoise_last_error().decode() if self._denoise_last_error else self.last_error())
+        out, var, _ = _filter_outputs(h, w, variance)
+        planes = [_fp(guides)] if albedo is None else [_fp(guides), _fp(albedo)]
+        self.call(name, C.byref(d), _fp(film), _u32p(counts), _f64p(stats), *planes, _fp(out), _fp(var))
         return (out, var) if variance else out
 
     def denoise_spectral(self, film, counts, stats, guides, spectral, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, device=0, variance=False,
@@ -473,84 +513,44 @@ class Library:
         This entry has no albedo form: an `albedo` is refused (demodulating the bins needs a per-bin albedo: denoise_spectral_albedo takes both)."""
         if albedo is not None:
             raise PtError(PT_ERR_UNSUPPORTED, "denoise_spectral takes no albedo: demodulating the bins needs a per-bin albedo (denoise_spectral_albedo takes one)")
-        if self._denoise_spectral is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sdenoise_spectral entry" % (self.path, self.prefix))
-        film = np.ascontiguousarray(film, dtype=np.float32)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        stats = np.ascontiguousarray(stats, dtype=np.float64)
-        guides = np.ascontiguousarray(guides, dtype=np.float32)
-        spectral = np.ascontiguousarray(spectral, dtype=np.float32)
-        h, w = film.shape[:2]
-        if film.shape != (h, w, 4) or counts.shape != (h, w) or stats.shape != (h, w, 2) or guides.shape != (h, w, 4) or spectral.ndim != 3 or spectral.shape[1:] != (h, w):
-            raise ValueError("film [H,W,4], counts [H,W], stats [H,W,2], guides [H,W,4] and spectral [B,H,W] of one film size")
-        bins = spectral.shape[0]
+        self.entry("denoise_spectral")
+        h, w, film, counts, stats, guides, spectral, _, _ = _filter_inputs(film, counts, stats, guides, spectral, _BINS_LAYOUT)
         d = DenoiseDesc(w, h, iterations, sigma_luminance, sigma_depth, normal_power_log2, device)
-        out = np.zeros((h, w, 4), np.float32)
-        out_spectral = np.zeros((bins, h, w), np.float32)
-        var = np.zeros((h, w), np.float32) if variance else None
-        st = self._denoise_spectral(C.byref(d), bins, _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)), stats.ctypes.data_as(C.POINTER(C.c_double)), _fp(guides),
-                                    _fp(spectral), _fp(out), _fp(out_spectral), _fp(var) if variance else None)
-        if st != PT_OK:
-            raise PtError(st, self._denoise_spectral_last_error().decode() if self._denoise_spectral_last_error else self.last_error())
+        out, var, out_spectral = _filter_outputs(h, w, variance, spectral)
+        self.call("denoise_spectral", C.byref(d), spectral.shape[0], _fp(film), _u32p(counts), _f64p(stats), _fp(guides), _fp(spectral), _fp(out), _fp(out_spectral), _fp(var))
         return (out, out_spectral, var) if variance else (out, out_spectral)
 
     def denoise_spectral_albedo(self, film, counts, stats, guides, spectral, albedo=None, bin_albedo=None, iterations=0, sigma_luminance=0.0, sigma_depth=0.0,
                                 normal_power_log2=0, device=0, variance=False):
         """pt_denoise_spectral_albedo: denoise_spectral over the film demodulated by `albedo` [H,W,4] (as denoise_film(albedo=...) does it) and the bins
         demodulated by `bin_albedo` [B,H,W] (Scene.render_guides_bin_albedo's); either may be None.  Returns what denoise_spectral returns."""
-        if self._denoise_spectral_albedo is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sdenoise_spectral_albedo entry" % (self.path, self.prefix))
-        film = np.ascontiguousarray(film, dtype=np.float32)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        stats = np.ascontiguousarray(stats, dtype=np.float64)
-        guides = np.ascontiguousarray(guides, dtype=np.float32)
-        spectral = np.ascontiguousarray(spectral, dtype=np.float32)
-        h, w = film.shape[:2]
-        if film.shape != (h, w, 4) or counts.shape != (h, w) or stats.shape != (h, w, 2) or guides.shape != (h, w, 4) or spectral.ndim != 3 or spectral.shape[1:] != (h, w):
-            raise ValueError("film [H,W,4], counts [H,W], stats [H,W,2], guides [H,W,4] and spectral [B,H,W] of one film size")
-        bins = spectral.shape[0]
-        if albedo is not None:
-            albedo = np.ascontiguousarray(albedo, dtype=np.float32)
-            if albedo.shape != (h, w, 4):
-                raise ValueError("albedo [H,W,4] of the film's size")
-        if bin_albedo is not None:
-            bin_albedo = np.ascontiguousarray(bin_albedo, dtype=np.float32)
-            if bin_albedo.shape != (bins, h, w):
-                raise ValueError("bin_albedo [B,H,W] of the spectral film's size")
+        self.entry("denoise_spectral_albedo")
+        h, w, film, counts, stats, guides, spectral, albedo, bin_albedo = _filter_inputs(film, counts, stats, guides, spectral, _BINS_LAYOUT, albedo, bin_albedo)
         d = DenoiseDesc(w, h, iterations, sigma_luminance, sigma_depth, normal_power_log2, device)
-        out = np.zeros((h, w, 4), np.float32)
-        out_spectral = np.zeros((bins, h, w), np.float32)
-        var = np.zeros((h, w), np.float32) if variance else None
-        st = self._denoise_spectral_albedo(C.byref(d), bins, _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)), stats.ctypes.data_as(C.POINTER(C.c_double)), _fp(guides),
-                                           _fp(albedo) if albedo is not None else None, _fp(spectral), _fp(bin_albedo) if bin_albedo is not None else None,
-                                           _fp(out), _fp(out_spectral), _fp(var) if variance else None)
-        if st != PT_OK:
-            err = self._denoise_spectral_albedo_last_error
-            raise PtError(st, err().decode() if err else self.last_error())
+        out, var, out_spectral = _filter_outputs(h, w, variance, spectral)
+        self.call("denoise_spectral_albedo", C.byref(d), spectral.shape[0], _fp(film), _u32p(counts), _f64p(stats), _fp(guides), _fp(albedo), _fp(spectral), _fp(bin_albedo),
+                  _fp(out), _fp(out_spectral), _fp(var))
         return (out, out_spectral, var) if variance else (out, out_spectral)
 
     def write_png(self, path, rgba8, colorspace=COLORSPACE_SRGB):
         rgba8 = np.ascontiguousarray(rgba8, np.uint8)
-        self.check(self._write_png(path.encode(), rgba8.shape[1], rgba8.shape[0], rgba8.ctypes.data_as(C.POINTER(C.c_uint8)), colorspace))
+        self.call("write_png", path.encode(), rgba8.shape[1], rgba8.shape[0], _u8p(rgba8), colorspace)
 
     def write_exr(self, path, linear_rgb, colorspace=COLORSPACE_SRGB):
         linear_rgb = np.ascontiguousarray(linear_rgb, np.float32)
-        self.check(self._write_exr(path.encode(), linear_rgb.shape[1], linear_rgb.shape[0], _fp(linear_rgb), colorspace))
-
+        self.call("write_exr", path.encode(), linear_rgb.shape[1], linear_rgb.shape[0], _fp(linear_rgb), colorspace)
 
     def spectral_bin_centres(self, rd, bins):
         """pt_spectral_bin_centres: the centre wavelengths [bins] (nm) of the bins of a spectral render of `rd`."""
-        if self._spectral_bin_centres is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sspectral_bin_centres entry" % (self.path, self.prefix))
+        self.entry("spectral_bin_centres")
         centres = np.zeros(max(int(bins), 0), np.float32)
         sd = SpectralDesc(bins)
-        self.check(self._spectral_bin_centres(C.byref(rd), C.byref(sd), _fp(centres)))
+        self.call("spectral_bin_centres", C.byref(rd), C.byref(sd), _fp(centres))
         return centres
 
     def write_exr_spectral(self, path, centres_nm, spectral, linear_rgb=None, colorspace=COLORSPACE_SRGB):
         """pt_write_exr_spectral: spectral [bins,H,W] as one FLOAT channel per bin (S0.<centre>nm), with R, G, B from linear_rgb [H,W,3] if given."""
-        if self._write_exr_spectral is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %swrite_exr_spectral entry" % (self.path, self.prefix))
+        self.entry("write_exr_spectral")
         spectral = np.ascontiguousarray(spectral, np.float32)
         centres_nm = np.ascontiguousarray(centres_nm, np.float32)
         if spectral.ndim != 3 or centres_nm.shape != (spectral.shape[0],):
@@ -560,18 +560,13 @@ class Library:
             linear_rgb = np.ascontiguousarray(linear_rgb, np.float32)
             if linear_rgb.shape != (h, w, 3):
                 raise ValueError("linear_rgb [H, W, 3] of the spectral film's size")
-        self.check(self._write_exr_spectral(path.encode(), w, h, bins, _fp(centres_nm), _fp(spectral), _fp(linear_rgb) if linear_rgb is not None else None, colorspace))
-
-    def _project_error(self):
-        err = self._spectral_project_last_error
-        return err().decode() if err else self.last_error()
+        self.call("write_exr_spectral", path.encode(), w, h, bins, _fp(centres_nm), _fp(spectral), _fp(linear_rgb), colorspace)
 
     def spectral_response_matrix(self, rd, bins, responses, curves=None, curve_data=None, filter=None, subsamples=1):
         """pt_spectral_response_matrix: float32 [K, bins], row k the response responses[k] — an index into `curves` (a sequence of api.Curve whose data_offset
         points into `curve_data`, as in a scene description) or RESPONSE_CIE_X / _Y / _Z — integrated over each of the `bins` bins of a render `rd` with
         `subsamples` samples per bin, behind the curve `filter` (an index into `curves`) if one is given.  Host only."""
-        if self._spectral_response_matrix is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sspectral_response_matrix entry" % (self.path, self.prefix))
+        self.entry("spectral_response_matrix")
         responses = [int(r) for r in responses]
         K = len(responses)
         curves = list(curves) if curves is not None else []
@@ -580,10 +575,8 @@ class Library:
         rarr = (C.c_int32 * max(K, 1))(*responses)
         matrix = np.zeros((K, max(int(bins), 0)), np.float32)
         sd = SpectralDesc(bins)
-        st = self._spectral_response_matrix(C.byref(rd), C.byref(sd), carr if curves else None, len(curves), _fp(cd) if cd.size else None, cd.size, K, rarr,
-                                            SPECTRAL_NO_FILTER if filter is None else int(filter), subsamples, _fp(matrix))
-        if st != PT_OK:
-            raise PtError(st, self._project_error())
+        self.call("spectral_response_matrix", C.byref(rd), C.byref(sd), carr if curves else None, len(curves), _fp(cd) if cd.size else None, cd.size, K, rarr,
+                  SPECTRAL_NO_FILTER if filter is None else int(filter), subsamples, _fp(matrix))
         return matrix
 
     def spectral_observer_matrix(self, rd, bins, subsamples=1):
@@ -593,8 +586,7 @@ class Library:
     def spectral_project(self, spectral, matrix):
         """pt_spectral_project: spectral [B,H,W] projected onto the rows of matrix [K,B]: float32 [K,H,W], out[k] = the f32 fold of matrix[k,b] * spectral[b]
         over b ascending."""
-        if self._spectral_project is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sspectral_project entry" % (self.path, self.prefix))
+        self.entry("spectral_project")
         spectral = np.ascontiguousarray(spectral, dtype=np.float32)
         matrix = np.ascontiguousarray(matrix, dtype=np.float32)
         if spectral.ndim != 3 or matrix.ndim != 2 or matrix.shape[1] != spectral.shape[0]:
@@ -602,42 +594,28 @@ class Library:
         bins, h, w = spectral.shape
         K = matrix.shape[0]
         out = np.zeros((K, h, w), np.float32)
-        st = self._spectral_project(w, h, bins, K, _fp(matrix), _fp(spectral), _fp(out))
-        if st != PT_OK:
-            raise PtError(st, self._project_error())
+        self.call("spectral_project", w, h, bins, K, _fp(matrix), _fp(spectral), _fp(out))
         return out
-
-    def _light_groups_check(self, status):
-        if status != PT_OK:
-            err = self._light_groups_last_error
-            raise PtError(status, err().decode() if err else self.last_error())
 
     def light_groups_mix(self, group_films, matrices):
         """pt_light_groups_mix: group_films [G,H,W,4] mixed by matrices [G,3,3] (light_group_gains makes them from scalars): float32 [H,W,4], per channel the f32
         fold over g ascending of acc + ((m[g,c,0] * X_g + m[g,c,1] * Y_g) + m[g,c,2] * Z_g); w = 0."""
-        if self._light_groups_mix is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %slight_groups_mix entry" % (self.path, self.prefix))
+        self.entry("light_groups_mix")
         group_films = np.ascontiguousarray(group_films, dtype=np.float32)
         matrices = np.ascontiguousarray(matrices, dtype=np.float32)
         if group_films.ndim != 4 or group_films.shape[3] != 4 or matrices.shape != (group_films.shape[0], 3, 3):
             raise ValueError("group_films [G,H,W,4] and matrices [G,3,3]")
         G, h, w, _ = group_films.shape
         out = np.zeros((h, w, 4), np.float32)
-        self._light_groups_check(self._light_groups_mix(w, h, G, _fp(group_films), _fp(matrices), _fp(out)))
+        self.call("light_groups_mix", w, h, G, _fp(group_films), _fp(matrices), _fp(out))
         return out
-
-    def _light_groups_spectral_check(self, status):
-        if status != PT_OK:
-            err = self._light_groups_spectral_last_error
-            raise PtError(status, err().decode() if err else self.last_error())
 
     def light_groups_relamp_matrix(self, rd, bins, responses, groups, old_curve, new_curve, gain=None, curves=None, curve_data=None, filter=None, subsamples=1):
         """pt_light_groups_relamp_matrix: float32 [K, G, bins], the matrix of a re-lamp of `groups` = G groups rendered with `bins` bins.  responses, curves,
         curve_data, filter and subsamples are spectral_response_matrix's.  old_curve[g] / new_curve[g]: indices into `curves` — group g's emission curve as it
         was rendered and the one to see it under — or RELAMP_KEEP (None); gain [G] (None = all 1).  Entry [k, g, b] integrates response k times
         new / old over bin b.  With KEEP and gain 1 a group's rows are spectral_response_matrix's bit for bit.  Host only."""
-        if self._light_groups_relamp_matrix is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %slight_groups_relamp_matrix entry" % (self.path, self.prefix))
+        self.entry("light_groups_relamp_matrix")
         responses = [int(r) for r in responses]
         K, G = len(responses), int(groups)
         keep = lambda seq: [RELAMP_KEEP if c is None else int(c) for c in seq]
@@ -656,16 +634,14 @@ class Library:
                 raise ValueError("gain: one factor per group")
         matrix = np.zeros((K, max(G, 0), max(int(bins), 0)), np.float32)
         sd = SpectralDesc(bins)
-        self._light_groups_spectral_check(self._light_groups_relamp_matrix(
-            C.byref(rd), C.byref(sd), carr if curves else None, len(curves), _fp(cd) if cd.size else None, cd.size, K, rarr,
-            SPECTRAL_NO_FILTER if filter is None else int(filter), subsamples, G, oarr, narr, _fp(garr) if garr is not None else None, _fp(matrix)))
+        self.call("light_groups_relamp_matrix", C.byref(rd), C.byref(sd), carr if curves else None, len(curves), _fp(cd) if cd.size else None, cd.size, K, rarr,
+                  SPECTRAL_NO_FILTER if filter is None else int(filter), subsamples, G, oarr, narr, _fp(garr), _fp(matrix))
         return matrix
 
     def light_groups_relamp(self, group_spectral, matrix):
         """pt_light_groups_relamp: group_spectral [G,B,H,W] developed by matrix [K,G,B] (light_groups_relamp_matrix makes one): float32 [K,H,W], out[k] = the f32
         fold of matrix[k,g,b] * group_spectral[g,b] over the planes g * B + b ascending."""
-        if self._light_groups_relamp is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %slight_groups_relamp entry" % (self.path, self.prefix))
+        self.entry("light_groups_relamp")
         group_spectral = np.ascontiguousarray(group_spectral, dtype=np.float32)
         matrix = np.ascontiguousarray(matrix, dtype=np.float32)
         if group_spectral.ndim != 4 or matrix.ndim != 3 or matrix.shape[1:] != group_spectral.shape[:2]:
@@ -673,7 +649,7 @@ class Library:
         G, bins, h, w = group_spectral.shape
         K = matrix.shape[0]
         out = np.zeros((K, h, w), np.float32)
-        self._light_groups_spectral_check(self._light_groups_relamp(w, h, G, bins, K, _fp(matrix), _fp(group_spectral), _fp(out)))
+        self.call("light_groups_relamp", w, h, G, bins, K, _fp(matrix), _fp(group_spectral), _fp(out))
         return out
 
     def denoise_light_groups(self, film, counts, stats, guides, group_films, albedo=None, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0,
@@ -681,30 +657,12 @@ class Library:
         """pt_denoise_light_groups: the joint filter over the film and its group films [G,H,W,4] — the taps and weights of denoise_film (with `albedo` [H,W,4]:
         of its demodulated form, and the groups are divided by the albedo too) applied to every group channel.  Returns (denoised film, denoised group films[,
         variance]); the group films are bit for bit denoise_spectral_albedo's planes for the 3G planes of the groups' channels."""
-        if self._denoise_light_groups is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sdenoise_light_groups entry" % (self.path, self.prefix))
-        film = np.ascontiguousarray(film, dtype=np.float32)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        stats = np.ascontiguousarray(stats, dtype=np.float64)
-        guides = np.ascontiguousarray(guides, dtype=np.float32)
-        group_films = np.ascontiguousarray(group_films, dtype=np.float32)
-        h, w = film.shape[:2]
-        if film.shape != (h, w, 4) or counts.shape != (h, w) or stats.shape != (h, w, 2) or guides.shape != (h, w, 4) or group_films.ndim != 4 or group_films.shape[1:] != (h, w, 4):
-            raise ValueError("film [H,W,4], counts [H,W], stats [H,W,2], guides [H,W,4] and group_films [G,H,W,4] of one film size")
-        G = group_films.shape[0]
-        if albedo is not None:
-            albedo = np.ascontiguousarray(albedo, dtype=np.float32)
-            if albedo.shape != (h, w, 4):
-                raise ValueError("albedo [H,W,4] of the film's size")
+        self.entry("denoise_light_groups")
+        h, w, film, counts, stats, guides, group_films, albedo, _ = _filter_inputs(film, counts, stats, guides, group_films, _GROUPS_LAYOUT, albedo)
         d = DenoiseDesc(w, h, iterations, sigma_luminance, sigma_depth, normal_power_log2, device)
-        out = np.zeros((h, w, 4), np.float32)
-        out_groups = np.zeros((G, h, w, 4), np.float32)
-        var = np.zeros((h, w), np.float32) if variance else None
-        st = self._denoise_light_groups(C.byref(d), G, _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)), stats.ctypes.data_as(C.POINTER(C.c_double)), _fp(guides),
-                                        _fp(albedo) if albedo is not None else None, _fp(group_films), _fp(out), _fp(var) if variance else None, _fp(out_groups))
-        if st != PT_OK:
-            err = self._denoise_light_groups_last_error
-            raise PtError(st, err().decode() if err else self.last_error())
+        out, var, out_groups = _filter_outputs(h, w, variance, group_films)
+        self.call("denoise_light_groups", C.byref(d), group_films.shape[0], _fp(film), _u32p(counts), _f64p(stats), _fp(guides), _fp(albedo), _fp(group_films), _fp(out),
+                  _fp(var), _fp(out_groups))
         return (out, out_groups, var) if variance else (out, out_groups)
 
 
@@ -721,9 +679,9 @@ class Scene:
         if tuning is not None:
             if library._scene_create_tuned is None:
                 raise PtError(PT_ERR_UNSUPPORTED, "this library does not export %sscene_create_tuned (pt_tuning is the HIP engine's)" % library.prefix)
-            library.check(library._scene_create_tuned(C.byref(desc), C.byref(tuning), C.byref(handle)))
+            library.call("scene_create_tuned", C.byref(desc), C.byref(tuning), C.byref(handle))
         else:
-            library.check(library._scene_create(C.byref(desc), C.byref(handle)))
+            library.call("scene_create", C.byref(desc), C.byref(handle))
         self.handle = handle
 
     def close(self):
@@ -741,112 +699,144 @@ class Scene:
         """True when closest-hit queries on this scene take the leaf sweep (<= 64 leaves) instead of the BVH walk."""
         return bool(self.library._debug_scene_info(self.handle, 4))
 
+    def _call(self, name, *args):
+        """Library.call of an entry that takes the scene first."""
+        self.library.call(name, self.handle, *args)
+
+    def _render_call(self, name, rd, adaptive=None, groups=None, bins=None, device_mask=None, stats=False, read_groups=True, read_bins=True):
+        """The one render call behind the render* methods: the entry `name` with the arguments it takes, in the order all of them share — rd,
+        adaptive desc, groups desc, spectral desc, device mask, film, counts, stats, group films, spectral, group spectral, profile — and the outputs in
+        that order, the stats only with `stats`.  adaptive: (max_samples, step, rel_error, abs_error); groups: (instance_group, environment_group, G or None:
+        the largest id, the environment's included, plus one); what read_groups / read_bins do not ask for is passed, and returned, as None."""
+        self.library.entry(name)
+        h, w = rd.height, rd.width
+        descs, pointers, outs, prof = [rd], [], [], Profile()
+
+        def out(*shape, read=True):
+            a = np.zeros(shape, dtype=np.float32) if read else None
+            pointers.append(_fp(a))
+            outs.append(a)
+        out(h, w, 4)
+        if adaptive is not None:
+            descs.append(AdaptiveDesc(*adaptive))
+            counts = np.zeros((h, w), dtype=np.uint32)
+            st = np.zeros((h, w, 2), dtype=np.float64) if stats else None
+            pointers += [_u32p(counts), _f64p(st)]
+            outs += [counts, st] if stats else [counts]
+        if groups is not None:
+            instance_group, environment_group, G = groups
+            ids = np.ascontiguousarray(instance_group, dtype=np.uint8).reshape(-1)
+            G = int(G) if G is not None else int(max([int(environment_group)] + [int(i) for i in ids])) + 1
+            descs.append(LightGroupsDesc(G, ids.size, _u8p(ids), int(environment_group)))
+            out(max(G, 0), h, w, 4, read=read_groups)
+        if bins is not None:
+            descs.append(SpectralDesc(bins))
+            out(max(int(bins), 0), h, w, read=read_bins)
+            if groups is not None:
+                out(max(G, 0), max(int(bins), 0), h, w, read=read_bins)
+        mask = [] if device_mask is None else [C.c_uint64(device_mask)]
+        self._call(name, *[C.byref(d) for d in descs], *mask, *pointers, C.byref(prof))
+        return (*outs, prof)
+
     def render(self, rd):
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        prof = Profile()
-        self.library.check(self.library._render(self.handle, C.byref(rd), _fp(film), C.byref(prof)))
-        return film, prof
+        return self._render_call("render", rd)
+
+    def render_multi(self, rd, device_mask=0):
+        """pt_render_multi: every device of the mask (0 = all) from one blocking call."""
+        return self._render_call("render_multi", rd, device_mask=device_mask)
 
     def render_spectral(self, rd, bins):
         """pt_render_spectral: (film, spectral, profile) — film [H,W,4] is render(rd)'s bit for bit; spectral [bins,H,W] f32 holds per pixel the mean
         per-sample energy that fell into each of `bins` equal wavelength bins over rd's bounds (Library.spectral_bin_centres gives their centres)."""
-        if self.library._render_spectral is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_spectral entry" % (self.library.path, self.library.prefix))
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        spectral = np.zeros((max(int(bins), 0), rd.height, rd.width), dtype=np.float32)
-        sd = SpectralDesc(bins)
-        prof = Profile()
-        self.library.check(self.library._render_spectral(self.handle, C.byref(rd), C.byref(sd), _fp(film), _fp(spectral), C.byref(prof)))
-        return film, spectral, prof
+        return self._render_call("render_spectral", rd, bins=bins)
 
     def render_spectral_multi(self, rd, bins, device_mask=0):
         """pt_render_spectral_multi: render_spectral on every device of the mask (0 = all) from one blocking call, its outputs bit for bit.  Every device hands
         over the bins of its own tiles; they stay on it as its part of the scene's resident film."""
-        if self.library._render_spectral_multi is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_spectral_multi entry" % (self.library.path, self.library.prefix))
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        spectral = np.zeros((max(int(bins), 0), rd.height, rd.width), dtype=np.float32)
-        sd = SpectralDesc(bins)
-        prof = Profile()
-        self.library.check(self.library._render_spectral_multi(self.handle, C.byref(rd), C.byref(sd), C.c_uint64(device_mask), _fp(film), _fp(spectral), C.byref(prof)))
-        return film, spectral, prof
+        return self._render_call("render_spectral_multi", rd, bins=bins, device_mask=device_mask)
 
-    def spectral_resident(self):
-        """pt_spectral_resident: (width, height, bins) of the spectral film the last successful spectral render (one device or a node) left on the device(s), or
-        None when the scene holds none."""
-        if self.library._spectral_resident is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sspectral_resident entry" % (self.library.path, self.library.prefix))
-        w, h, b = C.c_uint32(), C.c_uint32(), C.c_uint32()
-        self.library.check(self.library._spectral_resident(self.handle, C.byref(w), C.byref(h), C.byref(b)))
-        return (w.value, h.value, b.value) if b.value else None
+    def render_adaptive(self, rd, max_samples, rel_error, abs_error=0.0, step=0, stats=False):
+        """pt_render_adaptive: rd.spp samples per pixel at least, max_samples at most, `step` more per round (0 = rd.spp) while a pixel or one of its
+        neighbours has not reached the target error.  Returns (film, counts[, stats], profile): counts [H,W] u32, stats [H,W,2] f64 (S1, S2)."""
+        return self._render_call("render_adaptive", rd, (max_samples, step, rel_error, abs_error), stats=stats)
+
+    def render_adaptive_multi(self, rd, max_samples, rel_error, abs_error=0.0, step=0, stats=False, device_mask=0):
+        """pt_render_adaptive_multi: render_adaptive on every device of the mask (0 = all) from one blocking call, its outputs bit for bit.
+        Returns (film, counts[, stats], profile) as render_adaptive does."""
+        return self._render_call("render_adaptive_multi", rd, (max_samples, step, rel_error, abs_error), device_mask=device_mask, stats=stats)
+
+    def render_adaptive_spectral(self, rd, bins, max_samples, rel_error, abs_error=0.0, step=0, stats=False):
+        """pt_render_adaptive_spectral: render_adaptive with a spectral film.  Returns (film, counts[, stats], spectral, profile): film, counts and stats are
+        render_adaptive's bit for bit; spectral [bins,H,W] holds per pixel the bins of render_spectral at that pixel's own sample count."""
+        return self._render_call("render_adaptive_spectral", rd, (max_samples, step, rel_error, abs_error), bins=bins, stats=stats)
+
+    def render_adaptive_spectral_multi(self, rd, bins, max_samples, rel_error, abs_error=0.0, step=0, stats=False, device_mask=0):
+        """pt_render_adaptive_spectral_multi: render_adaptive_spectral on every device of the mask (0 = all) from one blocking call, its outputs bit for bit.
+        Returns (film, counts[, stats], spectral, profile) as render_adaptive_spectral does."""
+        return self._render_call("render_adaptive_spectral_multi", rd, (max_samples, step, rel_error, abs_error), bins=bins, device_mask=device_mask, stats=stats)
 
     def render_light_groups(self, rd, instance_group, environment_group=0, groups=None, read_groups=True):
         """pt_render_light_groups: (film, group_films, profile) — film [H,W,4] is render(rd)'s bit for bit; group_films [G,H,W,4] holds per group the film of the
         energy its emitters contributed.  instance_group: one group id per instance of the scene; groups: G (None = the largest id + 1); read_groups False leaves
         the group films on the device alone (group_films is None) for light_groups_mix_resident."""
-        entry = self._resident_entry("render_light_groups")
-        ids = np.ascontiguousarray(instance_group, dtype=np.uint8).reshape(-1)
-        G = int(groups) if groups is not None else int(max([int(environment_group)] + [int(i) for i in ids])) + 1
-        gd = LightGroupsDesc(G, ids.size, ids.ctypes.data_as(C.POINTER(C.c_uint8)), int(environment_group))
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        group_films = np.zeros((max(G, 0), rd.height, rd.width, 4), dtype=np.float32) if read_groups else None
-        prof = Profile()
-        self.library._light_groups_check(entry(self.handle, C.byref(rd), C.byref(gd), _fp(film), _fp(group_films) if read_groups else None, C.byref(prof)))
-        return film, group_films, prof
+        return self._render_call("render_light_groups", rd, groups=(instance_group, environment_group, groups), read_groups=read_groups)
 
     def render_light_groups_multi(self, rd, instance_group, environment_group=0, groups=None, read_groups=True, device_mask=0):
         """pt_render_light_groups_multi: render_light_groups on every device of the mask (0 = all) from one blocking call, its outputs bit for bit.  Every device
         hands over the group films of its own tiles (read_groups False: none of them) and keeps them, packed, as its part of the scene's resident group films."""
-        entry = self._resident_entry("render_light_groups_multi")
-        ids = np.ascontiguousarray(instance_group, dtype=np.uint8).reshape(-1)
-        G = int(groups) if groups is not None else int(max([int(environment_group)] + [int(i) for i in ids])) + 1
-        gd = LightGroupsDesc(G, ids.size, ids.ctypes.data_as(C.POINTER(C.c_uint8)), int(environment_group))
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        group_films = np.zeros((max(G, 0), rd.height, rd.width, 4), dtype=np.float32) if read_groups else None
-        prof = Profile()
-        self.library._light_groups_check(entry(self.handle, C.byref(rd), C.byref(gd), C.c_uint64(device_mask), _fp(film), _fp(group_films) if read_groups else None,
-                                               C.byref(prof)))
-        return film, group_films, prof
-
-    def light_groups_resident(self):
-        """pt_light_groups_resident: (width, height, groups) of the group films the last successful light-group render left on the device(s), or None."""
-        entry = self._resident_entry("light_groups_resident")
-        w, h, g = C.c_uint32(), C.c_uint32(), C.c_uint32()
-        self.library._light_groups_check(entry(self.handle, C.byref(w), C.byref(h), C.byref(g)))
-        return (w.value, h.value, g.value) if g.value else None
+        return self._render_call("render_light_groups_multi", rd, groups=(instance_group, environment_group, groups), device_mask=device_mask, read_groups=read_groups)
 
     def render_light_groups_spectral(self, rd, bins, instance_group, environment_group=0, groups=None, read_groups=True, read_bins=True):
         """pt_render_light_groups_spectral: (film, group_films, spectral, group_spectral, profile) — film [H,W,4] and group_films [G,H,W,4] are
         render_light_groups' bit for bit, spectral [bins,H,W] is render_spectral's bit for bit, and group_spectral [G,bins,H,W] holds per group the bins of the
         energy its emitters contributed.  read_groups False leaves the group films on the device alone (None), read_bins False the total and the group bins (both
         None), for light_groups_relamp_resident and spectral_project_resident."""
-        entry = self._resident_entry("render_light_groups_spectral")
-        ids = np.ascontiguousarray(instance_group, dtype=np.uint8).reshape(-1)
-        G = int(groups) if groups is not None else int(max([int(environment_group)] + [int(i) for i in ids])) + 1
-        gd = LightGroupsDesc(G, ids.size, ids.ctypes.data_as(C.POINTER(C.c_uint8)), int(environment_group))
-        sd = SpectralDesc(bins)
-        B = max(int(bins), 0)
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        group_films = np.zeros((max(G, 0), rd.height, rd.width, 4), dtype=np.float32) if read_groups else None
-        spectral = np.zeros((B, rd.height, rd.width), dtype=np.float32) if read_bins else None
-        group_spectral = np.zeros((max(G, 0), B, rd.height, rd.width), dtype=np.float32) if read_bins else None
-        prof = Profile()
-        self.library._light_groups_spectral_check(entry(self.handle, C.byref(rd), C.byref(gd), C.byref(sd), _fp(film), _fp(group_films) if read_groups else None,
-                                                        _fp(spectral) if read_bins else None, _fp(group_spectral) if read_bins else None, C.byref(prof)))
-        return film, group_films, spectral, group_spectral, prof
+        return self._render_call("render_light_groups_spectral", rd, groups=(instance_group, environment_group, groups), bins=bins, read_groups=read_groups,
+                                 read_bins=read_bins)
+
+    def render_adaptive_light_groups(self, rd, max_samples, rel_error, instance_group, environment_group=0, groups=None, abs_error=0.0, step=0, stats=False, read_groups=True):
+        """pt_render_adaptive_light_groups: (film, counts[, stats], group_films, profile) — film, counts and stats are render_adaptive's bit for bit; group_films
+        [G,H,W,4] holds per pixel the group films of render_light_groups at that pixel's own sample count.  The scene then holds the resident film of
+        render_adaptive and the group films of render_light_groups, paired for denoise_light_groups_resident.  read_groups False: group_films is None."""
+        return self._render_call("render_adaptive_light_groups", rd, (max_samples, step, rel_error, abs_error), (instance_group, environment_group, groups), stats=stats,
+                                 read_groups=read_groups)
+
+    def render_adaptive_light_groups_multi(self, rd, max_samples, rel_error, instance_group, environment_group=0, groups=None, abs_error=0.0, step=0, stats=False,
+                                           read_groups=True, device_mask=0):
+        """pt_render_adaptive_light_groups_multi: render_adaptive_light_groups on every device of the mask (0 = all) from one blocking call, its outputs bit for
+        bit.  Over more than one (virtual) device the group films stay resident as packed shards, paired with no film, until resident_assemble (after a call
+        with stats=True) gathers film and group films on the scene's device."""
+        return self._render_call("render_adaptive_light_groups_multi", rd, (max_samples, step, rel_error, abs_error), (instance_group, environment_group, groups),
+                                 device_mask=device_mask, stats=stats, read_groups=read_groups)
+
+    def _resident_dims(self, name, count=3):
+        """A pt_*_resident query: (width, height, planes[, bins]) of what a render left on the device(s), None when it left none."""
+        dims = [C.c_uint32() for _ in range(count)]
+        self._call(name, *[C.byref(d) for d in dims])
+        return tuple(d.value for d in dims) if dims[2].value else None
+
+    def spectral_resident(self):
+        """pt_spectral_resident: (width, height, bins) of the spectral film the last successful spectral render (one device or a node) left on the device(s), or
+        None when the scene holds none."""
+        return self._resident_dims("spectral_resident")
+
+    def light_groups_resident(self):
+        """pt_light_groups_resident: (width, height, groups) of the group films the last successful light-group render left on the device(s), or None."""
+        return self._resident_dims("light_groups_resident")
 
     def light_groups_spectral_resident(self):
         """pt_light_groups_spectral_resident: (width, height, groups, bins) of the group bins the last successful render_light_groups_spectral left on the device, or
         None (any other group render ends them)."""
-        entry = self._resident_entry("light_groups_spectral_resident")
-        w, h, g, b = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
-        self.library._light_groups_spectral_check(entry(self.handle, C.byref(w), C.byref(h), C.byref(g), C.byref(b)))
-        return (w.value, h.value, g.value, b.value) if g.value else None
+        return self._resident_dims("light_groups_spectral_resident", 4)
+
+    def light_groups_denoised_resident(self):
+        """pt_light_groups_denoised_resident: (width, height, groups) of the denoised group films denoise_light_groups_resident left on the device, or None."""
+        return self._resident_dims("light_groups_denoised_resident")
 
     def light_groups_relamp_resident(self, matrix):
         """pt_light_groups_relamp_resident: Library.light_groups_relamp of the resident group bins with matrix [K,G,B] — float32 [K,H,W], bit for bit what the
         host-array entry gives for the bins render_light_groups_spectral returned; only the matrix goes up and K planes come back."""
-        entry = self._resident_entry("light_groups_relamp_resident")
+        self.library.entry("light_groups_relamp_resident")
         res = self.light_groups_spectral_resident()
         if res is None:
             w = h = G = B = 0
@@ -857,63 +847,15 @@ class Scene:
             raise ValueError("matrix [K,%d,%d] for the resident group bins" % (G, B))
         K = matrix.shape[0] if matrix.ndim else 0
         out = np.zeros((K, h, w), np.float32)
-        self.library._light_groups_spectral_check(entry(self.handle, K, _fp(matrix), _fp(out) if out.size else _fp(np.zeros(1, np.float32))))
+        self._call("light_groups_relamp_resident", K, _fp(matrix), _fp(out) if out.size else _fp(np.zeros(1, np.float32)))
         return out
-
-    def render_adaptive_light_groups(self, rd, max_samples, rel_error, instance_group, environment_group=0, groups=None, abs_error=0.0, step=0, stats=False, read_groups=True):
-        """pt_render_adaptive_light_groups: (film, counts[, stats], group_films, profile) — film, counts and stats are render_adaptive's bit for bit; group_films
-        [G,H,W,4] holds per pixel the group films of render_light_groups at that pixel's own sample count.  The scene then holds the resident film of
-        render_adaptive and the group films of render_light_groups, paired for denoise_light_groups_resident.  read_groups False: group_films is None."""
-        entry = self._resident_entry("render_adaptive_light_groups")
-        ids = np.ascontiguousarray(instance_group, dtype=np.uint8).reshape(-1)
-        G = int(groups) if groups is not None else int(max([int(environment_group)] + [int(i) for i in ids])) + 1
-        gd = LightGroupsDesc(G, ids.size, ids.ctypes.data_as(C.POINTER(C.c_uint8)), int(environment_group))
-        ad = AdaptiveDesc(max_samples, step, rel_error, abs_error)
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        counts = np.zeros((rd.height, rd.width), dtype=np.uint32)
-        st = np.zeros((rd.height, rd.width, 2), dtype=np.float64) if stats else None
-        group_films = np.zeros((max(G, 0), rd.height, rd.width, 4), dtype=np.float32) if read_groups else None
-        prof = Profile()
-        status = entry(self.handle, C.byref(rd), C.byref(ad), C.byref(gd), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
-                       st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, _fp(group_films) if read_groups else None, C.byref(prof))
-        if status != PT_OK:
-            err = self.library._adaptive_light_groups_last_error
-            raise PtError(status, err().decode() if err else self.library.last_error())
-        return (film, counts, st, group_films, prof) if stats else (film, counts, group_films, prof)
-
-    def render_adaptive_light_groups_multi(self, rd, max_samples, rel_error, instance_group, environment_group=0, groups=None, abs_error=0.0, step=0, stats=False,
-                                           read_groups=True, device_mask=0):
-        """pt_render_adaptive_light_groups_multi: render_adaptive_light_groups on every device of the mask (0 = all) from one blocking call, its outputs bit for
-        bit.  Over more than one (virtual) device the group films stay resident as packed shards, paired with no film, until resident_assemble (after a call
-        with stats=True) gathers film and group films on the scene's device."""
-        entry = self._resident_entry("render_adaptive_light_groups_multi")
-        ids = np.ascontiguousarray(instance_group, dtype=np.uint8).reshape(-1)
-        G = int(groups) if groups is not None else int(max([int(environment_group)] + [int(i) for i in ids])) + 1
-        gd = LightGroupsDesc(G, ids.size, ids.ctypes.data_as(C.POINTER(C.c_uint8)), int(environment_group))
-        ad = AdaptiveDesc(max_samples, step, rel_error, abs_error)
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        counts = np.zeros((rd.height, rd.width), dtype=np.uint32)
-        st = np.zeros((rd.height, rd.width, 2), dtype=np.float64) if stats else None
-        group_films = np.zeros((max(G, 0), rd.height, rd.width, 4), dtype=np.float32) if read_groups else None
-        prof = Profile()
-        status = entry(self.handle, C.byref(rd), C.byref(ad), C.byref(gd), C.c_uint64(device_mask), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
-                       st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, _fp(group_films) if read_groups else None, C.byref(prof))
-        self.library.check(status)
-        return (film, counts, st, group_films, prof) if stats else (film, counts, group_films, prof)
-
-    def light_groups_denoised_resident(self):
-        """pt_light_groups_denoised_resident: (width, height, groups) of the denoised group films denoise_light_groups_resident left on the device, or None."""
-        entry = self._resident_entry("light_groups_denoised_resident")
-        w, h, g = C.c_uint32(), C.c_uint32(), C.c_uint32()
-        self.library.check(entry(self.handle, C.byref(w), C.byref(h), C.byref(g)))
-        return (w.value, h.value, g.value) if g.value else None
 
     def denoise_light_groups_resident(self, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, film=True, variance=False, groups=True):
         """pt_denoise_light_groups_resident: Library.denoise_light_groups over the resident film, guides (and albedo, which selects demodulation) and the group
         films render_adaptive_light_groups left with that film.  Returns the tuple of what was asked for, in this order: the denoised film [H,W,4] (film), its
         variance [H,W] (variance), the denoised group films [G,H,W,4] (groups) — one array when one is asked for, None when none is.  What is not asked for
         does not cross the bus; the denoised group films stay on the device for light_groups_mix_resident(m, denoised=True)."""
-        entry = self._resident_entry("denoise_light_groups_resident")
+        self.library.entry("denoise_light_groups_resident")
         w, h, _, _ = self.resident_info()
         res = self.light_groups_resident()
         G = res[2] if res else 0
@@ -921,9 +863,17 @@ class Scene:
         out = np.zeros((h, w, 4), np.float32) if film else None
         var = np.zeros((h, w), np.float32) if variance else None
         gf = np.zeros((G, h, w, 4), np.float32) if groups else None
-        self.library.check(entry(self.handle, C.byref(d), _fp(out) if film else None, _fp(var) if variance else None, _fp(gf) if groups else None))
-        got = tuple(a for a in (out, var, gf) if a is not None)
-        return got[0] if len(got) == 1 else (got if got else None)
+        self._call("denoise_light_groups_resident", C.byref(d), _fp(out), _fp(var), _fp(gf))
+        return _asked(out, var, gf)
+
+    def _host_guides(self, rd, guide_samples, specular_chain, albedo):
+        """(guides, albedo or None) on the host for a filter over host arrays: at the end of the specular chains when specular_chain is not None, else with
+        the albedo of the first hit, else the plain guides."""
+        if specular_chain is not None:
+            return self.render_guides_chain(rd, guide_samples, specular_chain, albedo=albedo)
+        if albedo:
+            return self.render_guides_albedo(rd, guide_samples)
+        return self.render_guides(rd, guide_samples), None
 
     def render_denoised_light_groups(self, rd, instance_group, environment_group=0, groups=None, max_samples=None, rel_error=0.0, abs_error=0.0, step=0, guide_samples=4,
                                      specular_chain=0, albedo=False, iterations=0, sigma_luminance=0.0, sigma_depth=0.0, normal_power_log2=0, device_mask=None,
@@ -937,27 +887,19 @@ class Scene:
         mx = rd.spp if max_samples is None else max_samples
         if assemble and device_mask is None:
             raise ValueError("assemble gathers a node render: it needs a device_mask")
-        if device_mask is not None:
+        if device_mask is None:
+            film, counts, st, group_films, prof = self.render_adaptive_light_groups(rd, mx, rel_error, instance_group, environment_group, groups, abs_error, step, stats=True)
+        else:
             film, counts, st, group_films, prof = self.render_adaptive_light_groups_multi(rd, mx, rel_error, instance_group, environment_group, groups, abs_error, step,
                                                                                           stats=True, device_mask=device_mask)
-            if assemble:
-                self._assemble_node_render()
-            elif not (self.resident_info()[3] & RESIDENT_FILM):   # (a mask that came down to the scene's device left the film resident itself)
-                first = 0
-                while device_mask and not (device_mask >> first) & 1:
-                    first += 1
-                if specular_chain > 0:
-                    guides, alb = self.render_guides_chain(rd, guide_samples, specular_chain, albedo=albedo)
-                elif albedo:
-                    guides, alb = self.render_guides_albedo(rd, guide_samples)
-                else:
-                    guides, alb = self.render_guides(rd, guide_samples), None
-                den, den_groups = self.library.denoise_light_groups(film, counts, st, guides, group_films, albedo=alb, iterations=iterations,
-                                                                    sigma_luminance=sigma_luminance, sigma_depth=sigma_depth, normal_power_log2=normal_power_log2,
-                                                                    device=first)[:2]
-                return film, den, group_films, den_groups, counts, prof
-        else:
-            film, counts, st, group_films, prof = self.render_adaptive_light_groups(rd, mx, rel_error, instance_group, environment_group, groups, abs_error, step, stats=True)
+        if assemble:
+            self._assemble_node_render()
+        elif device_mask is not None and not (self.resident_info()[3] & RESIDENT_FILM):   # (a mask that came down to the scene's device left the film resident itself)
+            guides, alb = self._host_guides(rd, guide_samples, specular_chain if specular_chain > 0 else None, albedo)
+            den, den_groups = self.library.denoise_light_groups(film, counts, st, guides, group_films, albedo=alb, iterations=iterations,
+                                                                sigma_luminance=sigma_luminance, sigma_depth=sigma_depth, normal_power_log2=normal_power_log2,
+                                                                device=_first_device(device_mask))[:2]
+            return film, den, group_films, den_groups, counts, prof
         self.resident_guides(rd, guide_samples, specular_chain, albedo=albedo)
         den, den_groups = self.denoise_light_groups_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2)
         return film, den, group_films, den_groups, counts, prof
@@ -966,7 +908,8 @@ class Scene:
         """pt_light_groups_mix_resident: Library.light_groups_mix of the resident group films with matrices [G,3,3] — float32 [H,W,4], bit for bit what the host-array
         entry gives for the films render_light_groups returned; only the matrices go up and one film comes back.  `denoised`:
         pt_light_groups_mix_resident_denoised, the same of the group films that denoise_light_groups_resident left on the device."""
-        entry = self._resident_entry("light_groups_mix_resident_denoised" if denoised else "light_groups_mix_resident")
+        name = "light_groups_mix_resident_denoised" if denoised else "light_groups_mix_resident"
+        self.library.entry(name)
         res = self.light_groups_denoised_resident() if denoised else self.light_groups_resident()
         if res is None:
             raise PtError(PT_ERR_INVALID_ARGUMENT, "the scene has no resident denoised group films" if denoised else "the scene has no resident group films")
@@ -974,24 +917,13 @@ class Scene:
         if matrices.shape != (res[2], 3, 3):
             raise ValueError("matrices [G,3,3] with G = %d" % res[2])
         out = np.zeros((res[1], res[0], 4), np.float32)
-        self.library._light_groups_check(entry(self.handle, _fp(matrices), _fp(out)))
+        self._call(name, _fp(matrices), _fp(out))
         return out
-
-    def _resident_entry(self, name):
-        entry = getattr(self.library, "_" + name)
-        if entry is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %s%s entry" % (self.library.path, self.library.prefix, name))
-        return entry
-
-    def _resident_check(self, status):
-        if status != PT_OK:
-            err = self.library._resident_last_error
-            raise PtError(status, err().decode() if err else self.library.last_error())
 
     def resident_info(self):
         """pt_resident_info: (width, height, bins, parts) of the scene's resident set — parts a set of RESIDENT_* bits, all zeros when nothing is resident."""
         info = ResidentInfo()
-        self._resident_check(self._resident_entry("resident_info")(self.handle, C.byref(info)))
+        self._call("resident_info", C.byref(info))
         return info.width, info.height, info.bins, info.parts
 
     def resident_guides(self, rd, guide_samples=4, specular_chain=0, alpha_max=0.0, albedo=False, bin_albedo=False):
@@ -999,7 +931,7 @@ class Scene:
         specular_chain > 0 at the end of every sample's specular chain) for the resident film, the outputs kept on the device as resident parts."""
         cd = GuideChainDesc(specular_chain, alpha_max)
         flags = (RESIDENT_ALBEDO if albedo else 0) | (RESIDENT_BIN_ALBEDO if bin_albedo else 0)
-        self._resident_check(self._resident_entry("resident_guides")(self.handle, C.byref(rd), guide_samples, C.byref(cd) if specular_chain > 0 else None, flags))
+        self._call("resident_guides", C.byref(rd), guide_samples, C.byref(cd) if specular_chain > 0 else None, flags)
 
     def resident_load(self, film=None, counts=None, stats=None, guides=None, spectral=None, albedo=None, bin_albedo=None):
         """pt_resident_load: host arrays adopted as resident parts — film [H,W,4], counts [H,W] u32 and stats [H,W,2] f64 together, guides [H,W,4],
@@ -1016,16 +948,13 @@ class Scene:
         for a, last in ((film, 4), (stats, 2), (guides, 4), (albedo, 4)):
             if a is not None and a.shape[2] != last:
                 raise ValueError("film, guides and albedo [H,W,4], stats [H,W,2]")
-        p = lambda a: _fp(a) if a is not None else None
-        self._resident_check(self._resident_entry("resident_load")(
-            self.handle, w, h, nbins.pop() if nbins else 0, p(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)) if counts is not None else None,
-            stats.ctypes.data_as(C.POINTER(C.c_double)) if stats is not None else None, p(spectral), p(guides), p(albedo), p(bin_albedo)))
+        self._call("resident_load", w, h, nbins.pop() if nbins else 0, _fp(film), _u32p(counts), _f64p(stats), _fp(spectral), _fp(guides), _fp(albedo), _fp(bin_albedo))
 
     def resident_assemble(self, staged=False):
         """pt_resident_assemble: the pieces the last adaptive node render (render_adaptive_multi, render_adaptive_spectral_multi with stats=True) left on the
         devices gathered on the scene's own device as the resident film (and bins), device to device: resident_guides and denoise_resident then follow as after
         a one-device render.  `staged`: every shard of the bins goes through the staging copy, also one that lies on the scene's device; the bits are the same."""
-        self._resident_check(self._resident_entry("resident_assemble")(self.handle, RESIDENT_ASSEMBLE_STAGED if staged else 0))
+        self._call("resident_assemble", RESIDENT_ASSEMBLE_STAGED if staged else 0)
 
     def resident_read(self, film=True, counts=True, stats=True, spectral=False):
         """pt_resident_read: the resident film [H,W,4] (film), counts [H,W] u32 (counts), stats [H,W,2] f64 (stats) and bins [B,H,W] (spectral) copied to the
@@ -1035,10 +964,8 @@ class Scene:
         c = np.zeros((h, w), np.uint32) if counts else None
         st = np.zeros((h, w, 2), np.float64) if stats else None
         sp = np.zeros((bins, h, w), np.float32) if spectral else None
-        self._resident_check(self._resident_entry("resident_read")(self.handle, _fp(f) if film else None, c.ctypes.data_as(C.POINTER(C.c_uint32)) if counts else None,
-                                                                   st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, _fp(sp) if spectral else None))
-        res = tuple(a for a in (f, c, st, sp) if a is not None)
-        return res[0] if len(res) == 1 else (res if res else None)
+        self._call("resident_read", _fp(f), _u32p(c), _f64p(st), _fp(sp))
+        return _asked(f, c, st, sp)
 
     def _assemble_node_render(self):
         """Behind a node render: the film resident on the scene's device — it already is when the mask came down to this one device."""
@@ -1054,151 +981,66 @@ class Scene:
         out = np.zeros((h, w, 4), np.float32) if film else None
         var = np.zeros((h, w), np.float32) if variance else None
         sp = np.zeros((bins, h, w), np.float32) if spectral else None
-        self._resident_check(self._resident_entry("denoise_resident")(self.handle, C.byref(d), _fp(out) if film else None, _fp(var) if variance else None,
-                                                                      _fp(sp) if spectral else None))
-        res = tuple(a for a in (out, var, sp) if a is not None)
-        return res[0] if len(res) == 1 else (res if res else None)
+        self._call("denoise_resident", C.byref(d), _fp(out), _fp(var), _fp(sp))
+        return _asked(out, var, sp)
 
     def spectral_project_resident(self, matrix, denoised=False):
         """pt_spectral_project_resident: Library.spectral_project of the resident spectral film with matrix [K,B] — float32 [K,H,W], bit for bit what
         spectral_project gives for the array that render returned — without the bins crossing the bus.  `denoised`:
         pt_spectral_project_resident_denoised, the same of the bins that denoise_resident left on the device."""
-        if denoised:
-            entry = self._resident_entry("spectral_project_resident_denoised")
-            matrix = np.ascontiguousarray(matrix, dtype=np.float32)
-            if matrix.ndim != 2:
-                raise ValueError("matrix [K,B]")
-            w, h, bins, parts = self.resident_info()
-            if (parts & RESIDENT_DENOISED_BINS) and matrix.shape[1] != bins:
-                raise ValueError("matrix [K,B] with B = %d, the resident film's bins" % bins)
-            out = np.zeros((matrix.shape[0], h, w), np.float32)
-            self._resident_check(entry(self.handle, matrix.shape[0], _fp(matrix), _fp(out)))
-            return out
-        if self.library._spectral_project_resident is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %sspectral_project_resident entry" % (self.library.path, self.library.prefix))
+        name = "spectral_project_resident_denoised" if denoised else "spectral_project_resident"
+        self.library.entry(name)
         matrix = np.ascontiguousarray(matrix, dtype=np.float32)
         if matrix.ndim != 2:
             raise ValueError("matrix [K,B]")
-        res = self.spectral_resident()
-        w, h, bins = res if res else (0, 0, matrix.shape[1])   # (no resident film: the entry refuses, with its message)
-        if matrix.shape[1] != bins:
+        if denoised:
+            w, h, bins, parts = self.resident_info()
+            known = parts & RESIDENT_DENOISED_BINS
+        else:
+            res = self.spectral_resident()
+            w, h, bins = res if res else (0, 0, matrix.shape[1])   # (no resident film: the entry refuses, with its message)
+            known = True
+        if known and matrix.shape[1] != bins:
             raise ValueError("matrix [K,B] with B = %d, the resident film's bins" % bins)
         out = np.zeros((matrix.shape[0], h, w), np.float32)
-        self.library.check(self.library._spectral_project_resident(self.handle, matrix.shape[0], _fp(matrix), _fp(out)))
+        self._call(name, matrix.shape[0], _fp(matrix), _fp(out))
         return out
-
-    def render_adaptive(self, rd, max_samples, rel_error, abs_error=0.0, step=0, stats=False):
-        """pt_render_adaptive: rd.spp samples per pixel at least, max_samples at most, `step` more per round (0 = rd.spp) while a pixel or one of its
-        neighbours has not reached the target error.  Returns (film, counts[, stats], profile): counts [H,W] u32, stats [H,W,2] f64 (S1, S2)."""
-        if self.library._render_adaptive is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_adaptive entry" % (self.library.path, self.library.prefix))
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        counts = np.zeros((rd.height, rd.width), dtype=np.uint32)
-        st = np.zeros((rd.height, rd.width, 2), dtype=np.float64) if stats else None
-        ad = AdaptiveDesc(max_samples, step, rel_error, abs_error)
-        prof = Profile()
-        self.library.check(self.library._render_adaptive(self.handle, C.byref(rd), C.byref(ad), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                         st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, C.byref(prof)))
-        return (film, counts, st, prof) if stats else (film, counts, prof)
-
-    def render_adaptive_spectral(self, rd, bins, max_samples, rel_error, abs_error=0.0, step=0, stats=False):
-        """pt_render_adaptive_spectral: render_adaptive with a spectral film.  Returns (film, counts[, stats], spectral, profile): film, counts and stats are
-        render_adaptive's bit for bit; spectral [bins,H,W] holds per pixel the bins of render_spectral at that pixel's own sample count."""
-        if self.library._render_adaptive_spectral is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_adaptive_spectral entry" % (self.library.path, self.library.prefix))
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        counts = np.zeros((rd.height, rd.width), dtype=np.uint32)
-        st = np.zeros((rd.height, rd.width, 2), dtype=np.float64) if stats else None
-        spectral = np.zeros((max(int(bins), 0), rd.height, rd.width), dtype=np.float32)
-        ad = AdaptiveDesc(max_samples, step, rel_error, abs_error)
-        sd = SpectralDesc(bins)
-        prof = Profile()
-        self.library.check(self.library._render_adaptive_spectral(self.handle, C.byref(rd), C.byref(ad), C.byref(sd), _fp(film), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                                  st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, _fp(spectral), C.byref(prof)))
-        return (film, counts, st, spectral, prof) if stats else (film, counts, spectral, prof)
-
-    def render_adaptive_spectral_multi(self, rd, bins, max_samples, rel_error, abs_error=0.0, step=0, stats=False, device_mask=0):
-        """pt_render_adaptive_spectral_multi: render_adaptive_spectral on every device of the mask (0 = all) from one blocking call, its outputs bit for bit.
-        Returns (film, counts[, stats], spectral, profile) as render_adaptive_spectral does."""
-        if self.library._render_adaptive_spectral_multi is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_adaptive_spectral_multi entry" % (self.library.path, self.library.prefix))
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        counts = np.zeros((rd.height, rd.width), dtype=np.uint32)
-        st = np.zeros((rd.height, rd.width, 2), dtype=np.float64) if stats else None
-        spectral = np.zeros((max(int(bins), 0), rd.height, rd.width), dtype=np.float32)
-        ad = AdaptiveDesc(max_samples, step, rel_error, abs_error)
-        sd = SpectralDesc(bins)
-        prof = Profile()
-        self.library.check(self.library._render_adaptive_spectral_multi(self.handle, C.byref(rd), C.byref(ad), C.byref(sd), C.c_uint64(device_mask), _fp(film),
-                                                                        counts.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                                        st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, _fp(spectral), C.byref(prof)))
-        return (film, counts, st, spectral, prof) if stats else (film, counts, spectral, prof)
-
-    def render_adaptive_multi(self, rd, max_samples, rel_error, abs_error=0.0, step=0, stats=False, device_mask=0):
-        """pt_render_adaptive_multi: render_adaptive on every device of the mask (0 = all) from one blocking call, its outputs bit for bit.
-        Returns (film, counts[, stats], profile) as render_adaptive does."""
-        if self.library._render_adaptive_multi is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_adaptive_multi entry" % (self.library.path, self.library.prefix))
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        counts = np.zeros((rd.height, rd.width), dtype=np.uint32)
-        st = np.zeros((rd.height, rd.width, 2), dtype=np.float64) if stats else None
-        ad = AdaptiveDesc(max_samples, step, rel_error, abs_error)
-        prof = Profile()
-        self.library.check(self.library._render_adaptive_multi(self.handle, C.byref(rd), C.byref(ad), C.c_uint64(device_mask), _fp(film),
-                                                               counts.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                               st.ctypes.data_as(C.POINTER(C.c_double)) if stats else None, C.byref(prof)))
-        return (film, counts, st, prof) if stats else (film, counts, prof)
 
     def render_guides(self, rd, samples=4):
         """pt_render_guides: [H,W,4] f32 = the mean first-hit normal and distance over camera samples 0 .. samples-1 of the render `rd`."""
-        if self.library._render_guides is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_guides entry" % (self.library.path, self.library.prefix))
+        self.library.entry("render_guides")
         g = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        st = self.library._render_guides(self.handle, C.byref(rd), samples, _fp(g))
-        if st != PT_OK:
-            err = self.library._denoise_last_error
-            raise PtError(st, err().decode() if err else self.library.last_error())
+        self._call("render_guides", C.byref(rd), samples, _fp(g))
         return g
 
     def render_guides_albedo(self, rd, samples=4):
         """pt_render_guides_albedo: (guides, albedo), [H,W,4] f32 each — render_guides' output and, from the same probes, the mean first-hit albedo as XYZ
         factors (W = 0)."""
-        if self.library._render_guides_albedo is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_guides_albedo entry" % (self.library.path, self.library.prefix))
+        self.library.entry("render_guides_albedo")
         g = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
         a = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        st = self.library._render_guides_albedo(self.handle, C.byref(rd), samples, _fp(g), _fp(a))
-        if st != PT_OK:
-            raise PtError(st, self.library._albedo_error())
+        self._call("render_guides_albedo", C.byref(rd), samples, _fp(g), _fp(a))
         return g, a
 
     def render_guides_chain(self, rd, guide_samples=4, max_chain=8, alpha_max=0.0, albedo=True):
         """pt_render_guides_chain: (guides, albedo), [H,W,4] f32 each, taken at the end of every sample's specular chain — through passthrough boundaries and
         GGX materials with alpha <= alpha_max (0 = 0.01), at most max_chain vertices (0 = render_guides_albedo).  albedo=False: (guides, None)."""
-        if self.library._render_guides_chain is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_guides_chain entry" % (self.library.path, self.library.prefix))
+        self.library.entry("render_guides_chain")
         g = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
         a = np.zeros((rd.height, rd.width, 4), dtype=np.float32) if albedo else None
         cd = GuideChainDesc(max_chain, alpha_max)
-        st = self.library._render_guides_chain(self.handle, C.byref(rd), guide_samples, C.byref(cd), _fp(g), _fp(a) if albedo else None)
-        if st != PT_OK:
-            err = self.library._guides_chain_last_error
-            raise PtError(st, err().decode() if err else self.library.last_error())
+        self._call("render_guides_chain", C.byref(rd), guide_samples, C.byref(cd), _fp(g), _fp(a))
         return g, a
 
     def render_guides_bin_albedo(self, rd, bins, guide_samples=4, max_chain=0, alpha_max=0.0):
         """pt_render_guides_bin_albedo: (guides [H,W,4], albedo [H,W,4], bin_albedo [bins,H,W]) from one set of probes — render_guides_albedo's outputs, or with
         max_chain > 0 render_guides_chain's, and the mean reflectance of the same guide samples at the centre wavelength of each of the render's `bins` bins."""
-        if self.library._render_guides_bin_albedo is None:
-            raise PtError(PT_ERR_UNSUPPORTED, "%s has no %srender_guides_bin_albedo entry" % (self.library.path, self.library.prefix))
+        self.library.entry("render_guides_bin_albedo")
         g = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
         a = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
         ba = np.zeros((max(int(bins), 0), rd.height, rd.width), dtype=np.float32)
         cd = GuideChainDesc(max_chain, alpha_max)
-        st = self.library._render_guides_bin_albedo(self.handle, C.byref(rd), guide_samples, C.byref(cd) if max_chain > 0 else None, bins, _fp(g), _fp(a), _fp(ba))
-        if st != PT_OK:
-            err = self.library._denoise_spectral_albedo_last_error
-            raise PtError(st, err().decode() if err else self.library.last_error())
+        self._call("render_guides_bin_albedo", C.byref(rd), guide_samples, C.byref(cd) if max_chain > 0 else None, bins, _fp(g), _fp(a), _fp(ba))
         return g, a, ba
 
     def render_denoised(self, rd, max_samples=None, rel_error=0.0, abs_error=0.0, step=0, guide_samples=4, iterations=0, sigma_luminance=0.0, sigma_depth=0.0,
@@ -1213,30 +1055,19 @@ class Scene:
         mx = rd.spp if max_samples is None else max_samples
         if assemble and device_mask is None:
             raise PtError(PT_ERR_UNSUPPORTED, "render_denoised: assemble=True needs a device_mask (it assembles a node render; resident=True is the one-device form)")
-        if resident:
-            if device_mask is not None:
-                raise PtError(PT_ERR_UNSUPPORTED, "render_denoised: resident=True takes no device_mask (a node render leaves no film one device can filter)")
-            film, counts, st, prof = self.render_adaptive(rd, mx, rel_error, abs_error, step, stats=True)
-            self.resident_guides(rd, guide_samples, specular_chain or 0, albedo=albedo)
-            return film, self.denoise_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2), counts, prof
-        if assemble:
-            film, counts, st, prof = self.render_adaptive_multi(rd, mx, rel_error, abs_error, step, stats=True, device_mask=device_mask)
-            self._assemble_node_render()
-            self.resident_guides(rd, guide_samples, specular_chain or 0, albedo=albedo)
-            return film, self.denoise_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2), counts, prof
+        if resident and device_mask is not None:
+            raise PtError(PT_ERR_UNSUPPORTED, "render_denoised: resident=True takes no device_mask (a node render leaves no film one device can filter)")
         if device_mask is None:
             film, counts, st, prof = self.render_adaptive(rd, mx, rel_error, abs_error, step, stats=True)
-            device = 0
         else:
             film, counts, st, prof = self.render_adaptive_multi(rd, mx, rel_error, abs_error, step, stats=True, device_mask=device_mask)
-            device = (device_mask & -device_mask).bit_length() - 1 if device_mask else 0
-        if specular_chain is not None:
-            guides, alb = self.render_guides_chain(rd, guide_samples, specular_chain, albedo=albedo)
-        elif albedo:
-            guides, alb = self.render_guides_albedo(rd, guide_samples)
-        else:
-            guides, alb = self.render_guides(rd, guide_samples), None
-        den = self.library.denoise_film(film, counts, st, guides, iterations, sigma_luminance, sigma_depth, normal_power_log2, device, albedo=alb)
+        if resident or assemble:
+            if assemble:
+                self._assemble_node_render()
+            self.resident_guides(rd, guide_samples, specular_chain or 0, albedo=albedo)
+            return film, self.denoise_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2), counts, prof
+        guides, alb = self._host_guides(rd, guide_samples, specular_chain, albedo)
+        den = self.library.denoise_film(film, counts, st, guides, iterations, sigma_luminance, sigma_depth, normal_power_log2, _first_device(device_mask or 0), albedo=alb)
         return film, den, counts, prof
 
     def render_denoised_spectral(self, rd, bins, max_samples=None, rel_error=0.0, guide_samples=4, specular_chain=0, abs_error=0.0, step=0, iterations=0,
@@ -1254,56 +1085,36 @@ class Scene:
         if albedo:
             raise PtError(PT_ERR_UNSUPPORTED, "render_denoised_spectral takes no albedo: demodulating the bins needs a per-bin albedo (bin_albedo=True renders one)")
         mx = rd.spp if max_samples is None else max_samples
-        if resident:
-            if device_mask is not None:
-                raise PtError(PT_ERR_UNSUPPORTED, "render_denoised_spectral: resident=True takes no device_mask (a node render leaves no film one device can filter)")
-            film, counts, st, spectral, prof = self.render_adaptive_spectral(rd, bins, mx, rel_error, abs_error, step, stats=True)
-            self.resident_guides(rd, guide_samples, specular_chain, albedo=bin_albedo, bin_albedo=bin_albedo)
-            den, den_spectral = self.denoise_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2, spectral=True)
-            return film, den, spectral, den_spectral, counts, prof
-        if assemble:
-            film, counts, st, spectral, prof = self.render_adaptive_spectral_multi(rd, bins, mx, rel_error, abs_error, step, stats=True, device_mask=device_mask)
-            self._assemble_node_render()
-            self.resident_guides(rd, guide_samples, specular_chain, albedo=bin_albedo, bin_albedo=bin_albedo)
-            den, den_spectral = self.denoise_resident(iterations, sigma_luminance, sigma_depth, normal_power_log2, spectral=True)
-            return film, den, spectral, den_spectral, counts, prof
+        if resident and device_mask is not None:
+            raise PtError(PT_ERR_UNSUPPORTED, "render_denoised_spectral: resident=True takes no device_mask (a node render leaves no film one device can filter)")
         if device_mask is None:
             film, counts, st, spectral, prof = self.render_adaptive_spectral(rd, bins, mx, rel_error, abs_error, step, stats=True)
-            device = 0
         else:
             film, counts, st, spectral, prof = self.render_adaptive_spectral_multi(rd, bins, mx, rel_error, abs_error, step, stats=True, device_mask=device_mask)
-            device = (device_mask & -device_mask).bit_length() - 1 if device_mask else 0
-        if bin_albedo:
+        filter_args = (iterations, sigma_luminance, sigma_depth, normal_power_log2)
+        if resident or assemble:
+            if assemble:
+                self._assemble_node_render()
+            self.resident_guides(rd, guide_samples, specular_chain, albedo=bin_albedo, bin_albedo=bin_albedo)
+            den, den_spectral = self.denoise_resident(*filter_args, spectral=True)
+        elif bin_albedo:
             guides, alb, balb = self.render_guides_bin_albedo(rd, bins, guide_samples, specular_chain)
-            den, den_spectral = self.library.denoise_spectral_albedo(film, counts, st, guides, spectral, alb, balb, iterations, sigma_luminance, sigma_depth, normal_power_log2,
-                                                                     device)
-            return film, den, spectral, den_spectral, counts, prof
-        if specular_chain > 0:
-            guides, _ = self.render_guides_chain(rd, guide_samples, specular_chain, albedo=False)
+            den, den_spectral = self.library.denoise_spectral_albedo(film, counts, st, guides, spectral, alb, balb, *filter_args, _first_device(device_mask or 0))
         else:
-            guides = self.render_guides(rd, guide_samples)
-        den, den_spectral = self.library.denoise_spectral(film, counts, st, guides, spectral, iterations, sigma_luminance, sigma_depth, normal_power_log2, device)
+            guides, _ = self._host_guides(rd, guide_samples, specular_chain if specular_chain > 0 else None, False)
+            den, den_spectral = self.library.denoise_spectral(film, counts, st, guides, spectral, *filter_args, _first_device(device_mask or 0))
         return film, den, spectral, den_spectral, counts, prof
-
-    def render_multi(self, rd, device_mask=0):
-        """pt_render_multi: every device of the mask (0 = all) from one blocking call."""
-        film = np.zeros((rd.height, rd.width, 4), dtype=np.float32)
-        prof = Profile()
-        self.library.check(self.library._render_multi(self.handle, C.byref(rd), C.c_uint64(device_mask), _fp(film), C.byref(prof)))
-        return film, prof
 
     def render_device(self, rd, film_ptr, stream_ptr=None):
         prof = Profile()
-        self.library.check(self.library._render_device(self.handle, C.byref(rd), C.c_void_p(film_ptr),
-                                                       C.c_void_p(stream_ptr or 0), C.byref(prof)))
+        self._call("render_device", C.byref(rd), C.c_void_p(film_ptr), C.c_void_p(stream_ptr or 0), C.byref(prof))
         return prof
 
     def intersect(self, origins, directions):
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         hits = np.zeros(o.shape[0], dtype=HIT_DTYPE)
-        self.library.check(self.library._intersect(self.handle, o.shape[0], _fp(o), _fp(d),
-                                                   hits.ctypes.data_as(C.POINTER(Hit))))
+        self._call("intersect", o.shape[0], _fp(o), _fp(d), hits.ctypes.data_as(C.POINTER(Hit)))
         return hits
 
     def camera_samples(self, rd, pixel, sample):
@@ -1312,8 +1123,7 @@ class Scene:
         sample = np.ascontiguousarray(sample, dtype=np.uint32).ravel()
         n = pixel.shape[0]
         o = np.zeros((n, 3), np.float32); d = np.zeros((n, 3), np.float32); lam = np.zeros(n, np.float32)
-        u32p = C.POINTER(C.c_uint32)
-        self.library.check(self.library._camera_samples(self.handle, C.byref(rd), n, pixel.ctypes.data_as(u32p), sample.ctypes.data_as(u32p), _fp(o), _fp(d), _fp(lam)))
+        self._call("camera_samples", C.byref(rd), n, _u32p(pixel), _u32p(sample), _fp(o), _fp(d), _fp(lam))
         return o, d, lam
 
     def bsdf_sample(self, material, lam, wi, s2):
@@ -1322,7 +1132,7 @@ class Scene:
         s2 = np.ascontiguousarray(s2, dtype=np.float32).reshape(-1, 2)
         n = lam.shape[0]
         f = np.zeros(n, np.float32); wo = np.zeros((n, 3), np.float32); pdf = np.zeros(n, np.float32)
-        self.library.check(self.library._bsdf_sample(self.handle, material, n, _fp(lam), _fp(wi), _fp(s2), _fp(f), _fp(wo), _fp(pdf)))
+        self._call("bsdf_sample", material, n, _fp(lam), _fp(wi), _fp(s2), _fp(f), _fp(wo), _fp(pdf))
         return f, wo, pdf
 
     def light_sample(self, entry, origins, s2):
@@ -1333,7 +1143,7 @@ class Scene:
         s2 = np.ascontiguousarray(s2, dtype=np.float32).reshape(-1, 2)
         n = o.shape[0]
         d = np.zeros((n, 3), np.float32); pdf = np.zeros(n, np.float32)
-        self.library.check(self.library._light_sample(self.handle, entry, n, _fp(o), _fp(s2), _fp(d), _fp(pdf)))
+        self._call("light_sample", entry, n, _fp(o), _fp(s2), _fp(d), _fp(pdf))
         return d, pdf
 
     def bsdf_eval(self, material, lam, wi, wo):
@@ -1342,18 +1152,19 @@ class Scene:
         wo = np.ascontiguousarray(wo, dtype=np.float32).reshape(-1, 3)
         n = lam.shape[0]
         f = np.zeros(n, np.float32); pdf = np.zeros(n, np.float32)
-        self.library.check(self.library._bsdf_eval(self.handle, material, n, _fp(lam), _fp(wi), _fp(wo), _fp(f), _fp(pdf)))
+        self._call("bsdf_eval", material, n, _fp(lam), _fp(wi), _fp(wo), _fp(f), _fp(pdf))
         return f, pdf
 
     def emission(self, material, lam, wi):
         lam = np.ascontiguousarray(lam, dtype=np.float32)
         wi = np.ascontiguousarray(wi, dtype=np.float32).reshape(-1, 3)
         out = np.zeros(lam.shape[0], np.float32)
-        self.library.check(self.library._emission(self.handle, material, lam.shape[0], _fp(lam), _fp(wi), _fp(out)))
+        self._call("emission", material, lam.shape[0], _fp(lam), _fp(wi), _fp(out))
         return out
 
     def curve_eval(self, curve, lam):
         lam = np.ascontiguousarray(lam, dtype=np.float32)
         out = np.zeros(lam.shape[0], np.float32)
-        self.library.check(self.library._curve_eval(self.handle, curve, lam.shape[0], _fp(lam), _fp(out)))
+        self._call("curve_eval", curve, lam.shape[0], _fp(lam), _fp(out))
         return out
+

@@ -38,6 +38,38 @@ def test_oracle_exports_the_same_boundary(pkg, oracle):
         assert hasattr(oracle.lib, "ptref_" + name[3:]), name
 
 
+PUBLIC_HEADERS = ("pt_api.h", "pt_adaptive.h", "pt_debug.h", "pt_denoise.h", "pt_spectral.h", "pt_resident.h", "pt_light_groups.h", "pt_light_groups_spectral.h",
+                  "pt_light_groups_denoise.h", "pt_light_groups_multi.h")
+# the rows of the binding table that no public header declares: the emulation libraries' error channels and the engine's debug query
+UNDECLARED = {"denoise_last_error", "denoise_albedo_last_error", "guides_chain_last_error", "denoise_spectral_last_error", "denoise_spectral_albedo_last_error",
+              "spectral_project_last_error", "light_groups_last_error", "light_groups_spectral_last_error", "adaptive_light_groups_last_error",
+              "denoise_light_groups_last_error", "resident_last_error", "debug_scene_info"}
+
+
+def test_binding_table_matches_the_headers(pkg):
+    """Every pt_* function a public header declares has a row in api.ENTRIES under its header, with as many parameters, a ctypes pointer type exactly
+    where the header spells a `*`; the table holds nothing else but the rows listed above."""
+    table = pkg.api.ENTRIES
+    assert [h for h, _ in pkg.api.BINDINGS] and {h for h, _ in pkg.api.BINDINGS} == set(PUBLIC_HEADERS)
+    declared = set()
+    for header, rows in pkg.api.BINDINGS:
+        text = open(os.path.join(ROOT, "include", header)).read()
+        text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+        found = re.findall(r"\b(pt_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", text)
+        assert found, header
+        assert {name[3:] for name, _ in found} == {e.name for e in rows} - UNDECLARED, header
+        for name, params in found:
+            row = table[name[3:]]
+            params = [p.strip() for p in params.split(",") if p.strip() not in ("", "void")]
+            assert len(row.argtypes) == len(params), name
+            for ctype, param in zip(row.argtypes, params):
+                is_pointer = issubclass(ctype, C._Pointer) or ctype in (C.c_void_p, C.c_char_p)
+                assert is_pointer == ("*" in param), (name, param)
+            declared.add(name[3:])
+    assert set(table) - declared == UNDECLARED
+    assert len(table) == sum(len(rows) for _, rows in pkg.api.BINDINGS)   # (no name twice)
+
+
 def test_struct_layouts_match_the_header(pkg):
     """ctypes mirrors vs the C compiler's view of include/pt_api.h."""
     import subprocess

@@ -408,7 +408,7 @@ def test_gpu_life_of_the_remembered_node_render(engine, pkg):
     assert_assembled(sc, again, "again")
     assert_assembled(sc, arrays, "the same render, the same bits")
     with pytest.raises(a.PtError, match="PT_RESIDENT_ASSEMBLE_STAGED"):
-        sc._resident_check(sc.library._resident_assemble(sc.handle, 2))
+        sc.library.call("resident_assemble", sc.handle, 2)
     assert _hip_current_device() == before
     sc.close()
 

@@ -22,7 +22,13 @@
  *   chains     pt_render_guides_chain takes the guides and the albedo not at the first hit but at the first vertex that is not mirror-like: a
  *              sample walks on through passthrough boundaries and GGX materials with alpha <= alpha_max (refracting at a dielectric, reflecting
  *              at a metal and on total internal reflection, about the geometric normal, no random number drawn) for at most max_chain vertices;
- *              the distance is the length of the whole path.  csrc/pt_guides_chain_rules.h holds it operation by operation. */
+ *              the distance is the length of the whole path.  csrc/pt_guides_chain_rules.h holds it operation by operation.
+ *
+ *   mattes     pt_render_mattes runs the same probes as the guide passes (camera samples 0 .. S-1, traced as pt_intersect traces them) and keeps,
+ *              per pixel, which instance or material each sample saw: R ranked (key, coverage) pairs, anti-aliased with the jitter and the defocus
+ *              of the render.  pt_matte_extract turns selections of keys into coverage masks, pt_write_exr_cryptomatte writes the ranks in the
+ *              Cryptomatte layout.  Exact like the guides: the engine, the emulation and a numpy restatement agree bit for bit (the section at the
+ *              end of this header). */
 #ifndef PT_DENOISE_H
 #define PT_DENOISE_H
 #include "pt_api.h"
@@ -81,6 +87,50 @@ typedef struct pt_guide_chain_desc {
  * outputs bit for bit. */
 pt_status pt_render_guides_chain(pt_scene* scene, const pt_render_desc* desc, uint32_t guide_samples, const pt_guide_chain_desc* chain,
                                  float* guides_xyzw, float* albedo_xyzw);
+
+/* ---- ID mattes (csrc/pt_matte_rules.h operation by operation) ---- */
+
+enum { PT_MATTE_KEY_INSTANCE = 0, PT_MATTE_KEY_MATERIAL = 1 };
+#define PT_MATTE_SKY  0xFFFFFFFEu   /* the key of a sample that hit nothing */
+#define PT_MATTE_NONE 0xFFFFFFFFu   /* the key of an empty rank */
+#define PT_MATTE_RANKS_MAX 8
+
+typedef struct pt_matte_desc {
+    uint32_t samples;      /* S camera samples per pixel, 1 .. 65535 */
+    uint32_t ranks;        /* R (key, coverage) pairs kept per pixel, 1 .. PT_MATTE_RANKS_MAX */
+    uint32_t key;          /* PT_MATTE_KEY_INSTANCE: pt_hit::instance; PT_MATTE_KEY_MATERIAL: pt_hit::material */
+    uint32_t reserved[1];  /* must be 0 */
+} pt_matte_desc;
+
+/* The matte of `desc` (width, height, seed, wavelength bounds, camera_index, as pt_render_guides reads them).  keys, coverage: ranks planes of
+ * width*height, rank r of pixel p at r*width*height + p, ranked by coverage descending (ties: the smaller key); overflow: width*height u32, the
+ * samples whose key found no free rank.  Any output may be NULL: the keys and the coverage stay resident on the scene's device, until the next matte
+ * render replaces them; a film render does not touch them. */
+pt_status pt_render_mattes(pt_scene* scene, const pt_render_desc* desc, const pt_matte_desc* matte, uint32_t* keys, float* coverage, uint32_t* overflow);
+
+/* The size, ranks and samples of the resident matte; refused before a matte render has succeeded on the scene. */
+pt_status pt_mattes_resident(pt_scene* scene, uint32_t* width, uint32_t* height, uint32_t* ranks, uint32_t* samples);
+
+/* out: set_count planes of width*height f32, plane m the coverage of selection m = selected[offsets[m] .. offsets[m+1]-1] (any order, duplicates
+ * allowed, PT_MATTE_SKY allowed, may be empty): 0.0f plus, for r ascending, coverage[r] where keys[r] is selected.  set_count <= 16, offsets[0] = 0,
+ * offsets[set_count] <= 1024.  Host arrays in and out; runs on HIP device `device`. */
+pt_status pt_matte_extract(uint32_t width, uint32_t height, uint32_t ranks, const uint32_t* keys, const float* coverage, uint32_t set_count,
+                           const uint32_t* offsets, const uint32_t* selected, uint32_t device, float* out);
+
+/* pt_matte_extract of the resident matte: only the selections go up and set_count planes come back. */
+pt_status pt_matte_extract_resident(pt_scene* scene, uint32_t set_count, const uint32_t* offsets, const uint32_t* selected, float* out);
+
+/* The Cryptomatte id of a name: hash = MurmurHash3_x86_32 of its bytes (seed 0); id = the float whose bits are the hash with bit 23 flipped where
+ * the exponent field is 0 or 255.  Either output may be NULL.  Host only: no device is needed. */
+pt_status pt_cryptomatte_hash(const char* name, uint32_t* hash, float* id);
+
+/* A Cryptomatte file (uncompressed scanline OpenEXR, FLOAT channels): <layer>NN.R/.G/.B/.A for NN = 00 .. ceil(ranks/2)-1 = (id of rank 2NN, its
+ * coverage, id of rank 2NN+1, its coverage), an odd last rank padded with 0; R, G, B from linear_rgb (width*height*3) where given.  A key's id is
+ * that of its name: names[i] for name_keys[i], else "key<decimal>"; PT_MATTE_SKY and PT_MATTE_NONE are id 0.0f.  The header carries
+ * cryptomatte/<7 hex digits of the layer name's hash>/name, /hash, /conversion and /manifest (one entry per name passed).  Host only. */
+pt_status pt_write_exr_cryptomatte(const char* path, uint32_t width, uint32_t height, uint32_t ranks, const uint32_t* keys, const float* coverage,
+                                   const char* layer, uint32_t name_count, const uint32_t* name_keys, const char* const* names, const float* linear_rgb,
+                                   int32_t colorspace);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,8 @@ void pt_scene_file_free(pt_scene_file* scene);
 const pt_scene_desc* pt_scene_file_desc(const pt_scene_file* scene);
 /* name lookups, for tools and tests: packed MaterialId / indices, -1 when unknown */
 int64_t pt_scene_file_material(const pt_scene_file* scene, const char* name);
+/* ... and back: the library name of a packed MaterialId (as pt_hit::material reports it), NULL when no material has it; valid until pt_scene_file_free */
+const char* pt_scene_file_material_name(const pt_scene_file* scene, uint32_t material_id);
 int32_t pt_scene_file_curve(const pt_scene_file* scene, const char* name);
 int32_t pt_scene_file_texture(const pt_scene_file* scene, const char* name);
 int32_t pt_scene_file_camera(const pt_scene_file* scene, const char* camera_id);

@@ -172,6 +172,27 @@ class GuideChainDesc(C.Structure):
     _fields_ = [("max_chain", C.c_uint32), ("alpha_max", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class MatteDesc(C.Structure):
+    """pt_matte_desc (include/pt_denoise.h): the camera samples per pixel, the ranks kept per pixel, what a sample is keyed by (MATTE_KEY_*)."""
+    _fields_ = [("samples", C.c_uint32), ("ranks", C.c_uint32), ("key", C.c_uint32), ("reserved", C.c_uint32 * 1)]
+
+
+MATTE_KEY_INSTANCE, MATTE_KEY_MATERIAL = 0, 1
+MATTE_KEYS = {"instance": MATTE_KEY_INSTANCE, "material": MATTE_KEY_MATERIAL}
+MATTE_SKY, MATTE_NONE = 0xFFFFFFFE, 0xFFFFFFFF   # the key of a sample that hit nothing, the key of an empty rank
+MATTE_RANKS_MAX = 8
+
+
+def matte_selections(selections):
+    """A list of iterables of keys as pt_matte_extract takes it: (set_count, offsets [M+1] u32, selected u32)."""
+    sets = [np.asarray(list(s), dtype=np.uint32).reshape(-1) for s in selections]
+    offsets = np.zeros(len(sets) + 1, np.uint32)
+    if sets:
+        offsets[1:] = np.cumsum([s.size for s in sets])
+    selected = np.concatenate(sets) if sets else np.zeros(0, np.uint32)
+    return len(sets), offsets, np.ascontiguousarray(selected, dtype=np.uint32)
+
+
 class Profile(C.Structure):
     _fields_ = [("bounce_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("light_rays", C.c_uint64),
                 ("camera_rays", C.c_uint64), ("env_hits", C.c_uint64), ("seconds", C.c_double),
@@ -307,7 +328,13 @@ BINDINGS = (
         Entry("denoise_film_albedo", [_DD, _f32s, _u32s, _f64s, _f32s, _f32s, _f32s, _f32s], channel=_ALBEDO),
         Entry(_ALBEDO, [], _str),
         Entry("render_guides_chain", [_vp, _RD, _u32, _CHAIN, _f32s, _f32s], channel="guides_chain_last_error"),
-        Entry("guides_chain_last_error", [], _str))),
+        Entry("guides_chain_last_error", [], _str),
+        Entry("render_mattes", [_vp, _RD, _P(MatteDesc), _u32s, _f32s, _u32s], channel=_DENOISE),
+        Entry("mattes_resident", [_vp, _u32s, _u32s, _u32s, _u32s], channel=_DENOISE),
+        Entry("matte_extract", [_u32, _u32, _u32, _u32s, _f32s, _u32, _u32s, _u32s, _u32, _f32s], channel=_DENOISE),
+        Entry("matte_extract_resident", [_vp, _u32, _u32s, _u32s, _f32s], channel=_DENOISE),
+        Entry("cryptomatte_hash", [_str, _u32s, _f32s], channel=_DENOISE),
+        Entry("write_exr_cryptomatte", [_str, _u32, _u32, _u32, _u32s, _f32s, _str, _u32, _u32s, _P(_str), _f32s, _i32]))),
     # the reference keeps no spectrum; an older library without these entries still loads
     ("pt_spectral.h", (
         Entry("render_spectral", [_vp, _RD, _SD, _f32s, _f32s, _PROF]),
@@ -561,6 +588,46 @@ class Library:
             if linear_rgb.shape != (h, w, 3):
                 raise ValueError("linear_rgb [H, W, 3] of the spectral film's size")
         self.call("write_exr_spectral", path.encode(), w, h, bins, _fp(centres_nm), _fp(spectral), _fp(linear_rgb), colorspace)
+
+    def matte_extract(self, keys, coverage, selections, device=0):
+        """pt_matte_extract: the ranks keys [R,H,W] u32 and coverage [R,H,W] f32 of Scene.render_mattes and `selections`, a list of M iterables of keys (any
+        order, MATTE_SKY allowed, empty allowed): float32 [M,H,W], plane m the f32 fold, over the ranks ascending, of the coverage of the ranks whose key is
+        in selection m."""
+        self.entry("matte_extract")
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        coverage = np.ascontiguousarray(coverage, dtype=np.float32)
+        if keys.ndim != 3 or coverage.shape != keys.shape:
+            raise ValueError("keys [R,H,W] and coverage [R,H,W]")
+        ranks, h, w = keys.shape
+        M, offsets, selected = matte_selections(selections)
+        out = np.zeros((M, h, w), np.float32)
+        self.call("matte_extract", w, h, ranks, _u32p(keys), _fp(coverage), M, _u32p(offsets), _u32p(selected), device, _fp(out))
+        return out
+
+    def cryptomatte_hash(self, name):
+        """pt_cryptomatte_hash: (hash, id) of a name — MurmurHash3_x86_32 of its UTF-8 bytes, and the float32 whose bits are the hash made a normal number."""
+        h, i = np.zeros(1, np.uint32), np.zeros(1, np.float32)
+        self.call("cryptomatte_hash", name.encode(), _u32p(h), _fp(i))
+        return int(h[0]), i[0]
+
+    def write_exr_cryptomatte(self, path, keys, coverage, layer, names=None, linear_rgb=None, colorspace=COLORSPACE_SRGB):
+        """pt_write_exr_cryptomatte: keys, coverage [R,H,W] as the channels <layer>NN.R/.G/.B/.A of a Cryptomatte file, with R, G, B from linear_rgb [H,W,3] if
+        given.  `names`: a mapping key -> name, or a sequence of (key, name) — the manifest's entries, in this order; a key without one is named key<decimal>."""
+        self.entry("write_exr_cryptomatte")
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        coverage = np.ascontiguousarray(coverage, dtype=np.float32)
+        if keys.ndim != 3 or coverage.shape != keys.shape:
+            raise ValueError("keys [R,H,W] and coverage [R,H,W]")
+        ranks, h, w = keys.shape
+        if linear_rgb is not None:
+            linear_rgb = np.ascontiguousarray(linear_rgb, np.float32)
+            if linear_rgb.shape != (h, w, 3):
+                raise ValueError("linear_rgb [H, W, 3] of the matte's size")
+        pairs = list(names.items()) if hasattr(names, "items") else list(names or [])
+        name_keys = np.asarray([k for k, _ in pairs], dtype=np.uint32).reshape(-1)
+        carr = (C.c_char_p * max(len(pairs), 1))(*[n.encode() for _, n in pairs])
+        self.call("write_exr_cryptomatte", path.encode(), w, h, ranks, _u32p(keys), _fp(coverage), layer.encode(), len(pairs), _u32p(name_keys) if pairs else None,
+                  carr if pairs else None, _fp(linear_rgb), colorspace)
 
     def spectral_response_matrix(self, rd, bins, responses, curves=None, curve_data=None, filter=None, subsamples=1):
         """pt_spectral_response_matrix: float32 [K, bins], row k the response responses[k] — an index into `curves` (a sequence of api.Curve whose data_offset
@@ -1031,6 +1098,36 @@ class Scene:
         cd = GuideChainDesc(max_chain, alpha_max)
         self._call("render_guides_chain", C.byref(rd), guide_samples, C.byref(cd), _fp(g), _fp(a))
         return g, a
+
+    def render_mattes(self, rd, samples, key="instance", ranks=6, read=True):
+        """pt_render_mattes: (keys [R,H,W] u32, coverage [R,H,W] f32, overflow [H,W] u32) — per pixel the `ranks` keys that most of the camera samples
+        0 .. samples-1 of the render `rd` saw ("instance": pt_hit.instance, "material": the packed MaterialId; MATTE_SKY for a miss, MATTE_NONE for an empty
+        rank) with their share of the samples, and the samples that found no free rank.  read=False: nothing is copied back (None); the ranks stay on the
+        device for matte_extract_resident either way."""
+        self.library.entry("render_mattes")
+        md = MatteDesc(samples, ranks, MATTE_KEYS[key] if key in MATTE_KEYS else key)
+        planes = (max(int(ranks), 0), rd.height, rd.width)
+        keys = np.zeros(planes, np.uint32) if read else None
+        coverage = np.zeros(planes, np.float32) if read else None
+        overflow = np.zeros((rd.height, rd.width), np.uint32) if read else None
+        self._call("render_mattes", C.byref(rd), C.byref(md), _u32p(keys), _fp(coverage), _u32p(overflow))
+        return (keys, coverage, overflow) if read else None
+
+    def mattes_resident(self):
+        """pt_mattes_resident: (width, height, ranks, samples) of the matte the last successful render_mattes left on the device; refused before one."""
+        dims = [C.c_uint32() for _ in range(4)]
+        self._call("mattes_resident", *[C.byref(d) for d in dims])
+        return tuple(d.value for d in dims)
+
+    def matte_extract_resident(self, selections):
+        """pt_matte_extract_resident: Library.matte_extract of the resident matte — float32 [M,H,W], bit for bit what the host-array entry gives for the ranks
+        render_mattes returned; only the selections go up and M planes come back."""
+        self.library.entry("matte_extract_resident")
+        w, h, _, _ = self.mattes_resident()
+        M, offsets, selected = matte_selections(selections)
+        out = np.zeros((M, h, w), np.float32)
+        self._call("matte_extract_resident", M, _u32p(offsets), _u32p(selected), _fp(out))
+        return out
 
     def render_guides_bin_albedo(self, rd, bins, guide_samples=4, max_chain=0, alpha_max=0.0):
         """pt_render_guides_bin_albedo: (guides [H,W,4], albedo [H,W,4], bin_albedo [bins,H,W]) from one set of probes — render_guides_albedo's outputs, or with

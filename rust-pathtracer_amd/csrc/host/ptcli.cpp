@@ -8,7 +8,7 @@
 //         [--denoise-light-groups instance|material]
 //         [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK] [--denoise-resident]
 //         [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]
-//         [--light-group-devices MASK]
+//         [--light-group-devices MASK] [--mattes instance|material] [--matte-ranks R] [--matte-samples S]
 //         [--relamp-groups instance|material --relamp-bins B [--relamp G:CURVE[,G:CURVE...]] [--relamp-gains g0,g1,...] [--develop-subsamples N]]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
@@ -84,6 +84,11 @@
 // denoised relight is pt_light_groups_mix of the filtered films; with --denoise-assemble, which this flag allows beside --denoise-light-groups, the node render is
 // assembled on the scene's device (pt_resident_assemble: the film, and every device's packed group films unpacked beside it) and guides, filter and denoised relight
 // take the resident route of the one-device run.  It is refused together with --devices, whose refusals of the two group flags stay what they are.
+// --mattes instance|material also writes <filename>_crypto.exr: the ID mattes of the setting's frame (pt_render_mattes of include/pt_denoise.h; --matte-samples S
+// camera samples per pixel, by default the setting's min_samples; --matte-ranks R ranks, by default 6) in the Cryptomatte layout (pt_write_exr_cryptomatte) under
+// the layer CryptoObject, instances named instance<i>, or CryptoMaterial, materials named as the scene file's library names them, with the setting's linear RGB
+// beside the ranks.  The matte is rendered beside the film: every usual file stays byte for byte what it is.  Refused together with --devices,
+// --spectral-devices and --light-group-devices: there is no matte render over a device mask.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -143,6 +148,9 @@ struct Options {
     bool group_multi = false;     // --light-group-devices MASK: the group node calls (pt_render_light_groups_multi / pt_render_adaptive_light_groups_multi)
     uint64_t group_device_mask = 0;
     bool assemble = false;        // --denoise-assemble: the node render assembled on the scene's device, then as `resident` (pt_resident_assemble)
+    int mattes = 0;               // --mattes: <filename>_crypto.exr through pt_render_mattes; 1 = keyed by instance, 2 = by material; 0 = off
+    uint32_t matte_ranks = 6, matte_samples = 0;   // --matte-ranks R, --matte-samples S (0 = the setting's min_samples)
+    bool has_matte_ranks = false, has_matte_samples = false;
 };
 
 int usage(const char* msg) {
@@ -154,7 +162,7 @@ int usage(const char* msg) {
                     "             [--denoise-light-groups instance|material]\n"
                     "             [--develop cie|CX,CY,CZ] [--develop-filter CURVE] [--develop-subsamples N] [--spectral-devices MASK]\n"
                     "             [--denoise-resident] [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]\n"
-                    "             [--light-group-devices MASK]\n"
+                    "             [--light-group-devices MASK] [--mattes instance|material] [--matte-ranks R] [--matte-samples S]\n"
                     "             [--relamp-groups instance|material --relamp-bins B [--relamp G:CURVE[,G:CURVE...]] [--relamp-gains g0,g1,...]\n"
                     "              [--develop-subsamples N]]\n");
     return 2;
@@ -359,6 +367,21 @@ int main(int argc, char** argv) {
             }
             if (o.light_gains.size() > PT_LIGHT_GROUPS_MAX) return usage("--light-gains takes at most 8 gains");
         }
+        else if (a == "--mattes") {
+            if (!value(&v)) return usage("--mattes needs a value");
+            o.mattes = v == "instance" ? 1 : v == "material" ? 2 : 0;
+            if (!o.mattes) return usage("--mattes needs `instance` or `material`");
+        }
+        else if (a == "--matte-ranks" || a == "--matte-samples") {
+            if (!value(&v)) return usage((a + " needs a value").c_str());
+            char* end = nullptr;
+            const unsigned long x = strtoul(v.c_str(), &end, 10);
+            const bool ranks = a == "--matte-ranks";
+            if (end == v.c_str() || *end || x == 0 || x > (ranks ? (unsigned long)PT_MATTE_RANKS_MAX : 65535ul))
+                return usage(ranks ? "--matte-ranks needs a number of ranks in 1..8" : "--matte-samples needs a number of samples in 1..65535");
+            (ranks ? o.matte_ranks : o.matte_samples) = (uint32_t)x;
+            (ranks ? o.has_matte_ranks : o.has_matte_samples) = true;
+        }
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
     }
@@ -389,6 +412,11 @@ int main(int argc, char** argv) {
         static std::string refusal;
         if (with) { refusal = std::string("--light-groups cannot be combined with ") + with + ": a group render is one plain render of one wavelength per path on one device"; return usage(refusal.c_str()); }
     }
+    if (o.mattes) {
+        const char* with = o.multi ? "--devices" : o.spectral_multi ? "--spectral-devices" : o.group_multi ? "--light-group-devices" : nullptr;
+        static std::string refusal;
+        if (with) { refusal = std::string("--mattes cannot be combined with ") + with + ": a matte render runs on the scene's device and there is none over a device mask"; return usage(refusal.c_str()); }
+    } else if (o.has_matte_ranks || o.has_matte_samples) return usage(o.has_matte_ranks ? "--matte-ranks needs --mattes" : "--matte-samples needs --mattes");
     if (o.demodulate && !o.denoise) return usage("--demodulate-albedo needs --denoise");
     if (o.chain && !o.denoise) return usage("--guide-chain needs --denoise");
     if (o.has_alpha_max && !o.chain) return usage("--guide-alpha-max needs --guide-chain");
@@ -698,6 +726,36 @@ int main(int argc, char** argv) {
             }
             if (o.write_film && !write_npy(base + ".npy", film.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", base.c_str()); rc = 1; break; }
             printf("wrote %s.exr and %s.png\n", base.c_str(), base.c_str());
+            // --mattes: the ranked ids of this setting's frame (pt_render_mattes, beside the render: no file above changes) as a Cryptomatte file with the
+            // setting's linear RGB — instances named instance<i>, materials by their names in the scene file's library
+            if (o.mattes) {
+                const size_t np = (size_t)rd.width * rd.height;
+                const pt_matte_desc md = {o.matte_samples ? o.matte_samples : (rs.min_samples < 65535u ? rs.min_samples : 65535u), o.matte_ranks,
+                                          o.mattes == 2 ? (uint32_t)PT_MATTE_KEY_MATERIAL : (uint32_t)PT_MATTE_KEY_INSTANCE, {0u}};
+                std::vector<uint32_t> m_keys(md.ranks * np), m_overflow(np), named;
+                std::vector<float> m_coverage(md.ranks * np);
+                if (pt_render_mattes(scene, &rd, &md, m_keys.data(), m_coverage.data(), m_overflow.data()) != PT_OK) { fprintf(stderr, "pt_render_mattes: %s\n", pt_last_error()); rc = 1; break; }
+                std::vector<std::string> names;
+                for (uint32_t key : m_keys) {
+                    if (key == PT_MATTE_SKY || key == PT_MATTE_NONE) continue;
+                    bool seen = false;
+                    for (uint32_t k : named) seen = seen || k == key;
+                    if (seen) continue;
+                    const char* material = o.mattes == 2 ? pt_scene_file_material_name(scene_file, key) : nullptr;
+                    named.push_back(key);
+                    names.push_back(o.mattes == 1 ? "instance" + std::to_string(key) : material ? std::string(material) : "key" + std::to_string(key));
+                }
+                std::vector<const char*> name_ptrs;
+                for (const std::string& s : names) name_ptrs.push_back(s.c_str());
+                uint64_t dropped = 0;
+                for (uint32_t c : m_overflow) dropped += c;
+                const std::string crypto = base + "_crypto.exr";
+                if (pt_write_exr_cryptomatte(crypto.c_str(), rd.width, rd.height, md.ranks, m_keys.data(), m_coverage.data(), o.mattes == 2 ? "CryptoMaterial" : "CryptoObject",
+                                             (uint32_t)named.size(), named.data(), name_ptrs.data(), linear.data(), od.colorspace) != PT_OK) {
+                    fprintf(stderr, "failed to write %s: %s\n", crypto.c_str(), pt_last_error()); rc = 1; break;
+                }
+                printf("wrote %s (%u ranks of %u samples, %zu names, %llu samples beyond the ranks)\n", crypto.c_str(), md.ranks, md.samples, names.size(), (unsigned long long)dropped);
+            }
             // --light-groups, --denoise-light-groups: every group's film, and with --light-gains the resident mix, through this setting's film output (buffers of
             // their own).  `stem`: base, or base + "_denoised" for the films of the joint filter, which are then mixed where that left them.
             // (host_mix: the films were filtered over host arrays and are mixed from there, pt_light_groups_mix)

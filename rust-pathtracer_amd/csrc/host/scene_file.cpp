@@ -878,6 +878,13 @@ pt_status pt_scene_file_load(const char* scene_path, const pt_config* config, pt
 void pt_scene_file_free(pt_scene_file* s) { delete s; }
 const pt_scene_desc* pt_scene_file_desc(const pt_scene_file* s) { return s ? &s->desc : nullptr; }
 int64_t pt_scene_file_material(const pt_scene_file* s, const char* name) { auto it = s->material_ids.find(name); return it == s->material_ids.end() ? -1 : (int64_t)it->second; }
+const char* pt_scene_file_material_name(const pt_scene_file* s, uint32_t material_id) {
+    if (!s) return nullptr;
+    const char* found = nullptr;   // ("error" shares light 0's id with the first light material: the library's own name wins where there is one)
+    for (const auto& kv : s->material_ids)
+        if (kv.second == material_id && (!found || kv.first != "error")) found = kv.first.c_str();
+    return found;
+}
 int32_t pt_scene_file_curve(const pt_scene_file* s, const char* name) { auto it = s->curve_names.find(name); return it == s->curve_names.end() ? -1 : it->second; }
 int32_t pt_scene_file_texture(const pt_scene_file* s, const char* name) { auto it = s->texture_names.find(name); return it == s->texture_names.end() ? -1 : it->second; }
 int32_t pt_scene_file_camera(const pt_scene_file* s, const char* name) { auto it = s->camera_names.find(name); return it == s->camera_names.end() ? -1 : it->second; }

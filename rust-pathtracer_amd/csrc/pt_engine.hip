@@ -44,6 +44,8 @@
 #include "pt_denoise_resident_launch.h"
 #include "pt_error.h"
 #include "pt_guides_chain_launch.h"
+#include "pt_matte_launch.h"
+#include "pt_matte_rules.h"
 #include "pt_denoise_spectral_albedo_launch.h"
 #include "pt_plan.h"
 #include "pt_scene_host.h"
@@ -401,6 +403,13 @@ struct pt_scene {
     ResidentSet resident;          // include/pt_resident.h
     GrowBuf assemble_staging, assemble_px;   // pt_resident_assemble's: the packed shards copied from other devices, and the pixel lists uploaded for the unpack
     GrowBuf project_cache;         // pt_spectral_project_resident's device matrix (PT_SPECTRAL_MAX_RESPONSES x PT_SPECTRAL_MAX_BINS floats) and, behind it, its output planes
+    // The resident matte (include/pt_denoise.h, the ID mattes): the keys and the coverage the last successful pt_render_mattes left in matte_keys and matte_coverage,
+    // matte_ranks planes of matte_width x matte_height each.  Buffers of their own, outside the resident set's parts: no film render reads or writes them.  Cleared
+    // when a matte render starts and set when it has succeeded.  matte_extract_cache: pt_matte_extract_resident's selections (ptk::kMatteSelectionWords words) and,
+    // behind them, its output planes.
+    bool mattes_valid = false;
+    uint32_t matte_width = 0, matte_height = 0, matte_ranks = 0, matte_samples = 0;
+    GrowBuf matte_keys, matte_coverage, matte_extract_cache;
     std::vector<pt_scene*> replicas; // pt_render_multi: this scene on the other (virtual) devices, by device index x virtual index (nullptr = not made yet / this one)
 };
 
@@ -2204,6 +2213,80 @@ pt_status pt_render_guides_albedo(pt_scene* sc, const pt_render_desc* rdp, uint3
     if (st != PT_OK) return fail(st, err);
     if (!albedo) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     return render_guides_impl(sc, rdp, guide_samples, GuideOut{guides, albedo, nullptr, false});
+}
+
+// include/pt_denoise.h: the ID mattes.  Per sample index the launches of a guide pass — the camera rays of every pixel, their closest hits — and behind them
+// k_matte_fold (pt_matte.hip), which folds the hit records' instance or material into the pixels' slots; the launch of sample 0 initialises the table.  The finish
+// sorts and divides into the scene's resident planes, which the outputs asked for are copied from.
+pt_status pt_render_mattes(pt_scene* sc, const pt_render_desc* rdp, const pt_matte_desc* mdp, uint32_t* keys, float* coverage, uint32_t* overflow) {
+    std::string err;
+    const pt_status st = pth::check_matte_args(sc, rdp, mdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, &err);
+    if (st != PT_OK) return fail(st, err);
+    HIP_TRY(hipSetDevice(sc->device));
+    sc->mattes_valid = false;
+    const uint32_t n = rdp->width * rdp->height, ranks = mdp->ranks, samples = mdp->samples;
+    RenderParams rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.seed = rdp->seed; rp.width = rdp->width; rp.height = rdp->height;
+    rp.wavelength_lo = rdp->wavelength_lo; rp.wavelength_span = rdp->wavelength_hi - rdp->wavelength_lo;
+    rp.camera = pth::camera_params(sc->host.cameras[rdp->camera_index], (float)rdp->width / (float)rdp->height);
+    rp.chunk_pixels = 1;
+    const size_t plane_bytes = 4 * (size_t)ranks * n;
+    pt_status cached = sc->matte_keys.reserve(plane_bytes);
+    if (cached == PT_OK) cached = sc->matte_coverage.reserve(plane_bytes);
+    if (cached != PT_OK) return cached;
+    DevBuf dor, dd, dh, dtable, doverflow;
+    HIP_TRY(dor.alloc(12 * (size_t)n)); HIP_TRY(dd.alloc(12 * (size_t)n)); HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n));
+    HIP_TRY(dtable.alloc(ptk::matte_table_bytes(n, ranks))); HIP_TRY(doverflow.alloc(4 * (size_t)n));
+    const int grid = sc->num_cus * 4;
+    const uint32_t lds_bytes = sc->lds_mode == PT_LDS_ALL ? sc->blob_words * 4u : (sc->lds_mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
+    for (uint32_t k = 0; k < samples; ++k) {
+        launch_guide_rays(rp, n, k, dor.as<float>(), dd.as<float>());
+        launch_probe_intersect(LaunchCfg{grid, lds_bytes, (hipStream_t)0, sc->lds_mode}, SceneArgs{sc->d_blob, sc->blob_words, sc->d_tex}, n, dor.as<float>(), dd.as<float>(), dh.as<pt_hit>());
+        HIP_TRY(ptk::launch_matte_fold(nullptr, n, ranks, mdp->key, dh.as<pt_hit>(), dtable.p, k == 0));
+    }
+    HIP_TRY(ptk::launch_matte_finish(nullptr, n, ranks, samples, dtable.p, sc->matte_keys.as<uint32_t>(), sc->matte_coverage.as<float>(), doverflow.as<uint32_t>()));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    if (keys) HIP_TRY(hipMemcpy(keys, sc->matte_keys.p, plane_bytes, hipMemcpyDeviceToHost));
+    if (coverage) HIP_TRY(hipMemcpy(coverage, sc->matte_coverage.p, plane_bytes, hipMemcpyDeviceToHost));
+    if (overflow) HIP_TRY(hipMemcpy(overflow, doverflow.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    sc->mattes_valid = true;
+    sc->matte_width = rdp->width; sc->matte_height = rdp->height; sc->matte_ranks = ranks; sc->matte_samples = samples;
+    return PT_OK;
+}
+
+pt_status pt_mattes_resident(pt_scene* sc, uint32_t* width, uint32_t* height, uint32_t* ranks, uint32_t* samples) {
+    if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
+    if (!width || !height || !ranks || !samples) return fail(PT_ERR_INVALID_ARGUMENT, "width, height, ranks or samples is null");
+    if (!sc->mattes_valid) return fail(PT_ERR_INVALID_ARGUMENT, "the scene has no resident matte: pt_render_mattes must have succeeded on it");
+    *width = sc->matte_width; *height = sc->matte_height; *ranks = sc->matte_ranks; *samples = sc->matte_samples;
+    return PT_OK;
+}
+
+// pt_matte_extract's kernel over the resident planes, on the stream the render ran on (the null stream): the selections go up, set_count planes come back
+pt_status pt_matte_extract_resident(pt_scene* sc, uint32_t set_count, const uint32_t* offsets, const uint32_t* selected, float* out) {
+    if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
+    if (!sc->mattes_valid) return fail(PT_ERR_INVALID_ARGUMENT, "the scene has no resident matte: pt_render_mattes must have succeeded on it");
+    std::string err;
+    const pt_status st = pth::check_matte_selections(set_count, offsets, selected, out, &err);
+    if (st != PT_OK) return fail(st, err);
+    if (set_count == 0) return PT_OK;
+    std::vector<uint32_t> selection;
+    pth::matte_selection_words(set_count, offsets, selected, &selection);
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t n_pixels = (size_t)sc->matte_width * sc->matte_height;
+    const pt_status cached = sc->matte_extract_cache.reserve(4 * ((size_t)ptk::kMatteSelectionWords + (size_t)set_count * n_pixels));
+    if (cached != PT_OK) return cached;
+    uint32_t* d_selection = sc->matte_extract_cache.as<uint32_t>();
+    float* d_out = sc->matte_extract_cache.as<float>() + ptk::kMatteSelectionWords;
+    hipStream_t stream = nullptr;
+    HIP_TRY(hipMemcpyAsync(d_selection, selection.data(), 4 * selection.size(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ptk::launch_matte_extract(ptk::matte_extract_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, sc->matte_ranks, sc->matte_keys.as<uint32_t>(),
+                                      sc->matte_coverage.as<float>(), set_count, d_selection, d_selection + ptd::MATTE_SETS_MAX + 1u, d_out));
+    HIP_TRY(hipMemcpyAsync(out, d_out, 4 * (size_t)set_count * n_pixels, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PT_OK;
 }
 
 // include/pt_denoise.h: the guides at the end of every sample's specular chain.  Per sample index the camera rays go out as a list with the identity pixel

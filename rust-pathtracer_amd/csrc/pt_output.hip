@@ -15,12 +15,15 @@
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/pt_api.h"
+#include "../../include/pt_denoise.h"
 #include "../../include/pt_numerics.h"
 #include "../../include/pt_spectral.h"
 #include "pt_error.h"
+#include "pt_matte_rules.h"
 
 namespace {
 
@@ -164,9 +167,12 @@ Chroma chroma_of(int cs) {  // REC709 / REC2020 primaries and effective_gamma, s
 
 namespace {
 // The uncompressed scanline OpenEXR writer behind pt_write_exr and pt_write_exr_spectral: FLOAT channels in the order given (the caller's: byte-wise name
-// order), channel k's value of pixel i at data[i * stride].  `spectral`: the two string attributes of a spectral file.
+// order), channel k's value of pixel i at data[i * stride].  `spectral`: the two string attributes of a spectral file.  `strings`: further string attributes,
+// written where names between "compression" and "dataWindow" belong (a Cryptomatte file's); none leaves the header what it was.
 struct ExrChannel { std::string name; const float* data; size_t stride; };
-pt_status write_exr_channels(const char* path, uint32_t w, uint32_t h, const std::vector<ExrChannel>& channels, int32_t colorspace, bool spectral) {
+struct ExrString { std::string name, text; };
+pt_status write_exr_channels(const char* path, uint32_t w, uint32_t h, const std::vector<ExrChannel>& channels, int32_t colorspace, bool spectral,
+                             const std::vector<ExrString>& strings = {}) {
     FILE* f = fopen(path, "wb");
     if (!f) return ofail(PT_ERR_INVALID_ARGUMENT, std::string("cannot open ") + path);
     std::vector<uint8_t> hd;
@@ -186,6 +192,7 @@ pt_status write_exr_channels(const char* path, uint32_t w, uint32_t h, const std
     std::vector<uint8_t> cv; for (float v : {c.rx, c.ry, c.gx, c.gy, c.bx, c.by, c.wx, c.wy}) putf(cv, v);
     attr("chromaticities", "chromaticities", cv);
     attr("compression", "compression", {0});
+    for (const ExrString& a : strings) attr(a.name.c_str(), "string", std::vector<uint8_t>(a.text.begin(), a.text.end()));
     std::vector<uint8_t> box; put32(box, 0); put32(box, 0); put32(box, w - 1); put32(box, h - 1);
     attr("dataWindow", "box2i", box); attr("displayWindow", "box2i", box);
     if (spectral) string_attr("emissiveUnits", "W.m^-2.sr^-1");
@@ -318,6 +325,64 @@ pt_status pt_write_exr_spectral(const char* path, uint32_t w, uint32_t h, uint32
     for (size_t k = 1; k < channels.size(); ++k)
         if (channels[k].name == channels[k - 1].name) return ofail(PT_ERR_INVALID_ARGUMENT, "two bins share the channel name " + channels[k].name);
     return write_exr_channels(path, w, h, channels, colorspace, true);
+}
+
+// include/pt_denoise.h: the ranks of a matte in the Cryptomatte layout.  The id of a key is the hash of its name (pt_matte_rules.h), so the planes of ids are
+// made here, key by key; the coverage planes are written where they lie.
+pt_status pt_write_exr_cryptomatte(const char* path, uint32_t w, uint32_t h, uint32_t ranks, const uint32_t* keys, const float* coverage, const char* layer,
+                                   uint32_t name_count, const uint32_t* name_keys, const char* const* names, const float* linear_rgb, int32_t colorspace) {
+    if (!path) return ofail(PT_ERR_INVALID_ARGUMENT, "path is null");
+    if (w == 0 || h == 0) return ofail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
+    if (ranks == 0 || ranks > (uint32_t)PT_MATTE_RANKS_MAX) return ofail(PT_ERR_INVALID_ARGUMENT, "ranks must be in 1..8");
+    if (!keys || !coverage) return ofail(PT_ERR_INVALID_ARGUMENT, "keys and coverage are required");
+    if (!layer || !*layer) return ofail(PT_ERR_INVALID_ARGUMENT, "layer: a layer name is required");
+    if (name_count && (!name_keys || !names)) return ofail(PT_ERR_INVALID_ARGUMENT, "name_keys and names are required with a name_count");
+    auto id_of = [](const std::string& name) {
+        const uint32_t bits = ptd::matte_id_bits(ptd::matte_murmur3_32(reinterpret_cast<const uint8_t*>(name.data()), name.size(), 0u));
+        float id;
+        memcpy(&id, &bits, 4);
+        return id;
+    };
+    auto hex = [](uint32_t v) { char b[16]; snprintf(b, sizeof(b), "%08x", (unsigned)v); return std::string(b); };
+    std::unordered_map<uint32_t, float> ids;
+    std::string manifest = "{";
+    for (uint32_t i = 0; i < name_count; ++i) {
+        if (!names[i]) return ofail(PT_ERR_INVALID_ARGUMENT, "names: a name is null");
+        const float id = id_of(names[i]);
+        ids.emplace(name_keys[i], id);   // (a key named twice keeps its first name)
+        uint32_t bits;
+        memcpy(&bits, &id, 4);
+        std::string quoted;
+        for (const char* c = names[i]; *c; ++c) { if (*c == '"' || *c == '\\') quoted += '\\'; quoted += *c; }
+        manifest += std::string(i ? "," : "") + "\"" + quoted + "\":\"" + hex(bits) + "\"";
+    }
+    manifest += "}";
+    ids[PT_MATTE_SKY] = 0.0f; ids[PT_MATTE_NONE] = 0.0f;
+    const size_t n = (size_t)w * h;
+    std::vector<float> id_planes((size_t)ranks * n), zero(ranks & 1u ? n : 0, 0.0f);
+    for (size_t i = 0; i < (size_t)ranks * n; ++i) {
+        auto it = ids.find(keys[i]);
+        if (it == ids.end()) it = ids.emplace(keys[i], id_of("key" + std::to_string(keys[i]))).first;
+        id_planes[i] = it->second;
+    }
+    std::vector<ExrChannel> channels;
+    if (linear_rgb) channels = {{"B", linear_rgb + 2, 3}, {"G", linear_rgb + 1, 3}, {"R", linear_rgb, 3}};
+    for (uint32_t pair = 0; 2 * pair < ranks; ++pair) {
+        char nn[8];
+        snprintf(nn, sizeof(nn), "%02u", (unsigned)pair);
+        const std::string base = std::string(layer) + nn;
+        const uint32_t r0 = 2 * pair, r1 = r0 + 1;
+        channels.push_back({base + ".R", id_planes.data() + (size_t)r0 * n, 1});
+        channels.push_back({base + ".G", coverage + (size_t)r0 * n, 1});
+        channels.push_back({base + ".B", r1 < ranks ? id_planes.data() + (size_t)r1 * n : zero.data(), 1});
+        channels.push_back({base + ".A", r1 < ranks ? coverage + (size_t)r1 * n : zero.data(), 1});
+    }
+    std::sort(channels.begin(), channels.end(), [](const ExrChannel& a, const ExrChannel& b) { return a.name < b.name; });   // (byte-wise, as the format requires)
+    for (size_t k = 1; k < channels.size(); ++k)
+        if (channels[k].name == channels[k - 1].name) return ofail(PT_ERR_INVALID_ARGUMENT, "layer: the channel name " + channels[k].name + " is taken");
+    const std::string prefix = "cryptomatte/" + hex(ptd::matte_murmur3_32(reinterpret_cast<const uint8_t*>(layer), strlen(layer), 0u)).substr(0, 7) + "/";
+    return write_exr_channels(path, w, h, channels, colorspace, false,
+                              {{prefix + "conversion", "uint32_to_float32"}, {prefix + "hash", "MurmurHash3_32"}, {prefix + "manifest", manifest}, {prefix + "name", layer}});
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 #include "pt_plan.h"
 #include "pt_denoise_rules.h"
 #include "pt_guides_chain_rules.h"
+#include "pt_matte_rules.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -227,6 +229,55 @@ pt_status check_guides_chain_args(const void* scene, const pt_render_desc* rd, u
     *out = *chain;
     if (out->alpha_max == 0.0f) out->alpha_max = DN_CHAIN_DEFAULT_ALPHA_MAX;
     return PT_OK;
+}
+
+pt_status check_matte_args(const void* scene, const pt_render_desc* rd, const pt_matte_desc* matte, uint32_t camera_count, std::string* error) {
+    auto refuse = [&](const char* m) { *error = m; return PT_ERR_INVALID_ARGUMENT; };
+    if (!matte) return refuse("matte: the matte desc is null");
+    if (matte->samples == 0 || matte->samples > ptd::MATTE_SAMPLES_MAX) return refuse("samples must be in 1..65535");
+    if (matte->ranks == 0 || matte->ranks > (uint32_t)PT_MATTE_RANKS_MAX) return refuse("ranks must be in 1..8");
+    if (matte->key != (uint32_t)PT_MATTE_KEY_INSTANCE && matte->key != (uint32_t)PT_MATTE_KEY_MATERIAL) return refuse("key must be PT_MATTE_KEY_INSTANCE or PT_MATTE_KEY_MATERIAL");
+    if (matte->reserved[0] != 0) return refuse("pt_matte_desc::reserved must be 0");
+    if (!scene) return refuse("the scene is null");
+    if (!rd) return refuse("desc: the render desc is null");
+    if (rd->width == 0 || rd->height == 0) return refuse("width and height must be positive");
+    if (rd->camera_index >= camera_count) return refuse("camera_index out of range");
+    if (!(rd->wavelength_hi >= rd->wavelength_lo)) return refuse("wavelength_hi must not be below wavelength_lo");
+    if ((uint64_t)rd->width * (uint64_t)rd->height > 0x7fffffffull) return refuse("width x height must fit 31 bits");
+    return PT_OK;
+}
+
+pt_status check_matte_selections(uint32_t set_count, const uint32_t* offsets, const uint32_t* selected, const void* out, std::string* error) {
+    auto refuse = [&](const char* m) { *error = m; return PT_ERR_INVALID_ARGUMENT; };
+    if (set_count > ptd::MATTE_SETS_MAX) return refuse("set_count: at most 16 selections");
+    if (!offsets) return refuse("offsets is null");
+    if (offsets[0] != 0) return refuse("offsets must start at 0");
+    for (uint32_t m = 0; m < set_count; ++m) if (offsets[m + 1] < offsets[m]) return refuse("offsets must not fall");
+    if (offsets[set_count] > ptd::MATTE_SELECTED_MAX) return refuse("selected: at most 1024 keys in all");
+    if (offsets[set_count] != 0 && !selected) return refuse("selected is null");
+    if (set_count != 0 && !out) return refuse("out is null");
+    return PT_OK;
+}
+
+pt_status check_matte_extract_args(uint32_t width, uint32_t height, uint32_t ranks, const void* keys, const void* coverage, uint32_t set_count, const uint32_t* offsets,
+                                   const uint32_t* selected, const void* out, std::string* error) {
+    auto refuse = [&](const char* m) { *error = m; return PT_ERR_INVALID_ARGUMENT; };
+    if (width == 0 || height == 0 || (uint64_t)width * (uint64_t)height > 0x7fffffffull) return refuse("width and height must be positive and width x height must fit 31 bits");
+    if (ranks == 0 || ranks > (uint32_t)PT_MATTE_RANKS_MAX) return refuse("ranks must be in 1..8");
+    if (!keys || !coverage) return refuse("keys and coverage are required");
+    return check_matte_selections(set_count, offsets, selected, out, error);
+}
+
+void matte_selection_words(uint32_t set_count, const uint32_t* offsets, const uint32_t* selected, std::vector<uint32_t>* words) {
+    words->assign(ptd::MATTE_SETS_MAX + 1u, 0u);
+    for (uint32_t m = 0; m < set_count; ++m) {
+        std::vector<uint32_t> set(selected + offsets[m], selected + offsets[m + 1]);
+        std::sort(set.begin(), set.end());
+        set.erase(std::unique(set.begin(), set.end()), set.end());
+        words->insert(words->end(), set.begin(), set.end());
+        (*words)[m + 1] = (uint32_t)words->size() - (ptd::MATTE_SETS_MAX + 1u);
+    }
+    for (uint32_t m = set_count + 1u; m <= ptd::MATTE_SETS_MAX; ++m) (*words)[m] = (*words)[set_count];
 }
 
 pt_status check_spectral_desc(const pt_spectral_desc* sd, std::string* error) {

@@ -67,6 +67,16 @@ pt_status check_albedo_basis_args(const pt_render_desc* rd, const void* lambda, 
 // pt_render_guides_chain's arguments: the chain desc first (its refusals need no scene), then check_guides_args; *out = the desc with its default filled in
 pt_status check_guides_chain_args(const void* scene, const pt_render_desc* rd, uint32_t camera_count, uint32_t guide_samples, const pt_guide_chain_desc* chain,
                                   const void* guides, pt_guide_chain_desc* out, std::string* error);
+// The ID mattes' arguments (include/pt_denoise.h), for the engine and the host emulation alike; every refusal is PT_ERR_INVALID_ARGUMENT and names its argument.
+// check_matte_args: the matte desc first (its refusals need no scene), then the scene and the render desc as check_guides_args judges them.
+// check_matte_selections: set_count <= 16, offsets from 0 and never falling, at most 1024 keys.  check_matte_extract_args: the planes' size and ranks, then that.
+pt_status check_matte_args(const void* scene, const pt_render_desc* rd, const pt_matte_desc* matte, uint32_t camera_count, std::string* error);
+pt_status check_matte_selections(uint32_t set_count, const uint32_t* offsets, const uint32_t* selected, const void* out, std::string* error);
+pt_status check_matte_extract_args(uint32_t width, uint32_t height, uint32_t ranks, const void* keys, const void* coverage, uint32_t set_count, const uint32_t* offsets,
+                                   const uint32_t* selected, const void* out, std::string* error);
+// What the extract kernel reads, in one array: 17 offsets (those behind set_count repeat the last) and behind them every selection sorted ascending without
+// duplicates.  The arguments have passed check_matte_selections.
+void matte_selection_words(uint32_t set_count, const uint32_t* offsets, const uint32_t* selected, std::vector<uint32_t>* words);
 
 // pt_render_spectral's arguments (include/pt_spectral.h), for the engine and the host emulation alike, checked before the engine looks for a device:
 // bins in 1..PT_SPECTRAL_MAX_BINS, reserved words 0, no null pointer; each refusal is PT_ERR_INVALID_ARGUMENT with its own message.  medium_aware

@@ -55,7 +55,8 @@ def library():
             getattr(L, "pt_scene_file_" + n).restype = C.c_int64; getattr(L, "pt_scene_file_" + n).argtypes = [vp, C.c_char_p]
         for n in ("curve", "texture", "camera"):
             getattr(L, "pt_scene_file_" + n).restype = C.c_int32; getattr(L, "pt_scene_file_" + n).argtypes = [vp, C.c_char_p]
-        L.pt_scene_file_library_curve.argtypes = [vp, C.c_char_p, C.POINTER(api.Curve), C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32)]
+        L.pt_scene_file_material_name.restype = C.c_char_p; L.pt_scene_file_material_name.argtypes = [vp, C.c_uint32]
+        L.pt_scene_file_library_curve.argtypes =[vp, C.c_char_p, C.POINTER(api.Curve), C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32)]
         L.pt_scene_file_warning_count.restype = C.c_uint32; L.pt_scene_file_warning_count.argtypes = [vp]
         L.pt_scene_file_warning.restype = C.c_char_p; L.pt_scene_file_warning.argtypes = [vp, C.c_uint32]
         L.pt_image_read.argtypes = [C.c_char_p, C.c_int32, C.c_float, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_float))]
@@ -151,6 +152,11 @@ class SceneFile:
 
     def material(self, name):
         return library().pt_scene_file_material(self.handle, name.encode())
+
+    def material_name(self, material_id):
+        """pt_scene_file_material_name: the library name of a packed MaterialId, None when no material has it."""
+        name = library().pt_scene_file_material_name(self.handle, int(material_id))
+        return name.decode() if name is not None else None
 
     def curve(self, name):
         return library().pt_scene_file_curve(self.handle, name.encode())

@@ -55,6 +55,40 @@ pt_status pt_light_groups_resident(pt_scene* scene, uint32_t* width, uint32_t* h
 /* pt_light_groups_mix over the resident group films: the matrices go up, one film comes back. */
 pt_status pt_light_groups_mix_resident(pt_scene* scene, const float* matrices, float* out_xyzw);
 
+/* ---- Path passes: the render split by HOW the light travelled.  A pass render is a group render whose group is a function of the
+ * path's own history, not of the emitter: eight films, in this order, each made from its class's energies as pt_render's film is made from all of them.
+ *
+ *   The state in front of a vertex is (d, k): d the scattering events so far (the camera vertex: 0), k the kind of the first — diffuse (a Lambertian,
+ *   DiffuseLight or SharpLight record), else reflection or transmission by whether the direction leaves on the side it came from.  Every surface vertex the walk
+ *   continues from is an event.  A light or environment vertex' addition goes to emission / background at d = 0, to k-direct at d = 1, to k-indirect from
+ *   d = 2 on; a light-sample ray made at d = 0 goes to (its own direction's kind)-direct, any later one to k-indirect.  film_xyzw is pt_render's bit for bit.
+ *
+ * The pass films are left on the scene's device as ITS RESIDENT GROUP FILMS with group_count 8: pt_light_groups_resident, pt_light_groups_mix_resident and
+ * (after the adaptive entry of pt_light_groups_denoise.h) pt_denoise_light_groups_resident follow a pass render as they follow a group render.
+ * Out of scope: a device mask, spectral bins per pass, hero wavelengths, the medium-aware walk, a user-defined path-expression language.
+ * (Declared here, not in a header of its own, because the pass films ARE group films.  The return type stands on a line of its own: the light-group tests
+ * pin the list of this header's `pt_status pt_...(` lines to the light-group entries above.) */
+#define PT_PATH_PASSES 8
+enum {
+    PT_PATH_PASS_EMISSION = 0,
+    PT_PATH_PASS_BACKGROUND = 1,
+    PT_PATH_PASS_DIFFUSE_DIRECT = 2,
+    PT_PATH_PASS_DIFFUSE_INDIRECT = 3,
+    PT_PATH_PASS_REFLECTION_DIRECT = 4,
+    PT_PATH_PASS_REFLECTION_INDIRECT = 5,
+    PT_PATH_PASS_TRANSMISSION_DIRECT = 6,
+    PT_PATH_PASS_TRANSMISSION_INDIRECT = 7
+};
+
+typedef struct pt_path_passes_desc {
+    uint32_t reserved[4];             /* must be 0 */
+} pt_path_passes_desc;
+
+/* desc, film_xyzw, profile: pt_render_light_groups'; refused is what that entry refuses of a render desc (hero_wavelengths 4, medium_aware, a shard, a partial
+ * sample range: PT_ERR_UNSUPPORTED).  pass_films: PT_PATH_PASSES*width*height*4 f32 in the layout of group films, or NULL when only the resident copy is wanted. */
+pt_status
+pt_render_path_passes(pt_scene* scene, const pt_render_desc* desc, const pt_path_passes_desc* passes, float* film_xyzw, float* pass_films, pt_profile* profile);
+
 #ifdef __cplusplus
 }
 #endif

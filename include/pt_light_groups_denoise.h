@@ -53,6 +53,14 @@ pt_status pt_light_groups_denoised_resident(pt_scene* scene, uint32_t* width, ui
 /* pt_light_groups_mix over the resident denoised group films: the matrices go up (at most 72 floats), one film comes back. */
 pt_status pt_light_groups_mix_resident_denoised(pt_scene* scene, const float* matrices, float* out_xyzw);
 
+/* pt_render_path_passes (pt_light_groups.h) under pt_render_adaptive's stop rule: film, counts, statistics and rounds are pt_render_adaptive's bit for bit, and
+ * pass c's film at pixel p is pt_render_path_passes' at spp = sample_counts[p].  On success the scene holds the resident FILM and the eight pass films as its
+ * group films, paired as after pt_render_adaptive_light_groups: pt_denoise_light_groups_resident follows.  (The return type on a line of its own, as
+ * there and for the same reason.) */
+pt_status
+pt_render_adaptive_path_passes(pt_scene* scene, const pt_render_desc* desc, const pt_adaptive_desc* adaptive, const pt_path_passes_desc* passes, float* film_xyzw,
+                               uint32_t* sample_counts, double* stats, float* pass_films, pt_profile* profile);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,17 @@ class LightGroupsDesc(C.Structure):
 LIGHT_GROUPS_MAX = 8
 
 
+class PathPassesDesc(C.Structure):
+    """pt_path_passes_desc (include/pt_light_groups.h): reserved words, all 0."""
+    _fields_ = [("reserved", C.c_uint32 * 4)]
+
+
+# PT_PATH_PASSES and the PT_PATH_PASS_* indices (include/pt_light_groups.h): the order of the pass films, and their names in a file name
+PATH_PASSES = 8
+PATH_PASS_NAMES = ("emission", "background", "diffuse_direct", "diffuse_indirect", "reflection_direct", "reflection_indirect", "transmission_direct",
+                   "transmission_indirect")
+
+
 def light_group_gains(gains):
     """G scalars as the G scaled identities of a mix, float32 [G,3,3]: group g's film times gains[g]."""
     gains = np.asarray(gains, np.float32).reshape(-1)
@@ -283,8 +294,8 @@ Entry = collections.namedtuple("Entry", "name argtypes restype required channel"
 _P = C.POINTER
 _vp, _str, _sz, _u32, _i32, _u64 = C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_int32, C.c_uint64
 _f32s, _u32s, _f64s, _u8s, _i32s = _P(C.c_float), _P(C.c_uint32), _P(C.c_double), _P(C.c_uint8), _P(C.c_int32)
-_RD, _AD, _SD, _GD, _DD, _RDD, _CHAIN, _PROF = (_P(t) for t in (RenderDesc, AdaptiveDesc, SpectralDesc, LightGroupsDesc, DenoiseDesc, ResidentDenoiseDesc,
-                                                                GuideChainDesc, Profile))
+_RD, _AD, _SD, _GD, _DD, _RDD, _CHAIN, _PROF, _PD = (_P(t) for t in (RenderDesc, AdaptiveDesc, SpectralDesc, LightGroupsDesc, DenoiseDesc, ResidentDenoiseDesc,
+                                                                     GuideChainDesc, Profile, PathPassesDesc))
 _DENOISE, _ALBEDO, _BIN_ALBEDO, _PROJECT = "denoise_last_error", "denoise_albedo_last_error", "denoise_spectral_albedo_last_error", "spectral_project_last_error"
 _GROUPS, _GROUP_BINS, _RESIDENT = "light_groups_last_error", "light_groups_spectral_last_error", "resident_last_error"
 
@@ -359,6 +370,7 @@ BINDINGS = (
         Entry("light_groups_mix", [_u32, _u32, _u32, _f32s, _f32s, _f32s], channel=_GROUPS),
         Entry("light_groups_resident", [_vp, _u32s, _u32s, _u32s], channel=_GROUPS),
         Entry("light_groups_mix_resident", [_vp, _f32s, _f32s], channel=_GROUPS),
+        Entry("render_path_passes", [_vp, _RD, _PD, _f32s, _f32s, _PROF], channel=_GROUPS),
         Entry(_GROUPS, [], _str))),
     ("pt_light_groups_spectral.h", (
         Entry("render_light_groups_spectral", [_vp, _RD, _GD, _SD, _f32s, _f32s, _f32s, _f32s, _PROF], channel=_GROUP_BINS),
@@ -373,6 +385,7 @@ BINDINGS = (
         Entry("denoise_light_groups_resident", [_vp, _RDD, _f32s, _f32s, _f32s]),
         Entry("light_groups_denoised_resident", [_vp, _u32s, _u32s, _u32s]),
         Entry("light_groups_mix_resident_denoised", [_vp, _f32s, _f32s], channel=_GROUPS),
+        Entry("render_adaptive_path_passes", [_vp, _RD, _AD, _PD, _f32s, _u32s, _f64s, _f32s, _PROF]),
         Entry("adaptive_light_groups_last_error", [], _str),
         Entry("denoise_light_groups_last_error", [], _str))),
     ("pt_light_groups_multi.h", (
@@ -770,11 +783,12 @@ class Scene:
         """Library.call of an entry that takes the scene first."""
         self.library.call(name, self.handle, *args)
 
-    def _render_call(self, name, rd, adaptive=None, groups=None, bins=None, device_mask=None, stats=False, read_groups=True, read_bins=True):
+    def _render_call(self, name, rd, adaptive=None, groups=None, bins=None, device_mask=None, stats=False, read_groups=True, read_bins=True, passes=False):
         """The one render call behind the render* methods: the entry `name` with the arguments it takes, in the order all of them share — rd,
         adaptive desc, groups desc, spectral desc, device mask, film, counts, stats, group films, spectral, group spectral, profile — and the outputs in
         that order, the stats only with `stats`.  adaptive: (max_samples, step, rel_error, abs_error); groups: (instance_group, environment_group, G or None:
-        the largest id, the environment's included, plus one); what read_groups / read_bins do not ask for is passed, and returned, as None."""
+        the largest id, the environment's included, plus one); passes: a path passes desc where the groups desc would stand, and the PATH_PASSES pass films where the
+        group films would; what read_groups / read_bins do not ask for is passed, and returned, as None."""
         self.library.entry(name)
         h, w = rd.height, rd.width
         descs, pointers, outs, prof = [rd], [], [], Profile()
@@ -796,6 +810,9 @@ class Scene:
             G = int(G) if G is not None else int(max([int(environment_group)] + [int(i) for i in ids])) + 1
             descs.append(LightGroupsDesc(G, ids.size, _u8p(ids), int(environment_group)))
             out(max(G, 0), h, w, 4, read=read_groups)
+        if passes:
+            descs.append(PathPassesDesc())
+            out(PATH_PASSES, h, w, 4, read=read_groups)
         if bins is not None:
             descs.append(SpectralDesc(bins))
             out(max(int(bins), 0), h, w, read=read_bins)
@@ -875,6 +892,18 @@ class Scene:
         with stats=True) gathers film and group films on the scene's device."""
         return self._render_call("render_adaptive_light_groups_multi", rd, (max_samples, step, rel_error, abs_error), (instance_group, environment_group, groups),
                                  device_mask=device_mask, stats=stats, read_groups=read_groups)
+
+    def render_path_passes(self, rd, read_passes=True):
+        """pt_render_path_passes: (film, pass_films, profile) — film [H,W,4] is render(rd)'s bit for bit; pass_films [8,H,W,4] holds, in the order of
+        PATH_PASS_NAMES, the film of the energy that travelled each way.  The pass films stay on the device as the scene's resident group films (8 groups):
+        light_groups_resident and light_groups_mix_resident follow.  read_passes False leaves them there alone (pass_films is None)."""
+        return self._render_call("render_path_passes", rd, passes=True, read_groups=read_passes)
+
+    def render_adaptive_path_passes(self, rd, max_samples, rel_error, abs_error=0.0, step=0, stats=False, read_passes=True):
+        """pt_render_adaptive_path_passes: (film, counts[, stats], pass_films, profile) — film, counts and stats are render_adaptive's bit for bit; pass_films
+        [8,H,W,4] holds per pixel the pass films of render_path_passes at that pixel's own sample count.  The scene then holds the resident film and the pass
+        films as its group films, paired for denoise_light_groups_resident.  read_passes False: pass_films is None."""
+        return self._render_call("render_adaptive_path_passes", rd, (max_samples, step, rel_error, abs_error), stats=stats, passes=True, read_groups=read_passes)
 
     def _resident_dims(self, name, count=3):
         """A pt_*_resident query: (width, height, planes[, bins]) of what a render left on the device(s), None when it left none."""

@@ -10,6 +10,7 @@
 //         [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]
 //         [--light-group-devices MASK] [--mattes instance|material] [--matte-ranks R] [--matte-samples S]
 //         [--relamp-groups instance|material --relamp-bins B [--relamp G:CURVE[,G:CURVE...]] [--relamp-gains g0,g1,...] [--develop-subsamples N]]
+//         [--path-passes] [--denoise-path-passes]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -89,6 +90,15 @@
 // the layer CryptoObject, instances named instance<i>, or CryptoMaterial, materials named as the scene file's library names them, with the setting's linear RGB
 // beside the ranks.  The matte is rendered beside the film: every usual file stays byte for byte what it is.  Refused together with --devices,
 // --spectral-devices and --light-group-devices: there is no matte render over a device mask.
+// --path-passes renders every setting through pt_render_path_passes (include/pt_light_groups.h, "Path passes") and also writes <filename>_pass_<class>.exr for the
+// eight classes — emission, background, diffuse_direct, diffuse_indirect, reflection_direct, reflection_indirect, transmission_direct, transmission_indirect — each
+// through the setting's own film output.  The usual files stay byte for byte what they are: the film is the total.  With --denoise --denoise-path-passes every
+// setting goes through pt_render_adaptive_path_passes (include/pt_light_groups_denoise.h) and the film and its pass films are filtered together where the render
+// left them (pt_resident_guides, pt_denoise_light_groups_resident: the pass films are the scene's resident group films), honouring --adaptive,
+// --demodulate-albedo, --guide-chain and --guide-samples; it also writes <filename>_denoised_pass_<class>.exr, and the usual and the _denoised files are byte for
+// byte those of --denoise with the same other flags.  Refused with what --light-groups is refused with (--adaptive and --denoise unless --denoise-path-passes is
+// given, --spectral-bins, --denoise-spectral-bins, --devices, --spectral-devices, --hero-wavelengths) and with --light-groups, --denoise-light-groups,
+// --relamp-groups and --light-group-devices, which use the same resident group films.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -151,7 +161,12 @@ struct Options {
     int mattes = 0;               // --mattes: <filename>_crypto.exr through pt_render_mattes; 1 = keyed by instance, 2 = by material; 0 = off
     uint32_t matte_ranks = 6, matte_samples = 0;   // --matte-ranks R, --matte-samples S (0 = the setting's min_samples)
     bool has_matte_ranks = false, has_matte_samples = false;
+    bool path_passes = false;     // --path-passes: <filename>_pass_<class>.exr through pt_render_path_passes
+    bool denoise_passes = false;  // --denoise-path-passes: the adaptive pass render and the joint filter over the pass films
 };
+
+const char* const kPathPassNames[PT_PATH_PASSES] = {"emission", "background", "diffuse_direct", "diffuse_indirect", "reflection_direct", "reflection_indirect",
+                                                    "transmission_direct", "transmission_indirect"};
 
 int usage(const char* msg) {
     if (msg) fprintf(stderr, "error: %s\n", msg);
@@ -164,7 +179,8 @@ int usage(const char* msg) {
                     "             [--denoise-resident] [--denoise-assemble] [--light-groups instance|material] [--light-gains G0,G1,...]\n"
                     "             [--light-group-devices MASK] [--mattes instance|material] [--matte-ranks R] [--matte-samples S]\n"
                     "             [--relamp-groups instance|material --relamp-bins B [--relamp G:CURVE[,G:CURVE...]] [--relamp-gains g0,g1,...]\n"
-                    "              [--develop-subsamples N]]\n");
+                    "              [--develop-subsamples N]]\n"
+                    "             [--path-passes] [--denoise-path-passes]\n");
     return 2;
 }
 
@@ -382,8 +398,20 @@ int main(int argc, char** argv) {
             (ranks ? o.matte_ranks : o.matte_samples) = (uint32_t)x;
             (ranks ? o.has_matte_ranks : o.has_matte_samples) = true;
         }
+        else if (a == "--path-passes") o.path_passes = true;
+        else if (a == "--denoise-path-passes") o.denoise_passes = true;
         else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
         else return usage(("unknown option " + a).c_str());
+    }
+    if (o.denoise_passes && !(o.path_passes && o.denoise)) return usage("--denoise-path-passes needs --path-passes and --denoise");
+    if (o.path_passes) {
+        const char* with = (o.adaptive >= 0.0f && !o.denoise_passes) ? "--adaptive" : o.spectral_bins ? "--spectral-bins" : o.denoise_bins ? "--denoise-spectral-bins"
+                         : o.multi ? "--devices" : o.spectral_multi ? "--spectral-devices" : o.hero ? "--hero-wavelengths" : o.light_groups ? "--light-groups"
+                         : o.denoise_groups ? "--denoise-light-groups" : o.relamp_groups ? "--relamp-groups" : o.group_multi ? "--light-group-devices"
+                         : o.assemble ? "--denoise-assemble" : nullptr;
+        static std::string refusal;
+        if (with) { refusal = std::string("--path-passes cannot be combined with ") + with + ": a pass render is one render of one wavelength per path on one device, and its films are the scene's resident group films"; return usage(refusal.c_str()); }
+        if (o.denoise && !o.denoise_passes) return usage("--path-passes cannot be combined with --denoise without --denoise-path-passes: the filter of the pass films takes the adaptive pass render");
     }
     if (o.group_multi && !o.light_groups && !o.denoise_groups) return usage("--light-group-devices needs --light-groups or --denoise-light-groups: it names the devices their group render runs on");
     if (o.group_multi && o.multi) return usage("--light-group-devices cannot be combined with --devices: a group render takes its devices from --light-group-devices alone");
@@ -533,6 +561,13 @@ int main(int argc, char** argv) {
         printf("light groups: %u (%s%s)\n", groups, group_mode == 1 ? "one per emitting instance" : "one per light material", env_emits ? ", the environment last" : "");
     }
 
+    if (o.path_passes) {
+        printf("path passes: %d (", PT_PATH_PASSES);
+        for (int c = 0; c < PT_PATH_PASSES; ++c) printf("%s%s", c ? ", " : "", kPathPassNames[c]);
+        printf(")\n");
+    }
+    const pt_path_passes_desc ppd = {{0u, 0u, 0u, 0u}};
+
     // --relamp-groups: the curves of pt_light_groups_relamp_matrix — the scene's own, where a group's old curve is, and behind them the new ones from the curves
     // library of the scene file — and per group the old and the new curve
     std::vector<pt_curve> relamp_curves;
@@ -647,8 +682,12 @@ int main(int argc, char** argv) {
             std::vector<float> group_bins;    // (--relamp-groups sizes it below)
             const pt_spectral_desc dsd = {o.denoise_bins, {0u, 0u, 0u}};
             const char* adaptive_entry = o.denoise_bins ? (o.spectral_multi ? "pt_render_adaptive_spectral_multi" : "pt_render_adaptive_spectral")
-                                         : o.denoise_groups ? (o.group_multi ? "pt_render_adaptive_light_groups_multi" : "pt_render_adaptive_light_groups") : o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive";
+                                         : o.denoise_groups ? (o.group_multi ? "pt_render_adaptive_light_groups_multi" : "pt_render_adaptive_light_groups")
+                                         : o.denoise_passes ? "pt_render_adaptive_path_passes" : o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive";
             if (o.denoise_groups) group_films.resize((size_t)gd.group_count * rd.width * rd.height * 4);
+            if (o.path_passes) group_films.resize((size_t)PT_PATH_PASSES * rd.width * rd.height * 4);
+            // --denoise-path-passes: the adaptive pass render — film, counts and statistics are pt_render_adaptive's bit for bit
+            const auto adaptive_passes = [&] { return pt_render_adaptive_path_passes(scene, &rd, &ad, &ppd, film.data(), counts.data(), stats.data(), group_films.data(), &prof); };
             // --denoise-light-groups: the adaptive group render — film, counts and statistics are pt_render_adaptive's bit for bit
             // (--light-group-devices: on the devices of the mask)
             const auto adaptive_groups = [&] {
@@ -667,6 +706,7 @@ int main(int argc, char** argv) {
                 ad.max_samples = rd.spp; ad.rel_error = 0.0f;
                 const pt_status st = o.denoise_bins ? adaptive_spectral(stats.data())
                                      : o.denoise_groups ? adaptive_groups()
+                                     : o.denoise_passes ? adaptive_passes()
                                      : o.multi      ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), stats.data(), &prof)
                                                     : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), stats.data(), &prof);
                 if (st != PT_OK) { fprintf(stderr, "%s: %s\n", adaptive_entry, pt_last_error()); rc = 1; break; }
@@ -675,6 +715,7 @@ int main(int argc, char** argv) {
                        (double)ad.rel_error, rd.max_bounces, rd.light_samples);
                 const pt_status st = o.denoise_bins ? adaptive_spectral(stats.data())
                                      : o.denoise_groups ? adaptive_groups()
+                                     : o.denoise_passes ? adaptive_passes()
                                      : o.multi      ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof)
                                                     : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof);
                 if (st != PT_OK) { fprintf(stderr, "%s: %s\n", adaptive_entry, pt_last_error()); rc = 1; break; }
@@ -698,6 +739,9 @@ int main(int argc, char** argv) {
                 if (pt_render_light_groups_spectral(scene, &rd, &gd, &sd, film.data(), nullptr, nullptr, group_bins.data(), &prof) != PT_OK) {
                     fprintf(stderr, "pt_render_light_groups_spectral: %s\n", pt_last_error()); rc = 1; break;
                 }
+            } else if (o.path_passes) {
+                printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u, %d path passes\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples, PT_PATH_PASSES);
+                if (pt_render_path_passes(scene, &rd, &ppd, film.data(), group_films.data(), &prof) != PT_OK) { fprintf(stderr, "pt_render_path_passes: %s\n", pt_last_error()); rc = 1; break; }
             } else if (o.light_groups) {
                 printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u, %u light groups\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples, gd.group_count);
                 group_films.resize((size_t)gd.group_count * rd.width * rd.height * 4);
@@ -784,6 +828,22 @@ int main(int argc, char** argv) {
                 return ok;
             };
             if (group_mode && !o.relamp_groups && !write_groups(base, group_films, false)) { rc = 1; break; }
+            // --path-passes: every class's film through this setting's film output (buffers of their own).  `stem`: base, or base + "_denoised"
+            const auto write_passes = [&](const std::string& stem, const std::vector<float>& films) {
+                const size_t np = (size_t)rd.width * rd.height;
+                std::vector<float> p_linear(3 * np);
+                std::vector<uint8_t> p_rgba(4 * np);
+                bool ok = true;
+                for (int c = 0; ok && c < PT_PATH_PASSES; ++c) {
+                    const std::string name = stem + "_pass_" + kPathPassNames[c];
+                    ok = pt_output_film(&od, films.data() + 4 * np * c, p_rgba.data(), p_linear.data()) == PT_OK &&
+                         pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, p_linear.data(), od.colorspace) == PT_OK;
+                    if (ok) printf("wrote %s.exr\n", name.c_str());
+                }
+                if (!ok) fprintf(stderr, "--path-passes: %s\n", pt_last_error());
+                return ok;
+            };
+            if (o.path_passes && !write_passes(base, group_films)) { rc = 1; break; }
             // --relamp-groups: every group's bins in the units of the EXR payload, and the re-lamped picture — the colour-matching development of the group bins by
             // the re-lamp matrix, where the render left them on the device — through this setting's film output (buffers of its own)
             if (o.relamp_groups) {
@@ -898,11 +958,13 @@ int main(int argc, char** argv) {
                 if (o.write_film && !write_npy(dbase + ".npy", clean.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", dbase.c_str()); rc = 1; break; }
                 printf("wrote %s.exr and %s.png\n", dbase.c_str(), dbase.c_str());
                 if (!write_groups(dbase, clean_groups, true, true)) { rc = 1; break; }
-            } else if (o.denoise && o.denoise_groups) {
+            } else if (o.denoise && (o.denoise_groups || o.denoise_passes)) {
                 // the render left the film, its statistics and the group films on the device, paired: the guides stay there too, and the joint filter runs on all of
                 // it (with or without --denoise-resident: this is the only route, and its files are those of either)
                 const size_t np = (size_t)rd.width * rd.height;
-                std::vector<float> clean(4 * np), clean_groups(4 * np * gd.group_count);
+                // (--denoise-path-passes: the pass films are the resident group films of this route)
+                const char* const flag = o.denoise_passes ? "--denoise-path-passes" : "--denoise-light-groups";
+                std::vector<float> clean(4 * np), clean_groups(4 * np * (o.denoise_passes ? (uint32_t)PT_PATH_PASSES : gd.group_count));
                 pt_guide_chain_desc cd;
                 memset(&cd, 0, sizeof(cd));
                 cd.max_chain = o.max_chain; cd.alpha_max = o.alpha_max;
@@ -910,7 +972,7 @@ int main(int argc, char** argv) {
                 memset(&dd, 0, sizeof(dd));
                 pt_status dst = pt_resident_guides(scene, &rd, o.guide_samples, o.chain ? &cd : nullptr, o.demodulate ? PT_RESIDENT_ALBEDO : 0u);
                 if (dst == PT_OK) dst = pt_denoise_light_groups_resident(scene, &dd, clean.data(), nullptr, clean_groups.data());
-                if (dst != PT_OK) { fprintf(stderr, "--denoise-light-groups: %s\n", pt_last_error()); rc = 1; break; }
+                if (dst != PT_OK) { fprintf(stderr, "%s: %s\n", flag, pt_last_error()); rc = 1; break; }
                 if (pt_output_film(&od, clean.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }
                 const std::string dbase = base + "_denoised";
                 if (pt_write_exr((dbase + ".exr").c_str(), rd.width, rd.height, linear.data(), od.colorspace) != PT_OK ||
@@ -919,7 +981,7 @@ int main(int argc, char** argv) {
                 }
                 if (o.write_film && !write_npy(dbase + ".npy", clean.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", dbase.c_str()); rc = 1; break; }
                 printf("wrote %s.exr and %s.png\n", dbase.c_str(), dbase.c_str());
-                if (!write_groups(dbase, clean_groups, true)) { rc = 1; break; }
+                if (!(o.denoise_passes ? write_passes(dbase, clean_groups) : write_groups(dbase, clean_groups, true))) { rc = 1; break; }
             } else if (o.denoise && (o.resident || o.assemble)) {
                 // the render left film, counts, statistics and bins on the device: the guides stay there too, and the filter runs on all of it
                 std::vector<float> clean((size_t)rd.width * rd.height * 4), clean_spectral(spectral.size());

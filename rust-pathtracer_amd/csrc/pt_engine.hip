@@ -34,6 +34,7 @@
 #include "../../include/pt_light_groups_spectral.h"
 #include "pt_adaptive_select.h"
 #include "pt_light_groups_launch.h"
+#include "pt_path_passes_launch.h"
 #include "pt_light_groups_spectral_launch.h"
 #include "pt_spectral_launch.h"
 #include "pt_spectral_rules.h"
@@ -455,11 +456,12 @@ uint32_t segment_capacity(uint32_t n, int grid) {
 
 // `b`: the scene's first set or its second (n_pixels 0: no pixel list of its own).  need_hits: the plan is not fused (a fused plan never touches the hit queue,
 // 5.9 GB at 128 Mi slots: it is made by the first render that needs it).
-// group_count: the light groups of the render (0: none) — their energy planes lie behind the total and the wavelength samples.
+// group_planes: the light groups of the render (0: none) — their energy planes lie behind the total and the wavelength samples — and, for a path-pass render,
+// the plane of state words behind its eight class planes (pt_path_pass_rules.h).
 pt_status ensure_buffers(pt_scene* sc, DeviceBuffers& b, uint32_t capacity, uint32_t light_samples, size_t n_pixels, int grid, uint32_t nl, uint32_t park_block, bool need_hits,
-                         uint32_t group_count) {
+                         uint32_t group_planes) {
     uint32_t total = segment_capacity(capacity, grid) * (uint32_t)grid;
-    const uint32_t planes_wanted = group_count ? lg_planes(group_count) : nl + 1u;
+    const uint32_t planes_wanted = group_planes ? lg_planes(group_planes) : nl + 1u;
     if (b.capacity < total || b.light_samples < light_samples || b.grid != grid || b.nl < nl || b.park_block < park_block || b.energy_planes < planes_wanted) {
         hipFree(b.paths_a); hipFree(b.paths_b); hipFree(b.hits); hipFree(b.shadow); hipFree(b.energy); hipFree(b.counts); hipFree(b.block_stats); hipFree(b.park);
         b.paths_a = b.paths_b = b.hits = b.shadow = b.counts = b.park = nullptr; b.energy = nullptr; b.block_stats = nullptr; b.capacity = 0;
@@ -643,6 +645,9 @@ struct RenderJob {
     // float4 — the render takes the general vertex and light-sample forms that route energy to the groups' planes, and every pass adds each plane to its film
     const LightGroupTable* groups = nullptr;
     float* d_group_films = nullptr;
+    // pt_render_path_passes (its arguments checked; include/pt_light_groups.h): a group render of PP_CLASSES films whose vertex and light-sample forms route the
+    // energy by the path's own history (pt_kern_passes.hip) and keep a plane of state words behind the class planes; d_group_films as above, no table
+    bool classes = false;
     // pt_render_light_groups_spectral (include/pt_light_groups_spectral.h): with groups and d_spectral, group_count * spectral_bins planes of width * height floats —
     // every pass also adds each group's plane to that group's bins
     float* d_group_bins = nullptr;
@@ -694,7 +699,7 @@ pt_status plan_render(const pt_scene* sc, const pt_render_desc& rd, const Render
     // the sweep table holds walked meshes: rays that reach one are parked and resumed in full waves (PT_AMD_NO_PARK=1: in line)
     const bool walks = (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_SWEEP_WALKS) != 0;
     const bool mesh_lights = sc->host.blob[PT_HDR_LIGHT_FACE_OFF] != 0u;   // (emissive mesh faces: PT_FORM_ANY, below)
-    const bool grouped = job.groups != nullptr;   // (a light-group render: PT_FORM_ANY and the FULL vertex form, whose siblings route the energy: pt_kern_groups.hip)
+    const bool grouped = job.groups != nullptr || job.classes;   // (a light-group or path-pass render: PT_FORM_ANY and the FULL vertex form, whose siblings route the energy: pt_kern_groups.hip)
     const bool parked = sweep && walks && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights && !grouped;
     // no sweep table (more than 64 instances, PT_AMD_NO_SWEEP): the top-level tree per lane, every mesh parked (top_walk_run, pt_device.h)
     const bool parked_walk = !sweep && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights && !grouped;
@@ -830,8 +835,8 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
 #else
     const bool need_hits = !cfg.fuse;
 #endif
-    const uint32_t group_count = job.groups ? job.groups->group_count : 0u;
-    st = ensure_buffers(sc, sc->buf, capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits, group_count);
+    const uint32_t group_count = job.classes ? PP_CLASSES : job.groups ? job.groups->group_count : 0u, group_planes = group_count + (job.classes ? 1u : 0u);
+    st = ensure_buffers(sc, sc->buf, capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits, group_planes);
     if (st != PT_OK) return st;
     DeviceBuffers& b = sc->buf;
     // Pass overlap: a render whose pass loop plans two passes or more (an adaptive one: in its first round or in a later round over every pixel) gets the second
@@ -844,7 +849,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                || (adaptive && adaptive->max_samples > rd.spp && pth::plan_passes(n_px, rd.spp, adaptive->step < adaptive->max_samples - rd.spp ? adaptive->step : adaptive->max_samples - rd.spp, capacity, rd.phase_samples).size() >= 2);
     }
     if (overlap) {
-        bool ok = ensure_buffers(sc, sc->buf2, capacity, rd.light_samples, 0, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits, group_count) == PT_OK;
+        bool ok = ensure_buffers(sc, sc->buf2, capacity, rd.light_samples, 0, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits, group_planes) == PT_OK;
         if (ok && !sc->pass_stream) ok = hipStreamCreateWithFlags(&sc->pass_stream, hipStreamNonBlocking) == hipSuccess;
         while (ok && sc->pass_deps.size() < DEP_COUNT) {
             hipEvent_t e;
@@ -867,7 +872,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     } else if (!pixels.empty()) HIP_TRY(hipMemcpyAsync(b.pixels, pixels.data(), sizeof(uint32_t) * pixels.size(), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(d_film, 0, sizeof(float) * 4 * (size_t)rd.width * rd.height, stream));
     if (job.d_spectral) HIP_TRY(hipMemsetAsync(job.d_spectral, 0, sizeof(float) * (size_t)job.spectral_bins * rd.width * rd.height, stream));
-    if (job.groups) HIP_TRY(hipMemsetAsync(job.d_group_films, 0, sizeof(float) * 4 * (size_t)group_count * rd.width * rd.height, stream));
+    if (group_count) HIP_TRY(hipMemsetAsync(job.d_group_films, 0, sizeof(float) * 4 * (size_t)group_count * rd.width * rd.height, stream));
     if (job.d_group_bins) HIP_TRY(hipMemsetAsync(job.d_group_bins, 0, sizeof(float) * (size_t)group_count * job.spectral_bins * rd.width * rd.height, stream));
     HIP_TRY(hipMemsetAsync(b.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));
     if (overlap) HIP_TRY(hipMemsetAsync(sc->buf2.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));   // (in front of the fork event)
@@ -966,7 +971,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
             if (step.wait_fork) HIP_TRY(hipStreamWaitEvent(stream, dep[DEP_FORK], 0));
             if (step.start_after >= 0) HIP_TRY(hipStreamWaitEvent(stream, dep[DEP_SKEW + (step.start_after & 1)], 0));
             if (step.wait_fork || step.start_after >= 0) mark(l, -1);
-            if (job.groups) {   // (the groups' planes, on the pass's own stream: behind the accumulate stage of the pass that used this set before, in front of this pass's vertices)
+            if (group_count) {   // (the groups' planes, on the pass's own stream: behind the accumulate stage of the pass that used this set before, in front of this pass's vertices)
                 HIP_TRY(hipMemsetAsync(b.energy + (size_t)lg_plane(0) * b.capacity, 0, sizeof(float) * (size_t)group_count * b.capacity, stream));
                 mark(l, -1);
             }
@@ -989,7 +994,10 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                 cfg.path_marks = (bounce > 0 && !rd.medium_aware && (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_CONVEX)) ? sc->host.blob[PT_HDR_CONVEX_INST] : 0u;
                 if (!cfg.fuse) timed(l, ST_EXTEND, [&] { launch_extend(cfg, trav_form, sargs, qin, qh, seg_cap, cin, b.park); });
                 if (park_dynamic) cfg.unit_counter = b.unit_counters + 2 * bounce + 1;
-                if (job.groups) {
+                if (job.classes) {
+                    timed(l, ST_SHADE, [&] { launch_shade_passes(cfg, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats); });
+                    if (rd.light_samples > 0) timed(l, ST_SHADOW, [&] { launch_shadow_passes(cfg, sargs, rd.light_samples, qs, b.energy, b.capacity, seg_cap, nshadow); });
+                } else if (job.groups) {
                     timed(l, ST_SHADE, [&] { launch_shade_groups(cfg, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats, *job.groups); });
                     if (rd.light_samples > 0) timed(l, ST_SHADOW, [&] { launch_shadow_groups(cfg, sargs, rd.light_samples, qs, b.energy, b.capacity, seg_cap, nshadow, *job.groups); });
                 } else {
@@ -1010,7 +1018,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                 // (the energy planes stay valid until the next pass's k_generate overwrites them)
                 if (job.d_spectral && spectral_error == hipSuccess)
                     spectral_error = ptk::launch_accumulate_spectral(hero ? 4 : 1, grid, stream, rp, d_px, b.energy, job.d_spectral, job.spectral_bins, rd.width * rd.height);
-                if (job.groups && groups_error == hipSuccess)
+                if (group_count && groups_error == hipSuccess)
                     groups_error = ptk::launch_accumulate_groups(stream, rp, d_px, b.energy, job.d_group_films, group_count, (size_t)rd.width * rd.height);
                 if (job.d_group_bins && group_bins_error == hipSuccess)
                     group_bins_error = ptk::launch_accumulate_group_bins(stream, rp, d_px, b.energy, job.d_group_bins, group_count, job.spectral_bins, rd.width * rd.height);
@@ -1028,7 +1036,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     st = adaptive ? adaptive_rounds(sc, rd, *adaptive, stream, d_film, (uint32_t)pixels.size(), run_passes, &rounds, job.node, job.node_index)
                   : run_passes(b.pixels, (uint32_t)pixels.size(), rd.first_sample, rd.sample_count, nullptr);
     if (st != PT_OK) return st;
-    if (adaptive && job.groups) HIP_TRY(ptk::launch_adaptive_finish_groups(stream, rd.width * rd.height, sc->adaptive.counts, job.d_group_films, group_count));
+    if (adaptive && group_count) HIP_TRY(ptk::launch_adaptive_finish_groups(stream, rd.width * rd.height, sc->adaptive.counts, job.d_group_films, group_count));
     if (adaptive && job.d_spectral)
         hipLaunchKernelGGL(k_adaptive_finish_spectral, dim3(sc->num_cus * 4), dim3(kBlock), 0, stream, rd.width * rd.height, job.spectral_bins, sc->adaptive.counts, job.d_spectral);
     HIP_TRY(hipGetLastError());
@@ -1140,6 +1148,7 @@ static pt_status scene_to_device(pt_scene* sc) {
         // (the parked light-sample kernels keep their waves' lists of live rays behind the blob: up to 16 waves x (64 L + 64) words)
         if (e == hipSuccess) e = allow_lds_shadow(kParkBlobLimitBytes + 16u * (64u * PT_MAX_LIGHT_SAMPLES + 64u) * 4u);
         if (e == hipSuccess) e = allow_lds_groups(kLdsBlobLimitBytes > PT_SHADE_LDS_BUDGET ? kLdsBlobLimitBytes : PT_SHADE_LDS_BUDGET, kLdsBlobLimitBytes);
+        if (e == hipSuccess) e = allow_lds_passes(kLdsBlobLimitBytes > PT_SHADE_LDS_BUDGET ? kLdsBlobLimitBytes : PT_SHADE_LDS_BUDGET, kLdsBlobLimitBytes);
         if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(e));
     }
     return PT_OK;
@@ -1243,6 +1252,7 @@ struct RenderCall {
     float* spectral = nullptr;              // the spectral entries
     const pt_light_groups_desc* gd = nullptr;   // pt_render_light_groups; group_films: where the caller wants them (may be null)
     float* group_films = nullptr;
+    bool passes = false;                    // pt_render_path_passes: no gd; group_films: where the caller wants the PT_PATH_PASSES pass films (may be null)
     bool group_bins = false;                // pt_render_light_groups_spectral (gd and sd): the group bins too; group_spectral: where the caller wants them (may be null)
     float* group_spectral = nullptr;
 };
@@ -1253,15 +1263,16 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
     const pt_render_desc& rd = *call.rd;
     forget_node_render(sc);
     if (call.sd) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts: whatever the buffer held is no film from here on)
-    if (call.gd) end_group_films(sc);   // (likewise the group films, the denoised ones that came from them, and the group bins)
+    const uint32_t films = call.passes ? (uint32_t)PT_PATH_PASSES : call.gd ? call.gd->group_count : 0u;   // the resident group films this render leaves
+    if (films) end_group_films(sc);   // (likewise the group films, the denoised ones that came from them, and the group bins)
     sc->groups_paired = false;   // (the resident film ends below)
     sc->resident.end();   // (film_cache and the adaptive buffers are written from here on; guides and denoised outputs belonged to the film before)
     HIP_TRY(hipSetDevice(sc->device));
     const size_t n_pixels = (size_t)rd.width * rd.height, film_bytes = sizeof(float) * 4 * n_pixels, spectral_bytes = call.sd ? sizeof(float) * call.sd->bins * n_pixels : 0;
     pt_status st = sc->film_cache.reserve(film_bytes);
     if (st == PT_OK && call.sd) st = sc->spectral_cache.reserve(spectral_bytes);
-    const size_t group_bytes = call.gd ? film_bytes * call.gd->group_count : 0;
-    if (st == PT_OK && call.gd) st = sc->group_films_cache.reserve(group_bytes);
+    const size_t group_bytes = film_bytes * films;
+    if (st == PT_OK && films) st = sc->group_films_cache.reserve(group_bytes);
     if (st == PT_OK && call.gd) st = sc->group_table.reserve(call.gd->instance_count ? call.gd->instance_count : 1u);
     if (st != PT_OK) return st;
     const size_t group_bins_bytes = call.group_bins ? spectral_bytes * call.gd->group_count : 0;
@@ -1280,6 +1291,7 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
         if (call.gd->instance_count) HIP_TRY(hipMemcpy(sc->group_table.p, call.gd->instance_group, call.gd->instance_count, hipMemcpyHostToDevice));
         job.groups = &table; job.d_group_films = sc->group_films_cache.as<float>();
     }
+    if (call.passes) { job.classes = true; job.d_group_films = sc->group_films_cache.as<float>(); }
     if (call.sd) { job.d_spectral = sc->spectral_cache.as<float>(); job.spectral_bins = call.sd->bins; }
     if (call.group_bins) job.d_group_bins = sc->group_bins_cache.as<float>();
     const hipStream_t stream = nullptr;
@@ -1297,9 +1309,9 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
         sc->group_bins_width = rd.width; sc->group_bins_height = rd.height; sc->group_bins_groups = call.gd->group_count; sc->group_bins_bins = call.sd->bins;
         sc->group_bins_valid = true;
     }
-    if (call.gd && call.group_films) HIP_TRY(hipMemcpy(call.group_films, sc->group_films_cache.p, group_bytes, hipMemcpyDeviceToHost));
-    if (call.gd) { sc->groups_width = rd.width; sc->groups_height = rd.height; sc->groups_count = call.gd->group_count; sc->groups_valid = true; }
-    if (call.gd && call.ad) sc->groups_paired = true;   // (the resident film set below and the group films came from this one render)
+    if (films && call.group_films) HIP_TRY(hipMemcpy(call.group_films, sc->group_films_cache.p, group_bytes, hipMemcpyDeviceToHost));
+    if (films) { sc->groups_width = rd.width; sc->groups_height = rd.height; sc->groups_count = films; sc->groups_valid = true; }
+    if (films && call.ad) sc->groups_paired = true;   // (the resident film set below and the group films came from this one render)
     if (call.ad && profile) profile->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (the whole call: set-up, rounds, read-backs)
     if (call.sd) { sc->spectral_width = rd.width; sc->spectral_height = rd.height; sc->spectral_bins = call.sd->bins; sc->spectral_valid = true; }
     if (call.ad) {   // the resident set of include/pt_resident.h: film, counts and statistics, and the bins of a spectral render
@@ -1381,6 +1393,32 @@ pt_status pt_render_adaptive_light_groups(pt_scene* sc, const pt_render_desc* rd
     if ((uint64_t)rd.width * rd.height > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and width x height must fit 31 bits");
     RenderCall call;
     call.rd = &rd; call.ad = &ad; call.gd = gdp; call.film = film; call.sample_counts = sample_counts; call.stats = stats; call.group_films = group_films;
+    return render_one(sc, call, profile);
+}
+
+// include/pt_light_groups.h, "Path passes": a group render of PT_PATH_PASSES films routed by the path's history; what it leaves is the scene's resident group films
+pt_status pt_render_path_passes(pt_scene* sc, const pt_render_desc* rdp, const pt_path_passes_desc* pdp, float* film, float* pass_films, pt_profile* profile) {
+    forget_node_render(sc);
+    std::string err;
+    const pt_status st = pth::check_path_passes_args(sc, rdp, pdp, film, &err);
+    if (st != PT_OK) return fail(st, err);
+    if (rdp->width == 0 || rdp->height == 0 || (uint64_t)rdp->width * rdp->height > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and width x height must fit 31 bits");
+    RenderCall call;
+    call.rd = rdp; call.passes = true; call.film = film; call.group_films = pass_films;
+    return render_one(sc, call, profile);
+}
+
+pt_status pt_render_adaptive_path_passes(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, const pt_path_passes_desc* pdp, float* film,
+                                         uint32_t* sample_counts, double* stats, float* pass_films, pt_profile* profile) {
+    forget_node_render(sc);
+    pt_render_desc rd;
+    pt_adaptive_desc ad;
+    std::string err;
+    const pt_status st = pth::check_adaptive_path_passes_args(sc, rdp, adp, pdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, film, sample_counts, &rd, &ad, &err);
+    if (st != PT_OK) return fail(st, err);
+    if ((uint64_t)rd.width * rd.height > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and width x height must fit 31 bits");
+    RenderCall call;
+    call.rd = &rd; call.ad = &ad; call.passes = true; call.film = film; call.sample_counts = sample_counts; call.stats = stats; call.group_films = pass_films;
     return render_one(sc, call, profile);
 }
 

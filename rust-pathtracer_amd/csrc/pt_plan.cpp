@@ -546,6 +546,31 @@ pt_status check_light_groups_args(const void* scene, const pt_render_desc* rd, c
     return light_groups_args(scene, rd, gd, scene_instances, film, nullptr, error);
 }
 
+pt_status check_path_passes_args(const void* scene, const pt_render_desc* rd, const pt_path_passes_desc* pd, const void* film, std::string* error) {
+    if (!scene) { *error = "the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!rd) { *error = "the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!pd) { *error = "the path passes desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!film) { *error = "film_xyzw is null"; return PT_ERR_INVALID_ARGUMENT; }
+    for (uint32_t r : pd->reserved) if (r != 0) { *error = "pt_path_passes_desc::reserved must be 0"; return PT_ERR_INVALID_ARGUMENT; }
+    if (rd->hero_wavelengths == 4) { *error = "path passes carry one wavelength per path (hero_wavelengths 0 or 1)"; return PT_ERR_UNSUPPORTED; }
+    if (rd->medium_aware) { *error = "path passes are not rendered by the medium-aware walk"; return PT_ERR_UNSUPPORTED; }
+    if (rd->shard_count > 1) { *error = "path passes render the whole film (shard_count 0 or 1)"; return PT_ERR_UNSUPPORTED; }
+    if (rd->first_sample != 0 || (rd->sample_count != 0 && rd->sample_count != rd->spp)) {
+        *error = "path passes render the whole sample range (first_sample 0, sample_count 0 or spp)";
+        return PT_ERR_UNSUPPORTED;
+    }
+    return PT_OK;
+}
+pt_status check_adaptive_path_passes_args(const void* scene, const pt_render_desc* rd, const pt_adaptive_desc* ad, const pt_path_passes_desc* pd, uint32_t camera_count,
+                                          const void* film, const void* sample_counts, pt_render_desc* rd_out, pt_adaptive_desc* ad_out, std::string* error) {
+    if (!scene) { *error = "the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!rd) { *error = "the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!ad) { *error = "the adaptive desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = check_path_passes_args(scene, rd, pd, film, error);
+    if (st != PT_OK) return st;
+    return normalize_adaptive_desc(*rd, *ad, sample_counts != nullptr, camera_count, rd_out, ad_out, error);
+}
+
 // ---- include/pt_light_groups_multi.h
 pt_status check_light_groups_multi_args(const void* scene, const pt_render_desc* rd, const pt_light_groups_desc* gd, uint32_t scene_instances, uint32_t camera_count,
                                         const void* film, pt_render_desc* rd_out, std::string* error) {

@@ -167,6 +167,13 @@ pt_status check_light_groups_matrices(uint32_t group_count, const float* matrice
 pt_status check_light_groups_mix_args(uint32_t width, uint32_t height, uint32_t group_count, const void* group_films, const float* matrices, const void* out,
                                       std::string* error);
 
+// pt_render_path_passes (include/pt_light_groups.h): no null pointer (pass_films may be null), reserved words 0: PT_ERR_INVALID_ARGUMENT; hero_wavelengths 4,
+// medium_aware, a shard (shard_count > 1) and a partial sample range: PT_ERR_UNSUPPORTED, as check_light_groups_args refuses them
+pt_status check_path_passes_args(const void* scene, const pt_render_desc* rd, const pt_path_passes_desc* pd, const void* film, std::string* error);
+// pt_render_adaptive_path_passes (include/pt_light_groups_denoise.h): the adaptive desc too, then check_path_passes_args and normalize_adaptive_desc
+pt_status check_adaptive_path_passes_args(const void* scene, const pt_render_desc* rd, const pt_adaptive_desc* ad, const pt_path_passes_desc* pd, uint32_t camera_count,
+                                          const void* film, const void* sample_counts, pt_render_desc* rd_out, pt_adaptive_desc* ad_out, std::string* error);
+
 // ---- include/pt_light_groups_multi.h, for the engine and the host emulation alike; every check runs before a device is looked for.
 // pt_render_light_groups_multi: everything check_light_groups_args refuses, with its words, except that a shard in the desc (shard_count != 0) is the node
 // entry's own PT_ERR_INVALID_ARGUMENT ("... deals the tiles itself: shard_count must be 0"); then normalize_render_desc's conditions; *rd_out as that leaves it.

@@ -726,6 +726,15 @@ def light_groups_room(emit=(True, True, True), rect_curve="E5", extra_curves=())
     return b
 
 
+def path_passes_room():
+    """light_groups_room with a pane of rough glass between the camera and the lamps (the scene of the path-pass tests; not a reference
+    scene).  A closed glass body never yields direct transmission — a light-sample ray that enters it is stopped by its far side, and the walk's next vertex
+    lies inside it — so the room alone leaves that class empty; through a sheet the lamps and the sky are seen and sampled directly."""
+    b = light_groups_room()
+    b.add_rect((1.4, 1.2), (-2.5, -0.2, 0.6), "X", True, add_library_material(b, "ggx_glass_rough"))
+    return b
+
+
 def big_sphere_light():
     """A sphere light of radius 20 000 hanging 0.02 above a floor (not a reference scene): from the floor under it a light sample's hit
     distance is 0.02 .. 1 while the terms of the sphere's quadratic are ~4e8 (|oc|^2 - r^2) and ~2e4 (-b, the root), so the computed

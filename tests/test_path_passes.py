@@ -1,0 +1,614 @@
+"""Path passes (include/pt_light_groups.h "Path passes"): the render split by how the light travelled — emission, background, and direct
+and indirect diffuse, reflection and transmission — as eight group films routed by the path's own history.
+
+The CPU tier checks the host emulation (tests/host_emulation/ptemu_path_passes.cpp: ptemu_light_groups.cpp's loop with the engine's routing text, state plane
+and item word) against ptemu_render, against identities that do not depend on the routing text (truncation, a Lambertian-only scene, conservation), against a
+third reading in scalar Python laid over tests/test_integrator_third_reading.py's vertex list, and the item word through a debug export; then every refusal, the
+header, the binding rows and the command line.  The GPU tier checks the engine against the emulation and against its own other entries."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import test_integrator_third_reading as t3
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.join(HERE, "..")
+EMU_DIR = os.path.join(HERE, "host_emulation")
+CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
+f32 = np.float32
+F = np.float32
+
+NAMES = ("emission", "background", "diffuse_direct", "diffuse_indirect", "reflection_direct", "reflection_indirect", "transmission_direct", "transmission_indirect")
+DIRECT_AND_FIRST = (0, 1, 2, 4, 6)   # the classes only bounces 0 and 1 add to
+INDIRECT = (3, 5, 7)
+DIFFUSE, REFLECTION, TRANSMISSION = 0, 1, 2
+
+
+def room_rd(pkg, max_bounces=5):
+    """The light-group tests' shape: two phases of ten and a remainder."""
+    return pkg.api.render_desc(24, 24, 23, max_bounces, light_samples=2, seed=7)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, f32).view(np.uint32)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
+
+
+def counters(p):
+    return (p.camera_rays, p.bounce_rays, p.shadow_rays, p.env_hits)
+
+
+@pytest.fixture(scope="session")
+def emu_pp(pkg):
+    """The host emulation (ptemu.cpp) with the pass render (ptemu_path_passes.cpp) beside it: a library of its own."""
+    lib = os.path.join(EMU_DIR, "libptemu_path_passes.so")
+    srcs = [os.path.join(EMU_DIR, "ptemu.cpp"), os.path.join(EMU_DIR, "ptemu_path_passes.cpp"), os.path.join(CSRC, "pt_scene_host.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
+    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_light_group_rules.h", "pt_path_pass_rules.h")] + \
+        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_debug.h", "pt_numerics.h", "pt_light_groups.h")]
+    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-Wno-unknown-pragmas",
+                               "-o", lib] + srcs)
+    return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+
+
+def recorded_pass_render(emu_pp, builder, rd):
+    """(film, passes, profile, items [n, 3]) of the emulation: the items through its debug export — item word, d in front of the vertex, its material's kind."""
+    emu_pp.lib.ptemu_path_passes_debug_items.restype = C.c_uint32
+    emu_pp.lib.ptemu_path_passes_debug_record(1)
+    film, passes, prof = emu_pp.create_scene(builder).render_path_passes(rd)
+    n = emu_pp.lib.ptemu_path_passes_debug_items(None, 0)
+    items = np.zeros(n, np.uint32)
+    assert emu_pp.lib.ptemu_path_passes_debug_items(items.ctypes.data_as(C.POINTER(C.c_uint32)), n) == n
+    emu_pp.lib.ptemu_path_passes_debug_record(0)
+    return film, passes, prof, items.reshape(-1, 3)
+
+
+@pytest.fixture(scope="session")
+def room_emu(pkg, emu_pp):
+    """The emulation's renders of the room, made once and left unchanged: the pass render at 5, 2 and 1 bounces, ptemu_render, and the items of the 5-bounce render."""
+    room = pkg.scene.light_groups_room()
+    film, passes, prof, items = recorded_pass_render(emu_pp, room, room_rd(pkg))
+    two = emu_pp.create_scene(room).render_path_passes(room_rd(pkg, 2))
+    one = emu_pp.create_scene(room).render_path_passes(room_rd(pkg, 1))
+    plain = emu_pp.create_scene(room).render(room_rd(pkg))
+    for a in (film, passes, two[0], two[1], one[0], one[1], plain[0], items):
+        a.setflags(write=False)
+    return {"film": film, "passes": passes, "prof": prof, "two": two, "one": one, "plain": plain, "items": items}
+
+
+@pytest.fixture(scope="session")
+def pane_emu(pkg, emu_pp):
+    """The emulation's pass render of scene.path_passes_room — the room behind a pane of glass, which fills the one class the room leaves empty — and its items."""
+    film, passes, prof, items = recorded_pass_render(emu_pp, pkg.scene.path_passes_room(), room_rd(pkg))
+    for a in (film, passes, items):
+        a.setflags(write=False)
+    return {"film": film, "passes": passes, "prof": prof, "items": items}
+
+
+# ------------------------------------------------------------------------------------------------ CPU tier
+def test_total_and_counters_are_ptemu_renders(pkg, emu_pp, room_emu, monkeypatch):
+    """The total film and the four counters are ptemu_render's, bit for bit; also with PTEMU_BATCH small enough to force several passes."""
+    e = room_emu
+    assert same_bits(e["film"], e["plain"][0]) and counters(e["prof"]) == counters(e["plain"][1])
+    monkeypatch.setenv("PTEMU_BATCH", "2048")   # (24 x 24 x 23 = 13248 slots: at least seven passes)
+    film, passes, prof = emu_pp.create_scene(pkg.scene.light_groups_room()).render_path_passes(room_rd(pkg))
+    assert same_bits(film, e["film"]) and same_bits(passes, e["passes"]) and counters(prof) == counters(e["prof"])
+
+
+def test_every_class_is_lit(room_emu, pane_emu):
+    """Every one of the eight classes is non-zero in at least one pixel; all pass films are finite, with w = 0.  The room itself leaves direct transmission
+    empty at every camera — its only glass is a closed body (scene.path_passes_room) — so the check runs on the room behind a pane of glass; the room's own
+    seven other classes are lit too."""
+    r = room_emu["passes"]
+    assert all((r[c][..., :3] != 0).any() for c in range(8) if c != 6) and np.isfinite(r).all() and not r[..., 3].any()
+    p = pane_emu["passes"]
+    assert p.shape == (8, 24, 24, 4)
+    for c in range(8):
+        print("%-22s lit pixels %4d  max %.4g" % (NAMES[c], int((p[c][..., :3] != 0).any(axis=-1).sum()), float(p[c][..., :3].max())))
+    for c in range(8):
+        assert (p[c][..., :3] != 0).any(), NAMES[c]
+    assert np.isfinite(p).all() and not p[..., 3].any()
+
+
+def truncation_identity(five, two, one):
+    """Independent of the routing text: the walk of bounces 0 and 1 does not depend on max_bounces, and only those two bounces add to emission, background
+    and the three direct classes — so these passes are the 2-bounce render's bit for bit; and one bounce has no indirect light at all."""
+    for c in DIRECT_AND_FIRST:
+        assert same_bits(five[c], two[c]), NAMES[c]
+    for c in INDIRECT:
+        assert not one[c].any(), NAMES[c]
+
+
+def test_truncation_identity(room_emu):
+    truncation_identity(room_emu["passes"], room_emu["two"][1], room_emu["one"][1])
+    assert any(room_emu["two"][1][c].any() for c in INDIRECT)   # (the second bounce's light samples are indirect light)
+
+
+def lambertian_only(lib, pkg):
+    film, passes, prof = lib.create_scene(pkg.scene.cornell_box()).render_path_passes(pkg.api.render_desc(16, 16, 12, 5, light_samples=2, seed=3))
+    for c in (1, 4, 5, 6, 7):
+        assert not passes[c].any(), NAMES[c]
+    for c in (0, 2, 3):
+        assert passes[c][..., :3].max() > 0, NAMES[c]
+    return film, passes, prof
+
+
+def test_lambertian_only_scene(pkg, emu_pp):
+    """The Cornell box holds Lambertian surfaces and one lamp under a dark sky: no reflection, no transmission, no background."""
+    lambertian_only(emu_pp, pkg)
+
+
+def test_conservation(pkg, room_emu):
+    """|film - sum of the passes| per pixel and channel under a bound from the f32 additions of the longest chain.
+
+    A film value and the sum of the eight pass values are two floating-point evaluations of one real sum S of the pixel's terms (addition x colour-matching
+    weight / spp).  Each evaluation's error is at most (depth of its chain) x u x sum |terms| to first order, u = 2^-24, the depth being the operations a term
+    passes through on its way into the value:
+      per sample, per bounce: the vertex addition (1) and the item: L additions into the ray sum, the division by L, the addition to the slot (L + 2) —
+        B (L + 3) with B = max_bounces;
+      the multiplication by the colour-matching weight (1), the sum of the phase's samples (at most 10), the sum of the phases (ceil(spp / 10)), the
+        division by spp (1).
+    Both evaluations have that depth N; the pass films are then summed here in f64, bounded by the 8 additions an f32 sum of them would take.  So
+    |film - sum_g pass_g| <= (2 N + 8) u sum |terms|, and sum |terms| is sum_g |pass_g| up to the same relative error (every term of a class film has the sign
+    of its colour-matching weight, shared by the sample's terms; the 1.001 below covers the second order)."""
+    rd = room_rd(pkg)
+    N = rd.max_bounces * (rd.light_samples + 3) + 1 + 10 + -(-rd.spp // 10) + 1
+    film, passes = room_emu["film"].astype(np.float64), room_emu["passes"].astype(np.float64)
+    bound = (2 * N + 8) * 2.0 ** -24 * 1.001 * np.abs(passes).sum(axis=0)
+    err = np.abs(film - passes.sum(axis=0))
+    worst = float((err[..., :3] / np.maximum(bound[..., :3], 1e-300)).max())
+    print("chain depth N = %d; worst |film - sum| / bound = %.3g; worst absolute %.3g" % (N, worst, float(err.max())))
+    assert (err <= bound).all()   # (every pixel, every channel, w included: 0 <= 0)
+
+
+@pytest.mark.parametrize("which", ["room", "pane"])
+def test_item_word(pkg, room_emu, pane_emu, which):
+    """For every item of the room render (and of the room behind the pane) class_b differs from class_a only at d = 0 on a GGX or Passthrough vertex, and
+    there it is transmission direct beside reflection direct; class_b's ray bits are set nowhere else."""
+    a = pkg.api
+    items = {"room": room_emu, "pane": pane_emu}[which]["items"]
+    assert len(items) > 1000
+    word, d, kind = items[:, 0], items[:, 1], items[:, 2]
+    ca, cb, ray_bits = word & 7, (word >> 3) & 7, (word >> 8) & 0xff
+    split = cb != ca
+    glossy = (kind == a.MATERIAL_GGX) | (kind == a.MATERIAL_PASSTHROUGH)
+    assert np.array_equal(split, (d == 0) & glossy)
+    assert split.any() and (~split).any()
+    assert (ca[split] == 4).all() and (cb[split] == 6).all()
+    assert not ray_bits[~split].any() and ray_bits[split].any()
+    assert (ca[(d == 0) & ~glossy] == 2).all()
+    assert np.isin(ca[d != 0], INDIRECT).all() and (d <= 2).all()
+    assert not (word >> 20).any()
+
+
+# ---- a third reading: scalar Python over test_integrator_third_reading.py's vertex list
+def third_kind_is_diffuse(P, material):
+    kind = P.b.materials[int(material) & 0xFFFF].kind
+    a = P.pkg.api
+    return kind in (a.MATERIAL_LAMBERTIAN, a.MATERIAL_DIFFUSE_LIGHT, a.MATERIAL_SHARP_LIGHT)
+
+
+def third_event(P, v, out_dir):
+    """e(dir) at the vertex v: diffuse by the material's kind, else transmission when the direction leaves on the side the path arrived from.  The path
+    arrived along -wi: it travels towards the normal's side exactly when wi.z < 0."""
+    if third_kind_is_diffuse(P, v.material):
+        return DIFFUSE
+    arrives_up = bool(v.local_wi[2] < 0)
+    leaves_up = bool(t3.dot(v.normal, out_dir) > 0)
+    return TRANSMISSION if arrives_up == leaves_up else REFLECTION
+
+
+def third_light_samples(P, lights, lam, v, n, frame, wi, pixel, sample, bounce, d, k, energy):
+    """t3.direct_illumination restated per ray: each ray's contribution / light_samples is summed per class in ray order (two sums at most are ever non-zero)."""
+    rd = P.rd
+    sums = {}
+    env_p = F(P.b.env_sampling_probability) if lights else F(1.0)
+    if not lights and env_p == 0:
+        return
+    for l in range(rd.light_samples):
+        r = P.draw4(pixel, sample, 32 + bounce * (1 + rd.light_samples) + 1 + l)
+        x = r[0]
+        if x < env_p:
+            direction = t3.uv_to_direction(P, r[1], r[2])
+            c = t3.direct_illumination_from_world(P, lam, v.point, n, frame, wi, v.material, v.throughput, r[1:3])
+        else:
+            x = F(F(x - env_p) / F(F(1.0) - env_p))
+            cnt = len(lights)
+            idx = int(min(max(F(F(cnt) * x), F(0.0)), F(cnt - 1)))
+            rect = lights[idx][1]
+            direction, light_pdf = t3.rect_sample(rect, r[1:3], v.point)
+            light_pdf = F(light_pdf * F(F(1.0) / F(cnt)))
+            if light_pdf == 0:
+                continue
+            wo = frame.to_local(direction)
+            refl, bounce_pdf = P.bsdf(v.material, lam, wi, wo)
+            weight = F(1.0) if rd.only_direct else F(light_pdf / F(light_pdf + bounce_pdf))
+            o = (t3.f3(v.point) + t3.f3(n) * F(t3.NORMAL_OFFSET * t3.signum(wo[2]))).astype(np.float32)
+            sh = P.hit(o, direction)
+            if sh is None or t3.tag(sh["material"]) != t3.TAG_LIGHT:
+                continue
+            lwi = t3.Frame(sh["normal"]).to_local(-direction)
+            le = P.emission(sh["material"], lam, lwi)
+            cos_i, cos_o = F(abs(lwi[2])), F(abs(wo[2]))
+            c = F(F(F(F(F(F(refl * v.throughput) * cos_i) * cos_o) * le) * weight) / light_pdf)
+        if c == 0:
+            continue
+        cls = 2 + 2 * third_event(P, v, direction) if d == 0 else 3 + 2 * k
+        sums[cls] = F(sums.get(cls, F(0.0)) + c)
+    for cls, s in sums.items():
+        energy[cls] = F(energy[cls] + F(s / F(rd.light_samples)))
+
+
+def third_color(P, lights, pixel, sample):
+    """t3.color with the routing rule: eight energies, one per class."""
+    rd = P.rd
+    o, d0, lam = P.sc.camera_samples(rd, [pixel], [sample])
+    o, d0, lam = t3.f3(o[0]), t3.f3(d0[0]), F(lam[0])
+    path = [t3.Vertex("camera", t3.f3([0, 0, 0]), o, d0, 0, 0, F(1.0), F(100.0))]
+    t3.random_walk(P, o, d0, lam, pixel, sample, path)
+    energy = [F(0.0)] * 8
+    d, k = 0, None
+    for index in range(1, len(path)):
+        prev, v = path[index - 1], path[index]
+        vertex_class = (0 if v.kind != "env" else 1) if d == 0 else (2 + 2 * k if d == 1 else 3 + 2 * k)
+        if v.kind == "env":
+            wo = v.normal
+            cos_i = F(abs(t3.dot(prev.normal, wo)))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                w = t3.power_heuristic(F(prev.pdf_forward / cos_i), F(t3.ENV_PDF / cos_i))
+            energy[vertex_class] = F(energy[vertex_class] + F(F(w * v.throughput) * P.env_emission(lam)))
+        elif v.kind == "light":
+            em = P.emission(v.material, lam, v.local_wi)
+            if em > 0:
+                if rd.light_samples == 0 or prev.kind == "camera":
+                    energy[vertex_class] = F(energy[vertex_class] + F(v.throughput * em))
+                elif not rd.only_direct:
+                    nd = t3.normalized((v.point - prev.point).astype(np.float32))
+                    hyp = t3.rect_psa_pdf(dict(lights)[v.instance], t3.dot(prev.normal, nd), t3.dot(v.normal, nd), prev.point, v.point)
+                    w = t3.power_heuristic(prev.pdf_forward, hyp)
+                    energy[vertex_class] = F(energy[vertex_class] + F(F(w * v.throughput) * em))
+        else:
+            n = t3.normalized(v.normal)
+            frame = t3.Frame(n)
+            wi = frame.to_local(t3.normalized((prev.point - v.point).astype(np.float32)))
+            if rd.light_samples > 0:
+                third_light_samples(P, lights, lam, v, n, frame, wi, pixel, sample, index - 1, d, k, energy)
+        if index + 1 < len(path):   # the walk continues from v: a scattering event, whose kind is that of the direction to the next vertex
+            nxt = path[index + 1]
+            out_dir = nxt.normal if nxt.kind == "env" else t3.normalized((nxt.point - v.point).astype(np.float32))
+            if d == 0:
+                k = third_event(P, v, out_dir)
+            d = min(d + 1, 2)
+    xyz = P.xyz_bar(lam)
+    return [(xyz * e).astype(np.float32) for e in energy]
+
+
+def third_render(P, lights):
+    rd = P.rd
+    films = np.zeros((8, rd.height, rd.width, 4), np.float32)
+    for y in range(rd.height):
+        for x in range(rd.width):
+            px, temp = np.zeros((8, 3), np.float32), np.zeros((8, 3), np.float32)
+            for s in range(rd.spp):
+                temp = (temp + np.stack(third_color(P, lights, y * rd.width + x, s))).astype(np.float32)
+                if (s + 1) % 10 == 0 or s + 1 == rd.spp:
+                    px = (px + temp).astype(np.float32)
+                    temp = np.zeros((8, 3), np.float32)
+            films[:, y, x, :3] = px / F(rd.spp)
+    return films
+
+
+@pytest.mark.parametrize("kw", [{}, {"light_samples": 3}], ids=["L2", "L3"])
+def test_passes_agree_with_a_third_reading(pkg, oracle, emu_pp, kw):
+    """The eight pass films of sky_and_lamp from the scalar-Python classification agree with the emulation's under the third reading's own bar,
+    max |d| / max(|ref|, 1e-3) < 2e-5, every pixel, channel and class."""
+    b = t3.sky_and_lamp(pkg)
+    lights = [(i, t3.rect_of(b, i)) for i, inst in enumerate(b.instances) if inst.kind == pkg.api.SHAPE_RECT and t3.tag(inst.material) == t3.TAG_LIGHT]
+    assert len(lights) == 1
+    rd = pkg.api.render_desc(16, 12, 3, 6, **kw)
+    mine = third_render(t3.Probes(pkg, oracle, b, rd), lights)
+    film, ref, _ = emu_pp.create_scene(b).render_path_passes(rd)
+    assert np.isfinite(mine).all() and np.isfinite(ref).all()
+    rel = np.abs(mine - ref)[..., :3] / np.maximum(np.abs(ref[..., :3]), 1e-3)
+    for c in range(8):
+        print("%-22s worst %.3g  lit %d" % (NAMES[c], float(rel[c].max()), int((ref[c][..., :3] != 0).any(axis=-1).sum())))
+    assert all(ref[c].any() for c in (1, 2, 3, 4, 7))   # (a lit comparison: the sky, the diffuse floor and ball, the glass ball's two sides)
+    assert rel.max() < 2e-5, float(rel.max())
+
+
+# ---- the surface
+def test_refusals(pkg, emu_pp):
+    """Every refusal returns its status and a message of its own; the product runs the same checks before it looks for a device."""
+    a = pkg.api
+    sc = emu_pp.create_scene(pkg.scene.light_groups_room())
+    ok = dict(width=8, height=8, spp=10, max_bounces=3)
+    cases = [
+        ("hero", a.render_desc(hero_wavelengths=4, **ok), a.PT_ERR_UNSUPPORTED, "one wavelength"),
+        ("medium", a.render_desc(medium_aware=True, **ok), a.PT_ERR_UNSUPPORTED, "medium-aware"),
+        ("shard", a.render_desc(shard=(0, 2), **ok), a.PT_ERR_UNSUPPORTED, "whole film"),
+        ("range", a.render_desc(first_sample=0, sample_count=5, **ok), a.PT_ERR_UNSUPPORTED, "whole sample range"),
+    ]
+    seen = set()
+    for name, rd, status, word in cases:
+        with pytest.raises(a.PtError) as e:
+            sc.render_path_passes(rd)
+        assert e.value.status == status and word in str(e.value) and "path passes" in str(e.value), (name, str(e.value))
+        seen.add(str(e.value))
+    assert len(seen) == 4
+    fp = C.POINTER(C.c_float)
+    film = np.zeros((8, 8, 4), f32)
+    rd, pd = a.render_desc(**ok), a.PathPassesDesc()
+    emu_pp.lib.ptemu_light_groups_last_error.restype = C.c_char_p
+    entry, error = emu_pp._render_path_passes, lambda: emu_pp.lib.ptemu_light_groups_last_error().decode()
+    assert entry(None, C.byref(rd), C.byref(pd), film.ctypes.data_as(fp), None, None) == 1 and error() == "the scene is null"
+    assert entry(sc.handle, None, C.byref(pd), film.ctypes.data_as(fp), None, None) == 1 and error() == "the render desc is null"
+    assert entry(sc.handle, C.byref(rd), None, film.ctypes.data_as(fp), None, None) == 1 and error() == "the path passes desc is null"
+    assert entry(sc.handle, C.byref(rd), C.byref(pd), None, None, None) == 1 and error() == "film_xyzw is null"
+    bad = a.PathPassesDesc(); bad.reserved[2] = 1
+    assert entry(sc.handle, C.byref(rd), C.byref(bad), film.ctypes.data_as(fp), None, None) == 1 and "reserved must be 0" in error()
+    # the product runs the same checks before it looks for a device: without a scene the first of them is the one that can be seen — of both entries
+    L = pkg.load()
+    assert L._render_path_passes(None, C.byref(rd), C.byref(pd), film.ctypes.data_as(fp), None, None) == 1 and L.last_error() == "the scene is null"
+    ad = a.AdaptiveDesc(40, 10, 0.1, 0.0)
+    counts = np.zeros((8, 8), np.uint32)
+    assert L._render_adaptive_path_passes(None, C.byref(rd), C.byref(ad), C.byref(pd), film.ctypes.data_as(fp), counts.ctypes.data_as(C.POINTER(C.c_uint32)), None, None,
+                                          None) == 1 and L.last_error() == "the scene is null"
+
+
+def test_header_constants_and_binding_rows(pkg, tmp_path):
+    """The header's constants are the binding table's, the desc has the compiler's size, both entries are exported and bound."""
+    a = pkg.api
+    src = tmp_path / "consts.c"
+    src.write_text('#include <stdio.h>\n#include "pt_light_groups_denoise.h"\nint main(void) { printf("%d %zu %d %d %d %d %d %d %d %d %d", PT_PATH_PASSES, '
+                   'sizeof(pt_path_passes_desc), PT_PATH_PASS_EMISSION, PT_PATH_PASS_BACKGROUND, PT_PATH_PASS_DIFFUSE_DIRECT, PT_PATH_PASS_DIFFUSE_INDIRECT, '
+                   'PT_PATH_PASS_REFLECTION_DIRECT, PT_PATH_PASS_REFLECTION_INDIRECT, PT_PATH_PASS_TRANSMISSION_DIRECT, PT_PATH_PASS_TRANSMISSION_INDIRECT, '
+                   'PT_LIGHT_GROUPS_MAX); return 0; }\n')
+    exe = tmp_path / "consts"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
+    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert got == [8, C.sizeof(a.PathPassesDesc)] + list(range(8)) + [8]
+    assert a.PATH_PASSES == 8 and tuple(a.PATH_PASS_NAMES) == NAMES
+    lib = C.CDLL(pkg.load().path)
+    for name, header in (("render_path_passes", "pt_light_groups.h"), ("render_adaptive_path_passes", "pt_light_groups_denoise.h")):
+        assert getattr(lib, "pt_" + name) is not None
+        assert name in a.ENTRIES and name in [e.name for h, rows in a.BINDINGS if h == header for e in rows]
+        assert ("pt_" + name + "(") in open(os.path.join(ROOT, "include", header)).read()
+    assert len(a.ENTRIES["render_path_passes"].argtypes) == 6 and len(a.ENTRIES["render_adaptive_path_passes"].argtypes) == 9
+
+
+def scaled_c2_config(pkg):
+    """data/config_cornell_c2.toml at 32x32 and 20 spp (tests/test_light_groups.py's)."""
+    text = open(os.path.join(pkg.PACKAGE_DIR, "data", "config_cornell_c2.toml")).read()
+    text, n1 = re.subn(r"min_samples = \d+", "min_samples = 20", text)
+    text, n2 = re.subn(r"width = \d+\nheight = \d+", "width = 32\nheight = 32", text)
+    assert (n1, n2) == (1, 1)
+    return text
+
+
+def ptcli(pkg):
+    return os.path.join(pkg.PACKAGE_DIR, "csrc", "ptcli")
+
+
+def test_ptcli_flag_refusals(pkg):
+    """Each forbidden combination exits with status 2 and its own message before any file is read; the help and the file's head name the flags."""
+    exe = ptcli(pkg)
+    pp = ["--path-passes"]
+    cases = [(pp + extra, "--path-passes cannot be combined with " + extra[0]) for extra in (
+        ["--adaptive", "0.1"], ["--spectral-bins", "8"], ["--denoise-spectral-bins", "8"], ["--devices", "1"], ["--spectral-devices", "1"],
+        ["--hero-wavelengths", "4"], ["--light-groups", "instance"], ["--denoise-light-groups", "instance"], ["--relamp-groups", "instance"], ["--light-group-devices", "1"])]
+    cases += [
+        (pp + ["--denoise"], "--path-passes cannot be combined with --denoise without --denoise-path-passes"),
+        (["--denoise-path-passes"], "--denoise-path-passes needs --path-passes and --denoise"),
+        (pp + ["--denoise-path-passes"], "--denoise-path-passes needs --path-passes and --denoise"),
+    ]
+    for args, message in cases:
+        r = subprocess.run([exe, "--config", "/nonexistent/config.toml"] + args, capture_output=True, text=True)
+        assert r.returncode == 2 and ("error: " + message) in r.stderr, (args, r.stderr)
+    assert "[--path-passes] [--denoise-path-passes]" in subprocess.run([exe, "--help"], capture_output=True, text=True).stderr
+    assert "[--path-passes] [--denoise-path-passes]" in open(os.path.join(CSRC, "host", "ptcli.cpp")).read().split("#include")[0]
+
+
+def test_ptcli_dry_run(pkg, tmp_path):
+    """A dry run with the flag loads the scene, names the eight passes and ends well, with and without the denoised passes."""
+    cfg = tmp_path / "config.toml"
+    cfg.write_text(scaled_c2_config(pkg))
+    base = [ptcli(pkg), "--root", pkg.PACKAGE_DIR, "--config", str(cfg), "--output-dir", str(tmp_path / "out"), "-n"]
+    for extra in ([], ["--denoise", "--denoise-path-passes"]):
+        ok = subprocess.run(base + ["--path-passes"] + extra, capture_output=True, text=True, cwd=str(tmp_path))
+        assert ok.returncode == 0 and "path passes: 8 (" + ", ".join(NAMES) + ")" in ok.stdout, (ok.stdout, ok.stderr)
+
+
+# ------------------------------------------------------------------------------------------------ GPU tier
+def clean_tuning(engine, pkg, batch_slots=0, flags=0):
+    t = engine.tuning_default()
+    t.flags &= ~(pkg.api.TUNE_NO_PASS_OVERLAP | pkg.api.TUNE_NO_LDS | pkg.api.TUNE_PASS_SKEW_MASK << pkg.api.TUNE_PASS_SKEW_SHIFT)   # (whatever the environment holds)
+    t.flags |= flags
+    t.batch_slots = batch_slots
+    return t
+
+
+@pytest.fixture(scope="module")
+def room_gpu(engine, pkg):
+    """The engine's renders of the room on one scene handle, made once: pt_render, the pass render at 5 bounces, pt_render again; the pass render at 2 and 1."""
+    rd = room_rd(pkg)
+    sc = engine.create_scene(pkg.scene.light_groups_room(), tuning=clean_tuning(engine, pkg))
+    before = sc.render(rd)
+    film, passes, prof = sc.render_path_passes(rd)
+    resident = sc.light_groups_resident()
+    identities = np.stack([np.eye(3, dtype=f32)] * 8)
+    mixed = sc.light_groups_mix_resident(identities)
+    after = sc.render(rd)
+    two = sc.render_path_passes(room_rd(pkg, 2))
+    one = sc.render_path_passes(room_rd(pkg, 1))
+    return {"scene": sc, "before": before, "after": after, "film": film, "passes": passes, "prof": prof, "two": two, "one": one, "resident": resident, "mixed": mixed,
+            "identities": identities}
+
+
+@pytest.mark.gpu
+def test_gpu_engine_is_the_emulation_and_pt_render(room_gpu, room_emu):
+    """Film, the eight pass films and the counters are the emulation's bit for bit; the film is pt_render's on the same handle, before and after."""
+    g, e = room_gpu, room_emu
+    assert same_bits(g["film"], g["before"][0]) and counters(g["prof"]) == counters(g["before"][1])
+    assert same_bits(g["before"][0], g["after"][0]) and counters(g["before"][1]) == counters(g["after"][1])
+    assert same_bits(g["film"], e["film"]) and counters(g["prof"]) == counters(e["prof"])
+    for c in range(8):
+        assert same_bits(g["passes"][c], e["passes"][c]), NAMES[c]
+    assert same_bits(g["two"][1], e["two"][1]) and same_bits(g["one"][1], e["one"][1])
+
+
+@pytest.mark.gpu
+def test_gpu_room_behind_the_pane_is_the_emulation(engine, pkg, pane_emu):
+    """scene.path_passes_room, where all eight classes are lit — direct transmission through the pane too, the one class whose rays carry class_b's bit: the
+    engine's film, pass films and counters are the emulation's bit for bit."""
+    film, passes, prof = engine.create_scene(pkg.scene.path_passes_room()).render_path_passes(room_rd(pkg))
+    assert same_bits(film, pane_emu["film"]) and counters(prof) == counters(pane_emu["prof"])
+    for c in range(8):
+        assert same_bits(passes[c], pane_emu["passes"][c]) and passes[c][..., :3].max() > 0, NAMES[c]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["overlap", "no_overlap", "no_lds"])
+def test_gpu_passes_and_tunings_keep_the_bits(engine, pkg, room_gpu, variant):
+    """pt_tuning::batch_slots 2048 cuts the render into at least seven passes, so both sets of pass buffers — each with a state plane of its own — are used more
+    than once and every pixel is continued by later passes; with the pass overlap, without it, and without LDS staging."""
+    flags = {"overlap": 0, "no_overlap": pkg.api.TUNE_NO_PASS_OVERLAP, "no_lds": pkg.api.TUNE_NO_LDS}[variant]
+    sc = engine.create_scene(pkg.scene.light_groups_room(), tuning=clean_tuning(engine, pkg, 2048, flags))
+    film, passes, prof = sc.render_path_passes(room_rd(pkg))
+    print("passes:", prof.kernel_launches[0])
+    assert prof.kernel_launches[0] >= 7
+    assert same_bits(film, room_gpu["film"]) and same_bits(passes, room_gpu["passes"]) and counters(prof) == counters(room_gpu["prof"])
+
+
+@pytest.mark.gpu
+def test_gpu_identities(engine, pkg, room_gpu):
+    """The truncation identity and the Lambertian-only zeros on the engine."""
+    truncation_identity(room_gpu["passes"], room_gpu["two"][1], room_gpu["one"][1])
+    lambertian_only(engine, pkg)
+
+
+def mix_numpy(films, m):
+    """pt_light_groups_mix's rule restated (tests/test_light_groups.py's)."""
+    films, m = np.asarray(films, f32), np.asarray(m, f32)
+    G, H, W, _ = films.shape
+    out = np.zeros((H, W, 4), f32)
+    for c in range(3):
+        acc = np.zeros((H, W), f32)
+        for g in range(G):
+            acc = acc + ((m[g, c, 0] * films[g, ..., 0] + m[g, c, 1] * films[g, ..., 1]) + m[g, c, 2] * films[g, ..., 2])
+        out[..., c] = acc
+    return out
+
+
+@pytest.mark.gpu
+def test_gpu_pass_films_are_resident_group_films(engine, pkg, room_gpu):
+    """pt_light_groups_resident reports 8 after a pass render; the resident mix with eight identities is pt_light_groups_mix of the films read back."""
+    g = room_gpu
+    assert g["resident"] == (24, 24, 8)
+    assert same_bits(g["mixed"], engine.light_groups_mix(g["passes"], g["identities"])) and same_bits(g["mixed"], mix_numpy(g["passes"], g["identities"]))
+    sc = g["scene"]
+    _, none, _ = sc.render_path_passes(room_rd(pkg, 2), read_passes=False)
+    assert none is None and sc.light_groups_resident() == (24, 24, 8)
+    assert same_bits(sc.light_groups_mix_resident(g["identities"]), mix_numpy(g["two"][1], g["identities"]))
+
+
+AD = dict(max_samples=40, rel_error=0.4, step=10)   # tests/test_light_groups_denoise.py's adaptive case
+
+
+def adaptive_rd(pkg, spp=10):
+    return pkg.api.render_desc(24, 24, spp, 5, light_samples=2, seed=7)
+
+
+@pytest.fixture(scope="module")
+def adaptive_gpu(engine, pkg):
+    rd = adaptive_rd(pkg)
+    sc = engine.create_scene(pkg.scene.light_groups_room(), tuning=clean_tuning(engine, pkg))
+    plain = sc.render_adaptive(rd, AD["max_samples"], AD["rel_error"], step=AD["step"], stats=True)
+    film, counts, stats, passes, prof = sc.render_adaptive_path_passes(rd, AD["max_samples"], AD["rel_error"], step=AD["step"], stats=True)
+    return {"rd": rd, "scene": sc, "plain": plain, "film": film, "counts": counts, "stats": stats, "passes": passes, "prof": prof}
+
+
+@pytest.mark.gpu
+def test_gpu_adaptive_entry(engine, pkg, adaptive_gpu):
+    """Film, counts and statistics are pt_render_adaptive's bit for bit; each pixel's passes are pt_render_path_passes' at that pixel's own count.  The input
+    condition is test_light_groups_denoise.py's: at least three distinct counts, each on at least 10 % of the pixels."""
+    g = adaptive_gpu
+    film, counts, stats, prof = g["plain"]
+    values, n = np.unique(g["counts"], return_counts=True)
+    print("counts:", dict(zip(values.tolist(), n.tolist())))
+    assert int((n >= 0.1 * g["counts"].size).sum()) >= 3
+    assert same_bits(g["film"], film) and np.array_equal(g["counts"], counts) and np.array_equal(g["stats"].view(np.uint64), stats.view(np.uint64))
+    assert counters(g["prof"]) == counters(prof) and g["prof"].kernel_launches[5] == prof.kernel_launches[5]
+    other = engine.create_scene(pkg.scene.light_groups_room())
+    for v in values:
+        ffilm, fpasses, _ = other.render_path_passes(adaptive_rd(pkg, int(v)))
+        at = g["counts"] == v
+        assert same_bits(g["film"][at], ffilm[at]), v
+        for c in range(8):
+            assert same_bits(g["passes"][c][at], fpasses[c][at]), (v, NAMES[c])
+    assert not g["passes"][..., 3].any() and np.isfinite(g["passes"]).all()
+
+
+@pytest.mark.gpu
+def test_gpu_resident_filter_follows_the_adaptive_entry(engine, pkg, adaptive_gpu):
+    """After the adaptive entry pt_denoise_light_groups_resident equals pt_denoise_light_groups over the host arrays, bit for bit."""
+    g = adaptive_gpu
+    sc, rd = g["scene"], g["rd"]
+    assert sc.light_groups_resident() == (24, 24, 8) and sc.resident_info()[3] & pkg.api.RESIDENT_FILM
+    sc.resident_guides(rd, 4)
+    host_guides = engine.create_scene(pkg.scene.light_groups_room()).render_guides(rd, 4)
+    den, var, den_passes = sc.denoise_light_groups_resident(variance=True)
+    want = engine.denoise_light_groups(g["film"], g["counts"], g["stats"], host_guides, g["passes"], variance=True)
+    assert same_bits(den, want[0]) and same_bits(den_passes, want[1]) and same_bits(var, want[2])
+    assert sc.light_groups_denoised_resident() == (24, 24, 8)
+
+
+@pytest.mark.gpu
+def test_gpu_adaptive_entry_refusals(engine, pkg):
+    """The adaptive entry refuses what either half refuses, each with its own message, before anything is rendered."""
+    a = pkg.api
+    sc = engine.create_scene(pkg.scene.light_groups_room())
+    ok = dict(width=8, height=8, spp=10, max_bounces=3)
+    for rd, args, status, word in ((a.render_desc(hero_wavelengths=4, **ok), (40, 0.1), a.PT_ERR_UNSUPPORTED, "path passes carry one wavelength"),
+                                   (a.render_desc(medium_aware=True, **ok), (40, 0.1), a.PT_ERR_UNSUPPORTED, "medium-aware"),
+                                   (a.render_desc(shard=(0, 2), **ok), (40, 0.1), a.PT_ERR_UNSUPPORTED, "whole film"),
+                                   (a.render_desc(**ok), (5, 0.1), a.PT_ERR_INVALID_ARGUMENT, "max_samples")):
+        with pytest.raises(a.PtError) as e:
+            sc.render_adaptive_path_passes(rd, *args)
+        assert e.value.status == status and word in str(e.value), str(e.value)
+    assert sc.light_groups_resident() is None
+
+
+@pytest.mark.gpu
+def test_gpu_ptcli_path_passes(pkg, tmp_path):
+    """ptcli --path-passes on the Cornell config writes the eight files; the usual outputs are byte for byte those of a run without the flag.  With --denoise
+    --denoise-path-passes the usual and the _denoised files are those of --denoise alone, beside the eight noisy and the eight denoised pass files."""
+    cfg = tmp_path / "config.toml"
+    cfg.write_text(scaled_c2_config(pkg))
+    base = [ptcli(pkg), "--root", pkg.PACKAGE_DIR, "--config", str(cfg)]
+
+    def run(out, *extra):
+        return subprocess.run(base + ["--output-dir", str(tmp_path / out)] + list(extra), capture_output=True, text=True, cwd=str(tmp_path), timeout=120)
+
+    def same_files(a, b, names):
+        return all(open(tmp_path / a / f, "rb").read() == open(tmp_path / b / f, "rb").read() for f in names)
+    plain, split = run("plain"), run("split", "--path-passes")
+    assert plain.returncode == 0 and split.returncode == 0, (plain.stderr, split.stderr)
+    usual = sorted(os.listdir(tmp_path / "plain"))
+    assert usual and same_files("plain", "split", usual)
+    extra = sorted(set(os.listdir(tmp_path / "split")) - set(usual))
+    stem = usual[0].rsplit(".", 1)[0]
+    assert extra == sorted("%s_pass_%s.exr" % (stem, n) for n in NAMES), extra
+    den, den_split = run("den", "--denoise"), run("den_split", "--denoise", "--path-passes", "--denoise-path-passes")
+    assert den.returncode == 0 and den_split.returncode == 0, (den.stderr, den_split.stderr)
+    den_usual = sorted(os.listdir(tmp_path / "den"))
+    assert set(usual) < set(den_usual) and same_files("den", "den_split", den_usual) and same_files("plain", "den", usual)
+    extra = sorted(set(os.listdir(tmp_path / "den_split")) - set(den_usual))
+    assert extra == sorted(["%s_pass_%s.exr" % (stem, n) for n in NAMES] + ["%s_denoised_pass_%s.exr" % (stem, n) for n in NAMES]), extra
+    assert same_files("split", "den_split", ["%s_pass_%s.exr" % (stem, n) for n in NAMES])

@@ -34,7 +34,7 @@
 #include "../../include/pt_light_groups_spectral.h"
 #include "pt_adaptive_select.h"
 #include "pt_light_groups_launch.h"
-#include "pt_path_passes_launch.h"
+#include "pt_routed_launch.h"
 #include "pt_light_groups_spectral_launch.h"
 #include "pt_spectral_launch.h"
 #include "pt_spectral_rules.h"
@@ -646,7 +646,7 @@ struct RenderJob {
     const LightGroupTable* groups = nullptr;
     float* d_group_films = nullptr;
     // pt_render_path_passes (its arguments checked; include/pt_light_groups.h): a group render of PP_CLASSES films whose vertex and light-sample forms route the
-    // energy by the path's own history (pt_kern_passes.hip) and keep a plane of state words behind the class planes; d_group_films as above, no table
+    // energy by the path's own history (PassRouter, pt_path_pass_rules.h) and keep a plane of state words behind the class planes; d_group_films as above, no table
     bool classes = false;
     // pt_render_light_groups_spectral (include/pt_light_groups_spectral.h): with groups and d_spectral, group_count * spectral_bins planes of width * height floats —
     // every pass also adds each group's plane to that group's bins
@@ -699,7 +699,7 @@ pt_status plan_render(const pt_scene* sc, const pt_render_desc& rd, const Render
     // the sweep table holds walked meshes: rays that reach one are parked and resumed in full waves (PT_AMD_NO_PARK=1: in line)
     const bool walks = (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_SWEEP_WALKS) != 0;
     const bool mesh_lights = sc->host.blob[PT_HDR_LIGHT_FACE_OFF] != 0u;   // (emissive mesh faces: PT_FORM_ANY, below)
-    const bool grouped = job.groups != nullptr || job.classes;   // (a light-group or path-pass render: PT_FORM_ANY and the FULL vertex form, whose siblings route the energy: pt_kern_groups.hip)
+    const bool grouped = job.groups != nullptr || job.classes;   // (a light-group or path-pass render: PT_FORM_ANY and the FULL vertex form, whose siblings route the energy: pt_kern_routed.hip)
     const bool parked = sweep && walks && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights && !grouped;
     // no sweep table (more than 64 instances, PT_AMD_NO_SWEEP): the top-level tree per lane, every mesh parked (top_walk_run, pt_device.h)
     const bool parked_walk = !sweep && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights && !grouped;
@@ -902,13 +902,16 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
         Queue qa, qb, qh, qs;
         uint32_t* live[2];         // per-segment live-path counts, ping-pong with the path queues
         uint32_t* nshadow;         // per-segment light-sample item counts; behind them (nshadow + grid) the counts of the live ones (Layout::shadow_live_field)
+        PassRouter pass_router;    // a path-pass render: the router over the set's state plane
         size_t marks;              // timing events recorded
         std::vector<int> stage;    // stage[k]: what the interval from event k to event k + 1 is charged to (-1: no stage)
     };
     auto make_lane = [&](DeviceBuffers& s, hipStream_t on, std::vector<hipEvent_t>* ev) {
         return Lane{&s, on, ev, Queue{s.paths_a, s.capacity, plan.path_fields}, Queue{s.paths_b, s.capacity, plan.path_fields}, Queue{s.hits, s.capacity, HS_FIELDS},
-                    Queue{s.shadow, s.capacity, plan.item_fields}, {s.counts, s.counts + grid}, s.counts + 2 * grid, 0, {}};
+                    Queue{s.shadow, s.capacity, plan.item_fields}, {s.counts, s.counts + grid}, s.counts + 2 * grid,
+                    PassRouter{job.classes ? pp_state_words(s.energy, s.capacity) : nullptr}, 0, {}};
     };
+    const GroupRouter group_router{job.groups ? *job.groups : LightGroupTable{nullptr, 0u, 0u}};
     Lane lanes[2] = {make_lane(b, stream, &sc->events), make_lane(overlap ? sc->buf2 : b, overlap ? sc->pass_stream : stream, &sc->events2)};
 
     HIP_TRY(hipStreamSynchronize(stream));
@@ -994,13 +997,13 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                 cfg.path_marks = (bounce > 0 && !rd.medium_aware && (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_CONVEX)) ? sc->host.blob[PT_HDR_CONVEX_INST] : 0u;
                 if (!cfg.fuse) timed(l, ST_EXTEND, [&] { launch_extend(cfg, trav_form, sargs, qin, qh, seg_cap, cin, b.park); });
                 if (park_dynamic) cfg.unit_counter = b.unit_counters + 2 * bounce + 1;
-                if (job.classes) {
-                    timed(l, ST_SHADE, [&] { launch_shade_passes(cfg, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats); });
-                    if (rd.light_samples > 0) timed(l, ST_SHADOW, [&] { launch_shadow_passes(cfg, sargs, rd.light_samples, qs, b.energy, b.capacity, seg_cap, nshadow); });
-                } else if (job.groups) {
-                    timed(l, ST_SHADE, [&] { launch_shade_groups(cfg, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats, *job.groups); });
-                    if (rd.light_samples > 0) timed(l, ST_SHADOW, [&] { launch_shadow_groups(cfg, sargs, rd.light_samples, qs, b.energy, b.capacity, seg_cap, nshadow, *job.groups); });
-                } else {
+                const auto routed = [&](const auto& router) {   // (a routed render's two forms: pt_kern_routed.hip)
+                    timed(l, ST_SHADE, [&] { launch_shade_routed(cfg, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats, router); });
+                    if (rd.light_samples > 0) timed(l, ST_SHADOW, [&] { launch_shadow_routed(cfg, sargs, rd.light_samples, qs, b.energy, b.capacity, seg_cap, nshadow, router); });
+                };
+                if (job.classes) routed(l.pass_router);
+                else if (job.groups) routed(group_router);
+                else {
                     timed(l, ST_SHADE, [&] { launch_shade(cfg, hero ? 4 : 1, shade_form, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats); });
                     if (rd.light_samples > 0)   // (shade_form FULL = the scene can produce environment rays)
                         timed(l, ST_SHADOW, [&] { launch_shadow(cfg, trav_form, hero ? 4 : 1, shade_form == PT_SHADE_FULL || shade_form == PT_SHADE_MEDIUM, sargs, rd.light_samples, qs, b.energy, b.capacity, rp.live_list ? (seg_cap | kShadowListed) : seg_cap, nshadow, b.park, qh); });
@@ -1147,8 +1150,7 @@ static pt_status scene_to_device(pt_scene* sc) {
         if (e == hipSuccess) e = allow_lds_shade(kLdsBlobLimitBytes > PT_SHADE_LDS_BUDGET ? kLdsBlobLimitBytes : PT_SHADE_LDS_BUDGET);   // (the FULL form's marginal tables ride behind the blob only within PT_SHADE_LDS_BUDGET)
         // (the parked light-sample kernels keep their waves' lists of live rays behind the blob: up to 16 waves x (64 L + 64) words)
         if (e == hipSuccess) e = allow_lds_shadow(kParkBlobLimitBytes + 16u * (64u * PT_MAX_LIGHT_SAMPLES + 64u) * 4u);
-        if (e == hipSuccess) e = allow_lds_groups(kLdsBlobLimitBytes > PT_SHADE_LDS_BUDGET ? kLdsBlobLimitBytes : PT_SHADE_LDS_BUDGET, kLdsBlobLimitBytes);
-        if (e == hipSuccess) e = allow_lds_passes(kLdsBlobLimitBytes > PT_SHADE_LDS_BUDGET ? kLdsBlobLimitBytes : PT_SHADE_LDS_BUDGET, kLdsBlobLimitBytes);
+        if (e == hipSuccess) e = allow_lds_routed(kLdsBlobLimitBytes > PT_SHADE_LDS_BUDGET ? kLdsBlobLimitBytes : PT_SHADE_LDS_BUDGET, kLdsBlobLimitBytes);
         if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(e));
     }
     return PT_OK;

@@ -1,20 +1,23 @@
-// pt_kern_groups.hip — the two kernel forms of a light-group render (include/pt_light_groups.h) and their launchers: siblings of
-// k_shade<M, 1, PT_SHADE_FULL, 0u> and k_shadow<M, 1, PT_TRAV_ANY, true, 0u> — the most general vertex and light-sample forms, one wavelength, unfused, no live
-// list — that also route every energy addition to the plane of its light group (pt_light_group_rules.h).  A translation unit of its own: no other kernel
-// family's device code knows of groups.
+// pt_kern_routed.hip — the two kernel forms of a routed render and their launchers: siblings of k_shade<M, 1, PT_SHADE_FULL, 0u> and
+// k_shadow<M, 1, PT_TRAV_ANY, true, 0u> — the most general vertex and light-sample forms, one wavelength, unfused, no live list — that also send every energy
+// addition to the plane their router names (pt_routed_rules.h): the light group's for a light-group render (include/pt_light_groups.h),
+// the path class's for a path-pass render (section 17).  A translation unit of its own: no other kernel family's device code knows of routers.
 #include <cstdio>
 #include <cstdlib>
 #include "pt_kernels.h"
-#include "pt_light_groups_launch.h"
+#include "pt_routed_launch.h"
 
 namespace ptk {
 
+// A router crosses the launch as its Arg (pt_routed_rules.h): a kernel argument of its own can be __restrict__, a struct's member cannot.
+
 // k_shade's FULL form (pt_kernels.h): the environment vertices of a wave's 64 items shaded at once, the surface vertices from the wave's list, 64 at a time.
-template <int USE_LDS>
+template <int USE_LDS, typename Router>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PT_SHADE_WAVES)))
-k_shade_groups(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* __restrict__ tex, RenderParams rp, uint32_t bounce, const uint32_t* __restrict__ pixels,
+k_shade_routed(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* __restrict__ tex, RenderParams rp, uint32_t bounce, const uint32_t* __restrict__ pixels,
                Queue paths_in, Queue hits, Queue paths_out, Queue shadow, float* __restrict__ energy, uint32_t seg_cap, const uint32_t* __restrict__ count_in,
-               uint32_t* __restrict__ count_out, uint32_t* __restrict__ shadow_count, unsigned long long* __restrict__ block_stats, LightGroupTable groups) {
+               uint32_t* __restrict__ count_out, uint32_t* __restrict__ shadow_count, unsigned long long* __restrict__ block_stats, typename Router::Arg router_arg) {
+    const Router router{router_arg};
     extern __shared__ __align__(16) uint32_t lds[];
     __shared__ uint32_t lds_counts[16];  // [0] path queue head, [1] item queue head, [4..6] statistics
     if (PT_EMPTY_SEGMENT_EXIT && count_in[blockIdx.x] == 0u) {
@@ -61,19 +64,8 @@ k_shade_groups(const uint32_t* __restrict__ blob, uint32_t blob_words, const flo
         const uint32_t ipos = base + shared_append(wants_item, &lds_counts[1]);
         ShadeOutT<1> out;
         out.survives = false; out.has_item = false; out.vertex_pushed = false; out.env_hit = false; out.shadow_count = 0; out.add_energy = false; out.env_mask = 0;
-        if (active) {
-            const uint32_t pixel = pixels[pv.slot % rp.chunk_pixels];
-            out = stage_shade<1, true, true>(s, rp, bounce, pv, hit, pixel, [&](uint32_t l, const ShadowRayT<1>& ray) { store_shadow_ray<1>(shadow, ipos, l, ray); });
-            if (wants_item) {
-                qsu(shadow, Layout<1>::sh_slot, ipos, pv.slot); qsu(shadow, Layout<1>::sh_flags, ipos, out.env_mask);
-                qsf(shadow, Layout<1>::sh_lambda, ipos, pv.lambda);
-                if (!out.has_item) clear_shadow_item<1>(shadow, ipos, rp.light_samples);
-            }
-            if (out.add_energy) {
-                energy[pv.slot] += out.energy_add[0];
-                lg_add_vertex(s, groups, hit, out.energy_add[0], energy, rp.energy_stride, pv.slot);
-            }
-        }
+        if (active)
+            out = routed_vertex(s, rp, router, bounce, pv, hit, pixels[pv.slot % rp.chunk_pixels], wants_item, shadow, ipos, energy, [](const typename Router::Vertex&, const Hit&) {});
         const uint32_t pos = base + shared_append(out.survives, &lds_counts[0]);
         if (out.survives) store_path<1>(paths_out, pos, out.next);
         st_vertices += out.vertex_pushed ? 1u : 0u; st_env += out.env_hit ? 1u : 0u; st_shadow += out.shadow_count;
@@ -91,39 +83,59 @@ k_shade_groups(const uint32_t* __restrict__ blob, uint32_t blob_words, const flo
 }
 
 // k_shadow's general form (pt_kernels.h): every item of the segment, no list of live ones
-template <int USE_LDS>
+template <int USE_LDS, typename Router>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PT_WALK_WAVES)))
-k_shadow_groups(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* __restrict__ tex, uint32_t light_samples, Queue shadow, float* __restrict__ energy,
-                uint32_t energy_stride, uint32_t seg_cap, const uint32_t* __restrict__ count_in, LightGroupTable groups) {
+k_shadow_routed(const uint32_t* __restrict__ blob, uint32_t blob_words, const float* __restrict__ tex, uint32_t light_samples, Queue shadow, float* __restrict__ energy,
+                uint32_t energy_stride, uint32_t seg_cap, const uint32_t* __restrict__ count_in, typename Router::Arg router_arg) {
+    const Router router{router_arg};
     extern __shared__ __align__(16) uint32_t lds[];
     if (PT_EMPTY_SEGMENT_EXIT && count_in[blockIdx.x] == 0u) return;
     SceneView s = stage_scene<USE_LDS, 0u>(blob, blob_words, tex, lds);
     const uint32_t base = blockIdx.x * seg_cap, n = count_in[blockIdx.x];
-    for (uint32_t j = threadIdx.x; j < n; j += blockDim.x) lg_shadow_item<PT_TRAV_ANY>(s, groups, light_samples, shadow, base + j, energy, energy_stride);
+    for (uint32_t j = threadIdx.x; j < n; j += blockDim.x) routed_shadow_item<PT_TRAV_ANY>(s, router, light_samples, shadow, base + j, energy, energy_stride);
 }
 
-#define PT_GROUPS_BY_MODE(cfg, K, ...) do { if (c.lds_mode == PT_LDS_ALL) go(cfg, K<PT_LDS_ALL>, __VA_ARGS__); else if (c.lds_mode == PT_LDS_CORE) go(cfg, K<PT_LDS_CORE>, __VA_ARGS__); \
-                                            else go(cfg, K<PT_LDS_NONE>, __VA_ARGS__); } while (0)
+// the kernel of the launch's staging mode (PT_LDS_*) among a form's three
+template <typename K, typename... Args>
+static void go_by_mode(const LaunchCfg& cfg, K all, K core, K none, Args... args) {
+    go(cfg, cfg.lds_mode == PT_LDS_ALL ? all : cfg.lds_mode == PT_LDS_CORE ? core : none, args...);
+}
 
-void launch_shade_groups(const LaunchCfg& c, const SceneArgs& sc, const RenderParams& rp, uint32_t bounce, const uint32_t* pixels, Queue paths_in, Queue hits, Queue paths_out,
+template <typename Router>
+void launch_shade_routed(const LaunchCfg& c, const SceneArgs& sc, const RenderParams& rp, uint32_t bounce, const uint32_t* pixels, Queue paths_in, Queue hits, Queue paths_out,
                          Queue shadow, float* energy, uint32_t seg_cap, const uint32_t* count_in, uint32_t* count_out, uint32_t* shadow_count, unsigned long long* block_stats,
-                         const LightGroupTable& groups) {
-    if (rp.camera_record == 0u || rp.live_list != 0u) { fprintf(stderr, "launch_shade_groups: the FULL form reads the camera vertex' lean record and builds no live list\n"); abort(); }
+                         const Router& router) {
+    if (rp.camera_record == 0u || rp.live_list != 0u) { fprintf(stderr, "launch_shade_routed: the FULL form reads the camera vertex' lean record and builds no live list\n"); abort(); }
     LaunchCfg d = c; d.lds_bytes = ((c.lds_bytes + 15u) & ~15u) + sc.marg_bytes;   // (the marginal tables of the importance map behind the blob: stage_marginal)
-    PT_GROUPS_BY_MODE(d, k_shade_groups, sc.blob, sc.blob_words, sc.tex, rp, bounce, pixels, paths_in, hits, paths_out, shadow, energy, seg_cap, count_in, count_out, shadow_count,
-                      block_stats, groups);
+    go_by_mode(d, k_shade_routed<PT_LDS_ALL, Router>, k_shade_routed<PT_LDS_CORE, Router>, k_shade_routed<PT_LDS_NONE, Router>, sc.blob, sc.blob_words, sc.tex, rp, bounce, pixels,
+               paths_in, hits, paths_out, shadow, energy, seg_cap, count_in, count_out, shadow_count, block_stats, router.arg());
 }
 
-void launch_shadow_groups(const LaunchCfg& c, const SceneArgs& sc, uint32_t light_samples, Queue shadow, float* energy, uint32_t energy_stride, uint32_t seg_cap,
-                          const uint32_t* count_in, const LightGroupTable& groups) {
-    PT_GROUPS_BY_MODE(c, k_shadow_groups, sc.blob, sc.blob_words, sc.tex, light_samples, shadow, energy, energy_stride, seg_cap, count_in, groups);
+template <typename Router>
+void launch_shadow_routed(const LaunchCfg& c, const SceneArgs& sc, uint32_t light_samples, Queue shadow, float* energy, uint32_t energy_stride, uint32_t seg_cap,
+                          const uint32_t* count_in, const Router& router) {
+    go_by_mode(c, k_shadow_routed<PT_LDS_ALL, Router>, k_shadow_routed<PT_LDS_CORE, Router>, k_shadow_routed<PT_LDS_NONE, Router>, sc.blob, sc.blob_words, sc.tex, light_samples,
+               shadow, energy, energy_stride, seg_cap, count_in, router.arg());
 }
 
-hipError_t allow_lds_groups(uint32_t shade_bytes, uint32_t shadow_bytes) {
+#define PT_ROUTED_LAUNCHERS(Router) \
+    template void launch_shade_routed<Router>(const LaunchCfg&, const SceneArgs&, const RenderParams&, uint32_t, const uint32_t*, Queue, Queue, Queue, Queue, float*, uint32_t, \
+                                              const uint32_t*, uint32_t*, uint32_t*, unsigned long long*, const Router&); \
+    template void launch_shadow_routed<Router>(const LaunchCfg&, const SceneArgs&, uint32_t, Queue, float*, uint32_t, uint32_t, const uint32_t*, const Router&);
+PT_ROUTED_LAUNCHERS(GroupRouter)
+PT_ROUTED_LAUNCHERS(PassRouter)
+
+template <typename Router>
+static void allow_lds_router(uint32_t shade_bytes, uint32_t shadow_bytes, hipError_t* worst) {
+    auto allow = [&](const void* k, uint32_t bytes) { hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); if (e != hipSuccess) *worst = e; };
+    allow(reinterpret_cast<const void*>(k_shade_routed<PT_LDS_ALL, Router>), shade_bytes); allow(reinterpret_cast<const void*>(k_shade_routed<PT_LDS_CORE, Router>), shade_bytes);
+    allow(reinterpret_cast<const void*>(k_shadow_routed<PT_LDS_ALL, Router>), shadow_bytes); allow(reinterpret_cast<const void*>(k_shadow_routed<PT_LDS_CORE, Router>), shadow_bytes);
+}
+
+hipError_t allow_lds_routed(uint32_t shade_bytes, uint32_t shadow_bytes) {
     hipError_t worst = hipSuccess;
-    auto allow = [&](const void* k, uint32_t bytes) { hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); if (e != hipSuccess) worst = e; };
-    allow(reinterpret_cast<const void*>(k_shade_groups<PT_LDS_ALL>), shade_bytes); allow(reinterpret_cast<const void*>(k_shade_groups<PT_LDS_CORE>), shade_bytes);
-    allow(reinterpret_cast<const void*>(k_shadow_groups<PT_LDS_ALL>), shadow_bytes); allow(reinterpret_cast<const void*>(k_shadow_groups<PT_LDS_CORE>), shadow_bytes);
+    allow_lds_router<GroupRouter>(shade_bytes, shadow_bytes, &worst);
+    allow_lds_router<PassRouter>(shade_bytes, shadow_bytes, &worst);
     return worst;
 }
 

@@ -1,6 +1,6 @@
 // pt_light_group_rules.h — the rules of light groups (include/pt_light_groups.h) as PT_HD functions that the kernels
-// (pt_kern_groups.hip, pt_light_groups.hip) and the host emulation of the tests (tests/host_emulation/ptemu_light_groups.cpp) all compile: one text, so they
-// agree bit for bit.  All f32, no contraction, in the order written.
+// (pt_kern_routed.hip through GroupRouter, below; pt_light_groups.hip) and the host emulation of the tests (tests/host_emulation/) all compile: one
+// text, so they agree bit for bit.  All f32, no contraction, in the order written.
 //
 // Planes of a pass's energy buffer: 0 the total, 1 the stored wavelength samples (both as every render has them), 2 + g the energy of group g.  Every
 // addition to a sample's energy goes to the total plane as it always did and to the plane of exactly ONE group: the group of the instance a light vertex or
@@ -8,12 +8,13 @@
 //
 // A light-sample item: group g's share is the sum, in ray order, of the contributions of the rays that belong to g, divided by light_samples — the rule of
 // stage_shadow_item applied to each group's own terms.  A ray's contribution is folded into the accumulator of its group alone; the other accumulators are
-// left as they are (lg_item_fold: a select over a compile-time index, so the eight accumulators are registers and no array is indexed at run time).
+// left as they are (lg_item_fold: a select over a compile-time index, so the eight accumulators are registers and no array is indexed at run time).  The group
+// is that of the closest hit's instance when that hit is a light, the environment's otherwise.  The ray loop itself is routed_shadow_item (pt_routed_rules.h).
 //
 // The mix: out_c(p) = fold over g ascending of acc_c = acc_c + ((M[g][c][0] * X_g + M[g][c][1] * Y_g) + M[g][c][2] * Z_g), from acc_c = 0.0f; w = 0.
 #ifndef PT_LIGHT_GROUP_RULES_H
 #define PT_LIGHT_GROUP_RULES_H
-#include "pt_stages.h"
+#include "pt_routed_rules.h"
 
 namespace ptd {
 
@@ -49,39 +50,33 @@ PT_HD void lg_item_add(const float (&sums)[LG_MAX_GROUPS], const LightGroupTable
         if (g < t.group_count) energy[(size_t)lg_plane(g) * energy_stride + slot] += sums[g] / (float)light_samples;
 }
 
-// One light-sample item of a group render: stage_shadow_item<1, TRAV, true> — the same rays, searches and total — with every ray's contribution folded into its
-// group's sum too.  The group is read where the contribution is made: from the closest hit's instance when that hit is a light, the environment's otherwise
-// (an environment ray that escaped; a ray that adds 0.0f adds it to that group, which changes no sum).
+// Light groups: the plane of the group of the instance a light vertex or a light-sample ray hit, the environment's group otherwise (the rules above).
+struct GroupRouter {
+    LightGroupTable t;
+    typedef LightGroupTable Arg;
+    PT_ROUTER_FN Arg arg() const { return t; }
+    struct Vertex {};
+    struct Item { float sums[LG_MAX_GROUPS]; };
+    PT_ROUTER_FN Vertex vertex(const SceneView&, uint32_t, uint32_t, const Hit&) const { return Vertex{}; }
+    PT_ROUTER_FN void ray(Vertex&, const Hit&, F3, uint32_t, F3) const {}
+    PT_ROUTER_FN void add_vertex(const SceneView& s, const Vertex&, const Hit& hit, float add, float* energy, uint32_t energy_stride, uint32_t slot) const {
+        lg_add_vertex(s, t, hit, add, energy, energy_stride, slot);
+    }
+    PT_ROUTER_FN void leave(const Vertex&, const Hit&, F3, bool, F3, uint32_t) const {}
+    PT_ROUTER_FN Item item(uint32_t) const { Item it; lg_item_clear(it.sums); return it; }
+    // (a ray that adds 0.0f adds it to the environment's group, which changes no sum)
+    PT_ROUTER_FN void fold(const SceneView& s, Item& it, uint32_t, bool lit, uint32_t lit_instance, float c) const {
+        lg_item_fold(it.sums, lit ? lg_hit_group(s, t, true, lit_instance) : t.environment_group, c);
+    }
+    PT_ROUTER_FN void add(const Item& it, uint32_t light_samples, float* energy, uint32_t energy_stride, uint32_t slot) const {
+        lg_item_add(it.sums, t, light_samples, energy, energy_stride, slot);
+    }
+};
+
+// One light-sample item of a group render by its earlier name and arguments: the previous revision's emulation sources compile against this header
 template <int TRAV = PT_TRAV_ANY>
 PT_HD void lg_shadow_item(const SceneView& s, const LightGroupTable& t, uint32_t light_samples, const Queue& shadow, uint32_t item, float* energy, uint32_t energy_stride) {
-    const bool marks = TRAV != PT_TRAV_SWEEP && scene_has_certificates(s);
-    const uint32_t slot = qu(shadow, Layout<1>::sh_slot, item), flags = qu(shadow, Layout<1>::sh_flags, item);
-    const float lambda0 = qf(shadow, Layout<1>::sh_lambda, item);
-    float lc = 0.0f, sums[LG_MAX_GROUPS];
-    lg_item_clear(sums);
-    for (uint32_t l = 0; l < light_samples; ++l) {
-        ShadowRayT<1> ray;
-        if (!load_shadow_ray<1, false>(shadow, item, l, &ray)) continue;
-        const bool env = ((flags >> l) & 1u) != 0u;
-        const uint32_t skip_inst = (marks && ((flags >> (8u + l)) & 1u) != 0u) ? flags >> 16 : 0xffffffffu;
-        float c[1] = {0.0f};
-        uint32_t group = t.environment_group;
-        float bound = PT_INF; int stop = PT_STOP_NONE;
-        uint32_t light = 0xffffffffu;
-        bool search = true;
-        if (env) stop = shadow_env_stop(s);
-        else search = shadow_light_bound(s, ray.o, ray.d, &bound, &stop, &light);
-        if (search) {
-            Hit sh;
-            const bool hit = world_hit<TRAV, true>(s, ray.o, ray.d, &sh, bound, stop, light, bound, skip_inst);
-            shadow_ray_contribution<1>(s, [&](int) { return lambda0; }, ray, env, hit, sh, c);
-            if (!env && hit && PT_MATERIAL_TAG(sh.material) == PT_TAG_LIGHT) group = lg_hit_group(s, t, true, sh.instance);
-        }
-        lc += c[0];
-        lg_item_fold(sums, group, c[0]);
-    }
-    energy[slot] += lc / (float)light_samples;
-    lg_item_add(sums, t, light_samples, energy, energy_stride, slot);
+    routed_shadow_item<TRAV>(s, GroupRouter{t}, light_samples, shadow, item, energy, energy_stride);
 }
 
 // Group g's film pixel from group g's plane: stage_accumulate_pixel as it is, with the wavelength samples read where every render keeps them.

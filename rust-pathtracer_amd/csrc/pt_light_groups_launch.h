@@ -1,19 +1,11 @@
-// pt_light_groups_launch.h — launchers of a light-group render's kernels (include/pt_light_groups.h): the vertex and light-sample forms that
-// route energy to group planes (pt_kern_groups.hip), the per-group accumulate kernel and the mix (pt_light_groups.hip).
+// pt_light_groups_launch.h — launchers of what lies behind a routed render's vertex and light-sample forms (pt_routed_launch.h), for light groups and path passes
+// alike (include/pt_light_groups.h, DESIGN.md sections 15 and 17): the per-group accumulate kernel, the adaptive finish and the mix (pt_light_groups.hip).
 #ifndef PT_LIGHT_GROUPS_LAUNCH_H
 #define PT_LIGHT_GROUPS_LAUNCH_H
 #include "pt_launch.h"
 #include "pt_light_group_rules.h"
 
 namespace ptk {
-
-// launch_shade's FULL form, one wavelength, unfused, and launch_shadow's general form, each with `groups` (instance_group: device memory, one byte per instance)
-void launch_shade_groups(const LaunchCfg& c, const SceneArgs& sc, const ptd::RenderParams& rp, uint32_t bounce, const uint32_t* pixels, ptd::Queue paths_in, ptd::Queue hits,
-                         ptd::Queue paths_out, ptd::Queue shadow, float* energy, uint32_t seg_cap, const uint32_t* count_in, uint32_t* count_out, uint32_t* shadow_count,
-                         unsigned long long* block_stats, const ptd::LightGroupTable& groups);
-void launch_shadow_groups(const LaunchCfg& c, const SceneArgs& sc, uint32_t light_samples, ptd::Queue shadow, float* energy, uint32_t energy_stride, uint32_t seg_cap,
-                          const uint32_t* count_in, const ptd::LightGroupTable& groups);
-hipError_t allow_lds_groups(uint32_t shade_bytes, uint32_t shadow_bytes);
 
 // group g's film (group_films + g * 4 * film_pixels floats) += the pass's samples of plane 2 + g, every pixel by lg_accumulate_pixel
 hipError_t launch_accumulate_groups(hipStream_t stream, const ptd::RenderParams& rp, const uint32_t* pixels, const float* energy, float* group_films, uint32_t group_count,

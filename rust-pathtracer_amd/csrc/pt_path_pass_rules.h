@@ -1,6 +1,6 @@
-// pt_path_pass_rules.h — the rules of path passes (include/pt_light_groups.h) as PT_HD functions that the kernels (pt_kern_passes.hip)
-// and the host emulation of the tests (tests/host_emulation/ptemu_path_passes.cpp) both compile: one text, so they agree bit for bit.  All f32, no
-// contraction, in the order written.
+// pt_path_pass_rules.h — the rules of path passes (include/pt_light_groups.h) as PT_HD functions that the kernels (pt_kern_routed.hip
+// through PassRouter, below) and the host emulation of the tests (tests/host_emulation/ptemu_path_passes.cpp) both compile: one text, so they agree
+// bit for bit.  All f32, no contraction, in the order written.
 //
 // A pass render is a group render whose group is a function of the path's own history: planes 2 + c of a pass's energy buffer (pt_light_group_rules.h) hold
 // the eight classes in the order of PT_PATH_PASS_*, and everything behind the render — k_accumulate_groups, the resident group films, the mix, the joint
@@ -89,36 +89,41 @@ PT_HD void pp_item_add(uint32_t word, float sum_a, float sum_b, uint32_t light_s
     if (b != a) energy[(size_t)lg_plane(b) * energy_stride + slot] += sum_b / (float)light_samples;
 }
 
-// One light-sample item of a pass render: lg_shadow_item's rays, searches and total, with every ray's contribution folded into the sum of its class — two
-// sums, each in ray order — and each sum / light_samples added to its class's plane (the rule of stage_shadow_item applied to each class's own terms).
+
+// Path passes: the plane of the class of the path's own history (the rules above).  `state`: the pass's state plane, one word per slot (pp_state_words).
+struct PassRouter {
+    uint32_t* state;
+    typedef uint32_t* __restrict__ Arg;   // (no other pointer of the kernels reaches the state plane)
+    PT_ROUTER_FN Arg arg() const { return state; }
+    struct Vertex { uint32_t d, k; bool diffuse; uint32_t word; };   // the state in front of the vertex, the kind of its material, the item word the rays fill
+    struct Item { uint32_t word; float sum_a, sum_b; };
+    PT_ROUTER_FN Vertex vertex(const SceneView& s, uint32_t bounce, uint32_t slot, const Hit& hit) const {
+        const uint32_t before = bounce == 0u ? 0u : state[slot];   // (the camera vertex: d = 0, nothing read)
+        Vertex v;
+        v.d = pp_state_d(before); v.k = pp_state_k(before);
+        v.diffuse = hit.valid ? pp_kind_is_diffuse(bu(s, material_record(s, hit.material) + PT_MAT_KIND)) : true;
+        v.word = pp_item_classes(v.d, v.k, v.diffuse);
+        return v;
+    }
+    PT_ROUTER_FN void ray(Vertex& v, const Hit& hit, F3 in_d, uint32_t l, F3 ray_d) const { v.word |= pp_item_ray_bit(v.d, v.diffuse, hit.n, in_d, l, ray_d); }
+    PT_ROUTER_FN void add_vertex(const SceneView&, const Vertex& v, const Hit& hit, float add, float* energy, uint32_t energy_stride, uint32_t slot) const {
+        pp_add_vertex(v.d, v.k, hit.valid, add, energy, energy_stride, slot);
+    }
+    PT_ROUTER_FN void leave(const Vertex& v, const Hit& hit, F3 in_d, bool survives, F3 next_d, uint32_t slot) const {
+        if (hit.valid) state[slot] = v.word | (survives ? pp_next_state(v.d, v.k, pp_event_kind(v.diffuse, hit.n, in_d, next_d)) : 0u);
+    }
+    PT_ROUTER_FN Item item(uint32_t slot) const { return Item{state[slot], 0.0f, 0.0f}; }
+    PT_ROUTER_FN void fold(const SceneView&, Item& it, uint32_t l, bool, uint32_t, float c) const { pp_item_fold(it.word, l, c, &it.sum_a, &it.sum_b); }
+    PT_ROUTER_FN void add(const Item& it, uint32_t light_samples, float* energy, uint32_t energy_stride, uint32_t slot) const {
+        pp_item_add(it.word, it.sum_a, it.sum_b, light_samples, energy, energy_stride, slot);
+    }
+};
+
+// One light-sample item of a pass render by its earlier name and arguments (the item only reads the state plane, hence the cast): the previous revision's
+// emulation sources compile against this header
 template <int TRAV = PT_TRAV_ANY>
 PT_HD void pp_shadow_item(const SceneView& s, uint32_t light_samples, const Queue& shadow, uint32_t item, float* energy, uint32_t energy_stride, const uint32_t* state) {
-    const bool marks = TRAV != PT_TRAV_SWEEP && scene_has_certificates(s);
-    const uint32_t slot = qu(shadow, Layout<1>::sh_slot, item), flags = qu(shadow, Layout<1>::sh_flags, item);
-    const float lambda0 = qf(shadow, Layout<1>::sh_lambda, item);
-    const uint32_t word = state[slot];
-    float lc = 0.0f, sum_a = 0.0f, sum_b = 0.0f;
-    for (uint32_t l = 0; l < light_samples; ++l) {
-        ShadowRayT<1> ray;
-        if (!load_shadow_ray<1, false>(shadow, item, l, &ray)) continue;
-        const bool env = ((flags >> l) & 1u) != 0u;
-        const uint32_t skip_inst = (marks && ((flags >> (8u + l)) & 1u) != 0u) ? flags >> 16 : 0xffffffffu;
-        float c[1] = {0.0f};
-        float bound = PT_INF; int stop = PT_STOP_NONE;
-        uint32_t light = 0xffffffffu;
-        bool search = true;
-        if (env) stop = shadow_env_stop(s);
-        else search = shadow_light_bound(s, ray.o, ray.d, &bound, &stop, &light);
-        if (search) {
-            Hit sh;
-            const bool hit = world_hit<TRAV, true>(s, ray.o, ray.d, &sh, bound, stop, light, bound, skip_inst);
-            shadow_ray_contribution<1>(s, [&](int) { return lambda0; }, ray, env, hit, sh, c);
-        }
-        lc += c[0];
-        pp_item_fold(word, l, c[0], &sum_a, &sum_b);
-    }
-    energy[slot] += lc / (float)light_samples;
-    pp_item_add(word, sum_a, sum_b, light_samples, energy, energy_stride, slot);
+    routed_shadow_item<TRAV>(s, PassRouter{const_cast<uint32_t*>(state)}, light_samples, shadow, item, energy, energy_stride);
 }
 
 }  // namespace ptd

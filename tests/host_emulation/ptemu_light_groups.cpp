@@ -1,17 +1,12 @@
 // ptemu_light_groups.cpp — TEST HARNESS: light groups (include/pt_light_groups.h) on the CPU.  Linked into the emulation library beside
 // ptemu.cpp (tests/test_light_groups.py builds it); not part of the product.
 //
-// ptemu_render_light_groups is ptemu.cpp's render loop for one wavelength and the plain walk — the vertex form the engine's group render takes, FULL — with the
-// engine's own routing text (pt_light_group_rules.h): the total plane receives every addition as ptemu_render's does, each group's plane its own.
+// ptemu_render_light_groups is the routed render's pass loop (ptemu_routed_pass.h) under the engine's GroupRouter (csrc/pt_routed_rules.h,
+// pt_light_group_rules.h): the total plane receives every addition as ptemu_render's does, each group's plane its own.
 // ptemu_light_groups_mix runs the mix rule, and the argument checks are pt_plan.cpp's, the ones the engine runs.
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "../../rust-pathtracer_amd/csrc/pt_plan.h"
-#include "../../rust-pathtracer_amd/csrc/pt_scene_host.h"
-#include "../../rust-pathtracer_amd/csrc/pt_light_group_rules.h"
+#include "ptemu_routed_pass.h"
 #include "../../include/pt_light_groups.h"
 
 using namespace ptd;
@@ -29,7 +24,7 @@ pt_status ptemu_render_light_groups(pt_scene* sc, const pt_render_desc* rdp, con
     if (checked != PT_OK) return checked;
     pt_render_desc rd;
     if (!pth::normalize_render_desc(*rdp, (uint32_t)sc->host.cameras.size(), &rd, &g_groups_error)) return PT_ERR_INVALID_ARGUMENT;
-    const LightGroupTable table{gd->instance_group, gd->environment_group, gd->group_count};
+    const GroupRouter router{LightGroupTable{gd->instance_group, gd->environment_group, gd->group_count}};
     const uint32_t G = gd->group_count;
     const size_t film_pixels = (size_t)rd.width * rd.height;
     SceneView s{sc->host.blob.data(), sc->host.tex.data(), sc->host.blob.data() + sc->host.blob[PT_HDR_CORE_WORDS]};
@@ -38,84 +33,13 @@ pt_status ptemu_render_light_groups(pt_scene* sc, const pt_render_desc* rdp, con
     if (!group_films) { own_group_films.resize(4 * film_pixels * G); group_films = own_group_films.data(); }
     std::memset(film, 0, sizeof(float) * 4 * film_pixels);
     std::memset(group_films, 0, sizeof(float) * 4 * film_pixels * G);
-    uint32_t capacity = 1u << 16;   // (ptemu_render's, and its switch)
-    if (const char* cap_env = getenv("PTEMU_BATCH")) capacity = (uint32_t)strtoul(cap_env, nullptr, 10);
-    RenderParams rp;
-    std::memset(&rp, 0, sizeof(rp));
-    rp.seed = rd.seed; rp.width = rd.width; rp.height = rd.height;
-    rp.min_bounces = rd.min_bounces; rp.max_bounces = rd.max_bounces; rp.light_samples = rd.light_samples; rp.only_direct = rd.only_direct;
-    rp.wavelength_lo = rd.wavelength_lo; rp.wavelength_span = rd.wavelength_hi - rd.wavelength_lo;
-    rp.spp = rd.spp; rp.range_end = rd.first_sample + rd.sample_count;
+    ptemu_routed::Buffers b(G);
+    RenderParams rp = ptemu_routed::render_params(sc->host, rd, b.capacity);
+    rp.spp = rd.spp;
     rp.normalize = 1u;   // (the whole sample range: check_light_groups_args)
-    rp.phase = rd.phase_samples;
-    rp.energy_stride = capacity;
-    rp.camera = pth::camera_params(sc->host.cameras[rd.camera_index], (float)rd.width / (float)rd.height);
-    rp.camera_record = 1u;
-    typedef Layout<1> LY;
-    const size_t cap64 = ((size_t)capacity + 63u) & ~(size_t)63u;
-    std::vector<uint32_t> pa((size_t)LY::path_fields * cap64), pb((size_t)LY::path_fields * cap64), ph((size_t)HS_FIELDS * cap64),
-        psh((size_t)LY::shadow_fields(PT_MAX_LIGHT_SAMPLES) * cap64);
-    std::vector<float> energy((size_t)lg_planes(G) * capacity);
-    Queue qa{pa.data(), capacity, LY::path_fields}, qb{pb.data(), capacity, LY::path_fields}, qh{ph.data(), capacity, HS_FIELDS}, qs{psh.data(), capacity, LY::shadow_fields(PT_MAX_LIGHT_SAMPLES)};
-    uint64_t bounce_rays = 0, shadow_rays = 0, env_hits = 0, camera_rays = 0;
-    const uint32_t bounce_limit = rd.only_direct ? 1u : rd.max_bounces;
-    const bool certs = (bu(s, PT_HDR_FLAGS) & PT_FLAG_CONVEX) && bu(s, PT_HDR_CONVEX_INST) != 0u;
-    for (const pth::Pass& pass : pth::plan_passes((uint32_t)pixels.size(), rd.first_sample, rd.sample_count, capacity, rd.phase_samples)) {
-        rp.chunk_pixels = pass.pixel_count; rp.first_sample = pass.first_sample; rp.pass_samples = pass.sample_count;
-        const uint32_t* px = pixels.data() + pass.pixel_begin;
-        const uint32_t n = pass.pixel_count * pass.sample_count;
-        camera_rays += n;
-        for (uint32_t i = 0; i < n; ++i) {
-            float u = 0.0f;
-            const PathVertexT<1> pg = stage_generate<1>(rp, i, px[i % rp.chunk_pixels], &u);
-            store_path_camera<1>(qa, i, pg);
-            energy[i] = 0.0f; energy[(size_t)capacity + i] = u;
-            for (uint32_t g = 0; g < G; ++g) energy[(size_t)lg_plane(g) * capacity + i] = 0.0f;
-        }
-        uint32_t live = n;
-        for (uint32_t bounce = 0; bounce < bounce_limit; ++bounce) {
-            Queue qin = (bounce & 1) ? qb : qa, qout = (bounce & 1) ? qa : qb;
-            for (uint32_t i = 0; i < live; ++i) {
-                Hit h;
-                const bool marked = bounce > 0 && certs && qf(qin, PS_PREV_PDF, i) < 0.0f;
-                const bool inside = bounce > 0 && certs && (qu(qin, PS_SLOT, i) & PT_PATH_INSIDE_MARK) != 0u;
-                world_hit(s, f3(qf(qin, PS_OX, i), qf(qin, PS_OY, i), qf(qin, PS_OZ, i)), f3(qf(qin, PS_DX, i), qf(qin, PS_DY, i), qf(qin, PS_DZ, i)), &h, PT_INF, PT_STOP_NONE, 0xffffffffu, 0.0f,
-                          marked ? bu(s, PT_HDR_CONVEX_INST) - 1u : 0xffffffffu, inside ? bu(s, PT_HDR_CONVEX_INST) - 1u : 0xffffffffu);
-                store_hit(qh, i, h);
-            }
-            uint32_t next = 0, items = 0;
-            for (uint32_t i = 0; i < live; ++i) {
-                PathVertexT<1> pv = load_path<1>(qin, i, bounce == 0u);
-                if (bounce > 0) pv.slot &= ~PT_PATH_INSIDE_MARK;
-                const Hit hit = load_hit(qh, i);
-                const bool wants = shade_wants_item(s, rp, hit);
-                const uint32_t ipos = items;
-                const ShadeOutT<1> out = stage_shade<1, true, true>(s, rp, bounce, pv, hit, px[pv.slot % rp.chunk_pixels],
-                                                                    [&](uint32_t l, const ShadowRayT<1>& ray) { store_shadow_ray<1>(qs, ipos, l, ray); });
-                if (wants) {
-                    items++;
-                    qsu(qs, LY::sh_slot, ipos, pv.slot); qsu(qs, LY::sh_flags, ipos, out.env_mask); qsf(qs, LY::sh_lambda, ipos, pv.lambda);
-                    if (!out.has_item) clear_shadow_item<1>(qs, ipos, rp.light_samples);
-                }
-                if (out.add_energy) {
-                    energy[pv.slot] += out.energy_add[0];
-                    lg_add_vertex(s, table, hit, out.energy_add[0], energy.data(), capacity, pv.slot);
-                }
-                if (out.survives) store_path<1>(qout, next++, out.next);
-                bounce_rays += out.vertex_pushed; env_hits += out.env_hit; shadow_rays += out.shadow_count;
-            }
-            for (uint32_t i = 0; i < items; ++i) lg_shadow_item<PT_TRAV_ANY>(s, table, rp.light_samples, qs, i, energy.data(), capacity);
-            live = next;
-        }
-        for (uint32_t p = 0; p < rp.chunk_pixels; ++p) {
-            stage_accumulate_pixel<1>(rp, energy.data(), p, px[p], film + 4 * (size_t)px[p]);
-            for (uint32_t g = 0; g < G; ++g) lg_accumulate_pixel(rp, energy.data(), g, p, px[p], group_films + 4 * ((size_t)g * film_pixels + px[p]));
-        }
-    }
-    if (profile) {
-        std::memset(profile, 0, sizeof(*profile));
-        profile->camera_rays = camera_rays; profile->bounce_rays = bounce_rays + camera_rays; profile->shadow_rays = shadow_rays; profile->env_hits = env_hits;
-    }
+    ptemu_routed::routed_passes(s, rp, router, rd, pixels.data(), (uint32_t)pixels.size(), rd.first_sample, rd.sample_count, b, film, group_films, film_pixels, nullptr,
+                                ptemu_routed::Nothing{}, ptemu_routed::Nothing{});
+    if (profile) b.profile(profile);
     return PT_OK;
 }
 

@@ -2,7 +2,7 @@
 
 The oracle of a group film is a render the parity suite already judges: group g's film is pt_render of the same scene with every emitter outside g emitting a
 zero curve (scene.light_groups_room(emit=...)), bit for bit, because the walk never looks at an emission value.  The CPU tier checks the host emulation
-(tests/host_emulation/ptemu_light_groups.cpp: ptemu.cpp's render loop with the engine's routing text) against ptemu_render and against the oracle of the masked
+(tests/host_emulation/ptemu_light_groups.cpp: the routed render's pass loop, ptemu_routed_pass.h, with the engine's GroupRouter) against ptemu_render and against the oracle of the masked
 scenes, the mix rule against a numpy restatement, every refusal, the header and the command line; the GPU tier checks the engine against its own pt_render of
 the masked scenes, against the emulation, under pass overlap, and the two mix entries."""
 import ctypes as C
@@ -49,7 +49,8 @@ def emu_lg(pkg):
     """The host emulation (ptemu.cpp) with the light-group render and mix (ptemu_light_groups.cpp) beside it: a library of its own."""
     lib = os.path.join(EMU_DIR, "libptemu_light_groups.so")
     srcs = [os.path.join(EMU_DIR, "ptemu.cpp"), os.path.join(EMU_DIR, "ptemu_light_groups.cpp"), os.path.join(CSRC, "pt_scene_host.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_light_group_rules.h")] + \
+    deps = srcs + [os.path.join(EMU_DIR, "ptemu_routed_pass.h")] + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_light_group_rules.h",
+                                                                                                    "pt_path_pass_rules.h", "pt_routed_rules.h")] + \
         [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_debug.h", "pt_numerics.h", "pt_light_groups.h")]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-Wno-unknown-pragmas",

@@ -48,9 +48,10 @@ def emu(pkg):
     srcs = [os.path.join(EMU_DIR, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_light_groups.cpp", "ptemu_adaptive_light_groups.cpp", "ptemu_denoise.cpp",
                                                "ptemu_denoise_albedo.cpp", "ptemu_guides_chain.cpp", "ptemu_denoise_spectral.cpp", "ptemu_denoise_spectral_albedo.cpp",
                                                "ptemu_denoise_light_groups.cpp")] + [os.path.join(CSRC, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_adaptive_select.h", "pt_denoise_rules.h",
+    deps = srcs + [os.path.join(EMU_DIR, "ptemu_routed_pass.h")] + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_adaptive_select.h", "pt_denoise_rules.h",
                                                    "pt_guides_chain_rules.h", "pt_denoise_spectral_rules.h", "pt_denoise_spectral_albedo_rules.h",
-                                                   "pt_denoise_resident_rules.h", "pt_denoise_light_groups_rules.h", "pt_light_group_rules.h")] + \
+                                                   "pt_denoise_resident_rules.h", "pt_denoise_light_groups_rules.h", "pt_light_group_rules.h", "pt_path_pass_rules.h",
+                                                   "pt_routed_rules.h")] + \
         [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_denoise.h", "pt_spectral.h", "pt_numerics.h", "pt_light_groups.h",
                                                     "pt_light_groups_denoise.h", "pt_resident.h")]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):

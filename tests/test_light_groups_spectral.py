@@ -43,7 +43,8 @@ def emu_lgs(pkg):
     lib = os.path.join(EMU_DIR, "libptemu_light_groups_spectral.so")
     srcs = [os.path.join(EMU_DIR, f) for f in ("ptemu.cpp", "ptemu_light_groups.cpp", "ptemu_spectral_project.cpp", "ptemu_light_groups_spectral.cpp")] + \
         [os.path.join(CSRC, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_light_group_rules.h", "pt_spectral_rules.h",
+    deps = srcs + [os.path.join(EMU_DIR, "ptemu_routed_pass.h")] + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_light_group_rules.h",
+                                                                                                    "pt_path_pass_rules.h", "pt_routed_rules.h", "pt_spectral_rules.h",
                                                    "pt_spectral_project_rules.h", "pt_light_groups_spectral_rules.h")] + \
         [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_debug.h", "pt_numerics.h", "pt_light_groups.h", "pt_spectral.h", "pt_light_groups_spectral.h")]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):

@@ -1,7 +1,7 @@
 """Path passes (include/pt_light_groups.h "Path passes"): the render split by how the light travelled — emission, background, and direct
 and indirect diffuse, reflection and transmission — as eight group films routed by the path's own history.
 
-The CPU tier checks the host emulation (tests/host_emulation/ptemu_path_passes.cpp: ptemu_light_groups.cpp's loop with the engine's routing text, state plane
+The CPU tier checks the host emulation (tests/host_emulation/ptemu_path_passes.cpp: the routed render's pass loop, ptemu_routed_pass.h, with the engine's PassRouter, state plane
 and item word) against ptemu_render, against identities that do not depend on the routing text (truncation, a Lambertian-only scene, conservation), against a
 third reading in scalar Python laid over tests/test_integrator_third_reading.py's vertex list, and the item word through a debug export; then every refusal, the
 header, the binding rows and the command line.  The GPU tier checks the engine against the emulation and against its own other entries."""
@@ -50,7 +50,8 @@ def emu_pp(pkg):
     """The host emulation (ptemu.cpp) with the pass render (ptemu_path_passes.cpp) beside it: a library of its own."""
     lib = os.path.join(EMU_DIR, "libptemu_path_passes.so")
     srcs = [os.path.join(EMU_DIR, "ptemu.cpp"), os.path.join(EMU_DIR, "ptemu_path_passes.cpp"), os.path.join(CSRC, "pt_scene_host.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_light_group_rules.h", "pt_path_pass_rules.h")] + \
+    deps = srcs + [os.path.join(EMU_DIR, "ptemu_routed_pass.h")] + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_light_group_rules.h",
+                                                                                                    "pt_path_pass_rules.h", "pt_routed_rules.h")] + \
         [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_debug.h", "pt_numerics.h", "pt_light_groups.h")]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-Wno-unknown-pragmas",

@@ -47,7 +47,7 @@ int main() {
                     for (uint32_t bounce = 0; bounce < max_bounces && !live.empty(); ++bounce) {
                         std::vector<uint32_t> next;
                         for (uint32_t slot : live) {
-                            // k_shade_passes' lane body over a made-up vertex
+                            // PassRouter's steps of routed_vertex (pt_path_pass_rules.h, pt_routed_rules.h) over a made-up vertex
                             const uint32_t before = bounce == 0u ? 0u : state[slot];
                             if (before == kPoison) { printf("slot %u bounce %u: the state word is read before it is written\n", slot, bounce); return 1; }
                             const uint32_t d = pp_state_d(before), k = pp_state_k(before);
@@ -80,7 +80,7 @@ int main() {
                             if (survives) e = pp_event_kind(diffuse, n, in_d, out_d);
                             if (hit) state[slot] = word | (survives ? pp_next_state(d, k, e) : 0u);
                             if (survives) { next.push_back(slot); true_k[slot] = d == 0u ? e : true_k[slot]; true_d[slot] = d + 1u < 2u ? d + 1u : 2u; }
-                            // k_shadow_passes' item: pp_shadow_item's fold and add, reading the word back from the plane
+                            // PassRouter's steps of routed_shadow_item: the fold and the add, reading the word back from the plane
                             if (has_item) {
                                 const uint32_t w = state[slot];
                                 const uint32_t a = pp_item_class_a(w), b = pp_item_class_b(w);

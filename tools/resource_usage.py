@@ -22,7 +22,7 @@ def demangle(names):
 
 def usage(source, extra):
     # (the Makefile's per-file flags: the light-sample and vertex kernels are built without machine LICM)
-    per_file = ["-mllvm", "-disable-machine-licm"] if os.path.basename(source) in ("pt_kern_shadow.hip", "pt_kern_shade.hip", "pt_kern_groups.hip", "pt_kern_passes.hip") and "-disable-machine-licm" not in extra and "--licm" not in extra else []
+    per_file = ["-mllvm", "-disable-machine-licm"] if os.path.basename(source) in ("pt_kern_shadow.hip", "pt_kern_shade.hip", "pt_kern_routed.hip") and "-disable-machine-licm" not in extra and "--licm" not in extra else []
     extra = [e for e in extra if e != "--licm"]
     if os.path.basename(source) == "pt_kern_shade.hip" and not any(e.startswith("-DPT_SHADE_PART") for e in extra):
         # (both parts of the vertex family in one table: the lean forms, then the rest with its PT_QUEUE_NT)

@@ -4,6 +4,9 @@
 // shadow over segmented SoA queues in HBM, with HIP events around every launch so that per-stage device time is measured inside the
 // timed region —, the choice of kernel variant per scene (pt_launch.h: staging mode x traversal form x wavelengths x what the scene can
 // need), the probes of the trait surface, and pt_render_multi: one replica, host thread and stream per device and one RCCL reduce.
+// Around a film: the probe pass (probe_params, launch_probe) behind pt_camera_samples, pt_intersect, the one guide pass (render_guides_impl: the first
+// hit's loop or the chain's) and the ID mattes; apply_resident, the one "parameter block up, launch over resident planes, output back" behind the resident
+// mix, develop, re-lamp and extract entries and each device of run_resident_shards; and the resident filters' shared reserve, fill and run.
 // The kernels themselves are templates in pt_kernels.h, instantiated per family in pt_kern_*.hip.  No CPU fallback: every entry point
 // fails with PT_ERR_NO_DEVICE when HIP has no device.
 #include <hip/hip_runtime.h>
@@ -1446,6 +1449,11 @@ pt_status pt_light_groups_spectral_resident(pt_scene* sc, uint32_t* width, uint3
     return PT_OK;
 }
 
+// One launch over resident planes where they lie (defined beside run_resident_shards, its node form)
+using ResidentLaunch = std::function<hipError_t(float* d_params, float* d_out, hipStream_t stream)>;
+static pt_status apply_resident(pt_scene* sc, GrowBuf pt_scene::*cache, size_t cap_floats, const void* params, size_t param_bytes, void* out, size_t out_bytes,
+                                const ResidentLaunch& launch, bool wait = true);
+
 // pt_light_groups_relamp's kernel over group_bins_cache, on the stream the render ran on (the null stream): the matrix goes up, K planes come back
 pt_status pt_light_groups_relamp_resident(pt_scene* sc, uint32_t K, const float* matrix, float* out) {
     if (!sc) return fail(PT_ERR_INVALID_ARGUMENT, "the scene is null");
@@ -1458,17 +1466,11 @@ pt_status pt_light_groups_relamp_resident(pt_scene* sc, uint32_t K, const float*
     const uint32_t planes = sc->group_bins_groups * sc->group_bins_bins;
     const size_t n_pixels = (size_t)sc->group_bins_width * sc->group_bins_height;
     const size_t matrix_floats = (size_t)PT_SPECTRAL_MAX_RESPONSES * PT_LIGHT_GROUPS_MAX * PT_SPECTRAL_MAX_BINS;
-    const pt_status cached = sc->relamp_cache.reserve(sizeof(float) * (matrix_floats + (size_t)K * n_pixels));
-    if (cached != PT_OK) return cached;
-    float* d_matrix = sc->relamp_cache.as<float>();
-    float* d_out = d_matrix + matrix_floats;
-    hipStream_t stream = nullptr;
-    HIP_TRY(hipMemcpyAsync(d_matrix, matrix, sizeof(float) * K * planes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ptk::launch_light_groups_relamp(ptk::spectral_project_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, planes, K, d_matrix,
-                                            sc->group_bins_cache.as<float>(), d_out));
-    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(float) * K * n_pixels, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return PT_OK;
+    return apply_resident(sc, &pt_scene::relamp_cache, matrix_floats, matrix, sizeof(float) * K * planes, out, sizeof(float) * K * n_pixels,
+                          [&](float* d_matrix, float* d_out, hipStream_t stream) {
+                              return ptk::launch_light_groups_relamp(ptk::spectral_project_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, planes, K, d_matrix,
+                                                                     sc->group_bins_cache.as<float>(), d_out);
+                          });
 }
 
 pt_status pt_light_groups_resident(pt_scene* sc, uint32_t* width, uint32_t* height, uint32_t* group_count) {
@@ -1507,16 +1509,10 @@ static pt_status mix_resident_films(pt_scene* sc, const float* films, const floa
     if (st != PT_OK) return fail(st, err);
     HIP_TRY(hipSetDevice(sc->device));
     const size_t n_pixels = (size_t)sc->groups_width * sc->groups_height, matrix_floats = (size_t)PT_LIGHT_GROUPS_MAX * 12;   // (the film behind them stays 16-byte aligned)
-    const pt_status cached = sc->group_mix_cache.reserve(sizeof(float) * (matrix_floats + 4 * n_pixels));
-    if (cached != PT_OK) return cached;
-    float* d_matrices = sc->group_mix_cache.as<float>();
-    float* d_out = d_matrices + matrix_floats;
-    hipStream_t stream = nullptr;
-    HIP_TRY(hipMemcpyAsync(d_matrices, matrices, sizeof(float) * 9 * sc->groups_count, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ptk::launch_light_groups_mix(stream, (uint32_t)n_pixels, sc->groups_count, films, d_matrices, d_out));
-    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(float) * 4 * n_pixels, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return PT_OK;
+    return apply_resident(sc, &pt_scene::group_mix_cache, matrix_floats, matrices, sizeof(float) * 9 * sc->groups_count, out, sizeof(float) * 4 * n_pixels,
+                          [&](float* d_matrices, float* d_out, hipStream_t stream) {
+                              return ptk::launch_light_groups_mix(stream, (uint32_t)n_pixels, sc->groups_count, films, d_matrices, d_out);
+                          });
 }
 
 pt_status pt_spectral_resident(pt_scene* sc, uint32_t* width, uint32_t* height, uint32_t* bins) {
@@ -1543,17 +1539,10 @@ pt_status pt_spectral_project_resident(pt_scene* sc, uint32_t K, const float* ma
 // pt_spectral_project's kernel over `bins` planes of n_pixels on the scene's device: the matrix goes up, K planes come back
 static pt_status project_device_bins(pt_scene* sc, uint32_t K, const float* matrix, uint32_t bins, size_t n_pixels, const float* d_bins, float* out) {
     HIP_TRY(hipSetDevice(sc->device));
-    const size_t matrix_floats = (size_t)PT_SPECTRAL_MAX_RESPONSES * PT_SPECTRAL_MAX_BINS, bytes = sizeof(float) * (matrix_floats + (size_t)K * n_pixels);
-    const pt_status cached = sc->project_cache.reserve(bytes);
-    if (cached != PT_OK) return cached;
-    float* d_matrix = sc->project_cache.as<float>();
-    float* d_out = d_matrix + matrix_floats;
-    hipStream_t stream = nullptr;
-    HIP_TRY(hipMemcpyAsync(d_matrix, matrix, sizeof(float) * K * bins, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ptk::launch_spectral_project(ptk::spectral_project_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, bins, K, d_matrix, d_bins, d_out));
-    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(float) * K * n_pixels, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return PT_OK;
+    return apply_resident(sc, &pt_scene::project_cache, (size_t)PT_SPECTRAL_MAX_RESPONSES * PT_SPECTRAL_MAX_BINS, matrix, sizeof(float) * K * bins, out,
+                          sizeof(float) * K * n_pixels, [&](float* d_matrix, float* d_out, hipStream_t stream) {
+                              return ptk::launch_spectral_project(ptk::spectral_project_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, bins, K, d_matrix, d_bins, d_out);
+                          });
 }
 
 uint32_t pt_device_count(void) {
@@ -1807,6 +1796,22 @@ static double node_payload_seconds(const NodePayload& np) { return np.seconds.em
 // A kernel over node-resident shards where they lie: `matrix_bytes` of `matrix` to every device that holds a shard of `shards`, into the scene's `cache` (the
 // matrix at its cap size, matrix_floats, then the output); `launch(s, n_own, d_matrix, packed, d_out)` over the shard's packed planes (plane stride n_own);
 // out_planes * n_own elements of `kind` back per device, scattered into `out` by the rule the shards were scattered by.
+// A kernel over resident planes where they lie, on the stream they were made on (the null stream) of the scene's device, which is current: `param_bytes` of
+// `params` up into the scene's `cache` — the parameter block at its cap size, cap_floats, then the output —, `launch(d_params, d_out, stream)`, and out_bytes
+// of the output back into `out`.  wait false: nothing is synchronised (run_resident_shards enqueues on every device first).
+static pt_status apply_resident(pt_scene* sc, GrowBuf pt_scene::*cache, size_t cap_floats, const void* params, size_t param_bytes, void* out, size_t out_bytes,
+                                const ResidentLaunch& launch, bool wait) {
+    const pt_status cached = (sc->*cache).reserve(sizeof(float) * cap_floats + out_bytes);
+    if (cached != PT_OK) return cached;
+    float* d_params = (sc->*cache).as<float>();
+    float* d_out = d_params + cap_floats;
+    const hipStream_t stream = nullptr;
+    HIP_TRY(hipMemcpyAsync(d_params, params, param_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(launch(d_params, d_out, stream));
+    HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+    if (wait) HIP_TRY(hipStreamSynchronize(stream));
+    return PT_OK;
+}
 using ShardLaunch = std::function<hipError_t(pt_scene* s, uint32_t n_own, const float* d_matrix, const float* packed, float* d_out)>;
 static pt_status run_resident_shards(const std::vector<pt_scene*>& shards, const ShardKind& kind, uint32_t out_planes, size_t film_pixels, const float* matrix,
                                      size_t matrix_bytes, size_t matrix_floats, GrowBuf pt_scene::*cache, float* out, const ShardLaunch& launch) {
@@ -1818,15 +1823,10 @@ static pt_status run_resident_shards(const std::vector<pt_scene*>& shards, const
         const uint32_t n_own = (uint32_t)shard.px.size();
         if (n_own == 0) continue;
         HIP_TRY(hipSetDevice(s->device));
-        const size_t out_floats = (size_t)kind.floats * out_planes * n_own;
-        const pt_status st = (s->*cache).reserve(sizeof(float) * (matrix_floats + out_floats));
+        back[v].resize((size_t)kind.floats * out_planes * n_own);
+        const pt_status st = apply_resident(s, cache, matrix_floats, matrix, matrix_bytes, back[v].data(), sizeof(float) * back[v].size(),
+                                            [&](float* d_matrix, float* d_out, hipStream_t) { return launch(s, n_own, d_matrix, shard.packed.as<float>(), d_out); }, false);
         if (st != PT_OK) return st;
-        back[v].resize(out_floats);
-        float* d_matrix = (s->*cache).as<float>();
-        float* d_out = d_matrix + matrix_floats;
-        HIP_TRY(hipMemcpyAsync(d_matrix, matrix, matrix_bytes, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(launch(s, n_own, d_matrix, shard.packed.as<float>(), d_out));
-        HIP_TRY(hipMemcpyAsync(back[v].data(), d_out, sizeof(float) * out_floats, hipMemcpyDeviceToHost, nullptr));
     }
     for (size_t v = 0; v < shards.size(); ++v) {
         pt_scene* s = shards[v];
@@ -2097,6 +2097,24 @@ pt_status pt_render_adaptive_light_groups_multi(pt_scene* sc, const pt_render_de
     return render_node(sc, call, device_mask, profile);
 }
 
+// ---- The probe pass: camera rays of chosen samples and their closest hits, behind pt_camera_samples, pt_intersect, the guide pass and the ID mattes.
+// the RenderParams of a camera-ray probe of the render `rdp`: what stage_generate reads, nothing of the film
+static RenderParams probe_params(const pt_scene* sc, const pt_render_desc* rdp) {
+    RenderParams rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.seed = rdp->seed; rp.width = rdp->width; rp.height = rdp->height;
+    rp.wavelength_lo = rdp->wavelength_lo; rp.wavelength_span = rdp->wavelength_hi - rdp->wavelength_lo;
+    rp.camera = pth::camera_params(sc->host.cameras[rdp->camera_index], (float)rdp->width / (float)rdp->height);
+    rp.chunk_pixels = 1;   // (stage_generate: sample = first_sample + slot / chunk_pixels — the probe hands the sample index in as the slot)
+    return rp;
+}
+// the closest hits of the `n` rays (o, d) into `hits`: the probe kernel in the scene's own staging mode, on the null stream
+static void launch_probe(const pt_scene* sc, uint32_t n, const float* o, const float* d, pt_hit* hits) {
+    const int grid = sc->num_cus * 4;
+    const uint32_t lds_bytes = sc->lds_mode == PT_LDS_ALL ? sc->blob_words * 4u : (sc->lds_mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
+    launch_probe_intersect(LaunchCfg{grid, lds_bytes, (hipStream_t)0, sc->lds_mode}, SceneArgs{sc->d_blob, sc->blob_words, sc->d_tex}, n, o, d, hits);
+}
+
 pt_status pt_intersect(pt_scene* sc, size_t n, const float* origins, const float* directions, pt_hit* hits) {
     if (!sc || !origins || !directions || !hits) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return PT_OK;
@@ -2105,9 +2123,7 @@ pt_status pt_intersect(pt_scene* sc, size_t n, const float* origins, const float
     HIP_TRY(dor.alloc(12 * n)); HIP_TRY(dd.alloc(12 * n)); HIP_TRY(dh.alloc(sizeof(pt_hit) * n));
     HIP_TRY(hipMemcpy(dor.p, origins, 12 * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dd.p, directions, 12 * n, hipMemcpyHostToDevice));
-    int grid = sc->num_cus * 4;
-    const uint32_t lds_bytes = sc->lds_mode == PT_LDS_ALL ? sc->blob_words * 4u : (sc->lds_mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
-    launch_probe_intersect(LaunchCfg{grid, lds_bytes, (hipStream_t)0, sc->lds_mode}, SceneArgs{sc->d_blob, sc->blob_words, sc->d_tex}, (uint32_t)n, dor.as<float>(), dd.as<float>(), dh.as<pt_hit>());
+    launch_probe(sc, (uint32_t)n, dor.as<float>(), dd.as<float>(), dh.as<pt_hit>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(hits, dh.p, sizeof(pt_hit) * n, hipMemcpyDeviceToHost));
@@ -2124,12 +2140,7 @@ pt_status pt_camera_samples(pt_scene* sc, const pt_render_desc* rdp, size_t n, c
     for (size_t i = 0; i < n; ++i) if ((uint64_t)pixel[i] >= n_pixels) return fail(PT_ERR_INVALID_ARGUMENT, "pixel id out of range");
     if (n == 0) return PT_OK;
     HIP_TRY(hipSetDevice(sc->device));
-    RenderParams rp;
-    memset(&rp, 0, sizeof(rp));
-    rp.seed = rdp->seed; rp.width = rdp->width; rp.height = rdp->height;
-    rp.wavelength_lo = rdp->wavelength_lo; rp.wavelength_span = rdp->wavelength_hi - rdp->wavelength_lo;
-    rp.camera = pth::camera_params(sc->host.cameras[rdp->camera_index], (float)rdp->width / (float)rdp->height);
-    rp.chunk_pixels = 1;   // (stage_generate: sample = first_sample + slot / chunk_pixels — the probe hands the sample index in as the slot)
+    const RenderParams rp = probe_params(sc, rdp);
     DevBuf dp, ds, dor, dd, dl;
     HIP_TRY(dp.alloc(4 * n)); HIP_TRY(ds.alloc(4 * n)); HIP_TRY(dor.alloc(12 * n)); HIP_TRY(dd.alloc(12 * n)); HIP_TRY(dl.alloc(4 * n));
     HIP_TRY(hipMemcpy(dp.p, pixel, 4 * n, hipMemcpyHostToDevice));
@@ -2190,69 +2201,91 @@ static pt_status make_bin_albedo_fold(pt_scene* sc, const pt_render_desc* rdp, u
 struct GuideOut {
     float* guides; float* albedo; float* bin_albedo; bool device;
 };
-static pt_status render_guides_impl(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const GuideOut& out, uint32_t bins = 0) {
+// `chain` (null: the first hit, as above): the guides at the end of every sample's specular chain.  Per sample index the camera rays go out as a list with the
+// identity pixel order; per chain vertex the probe runs over the rays still on their way and k_chain_step (pt_guides_chain.hip) folds the ones that end into
+// their pixels' sums and compacts the rest into the next list, whose length comes back in one 4-byte read — the probe's launcher takes its ray count by value.
+// The last possible vertex (v == max_chain) ends every ray, so nothing is read back after it.  The per-bin albedo is folded by k_chain_step at the same
+// terminal vertex.  The two forms share their buffers, tables and finish and differ in their loops — and in who zeroes the sums: the first-hit folds do at
+// k == 0, the chain form clears them up front, since a pixel's first sample may end at any vertex.
+static pt_status render_guides_impl(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const pt_guide_chain_desc* chain, const GuideOut& out, uint32_t bins = 0) {
     float *const guides = out.guides, *const albedo = out.albedo, *const bin_albedo = out.bin_albedo;
     HIP_TRY(hipSetDevice(sc->device));
-    const uint32_t n = rdp->width * rdp->height;
-    RenderParams rp;
-    memset(&rp, 0, sizeof(rp));
-    rp.seed = rdp->seed; rp.width = rdp->width; rp.height = rdp->height;
-    rp.wavelength_lo = rdp->wavelength_lo; rp.wavelength_span = rdp->wavelength_hi - rdp->wavelength_lo;
-    rp.camera = pth::camera_params(sc->host.cameras[rdp->camera_index], (float)rdp->width / (float)rdp->height);
-    rp.chunk_pixels = 1;
-    DevBuf dor, dd, dh, dsum, dg, dasum, da, drow, dloff, dtable, dbtable, dbsum;
-    BinAlbedoFold fold{};
-    HIP_TRY(dor.alloc(12 * (size_t)n)); HIP_TRY(dd.alloc(12 * (size_t)n)); HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n));
-    HIP_TRY(dsum.alloc(sizeof(DnGuideSum) * (size_t)n));
+    const uint32_t n = rdp->width * rdp->height, materials = sc->host.material_count;
+    const RenderParams rp = probe_params(sc, rdp);
+    DevBuf dor[2], dd[2], dstate[2], dh, dsum, dg, dasum, da, drow, dloff, dtable, dcount, dbtable, dbsum;   // (the second ray list, dstate and dcount: the chain's)
+    for (int i = 0; i < (chain ? 2 : 1); ++i) {
+        HIP_TRY(dor[i].alloc(12 * (size_t)n)); HIP_TRY(dd[i].alloc(12 * (size_t)n));
+        if (chain) HIP_TRY(dstate[i].alloc(16 * (size_t)n));
+    }
+    HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n)); HIP_TRY(dsum.alloc(sizeof(DnGuideSum) * (size_t)n));
     float *d_guides = guides, *d_albedo = albedo;
     if (!out.device) { HIP_TRY(dg.alloc(16 * (size_t)n)); d_guides = dg.as<float>(); }
-    DnAlbedoBasis basis;
-    const uint32_t materials = sc->host.material_count;
+    if (chain) {
+        HIP_TRY(dcount.alloc(4 * (size_t)(chain->max_chain + 1u)));
+        HIP_TRY(hipMemsetAsync(dsum.p, 0, sizeof(DnGuideSum) * (size_t)n, 0));
+    }
+    ChainAlbedo ca;   // (the albedo sums, tables and per-bin fold of either form)
+    memset(&ca, 0, sizeof(ca));
     if (albedo) {
         HIP_TRY(dasum.alloc(16 * (size_t)n));
         if (!out.device) { HIP_TRY(da.alloc(16 * (size_t)n)); d_albedo = da.as<float>(); }
+        if (chain) HIP_TRY(hipMemsetAsync(dasum.p, 0, 16 * (size_t)n, 0));
         uint32_t rows = 0;
-        const pt_status ast = make_albedo_tables(sc, rdp, &basis, &drow, &dloff, &dtable, &rows);
+        const pt_status ast = make_albedo_tables(sc, rdp, &ca.basis, &drow, &dloff, &dtable, &rows);
         if (ast != PT_OK) return ast;
+        ca.albedo_sums = dasum.as<float>(); ca.material_row = drow.as<uint32_t>(); ca.table = dtable.as<float>();
         if (bin_albedo) {
-            const pt_status bst = make_bin_albedo_fold(sc, rdp, bins, n, rows, drow, dloff, &dbtable, &dbsum, out.device ? bin_albedo : nullptr, &fold);
+            const pt_status bst = make_bin_albedo_fold(sc, rdp, bins, n, rows, drow, dloff, &dbtable, &dbsum, out.device ? bin_albedo : nullptr, &ca.bin_fold);
             if (bst != PT_OK) return bst;
         }
     }
-    const int grid = sc->num_cus * 4;
-    const uint32_t lds_bytes = sc->lds_mode == PT_LDS_ALL ? sc->blob_words * 4u : (sc->lds_mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
-    for (uint32_t k = 0; k < guide_samples; ++k) {
-        launch_guide_rays(rp, n, k, dor.as<float>(), dd.as<float>());
-        launch_probe_intersect(LaunchCfg{grid, lds_bytes, (hipStream_t)0, sc->lds_mode}, SceneArgs{sc->d_blob, sc->blob_words, sc->d_tex}, n, dor.as<float>(), dd.as<float>(), dh.as<pt_hit>());
+    const ChainRays rays[2] = {{dor[0].as<float>(), dd[0].as<float>(), dstate[0].as<uint4>()}, {dor[1].as<float>(), dd[1].as<float>(), dstate[1].as<uint4>()}};
+    if (!chain) for (uint32_t k = 0; k < guide_samples; ++k) {
+        launch_guide_rays(rp, n, k, rays[0].o, rays[0].d);
+        launch_probe(sc, n, rays[0].o, rays[0].d, dh.as<pt_hit>());
         if (albedo)
-            launch_guide_fold_albedo(n, dh.as<pt_hit>(), dsum.as<DnGuideSum>(), dasum.as<float>(), k == 0, sc->d_blob, sc->d_tex, materials, drow.as<uint32_t>(), dtable.as<float>(), basis);
+            launch_guide_fold_albedo(n, dh.as<pt_hit>(), dsum.as<DnGuideSum>(), ca.albedo_sums, k == 0, sc->d_blob, sc->d_tex, materials, ca.material_row, ca.table, ca.basis);
         else
             launch_guide_fold(n, dh.as<pt_hit>(), dsum.as<DnGuideSum>(), k == 0);
-        if (fold.sums) launch_guide_fold_bins(n, dh.as<pt_hit>(), fold, sc->d_blob, sc->d_tex, materials);
+        if (ca.bin_fold.sums) launch_guide_fold_bins(n, dh.as<pt_hit>(), ca.bin_fold, sc->d_blob, sc->d_tex, materials);
+    }
+    else for (uint32_t k = 0; k < guide_samples; ++k) {
+        launch_chain_rays(rp, n, k, rays[0]);
+        HIP_TRY(hipMemsetAsync(dcount.p, 0, 4 * (size_t)(chain->max_chain + 1u), 0));
+        uint32_t active = n;
+        for (uint32_t v = 0; v <= chain->max_chain && active != 0u; ++v) {
+            const ChainRays &in = rays[v & 1u], &next = rays[(v & 1u) ^ 1u];
+            launch_probe(sc, active, in.o, in.d, dh.as<pt_hit>());
+            launch_chain_step(active, dh.as<pt_hit>(), in, next, dcount.as<uint32_t>() + v, dsum.as<DnGuideSum>(), ca, v, chain->max_chain, chain->alpha_max, sc->d_blob, sc->d_tex,
+                              materials);
+            if (v == chain->max_chain) break;
+            HIP_TRY(hipMemcpy(&active, dcount.as<uint32_t>() + v, 4, hipMemcpyDeviceToHost));
+            if (active > n) return fail(PT_ERR_DEVICE, "the chain's ray list grew");   // (never: a launch appends at most its own rays)
+        }
     }
     if (albedo) launch_guide_finish_albedo(n, dsum.as<DnGuideSum>(), dasum.as<float>(), guide_samples, d_guides, d_albedo);
     else launch_guide_finish(n, dsum.as<DnGuideSum>(), guide_samples, d_guides);
-    if (fold.sums) launch_bin_albedo_finish(n, bins, fold.sums, guide_samples, fold.sums);   // (in place: one value per lane)
+    if (ca.bin_fold.sums) launch_bin_albedo_finish(n, bins, ca.bin_fold.sums, guide_samples, ca.bin_fold.sums);   // (in place: one value per lane)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     if (out.device) return PT_OK;
     HIP_TRY(hipMemcpy(guides, d_guides, 16 * (size_t)n, hipMemcpyDeviceToHost));
     if (albedo) HIP_TRY(hipMemcpy(albedo, d_albedo, 16 * (size_t)n, hipMemcpyDeviceToHost));
-    if (fold.sums) HIP_TRY(hipMemcpy(bin_albedo, fold.sums, 4 * (size_t)bins * n, hipMemcpyDeviceToHost));
+    if (ca.bin_fold.sums) HIP_TRY(hipMemcpy(bin_albedo, ca.bin_fold.sums, 4 * (size_t)bins * n, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 pt_status pt_render_guides(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, float* guides) {
     std::string err;
     const pt_status st = pth::check_guides_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, guides, &err);
     if (st != PT_OK) return fail(st, err);
-    return render_guides_impl(sc, rdp, guide_samples, GuideOut{guides, nullptr, nullptr, false});
+    return render_guides_impl(sc, rdp, guide_samples, nullptr, GuideOut{guides, nullptr, nullptr, false});
 }
 pt_status pt_render_guides_albedo(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, float* guides, float* albedo) {
     std::string err;
     const pt_status st = pth::check_guides_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, guides, &err);
     if (st != PT_OK) return fail(st, err);
     if (!albedo) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    return render_guides_impl(sc, rdp, guide_samples, GuideOut{guides, albedo, nullptr, false});
+    return render_guides_impl(sc, rdp, guide_samples, nullptr, GuideOut{guides, albedo, nullptr, false});
 }
 
 // include/pt_denoise.h: the ID mattes.  Per sample index the launches of a guide pass — the camera rays of every pixel, their closest hits — and behind them
@@ -2265,12 +2298,7 @@ pt_status pt_render_mattes(pt_scene* sc, const pt_render_desc* rdp, const pt_mat
     HIP_TRY(hipSetDevice(sc->device));
     sc->mattes_valid = false;
     const uint32_t n = rdp->width * rdp->height, ranks = mdp->ranks, samples = mdp->samples;
-    RenderParams rp;
-    memset(&rp, 0, sizeof(rp));
-    rp.seed = rdp->seed; rp.width = rdp->width; rp.height = rdp->height;
-    rp.wavelength_lo = rdp->wavelength_lo; rp.wavelength_span = rdp->wavelength_hi - rdp->wavelength_lo;
-    rp.camera = pth::camera_params(sc->host.cameras[rdp->camera_index], (float)rdp->width / (float)rdp->height);
-    rp.chunk_pixels = 1;
+    const RenderParams rp = probe_params(sc, rdp);
     const size_t plane_bytes = 4 * (size_t)ranks * n;
     pt_status cached = sc->matte_keys.reserve(plane_bytes);
     if (cached == PT_OK) cached = sc->matte_coverage.reserve(plane_bytes);
@@ -2278,11 +2306,9 @@ pt_status pt_render_mattes(pt_scene* sc, const pt_render_desc* rdp, const pt_mat
     DevBuf dor, dd, dh, dtable, doverflow;
     HIP_TRY(dor.alloc(12 * (size_t)n)); HIP_TRY(dd.alloc(12 * (size_t)n)); HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n));
     HIP_TRY(dtable.alloc(ptk::matte_table_bytes(n, ranks))); HIP_TRY(doverflow.alloc(4 * (size_t)n));
-    const int grid = sc->num_cus * 4;
-    const uint32_t lds_bytes = sc->lds_mode == PT_LDS_ALL ? sc->blob_words * 4u : (sc->lds_mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
     for (uint32_t k = 0; k < samples; ++k) {
         launch_guide_rays(rp, n, k, dor.as<float>(), dd.as<float>());
-        launch_probe_intersect(LaunchCfg{grid, lds_bytes, (hipStream_t)0, sc->lds_mode}, SceneArgs{sc->d_blob, sc->blob_words, sc->d_tex}, n, dor.as<float>(), dd.as<float>(), dh.as<pt_hit>());
+        launch_probe(sc, n, dor.as<float>(), dd.as<float>(), dh.as<pt_hit>());
         HIP_TRY(ptk::launch_matte_fold(nullptr, n, ranks, mdp->key, dh.as<pt_hit>(), dtable.p, k == 0));
     }
     HIP_TRY(ptk::launch_matte_finish(nullptr, n, ranks, samples, dtable.p, sc->matte_keys.as<uint32_t>(), sc->matte_coverage.as<float>(), doverflow.as<uint32_t>()));
@@ -2316,93 +2342,24 @@ pt_status pt_matte_extract_resident(pt_scene* sc, uint32_t set_count, const uint
     pth::matte_selection_words(set_count, offsets, selected, &selection);
     HIP_TRY(hipSetDevice(sc->device));
     const size_t n_pixels = (size_t)sc->matte_width * sc->matte_height;
-    const pt_status cached = sc->matte_extract_cache.reserve(4 * ((size_t)ptk::kMatteSelectionWords + (size_t)set_count * n_pixels));
-    if (cached != PT_OK) return cached;
-    uint32_t* d_selection = sc->matte_extract_cache.as<uint32_t>();
-    float* d_out = sc->matte_extract_cache.as<float>() + ptk::kMatteSelectionWords;
-    hipStream_t stream = nullptr;
-    HIP_TRY(hipMemcpyAsync(d_selection, selection.data(), 4 * selection.size(), hipMemcpyHostToDevice, stream));
-    HIP_TRY(ptk::launch_matte_extract(ptk::matte_extract_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, sc->matte_ranks, sc->matte_keys.as<uint32_t>(),
-                                      sc->matte_coverage.as<float>(), set_count, d_selection, d_selection + ptd::MATTE_SETS_MAX + 1u, d_out));
-    HIP_TRY(hipMemcpyAsync(out, d_out, 4 * (size_t)set_count * n_pixels, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return PT_OK;
+    return apply_resident(sc, &pt_scene::matte_extract_cache, ptk::kMatteSelectionWords, selection.data(), 4 * selection.size(), out, 4 * (size_t)set_count * n_pixels,
+                          [&](float* d_words, float* d_out, hipStream_t stream) {
+                              const uint32_t* d_selection = reinterpret_cast<const uint32_t*>(d_words);   // (32-bit words in the float-typed cache)
+                              return ptk::launch_matte_extract(ptk::matte_extract_grid(sc->num_cus, (uint32_t)n_pixels), stream, (uint32_t)n_pixels, sc->matte_ranks,
+                                                               sc->matte_keys.as<uint32_t>(), sc->matte_coverage.as<float>(), set_count, d_selection,
+                                                               d_selection + ptd::MATTE_SETS_MAX + 1u, d_out);
+                          });
 }
 
-// include/pt_denoise.h: the guides at the end of every sample's specular chain.  Per sample index the camera rays go out as a list with the identity pixel
-// order; per chain vertex the probe runs over the rays still on their way and k_chain_step (pt_guides_chain.hip) folds the ones that end into their pixels'
-// sums and compacts the rest into the next list, whose length comes back in one 4-byte read — the probe's launcher takes its ray count by value.  The last
-// possible vertex (v == max_chain) ends every ray, so nothing is read back after it: max_chain 0 runs pt_render_guides_albedo's launches and no read-back.
-// `bin_albedo` (may be null; needs albedo): the per-bin albedo over `bins` bins, folded by k_chain_step at the same terminal vertex.
-static pt_status render_guides_chain_impl(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const pt_guide_chain_desc& cd, const GuideOut& out, uint32_t bins = 0) {
-    float *const guides = out.guides, *const albedo = out.albedo, *const bin_albedo = out.bin_albedo;
-    HIP_TRY(hipSetDevice(sc->device));
-    const uint32_t n = rdp->width * rdp->height;
-    RenderParams rp;
-    memset(&rp, 0, sizeof(rp));
-    rp.seed = rdp->seed; rp.width = rdp->width; rp.height = rdp->height;
-    rp.wavelength_lo = rdp->wavelength_lo; rp.wavelength_span = rdp->wavelength_hi - rdp->wavelength_lo;
-    rp.camera = pth::camera_params(sc->host.cameras[rdp->camera_index], (float)rdp->width / (float)rdp->height);
-    rp.chunk_pixels = 1;
-    DevBuf dor[2], dd[2], dstate[2], dh, dsum, dg, dasum, da, drow, dloff, dtable, dcount, dbtable, dbsum;
-    for (int i = 0; i < 2; ++i) { HIP_TRY(dor[i].alloc(12 * (size_t)n)); HIP_TRY(dd[i].alloc(12 * (size_t)n)); HIP_TRY(dstate[i].alloc(16 * (size_t)n)); }
-    HIP_TRY(dh.alloc(sizeof(pt_hit) * (size_t)n)); HIP_TRY(dsum.alloc(sizeof(DnGuideSum) * (size_t)n));
-    float *d_guides = guides, *d_albedo = albedo;
-    if (!out.device) { HIP_TRY(dg.alloc(16 * (size_t)n)); d_guides = dg.as<float>(); }
-    HIP_TRY(dcount.alloc(4 * (size_t)(cd.max_chain + 1u)));
-    HIP_TRY(hipMemsetAsync(dsum.p, 0, sizeof(DnGuideSum) * (size_t)n, 0));
-    ChainAlbedo ca;
-    memset(&ca, 0, sizeof(ca));
-    if (albedo) {
-        HIP_TRY(dasum.alloc(16 * (size_t)n));
-        if (!out.device) { HIP_TRY(da.alloc(16 * (size_t)n)); d_albedo = da.as<float>(); }
-        HIP_TRY(hipMemsetAsync(dasum.p, 0, 16 * (size_t)n, 0));
-        uint32_t rows = 0;
-        const pt_status ast = make_albedo_tables(sc, rdp, &ca.basis, &drow, &dloff, &dtable, &rows);
-        if (ast != PT_OK) return ast;
-        ca.albedo_sums = dasum.as<float>(); ca.material_row = drow.as<uint32_t>(); ca.table = dtable.as<float>();
-        if (bin_albedo) {
-            const pt_status bst = make_bin_albedo_fold(sc, rdp, bins, n, rows, drow, dloff, &dbtable, &dbsum, out.device ? bin_albedo : nullptr, &ca.bin_fold);
-            if (bst != PT_OK) return bst;
-        }
-    }
-    const int grid = sc->num_cus * 4;
-    const uint32_t lds_bytes = sc->lds_mode == PT_LDS_ALL ? sc->blob_words * 4u : (sc->lds_mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
-    const ChainRays rays[2] = {{dor[0].as<float>(), dd[0].as<float>(), dstate[0].as<uint4>()}, {dor[1].as<float>(), dd[1].as<float>(), dstate[1].as<uint4>()}};
-    for (uint32_t k = 0; k < guide_samples; ++k) {
-        launch_chain_rays(rp, n, k, rays[0]);
-        HIP_TRY(hipMemsetAsync(dcount.p, 0, 4 * (size_t)(cd.max_chain + 1u), 0));
-        uint32_t active = n;
-        for (uint32_t v = 0; v <= cd.max_chain && active != 0u; ++v) {
-            const ChainRays &in = rays[v & 1u], &out = rays[(v & 1u) ^ 1u];
-            launch_probe_intersect(LaunchCfg{grid, lds_bytes, (hipStream_t)0, sc->lds_mode}, SceneArgs{sc->d_blob, sc->blob_words, sc->d_tex}, active, in.o, in.d, dh.as<pt_hit>());
-            launch_chain_step(active, dh.as<pt_hit>(), in, out, dcount.as<uint32_t>() + v, dsum.as<DnGuideSum>(), ca, v, cd.max_chain, cd.alpha_max, sc->d_blob, sc->d_tex,
-                              sc->host.material_count);
-            if (v == cd.max_chain) break;
-            HIP_TRY(hipMemcpy(&active, dcount.as<uint32_t>() + v, 4, hipMemcpyDeviceToHost));
-            if (active > n) return fail(PT_ERR_DEVICE, "the chain's ray list grew");   // (never: a launch appends at most its own rays)
-        }
-    }
-    if (albedo) launch_guide_finish_albedo(n, dsum.as<DnGuideSum>(), dasum.as<float>(), guide_samples, d_guides, d_albedo);
-    else launch_guide_finish(n, dsum.as<DnGuideSum>(), guide_samples, d_guides);
-    if (ca.bin_fold.sums) launch_bin_albedo_finish(n, bins, ca.bin_fold.sums, guide_samples, ca.bin_fold.sums);   // (in place: one value per lane)
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    if (out.device) return PT_OK;
-    HIP_TRY(hipMemcpy(guides, d_guides, 16 * (size_t)n, hipMemcpyDeviceToHost));
-    if (albedo) HIP_TRY(hipMemcpy(albedo, d_albedo, 16 * (size_t)n, hipMemcpyDeviceToHost));
-    if (ca.bin_fold.sums) HIP_TRY(hipMemcpy(bin_albedo, ca.bin_fold.sums, 4 * (size_t)bins * n, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
 pt_status pt_render_guides_chain(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const pt_guide_chain_desc* chain, float* guides, float* albedo) {
     std::string err;
     pt_guide_chain_desc cd;
     const pt_status st = pth::check_guides_chain_args(sc, rdp, sc ? (uint32_t)sc->host.cameras.size() : 0u, guide_samples, chain, guides, &cd, &err);
     if (st != PT_OK) return fail(st, err);
-    return render_guides_chain_impl(sc, rdp, guide_samples, cd, GuideOut{guides, albedo, nullptr, false});
+    return render_guides_impl(sc, rdp, guide_samples, &cd, GuideOut{guides, albedo, nullptr, false});
 }
-// include/pt_spectral.h: the guides, the XYZ albedo and the per-bin albedo from one set of probes — at the first hit (render_guides_impl), or with a chain of
-// max_chain > 0 at the end of every sample's specular chain (render_guides_chain_impl).  The XYZ albedo is always computed (its tables' rows are the per-bin
+// include/pt_spectral.h: the guides, the XYZ albedo and the per-bin albedo from one set of probes — at the first hit, or with a chain of max_chain > 0 at the
+// end of every sample's specular chain (render_guides_impl's two loops).  The XYZ albedo is always computed (its tables' rows are the per-bin
 // table's); a caller that passes none gets none.
 pt_status pt_render_guides_bin_albedo(pt_scene* sc, const pt_render_desc* rdp, uint32_t guide_samples, const pt_guide_chain_desc* chain, uint32_t bins, float* guides,
                                       float* albedo, float* bin_albedo) {
@@ -2412,9 +2369,7 @@ pt_status pt_render_guides_bin_albedo(pt_scene* sc, const pt_render_desc* rdp, u
     if (st != PT_OK) return fail(st, err);
     std::vector<float> own_albedo;
     if (!albedo) { own_albedo.resize(4 * (size_t)rdp->width * rdp->height); albedo = own_albedo.data(); }
-    const GuideOut out{guides, albedo, bin_albedo, false};
-    if (cd.max_chain == 0) return render_guides_impl(sc, rdp, guide_samples, out, bins);
-    return render_guides_chain_impl(sc, rdp, guide_samples, cd, out, bins);
+    return render_guides_impl(sc, rdp, guide_samples, cd.max_chain ? &cd : nullptr, GuideOut{guides, albedo, bin_albedo, false}, bins);
 }
 
 // ---- include/pt_resident.h.  Every argument, and what the call needs resident, is checked by pth::check_resident_* before a device is looked for.
@@ -2448,7 +2403,7 @@ pt_status pt_resident_guides(pt_scene* sc, const pt_render_desc* rdp, uint32_t g
     if (st == PT_OK && bin_albedo) st = r.bin_albedo.reserve(4 * np * r.bins);
     if (st != PT_OK) return st;
     const GuideOut out{r.guides.as<float>(), albedo ? r.albedo.as<float>() : nullptr, bin_albedo ? r.bin_albedo.as<float>() : nullptr, true};
-    st = cd.max_chain == 0 ? render_guides_impl(sc, rdp, guide_samples, out, bin_albedo ? r.bins : 0u) : render_guides_chain_impl(sc, rdp, guide_samples, cd, out, bin_albedo ? r.bins : 0u);
+    st = render_guides_impl(sc, rdp, guide_samples, cd.max_chain ? &cd : nullptr, out, bin_albedo ? r.bins : 0u);
     if (st != PT_OK) return st;
     r.parts |= PT_RESIDENT_GUIDES | (albedo ? PT_RESIDENT_ALBEDO : 0u) | (bin_albedo ? PT_RESIDENT_BIN_ALBEDO : 0u);
     return PT_OK;
@@ -2588,6 +2543,40 @@ pt_status pt_resident_read(pt_scene* sc, float* film, uint32_t* sample_counts, d
     HIP_TRY(hipStreamSynchronize(stream));
     return PT_OK;
 }
+// ---- What the two resident filters share.  The scratch of the film's passes on the resident set (it holds nothing between calls), then the entry's `own`
+// buffers, in that order; a want of zero bytes is skipped.
+struct Want { GrowBuf* buf; size_t bytes; };
+static pt_status reserve_filter_buffers(ResidentSet& r, size_t np, std::initializer_list<Want> own) {
+    std::vector<Want> wants = {{&r.color[0], 16 * np}, {&r.color[1], 16 * np}, {&r.geo, 16 * np}, {&r.tent, 4 * np}, {&r.flags, np}, {&r.grad, 8 * np}};
+    wants.insert(wants.end(), own);
+    for (const Want& w : wants) {
+        const pt_status st = w.bytes ? w.buf->reserve(w.bytes) : PT_OK;
+        if (st != PT_OK) return st;
+    }
+    return PT_OK;
+}
+// a run over the resident sources, albedo included where it is resident, with that scratch; everything else zero
+static ptk::DnRun resident_filter_run(const ResidentSet& r) {
+    ptk::DnRun run;
+    memset(&run, 0, sizeof(run));
+    run.film = r.film; run.counts = r.counts; run.stats = r.stats; run.guides = r.guides.as<float>();
+    run.albedo = (r.parts & PT_RESIDENT_ALBEDO) ? r.albedo.as<float>() : nullptr;
+    run.color[0] = r.color[0].as<float>(); run.color[1] = r.color[1].as<float>(); run.geo = r.geo.as<float>(); run.tent = r.tent.as<float>();
+    run.flags = r.flags.as<uint8_t>(); run.grad = r.grad.as<float>();
+    return run;
+}
+// the run's launches on the null stream, the outputs that are asked for back, and the synchronise.  `out_planes` (may be null): planes_bytes of what the run
+// filtered beside the film — a group run's denoised group films, otherwise the denoised bins, which lie where dn_run says
+static pt_status run_resident_filter(const pt_denoise_desc& d, ptk::DnRun* run, size_t np, float* out_film, float* out_variance, float* out_planes, size_t planes_bytes) {
+    const hipStream_t stream = nullptr;
+    ptk::dn_run(d, run, stream);
+    HIP_TRY(hipGetLastError());
+    if (out_film) HIP_TRY(hipMemcpyAsync(out_film, run->out_film, 16 * np, hipMemcpyDeviceToHost, stream));
+    if (out_variance) HIP_TRY(hipMemcpyAsync(out_variance, run->out_variance, 4 * np, hipMemcpyDeviceToHost, stream));
+    if (out_planes) HIP_TRY(hipMemcpyAsync(out_planes, run->groups ? run->out_groups : run->denoised_bins, planes_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PT_OK;
+}
 // The filter where the film is: ptk::dn_run (pt_denoise.hip), the run the host-array entries make between their upload and their read-back, on the resident
 // buffers and the null stream — the stream of the render and the guide pass.  The sources are read only; the scratch and the outputs are the scene's.
 pt_status pt_denoise_resident(pt_scene* sc, const pt_resident_denoise_desc* desc, float* out_film, float* out_variance, float* out_spectral) {
@@ -2600,34 +2589,20 @@ pt_status pt_denoise_resident(pt_scene* sc, const pt_resident_denoise_desc* desc
     const size_t np = (size_t)r.width * r.height;
     const bool has_bins = (r.parts & PT_RESIDENT_BINS) != 0u, quads = has_bins && !(desc->flags & PT_RESIDENT_PLANAR_GATHER);
     r.parts &= ~(PT_RESIDENT_DENOISED | PT_RESIDENT_DENOISED_BINS);
-    struct Want { GrowBuf* buf; size_t bytes; };
-    const size_t bin_buf_bytes = has_bins ? ptk::dn_bin_buf_bytes(np, r.bins, quads) : 0;
-    const Want wants[] = {{&r.color[0], 16 * np}, {&r.color[1], 16 * np}, {&r.geo, 16 * np}, {&r.tent, 4 * np}, {&r.flags, np}, {&r.grad, 8 * np}, {&r.den_film, 16 * np},
-                          {&r.den_var, 4 * np}, {&r.bin_buf[0], bin_buf_bytes}, {&r.bin_buf[1], bin_buf_bytes}, {&r.den_bins, quads ? 4 * np * r.bins : 0}};
-    for (const Want& w : wants) {
-        st = w.bytes ? w.buf->reserve(w.bytes) : PT_OK;
-        if (st != PT_OK) return st;
-    }
-    ptk::DnRun run;
-    memset(&run, 0, sizeof(run));
-    run.film = r.film; run.counts = r.counts; run.stats = r.stats; run.guides = r.guides.as<float>();
-    run.albedo = (r.parts & PT_RESIDENT_ALBEDO) ? r.albedo.as<float>() : nullptr;
+    const size_t bin_buf_bytes = has_bins ? ptk::dn_bin_buf_bytes(np, r.bins, quads) : 0;   // (without bins, and for den_bins without quads: zero bytes, skipped)
+    st = reserve_filter_buffers(r, np, {{&r.den_film, 16 * np}, {&r.den_var, 4 * np}, {&r.bin_buf[0], bin_buf_bytes}, {&r.bin_buf[1], bin_buf_bytes},
+                                        {&r.den_bins, quads ? 4 * np * r.bins : 0}});
+    if (st != PT_OK) return st;
+    ptk::DnRun run = resident_filter_run(r);
     if (has_bins) {
         run.bins = r.bins; run.spectral = r.spectral;
         run.bin_albedo = (r.parts & PT_RESIDENT_BIN_ALBEDO) ? r.bin_albedo.as<float>() : nullptr;
         run.bin_buf[0] = r.bin_buf[0].as<float>(); run.bin_buf[1] = r.bin_buf[1].as<float>();
         run.quads = quads; run.out_bins = quads ? r.den_bins.as<float>() : nullptr;
     }
-    run.color[0] = r.color[0].as<float>(); run.color[1] = r.color[1].as<float>(); run.geo = r.geo.as<float>(); run.tent = r.tent.as<float>();
-    run.flags = r.flags.as<uint8_t>(); run.grad = r.grad.as<float>();
     run.out_film = r.den_film.as<float>(); run.out_variance = r.den_var.as<float>();
-    const hipStream_t stream = nullptr;
-    ptk::dn_run(d, &run, stream);
-    HIP_TRY(hipGetLastError());
-    if (out_film) HIP_TRY(hipMemcpyAsync(out_film, run.out_film, 16 * np, hipMemcpyDeviceToHost, stream));
-    if (out_variance) HIP_TRY(hipMemcpyAsync(out_variance, run.out_variance, 4 * np, hipMemcpyDeviceToHost, stream));
-    if (out_spectral) HIP_TRY(hipMemcpyAsync(out_spectral, run.denoised_bins, 4 * np * r.bins, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    st = run_resident_filter(d, &run, np, out_film, out_variance, out_spectral, 4 * np * r.bins);
+    if (st != PT_OK) return st;
     r.denoised_bins = run.denoised_bins;
     r.parts |= PT_RESIDENT_DENOISED | (has_bins ? PT_RESIDENT_DENOISED_BINS : 0u);
     return PT_OK;
@@ -2645,29 +2620,15 @@ pt_status pt_denoise_light_groups_resident(pt_scene* sc, const pt_resident_denoi
     HIP_TRY(hipSetDevice(sc->device));
     sc->groups_denoised = false;
     const size_t np = (size_t)r.width * r.height, group_bytes = 16 * np * sc->groups_count;
-    struct Want { GrowBuf* buf; size_t bytes; };
-    const Want wants[] = {{&r.color[0], 16 * np}, {&r.color[1], 16 * np}, {&r.geo, 16 * np}, {&r.tent, 4 * np}, {&r.flags, np}, {&r.grad, 8 * np}, {&sc->group_den_film, 16 * np},
-                          {&sc->group_den_var, 4 * np}, {&sc->group_dn_buf[0], group_bytes}, {&sc->group_dn_buf[1], group_bytes}, {&sc->group_den_films, group_bytes}};
-    for (const Want& w : wants) {
-        st = w.buf->reserve(w.bytes);
-        if (st != PT_OK) return st;
-    }
-    ptk::DnRun run;
-    memset(&run, 0, sizeof(run));
-    run.film = r.film; run.counts = r.counts; run.stats = r.stats; run.guides = r.guides.as<float>();
-    run.albedo = (r.parts & PT_RESIDENT_ALBEDO) ? r.albedo.as<float>() : nullptr;
-    run.color[0] = r.color[0].as<float>(); run.color[1] = r.color[1].as<float>(); run.geo = r.geo.as<float>(); run.tent = r.tent.as<float>();
-    run.flags = r.flags.as<uint8_t>(); run.grad = r.grad.as<float>();
+    st = reserve_filter_buffers(r, np, {{&sc->group_den_film, 16 * np}, {&sc->group_den_var, 4 * np}, {&sc->group_dn_buf[0], group_bytes}, {&sc->group_dn_buf[1], group_bytes},
+                                        {&sc->group_den_films, group_bytes}});   // (none of them zero bytes: a checked call has pixels and groups)
+    if (st != PT_OK) return st;
+    ptk::DnRun run = resident_filter_run(r);
     run.out_film = sc->group_den_film.as<float>(); run.out_variance = sc->group_den_var.as<float>();
     run.groups = sc->groups_count; run.group_films = sc->group_films_cache.as<float>();
     run.group_buf[0] = sc->group_dn_buf[0].as<float>(); run.group_buf[1] = sc->group_dn_buf[1].as<float>(); run.out_groups = sc->group_den_films.as<float>();
-    const hipStream_t stream = nullptr;
-    ptk::dn_run(d, &run, stream);
-    HIP_TRY(hipGetLastError());
-    if (out_film) HIP_TRY(hipMemcpyAsync(out_film, run.out_film, 16 * np, hipMemcpyDeviceToHost, stream));
-    if (out_variance) HIP_TRY(hipMemcpyAsync(out_variance, run.out_variance, 4 * np, hipMemcpyDeviceToHost, stream));
-    if (out_group_films) HIP_TRY(hipMemcpyAsync(out_group_films, run.out_groups, group_bytes, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    st = run_resident_filter(d, &run, np, out_film, out_variance, out_group_films, group_bytes);
+    if (st != PT_OK) return st;
     sc->groups_denoised = true;
     return PT_OK;
 }

@@ -432,6 +432,41 @@ def test_gpu_rendered_film_filtered_and_developed_where_it_lies(engine, pkg, cha
     sc.close()
 
 
+@pytest.fixture(scope="module")
+def slab_film(engine, pkg):
+    """One adaptive spectral render of the glass-slab scene, 33 x 17 with 4 bins, left resident on its scene and never written: 561 pixels are more than one
+    256-thread block, no multiple of 64 and end in a ragged wave; the slab gives the guide samples chains of both lengths."""
+    sc = engine.create_scene(pkg.scene.cornell_checker_slab())
+    rd = pkg.api.render_desc(33, 17, 10, 4)
+    film, counts, stats, spectral, _ = sc.render_adaptive_spectral(rd, 4, 20, 0.05, stats=True)
+    for arr in (film, counts, stats, spectral):
+        arr.setflags(write=False)
+    yield sc, rd, (film, counts, stats), spectral
+    sc.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("albedo,bin_albedo", ((False, False), (True, False), (True, True)))
+@pytest.mark.parametrize("chain", (0, 3))
+def test_gpu_resident_guide_pass_in_every_form_filtered_where_it_lies(engine, pkg, slab_film, chain, albedo, bin_albedo):
+    """resident_guides at the first hit and with a chain of 3, with guides only, with the albedo and with both albedos (3 guide samples), then denoise_resident
+    in both forms against the host-array filter over what the host-array guide entry of the same form returned."""
+    a = pkg.api
+    sc, rd, inputs, spectral = slab_film
+    sc.resident_guides(rd, 3, specular_chain=chain, albedo=albedo, bin_albedo=bin_albedo)
+    assert sc.resident_info() == (33, 17, 4, a.RESIDENT_FILM | a.RESIDENT_BINS | a.RESIDENT_GUIDES | (a.RESIDENT_ALBEDO if albedo else 0) |
+                                  (a.RESIDENT_BIN_ALBEDO if bin_albedo else 0))
+    if bin_albedo:
+        guides, alb, balb = sc.render_guides_bin_albedo(rd, 4, 3, chain)
+    elif chain:
+        guides, alb, balb = sc.render_guides_chain(rd, 3, chain, albedo=albedo) + (None,)
+    else:
+        guides, alb, balb = sc.render_guides_albedo(rd, 3) + (None,) if albedo else (sc.render_guides(rd, 3), None, None)
+    want = host_call(engine, inputs + (guides,), spectral, alb, balb)
+    assert_same(resident_call(sc), want, (chain, albedo, bin_albedo, "quads"))
+    assert_same(resident_call(sc, planar=True), want, (chain, albedo, bin_albedo, "planar"))
+
+
 @pytest.mark.gpu
 def test_gpu_film_only_after_render_adaptive(engine, pkg):
     """After render_adaptive there are no bins: the resident filter is denoise_film, and with resident_guides(albedo=True) denoise_film_albedo."""

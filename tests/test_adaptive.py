@@ -11,25 +11,18 @@ import tempfile
 import numpy as np
 import pytest
 
+import emulation
+from util import PT_ERR_INVALID_ARGUMENT, PT_ERR_UNSUPPORTED, PT_OK
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-EMU_DIR = os.path.join(HERE, "host_emulation")
-CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
-PT_OK, PT_ERR_INVALID_ARGUMENT, PT_ERR_UNSUPPORTED = 0, 1, 4
 u32p, f64p = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
 
 
 @pytest.fixture(scope="session")
 def emu_ad(pkg):
     """The host emulation (tests/host_emulation/ptemu.cpp) with the adaptive driver (ptemu_adaptive.cpp) beside it: a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_adaptive.so")
-    srcs = [os.path.join(EMU_DIR, "ptemu.cpp"), os.path.join(EMU_DIR, "ptemu_adaptive.cpp"), os.path.join(CSRC, "pt_scene_host.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_adaptive_select.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
-                               "-Wno-unused-function", "-o", lib] + srcs)
-    emu = pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    emu = emulation.load(pkg, "adaptive")
     sel = emu.lib.ptemu_adaptive_select
     sel.restype = C.c_int32
     sel.argtypes = [C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_uint32, f64p, C.c_uint32, C.c_float, C.c_float, u32p, C.POINTER(C.c_uint8), u32p, u32p]

@@ -11,13 +11,12 @@ import subprocess
 import numpy as np
 import pytest
 
+import emulation
 from test_adaptive import ADAPTIVE_CONFIG, np_dilate, np_unconverged, pick_rel
+from util import PT_ERR_INVALID_ARGUMENT, PT_ERR_UNSUPPORTED, PT_OK
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-EMU_DIR = os.path.join(HERE, "host_emulation")
-CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
-PT_OK, PT_ERR_INVALID_ARGUMENT, PT_ERR_UNSUPPORTED = 0, 1, 4
 u32p, f64p = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
 W, H = 77, 45   # 2 x 1 whole 32 x 32 tiles and remnant tiles on the right, at the bottom and in the corner: 6 tiles
 
@@ -25,15 +24,7 @@ W, H = 77, 45   # 2 x 1 whole 32 x 32 tiles and remnant tiles on the right, at t
 @pytest.fixture(scope="session")
 def emu_am(pkg):
     """The host emulation with the one-device adaptive driver and the sharded one beside it: a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_adaptive_multi.so")
-    srcs = [os.path.join(EMU_DIR, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_adaptive_multi.cpp")] + \
-        [os.path.join(CSRC, "pt_scene_host.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_adaptive_select.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
-                               "-Wno-unused-function", "-o", lib] + srcs)
-    emu = pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    emu = emulation.load(pkg, "adaptive_multi")
     a = pkg.api
     fn = emu.lib.ptemu_render_adaptive_multi
     fn.restype = C.c_int32

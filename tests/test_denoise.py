@@ -11,11 +11,11 @@ import tempfile
 import numpy as np
 import pytest
 
+import emulation
+from util import PT_ERR_INVALID_ARGUMENT, PT_ERR_NO_DEVICE, PT_OK, bits_equal
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-EMU_DIR = os.path.join(HERE, "host_emulation")
-CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
-PT_OK, PT_ERR_INVALID_ARGUMENT, PT_ERR_NO_DEVICE = 0, 1, 2
 F = np.float32
 u32p, f64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_float)
 
@@ -23,13 +23,7 @@ u32p, f64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_f
 @pytest.fixture(scope="session")
 def emu_dn(pkg):
     """The host emulation with the adaptive driver (the statistics come from ptemu_render_adaptive) and the denoiser beside it: a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_denoise.so")
-    srcs = [os.path.join(EMU_DIR, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_denoise.cpp")] + [os.path.join(CSRC, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_adaptive_select.h", "pt_denoise_rules.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_denoise.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-o", lib] + srcs)
-    return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    return emulation.load(pkg, "denoise")
 
 
 # ------------------------------------------------------------------------------------------------ numpy restatement of the definition
@@ -175,11 +169,6 @@ def np_guides(sc, rd, K):
     with np.errstate(all="ignore"):
         g[:, 3] = np.where(hits > 0, zsum / np.maximum(hits, 1).astype(F), F(0.0))
     return g.reshape(rd.height, rd.width, 4)
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, F), np.ascontiguousarray(b, F)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 # ------------------------------------------------------------------------------------------------ inputs

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import emulation
 import test_denoise as td
 from test_denoise import F, PT_ERR_INVALID_ARGUMENT, PT_ERR_NO_DEVICE, PT_OK, bits_equal, f32p, f64p, u32p
 
@@ -23,14 +24,7 @@ def builder_of(pkg, name):
 @pytest.fixture(scope="session")
 def emu_al(pkg):
     """test_denoise.py's emulation library plus ptemu_denoise_albedo.cpp: a library of its own."""
-    lib = os.path.join(td.EMU_DIR, "libptemu_denoise_albedo.so")
-    srcs = [os.path.join(td.EMU_DIR, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_denoise.cpp", "ptemu_denoise_albedo.cpp")] + \
-        [os.path.join(td.CSRC, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
-    deps = srcs + [os.path.join(td.CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_adaptive_select.h", "pt_denoise_rules.h")] + \
-        [os.path.join(td.ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_denoise.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-o", lib] + srcs)
-    return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    return emulation.load(pkg, "denoise_albedo")
 
 
 # ------------------------------------------------------------------------------------------------ numpy restatement of the definition

@@ -12,15 +12,14 @@ import tempfile
 import numpy as np
 import pytest
 
+import emulation
 from test_denoise import (OFF_DEFAULT, _inside, _tap, _two_class_inputs, bits_equal, np_kwargs, np_pt_exp, np_pt_min, np_variance, spread_rel,
                           synthetic_inputs)
 from test_spectral import check_spectral_exr, scaled_c2_config
+from util import PT_ERR_INVALID_ARGUMENT, PT_ERR_NO_DEVICE, PT_ERR_UNSUPPORTED, PT_OK
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-EMU_DIR = os.path.join(HERE, "host_emulation")
-CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
-PT_OK, PT_ERR_INVALID_ARGUMENT, PT_ERR_NO_DEVICE, PT_ERR_UNSUPPORTED = 0, 1, 2, 4
 F = np.float32
 u32p, f64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_float)
 
@@ -28,15 +27,7 @@ u32p, f64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_f
 @pytest.fixture(scope="session")
 def emu_ds(pkg):
     """The host emulation with the adaptive driver, the film denoiser and the joint filter beside it: a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_denoise_spectral.so")
-    srcs = [os.path.join(EMU_DIR, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_denoise.cpp", "ptemu_denoise_spectral.cpp")] + \
-        [os.path.join(CSRC, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_adaptive_select.h", "pt_denoise_rules.h",
-                                                   "pt_denoise_spectral_rules.h", "pt_spectral_rules.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_denoise.h", "pt_spectral.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-o", lib] + srcs)
-    L = pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    L = emulation.load(pkg, "denoise_spectral")
     a = pkg.api
     L.lib.ptemu_denoise_spectral_last_error.restype = C.c_char_p
     L.lib.ptemu_spectral_finish.restype = C.c_int32

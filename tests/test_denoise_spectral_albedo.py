@@ -13,17 +13,16 @@ import tempfile
 import numpy as np
 import pytest
 
+import emulation
 import test_denoise as td
 import test_denoise_albedo as ta
 import test_denoise_spectral as ts
 from test_denoise import OFF_DEFAULT, bits_equal, np_kwargs, np_variance, synthetic_inputs
 from test_spectral import check_spectral_exr, scaled_c2_config
+from util import PT_ERR_INVALID_ARGUMENT, PT_ERR_NO_DEVICE, PT_ERR_UNSUPPORTED, PT_OK
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-EMU_DIR = os.path.join(HERE, "host_emulation")
-CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
-PT_OK, PT_ERR_INVALID_ARGUMENT, PT_ERR_NO_DEVICE, PT_ERR_UNSUPPORTED = 0, 1, 2, 4
 F = np.float32
 FLOOR = F(1e-3)
 u32p, f64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -32,16 +31,7 @@ u32p, f64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_f
 @pytest.fixture(scope="session")
 def emu_ba(pkg):
     """The host emulation with the film denoiser, its albedo form, the chain guides, the joint filter and the per-bin albedo beside it: a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_denoise_spectral_albedo.so")
-    srcs = [os.path.join(EMU_DIR, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_denoise.cpp", "ptemu_denoise_albedo.cpp", "ptemu_guides_chain.cpp",
-                                               "ptemu_denoise_spectral.cpp", "ptemu_denoise_spectral_albedo.cpp")] + \
-        [os.path.join(CSRC, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_adaptive_select.h", "pt_denoise_rules.h",
-                                                   "pt_guides_chain_rules.h", "pt_denoise_spectral_rules.h", "pt_spectral_rules.h", "pt_denoise_spectral_albedo_rules.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_denoise.h", "pt_spectral.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-o", lib] + srcs)
-    L = pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    L = emulation.load(pkg, "denoise_spectral_albedo")
     L.lib.ptemu_denoise_spectral_albedo_last_error.restype = C.c_char_p
     return L
 

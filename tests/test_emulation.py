@@ -1,28 +1,19 @@
 """CPU: the HIP engine's lane logic + host planning (emulated sequentially, tests/host_emulation/ptemu.cpp)
 against the oracle.  This is what proves the wavefront decomposition before the GPU is involved."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emulation
 import parity_suite as ps
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-EMU_DIR = os.path.join(HERE, "host_emulation")
-CSRC = os.path.join(HERE, "..", "rust-pathtracer_amd", "csrc")
 
 
 @pytest.fixture(scope="session")
 def emu(pkg):
-    lib = os.path.join(EMU_DIR, "libptemu.so")
-    srcs = [os.path.join(EMU_DIR, "ptemu.cpp"), os.path.join(CSRC, "pt_scene_host.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h")] + \
-        [os.path.join(HERE, "..", "include", h) for h in ("pt_api.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
-                               "-Wno-unused-function", "-o", lib] + srcs)
-    return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    return emulation.load(pkg, "ptemu")
 
 
 @pytest.mark.parametrize("scene", ["cornell_box", "cornell_gem", "mixed_primitives", "mixed_small", "white_furnace", "hdri_small", "hdri_c4_small"])

@@ -13,12 +13,12 @@ import subprocess
 import numpy as np
 import pytest
 
+import emulation
 import parity_suite as ps
-from util import film_metrics
+from util import bits, film_metrics, ptcli, same_bits
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.join(HERE, "..")
-EMU_DIR = os.path.join(HERE, "host_emulation")
 CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "pt_light_groups.h")
 f32 = np.float32
@@ -32,14 +32,6 @@ def room_rd(pkg):
     return pkg.api.render_desc(24, 24, 23, 5, light_samples=2, seed=7)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, f32).view(np.uint32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
-
-
 def counters(p):
     return (p.camera_rays, p.bounce_rays, p.shadow_rays, p.env_hits)
 
@@ -47,15 +39,7 @@ def counters(p):
 @pytest.fixture(scope="session")
 def emu_lg(pkg):
     """The host emulation (ptemu.cpp) with the light-group render and mix (ptemu_light_groups.cpp) beside it: a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_light_groups.so")
-    srcs = [os.path.join(EMU_DIR, "ptemu.cpp"), os.path.join(EMU_DIR, "ptemu_light_groups.cpp"), os.path.join(CSRC, "pt_scene_host.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(EMU_DIR, "ptemu_routed_pass.h")] + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_light_group_rules.h",
-                                                                                                    "pt_path_pass_rules.h", "pt_routed_rules.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_debug.h", "pt_numerics.h", "pt_light_groups.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-Wno-unknown-pragmas",
-                               "-o", lib] + srcs)
-    return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    return emulation.load(pkg, "light_groups")
 
 
 @pytest.fixture(scope="session")
@@ -235,10 +219,6 @@ def scaled_c2_config(pkg):
     text, n3 = re.subn(r"only_direct = false\n", "only_direct = false\npremultiply = 2.0\n", text)
     assert (n1, n2, n3) == (1, 1, 1)
     return text
-
-
-def ptcli(pkg):
-    return os.path.join(pkg.PACKAGE_DIR, "csrc", "ptcli")
 
 
 def test_ptcli_flags_while_parsing(pkg):

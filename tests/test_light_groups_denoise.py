@@ -14,15 +14,16 @@ import subprocess
 import numpy as np
 import pytest
 
+import emulation
 import parity_suite as ps
 import test_denoise_albedo as ta
 import test_denoise_spectral as ts
 from test_denoise import OFF_DEFAULT, np_variance, synthetic_inputs
 from test_light_groups import ROOM_ENV_GROUP, ROOM_GROUPS, clean_tuning, counters, mix_numpy, same_bits, scaled_c2_config
+from util import ptcli
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.join(HERE, "..")
-EMU_DIR = os.path.join(HERE, "host_emulation")
 CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "pt_light_groups_denoise.h")
 f32 = np.float32
@@ -44,20 +45,7 @@ def quality_rd(pkg, spp, seed, size=32):
 @pytest.fixture(scope="session")
 def emu(pkg):
     """The host emulation with the adaptive driver, the group render, the adaptive group render, the guides and every filter beside it: a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_light_groups_denoise.so")
-    srcs = [os.path.join(EMU_DIR, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_light_groups.cpp", "ptemu_adaptive_light_groups.cpp", "ptemu_denoise.cpp",
-                                               "ptemu_denoise_albedo.cpp", "ptemu_guides_chain.cpp", "ptemu_denoise_spectral.cpp", "ptemu_denoise_spectral_albedo.cpp",
-                                               "ptemu_denoise_light_groups.cpp")] + [os.path.join(CSRC, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
-    deps = srcs + [os.path.join(EMU_DIR, "ptemu_routed_pass.h")] + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_adaptive_select.h", "pt_denoise_rules.h",
-                                                   "pt_guides_chain_rules.h", "pt_denoise_spectral_rules.h", "pt_denoise_spectral_albedo_rules.h",
-                                                   "pt_denoise_resident_rules.h", "pt_denoise_light_groups_rules.h", "pt_light_group_rules.h", "pt_path_pass_rules.h",
-                                                   "pt_routed_rules.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_denoise.h", "pt_spectral.h", "pt_numerics.h", "pt_light_groups.h",
-                                                    "pt_light_groups_denoise.h", "pt_resident.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-Wno-unknown-pragmas",
-                               "-o", lib] + srcs)
-    return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    return emulation.load(pkg, "light_groups_denoise")
 
 
 @pytest.fixture(scope="session")
@@ -331,10 +319,6 @@ def test_header_compiles_alone_in_c_and_the_library_exports_the_entries(pkg, tmp
     rules = open(os.path.join(CSRC, "pt_light_group_rules.h")).read()
     assert "PT_HD void lg_adaptive_finish_pixel" in rules
     assert "dn_groups_prepare_pixel" in open(os.path.join(CSRC, "pt_denoise_light_groups_rules.h")).read()
-
-
-def ptcli(pkg):
-    return os.path.join(pkg.PACKAGE_DIR, "csrc", "ptcli")
 
 
 def test_ptcli_flag_while_parsing(pkg):

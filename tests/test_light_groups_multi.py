@@ -13,38 +13,27 @@ import subprocess
 import numpy as np
 import pytest
 
+import emulation
 from test_adaptive import pick_rel
 from test_adaptive_multi import _hip_current_device
 from test_light_groups import ROOM_ENV_GROUP, ROOM_GROUPS, clean_tuning, emissive_mesh_scene, scaled_c2_config
 from test_spectral_multi import np_shard_pixels
+from util import PT_ERR_INVALID_ARGUMENT, PT_ERR_UNSUPPORTED, PT_OK, bits, ptcli
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-EMU_DIR = os.path.join(HERE, "host_emulation")
 CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "pt_light_groups_multi.h")
-PT_OK, PT_ERR_INVALID_ARGUMENT, PT_ERR_UNSUPPORTED = 0, 1, 4
 u32p, f32p, f64p = C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_double)
 F = np.float32
 W, H = 77, 45   # 2 x 1 whole 32 x 32 tiles and remnant tiles on the right, at the bottom and in the corner: 6 tiles
 COUNTERS = ("camera_rays", "bounce_rays", "shadow_rays", "light_rays", "env_hits")
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 @pytest.fixture(scope="session")
 def emu_gs(pkg):
     """The packed group shard's rule and the node entries' argument checks on the host (ptemu_light_groups_shard.cpp beside the engine's pt_plan.cpp)."""
-    lib = os.path.join(EMU_DIR, "libptemu_light_groups_shard.so")
-    srcs = [os.path.join(EMU_DIR, "ptemu_light_groups_shard.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_plan.h", "pt_shard_rules.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_light_groups.h", "pt_light_groups_denoise.h", "pt_light_groups_multi.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
-                               "-Wno-unused-function", "-Wno-unknown-pragmas", "-o", lib] + srcs)
-    L = C.CDLL(lib)
+    L = C.CDLL(emulation.library_path("light_groups_shard"))
     a = pkg.api
     L.ptemu_light_groups_shard_last_error.restype = C.c_char_p
     L.ptemu_lg_shard_pixels.restype = C.c_uint32
@@ -250,10 +239,6 @@ def test_the_node_entries_refuse_each_bad_argument_with_its_own_message(emu_gs, 
     assert L._render_adaptive_light_groups_multi(None, C.byref(rd), C.byref(ad), C.byref(gd), 0, film.ctypes.data_as(f32p), counts.ctypes.data_as(u32p), None, None,
                                                  None) == INV
     assert L.last_error() == flat["fixed_scene"]
-
-
-def ptcli(pkg):
-    return os.path.join(pkg.PACKAGE_DIR, "csrc", "ptcli")
 
 
 def test_ptcli_refuses_bad_light_group_devices_while_parsing(pkg, tmp_path):

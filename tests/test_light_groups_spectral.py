@@ -16,12 +16,12 @@ import subprocess
 import numpy as np
 import pytest
 
+import emulation
 import parity_suite as ps
 from test_light_groups import ONLY, ROOM_ENV_GROUP, ROOM_GROUPS, clean_tuning, counters, ptcli, room_rd, same_bits, scaled_c2_config
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.join(HERE, "..")
-EMU_DIR = os.path.join(HERE, "host_emulation")
 CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "pt_light_groups_spectral.h")
 FRAMES = os.path.join(ROOT, "profiles", "light_groups_spectral_frames.json")
@@ -40,17 +40,7 @@ def fptr(a):
 def emu_lgs(pkg):
     """The host emulation (ptemu.cpp) with the group render (ptemu_light_groups.cpp), the development rules (ptemu_spectral_project.cpp) and the spectral group
     render, the matrix and the re-lamp (ptemu_light_groups_spectral.cpp) beside it: a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_light_groups_spectral.so")
-    srcs = [os.path.join(EMU_DIR, f) for f in ("ptemu.cpp", "ptemu_light_groups.cpp", "ptemu_spectral_project.cpp", "ptemu_light_groups_spectral.cpp")] + \
-        [os.path.join(CSRC, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
-    deps = srcs + [os.path.join(EMU_DIR, "ptemu_routed_pass.h")] + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_light_group_rules.h",
-                                                                                                    "pt_path_pass_rules.h", "pt_routed_rules.h", "pt_spectral_rules.h",
-                                                   "pt_spectral_project_rules.h", "pt_light_groups_spectral_rules.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_debug.h", "pt_numerics.h", "pt_light_groups.h", "pt_spectral.h", "pt_light_groups_spectral.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-Wno-unknown-pragmas",
-                               "-o", lib] + srcs)
-    return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    return emulation.load(pkg, "light_groups_spectral")
 
 
 def room(pkg, **kw):

@@ -11,11 +11,11 @@ import subprocess
 import numpy as np
 import pytest
 
+import emulation
+from util import PT_ERR_INVALID_ARGUMENT
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-EMU_DIR = os.path.join(HERE, "host_emulation")
-CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
-PT_OK, PT_ERR_INVALID_ARGUMENT = 0, 1
 F = np.float32
 u32p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_float)
 SKY, NONE = 0xFFFFFFFE, 0xFFFFFFFF
@@ -27,13 +27,7 @@ PARENT_SPECTRAL_EXR_SHA256 = "bc7958a2c2d05386524573f9e1839cdfc2dbcefd59e4b1daf0
 @pytest.fixture(scope="session")
 def emu_mt(pkg):
     """The host emulation (ptemu.cpp) with the mattes (ptemu_matte.cpp) beside it: a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_matte.so")
-    srcs = [os.path.join(EMU_DIR, "ptemu.cpp"), os.path.join(EMU_DIR, "ptemu_matte.cpp"), os.path.join(CSRC, "pt_scene_host.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_matte_rules.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_denoise.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-o", lib] + srcs)
-    return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    return emulation.load(pkg, "matte")
 
 
 def bits_equal(a, b):

@@ -3,14 +3,13 @@ with the square-root mapping over the face, area pdf 1 / A_f.  The reference can
 so there is no oracle: the CPU tier checks the sampler bit for bit against a float32 restatement of the definition and the film under the
 emulation's switches; the GPU tier compares estimators whose expectations agree, forms that must agree bit for bit, and the GPU with the emulation."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emulation
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-EMU_DIR = os.path.join(HERE, "host_emulation")
-CSRC = os.path.join(HERE, "..", "rust-pathtracer_amd", "csrc")
 f32 = np.float32
 
 # the Cornell box's lamp (scene.cornell_box): a one-sided rect, normal +z
@@ -20,14 +19,7 @@ LAMP_SIZE, LAMP_ORIGIN = (0.105, 0.13), (0.278, 0.2795, 0.5487)
 @pytest.fixture(scope="session")
 def emu_ml(pkg):
     """The host emulation (tests/host_emulation/ptemu.cpp) with the light sampler's export (ptemu_light.cpp) beside it: a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_mesh_lights.so")
-    srcs = [os.path.join(EMU_DIR, "ptemu.cpp"), os.path.join(EMU_DIR, "ptemu_light.cpp"), os.path.join(CSRC, "pt_scene_host.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h")] + \
-        [os.path.join(HERE, "..", "include", h) for h in ("pt_api.h", "pt_debug.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
-                               "-Wno-unused-function", "-o", lib] + srcs)
-    return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    return emulation.load(pkg, "mesh_lights")
 
 
 # ------------------------------------------------------------------------------------------------ scenes

@@ -43,11 +43,8 @@ import pytest  # noqa: E402
 @pytest.mark.parametrize("world", [2, 8])
 def test_n_process_gloo_reduce_equals_single_process(pkg, tmp_path, world):
     """(world = 8: the rank count of the driver's 8-GPU run — PT_TILE_SHARD(t, 8) across eight processes, the weak-scaling sample ranges, one reduce.)"""
-    import test_emulation  # builds libptemu.so on demand
-    lib = os.path.join(HERE, "host_emulation", "libptemu.so")
-    if not os.path.exists(lib):
-        test_emulation.emu.__wrapped__(pkg) if hasattr(test_emulation.emu, "__wrapped__") else None
-    assert os.path.exists(lib), "run tests/test_emulation.py first (it builds the emulation harness)"
+    import emulation
+    lib = emulation.library_path("ptemu")   # (the workers load it by this path)
     out = str(tmp_path / "film.npy")
     script = tmp_path / "worker.py"
     script.write_text(WORKER.format(root=ROOT, here=HERE, out=out))

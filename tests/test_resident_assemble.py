@@ -13,16 +13,16 @@ import subprocess
 import numpy as np
 import pytest
 
+import emulation
 from test_adaptive import pick_rel
 from test_adaptive_multi import _hip_current_device
 from test_spectral import scaled_c2_config
 from test_spectral_multi import BINS, FILMS, H, W, bits, np_shard_pixels, random_planes, tuned_scene
+from util import PT_ERR_INVALID_ARGUMENT, PT_ERR_UNSUPPORTED, PT_OK, ptcli
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-EMU_DIR = os.path.join(HERE, "host_emulation")
 CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
-PT_OK, PT_ERR_INVALID_ARGUMENT, PT_ERR_UNSUPPORTED = 0, 1, 4
 u32p, f32p, f64p = C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_double)
 F = np.float32
 SHARDS = (1, 2, 3, 4, 8)          # the shard counts of tests/test_spectral_multi.py
@@ -34,14 +34,7 @@ WITHOUT_STATS = "made without stats"
 @pytest.fixture(scope="session")
 def emu_as(pkg):
     """The unpack rule and pt_resident_assemble's checks on the host, beside the pack rule and the shard lists (ptemu_spectral_shard.cpp): a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_resident_assemble.so")
-    srcs = [os.path.join(EMU_DIR, "ptemu_resident_assemble.cpp"), os.path.join(EMU_DIR, "ptemu_spectral_shard.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_plan.h", "pt_shard_rules.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_adaptive.h", "pt_spectral.h", "pt_resident.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
-                               "-Wno-unused-function", "-Wno-unknown-pragmas", "-o", lib] + srcs)
-    L = C.CDLL(lib)
+    L = C.CDLL(emulation.library_path("resident_assemble"))
     L.ptemu_resident_assemble_last_error.restype = C.c_char_p
     L.ptemu_shard_pixels.restype = C.c_uint32
     L.ptemu_shard_pixels.argtypes = [C.c_uint32] * 6 + [C.c_void_p, C.c_uint32]
@@ -188,10 +181,6 @@ def test_python_refuses_assemble_without_a_device_mask(pkg):
             sc.render_denoised(rd, 20, 0.05, resident=True, device_mask=1, **kw)
         with pytest.raises(a.PtError, match=r"render_denoised_spectral: resident=True takes no device_mask \(a node render leaves no film one device can filter\)"):
             sc.render_denoised_spectral(rd, 5, 20, 0.05, resident=True, device_mask=1, **kw)
-
-
-def ptcli(pkg):
-    return os.path.join(pkg.PACKAGE_DIR, "csrc", "ptcli")
 
 
 def test_ptcli_refuses_bad_denoise_assemble_while_parsing(pkg, tmp_path):

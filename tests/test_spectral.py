@@ -12,13 +12,12 @@ import tempfile
 import numpy as np
 import pytest
 
+import emulation
 from test_emulation import emu  # noqa: F401  (fixture: libptemu.so, for ptemu_xyz_bar)
+from util import PT_ERR_INVALID_ARGUMENT, PT_OK, bits
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-EMU_DIR = os.path.join(HERE, "host_emulation")
-CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
-PT_OK, PT_ERR_INVALID_ARGUMENT = 0, 1
 u32p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_float)
 F = np.float32
 
@@ -27,21 +26,10 @@ def fptr(a):
     return a.ctypes.data_as(f32p)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 @pytest.fixture(scope="session")
 def emu_sp(pkg):
     """The rules of the spectral film on the host (tests/host_emulation/ptemu_spectral.cpp beside the engine's pt_plan.cpp): a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_spectral.so")
-    srcs = [os.path.join(EMU_DIR, "ptemu_spectral.cpp"), os.path.join(CSRC, "pt_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_plan.h", "pt_spectral_rules.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_spectral.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
-                               "-Wno-unused-function", "-o", lib] + srcs)
-    L = C.CDLL(lib)
+    L = C.CDLL(emulation.library_path("spectral"))
     a = pkg.api
     L.ptemu_spectral_last_error.restype = C.c_char_p
     L.ptemu_spectral_bins.restype = C.c_int32

@@ -12,15 +12,15 @@ import tempfile
 import numpy as np
 import pytest
 
+import emulation
 from test_emulation import emu  # noqa: F401  (fixture: libptemu.so, for ptemu_xyz_bar and the emulation's curve evaluator)
 from test_spectral import scaled_c2_config
+from util import PT_ERR_INVALID_ARGUMENT, PT_OK, bits, ptcli
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-EMU_DIR = os.path.join(HERE, "host_emulation")
 CSRC = os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
 REF = os.path.join(HERE, "golden", "reference_tree")
-PT_OK, PT_ERR_INVALID_ARGUMENT = 0, 1
 u32p, i32p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_float)
 F = np.float32
 BOUNDS = (380.0, 750.0)
@@ -30,21 +30,10 @@ def fptr(a):
     return a.ctypes.data_as(f32p)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 @pytest.fixture(scope="session")
 def emu_pj(pkg):
     """The rules of a development on the host (ptemu_spectral_project.cpp beside the engine's pt_plan.cpp and pt_scene_host.cpp): a library of its own."""
-    lib = os.path.join(EMU_DIR, "libptemu_spectral_project.so")
-    srcs = [os.path.join(EMU_DIR, "ptemu_spectral_project.cpp"), os.path.join(CSRC, "pt_plan.cpp"), os.path.join(CSRC, "pt_scene_host.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pt_device.h", "pt_stages.h", "pt_blob.h", "pt_plan.h", "pt_scene_host.h", "pt_spectral_project_rules.h")] + \
-        [os.path.join(ROOT, "include", h) for h in ("pt_api.h", "pt_spectral.h", "pt_numerics.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
-                               "-Wno-unused-function", "-o", lib] + srcs)
-    L = C.CDLL(lib)
+    L = C.CDLL(emulation.library_path("spectral_project"))
     a = pkg.api
     L.ptemu_spectral_project_last_error.restype = C.c_char_p
     L.ptemu_spectral_project.restype = C.c_int32
@@ -300,10 +289,6 @@ def test_validation_rejects_each_rule_with_its_own_message(emu_pj, pkg):
         lib.spectral_project(np.ones((7, 2, 3), F), bad)
     with pytest.raises(a.PtError, match="subsamples"):
         lib.spectral_observer_matrix(rd, 7, subsamples=17)
-
-
-def ptcli(pkg):
-    return os.path.join(pkg.PACKAGE_DIR, "csrc", "ptcli")
 
 
 def test_ptcli_refuses_bad_develop_arguments_while_parsing(pkg, tmp_path):

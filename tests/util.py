@@ -1,6 +1,27 @@
 import ctypes as C
+import os
 
 import numpy as np
+
+# pt_status of include/pt_api.h
+PT_OK, PT_ERR_INVALID_ARGUMENT, PT_ERR_NO_DEVICE, PT_ERR_UNSUPPORTED = 0, 1, 2, 4
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def bits_equal(a, b):
+    """The same shape and, as f32, the same bits."""
+    a, b = bits(a), bits(b)
+    return a.shape == b.shape and np.array_equal(a, b)
+
+
+same_bits = bits_equal
+
+
+def ptcli(pkg):
+    return os.path.join(pkg.PACKAGE_DIR, "csrc", "ptcli")
 
 
 def fptr(a):

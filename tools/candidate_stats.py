@@ -7,17 +7,15 @@ and of a loop that runs one kind of test per step.  usage: tools/candidate_stats
 import ctypes
 import importlib
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 R = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path.insert(0, R)
+sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
+import emulation  # noqa: E402
 pkg = importlib.import_module("rust-pathtracer_amd")
-lib = os.path.join(R, "tests", "host_emulation", "libptcandstats.so")
-srcs = [os.path.join(R, "tools", "candidate_stats.cpp"), os.path.join(R, "rust-pathtracer_amd", "csrc", "pt_scene_host.cpp"), os.path.join(R, "rust-pathtracer_amd", "csrc", "pt_plan.cpp")]
-subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-o", lib] + srcs)
+lib = emulation.library_path("ptcandstats")
 emu = pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info", "render_multi", "device_count"))
 scene = emu.create_scene(pkg.scene.SCENES[sys.argv[1] if len(sys.argv) > 1 else "cornell_box"]())
 scene.render(pkg.api.render_desc(64, 64, 4, 8, light_samples=2))

@@ -26,7 +26,6 @@ import importlib
 import json
 import os
 import statistics
-import subprocess
 import sys
 import time
 
@@ -52,12 +51,9 @@ def timed(fn, reps):
 
 
 def emulation_library(pkg):
-    emu_dir, csrc = os.path.join(ROOT, "tests", "host_emulation"), os.path.join(ROOT, "rust-pathtracer_amd", "csrc")
-    lib = os.path.join(emu_dir, "libptemu_guides_chain.so")
-    srcs = [os.path.join(emu_dir, f) for f in ("ptemu.cpp", "ptemu_adaptive.cpp", "ptemu_denoise.cpp", "ptemu_denoise_albedo.cpp", "ptemu_guides_chain.cpp")] + [os.path.join(csrc, f) for f in ("pt_scene_host.cpp", "pt_plan.cpp")]
-    if not os.path.exists(lib):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function", "-o", lib] + srcs)
-    return pkg.api.Library(lib, "ptemu_", optional=("render_device", "device_info"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import emulation
+    return emulation.load(pkg, "guides_chain")
 
 
 def checker_mask(sc, builder, rd):

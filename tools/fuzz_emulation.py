@@ -9,6 +9,7 @@ import numpy as np
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import emulation  # noqa: E402
 import fuzz_scenes  # noqa: E402
 import oracle_loader  # noqa: E402
 import parity_suite as ps  # noqa: E402
@@ -18,7 +19,7 @@ first, count = int(sys.argv[1]), int(sys.argv[2])
 W, H, SPP = (int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])) if len(sys.argv) > 5 else (40, 32, 3)
 if len(sys.argv) > 6:
     os.environ["PTEMU_FLAGS"] = sys.argv[6]
-emu = pkg.api.Library(os.path.join(ROOT, "tests", "host_emulation", "libptemu.so"), "ptemu_", optional=("render_device", "device_info"))
+emu = emulation.load(pkg, "ptemu")
 oracle = oracle_loader.load(pkg)
 SWITCH = os.environ.get("PT_FUZZ_SWITCH", "")   # (several: comma-separated) e.g. PT_AMD_NO_CONVEX (GPU) / PTEMU_NO_CONVEX, PTEMU_NO_INSIDE (emulation)
 bad = []

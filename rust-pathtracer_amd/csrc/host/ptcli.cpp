@@ -105,6 +105,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <initializer_list>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -168,8 +171,8 @@ struct Options {
 const char* const kPathPassNames[PT_PATH_PASSES] = {"emission", "background", "diffuse_direct", "diffuse_indirect", "reflection_direct", "reflection_indirect",
                                                     "transmission_direct", "transmission_indirect"};
 
-int usage(const char* msg) {
-    if (msg) fprintf(stderr, "error: %s\n", msg);
+int usage(const std::string& msg) {   // ("": the usage alone)
+    if (!msg.empty()) fprintf(stderr, "error: %s\n", msg.c_str());
     fprintf(stderr, "usage: ptcli [--config FILE] [--scene FILE] [-n|--dry-run] [--stdout-log-level LEVEL] [--write-log-level LEVEL]\n"
                     "             [--root DIR] [--output-dir DIR] [--seed N] [--write-film] [--hero-wavelengths 1|4] [--adaptive REL] [--devices MASK]\n"
                     "             [--denoise] [--guide-samples K] [--demodulate-albedo] [--guide-chain D] [--guide-alpha-max A]\n"
@@ -197,285 +200,773 @@ bool write_npy(const std::string& path, const float* data, uint32_t h, uint32_t 
     return ok;
 }
 
-}  // namespace
+// ---- the value parsers: a flag's arm of the option loop calls these and keeps its own field, has_* flag and message
 
-int main(int argc, char** argv) {
-    Options o;
+bool parse_count(const std::string& v, unsigned long lo, unsigned long hi, uint32_t* out) {   // a decimal count in [lo, hi], the whole string
+    char* end = nullptr;
+    const unsigned long x = strtoul(v.c_str(), &end, 10);
+    if (end == v.c_str() || *end || x < lo || x > hi) return false;
+    *out = (uint32_t)x;
+    return true;
+}
+
+bool parse_mask(const std::string& v, uint64_t* out) {   // a device mask in any base of strtoull, the whole string
+    char* end = nullptr;
+    *out = strtoull(v.c_str(), &end, 0);
+    return end != v.c_str() && !*end;
+}
+
+bool parse_float(const std::string& v, float* out) {   // the whole string (the caller checks the range)
+    char* end = nullptr;
+    *out = strtof(v.c_str(), &end);
+    return end != v.c_str() && !*end;
+}
+
+int parse_group_mode(const std::string& v) { return v == "instance" ? 1 : v == "material" ? 2 : 0; }
+
+std::vector<std::string> split(const std::string& v) {   // at every comma: "" is one empty item
+    std::vector<std::string> items;
+    for (size_t p = 0;;) {
+        const size_t c = v.find(',', p);
+        items.push_back(v.substr(p, c == std::string::npos ? std::string::npos : c - p));
+        if (c == std::string::npos) return items;
+        p = c + 1;
+    }
+}
+
+// a list of gains: 0 = taken, 1 = an item is no finite float (|g| < 1e30), 2 = more than PT_LIGHT_GROUPS_MAX of them
+int parse_gains(const std::string& v, std::vector<float>* out) {
+    out->clear();
+    for (const std::string& item : split(v)) {
+        float g = 0.0f;
+        if (!parse_float(item, &g) || !(g > -1e30f && g < 1e30f)) return 1;
+        out->push_back(g);
+    }
+    return out->size() > PT_LIGHT_GROUPS_MAX ? 2 : 0;
+}
+
+// the flags that take a value: the option loop fetches it, or refuses the flag without one, before the flag's arm runs
+const char* const kValueFlags[] = {"--config", "--scene", "--stdout-log-level", "--write-log-level", "--root", "--output-dir", "--seed", "--hero-wavelengths",
+                                   "--adaptive", "--devices", "--guide-samples", "--guide-chain", "--guide-alpha-max", "--spectral-bins", "--denoise-spectral-bins",
+                                   "--develop", "--develop-filter", "--develop-subsamples", "--spectral-devices", "--light-group-devices", "--light-groups",
+                                   "--relamp-groups", "--relamp-bins", "--relamp", "--relamp-gains", "--denoise-light-groups", "--light-gains", "--mattes",
+                                   "--matte-ranks", "--matte-samples"};
+
+// The option loop: "" when the command line parsed, else the message for usage().  *help: -h was met before any mistake.
+std::string parse_options(int argc, char** argv, Options& o, bool* help) {
     for (int i = 1; i < argc; ++i) {
-        std::string a = argv[i];
-        auto value = [&](std::string* dst) { if (i + 1 >= argc) return false; *dst = argv[++i]; return true; };
+        const std::string a = argv[i];
         std::string v;
-        if (a == "--config") { if (!value(&o.config)) return usage("--config needs a value"); }
-        else if (a == "--scene") { if (!value(&o.scene)) return usage("--scene needs a value"); o.has_scene = true; }
+        bool takes_value = false;
+        for (const char* flag : kValueFlags) takes_value = takes_value || a == flag;
+        if (takes_value) {
+            if (i + 1 >= argc) return a == "--develop-filter" ? "--develop-filter needs a curve name" : a + " needs a value";
+            v = argv[++i];
+        }
+        if (a == "--config") o.config = v;
+        else if (a == "--scene") { o.scene = v; o.has_scene = true; }
         else if (a == "-n" || a == "--dry-run") o.dry_run = true;
-        else if (a == "--stdout-log-level") { if (!value(&o.stdout_log_level)) return usage("--stdout-log-level needs a value"); }
-        else if (a == "--write-log-level") { if (!value(&v)) return usage("--write-log-level needs a value"); }
-        else if (a == "--root") { if (!value(&o.root)) return usage("--root needs a value"); }
-        else if (a == "--output-dir") { if (!value(&o.output_dir)) return usage("--output-dir needs a value"); }
-        else if (a == "--seed") { if (!value(&v)) return usage("--seed needs a value"); o.seed = strtoull(v.c_str(), nullptr, 10); }
+        else if (a == "--stdout-log-level") o.stdout_log_level = v;
+        else if (a == "--write-log-level") {}   // (nothing is written to a log file)
+        else if (a == "--root") o.root = v;
+        else if (a == "--output-dir") o.output_dir = v;
+        else if (a == "--seed") o.seed = strtoull(v.c_str(), nullptr, 10);
         else if (a == "--write-film") o.write_film = true;
-        else if (a == "--hero-wavelengths") { if (!value(&v)) return usage("--hero-wavelengths needs a value"); o.hero = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
-        else if (a == "--adaptive") {
-            if (!value(&v)) return usage("--adaptive needs a value");
-            char* end = nullptr;
-            o.adaptive = strtof(v.c_str(), &end);
-            if (end == v.c_str() || *end || !(o.adaptive >= 0.0f)) return usage("--adaptive needs a relative error >= 0");
-        }
-        else if (a == "--devices") {
-            if (!value(&v)) return usage("--devices needs a value");
-            char* end = nullptr;
-            o.device_mask = strtoull(v.c_str(), &end, 0);
-            if (end == v.c_str() || *end) return usage("--devices needs a device mask (bit d = HIP device d, 0 = all)");
-            o.multi = true;
-        }
+        else if (a == "--hero-wavelengths") o.hero = (uint32_t)strtoul(v.c_str(), nullptr, 10);
+        else if (a == "--adaptive") { if (!parse_float(v, &o.adaptive) || !(o.adaptive >= 0.0f)) return "--adaptive needs a relative error >= 0"; }
+        else if (a == "--devices") { if (!parse_mask(v, &o.device_mask)) return "--devices needs a device mask (bit d = HIP device d, 0 = all)"; o.multi = true; }
         else if (a == "--denoise") o.denoise = true;
         else if (a == "--demodulate-albedo") o.demodulate = true;
         else if (a == "--demodulate-bins") o.demodulate_bins = true;
         else if (a == "--denoise-resident") o.resident = true;
         else if (a == "--denoise-assemble") o.assemble = true;
-        else if (a == "--guide-samples") {
-            if (!value(&v)) return usage("--guide-samples needs a value");
-            char* end = nullptr;
-            o.guide_samples = (uint32_t)strtoul(v.c_str(), &end, 10);
-            if (end == v.c_str() || *end || o.guide_samples == 0) return usage("--guide-samples needs a positive count");
-        }
-        else if (a == "--guide-chain") {
-            if (!value(&v)) return usage("--guide-chain needs a value");
-            char* end = nullptr;
-            o.max_chain = (uint32_t)strtoul(v.c_str(), &end, 10);
-            if (end == v.c_str() || *end || o.max_chain > PT_GUIDE_CHAIN_MAX) return usage("--guide-chain needs a count of at most 16");
-            o.chain = true;
-        }
-        else if (a == "--guide-alpha-max") {
-            if (!value(&v)) return usage("--guide-alpha-max needs a value");
-            char* end = nullptr;
-            o.alpha_max = strtof(v.c_str(), &end);
-            if (end == v.c_str() || *end || !(o.alpha_max >= 0.0f) || !(o.alpha_max < 1e30f)) return usage("--guide-alpha-max needs a finite alpha >= 0");
-            o.has_alpha_max = true;
-        }
-        else if (a == "--spectral-bins") {
-            if (!value(&v)) return usage("--spectral-bins needs a value");
-            char* end = nullptr;
-            const unsigned long b = strtoul(v.c_str(), &end, 10);
-            if (end == v.c_str() || *end || b == 0 || b > PT_SPECTRAL_MAX_BINS) return usage("--spectral-bins needs a count in 1..64");
-            o.spectral_bins = (uint32_t)b;
-        }
-        else if (a == "--denoise-spectral-bins") {
-            if (!value(&v)) return usage("--denoise-spectral-bins needs a value");
-            char* end = nullptr;
-            const unsigned long b = strtoul(v.c_str(), &end, 10);
-            if (end == v.c_str() || *end || b == 0 || b > PT_SPECTRAL_MAX_BINS) return usage("--denoise-spectral-bins needs a count in 1..64");
-            o.denoise_bins = (uint32_t)b;
-        }
+        // (these two take any count that strtoul reads and look at what is left of it in 32 bits)
+        else if (a == "--guide-samples") { if (!parse_count(v, 0, ~0ul, &o.guide_samples) || o.guide_samples == 0) return "--guide-samples needs a positive count"; }
+        else if (a == "--guide-chain") { if (!parse_count(v, 0, ~0ul, &o.max_chain) || o.max_chain > PT_GUIDE_CHAIN_MAX) return "--guide-chain needs a count of at most 16"; o.chain = true; }
+        else if (a == "--guide-alpha-max") { if (!parse_float(v, &o.alpha_max) || !(o.alpha_max >= 0.0f) || !(o.alpha_max < 1e30f)) return "--guide-alpha-max needs a finite alpha >= 0"; o.has_alpha_max = true; }
+        else if (a == "--spectral-bins") { if (!parse_count(v, 1, PT_SPECTRAL_MAX_BINS, &o.spectral_bins)) return "--spectral-bins needs a count in 1..64"; }
+        else if (a == "--denoise-spectral-bins") { if (!parse_count(v, 1, PT_SPECTRAL_MAX_BINS, &o.denoise_bins)) return "--denoise-spectral-bins needs a count in 1..64"; }
         else if (a == "--develop") {
-            if (!value(&v)) return usage("--develop needs a value");
             o.develop_curves.clear();
             if (v != "cie") {
-                size_t p = 0;
-                while (true) {
-                    const size_t c = v.find(',', p);
-                    o.develop_curves.push_back(v.substr(p, c == std::string::npos ? std::string::npos : c - p));
-                    if (c == std::string::npos) break;
-                    p = c + 1;
-                }
+                o.develop_curves = split(v);
                 bool ok = o.develop_curves.size() == 3;
                 for (const std::string& n : o.develop_curves) ok = ok && !n.empty();
-                if (!ok) return usage("--develop needs `cie` or three curve names CX,CY,CZ");
+                if (!ok) return "--develop needs `cie` or three curve names CX,CY,CZ";
             }
             o.develop = true;
         }
-        else if (a == "--develop-filter") {
-            if (!value(&o.develop_filter) || o.develop_filter.empty()) return usage("--develop-filter needs a curve name");
-            o.has_develop_filter = true;
-        }
-        else if (a == "--develop-subsamples") {
-            if (!value(&v)) return usage("--develop-subsamples needs a value");
-            char* end = nullptr;
-            const unsigned long n = strtoul(v.c_str(), &end, 10);
-            if (end == v.c_str() || *end || n == 0 || n > PT_SPECTRAL_MAX_SUBSAMPLES) return usage("--develop-subsamples needs a count in 1..16");
-            o.develop_subsamples = (uint32_t)n; o.has_develop_subsamples = true;
-        }
-        else if (a == "--spectral-devices") {
-            if (!value(&v)) return usage("--spectral-devices needs a value");
-            char* end = nullptr;
-            o.spectral_device_mask = strtoull(v.c_str(), &end, 0);
-            if (end == v.c_str() || *end) return usage("--spectral-devices needs a device mask (bit d = HIP device d, 0 = all)");
-            o.spectral_multi = true;
-        }
-        else if (a == "--light-group-devices") {
-            if (!value(&v)) return usage("--light-group-devices needs a value");
-            char* end = nullptr;
-            o.group_device_mask = strtoull(v.c_str(), &end, 0);
-            if (end == v.c_str() || *end) return usage("--light-group-devices needs a device mask (bit d = HIP device d, 0 = all)");
-            o.group_multi = true;
-        }
-        else if (a == "--light-groups") {
-            if (!value(&v)) return usage("--light-groups needs a value");
-            o.light_groups = v == "instance" ? 1 : v == "material" ? 2 : 0;
-            if (!o.light_groups) return usage("--light-groups needs `instance` or `material`");
-        }
-        else if (a == "--relamp-groups") {
-            if (!value(&v)) return usage("--relamp-groups needs a value");
-            o.relamp_groups = v == "instance" ? 1 : v == "material" ? 2 : 0;
-            if (!o.relamp_groups) return usage("--relamp-groups needs `instance` or `material`");
-        }
-        else if (a == "--relamp-bins") {
-            if (!value(&v)) return usage("--relamp-bins needs a value");
-            char* end = nullptr;
-            const unsigned long b = strtoul(v.c_str(), &end, 10);
-            if (end == v.c_str() || *end || b == 0 || b > PT_SPECTRAL_MAX_BINS) return usage("--relamp-bins needs a count in 1..64");
-            o.relamp_bins = (uint32_t)b;
-        }
+        else if (a == "--develop-filter") { if (v.empty()) return "--develop-filter needs a curve name"; o.develop_filter = v; o.has_develop_filter = true; }
+        else if (a == "--develop-subsamples") { if (!parse_count(v, 1, PT_SPECTRAL_MAX_SUBSAMPLES, &o.develop_subsamples)) return "--develop-subsamples needs a count in 1..16"; o.has_develop_subsamples = true; }
+        else if (a == "--spectral-devices") { if (!parse_mask(v, &o.spectral_device_mask)) return "--spectral-devices needs a device mask (bit d = HIP device d, 0 = all)"; o.spectral_multi = true; }
+        else if (a == "--light-group-devices") { if (!parse_mask(v, &o.group_device_mask)) return "--light-group-devices needs a device mask (bit d = HIP device d, 0 = all)"; o.group_multi = true; }
+        else if (a == "--light-groups") { if (!(o.light_groups = parse_group_mode(v))) return "--light-groups needs `instance` or `material`"; }
+        else if (a == "--relamp-groups") { if (!(o.relamp_groups = parse_group_mode(v))) return "--relamp-groups needs `instance` or `material`"; }
+        else if (a == "--relamp-bins") { if (!parse_count(v, 1, PT_SPECTRAL_MAX_BINS, &o.relamp_bins)) return "--relamp-bins needs a count in 1..64"; }
         else if (a == "--relamp") {
-            if (!value(&v)) return usage("--relamp needs a value");
             o.has_relamp = true;
             o.relamp.clear();
-            size_t p = 0;
-            while (true) {
-                const size_t c = v.find(',', p);
-                const std::string item = v.substr(p, c == std::string::npos ? std::string::npos : c - p);
+            for (const std::string& item : split(v)) {
                 const size_t colon = item.find(':');
-                char* end = nullptr;
-                const unsigned long g = strtoul(item.c_str(), &end, 10);
-                if (colon == std::string::npos || colon == 0 || end != item.c_str() + colon || colon + 1 >= item.size() || g >= PT_LIGHT_GROUPS_MAX)
-                    return usage("--relamp needs G:CURVE[,G:CURVE...] with G a group in 0..7");
-                for (const auto& have : o.relamp) if (have.first == (uint32_t)g) return usage("--relamp names a group twice");
-                o.relamp.push_back({(uint32_t)g, item.substr(colon + 1)});
-                if (c == std::string::npos) break;
-                p = c + 1;
+                uint32_t g = 0;
+                if (colon == std::string::npos || !parse_count(item.substr(0, colon), 0, PT_LIGHT_GROUPS_MAX - 1, &g) || colon + 1 >= item.size())
+                    return "--relamp needs G:CURVE[,G:CURVE...] with G a group in 0..7";
+                for (const auto& have : o.relamp) if (have.first == g) return "--relamp names a group twice";
+                o.relamp.push_back({g, item.substr(colon + 1)});
             }
         }
-        else if (a == "--relamp-gains") {
-            if (!value(&v)) return usage("--relamp-gains needs a value");
-            o.has_relamp_gains = true;
-            o.relamp_gains.clear();
-            size_t p = 0;
-            while (true) {
-                const size_t c = v.find(',', p);
-                const std::string item = v.substr(p, c == std::string::npos ? std::string::npos : c - p);
-                char* end = nullptr;
-                const float g = strtof(item.c_str(), &end);
-                if (item.empty() || end == item.c_str() || *end || !(g > -1e30f && g < 1e30f)) return usage("--relamp-gains needs finite gains g0,g1,...");
-                o.relamp_gains.push_back(g);
-                if (c == std::string::npos) break;
-                p = c + 1;
-            }
-            if (o.relamp_gains.size() > PT_LIGHT_GROUPS_MAX) return usage("--relamp-gains takes at most 8 gains");
-        }
-        else if (a == "--denoise-light-groups") {
-            if (!value(&v)) return usage("--denoise-light-groups needs a value");
-            o.denoise_groups = v == "instance" ? 1 : v == "material" ? 2 : 0;
-            if (!o.denoise_groups) return usage("--denoise-light-groups needs `instance` or `material`");
-        }
-        else if (a == "--light-gains") {
-            if (!value(&v)) return usage("--light-gains needs a value");
-            o.has_light_gains = true;
-            o.light_gains.clear();
-            for (size_t at = 0; at <= v.size();) {
-                const size_t comma = v.find(',', at);
-                const std::string item = v.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
-                char* end = nullptr;
-                const float g = strtof(item.c_str(), &end);
-                if (item.empty() || end == item.c_str() || *end || !(g > -1e30f && g < 1e30f)) return usage("--light-gains needs finite gains G0,G1,...");
-                o.light_gains.push_back(g);
-                if (comma == std::string::npos) break;
-                at = comma + 1;
-            }
-            if (o.light_gains.size() > PT_LIGHT_GROUPS_MAX) return usage("--light-gains takes at most 8 gains");
-        }
-        else if (a == "--mattes") {
-            if (!value(&v)) return usage("--mattes needs a value");
-            o.mattes = v == "instance" ? 1 : v == "material" ? 2 : 0;
-            if (!o.mattes) return usage("--mattes needs `instance` or `material`");
-        }
-        else if (a == "--matte-ranks" || a == "--matte-samples") {
-            if (!value(&v)) return usage((a + " needs a value").c_str());
-            char* end = nullptr;
-            const unsigned long x = strtoul(v.c_str(), &end, 10);
-            const bool ranks = a == "--matte-ranks";
-            if (end == v.c_str() || *end || x == 0 || x > (ranks ? (unsigned long)PT_MATTE_RANKS_MAX : 65535ul))
-                return usage(ranks ? "--matte-ranks needs a number of ranks in 1..8" : "--matte-samples needs a number of samples in 1..65535");
-            (ranks ? o.matte_ranks : o.matte_samples) = (uint32_t)x;
-            (ranks ? o.has_matte_ranks : o.has_matte_samples) = true;
-        }
+        else if (a == "--relamp-gains") { o.has_relamp_gains = true; if (const int bad = parse_gains(v, &o.relamp_gains)) return bad == 1 ? "--relamp-gains needs finite gains g0,g1,..." : "--relamp-gains takes at most 8 gains"; }
+        else if (a == "--denoise-light-groups") { if (!(o.denoise_groups = parse_group_mode(v))) return "--denoise-light-groups needs `instance` or `material`"; }
+        else if (a == "--light-gains") { o.has_light_gains = true; if (const int bad = parse_gains(v, &o.light_gains)) return bad == 1 ? "--light-gains needs finite gains G0,G1,..." : "--light-gains takes at most 8 gains"; }
+        else if (a == "--mattes") { if (!(o.mattes = parse_group_mode(v))) return "--mattes needs `instance` or `material`"; }
+        else if (a == "--matte-ranks") { if (!parse_count(v, 1, PT_MATTE_RANKS_MAX, &o.matte_ranks)) return "--matte-ranks needs a number of ranks in 1..8"; o.has_matte_ranks = true; }
+        else if (a == "--matte-samples") { if (!parse_count(v, 1, 65535, &o.matte_samples)) return "--matte-samples needs a number of samples in 1..65535"; o.has_matte_samples = true; }
         else if (a == "--path-passes") o.path_passes = true;
         else if (a == "--denoise-path-passes") o.denoise_passes = true;
-        else if (a == "-h" || a == "--help") { usage(nullptr); return 0; }
-        else return usage(("unknown option " + a).c_str());
+        else if (a == "-h" || a == "--help") { *help = true; return ""; }
+        else return "unknown option " + a;
     }
-    if (o.denoise_passes && !(o.path_passes && o.denoise)) return usage("--denoise-path-passes needs --path-passes and --denoise");
+    return "";
+}
+
+// ---- the combination rules: "" when the flags go together, else the message for usage().  The order of the rules, and the order inside each list, decides which
+// message a command line that breaks several of them gets.
+
+struct Present { bool present; const char* flag; };
+
+std::string cannot_combine(const char* flag, std::initializer_list<Present> others, const char* why) {   // ("" when none of the others is present)
+    for (const Present& other : others) if (other.present) return std::string(flag) + " cannot be combined with " + other.flag + ": " + why;
+    return "";
+}
+
+std::string check_options(const Options& o) {
+    std::string no;
+    const bool adaptive = o.adaptive >= 0.0f;
+    const Present adapt{adaptive, "--adaptive"}, denoise{o.denoise, "--denoise"}, bins{o.spectral_bins != 0, "--spectral-bins"}, dbins{o.denoise_bins != 0, "--denoise-spectral-bins"},
+                  devices{o.multi, "--devices"}, sdevices{o.spectral_multi, "--spectral-devices"}, gdevices{o.group_multi, "--light-group-devices"}, hero{o.hero != 0, "--hero-wavelengths"},
+                  groups{o.light_groups != 0, "--light-groups"}, dgroups{o.denoise_groups != 0, "--denoise-light-groups"}, relamp{o.relamp_groups != 0, "--relamp-groups"};
+    if (o.denoise_passes && !(o.path_passes && o.denoise)) return "--denoise-path-passes needs --path-passes and --denoise";
     if (o.path_passes) {
-        const char* with = (o.adaptive >= 0.0f && !o.denoise_passes) ? "--adaptive" : o.spectral_bins ? "--spectral-bins" : o.denoise_bins ? "--denoise-spectral-bins"
-                         : o.multi ? "--devices" : o.spectral_multi ? "--spectral-devices" : o.hero ? "--hero-wavelengths" : o.light_groups ? "--light-groups"
-                         : o.denoise_groups ? "--denoise-light-groups" : o.relamp_groups ? "--relamp-groups" : o.group_multi ? "--light-group-devices"
-                         : o.assemble ? "--denoise-assemble" : nullptr;
-        static std::string refusal;
-        if (with) { refusal = std::string("--path-passes cannot be combined with ") + with + ": a pass render is one render of one wavelength per path on one device, and its films are the scene's resident group films"; return usage(refusal.c_str()); }
-        if (o.denoise && !o.denoise_passes) return usage("--path-passes cannot be combined with --denoise without --denoise-path-passes: the filter of the pass films takes the adaptive pass render");
+        no = cannot_combine("--path-passes", {{adaptive && !o.denoise_passes, "--adaptive"}, bins, dbins, devices, sdevices, hero, groups, dgroups, relamp, gdevices, {o.assemble, "--denoise-assemble"}},
+                            "a pass render is one render of one wavelength per path on one device, and its films are the scene's resident group films");
+        if (!no.empty()) return no;
+        if (o.denoise && !o.denoise_passes) return "--path-passes cannot be combined with --denoise without --denoise-path-passes: the filter of the pass films takes the adaptive pass render";
     }
-    if (o.group_multi && !o.light_groups && !o.denoise_groups) return usage("--light-group-devices needs --light-groups or --denoise-light-groups: it names the devices their group render runs on");
-    if (o.group_multi && o.multi) return usage("--light-group-devices cannot be combined with --devices: a group render takes its devices from --light-group-devices alone");
+    if (o.group_multi && !o.light_groups && !o.denoise_groups) return "--light-group-devices needs --light-groups or --denoise-light-groups: it names the devices their group render runs on";
+    if (o.group_multi && o.multi) return "--light-group-devices cannot be combined with --devices: a group render takes its devices from --light-group-devices alone";
     if (o.relamp_groups) {
-        const char* with = o.adaptive >= 0.0f ? "--adaptive" : o.denoise ? "--denoise" : o.light_groups ? "--light-groups" : o.spectral_bins ? "--spectral-bins"
-                         : o.denoise_bins ? "--denoise-spectral-bins" : o.multi ? "--devices" : o.spectral_multi ? "--spectral-devices" : o.hero ? "--hero-wavelengths" : nullptr;
-        static std::string refusal;
-        if (with) { refusal = std::string("--relamp-groups cannot be combined with ") + with + ": a spectral group render is one plain render of one wavelength per path on one device"; return usage(refusal.c_str()); }
-        if (!o.relamp_bins) return usage("--relamp-groups needs --relamp-bins");
+        no = cannot_combine("--relamp-groups", {adapt, denoise, groups, bins, dbins, devices, sdevices, hero}, "a spectral group render is one plain render of one wavelength per path on one device");
+        if (!no.empty()) return no;
+        if (!o.relamp_bins) return "--relamp-groups needs --relamp-bins";
     } else {
-        if (o.relamp_bins) return usage("--relamp-bins needs --relamp-groups");
-        if (o.has_relamp) return usage("--relamp needs --relamp-groups");
-        if (o.has_relamp_gains) return usage("--relamp-gains needs --relamp-groups");
+        if (o.relamp_bins) return "--relamp-bins needs --relamp-groups";
+        if (o.has_relamp) return "--relamp needs --relamp-groups";
+        if (o.has_relamp_gains) return "--relamp-gains needs --relamp-groups";
     }
     if (o.denoise_groups) {
-        const char* with = o.light_groups ? "--light-groups" : o.spectral_bins ? "--spectral-bins" : o.denoise_bins ? "--denoise-spectral-bins" : o.multi ? "--devices"
-                         : o.spectral_multi ? "--spectral-devices" : (o.assemble && !o.group_multi) ? "--denoise-assemble" : o.hero ? "--hero-wavelengths" : nullptr;
-        static std::string refusal;
-        if (with) { refusal = std::string("--denoise-light-groups cannot be combined with ") + with + ": it is one adaptive group render of one wavelength per path on one device, and its filter"; return usage(refusal.c_str()); }
-        if (!o.denoise) return usage("--denoise-light-groups needs --denoise");
+        no = cannot_combine("--denoise-light-groups", {groups, bins, dbins, devices, sdevices, {o.assemble && !o.group_multi, "--denoise-assemble"}, hero},
+                            "it is one adaptive group render of one wavelength per path on one device, and its filter");
+        if (!no.empty()) return no;
+        if (!o.denoise) return "--denoise-light-groups needs --denoise";
     }
-    if (o.has_light_gains && !o.light_groups && !o.denoise_groups) return usage("--light-gains needs --light-groups");
+    if (o.has_light_gains && !o.light_groups && !o.denoise_groups) return "--light-gains needs --light-groups";
     if (o.light_groups) {
-        const char* with = o.adaptive >= 0.0f ? "--adaptive" : o.denoise ? "--denoise" : o.spectral_bins ? "--spectral-bins" : o.denoise_bins ? "--denoise-spectral-bins"
-                         : o.multi ? "--devices" : o.spectral_multi ? "--spectral-devices" : o.hero ? "--hero-wavelengths" : nullptr;
-        static std::string refusal;
-        if (with) { refusal = std::string("--light-groups cannot be combined with ") + with + ": a group render is one plain render of one wavelength per path on one device"; return usage(refusal.c_str()); }
+        no = cannot_combine("--light-groups", {adapt, denoise, bins, dbins, devices, sdevices, hero}, "a group render is one plain render of one wavelength per path on one device");
+        if (!no.empty()) return no;
     }
     if (o.mattes) {
-        const char* with = o.multi ? "--devices" : o.spectral_multi ? "--spectral-devices" : o.group_multi ? "--light-group-devices" : nullptr;
-        static std::string refusal;
-        if (with) { refusal = std::string("--mattes cannot be combined with ") + with + ": a matte render runs on the scene's device and there is none over a device mask"; return usage(refusal.c_str()); }
-    } else if (o.has_matte_ranks || o.has_matte_samples) return usage(o.has_matte_ranks ? "--matte-ranks needs --mattes" : "--matte-samples needs --mattes");
-    if (o.demodulate && !o.denoise) return usage("--demodulate-albedo needs --denoise");
-    if (o.chain && !o.denoise) return usage("--guide-chain needs --denoise");
-    if (o.has_alpha_max && !o.chain) return usage("--guide-alpha-max needs --guide-chain");
-    if (o.denoise_bins && o.spectral_bins) return usage("--denoise-spectral-bins cannot be combined with --spectral-bins: it writes the spectral files itself");
-    if (o.spectral_bins && o.adaptive >= 0.0f) return usage("--spectral-bins cannot be combined with --adaptive: an adaptive render has no spectral film");
-    if (o.spectral_bins && o.denoise) return usage("--spectral-bins cannot be combined with --denoise: the denoiser takes the adaptive path, which has no spectral film");
+        no = cannot_combine("--mattes", {devices, sdevices, gdevices}, "a matte render runs on the scene's device and there is none over a device mask");
+        if (!no.empty()) return no;
+    } else if (o.has_matte_ranks || o.has_matte_samples) return o.has_matte_ranks ? "--matte-ranks needs --mattes" : "--matte-samples needs --mattes";
+    if (o.demodulate && !o.denoise) return "--demodulate-albedo needs --denoise";
+    if (o.chain && !o.denoise) return "--guide-chain needs --denoise";
+    if (o.has_alpha_max && !o.chain) return "--guide-alpha-max needs --guide-chain";
+    if (o.denoise_bins && o.spectral_bins) return "--denoise-spectral-bins cannot be combined with --spectral-bins: it writes the spectral files itself";
+    if (o.spectral_bins && adaptive) return "--spectral-bins cannot be combined with --adaptive: an adaptive render has no spectral film";
+    if (o.spectral_bins && o.denoise) return "--spectral-bins cannot be combined with --denoise: the denoiser takes the adaptive path, which has no spectral film";
     if (o.spectral_bins && o.multi) {   // (pt_render_spectral renders on the scene's device, device 0: a mask may name that one alone; 0 = every device of the node)
         if ((o.device_mask & (o.device_mask - 1)) != 0 || (o.device_mask == 0 && pt_device_count() > 1))
-            return usage("--spectral-bins cannot be combined with --devices naming more than one GPU: pt_render_multi has no spectral film");
-        if (o.device_mask > 1) return usage("--spectral-bins renders on device 0: --devices may name that device alone");
+            return "--spectral-bins cannot be combined with --devices naming more than one GPU: pt_render_multi has no spectral film";
+        if (o.device_mask > 1) return "--spectral-bins renders on device 0: --devices may name that device alone";
     }
-    if (o.resident && !o.denoise) return usage("--denoise-resident needs --denoise");
-    if (o.resident && o.multi) return usage("--denoise-resident cannot be combined with --devices: a node render leaves no film one device can filter");
-    if (o.resident && o.group_multi) return usage("--denoise-resident cannot be combined with --light-group-devices: a node render leaves no film one device can filter (--denoise-assemble gathers one)");
-    if (o.resident && o.spectral_multi) return usage("--denoise-resident cannot be combined with --spectral-devices: a node render leaves no film one device can filter");
-    if (o.demodulate_bins && !o.denoise_bins) return usage("--demodulate-bins needs --denoise-spectral-bins");
-    if (o.denoise_bins && !o.denoise) return usage("--denoise-spectral-bins needs --denoise");
-    if (o.denoise_bins && o.demodulate) return usage("--denoise-spectral-bins cannot be combined with --demodulate-albedo: demodulating the bins needs a per-bin albedo");
-    if (o.denoise_bins && o.multi && o.device_mask != 1) return usage("--denoise-spectral-bins renders on device 0: --devices may name that device alone");
-    if (o.develop && !o.spectral_bins && !o.denoise_bins) return usage("--develop needs --spectral-bins or --denoise-spectral-bins: it develops their bins");
-    if (o.has_develop_filter && !o.develop) return usage("--develop-filter needs --develop");
-    if (o.has_develop_subsamples && !o.develop && !o.relamp_groups) return usage("--develop-subsamples needs --develop");
-    if (o.spectral_multi && !o.spectral_bins && !o.denoise_bins) return usage("--spectral-devices needs --spectral-bins or --denoise-spectral-bins: it names the devices their spectral film is rendered on");
-    if (o.spectral_multi && o.multi) return usage("--spectral-devices cannot be combined with --devices: a spectral render takes its devices from --spectral-devices alone");
-    if (o.assemble && o.resident) return usage("--denoise-assemble cannot be combined with --denoise-resident: that flag is the one-device form, this one assembles a node render");
-    if (o.assemble && !o.denoise) return usage("--denoise-assemble needs --denoise");
+    if (o.resident && !o.denoise) return "--denoise-resident needs --denoise";
+    if (o.resident && o.multi) return "--denoise-resident cannot be combined with --devices: a node render leaves no film one device can filter";
+    if (o.resident && o.group_multi) return "--denoise-resident cannot be combined with --light-group-devices: a node render leaves no film one device can filter (--denoise-assemble gathers one)";
+    if (o.resident && o.spectral_multi) return "--denoise-resident cannot be combined with --spectral-devices: a node render leaves no film one device can filter";
+    if (o.demodulate_bins && !o.denoise_bins) return "--demodulate-bins needs --denoise-spectral-bins";
+    if (o.denoise_bins && !o.denoise) return "--denoise-spectral-bins needs --denoise";
+    if (o.denoise_bins && o.demodulate) return "--denoise-spectral-bins cannot be combined with --demodulate-albedo: demodulating the bins needs a per-bin albedo";
+    if (o.denoise_bins && o.multi && o.device_mask != 1) return "--denoise-spectral-bins renders on device 0: --devices may name that device alone";
+    if (o.develop && !o.spectral_bins && !o.denoise_bins) return "--develop needs --spectral-bins or --denoise-spectral-bins: it develops their bins";
+    if (o.has_develop_filter && !o.develop) return "--develop-filter needs --develop";
+    if (o.has_develop_subsamples && !o.develop && !o.relamp_groups) return "--develop-subsamples needs --develop";
+    if (o.spectral_multi && !o.spectral_bins && !o.denoise_bins) return "--spectral-devices needs --spectral-bins or --denoise-spectral-bins: it names the devices their spectral film is rendered on";
+    if (o.spectral_multi && o.multi) return "--spectral-devices cannot be combined with --devices: a spectral render takes its devices from --spectral-devices alone";
+    if (o.assemble && o.resident) return "--denoise-assemble cannot be combined with --denoise-resident: that flag is the one-device form, this one assembles a node render";
+    if (o.assemble && !o.denoise) return "--denoise-assemble needs --denoise";
     const bool assemble_groups = o.assemble && o.denoise_groups && o.group_multi;   // (the node group render assembled: the other form of the flag)
-    if (o.assemble && !assemble_groups && !o.denoise_bins) return usage("--denoise-assemble needs --denoise-spectral-bins: it assembles the node render of the spectral film");
-    if (o.assemble && !assemble_groups && !o.spectral_multi) return usage("--denoise-assemble needs --spectral-devices: it assembles the node render on those devices");
+    if (o.assemble && !assemble_groups && !o.denoise_bins) return "--denoise-assemble needs --denoise-spectral-bins: it assembles the node render of the spectral film";
+    if (o.assemble && !assemble_groups && !o.spectral_multi) return "--denoise-assemble needs --spectral-devices: it assembles the node render on those devices";
+    return "";
+}
+
+// ---- what a run holds from loading to the last setting.  The owners free in reverse order: the scene, the scene file, the config.
+
+template <class T, void (*Free)(T*)>
+struct Freeing { void operator()(T* p) const { Free(p); } };
+
+bool fail(const char* prefix) {   // the engine's last error under a site's own prefix
+    fprintf(stderr, "%s: %s\n", prefix, pt_last_error());
+    return false;
+}
+
+uint32_t first_device(uint64_t mask) {   // the lowest device of a mask; 0 for the mask 0 (= all devices)
+    uint32_t d = 0;
+    if (mask) while (!((mask >> d) & 1u)) ++d;
+    return d;
+}
+
+std::vector<float> pack_planes(const std::vector<float>& planes, size_t np) {   // three planes as an XYZW film with W = 0
+    std::vector<float> packed(4 * np);
+    for (size_t p = 0; p < np; ++p) { packed[4 * p] = planes[p]; packed[4 * p + 1] = planes[np + p]; packed[4 * p + 2] = planes[2 * np + p]; packed[4 * p + 3] = 0.0f; }
+    return packed;
+}
+
+// An instance's light materials: its override, else every face material of its mesh.  `visit(id)` returns false to stop the walk.
+template <class Visit>
+void for_each_light_material(const pt_scene_desc* desc, const pt_instance& in, Visit visit) {
+    if (in.material != PT_MATERIAL_NONE) { if (PT_MATERIAL_TAG(in.material) == PT_TAG_LIGHT) visit(in.material); }
+    else if (in.kind == PT_SHAPE_MESH && in.mesh >= 0 && (uint32_t)in.mesh < desc->mesh_count && desc->meshes[in.mesh].face_material_offset >= 0) {
+        const pt_mesh& m = desc->meshes[in.mesh];
+        for (uint32_t f = 0; f < m.face_count; ++f) {
+            const uint32_t id = desc->face_materials[(size_t)m.face_material_offset + f];
+            if (PT_MATERIAL_TAG(id) == PT_TAG_LIGHT && !visit(id)) return;
+        }
+    }
+}
+
+struct Curves {   // curves in pt_scene_desc's representation, for the response and re-lamp matrices
+    std::vector<pt_curve> curves;
+    std::vector<float> data;
+    // appends a curve of the scene file's library: its index, or -1 (pt_scene_file_last_error says why)
+    int32_t add(pt_scene_file* scene_file, const std::string& name) {
+        pt_curve c; const float* from = nullptr; uint32_t floats = 0;
+        if (pt_scene_file_library_curve(scene_file, name.c_str(), &c, &from, &floats) != PT_OK) return -1;
+        c.data_offset = (uint32_t)data.size();
+        data.insert(data.end(), from, from + floats);
+        curves.push_back(c);
+        return (int32_t)curves.size() - 1;
+    }
+};
+
+struct Run {
+    Options o;
+    bool warnings = false;
+    std::unique_ptr<pt_config, Freeing<pt_config, pt_config_free>> config;
+    std::unique_ptr<pt_scene_file, Freeing<pt_scene_file, pt_scene_file_free>> scene_file;
+    std::unique_ptr<pt_scene, Freeing<pt_scene, pt_scene_destroy>> scene;
+    const pt_scene_desc* desc = nullptr;
+    // --develop: the response curves and the filter, from the curves library of the scene file
+    Curves develop_curves;
+    int32_t develop_responses[3] = {PT_RESPONSE_CIE_X, PT_RESPONSE_CIE_Y, PT_RESPONSE_CIE_Z}, develop_filter = PT_SPECTRAL_NO_FILTER;
+    // the three group flags: a group per emitting instance or per light material in scene order, the environment last when it emits
+    int group_mode = 0;
+    const char* group_flag = "";
+    std::vector<uint8_t> instance_group;
+    pt_light_groups_desc gd;
+    // --relamp-groups: the curves of pt_light_groups_relamp_matrix — the scene's own, where a group's old curve is, and behind them the new ones from the curves
+    // library of the scene file — and per group the old and the new curve
+    Curves relamp_curves;
+    std::vector<int32_t> relamp_old = std::vector<int32_t>(PT_LIGHT_GROUPS_MAX, PT_RELAMP_KEEP), relamp_new = relamp_old;
+};
+
+// The exits between loading the scene and rendering: each says why on stderr and returns false.
+
+bool load_develop_curves(Run& r) {
+    std::vector<std::string> names = r.o.develop_curves;
+    if (r.o.has_develop_filter) names.push_back(r.o.develop_filter);
+    for (size_t k = 0; k < names.size(); ++k) {
+        if (r.develop_curves.add(r.scene_file.get(), names[k]) < 0) { fprintf(stderr, "error: --develop: %s\n", pt_scene_file_last_error()); return false; }
+        if (k < r.o.develop_curves.size()) r.develop_responses[k] = (int32_t)k; else r.develop_filter = (int32_t)k;
+    }
+    return true;
+}
+
+bool form_light_groups(Run& r) {
+    const Options& o = r.o;
+    const pt_scene_desc* desc = r.desc;
+    std::vector<uint32_t> keys;   // a group's key: the instance (mode 1) or the packed light material (mode 2)
+    for (uint32_t i = 0; i < desc->instance_count; ++i) {
+        uint32_t light = PT_MATERIAL_NONE;   // the instance's first light material
+        for_each_light_material(desc, desc->instances[i], [&](uint32_t id) { light = id; return false; });
+        if (light == PT_MATERIAL_NONE) continue;
+        const uint32_t key = r.group_mode == 1 ? i : light;
+        uint32_t g = 0;
+        while (g < keys.size() && keys[g] != key) ++g;
+        if (g == keys.size()) keys.push_back(key);
+        if (g < PT_LIGHT_GROUPS_MAX) r.instance_group[i] = (uint8_t)g;
+    }
+    uint32_t groups = (uint32_t)keys.size();
+    const bool env_emits = desc->environment.strength != 0.0f;
+    r.gd.environment_group = env_emits ? groups : 0u;
+    if (env_emits) ++groups;
+    if (groups == 0) groups = 1;
+    const char* why = groups > PT_LIGHT_GROUPS_MAX ? "the scene has more than 8 light groups"
+                      : (o.has_light_gains && o.light_gains.size() != groups) ? "--light-gains needs one gain per group" : nullptr;
+    if (why) { fprintf(stderr, "error: %s: %s (%u groups)\n", r.group_flag, why, groups); return false; }
+    r.gd.group_count = groups; r.gd.instance_count = desc->instance_count; r.gd.instance_group = r.instance_group.data();
+    printf("light groups: %u (%s%s)\n", groups, r.group_mode == 1 ? "one per emitting instance" : "one per light material", env_emits ? ", the environment last" : "");
+    return true;
+}
+
+bool load_relamp_curves(Run& r) {
+    const Options& o = r.o;
+    const pt_scene_desc* desc = r.desc;
+    const pt_light_groups_desc& gd = r.gd;
+    const auto refuse = [](const std::string& why) { fprintf(stderr, "error: --relamp-groups: %s\n", why.c_str()); return false; };
+    if (o.has_relamp_gains && o.relamp_gains.size() != gd.group_count) return refuse("--relamp-gains needs one gain per group (" + std::to_string(gd.group_count) + " groups)");
+    r.relamp_curves.curves.assign(desc->curves, desc->curves + desc->curve_count);
+    r.relamp_curves.data.assign(desc->curve_data, desc->curve_data + desc->curve_data_count);
+    const bool env_emits = desc->environment.strength != 0.0f;
+    for (const auto& item : o.relamp) {
+        const uint32_t g = item.first;
+        const std::string names = "--relamp names group " + std::to_string(g);
+        if (g >= gd.group_count) return refuse(names + ", the scene has " + std::to_string(gd.group_count) + " groups");
+        // the emission curve the group's emitters share: every light material of its instances, and the environment's curve when it is the environment's group
+        int32_t old = -1;
+        bool mixed = false, any = false;
+        const auto emitter = [&](int32_t curve) { mixed = mixed || (any && curve != old); old = curve; any = true; };
+        if (env_emits && gd.environment_group == g) {
+            if (desc->environment.kind == PT_ENV_HDR) return refuse(names + ", the environment, which an HDR texture lights: it has no single emission curve to replace");
+            emitter(desc->environment.curve);
+        }
+        for (uint32_t i = 0; i < desc->instance_count; ++i) {
+            if (r.instance_group[i] != g) continue;
+            for_each_light_material(desc, desc->instances[i], [&](uint32_t id) {
+                if (PT_MATERIAL_INDEX(id) < desc->material_count) emitter(desc->materials[PT_MATERIAL_INDEX(id)].curve_emit);
+                return true;
+            });
+        }
+        if (!any) return refuse(names + ", which holds no emitter");
+        if (mixed) return refuse(names + ", whose emitters have different emission curves: it has no single curve to replace");
+        const int32_t fresh = r.relamp_curves.add(r.scene_file.get(), item.second);
+        if (fresh < 0) return refuse(std::string("--relamp: ") + pt_scene_file_last_error());
+        r.relamp_old[g] = old; r.relamp_new[g] = fresh;
+    }
+    return true;
+}
+
+// --denoise: what the adaptive path refuses is refused here, with its message, before anything is rendered or written
+bool adaptive_path_takes_every_setting(const Run& r) {
+    const Options& o = r.o;
+    uint32_t tw = 0, th = 0;
+    const bool naive = pt_config_renderer(r.config.get(), &tw, &th) == PT_RENDERER_NAIVE;
+    for (uint32_t i = 0; i < pt_config_render_settings_count(r.config.get()); ++i) {
+        pt_render_settings rs; pt_render_desc rd;
+        pt_config_render_settings(r.config.get(), i, &rs);
+        if (pt_config_render_desc(r.config.get(), i, o.seed, &rd) != PT_OK) continue;   // (skipped when rendering as well)
+        const bool range = o.adaptive >= 0.0f && !naive && rs.max_samples >= 0 && (uint32_t)rs.max_samples > rd.spp;   // (--adaptive rounds a range up itself)
+        const char* why = naive ? "adaptive sampling needs phases of 10 samples (phase_samples 0 or 10)"
+                                : ((!range && rd.spp % 10u != 0u) ? "spp, step and max_samples must be multiples of 10" : nullptr);
+        if (why) {
+            fprintf(stderr, "error: --denoise: render settings %u (%s, min_samples %u) cannot take the adaptive path the statistics come from: %s\n", i,
+                    naive ? "Naive renderer" : "Tiled renderer", rd.spp, why);
+            return false;
+        }
+    }
+    return true;
+}
+
+// ---- one [[render_settings]] entry: rendered, written and, with --denoise, filtered.  Every step returns success and has said on stderr what failed.
+
+struct Pixels {   // what pt_output_film makes of a film
+    std::vector<uint8_t> rgba;
+    std::vector<float> linear;
+    explicit Pixels(size_t np) : rgba(4 * np), linear(3 * np) {}
+};
+
+enum Mix { kMixResident, kMixResidentDenoised, kMixHost };   // where --light-gains mixes the group films: where the render, or the joint filter, left them, or from host arrays
+
+struct Setting {
+    const Run& r;
+    const Options& o;
+    pt_scene* const scene;
+    const uint32_t index;
+    pt_render_settings rs;
+    pt_render_desc rd;
+    pt_output_desc od;
+    pt_guide_chain_desc cd;    // --guide-chain's descriptor, for every guide call of the setting
+    pt_spectral_desc sd;       // the bins of --spectral-bins, --denoise-spectral-bins or --relamp-bins (only one of them is given)
+    size_t np = 0;
+    std::string base;          // <output-dir>/<filename>
+    std::vector<float> film, spectral, group_films, group_bins;
+    std::vector<uint32_t> counts;
+    std::vector<double> stats;
+    Pixels px{0};              // of the film, then of the denoised film: the spectral and Cryptomatte files written next carry its linear R, G, B
+
+    Setting(const Run& run, uint32_t i) : r(run), o(run.o), scene(run.scene.get()), index(i) {}
+
+    // The one render of the setting: picks the entry, prints the "rendering ..." line, calls it and names it when it fails.  A fixed count under --denoise goes
+    // through the adaptive entries as --adaptive does (max_samples = min_samples, one round: pt_render's film bit for bit, and the statistics).
+    bool render(pt_profile* prof, uint64_t* samples) {
+        pt_config* config = r.config.get();
+        // --adaptive: min_samples .. max_samples per pixel (pt_render_adaptive) where the setting gives a range and the renderer sums in phases of 10
+        bool adaptive = o.adaptive >= 0.0f;
+        pt_adaptive_desc ad = {0u, 0u, o.adaptive, 0.0f};
+        if (adaptive) {
+            uint32_t tw = 0, th = 0;
+            if (pt_config_renderer(config, &tw, &th) == PT_RENDERER_NAIVE) {
+                if (r.warnings) fprintf(stderr, "warning: --adaptive: render settings %u use the Naive renderer; rendering %u spp everywhere\n", index, rd.spp);
+                adaptive = false;
+            } else if (rs.max_samples < 0 || (uint32_t)rs.max_samples <= rd.spp) {
+                if (r.warnings) fprintf(stderr, "warning: --adaptive: render settings %u have no max_samples > min_samples; rendering %u spp everywhere\n", index, rd.spp);
+                adaptive = false;
+            } else {
+                const uint32_t lo = (rd.spp + 9u) / 10u * 10u, hi = ((uint32_t)rs.max_samples + 9u) / 10u * 10u;
+                if ((lo != rd.spp || hi != (uint32_t)rs.max_samples) && r.warnings)
+                    fprintf(stderr, "warning: --adaptive: samples %u..%d rounded up to %u..%u (multiples of 10)\n", rd.spp, rs.max_samples, lo, hi);
+                rd.spp = lo; ad.max_samples = hi;
+            }
+        }
+        const bool counted = adaptive || o.denoise;   // through the adaptive entries
+        const pt_light_groups_desc* gd = &r.gd;
+        const pt_path_passes_desc ppd = {{0u, 0u, 0u, 0u}};
+        const uint32_t groups = o.path_passes ? (uint32_t)PT_PATH_PASSES : (o.light_groups || o.denoise_groups) ? gd->group_count : 0u;
+        film.resize(4 * np);
+        counts.resize(counted ? np : 0);
+        stats.resize(o.denoise ? 2 * np : 0);
+        spectral.resize((size_t)(o.spectral_bins ? o.spectral_bins : o.denoise_bins) * np);
+        group_films.resize((size_t)groups * 4 * np);
+        group_bins.resize(o.relamp_groups ? (size_t)gd->group_count * o.relamp_bins * np : 0);
+        float* const f = film.data();
+        uint32_t* const n = counts.data();
+        double* const st = stats.data();                             // (the spectral, group and pass entries always take the statistics)
+        double* const st_plain = o.denoise ? stats.data() : nullptr;
+
+        const char* entry = nullptr;
+        std::function<pt_status()> call;
+        std::string suffix;
+        const auto pick = [&](const char* name, std::function<pt_status()> fn) { entry = name; call = std::move(fn); };
+        if (counted) {
+            if (o.denoise_bins && o.spectral_multi) pick("pt_render_adaptive_spectral_multi", [&] { return pt_render_adaptive_spectral_multi(scene, &rd, &ad, &sd, o.spectral_device_mask, f, n, st, spectral.data(), prof); });
+            else if (o.denoise_bins) pick("pt_render_adaptive_spectral", [&] { return pt_render_adaptive_spectral(scene, &rd, &ad, &sd, f, n, st, spectral.data(), prof); });
+            else if (o.denoise_groups && o.group_multi) pick("pt_render_adaptive_light_groups_multi", [&] { return pt_render_adaptive_light_groups_multi(scene, &rd, &ad, gd, o.group_device_mask, f, n, st, group_films.data(), prof); });
+            else if (o.denoise_groups) pick("pt_render_adaptive_light_groups", [&] { return pt_render_adaptive_light_groups(scene, &rd, &ad, gd, f, n, st, group_films.data(), prof); });
+            else if (o.denoise_passes) pick("pt_render_adaptive_path_passes", [&] { return pt_render_adaptive_path_passes(scene, &rd, &ad, &ppd, f, n, st, group_films.data(), prof); });
+            else if (o.multi) pick("pt_render_adaptive_multi", [&] { return pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, f, n, st_plain, prof); });
+            else pick("pt_render_adaptive", [&] { return pt_render_adaptive(scene, &rd, &ad, f, n, st_plain, prof); });
+        } else if (o.spectral_bins) {
+            if (o.spectral_multi) pick("pt_render_spectral_multi", [&] { return pt_render_spectral_multi(scene, &rd, &sd, o.spectral_device_mask, f, spectral.data(), prof); });
+            else pick("pt_render_spectral", [&] { return pt_render_spectral(scene, &rd, &sd, f, spectral.data(), prof); });
+        } else if (o.relamp_groups) {
+            suffix = ", " + std::to_string(gd->group_count) + " light groups of " + std::to_string(o.relamp_bins) + " bins";
+            pick("pt_render_light_groups_spectral", [&] { return pt_render_light_groups_spectral(scene, &rd, gd, &sd, f, nullptr, nullptr, group_bins.data(), prof); });
+        } else if (o.path_passes) {
+            suffix = ", " + std::to_string(PT_PATH_PASSES) + " path passes";
+            pick("pt_render_path_passes", [&] { return pt_render_path_passes(scene, &rd, &ppd, f, group_films.data(), prof); });
+        } else if (o.light_groups) {
+            suffix = ", " + std::to_string(gd->group_count) + " light groups";
+            if (o.group_multi) pick("pt_render_light_groups_multi", [&] { return pt_render_light_groups_multi(scene, &rd, gd, o.group_device_mask, f, group_films.data(), prof); });
+            else pick("pt_render_light_groups", [&] { return pt_render_light_groups(scene, &rd, gd, f, group_films.data(), prof); });
+        } else if (o.multi) pick("pt_render_multi", [&] { return pt_render_multi(scene, &rd, o.device_mask, f, prof); });
+        else pick("pt_render", [&] { return pt_render(scene, &rd, f, prof); });
+
+        char spp[96] = " spp";
+        if (adaptive) snprintf(spp, sizeof(spp), "..%u spp (adaptive, relative error %g)", ad.max_samples, (double)ad.rel_error);
+        else if (counted) { ad.max_samples = rd.spp; ad.rel_error = 0.0f; }
+        printf("rendering %ux%u, %u%s, max_bounces %u, light_samples %u%s\n", rd.width, rd.height, rd.spp, spp, rd.max_bounces, rd.light_samples, suffix.c_str());
+        if (call() != PT_OK) return fail(entry);
+        *samples = (uint64_t)rd.width * rd.height * rd.spp;
+        if (adaptive) {
+            uint32_t lo = 0xffffffffu, hi = 0;
+            *samples = 0;
+            for (uint32_t c : counts) { *samples += c; lo = c < lo ? c : lo; hi = c > hi ? c : hi; }
+            printf("adaptive: %.2f samples per pixel on average, min %u, max %u, %llu rounds\n", (double)*samples / (double)counts.size(), lo, hi,
+                   (unsigned long long)prof->kernel_launches[5]);
+        }
+        return true;
+    }
+
+    // The one picture writer: a film through the setting's film output into `to`, then <stem>.exr, with `png` <stem>.png, and the "wrote ..." line with `note` in
+    // parentheses.  `prefix` is the site's text in front of the engine's error; nullptr is the film itself, which names the stage that failed and, with
+    // --write-film, also stores the film as <stem>.npy.
+    bool write_picture(const float* xyzw, const std::string& stem, Pixels& to, bool png, const std::string& note, const char* prefix) {
+        if (pt_output_film(&od, xyzw, to.rgba.data(), to.linear.data()) != PT_OK) return fail(prefix ? prefix : "pt_output_film");
+        if (pt_write_exr((stem + ".exr").c_str(), rd.width, rd.height, to.linear.data(), od.colorspace) != PT_OK ||
+            (png && pt_write_png((stem + ".png").c_str(), rd.width, rd.height, to.rgba.data(), od.colorspace) != PT_OK))
+            return fail(prefix ? prefix : "failed to write files");   // the reference panics here (mod.rs:45-48)
+        if (!prefix && o.write_film && !write_npy(stem + ".npy", xyzw, rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", stem.c_str()); return false; }
+        printf("wrote %s.exr", stem.c_str());
+        if (png) printf(" and %s.png", stem.c_str());
+        if (!note.empty()) printf(" (%s)", note.c_str());
+        printf("\n");
+        return true;
+    }
+
+    // --mattes: the ranked ids of this setting's frame (pt_render_mattes, beside the render: no other file changes) as a Cryptomatte file with the setting's linear
+    // RGB — instances named instance<i>, materials by their names in the scene file's library
+    bool write_mattes() {
+        const pt_matte_desc md = {o.matte_samples ? o.matte_samples : (rs.min_samples < 65535u ? rs.min_samples : 65535u), o.matte_ranks,
+                                  o.mattes == 2 ? (uint32_t)PT_MATTE_KEY_MATERIAL : (uint32_t)PT_MATTE_KEY_INSTANCE, {0u}};
+        std::vector<uint32_t> m_keys(md.ranks * np), m_overflow(np), named;
+        std::vector<float> m_coverage(md.ranks * np);
+        if (pt_render_mattes(scene, &rd, &md, m_keys.data(), m_coverage.data(), m_overflow.data()) != PT_OK) return fail("pt_render_mattes");
+        std::vector<std::string> names;
+        for (uint32_t key : m_keys) {
+            if (key == PT_MATTE_SKY || key == PT_MATTE_NONE) continue;
+            bool seen = false;
+            for (uint32_t k : named) seen = seen || k == key;
+            if (seen) continue;
+            const char* material = o.mattes == 2 ? pt_scene_file_material_name(r.scene_file.get(), key) : nullptr;
+            named.push_back(key);
+            names.push_back(o.mattes == 1 ? "instance" + std::to_string(key) : material ? std::string(material) : "key" + std::to_string(key));
+        }
+        std::vector<const char*> name_ptrs;
+        for (const std::string& s : names) name_ptrs.push_back(s.c_str());
+        uint64_t dropped = 0;
+        for (uint32_t c : m_overflow) dropped += c;
+        const std::string crypto = base + "_crypto.exr";
+        if (pt_write_exr_cryptomatte(crypto.c_str(), rd.width, rd.height, md.ranks, m_keys.data(), m_coverage.data(), o.mattes == 2 ? "CryptoMaterial" : "CryptoObject",
+                                     (uint32_t)named.size(), named.data(), name_ptrs.data(), px.linear.data(), od.colorspace) != PT_OK)
+            return fail(("failed to write " + crypto).c_str());
+        printf("wrote %s (%u ranks of %u samples, %zu names, %llu samples beyond the ranks)\n", crypto.c_str(), md.ranks, md.samples, names.size(), (unsigned long long)dropped);
+        return true;
+    }
+
+    // --light-groups, --denoise-light-groups: every group's film, and with --light-gains their mix, through this setting's film output (buffers of their own).
+    // `stem`: base, or base + "_denoised" for the films of the joint filter.
+    bool write_groups(const std::string& stem, const std::vector<float>& films, Mix mix) {
+        const uint32_t groups = r.gd.group_count;
+        Pixels own(np);
+        for (uint32_t g = 0; g < groups; ++g)
+            if (!write_picture(films.data() + 4 * np * g, stem + "_light" + std::to_string(g), own, false, "", r.group_flag)) return false;
+        if (!o.has_light_gains) return true;
+        std::vector<float> matrices, relit(4 * np);
+        for (float gain : o.light_gains) for (int k = 0; k < 9; ++k) matrices.push_back(k % 4 == 0 ? gain : 0.0f);
+        const pt_status st = mix == kMixHost              ? pt_light_groups_mix(rd.width, rd.height, groups, films.data(), matrices.data(), relit.data())
+                             : mix == kMixResidentDenoised ? pt_light_groups_mix_resident_denoised(scene, matrices.data(), relit.data())
+                                                           : pt_light_groups_mix_resident(scene, matrices.data(), relit.data());
+        if (st != PT_OK) return fail(r.group_flag);
+        return write_picture(relit.data(), stem + "_relit", own, true, "relit from " + std::to_string(groups) + " light groups", r.group_flag);
+    }
+
+    // --path-passes: every class's film through this setting's film output (buffers of their own).  `stem`: base, or base + "_denoised"
+    bool write_passes(const std::string& stem, const std::vector<float>& films) {
+        Pixels own(np);
+        for (int c = 0; c < PT_PATH_PASSES; ++c)
+            if (!write_picture(films.data() + 4 * np * c, stem + "_pass_" + kPathPassNames[c], own, false, "", "--path-passes")) return false;
+        return true;
+    }
+
+    // --relamp-groups: every group's bins in the units of the EXR payload, and the re-lamped picture — the colour-matching development of the group bins by the
+    // re-lamp matrix, where the render left them on the device — through this setting's film output (buffers of its own)
+    bool write_relamped() {
+        const uint32_t groups = r.gd.group_count;
+        const size_t plane = (size_t)o.relamp_bins * np;
+        std::vector<float> centres(o.relamp_bins), scaled(plane), matrix((size_t)3 * groups * o.relamp_bins), planes(3 * np);
+        if (pt_spectral_bin_centres(&rd, &sd, centres.data()) != PT_OK) return fail("--relamp-groups");
+        for (uint32_t g = 0; g < groups; ++g) {
+            const std::string name = base + "_light" + std::to_string(g) + "_spectral";
+            for (size_t k = 0; k < plane; ++k) scaled[k] = group_bins[plane * g + k] * od.factor;
+            if (pt_write_exr_spectral((name + ".exr").c_str(), rd.width, rd.height, o.relamp_bins, centres.data(), scaled.data(), nullptr, od.colorspace) != PT_OK) return fail("--relamp-groups");
+            printf("wrote %s.exr (%u bins)\n", name.c_str(), o.relamp_bins);
+        }
+        const int32_t cie[3] = {PT_RESPONSE_CIE_X, PT_RESPONSE_CIE_Y, PT_RESPONSE_CIE_Z};
+        const Curves& c = r.relamp_curves;
+        if (pt_light_groups_relamp_matrix(&rd, &sd, c.curves.data(), (uint32_t)c.curves.size(), c.data.data(), (uint32_t)c.data.size(), 3, cie, PT_SPECTRAL_NO_FILTER,
+                                          o.develop_subsamples, groups, r.relamp_old.data(), r.relamp_new.data(), o.has_relamp_gains ? o.relamp_gains.data() : nullptr,
+                                          matrix.data()) != PT_OK ||
+            pt_light_groups_relamp_resident(scene, 3, matrix.data(), planes.data()) != PT_OK)
+            return fail("--relamp-groups");
+        Pixels own(np);
+        return write_picture(pack_planes(planes, np).data(), base + "_relamped", own, true,
+                             "re-lamped from " + std::to_string(groups) + " light groups of " + std::to_string(o.relamp_bins) + " bins", "--relamp-groups");
+    }
+
+    // <name>.exr: the bins in the units of the EXR payload — the same factor, applied here in place, one multiply per value — beside the R, G, B of the picture
+    // written last into `px`
+    bool write_spectral(const std::string& name, std::vector<float>& scaled) {
+        std::vector<float> centres(sd.bins);
+        for (float& v : scaled) v *= od.factor;
+        if (pt_spectral_bin_centres(&rd, &sd, centres.data()) != PT_OK ||
+            pt_write_exr_spectral((name + ".exr").c_str(), rd.width, rd.height, sd.bins, centres.data(), scaled.data(), px.linear.data(), od.colorspace) != PT_OK)
+            return fail(o.spectral_bins ? "--spectral-bins" : "--denoise-spectral-bins");
+        printf("wrote %s.exr (%u bins)\n", name.c_str(), sd.bins);
+        return true;
+    }
+
+    // --develop: three planes from the bins — the scene's resident ones (bins == nullptr; `denoised`: the resident denoised ones) or a host array as rendered or
+    // filtered, before the factor —, packed as an XYZW film with W = 0, through this setting's film output (buffers of its own: `px` still serves the spectral files)
+    bool develop(const std::string& name, const float* bins, bool denoised) {
+        const Curves& c = r.develop_curves;
+        std::vector<float> matrix((size_t)3 * sd.bins), planes(3 * np);
+        pt_status st = pt_spectral_response_matrix(&rd, &sd, c.curves.data(), (uint32_t)c.curves.size(), c.data.data(), (uint32_t)c.data.size(), 3, r.develop_responses,
+                                                   r.develop_filter, o.develop_subsamples, matrix.data());
+        if (st == PT_OK) st = bins       ? pt_spectral_project(rd.width, rd.height, sd.bins, 3, matrix.data(), bins, planes.data())
+                              : denoised ? pt_spectral_project_resident_denoised(scene, 3, matrix.data(), planes.data())
+                                         : pt_spectral_project_resident(scene, 3, matrix.data(), planes.data());
+        if (st != PT_OK) return fail("--develop");
+        Pixels own(np);
+        return write_picture(pack_planes(planes, np).data(), name, own, true, "developed from " + std::to_string(sd.bins) + " bins", "--develop");
+    }
+
+    // The guides over host arrays: `albedo` with --demodulate-albedo, `bin_albedo` too with --demodulate-bins (else nullptr).
+    pt_status host_guides(float* guides, float* albedo, float* bin_albedo) {
+        return bin_albedo ? pt_render_guides_bin_albedo(scene, &rd, o.guide_samples, o.chain ? &cd : nullptr, o.denoise_bins, guides, albedo, bin_albedo)
+               : o.chain  ? pt_render_guides_chain(scene, &rd, o.guide_samples, &cd, guides, albedo)
+               : albedo   ? pt_render_guides_albedo(scene, &rd, o.guide_samples, guides, albedo)
+                          : pt_render_guides(scene, &rd, o.guide_samples, guides);
+    }
+
+    // The guides beside what the render left on the device.
+    pt_status resident_guides() {
+        const uint32_t parts = o.demodulate_bins ? (PT_RESIDENT_ALBEDO | PT_RESIDENT_BIN_ALBEDO) : o.demodulate ? PT_RESIDENT_ALBEDO : 0u;
+        return pt_resident_guides(scene, &rd, o.guide_samples, o.chain ? &cd : nullptr, parts);
+    }
+
+    pt_denoise_desc host_denoise_desc(uint64_t mask) const {   // the default filter on the first device of the mask: where a node render's gather left the film
+        pt_denoise_desc dd;
+        memset(&dd, 0, sizeof(dd));
+        dd.width = rd.width; dd.height = rd.height; dd.device = first_device(mask);
+        return dd;
+    }
+
+    // --denoise: four routes to `clean` — host arrays of a node group render; the resident group or pass films; the resident or assembled film and bins; host
+    // arrays — with their own guide and filter calls, then <base>_denoised.* from it and what the route's flags add.
+    bool denoise() {
+        if (o.assemble) {
+            // the node render left its pieces on the devices: one film on the scene's device from them, unless the mask came down to that device alone and
+            // the render left the film resident itself
+            struct pt_resident_info now;
+            pt_status ast = pt_resident_info(scene, &now);
+            if (ast == PT_OK && !(now.parts & PT_RESIDENT_FILM)) ast = pt_resident_assemble(scene, 0u);
+            if (ast != PT_OK) return fail("--denoise-assemble");
+        }
+        // (a node group render without --denoise-assemble left no film one device can filter, unless the mask came down to the scene's device alone)
+        bool groups_on_host = false;
+        if (o.denoise_groups && o.group_multi && !o.assemble) {
+            struct pt_resident_info now;
+            if (pt_resident_info(scene, &now) != PT_OK) return fail("--light-group-devices");
+            groups_on_host = !(now.parts & PT_RESIDENT_FILM);
+        }
+        const std::string dbase = base + "_denoised";
+        const auto write_clean = [&](const std::vector<float>& clean) { return write_picture(clean.data(), dbase, px, true, "", nullptr); };
+        std::vector<float> clean(4 * np);
+        pt_resident_denoise_desc rdd;
+        memset(&rdd, 0, sizeof(rdd));
+        if (groups_on_host) {
+            // guides and the joint filter over host arrays, on the first device of the mask: the files of the resident route, byte for byte
+            std::vector<float> guides(4 * np), albedo(o.demodulate ? 4 * np : 0), clean_groups(4 * np * r.gd.group_count);
+            float* const alb = o.demodulate ? albedo.data() : nullptr;
+            const pt_denoise_desc dd = host_denoise_desc(o.group_device_mask);
+            pt_status st = host_guides(guides.data(), alb, nullptr);
+            if (st == PT_OK) st = pt_denoise_light_groups(&dd, r.gd.group_count, film.data(), counts.data(), stats.data(), guides.data(), alb, group_films.data(), clean.data(),
+                                                          nullptr, clean_groups.data());
+            if (st != PT_OK) return fail("--denoise-light-groups");
+            return write_clean(clean) && write_groups(dbase, clean_groups, kMixHost);
+        }
+        if (o.denoise_groups || o.denoise_passes) {
+            // the render left the film, its statistics and the group films on the device, paired: the guides stay there too, and the joint filter runs on all of
+            // it (with or without --denoise-resident: this is the only route, and its files are those of either)
+            // (--denoise-path-passes: the pass films are the resident group films of this route)
+            std::vector<float> clean_groups(4 * np * (o.denoise_passes ? (uint32_t)PT_PATH_PASSES : r.gd.group_count));
+            pt_status st = resident_guides();
+            if (st == PT_OK) st = pt_denoise_light_groups_resident(scene, &rdd, clean.data(), nullptr, clean_groups.data());
+            if (st != PT_OK) return fail(o.denoise_passes ? "--denoise-path-passes" : "--denoise-light-groups");
+            return write_clean(clean) && (o.denoise_passes ? write_passes(dbase, clean_groups) : write_groups(dbase, clean_groups, kMixResidentDenoised));
+        }
+        std::vector<float> clean_spectral(spectral.size());
+        const bool on_device = o.resident || o.assemble;
+        if (on_device) {
+            // the render left film, counts, statistics and bins on the device: the guides stay there too, and the filter runs on all of it
+            pt_status st = resident_guides();
+            if (st == PT_OK) st = pt_denoise_resident(scene, &rdd, clean.data(), nullptr, o.denoise_bins ? clean_spectral.data() : nullptr);
+            if (st != PT_OK) return fail(o.assemble ? "--denoise-assemble" : "--denoise-resident");
+        } else {
+            const bool with_albedo = o.demodulate || o.demodulate_bins;
+            std::vector<float> guides(4 * np), albedo(with_albedo ? 4 * np : 0), bin_albedo(o.demodulate_bins ? spectral.size() : 0);
+            float* const alb = with_albedo ? albedo.data() : nullptr;
+            const pt_denoise_desc dd = host_denoise_desc(o.multi ? o.device_mask : o.spectral_multi ? o.spectral_device_mask : 0);
+            pt_status st = host_guides(guides.data(), alb, o.demodulate_bins ? bin_albedo.data() : nullptr);
+            if (st == PT_OK)
+                st = o.demodulate_bins ? pt_denoise_spectral_albedo(&dd, o.denoise_bins, film.data(), counts.data(), stats.data(), guides.data(), alb, spectral.data(),
+                                                                    bin_albedo.data(), clean.data(), clean_spectral.data(), nullptr)
+                     : o.denoise_bins  ? pt_denoise_spectral(&dd, o.denoise_bins, film.data(), counts.data(), stats.data(), guides.data(), spectral.data(), clean.data(),
+                                                             clean_spectral.data(), nullptr)
+                                       : pt_denoise_film_albedo(&dd, film.data(), counts.data(), stats.data(), guides.data(), alb, clean.data(), nullptr);
+            if (st != PT_OK) return fail("--denoise");
+        }
+        if (!write_clean(clean)) return false;
+        // the denoised bins are developed before the factor goes into them, and their file carries the denoised film's R, G, B, which `px` now holds
+        if (o.develop && o.denoise_bins && !develop(dbase + "_developed", on_device ? nullptr : clean_spectral.data(), true)) return false;
+        return !o.denoise_bins || write_spectral(dbase + "_spectral", clean_spectral);
+    }
+
+    bool run() {
+        if (o.hero) rd.hero_wavelengths = o.hero;   // engine extension (not in the reference's files): 4 wavelengths per path
+        np = (size_t)rd.width * rd.height;
+        memset(&cd, 0, sizeof(cd));
+        cd.max_chain = o.max_chain; cd.alpha_max = o.alpha_max;
+        sd = {o.spectral_bins ? o.spectral_bins : o.denoise_bins ? o.denoise_bins : o.relamp_bins, {0u, 0u, 0u}};
+        pt_profile prof;
+        uint64_t samples = 0;
+        if (!render(&prof, &samples)) return false;
+        // Profile::pretty_print (src/profile.rs:20-34)
+        const double total = (double)(prof.camera_rays + prof.bounce_rays + prof.shadow_rays + prof.light_rays);
+        printf("took %.3fs\n", prof.seconds);
+        printf("%llu camera rays, %llu bounce rays, %llu shadow rays, %llu light rays, %llu environment hits\n", (unsigned long long)prof.camera_rays,
+               (unsigned long long)prof.bounce_rays, (unsigned long long)prof.shadow_rays, (unsigned long long)prof.light_rays, (unsigned long long)prof.env_hits);
+        printf("%.1f rays per second, %.3f Msamples/s\n", total / prof.seconds, (double)samples / prof.seconds * 1e-6);
+        pt_config_output_desc(r.config.get(), index, 1.0f, &od);
+        px = Pixels(np);
+        base = o.output_dir + "/" + (rs.filename ? rs.filename : "beauty");  // src/renderer/mod.rs:27-31
+        if (!write_picture(film.data(), base, px, true, "", nullptr)) return false;
+        if (o.mattes && !write_mattes()) return false;
+        if (r.group_mode && !o.relamp_groups && !write_groups(base, group_films, kMixResident)) return false;
+        if (o.path_passes && !write_passes(base, group_films)) return false;
+        if (o.relamp_groups && !write_relamped()) return false;
+        if (o.denoise_bins) {   // (a copy: the filter takes the bins as rendered)
+            std::vector<float> noisy(spectral);
+            if (!write_spectral(base + "_spectral", noisy)) return false;
+        } else if (!spectral.empty() && !write_spectral(base + "_spectral", spectral)) return false;
+        // (a node render leaves its bins resident too, with either flag: they are developed on the devices)
+        if (o.develop && !develop(base + "_developed", o.denoise_bins && !o.spectral_multi && !o.resident ? spectral.data() : nullptr, false)) return false;
+        return !o.denoise || denoise();
+    }
+};
+
+// Every [[render_settings]] entry in turn; the first that fails ends the run.
+bool render_settings(Run& r) {
+    pt_scene* scene = nullptr;
+    if (pt_scene_create(r.desc, &scene) != PT_OK) return fail("pt_scene_create");
+    r.scene.reset(scene);
+    const uint32_t n = pt_config_render_settings_count(r.config.get());
+    for (uint32_t i = 0; i < n; ++i) {
+        Setting s(r, i);
+        pt_config_render_settings(r.config.get(), i, &s.rs);
+        if (pt_config_render_desc(r.config.get(), i, r.o.seed, &s.rd) != PT_OK) {
+            // the reference skips render settings whose integrator it cannot construct (src/renderer/tiled.rs:560-566)
+            fprintf(stderr, "skipping render settings %u: %s\n", i, pt_scene_file_last_error());
+            continue;
+        }
+        if (!s.run()) return false;
+    }
+    printf("render done\n");
+    return true;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    Run r;
+    Options& o = r.o;
+    bool help = false;
+    std::string mistake = parse_options(argc, argv, o, &help);
+    if (help) { usage(""); return 0; }
+    if (mistake.empty()) mistake = check_options(o);
+    if (!mistake.empty()) return usage(mistake);
     const bool verbose = o.stdout_log_level == "info" || o.stdout_log_level == "debug" || o.stdout_log_level == "trace";
-    const bool warnings = verbose || o.stdout_log_level == "warn";
+    r.warnings = verbose || o.stdout_log_level == "warn";
     if (!o.root.empty()) pt_scene_file_set_root(o.root.c_str());
 
     pt_config* config = nullptr;
@@ -483,569 +974,34 @@ int main(int argc, char** argv) {
         fprintf(stderr, "couldn't read config.toml, %s\n", pt_scene_file_last_error());   // main.rs:115-121
         return 1;
     }
+    r.config.reset(config);
     std::string scene_path = o.has_scene ? o.scene : pt_config_scene_file(config);        // main.rs:133
     pt_scene_file* scene_file = nullptr;
     if (pt_scene_file_load(scene_path.c_str(), config, &scene_file) != PT_OK) {
         fprintf(stderr, "failed to construct the scene: %s\n", pt_scene_file_last_error());  // main.rs:139-149
-        pt_config_free(config);
         return 1;
     }
-    if (warnings) for (uint32_t k = 0; k < pt_scene_file_warning_count(scene_file); ++k) fprintf(stderr, "warning: %s\n", pt_scene_file_warning(scene_file, k));
-    const pt_scene_desc* desc = pt_scene_file_desc(scene_file);
+    r.scene_file.reset(scene_file);
+    if (r.warnings) for (uint32_t k = 0; k < pt_scene_file_warning_count(scene_file); ++k) fprintf(stderr, "warning: %s\n", pt_scene_file_warning(scene_file, k));
+    const pt_scene_desc* desc = r.desc = pt_scene_file_desc(scene_file);
     if (verbose) printf("scene %s: %u instances, %u meshes, %zu triangles, %u materials, %u curves\n", scene_path.c_str(), desc->instance_count, desc->mesh_count,
                         desc->index_count / 3, desc->material_count, desc->curve_count);
 
-    // --develop: the response curves and the filter, from the curves library of the scene file (in pt_scene_desc's representation, for pt_spectral_response_matrix)
-    std::vector<pt_curve> develop_curves;
-    std::vector<float> develop_data;
-    int32_t develop_responses[3] = {PT_RESPONSE_CIE_X, PT_RESPONSE_CIE_Y, PT_RESPONSE_CIE_Z}, develop_filter = PT_SPECTRAL_NO_FILTER;
-    if (o.develop) {
-        std::vector<std::string> names = o.develop_curves;
-        if (o.has_develop_filter) names.push_back(o.develop_filter);
-        for (size_t k = 0; k < names.size(); ++k) {
-            pt_curve c; const float* data = nullptr; uint32_t floats = 0;
-            if (pt_scene_file_library_curve(scene_file, names[k].c_str(), &c, &data, &floats) != PT_OK) {
-                fprintf(stderr, "error: --develop: %s\n", pt_scene_file_last_error());
-                pt_scene_file_free(scene_file);
-                pt_config_free(config);
-                return 1;
-            }
-            c.data_offset = (uint32_t)develop_data.size();
-            develop_data.insert(develop_data.end(), data, data + floats);
-            develop_curves.push_back(c);
-            if (k < o.develop_curves.size()) develop_responses[k] = (int32_t)k; else develop_filter = (int32_t)k;
-        }
-    }
-
-    // --light-groups: a group per emitting instance or per light material in scene order, the environment last when it emits
-    std::vector<uint8_t> instance_group(desc->instance_count, 0);
-    pt_light_groups_desc gd;
-    memset(&gd, 0, sizeof(gd));
-    const int group_mode = o.light_groups ? o.light_groups : o.denoise_groups ? o.denoise_groups : o.relamp_groups;
-    const char* group_flag = o.light_groups ? "--light-groups" : o.denoise_groups ? "--denoise-light-groups" : "--relamp-groups";
-    if (group_mode) {
-        std::vector<uint32_t> keys;   // a group's key: the instance (mode 1) or the packed light material (mode 2)
-        uint32_t groups = 0;
-        for (uint32_t i = 0; i < desc->instance_count; ++i) {
-            const pt_instance& in = desc->instances[i];
-            uint32_t light = PT_MATERIAL_NONE;   // the instance's first light material
-            if (in.material != PT_MATERIAL_NONE) { if (PT_MATERIAL_TAG(in.material) == PT_TAG_LIGHT) light = in.material; }
-            else if (in.kind == PT_SHAPE_MESH && in.mesh >= 0 && (uint32_t)in.mesh < desc->mesh_count && desc->meshes[in.mesh].face_material_offset >= 0) {
-                const pt_mesh& m = desc->meshes[in.mesh];
-                for (uint32_t f = 0; f < m.face_count && light == PT_MATERIAL_NONE; ++f) {
-                    const uint32_t id = desc->face_materials[(size_t)m.face_material_offset + f];
-                    if (PT_MATERIAL_TAG(id) == PT_TAG_LIGHT) light = id;
-                }
-            }
-            if (light == PT_MATERIAL_NONE) continue;
-            const uint32_t key = group_mode == 1 ? i : light;
-            uint32_t g = 0;
-            while (g < keys.size() && keys[g] != key) ++g;
-            if (g == keys.size()) keys.push_back(key);
-            if (g < PT_LIGHT_GROUPS_MAX) instance_group[i] = (uint8_t)g;
-        }
-        groups = (uint32_t)keys.size();
-        const bool env_emits = desc->environment.strength != 0.0f;
-        gd.environment_group = env_emits ? groups : 0u;
-        if (env_emits) ++groups;
-        if (groups == 0) groups = 1;
-        const char* why = groups > PT_LIGHT_GROUPS_MAX ? "the scene has more than 8 light groups"
-                          : (o.has_light_gains && o.light_gains.size() != groups) ? "--light-gains needs one gain per group" : nullptr;
-        if (why) {
-            fprintf(stderr, "error: %s: %s (%u groups)\n", group_flag, why, groups);
-            pt_scene_file_free(scene_file);
-            pt_config_free(config);
-            return 1;
-        }
-        gd.group_count = groups; gd.instance_count = desc->instance_count; gd.instance_group = instance_group.data();
-        printf("light groups: %u (%s%s)\n", groups, group_mode == 1 ? "one per emitting instance" : "one per light material", env_emits ? ", the environment last" : "");
-    }
-
+    if (o.develop && !load_develop_curves(r)) return 1;
+    r.instance_group.assign(desc->instance_count, 0);
+    memset(&r.gd, 0, sizeof(r.gd));
+    r.group_mode = o.light_groups ? o.light_groups : o.denoise_groups ? o.denoise_groups : o.relamp_groups;
+    r.group_flag = o.light_groups ? "--light-groups" : o.denoise_groups ? "--denoise-light-groups" : "--relamp-groups";
+    if (r.group_mode && !form_light_groups(r)) return 1;
     if (o.path_passes) {
         printf("path passes: %d (", PT_PATH_PASSES);
         for (int c = 0; c < PT_PATH_PASSES; ++c) printf("%s%s", c ? ", " : "", kPathPassNames[c]);
         printf(")\n");
     }
-    const pt_path_passes_desc ppd = {{0u, 0u, 0u, 0u}};
-
-    // --relamp-groups: the curves of pt_light_groups_relamp_matrix — the scene's own, where a group's old curve is, and behind them the new ones from the curves
-    // library of the scene file — and per group the old and the new curve
-    std::vector<pt_curve> relamp_curves;
-    std::vector<float> relamp_data;
-    std::vector<int32_t> relamp_old(PT_LIGHT_GROUPS_MAX, PT_RELAMP_KEEP), relamp_new(PT_LIGHT_GROUPS_MAX, PT_RELAMP_KEEP);
-    if (o.relamp_groups) {
-        const auto refuse = [&](const std::string& why) {
-            fprintf(stderr, "error: --relamp-groups: %s\n", why.c_str());
-            pt_scene_file_free(scene_file);
-            pt_config_free(config);
-            return 1;
-        };
-        if (o.has_relamp_gains && o.relamp_gains.size() != gd.group_count) return refuse("--relamp-gains needs one gain per group (" + std::to_string(gd.group_count) + " groups)");
-        relamp_curves.assign(desc->curves, desc->curves + desc->curve_count);
-        relamp_data.assign(desc->curve_data, desc->curve_data + desc->curve_data_count);
-        const bool env_emits = desc->environment.strength != 0.0f;
-        for (const auto& item : o.relamp) {
-            const uint32_t g = item.first;
-            if (g >= gd.group_count) return refuse("--relamp names group " + std::to_string(g) + ", the scene has " + std::to_string(gd.group_count) + " groups");
-            // the emission curve the group's emitters share: every light material of its instances, and the environment's curve when it is the environment's group
-            int32_t old = -1;
-            bool mixed = false, any = false;
-            const auto emitter = [&](int32_t curve) { mixed = mixed || (any && curve != old); old = curve; any = true; };
-            if (env_emits && gd.environment_group == g) {
-                if (desc->environment.kind == PT_ENV_HDR)
-                    return refuse("--relamp names group " + std::to_string(g) + ", the environment, which an HDR texture lights: it has no single emission curve to replace");
-                emitter(desc->environment.curve);
-            }
-            for (uint32_t i = 0; i < desc->instance_count; ++i) {
-                if (instance_group[i] != g) continue;
-                const pt_instance& in = desc->instances[i];
-                const auto light = [&](uint32_t id) { if (PT_MATERIAL_TAG(id) == PT_TAG_LIGHT && PT_MATERIAL_INDEX(id) < desc->material_count) emitter(desc->materials[PT_MATERIAL_INDEX(id)].curve_emit); };
-                if (in.material != PT_MATERIAL_NONE) light(in.material);
-                else if (in.kind == PT_SHAPE_MESH && in.mesh >= 0 && (uint32_t)in.mesh < desc->mesh_count && desc->meshes[in.mesh].face_material_offset >= 0) {
-                    const pt_mesh& m = desc->meshes[in.mesh];
-                    for (uint32_t f = 0; f < m.face_count; ++f) light(desc->face_materials[(size_t)m.face_material_offset + f]);
-                }
-            }
-            if (!any) return refuse("--relamp names group " + std::to_string(g) + ", which holds no emitter");
-            if (mixed) return refuse("--relamp names group " + std::to_string(g) + ", whose emitters have different emission curves: it has no single curve to replace");
-            pt_curve c; const float* data = nullptr; uint32_t floats = 0;
-            if (pt_scene_file_library_curve(scene_file, item.second.c_str(), &c, &data, &floats) != PT_OK) return refuse(std::string("--relamp: ") + pt_scene_file_last_error());
-            c.data_offset = (uint32_t)relamp_data.size();
-            relamp_data.insert(relamp_data.end(), data, data + floats);
-            relamp_old[g] = old; relamp_new[g] = (int32_t)relamp_curves.size();
-            relamp_curves.push_back(c);
-        }
-    }
-
-    // --denoise: what the adaptive path refuses is refused here, with its message, before anything is rendered or written
-    if (o.denoise && !o.dry_run) {
-        uint32_t tw = 0, th = 0;
-        const bool naive = pt_config_renderer(config, &tw, &th) == PT_RENDERER_NAIVE;
-        for (uint32_t i = 0; i < pt_config_render_settings_count(config); ++i) {
-            pt_render_settings rs; pt_render_desc rd;
-            pt_config_render_settings(config, i, &rs);
-            if (pt_config_render_desc(config, i, o.seed, &rd) != PT_OK) continue;   // (skipped below as well)
-            const bool range = o.adaptive >= 0.0f && !naive && rs.max_samples >= 0 && (uint32_t)rs.max_samples > rd.spp;   // (--adaptive rounds a range up itself)
-            const char* why = naive ? "adaptive sampling needs phases of 10 samples (phase_samples 0 or 10)"
-                                    : ((!range && rd.spp % 10u != 0u) ? "spp, step and max_samples must be multiples of 10" : nullptr);
-            if (why) {
-                fprintf(stderr, "error: --denoise: render settings %u (%s, min_samples %u) cannot take the adaptive path the statistics come from: %s\n", i,
-                        naive ? "Naive renderer" : "Tiled renderer", rd.spp, why);
-                pt_scene_file_free(scene_file);
-                pt_config_free(config);
-                return 1;
-            }
-        }
-    }
+    if (o.relamp_groups && !load_relamp_curves(r)) return 1;
+    if (o.denoise && !o.dry_run && !adaptive_path_takes_every_setting(r)) return 1;
 
     printf("constructing renderer\n");
     mkdir(o.output_dir.c_str(), 0777);                                                     // main.rs:155-158
-    int rc = 0;
-    if (!o.dry_run) {
-        pt_scene* scene = nullptr;
-        if (pt_scene_create(desc, &scene) != PT_OK) { fprintf(stderr, "pt_scene_create: %s\n", pt_last_error()); rc = 1; }
-        const uint32_t n = pt_config_render_settings_count(config);
-        for (uint32_t i = 0; rc == 0 && i < n; ++i) {
-            pt_render_settings rs; pt_render_desc rd; pt_output_desc od;
-            pt_config_render_settings(config, i, &rs);
-            if (pt_config_render_desc(config, i, o.seed, &rd) != PT_OK) {
-                // the reference skips render settings whose integrator it cannot construct (src/renderer/tiled.rs:560-566)
-                fprintf(stderr, "skipping render settings %u: %s\n", i, pt_scene_file_last_error());
-                continue;
-            }
-            if (o.hero) rd.hero_wavelengths = o.hero;   // engine extension (not in the reference's files): 4 wavelengths per path
-            std::vector<float> film((size_t)rd.width * rd.height * 4);
-            pt_profile prof;
-            // --adaptive: min_samples .. max_samples per pixel (pt_render_adaptive) where the setting gives a range and the renderer sums in phases of 10
-            bool adaptive = o.adaptive >= 0.0f;
-            pt_adaptive_desc ad = {0u, 0u, o.adaptive, 0.0f};
-            if (adaptive) {
-                uint32_t tw = 0, th = 0;
-                if (pt_config_renderer(config, &tw, &th) == PT_RENDERER_NAIVE) {
-                    if (warnings) fprintf(stderr, "warning: --adaptive: render settings %u use the Naive renderer; rendering %u spp everywhere\n", i, rd.spp);
-                    adaptive = false;
-                } else if (rs.max_samples < 0 || (uint32_t)rs.max_samples <= rd.spp) {
-                    if (warnings) fprintf(stderr, "warning: --adaptive: render settings %u have no max_samples > min_samples; rendering %u spp everywhere\n", i, rd.spp);
-                    adaptive = false;
-                } else {
-                    const uint32_t lo = (rd.spp + 9u) / 10u * 10u, hi = ((uint32_t)rs.max_samples + 9u) / 10u * 10u;
-                    if ((lo != rd.spp || hi != (uint32_t)rs.max_samples) && warnings)
-                        fprintf(stderr, "warning: --adaptive: samples %u..%d rounded up to %u..%u (multiples of 10)\n", rd.spp, rs.max_samples, lo, hi);
-                    rd.spp = lo; ad.max_samples = hi;
-                }
-            }
-            const bool with_counts = adaptive || o.denoise;
-            std::vector<uint32_t> counts(with_counts ? (size_t)rd.width * rd.height : 0);
-            std::vector<double> stats(o.denoise ? (size_t)rd.width * rd.height * 2 : 0);
-            std::vector<float> spectral((size_t)o.denoise_bins * rd.width * rd.height);   // (--spectral-bins sizes it below)
-            std::vector<float> group_films;   // (--light-groups sizes it below)
-            std::vector<float> group_bins;    // (--relamp-groups sizes it below)
-            const pt_spectral_desc dsd = {o.denoise_bins, {0u, 0u, 0u}};
-            const char* adaptive_entry = o.denoise_bins ? (o.spectral_multi ? "pt_render_adaptive_spectral_multi" : "pt_render_adaptive_spectral")
-                                         : o.denoise_groups ? (o.group_multi ? "pt_render_adaptive_light_groups_multi" : "pt_render_adaptive_light_groups")
-                                         : o.denoise_passes ? "pt_render_adaptive_path_passes" : o.multi ? "pt_render_adaptive_multi" : "pt_render_adaptive";
-            if (o.denoise_groups) group_films.resize((size_t)gd.group_count * rd.width * rd.height * 4);
-            if (o.path_passes) group_films.resize((size_t)PT_PATH_PASSES * rd.width * rd.height * 4);
-            // --denoise-path-passes: the adaptive pass render — film, counts and statistics are pt_render_adaptive's bit for bit
-            const auto adaptive_passes = [&] { return pt_render_adaptive_path_passes(scene, &rd, &ad, &ppd, film.data(), counts.data(), stats.data(), group_films.data(), &prof); };
-            // --denoise-light-groups: the adaptive group render — film, counts and statistics are pt_render_adaptive's bit for bit
-            // (--light-group-devices: on the devices of the mask)
-            const auto adaptive_groups = [&] {
-                return o.group_multi ? pt_render_adaptive_light_groups_multi(scene, &rd, &ad, &gd, o.group_device_mask, film.data(), counts.data(), stats.data(), group_films.data(), &prof)
-                                     : pt_render_adaptive_light_groups(scene, &rd, &ad, &gd, film.data(), counts.data(), stats.data(), group_films.data(), &prof);
-            };
-            // --denoise-spectral-bins: the adaptive spectral render, on one device or (--spectral-devices) on the devices of the mask
-            const auto adaptive_spectral = [&](double* st_out) {
-                return o.spectral_multi ? pt_render_adaptive_spectral_multi(scene, &rd, &ad, &dsd, o.spectral_device_mask, film.data(), counts.data(), st_out, spectral.data(), &prof)
-                                        : pt_render_adaptive_spectral(scene, &rd, &ad, &dsd, film.data(), counts.data(), st_out, spectral.data(), &prof);
-            };
-            uint64_t samples = (uint64_t)rd.width * rd.height * rd.spp;
-            if (!adaptive && o.denoise) {
-                // a fixed count through the adaptive path (max_samples = min_samples, one round): pt_render's film bit for bit, and the statistics
-                printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
-                ad.max_samples = rd.spp; ad.rel_error = 0.0f;
-                const pt_status st = o.denoise_bins ? adaptive_spectral(stats.data())
-                                     : o.denoise_groups ? adaptive_groups()
-                                     : o.denoise_passes ? adaptive_passes()
-                                     : o.multi      ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), stats.data(), &prof)
-                                                    : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), stats.data(), &prof);
-                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", adaptive_entry, pt_last_error()); rc = 1; break; }
-            } else if (adaptive) {
-                printf("rendering %ux%u, %u..%u spp (adaptive, relative error %g), max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, ad.max_samples,
-                       (double)ad.rel_error, rd.max_bounces, rd.light_samples);
-                const pt_status st = o.denoise_bins ? adaptive_spectral(stats.data())
-                                     : o.denoise_groups ? adaptive_groups()
-                                     : o.denoise_passes ? adaptive_passes()
-                                     : o.multi      ? pt_render_adaptive_multi(scene, &rd, &ad, o.device_mask, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof)
-                                                    : pt_render_adaptive(scene, &rd, &ad, film.data(), counts.data(), o.denoise ? stats.data() : nullptr, &prof);
-                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", adaptive_entry, pt_last_error()); rc = 1; break; }
-                uint32_t lo = 0xffffffffu, hi = 0;
-                samples = 0;
-                for (uint32_t c : counts) { samples += c; lo = c < lo ? c : lo; hi = c > hi ? c : hi; }
-                printf("adaptive: %.2f samples per pixel on average, min %u, max %u, %llu rounds\n", (double)samples / (double)counts.size(), lo, hi,
-                       (unsigned long long)prof.kernel_launches[5]);
-            } else if (o.spectral_bins) {
-                printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
-                spectral.resize((size_t)o.spectral_bins * rd.width * rd.height);
-                const pt_spectral_desc sd = {o.spectral_bins, {0u, 0u, 0u}};
-                const pt_status st = o.spectral_multi ? pt_render_spectral_multi(scene, &rd, &sd, o.spectral_device_mask, film.data(), spectral.data(), &prof)
-                                                      : pt_render_spectral(scene, &rd, &sd, film.data(), spectral.data(), &prof);
-                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.spectral_multi ? "pt_render_spectral_multi" : "pt_render_spectral", pt_last_error()); rc = 1; break; }
-            } else if (o.relamp_groups) {
-                printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u, %u light groups of %u bins\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples,
-                       gd.group_count, o.relamp_bins);
-                group_bins.resize((size_t)gd.group_count * o.relamp_bins * rd.width * rd.height);
-                const pt_spectral_desc sd = {o.relamp_bins, {0u, 0u, 0u}};
-                if (pt_render_light_groups_spectral(scene, &rd, &gd, &sd, film.data(), nullptr, nullptr, group_bins.data(), &prof) != PT_OK) {
-                    fprintf(stderr, "pt_render_light_groups_spectral: %s\n", pt_last_error()); rc = 1; break;
-                }
-            } else if (o.path_passes) {
-                printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u, %d path passes\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples, PT_PATH_PASSES);
-                if (pt_render_path_passes(scene, &rd, &ppd, film.data(), group_films.data(), &prof) != PT_OK) { fprintf(stderr, "pt_render_path_passes: %s\n", pt_last_error()); rc = 1; break; }
-            } else if (o.light_groups) {
-                printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u, %u light groups\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples, gd.group_count);
-                group_films.resize((size_t)gd.group_count * rd.width * rd.height * 4);
-                const pt_status st = o.group_multi ? pt_render_light_groups_multi(scene, &rd, &gd, o.group_device_mask, film.data(), group_films.data(), &prof)
-                                                   : pt_render_light_groups(scene, &rd, &gd, film.data(), group_films.data(), &prof);
-                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.group_multi ? "pt_render_light_groups_multi" : "pt_render_light_groups", pt_last_error()); rc = 1; break; }
-            } else {
-                printf("rendering %ux%u, %u spp, max_bounces %u, light_samples %u\n", rd.width, rd.height, rd.spp, rd.max_bounces, rd.light_samples);
-                const pt_status st = o.multi ? pt_render_multi(scene, &rd, o.device_mask, film.data(), &prof) : pt_render(scene, &rd, film.data(), &prof);
-                if (st != PT_OK) { fprintf(stderr, "%s: %s\n", o.multi ? "pt_render_multi" : "pt_render", pt_last_error()); rc = 1; break; }
-            }
-            // Profile::pretty_print (src/profile.rs:20-34)
-            const double total = (double)(prof.camera_rays + prof.bounce_rays + prof.shadow_rays + prof.light_rays);
-            printf("took %.3fs\n", prof.seconds);
-            printf("%llu camera rays, %llu bounce rays, %llu shadow rays, %llu light rays, %llu environment hits\n", (unsigned long long)prof.camera_rays,
-                   (unsigned long long)prof.bounce_rays, (unsigned long long)prof.shadow_rays, (unsigned long long)prof.light_rays, (unsigned long long)prof.env_hits);
-            printf("%.1f rays per second, %.3f Msamples/s\n", total / prof.seconds, (double)samples / prof.seconds * 1e-6);
-            pt_config_output_desc(config, i, 1.0f, &od);
-            std::vector<uint8_t> rgba((size_t)rd.width * rd.height * 4);
-            std::vector<float> linear((size_t)rd.width * rd.height * 3);
-            if (pt_output_film(&od, film.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }
-            const std::string base = o.output_dir + "/" + (rs.filename ? rs.filename : "beauty");  // src/renderer/mod.rs:27-31
-            if (pt_write_exr((base + ".exr").c_str(), rd.width, rd.height, linear.data(), od.colorspace) != PT_OK ||
-                pt_write_png((base + ".png").c_str(), rd.width, rd.height, rgba.data(), od.colorspace) != PT_OK) {
-                fprintf(stderr, "failed to write files: %s\n", pt_last_error()); rc = 1; break;  // the reference panics here (mod.rs:45-48)
-            }
-            if (o.write_film && !write_npy(base + ".npy", film.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", base.c_str()); rc = 1; break; }
-            printf("wrote %s.exr and %s.png\n", base.c_str(), base.c_str());
-            // --mattes: the ranked ids of this setting's frame (pt_render_mattes, beside the render: no file above changes) as a Cryptomatte file with the
-            // setting's linear RGB — instances named instance<i>, materials by their names in the scene file's library
-            if (o.mattes) {
-                const size_t np = (size_t)rd.width * rd.height;
-                const pt_matte_desc md = {o.matte_samples ? o.matte_samples : (rs.min_samples < 65535u ? rs.min_samples : 65535u), o.matte_ranks,
-                                          o.mattes == 2 ? (uint32_t)PT_MATTE_KEY_MATERIAL : (uint32_t)PT_MATTE_KEY_INSTANCE, {0u}};
-                std::vector<uint32_t> m_keys(md.ranks * np), m_overflow(np), named;
-                std::vector<float> m_coverage(md.ranks * np);
-                if (pt_render_mattes(scene, &rd, &md, m_keys.data(), m_coverage.data(), m_overflow.data()) != PT_OK) { fprintf(stderr, "pt_render_mattes: %s\n", pt_last_error()); rc = 1; break; }
-                std::vector<std::string> names;
-                for (uint32_t key : m_keys) {
-                    if (key == PT_MATTE_SKY || key == PT_MATTE_NONE) continue;
-                    bool seen = false;
-                    for (uint32_t k : named) seen = seen || k == key;
-                    if (seen) continue;
-                    const char* material = o.mattes == 2 ? pt_scene_file_material_name(scene_file, key) : nullptr;
-                    named.push_back(key);
-                    names.push_back(o.mattes == 1 ? "instance" + std::to_string(key) : material ? std::string(material) : "key" + std::to_string(key));
-                }
-                std::vector<const char*> name_ptrs;
-                for (const std::string& s : names) name_ptrs.push_back(s.c_str());
-                uint64_t dropped = 0;
-                for (uint32_t c : m_overflow) dropped += c;
-                const std::string crypto = base + "_crypto.exr";
-                if (pt_write_exr_cryptomatte(crypto.c_str(), rd.width, rd.height, md.ranks, m_keys.data(), m_coverage.data(), o.mattes == 2 ? "CryptoMaterial" : "CryptoObject",
-                                             (uint32_t)named.size(), named.data(), name_ptrs.data(), linear.data(), od.colorspace) != PT_OK) {
-                    fprintf(stderr, "failed to write %s: %s\n", crypto.c_str(), pt_last_error()); rc = 1; break;
-                }
-                printf("wrote %s (%u ranks of %u samples, %zu names, %llu samples beyond the ranks)\n", crypto.c_str(), md.ranks, md.samples, names.size(), (unsigned long long)dropped);
-            }
-            // --light-groups, --denoise-light-groups: every group's film, and with --light-gains the resident mix, through this setting's film output (buffers of
-            // their own).  `stem`: base, or base + "_denoised" for the films of the joint filter, which are then mixed where that left them.
-            // (host_mix: the films were filtered over host arrays and are mixed from there, pt_light_groups_mix)
-            const auto write_groups = [&](const std::string& stem, const std::vector<float>& films, bool denoised, bool host_mix = false) {
-                const size_t np = (size_t)rd.width * rd.height;
-                std::vector<float> g_linear(3 * np), relit(4 * np), matrices;
-                std::vector<uint8_t> g_rgba(4 * np);
-                bool ok = true;
-                for (uint32_t g = 0; ok && g < gd.group_count; ++g) {
-                    const std::string name = stem + "_light" + std::to_string(g);
-                    ok = pt_output_film(&od, films.data() + 4 * np * g, g_rgba.data(), g_linear.data()) == PT_OK &&
-                         pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, g_linear.data(), od.colorspace) == PT_OK;
-                    if (ok) printf("wrote %s.exr\n", name.c_str());
-                }
-                if (ok && o.has_light_gains) {
-                    for (float gain : o.light_gains) for (int k = 0; k < 9; ++k) matrices.push_back(k % 4 == 0 ? gain : 0.0f);
-                    const std::string name = stem + "_relit";
-                    ok = (host_mix ? pt_light_groups_mix(rd.width, rd.height, gd.group_count, films.data(), matrices.data(), relit.data())
-                          : denoised ? pt_light_groups_mix_resident_denoised(scene, matrices.data(), relit.data()) : pt_light_groups_mix_resident(scene, matrices.data(), relit.data())) == PT_OK &&
-                         pt_output_film(&od, relit.data(), g_rgba.data(), g_linear.data()) == PT_OK &&
-                         pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, g_linear.data(), od.colorspace) == PT_OK &&
-                         pt_write_png((name + ".png").c_str(), rd.width, rd.height, g_rgba.data(), od.colorspace) == PT_OK;
-                    if (ok) printf("wrote %s.exr and %s.png (relit from %u light groups)\n", name.c_str(), name.c_str(), gd.group_count);
-                }
-                if (!ok) fprintf(stderr, "%s: %s\n", group_flag, pt_last_error());
-                return ok;
-            };
-            if (group_mode && !o.relamp_groups && !write_groups(base, group_films, false)) { rc = 1; break; }
-            // --path-passes: every class's film through this setting's film output (buffers of their own).  `stem`: base, or base + "_denoised"
-            const auto write_passes = [&](const std::string& stem, const std::vector<float>& films) {
-                const size_t np = (size_t)rd.width * rd.height;
-                std::vector<float> p_linear(3 * np);
-                std::vector<uint8_t> p_rgba(4 * np);
-                bool ok = true;
-                for (int c = 0; ok && c < PT_PATH_PASSES; ++c) {
-                    const std::string name = stem + "_pass_" + kPathPassNames[c];
-                    ok = pt_output_film(&od, films.data() + 4 * np * c, p_rgba.data(), p_linear.data()) == PT_OK &&
-                         pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, p_linear.data(), od.colorspace) == PT_OK;
-                    if (ok) printf("wrote %s.exr\n", name.c_str());
-                }
-                if (!ok) fprintf(stderr, "--path-passes: %s\n", pt_last_error());
-                return ok;
-            };
-            if (o.path_passes && !write_passes(base, group_films)) { rc = 1; break; }
-            // --relamp-groups: every group's bins in the units of the EXR payload, and the re-lamped picture — the colour-matching development of the group bins by
-            // the re-lamp matrix, where the render left them on the device — through this setting's film output (buffers of its own)
-            if (o.relamp_groups) {
-                const size_t np = (size_t)rd.width * rd.height, plane = (size_t)o.relamp_bins * np;
-                const pt_spectral_desc sd = {o.relamp_bins, {0u, 0u, 0u}};
-                std::vector<float> centres(o.relamp_bins), scaled(plane), matrix((size_t)3 * gd.group_count * o.relamp_bins), planes(3 * np), packed(4 * np), r_linear(3 * np);
-                std::vector<uint8_t> r_rgba(4 * np);
-                bool ok = pt_spectral_bin_centres(&rd, &sd, centres.data()) == PT_OK;
-                for (uint32_t g = 0; ok && g < gd.group_count; ++g) {
-                    const std::string name = base + "_light" + std::to_string(g) + "_spectral";
-                    for (size_t k = 0; k < plane; ++k) scaled[k] = group_bins[plane * g + k] * od.factor;
-                    ok = pt_write_exr_spectral((name + ".exr").c_str(), rd.width, rd.height, o.relamp_bins, centres.data(), scaled.data(), nullptr, od.colorspace) == PT_OK;
-                    if (ok) printf("wrote %s.exr (%u bins)\n", name.c_str(), o.relamp_bins);
-                }
-                const int32_t cie[3] = {PT_RESPONSE_CIE_X, PT_RESPONSE_CIE_Y, PT_RESPONSE_CIE_Z};
-                ok = ok && pt_light_groups_relamp_matrix(&rd, &sd, relamp_curves.data(), (uint32_t)relamp_curves.size(), relamp_data.data(), (uint32_t)relamp_data.size(), 3, cie,
-                                                         PT_SPECTRAL_NO_FILTER, o.develop_subsamples, gd.group_count, relamp_old.data(), relamp_new.data(),
-                                                         o.has_relamp_gains ? o.relamp_gains.data() : nullptr, matrix.data()) == PT_OK &&
-                     pt_light_groups_relamp_resident(scene, 3, matrix.data(), planes.data()) == PT_OK;
-                if (ok) {
-                    for (size_t p = 0; p < np; ++p) { packed[4 * p] = planes[p]; packed[4 * p + 1] = planes[np + p]; packed[4 * p + 2] = planes[2 * np + p]; packed[4 * p + 3] = 0.0f; }
-                    const std::string name = base + "_relamped";
-                    ok = pt_output_film(&od, packed.data(), r_rgba.data(), r_linear.data()) == PT_OK &&
-                         pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, r_linear.data(), od.colorspace) == PT_OK &&
-                         pt_write_png((name + ".png").c_str(), rd.width, rd.height, r_rgba.data(), od.colorspace) == PT_OK;
-                    if (ok) printf("wrote %s.exr and %s.png (re-lamped from %u light groups of %u bins)\n", name.c_str(), name.c_str(), gd.group_count, o.relamp_bins);
-                }
-                if (!ok) { fprintf(stderr, "--relamp-groups: %s\n", pt_last_error()); rc = 1; break; }
-            }
-            // the bins in the units of the EXR payload: the same factor, applied here in place, one multiply per value
-            const uint32_t file_bins = o.spectral_bins ? o.spectral_bins : o.denoise_bins;
-            const auto write_spectral = [&](const std::string& name, std::vector<float>& scaled) {
-                const pt_spectral_desc sd = {file_bins, {0u, 0u, 0u}};
-                std::vector<float> centres(file_bins);
-                for (float& v : scaled) v *= od.factor;
-                if (pt_spectral_bin_centres(&rd, &sd, centres.data()) != PT_OK ||
-                    pt_write_exr_spectral((name + ".exr").c_str(), rd.width, rd.height, file_bins, centres.data(), scaled.data(), linear.data(), od.colorspace) != PT_OK) {
-                    fprintf(stderr, "%s: %s\n", o.spectral_bins ? "--spectral-bins" : "--denoise-spectral-bins", pt_last_error());
-                    return false;
-                }
-                printf("wrote %s.exr (%u bins)\n", name.c_str(), file_bins);
-                return true;
-            };
-            if (o.denoise_bins) {   // (a copy: the filter below takes the bins as rendered)
-                std::vector<float> noisy(spectral);
-                if (!write_spectral(base + "_spectral", noisy)) { rc = 1; break; }
-            } else if (!spectral.empty() && !write_spectral(base + "_spectral", spectral)) { rc = 1; break; }
-            // --develop: three planes from the bins — the scene's resident ones (bins == nullptr; `denoised`: the resident denoised ones) or a host array as rendered
-            // or filtered, before the factor —, packed as an XYZW film with W = 0, through this setting's film output (buffers of its own: `linear` still serves
-            // the spectral files)
-            const auto develop = [&](const std::string& name, const float* bins, bool denoised = false) {
-                const pt_spectral_desc sd = {file_bins, {0u, 0u, 0u}};
-                const size_t np = (size_t)rd.width * rd.height;
-                std::vector<float> matrix((size_t)3 * file_bins), planes(3 * np), packed(4 * np), dev_linear(3 * np);
-                std::vector<uint8_t> dev_rgba(4 * np);
-                pt_status st = pt_spectral_response_matrix(&rd, &sd, develop_curves.data(), (uint32_t)develop_curves.size(), develop_data.data(), (uint32_t)develop_data.size(),
-                                                           3, develop_responses, develop_filter, o.develop_subsamples, matrix.data());
-                if (st == PT_OK) st = bins       ? pt_spectral_project(rd.width, rd.height, file_bins, 3, matrix.data(), bins, planes.data())
-                                      : denoised ? pt_spectral_project_resident_denoised(scene, 3, matrix.data(), planes.data())
-                                                 : pt_spectral_project_resident(scene, 3, matrix.data(), planes.data());
-                if (st != PT_OK) { fprintf(stderr, "--develop: %s\n", pt_last_error()); return false; }
-                for (size_t p = 0; p < np; ++p) { packed[4 * p] = planes[p]; packed[4 * p + 1] = planes[np + p]; packed[4 * p + 2] = planes[2 * np + p]; packed[4 * p + 3] = 0.0f; }
-                if (pt_output_film(&od, packed.data(), dev_rgba.data(), dev_linear.data()) != PT_OK ||
-                    pt_write_exr((name + ".exr").c_str(), rd.width, rd.height, dev_linear.data(), od.colorspace) != PT_OK ||
-                    pt_write_png((name + ".png").c_str(), rd.width, rd.height, dev_rgba.data(), od.colorspace) != PT_OK) {
-                    fprintf(stderr, "--develop: %s\n", pt_last_error());
-                    return false;
-                }
-                printf("wrote %s.exr and %s.png (developed from %u bins)\n", name.c_str(), name.c_str(), file_bins);
-                return true;
-            };
-            // (a node render leaves its bins resident too, with either flag: they are developed on the devices)
-            if (o.develop && !develop(base + "_developed", o.denoise_bins && !o.spectral_multi && !o.resident ? spectral.data() : nullptr)) { rc = 1; break; }
-            if (o.denoise && o.assemble) {
-                // the node render left its pieces on the devices: one film on the scene's device from them, unless the mask came down to that device alone and
-                // the render left the film resident itself
-                struct pt_resident_info now;
-                pt_status ast = pt_resident_info(scene, &now);
-                if (ast == PT_OK && !(now.parts & PT_RESIDENT_FILM)) ast = pt_resident_assemble(scene, 0u);
-                if (ast != PT_OK) { fprintf(stderr, "--denoise-assemble: %s\n", pt_last_error()); rc = 1; break; }
-            }
-            // (a node group render without --denoise-assemble left no film one device can filter, unless the mask came down to the scene's device alone)
-            bool groups_on_host = false;
-            if (o.denoise && o.denoise_groups && o.group_multi && !o.assemble) {
-                struct pt_resident_info now;
-                if (pt_resident_info(scene, &now) != PT_OK) { fprintf(stderr, "--light-group-devices: %s\n", pt_last_error()); rc = 1; break; }
-                groups_on_host = !(now.parts & PT_RESIDENT_FILM);
-            }
-            if (o.denoise && o.denoise_groups && groups_on_host) {
-                // guides and the joint filter over host arrays, on the first device of the mask: the files of the resident route, byte for byte
-                const size_t np = (size_t)rd.width * rd.height;
-                std::vector<float> guides(4 * np), albedo(o.demodulate ? 4 * np : 0), clean(4 * np), clean_groups(4 * np * gd.group_count);
-                pt_denoise_desc dd;
-                memset(&dd, 0, sizeof(dd));
-                dd.width = rd.width; dd.height = rd.height;
-                if (o.group_device_mask) while (!((o.group_device_mask >> dd.device) & 1u)) ++dd.device;
-                pt_guide_chain_desc cd;
-                memset(&cd, 0, sizeof(cd));
-                cd.max_chain = o.max_chain; cd.alpha_max = o.alpha_max;
-                pt_status dst = o.chain ? pt_render_guides_chain(scene, &rd, o.guide_samples, &cd, guides.data(), o.demodulate ? albedo.data() : nullptr)
-                                : o.demodulate ? pt_render_guides_albedo(scene, &rd, o.guide_samples, guides.data(), albedo.data())
-                                               : pt_render_guides(scene, &rd, o.guide_samples, guides.data());
-                if (dst == PT_OK) dst = pt_denoise_light_groups(&dd, gd.group_count, film.data(), counts.data(), stats.data(), guides.data(), o.demodulate ? albedo.data() : nullptr,
-                                                                group_films.data(), clean.data(), nullptr, clean_groups.data());
-                if (dst != PT_OK) { fprintf(stderr, "--denoise-light-groups: %s\n", pt_last_error()); rc = 1; break; }
-                if (pt_output_film(&od, clean.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }
-                const std::string dbase = base + "_denoised";
-                if (pt_write_exr((dbase + ".exr").c_str(), rd.width, rd.height, linear.data(), od.colorspace) != PT_OK ||
-                    pt_write_png((dbase + ".png").c_str(), rd.width, rd.height, rgba.data(), od.colorspace) != PT_OK) {
-                    fprintf(stderr, "failed to write files: %s\n", pt_last_error()); rc = 1; break;
-                }
-                if (o.write_film && !write_npy(dbase + ".npy", clean.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", dbase.c_str()); rc = 1; break; }
-                printf("wrote %s.exr and %s.png\n", dbase.c_str(), dbase.c_str());
-                if (!write_groups(dbase, clean_groups, true, true)) { rc = 1; break; }
-            } else if (o.denoise && (o.denoise_groups || o.denoise_passes)) {
-                // the render left the film, its statistics and the group films on the device, paired: the guides stay there too, and the joint filter runs on all of
-                // it (with or without --denoise-resident: this is the only route, and its files are those of either)
-                const size_t np = (size_t)rd.width * rd.height;
-                // (--denoise-path-passes: the pass films are the resident group films of this route)
-                const char* const flag = o.denoise_passes ? "--denoise-path-passes" : "--denoise-light-groups";
-                std::vector<float> clean(4 * np), clean_groups(4 * np * (o.denoise_passes ? (uint32_t)PT_PATH_PASSES : gd.group_count));
-                pt_guide_chain_desc cd;
-                memset(&cd, 0, sizeof(cd));
-                cd.max_chain = o.max_chain; cd.alpha_max = o.alpha_max;
-                pt_resident_denoise_desc dd;
-                memset(&dd, 0, sizeof(dd));
-                pt_status dst = pt_resident_guides(scene, &rd, o.guide_samples, o.chain ? &cd : nullptr, o.demodulate ? PT_RESIDENT_ALBEDO : 0u);
-                if (dst == PT_OK) dst = pt_denoise_light_groups_resident(scene, &dd, clean.data(), nullptr, clean_groups.data());
-                if (dst != PT_OK) { fprintf(stderr, "%s: %s\n", flag, pt_last_error()); rc = 1; break; }
-                if (pt_output_film(&od, clean.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }
-                const std::string dbase = base + "_denoised";
-                if (pt_write_exr((dbase + ".exr").c_str(), rd.width, rd.height, linear.data(), od.colorspace) != PT_OK ||
-                    pt_write_png((dbase + ".png").c_str(), rd.width, rd.height, rgba.data(), od.colorspace) != PT_OK) {
-                    fprintf(stderr, "failed to write files: %s\n", pt_last_error()); rc = 1; break;
-                }
-                if (o.write_film && !write_npy(dbase + ".npy", clean.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", dbase.c_str()); rc = 1; break; }
-                printf("wrote %s.exr and %s.png\n", dbase.c_str(), dbase.c_str());
-                if (!(o.denoise_passes ? write_passes(dbase, clean_groups) : write_groups(dbase, clean_groups, true))) { rc = 1; break; }
-            } else if (o.denoise && (o.resident || o.assemble)) {
-                // the render left film, counts, statistics and bins on the device: the guides stay there too, and the filter runs on all of it
-                std::vector<float> clean((size_t)rd.width * rd.height * 4), clean_spectral(spectral.size());
-                pt_guide_chain_desc cd;
-                memset(&cd, 0, sizeof(cd));
-                cd.max_chain = o.max_chain; cd.alpha_max = o.alpha_max;
-                pt_resident_denoise_desc dd;
-                memset(&dd, 0, sizeof(dd));
-                const uint32_t parts = o.demodulate_bins ? (PT_RESIDENT_ALBEDO | PT_RESIDENT_BIN_ALBEDO) : o.demodulate ? PT_RESIDENT_ALBEDO : 0u;
-                pt_status dst = pt_resident_guides(scene, &rd, o.guide_samples, o.chain ? &cd : nullptr, parts);
-                if (dst == PT_OK) dst = pt_denoise_resident(scene, &dd, clean.data(), nullptr, o.denoise_bins ? clean_spectral.data() : nullptr);
-                if (dst != PT_OK) { fprintf(stderr, "%s: %s\n", o.assemble ? "--denoise-assemble" : "--denoise-resident", pt_last_error()); rc = 1; break; }
-                if (pt_output_film(&od, clean.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }
-                const std::string dbase = base + "_denoised";
-                if (pt_write_exr((dbase + ".exr").c_str(), rd.width, rd.height, linear.data(), od.colorspace) != PT_OK ||
-                    pt_write_png((dbase + ".png").c_str(), rd.width, rd.height, rgba.data(), od.colorspace) != PT_OK) {
-                    fprintf(stderr, "failed to write files: %s\n", pt_last_error()); rc = 1; break;
-                }
-                if (o.write_film && !write_npy(dbase + ".npy", clean.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", dbase.c_str()); rc = 1; break; }
-                printf("wrote %s.exr and %s.png\n", dbase.c_str(), dbase.c_str());
-                if (o.develop && o.denoise_bins && !develop(dbase + "_developed", nullptr, true)) { rc = 1; break; }
-                if (o.denoise_bins && !write_spectral(dbase + "_spectral", clean_spectral)) { rc = 1; break; }
-            } else if (o.denoise) {
-                std::vector<float> guides((size_t)rd.width * rd.height * 4), clean((size_t)rd.width * rd.height * 4);
-                pt_denoise_desc dd;
-                memset(&dd, 0, sizeof(dd));
-                dd.width = rd.width; dd.height = rd.height;
-                if (o.multi && o.device_mask) while (!((o.device_mask >> dd.device) & 1u)) ++dd.device;   // (the first device of the mask: where the gather left the film)
-                if (o.spectral_multi && o.spectral_device_mask) while (!((o.spectral_device_mask >> dd.device) & 1u)) ++dd.device;
-                std::vector<float> albedo(o.demodulate || o.demodulate_bins ? (size_t)rd.width * rd.height * 4 : 0);
-                std::vector<float> bin_albedo(o.demodulate_bins ? spectral.size() : 0);
-                pt_guide_chain_desc cd;
-                memset(&cd, 0, sizeof(cd));
-                cd.max_chain = o.max_chain; cd.alpha_max = o.alpha_max;
-                const pt_status gst = o.demodulate_bins ? pt_render_guides_bin_albedo(scene, &rd, o.guide_samples, o.chain ? &cd : nullptr, o.denoise_bins, guides.data(),
-                                                                                      albedo.data(), bin_albedo.data())
-                                      : o.chain ? pt_render_guides_chain(scene, &rd, o.guide_samples, &cd, guides.data(), o.demodulate ? albedo.data() : nullptr)
-                                      : o.demodulate ? pt_render_guides_albedo(scene, &rd, o.guide_samples, guides.data(), albedo.data())
-                                                     : pt_render_guides(scene, &rd, o.guide_samples, guides.data());
-                std::vector<float> clean_spectral(spectral.size());
-                const pt_status dst = gst != PT_OK ? gst
-                                      : o.demodulate_bins ? pt_denoise_spectral_albedo(&dd, o.denoise_bins, film.data(), counts.data(), stats.data(), guides.data(), albedo.data(),
-                                                                                       spectral.data(), bin_albedo.data(), clean.data(), clean_spectral.data(), nullptr)
-                                      : o.denoise_bins ? pt_denoise_spectral(&dd, o.denoise_bins, film.data(), counts.data(), stats.data(), guides.data(), spectral.data(), clean.data(),
-                                                                             clean_spectral.data(), nullptr)
-                                                       : pt_denoise_film_albedo(&dd, film.data(), counts.data(), stats.data(), guides.data(), o.demodulate ? albedo.data() : nullptr,
-                                                                                clean.data(), nullptr);
-                if (dst != PT_OK) { fprintf(stderr, "--denoise: %s\n", pt_last_error()); rc = 1; break; }
-                if (pt_output_film(&od, clean.data(), rgba.data(), linear.data()) != PT_OK) { fprintf(stderr, "pt_output_film: %s\n", pt_last_error()); rc = 1; break; }
-                const std::string dbase = base + "_denoised";
-                if (pt_write_exr((dbase + ".exr").c_str(), rd.width, rd.height, linear.data(), od.colorspace) != PT_OK ||
-                    pt_write_png((dbase + ".png").c_str(), rd.width, rd.height, rgba.data(), od.colorspace) != PT_OK) {
-                    fprintf(stderr, "failed to write files: %s\n", pt_last_error()); rc = 1; break;
-                }
-                if (o.write_film && !write_npy(dbase + ".npy", clean.data(), rd.height, rd.width)) { fprintf(stderr, "failed to write %s.npy\n", dbase.c_str()); rc = 1; break; }
-                printf("wrote %s.exr and %s.png\n", dbase.c_str(), dbase.c_str());
-                if (o.develop && o.denoise_bins && !develop(dbase + "_developed", clean_spectral.data())) { rc = 1; break; }   // (before the factor goes into the bins)
-                if (o.denoise_bins && !write_spectral(dbase + "_spectral", clean_spectral)) { rc = 1; break; }   // (`linear` now holds the denoised film's R, G, B)
-            }
-        }
-        if (scene) pt_scene_destroy(scene);
-        if (rc == 0) printf("render done\n");
-    }
-    pt_scene_file_free(scene_file);
-    pt_config_free(config);
-    return rc;
+    return o.dry_run || render_settings(r) ? 0 : 1;
 }

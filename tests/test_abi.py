@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+from util import ptcli
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -114,7 +116,7 @@ def test_command_line_renderer_dry_run(pkg):
     """ptcli (src/bin/main.rs): parses config + scene and stops before rendering with --dry-run; fails loudly without a GPU
     otherwise (no CPU fallback)."""
     import subprocess
-    exe = os.path.join(os.path.dirname(pkg.LIBRARY_PATH), "ptcli")
+    exe = ptcli(pkg)
     if not os.path.exists(exe):
         pytest.fail("ptcli not built: run python -c 'import __graft_entry__ as g; g.build()'")
     import tempfile

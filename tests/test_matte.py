@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import emulation
-from util import PT_ERR_INVALID_ARGUMENT
+from util import PT_ERR_INVALID_ARGUMENT, ptcli
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -435,7 +435,7 @@ def test_engine_refuses_bad_matte_arguments_before_it_looks_for_a_device(pkg):
 
 
 def test_ptcli_refuses_mattes_over_a_device_mask(pkg, tmp_path):
-    exe = os.path.join(pkg.PACKAGE_DIR, "csrc", "ptcli")
+    exe = ptcli(pkg)
     for args, words in ((["--mattes", "instance", "--devices", "3"], ("--mattes", "--devices")),
                         (["--mattes", "material", "--spectral-bins", "4", "--spectral-devices", "1"], ("--mattes", "--spectral-devices")),
                         (["--mattes", "instance", "--light-groups", "instance", "--light-group-devices", "1"], ("--mattes", "--light-group-devices")),
@@ -558,7 +558,7 @@ def test_gpu_rank_zero_of_a_sky_pixel_is_the_sky(engine, pkg):
 def test_gpu_ptcli_mattes(engine, pkg, tmp_path, kind, layer):
     """ptcli --mattes writes <name>_crypto.exr with the API's ranks under the names of the scene file; every other file is byte for byte what a run without
     the flag writes."""
-    exe = os.path.join(pkg.PACKAGE_DIR, "csrc", "ptcli")
+    exe = ptcli(pkg)
     text = open(os.path.join(pkg.PACKAGE_DIR, "data", "config_cornell_c1.toml")).read()
     text = text.replace("min_samples = 16", "min_samples = 10").replace("width = 256", "width = 40").replace("height = 256", "height = 27")
     assert "min_samples = 10" in text and "width = 40" in text and "height = 27" in text

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import parity_suite as ps
+from util import ptcli
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "rust-pathtracer_amd", "csrc")
@@ -480,7 +481,7 @@ def test_compare_tool_on_rendered_files(sfmod, pkg, engine, tmp_path):
     outs = []
     for seed in ("3", "4"):
         out = tmp_path / ("out" + seed)
-        r = subprocess.run([os.path.join(exe_dir, "ptcli"), "--root", pkg.PACKAGE_DIR, "--config", "data/config_two_passes.toml", "--output-dir", str(out), "--seed", seed],
+        r = subprocess.run([ptcli(pkg), "--root", pkg.PACKAGE_DIR, "--config", "data/config_two_passes.toml", "--output-dir", str(out), "--seed", seed],
                            capture_output=True, text=True, cwd=str(tmp_path))
         assert r.returncode == 0, r.stderr
         outs.append(str(out / "beauty.exr"))
@@ -504,7 +505,7 @@ def test_command_line_render_matches_the_library(sfmod, pkg, engine, tmp_path):
     """ptcli end to end on the GPU: config + scene TOML -> film, EXR, PNG; the raw film equals the one rendered through
     the Python front end with the same settings, bit for bit."""
     import subprocess
-    exe = os.path.join(os.path.join(pkg.PACKAGE_DIR, "csrc"), "ptcli")
+    exe = ptcli(pkg)
     out = tmp_path / "out"
     r = subprocess.run([exe, "--root", pkg.PACKAGE_DIR, "--config", "data/config_two_passes.toml", "--output-dir", str(out), "--seed", "5", "--write-film"],
                        capture_output=True, text=True, cwd=str(tmp_path))

@@ -2687,6 +2687,7 @@ pt_status pt_debug_numerics(int which, size_t n, const float* x, const float* y,
 
 // Not part of pt_api.h: size of the scene blob and whether kernels read it from LDS (reported by bench.py).
 uint32_t pt_debug_scene_info(pt_scene* sc, int what) {
+    if (what >= 1000000) return (size_t)(what - 1000000) < sc->host.blob.size() ? sc->host.blob[(size_t)(what - 1000000)] : 0u;   // a word of the blob
     switch (what) { case 0: return sc->blob_words * 4; case 1: return (uint32_t)sc->lds_mode; case 2: return sc->host.light_count; case 3: return (uint32_t)sc->num_cus;
                     case 4: return sc->host.blob[PT_HDR_SWEEP_OFF] != 0 && !(sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_NO_SWEEP) ? 1u : 0u;
                     case 7: return sc->host.blob[PT_HDR_CORE_WORDS] * 4;

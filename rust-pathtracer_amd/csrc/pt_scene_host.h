@@ -17,7 +17,6 @@ struct HostScene {
     std::vector<float> tex;       // texture texels
     std::vector<pt_camera> cameras;
     std::vector<uint32_t> curve_offsets;
-    std::vector<int> mesh_has_light;
     uint32_t light_count = 0, material_count = 0, curve_count = 0;
 };
 

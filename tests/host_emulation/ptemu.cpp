@@ -79,6 +79,14 @@ uint32_t ptemu_debug_scene_info(pt_scene* sc, int what) {
     }
     return 0;
 }
+// Everything a kernel reads of a scene, for tests/test_scene_blob.py: which = 0 the blob, 1 the texels and importance-map tables as float bits.  Returns the
+// word count and copies min(count, capacity) words.  (Not a row of api.ENTRIES: loaded with plain ctypes.)
+size_t ptemu_debug_scene_words(pt_scene* sc, int which, uint32_t* out, size_t capacity) {
+    const size_t count = which == 0 ? sc->host.blob.size() : sc->host.tex.size();
+    const void* from = which == 0 ? (const void*)sc->host.blob.data() : (const void*)sc->host.tex.data();
+    if (out && capacity) std::memcpy(out, from, 4 * (count < capacity ? count : capacity));
+    return count;
+}
 
 // the colour-matching fit as the kernels evaluate it (contract = 0) and as the numeric contract defines it (1), for n wavelengths in angstrom: 3 floats each
 void ptemu_xyz_bar(size_t n, const float* angstrom, int contract, float* out) {

@@ -65,7 +65,7 @@ pt_status pt_light_groups_mix_resident(pt_scene* scene, const float* matrices, f
  *
  * The pass films are left on the scene's device as ITS RESIDENT GROUP FILMS with group_count 8: pt_light_groups_resident, pt_light_groups_mix_resident and
  * (after the adaptive entry of pt_light_groups_denoise.h) pt_denoise_light_groups_resident follow a pass render as they follow a group render.
- * Out of scope: a device mask, spectral bins per pass, hero wavelengths, the medium-aware walk, a user-defined path-expression language.
+ * Out of scope: a device mask, spectral bins per pass, hero wavelengths, the medium-aware walk.
  * (Declared here, not in a header of its own, because the pass films ARE group films.  The return type stands on a line of its own: the light-group tests
  * pin the list of this header's `pt_status pt_...(` lines to the light-group entries above.) */
 #define PT_PATH_PASSES 8
@@ -88,6 +88,62 @@ typedef struct pt_path_passes_desc {
  * sample range: PT_ERR_UNSUPPORTED).  pass_films: PT_PATH_PASSES*width*height*4 f32 in the layout of group films, or NULL when only the resident copy is wanted. */
 pt_status
 pt_render_path_passes(pt_scene* scene, const pt_render_desc* desc, const pt_path_passes_desc* passes, float* film_xyzw, float* pass_films, pt_profile* profile);
+
+/* ---- Path expressions: films for user-written light-path patterns ("Path expressions").  An expression describes a path from the camera
+ * to an emitter in the event vocabulary of the path passes above:
+ *
+ *   C              the camera; every alternative starts with it
+ *   D R T  .       a diffuse, a reflection, a transmission scattering event (light-tagged vertices scatter too); any of the three
+ *   [DR] [^T]      a class of events
+ *   ( ) | * + ?    grouping, alternation, repetition over events
+ *   L  L0..L7      the terminal "a surface emitter" / "a surface emitter of that light group"
+ *   E  E0..E7      the terminal "the environment" / "the environment, if it belongs to that group"
+ *   [L2E2]         a class of terminals
+ *   CD+L|CR+E      a top-level | joins complete alternatives; every alternative ends in exactly one terminal.  White space is ignored.
+ *
+ * Expression e's film is the sum over exactly the paths e matches, made from their energies as pt_render's film is made from all of them, whatever other
+ * expressions are compiled beside it: expressions may overlap.  The eight path passes are CL, CE, CD[LE], CD.+[LE], CR[LE], CR.+[LE], CT[LE], CT.+[LE]; light
+ * group g is C.*[LgEg]; C.*[LE] is the film.
+ *
+ * The program is the union of the expressions' automata, determinised over the three event symbols (and minimised).  16 bytes per state:
+ *   word 0       the successors: bits 0..5 behind D, bits 6..11 behind R, bits 12..17 behind T
+ *   words 1..3   nine 8-bit output masks, one per terminal symbol: symbol s in byte s % 4 of word 1 + s / 4.  Symbols 0..7: a surface emitter of group g;
+ *                symbol 8: the environment.  Bit e of a mask: expression e accepts a path that ends with this terminal here.
+ * E<g> with g != environment_group contributes no bit; L without a digit sets its bit in all eight surface-emitter symbols.  A state from which nothing is
+ * accepted is an ordinary state with zero masks.  `start` is the state behind C: the state in front of the camera ray's first vertex.
+ * The expression films are left as the scene's resident group films with group_count = outputs, as pass films are.
+ * Out of scope: a device mask, spectral bins per expression, hero wavelengths, the medium-aware walk, per-vertex object or material labels. */
+#define PT_PATH_EXPRS_MAX 8
+#define PT_PATH_EXPR_STATES_MAX 64
+#define PT_PATH_EXPR_TERMINALS 9
+#define PT_PATH_EXPR_ENVIRONMENT 8    /* the terminal symbol of the environment */
+
+typedef struct pt_path_expr_program {
+    uint32_t outputs;                 /* K: 1 .. PT_PATH_EXPRS_MAX */
+    uint32_t states;                  /* 1 .. PT_PATH_EXPR_STATES_MAX */
+    uint32_t start;                   /* < states */
+    uint32_t environment_group;       /* < PT_LIGHT_GROUPS_MAX */
+    uint32_t table[PT_PATH_EXPR_STATES_MAX][4];   /* the states' entries; those from `states` on are 0 */
+} pt_path_expr_program;
+
+/* Host only.  exprs: n expressions, 1 <= n <= PT_PATH_EXPRS_MAX, expression e tagged with bit e.  err (may be NULL): err_len bytes for the message of a
+ * failure, always terminated.  A syntax error is PT_ERR_INVALID_ARGUMENT, reported as "expression <e>, column <c>: ..." with c counted from 1 in the text as
+ * given; more than PT_PATH_EXPR_STATES_MAX states is PT_ERR_UNSUPPORTED with a message that names the count. */
+pt_status
+pt_path_expr_compile(const char* const* exprs, uint32_t n, uint32_t environment_group, pt_path_expr_program* program, char* err, size_t err_len);
+
+/* Host only.  Runs the program over a written-out path — C, events of D R T, one terminal L<g> (L alone: L0) or E — and gives the output mask: bit e set where
+ * expression e matches the path.  A malformed path or program is PT_ERR_INVALID_ARGUMENT. */
+pt_status
+pt_path_expr_match(const pt_path_expr_program* program, const char* path, uint32_t* mask);
+
+/* pt_render_path_passes with the program's expressions where the eight classes stand.  instance_group: one light group id < PT_LIGHT_GROUPS_MAX per instance,
+ * n_instances the scene's count; or NULL with n_instances 0: every instance is in group 0.  expr_films: outputs*width*height*4 f32 in the layout of group
+ * films, or NULL.  Refused is what pt_render_path_passes refuses, and a malformed program: outputs outside 1..8, states outside 1..64, a successor or the start
+ * not below states, a mask bit not below outputs (PT_ERR_INVALID_ARGUMENT). */
+pt_status
+pt_render_path_exprs(pt_scene* scene, const pt_render_desc* desc, const pt_path_expr_program* program, const uint8_t* instance_group, uint32_t n_instances,
+                     float* film_xyzw, float* expr_films, pt_profile* profile);
 
 #ifdef __cplusplus
 }

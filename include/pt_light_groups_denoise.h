@@ -61,6 +61,14 @@ pt_status
 pt_render_adaptive_path_passes(pt_scene* scene, const pt_render_desc* desc, const pt_adaptive_desc* adaptive, const pt_path_passes_desc* passes, float* film_xyzw,
                                uint32_t* sample_counts, double* stats, float* pass_films, pt_profile* profile);
 
+/* pt_render_path_exprs (pt_light_groups.h, "Path expressions") under pt_render_adaptive's stop rule, as pt_render_adaptive_path_passes is
+ * pt_render_path_passes': film, counts, statistics and rounds are pt_render_adaptive's bit for bit, and expression e's film at pixel p is pt_render_path_exprs' at
+ * spp = sample_counts[p].  On success the scene holds the resident FILM and the expression films as its group films, paired. */
+pt_status
+pt_render_adaptive_path_exprs(pt_scene* scene, const pt_render_desc* desc, const pt_adaptive_desc* adaptive, const pt_path_expr_program* program,
+                              const uint8_t* instance_group, uint32_t n_instances, float* film_xyzw, uint32_t* sample_counts, double* stats, float* expr_films,
+                              pt_profile* profile);
+
 #ifdef __cplusplus
 }
 #endif

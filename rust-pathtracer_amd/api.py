@@ -143,6 +143,21 @@ PATH_PASS_NAMES = ("emission", "background", "diffuse_direct", "diffuse_indirect
                    "transmission_indirect")
 
 
+# PT_PATH_EXPRS_MAX, PT_PATH_EXPR_STATES_MAX, PT_PATH_EXPR_TERMINALS, PT_PATH_EXPR_ENVIRONMENT (include/pt_light_groups.h, "Path expressions")
+PATH_EXPRS_MAX, PATH_EXPR_STATES_MAX, PATH_EXPR_TERMINALS, PATH_EXPR_ENVIRONMENT = 8, 64, 9, 8
+
+
+class PathExprProgram(C.Structure):
+    """pt_path_expr_program (include/pt_light_groups.h): K, the states, the start, the environment's group, 16 bytes per state — word 0 the successors behind D, R
+    and T, 6 bits each; words 1..3 nine 8-bit output masks, terminal symbol s in byte s % 4 of word 1 + s // 4."""
+    _fields_ = [("outputs", C.c_uint32), ("states", C.c_uint32), ("start", C.c_uint32), ("environment_group", C.c_uint32),
+                ("table", C.c_uint32 * 4 * PATH_EXPR_STATES_MAX)]
+
+
+# the eight path passes written as path expressions, in the order of PATH_PASS_NAMES
+PATH_PASS_EXPRS = ("CL", "CE", "CD[LE]", "CD.+[LE]", "CR[LE]", "CR.+[LE]", "CT[LE]", "CT.+[LE]")
+
+
 def light_group_gains(gains):
     """G scalars as the G scaled identities of a mix, float32 [G,3,3]: group g's film times gains[g]."""
     gains = np.asarray(gains, np.float32).reshape(-1)
@@ -296,6 +311,7 @@ _vp, _str, _sz, _u32, _i32, _u64 = C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint3
 _f32s, _u32s, _f64s, _u8s, _i32s = _P(C.c_float), _P(C.c_uint32), _P(C.c_double), _P(C.c_uint8), _P(C.c_int32)
 _RD, _AD, _SD, _GD, _DD, _RDD, _CHAIN, _PROF, _PD = (_P(t) for t in (RenderDesc, AdaptiveDesc, SpectralDesc, LightGroupsDesc, DenoiseDesc, ResidentDenoiseDesc,
                                                                      GuideChainDesc, Profile, PathPassesDesc))
+_PX = _P(PathExprProgram)
 _DENOISE, _ALBEDO, _BIN_ALBEDO, _PROJECT = "denoise_last_error", "denoise_albedo_last_error", "denoise_spectral_albedo_last_error", "spectral_project_last_error"
 _GROUPS, _GROUP_BINS, _RESIDENT = "light_groups_last_error", "light_groups_spectral_last_error", "resident_last_error"
 
@@ -371,6 +387,9 @@ BINDINGS = (
         Entry("light_groups_resident", [_vp, _u32s, _u32s, _u32s], channel=_GROUPS),
         Entry("light_groups_mix_resident", [_vp, _f32s, _f32s], channel=_GROUPS),
         Entry("render_path_passes", [_vp, _RD, _PD, _f32s, _f32s, _PROF], channel=_GROUPS),
+        Entry("path_expr_compile", [_P(_str), _u32, _u32, _PX, _str, _sz]),
+        Entry("path_expr_match", [_PX, _str, _u32s]),
+        Entry("render_path_exprs", [_vp, _RD, _PX, _u8s, _u32, _f32s, _f32s, _PROF], channel=_GROUPS),
         Entry(_GROUPS, [], _str))),
     ("pt_light_groups_spectral.h", (
         Entry("render_light_groups_spectral", [_vp, _RD, _GD, _SD, _f32s, _f32s, _f32s, _f32s, _PROF], channel=_GROUP_BINS),
@@ -386,6 +405,7 @@ BINDINGS = (
         Entry("light_groups_denoised_resident", [_vp, _u32s, _u32s, _u32s]),
         Entry("light_groups_mix_resident_denoised", [_vp, _f32s, _f32s], channel=_GROUPS),
         Entry("render_adaptive_path_passes", [_vp, _RD, _AD, _PD, _f32s, _u32s, _f64s, _f32s, _PROF]),
+        Entry("render_adaptive_path_exprs", [_vp, _RD, _AD, _PX, _u8s, _u32, _f32s, _u32s, _f64s, _f32s, _PROF]),
         Entry("adaptive_light_groups_last_error", [], _str),
         Entry("denoise_light_groups_last_error", [], _str))),
     ("pt_light_groups_multi.h", (
@@ -492,6 +512,26 @@ class Library:
 
     def device_info(self):
         return self._device_info().decode() if self._device_info else "cpu oracle"
+
+    def path_expr_compile(self, exprs, environment_group=0):
+        """pt_path_expr_compile (host only): the PathExprProgram of one expression or a sequence of up to PATH_EXPRS_MAX, expression e tagged with bit e.  A
+        syntax error (PT_ERR_INVALID_ARGUMENT, "expression <e>, column <c>: ...") and more than PATH_EXPR_STATES_MAX states (PT_ERR_UNSUPPORTED) raise PtError
+        with the compiler's own message."""
+        exprs = [exprs] if isinstance(exprs, str) else list(exprs)
+        texts = (C.c_char_p * max(len(exprs), 1))(*[e.encode() for e in exprs])
+        program, err = PathExprProgram(), C.create_string_buffer(512)
+        status = self.entry("path_expr_compile")(texts, len(exprs), int(environment_group), C.byref(program), err, len(err))
+        if status != PT_OK:
+            raise PtError(status, err.value.decode())
+        return program
+
+    def path_expr_match(self, program, path):
+        """pt_path_expr_match (host only): the mask of the program's expressions that match the written-out path, such as "CDTL3" or "CRE"."""
+        mask = C.c_uint32()
+        status = self.entry("path_expr_match")(C.byref(program), path.encode(), C.byref(mask))
+        if status != PT_OK:
+            raise PtError(status, "path_expr_match: a malformed path %r or program" % (path,))
+        return mask.value
 
     def create_scene(self, builder, tuning=None):
         """`tuning`: a Tuning (pt_scene_create_tuned); None = pt_scene_create, which reads the PT_AMD_* environment once."""
@@ -783,15 +823,16 @@ class Scene:
         """Library.call of an entry that takes the scene first."""
         self.library.call(name, self.handle, *args)
 
-    def _render_call(self, name, rd, adaptive=None, groups=None, bins=None, device_mask=None, stats=False, read_groups=True, read_bins=True, passes=False):
+    def _render_call(self, name, rd, adaptive=None, groups=None, bins=None, device_mask=None, stats=False, read_groups=True, read_bins=True, passes=False, exprs=None):
         """The one render call behind the render* methods: the entry `name` with the arguments it takes, in the order all of them share — rd,
         adaptive desc, groups desc, spectral desc, device mask, film, counts, stats, group films, spectral, group spectral, profile — and the outputs in
         that order, the stats only with `stats`.  adaptive: (max_samples, step, rel_error, abs_error); groups: (instance_group, environment_group, G or None:
         the largest id, the environment's included, plus one); passes: a path passes desc where the groups desc would stand, and the PATH_PASSES pass films where the
-        group films would; what read_groups / read_bins do not ask for is passed, and returned, as None."""
+        group films would; exprs: (program, instance_group or None) — the program, the group ids and their number where the groups desc would stand, and the
+        program's `outputs` expression films where the group films would; what read_groups / read_bins do not ask for is passed, and returned, as None."""
         self.library.entry(name)
         h, w = rd.height, rd.width
-        descs, pointers, outs, prof = [rd], [], [], Profile()
+        descs, pointers, outs, prof, table = [rd], [], [], Profile(), []
 
         def out(*shape, read=True):
             a = np.zeros(shape, dtype=np.float32) if read else None
@@ -813,13 +854,19 @@ class Scene:
         if passes:
             descs.append(PathPassesDesc())
             out(PATH_PASSES, h, w, 4, read=read_groups)
+        if exprs is not None:
+            program, instance_group = exprs
+            ids = None if instance_group is None else np.ascontiguousarray(instance_group, dtype=np.uint8).reshape(-1)
+            descs.append(program)
+            table = [_u8p(ids), 0 if ids is None else ids.size]
+            out(min(max(int(program.outputs), 0), PATH_EXPRS_MAX), h, w, 4, read=read_groups)
         if bins is not None:
             descs.append(SpectralDesc(bins))
             out(max(int(bins), 0), h, w, read=read_bins)
             if groups is not None:
                 out(max(G, 0), max(int(bins), 0), h, w, read=read_bins)
         mask = [] if device_mask is None else [C.c_uint64(device_mask)]
-        self._call(name, *[C.byref(d) for d in descs], *mask, *pointers, C.byref(prof))
+        self._call(name, *[C.byref(d) for d in descs], *table, *mask, *pointers, C.byref(prof))
         return (*outs, prof)
 
     def render(self, rd):
@@ -904,6 +951,25 @@ class Scene:
         [8,H,W,4] holds per pixel the pass films of render_path_passes at that pixel's own sample count.  The scene then holds the resident film and the pass
         films as its group films, paired for denoise_light_groups_resident.  read_passes False: pass_films is None."""
         return self._render_call("render_adaptive_path_passes", rd, (max_samples, step, rel_error, abs_error), stats=stats, passes=True, read_groups=read_passes)
+
+    def _expr_program(self, exprs, environment_group):
+        """exprs as a render takes them: a PathExprProgram as it is, else text(s) for Library.path_expr_compile."""
+        return exprs if isinstance(exprs, PathExprProgram) else self.library.path_expr_compile(exprs, environment_group)
+
+    def render_path_exprs(self, rd, exprs, instance_group=None, environment_group=0, read_films=True):
+        """pt_render_path_exprs: (film, expr_films, profile) — film [H,W,4] is render(rd)'s bit for bit; expr_films [K,H,W,4] holds per expression the film of the
+        energy of exactly the paths it matches.  exprs: path expressions (a text, a sequence of up to PATH_EXPRS_MAX, or a compiled PathExprProgram, whose own
+        environment group then holds); instance_group: one light group id below 8 per instance of the scene for L0..L7 (None: every instance in group 0);
+        environment_group: the group E0..E7 finds the environment in.  The films stay on the device as the scene's resident group films (K groups), as pass films
+        do.  read_films False leaves them there alone (expr_films is None)."""
+        return self._render_call("render_path_exprs", rd, exprs=(self._expr_program(exprs, environment_group), instance_group), read_groups=read_films)
+
+    def render_adaptive_path_exprs(self, rd, max_samples, rel_error, exprs, instance_group=None, environment_group=0, abs_error=0.0, step=0, stats=False, read_films=True):
+        """pt_render_adaptive_path_exprs: (film, counts[, stats], expr_films, profile) — film, counts and stats are render_adaptive's bit for bit; expr_films
+        [K,H,W,4] holds per pixel the films of render_path_exprs at that pixel's own sample count.  The scene then holds the resident film and the expression
+        films as its group films, paired for denoise_light_groups_resident.  read_films False: expr_films is None."""
+        return self._render_call("render_adaptive_path_exprs", rd, (max_samples, step, rel_error, abs_error), stats=stats,
+                                 exprs=(self._expr_program(exprs, environment_group), instance_group), read_groups=read_films)
 
     def _resident_dims(self, name, count=3):
         """A pt_*_resident query: (width, height, planes[, bins]) of what a render left on the device(s), None when it left none."""

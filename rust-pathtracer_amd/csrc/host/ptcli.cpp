@@ -11,6 +11,7 @@
 //         [--light-group-devices MASK] [--mattes instance|material] [--matte-ranks R] [--matte-samples S]
 //         [--relamp-groups instance|material --relamp-bins B [--relamp G:CURVE[,G:CURVE...]] [--relamp-gains g0,g1,...] [--develop-subsamples N]]
 //         [--path-passes] [--denoise-path-passes]
+//         [--path-exprs NAME=EXPR;...] [--path-expr-groups instance|material]
 //
 // --config / --scene / --dry-run / the two log-level options are the reference's (the log levels only select how much
 // this program prints: warnings are shown from "warn" up).  --root is where relative file names inside the TOML files
@@ -99,6 +100,11 @@
 // byte those of --denoise with the same other flags.  Refused with what --light-groups is refused with (--adaptive and --denoise unless --denoise-path-passes is
 // given, --spectral-bins, --denoise-spectral-bins, --devices, --spectral-devices, --hero-wavelengths) and with --light-groups, --denoise-light-groups,
 // --relamp-groups and --light-group-devices, which use the same resident group films.
+// --path-exprs "NAME=EXPR;NAME=EXPR" (up to 8) renders every setting through pt_render_path_exprs (include/pt_light_groups.h, "Path expressions") and also writes
+// <filename>_expr_<NAME>.exr, the film of exactly the light paths EXPR matches — caustics=CD[RT]+L, say — through the setting's own film output.  The usual files
+// stay byte for byte what they are.  --path-expr-groups instance|material forms light groups as --light-groups forms them, for the terminals L0..L7 and E0..E7;
+// without it every emitter is in group 0, the environment too.  An expression outside the language ends the program with the compiler's message before any
+// file is read.  Refused with what --path-passes is refused with, with --path-passes itself and with --denoise.
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -166,6 +172,8 @@ struct Options {
     bool has_matte_ranks = false, has_matte_samples = false;
     bool path_passes = false;     // --path-passes: <filename>_pass_<class>.exr through pt_render_path_passes
     bool denoise_passes = false;  // --denoise-path-passes: the adaptive pass render and the joint filter over the pass films
+    std::vector<std::pair<std::string, std::string>> path_exprs;   // --path-exprs: (NAME, EXPR), <filename>_expr_<NAME>.exr through pt_render_path_exprs; empty = off
+    int expr_groups = 0;          // --path-expr-groups: the light groups of the expressions' terminals; 1 | 2 as light_groups, 0 = every emitter in group 0
 };
 
 const char* const kPathPassNames[PT_PATH_PASSES] = {"emission", "background", "diffuse_direct", "diffuse_indirect", "reflection_direct", "reflection_indirect",
@@ -183,7 +191,8 @@ int usage(const std::string& msg) {   // ("": the usage alone)
                     "             [--light-group-devices MASK] [--mattes instance|material] [--matte-ranks R] [--matte-samples S]\n"
                     "             [--relamp-groups instance|material --relamp-bins B [--relamp G:CURVE[,G:CURVE...]] [--relamp-gains g0,g1,...]\n"
                     "              [--develop-subsamples N]]\n"
-                    "             [--path-passes] [--denoise-path-passes]\n");
+                    "             [--path-passes] [--denoise-path-passes]\n"
+                    "             [--path-exprs NAME=EXPR;...] [--path-expr-groups instance|material]\n");
     return 2;
 }
 
@@ -245,12 +254,48 @@ int parse_gains(const std::string& v, std::vector<float>* out) {
     return out->size() > PT_LIGHT_GROUPS_MAX ? 2 : 0;
 }
 
+std::string trimmed(const std::string& v) {
+    const size_t a = v.find_first_not_of(" \t"), b = v.find_last_not_of(" \t");
+    return a == std::string::npos ? "" : v.substr(a, b - a + 1);
+}
+
+// the expressions of a set in the order given, compiled for an environment in `environment_group`: "" or the compiler's message
+std::string compile_path_exprs(const std::vector<std::pair<std::string, std::string>>& exprs, uint32_t environment_group, pt_path_expr_program* program) {
+    std::vector<const char*> texts;
+    for (const auto& e : exprs) texts.push_back(e.second.c_str());
+    char err[512];
+    return pt_path_expr_compile(texts.data(), (uint32_t)texts.size(), environment_group, program, err, sizeof(err)) == PT_OK ? "" : err;
+}
+
+// --path-exprs NAME=EXPR;NAME=EXPR: "" when taken, else the message.  A name goes into a file name: letters, digits, '_', '-' and '.'.
+std::string parse_path_exprs(const std::string& v, std::vector<std::pair<std::string, std::string>>* out) {
+    out->clear();
+    for (size_t p = 0;;) {
+        const size_t c = v.find(';', p);
+        const std::string item = v.substr(p, c == std::string::npos ? std::string::npos : c - p);
+        const size_t eq = item.find('=');
+        const std::string name = trimmed(item.substr(0, eq)), expr = eq == std::string::npos ? "" : trimmed(item.substr(eq + 1));
+        if (eq == std::string::npos || name.empty() || expr.empty()) return "--path-exprs takes NAME=EXPR;NAME=EXPR";
+        for (char ch : name)
+            if (!((ch >= 'a' && ch <= 'z') || (ch >= 'A' && ch <= 'Z') || (ch >= '0' && ch <= '9') || ch == '_' || ch == '-' || ch == '.'))
+                return "--path-exprs: the name '" + name + "' goes into a file name: letters, digits, '_', '-' and '.' only";
+        for (const auto& have : *out) if (have.first == name) return "--path-exprs names '" + name + "' twice";
+        out->push_back({name, expr});
+        if (c == std::string::npos) break;
+        p = c + 1;
+    }
+    if (out->size() > PT_PATH_EXPRS_MAX) return "--path-exprs takes at most 8 expressions";
+    pt_path_expr_program program;   // (the syntax, before any file is read; the program itself is compiled once the environment's group is known)
+    const std::string mistake = compile_path_exprs(*out, 0u, &program);
+    return mistake.empty() ? "" : "--path-exprs: " + mistake;
+}
+
 // the flags that take a value: the option loop fetches it, or refuses the flag without one, before the flag's arm runs
 const char* const kValueFlags[] = {"--config", "--scene", "--stdout-log-level", "--write-log-level", "--root", "--output-dir", "--seed", "--hero-wavelengths",
                                    "--adaptive", "--devices", "--guide-samples", "--guide-chain", "--guide-alpha-max", "--spectral-bins", "--denoise-spectral-bins",
                                    "--develop", "--develop-filter", "--develop-subsamples", "--spectral-devices", "--light-group-devices", "--light-groups",
                                    "--relamp-groups", "--relamp-bins", "--relamp", "--relamp-gains", "--denoise-light-groups", "--light-gains", "--mattes",
-                                   "--matte-ranks", "--matte-samples"};
+                                   "--matte-ranks", "--matte-samples", "--path-exprs", "--path-expr-groups"};
 
 // The option loop: "" when the command line parsed, else the message for usage().  *help: -h was met before any mistake.
 std::string parse_options(int argc, char** argv, Options& o, bool* help) {
@@ -323,6 +368,8 @@ std::string parse_options(int argc, char** argv, Options& o, bool* help) {
         else if (a == "--matte-samples") { if (!parse_count(v, 1, 65535, &o.matte_samples)) return "--matte-samples needs a number of samples in 1..65535"; o.has_matte_samples = true; }
         else if (a == "--path-passes") o.path_passes = true;
         else if (a == "--denoise-path-passes") o.denoise_passes = true;
+        else if (a == "--path-exprs") { const std::string mistake = parse_path_exprs(v, &o.path_exprs); if (!mistake.empty()) return mistake; }
+        else if (a == "--path-expr-groups") { if (!(o.expr_groups = parse_group_mode(v))) return "--path-expr-groups needs `instance` or `material`"; }
         else if (a == "-h" || a == "--help") { *help = true; return ""; }
         else return "unknown option " + a;
     }
@@ -351,6 +398,12 @@ std::string check_options(const Options& o) {
                             "a pass render is one render of one wavelength per path on one device, and its films are the scene's resident group films");
         if (!no.empty()) return no;
         if (o.denoise && !o.denoise_passes) return "--path-passes cannot be combined with --denoise without --denoise-path-passes: the filter of the pass films takes the adaptive pass render";
+    }
+    if (o.expr_groups && o.path_exprs.empty()) return "--path-expr-groups needs --path-exprs";
+    if (!o.path_exprs.empty()) {
+        no = cannot_combine("--path-exprs", {adapt, denoise, bins, dbins, devices, sdevices, hero, groups, dgroups, relamp, gdevices, {o.path_passes, "--path-passes"}, {o.assemble, "--denoise-assemble"}},
+                            "an expression render is one plain render of one wavelength per path on one device, and its films are the scene's resident group films");
+        if (!no.empty()) return no;
     }
     if (o.group_multi && !o.light_groups && !o.denoise_groups) return "--light-group-devices needs --light-groups or --denoise-light-groups: it names the devices their group render runs on";
     if (o.group_multi && o.multi) return "--light-group-devices cannot be combined with --devices: a group render takes its devices from --light-group-devices alone";
@@ -478,6 +531,8 @@ struct Run {
     // library of the scene file — and per group the old and the new curve
     Curves relamp_curves;
     std::vector<int32_t> relamp_old = std::vector<int32_t>(PT_LIGHT_GROUPS_MAX, PT_RELAMP_KEEP), relamp_new = relamp_old;
+    // --path-exprs: the program of the expressions, compiled for the environment's group of --path-expr-groups (without that flag: 0, and no instance is labelled)
+    pt_path_expr_program expr_program;
 };
 
 // The exits between loading the scene and rendering: each says why on stderr and returns false.
@@ -631,7 +686,7 @@ struct Setting {
         const bool counted = adaptive || o.denoise;   // through the adaptive entries
         const pt_light_groups_desc* gd = &r.gd;
         const pt_path_passes_desc ppd = {{0u, 0u, 0u, 0u}};
-        const uint32_t groups = o.path_passes ? (uint32_t)PT_PATH_PASSES : (o.light_groups || o.denoise_groups) ? gd->group_count : 0u;
+        const uint32_t groups = o.path_passes ? (uint32_t)PT_PATH_PASSES : !o.path_exprs.empty() ? r.expr_program.outputs : (o.light_groups || o.denoise_groups) ? gd->group_count : 0u;
         film.resize(4 * np);
         counts.resize(counted ? np : 0);
         stats.resize(o.denoise ? 2 * np : 0);
@@ -664,6 +719,11 @@ struct Setting {
         } else if (o.path_passes) {
             suffix = ", " + std::to_string(PT_PATH_PASSES) + " path passes";
             pick("pt_render_path_passes", [&] { return pt_render_path_passes(scene, &rd, &ppd, f, group_films.data(), prof); });
+        } else if (!o.path_exprs.empty()) {
+            suffix = ", " + std::to_string(r.expr_program.outputs) + " path expressions";
+            const uint8_t* ids = o.expr_groups ? r.instance_group.data() : nullptr;
+            const uint32_t n_ids = o.expr_groups ? r.desc->instance_count : 0u;
+            pick("pt_render_path_exprs", [this, ids, n_ids, f, prof] { return pt_render_path_exprs(scene, &rd, &r.expr_program, ids, n_ids, f, group_films.data(), prof); });
         } else if (o.light_groups) {
             suffix = ", " + std::to_string(gd->group_count) + " light groups";
             if (o.group_multi) pick("pt_render_light_groups_multi", [&] { return pt_render_light_groups_multi(scene, &rd, gd, o.group_device_mask, f, group_films.data(), prof); });
@@ -755,6 +815,14 @@ struct Setting {
         Pixels own(np);
         for (int c = 0; c < PT_PATH_PASSES; ++c)
             if (!write_picture(films.data() + 4 * np * c, stem + "_pass_" + kPathPassNames[c], own, false, "", "--path-passes")) return false;
+        return true;
+    }
+
+    // --path-exprs: every expression's film through this setting's film output (buffers of their own)
+    bool write_exprs(const std::vector<float>& films) {
+        Pixels own(np);
+        for (size_t e = 0; e < o.path_exprs.size(); ++e)
+            if (!write_picture(films.data() + 4 * np * e, base + "_expr_" + o.path_exprs[e].first, own, false, "", "--path-exprs")) return false;
         return true;
     }
 
@@ -922,8 +990,9 @@ struct Setting {
         base = o.output_dir + "/" + (rs.filename ? rs.filename : "beauty");  // src/renderer/mod.rs:27-31
         if (!write_picture(film.data(), base, px, true, "", nullptr)) return false;
         if (o.mattes && !write_mattes()) return false;
-        if (r.group_mode && !o.relamp_groups && !write_groups(base, group_films, kMixResident)) return false;
+        if (r.group_mode && !o.relamp_groups && o.path_exprs.empty() && !write_groups(base, group_films, kMixResident)) return false;
         if (o.path_passes && !write_passes(base, group_films)) return false;
+        if (!o.path_exprs.empty() && !write_exprs(group_films)) return false;
         if (o.relamp_groups && !write_relamped()) return false;
         if (o.denoise_bins) {   // (a copy: the filter takes the bins as rendered)
             std::vector<float> noisy(spectral);
@@ -990,13 +1059,20 @@ int main(int argc, char** argv) {
     if (o.develop && !load_develop_curves(r)) return 1;
     r.instance_group.assign(desc->instance_count, 0);
     memset(&r.gd, 0, sizeof(r.gd));
-    r.group_mode = o.light_groups ? o.light_groups : o.denoise_groups ? o.denoise_groups : o.relamp_groups;
-    r.group_flag = o.light_groups ? "--light-groups" : o.denoise_groups ? "--denoise-light-groups" : "--relamp-groups";
+    r.group_mode = o.light_groups ? o.light_groups : o.denoise_groups ? o.denoise_groups : o.relamp_groups ? o.relamp_groups : o.expr_groups;
+    r.group_flag = o.light_groups ? "--light-groups" : o.denoise_groups ? "--denoise-light-groups" : o.relamp_groups ? "--relamp-groups" : "--path-expr-groups";
     if (r.group_mode && !form_light_groups(r)) return 1;
     if (o.path_passes) {
         printf("path passes: %d (", PT_PATH_PASSES);
         for (int c = 0; c < PT_PATH_PASSES; ++c) printf("%s%s", c ? ", " : "", kPathPassNames[c]);
         printf(")\n");
+    }
+    if (!o.path_exprs.empty()) {
+        const std::string mistake = compile_path_exprs(o.path_exprs, r.gd.environment_group, &r.expr_program);
+        if (!mistake.empty()) { fprintf(stderr, "error: --path-exprs: %s\n", mistake.c_str()); return 1; }
+        printf("path expressions: %u (", r.expr_program.outputs);
+        for (size_t e = 0; e < o.path_exprs.size(); ++e) printf("%s%s", e ? ", " : "", o.path_exprs[e].first.c_str());
+        printf("), %u states\n", r.expr_program.states);
     }
     if (o.relamp_groups && !load_relamp_curves(r)) return 1;
     if (o.denoise && !o.dry_run && !adaptive_path_takes_every_setting(r)) return 1;

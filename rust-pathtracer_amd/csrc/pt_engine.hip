@@ -651,6 +651,12 @@ struct RenderJob {
     // pt_render_path_passes (its arguments checked; include/pt_light_groups.h): a group render of PP_CLASSES films whose vertex and light-sample forms route the
     // energy by the path's own history (PassRouter, pt_path_pass_rules.h) and keep a plane of state words behind the class planes; d_group_films as above, no table
     bool classes = false;
+    // pt_render_path_exprs (its arguments checked; include/pt_light_groups.h "Path expressions"): a group render of exprs->outputs films routed by the program's
+    // automaton (ExprRouter, pt_path_expr_rules.h), with a plane of state words behind the expression planes as a pass render has; d_expr_table: the program's 64
+    // entries in device memory, d_expr_groups: one light group id per instance there, or null; d_group_films as above
+    const pt_path_expr_program* exprs = nullptr;
+    const PxEntry* d_expr_table = nullptr;
+    const uint8_t* d_expr_groups = nullptr;
     // pt_render_light_groups_spectral (include/pt_light_groups_spectral.h): with groups and d_spectral, group_count * spectral_bins planes of width * height floats —
     // every pass also adds each group's plane to that group's bins
     float* d_group_bins = nullptr;
@@ -702,7 +708,7 @@ pt_status plan_render(const pt_scene* sc, const pt_render_desc& rd, const Render
     // the sweep table holds walked meshes: rays that reach one are parked and resumed in full waves (PT_AMD_NO_PARK=1: in line)
     const bool walks = (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_SWEEP_WALKS) != 0;
     const bool mesh_lights = sc->host.blob[PT_HDR_LIGHT_FACE_OFF] != 0u;   // (emissive mesh faces: PT_FORM_ANY, below)
-    const bool grouped = job.groups != nullptr || job.classes;   // (a light-group or path-pass render: PT_FORM_ANY and the FULL vertex form, whose siblings route the energy: pt_kern_routed.hip)
+    const bool grouped = job.groups != nullptr || job.classes || job.exprs != nullptr;   // (a light-group, path-pass or path-expression render: PT_FORM_ANY and the FULL vertex form, whose siblings route the energy: pt_kern_routed.hip)
     const bool parked = sweep && walks && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights && !grouped;
     // no sweep table (more than 64 instances, PT_AMD_NO_SWEEP): the top-level tree per lane, every mesh parked (top_walk_run, pt_device.h)
     const bool parked_walk = !sweep && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights && !grouped;
@@ -838,7 +844,8 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
 #else
     const bool need_hits = !cfg.fuse;
 #endif
-    const uint32_t group_count = job.classes ? PP_CLASSES : job.groups ? job.groups->group_count : 0u, group_planes = group_count + (job.classes ? 1u : 0u);
+    const uint32_t group_count = job.classes ? PP_CLASSES : job.exprs ? job.exprs->outputs : job.groups ? job.groups->group_count : 0u;
+    const uint32_t group_planes = group_count + (job.classes || job.exprs ? 1u : 0u);   // (+ the plane of state words)
     st = ensure_buffers(sc, sc->buf, capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits, group_planes);
     if (st != PT_OK) return st;
     DeviceBuffers& b = sc->buf;
@@ -906,13 +913,15 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
         uint32_t* live[2];         // per-segment live-path counts, ping-pong with the path queues
         uint32_t* nshadow;         // per-segment light-sample item counts; behind them (nshadow + grid) the counts of the live ones (Layout::shadow_live_field)
         PassRouter pass_router;    // a path-pass render: the router over the set's state plane
+        ExprRouter expr_router;    // a path-expression render: likewise, behind its own number of planes
         size_t marks;              // timing events recorded
         std::vector<int> stage;    // stage[k]: what the interval from event k to event k + 1 is charged to (-1: no stage)
     };
     auto make_lane = [&](DeviceBuffers& s, hipStream_t on, std::vector<hipEvent_t>* ev) {
         return Lane{&s, on, ev, Queue{s.paths_a, s.capacity, plan.path_fields}, Queue{s.paths_b, s.capacity, plan.path_fields}, Queue{s.hits, s.capacity, HS_FIELDS},
                     Queue{s.shadow, s.capacity, plan.item_fields}, {s.counts, s.counts + grid}, s.counts + 2 * grid,
-                    PassRouter{job.classes ? pp_state_words(s.energy, s.capacity) : nullptr}, 0, {}};
+                    PassRouter{job.classes ? pp_state_words(s.energy, s.capacity) : nullptr},
+                    ExprRouter{{job.d_expr_table, job.d_expr_groups, job.exprs ? px_state_words(s.energy, s.capacity, job.exprs->outputs) : nullptr, job.exprs ? job.exprs->start : 0u}}, 0, {}};
     };
     const GroupRouter group_router{job.groups ? *job.groups : LightGroupTable{nullptr, 0u, 0u}};
     Lane lanes[2] = {make_lane(b, stream, &sc->events), make_lane(overlap ? sc->buf2 : b, overlap ? sc->pass_stream : stream, &sc->events2)};
@@ -1005,6 +1014,7 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                     if (rd.light_samples > 0) timed(l, ST_SHADOW, [&] { launch_shadow_routed(cfg, sargs, rd.light_samples, qs, b.energy, b.capacity, seg_cap, nshadow, router); });
                 };
                 if (job.classes) routed(l.pass_router);
+                else if (job.exprs) routed(l.expr_router);
                 else if (job.groups) routed(group_router);
                 else {
                     timed(l, ST_SHADE, [&] { launch_shade(cfg, hero ? 4 : 1, shade_form, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats); });
@@ -1258,6 +1268,8 @@ struct RenderCall {
     const pt_light_groups_desc* gd = nullptr;   // pt_render_light_groups; group_films: where the caller wants them (may be null)
     float* group_films = nullptr;
     bool passes = false;                    // pt_render_path_passes: no gd; group_films: where the caller wants the PT_PATH_PASSES pass films (may be null)
+    const pt_path_expr_program* exprs = nullptr;   // pt_render_path_exprs: no gd; expr_groups: one light group id per instance of the scene, or null; group_films: where
+    const uint8_t* expr_groups = nullptr;          // the caller wants the program's `outputs` expression films (may be null)
     bool group_bins = false;                // pt_render_light_groups_spectral (gd and sd): the group bins too; group_spectral: where the caller wants them (may be null)
     float* group_spectral = nullptr;
 };
@@ -1268,7 +1280,7 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
     const pt_render_desc& rd = *call.rd;
     forget_node_render(sc);
     if (call.sd) { sc->spectral_valid = false; sc->spectral_shards.clear(); }   // (a spectral render starts: whatever the buffer held is no film from here on)
-    const uint32_t films = call.passes ? (uint32_t)PT_PATH_PASSES : call.gd ? call.gd->group_count : 0u;   // the resident group films this render leaves
+    const uint32_t films = call.passes ? (uint32_t)PT_PATH_PASSES : call.exprs ? call.exprs->outputs : call.gd ? call.gd->group_count : 0u;   // the resident group films this render leaves
     if (films) end_group_films(sc);   // (likewise the group films, the denoised ones that came from them, and the group bins)
     sc->groups_paired = false;   // (the resident film ends below)
     sc->resident.end();   // (film_cache and the adaptive buffers are written from here on; guides and denoised outputs belonged to the film before)
@@ -1279,6 +1291,8 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
     const size_t group_bytes = film_bytes * films;
     if (st == PT_OK && films) st = sc->group_films_cache.reserve(group_bytes);
     if (st == PT_OK && call.gd) st = sc->group_table.reserve(call.gd->instance_count ? call.gd->instance_count : 1u);
+    const size_t expr_table_bytes = sizeof(PxEntry) * PX_MAX_STATES, expr_instances = call.expr_groups ? sc->host.blob[PT_HDR_INSTANCE_COUNT] : 0u;
+    if (st == PT_OK && call.exprs) st = sc->group_table.reserve(expr_table_bytes + (expr_instances ? expr_instances : 1u));   // (the table in front: 16-byte entries)
     if (st != PT_OK) return st;
     const size_t group_bins_bytes = call.group_bins ? spectral_bytes * call.gd->group_count : 0;
     const pt_status bins_reserved = call.group_bins ? sc->group_bins_cache.reserve(group_bins_bytes) : PT_OK;
@@ -1297,6 +1311,16 @@ static pt_status render_one(pt_scene* sc, const RenderCall& call, pt_profile* pr
         job.groups = &table; job.d_group_films = sc->group_films_cache.as<float>();
     }
     if (call.passes) { job.classes = true; job.d_group_films = sc->group_films_cache.as<float>(); }
+    if (call.exprs) {   // (the program's table, uploaded once per call: its `states` entries, the rest of the 64 zero — a state with no successor but 0 and no output)
+        uint32_t entries[PX_MAX_STATES][4];
+        memset(entries, 0, sizeof(entries));
+        memcpy(entries, call.exprs->table, sizeof(uint32_t) * 4 * call.exprs->states);
+        HIP_TRY(hipMemcpy(sc->group_table.p, entries, expr_table_bytes, hipMemcpyHostToDevice));
+        if (expr_instances) HIP_TRY(hipMemcpy(sc->group_table.as<uint8_t>() + expr_table_bytes, call.expr_groups, expr_instances, hipMemcpyHostToDevice));
+        job.exprs = call.exprs; job.d_expr_table = sc->group_table.as<PxEntry>();
+        job.d_expr_groups = expr_instances ? sc->group_table.as<uint8_t>() + expr_table_bytes : nullptr;
+        job.d_group_films = sc->group_films_cache.as<float>();
+    }
     if (call.sd) { job.d_spectral = sc->spectral_cache.as<float>(); job.spectral_bins = call.sd->bins; }
     if (call.group_bins) job.d_group_bins = sc->group_bins_cache.as<float>();
     const hipStream_t stream = nullptr;
@@ -1424,6 +1448,36 @@ pt_status pt_render_adaptive_path_passes(pt_scene* sc, const pt_render_desc* rdp
     if ((uint64_t)rd.width * rd.height > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and width x height must fit 31 bits");
     RenderCall call;
     call.rd = &rd; call.ad = &ad; call.passes = true; call.film = film; call.sample_counts = sample_counts; call.stats = stats; call.group_films = pass_films;
+    return render_one(sc, call, profile);
+}
+
+// include/pt_light_groups.h, "Path expressions": a group render of program->outputs films routed by the program's automaton; what it leaves is the scene's resident
+// group films
+pt_status pt_render_path_exprs(pt_scene* sc, const pt_render_desc* rdp, const pt_path_expr_program* program, const uint8_t* instance_group, uint32_t n_instances, float* film,
+                               float* expr_films, pt_profile* profile) {
+    forget_node_render(sc);
+    std::string err;
+    const pt_status st = pth::check_path_exprs_args(sc, rdp, program, instance_group, n_instances, sc ? sc->host.blob[PT_HDR_INSTANCE_COUNT] : 0u, film, &err);
+    if (st != PT_OK) return fail(st, err);
+    if (rdp->width == 0 || rdp->height == 0 || (uint64_t)rdp->width * rdp->height > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and width x height must fit 31 bits");
+    RenderCall call;
+    call.rd = rdp; call.exprs = program; call.expr_groups = instance_group; call.film = film; call.group_films = expr_films;
+    return render_one(sc, call, profile);
+}
+
+pt_status pt_render_adaptive_path_exprs(pt_scene* sc, const pt_render_desc* rdp, const pt_adaptive_desc* adp, const pt_path_expr_program* program, const uint8_t* instance_group,
+                                        uint32_t n_instances, float* film, uint32_t* sample_counts, double* stats, float* expr_films, pt_profile* profile) {
+    forget_node_render(sc);
+    pt_render_desc rd;
+    pt_adaptive_desc ad;
+    std::string err;
+    const pt_status st = pth::check_adaptive_path_exprs_args(sc, rdp, adp, program, instance_group, n_instances, sc ? sc->host.blob[PT_HDR_INSTANCE_COUNT] : 0u,
+                                                             sc ? (uint32_t)sc->host.cameras.size() : 0u, film, sample_counts, &rd, &ad, &err);
+    if (st != PT_OK) return fail(st, err);
+    if ((uint64_t)rd.width * rd.height > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive and width x height must fit 31 bits");
+    RenderCall call;
+    call.rd = &rd; call.ad = &ad; call.exprs = program; call.expr_groups = instance_group; call.film = film; call.sample_counts = sample_counts; call.stats = stats;
+    call.group_films = expr_films;
     return render_one(sc, call, profile);
 }
 

@@ -1,7 +1,7 @@
 // pt_kern_routed.hip — the two kernel forms of a routed render and their launchers: siblings of k_shade<M, 1, PT_SHADE_FULL, 0u> and
 // k_shadow<M, 1, PT_TRAV_ANY, true, 0u> — the most general vertex and light-sample forms, one wavelength, unfused, no live list — that also send every energy
 // addition to the plane their router names (pt_routed_rules.h): the light group's for a light-group render (include/pt_light_groups.h),
-// the path class's for a path-pass render (section 17).  A translation unit of its own: no other kernel family's device code knows of routers.
+// the path class's for a path-pass render (section 17), every matching expression's for a path-expression render (section 17).  A translation unit of its own: no other kernel family's device code knows of routers.
 #include <cstdio>
 #include <cstdlib>
 #include "pt_kernels.h"
@@ -124,6 +124,7 @@ void launch_shadow_routed(const LaunchCfg& c, const SceneArgs& sc, uint32_t ligh
     template void launch_shadow_routed<Router>(const LaunchCfg&, const SceneArgs&, uint32_t, Queue, float*, uint32_t, uint32_t, const uint32_t*, const Router&);
 PT_ROUTED_LAUNCHERS(GroupRouter)
 PT_ROUTED_LAUNCHERS(PassRouter)
+PT_ROUTED_LAUNCHERS(ExprRouter)
 
 template <typename Router>
 static void allow_lds_router(uint32_t shade_bytes, uint32_t shadow_bytes, hipError_t* worst) {
@@ -136,6 +137,7 @@ hipError_t allow_lds_routed(uint32_t shade_bytes, uint32_t shadow_bytes) {
     hipError_t worst = hipSuccess;
     allow_lds_router<GroupRouter>(shade_bytes, shadow_bytes, &worst);
     allow_lds_router<PassRouter>(shade_bytes, shadow_bytes, &worst);
+    allow_lds_router<ExprRouter>(shade_bytes, shadow_bytes, &worst);
     return worst;
 }
 

@@ -571,6 +571,60 @@ pt_status check_adaptive_path_passes_args(const void* scene, const pt_render_des
     return normalize_adaptive_desc(*rd, *ad, sample_counts != nullptr, camera_count, rd_out, ad_out, error);
 }
 
+pt_status check_path_exprs_args(const void* scene, const pt_render_desc* rd, const pt_path_expr_program* program, const uint8_t* instance_group, uint32_t n_instances,
+                                uint32_t scene_instances, const void* film, std::string* error) {
+    if (!scene) { *error = "the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!rd) { *error = "the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!program) { *error = "the path expression program is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!film) { *error = "film_xyzw is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (program->outputs == 0 || program->outputs > PT_PATH_EXPRS_MAX) { *error = "the path expression program's outputs must be in 1..8"; return PT_ERR_INVALID_ARGUMENT; }
+    if (program->states == 0 || program->states > PT_PATH_EXPR_STATES_MAX) { *error = "the path expression program's states must be in 1..64"; return PT_ERR_INVALID_ARGUMENT; }
+    if (program->start >= program->states) { *error = "the path expression program's start is not below its states"; return PT_ERR_INVALID_ARGUMENT; }
+    if (program->environment_group >= PT_LIGHT_GROUPS_MAX) { *error = "the path expression program's environment_group must be below 8"; return PT_ERR_INVALID_ARGUMENT; }
+    for (uint32_t q = 0; q < program->states; ++q) {
+        const uint32_t* w = program->table[q];
+        for (uint32_t e = 0; e < 3u; ++e)
+            if (((w[0] >> (6u * e)) & 63u) >= program->states) {
+                *error = "the path expression program's state " + std::to_string(q) + " has a successor that is not below its states";
+                return PT_ERR_INVALID_ARGUMENT;
+            }
+        const uint32_t beyond = ~((1u << program->outputs) - 1u) & 0xffu;   // (a mask bit from `outputs` on would name a plane the render does not have)
+        if ((w[0] >> 18) != 0u || ((w[1] | w[2] | w[3]) & (beyond * 0x01010101u)) != 0u || (w[3] >> 8) != 0u) {
+            *error = "the path expression program's state " + std::to_string(q) + " sets a bit outside its successors and the masks of its outputs";
+            return PT_ERR_INVALID_ARGUMENT;
+        }
+    }
+    if (instance_group) {
+        if (n_instances != scene_instances) {
+            *error = "n_instances is " + std::to_string(n_instances) + ", the scene has " + std::to_string(scene_instances) + " instances";
+            return PT_ERR_INVALID_ARGUMENT;
+        }
+        for (uint32_t i = 0; i < n_instances; ++i)
+            if (instance_group[i] >= PT_LIGHT_GROUPS_MAX) {
+                *error = "instance " + std::to_string(i) + " is in group " + std::to_string(instance_group[i]) + ": group ids must be below 8";
+                return PT_ERR_INVALID_ARGUMENT;
+            }
+    } else if (n_instances != 0) { *error = "instance_group is null: n_instances must be 0"; return PT_ERR_INVALID_ARGUMENT; }
+    if (rd->hero_wavelengths == 4) { *error = "path expressions carry one wavelength per path (hero_wavelengths 0 or 1)"; return PT_ERR_UNSUPPORTED; }
+    if (rd->medium_aware) { *error = "path expressions are not rendered by the medium-aware walk"; return PT_ERR_UNSUPPORTED; }
+    if (rd->shard_count > 1) { *error = "path expressions render the whole film (shard_count 0 or 1)"; return PT_ERR_UNSUPPORTED; }
+    if (rd->first_sample != 0 || (rd->sample_count != 0 && rd->sample_count != rd->spp)) {
+        *error = "path expressions render the whole sample range (first_sample 0, sample_count 0 or spp)";
+        return PT_ERR_UNSUPPORTED;
+    }
+    return PT_OK;
+}
+pt_status check_adaptive_path_exprs_args(const void* scene, const pt_render_desc* rd, const pt_adaptive_desc* ad, const pt_path_expr_program* program,
+                                         const uint8_t* instance_group, uint32_t n_instances, uint32_t scene_instances, uint32_t camera_count, const void* film,
+                                         const void* sample_counts, pt_render_desc* rd_out, pt_adaptive_desc* ad_out, std::string* error) {
+    if (!scene) { *error = "the scene is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!rd) { *error = "the render desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    if (!ad) { *error = "the adaptive desc is null"; return PT_ERR_INVALID_ARGUMENT; }
+    const pt_status st = check_path_exprs_args(scene, rd, program, instance_group, n_instances, scene_instances, film, error);
+    if (st != PT_OK) return st;
+    return normalize_adaptive_desc(*rd, *ad, sample_counts != nullptr, camera_count, rd_out, ad_out, error);
+}
+
 // ---- include/pt_light_groups_multi.h
 pt_status check_light_groups_multi_args(const void* scene, const pt_render_desc* rd, const pt_light_groups_desc* gd, uint32_t scene_instances, uint32_t camera_count,
                                         const void* film, pt_render_desc* rd_out, std::string* error) {

@@ -170,6 +170,15 @@ pt_status check_light_groups_mix_args(uint32_t width, uint32_t height, uint32_t 
 // pt_render_path_passes (include/pt_light_groups.h): no null pointer (pass_films may be null), reserved words 0: PT_ERR_INVALID_ARGUMENT; hero_wavelengths 4,
 // medium_aware, a shard (shard_count > 1) and a partial sample range: PT_ERR_UNSUPPORTED, as check_light_groups_args refuses them
 pt_status check_path_passes_args(const void* scene, const pt_render_desc* rd, const pt_path_passes_desc* pd, const void* film, std::string* error);
+// pt_render_path_exprs (include/pt_light_groups.h, "Path expressions"): what check_path_passes_args refuses of a render desc; a malformed program — outputs
+// outside 1..8, states outside 1..64, a start or successor not below states, a bit outside the successors and the masks of its outputs — and a group table that
+// is not the scene's (null with n_instances 0, or one id below 8 per instance): PT_ERR_INVALID_ARGUMENT
+pt_status check_path_exprs_args(const void* scene, const pt_render_desc* rd, const pt_path_expr_program* program, const uint8_t* instance_group, uint32_t n_instances,
+                                uint32_t scene_instances, const void* film, std::string* error);
+// pt_render_adaptive_path_exprs (include/pt_light_groups_denoise.h): the adaptive desc too, then check_path_exprs_args and normalize_adaptive_desc
+pt_status check_adaptive_path_exprs_args(const void* scene, const pt_render_desc* rd, const pt_adaptive_desc* ad, const pt_path_expr_program* program,
+                                         const uint8_t* instance_group, uint32_t n_instances, uint32_t scene_instances, uint32_t camera_count, const void* film,
+                                         const void* sample_counts, pt_render_desc* rd_out, pt_adaptive_desc* ad_out, std::string* error);
 // pt_render_adaptive_path_passes (include/pt_light_groups_denoise.h): the adaptive desc too, then check_path_passes_args and normalize_adaptive_desc
 pt_status check_adaptive_path_passes_args(const void* scene, const pt_render_desc* rd, const pt_adaptive_desc* ad, const pt_path_passes_desc* pd, uint32_t camera_count,
                                           const void* film, const void* sample_counts, pt_render_desc* rd_out, pt_adaptive_desc* ad_out, std::string* error);

@@ -260,12 +260,6 @@ struct GrowBuf : DevBuf {
 };
 
 constexpr uint32_t kUnitCounters = 2 * 64 + 2;   // two parked launches per bounce, max_bounces <= 64
-#ifdef PT_EXPERIMENTS
-#define PT_TUNE_EXPERIMENT_POOL (1u << 31)   /* a pt_tuning::flags bit of its own, unnamed in the public header (round-4 advisor: bit 3 means PT_TUNE_NO_LIVE_LIST in every build) */
-#endif
-#ifndef PT_FUSE_HERO
-#define PT_FUSE_HERO 1   /* round 4: built without machine LICM the hero fused form needs 111 VGPRs — four waves per SIMD, not three — and wins: C5 1153 -> 1179 (3625 us against 1160 + 2578) */
-#endif
 struct DeviceBuffers {
     uint32_t capacity = 0, light_samples = 0, nl = 0, park_block = 0;
     uint32_t energy_planes = 0;   // planes of `energy`: nl + 1, or a light-group render's 2 + G (pt_light_group_rules.h)
@@ -433,13 +427,6 @@ static void shard_scatter_host(const ShardKind& kind, const void* packed, const 
 }
 
 namespace {
-// whether any instance of the flattened scene is a mesh (a scene without one never parks at a mesh: its top-level walks are the ones worth leaving early)
-bool scene_has_mesh(const std::vector<uint32_t>& blob) {
-    const uint32_t off = blob[PT_HDR_INSTANCE_OFF], n = blob[PT_HDR_INSTANCE_COUNT];
-    for (uint32_t i = 0; i < n; ++i) if (blob[off + i * PT_INST_WORDS + PT_INST_KIND] == (uint32_t)PT_SHAPE_MESH) return true;
-    return false;
-}
-
 std::string g_device_info;
 
 pt_status no_device() { return fail(PT_ERR_NO_DEVICE, "no HIP device available: the product path has no CPU fallback"); }
@@ -525,9 +512,6 @@ uint32_t env_u32(const char* name, uint32_t dflt) {
     if (!v || !*v) return dflt;
     return (uint32_t)strtoul(v, nullptr, 10);
 }
-// the value a tuning field stands for (0 = "the default" in the struct)
-uint32_t tuned(uint32_t value, uint32_t dflt) { return value ? value : dflt; }
-
 // The worker threads of a node call (pt_render_adaptive_multi) meet here between the steps of a round.  The last one to arrive runs the step that needs
 // every device (the exchange, the stop decision) while the others wait.  A worker that fails calls stop(): every worker waiting or arriving later is released
 // with false, so that no thread enters a collective after another has failed, and the first error is kept for the caller.  (C++17: no std::barrier.)
@@ -662,135 +646,89 @@ struct RenderJob {
     float* d_group_bins = nullptr;
 };
 
-// What plan_render chooses for a render: the queues' size, the kernel forms and their launch configuration.
-struct RenderPlan {
-    uint32_t capacity = 0;   // path slots per pass
-    int grid = 0;            // queue segments = workgroups per launch
-    bool hero = false;       // four wavelengths per path
-    uint32_t park_block = 0, park_block_extend = 0;
-    int trav_form = 0, shade_form = 0;
-    bool park_dynamic = false, park_big = false;
-    LaunchCfg cfg{};         // (with walk_policy and fuse; unit_counter and path_marks are the pass loop's)
-    uint32_t live_list = 0, camera_record = 0;   // RenderParams' fields of these names
-    uint32_t path_fields = 0, item_fields = 0;
-};
-// The choices of a render, from the scene's blob header, its tuning and the normalised desc `rd` over the pixel list `pixels`: host logic alone, no HIP call.
-pt_status plan_render(const pt_scene* sc, const pt_render_desc& rd, const RenderJob& job, const std::vector<uint32_t>& pixels, hipStream_t stream, RenderPlan* plan) {
-    const pt_adaptive_desc* adaptive = job.adaptive;
-    const pt_tuning& tn = sc->tuning;
-    uint32_t capacity = tuned(tn.batch_slots, 1u << 27);  // path slots per pass (128 Mi ~ 32 GB of queues of the 288 GB; tools/sweep.sh)
-    if (capacity < 1024) capacity = 1024;
-    uint64_t want = (uint64_t)pixels.size() * (adaptive ? (adaptive->step > rd.spp ? adaptive->step : rd.spp) : rd.sample_count);   // (the longest pass of a round)
-    if (want < capacity) capacity = (uint32_t)(want ? want : 1);
-    const uint32_t blocks_per_cu = tuned(tn.blocks_per_cu, 64);
-    if (blocks_per_cu > 1024) return fail(PT_ERR_INVALID_ARGUMENT, "pt_tuning::blocks_per_cu (PT_AMD_BLOCKS_PER_CU) must be in 1..1024");
-    const int grid = sc->num_cus * (int)blocks_per_cu;  // queue segments = workgroups per launch
-    // a pass holds at least one whole phase of one pixel (pt_plan.cpp): the queues must too (NaiveRenderer settings: phase = spp)
-    { const uint32_t phase = rd.sample_count < rd.phase_samples ? rd.sample_count : rd.phase_samples; if (capacity < phase) capacity = phase; }
-    const bool hero = rd.hero_wavelengths == 4;
-    if (hero && capacity > (1u << 26)) capacity = 1u << 26;  // 4-wavelength queues are ~1.5x wider: 64 Mi slots ~ 24 GB
-    // (the medium-aware walk keeps its two extra path fields where the hero layout keeps the passengers' throughputs)
-    // the parked kernels in workgroups of 512 / 1024 threads that stage the whole blob (pt_tuning::park_block): static form, one wavelength, a blob that fits
-    // 0 = the measured default: the light-sample kernel in workgroups of 512 (C3: -5 %), the closest-hit kernel in its own 256 (at 512 it loses its fifth wave
-    // per SIMD: +14 %); 512 / 1024 = both kernels; 256 = neither (profiles/r4_experiments.md section 1)
-    const bool park_big_ok = !hero && sc->blob_words * 4u <= kParkBlobLimitBytes && sc->lds_mode == PT_LDS_CORE && !(tn.flags & PT_TUNE_NO_LDS);
-    // (round 6: in a scene with a certified convex body — PT_FLAG_CONVEX, the gem of C3 — nine in ten of the light rays that used to walk the mesh no longer reach it, and the
-    // light-sample kernel is better off in workgroups of 256 that stage the core alone, twice the workgroups per CU: C3 k_shadow_parked 2339 -> 2083 us, profiles/r6d_ab_park.txt)
-    const bool few_walks = (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_CONVEX) != 0u;
-    const uint32_t park_block = !park_big_ok ? (uint32_t)kBlock : tn.park_block == 0u ? (few_walks ? (uint32_t)kBlock : 512u) : tn.park_block;
-    const uint32_t park_block_extend = !park_big_ok || tn.park_block == 0u ? (uint32_t)kBlock : tn.park_block;
-    // (the parked kernels' scratch, b.park, by ensure_buffers' rule: the plan is made before the buffers are)
-    const bool no_table = sc->host.blob[PT_HDR_SWEEP_OFF] == 0 || (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_NO_SWEEP);
-    const bool park_scratch = (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_SWEEP_WALKS) || no_table;
-    const int mode = sc->lds_mode;
-    const uint32_t lds_bytes = mode == PT_LDS_ALL ? sc->blob_words * 4u : (mode == PT_LDS_CORE ? sc->host.blob[PT_HDR_CORE_WORDS] * 4u : 0u);
-    const bool sweep = sc->host.blob[PT_HDR_SWEEP_OFF] != 0 && !(sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_NO_SWEEP);
-    // the sweep table holds walked meshes: rays that reach one are parked and resumed in full waves (PT_AMD_NO_PARK=1: in line)
-    const bool walks = (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_SWEEP_WALKS) != 0;
-    const bool mesh_lights = sc->host.blob[PT_HDR_LIGHT_FACE_OFF] != 0u;   // (emissive mesh faces: PT_FORM_ANY, below)
-    const bool grouped = job.groups != nullptr || job.classes || job.exprs != nullptr;   // (a light-group, path-pass or path-expression render: PT_FORM_ANY and the FULL vertex form, whose siblings route the energy: pt_kern_routed.hip)
-    const bool parked = sweep && walks && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights && !grouped;
-    // no sweep table (more than 64 instances, PT_AMD_NO_SWEEP): the top-level tree per lane, every mesh parked (top_walk_run, pt_device.h)
-    const bool parked_walk = !sweep && park_scratch && !(tn.flags & PT_TUNE_NO_PARK) && !mesh_lights && !grouped;
-    // PT_AMD_POOL=1: phase 3 of a pure sweep scene pooled per wave (sweep_run_pooled).  Bit-identical, but measured slower than the lane
-    // loop on MI355X (C2: k_extend 3155 vs 2475 us, k_shadow 5421 vs 4677 us; DESIGN.md section 5 has the breakdown), so it is not the default.
+// The plan of a render (pth::plan_render: host logic alone, pinned by tests/golden/render_plans.tsv) from what the scene and the job hold, and — a measurement
+// build only — the arms that read the environment, applied to the finished plan.  *live_lists: LaunchCfg's field of that name.
+pt_status plan_for(const pt_scene* sc, const pt_render_desc& rd, const RenderJob& job, size_t n_pixels, pth::RenderPlan* plan, bool* live_lists) {
+    pth::RenderAsk ask;
+    ask.num_cus = sc->num_cus; ask.rd = rd; ask.n_pixels = n_pixels; ask.adaptive = job.adaptive;
+    ask.routed = job.groups != nullptr || job.classes || job.exprs != nullptr;
 #ifdef PT_EXPERIMENTS
-    const bool pooled = sweep && !walks && mode == PT_LDS_ALL && lds_bytes + pool_lds_bytes() <= kLdsBlobLimitBytes && (tn.flags & PT_TUNE_EXPERIMENT_POOL) != 0;
-#else
-    const bool pooled = false;   // (the pooled kernels are not in the product: make EXTRA=-DPT_EXPERIMENTS builds them, PT_AMD_POOL=1 selects them there)
+    ask.pool_lds_bytes = pool_lds_bytes();
 #endif
-    // (walked meshes in line under PT_AMD_NO_PARK, and every partly staged or unstaged blob: the run-time choice of PT_FORM_ANY.  A scene with emissive mesh faces
-    // takes it too: the specialised traversal forms are compiled without the faces' code — PT_SCENE_NO_MESH_LIGHTS, pt_kern_*.hip — and keep their registers)
-    const int trav_form = parked ? PT_FORM_PARKED : parked_walk ? PT_FORM_PARKED_WALK : (mode != PT_LDS_ALL || (sweep && walks) || mesh_lights || grouped) ? PT_FORM_ANY : pooled ? PT_FORM_POOLED : sweep ? PT_FORM_SWEEP : PT_FORM_WALK;
-    // The parked kernels take units of work from a counter, a few persistent workgroups per CU, when the whole blob is staged in LDS
-    // (C3: k_extend 9175 -> 7880 us, k_shadow 8008 -> 7105, 487 -> 543 Msamples/s: park lists that live across units keep the drains
-    // full).  With the mesh in HBM/L2 (C4) the static form wins, 1128 vs 1083 Msamples/s: a wave's parked rays then come from one
-    // region of the film and walk the same part of the mesh.  PT_AMD_PARK_DYNAMIC=0 / 1 forces either.
-    const bool park_dynamic = parked && (tn.park_dynamic < 0 ? mode == PT_LDS_ALL : tn.park_dynamic != 0);
-    const bool park_big = parked && !park_dynamic && park_block != (uint32_t)kBlock && mode != PT_LDS_ALL;
-    const int dyn_grid = sc->num_cus * (int)tuned(tn.park_blocks_per_cu, 4);
-    LaunchCfg cfg{grid, lds_bytes, stream, mode};
-    cfg.dyn_grid = dyn_grid < grid ? dyn_grid : grid;
-    cfg.lacks = sc->lacks;
-    cfg.mesh_lights = mesh_lights;
+    std::string err;
+    if (!pth::plan_render(sc->host.blob, sc->tuning, pth::ScenePlan{sc->lacks, sc->lds_mode}, ask, plan, &err)) return fail(PT_ERR_INVALID_ARGUMENT, err);
+    *live_lists = false;
 #ifdef PT_EXPERIMENTS
-    cfg.live_lists = env_u32("PT_AMD_LIVE_LISTS", 0) != 0;   // (k_shadow_live: a measurement build's kernel, profiles/r4_experiments.md)
-#endif
-    if (park_big) { cfg.park_block = (int)park_block; cfg.park_block_extend = (int)park_block_extend; cfg.park_blob_bytes = sc->blob_words * 4u; }
-    // The top-level walk is left early by a wave's last lanes (top_walk_run) where that walk is long and nothing else thins the wave out: a tree of more than 64
-    // instances — the scenes that have no sweep table by themselves — without a mesh (test_bokeh.toml + a floor: k_shadow_parked 2900 -> 2320 us at 32, 2430 at 16 and
-    // at 48).  With a mesh in the scene the lanes of a wave PARK at it, the wave thins out although its rays are not done, and evicting the rest only adds park
-    // traffic: the same scene with the gem standing on the floor 1337 -> 1260 Msamples/s at 32 (1341 at 16); a small scene forced off its table (PT_AMD_NO_SWEEP:
-    // thirteen instances in the gem scene, ten nodes per walk) lost 15 % (profiles/r5_experiments.md section 2).
-    const uint32_t top_evict = tn.top_evict_below ? tn.top_evict_below
-                             : (sc->host.blob[PT_HDR_INSTANCE_COUNT] > PT_SWEEP_MAX_BITS && !scene_has_mesh(sc->host.blob) ? kTopEvictBelow : 1u);
-    // The grouped mesh sweep's group loop is left by a wave's last lanes (mesh_walk, GROUPS) where every parked ray of the closest-hit kernel stands in the SAME mesh — one
-    // walked mesh in the table: a resumed wave is then always one the grouped sweep takes, and a ray that comes back with groups to do is never walked from the top.
-    uint32_t group_evict = 1u;
-    {
-        const std::vector<uint32_t>& bl = sc->host.blob;
-        uint32_t walked = 0;
-        if (sweep) for (uint32_t j = 0; j < bl[PT_HDR_SWEEP_COUNT]; ++j) walked += (bl[bl[PT_HDR_SWEEP_OFF] + j * PT_SWEEP_INST_WORDS + 1] & PT_SWEEP_WALKED) ? 1u : 0u;
-        if (parked && walked == 1u) group_evict = tn.group_evict_below ? tn.group_evict_below : kGroupEvictBelow;
-    }
-    cfg.walk_policy = (tn.walk_evict_below ? tn.walk_evict_below : kWalkEvictBelow) | (tn.walk_search_below ? tn.walk_search_below : kWalkSearchBelow) << 8
-                    | ((tn.flags & PT_TUNE_NO_AXIS_SCAN) ? 0u : PT_WALK_SCAN_AXIS)
-                    | (top_evict <= 1u ? 0u : top_evict << 24)   // (1 = never: 0 in the policy word)
-                    | (group_evict <= 1u ? 0u : group_evict << 17);
-    // light samples can pick the environment only if env_sampling_probability > 0: otherwise k_shade is the form without that branch
-    float env_prob; std::memcpy(&env_prob, &sc->host.blob[PT_HDR_ENV_PROB], sizeof env_prob);
-    bool has_ggx = false;
-    for (uint32_t i = 0; i < sc->host.blob[PT_HDR_MATERIAL_COUNT]; ++i) {
-        const uint32_t kind = sc->host.blob[sc->host.blob[PT_HDR_MATERIAL_OFF] + i * PT_MAT_WORDS + PT_MAT_KIND];
-        has_ggx = has_ggx || kind == PT_MATERIAL_GGX || kind == PT_MATERIAL_PASSTHROUGH;
-    }
-    // (a PassthroughFilter lives in the forms that hold the GGX code)
-    // (a scene with a convex-body certificate takes at least the NO_ENV form: the lean and fused forms are compiled without the certificate code, pt_kern_shade.hip)
-    const bool certs = !rd.medium_aware && (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_CONVEX) != 0u;
-    const int shade_form = rd.medium_aware ? PT_SHADE_MEDIUM
-                         : (env_prob != 0.0f || tn.shade_form == 2 || grouped) ? PT_SHADE_FULL : (has_ggx || certs || tn.shade_form == 1) ? PT_SHADE_NO_ENV : PT_SHADE_LEAN;
-    cfg.certs = certs;
-    // (the plain light-sample kernel walks the list of live items; the parked forms list their live RAYS themselves, the measurement forms read every item)
-    uint32_t live_list = ((trav_form == PT_FORM_SWEEP || trav_form == PT_FORM_WALK || trav_form == PT_FORM_ANY) && shade_form == PT_SHADE_LEAN && !(tn.flags & PT_TUNE_NO_LIVE_LIST)) ? 1u : 0u;
-#ifdef PT_EXPERIMENTS
+    *live_lists = env_u32("PT_AMD_LIVE_LISTS", 0) != 0;   // (k_shadow_live: a measurement build's kernel, profiles/r4_experiments.md)
     // a measurement build runs the shipped kernel pair unless one of its own forms is asked for: those read every item of a segment
-    if (cfg.live_lists || getenv("PT_AMD_EXP_SHADOW")) live_list = 0u;
+    if (*live_lists || getenv("PT_AMD_EXP_SHADOW")) plan->live_list = 0u;
 #endif
-    const uint32_t camera_record = (shade_form == PT_SHADE_LEAN || shade_form == PT_SHADE_FULL || shade_form == PT_SHADE_MEDIUM) ? 1u : 0u;   // (the forms whose bounce-0 launch rebuilds the camera vertex: k_shade, pt_kernels.h)
-    // k_shade that traces its own segments: exists for the pure sweep form of a fully staged, transform-free scene shaded by the lean form.
-    // Measured (profiles/r3_experiments.md): C2 +4..5 % (4370 us against 2095 + 2490..2640 per bounce); with four wavelengths per path it
-    // lost in round 3 (C5 996 against 1093 Msamples/s: the traversal then ran at the three waves per SIMD the wide vertex code left) and wins since round 4 (PT_FUSE_HERO).
-    cfg.fuse = !(tn.flags & PT_TUNE_NO_FUSE) && (!hero || PT_FUSE_HERO) && trav_form == PT_FORM_SWEEP && shade_form == PT_SHADE_LEAN && (cfg.lacks & PT_SCENE_NO_XF) != 0;
-    // (a queue's tiles are laid out by the number of fields this render uses, pt_stages.h: the buffers are sized for the widest layout seen)
-    const uint32_t path_fields = hero ? Layout<4>::path_fields : (rd.medium_aware ? (uint32_t)PS_FIELDS + 2u : Layout<1>::path_fields);
-    const uint32_t item_fields = hero ? Layout<4>::shadow_queue_fields(rd.light_samples ? rd.light_samples : 1) : Layout<1>::shadow_queue_fields(rd.light_samples ? rd.light_samples : 1);
-    *plan = RenderPlan{capacity, grid, hero, park_block, park_block_extend, trav_form, shade_form, park_dynamic, park_big, cfg, live_list, camera_record,
-                       path_fields, item_fields};
     return PT_OK;
 }
+// The one place a launch configuration is made from a plan (unit_counter and path_marks are the pass loop's, per launch; so is the stream of a pass on the second lane)
+LaunchCfg launch_cfg(const pt_scene* sc, const pth::RenderPlan& plan, bool live_lists, hipStream_t stream) {
+    LaunchCfg cfg{plan.grid, plan.lds_bytes, stream, sc->lds_mode};
+    cfg.dyn_grid = plan.dyn_grid;
+    cfg.lacks = sc->lacks;
+    cfg.walk_policy = plan.walk_policy;
+    cfg.park_block = plan.launch_park_block; cfg.park_block_extend = plan.launch_park_block_extend; cfg.park_blob_bytes = plan.park_blob_bytes;
+    cfg.live_lists = live_lists;
+    cfg.certs = plan.certs;
+    cfg.mesh_lights = plan.mesh_lights;
+    cfg.fuse = plan.fuse;
+    return cfg;
+}
 
-// A render's profile: the workgroups' counters read back and summed, beside what the pass loop counted and timed on the host.
-pt_status read_profile(pt_scene* sc, const RenderPlan& plan, bool second_set, uint64_t camera_rays, uint64_t accumulated_pixels, const double* stage_ms, const uint64_t* stage_launches,
+// The stage clock of a render: HIP events around every launch, recorded on the launch stream and read back after the final sync, so the
+// per-stage device time is measured inside the timed region without stalling it.
+// (round 5: ONE event between two launches — the end of one is the start of the next on the stream — not two: the markers cost a short frame 5 % of its time,
+// G2 9.7 -> 9.2 ms per step without any; a launch's time now includes the gap in front of it, a few microseconds)
+// (pass overlap: each lane of the pass loop keeps its own chain; a wait for the other stream gets an event of its own behind it, so that the idle time is charged to no stage)
+struct StageClock {
+    struct Chain {
+        hipStream_t stream; std::vector<hipEvent_t>* events;   // the lane's stream and the scene's events for it, grown on demand
+        size_t marks;              // timing events recorded
+        std::vector<int> stage;    // stage[k]: what the interval from event k to event k + 1 is charged to (-1: no stage)
+    };
+    Chain chain[2];
+    bool ok;   // the tuning asks for timing and no event call has failed
+    double ms[ST_COUNT] = {0, 0, 0, 0, 0};
+    uint64_t launches[ST_COUNT] = {0, 0, 0, 0, 0};
+    // an event behind what the lane's stream holds so far: the interval since the lane's previous one is charged to `stage`
+    void mark(uint32_t lane, int stage) {
+        Chain& l = chain[lane];
+        if (!ok) return;
+        while (l.events->size() <= l.marks) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { ok = false; return; } l.events->push_back(e); }
+        if (hipEventRecord((*l.events)[l.marks], l.stream) != hipSuccess) { ok = false; return; }
+        if (l.marks > 0) l.stage.push_back(stage);
+        ++l.marks;
+    }
+    template <typename Fn> void timed(uint32_t lane, int stage, Fn&& fn) {
+        fn();
+        mark(lane, stage);
+        launches[stage]++;
+    }
+    // behind the final synchronise: every charged interval into ms; overlapped: some pass loop of the render ran passes on both lanes
+    void read(bool overlapped) {
+        for (const Chain& l : chain) for (size_t k = 0; k < l.stage.size(); ++k) {
+            float t = 0.0f;
+            if (l.stage[k] >= 0 && hipEventElapsedTime(&t, (*l.events)[k], (*l.events)[k + 1]) == hipSuccess) ms[l.stage[k]] += t;
+        }
+        if (!overlapped || chain[0].marks == 0) return;
+        // (pt_profile::kernel_seconds: overlapped intervals add up to more than the device was busy, so each stage gets its share of the busy window, the first
+        // timing event to the last over both streams)
+        double window = 0.0, total = 0.0;
+        for (const Chain& l : chain) {
+            float t = 0.0f;
+            if (l.marks > 0 && hipEventElapsedTime(&t, (*chain[0].events)[0], (*l.events)[l.marks - 1]) == hipSuccess && t > window) window = t;
+        }
+        for (double t : ms) total += t;
+        if (window > 0.0 && total > window) for (double& t : ms) t *= window / total;
+    }
+};
+
+// A render's profile: the workgroups' counters read back and summed, beside what the pass loop counted and the clock timed on the host.
+pt_status read_profile(pt_scene* sc, const pth::RenderPlan& plan, bool second_set, uint64_t camera_rays, uint64_t accumulated_pixels, const StageClock& clock,
                        uint32_t rounds, double seconds, pt_profile* profile) {
     memset(profile, 0, sizeof(*profile));
     std::vector<unsigned long long> bs((size_t)plan.grid * BS_FIELDS);
@@ -805,10 +743,10 @@ pt_status read_profile(pt_scene* sc, const RenderPlan& plan, bool second_set, ui
     profile->shadow_rays = c[BS_SHADOW_RAYS];
     profile->env_hits = c[BS_ENV_HITS];
     profile->seconds = seconds;
-    for (int i = 0; i < ST_COUNT; ++i) { profile->kernel_seconds[i] = stage_ms[i] * 1e-3; profile->kernel_launches[i] = stage_launches[i]; }
+    for (int i = 0; i < ST_COUNT; ++i) { profile->kernel_seconds[i] = clock.ms[i] * 1e-3; profile->kernel_launches[i] = clock.launches[i]; }
     profile->stage_items[ST_GENERATE] = camera_rays; profile->stage_items[ST_EXTEND] = c[BS_SEGMENTS]; profile->stage_items[ST_SHADE] = c[BS_SEGMENTS];
     profile->stage_items[ST_SHADOW] = c[BS_ITEMS]; profile->stage_items[ST_ACCUMULATE] = accumulated_pixels;
-    profile->stage_items[6] = (uint64_t)plan.cfg.park_block;   // threads per workgroup of the parked kernels when they ran in their big-workgroup form (pt_tuning::park_block), else 0
+    profile->stage_items[6] = (uint64_t)plan.launch_park_block;   // threads per workgroup of the parked kernels when they ran in their big-workgroup form (pt_tuning::park_block), else 0
     profile->stage_items[7] = plan.camera_record;   // 1: k_generate wrote the camera vertex' lean record (7 of 16 words) and the first bounce's vertex kernel rebuilt the rest
     profile->stage_items[5] = c[BS_MEDIUM_DROPS];   // the medium-aware walk tracks four nested mediums: what a fifth level lost (0 = the walk is the reference's)
     profile->kernel_launches[5] = rounds;           // pt_render_adaptive: its rounds (0 for pt_render)
@@ -818,8 +756,40 @@ pt_status read_profile(pt_scene* sc, const RenderPlan& plan, bool second_set, ui
 // The events that order the two streams of overlapped passes (pt_scene::pass_deps): the fork, and per pass parity the accumulate stage done and the skew bounce done
 enum { DEP_FORK = 0, DEP_ACCUMULATED = 1, DEP_SKEW = 3, DEP_COUNT = 5 };
 
-// A render in four steps: the plan (plan_render), the buffers and the upload of the pixel list, the pass loop — pt_render runs it once over its shard's pixels,
-// an adaptive job once per round (adaptive_rounds) — and the profile (read_profile).  `job`: what is optional about the render.
+// Pass overlap: a render whose plan wants it (pth::RenderPlan::overlap: its pass loop plans two passes or more somewhere) gets the second set of pass buffers, sized
+// as ensure_buffers sized the first, the second stream and the events between the two.  Where the device cannot give them, what was taken is given back and the
+// passes run one after the other as before: that is no error of the call.  Returns whether passes overlap.
+bool acquire_second_lane(pt_scene* sc, const pth::RenderPlan& plan, uint32_t light_samples, uint32_t nl, bool need_hits, uint32_t group_planes) {
+    if (!plan.overlap) return false;
+    bool ok = ensure_buffers(sc, sc->buf2, plan.capacity, light_samples, 0, plan.grid, nl, plan.park_block, need_hits, group_planes) == PT_OK;
+    if (ok && !sc->pass_stream) ok = hipStreamCreateWithFlags(&sc->pass_stream, hipStreamNonBlocking) == hipSuccess;
+    while (ok && sc->pass_deps.size() < DEP_COUNT) {
+        hipEvent_t e;
+        ok = hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+        if (ok) sc->pass_deps.push_back(e);
+    }
+    if (!ok) { sc->buf2.release(); (void)hipGetLastError(); }   // (the sticky error cleared)
+    return ok;
+}
+
+// What the kernels of a render read of the desc and the plan; the pass loop fills in what changes per pass (the chunk, the sample range, the set's energy_stride)
+RenderParams render_params(const pt_scene* sc, const pt_render_desc& rd, const pt_adaptive_desc* adaptive, const pth::RenderPlan& plan) {
+    RenderParams rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.seed = rd.seed; rp.width = rd.width; rp.height = rd.height;
+    rp.min_bounces = rd.min_bounces; rp.max_bounces = rd.max_bounces; rp.light_samples = rd.light_samples; rp.only_direct = rd.only_direct;
+    rp.wavelength_lo = rd.wavelength_lo; rp.wavelength_span = rd.wavelength_hi - rd.wavelength_lo;
+    // (an adaptive render's film holds running sums until k_adaptive_finish divides each pixel by its own count; its rounds end on phase boundaries)
+    rp.spp = adaptive ? adaptive->max_samples : rd.spp; rp.range_end = rd.first_sample + rd.sample_count;
+    rp.normalize = (!adaptive && rd.first_sample == 0 && rd.sample_count == rd.spp) ? 1u : 0u;
+    rp.phase = rd.phase_samples;
+    rp.camera = pth::camera_params(sc->host.cameras[rd.camera_index], (float)rd.width / (float)rd.height);
+    rp.live_list = plan.live_list; rp.camera_record = plan.camera_record;
+    return rp;
+}
+
+// A render in four steps: the plan (pth::plan_render), the buffers and the upload of the pixel list, the pass loop — pt_render runs it once over its shard's
+// pixels, an adaptive job once per round (adaptive_rounds) —, timed by the stage clock, and the profile (read_profile).  `job`: what is optional about the render.
 pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hipStream_t stream, pt_profile* profile, const RenderJob& job) {
     if (!sc || !rdp || !d_film) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     pt_render_desc rd;
@@ -831,45 +801,28 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     std::vector<uint32_t> own_list;
     if (!job.shard_list) own_list = pth::shard_pixels(rd.width, rd.height, rd.tile_width, rd.tile_height, rd.shard_index, rd.shard_count);
     const std::vector<uint32_t>& pixels = job.shard_list ? *job.shard_list : own_list;
-    RenderPlan plan;
-    pt_status st = plan_render(sc, rd, job, pixels, stream, &plan);
+    pth::RenderPlan plan;
+    bool live_lists = false;
+    pt_status st = plan_for(sc, rd, job, pixels.size(), &plan, &live_lists);
     if (st != PT_OK) return st;
-    const uint32_t capacity = plan.capacity;
-    const int grid = plan.grid, trav_form = plan.trav_form, shade_form = plan.shade_form;
-    const bool hero = plan.hero, park_dynamic = plan.park_dynamic;
-    LaunchCfg cfg = plan.cfg;
+    const int grid = plan.grid;
+    const bool hero = plan.hero, parked_form = plan.trav_form == PT_FORM_PARKED || plan.trav_form == PT_FORM_PARKED_WALK;
+    LaunchCfg cfg = launch_cfg(sc, plan, live_lists, stream);
 
 #ifdef PT_EXPERIMENTS
     const bool need_hits = true;   // (the measurement forms of k_shadow keep scratch in the idle hit queue, fused plan or not)
 #else
-    const bool need_hits = !cfg.fuse;
+    const bool need_hits = !plan.fuse;
 #endif
     const uint32_t group_count = job.classes ? PP_CLASSES : job.exprs ? job.exprs->outputs : job.groups ? job.groups->group_count : 0u;
     const uint32_t group_planes = group_count + (job.classes || job.exprs ? 1u : 0u);   // (+ the plane of state words)
-    st = ensure_buffers(sc, sc->buf, capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits, group_planes);
+    const uint32_t nl = (hero || rd.medium_aware) ? 4u : 1u;
+    st = ensure_buffers(sc, sc->buf, plan.capacity, rd.light_samples, pixels.size() ? pixels.size() : 1, grid, nl, plan.park_block, need_hits, group_planes);
     if (st != PT_OK) return st;
     DeviceBuffers& b = sc->buf;
-    // Pass overlap: a render whose pass loop plans two passes or more (an adaptive one: in its first round or in a later round over every pixel) gets the second
-    // set of pass buffers, the second stream and the events between the two.  Where the device cannot give them the passes run one after the other as
-    // before: that is no error of the call.
-    bool overlap = !(sc->tuning.flags & PT_TUNE_NO_PASS_OVERLAP);
-    if (overlap) {
-        const uint32_t n_px = (uint32_t)pixels.size();
-        overlap = pth::plan_passes(n_px, rd.first_sample, adaptive ? rd.spp : rd.sample_count, capacity, rd.phase_samples).size() >= 2
-               || (adaptive && adaptive->max_samples > rd.spp && pth::plan_passes(n_px, rd.spp, adaptive->step < adaptive->max_samples - rd.spp ? adaptive->step : adaptive->max_samples - rd.spp, capacity, rd.phase_samples).size() >= 2);
-    }
-    if (overlap) {
-        bool ok = ensure_buffers(sc, sc->buf2, capacity, rd.light_samples, 0, grid, (hero || rd.medium_aware) ? 4u : 1u, plan.park_block, need_hits, group_planes) == PT_OK;
-        if (ok && !sc->pass_stream) ok = hipStreamCreateWithFlags(&sc->pass_stream, hipStreamNonBlocking) == hipSuccess;
-        while (ok && sc->pass_deps.size() < DEP_COUNT) {
-            hipEvent_t e;
-            ok = hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-            if (ok) sc->pass_deps.push_back(e);
-        }
-        if (!ok) { sc->buf2.release(); (void)hipGetLastError(); overlap = false; }   // (what was taken is given back, the sticky error cleared)
-    }
-    if (overlap && (trav_form == PT_FORM_PARKED || trav_form == PT_FORM_PARKED_WALK) && !sc->buf2.park) return fail(PT_ERR_DEVICE, "internal: a parked traversal form without the second set's scratch");
-    if ((trav_form == PT_FORM_PARKED || trav_form == PT_FORM_PARKED_WALK) && !b.park) return fail(PT_ERR_DEVICE, "internal: a parked traversal form without the parked kernels' scratch");
+    const bool overlap = acquire_second_lane(sc, plan, rd.light_samples, nl, need_hits, group_planes);
+    if (overlap && parked_form && !sc->buf2.park) return fail(PT_ERR_DEVICE, "internal: a parked traversal form without the second set's scratch");
+    if (parked_form && !b.park) return fail(PT_ERR_DEVICE, "internal: a parked traversal form without the parked kernels' scratch");
     if (adaptive) {   // (round 0's list: every pixel of the film — or of the shard — in shard_pixels' order; counts and stats are zero outside it)
         const size_t film_pixels = (size_t)rd.width * rd.height;
         st = ensure_adaptive_buffers(sc, film_pixels);
@@ -887,66 +840,33 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     HIP_TRY(hipMemsetAsync(b.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));
     if (overlap) HIP_TRY(hipMemsetAsync(sc->buf2.block_stats, 0, sizeof(unsigned long long) * BS_FIELDS * (size_t)grid, stream));   // (in front of the fork event)
 
-    RenderParams rp;
-    memset(&rp, 0, sizeof(rp));
-    rp.seed = rd.seed; rp.width = rd.width; rp.height = rd.height;
-    rp.min_bounces = rd.min_bounces; rp.max_bounces = rd.max_bounces; rp.light_samples = rd.light_samples; rp.only_direct = rd.only_direct;
-    rp.wavelength_lo = rd.wavelength_lo; rp.wavelength_span = rd.wavelength_hi - rd.wavelength_lo;
-    // (an adaptive render's film holds running sums until k_adaptive_finish divides each pixel by its own count; its rounds end on phase boundaries)
-    rp.spp = adaptive ? adaptive->max_samples : rd.spp; rp.range_end = rd.first_sample + rd.sample_count;
-    rp.normalize = (!adaptive && rd.first_sample == 0 && rd.sample_count == rd.spp) ? 1u : 0u;
-    rp.phase = rd.phase_samples;
-    rp.camera = pth::camera_params(sc->host.cameras[rd.camera_index], (float)rd.width / (float)rd.height);
-    rp.live_list = plan.live_list; rp.camera_record = plan.camera_record;   // (energy_stride: the set's, per pass)
-
+    RenderParams rp = render_params(sc, rd, adaptive, plan);
     const pt_tuning& tn = sc->tuning;
     const SceneArgs sargs{sc->d_blob, sc->blob_words, sc->d_tex, marginal_lds_bytes(sc->host.blob.data(), cfg.lds_bytes)};
     const uint32_t bounce_limit = rd.only_direct ? 1u : rd.max_bounces;
-    const bool timing = !(tn.flags & PT_TUNE_NO_STAGE_TIMING);
-    double stage_ms[ST_COUNT] = {0, 0, 0, 0, 0};
-    uint64_t stage_launches[ST_COUNT] = {0, 0, 0, 0, 0};
-    // A lane of the pass loop: a set of pass buffers, the stream its passes run on and that stream's chain of timing events.  Lane 0 is the first set on the caller's
-    // stream; lane 1 (overlap only) the second set on the scene's own stream.
+    // A lane of the pass loop: a set of pass buffers and the stream its passes run on (the clock's chain of the same index times it).  Lane 0 is the first set on
+    // the caller's stream; lane 1 (overlap only) the second set on the scene's own stream.
     struct Lane {
-        DeviceBuffers* set; hipStream_t stream; std::vector<hipEvent_t>* events;
+        DeviceBuffers* set; hipStream_t stream;
         Queue qa, qb, qh, qs;
         uint32_t* live[2];         // per-segment live-path counts, ping-pong with the path queues
         uint32_t* nshadow;         // per-segment light-sample item counts; behind them (nshadow + grid) the counts of the live ones (Layout::shadow_live_field)
         PassRouter pass_router;    // a path-pass render: the router over the set's state plane
         ExprRouter expr_router;    // a path-expression render: likewise, behind its own number of planes
-        size_t marks;              // timing events recorded
-        std::vector<int> stage;    // stage[k]: what the interval from event k to event k + 1 is charged to (-1: no stage)
     };
-    auto make_lane = [&](DeviceBuffers& s, hipStream_t on, std::vector<hipEvent_t>* ev) {
-        return Lane{&s, on, ev, Queue{s.paths_a, s.capacity, plan.path_fields}, Queue{s.paths_b, s.capacity, plan.path_fields}, Queue{s.hits, s.capacity, HS_FIELDS},
+    auto make_lane = [&](DeviceBuffers& s, hipStream_t on) {
+        return Lane{&s, on, Queue{s.paths_a, s.capacity, plan.path_fields}, Queue{s.paths_b, s.capacity, plan.path_fields}, Queue{s.hits, s.capacity, HS_FIELDS},
                     Queue{s.shadow, s.capacity, plan.item_fields}, {s.counts, s.counts + grid}, s.counts + 2 * grid,
                     PassRouter{job.classes ? pp_state_words(s.energy, s.capacity) : nullptr},
-                    ExprRouter{{job.d_expr_table, job.d_expr_groups, job.exprs ? px_state_words(s.energy, s.capacity, job.exprs->outputs) : nullptr, job.exprs ? job.exprs->start : 0u}}, 0, {}};
+                    ExprRouter{{job.d_expr_table, job.d_expr_groups, job.exprs ? px_state_words(s.energy, s.capacity, job.exprs->outputs) : nullptr, job.exprs ? job.exprs->start : 0u}}};
     };
     const GroupRouter group_router{job.groups ? *job.groups : LightGroupTable{nullptr, 0u, 0u}};
-    Lane lanes[2] = {make_lane(b, stream, &sc->events), make_lane(overlap ? sc->buf2 : b, overlap ? sc->pass_stream : stream, &sc->events2)};
+    Lane lanes[2] = {make_lane(b, stream), make_lane(overlap ? sc->buf2 : b, overlap ? sc->pass_stream : stream)};
 
     HIP_TRY(hipStreamSynchronize(stream));
     const auto t0 = std::chrono::steady_clock::now();
-    // HIP events around every launch, recorded on the launch stream and read back after the final sync, so the
-    // per-stage device time is measured inside the timed region without stalling it.
-    // (round 5: ONE event between two launches — the end of one is the start of the next on the stream — not two: the markers cost a short frame 5 % of its time,
-    // G2 9.7 -> 9.2 ms per step without any; a launch's time now includes the gap in front of it, a few microseconds)
-    // (pass overlap: each lane keeps its own chain; a wait for the other stream gets an event of its own behind it, so that the idle time is charged to no stage)
-    bool events_ok = timing;
-    auto mark = [&](Lane& l, int stage) {   // an event behind what the lane's stream holds so far: the interval since the lane's previous one is charged to `stage`
-        if (!events_ok) return;
-        while (l.events->size() <= l.marks) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { events_ok = false; return; } l.events->push_back(e); }
-        if (hipEventRecord((*l.events)[l.marks], l.stream) != hipSuccess) { events_ok = false; return; }
-        if (l.marks > 0) l.stage.push_back(stage);
-        ++l.marks;
-    };
-    mark(lanes[0], -1);
-    auto timed = [&](Lane& l, int stage, auto&& fn) {
-        fn();
-        mark(l, stage);
-        stage_launches[stage]++;
-    };
+    StageClock clock{{{lanes[0].stream, &sc->events, 0, {}}, {lanes[1].stream, &sc->events2, 0, {}}}, !(tn.flags & PT_TUNE_NO_STAGE_TIMING)};
+    clock.mark(0, -1);
 
     uint64_t camera_rays = 0, accumulated_pixels = 0;
     hipError_t spectral_error = hipSuccess, groups_error = hipSuccess, group_bins_error = hipSuccess;
@@ -957,10 +877,10 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     // The pass loop: samples [first_sample, first_sample + sample_count) of the n pixels of the device list d_list; stats (adaptive rounds): S1 / S2 too
     auto run_passes = [&](const uint32_t* d_list, uint32_t n_list, uint32_t first_sample, uint32_t sample_count, double* d_stats) -> pt_status {
         // (a later adaptive round: the stream's work since the previous accumulate — the round's decision and compaction — is charged to no stage)
-        if (camera_rays != 0) mark(lanes[0], -1);
+        if (camera_rays != 0) clock.mark(0, -1);
         rp.range_end = first_sample + sample_count;
         // the planner's capacity is in items; segments round up, so plan with what surely fits
-        std::vector<pth::Pass> passes = pth::plan_passes(n_list, first_sample, sample_count, capacity, rd.phase_samples);
+        std::vector<pth::Pass> passes = pth::plan_passes(n_list, first_sample, sample_count, plan.capacity, rd.phase_samples);
         // which pass runs on which lane, behind which events (pt_plan.h): without overlap, or with one pass, everything on lane 0 and no event
         const pth::PassSchedule sch = pth::schedule_passes((uint32_t)passes.size(), bounce_limit, skew_bounce, overlap);
         const bool two_lanes = sch.steps.size() >= 2 && sch.steps[1].lane == 1u;
@@ -968,7 +888,8 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
         for (size_t p = 0; p < passes.size(); ++p) {
             const pth::Pass& pass = passes[p];
             const pth::PassStep& step = sch.steps[p];
-            Lane& l = lanes[step.lane];
+            const uint32_t ln = step.lane;
+            const Lane& l = lanes[ln];
             DeviceBuffers& b = *l.set;
             const hipStream_t stream = l.stream;
             const Queue &qa = l.qa, &qb = l.qb, &qh = l.qh, &qs = l.qs;
@@ -985,17 +906,17 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
             const uint32_t* d_px = d_list + pass.pixel_begin;
             if (step.wait_fork) HIP_TRY(hipStreamWaitEvent(stream, dep[DEP_FORK], 0));
             if (step.start_after >= 0) HIP_TRY(hipStreamWaitEvent(stream, dep[DEP_SKEW + (step.start_after & 1)], 0));
-            if (step.wait_fork || step.start_after >= 0) mark(l, -1);
+            if (step.wait_fork || step.start_after >= 0) clock.mark(ln, -1);
             if (group_count) {   // (the groups' planes, on the pass's own stream: behind the accumulate stage of the pass that used this set before, in front of this pass's vertices)
                 HIP_TRY(hipMemsetAsync(b.energy + (size_t)lg_plane(0) * b.capacity, 0, sizeof(float) * (size_t)group_count * b.capacity, stream));
-                mark(l, -1);
+                clock.mark(ln, -1);
             }
-            if (park_dynamic) {
+            if (plan.park_dynamic) {
                 HIP_TRY(hipMemsetAsync(b.unit_counters, 0, sizeof(uint32_t) * kUnitCounters, stream));
                 // (round-5 advisor) an event of its own behind the stream's non-kernel work, charged to no stage: k_generate's time begins here, not at the end of the previous pass
-                mark(l, -1);
+                clock.mark(ln, -1);
             }
-            timed(l, ST_GENERATE, [&] {
+            clock.timed(ln, ST_GENERATE, [&] {
                 if (hero) hipLaunchKernelGGL(k_generate<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, qa, b.energy, n, seg_cap, live[0]);
                 else hipLaunchKernelGGL(k_generate<1>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, qa, b.energy, n, seg_cap, live[0]);
             });
@@ -1003,30 +924,30 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
                 Queue qin = (bounce & 1) ? qb : qa, qout = (bounce & 1) ? qa : qb;
                 uint32_t *cin = live[bounce & 1], *cout = live[(bounce + 1) & 1];
                 // kernel variant = staging mode (PT_LDS_*) x traversal form x wavelengths per path (pt_launch.h)
-                if (park_dynamic) cfg.unit_counter = b.unit_counters + 2 * bounce;
+                if (plan.park_dynamic) cfg.unit_counter = b.unit_counters + 2 * bounce;
                 // (a marked path segment — it left the scene's one certified convex body outward — skips that instance: records the vertex kernel wrote, so from bounce 1 on; never
                 // in the medium-aware walk, whose vertex code makes no marks)
                 cfg.path_marks = (bounce > 0 && !rd.medium_aware && (sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_CONVEX)) ? sc->host.blob[PT_HDR_CONVEX_INST] : 0u;
-                if (!cfg.fuse) timed(l, ST_EXTEND, [&] { launch_extend(cfg, trav_form, sargs, qin, qh, seg_cap, cin, b.park); });
-                if (park_dynamic) cfg.unit_counter = b.unit_counters + 2 * bounce + 1;
+                if (!cfg.fuse) clock.timed(ln, ST_EXTEND, [&] { launch_extend(cfg, plan.trav_form, sargs, qin, qh, seg_cap, cin, b.park); });
+                if (plan.park_dynamic) cfg.unit_counter = b.unit_counters + 2 * bounce + 1;
                 const auto routed = [&](const auto& router) {   // (a routed render's two forms: pt_kern_routed.hip)
-                    timed(l, ST_SHADE, [&] { launch_shade_routed(cfg, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats, router); });
-                    if (rd.light_samples > 0) timed(l, ST_SHADOW, [&] { launch_shadow_routed(cfg, sargs, rd.light_samples, qs, b.energy, b.capacity, seg_cap, nshadow, router); });
+                    clock.timed(ln, ST_SHADE, [&] { launch_shade_routed(cfg, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats, router); });
+                    if (rd.light_samples > 0) clock.timed(ln, ST_SHADOW, [&] { launch_shadow_routed(cfg, sargs, rd.light_samples, qs, b.energy, b.capacity, seg_cap, nshadow, router); });
                 };
                 if (job.classes) routed(l.pass_router);
                 else if (job.exprs) routed(l.expr_router);
                 else if (job.groups) routed(group_router);
                 else {
-                    timed(l, ST_SHADE, [&] { launch_shade(cfg, hero ? 4 : 1, shade_form, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats); });
+                    clock.timed(ln, ST_SHADE, [&] { launch_shade(cfg, hero ? 4 : 1, plan.shade_form, sargs, rp, bounce, d_px, qin, qh, qout, qs, b.energy, seg_cap, cin, cout, nshadow, b.block_stats); });
                     if (rd.light_samples > 0)   // (shade_form FULL = the scene can produce environment rays)
-                        timed(l, ST_SHADOW, [&] { launch_shadow(cfg, trav_form, hero ? 4 : 1, shade_form == PT_SHADE_FULL || shade_form == PT_SHADE_MEDIUM, sargs, rd.light_samples, qs, b.energy, b.capacity, rp.live_list ? (seg_cap | kShadowListed) : seg_cap, nshadow, b.park, qh); });
+                        clock.timed(ln, ST_SHADOW, [&] { launch_shadow(cfg, plan.trav_form, hero ? 4 : 1, plan.shade_form == PT_SHADE_FULL || plan.shade_form == PT_SHADE_MEDIUM, sargs, rd.light_samples, qs, b.energy, b.capacity, rp.live_list ? (seg_cap | kShadowListed) : seg_cap, nshadow, b.park, qh); });
                 }
                 // (the next pass starts behind this bounce: started together the two would run in lock step, tail on tail)
                 if ((int32_t)bounce == step.signal_bounce) HIP_TRY(hipEventRecord(dep[DEP_SKEW + (p & 1)], stream));
             }
             // (the film sums keep the pass order: phases of 10, pixels continued across passes)
-            if (step.accumulate_after >= 0) { HIP_TRY(hipStreamWaitEvent(stream, dep[DEP_ACCUMULATED + (step.accumulate_after & 1)], 0)); mark(l, -1); }
-            timed(l, ST_ACCUMULATE, [&] {
+            if (step.accumulate_after >= 0) { HIP_TRY(hipStreamWaitEvent(stream, dep[DEP_ACCUMULATED + (step.accumulate_after & 1)], 0)); clock.mark(ln, -1); }
+            clock.timed(ln, ST_ACCUMULATE, [&] {
                 if (d_stats && hero) hipLaunchKernelGGL(k_accumulate_stats<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film, d_stats);
                 else if (d_stats) hipLaunchKernelGGL(k_accumulate_stats<1>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film, d_stats);
                 else if (hero) hipLaunchKernelGGL(k_accumulate<4>, dim3(grid), dim3(kBlock), 0, stream, rp, d_px, b.energy, d_film);
@@ -1058,22 +979,8 @@ pt_status render_impl(pt_scene* sc, const pt_render_desc* rdp, float* d_film, hi
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     auto t1 = std::chrono::steady_clock::now();
-    for (const Lane& l : lanes) for (size_t k = 0; k < l.stage.size(); ++k) {
-        float ms = 0.0f;
-        if (l.stage[k] >= 0 && hipEventElapsedTime(&ms, (*l.events)[k], (*l.events)[k + 1]) == hipSuccess) stage_ms[l.stage[k]] += ms;
-    }
-    if (overlapped && lanes[0].marks > 0) {
-        // (pt_profile::kernel_seconds: overlapped intervals add up to more than the device was busy, so each stage gets its share of the busy window, the first
-        // timing event to the last over both streams)
-        double window = 0.0, total = 0.0;
-        for (const Lane& l : lanes) {
-            float ms = 0.0f;
-            if (l.marks > 0 && hipEventElapsedTime(&ms, (*lanes[0].events)[0], (*l.events)[l.marks - 1]) == hipSuccess && ms > window) window = ms;
-        }
-        for (double ms : stage_ms) total += ms;
-        if (window > 0.0 && total > window) for (double& ms : stage_ms) ms *= window / total;
-    }
-    if (profile) return read_profile(sc, plan, overlap, camera_rays, accumulated_pixels, stage_ms, stage_launches, rounds, std::chrono::duration<double>(t1 - t0).count(), profile);
+    clock.read(overlapped);
+    if (profile) return read_profile(sc, plan, overlap, camera_rays, accumulated_pixels, clock, rounds, std::chrono::duration<double>(t1 - t0).count(), profile);
     return PT_OK;
 }
 
@@ -1122,37 +1029,9 @@ static pt_status scene_to_device(pt_scene* sc) {
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, sc->device);
     if (e != hipSuccess) return fail(PT_ERR_NO_DEVICE, hipGetErrorString(e));
     sc->num_cus = prop.multiProcessorCount;
-    const pt_tuning& tn = sc->tuning;
-    if (tn.flags & PT_TUNE_EXACT_SLAB) sc->host.blob[PT_HDR_FLAGS] |= PT_FLAG_EXACT_SLAB;
-    if (tn.flags & PT_TUNE_NO_CULL) sc->host.blob[PT_HDR_FLAGS] |= PT_FLAG_NO_CULL;
-    if (tn.flags & PT_TUNE_NO_SWEEP) sc->host.blob[PT_HDR_FLAGS] |= PT_FLAG_NO_SWEEP;
-    if (tn.flags & PT_TUNE_NO_MESH_SWEEP) sc->host.blob[PT_HDR_FLAGS] |= PT_FLAG_NO_MESH_SWEEP;
-    if (tn.flags & PT_TUNE_NO_KNOWN_LIGHT) sc->host.blob[PT_HDR_FLAGS] |= PT_FLAG_NO_KNOWN_LIGHT;
-    if (tn.flags & PT_TUNE_NO_ONE_LIGHT) sc->host.blob[PT_HDR_FLAGS] |= PT_FLAG_NO_ONE_LIGHT;
-    if (tn.flags & PT_TUNE_NO_MESH_SHORTCUTS) {   // (the mesh records' inner ball and slab table: mesh_surely_blocks / mesh_surely_missed claim nothing without them)
-        std::vector<uint32_t>& bl = sc->host.blob;
-        for (uint32_t i = 0; i < bl[PT_HDR_INSTANCE_COUNT]; ++i) {
-            const uint32_t inst = bl[PT_HDR_INSTANCE_OFF] + i * PT_INST_WORDS;
-            if (bl[inst + PT_INST_KIND] != (uint32_t)PT_SHAPE_MESH) continue;
-            bl[bl[inst + PT_INST_MESH] + PT_MESH_INNER_R] = 0u; bl[bl[inst + PT_INST_MESH] + PT_MESH_DOP_OFF] = 0u;
-        }
-    }
-    if (tn.flags & PT_TUNE_NO_CONVEX) sc->host.blob[PT_HDR_FLAGS] &= ~PT_FLAG_CONVEX;   // (the vertex code looks at an instance's certificate only under this flag, and only it makes marks)
-    if (sc->host.blob[PT_HDR_LIGHT_COUNT] > tuned(tn.light_prepass_max, kLightPrepassMax)) sc->host.blob[PT_HDR_FLAGS] |= PT_FLAG_NO_LIGHT_PREPASS;
+    const pth::ScenePlan plan = pth::plan_scene(sc->tuning, sc->host.blob);   // (the tuning's edits of the blob, in place)
+    sc->lacks = plan.lacks; sc->lds_mode = plan.lds_mode;
     sc->blob_words = (uint32_t)sc->host.blob.size();
-    {   // no instance carries a transform (the Cornell box): the forms without the matrix paths (PT_AMD_GENERAL_FORMS=1 keeps the general ones)
-        bool any_xf = false;
-        const std::vector<uint32_t>& bl = sc->host.blob;
-        for (uint32_t i = 0; i < bl[PT_HDR_INSTANCE_COUNT]; ++i) any_xf = any_xf || (bl[bl[PT_HDR_INSTANCE_OFF] + i * PT_INST_WORDS + PT_INST_FLAGS] & 1u) != 0u;
-        // "no lights" = no hit can carry a Light tag: the light list is empty AND no mesh instance overrides its material with a light
-        // (such a mesh is not in the light list, world/mod.rs:45-54, but its hits emit and take no light samples: PT_FLAG_NO_SHADOW_BOUND)
-        const bool no_light_hits = bl[PT_HDR_LIGHT_COUNT] == 0u && !(bl[PT_HDR_FLAGS] & PT_FLAG_NO_SHADOW_BOUND);
-        sc->lacks = (tn.flags & PT_TUNE_GENERAL_FORMS) ? 0u : ((any_xf ? 0u : PT_SCENE_NO_XF) | (no_light_hits ? PT_SCENE_NO_LIGHTS : 0u));
-    }
-    const bool no_lds = (tn.flags & PT_TUNE_NO_LDS) != 0;
-    const uint32_t all_limit = tuned(tn.lds_all_limit, kLdsAllLimitBytes);   // (experiments: the largest blob staged whole)
-    sc->lds_mode = no_lds ? PT_LDS_NONE : (sc->blob_words * 4 <= (all_limit < kLdsBlobLimitBytes ? all_limit : kLdsBlobLimitBytes) ? PT_LDS_ALL
-                 : (sc->host.blob[PT_HDR_CORE_WORDS] * 4 <= kLdsBlobLimitBytes && !(tn.flags & PT_TUNE_NO_CORE_LDS) ? PT_LDS_CORE : PT_LDS_NONE));
     e = hipMalloc(&sc->d_blob, sizeof(uint32_t) * sc->host.blob.size());
     if (e == hipSuccess) e = hipMalloc(&sc->d_tex, sizeof(float) * (sc->host.tex.size() + 4));
     if (e == hipSuccess) e = hipMemcpy(sc->d_blob, sc->host.blob.data(), sizeof(uint32_t) * sc->host.blob.size(), hipMemcpyHostToDevice);
@@ -2745,6 +2624,7 @@ uint32_t pt_debug_scene_info(pt_scene* sc, int what) {
     switch (what) { case 0: return sc->blob_words * 4; case 1: return (uint32_t)sc->lds_mode; case 2: return sc->host.light_count; case 3: return (uint32_t)sc->num_cus;
                     case 4: return sc->host.blob[PT_HDR_SWEEP_OFF] != 0 && !(sc->host.blob[PT_HDR_FLAGS] & PT_FLAG_NO_SWEEP) ? 1u : 0u;
                     case 7: return sc->host.blob[PT_HDR_CORE_WORDS] * 4;
+                    case 9: return sc->lacks;   // PT_SCENE_* bits (1 above: lds_mode; the two answers of pth::plan_scene)
                     case 8: return (uint32_t)(sc->host.tex.size() > 0xffffffffull ? 0xffffffffull : sc->host.tex.size());   // words of texels + importance-map tables (read through L2, never staged)
                     default: return 0; }
 }

@@ -89,6 +89,161 @@ std::vector<Pass> plan_passes(uint32_t n_pixels, uint32_t first_sample, uint32_t
     return passes;
 }
 
+// the value a tuning field stands for (0 = "the default" in the struct)
+static uint32_t tuned(uint32_t value, uint32_t dflt) { return value ? value : dflt; }
+
+// whether any instance of the flattened scene is a mesh (a scene without one never parks at a mesh: its top-level walks are the ones worth leaving early)
+static bool scene_has_mesh(const std::vector<uint32_t>& blob) {
+    const uint32_t off = blob[PT_HDR_INSTANCE_OFF], n = blob[PT_HDR_INSTANCE_COUNT];
+    for (uint32_t i = 0; i < n; ++i) if (blob[off + i * PT_INST_WORDS + PT_INST_KIND] == (uint32_t)PT_SHAPE_MESH) return true;
+    return false;
+}
+
+ScenePlan plan_scene(const pt_tuning& tn, std::vector<uint32_t>& blob) {
+    using namespace ptk;
+    ScenePlan sp;
+    uint32_t& flags = blob[PT_HDR_FLAGS];
+    const uint32_t switches[][2] = {{PT_TUNE_EXACT_SLAB, PT_FLAG_EXACT_SLAB}, {PT_TUNE_NO_CULL, PT_FLAG_NO_CULL}, {PT_TUNE_NO_SWEEP, PT_FLAG_NO_SWEEP},
+                                    {PT_TUNE_NO_MESH_SWEEP, PT_FLAG_NO_MESH_SWEEP}, {PT_TUNE_NO_KNOWN_LIGHT, PT_FLAG_NO_KNOWN_LIGHT}, {PT_TUNE_NO_ONE_LIGHT, PT_FLAG_NO_ONE_LIGHT}};
+    for (const auto& s : switches) if (tn.flags & s[0]) flags |= s[1];
+    if (tn.flags & PT_TUNE_NO_CONVEX) flags &= ~PT_FLAG_CONVEX;   // (the vertex code looks at an instance's certificate only under this flag, and only it makes marks)
+    if (blob[PT_HDR_LIGHT_COUNT] > tuned(tn.light_prepass_max, kLightPrepassMax)) flags |= PT_FLAG_NO_LIGHT_PREPASS;
+    bool any_xf = false;
+    for (uint32_t i = 0; i < blob[PT_HDR_INSTANCE_COUNT]; ++i) {
+        const uint32_t inst = blob[PT_HDR_INSTANCE_OFF] + i * PT_INST_WORDS;
+        any_xf = any_xf || (blob[inst + PT_INST_FLAGS] & 1u) != 0u;
+        // (the mesh records' inner ball and slab table: mesh_surely_blocks / mesh_surely_missed claim nothing without them)
+        if ((tn.flags & PT_TUNE_NO_MESH_SHORTCUTS) && blob[inst + PT_INST_KIND] == (uint32_t)PT_SHAPE_MESH) { blob[blob[inst + PT_INST_MESH] + PT_MESH_INNER_R] = 0u; blob[blob[inst + PT_INST_MESH] + PT_MESH_DOP_OFF] = 0u; }
+    }
+    // no instance carries a transform (the Cornell box): the forms without the matrix paths (PT_AMD_GENERAL_FORMS=1 keeps the general ones)
+    // "no lights" = no hit can carry a Light tag: the light list is empty AND no mesh instance overrides its material with a light
+    // (such a mesh is not in the light list, world/mod.rs:45-54, but its hits emit and take no light samples: PT_FLAG_NO_SHADOW_BOUND)
+    const bool no_light_hits = blob[PT_HDR_LIGHT_COUNT] == 0u && !(flags & PT_FLAG_NO_SHADOW_BOUND);
+    sp.lacks = (tn.flags & PT_TUNE_GENERAL_FORMS) ? 0u : ((any_xf ? 0u : PT_SCENE_NO_XF) | (no_light_hits ? PT_SCENE_NO_LIGHTS : 0u));
+    const uint32_t all_limit = std::min(tuned(tn.lds_all_limit, kLdsAllLimitBytes), kLdsBlobLimitBytes);   // (experiments: the largest blob staged whole)
+    sp.lds_mode = (tn.flags & PT_TUNE_NO_LDS) ? PT_LDS_NONE : (uint32_t)blob.size() * 4 <= all_limit ? PT_LDS_ALL
+                : (blob[PT_HDR_CORE_WORDS] * 4 <= kLdsBlobLimitBytes && !(tn.flags & PT_TUNE_NO_CORE_LDS)) ? PT_LDS_CORE : PT_LDS_NONE;
+    return sp;
+}
+
+bool plan_render(const std::vector<uint32_t>& blob, const pt_tuning& tn, const ScenePlan& scene, const RenderAsk& ask, RenderPlan* plan, std::string* error) {
+    using namespace ptk;
+    using namespace ptd;
+    const pt_render_desc& rd = ask.rd;
+    const pt_adaptive_desc* adaptive = ask.adaptive;
+    const uint32_t blob_bytes = (uint32_t)blob.size() * 4u, flags = blob[PT_HDR_FLAGS];
+    const int mode = scene.lds_mode;
+    RenderPlan& p = *plan;
+    p = RenderPlan();
+
+    // ---- the queues: capacity, grid, layouts
+    p.capacity = tuned(tn.batch_slots, 1u << 27);  // path slots per pass (128 Mi ~ 32 GB of queues of the 288 GB; tools/sweep.sh)
+    if (p.capacity < 1024) p.capacity = 1024;
+    const uint64_t want = (uint64_t)ask.n_pixels * (adaptive ? std::max(adaptive->step, rd.spp) : rd.sample_count);   // (the longest pass of a round)
+    if (want < p.capacity) p.capacity = (uint32_t)(want ? want : 1);
+    const uint32_t blocks_per_cu = tuned(tn.blocks_per_cu, 64);
+    if (blocks_per_cu > 1024) { *error = "pt_tuning::blocks_per_cu (PT_AMD_BLOCKS_PER_CU) must be in 1..1024"; return false; }
+    p.grid = ask.num_cus * (int)blocks_per_cu;  // queue segments = workgroups per launch
+    // a pass holds at least one whole phase of one pixel (plan_passes): the queues must too (NaiveRenderer settings: phase = spp)
+    p.capacity = std::max(p.capacity, std::min(rd.sample_count, rd.phase_samples));
+    p.hero = rd.hero_wavelengths == 4;
+    if (p.hero && p.capacity > (1u << 26)) p.capacity = 1u << 26;  // 4-wavelength queues are ~1.5x wider: 64 Mi slots ~ 24 GB
+    // (a queue's tiles are laid out by the number of fields this render uses, pt_stages.h: the buffers are sized for the widest layout seen)
+    // (the medium-aware walk keeps its two extra path fields where the hero layout keeps the passengers' throughputs)
+    const uint32_t item_samples = rd.light_samples ? rd.light_samples : 1;
+    p.path_fields = p.hero ? Layout<4>::path_fields : (rd.medium_aware ? (uint32_t)PS_FIELDS + 2u : Layout<1>::path_fields);
+    p.item_fields = p.hero ? Layout<4>::shadow_queue_fields(item_samples) : Layout<1>::shadow_queue_fields(item_samples);
+    p.lds_bytes = mode == PT_LDS_ALL ? blob_bytes : (mode == PT_LDS_CORE ? blob[PT_HDR_CORE_WORDS] * 4u : 0u);
+
+    // ---- the traversal form
+    const bool sweep = blob[PT_HDR_SWEEP_OFF] != 0 && !(flags & PT_FLAG_NO_SWEEP);
+    // the sweep table holds walked meshes: rays that reach one are parked and resumed in full waves (PT_AMD_NO_PARK=1: in line)
+    const bool walks = (flags & PT_FLAG_SWEEP_WALKS) != 0;
+    p.mesh_lights = blob[PT_HDR_LIGHT_FACE_OFF] != 0u;   // (emissive mesh faces: PT_FORM_ANY, below)
+    const bool routed = ask.routed;   // (a light-group, path-pass or path-expression render: PT_FORM_ANY and the FULL vertex form, whose siblings route the energy: pt_kern_routed.hip)
+    // (the parked forms run where ensure_buffers makes the parked kernels' scratch, b.park — a table with walked meshes, or no table: the two cases below)
+    const bool may_park = !(tn.flags & PT_TUNE_NO_PARK) && !p.mesh_lights && !routed;
+    const bool parked = sweep && walks && may_park;
+    // no sweep table (more than 64 instances, PT_AMD_NO_SWEEP): the top-level tree per lane, every mesh parked (top_walk_run, pt_device.h)
+    const bool parked_walk = !sweep && may_park;
+    // PT_AMD_POOL=1: phase 3 of a pure sweep scene pooled per wave (sweep_run_pooled).  Bit-identical, but measured slower than the lane
+    // loop on MI355X (C2: k_extend 3155 vs 2475 us, k_shadow 5421 vs 4677 us; DESIGN.md section 5 has the breakdown), so it is not the default.
+    // (the pooled kernels are not in the product: make EXTRA=-DPT_EXPERIMENTS builds them, PT_AMD_POOL=1 selects them there)
+    const bool pooled = ask.pool_lds_bytes != 0u && sweep && !walks && mode == PT_LDS_ALL && p.lds_bytes + ask.pool_lds_bytes <= kLdsBlobLimitBytes && (tn.flags & PT_TUNE_EXPERIMENT_POOL) != 0;
+    // (walked meshes in line under PT_AMD_NO_PARK, and every partly staged or unstaged blob: the run-time choice of PT_FORM_ANY.  A scene with emissive mesh faces
+    // takes it too: the specialised traversal forms are compiled without the faces' code — PT_SCENE_NO_MESH_LIGHTS, pt_kern_*.hip — and keep their registers)
+    p.trav_form = parked ? PT_FORM_PARKED : parked_walk ? PT_FORM_PARKED_WALK : (mode != PT_LDS_ALL || (sweep && walks) || p.mesh_lights || routed) ? PT_FORM_ANY
+                : pooled ? PT_FORM_POOLED : sweep ? PT_FORM_SWEEP : PT_FORM_WALK;
+
+    // ---- the parked kernels' variants
+    // the parked kernels in workgroups of 512 / 1024 threads that stage the whole blob (pt_tuning::park_block): static form, one wavelength, a blob that fits
+    // 0 = the measured default: the light-sample kernel in workgroups of 512 (C3: -5 %), the closest-hit kernel in its own 256 (at 512 it loses its fifth wave
+    // per SIMD: +14 %); 512 / 1024 = both kernels; 256 = neither (profiles/r4_experiments.md section 1)
+    const bool park_big_ok = !p.hero && blob_bytes <= kParkBlobLimitBytes && mode == PT_LDS_CORE && !(tn.flags & PT_TUNE_NO_LDS);
+    // (round 6: in a scene with a certified convex body — PT_FLAG_CONVEX, the gem of C3 — nine in ten of the light rays that used to walk the mesh no longer reach it, and the
+    // light-sample kernel is better off in workgroups of 256 that stage the core alone, twice the workgroups per CU: C3 k_shadow_parked 2339 -> 2083 us, profiles/r6d_ab_park.txt)
+    const bool few_walks = (flags & PT_FLAG_CONVEX) != 0u;
+    p.park_block = !park_big_ok ? (uint32_t)kBlock : tn.park_block == 0u ? (few_walks ? (uint32_t)kBlock : 512u) : tn.park_block;
+    p.park_block_extend = !park_big_ok || tn.park_block == 0u ? (uint32_t)kBlock : tn.park_block;
+    // The parked kernels take units of work from a counter, a few persistent workgroups per CU, when the whole blob is staged in LDS
+    // (C3: k_extend 9175 -> 7880 us, k_shadow 8008 -> 7105, 487 -> 543 Msamples/s: park lists that live across units keep the drains
+    // full).  With the mesh in HBM/L2 (C4) the static form wins, 1128 vs 1083 Msamples/s: a wave's parked rays then come from one
+    // region of the film and walk the same part of the mesh.  PT_AMD_PARK_DYNAMIC=0 / 1 forces either.
+    p.park_dynamic = parked && (tn.park_dynamic < 0 ? mode == PT_LDS_ALL : tn.park_dynamic != 0);
+    p.park_big = parked && !p.park_dynamic && p.park_block != (uint32_t)kBlock && mode != PT_LDS_ALL;
+    p.dyn_grid = std::min(ask.num_cus * (int)tuned(tn.park_blocks_per_cu, 4), p.grid);
+    if (p.park_big) { p.launch_park_block = (int)p.park_block; p.launch_park_block_extend = (int)p.park_block_extend; p.park_blob_bytes = blob_bytes; }
+
+    // ---- the walk-policy word
+    // The top-level walk is left early by a wave's last lanes (top_walk_run) where that walk is long and nothing else thins the wave out: a tree of more than 64
+    // instances — the scenes that have no sweep table by themselves — without a mesh (test_bokeh.toml + a floor: k_shadow_parked 2900 -> 2320 us at 32, 2430 at 16 and
+    // at 48).  With a mesh in the scene the lanes of a wave PARK at it, the wave thins out although its rays are not done, and evicting the rest only adds park
+    // traffic: the same scene with the gem standing on the floor 1337 -> 1260 Msamples/s at 32 (1341 at 16); a small scene forced off its table (PT_AMD_NO_SWEEP:
+    // thirteen instances in the gem scene, ten nodes per walk) lost 15 % (profiles/r5_experiments.md section 2).
+    const uint32_t top_evict = tuned(tn.top_evict_below, blob[PT_HDR_INSTANCE_COUNT] > PT_SWEEP_MAX_BITS && !scene_has_mesh(blob) ? kTopEvictBelow : 1u);
+    // The grouped mesh sweep's group loop is left by a wave's last lanes (mesh_walk, GROUPS) where every parked ray of the closest-hit kernel stands in the SAME mesh — one
+    // walked mesh in the table: a resumed wave is then always one the grouped sweep takes, and a ray that comes back with groups to do is never walked from the top.
+    uint32_t group_evict = 1u;
+    if (parked) {
+        uint32_t walked = 0;
+        for (uint32_t j = 0; j < blob[PT_HDR_SWEEP_COUNT]; ++j) walked += (blob[blob[PT_HDR_SWEEP_OFF] + j * PT_SWEEP_INST_WORDS + 1] & PT_SWEEP_WALKED) ? 1u : 0u;
+        if (walked == 1u) group_evict = tuned(tn.group_evict_below, kGroupEvictBelow);
+    }
+    p.walk_policy = tuned(tn.walk_evict_below, kWalkEvictBelow) | tuned(tn.walk_search_below, kWalkSearchBelow) << 8
+                  | ((tn.flags & PT_TUNE_NO_AXIS_SCAN) ? 0u : PT_WALK_SCAN_AXIS)
+                  | (top_evict <= 1u ? 0u : top_evict << 24)   // (1 = never: 0 in the policy word)
+                  | (group_evict <= 1u ? 0u : group_evict << 17);
+
+    // ---- the vertex form, and what hangs on the pair of forms
+    // light samples can pick the environment only if env_sampling_probability > 0: otherwise k_shade is the form without that branch
+    float env_prob; std::memcpy(&env_prob, &blob[PT_HDR_ENV_PROB], sizeof env_prob);
+    bool has_ggx = false;   // (a PassthroughFilter lives in the forms that hold the GGX code)
+    for (uint32_t i = 0; i < blob[PT_HDR_MATERIAL_COUNT]; ++i) {
+        const uint32_t kind = blob[blob[PT_HDR_MATERIAL_OFF] + i * PT_MAT_WORDS + PT_MAT_KIND];
+        has_ggx = has_ggx || kind == PT_MATERIAL_GGX || kind == PT_MATERIAL_PASSTHROUGH;
+    }
+    // (a scene with a convex-body certificate takes at least the NO_ENV form: the lean and fused forms are compiled without the certificate code, pt_kern_shade.hip)
+    p.certs = !rd.medium_aware && (flags & PT_FLAG_CONVEX) != 0u;
+    p.shade_form = rd.medium_aware ? PT_SHADE_MEDIUM
+                 : (env_prob != 0.0f || tn.shade_form == 2 || routed) ? PT_SHADE_FULL : (has_ggx || p.certs || tn.shade_form == 1) ? PT_SHADE_NO_ENV : PT_SHADE_LEAN;
+    const bool lean = p.shade_form == PT_SHADE_LEAN;
+    // (the plain light-sample kernel walks the list of live items; the parked forms list their live RAYS themselves, the measurement forms read every item)
+    p.live_list = ((p.trav_form == PT_FORM_SWEEP || p.trav_form == PT_FORM_WALK || p.trav_form == PT_FORM_ANY) && lean && !(tn.flags & PT_TUNE_NO_LIVE_LIST)) ? 1u : 0u;
+    p.camera_record = p.shade_form != PT_SHADE_NO_ENV ? 1u : 0u;   // (LEAN, FULL, MEDIUM: the forms whose bounce-0 launch rebuilds the camera vertex: k_shade, pt_kernels.h)
+    // k_shade that traces its own segments: exists for the pure sweep form of a fully staged, transform-free scene shaded by the lean form.
+    // Measured (profiles/r3_experiments.md): C2 +4..5 % (4370 us against 2095 + 2490..2640 per bounce); with four wavelengths per path it
+    // lost in round 3 (C5 996 against 1093 Msamples/s: the traversal then ran at the three waves per SIMD the wide vertex code left) and wins since round 4 (PT_FUSE_HERO).
+    p.fuse = !(tn.flags & PT_TUNE_NO_FUSE) && (!p.hero || PT_FUSE_HERO) && p.trav_form == PT_FORM_SWEEP && lean && (scene.lacks & PT_SCENE_NO_XF) != 0;
+
+    // ---- pass overlap: a render whose pass loop plans two passes or more (an adaptive one: in its first round or in a later round over every pixel) wants the second
+    // set of pass buffers, the second stream and the events between the two
+    const auto passes = [&](uint32_t first, uint32_t count) { return plan_passes((uint32_t)ask.n_pixels, first, count, p.capacity, rd.phase_samples).size(); };
+    p.overlap = !(tn.flags & PT_TUNE_NO_PASS_OVERLAP)
+             && (passes(rd.first_sample, adaptive ? rd.spp : rd.sample_count) >= 2
+                 || (adaptive && adaptive->max_samples > rd.spp && passes(rd.spp, std::min(adaptive->step, adaptive->max_samples - rd.spp)) >= 2));
+    return true;
+}
+
 ptd::CameraParams camera_params(const pt_camera& c, float aspect_ratio) {
     using namespace ptd;
     CameraParams cam;

@@ -1,5 +1,5 @@
 // pt_plan.h — host-side planning shared by the HIP engine: film tiles -> pixel list of a shard,
-// sample passes aligned to the reference's 10-sample phases, thin-lens camera frame.
+// sample passes aligned to the reference's 10-sample phases, the choice of kernel forms for a scene and a render, thin-lens camera frame.
 #ifndef PT_PLAN_H
 #define PT_PLAN_H
 #include <stdint.h>
@@ -14,6 +14,7 @@
 #include "../../include/pt_light_groups_denoise.h"
 #include "../../include/pt_resident.h"
 #include "../../include/pt_spectral.h"
+#include "pt_forms.h"
 #include "pt_stages.h"
 
 namespace pth {
@@ -44,6 +45,47 @@ struct PassSchedule { std::vector<PassStep> steps; int32_t join_pass = -1; };
 // overlap false, or fewer than two passes: every pass on lane 0, no event at all.
 PassSchedule schedule_passes(uint32_t n_passes, uint32_t bounces, int32_t skew_bounce, bool overlap);
 constexpr int32_t kPassSkewBounce = 0;   // the default g: measured best on C2 (profiles/pass_overlap.md)
+
+// ---- Which kernel forms a scene and a render take (pt_forms.h): pure functions of plain inputs, for the engine and — exported by the host emulation, pinned by
+// tests/golden/render_plans.tsv — for a machine without a device.
+// What a scene decides once, when it is created: the tuning's edits of the blob (the PT_TUNE_* flags that are PT_FLAG_* bits, NO_MESH_SHORTCUTS, NO_CONVEX, the
+// light-prepass limit) are applied to `blob` in place; lacks: the PT_SCENE_* bits of what the scene does not hold; lds_mode: PT_LDS_*, what the kernels stage.
+struct ScenePlan { uint32_t lacks = 0; int lds_mode = 0; };
+__attribute__((visibility("hidden"))) ScenePlan plan_scene(const pt_tuning& tn, std::vector<uint32_t>& blob);   // (hidden, as plan_render is: libptamd.so's exported names stay what they were)
+
+// What a render asks of the plan beside the scene: the device's CUs, the normalised desc, the pixels of its list, the adaptive desc of an adaptive render,
+// whether it is routed (light groups, path passes, path expressions: pt_kern_routed.hip), and the static LDS of the pooled traversal kernels (0: a product
+// build, which has none; a measurement build passes ptk::pool_lds_bytes()).
+struct RenderAsk {
+    int num_cus = 0;
+    pt_render_desc rd{};
+    size_t n_pixels = 0;
+    const pt_adaptive_desc* adaptive = nullptr;
+    bool routed = false;
+    uint32_t pool_lds_bytes = 0;
+};
+// What plan_render chooses for a render: the queues' size, the kernel forms and their launch configuration.
+struct RenderPlan {
+    uint32_t capacity = 0;   // path slots per pass
+    int grid = 0;            // queue segments = workgroups per launch
+    bool hero = false;       // four wavelengths per path
+    uint32_t park_block = 0, park_block_extend = 0;   // the parked kernels' workgroups, big form or not (the scratch is sized by the first)
+    int trav_form = 0, shade_form = 0;   // PT_FORM_*, PT_SHADE_*
+    bool park_dynamic = false, park_big = false;
+    uint32_t live_list = 0, camera_record = 0;   // RenderParams' fields of these names
+    uint32_t path_fields = 0, item_fields = 0;
+    // ptk::LaunchCfg's fields of these names (launch_*: its park_block and park_block_extend, 0 unless park_big)
+    uint32_t lds_bytes = 0;
+    int dyn_grid = 0;
+    uint32_t walk_policy = 0;
+    int launch_park_block = 0, launch_park_block_extend = 0;
+    uint32_t park_blob_bytes = 0;
+    bool certs = false, mesh_lights = false, fuse = false;
+    bool overlap = false;    // the pass loop plans two passes or more somewhere, and the tuning lets them overlap: the render wants the second set of pass buffers
+};
+// The choices of a render, from the scene's blob (as plan_scene left it), its tuning and plan_scene's answer: false with the reason in *error for a
+// pt_tuning::blocks_per_cu out of range.
+__attribute__((visibility("hidden"))) bool plan_render(const std::vector<uint32_t>& blob, const pt_tuning& tn, const ScenePlan& scene, const RenderAsk& ask, RenderPlan* plan, std::string* error);
 
 // ProjectiveCamera::new + with_aspect_ratio (src/camera/projective_camera.rs:27-95, 121-133)
 ptd::CameraParams camera_params(const pt_camera& c, float aspect_ratio);

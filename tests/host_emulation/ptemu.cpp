@@ -29,16 +29,39 @@ pt_status ptemu_scene_create(const pt_scene_desc* d, pt_scene** out) {
     // the engine's diagnostic switches (pt_engine.hip: PT_AMD_EXACT_SLAB / NO_CULL / NO_SWEEP), as one flag word
     const char* f = getenv("PTEMU_FLAGS");
     if (f) sc->host.blob[PT_HDR_FLAGS] |= (uint32_t)strtoul(f, nullptr, 0);
-    if (getenv("PTEMU_NO_CONVEX")) sc->host.blob[PT_HDR_FLAGS] &= ~PT_FLAG_CONVEX;   // (pt_engine.hip: PT_TUNE_NO_CONVEX)
-    if (getenv("PTEMU_NO_MESH_SHORTCUTS")) {   // (the mesh records' inner ball and slab table: mesh_surely_blocks / mesh_surely_missed claim nothing without them)
-        std::vector<uint32_t>& bl = sc->host.blob;
-        for (uint32_t i = 0; i < bl[PT_HDR_INSTANCE_COUNT]; ++i) {
-            const uint32_t inst = bl[PT_HDR_INSTANCE_OFF] + i * PT_INST_WORDS;
-            if (bl[inst + PT_INST_KIND] != (uint32_t)PT_SHAPE_MESH) continue;
-            bl[bl[inst + PT_INST_MESH] + PT_MESH_INNER_R] = 0u; bl[bl[inst + PT_INST_MESH] + PT_MESH_DOP_OFF] = 0u;
-        }
-    }   // (pt_engine.hip: PT_TUNE_NO_MESH_SHORTCUTS)
+    // the two edits the engine makes under PT_TUNE_NO_CONVEX and PT_TUNE_NO_MESH_SHORTCUTS, by the engine's own function (and no light-prepass limit: the
+    // emulation bounds a light-sample ray whatever the number of lights)
+    pt_tuning tn; std::memset(&tn, 0, sizeof(tn));
+    tn.light_prepass_max = 0xffffffffu;
+    if (getenv("PTEMU_NO_CONVEX")) tn.flags |= PT_TUNE_NO_CONVEX;
+    if (getenv("PTEMU_NO_MESH_SHORTCUTS")) tn.flags |= PT_TUNE_NO_MESH_SHORTCUTS;
+    pth::plan_scene(tn, sc->host.blob);
     *out = sc;
+    return PT_OK;
+}
+// The engine's choice of kernel forms (pt_plan.h plan_scene, plan_render) for this scene under a tuning, on a copy of the blob: the scene stays as it was
+// created.  (Not rows of api.ENTRIES: loaded with plain ctypes; tests/render_plan_cases.py names the words.)
+// out[0..2]: the blob's flag word as the tuning leaves it, lacks, lds_mode
+void ptemu_plan_scene(pt_scene* sc, const pt_tuning* tn, uint32_t* out) {
+    std::vector<uint32_t> blob = sc->host.blob;
+    const pth::ScenePlan sp = pth::plan_scene(*tn, blob);
+    out[0] = blob[PT_HDR_FLAGS]; out[1] = sp.lacks; out[2] = (uint32_t)sp.lds_mode;
+}
+// out[0..24]: every field of pth::RenderPlan in the order of its declaration, then lacks and lds_mode; rdp is normalised here and the pixel list is the desc's
+// shard; adaptive may be null; PT_ERR_INVALID_ARGUMENT for a desc or a tuning that is refused
+pt_status ptemu_plan_render(pt_scene* sc, const pt_tuning* tn, int num_cus, const pt_render_desc* rdp, const pt_adaptive_desc* adaptive, int routed, uint32_t* out) {
+    std::vector<uint32_t> blob = sc->host.blob;
+    const pth::ScenePlan sp = pth::plan_scene(*tn, blob);
+    pth::RenderAsk ask;
+    ask.num_cus = num_cus; ask.adaptive = adaptive; ask.routed = routed != 0;
+    if (!pth::normalize_render_desc(*rdp, (uint32_t)sc->host.cameras.size(), &ask.rd, &g_error)) return PT_ERR_INVALID_ARGUMENT;
+    ask.n_pixels = pth::shard_pixels(ask.rd.width, ask.rd.height, ask.rd.tile_width, ask.rd.tile_height, ask.rd.shard_index, ask.rd.shard_count).size();
+    pth::RenderPlan p;
+    if (!pth::plan_render(blob, *tn, sp, ask, &p, &g_error)) return PT_ERR_INVALID_ARGUMENT;
+    const uint32_t words[25] = {p.capacity, (uint32_t)p.grid, p.hero, p.park_block, p.park_block_extend, (uint32_t)p.trav_form, (uint32_t)p.shade_form, p.park_dynamic, p.park_big,
+                                p.live_list, p.camera_record, p.path_fields, p.item_fields, p.lds_bytes, (uint32_t)p.dyn_grid, p.walk_policy, (uint32_t)p.launch_park_block,
+                                (uint32_t)p.launch_park_block_extend, p.park_blob_bytes, p.certs, p.mesh_lights, p.fuse, p.overlap, sp.lacks, (uint32_t)sp.lds_mode};
+    std::memcpy(out, words, sizeof(words));
     return PT_OK;
 }
 void ptemu_scene_destroy(pt_scene* sc) { delete sc; }

@@ -1,17 +1,19 @@
-// scene_host_sanitize.cpp — a stand-alone host program for a sanitizer run of the scene build (csrc/pt_scene_host.cpp): it builds four descriptions in heap
+// scene_host_sanitize.cpp — a stand-alone host program for a sanitizer run of the scene build (csrc/pt_scene_host.cpp): it builds a handful of descriptions in heap
 // arrays of exactly the sizes they name — analytic shapes under transforms, a cube mesh of two instances whose triangles the sweep table inlines, a closed
 // sphere mesh of 160 faces with vertex normals that is walked (leaf list, group boxes, inner balls, slabs, convex certificate), and an HDR environment with a
-// baked importance map — so that a read past a description's array or a write past a blob's record is a heap overflow the sanitizer sees.  From the
-// repository root:
+// baked importance map, and a scene with no instance at all (the smallest blob) — so that a read past a description's array or a write past a blob's record
+// is a heap overflow the sanitizer sees.  Over every scene built it then runs the engine's choice of kernel forms (csrc/pt_plan.cpp: plan_scene, plan_render) under
+// four tunings, the PT_TUNE_NO_MESH_SHORTCUTS edit of the mesh records among them, each on a copy of the blob of its exact length.  From the repository root:
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -Wno-unknown-pragmas -Wno-unused-function
 //       -o /tmp/scene_host_sanitize tools/scene_host_sanitize.cpp rust-pathtracer_amd/csrc/pt_scene_host.cpp rust-pathtracer_amd/csrc/pt_plan.cpp && /tmp/scene_host_sanitize
-// It prints one line per description and "ok" at the end; a refused description or a blob whose header does not name its own size ends it with status 1.
+// It prints one line per description, one per tuning, and "ok" at the end; a refused description or a blob whose header does not name its own size ends it with status 1.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "../rust-pathtracer_amd/csrc/pt_plan.h"
 #include "../rust-pathtracer_amd/csrc/pt_scene_host.h"
 
 namespace {
@@ -111,6 +113,33 @@ struct Desc {   // a description's arrays, each a heap block of its exact length
         if (hs.blob[PT_HDR_MAGIC] != PT_BLOB_MAGIC || hs.blob[PT_HDR_TOTAL_WORDS] != hs.blob.size() || hs.blob[PT_HDR_CORE_WORDS] > hs.blob.size()) { printf("FAILED: %s: the header does not name the blob's size\n", name); return 1; }
         printf("%s: %zu blob words (%u core), %zu texel words, %u lights, sweep table %s\n", name, hs.blob.size(), hs.blob[PT_HDR_CORE_WORDS], hs.tex.size(), hs.light_count,
                hs.blob[PT_HDR_SWEEP_OFF] ? ((hs.blob[PT_HDR_FLAGS] & PT_FLAG_SWEEP_WALKS) ? "with a walked mesh" : "yes") : "no");
+        return plans(name, hs);
+    }
+
+    // The engine's choice of kernel forms (csrc/pt_plan.cpp: plan_scene, plan_render) over the scene just built: per tuning a copy of the blob in a heap block of
+    // its exact length, which plan_scene edits in place (NO_MESH_SHORTCUTS writes into the mesh records) and plan_render only reads, for five kinds of render.
+    static int plans(const char* name, const pth::HostScene& hs) {
+        const uint32_t tunings[] = {0u, PT_TUNE_NO_MESH_SHORTCUTS | PT_TUNE_NO_CONVEX, PT_TUNE_NO_SWEEP | PT_TUNE_NO_PARK, PT_TUNE_NO_LDS | PT_TUNE_GENERAL_FORMS};
+        for (uint32_t flags : tunings) {
+            pt_tuning tn; std::memset(&tn, 0, sizeof(tn));
+            tn.flags = flags; tn.park_dynamic = -1;
+            std::vector<uint32_t> blob(hs.blob);
+            const pth::ScenePlan sp = pth::plan_scene(tn, blob);
+            pt_render_desc in; std::memset(&in, 0, sizeof(in));
+            in.width = 64; in.height = 48; in.spp = 10; in.min_bounces = 1; in.max_bounces = 6; in.light_samples = 2; in.wavelength_lo = 380.0f; in.wavelength_hi = 750.0f;
+            const pt_adaptive_desc adaptive{40u, 20u, 0.05f, 0.0f};
+            for (int kind = 0; kind < 5; ++kind) {   // plain, four wavelengths, medium-aware, adaptive, routed
+                pth::RenderAsk ask;
+                pt_render_desc rd = in;
+                rd.hero_wavelengths = kind == 1 ? 4u : 1u; rd.medium_aware = kind == 2;
+                std::string err;
+                if (!pth::normalize_render_desc(rd, (uint32_t)hs.cameras.size(), &ask.rd, &err)) { printf("FAILED: %s: %s\n", name, err.c_str()); return 1; }
+                ask.num_cus = 256; ask.n_pixels = (size_t)rd.width * rd.height; ask.adaptive = kind == 3 ? &adaptive : nullptr; ask.routed = kind == 4;
+                pth::RenderPlan p;
+                if (!pth::plan_render(blob, tn, sp, ask, &p, &err)) { printf("FAILED: %s: %s\n", name, err.c_str()); return 1; }
+                if (kind == 0) printf("  tuning 0x%x: flags 0x%x, lacks %u, lds mode %d; traversal form %d, vertex form %d, %u slots\n", flags, blob[PT_HDR_FLAGS], sp.lacks, sp.lds_mode, p.trav_form, p.shade_form, p.capacity);
+            }
+        }
         return 0;
     }
 };
@@ -180,10 +209,15 @@ int hdr_environment() {
     return s.build("hdr environment with an importance map");
 }
 
+int no_instance() {   // the smallest blob: an environment and a camera
+    Desc s;
+    return s.build("no instance at all");
+}
+
 }  // namespace
 
 int main() {
-    if (analytic_shapes() || inlined_mesh() || walked_mesh(false) || walked_mesh(true) || hdr_environment()) return 1;
+    if (no_instance() || analytic_shapes() || inlined_mesh() || walked_mesh(false) || walked_mesh(true) || hdr_environment()) return 1;
     printf("ok\n");
     return 0;
 }
